@@ -23,6 +23,10 @@ run AFTER the timed region on rank 0 of a one-GPU ensemble run: `sustained` -- 1
 of the same (10-year, quiet) digest; `sustained_heavy` -- 16 384 members through the whole 1-YEAR forcing, ten times the
 evapo-transpiration per row, the regime with failed BDF attempts; `cpu_baseline` -- the C oracle (oracle/, a port of the
 same algorithm) on every host core this process may use, for >= 30 s.
+
+--dump-outputs DIR writes what the last timed step computed (member states, water-table statistics of its rows) as
+DIR/<name>.npy in float64, read after the timed region (`dump_outputs`).  The inputs depend on the arguments alone
+(synthetic forcing, --seed), so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -104,7 +108,14 @@ def parse():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for rehearsals)")
     ap.add_argument("--probe-ranks", action="store_true",
                     help="only start the ranks, all-reduce a one and print what the process group saw (no GPU work)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float64): "
+                         "the states of a fixed, seeded sample of members and the water-table statistics of its rows")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
     if args.steps is None:
         args.steps = 30 if args.workload == "ensemble" else 2
     if args.members is None:
@@ -288,6 +299,33 @@ def roofline_object(bytes_per_launch, launch_ms, per_launch_ms, launches, pmc, p
             "algorithmic_bytes_per_launch": bytes_per_launch, "note": note}
 
 
+DUMP_MEMBERS = 4096             # --dump-outputs: states of at most this many members (<= 21 MB at the deepest D = 640)
+DUMP_SEED = 12345               # ... drawn by this fixed seed when the rank holds more
+
+
+def dump_outputs(out_dir, stepper, row_begin, moments, dz, z0):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy in float64 --
+      psi          [S][D]        states after the step of S members (all of them up to DUMP_MEMBERS, else a fixed, seeded
+                                 sample, in ascending member order; rank 0's members when several ranks run)
+      noise_scale  [S]           those members' damping of their Philox base vector
+      wtd_moments  [(P,) 3][48]  count / sum idx / sum idx^2 of the water-table index on each row of the step
+      wtd_mean_cm, wtd_std_cm  [(P,) 48]   the same rows as mean and sigma in cm
+    `moments` is the whole [(P,) 3][T] table (every rank's members); the step covered rows [row_begin, row_begin + 48)."""
+    from hydromodel_amd.stepper import moments_to_mean_std
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    n = stepper.N
+    ids = (np.arange(n) if n <= DUMP_MEMBERS else
+           np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MEMBERS, replace=False)))
+    psi = np.concatenate([stepper.get_state(int(k), 1) for k in ids])
+    scale = np.concatenate([stepper.noise_scale(int(k), 1) for k in ids])
+    m = np.asarray(moments)[..., row_begin:row_begin + ROWS_PER_DAY]
+    mean_cm, std_cm = moments_to_mean_std(m, dz, z0)
+    arrays = {"psi": psi, "noise_scale": scale, "wtd_moments": m, "wtd_mean_cm": mean_cm, "wtd_std_cm": std_cm}
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float64))
+
+
 def probe_ranks(args, rank, world):
     """--probe-ranks: what did the launcher start?  Every rank joins the process group and adds a one."""
     import torch
@@ -395,6 +433,8 @@ def run_sweep(args, rank, world, dev, dist):
                                                              for j, k in enumerate(mine)}, forcing.dim_t, D)
     assemble_s = time.perf_counter() - t_asm
     counts_last = whole[:, 0, last]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sim.stepper, sim.next_row - ROWS_PER_DAY, whole, cols_list[0].dz, cols_list[0].z[0])
     out = {
         "metric": "ensemble column-days/sec", "value": col_days / elapsed, "unit": "column-days/s",
         "n_gpus": world, "ranks": world, "backend": (dist.get_backend() if world > 1 else None),
@@ -511,6 +551,8 @@ def run_ensemble(args, rank, world, dev, dist):
     mean_cm, std_cm = sim.wtd_mean_std(moments)
     last_row = sim.next_row - 1
     members_seen = int(moments[0][last_row])                   # count row of the reduced table: every rank's members
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sim.stepper, sim.next_row - ROWS_PER_DAY, moments, cols.dz, cols.z[0])
 
     col_days = float(N) * world * args.steps
     value = col_days / elapsed

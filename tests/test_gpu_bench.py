@@ -122,6 +122,27 @@ def test_bench_under_a_launcher_still_works():
     assert two["n_gpus"] == 2 and two["ranks"] == 2 and two["members_in_reduced_moments"] == 2048
 
 
+def test_bench_dumps_the_last_step_and_repeats_it_to_the_bit(tmp_path):
+    """--dump-outputs: two runs with the same arguments write the same arrays (the inputs depend on the arguments alone);
+    --steps sets the timed steps, and the dump holds the rows of the last of them."""
+    import numpy as np
+    common = ["--members", "5000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-sustained", "--no-heavy",
+              "--no-n1e6"]
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        lines.append(_run([sys.executable, "bench.py", "--dump-outputs", str(tmp_path / run)] + common))
+        dumps.append({p.stem: np.load(p) for p in (tmp_path / run).glob("*.npy")})
+    a, b = dumps
+    assert sorted(a) == ["noise_scale", "psi", "wtd_mean_cm", "wtd_moments", "wtd_std_cm"] and a.keys() == b.keys()
+    for k in a:
+        assert a[k].dtype == np.float64 and np.array_equal(a[k], b[k], equal_nan=True), k
+    assert sum(p.stat().st_size for p in (tmp_path / "a").glob("*.npy")) <= 64 << 20
+    assert a["psi"].shape == (4096, 300) and np.isfinite(a["psi"]).all()
+    assert a["wtd_moments"].shape == (3, 48) and (a["wtd_moments"][0] == 5000).all()
+    assert lines[0]["steps"] == 3 and lines[0]["roofline"]["launches"] == 3 and lines[0]["ms_per_step"] > 0
+    assert lines[0]["moments_sha1"] == lines[1]["moments_sha1"]
+
+
 def test_bench_refuses_more_rccl_ranks_than_gpus():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--members", "1024", "--steps", "1"], cwd=REPO, env=env,
