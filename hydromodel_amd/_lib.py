@@ -79,6 +79,14 @@ EXPORTS = {
     "hc_set_noise_scale": ([C.c_void_p, _dp, C.c_int64, C.c_int64], C.c_int),
     "hc_set_point_member_bases": ([C.c_void_p, _lp], C.c_int),
     "hc_get_point_costs": ([C.c_void_p, C.POINTER(C.c_uint64)], C.c_int),
+    "hc_set_profile_stats": ([C.c_void_p, C.c_int32], C.c_int),
+    "hc_get_profile_stats_words": ([C.c_void_p, _lp], C.c_int),
+    "hc_profile_snapshot": ([C.c_void_p, C.c_int64], C.c_int),
+    "hc_get_profile_stats": ([C.c_void_p, _lp, C.c_int64], C.c_int),
+    "hc_set_profile_stats_tables": ([C.c_void_p, _lp, C.c_int64], C.c_int),
+    "hc_export_profile_stats": ([C.c_void_p, C.c_void_p, C.c_int64], C.c_int),
+    "hc_reset_profile_stats": ([C.c_void_p], C.c_int),
+    "hc_get_profile_overflow": ([C.c_void_p, C.POINTER(C.c_uint64)], C.c_int),
     "hc_rhs": ([C.c_void_p, C.c_int64, C.c_int32, _dp, _dp], C.c_int),
     "hc_model_nodes": ([C.c_void_p, _dp, _dp], C.c_int),
     "hc_plugin_eval": ([C.c_int, C.POINTER(ColumnParams), C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp],

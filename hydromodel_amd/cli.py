@@ -21,6 +21,11 @@ unknown keys, only membership of the 12 is checked):
   moment table over RCCL; for a sweep also the per-point initial conditions) and rank 0 writes
   ``<Output_Name>_ensemble.h5`` once -- the reference's single ``sim.run(); sim.saveResults()``
   (``berkeley_hydro_main.py:128-137``), bit-identical at any N.
+* ``"Ensemble": {..., "Profiles": 48}``: ensemble profile statistics reduced on the GPU -- every 48th forcing row (1 = every
+  row, as the reference stores them) the mean / sigma over the members of ``theta_vol``, ``psi_press`` and ``S_eff``
+  ``[T_out][D]``, and for every solved row those of ``transpiration`` / ``lateral_flow`` and ``abs_error_mean`` ``[T]``
+  (simulation.py:658-671; ``<key>_mean`` / ``<key>_std``, with ``profile_rows`` and ``profile_count``), added to
+  ``<Output_Name>_ensemble.h5`` (a sweep: a leading ``[P]`` axis).  The integer tables are all-reduced with the moments.
 * ``"Ensemble": {"repair_predict": true}`` with ``Simulation_Flags.PREDICT``: run the repaired predictive lateral flow
    instead of raising the reference's ``TypeError``.
 """
@@ -143,9 +148,10 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     lo, hi = multigpu.shard(n_members, ranks.rank, ranks.world)
     if hi <= lo:
         raise ValueError(f" Ensemble: {n_members} members do not shard over {ranks.world} GPUs (a rank would be empty).")
+    stride = _profile_stride(ens)
     sim = EnsembleSimulation(cols, forcing, hi - lo, seed=int(ens.get("Seed", 0)), device=device, member_offset=lo,
                              noise=str(ens.get("Noise", "philox")).lower(),
-                             spinup=str(ens.get("Spinup", "shared")).lower())
+                             spinup=str(ens.get("Spinup", "shared")).lower(), profile_stride=stride)
     done = 0
     while done < rows:
         n = min(48 * 30, rows - done)
@@ -175,10 +181,33 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
             psi0 = ranks.allreduce_sum(table)
         else:
             extra["initial_cond_members"] = np.array([lo, hi])
+    if stride:
+        # the profile tables are int64 sums like the moments: one more exact all-reduce
+        extra.update(_profile_datasets(sim.profile_stats(ranks.allreduce_sum(sim.profile_table()))))
     arrays = dict(moments=moments, wtd_mean_cm=mean_cm, wtd_std_cm=std_cm, rows=np.array(rows),
                   members=np.array(n_members), gpus=np.array(ranks.world), initial_cond=psi0, **extra)
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "ensemble water-table statistics", ranks)
     sim.close()
+
+
+def _profile_stride(ens):
+    """Ensemble.Profiles: stride of the profile rows (absent / 0: no profile statistics)."""
+    stride = int(ens.get("Profiles", 0) or 0)
+    if stride < 0:
+        raise ValueError(f" Ensemble: Profiles = {stride} must be a positive row stride.")
+    return stride
+
+
+def _profile_datasets(stats):
+    """The datasets of the profile statistics: the reference's output keys with _mean / _std (simulation.py:658-671)."""
+    import numpy as np
+    keys = ("theta_vol_mean", "theta_vol_std", "psi_press_mean", "psi_press_std", "S_eff_mean", "S_eff_std",
+            "transpiration_mean", "transpiration_std", "lateral_flow_mean", "lateral_flow_std", "abs_error_mean")
+    out = {k: np.asarray(stats[k]) for k in keys}
+    out["profile_rows"] = np.asarray(stats["rows"])
+    out["profile_count"] = np.asarray(stats["count"])
+    out["profile_overflow"] = np.array(stats["overflow"], dtype=np.int64)
+    return out
 
 
 def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks):
@@ -202,8 +231,11 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     points = [ColumnTables(merged[k], well) for k in mine]
     D, T = None, forcing.dim_t
     local = {}
+    stride = _profile_stride(ens)
+    prof_local = None
     if mine:
-        sim = SweepSimulation(points, forcing, n_members, seed=int(ens.get("Seed", 0)), device=device, point_ids=mine)
+        sim = SweepSimulation(points, forcing, n_members, seed=int(ens.get("Seed", 0)), device=device, point_ids=mine,
+                              profile_stride=stride)
         done = 0
         while done < rows:
             n = min(48 * 30, rows - done)
@@ -216,6 +248,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
             local[k] = {"moments": table[j], "psi0": sim.psi0[j],
                         "spinup_iterations": None if sim.spinup_iters is None else int(sim.spinup_iters[j])}
         D = points[0].dim_d
+        if stride:
+            prof_local = sim.profile_table()
         sim.close()
     if D is None:        # a rank without points still joins the collectives: the grid is the well's, whoever owns it
         D = ColumnTables(merged[0], well).dim_d
@@ -225,6 +259,22 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     arrays = dict(moments=moments, wtd_mean_cm=mean_cm, wtd_std_cm=std_cm, rows=np.array(rows),
                   members=np.array(n_members), points=np.array(P), gpus=np.array(ranks.world), initial_cond=psi0,
                   spinup_iterations=spin)
+    if stride:
+        # every rank places its points' parts in zeroed [P] tables; the sum over the ranks is the whole sweep's table
+        from .stepper import join_profile_table, profile_layout, profile_tables_to_stats, split_profile_table
+        parts = {k: np.zeros(sh, dtype=np.int64) for k, (_, sh) in profile_layout(P, T, D, stride).items() if k != "words"}
+        if prof_local is not None:
+            mine_parts = split_profile_table(prof_local, len(mine), T, D, stride)
+            for j, k in enumerate(mine):
+                for name in ("prof", "pcnt", "flux", "fcnt", "aerr"):
+                    parts[name][k] = mine_parts[name][j]
+            parts["ovf"][:] = mine_parts["ovf"]
+        table = ranks.allreduce_sum(join_profile_table(parts))
+        por = np.stack([(points[mine.index(k)] if k in mine else ColumnTables(merged[k], well)).por_node for k in range(P)])
+        stats = profile_tables_to_stats(table, P, T, D, stride, por, ref.dz)
+        if P == 1:       # keep the [P] axis of a sweep's datasets
+            stats = {k: (v[None] if isinstance(v, np.ndarray) and k != "rows" else v) for k, v in stats.items()}
+        arrays.update(_profile_datasets(stats))
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "sweep's water-table statistics", ranks)
 
 

@@ -133,6 +133,12 @@ struct hc_handle {
     uint64_t seed = 0;
     int64_t member_offset = 0;
     int rows_per_launch = 0;     // 0: chosen from the member count (auto_rows_per_launch)
+    // ensemble profile statistics (hc_set_profile_stats): one int64 table, layout in include/hydrocol.h; its shape is
+    // re-derived (and the table re-created, zeroed) when points, rows or depth change, like the moment table
+    int prof_stride = 0;         // 0: off
+    int prof_points = 0, prof_d = 0;
+    int64_t prof_t = 0;          // forcing rows the table was made for
+    DevBuf<long long> prof;
     int n_cu = 256;
     double jac_reject = NUM_JAC_DIFF_REJECT;
 };
@@ -172,6 +178,143 @@ __global__ void moments_kernel(const unsigned short *wtd, const int *wtd_obs, lo
         moments[n_forcing + row] += sh1[0];
         moments[2 * n_forcing + row] += sh2[0];
     }
+}
+
+// ---- ensemble profile statistics (hc_set_profile_stats, include/hydrocol.h): integer sums only
+// q = rint(x * 2^s), clamped to |q| <= HC_PROF_Q_MAX (and counted); a member adds q to word 0 and the four 20-bit limbs of
+// q^2 (< 2^80) to words 1..4.  Every update is an integer add, so the tables do not depend on launch length, member
+// slicing, point order or the number of handles / ranks that are summed.
+__device__ __forceinline__ long long prof_quantise(double x, double scale, unsigned &ovf)
+{
+    double y = rint(x * scale);              // x * 2^s is exact: the rounding is rint's alone
+    const double qmax = (double)HC_PROF_Q_MAX;
+    if (!(fabs(y) <= qmax)) {                // out of range, infinite or NaN
+        ovf++;
+        y = (y != y) ? 0.0 : copysign(qmax, y);
+    }
+    return (long long)y;
+}
+__device__ __forceinline__ void prof_add(long long (&acc)[HC_PROF_WORDS], long long q)
+{
+    const unsigned long long a = (unsigned long long)(q < 0 ? -q : q), M = (1ull << 20) - 1;
+    const unsigned long long lo = a * a, hi = __umul64hi(a, a);
+    acc[0] += q;
+    acc[1] += (long long)(lo & M);
+    acc[2] += (long long)((lo >> 20) & M);
+    acc[3] += (long long)((lo >> 40) & M);
+    acc[4] += (long long)(((lo >> 60) | (hi << 4)) & M);
+}
+constexpr int PROF_TILE = 64;       // nodes per block: one wave-wide, coalesced row segment of a member's state
+constexpr int PROF_WAVES = 4;
+
+// psi and theta of one profile row: grid x = 64-node tiles, y = member slices of one point, z = point.  Wave w of a block
+// reads members w, w + 4, ... of its slice, lane = node, so every load is 64 contiguous doubles of one member's row.  theta
+// is the cell model's own (model_cell, as model_nodes_kernel calls it; theta has no noise term).  The four waves' partial
+// sums meet in LDS; wave 0 adds them to the table with int64 atomics (order-independent).  A skipped row (wtd_obs < 0)
+// counts nobody unless the row is a snapshot (hc_profile_snapshot: the state before any solve).
+__global__ __launch_bounds__(PROF_TILE * PROF_WAVES) void profile_kernel(
+    const StepArgs A, const double *node_tabs, int special, const double *stage, const int *wtd_obs, long long row,
+    long long prow, long long n_prow, int snapshot, long long members_per_block, long long *prof, long long *pcnt,
+    unsigned long long *ovf_word)
+{
+    if (!snapshot && wtd_obs[row] < 0) return;
+    const int D = A.D;
+    const int lane = threadIdx.x % PROF_TILE, wave = threadIdx.x / PROF_TILE;
+    const int i = blockIdx.x * PROF_TILE + lane;
+    const long long point = blockIdx.z;
+    const long long end = (point + 1) * A.members_per_point;
+    const long long m0 = point * A.members_per_point + (long long)blockIdx.y * members_per_block;
+    const long long m1 = m0 + members_per_block < end ? m0 + members_per_block : end;
+    long long acc[2][HC_PROF_WORDS] = {};
+    unsigned ovf = 0;
+    if (i < D) {
+        const ColumnDev P = A.P[point];
+        const double *nt = node_tabs + (size_t)point * 3 * D;
+        const double por = nt[i], meank = nt[D + i], noisec = nt[2 * D + i];
+        const double mk = meank == 0.0 ? 1.0e-7 : meank;
+        const double rdelta = 1.0 / (por - P.theta_res), logm = log(mk), invm2 = 1.0 / (mk * mk);
+        const double s_psi = ldexp(1.0, HC_PROF_SCALE_PSI), s_theta = ldexp(1.0, HC_PROF_SCALE_THETA);
+        for (long long m = m0 + wave; m < m1; m += PROF_WAVES) {
+            const double psi = stage[(size_t)m * D + i];
+            double th, K, C, kb, pf;
+            if (special)
+                model_cell<true>(P, psi, por, rdelta, logm, invm2, noisec, 0.0, th, K, C, kb, pf);
+            else
+                model_cell<false>(P, psi, por, rdelta, logm, invm2, noisec, 0.0, th, K, C, kb, pf);
+            prof_add(acc[0], prof_quantise(psi, s_psi, ovf));
+            prof_add(acc[1], prof_quantise(th, s_theta, ovf));
+        }
+    }
+    __shared__ long long part[PROF_WAVES][2 * HC_PROF_WORDS][PROF_TILE];
+#pragma unroll
+    for (int q = 0; q < 2; q++)
+#pragma unroll
+        for (int k = 0; k < HC_PROF_WORDS; k++) part[wave][q * HC_PROF_WORDS + k][lane] = acc[q][k];
+    __syncthreads();
+    if (wave == 0 && i < D) {
+        long long *t = prof + (((size_t)point * n_prow + prow) * D + i) * 2 * HC_PROF_WORDS;
+#pragma unroll
+        for (int w = 0; w < 2 * HC_PROF_WORDS; w++) {
+            long long sum = 0;
+#pragma unroll
+            for (int v = 0; v < PROF_WAVES; v++) sum += part[v][w][lane];
+            atomicAdd(reinterpret_cast<unsigned long long *>(t + w), (unsigned long long)sum);
+        }
+    }
+    if (ovf) atomicAdd(ovf_word, (unsigned long long)ovf);
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        atomicAdd(reinterpret_cast<unsigned long long *>(pcnt + (size_t)point * n_prow + prow), (unsigned long long)(m1 - m0));
+}
+
+// transpiration / lateral flow of every solved row of a launch, the member count and sum |obs - wtd| (abs_error in grid
+// steps): one block per (launch row, point) as moments_kernel, partial sums through cross-lane shuffles then LDS, one writer
+__global__ __launch_bounds__(256) void flux_stats_kernel(const double *diag, const unsigned short *wtd, const int *wtd_obs,
+                                                         long long n_members, long long members_per_point, long long row_begin,
+                                                         long long n_forcing, long long *flux, long long *fcnt, long long *aerr,
+                                                         unsigned long long *ovf_word)
+{
+    const long long row = row_begin + blockIdx.x;
+    const int obs = wtd_obs[row];
+    if (obs < 0) return;
+    const long long first = (long long)blockIdx.y * members_per_point;
+    const double s_flux = ldexp(1.0, HC_PROF_SCALE_FLUX);
+    long long acc[2][HC_PROF_WORDS] = {};
+    long long ae = 0;
+    unsigned ovf = 0;
+    for (long long k = first + threadIdx.x; k < first + members_per_point; k += blockDim.x) {
+        const size_t e = (size_t)blockIdx.x * n_members + k;
+        prof_add(acc[0], prof_quantise(diag[2 * e + 0], s_flux, ovf));
+        prof_add(acc[1], prof_quantise(diag[2 * e + 1], s_flux, ovf));
+        const int d = obs - (int)wtd[e];
+        ae += d < 0 ? -d : d;
+    }
+    constexpr int NW = 2 * HC_PROF_WORDS + 1;
+    long long v[NW];
+#pragma unroll
+    for (int q = 0; q < 2; q++)
+#pragma unroll
+        for (int k = 0; k < HC_PROF_WORDS; k++) v[q * HC_PROF_WORDS + k] = acc[q][k];
+    v[NW - 1] = ae;
+#pragma unroll
+    for (int w = 0; w < NW; w++)
+        for (int o = WAVE / 2; o > 0; o >>= 1) v[w] += __shfl_xor(v[w], o);
+    __shared__ long long part[256 / WAVE][NW];
+    const int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
+    if (lane == 0)
+#pragma unroll
+        for (int w = 0; w < NW; w++) part[wave][w] = v[w];
+    if (ovf) atomicAdd(ovf_word, (unsigned long long)ovf);
+    __syncthreads();
+    if (threadIdx.x < NW) {
+        long long sum = 0;
+        for (int u = 0; u < (int)(blockDim.x / WAVE); u++) sum += part[u][threadIdx.x];
+        const size_t pr = (size_t)blockIdx.y * n_forcing + row;
+        if (threadIdx.x < NW - 1)
+            flux[pr * 2 * HC_PROF_WORDS + threadIdx.x] += sum;
+        else
+            aerr[pr] += sum;
+    }
+    if (threadIdx.x == 0) fcnt[(size_t)blockIdx.y * n_forcing + row] += members_per_point;
 }
 
 __global__ void widen_u16(const unsigned short *in, int *out, size_t n)
@@ -612,6 +755,7 @@ int hc_destroy(hc_handle *h)
     h->Pdev.release(); h->iodev.release();
     h->point_base.release(); h->point_order.release(); h->point_cost.release();
     h->daylight.release(); h->refresh.release(); h->wtd_u16.release(); h->moments.release(); h->counters.release();
+    h->prof.release();
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -947,6 +1091,70 @@ static int auto_rows_per_launch(int64_t n_members, bool in_kernel_noise)
     return (int)(48 * days);
 }
 
+}  // extern "C"
+
+namespace {
+// Word offsets of the profile-statistics table (include/hydrocol.h, hc_set_profile_stats)
+struct ProfLayout {
+    int64_t n_prow = 0, prof = 0, pcnt = 0, flux = 0, fcnt = 0, aerr = 0, ovf = 0, words = 0;
+};
+ProfLayout prof_layout(const hc_handle *h)
+{
+    ProfLayout L;
+    const int64_t P = h->n_points, T = h->n_rows, D = h->p.dim_d;
+    L.n_prow = (T - 1) / h->prof_stride + 1;
+    L.pcnt = L.prof + P * L.n_prow * D * 2 * HC_PROF_WORDS;
+    L.flux = L.pcnt + P * L.n_prow;
+    L.fcnt = L.flux + P * T * 2 * HC_PROF_WORDS;
+    L.aerr = L.fcnt + P * T;
+    L.ovf = L.aerr + P * T;
+    L.words = L.ovf + 1;
+    return L;
+}
+// the table exists, zeroed, for the current points / rows / depth (re-created when one of them changed)
+int ensure_prof(hc_handle *h)
+{
+    if (h->prof_stride <= 0) return fail(HC_ERR_ARG, "profile statistics are off (hc_set_profile_stats)");
+    if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
+    if (h->prof_points != h->n_points || h->prof_t != h->n_rows || h->prof_d != h->p.dim_d) {
+        const ProfLayout L = prof_layout(h);
+        if (h->prof.ensure((size_t)L.words)) return HC_ERR_DEVICE;
+        HIP_TRY(hipMemset(h->prof.p, 0, (size_t)L.words * 8));
+        h->prof_points = h->n_points;
+        h->prof_t = h->n_rows;
+        h->prof_d = h->p.dim_d;
+    }
+    return HC_OK;
+}
+int prof_words_check(hc_handle *h, int64_t n_words, const char *who)
+{
+    if (int rc = ensure_prof(h)) return rc;
+    const int64_t want = prof_layout(h).words;
+    if (n_words != want) return fail(HC_ERR_ARG, "%s: the table has %lld words, not %lld", who, (long long)want, (long long)n_words);
+    return HC_OK;
+}
+// staging of a launch with profile statistics: transpiration / lateral flow of every row (at most 1 GiB) and, for short
+// strides, the end-of-row states of every row; about 4 GiB at most, a launch stages at least one row whatever the size
+constexpr int64_t PROF_STAGE_BYTES = int64_t(4) << 30, PROF_DIAG_BYTES = int64_t(1) << 30;
+constexpr long long PROF_MEMBERS_PER_BLOCK = 1024;
+
+int launch_profile(hc_handle *h, const StepArgs &A, const ProfLayout &L, const double *stage, int64_t row, int snapshot)
+{
+    const long long mpp = h->n_members / h->n_points;
+    const dim3 grid((unsigned)((h->p.dim_d + PROF_TILE - 1) / PROF_TILE),
+                    (unsigned)((mpp + PROF_MEMBERS_PER_BLOCK - 1) / PROF_MEMBERS_PER_BLOCK), (unsigned)h->n_points);
+    long long *t = h->prof.p;
+    hipLaunchKernelGGL(profile_kernel, grid, dim3(PROF_TILE * PROF_WAVES), 0, h->stream, A, h->node_tabs.p,
+                       (int)h->use_special(), stage, h->wtd_obs.p, (long long)row, (long long)(row / h->prof_stride),
+                       (long long)L.n_prow, snapshot, PROF_MEMBERS_PER_BLOCK, t + L.prof, t + L.pcnt,
+                       reinterpret_cast<unsigned long long *>(t + L.ovf));
+    HIP_TRY(hipGetLastError());
+    return HC_OK;
+}
+}  // namespace
+
+extern "C" {
+
 int hc_step_rows(hc_handle *h, hc_step_args *a)
 {
     if (!h || !a) return fail(HC_ERR_ARG, "hc_step_rows: NULL argument");
@@ -976,11 +1184,39 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
     if (a->diag_out) out_bytes_per_row += N * 2 * 8;
     if (a->wtd_out) out_bytes_per_row += N * 4;
     const int64_t rows_cap = out_bytes_per_row > 0 ? std::max<int64_t>(1, (int64_t(1) << 30) / out_bytes_per_row) : INT32_MAX;
+    // profile statistics (hc_set_profile_stats): spin-up solves accumulate nothing
+    const bool prof_on = h->prof_stride > 0 && !a->spinup;
+    ProfLayout PL;
+    if (prof_on) {
+        if (int rc2 = ensure_prof(h)) return rc2;
+        PL = prof_layout(h);
+    }
     for (int64_t done = 0; done < a->n_rows;) {
         int per_launch = h->rows_per_launch > 0 ? h->rows_per_launch : auto_rows_per_launch(N, h->philox);
         if (h->rows_per_launch <= 0) per_launch = (int)std::min<int64_t>(per_launch, rows_cap);
-        const int chunk = (int)std::min<int64_t>(per_launch, a->n_rows - done);
+        int chunk = (int)std::min<int64_t>(per_launch, a->n_rows - done);
         const int64_t row0 = a->spinup ? a->row_begin : a->row_begin + done;
+        // Profile rows of this launch (the step kernels are not changed for them; results do not depend on launch length):
+        //  stride >= the rows the staging cap admits: the launch ends ON the next profile row, whose states are then the
+        //    members' current states (no staging at all);
+        //  shorter strides: every row of the launch is staged through psi_rows (as psi_rows_out does), the launch
+        //    shortened to the cap, and the profile rows are read from there.
+        bool stage_all = false, end_on_profile = false;
+        if (prof_on) {
+            const int64_t s = h->prof_stride, diag_row = N * 2 * 8, row_bytes = N * (int64_t)D * 8;
+            chunk = (int)std::min<int64_t>(chunk, std::max<int64_t>(1, PROF_DIAG_BYTES / diag_row));
+            const int64_t cap_rows = std::max<int64_t>(1, (PROF_STAGE_BYTES - (int64_t)chunk * diag_row) / row_bytes);
+            if (a->psi_rows_out) {
+                stage_all = true;       // every row is staged for the caller already
+            } else if (s >= cap_rows) {
+                const int64_t next = (row0 + s - 1) / s * s;
+                chunk = (int)std::min<int64_t>(chunk, next - row0 + 1);
+                end_on_profile = (row0 + chunk - 1) % s == 0;
+            } else {
+                chunk = (int)std::min<int64_t>(chunk, cap_rows);
+                stage_all = true;
+            }
+        }
         int n_fresh = 0;
         if (!a->spinup)
             for (int r = 0; r < chunk; r++) n_fresh += h->h_refresh[(size_t)(row0 + r)] ? 1 : 0;
@@ -994,15 +1230,16 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
         if (h->wtd_u16.ensure((size_t)chunk * N)) return HC_ERR_DEVICE;
         if (a->stats_out && h->stats.ensure((size_t)chunk * N * 6)) return HC_ERR_DEVICE;
         if (a->psi_rows_out && h->psi_rows.ensure((size_t)chunk * N * D)) return HC_ERR_DEVICE;
-        if (a->diag_out && h->diag.ensure((size_t)chunk * N * 2)) return HC_ERR_DEVICE;
+        if ((a->diag_out || prof_on) && h->diag.ensure((size_t)chunk * N * 2)) return HC_ERR_DEVICE;
+        if (stage_all && h->psi_rows.ensure((size_t)chunk * N * D)) return HC_ERR_DEVICE;
         h->io_host.fresh = h->fresh.p;
         h->io_host.row_begin = row0;
         A.n_rows = chunk;
         A.spinup = a->spinup;
         h->io_host.wtd_u16 = h->wtd_u16.p;
         h->io_host.stats = a->stats_out ? h->stats.p : nullptr;
-        h->io_host.psi_rows = a->psi_rows_out ? h->psi_rows.p : nullptr;
-        h->io_host.diag = a->diag_out ? h->diag.p : nullptr;
+        h->io_host.psi_rows = (a->psi_rows_out || stage_all) ? h->psi_rows.p : nullptr;
+        h->io_host.diag = (a->diag_out || prof_on) ? h->diag.p : nullptr;
         rc = push_io(h);
         if (rc) return rc;
         if (h->n_points > 1) {
@@ -1018,6 +1255,20 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
             hipLaunchKernelGGL(moments_kernel, dim3(chunk, h->n_points), dim3(256), 0, h->stream, h->wtd_u16.p,
                                h->wtd_obs.p, (long long)N, (long long)(N / h->n_points), (long long)row0,
                                (long long)h->n_rows, h->moments.p);
+            HIP_TRY(hipGetLastError());
+        }
+        if (prof_on) {
+            for (int r = 0; r < chunk; r++) {
+                if ((row0 + r) % h->prof_stride != 0) continue;
+                const double *stage = stage_all ? h->psi_rows.p + (size_t)r * N * D : h->psi.p;
+                if (!stage_all && !(end_on_profile && r == chunk - 1)) return fail(HC_ERR_DEVICE, "profile row %lld not staged (internal error)", (long long)(row0 + r));
+                if (int rc2 = launch_profile(h, A, PL, stage, row0 + r, 0)) return rc2;
+            }
+            long long *t = h->prof.p;
+            hipLaunchKernelGGL(flux_stats_kernel, dim3(chunk, h->n_points), dim3(256), 0, h->stream, h->diag.p, h->wtd_u16.p,
+                               h->wtd_obs.p, (long long)N, (long long)(N / h->n_points), (long long)row0,
+                               (long long)h->n_rows, t + PL.flux, t + PL.fcnt, t + PL.aerr,
+                               reinterpret_cast<unsigned long long *>(t + PL.ovf));
             HIP_TRY(hipGetLastError());
         }
         if (a->wtd_out) {
@@ -1207,6 +1458,95 @@ int hc_reset_moments(hc_handle *h)
     HIP_TRY(hipSetDevice(h->device));
     h->moments_points = 0;
     return ensure_moments(h);
+}
+
+int hc_set_profile_stats(hc_handle *h, int32_t stride)
+{
+    if (!h || stride < 0) return fail(HC_ERR_ARG, "hc_set_profile_stats: bad argument");
+    if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->prof_stride = stride;
+    h->prof_points = 0;          // re-created, zeroed
+    if (stride == 0) {
+        h->prof.release();
+        return HC_OK;
+    }
+    return ensure_prof(h);
+}
+
+int hc_get_profile_stats_words(hc_handle *h, int64_t *n_words)
+{
+    if (!h || !n_words) return fail(HC_ERR_ARG, "hc_get_profile_stats_words: bad argument");
+    if (int rc = ensure_prof(h)) return rc;
+    *n_words = prof_layout(h).words;
+    return HC_OK;
+}
+
+int hc_profile_snapshot(hc_handle *h, int64_t row)
+{
+    if (!h) return fail(HC_ERR_ARG, "hc_profile_snapshot: NULL handle");
+    StepArgs A;
+    int rc = fill_args(h, A);
+    if (rc) return rc;
+    if (int rc2 = ensure_prof(h)) return rc2;
+    if (row < 0 || row >= h->n_rows || row % h->prof_stride != 0)
+        return fail(HC_ERR_ARG, "hc_profile_snapshot: row %lld is not a profile row (stride %d, %lld rows)", (long long)row,
+                    h->prof_stride, (long long)h->n_rows);
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc2 = launch_profile(h, A, prof_layout(h), h->psi.p, row, 1)) return rc2;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return HC_OK;
+}
+
+int hc_get_profile_stats(hc_handle *h, int64_t *table, int64_t n_words)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_get_profile_stats: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = prof_words_check(h, n_words, "hc_get_profile_stats")) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(table, h->prof.p, (size_t)n_words * 8, hipMemcpyDeviceToHost));
+    return HC_OK;
+}
+
+int hc_set_profile_stats_tables(hc_handle *h, const int64_t *table, int64_t n_words)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_set_profile_stats_tables: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = prof_words_check(h, n_words, "hc_set_profile_stats_tables")) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(h->prof.p, table, (size_t)n_words * 8, hipMemcpyHostToDevice));
+    return HC_OK;
+}
+
+int hc_export_profile_stats(hc_handle *h, void *device_dst, int64_t n_words)
+{
+    if (!h || !device_dst) return fail(HC_ERR_ARG, "hc_export_profile_stats: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = prof_words_check(h, n_words, "hc_export_profile_stats")) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(device_dst, h->prof.p, (size_t)n_words * 8, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipDeviceSynchronize());
+    return HC_OK;
+}
+
+int hc_reset_profile_stats(hc_handle *h)
+{
+    if (!h) return fail(HC_ERR_ARG, "hc_reset_profile_stats: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->prof_points = 0;
+    return ensure_prof(h);
+}
+
+int hc_get_profile_overflow(hc_handle *h, uint64_t *count)
+{
+    if (!h || !count) return fail(HC_ERR_ARG, "hc_get_profile_overflow: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = ensure_prof(h)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(count, h->prof.p + prof_layout(h).ovf, 8, hipMemcpyDeviceToHost));
+    return HC_OK;
 }
 
 // The path's one collective without torch: a single process that drives several devices (one handle each) sums the

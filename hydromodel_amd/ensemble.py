@@ -97,10 +97,19 @@ class EnsembleSimulation:
     #1 base vector, then one vector per refresh row (simulation.py:426,561,601) -- and uploaded per launch.
     spinup="shared" (default): one spin-up (global member 0's first draw) broadcast to all members;
     spinup="member": every member spins up with its own first draw (`spinup_members_on_gpu`).
+    profile_stride > 0: ensemble profile statistics (psi, theta every ``profile_stride``-th row from row 0 = the initial
+    states, fluxes and abs_error every solved row) accumulated on the device: :meth:`profile_stats`.
     """
 
     def __init__(self, cols, forcing, n_members, seed=0, device=0, member_offset=0, psi0=None, flags=None,
-                 noise="philox", spinup="shared"):
+                 noise="philox", spinup="shared", profile_stride=0):
+        self._start(cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup)
+        self.profile_stride = int(profile_stride)
+        if self.profile_stride:
+            self.stepper.set_profile_stats(self.profile_stride)
+            self.stepper.profile_snapshot(0)       # psi[0], theta_vol[0]: the state before any solve
+
+    def _start(self, cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup):
         if noise not in ("philox", "numpy") or spinup not in ("shared", "member"):
             raise ValueError(f" {self.__class__.__name__}: unknown noise / spinup mode ({noise}, {spinup}).")
         self.cols, self.forcing = cols, forcing
@@ -178,6 +187,14 @@ class EnsembleSimulation:
         m = self.moments() if moments is None else moments
         return moments_to_mean_std(m, self.cols.dz, self.cols.z[0])
 
+    def profile_table(self):
+        return self.stepper.profile_table()
+
+    def profile_stats(self, table=None):
+        """theta_vol / psi_press / S_eff mean and sigma [T_out][D], transpiration / lateral_flow mean and sigma and
+        abs_error_mean [T], rows, count (stepper.profile_tables_to_stats); ``table``: e.g. the sum over ranks."""
+        return self.stepper.profile_stats(table)
+
     # -- checkpoint / resume (the single-column analogue in the reference is IC_Filename, simulation.py:358-385) ------
     CHECKPOINT_KEYS = ("psi", "noise_scale", "moments", "next_row", "seed", "member_offset", "n_members", "dim_d",
                        "dim_t", "initial_cond")
@@ -196,6 +213,9 @@ class EnsembleSimulation:
                       seed=np.array(self.seed, dtype=np.uint64), member_offset=np.array(self.member_offset, dtype=np.int64),
                       n_members=np.array(self.n_members, dtype=np.int64), dim_d=np.array(self.cols.dim_d, dtype=np.int64),
                       dim_t=np.array(self.forcing.dim_t, dtype=np.int64), initial_cond=np.asarray(self.psi0, dtype=float))
+        if self.profile_stride:
+            arrays["profile_stride"] = np.array(self.profile_stride, dtype=np.int64)
+            arrays["profile_table"] = self.stepper.profile_table()
         path = Path(path)
         if hdf5io.available() and path.suffix != ".npz":
             hdf5io.write(path, arrays)
@@ -219,11 +239,14 @@ class EnsembleSimulation:
             raise ValueError(f" EnsembleSimulation: checkpoint of a [{D}]-node column over {T} rows does not fit "
                              f"this run ([{cols.dim_d}], {forcing.dim_t}).")
         psi = np.asarray(data["psi"], dtype=float).reshape(n, D)
+        stride = int(data["profile_stride"]) if "profile_stride" in data else 0
         sim = cls(cols, forcing, n, seed=int(data["seed"]), device=device, member_offset=int(data["member_offset"]),
-                  psi0=np.asarray(data["initial_cond"], dtype=float).reshape(-1)[:D], flags=flags)
+                  psi0=np.asarray(data["initial_cond"], dtype=float).reshape(-1)[:D], flags=flags, profile_stride=stride)
         sim.stepper.set_state(psi if n > 1 else psi[0])
         sim.stepper.set_noise_scale(np.asarray(data["noise_scale"], dtype=float).reshape(n))
         sim.stepper.set_moments(np.asarray(data["moments"], dtype=np.int64))
+        if stride:
+            sim.stepper.set_profile_table(np.asarray(data["profile_table"], dtype=np.int64))
         sim.next_row = int(data["next_row"])
         return sim
 
@@ -318,7 +341,7 @@ class SweepSimulation:
     result is broadcast to the point's members."""
 
     def __init__(self, cols_list, forcing, n_members, seed=0, device=0, first_point=0, flags=None, psi0=None,
-                 point_ids=None):
+                 point_ids=None, profile_stride=0):
         self.points = list(cols_list)
         self.P, self.n = len(self.points), int(n_members)
         self.forcing, self.seed, self.device = forcing, int(seed), device
@@ -344,6 +367,10 @@ class SweepSimulation:
         self.stepper.set_noise_philox(self.seed, self.member_offset)
         if self.P > 1:
             self.stepper.set_point_member_bases(self.bases)
+        self.profile_stride = int(profile_stride)
+        if self.profile_stride:
+            self.stepper.set_profile_stats(self.profile_stride)
+            self.stepper.profile_snapshot(0)
         self.next_row, self.kernel_ms, self.launches = 1, 0.0, 0
 
     def _spinup(self, flags):
@@ -371,6 +398,13 @@ class SweepSimulation:
     def moments(self):
         """[P][3][T]"""
         return np.asarray(self.stepper.moments()).reshape(self.P, 3, self.forcing.dim_t)
+
+    def profile_table(self):
+        return self.stepper.profile_table()
+
+    def profile_stats(self, table=None):
+        """As EnsembleSimulation.profile_stats, with a leading [P] axis when the handle holds several points."""
+        return self.stepper.profile_stats(table)
 
     def close(self):
         self.stepper.close()

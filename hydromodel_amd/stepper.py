@@ -41,7 +41,7 @@ class EnsembleStepper:
     forcing): with P points the N members are point-major, point k owns members [k N/P, (k+1) N/P), and one launch
     advances all of them; ``moments()`` then returns [P][3][T]."""
 
-    def __init__(self, cols, forcing, n_members, device=0, flags=None):
+    def __init__(self, cols, forcing, n_members, device=0, flags=None, profile_stride=0):
         self.lib = L.load()
         points = list(cols) if isinstance(cols, (list, tuple)) else [cols]
         cols = points[0]
@@ -73,6 +73,9 @@ class EnsembleStepper:
         L.check(self.lib.hc_set_members(self.h, self.N))
         self.last_kernel_ms = 0.0
         self.last_launches = 0
+        self.profile_stride = 0
+        if profile_stride:
+            self.set_profile_stats(profile_stride)
 
     def close(self):
         if getattr(self, "h", None):
@@ -232,6 +235,52 @@ class EnsembleStepper:
     def reset_moments(self):
         L.check(self.lib.hc_reset_moments(self.h))
 
+    # -- ensemble profile statistics (include/hydrocol.h hc_set_profile_stats) ---------------------------------------
+    def set_profile_stats(self, stride):
+        """Accumulate psi / theta of every ``stride``-th forcing row and the fluxes of every solved row (0 = off).  Row 0 is
+        the state before any solve: call :meth:`profile_snapshot` once the initial states are in place."""
+        stride = int(stride)
+        if stride < 0:
+            raise ValueError(f"profile stride must be >= 0, got {stride}")
+        L.check(self.lib.hc_set_profile_stats(self.h, stride))
+        self.profile_stride = stride
+
+    def profile_snapshot(self, row=0):
+        L.check(self.lib.hc_profile_snapshot(self.h, int(row)))
+
+    def profile_words(self):
+        n = C.c_int64()
+        L.check(self.lib.hc_get_profile_stats_words(self.h, C.byref(n)))
+        return int(n.value)
+
+    def profile_table(self):
+        """The raw int64 table (layout: :func:`profile_layout`)."""
+        t = np.zeros(self.profile_words(), dtype=np.int64)
+        L.check(self.lib.hc_get_profile_stats(self.h, L.lptr(t), t.size))
+        return t
+
+    def set_profile_table(self, table):
+        t = np.ascontiguousarray(table, dtype=np.int64).reshape(-1)
+        L.check(self.lib.hc_set_profile_stats_tables(self.h, L.lptr(t), t.size))
+
+    def export_profile_stats(self, device_ptr):
+        """Copy the table device-to-device to ``device_ptr`` (``profile_words()`` int64 on this handle's device)."""
+        L.check(self.lib.hc_export_profile_stats(self.h, C.c_void_p(int(device_ptr)), self.profile_words()))
+
+    def reset_profile_stats(self):
+        L.check(self.lib.hc_reset_profile_stats(self.h))
+
+    def profile_overflow(self):
+        out = C.c_uint64()
+        L.check(self.lib.hc_get_profile_overflow(self.h, C.byref(out)))
+        return int(out.value)
+
+    def profile_stats(self, table=None):
+        """Mean / sigma arrays of ``profile_table()`` (or of ``table``, e.g. summed over ranks): :func:`profile_tables_to_stats`."""
+        t = self.profile_table() if table is None else table
+        return profile_tables_to_stats(t, self.P, self.T, self.D, self.profile_stride,
+                                       np.stack([pt.por_node for pt in self.points]), self.cols.dz)
+
     # -- hooks ----------------------------------------------------------------------
     def spinup(self, zwtd_cm, z0_cm, forcing_row=0, max_iterations=1500):
         """Per-member ``Simulation.initial_conditions`` (simulation.py:389-493) in one launch: every member
@@ -270,6 +319,100 @@ def moments_to_mean_std(moments, dz, z0=0.0):
         mean_idx = moments[..., 1, :] / cnt
         var_idx = np.maximum(moments[..., 2, :] / cnt - mean_idx ** 2, 0.0)
     return z0 + dz * mean_idx, dz * np.sqrt(var_idx)
+
+
+# ---- profile statistics on the host: layout, quantisation, limb normalisation (include/hydrocol.h) ----------------------
+PROF_WORDS = 5
+PROF_SCALE_PSI, PROF_SCALE_THETA, PROF_SCALE_FLUX = 16, 40, 32
+PROF_Q_MAX = (1 << 40) - 1
+
+
+def profile_layout(P, T, D, stride):
+    """{part: (offset, shape)} of the int64 table: prof [P][T_out][D][2][5] (psi_press, theta_vol), pcnt [P][T_out],
+    flux [P][T][2][5] (transpiration, lateral_flow), fcnt [P][T], aerr [P][T], ovf [1]; T_out = (T - 1) // stride + 1."""
+    n_prow = (int(T) - 1) // int(stride) + 1
+    shapes = [("prof", (P, n_prow, D, 2, PROF_WORDS)), ("pcnt", (P, n_prow)), ("flux", (P, T, 2, PROF_WORDS)),
+              ("fcnt", (P, T)), ("aerr", (P, T)), ("ovf", (1,))]
+    out, off = {}, 0
+    for name, shape in shapes:
+        out[name] = (off, shape)
+        off += int(np.prod(shape))
+    out["words"] = (off, ())
+    return out
+
+
+def split_profile_table(table, P, T, D, stride):
+    """Views of the parts of a flat table (see :func:`profile_layout`)."""
+    t = np.asarray(table, dtype=np.int64).reshape(-1)
+    lay = profile_layout(P, T, D, stride)
+    if t.size != lay["words"][0]:
+        raise ValueError(f"profile table of {t.size} words, the layout has {lay['words'][0]}")
+    return {k: t[o:o + int(np.prod(sh))].reshape(sh) for k, (o, sh) in lay.items() if k != "words"}
+
+
+def join_profile_table(parts):
+    """The flat table of ``split_profile_table`` parts (same order)."""
+    return np.concatenate([np.asarray(parts[k], dtype=np.int64).reshape(-1)
+                           for k in ("prof", "pcnt", "flux", "fcnt", "aerr", "ovf")])
+
+
+def profile_quantise(x, scale_bits):
+    """q = rint(x 2^s) clamped to |q| <= 2^40 - 1 (NaN -> 0), as the device does; returns (q int64, values clamped)."""
+    y = np.rint(np.asarray(x, dtype=np.float64) * 2.0 ** scale_bits)
+    bad = ~(np.abs(y) <= PROF_Q_MAX)
+    y = np.where(np.isnan(y), 0.0, np.clip(y, -PROF_Q_MAX, PROF_Q_MAX))
+    return y.astype(np.int64), int(bad.sum())
+
+
+def profile_words_of(q):
+    """[..., 5] int64 words one member adds for quantised values q: q, then the 20-bit limbs of q^2."""
+    q = np.asarray(q, dtype=np.int64)
+    a = np.abs(q).astype(object)
+    sq = a * a
+    limbs = [np.asarray((sq >> (20 * k)) & ((1 << 20) - 1), dtype=np.int64) for k in range(4)]
+    return np.stack([q] + limbs, axis=-1)
+
+
+def limbs_to_mean_std(count, words, scale_bits):
+    """Mean and population sigma from (count, [..., 5] words): the limbs are recombined with Python integers, the
+    variance numerator n sum q^2 - (sum q)^2 is formed exactly and only then divided and rounded (no E[x^2] - E[x]^2
+    cancellation).  Entries with count 0 are NaN.  Same convention as :func:`moments_to_mean_std`."""
+    words = np.asarray(words, dtype=np.int64)
+    n = np.broadcast_to(np.asarray(count, dtype=np.int64), words.shape[:-1])
+    empty = n <= 0
+    no = np.where(empty, 1, n).astype(object)
+    s1 = words[..., 0].astype(object)
+    s2 = sum(words[..., k + 1].astype(object) * (1 << (20 * k)) for k in range(4))
+    var_num = no * s2 - s1 * s1
+    scale = 2.0 ** -scale_bits
+    mean = np.asarray(np.asarray(s1 / no, dtype=np.float64) * scale)
+    std = np.asarray(np.sqrt(np.asarray(var_num / (no * no), dtype=np.float64)) * scale)
+    return np.where(empty, np.nan, mean), np.where(empty, np.nan, std)
+
+
+def profile_tables_to_stats(table, P, T, D, stride, porosity, dz):
+    """The science arrays of a profile-statistics table: ``{theta_vol, psi_press, S_eff}_{mean,std}`` [P][T_out][D]
+    (S_eff = theta_vol / porosity, simulation.py:658), ``{transpiration, lateral_flow}_{mean,std}`` and
+    ``abs_error_mean`` [P][T] (NaN where no member was counted), ``rows`` [T_out], ``count`` [P][T_out] (members in each
+    profile row), ``row_count`` [P][T] and ``overflow``.  The leading [P] axis is dropped for a single point."""
+    parts = split_profile_table(table, P, T, D, stride)
+    pcnt = parts["pcnt"][..., None]
+    out = {}
+    out["psi_press_mean"], out["psi_press_std"] = limbs_to_mean_std(pcnt, parts["prof"][..., 0, :], PROF_SCALE_PSI)
+    out["theta_vol_mean"], out["theta_vol_std"] = limbs_to_mean_std(pcnt, parts["prof"][..., 1, :], PROF_SCALE_THETA)
+    por = np.asarray(porosity, dtype=np.float64).reshape(P, 1, D)
+    out["S_eff_mean"], out["S_eff_std"] = out["theta_vol_mean"] / por, out["theta_vol_std"] / por
+    fcnt = parts["fcnt"]
+    out["transpiration_mean"], out["transpiration_std"] = limbs_to_mean_std(fcnt, parts["flux"][..., 0, :], PROF_SCALE_FLUX)
+    out["lateral_flow_mean"], out["lateral_flow_std"] = limbs_to_mean_std(fcnt, parts["flux"][..., 1, :], PROF_SCALE_FLUX)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["abs_error_mean"] = np.where(fcnt > 0, float(dz) * parts["aerr"] / np.maximum(fcnt, 1), np.nan)
+    out["count"], out["row_count"] = parts["pcnt"].copy(), fcnt.copy()
+    if P == 1:
+        out = {k: v[0] for k, v in out.items()}
+    out["rows"] = np.arange(parts["pcnt"].shape[1], dtype=np.int64) * int(stride)
+    out["overflow"] = int(parts["ovf"][0])
+    return out
 
 
 def allreduce_handles(steppers):

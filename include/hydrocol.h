@@ -33,6 +33,9 @@
  *   hc_set_point_member_bases <- which realisation a member is: the reference seeds one generator per run
  *                         (src/simulation.py:66-70); here member j of sweep point k draws stream base[k] + j
  *   hc_allreduce_moments, hc_get_point_costs <- (new) the ensemble's one collective; per-point cost for scheduling
+ *   hc_set_profile_stats, hc_profile_snapshot, hc_get/set/export/reset_profile_stats*, hc_get_profile_overflow
+ *                      <- Simulation.run's science output (src/simulation.py:658-671) as ensemble mean / sigma:
+ *                         psi_press, theta_vol (and S_eff on the host), transpiration, lateral_flow, abs_error
  *
  * Conventions: every function returns 0 on success or a negative hc_status; nothing throws
  * or aborts across the boundary; hc_last_error() gives the thread-local message.  Host
@@ -222,6 +225,49 @@ int hc_get_moments(hc_handle *h, int64_t *moments);
 int hc_export_moments(hc_handle *h, void *device_dst);
 int hc_set_moments(hc_handle *h, const int64_t *moments);
 int hc_reset_moments(hc_handle *h);
+
+/* Ensemble profile statistics: what Simulation.run returns for one column (src/simulation.py:658-671) as the mean and
+ * population sigma over the members of each parameter point, reduced on the device.
+ *   profile rows r % stride == 0 (r < n_forcing_rows): psi_press = the state after the row's solve (psi[i], :615) and
+ *     theta_vol = theta of that state at the nodes (h_model, :620; bit for bit hc_model_nodes' out[0]); row 0 is the state
+ *     before any solve (psi[0], theta_vol[0]) and comes from hc_profile_snapshot on the current states;
+ *   every solved row: transpiration, lateral_flow (pde_model.arg_out after the row's solve, :629-630; the values
+ *     hc_step_args.diag_out returns) and sum |obs_idx - wtd_idx| (abs_error = dz * that sum / count, :612).
+ * Skipped rows (wtd_obs < 0) count no members; spin-up solves accumulate nothing.
+ * Integer sums only: x is quantised to q = rint(x * 2^s), s = HC_PROF_SCALE_* below, |q| <= HC_PROF_Q_MAX (a value outside is
+ * clamped and counted in the overflow slot); each member adds q to word 0 and the four 20-bit limbs of q^2 (< 2^80),
+ * (q^2 >> 20k) & (2^20 - 1), to words 1 + k.  Five int64 words per (row, node, quantity): sums over ranks / handles are
+ * plain int64 sums (exact, order-independent); the host forms n sum q^2 - (sum q)^2 exactly before any rounding.
+ * Table (int64, n_prow = (n_forcing_rows - 1) / stride + 1, P points, T forcing rows, D nodes), in this order:
+ *   prof [P][n_prow][D][2][5]   quantity 0 = psi_press, 1 = theta_vol
+ *   pcnt [P][n_prow]            members counted in each profile row
+ *   flux [P][T][2][5]           quantity 0 = transpiration, 1 = lateral_flow
+ *   fcnt [P][T]                 members counted in each solved row
+ *   aerr [P][T]                 sum |obs_idx - wtd_idx|
+ *   ovf  [1]                    values clamped by the quantisation (summed like the rest)
+ * hc_step_rows with statistics on stages the two fluxes of every row ([rows][N][2] doubles, at most 1 GiB) on the device.
+ * When the stride is at least the number of rows whose states fit in about 4 GiB ([rows][N][D] doubles), a launch ends on
+ * each profile row and that row is reduced from the members' current states; shorter strides stage the states of every
+ * row of a launch (as psi_rows_out does) and the launches are shortened to fit.  The step kernels are the same either way
+ * and results do not depend on launch length.
+ * hc_set_profile_stats: stride 0 = off (default); otherwise (re)creates the table zeroed.  Like the moment table it is
+ * re-created, zeroed, when the points, the forcing rows or the depth change.  get / set / export take the table's size in
+ * words (hc_get_profile_stats_words) and fail on any other. */
+#define HC_PROF_WORDS 5
+#define HC_PROF_SCALE_PSI 16        /* psi [cm]: 2^-16 cm steps, |psi| < 2^24 cm                                   */
+#define HC_PROF_SCALE_THETA 40      /* theta in [0, 1]: 2^-40 steps                                                */
+#define HC_PROF_SCALE_FLUX 32       /* transpiration, lateral flow [cm per row]: 2^-32 steps, |x| < 2^8             */
+#define HC_PROF_Q_MAX ((1LL << 40) - 1)
+int hc_set_profile_stats(hc_handle *h, int32_t stride);
+int hc_get_profile_stats_words(hc_handle *h, int64_t *n_words);
+/* accumulates every member's current state as profile row `row` (row % stride == 0), counting all members */
+int hc_profile_snapshot(hc_handle *h, int64_t row);
+int hc_get_profile_stats(hc_handle *h, int64_t *table, int64_t n_words);
+int hc_set_profile_stats_tables(hc_handle *h, const int64_t *table, int64_t n_words);   /* checkpoint / resume */
+/* device-to-device into caller-owned memory on the handle's device (the buffer of a collective); complete on return */
+int hc_export_profile_stats(hc_handle *h, void *device_dst, int64_t n_words);
+int hc_reset_profile_stats(hc_handle *h);
+int hc_get_profile_overflow(hc_handle *h, uint64_t *count);   /* the ovf slot */
 
 /* The path's one collective inside the library, for a single process that drives several devices with
  * one handle each: every handle's moment table is replaced by the sum over all n handles (ncclAllReduce, ncclInt64,
