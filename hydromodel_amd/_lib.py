@@ -87,6 +87,11 @@ EXPORTS = {
     "hc_export_profile_stats": ([C.c_void_p, C.c_void_p, C.c_int64], C.c_int),
     "hc_reset_profile_stats": ([C.c_void_p], C.c_int),
     "hc_get_profile_overflow": ([C.c_void_p, C.POINTER(C.c_uint64)], C.c_int),
+    "hc_set_wtd_hist": ([C.c_void_p, C.c_int32], C.c_int),
+    "hc_get_wtd_hist": ([C.c_void_p, _ip, C.c_int64], C.c_int),
+    "hc_set_wtd_hist_table": ([C.c_void_p, _ip, C.c_int64], C.c_int),
+    "hc_reset_wtd_hist": ([C.c_void_p], C.c_int),
+    "hc_wtd_distribution": ([C.c_int, _ip, _ip, C.c_int64, C.c_int32, _dp, C.c_int32, C.c_double, _lp, _ip, _dp], C.c_int),
     "hc_rhs": ([C.c_void_p, C.c_int64, C.c_int32, _dp, _dp], C.c_int),
     "hc_model_nodes": ([C.c_void_p, _dp, _dp], C.c_int),
     "hc_plugin_eval": ([C.c_int, C.POINTER(ColumnParams), C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp],

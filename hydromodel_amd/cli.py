@@ -26,6 +26,14 @@ unknown keys, only membership of the 12 is checked):
   ``[T_out][D]``, and for every solved row those of ``transpiration`` / ``lateral_flow`` and ``abs_error_mean`` ``[T]``
   (simulation.py:658-671; ``<key>_mean`` / ``<key>_std``, with ``profile_rows`` and ``profile_count``), added to
   ``<Output_Name>_ensemble.h5`` (a sweep: a leading ``[P]`` axis).  The integer tables are all-reduced with the moments.
+* ``"Ensemble": {..., "Distribution": {"Stride": 48, "Quantiles": [0.05, 0.5, 0.95]}}``: the members' water-table index
+  counted per row on the GPU -- every 48th forcing row (default 48; 0 = off) a histogram over the depth grid, summed over
+  the ranks like the moments -- and from it the quantile depths (NumPy's ``method="inverted_cdf"``; default levels 0.05,
+  0.25, 0.5, 0.75, 0.95, at most 16) and the CRPS against the well, the ensemble form of the reference's ``abs_error``
+  (simulation.py:612-615: for one member the CRPS is ``abs_error``).  Added to ``<Output_Name>_ensemble.h5``:
+  ``wtd_hist`` ``[T_out][D]``, ``wtd_hist_rows``, ``wtd_hist_count``, ``wtd_quantile_levels``, ``wtd_quantile_cm``
+  ``[T_out][L]``, ``wtd_crps_cm`` ``[T_out]`` and ``wtd_crps_mean_cm`` (a sweep: a leading ``[P]`` axis), and the run
+  ends with the line `` [Ensemble xN] CRPS = ... cm over R rows``, as the reference ends with its MAE.
 * ``"Ensemble": {"repair_predict": true}`` with ``Simulation_Flags.PREDICT``: run the repaired predictive lateral flow
    instead of raising the reference's ``TypeError``.
 """
@@ -80,6 +88,8 @@ def main(params_file=None, data_file=None, seed=None, device=0, gpus=None, _sett
     csv_path = Path(data_file) if data_file is not None else Path(params["Data_Filename"])
     ranks = None
     try:
+        if params.get("Ensemble"):
+            distribution_settings(params["Ensemble"])      # a bad Distribution block fails before any GPU is touched
         n_gpus = multigpu.requested_gpus(gpus, params)
         ranks = multigpu.Ranks(expect=n_gpus if (n_gpus > 1 or multigpu.in_rank()) else None)
         if ranks.world > 1:
@@ -136,6 +146,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     from . import multigpu
     from .digest import ColumnTables, ForcingDigest, load_site_well
     from .ensemble import EnsembleSimulation
+    dist_stride, dist_levels = distribution_settings(ens)
     cols = ColumnTables(params, load_site_well(params))
     forcing = ForcingDigest(params, water_data, cols)
     if cols.flags["PREDICT"] and not ens.get("repair_predict"):
@@ -144,14 +155,15 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     days = int(ens.get("Days", (forcing.dim_t - 1) // 48))
     rows = min(days * 48, forcing.dim_t - 1)
     if ens.get("Points"):
-        return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks)
+        return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels)
     lo, hi = multigpu.shard(n_members, ranks.rank, ranks.world)
     if hi <= lo:
         raise ValueError(f" Ensemble: {n_members} members do not shard over {ranks.world} GPUs (a rank would be empty).")
     stride = _profile_stride(ens)
     sim = EnsembleSimulation(cols, forcing, hi - lo, seed=int(ens.get("Seed", 0)), device=device, member_offset=lo,
                              noise=str(ens.get("Noise", "philox")).lower(),
-                             spinup=str(ens.get("Spinup", "shared")).lower(), profile_stride=stride)
+                             spinup=str(ens.get("Spinup", "shared")).lower(), profile_stride=stride,
+                             wtd_hist_stride=dist_stride)
     done = 0
     while done < rows:
         n = min(48 * 30, rows - done)
@@ -184,10 +196,72 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     if stride:
         # the profile tables are int64 sums like the moments: one more exact all-reduce
         extra.update(_profile_datasets(sim.profile_stats(ranks.allreduce_sum(sim.profile_table()))))
+    crps_line = None
+    if dist_stride:
+        # int32 counts, summed as int64 like the moments; rank 0 forms the summary
+        hist = ranks.allreduce_sum(sim.wtd_hist_table().astype(np.int64))
+        if ranks.rank == 0:
+            dist = sim.wtd_distribution(dist_levels, table=hist)
+            extra.update(_distribution_datasets(hist, dist))
+            crps_line = _crps_line(f"Ensemble x{n_members}", dist)
     arrays = dict(moments=moments, wtd_mean_cm=mean_cm, wtd_std_cm=std_cm, rows=np.array(rows),
                   members=np.array(n_members), gpus=np.array(ranks.world), initial_cond=psi0, **extra)
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "ensemble water-table statistics", ranks)
+    if crps_line:
+        print(crps_line)
     sim.close()
+
+
+DEFAULT_QUANTILES = (0.05, 0.25, 0.5, 0.75, 0.95)
+
+
+def distribution_settings(ens):
+    """Ensemble.Distribution -> (stride, quantile levels); (0, None) when absent or off.  Pure: runs before any GPU call,
+    and a bad value is a ValueError (message + exit status 1)."""
+    import math
+    from numbers import Real
+    block = ens.get("Distribution")
+    if block is None:
+        return 0, None
+    if not isinstance(block, dict):
+        raise ValueError(f" Ensemble: Distribution = {block!r} must be an object such as "
+                         f"{{\"Stride\": 48, \"Quantiles\": [0.05, 0.5, 0.95]}}.")
+    stride = block.get("Stride", 48)
+    if (isinstance(stride, bool) or not isinstance(stride, Real) or not math.isfinite(stride) or stride != int(stride)
+            or stride < 0):
+        raise ValueError(f" Ensemble: Distribution.Stride = {stride!r} must be a row stride >= 0 (0: off).")
+    levels = block.get("Quantiles", list(DEFAULT_QUANTILES))
+    if not isinstance(levels, (list, tuple)) or not levels:
+        raise ValueError(f" Ensemble: Distribution.Quantiles = {levels!r} must be a non-empty list of levels in [0, 1].")
+    if len(levels) > 16:
+        raise ValueError(f" Ensemble: Distribution.Quantiles holds {len(levels)} levels; at most 16 are supported.")
+    for q in levels:
+        if isinstance(q, bool) or not isinstance(q, Real) or not math.isfinite(q):
+            raise ValueError(f" Ensemble: Distribution.Quantiles: {q!r} is not a number.")
+        if not 0.0 <= q <= 1.0:
+            raise ValueError(f" Ensemble: Distribution.Quantiles: {q!r} lies outside [0, 1].")
+    stride = int(stride)
+    return (stride, tuple(float(q) for q in levels)) if stride else (0, None)
+
+
+def _distribution_datasets(hist, dist):
+    """The datasets of the water-table distribution (hist: the int64 sum over the ranks, stored as int32)."""
+    import numpy as np
+    return {"wtd_hist": np.asarray(hist, dtype=np.int32), "wtd_hist_rows": np.asarray(dist["rows"], dtype=np.int64),
+            "wtd_hist_count": np.asarray(dist["count"], dtype=np.int64),
+            "wtd_quantile_levels": np.asarray(dist["levels"], dtype=np.float64),
+            "wtd_quantile_cm": np.asarray(dist["quantile_cm"]), "wtd_crps_cm": np.asarray(dist["crps_cm"]),
+            "wtd_crps_mean_cm": np.asarray(dist["crps_mean_cm"], dtype=np.float64)}
+
+
+def _crps_line(what, dist):
+    """The closing line, after the reference's running MAE (simulation.py:633-649): the mean CRPS over the histogram rows
+    that counted members (all points of a sweep together)."""
+    import numpy as np
+    solved = np.asarray(dist["count"]) > 0
+    n = int(solved.sum())
+    mean = float(np.asarray(dist["crps_cm"])[solved].mean()) if n else float("nan")
+    return f" [{what}] CRPS = {mean:.3f} cm over {n} rows"
 
 
 def _profile_stride(ens):
@@ -210,7 +284,7 @@ def _profile_datasets(stats):
     return out
 
 
-def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks):
+def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride=0, dist_levels=None):
     """Parameter points x members: this rank's points in one handle (ensemble.SweepSimulation), the whole table assembled
     over the ranks (multigpu.assemble_points)."""
     import numpy as np
@@ -232,10 +306,10 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     D, T = None, forcing.dim_t
     local = {}
     stride = _profile_stride(ens)
-    prof_local = None
+    prof_local = hist_local = None
     if mine:
         sim = SweepSimulation(points, forcing, n_members, seed=int(ens.get("Seed", 0)), device=device, point_ids=mine,
-                              profile_stride=stride)
+                              profile_stride=stride, wtd_hist_stride=dist_stride)
         done = 0
         while done < rows:
             n = min(48 * 30, rows - done)
@@ -250,6 +324,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
         D = points[0].dim_d
         if stride:
             prof_local = sim.profile_table()
+        if dist_stride:
+            hist_local = sim.wtd_hist_table()
         sim.close()
     if D is None:        # a rank without points still joins the collectives: the grid is the well's, whoever owns it
         D = ColumnTables(merged[0], well).dim_d
@@ -275,7 +351,20 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
         if P == 1:       # keep the [P] axis of a sweep's datasets
             stats = {k: (v[None] if isinstance(v, np.ndarray) and k != "rows" else v) for k, v in stats.items()}
         arrays.update(_profile_datasets(stats))
+    crps_line = None
+    if dist_stride:
+        # as the profile table: every rank's points in a zeroed [P] table, summed over the ranks; rank 0 forms the summary
+        from .stepper import place_points, wtd_distribution, wtd_hist_slots
+        if hist_local is None:
+            hist_local = np.zeros((0, wtd_hist_slots(T, dist_stride), D), dtype=np.int32)
+        hist = ranks.allreduce_sum(place_points(hist_local, mine, P))
+        if ranks.rank == 0:
+            dist = wtd_distribution(hist, forcing.wtd_obs, dist_levels, ref.dz, ref.z, device, dist_stride)
+            arrays.update(_distribution_datasets(hist, dist))
+            crps_line = _crps_line(f"Sweep {P} points x{n_members}", dist)
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "sweep's water-table statistics", ranks)
+    if crps_line:
+        print(crps_line)
 
 
 def run_cli(argv=None):

@@ -139,6 +139,11 @@ struct hc_handle {
     int prof_points = 0, prof_d = 0;
     int64_t prof_t = 0;          // forcing rows the table was made for
     DevBuf<long long> prof;
+    // ensemble water-table histograms (hc_set_wtd_hist): int32 [P][n_hrow][D], re-created like the profile table
+    int hist_stride = 0;         // 0: off
+    int hist_points = 0, hist_d = 0;
+    int64_t hist_t = 0;
+    DevBuf<int> hist;
     int n_cu = 256;
     double jac_reject = NUM_JAC_DIFF_REJECT;
 };
@@ -315,6 +320,157 @@ __global__ __launch_bounds__(256) void flux_stats_kernel(const double *diag, con
             aerr[pr] += sum;
     }
     if (threadIdx.x == 0) fcnt[(size_t)blockIdx.y * n_forcing + row] += members_per_point;
+}
+
+// ---- ensemble water-table histograms (hc_set_wtd_hist, include/hydrocol.h)
+constexpr int HIST_THREADS = 256;
+
+// The histogram rows of one launch: grid x = (histogram row j of the launch) x (member slice), y = point.  Launch row
+// first + j stride is forcing row row0 + first + j stride.  Bins are counted in LDS (D <= 640 uint32).  The members of one
+// well sit in a few bins, so a plain ds_add_u32 per lane would serialise on one address: each wave first groups its 64
+// members by bin (one ballot per distinct bin: a wave of one bin costs one LDS add instead of 64), and one lane adds the
+// group's size.  Only nonzero bins go to the table, with int32 atomics (integer adds: order-independent).
+__global__ __launch_bounds__(HIST_THREADS) void wtd_hist_kernel(const unsigned short *wtd, const int *wtd_obs,
+                                                                long long n_members, long long members_per_point,
+                                                                long long members_per_block, int slices, long long row0,
+                                                                int first, int stride, long long n_hrow, int D, int *hist)
+{
+    const long long j = blockIdx.x / slices;
+    const long long slice = blockIdx.x % slices;
+    const long long r = first + j * stride;
+    const long long row = row0 + r;
+    if (wtd_obs[row] < 0) return;
+    __shared__ unsigned bins[HC_MAX_DEPTH_NODES];
+    for (int b = threadIdx.x; b < D; b += HIST_THREADS) bins[b] = 0;
+    __syncthreads();
+    const long long point = blockIdx.y;
+    const long long end = (point + 1) * members_per_point;
+    const long long m0 = point * members_per_point + slice * members_per_block;
+    const long long m1 = m0 + members_per_block < end ? m0 + members_per_block : end;
+    const unsigned short *w = wtd + (size_t)r * n_members;
+    const int lane = threadIdx.x % WAVE;
+    // wave-uniform trip count: every lane of a wave runs the ballots of every round
+    for (long long k0 = m0 + (threadIdx.x - lane); k0 < m1; k0 += HIST_THREADS) {
+        const long long k = k0 + lane;
+        const int b = k < m1 ? (int)w[k] : -1;
+        unsigned long long pending = __ballot(b >= 0 && b < D);
+        while (pending) {
+            const int leader = __ffsll((long long)pending) - 1;
+            const int v = __builtin_amdgcn_readlane(b, leader);
+            const unsigned long long same = __ballot(b == v) & pending;
+            if (lane == leader) atomicAdd(&bins[v], (unsigned)__popcll(same));
+            pending &= ~same;
+        }
+    }
+    __syncthreads();
+    int *t = hist + ((size_t)point * n_hrow + (size_t)(row / stride)) * D;
+    for (int b = threadIdx.x; b < D; b += HIST_THREADS) {
+        const unsigned c = bins[b];
+        if (c) atomicAdd(t + b, (int)c);
+    }
+}
+
+struct WtdLevels {
+    double q[HC_WTD_MAX_LEVELS];
+};
+constexpr int DIST_BINS = HC_MAX_DEPTH_NODES / WAVE;    // bins per lane at the deepest column
+
+// 128-bit unsigned accumulator (hi, lo) += v
+__device__ __forceinline__ void add_u128(unsigned long long &hi, unsigned long long &lo, unsigned long long vhi,
+                                         unsigned long long vlo)
+{
+    lo += vlo;
+    hi += vhi + (lo < vlo ? 1ull : 0ull);
+}
+__device__ __forceinline__ void two_sum(double a, double b, double &s, double &e)
+{
+    s = a + b;
+    const double bb = s - a;
+    e = (a - (s - bb)) + (b - bb);
+}
+
+// dz S / n^2 for the exact S = (hi, lo): S and n^2 as double-double, one quotient, one rounding at the end
+__device__ double crps_of(unsigned long long s_hi, unsigned long long s_lo, long long n, double dz)
+{
+    // S = a + b + c, each term exact in fp64 (S < 2^92: s_hi < 2^28)
+    const double a = (double)s_hi * 0x1p64, b = (double)(s_lo >> 32) * 0x1p32, c = (double)(s_lo & 0xffffffffull);
+    double s1, e1, s2, e2, x_hi, x_lo;
+    two_sum(a, b, s1, e1);
+    two_sum(s1, c, s2, e2);
+    two_sum(s2, e1 + e2, x_hi, x_lo);
+    const double nd = (double)n;                   // exact: n < 2^41
+    const double d_hi = nd * nd, d_lo = fma(nd, nd, -d_hi);
+    const double q1 = x_hi / d_hi;
+    const double r = fma(-q1, d_hi, x_hi) + x_lo - q1 * d_lo;
+    const double q2 = r / d_hi;
+    const double p = q1 * dz, pe = fma(q1, dz, -p);
+    return p + (pe + q2 * dz);
+}
+
+// The summary of hist [n_rows][D] (hc_wtd_distribution): one wavefront per row, grid-stride over the rows.  Lane l holds the
+// contiguous bins [l per, (l + 1) per); a shuffle scan of the lane totals gives the cumulative counts; a quantile is the
+// first bin whose cumulative count reaches k, one ballot per level; S is summed exactly in two 64-bit words per lane, then
+// across the lanes.
+__global__ __launch_bounds__(256) void wtd_dist_kernel(const int *hist, const int *obs_idx, long long n_rows, int D,
+                                                       WtdLevels lv, int n_levels, double dz, long long *count,
+                                                       int *quantile_idx, double *crps_cm)
+{
+    const int lane = threadIdx.x % WAVE;
+    const long long waves = (long long)gridDim.x * (blockDim.x / WAVE);
+    const int per = (D + WAVE - 1) / WAVE;
+    for (long long row = (long long)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE; row < n_rows; row += waves) {
+        const int *hr = hist + (size_t)row * D;
+        const int o = obs_idx[row];
+        long long c[DIST_BINS];
+        long long tot = 0;
+#pragma unroll
+        for (int t = 0; t < DIST_BINS; t++) {
+            const int b = lane * per + t;
+            if (t < per && b < D) tot += hr[b];
+            c[t] = tot;
+        }
+        long long incl = tot;
+        for (int d = 1; d < WAVE; d <<= 1) {
+            const long long u = __shfl_up(incl, d);
+            if (lane >= d) incl += u;
+        }
+        const long long excl = incl - tot;
+        const long long n = __shfl(incl, WAVE - 1);
+#pragma unroll
+        for (int t = 0; t < DIST_BINS; t++) c[t] += excl;
+        for (int l = 0; l < n_levels; l++) {
+            int idx = -1;
+            if (n > 0) {
+                long long k = (long long)ceil((double)n * lv.q[l]);
+                k = k < 1 ? 1 : k;
+                int mine = -1;
+#pragma unroll
+                for (int t = DIST_BINS - 1; t >= 0; t--)
+                    if (t < per && lane * per + t < D && c[t] >= k) mine = lane * per + t;
+                const unsigned long long hit = __ballot(mine >= 0);
+                idx = hit ? __shfl(mine, __ffsll((long long)hit) - 1) : -1;
+            }
+            if (lane == 0) quantile_idx[(size_t)row * n_levels + l] = idx;
+        }
+        unsigned long long s_hi = 0, s_lo = 0;
+#pragma unroll
+        for (int t = 0; t < DIST_BINS; t++) {
+            const int b = lane * per + t;
+            if (t < per && b < D - 1) {
+                const long long d = c[t] - (b >= o ? n : 0);
+                const unsigned long long m = (unsigned long long)(d < 0 ? -d : d);
+                add_u128(s_hi, s_lo, __umul64hi(m, m), m * m);
+            }
+        }
+        for (int off = WAVE / 2; off > 0; off >>= 1) {
+            const unsigned long long ohi = __shfl_xor(s_hi, off), olo = __shfl_xor(s_lo, off);
+            add_u128(s_hi, s_lo, ohi, olo);
+        }
+        if (lane == 0) {
+            count[row] = n;
+            crps_cm[row] = (n > 0 && o >= 0 && o < D) ? crps_of(s_hi, s_lo, n, dz) : __builtin_nan("");
+        }
+    }
 }
 
 __global__ void widen_u16(const unsigned short *in, int *out, size_t n)
@@ -755,7 +911,7 @@ int hc_destroy(hc_handle *h)
     h->Pdev.release(); h->iodev.release();
     h->point_base.release(); h->point_order.release(); h->point_cost.release();
     h->daylight.release(); h->refresh.release(); h->wtd_u16.release(); h->moments.release(); h->counters.release();
-    h->prof.release();
+    h->prof.release(); h->hist.release();
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1151,6 +1307,79 @@ int launch_profile(hc_handle *h, const StepArgs &A, const ProfLayout &L, const d
     HIP_TRY(hipGetLastError());
     return HC_OK;
 }
+
+// the water-table histogram table (hc_set_wtd_hist): its entries, and the table itself, zeroed, for the current points /
+// rows / depth (re-created when one of them changed)
+int64_t hist_rows(const hc_handle *h) { return (h->n_rows - 1) / h->hist_stride + 1; }
+int64_t hist_entries(const hc_handle *h) { return (int64_t)h->n_points * hist_rows(h) * h->p.dim_d; }
+int ensure_hist(hc_handle *h)
+{
+    if (h->hist_stride <= 0) return fail(HC_ERR_ARG, "water-table histograms are off (hc_set_wtd_hist)");
+    if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
+    if (h->n_members / std::max(h->n_points, 1) > INT32_MAX)
+        return fail(HC_ERR_ARG, "water-table histograms: %lld members per point do not fit an int32 bin",
+                    (long long)(h->n_members / std::max(h->n_points, 1)));
+    if (hist_entries(h) > HC_WTD_HIST_MAX_ENTRIES)
+        return fail(HC_ERR_ARG, "water-table histograms: %lld entries exceed HC_WTD_HIST_MAX_ENTRIES (take a longer stride)",
+                    (long long)hist_entries(h));
+    if (h->hist_points != h->n_points || h->hist_t != h->n_rows || h->hist_d != h->p.dim_d) {
+        const size_t n = (size_t)hist_entries(h);
+        if (h->hist.ensure(n)) return HC_ERR_DEVICE;
+        HIP_TRY(hipMemset(h->hist.p, 0, n * 4));
+        h->hist_points = h->n_points;
+        h->hist_t = h->n_rows;
+        h->hist_d = h->p.dim_d;
+    }
+    return HC_OK;
+}
+int hist_entries_check(hc_handle *h, int64_t n_entries, const char *who)
+{
+    if (int rc = ensure_hist(h)) return rc;
+    if (n_entries != hist_entries(h))
+        return fail(HC_ERR_ARG, "%s: the table has %lld entries, not %lld", who, (long long)hist_entries(h), (long long)n_entries);
+    return HC_OK;
+}
+constexpr long long HIST_MEMBERS_PER_BLOCK = 4096;
+
+// the histogram rows among launch rows [row0, row0 + chunk) of the water-table indices in wtd_u16
+int launch_hist(hc_handle *h, int64_t row0, int chunk)
+{
+    const int64_t s = h->hist_stride;
+    const int64_t first = (s - row0 % s) % s;
+    if (first >= chunk) return HC_OK;
+    const int64_t n_here = (chunk - 1 - first) / s + 1;
+    const long long mpp = h->n_members / h->n_points;
+    // at most 65536 slices per row keeps the grid's x extent (rows x slices) far below 2^31
+    const long long mpb = std::max(HIST_MEMBERS_PER_BLOCK, (mpp + 65535) / 65536);
+    const long long slices = (mpp + mpb - 1) / mpb;
+    hipLaunchKernelGGL(wtd_hist_kernel, dim3((unsigned)(n_here * slices), (unsigned)h->n_points), dim3(HIST_THREADS), 0,
+                       h->stream, h->wtd_u16.p, h->wtd_obs.p, (long long)h->n_members, mpp, mpb, (int)slices,
+                       (long long)row0, (int)first, (int)s, (long long)hist_rows(h), h->p.dim_d, h->hist.p);
+    HIP_TRY(hipGetLastError());
+    return HC_OK;
+}
+
+int wtd_distribution_run(const int32_t *hist, const int32_t *obs_idx, int64_t n_rows, int32_t D, const WtdLevels &lv,
+                         int32_t n_levels, double dz, int64_t *count, int32_t *quantile_idx, double *crps_cm,
+                         DevBuf<int> &d_hist, DevBuf<int> &d_obs, DevBuf<long long> &d_count, DevBuf<int> &d_q,
+                         DevBuf<double> &d_crps)
+{
+    const size_t R = (size_t)n_rows;
+    if (d_hist.ensure(R * D) || d_obs.ensure(R) || d_count.ensure(R) || d_q.ensure(R * std::max(n_levels, 1)) ||
+        d_crps.ensure(R))
+        return HC_ERR_DEVICE;
+    HIP_TRY(hipMemcpy(d_hist.p, hist, R * D * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_obs.p, obs_idx, R * 4, hipMemcpyHostToDevice));
+    const unsigned blocks = (unsigned)std::min<int64_t>((n_rows + 3) / 4, 2048);
+    hipLaunchKernelGGL(wtd_dist_kernel, dim3(blocks), dim3(256), 0, nullptr, d_hist.p, d_obs.p, (long long)n_rows, (int)D, lv,
+                       (int)n_levels, dz, d_count.p, d_q.p, d_crps.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(count, d_count.p, R * 8, hipMemcpyDeviceToHost));
+    if (n_levels > 0) HIP_TRY(hipMemcpy(quantile_idx, d_q.p, R * n_levels * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(crps_cm, d_crps.p, R * 8, hipMemcpyDeviceToHost));
+    return HC_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1191,6 +1420,10 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
         if (int rc2 = ensure_prof(h)) return rc2;
         PL = prof_layout(h);
     }
+    // water-table histograms (hc_set_wtd_hist): read from wtd_u16 after each launch; spin-up solves accumulate nothing
+    const bool hist_on = h->hist_stride > 0 && !a->spinup;
+    if (hist_on)
+        if (int rc2 = ensure_hist(h)) return rc2;
     for (int64_t done = 0; done < a->n_rows;) {
         int per_launch = h->rows_per_launch > 0 ? h->rows_per_launch : auto_rows_per_launch(N, h->philox);
         if (h->rows_per_launch <= 0) per_launch = (int)std::min<int64_t>(per_launch, rows_cap);
@@ -1257,6 +1490,8 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
                                (long long)h->n_rows, h->moments.p);
             HIP_TRY(hipGetLastError());
         }
+        if (hist_on)
+            if (int rc2 = launch_hist(h, row0, chunk)) return rc2;
         if (prof_on) {
             for (int r = 0; r < chunk; r++) {
                 if ((row0 + r) % h->prof_stride != 0) continue;
@@ -1547,6 +1782,80 @@ int hc_get_profile_overflow(hc_handle *h, uint64_t *count)
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipMemcpy(count, h->prof.p + prof_layout(h).ovf, 8, hipMemcpyDeviceToHost));
     return HC_OK;
+}
+
+int hc_set_wtd_hist(hc_handle *h, int32_t stride)
+{
+    if (!h || stride < 0) return fail(HC_ERR_ARG, "hc_set_wtd_hist: bad argument");
+    if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->hist_stride = stride;
+    h->hist_points = 0;          // re-created, zeroed
+    const int rc = stride == 0 ? HC_OK : ensure_hist(h);
+    if (stride == 0 || rc != HC_OK) {   // off, or refused: off
+        h->hist_stride = 0;
+        h->hist.release();
+    }
+    return rc;
+}
+
+int hc_get_wtd_hist(hc_handle *h, int32_t *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_get_wtd_hist: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = hist_entries_check(h, n_entries, "hc_get_wtd_hist")) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(table, h->hist.p, (size_t)n_entries * 4, hipMemcpyDeviceToHost));
+    return HC_OK;
+}
+
+int hc_set_wtd_hist_table(hc_handle *h, const int32_t *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_set_wtd_hist_table: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = hist_entries_check(h, n_entries, "hc_set_wtd_hist_table")) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(h->hist.p, table, (size_t)n_entries * 4, hipMemcpyHostToDevice));
+    return HC_OK;
+}
+
+int hc_reset_wtd_hist(hc_handle *h)
+{
+    if (!h) return fail(HC_ERR_ARG, "hc_reset_wtd_hist: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->hist_points = 0;
+    return ensure_hist(h);
+}
+
+int hc_wtd_distribution(int device, const int32_t *hist, const int32_t *obs_idx, int64_t n_rows, int32_t D,
+                        const double *levels, int32_t n_levels, double dz, int64_t *count, int32_t *quantile_idx,
+                        double *crps_cm)
+{
+    if (device < 0 || n_rows < 0 || D < 2 || D > HC_MAX_DEPTH_NODES || n_levels < 0 || n_levels > HC_WTD_MAX_LEVELS ||
+        !std::isfinite(dz))
+        return fail(HC_ERR_ARG, "hc_wtd_distribution: bad argument (D = %d in [2, %d], %d levels of at most %d)", (int)D,
+                    HC_MAX_DEPTH_NODES, (int)n_levels, HC_WTD_MAX_LEVELS);
+    if (n_rows > HC_WTD_HIST_MAX_ENTRIES / D)
+        return fail(HC_ERR_ARG, "hc_wtd_distribution: %lld rows of %d bins exceed HC_WTD_HIST_MAX_ENTRIES", (long long)n_rows, (int)D);
+    if (n_rows > 0 && (!hist || !obs_idx || !count || !crps_cm || (n_levels > 0 && (!levels || !quantile_idx))))
+        return fail(HC_ERR_ARG, "hc_wtd_distribution: NULL argument");
+    WtdLevels lv{};
+    for (int l = 0; l < n_levels; l++) {
+        if (!(levels[l] >= 0.0 && levels[l] <= 1.0))
+            return fail(HC_ERR_ARG, "hc_wtd_distribution: level %d = %g is outside [0, 1]", l, levels[l]);
+        lv.q[l] = levels[l];
+    }
+    if (n_rows == 0) return HC_OK;
+    HIP_TRY(hipSetDevice(device));
+    DevBuf<int> d_hist, d_obs, d_q;
+    DevBuf<long long> d_count;
+    DevBuf<double> d_crps;
+    const int rc = wtd_distribution_run(hist, obs_idx, n_rows, D, lv, n_levels, dz, count, quantile_idx, crps_cm, d_hist,
+                                        d_obs, d_count, d_q, d_crps);
+    d_hist.release(); d_obs.release(); d_q.release(); d_count.release(); d_crps.release();
+    return rc;
 }
 
 // The path's one collective without torch: a single process that drives several devices (one handle each) sums the

@@ -9,7 +9,7 @@ all-reduce of the per-row water-table moments (see :func:`allreduce_moments`).
 import numpy as np
 
 from .digest import inverse_retention
-from .stepper import EnsembleStepper, moments_to_mean_std
+from .stepper import EnsembleStepper, moments_to_mean_std, wtd_distribution
 
 
 def pressure_head(cols, theta):
@@ -99,15 +99,20 @@ class EnsembleSimulation:
     spinup="member": every member spins up with its own first draw (`spinup_members_on_gpu`).
     profile_stride > 0: ensemble profile statistics (psi, theta every ``profile_stride``-th row from row 0 = the initial
     states, fluxes and abs_error every solved row) accumulated on the device: :meth:`profile_stats`.
+    wtd_hist_stride > 0: per-row histograms of the members' water-table index every ``wtd_hist_stride``-th row, counted on
+    the device: :meth:`wtd_distribution` (quantiles, CRPS against the well).
     """
 
     def __init__(self, cols, forcing, n_members, seed=0, device=0, member_offset=0, psi0=None, flags=None,
-                 noise="philox", spinup="shared", profile_stride=0):
+                 noise="philox", spinup="shared", profile_stride=0, wtd_hist_stride=0):
         self._start(cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup)
         self.profile_stride = int(profile_stride)
         if self.profile_stride:
             self.stepper.set_profile_stats(self.profile_stride)
             self.stepper.profile_snapshot(0)       # psi[0], theta_vol[0]: the state before any solve
+        self.wtd_hist_stride = int(wtd_hist_stride)
+        if self.wtd_hist_stride:
+            self.stepper.set_wtd_hist(self.wtd_hist_stride)
 
     def _start(self, cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup):
         if noise not in ("philox", "numpy") or spinup not in ("shared", "member"):
@@ -195,6 +200,17 @@ class EnsembleSimulation:
         abs_error_mean [T], rows, count (stepper.profile_tables_to_stats); ``table``: e.g. the sum over ranks."""
         return self.stepper.profile_stats(table)
 
+    def wtd_hist_table(self):
+        """[n_hrow][D] int32: members per water-table index on every histogram row (stepper.wtd_hist_rows)."""
+        return self.stepper.wtd_hist_table()[0]
+
+    def wtd_distribution(self, levels=(0.05, 0.25, 0.5, 0.75, 0.95), table=None):
+        """Quantiles of the water-table depth and CRPS against the well per histogram row (stepper.wtd_distribution);
+        ``table``: e.g. the sum over ranks."""
+        t = self.wtd_hist_table() if table is None else table
+        return wtd_distribution(t, self.forcing.wtd_obs, levels, self.cols.dz, self.cols.z, self.device,
+                                self.wtd_hist_stride)
+
     # -- checkpoint / resume (the single-column analogue in the reference is IC_Filename, simulation.py:358-385) ------
     CHECKPOINT_KEYS = ("psi", "noise_scale", "moments", "next_row", "seed", "member_offset", "n_members", "dim_d",
                        "dim_t", "initial_cond")
@@ -216,6 +232,9 @@ class EnsembleSimulation:
         if self.profile_stride:
             arrays["profile_stride"] = np.array(self.profile_stride, dtype=np.int64)
             arrays["profile_table"] = self.stepper.profile_table()
+        if self.wtd_hist_stride:
+            arrays["wtd_hist_stride"] = np.array(self.wtd_hist_stride, dtype=np.int64)
+            arrays["wtd_hist"] = self.stepper.wtd_hist_table()
         path = Path(path)
         if hdf5io.available() and path.suffix != ".npz":
             hdf5io.write(path, arrays)
@@ -240,13 +259,17 @@ class EnsembleSimulation:
                              f"this run ([{cols.dim_d}], {forcing.dim_t}).")
         psi = np.asarray(data["psi"], dtype=float).reshape(n, D)
         stride = int(data["profile_stride"]) if "profile_stride" in data else 0
+        hist_stride = int(data["wtd_hist_stride"]) if "wtd_hist_stride" in data else 0
         sim = cls(cols, forcing, n, seed=int(data["seed"]), device=device, member_offset=int(data["member_offset"]),
-                  psi0=np.asarray(data["initial_cond"], dtype=float).reshape(-1)[:D], flags=flags, profile_stride=stride)
+                  psi0=np.asarray(data["initial_cond"], dtype=float).reshape(-1)[:D], flags=flags, profile_stride=stride,
+                  wtd_hist_stride=hist_stride)
         sim.stepper.set_state(psi if n > 1 else psi[0])
         sim.stepper.set_noise_scale(np.asarray(data["noise_scale"], dtype=float).reshape(n))
         sim.stepper.set_moments(np.asarray(data["moments"], dtype=np.int64))
         if stride:
             sim.stepper.set_profile_table(np.asarray(data["profile_table"], dtype=np.int64))
+        if hist_stride:
+            sim.stepper.set_wtd_hist_table(np.asarray(data["wtd_hist"]))
         sim.next_row = int(data["next_row"])
         return sim
 
@@ -341,7 +364,7 @@ class SweepSimulation:
     result is broadcast to the point's members."""
 
     def __init__(self, cols_list, forcing, n_members, seed=0, device=0, first_point=0, flags=None, psi0=None,
-                 point_ids=None, profile_stride=0):
+                 point_ids=None, profile_stride=0, wtd_hist_stride=0):
         self.points = list(cols_list)
         self.P, self.n = len(self.points), int(n_members)
         self.forcing, self.seed, self.device = forcing, int(seed), device
@@ -371,6 +394,9 @@ class SweepSimulation:
         if self.profile_stride:
             self.stepper.set_profile_stats(self.profile_stride)
             self.stepper.profile_snapshot(0)
+        self.wtd_hist_stride = int(wtd_hist_stride)
+        if self.wtd_hist_stride:
+            self.stepper.set_wtd_hist(self.wtd_hist_stride)
         self.next_row, self.kernel_ms, self.launches = 1, 0.0, 0
 
     def _spinup(self, flags):
@@ -405,6 +431,16 @@ class SweepSimulation:
     def profile_stats(self, table=None):
         """As EnsembleSimulation.profile_stats, with a leading [P] axis when the handle holds several points."""
         return self.stepper.profile_stats(table)
+
+    def wtd_hist_table(self):
+        """[P][n_hrow][D] int32 (one table per parameter point of this handle)."""
+        return self.stepper.wtd_hist_table()
+
+    def wtd_distribution(self, levels=(0.05, 0.25, 0.5, 0.75, 0.95), table=None):
+        """As EnsembleSimulation.wtd_distribution, with a leading [P] axis; ``table``: e.g. the sweep assembled over ranks."""
+        t = self.wtd_hist_table() if table is None else table
+        return wtd_distribution(t, self.forcing.wtd_obs, levels, self.points[0].dz, self.points[0].z, self.device,
+                                self.wtd_hist_stride)
 
     def close(self):
         self.stepper.close()

@@ -74,6 +74,7 @@ class EnsembleStepper:
         self.last_kernel_ms = 0.0
         self.last_launches = 0
         self.profile_stride = 0
+        self.wtd_hist_stride = 0
         if profile_stride:
             self.set_profile_stats(profile_stride)
 
@@ -281,6 +282,32 @@ class EnsembleStepper:
         return profile_tables_to_stats(t, self.P, self.T, self.D, self.profile_stride,
                                        np.stack([pt.por_node for pt in self.points]), self.cols.dz)
 
+    # -- ensemble water-table histograms (include/hydrocol.h hc_set_wtd_hist) ----------------------------------------
+    def set_wtd_hist(self, stride):
+        """Count the members' water-table indices of every ``stride``-th forcing row into a [P][n_hrow][D] int32 table
+        (0 = off).  Row 0 (the initial state) stays empty: the reference computes no water table for it."""
+        stride = int(stride)
+        if stride < 0:
+            raise ValueError(f"histogram stride must be >= 0, got {stride}")
+        L.check(self.lib.hc_set_wtd_hist(self.h, stride))
+        self.wtd_hist_stride = stride
+
+    def wtd_hist_table(self):
+        """[P][n_hrow][D] int32 (slot j <-> forcing row j stride: :func:`wtd_hist_rows`)."""
+        t = np.zeros((self.P, wtd_hist_slots(self.T, self.wtd_hist_stride), self.D), dtype=np.int32)
+        L.check(self.lib.hc_get_wtd_hist(self.h, L.iptr(t), t.size))
+        return t
+
+    def set_wtd_hist_table(self, table):
+        t = np.asarray(table)
+        if t.size and (t.min() < 0 or t.max() > INT32_MAX):
+            raise ValueError("histogram counts must lie in [0, 2^31 - 1]")
+        t = np.ascontiguousarray(t, dtype=np.int32).reshape(-1)
+        L.check(self.lib.hc_set_wtd_hist_table(self.h, L.iptr(t), t.size))
+
+    def reset_wtd_hist(self):
+        L.check(self.lib.hc_reset_wtd_hist(self.h))
+
     # -- hooks ----------------------------------------------------------------------
     def spinup(self, zwtd_cm, z0_cm, forcing_row=0, max_iterations=1500):
         """Per-member ``Simulation.initial_conditions`` (simulation.py:389-493) in one launch: every member
@@ -413,6 +440,73 @@ def profile_tables_to_stats(table, P, T, D, stride, porosity, dz):
     out["rows"] = np.arange(parts["pcnt"].shape[1], dtype=np.int64) * int(stride)
     out["overflow"] = int(parts["ovf"][0])
     return out
+
+
+# ---- water-table distributions (include/hydrocol.h hc_set_wtd_hist, hc_wtd_distribution) -------------------------------
+WTD_MAX_LEVELS = 16
+INT32_MAX = (1 << 31) - 1
+
+
+def wtd_hist_slots(T, stride):
+    """Histogram rows of ``T`` forcing rows at ``stride``: rows 0, stride, 2 stride, ... < T."""
+    return (int(T) - 1) // int(stride) + 1
+
+
+def wtd_hist_rows(T, stride):
+    """The forcing row of each slot: slot j <-> row j stride (the profile rows of the same stride)."""
+    return np.arange(wtd_hist_slots(T, stride), dtype=np.int64) * int(stride)
+
+
+def place_points(local, point_ids, n_points):
+    """A rank's [p][...] tables in a zeroed int64 [n_points][...] table at rows ``point_ids``: summed over the ranks, the
+    parts give the whole sweep's table (every point has exactly one owner)."""
+    local = np.asarray(local)
+    out = np.zeros((int(n_points),) + local.shape[1:], dtype=np.int64)
+    if len(point_ids):
+        out[np.asarray(point_ids, dtype=np.int64)] = local
+    return out
+
+
+def wtd_distribution(hist, obs_idx, levels, dz, z, device=0, stride=1):
+    """Quantiles and CRPS of water-table histograms ``hist`` [..., n_hrow, D] (one table, or [P] of them) on the GPU
+    (``hc_wtd_distribution``).  ``obs_idx`` is the forcing's observation index of every row (``forcing.wtd_obs``); slot j
+    is row j ``stride``.  Returns ``rows`` [n_hrow], ``count`` [..., n_hrow], ``quantile_idx`` [..., n_hrow, L] (-1: no
+    member), ``quantile_cm`` (``z[idx]``, NaN for -1), ``crps_cm`` [..., n_hrow] (NaN: no member) and ``crps_mean_cm``
+    [...] (the mean over rows with members: the ensemble's analogue of the reference's MAE) and ``levels``."""
+    lib = L.load()
+    hist = np.asarray(hist)
+    if hist.ndim < 2:
+        raise ValueError(f"histograms must be [..., n_hrow, D], got shape {hist.shape}")
+    if hist.size and (hist.min() < 0 or hist.max() > INT32_MAX):
+        raise ValueError("histogram counts must lie in [0, 2^31 - 1]")
+    lv = np.ascontiguousarray(np.asarray(levels, dtype=np.float64).reshape(-1))
+    if lv.size > WTD_MAX_LEVELS or not np.all((lv >= 0.0) & (lv <= 1.0)):
+        raise ValueError(f"at most {WTD_MAX_LEVELS} quantile levels, each in [0, 1]: got {lv.tolist()}")
+    lead, n_hrow, D = hist.shape[:-2], hist.shape[-2], hist.shape[-1]
+    rows = np.arange(n_hrow, dtype=np.int64) * int(stride)
+    obs = np.asarray(obs_idx, dtype=np.int64).reshape(-1)
+    if rows.size and rows[-1] >= obs.size:
+        raise ValueError(f"{n_hrow} histogram rows at stride {stride} need {rows[-1] + 1} observations, got {obs.size}")
+    obs = np.ascontiguousarray(np.broadcast_to(obs[rows].astype(np.int32), lead + (n_hrow,)).reshape(-1))
+    h = np.ascontiguousarray(hist, dtype=np.int32).reshape(-1, D)
+    R = h.shape[0]
+    count = np.zeros(R, dtype=np.int64)
+    qidx = np.zeros((R, lv.size), dtype=np.int32)
+    crps = np.zeros(R, dtype=np.float64)
+    L.check(lib.hc_wtd_distribution(int(device), L.iptr(h), L.iptr(obs), R, D, L.dptr(lv), lv.size, float(dz),
+                                    L.lptr(count), L.iptr(qidx), L.dptr(crps)))
+    z = np.asarray(z, dtype=np.float64)
+    qcm = np.where(qidx >= 0, z[np.clip(qidx, 0, D - 1)], np.nan)
+    count, crps = count.reshape(lead + (n_hrow,)), crps.reshape(lead + (n_hrow,))
+    with np.errstate(invalid="ignore"):
+        solved = count > 0
+        crps_mean = np.where(solved.any(axis=-1), np.where(solved, crps, 0.0).sum(axis=-1) / np.maximum(solved.sum(axis=-1), 1),
+                             np.nan)
+    if not lead:
+        crps_mean = float(crps_mean)
+    return {"rows": rows, "count": count, "quantile_idx": qidx.reshape(lead + (n_hrow, lv.size)),
+            "quantile_cm": qcm.reshape(lead + (n_hrow, lv.size)), "crps_cm": crps, "crps_mean_cm": crps_mean,
+            "levels": lv}
 
 
 def allreduce_handles(steppers):

@@ -36,6 +36,9 @@
  *   hc_set_profile_stats, hc_profile_snapshot, hc_get/set/export/reset_profile_stats*, hc_get_profile_overflow
  *                      <- Simulation.run's science output (src/simulation.py:658-671) as ensemble mean / sigma:
  *                         psi_press, theta_vol (and S_eff on the host), transpiration, lateral_flow, abs_error
+ *   hc_set_wtd_hist, hc_get_wtd_hist, hc_set_wtd_hist_table, hc_reset_wtd_hist, hc_wtd_distribution
+ *                      <- wtd_est / abs_error per row (src/simulation.py:612-615) as the ensemble's distribution:
+ *                         per-row histograms of the water-table index, quantiles and the CRPS against the well
  *
  * Conventions: every function returns 0 on success or a negative hc_status; nothing throws
  * or aborts across the boundary; hc_last_error() gives the thread-local message.  Host
@@ -268,6 +271,41 @@ int hc_set_profile_stats_tables(hc_handle *h, const int64_t *table, int64_t n_wo
 int hc_export_profile_stats(hc_handle *h, void *device_dst, int64_t n_words);
 int hc_reset_profile_stats(hc_handle *h);
 int hc_get_profile_overflow(hc_handle *h, uint64_t *count);   /* the ovf slot */
+
+/* Ensemble water-table distribution: the reference's wtd_est = find_wtd(...) and abs_error = |zWtd_cm - z[wtd_est]| of one
+ * column (src/simulation.py:612-615) over the members of each parameter point, as exact integer histograms.
+ *   histogram rows r % stride == 0 (r < n_forcing_rows), n_hrow = (n_forcing_rows - 1) / stride + 1, slot j <-> row j stride
+ *   (the profile rows of hc_set_profile_stats).  Row 0 is the initial state: no water table is computed for it, its
+ *   histogram stays empty.  Skipped rows (wtd_obs < 0) count no members; spin-up solves accumulate nothing.
+ *   hist [P][n_hrow][D] int32: hist[p][j][b] = members of point p whose water-table index after row j stride's solve is b
+ *   (the index moments_kernel sums, hc_step_args.wtd_out).  Integer adds only: the table does not depend on launch length,
+ *   member split, point order or the number of handles / ranks summed.
+ * hc_set_wtd_hist: stride 0 = off (default); otherwise (re)creates the table zeroed.  Like the moment table it is re-created,
+ * zeroed, when the points, the forcing rows or the depth change.  HC_ERR_ARG for a table of more than HC_WTD_HIST_MAX_ENTRIES
+ * entries or a point of more than 2^31 - 1 members (a count must fit its int32 bin).  get / set take the table's size in
+ * entries (P n_hrow D) and fail on any other.  The step kernels are the same with the table on or off.
+ *
+ * hc_wtd_distribution: the summary of n_rows histograms of D bins (hist [n_rows][D], e.g. a [P][n_hrow][D] table summed over
+ * ranks, flattened) against obs_idx [n_rows], on `device`, for the caller's table (no handle: the points of a sweep
+ * assembled over ranks belong to no single handle).  Per row, with c_b the cumulative count and n = c_{D-1}:
+ *   count[r] = n;
+ *   quantile_idx[r][l] = the smallest b with c_b >= k, k = max(1, ceil(n levels[l])) in fp64: numpy.quantile(idx, q,
+ *     method="inverted_cdf") of the members' indices; -1 when n = 0;
+ *   crps_cm[r] = dz S / n^2, S = sum_{b=0}^{D-2} (c_b - n [b >= obs_idx[r]])^2: the CRPS of the ensemble's empirical CDF on the
+ *     grid against the observation, integral (F(x) - 1{x >= z_obs})^2 dx; for n = 1 exactly the reference's abs_error.  S is
+ *     an exact 128-bit integer; S / n^2 is formed in double-double and rounded once (within 1 ulp of dz S / n^2).  NaN when
+ *     n = 0 or obs_idx[r] is outside [0, D).
+ * Levels in [0, 1], at most HC_WTD_MAX_LEVELS of them; n_rows D <= HC_WTD_HIST_MAX_ENTRIES.  Host pointers in and out;
+ * complete on return. */
+#define HC_WTD_MAX_LEVELS 16
+#define HC_WTD_HIST_MAX_ENTRIES (1LL << 30)      /* 4 GiB of int32 bins */
+int hc_set_wtd_hist(hc_handle *h, int32_t stride);
+int hc_get_wtd_hist(hc_handle *h, int32_t *table, int64_t n_entries);
+int hc_set_wtd_hist_table(hc_handle *h, const int32_t *table, int64_t n_entries);   /* checkpoint / resume, rank sums */
+int hc_reset_wtd_hist(hc_handle *h);
+int hc_wtd_distribution(int device, const int32_t *hist, const int32_t *obs_idx, int64_t n_rows, int32_t D,
+                        const double *levels, int32_t n_levels, double dz, int64_t *count, int32_t *quantile_idx,
+                        double *crps_cm);
 
 /* The path's one collective inside the library, for a single process that drives several devices with
  * one handle each: every handle's moment table is replaced by the sum over all n handles (ncclAllReduce, ncclInt64,
