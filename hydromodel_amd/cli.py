@@ -164,13 +164,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
                              noise=str(ens.get("Noise", "philox")).lower(),
                              spinup=str(ens.get("Spinup", "shared")).lower(), profile_stride=stride,
                              wtd_hist_stride=dist_stride)
-    done = 0
-    while done < rows:
-        n = min(48 * 30, rows - done)
-        sim.advance(n)
-        done += n
-        if ranks.rank == 0:
-            print(f" [Ensemble x{n_members}{'' if ranks.world == 1 else f' on {ranks.world} GPUs'}] {done} rows done")
+    label = f"Ensemble x{n_members}"
+    _step_all(sim, rows, label, ranks)
     # the run's one collective: int64 (count, sum idx, sum idx^2) per row, exact and order-independent
     moments = ranks.allreduce_sum(np.asarray(sim.moments(), dtype=np.int64))
     mean_cm, std_cm = sim.wtd_mean_std(moments)
@@ -188,22 +183,13 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
         # one spin-up per member: the shards' initial conditions, assembled like a sweep's (zeros elsewhere, summed) when
         # the table is small enough to travel; otherwise rank 0's block, with its member range
         if n_members * psi0.shape[1] * 8 <= 256 * 1024 * 1024:
-            table = np.zeros((n_members, psi0.shape[1]))
-            table[lo:hi] = psi0
-            psi0 = ranks.allreduce_sum(table)
+            psi0 = multigpu.place_points(psi0, np.arange(lo, hi), n_members, ranks)
         else:
             extra["initial_cond_members"] = np.array([lo, hi])
-    if stride:
-        # the profile tables are int64 sums like the moments: one more exact all-reduce
-        extra.update(_profile_datasets(sim.profile_stats(ranks.allreduce_sum(sim.profile_table()))))
-    crps_line = None
-    if dist_stride:
-        # int32 counts, summed as int64 like the moments; rank 0 forms the summary
-        hist = ranks.allreduce_sum(sim.wtd_hist_table().astype(np.int64))
-        if ranks.rank == 0:
-            dist = sim.wtd_distribution(dist_levels, table=hist)
-            extra.update(_distribution_datasets(hist, dist))
-            crps_line = _crps_line(f"Ensemble x{n_members}", dist)
+    # the optional tables are integer sums like the moments: one more exact all-reduce each
+    tables, crps_line = _reduce_optional(ranks, sim, [0], [cols], forcing, stride, dist_stride, dist_levels, device,
+                                         label, keep_points=False)
+    extra.update(tables)
     arrays = dict(moments=moments, wtd_mean_cm=mean_cm, wtd_std_cm=std_cm, rows=np.array(rows),
                   members=np.array(n_members), gpus=np.array(ranks.world), initial_cond=psi0, **extra)
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "ensemble water-table statistics", ranks)
@@ -284,6 +270,53 @@ def _profile_datasets(stats):
     return out
 
 
+def _step_all(sim, rows, label, ranks):
+    """Advance `sim` over its first `rows` forcing rows, 30 days per call, each call followed by the progress line."""
+    where = "" if ranks.world == 1 else f" on {ranks.world} GPUs"
+    done = 0
+    while done < rows:
+        n = min(48 * 30, rows - done)
+        sim.advance(n)
+        done += n
+        if ranks.rank == 0:
+            print(f" [{label}{where}] {done} rows done")
+
+
+def _reduce_optional(ranks, sim, ids, cols_all, forcing, stride, dist_stride, dist_levels, device, label, keep_points):
+    """The run's optional tables -- profile statistics (``stride``), water-table histograms (``dist_stride``) -- from this
+    rank's handle ``sim`` (None: the rank holds no points), whose points are ``ids`` of the run's ``cols_all`` (an ensemble:
+    point 0 of 1), placed in the whole run's tables and summed over the ranks (``multigpu.place_points``).  Returns their
+    datasets (a sweep, ``keep_points``: with the leading [P] axis, at P = 1 too) and the closing CRPS line (rank 0, and
+    only with histograms; None otherwise)."""
+    import numpy as np
+    from .multigpu import place_points
+    from .stepper import (join_profile_table, profile_layout, profile_tables_to_stats, split_profile_table,
+                          wtd_distribution, wtd_hist_slots)
+    P, T, D, ref = len(cols_all), forcing.dim_t, cols_all[0].dim_d, cols_all[0]
+    out, crps_line = {}, None
+    if stride:
+        # the [P]-leading parts are placed at the points, the global overflow word is summed as it is
+        local = sim.profile_table() if sim is not None else np.zeros(profile_layout(0, T, D, stride)["words"][0], dtype=np.int64)
+        parts = split_profile_table(local, len(ids), T, D, stride)
+        table = ranks.allreduce_sum(join_profile_table({k: v if k == "ovf" else place_points(v, ids, P)
+                                                        for k, v in parts.items()}))
+        stats = profile_tables_to_stats(table, P, T, D, stride, np.stack([c.por_node for c in cols_all]), ref.dz)
+        if keep_points and P == 1:
+            stats = {k: (v[None] if isinstance(v, np.ndarray) and k != "rows" else v) for k, v in stats.items()}
+        out.update(_profile_datasets(stats))
+    if dist_stride:
+        # int32 counts, summed as int64 like the moments; rank 0 forms the summary
+        local = (sim.stepper.wtd_hist_table() if sim is not None else
+                 np.zeros((0, wtd_hist_slots(T, dist_stride), D), dtype=np.int32))
+        hist = place_points(local, ids, P, ranks)
+        hist = hist if keep_points else hist[0]
+        if ranks.rank == 0:
+            dist = wtd_distribution(hist, forcing.wtd_obs, dist_levels, ref.dz, ref.z, device, dist_stride)
+            out.update(_distribution_datasets(hist, dist))
+            crps_line = _crps_line(label, dist)
+    return out, crps_line
+
+
 def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride=0, dist_levels=None):
     """Parameter points x members: this rank's points in one handle (ensemble.SweepSimulation), the whole table assembled
     over the ranks (multigpu.assemble_points)."""
@@ -302,66 +335,30 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     merged = check_sweep_points(params, ens["Points"])
     P = len(merged)
     mine = deal_points(P, ranks.rank, ranks.world)
-    points = [ColumnTables(merged[k], well) for k in mine]
-    D, T = None, forcing.dim_t
-    local = {}
+    # every point's tables: a rank without points still joins the collectives (the grid is the well's, whoever owns it)
+    cols_all = [ColumnTables(m, well) for m in merged]
+    points, ref, T = [cols_all[k] for k in mine], cols_all[0], forcing.dim_t
+    local, sim = {}, None
     stride = _profile_stride(ens)
-    prof_local = hist_local = None
+    label = f"Sweep {P} points x{n_members}"
     if mine:
         sim = SweepSimulation(points, forcing, n_members, seed=int(ens.get("Seed", 0)), device=device, point_ids=mine,
                               profile_stride=stride, wtd_hist_stride=dist_stride)
-        done = 0
-        while done < rows:
-            n = min(48 * 30, rows - done)
-            sim.advance(n)
-            done += n
-            if ranks.rank == 0:
-                print(f" [Sweep {P} points x{n_members}{'' if ranks.world == 1 else f' on {ranks.world} GPUs'}] {done} rows done")
+        _step_all(sim, rows, label, ranks)
         table = sim.moments()
         for j, k in enumerate(mine):
             local[k] = {"moments": table[j], "psi0": sim.psi0[j],
                         "spinup_iterations": None if sim.spinup_iters is None else int(sim.spinup_iters[j])}
-        D = points[0].dim_d
-        if stride:
-            prof_local = sim.profile_table()
-        if dist_stride:
-            hist_local = sim.wtd_hist_table()
-        sim.close()
-    if D is None:        # a rank without points still joins the collectives: the grid is the well's, whoever owns it
-        D = ColumnTables(merged[0], well).dim_d
-    moments, psi0, spin = multigpu.assemble_points(ranks, P, local, T, D)
-    ref = points[0] if points else ColumnTables(merged[0], well)
+    moments, psi0, spin = multigpu.assemble_points(ranks, P, local, T, ref.dim_d)
     mean_cm, std_cm = moments_to_mean_std(moments, ref.dz, ref.z[0])
     arrays = dict(moments=moments, wtd_mean_cm=mean_cm, wtd_std_cm=std_cm, rows=np.array(rows),
                   members=np.array(n_members), points=np.array(P), gpus=np.array(ranks.world), initial_cond=psi0,
                   spinup_iterations=spin)
-    if stride:
-        # every rank places its points' parts in zeroed [P] tables; the sum over the ranks is the whole sweep's table
-        from .stepper import join_profile_table, profile_layout, profile_tables_to_stats, split_profile_table
-        parts = {k: np.zeros(sh, dtype=np.int64) for k, (_, sh) in profile_layout(P, T, D, stride).items() if k != "words"}
-        if prof_local is not None:
-            mine_parts = split_profile_table(prof_local, len(mine), T, D, stride)
-            for j, k in enumerate(mine):
-                for name in ("prof", "pcnt", "flux", "fcnt", "aerr"):
-                    parts[name][k] = mine_parts[name][j]
-            parts["ovf"][:] = mine_parts["ovf"]
-        table = ranks.allreduce_sum(join_profile_table(parts))
-        por = np.stack([(points[mine.index(k)] if k in mine else ColumnTables(merged[k], well)).por_node for k in range(P)])
-        stats = profile_tables_to_stats(table, P, T, D, stride, por, ref.dz)
-        if P == 1:       # keep the [P] axis of a sweep's datasets
-            stats = {k: (v[None] if isinstance(v, np.ndarray) and k != "rows" else v) for k, v in stats.items()}
-        arrays.update(_profile_datasets(stats))
-    crps_line = None
-    if dist_stride:
-        # as the profile table: every rank's points in a zeroed [P] table, summed over the ranks; rank 0 forms the summary
-        from .stepper import place_points, wtd_distribution, wtd_hist_slots
-        if hist_local is None:
-            hist_local = np.zeros((0, wtd_hist_slots(T, dist_stride), D), dtype=np.int32)
-        hist = ranks.allreduce_sum(place_points(hist_local, mine, P))
-        if ranks.rank == 0:
-            dist = wtd_distribution(hist, forcing.wtd_obs, dist_levels, ref.dz, ref.z, device, dist_stride)
-            arrays.update(_distribution_datasets(hist, dist))
-            crps_line = _crps_line(f"Sweep {P} points x{n_members}", dist)
+    tables, crps_line = _reduce_optional(ranks, sim, mine, cols_all, forcing, stride, dist_stride, dist_levels, device,
+                                         label, keep_points=True)
+    arrays.update(tables)
+    if sim is not None:
+        sim.close()
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "sweep's water-table statistics", ranks)
     if crps_line:
         print(crps_line)

@@ -71,6 +71,28 @@ struct DevBuf {
     }
 };
 
+// A table the handle accumulates over the members -- the per-row water-table moments, the profile statistics, the
+// water-table histograms: its device buffer and the shape key it was made for.  `ensure` re-creates it, zeroed, when the
+// key changed or after `invalidate`.
+template <typename T>
+struct AccTable {
+    const char *unit;            // what a size check counts: "words" or "entries"
+    DevBuf<T> buf;
+    int64_t key[3] = {-1, -1, -1};   // (key[0] = -1: no table)
+    int64_t n = 0;               // entries of the current table
+    int ensure(int64_t k0, int64_t k1, int64_t k2, int64_t count)
+    {
+        if (key[0] == k0 && key[1] == k1 && key[2] == k2) return HC_OK;
+        if (buf.ensure((size_t)count)) return HC_ERR_DEVICE;
+        HIP_TRY(hipMemset(buf.p, 0, (size_t)count * sizeof(T)));
+        key[0] = k0, key[1] = k1, key[2] = k2;
+        n = count;
+        return HC_OK;
+    }
+    void invalidate() { key[0] = -1; }
+    void release() { buf.release(), invalidate(); }
+};
+
 }  // namespace
 
 struct hc_handle {
@@ -85,7 +107,7 @@ struct hc_handle {
     bool force_generic = false;  // hc_set_generic_exponents: never take the specialised cell model
     bool use_special() const { return special && !force_generic; }
     // parameter points (BASELINE config 5): host copies, uploaded by fill_args when `points_dirty`
-    int n_points = 0, moments_points = 0;
+    int n_points = 0;
     std::vector<ColumnDev> P_host;
     std::vector<double> tab_host, node_host;
     bool points_dirty = false;
@@ -114,7 +136,7 @@ struct hc_handle {
     DevBuf<int> gtab, wtd_obs, draw_idx, stats, scratch_i;
     DevBuf<unsigned char> daylight, refresh;
     DevBuf<unsigned short> wtd_u16;
-    DevBuf<long long> moments;
+    AccTable<long long> moments{"words"};     // [P][3][T], keyed by the point count, reset by hc_set_forcing
     DevBuf<unsigned long long> counters;
     DevBuf<ColumnDev> Pdev;
     DevBuf<IoArgs> iodev;
@@ -133,17 +155,13 @@ struct hc_handle {
     uint64_t seed = 0;
     int64_t member_offset = 0;
     int rows_per_launch = 0;     // 0: chosen from the member count (auto_rows_per_launch)
-    // ensemble profile statistics (hc_set_profile_stats): one int64 table, layout in include/hydrocol.h; its shape is
-    // re-derived (and the table re-created, zeroed) when points, rows or depth change, like the moment table
+    // ensemble profile statistics (hc_set_profile_stats): one int64 table, layout in include/hydrocol.h, keyed by
+    // (points, rows, depth)
     int prof_stride = 0;         // 0: off
-    int prof_points = 0, prof_d = 0;
-    int64_t prof_t = 0;          // forcing rows the table was made for
-    DevBuf<long long> prof;
-    // ensemble water-table histograms (hc_set_wtd_hist): int32 [P][n_hrow][D], re-created like the profile table
+    AccTable<long long> prof{"words"};
+    // ensemble water-table histograms (hc_set_wtd_hist): int32 [P][n_hrow][D], keyed like the profile table
     int hist_stride = 0;         // 0: off
-    int hist_points = 0, hist_d = 0;
-    int64_t hist_t = 0;
-    DevBuf<int> hist;
+    AccTable<int> hist{"entries"};
     int n_cu = 256;
     double jac_reject = NUM_JAC_DIFF_REJECT;
 };
@@ -710,6 +728,81 @@ int launch_rhs(hc_handle *h, const StepArgs &A, long long row, double *dydt, dou
     return HC_OK;
 }
 
+// ------------------------------------------------------------------ accumulated tables (AccTable)
+// Each `ensure_*` applies the table's own rules, then has the table exist, zeroed, for the current shape key.
+// the moment tables exist once forcing and column are known: [n_points][3][n_rows]; hc_set_forcing resets them
+int ensure_moments(hc_handle *h)
+{
+    if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
+    return h->moments.ensure(h->n_points, 0, 0, (int64_t)h->n_points * 3 * h->n_rows);
+}
+
+// Word offsets of the profile-statistics table (include/hydrocol.h, hc_set_profile_stats)
+struct ProfLayout {
+    int64_t n_prow = 0, prof = 0, pcnt = 0, flux = 0, fcnt = 0, aerr = 0, ovf = 0, words = 0;
+};
+ProfLayout prof_layout(const hc_handle *h)
+{
+    ProfLayout L;
+    const int64_t P = h->n_points, T = h->n_rows, D = h->p.dim_d;
+    L.n_prow = (T - 1) / h->prof_stride + 1;
+    L.pcnt = L.prof + P * L.n_prow * D * 2 * HC_PROF_WORDS;
+    L.flux = L.pcnt + P * L.n_prow;
+    L.fcnt = L.flux + P * T * 2 * HC_PROF_WORDS;
+    L.aerr = L.fcnt + P * T;
+    L.ovf = L.aerr + P * T;
+    L.words = L.ovf + 1;
+    return L;
+}
+int ensure_prof(hc_handle *h)
+{
+    if (h->prof_stride <= 0) return fail(HC_ERR_ARG, "profile statistics are off (hc_set_profile_stats)");
+    if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
+    return h->prof.ensure(h->n_points, h->n_rows, h->p.dim_d, prof_layout(h).words);
+}
+
+// the water-table histogram table (hc_set_wtd_hist): [P][hist_rows][D] int32
+int64_t hist_rows(const hc_handle *h) { return (h->n_rows - 1) / h->hist_stride + 1; }
+int64_t hist_entries(const hc_handle *h) { return (int64_t)h->n_points * hist_rows(h) * h->p.dim_d; }
+int ensure_hist(hc_handle *h)
+{
+    if (h->hist_stride <= 0) return fail(HC_ERR_ARG, "water-table histograms are off (hc_set_wtd_hist)");
+    if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
+    if (h->n_members / std::max(h->n_points, 1) > INT32_MAX)
+        return fail(HC_ERR_ARG, "water-table histograms: %lld members per point do not fit an int32 bin",
+                    (long long)(h->n_members / std::max(h->n_points, 1)));
+    if (hist_entries(h) > HC_WTD_HIST_MAX_ENTRIES)
+        return fail(HC_ERR_ARG, "water-table histograms: %lld entries exceed HC_WTD_HIST_MAX_ENTRIES (take a longer stride)",
+                    (long long)hist_entries(h));
+    return h->hist.ensure(h->n_points, h->n_rows, h->p.dim_d, hist_entries(h));
+}
+
+// The bodies of the table entry points: the table as `ensure` leaves it (its rules and refusals), a size check when the
+// caller names one (n >= 0), the stream drained, one copy of the whole table: host -> table, table -> host or
+// table -> device memory elsewhere (`kind`).
+template <typename T>
+int table_copy(hc_handle *h, AccTable<T> &t, int (*ensure)(hc_handle *), hipMemcpyKind kind, void *other, int64_t n = -1,
+               const char *who = nullptr)
+{
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = ensure(h)) return rc;
+    if (n >= 0 && n != t.n)
+        return fail(HC_ERR_ARG, "%s: the table has %lld %s, not %lld", who, (long long)t.n, t.unit, (long long)n);
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const bool in = kind == hipMemcpyHostToDevice;
+    HIP_TRY(hipMemcpy(in ? (void *)t.buf.p : other, in ? other : (void *)t.buf.p, (size_t)t.n * sizeof(T), kind));
+    if (kind == hipMemcpyDeviceToDevice) HIP_TRY(hipDeviceSynchronize());
+    return HC_OK;
+}
+template <typename T>
+int table_reset(hc_handle *h, AccTable<T> &t, int (*ensure)(hc_handle *))
+{
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    t.invalidate();
+    return ensure(h);
+}
+
 int push_io(hc_handle *h)
 {
     HIP_TRY(hipMemcpyAsync(h->iodev.p, &h->io_host, sizeof(IoArgs), hipMemcpyHostToDevice, h->stream));
@@ -747,12 +840,7 @@ int fill_args(hc_handle *h, StepArgs &A)
         }
         h->points_dirty = false;
     }
-    if (h->moments_points != NP) {      // one [3][T] table per point, zeroed when the number of points changes
-        const size_t cnt = (size_t)NP * 3 * h->n_rows;
-        if (h->moments.ensure(cnt)) return HC_ERR_DEVICE;
-        HIP_TRY(hipMemset(h->moments.p, 0, cnt * 8));
-        h->moments_points = NP;
-    }
+    if (int rc = ensure_moments(h)) return rc;
     A.n_points = NP;
     A.members_per_point = h->n_members / NP;
     {
@@ -1105,7 +1193,7 @@ int hc_set_forcing(hc_handle *h, int64_t n_rows, const double *precip, const dou
     HIP_TRY(hipMemcpy(h->draw_idx.p, draw.data(), T * 4, hipMemcpyHostToDevice));
     h->h_refresh.assign(refresh, refresh + T);
     h->n_rows = n_rows;
-    h->moments_points = 0;       // (re)allocated and zeroed by the next call that needs the moment tables
+    h->moments.invalidate();     // (re)allocated and zeroed by the next call that needs the moment tables
     h->have_forcing = true;
     return HC_OK;
 }
@@ -1250,45 +1338,6 @@ static int auto_rows_per_launch(int64_t n_members, bool in_kernel_noise)
 }  // extern "C"
 
 namespace {
-// Word offsets of the profile-statistics table (include/hydrocol.h, hc_set_profile_stats)
-struct ProfLayout {
-    int64_t n_prow = 0, prof = 0, pcnt = 0, flux = 0, fcnt = 0, aerr = 0, ovf = 0, words = 0;
-};
-ProfLayout prof_layout(const hc_handle *h)
-{
-    ProfLayout L;
-    const int64_t P = h->n_points, T = h->n_rows, D = h->p.dim_d;
-    L.n_prow = (T - 1) / h->prof_stride + 1;
-    L.pcnt = L.prof + P * L.n_prow * D * 2 * HC_PROF_WORDS;
-    L.flux = L.pcnt + P * L.n_prow;
-    L.fcnt = L.flux + P * T * 2 * HC_PROF_WORDS;
-    L.aerr = L.fcnt + P * T;
-    L.ovf = L.aerr + P * T;
-    L.words = L.ovf + 1;
-    return L;
-}
-// the table exists, zeroed, for the current points / rows / depth (re-created when one of them changed)
-int ensure_prof(hc_handle *h)
-{
-    if (h->prof_stride <= 0) return fail(HC_ERR_ARG, "profile statistics are off (hc_set_profile_stats)");
-    if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
-    if (h->prof_points != h->n_points || h->prof_t != h->n_rows || h->prof_d != h->p.dim_d) {
-        const ProfLayout L = prof_layout(h);
-        if (h->prof.ensure((size_t)L.words)) return HC_ERR_DEVICE;
-        HIP_TRY(hipMemset(h->prof.p, 0, (size_t)L.words * 8));
-        h->prof_points = h->n_points;
-        h->prof_t = h->n_rows;
-        h->prof_d = h->p.dim_d;
-    }
-    return HC_OK;
-}
-int prof_words_check(hc_handle *h, int64_t n_words, const char *who)
-{
-    if (int rc = ensure_prof(h)) return rc;
-    const int64_t want = prof_layout(h).words;
-    if (n_words != want) return fail(HC_ERR_ARG, "%s: the table has %lld words, not %lld", who, (long long)want, (long long)n_words);
-    return HC_OK;
-}
 // staging of a launch with profile statistics: transpiration / lateral flow of every row (at most 1 GiB) and, for short
 // strides, the end-of-row states of every row; about 4 GiB at most, a launch stages at least one row whatever the size
 constexpr int64_t PROF_STAGE_BYTES = int64_t(4) << 30, PROF_DIAG_BYTES = int64_t(1) << 30;
@@ -1299,7 +1348,7 @@ int launch_profile(hc_handle *h, const StepArgs &A, const ProfLayout &L, const d
     const long long mpp = h->n_members / h->n_points;
     const dim3 grid((unsigned)((h->p.dim_d + PROF_TILE - 1) / PROF_TILE),
                     (unsigned)((mpp + PROF_MEMBERS_PER_BLOCK - 1) / PROF_MEMBERS_PER_BLOCK), (unsigned)h->n_points);
-    long long *t = h->prof.p;
+    long long *t = h->prof.buf.p;
     hipLaunchKernelGGL(profile_kernel, grid, dim3(PROF_TILE * PROF_WAVES), 0, h->stream, A, h->node_tabs.p,
                        (int)h->use_special(), stage, h->wtd_obs.p, (long long)row, (long long)(row / h->prof_stride),
                        (long long)L.n_prow, snapshot, PROF_MEMBERS_PER_BLOCK, t + L.prof, t + L.pcnt,
@@ -1308,37 +1357,6 @@ int launch_profile(hc_handle *h, const StepArgs &A, const ProfLayout &L, const d
     return HC_OK;
 }
 
-// the water-table histogram table (hc_set_wtd_hist): its entries, and the table itself, zeroed, for the current points /
-// rows / depth (re-created when one of them changed)
-int64_t hist_rows(const hc_handle *h) { return (h->n_rows - 1) / h->hist_stride + 1; }
-int64_t hist_entries(const hc_handle *h) { return (int64_t)h->n_points * hist_rows(h) * h->p.dim_d; }
-int ensure_hist(hc_handle *h)
-{
-    if (h->hist_stride <= 0) return fail(HC_ERR_ARG, "water-table histograms are off (hc_set_wtd_hist)");
-    if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
-    if (h->n_members / std::max(h->n_points, 1) > INT32_MAX)
-        return fail(HC_ERR_ARG, "water-table histograms: %lld members per point do not fit an int32 bin",
-                    (long long)(h->n_members / std::max(h->n_points, 1)));
-    if (hist_entries(h) > HC_WTD_HIST_MAX_ENTRIES)
-        return fail(HC_ERR_ARG, "water-table histograms: %lld entries exceed HC_WTD_HIST_MAX_ENTRIES (take a longer stride)",
-                    (long long)hist_entries(h));
-    if (h->hist_points != h->n_points || h->hist_t != h->n_rows || h->hist_d != h->p.dim_d) {
-        const size_t n = (size_t)hist_entries(h);
-        if (h->hist.ensure(n)) return HC_ERR_DEVICE;
-        HIP_TRY(hipMemset(h->hist.p, 0, n * 4));
-        h->hist_points = h->n_points;
-        h->hist_t = h->n_rows;
-        h->hist_d = h->p.dim_d;
-    }
-    return HC_OK;
-}
-int hist_entries_check(hc_handle *h, int64_t n_entries, const char *who)
-{
-    if (int rc = ensure_hist(h)) return rc;
-    if (n_entries != hist_entries(h))
-        return fail(HC_ERR_ARG, "%s: the table has %lld entries, not %lld", who, (long long)hist_entries(h), (long long)n_entries);
-    return HC_OK;
-}
 constexpr long long HIST_MEMBERS_PER_BLOCK = 4096;
 
 // the histogram rows among launch rows [row0, row0 + chunk) of the water-table indices in wtd_u16
@@ -1354,7 +1372,7 @@ int launch_hist(hc_handle *h, int64_t row0, int chunk)
     const long long slices = (mpp + mpb - 1) / mpb;
     hipLaunchKernelGGL(wtd_hist_kernel, dim3((unsigned)(n_here * slices), (unsigned)h->n_points), dim3(HIST_THREADS), 0,
                        h->stream, h->wtd_u16.p, h->wtd_obs.p, (long long)h->n_members, mpp, mpb, (int)slices,
-                       (long long)row0, (int)first, (int)s, (long long)hist_rows(h), h->p.dim_d, h->hist.p);
+                       (long long)row0, (int)first, (int)s, (long long)hist_rows(h), h->p.dim_d, h->hist.buf.p);
     HIP_TRY(hipGetLastError());
     return HC_OK;
 }
@@ -1380,6 +1398,169 @@ int wtd_distribution_run(const int32_t *hist, const int32_t *obs_idx, int64_t n_
     HIP_TRY(hipMemcpy(crps_cm, d_crps.p, R * 8, hipMemcpyDeviceToHost));
     return HC_OK;
 }
+
+// ------------------------------------------------------------------ hc_step_rows, one launch at a time
+// The rows of one launch and where its profile rows are read from.
+struct Chunk {
+    int64_t row0 = 0;             // first forcing row
+    int rows = 0;
+    bool stage_all = false;       // the end states of every row are staged through psi_rows
+    bool end_on_profile = false;  // the launch ends ON a profile row: its states are the members' current states
+};
+
+// The launch after `done` rows of the request.  Per-row outputs are staged in device buffers of rows x members entries:
+// a caller that asks for them gets shorter launches, so that the largest (psi_rows: 8 D bytes per member-row) stays
+// within ~1 GiB however long the request.  Profile rows (the step kernels are not changed for them; results do not
+// depend on launch length):
+//  stride >= the rows the staging cap admits: the launch ends ON the next profile row, whose states are then the
+//    members' current states (no staging at all);
+//  shorter strides: every row of the launch is staged through psi_rows (as psi_rows_out does), the launch
+//    shortened to the cap, and the profile rows are read from there.
+Chunk plan_chunk(const hc_handle *h, const hc_step_args *a, int64_t done, bool prof_on)
+{
+    const int64_t N = h->n_members, D = h->p.dim_d;
+    int64_t out_bytes_per_row = 0;
+    if (a->psi_rows_out) out_bytes_per_row += N * D * 8;
+    if (a->stats_out) out_bytes_per_row += N * 6 * 4;
+    if (a->diag_out) out_bytes_per_row += N * 2 * 8;
+    if (a->wtd_out) out_bytes_per_row += N * 4;
+    const int64_t rows_cap = out_bytes_per_row > 0 ? std::max<int64_t>(1, (int64_t(1) << 30) / out_bytes_per_row) : INT32_MAX;
+    int per_launch = h->rows_per_launch > 0 ? h->rows_per_launch : auto_rows_per_launch(N, h->philox);
+    if (h->rows_per_launch <= 0) per_launch = (int)std::min<int64_t>(per_launch, rows_cap);
+    Chunk c;
+    c.rows = (int)std::min<int64_t>(per_launch, a->n_rows - done);
+    c.row0 = a->spinup ? a->row_begin : a->row_begin + done;
+    if (!prof_on) return c;
+    const int64_t s = h->prof_stride, diag_row = N * 2 * 8, row_bytes = N * D * 8;
+    c.rows = (int)std::min<int64_t>(c.rows, std::max<int64_t>(1, PROF_DIAG_BYTES / diag_row));
+    const int64_t cap_rows = std::max<int64_t>(1, (PROF_STAGE_BYTES - (int64_t)c.rows * diag_row) / row_bytes);
+    if (a->psi_rows_out) {
+        c.stage_all = true;       // every row is staged for the caller already
+    } else if (s >= cap_rows) {
+        const int64_t next = (c.row0 + s - 1) / s * s;
+        c.rows = (int)std::min<int64_t>(c.rows, next - c.row0 + 1);
+        c.end_on_profile = (c.row0 + c.rows - 1) % s == 0;
+    } else {
+        c.rows = (int)std::min<int64_t>(c.rows, cap_rows);
+        c.stage_all = true;
+    }
+    return c;
+}
+
+// the caller's noise vectors of the launch's refresh rows, on the device (host noise); n_fresh: how many
+int stage_noise(hc_handle *h, const hc_step_args *a, const Chunk &c, int64_t consumed, int &n_fresh)
+{
+    const int64_t N = h->n_members, D = h->p.dim_d;
+    n_fresh = 0;
+    if (!a->spinup)
+        for (int r = 0; r < c.rows; r++) n_fresh += h->h_refresh[(size_t)(c.row0 + r)] ? 1 : 0;
+    if (h->philox || n_fresh == 0) return HC_OK;
+    if (!a->fresh_noise) return fail(HC_ERR_ARG, "host noise mode: fresh_noise is NULL but rows refresh");
+    const size_t cnt = (size_t)n_fresh * N * D;
+    if (h->fresh.ensure(cnt)) return HC_ERR_DEVICE;
+    HIP_TRY(hipMemcpyAsync(h->fresh.p, a->fresh_noise + (size_t)consumed * N * D, cnt * 8, hipMemcpyHostToDevice, h->stream));
+    return HC_OK;
+}
+
+// the launch's staging buffers and IoArgs, the points' walk order, and the step kernel between the two timing events
+int launch_chunk(hc_handle *h, StepArgs &A, const hc_step_args *a, const Chunk &c, bool prof_on)
+{
+    const int64_t N = h->n_members, D = h->p.dim_d;
+    const size_t rows = (size_t)c.rows;
+    if (h->wtd_u16.ensure(rows * N)) return HC_ERR_DEVICE;
+    if (a->stats_out && h->stats.ensure(rows * N * 6)) return HC_ERR_DEVICE;
+    if (a->psi_rows_out && h->psi_rows.ensure(rows * N * D)) return HC_ERR_DEVICE;
+    if ((a->diag_out || prof_on) && h->diag.ensure(rows * N * 2)) return HC_ERR_DEVICE;
+    if (c.stage_all && h->psi_rows.ensure(rows * N * D)) return HC_ERR_DEVICE;
+    h->io_host.fresh = h->fresh.p;
+    h->io_host.row_begin = c.row0;
+    A.n_rows = c.rows;
+    A.spinup = a->spinup;
+    h->io_host.wtd_u16 = h->wtd_u16.p;
+    h->io_host.stats = a->stats_out ? h->stats.p : nullptr;
+    h->io_host.psi_rows = (a->psi_rows_out || c.stage_all) ? h->psi_rows.p : nullptr;
+    h->io_host.diag = (a->diag_out || prof_on) ? h->diag.p : nullptr;
+    if (int rc = push_io(h)) return rc;
+    if (h->n_points > 1) {
+        HIP_TRY(hipMemcpyAsync(h->point_order.p, h->order_host.data(), (size_t)h->n_points * 4, hipMemcpyHostToDevice,
+                               h->stream));
+        HIP_TRY(hipMemsetAsync(h->point_cost.p, 0, (size_t)h->n_points * 8, h->stream));
+    }
+    HIP_TRY(hipEventRecord(h->ev0, h->stream));
+    if (int rc = launch_step(h, A)) return rc;
+    HIP_TRY(hipEventRecord(h->ev1, h->stream));
+    return HC_OK;
+}
+
+// what the launch adds to the accumulated tables: moments, histograms, profile rows and fluxes
+int accumulate(hc_handle *h, const StepArgs &A, const hc_step_args *a, const Chunk &c, bool prof_on, bool hist_on)
+{
+    const int64_t N = h->n_members, D = h->p.dim_d;
+    if (a->accumulate_moments) {
+        hipLaunchKernelGGL(moments_kernel, dim3(c.rows, h->n_points), dim3(256), 0, h->stream, h->wtd_u16.p,
+                           h->wtd_obs.p, (long long)N, (long long)(N / h->n_points), (long long)c.row0,
+                           (long long)h->n_rows, h->moments.buf.p);
+        HIP_TRY(hipGetLastError());
+    }
+    if (hist_on)
+        if (int rc = launch_hist(h, c.row0, c.rows)) return rc;
+    if (!prof_on) return HC_OK;
+    const ProfLayout PL = prof_layout(h);
+    for (int r = 0; r < c.rows; r++) {
+        if ((c.row0 + r) % h->prof_stride != 0) continue;
+        const double *stage = c.stage_all ? h->psi_rows.p + (size_t)r * N * D : h->psi.p;
+        if (!c.stage_all && !(c.end_on_profile && r == c.rows - 1))
+            return fail(HC_ERR_DEVICE, "profile row %lld not staged (internal error)", (long long)(c.row0 + r));
+        if (int rc = launch_profile(h, A, PL, stage, c.row0 + r, 0)) return rc;
+    }
+    long long *t = h->prof.buf.p;
+    hipLaunchKernelGGL(flux_stats_kernel, dim3(c.rows, h->n_points), dim3(256), 0, h->stream, h->diag.p, h->wtd_u16.p,
+                       h->wtd_obs.p, (long long)N, (long long)(N / h->n_points), (long long)c.row0,
+                       (long long)h->n_rows, t + PL.flux, t + PL.fcnt, t + PL.aerr,
+                       reinterpret_cast<unsigned long long *>(t + PL.ovf));
+    HIP_TRY(hipGetLastError());
+    return HC_OK;
+}
+
+// the per-row outputs the caller asked for: rows [done, done + c.rows) of its arrays
+int copy_outputs(hc_handle *h, hc_step_args *a, const Chunk &c, int64_t done)
+{
+    const int64_t N = h->n_members, D = h->p.dim_d;
+    const size_t rows = (size_t)c.rows;
+    if (a->wtd_out) {
+        const size_t cnt = rows * N;
+        if (h->scratch_i.ensure(cnt)) return HC_ERR_DEVICE;
+        hipLaunchKernelGGL(widen_u16, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, h->wtd_u16.p,
+                           h->scratch_i.p, cnt);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(a->wtd_out + (size_t)done * N, h->scratch_i.p, cnt * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (a->stats_out)
+        HIP_TRY(hipMemcpyAsync(a->stats_out + (size_t)done * N * 6, h->stats.p, rows * N * 6 * 4, hipMemcpyDeviceToHost,
+                               h->stream));
+    if (a->psi_rows_out)
+        HIP_TRY(hipMemcpyAsync(a->psi_rows_out + (size_t)done * N * D, h->psi_rows.p, rows * N * D * 8,
+                               hipMemcpyDeviceToHost, h->stream));
+    if (a->diag_out)
+        HIP_TRY(hipMemcpyAsync(a->diag_out + (size_t)done * N * 2, h->diag.p, rows * N * 2 * 8, hipMemcpyDeviceToHost,
+                               h->stream));
+    return HC_OK;
+}
+
+// After the launches of a call: a split-column mailbox exchange that timed out invalidates the results.  An attempt that
+// exhausts the kernel's iteration budget is abandoned like a solve that gave up (the x0.8 retry rule applies); it is
+// counted ([2], last place in [3]) and only fatal on request.
+int check_counters(hc_handle *h)
+{
+    unsigned long long cnt[6];
+    HIP_TRY(hipMemcpy(cnt, h->counters.p, sizeof(cnt), hipMemcpyDeviceToHost));
+    if (cnt[5] != 0)
+        return fail(HC_ERR_DEVICE, "split-column kernel: %llu mailbox exchanges timed out (internal error; results are invalid)", cnt[5]);
+    if (cnt[2] != 0 && h->strict_guard)
+        return fail(HC_ERR_DEVICE, "%llu BDF attempts hit the kernel's iteration guard (last: member %llu, row %llu)",
+                    cnt[2], cnt[3] >> 24, cnt[3] & 0xFFFFFFull);
+    return HC_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1400,137 +1581,27 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
                     (long long)(a->row_begin + a->n_rows), (long long)h->n_rows);
     }
     HIP_TRY(hipSetDevice(h->device));
-    const int D = h->p.dim_d;
-    const int64_t N = h->n_members;
     a->kernel_ms = 0.0;
     a->launches = 0;
+    // profile statistics (hc_set_profile_stats) and water-table histograms (hc_set_wtd_hist, read from wtd_u16 after
+    // each launch): spin-up solves accumulate nothing
+    const bool prof_on = h->prof_stride > 0 && !a->spinup, hist_on = h->hist_stride > 0 && !a->spinup;
+    if ((prof_on && (rc = ensure_prof(h))) || (hist_on && (rc = ensure_hist(h)))) return rc;
     int64_t fresh_consumed = 0;
-    // Per-row outputs are staged in device buffers of rows x members entries: a caller that asks for them gets shorter
-    // launches, so that the largest (psi_rows: 8 D bytes per member-row) stays within ~1 GiB however long the request.
-    int64_t out_bytes_per_row = 0;
-    if (a->psi_rows_out) out_bytes_per_row += N * (int64_t)D * 8;
-    if (a->stats_out) out_bytes_per_row += N * 6 * 4;
-    if (a->diag_out) out_bytes_per_row += N * 2 * 8;
-    if (a->wtd_out) out_bytes_per_row += N * 4;
-    const int64_t rows_cap = out_bytes_per_row > 0 ? std::max<int64_t>(1, (int64_t(1) << 30) / out_bytes_per_row) : INT32_MAX;
-    // profile statistics (hc_set_profile_stats): spin-up solves accumulate nothing
-    const bool prof_on = h->prof_stride > 0 && !a->spinup;
-    ProfLayout PL;
-    if (prof_on) {
-        if (int rc2 = ensure_prof(h)) return rc2;
-        PL = prof_layout(h);
-    }
-    // water-table histograms (hc_set_wtd_hist): read from wtd_u16 after each launch; spin-up solves accumulate nothing
-    const bool hist_on = h->hist_stride > 0 && !a->spinup;
-    if (hist_on)
-        if (int rc2 = ensure_hist(h)) return rc2;
     for (int64_t done = 0; done < a->n_rows;) {
-        int per_launch = h->rows_per_launch > 0 ? h->rows_per_launch : auto_rows_per_launch(N, h->philox);
-        if (h->rows_per_launch <= 0) per_launch = (int)std::min<int64_t>(per_launch, rows_cap);
-        int chunk = (int)std::min<int64_t>(per_launch, a->n_rows - done);
-        const int64_t row0 = a->spinup ? a->row_begin : a->row_begin + done;
-        // Profile rows of this launch (the step kernels are not changed for them; results do not depend on launch length):
-        //  stride >= the rows the staging cap admits: the launch ends ON the next profile row, whose states are then the
-        //    members' current states (no staging at all);
-        //  shorter strides: every row of the launch is staged through psi_rows (as psi_rows_out does), the launch
-        //    shortened to the cap, and the profile rows are read from there.
-        bool stage_all = false, end_on_profile = false;
-        if (prof_on) {
-            const int64_t s = h->prof_stride, diag_row = N * 2 * 8, row_bytes = N * (int64_t)D * 8;
-            chunk = (int)std::min<int64_t>(chunk, std::max<int64_t>(1, PROF_DIAG_BYTES / diag_row));
-            const int64_t cap_rows = std::max<int64_t>(1, (PROF_STAGE_BYTES - (int64_t)chunk * diag_row) / row_bytes);
-            if (a->psi_rows_out) {
-                stage_all = true;       // every row is staged for the caller already
-            } else if (s >= cap_rows) {
-                const int64_t next = (row0 + s - 1) / s * s;
-                chunk = (int)std::min<int64_t>(chunk, next - row0 + 1);
-                end_on_profile = (row0 + chunk - 1) % s == 0;
-            } else {
-                chunk = (int)std::min<int64_t>(chunk, cap_rows);
-                stage_all = true;
-            }
-        }
+        const Chunk c = plan_chunk(h, a, done, prof_on);
         int n_fresh = 0;
-        if (!a->spinup)
-            for (int r = 0; r < chunk; r++) n_fresh += h->h_refresh[(size_t)(row0 + r)] ? 1 : 0;
-        if (!h->philox && n_fresh > 0) {
-            if (!a->fresh_noise) return fail(HC_ERR_ARG, "host noise mode: fresh_noise is NULL but rows refresh");
-            const size_t cnt = (size_t)n_fresh * N * D;
-            if (h->fresh.ensure(cnt)) return HC_ERR_DEVICE;
-            HIP_TRY(hipMemcpyAsync(h->fresh.p, a->fresh_noise + (size_t)fresh_consumed * N * D, cnt * 8,
-                                   hipMemcpyHostToDevice, h->stream));
-        }
-        if (h->wtd_u16.ensure((size_t)chunk * N)) return HC_ERR_DEVICE;
-        if (a->stats_out && h->stats.ensure((size_t)chunk * N * 6)) return HC_ERR_DEVICE;
-        if (a->psi_rows_out && h->psi_rows.ensure((size_t)chunk * N * D)) return HC_ERR_DEVICE;
-        if ((a->diag_out || prof_on) && h->diag.ensure((size_t)chunk * N * 2)) return HC_ERR_DEVICE;
-        if (stage_all && h->psi_rows.ensure((size_t)chunk * N * D)) return HC_ERR_DEVICE;
-        h->io_host.fresh = h->fresh.p;
-        h->io_host.row_begin = row0;
-        A.n_rows = chunk;
-        A.spinup = a->spinup;
-        h->io_host.wtd_u16 = h->wtd_u16.p;
-        h->io_host.stats = a->stats_out ? h->stats.p : nullptr;
-        h->io_host.psi_rows = (a->psi_rows_out || stage_all) ? h->psi_rows.p : nullptr;
-        h->io_host.diag = (a->diag_out || prof_on) ? h->diag.p : nullptr;
-        rc = push_io(h);
-        if (rc) return rc;
-        if (h->n_points > 1) {
-            HIP_TRY(hipMemcpyAsync(h->point_order.p, h->order_host.data(), (size_t)h->n_points * 4, hipMemcpyHostToDevice,
-                                   h->stream));
-            HIP_TRY(hipMemsetAsync(h->point_cost.p, 0, (size_t)h->n_points * 8, h->stream));
-        }
-        HIP_TRY(hipEventRecord(h->ev0, h->stream));
-        rc = launch_step(h, A);
-        if (rc) return rc;
-        HIP_TRY(hipEventRecord(h->ev1, h->stream));
-        if (a->accumulate_moments) {
-            hipLaunchKernelGGL(moments_kernel, dim3(chunk, h->n_points), dim3(256), 0, h->stream, h->wtd_u16.p,
-                               h->wtd_obs.p, (long long)N, (long long)(N / h->n_points), (long long)row0,
-                               (long long)h->n_rows, h->moments.p);
-            HIP_TRY(hipGetLastError());
-        }
-        if (hist_on)
-            if (int rc2 = launch_hist(h, row0, chunk)) return rc2;
-        if (prof_on) {
-            for (int r = 0; r < chunk; r++) {
-                if ((row0 + r) % h->prof_stride != 0) continue;
-                const double *stage = stage_all ? h->psi_rows.p + (size_t)r * N * D : h->psi.p;
-                if (!stage_all && !(end_on_profile && r == chunk - 1)) return fail(HC_ERR_DEVICE, "profile row %lld not staged (internal error)", (long long)(row0 + r));
-                if (int rc2 = launch_profile(h, A, PL, stage, row0 + r, 0)) return rc2;
-            }
-            long long *t = h->prof.p;
-            hipLaunchKernelGGL(flux_stats_kernel, dim3(chunk, h->n_points), dim3(256), 0, h->stream, h->diag.p, h->wtd_u16.p,
-                               h->wtd_obs.p, (long long)N, (long long)(N / h->n_points), (long long)row0,
-                               (long long)h->n_rows, t + PL.flux, t + PL.fcnt, t + PL.aerr,
-                               reinterpret_cast<unsigned long long *>(t + PL.ovf));
-            HIP_TRY(hipGetLastError());
-        }
-        if (a->wtd_out) {
-            const size_t cnt = (size_t)chunk * N;
-            if (h->scratch_i.ensure(cnt)) return HC_ERR_DEVICE;
-            hipLaunchKernelGGL(widen_u16, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, h->wtd_u16.p,
-                               h->scratch_i.p, cnt);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(a->wtd_out + (size_t)done * N, h->scratch_i.p, cnt * 4, hipMemcpyDeviceToHost,
-                                   h->stream));
-        }
-        if (a->stats_out)
-            HIP_TRY(hipMemcpyAsync(a->stats_out + (size_t)done * N * 6, h->stats.p, (size_t)chunk * N * 6 * 4,
-                                   hipMemcpyDeviceToHost, h->stream));
-        if (a->psi_rows_out)
-            HIP_TRY(hipMemcpyAsync(a->psi_rows_out + (size_t)done * N * D, h->psi_rows.p, (size_t)chunk * N * D * 8,
-                                   hipMemcpyDeviceToHost, h->stream));
-        if (a->diag_out)
-            HIP_TRY(hipMemcpyAsync(a->diag_out + (size_t)done * N * 2, h->diag.p, (size_t)chunk * N * 2 * 8,
-                                   hipMemcpyDeviceToHost, h->stream));
+        if ((rc = stage_noise(h, a, c, fresh_consumed, n_fresh))) return rc;
+        if ((rc = launch_chunk(h, A, a, c, prof_on))) return rc;
+        if ((rc = accumulate(h, A, a, c, prof_on, hist_on))) return rc;
+        if ((rc = copy_outputs(h, a, c, done))) return rc;
         HIP_TRY(hipStreamSynchronize(h->stream));
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
         a->kernel_ms += ms;
         a->launches++;
         fresh_consumed += n_fresh;
-        done += chunk;
+        done += c.rows;
         if (h->n_points > 1 && !a->spinup) {
             // what each point cost in this launch orders the next one: costliest point first (results do not depend on it)
             std::vector<unsigned long long> cost((size_t)h->n_points);
@@ -1541,16 +1612,7 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
                                  [&](int x, int y) { return cost[(size_t)x] > cost[(size_t)y]; });
         }
     }
-    unsigned long long cnt[6];
-    HIP_TRY(hipMemcpy(cnt, h->counters.p, sizeof(cnt), hipMemcpyDeviceToHost));
-    if (cnt[5] != 0)
-        return fail(HC_ERR_DEVICE, "split-column kernel: %llu mailbox exchanges timed out (internal error; results are invalid)", cnt[5]);
-    // An attempt that exhausts the kernel's iteration budget is abandoned like a solve that gave up (the x0.8
-    // retry rule applies); it is counted ([2], last place in [3]) and only fatal on request.
-    if (cnt[2] != 0 && h->strict_guard)
-        return fail(HC_ERR_DEVICE, "%llu BDF attempts hit the kernel's iteration guard (last: member %llu, row %llu)",
-                    cnt[2], cnt[3] >> 24, cnt[3] & 0xFFFFFFull);
-    return HC_OK;
+    return check_counters(h);
 }
 
 int hc_spinup(hc_handle *h, hc_spinup_args *a)
@@ -1583,16 +1645,7 @@ int hc_spinup(hc_handle *h, hc_spinup_args *a)
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
     a->kernel_ms = ms;
-    unsigned long long cnt[6];
-    HIP_TRY(hipMemcpy(cnt, h->counters.p, sizeof(cnt), hipMemcpyDeviceToHost));
-    if (cnt[5] != 0)
-        return fail(HC_ERR_DEVICE, "split-column kernel: %llu mailbox exchanges timed out (internal error; results are invalid)", cnt[5]);
-    // An attempt that exhausts the kernel's iteration budget is abandoned like a solve that gave up (the x0.8
-    // retry rule applies); it is counted ([2], last place in [3]) and only fatal on request.
-    if (cnt[2] != 0 && h->strict_guard)
-        return fail(HC_ERR_DEVICE, "%llu BDF attempts hit the kernel's iteration guard (last: member %llu, row %llu)",
-                    cnt[2], cnt[3] >> 24, cnt[3] & 0xFFFFFFull);
-    return HC_OK;
+    return check_counters(h);
 }
 
 int hc_get_counters(hc_handle *h, uint64_t *out4)
@@ -1644,55 +1697,28 @@ int hc_synchronize(hc_handle *h)
     return HC_OK;
 }
 
-// the moment tables exist once forcing and column are known: [n_points][3][n_rows]
-static int ensure_moments(hc_handle *h)
-{
-    if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
-    if (h->moments_points != h->n_points) {
-        const size_t cnt = (size_t)h->n_points * 3 * h->n_rows;
-        if (h->moments.ensure(cnt)) return HC_ERR_DEVICE;
-        HIP_TRY(hipMemset(h->moments.p, 0, cnt * 8));
-        h->moments_points = h->n_points;
-    }
-    return HC_OK;
-}
-
 int hc_get_moments(hc_handle *h, int64_t *moments)
 {
     if (!h || !moments) return fail(HC_ERR_ARG, "hc_get_moments: bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    if (int rc = ensure_moments(h)) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(moments, h->moments.p, (size_t)h->n_points * 3 * h->n_rows * 8, hipMemcpyDeviceToHost));
-    return HC_OK;
+    return table_copy(h, h->moments, ensure_moments, hipMemcpyDeviceToHost, moments);
 }
 
 int hc_export_moments(hc_handle *h, void *device_dst)
 {
     if (!h || !device_dst) return fail(HC_ERR_ARG, "hc_export_moments: bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    if (int rc = ensure_moments(h)) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(device_dst, h->moments.p, (size_t)h->n_points * 3 * h->n_rows * 8, hipMemcpyDeviceToDevice));
-    HIP_TRY(hipDeviceSynchronize());
-    return HC_OK;
+    return table_copy(h, h->moments, ensure_moments, hipMemcpyDeviceToDevice, device_dst);
 }
 
 int hc_set_moments(hc_handle *h, const int64_t *moments)
 {
     if (!h || !moments) return fail(HC_ERR_ARG, "hc_set_moments: bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    if (int rc = ensure_moments(h)) return rc;
-    HIP_TRY(hipMemcpy(h->moments.p, moments, (size_t)h->n_points * 3 * h->n_rows * 8, hipMemcpyHostToDevice));
-    return HC_OK;
+    return table_copy(h, h->moments, ensure_moments, hipMemcpyHostToDevice, const_cast<int64_t *>(moments));
 }
 
 int hc_reset_moments(hc_handle *h)
 {
     if (!h) return fail(HC_ERR_ARG, "hc_reset_moments: bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    h->moments_points = 0;
-    return ensure_moments(h);
+    return table_reset(h, h->moments, ensure_moments);
 }
 
 int hc_set_profile_stats(hc_handle *h, int32_t stride)
@@ -1702,19 +1728,15 @@ int hc_set_profile_stats(hc_handle *h, int32_t stride)
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->prof_stride = stride;
-    h->prof_points = 0;          // re-created, zeroed
-    if (stride == 0) {
-        h->prof.release();
-        return HC_OK;
-    }
-    return ensure_prof(h);
+    h->prof.release();           // re-created, zeroed, when on
+    return stride == 0 ? HC_OK : ensure_prof(h);
 }
 
 int hc_get_profile_stats_words(hc_handle *h, int64_t *n_words)
 {
     if (!h || !n_words) return fail(HC_ERR_ARG, "hc_get_profile_stats_words: bad argument");
     if (int rc = ensure_prof(h)) return rc;
-    *n_words = prof_layout(h).words;
+    *n_words = h->prof.n;
     return HC_OK;
 }
 
@@ -1737,41 +1759,26 @@ int hc_profile_snapshot(hc_handle *h, int64_t row)
 int hc_get_profile_stats(hc_handle *h, int64_t *table, int64_t n_words)
 {
     if (!h || !table) return fail(HC_ERR_ARG, "hc_get_profile_stats: bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    if (int rc = prof_words_check(h, n_words, "hc_get_profile_stats")) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(table, h->prof.p, (size_t)n_words * 8, hipMemcpyDeviceToHost));
-    return HC_OK;
+    return table_copy(h, h->prof, ensure_prof, hipMemcpyDeviceToHost, table, n_words, "hc_get_profile_stats");
 }
 
 int hc_set_profile_stats_tables(hc_handle *h, const int64_t *table, int64_t n_words)
 {
     if (!h || !table) return fail(HC_ERR_ARG, "hc_set_profile_stats_tables: bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    if (int rc = prof_words_check(h, n_words, "hc_set_profile_stats_tables")) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(h->prof.p, table, (size_t)n_words * 8, hipMemcpyHostToDevice));
-    return HC_OK;
+    return table_copy(h, h->prof, ensure_prof, hipMemcpyHostToDevice, const_cast<int64_t *>(table), n_words,
+                      "hc_set_profile_stats_tables");
 }
 
 int hc_export_profile_stats(hc_handle *h, void *device_dst, int64_t n_words)
 {
     if (!h || !device_dst) return fail(HC_ERR_ARG, "hc_export_profile_stats: bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    if (int rc = prof_words_check(h, n_words, "hc_export_profile_stats")) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(device_dst, h->prof.p, (size_t)n_words * 8, hipMemcpyDeviceToDevice));
-    HIP_TRY(hipDeviceSynchronize());
-    return HC_OK;
+    return table_copy(h, h->prof, ensure_prof, hipMemcpyDeviceToDevice, device_dst, n_words, "hc_export_profile_stats");
 }
 
 int hc_reset_profile_stats(hc_handle *h)
 {
     if (!h) return fail(HC_ERR_ARG, "hc_reset_profile_stats: bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    h->prof_points = 0;
-    return ensure_prof(h);
+    return table_reset(h, h->prof, ensure_prof);
 }
 
 int hc_get_profile_overflow(hc_handle *h, uint64_t *count)
@@ -1780,7 +1787,7 @@ int hc_get_profile_overflow(hc_handle *h, uint64_t *count)
     HIP_TRY(hipSetDevice(h->device));
     if (int rc = ensure_prof(h)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(count, h->prof.p + prof_layout(h).ovf, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(count, h->prof.buf.p + prof_layout(h).ovf, 8, hipMemcpyDeviceToHost));
     return HC_OK;
 }
 
@@ -1791,42 +1798,29 @@ int hc_set_wtd_hist(hc_handle *h, int32_t stride)
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->hist_stride = stride;
-    h->hist_points = 0;          // re-created, zeroed
+    h->hist.release();           // re-created, zeroed, when on
     const int rc = stride == 0 ? HC_OK : ensure_hist(h);
-    if (stride == 0 || rc != HC_OK) {   // off, or refused: off
-        h->hist_stride = 0;
-        h->hist.release();
-    }
+    if (rc != HC_OK) h->hist_stride = 0, h->hist.release();      // refused: off
     return rc;
 }
 
 int hc_get_wtd_hist(hc_handle *h, int32_t *table, int64_t n_entries)
 {
     if (!h || !table) return fail(HC_ERR_ARG, "hc_get_wtd_hist: bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    if (int rc = hist_entries_check(h, n_entries, "hc_get_wtd_hist")) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(table, h->hist.p, (size_t)n_entries * 4, hipMemcpyDeviceToHost));
-    return HC_OK;
+    return table_copy(h, h->hist, ensure_hist, hipMemcpyDeviceToHost, table, n_entries, "hc_get_wtd_hist");
 }
 
 int hc_set_wtd_hist_table(hc_handle *h, const int32_t *table, int64_t n_entries)
 {
     if (!h || !table) return fail(HC_ERR_ARG, "hc_set_wtd_hist_table: bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    if (int rc = hist_entries_check(h, n_entries, "hc_set_wtd_hist_table")) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(h->hist.p, table, (size_t)n_entries * 4, hipMemcpyHostToDevice));
-    return HC_OK;
+    return table_copy(h, h->hist, ensure_hist, hipMemcpyHostToDevice, const_cast<int32_t *>(table), n_entries,
+                      "hc_set_wtd_hist_table");
 }
 
 int hc_reset_wtd_hist(hc_handle *h)
 {
     if (!h) return fail(HC_ERR_ARG, "hc_reset_wtd_hist: bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    h->hist_points = 0;
-    return ensure_hist(h);
+    return table_reset(h, h->hist, ensure_hist);
 }
 
 int hc_wtd_distribution(int device, const int32_t *hist, const int32_t *obs_idx, int64_t n_rows, int32_t D,
@@ -1900,7 +1894,7 @@ int hc_allreduce_moments(hc_handle **handles, int n)
         if (!h) return fail(HC_ERR_ARG, "handle %d is NULL", k);
         HIP_TRY(hipSetDevice(h->device));
         if (int rc = ensure_moments(h)) return rc;
-        const size_t c = (size_t)h->n_points * 3 * h->n_rows;
+        const size_t c = (size_t)h->moments.n;
         if (k == 0) count = c;
         if (c != count) return fail(HC_ERR_ARG, "handle %d holds a moment table of another shape", k);
         for (int j = 0; j < k; j++)
@@ -1918,7 +1912,7 @@ int hc_allreduce_moments(hc_handle **handles, int n)
     bad = bad ? bad : r.GroupStart();
     for (int k = 0; k < n && !bad; k++) {
         (void)hipSetDevice(handles[k]->device);
-        bad = r.AllReduce(handles[k]->moments.p, handles[k]->moments.p, count, NCCL_INT64, NCCL_SUM, comms[(size_t)k],
+        bad = r.AllReduce(handles[k]->moments.buf.p, handles[k]->moments.buf.p, count, NCCL_INT64, NCCL_SUM, comms[(size_t)k],
                           handles[k]->stream);
     }
     const int ge = r.GroupEnd();

@@ -89,23 +89,18 @@ def member_generators(seed, n_members, member_offset=0):
     return gens
 
 
-class EnsembleSimulation:
-    """N members of one parameter point on one device.
+class _Run:
+    """What an ensemble and a sweep share: one handle (``stepper``) stepped from ``next_row`` on, and its optional tables.
 
-    noise="philox" (default): counter-based normals generated in the kernel, keyed by the global member id.
-    noise="numpy": host NumPy streams (`member_generators`), drawn in the reference's order -- #0 spin-up,
-    #1 base vector, then one vector per refresh row (simulation.py:426,561,601) -- and uploaded per launch.
-    spinup="shared" (default): one spin-up (global member 0's first draw) broadcast to all members;
-    spinup="member": every member spins up with its own first draw (`spinup_members_on_gpu`).
     profile_stride > 0: ensemble profile statistics (psi, theta every ``profile_stride``-th row from row 0 = the initial
     states, fluxes and abs_error every solved row) accumulated on the device: :meth:`profile_stats`.
     wtd_hist_stride > 0: per-row histograms of the members' water-table index every ``wtd_hist_stride``-th row, counted on
     the device: :meth:`wtd_distribution` (quantiles, CRPS against the well).
-    """
+    ``_lead`` is the leading shape of the per-point tables: () for an ensemble, (P,) for a sweep."""
 
-    def __init__(self, cols, forcing, n_members, seed=0, device=0, member_offset=0, psi0=None, flags=None,
-                 noise="philox", spinup="shared", profile_stride=0, wtd_hist_stride=0):
-        self._start(cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup)
+    _lead = ()
+
+    def _start_tables(self, profile_stride, wtd_hist_stride):
         self.profile_stride = int(profile_stride)
         if self.profile_stride:
             self.stepper.set_profile_stats(self.profile_stride)
@@ -113,6 +108,59 @@ class EnsembleSimulation:
         self.wtd_hist_stride = int(wtd_hist_stride)
         if self.wtd_hist_stride:
             self.stepper.set_wtd_hist(self.wtd_hist_stride)
+
+    def advance(self, n_rows, **kw):
+        """Solve the next ``n_rows`` forcing rows for every member."""
+        out = self.stepper.step_rows(self.next_row, n_rows, **kw)
+        self.next_row += n_rows
+        self.kernel_ms += out["kernel_ms"]
+        self.launches += out["launches"]
+        return out
+
+    def moments(self):
+        """[3][T]; a sweep: [P][3][T]"""
+        return np.asarray(self.stepper.moments()).reshape(self._lead + (3, self.forcing.dim_t))
+
+    def profile_table(self):
+        return self.stepper.profile_table()
+
+    def profile_stats(self, table=None):
+        """theta_vol / psi_press / S_eff mean and sigma [T_out][D], transpiration / lateral_flow mean and sigma and
+        abs_error_mean [T], rows, count (stepper.profile_tables_to_stats), with a leading [P] axis when the handle holds
+        several points; ``table``: e.g. the sum over ranks."""
+        return self.stepper.profile_stats(table)
+
+    def wtd_hist_table(self):
+        """[n_hrow][D] int32: members per water-table index on every histogram row (stepper.wtd_hist_rows); a sweep:
+        [P][n_hrow][D], one table per parameter point of this handle."""
+        return self.stepper.wtd_hist_table().reshape(self._lead + (-1, self.cols.dim_d))
+
+    def wtd_distribution(self, levels=(0.05, 0.25, 0.5, 0.75, 0.95), table=None):
+        """Quantiles of the water-table depth and CRPS against the well per histogram row (stepper.wtd_distribution), with
+        the leading shape of the table; ``table``: e.g. the sum over ranks."""
+        t = self.wtd_hist_table() if table is None else table
+        return wtd_distribution(t, self.forcing.wtd_obs, levels, self.cols.dz, self.cols.z, self.device,
+                                self.wtd_hist_stride)
+
+    def close(self):
+        self.stepper.close()
+
+
+class EnsembleSimulation(_Run):
+    """N members of one parameter point on one device.
+
+    noise="philox" (default): counter-based normals generated in the kernel, keyed by the global member id.
+    noise="numpy": host NumPy streams (`member_generators`), drawn in the reference's order -- #0 spin-up,
+    #1 base vector, then one vector per refresh row (simulation.py:426,561,601) -- and uploaded per launch.
+    spinup="shared" (default): one spin-up (global member 0's first draw) broadcast to all members;
+    spinup="member": every member spins up with its own first draw (`spinup_members_on_gpu`).
+    profile_stride, wtd_hist_stride: the optional tables (:class:`_Run`).
+    """
+
+    def __init__(self, cols, forcing, n_members, seed=0, device=0, member_offset=0, psi0=None, flags=None,
+                 noise="philox", spinup="shared", profile_stride=0, wtd_hist_stride=0):
+        self._start(cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup)
+        self._start_tables(profile_stride, wtd_hist_stride)
 
     def _start(self, cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup):
         if noise not in ("philox", "numpy") or spinup not in ("shared", "member"):
@@ -179,37 +227,11 @@ class EnsembleSimulation:
                 for k, g in enumerate(self.gens):
                     fresh[q, k] = g.standard_normal(self.cols.dim_d)
             kw["fresh_noise"] = fresh
-        out = self.stepper.step_rows(self.next_row, n_rows, **kw)
-        self.next_row += n_rows
-        self.kernel_ms += out["kernel_ms"]
-        self.launches += out["launches"]
-        return out
-
-    def moments(self):
-        return self.stepper.moments()
+        return super().advance(n_rows, **kw)
 
     def wtd_mean_std(self, moments=None):
         m = self.moments() if moments is None else moments
         return moments_to_mean_std(m, self.cols.dz, self.cols.z[0])
-
-    def profile_table(self):
-        return self.stepper.profile_table()
-
-    def profile_stats(self, table=None):
-        """theta_vol / psi_press / S_eff mean and sigma [T_out][D], transpiration / lateral_flow mean and sigma and
-        abs_error_mean [T], rows, count (stepper.profile_tables_to_stats); ``table``: e.g. the sum over ranks."""
-        return self.stepper.profile_stats(table)
-
-    def wtd_hist_table(self):
-        """[n_hrow][D] int32: members per water-table index on every histogram row (stepper.wtd_hist_rows)."""
-        return self.stepper.wtd_hist_table()[0]
-
-    def wtd_distribution(self, levels=(0.05, 0.25, 0.5, 0.75, 0.95), table=None):
-        """Quantiles of the water-table depth and CRPS against the well per histogram row (stepper.wtd_distribution);
-        ``table``: e.g. the sum over ranks."""
-        t = self.wtd_hist_table() if table is None else table
-        return wtd_distribution(t, self.forcing.wtd_obs, levels, self.cols.dz, self.cols.z, self.device,
-                                self.wtd_hist_stride)
 
     # -- checkpoint / resume (the single-column analogue in the reference is IC_Filename, simulation.py:358-385) ------
     CHECKPOINT_KEYS = ("psi", "noise_scale", "moments", "next_row", "seed", "member_offset", "n_members", "dim_d",
@@ -272,9 +294,6 @@ class EnsembleSimulation:
             sim.stepper.set_wtd_hist_table(np.asarray(data["wtd_hist"]))
         sim.next_row = int(data["next_row"])
         return sim
-
-    def close(self):
-        self.stepper.close()
 
 
 def allreduce_moments(moments, device, force=False):
@@ -351,7 +370,7 @@ def check_sweep_points(params, points):
     return merged
 
 
-class SweepSimulation:
+class SweepSimulation(_Run):
     """BASELINE config 5: P parameter points x ``n_members`` stochastic members each, ALL in one handle and one
     launch per batch of rows (``hc_add_point``): per-member parameter point -> its own column parameters and slot
     tables in the step kernel, per-point moments.
@@ -367,6 +386,7 @@ class SweepSimulation:
                  point_ids=None, profile_stride=0, wtd_hist_stride=0):
         self.points = list(cols_list)
         self.P, self.n = len(self.points), int(n_members)
+        self._lead = (self.P,)
         self.forcing, self.seed, self.device = forcing, int(seed), device
         # global index of each of this handle's points in the whole sweep: consecutive from `first_point`, or any
         # list (`point_ids`) when points are dealt to ranks round-robin so that every rank gets the same mix of costs
@@ -390,13 +410,7 @@ class SweepSimulation:
         self.stepper.set_noise_philox(self.seed, self.member_offset)
         if self.P > 1:
             self.stepper.set_point_member_bases(self.bases)
-        self.profile_stride = int(profile_stride)
-        if self.profile_stride:
-            self.stepper.set_profile_stats(self.profile_stride)
-            self.stepper.profile_snapshot(0)
-        self.wtd_hist_stride = int(wtd_hist_stride)
-        if self.wtd_hist_stride:
-            self.stepper.set_wtd_hist(self.wtd_hist_stride)
+        self._start_tables(profile_stride, wtd_hist_stride)
         self.next_row, self.kernel_ms, self.launches = 1, 0.0, 0
 
     def _spinup(self, flags):
@@ -413,37 +427,6 @@ class SweepSimulation:
             return lead.get_state(), iters
         finally:
             lead.close()
-
-    def advance(self, n_rows, **kw):
-        out = self.stepper.step_rows(self.next_row, n_rows, **kw)
-        self.next_row += n_rows
-        self.kernel_ms += out["kernel_ms"]
-        self.launches += out["launches"]
-        return out
-
-    def moments(self):
-        """[P][3][T]"""
-        return np.asarray(self.stepper.moments()).reshape(self.P, 3, self.forcing.dim_t)
-
-    def profile_table(self):
-        return self.stepper.profile_table()
-
-    def profile_stats(self, table=None):
-        """As EnsembleSimulation.profile_stats, with a leading [P] axis when the handle holds several points."""
-        return self.stepper.profile_stats(table)
-
-    def wtd_hist_table(self):
-        """[P][n_hrow][D] int32 (one table per parameter point of this handle)."""
-        return self.stepper.wtd_hist_table()
-
-    def wtd_distribution(self, levels=(0.05, 0.25, 0.5, 0.75, 0.95), table=None):
-        """As EnsembleSimulation.wtd_distribution, with a leading [P] axis; ``table``: e.g. the sweep assembled over ranks."""
-        t = self.wtd_hist_table() if table is None else table
-        return wtd_distribution(t, self.forcing.wtd_obs, levels, self.points[0].dz, self.points[0].z, self.device,
-                                self.wtd_hist_stride)
-
-    def close(self):
-        self.stepper.close()
 
 
 def deal_points(n_points, rank, world):

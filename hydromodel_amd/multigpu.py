@@ -8,9 +8,10 @@ a GPU, never a re-exec -- and every rank runs its share with no communication wh
 * ensemble: rank r owns the contiguous member block ``shard(N, r, world)``; the Philox stream is keyed by the GLOBAL
   member id, the shared initial condition is global member 0's spin-up on every rank, and ONE int64 all-reduce of the
   per-row water-table moments ``[3][T]`` ends the run (RCCL over xGMI with the nccl backend);
-* sweep (BASELINE config 5): whole points are dealt round-robin (``ensemble.deal_points``); every rank writes ITS points
-  into zeroed ``[P][3][T]`` / ``[P][D]`` / ``[P]`` tables and one all-reduce each assembles them (x + 0 is exact, so the
-  assembled file holds every point's bits exactly as the rank that ran it produced them).
+* sweep (BASELINE config 5): whole points are dealt round-robin (``ensemble.deal_points``); every rank places ITS points
+  in zeroed ``[P][3][T]`` / ``[P][D]`` / ``[P]`` tables and one all-reduce each assembles them (:func:`place_points`: float64
+  tables travel as their int64 bits, so the assembled file holds every point's bits exactly as the rank that ran it
+  produced them).
 
 Rank 0 owns the output file.  Integer moment sums are order-independent: the file is bit-identical at any rank count.
 """
@@ -108,27 +109,35 @@ def shard(n_members, rank, world):
     return lo, lo + base + (1 if r < extra else 0)
 
 
+def place_points(local, point_ids, n_points, ranks=None):
+    """A rank's ``[p][...]`` tables at rows ``point_ids`` of a zeroed ``[n_points][...]`` table, summed over ``ranks`` when
+    given: every point has one owner, so the sum is the whole table with each point's entries as its rank made them.
+    Integer tables come back as int64.  float64 tables are summed as their int64 bit patterns (``x + 0.0`` is not ``x`` for
+    ``-0.0``, nor need a NaN's payload survive an add), so every bit of them survives."""
+    local = np.asarray(local)
+    bits = local.dtype == np.float64
+    out = np.zeros((int(n_points),) + local.shape[1:], dtype=np.int64)
+    if len(point_ids):
+        out[np.asarray(point_ids, dtype=np.int64)] = local.view(np.int64) if bits else local
+    if ranks is not None:
+        out = ranks.allreduce_sum(out)
+    return out.view(np.float64) if bits else out
+
+
 def assemble_points(ranks, n_points, local, T, D):
     """Sweep result of ALL ranks from each rank's own points.
 
     ``local`` = {global point index: {"moments" int64 [3][T], "psi0" float64 [D], "spinup_iterations" int}} for the points
-    this rank ran (possibly none).  Every rank fills zeroed [P][3][T] / [P][D] / [P] tables with its points and the tables
-    are summed over the ranks: a point's entries meet only zeros, so its bits survive unchanged.  ``owners`` counts how
-    many ranks delivered each point -- exactly one each, or the sweep was dealt wrongly."""
-    P = int(n_points)
-    moments = np.zeros((P, 3, T), dtype=np.int64)
-    psi0 = np.zeros((P, D), dtype=np.float64)
-    spin = np.zeros(P, dtype=np.int64)
-    owners = np.zeros(P, dtype=np.int64)
-    for k, rec in local.items():
-        moments[k] = rec["moments"]
-        psi0[k] = rec["psi0"]
-        spin[k] = 0 if rec.get("spinup_iterations") is None else int(rec["spinup_iterations"])
-        owners[k] = 1
-    moments = ranks.allreduce_sum(moments)
-    psi0 = ranks.allreduce_sum(psi0)
-    spin = ranks.allreduce_sum(spin)
-    owners = ranks.allreduce_sum(owners)
+    this rank ran (possibly none).  Every rank's points are placed and summed over the ranks (:func:`place_points`), so
+    every point's bits survive unchanged.  ``owners`` counts how many ranks delivered each point -- exactly one each, or
+    the sweep was dealt wrongly."""
+    P, ids = int(n_points), list(local)
+    recs = [local[k] for k in ids]
+    moments = place_points(np.array([r["moments"] for r in recs], dtype=np.int64).reshape(-1, 3, T), ids, P, ranks)
+    psi0 = place_points(np.array([r["psi0"] for r in recs], dtype=np.float64).reshape(-1, D), ids, P, ranks)
+    spin = np.array([0 if r.get("spinup_iterations") is None else int(r["spinup_iterations"]) for r in recs], dtype=np.int64)
+    spin = place_points(spin, ids, P, ranks)
+    owners = place_points(np.ones(len(ids), dtype=np.int64), ids, P, ranks)
     if not np.array_equal(owners, np.ones(P, dtype=np.int64)):
         bad = np.flatnonzero(owners != 1)
         raise RuntimeError(f" Sweep: points {bad[:8].tolist()} were delivered by {owners[bad[:8]].tolist()} ranks (expected one each).")

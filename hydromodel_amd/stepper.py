@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from .multigpu import place_points  # noqa: F401  (the sweep's tables over the ranks: place at point ids, sum)
 
 
 def column_params(cols, surface_evap, flags=None):
@@ -354,10 +355,15 @@ PROF_SCALE_PSI, PROF_SCALE_THETA, PROF_SCALE_FLUX = 16, 40, 32
 PROF_Q_MAX = (1 << 40) - 1
 
 
+def stride_rows(T, stride):
+    """Rows of a table that samples every ``stride``-th of ``T`` forcing rows: rows 0, stride, 2 stride, ... < T."""
+    return (int(T) - 1) // int(stride) + 1
+
+
 def profile_layout(P, T, D, stride):
     """{part: (offset, shape)} of the int64 table: prof [P][T_out][D][2][5] (psi_press, theta_vol), pcnt [P][T_out],
-    flux [P][T][2][5] (transpiration, lateral_flow), fcnt [P][T], aerr [P][T], ovf [1]; T_out = (T - 1) // stride + 1."""
-    n_prow = (int(T) - 1) // int(stride) + 1
+    flux [P][T][2][5] (transpiration, lateral_flow), fcnt [P][T], aerr [P][T], ovf [1]; T_out = stride_rows(T, stride)."""
+    n_prow = stride_rows(T, stride)
     shapes = [("prof", (P, n_prow, D, 2, PROF_WORDS)), ("pcnt", (P, n_prow)), ("flux", (P, T, 2, PROF_WORDS)),
               ("fcnt", (P, T)), ("aerr", (P, T)), ("ovf", (1,))]
     out, off = {}, 0
@@ -447,24 +453,12 @@ WTD_MAX_LEVELS = 16
 INT32_MAX = (1 << 31) - 1
 
 
-def wtd_hist_slots(T, stride):
-    """Histogram rows of ``T`` forcing rows at ``stride``: rows 0, stride, 2 stride, ... < T."""
-    return (int(T) - 1) // int(stride) + 1
+wtd_hist_slots = stride_rows      # histogram rows of T forcing rows at a stride (the profile rows of the same stride)
 
 
 def wtd_hist_rows(T, stride):
     """The forcing row of each slot: slot j <-> row j stride (the profile rows of the same stride)."""
     return np.arange(wtd_hist_slots(T, stride), dtype=np.int64) * int(stride)
-
-
-def place_points(local, point_ids, n_points):
-    """A rank's [p][...] tables in a zeroed int64 [n_points][...] table at rows ``point_ids``: summed over the ranks, the
-    parts give the whole sweep's table (every point has exactly one owner)."""
-    local = np.asarray(local)
-    out = np.zeros((int(n_points),) + local.shape[1:], dtype=np.int64)
-    if len(point_ids):
-        out[np.asarray(point_ids, dtype=np.int64)] = local
-    return out
 
 
 def wtd_distribution(hist, obs_idx, levels, dz, z, device=0, stride=1):

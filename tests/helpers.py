@@ -58,3 +58,33 @@ def golden(name):
 def rel_err(a, b, floor=1.0):
     a, b = np.asarray(a, float), np.asarray(b, float)
     return float(np.max(np.abs(a - b) / np.maximum(floor, np.abs(b)))) if a.size else 0.0
+
+
+def cli_params(tmp_path):
+    """The CLI's parameter dict on the synthetic well (D = 200) and one year of synthetic forcing, files under tmp_path."""
+    from hydromodel_amd.synthetic import write_forcing_csv, write_site_information
+    params = default_parameters()
+    params["Site_Information"] = str(write_site_information(tmp_path / "site.json", {10: WELLS[200]}))
+    params["Data_Filename"] = str(write_forcing_csv(tmp_path / "forcing.csv", 1))
+    return params
+
+
+def run_cli_ranks(tmp_path, name, params, gpus):
+    """berkeley_hydro_main.py on `params` in tmp_path/name with `gpus` ranks sharing card 0 over gloo; returns the
+    datasets of <name>_ensemble.h5 and the printed output."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from hydromodel_amd.simulation import loadResults
+    d = tmp_path / name
+    d.mkdir()
+    (d / "p.json").write_text(json.dumps(dict(params, Output_Name=name)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
+    env.update(HYDROCOL_DIST_BACKEND="gloo", HYDROCOL_SHARE_DEVICE="1")
+    cmd = [sys.executable, str(GOLDEN.parent.parent / "berkeley_hydro_main.py"), "--params", str(d / "p.json")]
+    if gpus > 1:
+        cmd += ["--gpus", str(gpus)]
+    r = subprocess.run(cmd, cwd=d, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    return loadResults(d / f"{name}_ensemble.h5"), r.stdout

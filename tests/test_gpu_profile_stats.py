@@ -7,7 +7,7 @@ import json
 import numpy as np
 import pytest
 
-from helpers import WELLS, digest, digest_point, golden
+from helpers import WELLS, cli_params, digest, digest_point, golden, run_cli_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -226,3 +226,58 @@ def test_cli_profiles_block_writes_the_new_datasets_and_leaves_the_rest_alone(tm
     for k in plain:                                          # (rows past the run are NaN in both)
         a, b = np.asarray(plain[k]), np.asarray(prof[k])
         assert a.dtype == b.dtype and np.array_equal(a, b, equal_nan=a.dtype.kind == "f"), k
+
+
+PROFILE_KEYS = ("theta_vol_mean", "theta_vol_std", "psi_press_mean", "psi_press_std", "S_eff_mean", "S_eff_std",
+                "transpiration_mean", "transpiration_std", "lateral_flow_mean", "lateral_flow_std", "abs_error_mean")
+
+
+@pytest.mark.parametrize("n_points", [1, 2])
+def test_cli_sweep_profiles_keep_the_point_axis_and_leave_the_rest_alone(tmp_path, monkeypatch, n_points):
+    from hydromodel_amd import cli
+    from hydromodel_amd.simulation import loadResults
+    params = cli_params(tmp_path)
+    monkeypatch.chdir(tmp_path)
+    pts = [{"Soil_Properties": {"n": n}} for n in (1.6, 2.4)][:n_points]
+    files = {}
+    for tag, extra in (("plain", {}), ("prof", {"Profiles": 24, "Distribution": {"Stride": 48}})):
+        params["Output_Name"] = f"Run_{tag}"
+        params["Ensemble"] = {"Members": 128, "Seed": 3, "Days": 2, "Points": pts, **extra}
+        (tmp_path / f"{tag}.json").write_text(json.dumps(params))
+        cli.run_cli(["berkeley_hydro_main.py", "--params", str(tmp_path / f"{tag}.json")])
+        files[tag] = loadResults(tmp_path / f"Run_{tag}_ensemble.h5")
+    plain, prof = files["plain"], files["prof"]
+    P, T, D = n_points, plain["moments"].shape[-1], plain["initial_cond"].shape[-1]
+    n_prow = (T - 1) // 24 + 1
+    for key in ("theta_vol", "psi_press", "S_eff"):
+        assert prof[key + "_mean"].shape == (P, n_prow, D) and prof[key + "_std"].shape == (P, n_prow, D)
+    for key in ("transpiration_mean", "transpiration_std", "lateral_flow_mean", "lateral_flow_std", "abs_error_mean"):
+        assert prof[key].shape == (P, T)
+    assert prof["profile_rows"].tolist() == list(range(0, T, 24)) and int(prof["profile_overflow"]) == 0
+    assert prof["profile_count"].shape == (P, n_prow)
+    assert (prof["profile_count"][:, :5] == 128).all() and (prof["profile_count"][:, 5:] == 0).all()   # rows 0 ... 96
+    assert np.all(np.isfinite(prof["theta_vol_mean"][:, :5])) and np.isnan(prof["theta_vol_mean"][:, 5:]).all()
+    assert prof["wtd_hist"].shape == (P, (T - 1) // 48 + 1, D)
+    for k in plain:                                          # every pre-existing dataset, byte for byte
+        a, b = np.asarray(plain[k]), np.asarray(prof[k])
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), k
+
+
+@pytest.mark.parametrize("sweep", [False, True])
+def test_two_ranks_sharing_the_card_write_the_profiles_one_rank_writes(tmp_path, sweep):
+    params = cli_params(tmp_path)
+    ens = {"Members": 250, "Seed": 5, "Days": 2, "Profiles": 24, "Distribution": {"Stride": 12}}
+    if sweep:                                                # three points dealt to two ranks: 2 + 1
+        ens.update(Members=32, Points=[{"Soil_Properties": {"n": n}} for n in (1.6, 2.0, 2.4)])
+    params["Ensemble"] = ens
+    one, log1 = run_cli_ranks(tmp_path, "one", params, 1)
+    two, log2 = run_cli_ranks(tmp_path, "two", params, 2)
+    assert set(PROFILE_KEYS) <= set(one) and set(one) == set(two)
+    assert int(one["gpus"]) == 1 and int(two["gpus"]) == 2
+    for k in one:
+        if k == "gpus":
+            continue
+        a, b = np.asarray(one[k]), np.asarray(two[k])
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), k
+    line = [s for s in log1.splitlines() if "CRPS" in s]
+    assert len(line) == 1 and line == [s for s in log2.splitlines() if "CRPS" in s]

@@ -5,19 +5,15 @@ against an exact restatement with Python integers and, for one member, against t
 effects on the run, resume, and the CLI's "Ensemble": {"Distribution": ...} block.
 Reference surface: wtd_est / abs_error of Simulation.run, simulation.py:612-615."""
 import json
-import os
-import subprocess
-import sys
 from fractions import Fraction
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 from helpers import WELLS, digest, forcing_frame, golden
+from helpers import cli_params as _cli_params, run_cli_ranks as _run_ranks
 
 pytestmark = pytest.mark.gpu
-REPO = Path(__file__).resolve().parent.parent
 ROWS = 96                                                   # two days
 LEVELS = (0.0, 0.05, 0.5, 0.95, 1.0)
 
@@ -252,14 +248,6 @@ NEW_KEYS = {"wtd_hist", "wtd_hist_rows", "wtd_hist_count", "wtd_quantile_levels"
             "wtd_crps_mean_cm"}
 
 
-def _cli_params(tmp_path):
-    from hydromodel_amd.synthetic import default_parameters, write_forcing_csv, write_site_information
-    params = default_parameters()
-    params["Site_Information"] = str(write_site_information(tmp_path / "site.json", {10: WELLS[200]}))
-    params["Data_Filename"] = str(write_forcing_csv(tmp_path / "forcing.csv", 1))
-    return params
-
-
 def test_cli_distribution_block_writes_the_new_datasets_and_leaves_the_rest_alone(tmp_path, monkeypatch, capsys):
     from hydromodel_amd import cli
     from hydromodel_amd.simulation import loadResults
@@ -299,21 +287,6 @@ def test_cli_distribution_block_writes_the_new_datasets_and_leaves_the_rest_alon
     assert sweep["wtd_crps_mean_cm"].shape == (2,) and np.isfinite(sweep["wtd_crps_mean_cm"]).all()
     assert sweep["wtd_hist_count"][:, 1:3].tolist() == [[128, 128], [128, 128]]
     assert "[Sweep 2 points x128] CRPS = " in logs["sweep"]
-
-
-def _run_ranks(tmp, name, params, gpus):
-    d = tmp / name
-    d.mkdir()
-    (d / "p.json").write_text(json.dumps(dict(params, Output_Name=name)))
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
-    env.update(HYDROCOL_DIST_BACKEND="gloo", HYDROCOL_SHARE_DEVICE="1")
-    cmd = [sys.executable, str(REPO / "berkeley_hydro_main.py"), "--params", str(d / "p.json")]
-    if gpus > 1:
-        cmd += ["--gpus", str(gpus)]
-    r = subprocess.run(cmd, cwd=d, env=env, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    from hydromodel_amd.simulation import loadResults
-    return loadResults(d / f"{name}_ensemble.h5"), r.stdout
 
 
 @pytest.mark.parametrize("sweep", [False, True])

@@ -42,6 +42,16 @@ def _fake_point(k, T, D):
             "spinup_iterations": 100 + k}
 
 
+def _planted_point(k, T, D):
+    """A point whose psi0 holds -0.0 and NaNs with payloads: bits an all-reduce of float64 values does not keep."""
+    rec = _fake_point(k, T, D)
+    bits = rec["psi0"].view(np.int64)
+    bits[0] = np.int64(-(2**63))                                      # -0.0
+    bits[1] = np.int64(0x7FF8_0000_0BAD_CAFE)                         # quiet NaN, payload
+    bits[2] = np.uint64(0xFFF8_0000_0000_1234).view(np.int64)         # negative quiet NaN, payload
+    return rec
+
+
 def _assemble_worker(rank, world, port, P, T, D, out_dir, mode):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank), HYDROCOL_DIST_BACKEND="gloo")
@@ -49,7 +59,7 @@ def _assemble_worker(rank, world, port, P, T, D, out_dir, mode):
     mine = deal_points(P, rank, world)
     if mode == "duplicate":
         mine = sorted(set(mine) | {0})                    # both ranks claim point 0
-    local = {k: _fake_point(k, T, D) for k in mine}
+    local = {k: (_planted_point if mode == "planted" else _fake_point)(k, T, D) for k in mine}
     try:
         m, psi0, spin = multigpu.assemble_points(ranks, P, local, T, D)
         np.savez(os.path.join(out_dir, f"r{rank}.npz"), m=m, psi0=psi0, spin=spin)
@@ -112,6 +122,16 @@ def test_member_shards_reduce_to_the_whole_ensemble_on_eight_ranks(tmp_path):
     for t in range(T):
         idx = (ids * 7 + t) % 300
         assert total[:, t].tolist() == [N, int(idx.sum()), int((idx * idx).sum())]
+
+
+def test_sweep_assembly_keeps_negative_zero_and_nan_payloads(tmp_path):
+    """x + 0.0 is not the identity on every float64: -0.0 + 0.0 = +0.0.  The assembly sums the bits, not the values."""
+    world, P, T, D = 2, 3, 5, 4
+    mp.spawn(_assemble_worker, args=(world, _free_port(), P, T, D, str(tmp_path), "planted"), nprocs=world, join=True)
+    want = np.stack([_planted_point(k, T, D)["psi0"] for k in range(P)]).view(np.int64)
+    for r in range(world):
+        got = np.load(tmp_path / f"r{r}.npz")["psi0"]
+        assert got.dtype == np.float64 and np.array_equal(got.view(np.int64), want)
 
 
 def test_sweep_assembly_refuses_a_point_delivered_twice(tmp_path):
