@@ -92,6 +92,14 @@ EXPORTS = {
     "hc_set_wtd_hist_table": ([C.c_void_p, _ip, C.c_int64], C.c_int),
     "hc_reset_wtd_hist": ([C.c_void_p], C.c_int),
     "hc_wtd_distribution": ([C.c_int, _ip, _ip, C.c_int64, C.c_int32, _dp, C.c_int32, C.c_double, _lp, _ip, _dp], C.c_int),
+    "hc_set_filter": ([C.c_void_p, C.c_int32, C.c_double, C.c_uint64], C.c_int),
+    "hc_get_filter_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),
+    "hc_set_filter_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),
+    "hc_get_filter_base": ([C.c_void_p, _dp, C.c_int64, C.c_int64], C.c_int),
+    "hc_set_filter_base": ([C.c_void_p, _dp], C.c_int),
+    "hc_get_filter_ancestors": ([C.c_void_p, _lp], C.c_int),
+    "hc_get_filter_weights": ([C.c_void_p, _lp], C.c_int),
+    "hc_get_filter_draw": ([C.c_void_p, _lp], C.c_int),
     "hc_rhs": ([C.c_void_p, C.c_int64, C.c_int32, _dp, _dp], C.c_int),
     "hc_model_nodes": ([C.c_void_p, _dp, _dp], C.c_int),
     "hc_plugin_eval": ([C.c_int, C.POINTER(ColumnParams), C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp],

@@ -34,6 +34,15 @@ unknown keys, only membership of the 12 is checked):
   ``wtd_hist`` ``[T_out][D]``, ``wtd_hist_rows``, ``wtd_hist_count``, ``wtd_quantile_levels``, ``wtd_quantile_cm``
   ``[T_out][L]``, ``wtd_crps_cm`` ``[T_out]`` and ``wtd_crps_mean_cm`` (a sweep: a leading ``[P]`` axis), and the run
   ends with the line `` [Ensemble xN] CRPS = ... cm over R rows``, as the reference ends with its MAE.
+* ``"Ensemble": {..., "Filter": {"Stride": 48, "Sigma_cm": 10.0, "Seed": s}}``: a bootstrap particle filter on the well
+  (include/hydrocol.h hc_set_filter) -- on every 48th forcing row (default 48; 0 = off) that has an observation the members
+  of each parameter point are weighted by the Gaussian likelihood of the observed water table (``Sigma_cm``, required:
+  finite and > 0) and resampled on the GPU (``Seed``: default the ensemble's seed).  Moments, profiles and histograms
+  describe the forecast of each row; the states continue from the analysis.  Added to ``<Output_Name>_ensemble.h5``:
+  ``filter_rows``, ``filter_count``, ``filter_ess``, ``filter_loglik_rows``, ``filter_survivors`` ``[R]``, ``filter_loglik``
+  (the log marginal likelihood of the well record, log cm^-1) and ``filter_sigma_cm`` (a sweep: a leading ``[P]`` axis), and
+  the run ends with `` [Ensemble xN] filter log-likelihood = ... over R rows`` (a sweep: the best point).  A single-point
+  ensemble on several GPUs is refused (resampling would move states between ranks).
 * ``"Ensemble": {"repair_predict": true}`` with ``Simulation_Flags.PREDICT``: run the repaired predictive lateral flow
    instead of raising the reference's ``TypeError``.
 """
@@ -91,6 +100,8 @@ def main(params_file=None, data_file=None, seed=None, device=0, gpus=None, _sett
         if params.get("Ensemble"):
             distribution_settings(params["Ensemble"])      # a bad Distribution block fails before any GPU is touched
         n_gpus = multigpu.requested_gpus(gpus, params)
+        if params.get("Ensemble"):
+            filter_settings(params["Ensemble"], n_gpus)     # so does a bad Filter block
         ranks = multigpu.Ranks(expect=n_gpus if (n_gpus > 1 or multigpu.in_rank()) else None)
         if ranks.world > 1:
             device = ranks.device_index()
@@ -147,6 +158,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     from .digest import ColumnTables, ForcingDigest, load_site_well
     from .ensemble import EnsembleSimulation
     dist_stride, dist_levels = distribution_settings(ens)
+    filt = filter_settings(ens, ranks.world)
     cols = ColumnTables(params, load_site_well(params))
     forcing = ForcingDigest(params, water_data, cols)
     if cols.flags["PREDICT"] and not ens.get("repair_predict"):
@@ -155,7 +167,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     days = int(ens.get("Days", (forcing.dim_t - 1) // 48))
     rows = min(days * 48, forcing.dim_t - 1)
     if ens.get("Points"):
-        return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels)
+        return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels, filt)
     lo, hi = multigpu.shard(n_members, ranks.rank, ranks.world)
     if hi <= lo:
         raise ValueError(f" Ensemble: {n_members} members do not shard over {ranks.world} GPUs (a rank would be empty).")
@@ -163,7 +175,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     sim = EnsembleSimulation(cols, forcing, hi - lo, seed=int(ens.get("Seed", 0)), device=device, member_offset=lo,
                              noise=str(ens.get("Noise", "philox")).lower(),
                              spinup=str(ens.get("Spinup", "shared")).lower(), profile_stride=stride,
-                             wtd_hist_stride=dist_stride)
+                             wtd_hist_stride=dist_stride, **_filter_kwargs(filt))
     label = f"Ensemble x{n_members}"
     _step_all(sim, rows, label, ranks)
     # the run's one collective: int64 (count, sum idx, sum idx^2) per row, exact and order-independent
@@ -190,11 +202,15 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     tables, crps_line = _reduce_optional(ranks, sim, [0], [cols], forcing, stride, dist_stride, dist_levels, device,
                                          label, keep_points=False)
     extra.update(tables)
+    ftables, filter_line = _reduce_filter(ranks, sim, [0], 1, forcing.dim_t, filt, label, keep_points=False)
+    extra.update(ftables)
     arrays = dict(moments=moments, wtd_mean_cm=mean_cm, wtd_std_cm=std_cm, rows=np.array(rows),
                   members=np.array(n_members), gpus=np.array(ranks.world), initial_cond=psi0, **extra)
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "ensemble water-table statistics", ranks)
     if crps_line:
         print(crps_line)
+    if filter_line:
+        print(filter_line)
     sim.close()
 
 
@@ -228,6 +244,79 @@ def distribution_settings(ens):
             raise ValueError(f" Ensemble: Distribution.Quantiles: {q!r} lies outside [0, 1].")
     stride = int(stride)
     return (stride, tuple(float(q) for q in levels)) if stride else (0, None)
+
+
+FILTER_KEYS = ("Stride", "Sigma_cm", "Seed")
+
+
+def filter_settings(ens, n_gpus=1):
+    """Ensemble.Filter -> (stride, sigma_cm, seed or None = the ensemble's seed); (0, None, None) when absent or off.  Pure:
+    runs before any GPU call, and a bad value is a ValueError (message + exit status 1).  A single-point ensemble on more
+    than one GPU is refused: resampling would have to move states between ranks."""
+    import math
+    from numbers import Integral, Real
+    block = ens.get("Filter")
+    if block is None:
+        return 0, None, None
+    if not isinstance(block, dict):
+        raise ValueError(f" Ensemble: Filter = {block!r} must be an object such as "
+                         f"{{\"Stride\": 48, \"Sigma_cm\": 10.0}}.")
+    unknown = sorted(set(block) - set(FILTER_KEYS))
+    if unknown:
+        raise ValueError(f" Ensemble: Filter has unknown keys {unknown} (known: {list(FILTER_KEYS)}).")
+    stride = block.get("Stride", 48)
+    if (isinstance(stride, bool) or not isinstance(stride, Real) or not math.isfinite(stride) or stride != int(stride)
+            or stride < 0 or stride > (1 << 31) - 1):
+        raise ValueError(f" Ensemble: Filter.Stride = {stride!r} must be a row stride >= 0 (0: off).")
+    if "Sigma_cm" not in block:
+        raise ValueError(" Ensemble: Filter.Sigma_cm (the observation error of the well, cm) is required.")
+    sigma = block["Sigma_cm"]
+    if isinstance(sigma, bool) or not isinstance(sigma, Real) or not math.isfinite(sigma) or not sigma > 0:
+        raise ValueError(f" Ensemble: Filter.Sigma_cm = {sigma!r} must be a finite number > 0.")
+    seed = block.get("Seed")
+    if seed is not None and (isinstance(seed, bool) or not isinstance(seed, Integral) or not 0 <= seed < (1 << 64)):
+        raise ValueError(f" Ensemble: Filter.Seed = {seed!r} must be an integer in [0, 2^64).")
+    stride = int(stride)
+    if not stride:
+        return 0, None, None
+    if not ens.get("Points") and int(n_gpus) > 1:
+        raise ValueError(f" Ensemble: Filter with one parameter point runs on one GPU ({n_gpus} requested): resampling "
+                         f"would move members between ranks.")
+    return stride, float(sigma), (None if seed is None else int(seed))
+
+
+def _filter_kwargs(filt):
+    stride, sigma, seed = filt
+    return dict(filter_stride=stride, filter_sigma_cm=sigma, filter_seed=seed) if stride else {}
+
+
+def _reduce_filter(ranks, sim, ids, P, T, filt, label, keep_points):
+    """The filter's datasets from this rank's handle ``sim`` (None: no points), its points ``ids`` placed in the run's [P]
+    table and summed over the ranks (float64 as int64 bits: ``multigpu.place_points``), and the closing line (rank 0)."""
+    import numpy as np
+    from .multigpu import place_points
+    from .stepper import filter_summary, stride_rows
+    stride, sigma, _ = filt
+    if not stride:
+        return {}, None
+    n_arow = stride_rows(T, stride)
+    local = sim.filter_table().reshape(-1, n_arow, 4) if sim is not None else np.zeros((0, n_arow, 4))
+    table = place_points(local, ids, P, ranks)
+    summary = filter_summary(table if keep_points else table[0], stride, sigma)
+    out = {"filter_rows": summary["rows"], "filter_count": summary["count"], "filter_ess": summary["ess"],
+           "filter_loglik_rows": summary["loglik_rows"], "filter_survivors": summary["survivors"],
+           "filter_loglik": np.asarray(summary["loglik"], dtype=np.float64),
+           "filter_sigma_cm": np.array(sigma, dtype=np.float64)}
+    n = int(summary["rows"].size)
+    if ranks.rank != 0:
+        return out, None
+    if keep_points:
+        ll = np.asarray(summary["loglik"], dtype=np.float64)
+        best = int(np.nanargmax(ll)) if np.isfinite(ll).any() else 0
+        line = f" [{label}] filter log-likelihood: best point {best} = {ll[best]:.3f} over {n} rows"
+    else:
+        line = f" [{label}] filter log-likelihood = {float(summary['loglik']):.3f} over {n} rows"
+    return out, line
 
 
 def _distribution_datasets(hist, dist):
@@ -317,7 +406,8 @@ def _reduce_optional(ranks, sim, ids, cols_all, forcing, stride, dist_stride, di
     return out, crps_line
 
 
-def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride=0, dist_levels=None):
+def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride=0, dist_levels=None,
+               filt=(0, None, None)):
     """Parameter points x members: this rank's points in one handle (ensemble.SweepSimulation), the whole table assembled
     over the ranks (multigpu.assemble_points)."""
     import numpy as np
@@ -343,7 +433,7 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     label = f"Sweep {P} points x{n_members}"
     if mine:
         sim = SweepSimulation(points, forcing, n_members, seed=int(ens.get("Seed", 0)), device=device, point_ids=mine,
-                              profile_stride=stride, wtd_hist_stride=dist_stride)
+                              profile_stride=stride, wtd_hist_stride=dist_stride, **_filter_kwargs(filt))
         _step_all(sim, rows, label, ranks)
         table = sim.moments()
         for j, k in enumerate(mine):
@@ -357,11 +447,15 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     tables, crps_line = _reduce_optional(ranks, sim, mine, cols_all, forcing, stride, dist_stride, dist_levels, device,
                                          label, keep_points=True)
     arrays.update(tables)
+    ftables, filter_line = _reduce_filter(ranks, sim, mine, P, T, filt, label, keep_points=True)
+    arrays.update(ftables)
     if sim is not None:
         sim.close()
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "sweep's water-table statistics", ranks)
     if crps_line:
         print(crps_line)
+    if filter_line:
+        print(filter_line)
 
 
 def run_cli(argv=None):
@@ -380,6 +474,12 @@ def run_cli(argv=None):
         from . import multigpu
         settings = _read_parameters(args.params)
         n_gpus = multigpu.requested_gpus(args.gpus, settings)
+        if settings.get("Ensemble") and n_gpus > 1 and not multigpu.in_rank():
+            try:                                    # a bad Filter block ends the command before any rank starts
+                filter_settings(settings["Ensemble"], n_gpus)
+            except ValueError as bad:
+                print(bad)
+                sys.exit(1)
         if n_gpus > 1 and not multigpu.in_rank():
             # the parent only starts the ranks (nothing here has touched a GPU) and hands their exit status on
             script = Path(argv[0]).resolve()

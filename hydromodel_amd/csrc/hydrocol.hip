@@ -162,6 +162,20 @@ struct hc_handle {
     // ensemble water-table histograms (hc_set_wtd_hist): int32 [P][n_hrow][D], keyed like the profile table
     int hist_stride = 0;         // 0: off
     AccTable<int> hist{"entries"};
+    // particle filter on the well's water table (hc_set_filter): diagnostics float64 [P][n_arow][4] keyed by
+    // (points, rows, stride), the second state / base buffers of the gather, the last assimilation's q_b, {Q, r} and
+    // ancestors (test hooks), and the host copy of wtd_obs that decides which rows are assimilated
+    int filt_stride = 0;         // 0: off
+    double filt_sigma = 0.0;
+    uint64_t filt_seed = 0;
+    bool filt_done = false;      // an assimilation has run since the filter was set
+    bool filt_host() const { return filt_stride > 0 && philox; }   // Philox noise handed to the kernel as caller noise
+    AccTable<double> filt{"entries"};
+    DevBuf<double> psi_alt, base_alt;
+    DevBuf<long long> filt_q, filt_anc, filt_tiles, filt_rows;
+    DevBuf<unsigned long long> filt_qr, filt_surv;
+    std::vector<long long> filt_rows_host;
+    std::vector<int> h_wtd_obs;
     int n_cu = 256;
     double jac_reject = NUM_JAC_DIFF_REJECT;
 };
@@ -491,6 +505,286 @@ __global__ __launch_bounds__(256) void wtd_dist_kernel(const int *hist, const in
     }
 }
 
+// ---- particle filter on the well's water table (hc_set_filter, include/hydrocol.h)
+// Everything the ancestry depends on is an integer: q_b, the prefix sums C_m, the draw r and the slot ranges.  The
+// floating-point parts (l_b, W, the increment, the ESS quotient) run with contraction off, so that a NumPy restatement
+// of the same expressions agrees to the last few ulps.
+constexpr int FILT_THREADS = 256;
+constexpr int FILT_PER_THREAD = 4;
+constexpr long long FILT_TILE = FILT_THREADS * FILT_PER_THREAD;    // members per block of the prefix scan
+
+// 128-bit unsigned integer -> (x_hi + x_lo) in double-double: four exact 32-bit limbs, summed with error terms
+__device__ void u128_to_dd(unsigned long long hi, unsigned long long lo, double &x_hi, double &x_lo)
+{
+    const double v[4] = {(double)(hi >> 32) * 0x1p96, (double)(hi & 0xffffffffull) * 0x1p64, (double)(lo >> 32) * 0x1p32,
+                         (double)(lo & 0xffffffffull)};
+    double s = v[0], err = 0.0;
+    for (int k = 1; k < 4; k++) {
+        double t, e;
+        two_sum(s, v[k], t, e);
+        s = t;
+        err += e;
+    }
+    two_sum(s, err, x_hi, x_lo);
+}
+
+// the Philox value of the filter's draw at (seed, point key, row).  The counter's first word is 0xFFFFFFFF: a noise
+// draw's first word is a depth index / 2 (< HC_MAX_DEPTH_NODES / 2), so the two never share a counter under one key.
+__device__ __forceinline__ unsigned long long filter_philox64(unsigned long long seed, unsigned long long point_key,
+                                                              unsigned row)
+{
+    uint32_t r[4];
+    philox4x32_10(0xFFFFFFFFu, row, (uint32_t)point_key, (uint32_t)(point_key >> 32), (uint32_t)seed,
+                  (uint32_t)(seed >> 32), r);
+    return ((unsigned long long)r[1] << 32) | r[0];
+}
+
+// One block per point: bin counts n_b of the assimilation row's water-table indices (grouped by ballots as in
+// wtd_hist_kernel), then one thread forms s, q_b, W, the exact sums of the ESS, the increment and the draw.
+// qr[p] = {Q, r}; stats row = {count, ESS, increment, survivors (written by filter_fill_kernel's finish)}.
+__global__ __launch_bounds__(FILT_THREADS) void filter_weights_kernel(
+    const unsigned short *w, long long members_per_point, int D, int obs, double dz, double sigma, unsigned long long seed,
+    const long long *point_base, long long member_offset, unsigned row, long long n_arow, long long slot, long long *q_out,
+    unsigned long long *qr, double *stats, unsigned long long *surv)
+{
+#pragma clang fp contract(off)
+    __shared__ unsigned bins[HC_MAX_DEPTH_NODES];
+    __shared__ long long qsh[HC_MAX_DEPTH_NODES];
+    for (int b = threadIdx.x; b < D; b += FILT_THREADS) bins[b] = 0;
+    __syncthreads();
+    const long long p = blockIdx.x;
+    const long long m0 = p * members_per_point, m1 = m0 + members_per_point;
+    const int lane = threadIdx.x % WAVE;
+    for (long long k0 = m0 + (threadIdx.x - lane); k0 < m1; k0 += FILT_THREADS) {
+        const long long k = k0 + lane;
+        const int b = k < m1 ? (int)w[k] : -1;
+        unsigned long long pending = __ballot(b >= 0 && b < D);
+        while (pending) {
+            const int leader = __ffsll((long long)pending) - 1;
+            const int v = __builtin_amdgcn_readlane(b, leader);
+            const unsigned long long same = __ballot(b == v) & pending;
+            if (lane == leader) atomicAdd(&bins[v], (unsigned)__popcll(same));
+            pending &= ~same;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        // l_b = -0.5 (dz (b - o) / sigma)^2; s = max over the occupied bins
+        double s = -INFINITY;
+        long long n = 0;
+        for (int b = 0; b < D; b++)
+            if (bins[b]) {
+                const double t = dz * (double)(b - obs) / sigma;
+                const double l = -0.5 * (t * t);
+                s = l > s ? l : s;
+                n += bins[b];
+            }
+        double W = 0.0;
+        unsigned long long Q = 0, b_hi = 0, b_lo = 0;
+        for (int b = 0; b < D; b++) {
+            long long q = 0;
+            if (bins[b]) {
+                const double t = dz * (double)(b - obs) / sigma;
+                const double e = exp(-0.5 * (t * t) - s);
+                q = (long long)floor(0x1p31 * e);              // 2^31 at the nearest occupied bin, 0 below ~2^-31
+                W += (double)bins[b] * e;
+                const unsigned long long uq = (unsigned long long)q, nb = bins[b];
+                Q += nb * uq;                                  // < 2^31 members x 2^31
+                const unsigned long long sq = uq * uq;         // < 2^62
+                add_u128(b_hi, b_lo, __umul64hi(sq, nb), sq * nb);
+            }
+            qsh[b] = q;
+        }
+        double *st = stats + ((size_t)p * n_arow + slot) * 4;
+        st[0] = (double)n;
+        if (n > 0 && Q > 0) {
+            // ESS = Q^2 / sum n_b q_b^2: both exact, the quotient from a double-double correction (within 2 ulp)
+            double a_hi, a_lo, d_hi, d_lo;
+            u128_to_dd(__umul64hi(Q, Q), Q * Q, a_hi, a_lo);
+            u128_to_dd(b_hi, b_lo, d_hi, d_lo);
+            const double q1 = a_hi / d_hi;
+            const double rr = fma(-q1, d_hi, a_hi) + a_lo - q1 * d_lo;
+            st[1] = q1 + rr / d_hi;
+            st[2] = s + log(W / (double)n) - log(sigma) - 0.5 * log(2.0 * M_PI);
+        } else {
+            st[1] = __builtin_nan("");
+            st[2] = __builtin_nan("");
+        }
+        const unsigned long long key = point_base ? (unsigned long long)point_base[p]
+                                                  : (unsigned long long)(member_offset + p * members_per_point);
+        const unsigned long long x = filter_philox64(seed, key, row);
+        qr[2 * p] = Q;
+        qr[2 * p + 1] = __umul64hi(x, Q);                      // r = floor(x Q / 2^64) < Q
+        surv[p] = 0;
+    }
+    __syncthreads();
+    for (int b = threadIdx.x; b < D; b += FILT_THREADS) q_out[(size_t)p * D + b] = qsh[b];
+}
+
+__device__ __forceinline__ long long filter_q(const unsigned short *w, const long long *q, int D, long long k)
+{
+    const int b = (int)w[k];
+    return b < D ? q[b] : 0;
+}
+
+// inclusive wave64 scan of one value per lane (shuffles), then the block's exclusive offsets through LDS
+__device__ __forceinline__ long long block_exclusive_scan(long long v, long long &total)
+{
+    __shared__ long long wsum[FILT_THREADS / WAVE];
+    const int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
+    long long incl = v;
+    for (int d = 1; d < WAVE; d <<= 1) {
+        const long long u = __shfl_up(incl, d);
+        if (lane >= d) incl += u;
+    }
+    if (lane == WAVE - 1) wsum[wave] = incl;
+    __syncthreads();
+    long long before = 0;
+    total = 0;
+    for (int u = 0; u < FILT_THREADS / WAVE; u++) {
+        if (u < wave) before += wsum[u];
+        total += wsum[u];
+    }
+    __syncthreads();              // wsum may be reused by the next call
+    return before + incl - v;
+}
+
+// the sum of q_m over each tile of FILT_TILE members of a point: tiles[p][t]
+__global__ __launch_bounds__(FILT_THREADS) void filter_tile_sum_kernel(const unsigned short *w, const long long *q_all,
+                                                                       long long members_per_point, int D, long long n_tiles,
+                                                                       long long *tiles)
+{
+    const long long p = blockIdx.y, t = blockIdx.x;
+    const long long *q = q_all + (size_t)p * D;
+    const long long first = p * members_per_point, m0 = t * FILT_TILE;
+    long long v = 0;
+    for (int j = 0; j < FILT_PER_THREAD; j++) {
+        const long long m = m0 + (long long)threadIdx.x * FILT_PER_THREAD + j;
+        if (m < members_per_point) v += filter_q(w, q, D, first + m);
+    }
+    long long total;
+    (void)block_exclusive_scan(v, total);
+    if (threadIdx.x == 0) tiles[(size_t)p * n_tiles + t] = total;
+}
+
+// the block-offset pass: tiles[p][*] -> their exclusive prefix sums, one block per point in rounds of FILT_THREADS tiles
+__global__ __launch_bounds__(FILT_THREADS) void filter_tile_scan_kernel(long long n_tiles, long long *tiles)
+{
+    long long *t = tiles + (size_t)blockIdx.x * n_tiles;
+    long long carry = 0;
+    for (long long k0 = 0; k0 < n_tiles; k0 += FILT_THREADS) {
+        const long long k = k0 + threadIdx.x;
+        const long long v = k < n_tiles ? t[k] : 0;
+        long long total;
+        const long long ex = block_exclusive_scan(v, total);
+        if (k < n_tiles) t[k] = carry + ex;
+        carry += total;
+    }
+}
+
+// Member m of point p (C_m = its exclusive prefix sum of q in member order) fills the slots
+// k in [ceil((C_m N_p - r) / Q), ceil(((C_m + q_m) N_p - r) / Q)) with its handle-local index; survivors are counted.
+__device__ __forceinline__ long long filter_slot(unsigned long long c, unsigned long long Np, unsigned long long r,
+                                                 unsigned long long Q)
+{
+    const unsigned __int128 num = (unsigned __int128)c * Np;
+    if (num <= r) return 0;
+    return (long long)((num - r + (Q - 1)) / Q);
+}
+
+__global__ __launch_bounds__(FILT_THREADS) void filter_fill_kernel(const unsigned short *w, const long long *q_all,
+                                                                   long long members_per_point, int D, long long n_tiles,
+                                                                   const long long *tiles, const unsigned long long *qr,
+                                                                   long long *anc, unsigned long long *surv)
+{
+    const long long p = blockIdx.y, t = blockIdx.x;
+    const long long *q = q_all + (size_t)p * D;
+    const long long first = p * members_per_point, m0 = t * FILT_TILE + (long long)threadIdx.x * FILT_PER_THREAD;
+    const unsigned long long Q = qr[2 * p], r = qr[2 * p + 1], Np = (unsigned long long)members_per_point;
+    long long qm[FILT_PER_THREAD], v = 0;
+    for (int j = 0; j < FILT_PER_THREAD; j++) {
+        const long long m = m0 + j;
+        qm[j] = m < members_per_point ? filter_q(w, q, D, first + m) : 0;
+        v += qm[j];
+    }
+    long long total;
+    unsigned long long c = (unsigned long long)(tiles[(size_t)p * n_tiles + t] + block_exclusive_scan(v, total));
+    unsigned alive = 0;
+    const int lane = threadIdx.x % WAVE;
+    // every lane runs every round (ballots below): members past the point's end have an empty range
+    for (int j = 0; j < FILT_PER_THREAD; j++) {
+        const long long m = m0 + j;
+        long long k0 = 0, k1 = 0;
+        if (m < members_per_point) {
+            if (Q == 0) {                   // no member counted: the ancestry stays the identity
+                k0 = m, k1 = m + 1;
+            } else {
+                k0 = filter_slot(c, Np, r, Q);
+                k1 = filter_slot(c + (unsigned long long)qm[j], Np, r, Q);
+            }
+            k1 = k1 < members_per_point ? k1 : members_per_point;
+        }
+        // a short range is written by its own lane; a long one (weight concentrated on a few members: up to N_p slots)
+        // by the whole wave, one such range after the other, 64 consecutive slots per store
+        const bool wide = k1 - k0 > WAVE;
+        if (!wide)
+            for (long long k = k0; k < k1; k++) anc[first + k] = first + m;
+        for (unsigned long long pend = __ballot(wide); pend; pend &= pend - 1) {
+            const int src = __ffsll((long long)pend) - 1;
+            const long long a = __shfl(k0, src), b = __shfl(k1, src), v = __shfl(first + m, src);
+            for (long long k = a + lane; k < b; k += WAVE) anc[first + k] = v;
+        }
+        alive += k1 > k0 ? 1u : 0u;
+        c += m < members_per_point ? (unsigned long long)qm[j] : 0ull;
+    }
+    for (int o = WAVE / 2; o > 0; o >>= 1) alive += __shfl_xor(alive, o);
+    if (threadIdx.x % WAVE == 0 && alive) atomicAdd(surv + p, (unsigned long long)alive);
+}
+
+__global__ void filter_survivors_kernel(const unsigned long long *surv, int n_points, long long n_arow, long long slot,
+                                        double *stats)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n_points) stats[((size_t)p * n_arow + slot) * 4 + 3] = (double)surv[p];
+}
+
+// slot k takes the state and the base noise vector of its ancestor (into the second buffers; the host swaps them in)
+__global__ void filter_gather_kernel(const long long *anc, const double *psi, const double *base, double *psi_out,
+                                     double *base_out, long long n_members, int D)
+{
+    const size_t total = (size_t)n_members * D;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const long long k = (long long)(e / D), a = anc[k];
+        const size_t src = (size_t)(a >= 0 && a < n_members ? a : k) * D + e % D;     // (every slot is filled: a guard)
+        psi_out[e] = psi[src];
+        if (base) base_out[e] = base[src];
+    }
+}
+
+// a filtered Philox run hands the step kernel caller-style noise made from the kernel's own normals: n_vec vectors
+// [n_vec][N][D]; rows == NULL: the base vectors (draw 0) times the member's scale, else the refresh rows rows[v] with
+// their draw indices.  A member's stream is keyed by its slot (member_offset + m, or the point's base + j).
+__global__ void filter_philox_fill_kernel(double *out, long long n_vec, const long long *rows, const int *draw_idx,
+                                          unsigned long long seed, long long member_offset, const long long *point_base,
+                                          long long members_per_point, long long n_members, int D, const double *nscale)
+{
+    const size_t per = (size_t)n_members * D, total = per * (size_t)n_vec;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const long long v = (long long)(e / per), m = (long long)((e % per) / D);
+        const int i = (int)(e % D);
+        const unsigned draw = rows ? (unsigned)draw_idx[rows[v]] : 0u;
+        const long long gid = point_base ? point_base[m / members_per_point] + m % members_per_point : member_offset + m;
+        const double z = philox_normal(seed, (unsigned long long)gid, draw, (unsigned)i);
+        out[e] = nscale ? z * nscale[m] : z;
+    }
+}
+
+__global__ void filter_stats_init_kernel(double *stats, size_t n)
+{
+    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n) stats[k] = k % 4 == 0 ? 0.0 : __builtin_nan("");
+}
+
 __global__ void widen_u16(const unsigned short *in, int *out, size_t n)
 {
     size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -777,6 +1071,36 @@ int ensure_hist(hc_handle *h)
     return h->hist.ensure(h->n_points, h->n_rows, h->p.dim_d, hist_entries(h));
 }
 
+// the particle filter's diagnostics (hc_set_filter): [P][n_arow][4] float64, created as count 0 and NaN
+int64_t filter_rows(const hc_handle *h) { return (h->n_rows - 1) / h->filt_stride + 1; }
+int ensure_filter(hc_handle *h)
+{
+    if (h->filt_stride <= 0) return fail(HC_ERR_ARG, "the particle filter is off (hc_set_filter)");
+    if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
+    AccTable<double> &t = h->filt;
+    const bool fresh = !(t.key[0] == h->n_points && t.key[1] == h->n_rows && t.key[2] == h->filt_stride);
+    const int64_t n = (int64_t)h->n_points * filter_rows(h) * 4;
+    if (int rc = t.ensure(h->n_points, h->n_rows, h->filt_stride, n)) return rc;
+    if (fresh) {
+        hipLaunchKernelGGL(filter_stats_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, t.buf.p,
+                           (size_t)n);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    return HC_OK;
+}
+
+// what turns the filter off: new points, members or noise source (include/hydrocol.h hc_set_filter)
+void filter_off(hc_handle *h)
+{
+    h->filt_stride = 0;
+    h->filt_done = false;
+    h->filt.release();
+    h->psi_alt.release(); h->base_alt.release();
+    h->filt_q.release(); h->filt_anc.release(); h->filt_tiles.release(); h->filt_rows.release();
+    h->filt_qr.release(); h->filt_surv.release();
+}
+
 // The bodies of the table entry points: the table as `ensure` leaves it (its rules and refusals), a size check when the
 // caller names one (n >= 0), the stream drained, one copy of the whole table: host -> table, table -> host or
 // table -> device memory elsewhere (`kind`).
@@ -871,13 +1195,13 @@ int fill_args(hc_handle *h, StepArgs &A)
     A.n_members = h->n_members;
     A.D = h->P.D;
     A.n_groups = h->P.n_groups;
-    A.host_noise = h->philox ? 0 : 1;
+    A.host_noise = h->philox && !h->filt_host() ? 0 : 1;   // a filtered Philox run hands its normals over as caller noise
     A.psi_sat = h->P.psi_sat;
     A.jac_reject = h->jac_reject;
     A.max_phase_iterations = h->max_phase_iterations;
     A.scipy_152 = h->scipy_152;
     io.psi = h->psi.p;
-    io.base_noise = h->philox ? nullptr : h->base.p;
+    io.base_noise = A.host_noise ? h->base.p : nullptr;
     io.nscale = h->nscale.p;
     io.precip = h->precip.p;
     io.atm = h->atm.p;
@@ -1000,6 +1324,7 @@ int hc_destroy(hc_handle *h)
     h->point_base.release(); h->point_order.release(); h->point_cost.release();
     h->daylight.release(); h->refresh.release(); h->wtd_u16.release(); h->moments.release(); h->counters.release();
     h->prof.release(); h->hist.release();
+    filter_off(h);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1098,6 +1423,10 @@ static int build_point(hc_handle *h, const hc_column_params *p, const double *no
     } else {
         h->special = h->special && special;
     }
+    if (h->filt_stride > 0) {                    // the points change: the filter is off
+        (void)hipStreamSynchronize(h->stream);
+        filter_off(h);
+    }
     h->P_host.push_back(P);
     h->tab_host.insert(h->tab_host.end(), tab.begin(), tab.end());
     h->node_host.insert(h->node_host.end(), node_tabs, node_tabs + (size_t)3 * D);
@@ -1192,6 +1521,7 @@ int hc_set_forcing(hc_handle *h, int64_t n_rows, const double *precip, const dou
     HIP_TRY(hipMemcpy(h->wtd_obs.p, wtd_obs, T * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->draw_idx.p, draw.data(), T * 4, hipMemcpyHostToDevice));
     h->h_refresh.assign(refresh, refresh + T);
+    h->h_wtd_obs.assign(wtd_obs, wtd_obs + T);
     h->n_rows = n_rows;
     h->moments.invalidate();     // (re)allocated and zeroed by the next call that needs the moment tables
     h->have_forcing = true;
@@ -1212,6 +1542,7 @@ int hc_set_forcing_row(hc_handle *h, int64_t row, double precip, double atm, uin
     HIP_TRY(hipMemcpy(h->wtd_obs.p + row, &wtd_obs, 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->refresh.p + row, &zero, 1, hipMemcpyHostToDevice));
     h->h_refresh[(size_t)row] = 0;
+    h->h_wtd_obs[(size_t)row] = wtd_obs;
     return HC_OK;
 }
 
@@ -1220,6 +1551,8 @@ int hc_set_members(hc_handle *h, int64_t n_members)
     if (!h || n_members < 1) return fail(HC_ERR_ARG, "hc_set_members: bad argument");
     if (!h->have_column) return fail(HC_ERR_ARG, "hc_set_column must come first");
     HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    filter_off(h);
     const size_t n = (size_t)n_members * h->p.dim_d;
     if (h->psi.ensure(n) || h->nscale.ensure((size_t)n_members)) return HC_ERR_DEVICE;
     hipLaunchKernelGGL(fill_d, dim3((unsigned)((n_members + 255) / 256)), dim3(256), 0, h->stream, h->nscale.p, 1.0,
@@ -1273,6 +1606,8 @@ int hc_set_noise_host(hc_handle *h, const double *base)
     if (!h || !base) return fail(HC_ERR_ARG, "hc_set_noise_host: bad argument");
     if (h->n_members <= 0) return fail(HC_ERR_ARG, "hc_set_members must come first");
     HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    filter_off(h);
     const size_t n = (size_t)h->n_members * h->p.dim_d;
     if (h->base.ensure(n)) return HC_ERR_DEVICE;
     HIP_TRY(hipMemcpy(h->base.p, base, n * 8, hipMemcpyHostToDevice));
@@ -1297,6 +1632,8 @@ int hc_set_noise_philox(hc_handle *h, uint64_t seed, int64_t member_offset)
     if (!h || member_offset < 0) return fail(HC_ERR_ARG, "hc_set_noise_philox: bad argument");
     if (h->n_members <= 0) return fail(HC_ERR_ARG, "hc_set_members must come first");
     HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    filter_off(h);
     hipLaunchKernelGGL(fill_d, dim3((unsigned)((h->n_members + 255) / 256)), dim3(256), 0, h->stream, h->nscale.p,
                        1.0, (size_t)h->n_members);
     HIP_TRY(hipGetLastError());
@@ -1416,6 +1753,16 @@ struct Chunk {
 //    members' current states (no staging at all);
 //  shorter strides: every row of the launch is staged through psi_rows (as psi_rows_out does), the launch
 //    shortened to the cap, and the profile rows are read from there.
+// a filtered Philox run stages the launch's refresh vectors (N D doubles each) on the device: about 4 GiB at most
+constexpr int64_t FILT_FRESH_BYTES = int64_t(4) << 30;
+
+bool is_assimilation_row(const hc_handle *h, int64_t row)
+{
+    return h->filt_stride > 0 && row >= 1 && row % h->filt_stride == 0 && h->h_wtd_obs[(size_t)row] >= 0;
+}
+
+// The launch after `done` rows of the request.  With the filter on, a launch ends on the next assimilation row and, in a
+// filtered Philox run, holds at most as many refresh rows as FILT_FRESH_BYTES admits.
 Chunk plan_chunk(const hc_handle *h, const hc_step_args *a, int64_t done, bool prof_on)
 {
     const int64_t N = h->n_members, D = h->p.dim_d;
@@ -1430,6 +1777,23 @@ Chunk plan_chunk(const hc_handle *h, const hc_step_args *a, int64_t done, bool p
     Chunk c;
     c.rows = (int)std::min<int64_t>(per_launch, a->n_rows - done);
     c.row0 = a->spinup ? a->row_begin : a->row_begin + done;
+    if (h->filt_stride > 0 && !a->spinup) {
+        const int64_t s = h->filt_stride;
+        for (int64_t r = std::max<int64_t>(s, (c.row0 + s - 1) / s * s); r < c.row0 + c.rows; r += s)
+            if (is_assimilation_row(h, r)) {
+                c.rows = (int)(r - c.row0 + 1);
+                break;
+            }
+        if (h->filt_host()) {
+            const int64_t cap = std::max<int64_t>(1, FILT_FRESH_BYTES / (N * D * 8));
+            int64_t n_fresh = 0;
+            for (int r = 0; r < c.rows; r++)
+                if (h->h_refresh[(size_t)(c.row0 + r)] && ++n_fresh > cap) {
+                    c.rows = r;
+                    break;
+                }
+        }
+    }
     if (!prof_on) return c;
     const int64_t s = h->prof_stride, diag_row = N * 2 * 8, row_bytes = N * D * 8;
     c.rows = (int)std::min<int64_t>(c.rows, std::max<int64_t>(1, PROF_DIAG_BYTES / diag_row));
@@ -1454,7 +1818,25 @@ int stage_noise(hc_handle *h, const hc_step_args *a, const Chunk &c, int64_t con
     n_fresh = 0;
     if (!a->spinup)
         for (int r = 0; r < c.rows; r++) n_fresh += h->h_refresh[(size_t)(c.row0 + r)] ? 1 : 0;
-    if (h->philox || n_fresh == 0) return HC_OK;
+    if (n_fresh == 0) return HC_OK;
+    if (h->filt_host()) {
+        // the kernel's own normals of the launch's refresh rows, keyed by each slot's stream and the row's draw index
+        h->filt_rows_host.clear();
+        for (int r = 0; r < c.rows; r++)
+            if (h->h_refresh[(size_t)(c.row0 + r)]) h->filt_rows_host.push_back(c.row0 + r);
+        const size_t cnt = (size_t)n_fresh * N * D;
+        if (h->fresh.ensure(cnt) || h->filt_rows.ensure((size_t)n_fresh)) return HC_ERR_DEVICE;
+        HIP_TRY(hipMemcpyAsync(h->filt_rows.p, h->filt_rows_host.data(), (size_t)n_fresh * 8, hipMemcpyHostToDevice,
+                               h->stream));
+        const unsigned blocks = (unsigned)std::min<size_t>((cnt + 255) / 256, (size_t)h->n_cu * 64);
+        hipLaunchKernelGGL(filter_philox_fill_kernel, dim3(blocks), dim3(256), 0, h->stream, h->fresh.p, (long long)n_fresh,
+                           h->filt_rows.p, h->draw_idx.p, (unsigned long long)h->seed, (long long)h->member_offset,
+                           h->n_points > 1 ? h->point_base.p : nullptr, (long long)(N / h->n_points), (long long)N,
+                           (int)D, nullptr);
+        HIP_TRY(hipGetLastError());
+        return HC_OK;
+    }
+    if (h->philox) return HC_OK;
     if (!a->fresh_noise) return fail(HC_ERR_ARG, "host noise mode: fresh_noise is NULL but rows refresh");
     const size_t cnt = (size_t)n_fresh * N * D;
     if (h->fresh.ensure(cnt)) return HC_ERR_DEVICE;
@@ -1547,6 +1929,52 @@ int copy_outputs(hc_handle *h, hc_step_args *a, const Chunk &c, int64_t done)
     return HC_OK;
 }
 
+// The assimilation at the launch's last row (its water-table indices are wtd_u16's last row): weights, diagnostics and
+// draw per point, the member prefix scan, the slot fill, then psi and base gathered into the second buffers and swapped in.
+int assimilate(hc_handle *h, const Chunk &c)
+{
+    const int64_t N = h->n_members, D = h->p.dim_d, P = h->n_points, mpp = N / P;
+    const int64_t row = c.row0 + c.rows - 1, slot = row / h->filt_stride, n_arow = filter_rows(h);
+    const int64_t n_tiles = (mpp + FILT_TILE - 1) / FILT_TILE;
+    if (h->filt_q.ensure((size_t)(P * D)) || h->filt_qr.ensure((size_t)(2 * P)) || h->filt_surv.ensure((size_t)P) ||
+        h->filt_tiles.ensure((size_t)(P * n_tiles)) || h->filt_anc.ensure((size_t)N) || h->psi_alt.ensure((size_t)(N * D)))
+        return HC_ERR_DEVICE;
+    if (h->base.ensure((size_t)(N * D)) || h->base_alt.ensure((size_t)(N * D))) return HC_ERR_DEVICE;
+    const unsigned short *w = h->wtd_u16.p + (size_t)(c.rows - 1) * N;
+    const long long *pbase = P > 1 ? h->point_base.p : nullptr;
+    hipLaunchKernelGGL(filter_weights_kernel, dim3((unsigned)P), dim3(FILT_THREADS), 0, h->stream, w, (long long)mpp,
+                       (int)D, h->h_wtd_obs[(size_t)row], h->p.dz, h->filt_sigma, (unsigned long long)h->filt_seed, pbase,
+                       (long long)h->member_offset, (unsigned)row, (long long)n_arow, (long long)slot, h->filt_q.p,
+                       h->filt_qr.p, h->filt.buf.p, h->filt_surv.p);
+    HIP_TRY(hipGetLastError());
+    const dim3 tiles((unsigned)n_tiles, (unsigned)P);
+    hipLaunchKernelGGL(filter_tile_sum_kernel, tiles, dim3(FILT_THREADS), 0, h->stream, w, h->filt_q.p, (long long)mpp,
+                       (int)D, (long long)n_tiles, h->filt_tiles.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(filter_tile_scan_kernel, dim3((unsigned)P), dim3(FILT_THREADS), 0, h->stream, (long long)n_tiles,
+                       h->filt_tiles.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(h->filt_anc.p, 0xFF, (size_t)N * 8, h->stream));
+    hipLaunchKernelGGL(filter_fill_kernel, tiles, dim3(FILT_THREADS), 0, h->stream, w, h->filt_q.p, (long long)mpp, (int)D,
+                       (long long)n_tiles, h->filt_tiles.p, h->filt_qr.p, h->filt_anc.p, h->filt_surv.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(filter_survivors_kernel, dim3((unsigned)((P + 63) / 64)), dim3(64), 0, h->stream, h->filt_surv.p,
+                       (int)P, (long long)n_arow, (long long)slot, h->filt.buf.p);
+    HIP_TRY(hipGetLastError());
+    const size_t total = (size_t)N * D;
+    const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)h->n_cu * 64);
+    hipLaunchKernelGGL(filter_gather_kernel, dim3(blocks), dim3(256), 0, h->stream, h->filt_anc.p, h->psi.p, h->base.p,
+                       h->psi_alt.p, h->base_alt.p, (long long)N, (int)D);
+    HIP_TRY(hipGetLastError());
+    std::swap(h->psi, h->psi_alt);
+    std::swap(h->base, h->base_alt);
+    // the rest of this hc_step_rows call launches on the analysis (fill_args took the pointers before the swap)
+    h->io_host.psi = h->psi.p;
+    if (h->io_host.base_noise) h->io_host.base_noise = h->base.p;
+    h->filt_done = true;
+    return HC_OK;
+}
+
 // After the launches of a call: a split-column mailbox exchange that timed out invalidates the results.  An attempt that
 // exhausts the kernel's iteration budget is abandoned like a solve that gave up (the x0.8 retry rule applies); it is
 // counted ([2], last place in [3]) and only fatal on request.
@@ -1587,6 +2015,11 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
     // each launch): spin-up solves accumulate nothing
     const bool prof_on = h->prof_stride > 0 && !a->spinup, hist_on = h->hist_stride > 0 && !a->spinup;
     if ((prof_on && (rc = ensure_prof(h))) || (hist_on && (rc = ensure_hist(h)))) return rc;
+    // the particle filter (hc_set_filter): spin-up solves are never filtered
+    if (a->spinup && h->filt_host())
+        return fail(HC_ERR_ARG, "spin-up solves with the particle filter on in a Philox run: set the filter after the spin-up");
+    const bool filt_on = h->filt_stride > 0 && !a->spinup;
+    if (filt_on && (rc = ensure_filter(h))) return rc;
     int64_t fresh_consumed = 0;
     for (int64_t done = 0; done < a->n_rows;) {
         const Chunk c = plan_chunk(h, a, done, prof_on);
@@ -1595,6 +2028,7 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
         if ((rc = launch_chunk(h, A, a, c, prof_on))) return rc;
         if ((rc = accumulate(h, A, a, c, prof_on, hist_on))) return rc;
         if ((rc = copy_outputs(h, a, c, done))) return rc;
+        if (filt_on && is_assimilation_row(h, c.row0 + c.rows - 1) && (rc = assimilate(h, c))) return rc;
         HIP_TRY(hipStreamSynchronize(h->stream));
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
@@ -1623,6 +2057,8 @@ int hc_spinup(hc_handle *h, hc_spinup_args *a)
     if (rc) return rc;
     if (a->forcing_row < 0 || a->forcing_row >= h->n_rows) return fail(HC_ERR_ARG, "spin-up forcing row out of range");
     if (a->max_iterations < 1 || a->max_iterations > 1000000) return fail(HC_ERR_ARG, "max_iterations out of range");
+    if (h->filt_host())
+        return fail(HC_ERR_ARG, "hc_spinup with the particle filter on in a Philox run: set the filter after the spin-up");
     HIP_TRY(hipSetDevice(h->device));
     const int64_t N = h->n_members;
     if (h->spin_iters.ensure((size_t)N)) return HC_ERR_DEVICE;
@@ -1852,6 +2288,117 @@ int hc_wtd_distribution(int device, const int32_t *hist, const int32_t *obs_idx,
     return rc;
 }
 
+int hc_set_filter(hc_handle *h, int32_t stride, double sigma_cm, uint64_t seed)
+{
+    if (!h || stride < 0) return fail(HC_ERR_ARG, "hc_set_filter: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    filter_off(h);
+    if (stride == 0) return HC_OK;
+    if (!(std::isfinite(sigma_cm) && sigma_cm > 0.0))
+        return fail(HC_ERR_ARG, "hc_set_filter: sigma_cm = %g must be finite and > 0", sigma_cm);
+    StepArgs A;
+    if (int rc = fill_args(h, A)) return rc;     // column, forcing, members and noise are in place; point keys uploaded
+    if (h->n_rows > (int64_t)UINT32_MAX) return fail(HC_ERR_ARG, "hc_set_filter: %lld forcing rows exceed 2^32 - 1", (long long)h->n_rows);
+    if (A.members_per_point > INT32_MAX)
+        return fail(HC_ERR_ARG, "hc_set_filter: %lld members per point exceed 2^31 - 1", (long long)A.members_per_point);
+    h->filt_stride = stride;
+    h->filt_sigma = sigma_cm;
+    h->filt_seed = seed;
+    int rc = ensure_filter(h);
+    if (rc == HC_OK && h->philox) {
+        // the base vectors the kernel's Philox path would build, z * scale (one rounding), from here on carried like
+        // the caller's: damped in place, copied from the ancestor
+        const size_t total = (size_t)h->n_members * h->p.dim_d;
+        rc = h->base.ensure(total);
+        if (rc == HC_OK) {
+            const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)h->n_cu * 64);
+            hipLaunchKernelGGL(filter_philox_fill_kernel, dim3(blocks), dim3(256), 0, h->stream, h->base.p, 1ll, nullptr,
+                               h->draw_idx.p, (unsigned long long)h->seed, (long long)h->member_offset,
+                               h->n_points > 1 ? h->point_base.p : nullptr, (long long)A.members_per_point,
+                               (long long)h->n_members, h->p.dim_d, h->nscale.p);
+            const hipError_t e = hipGetLastError();
+            const hipError_t e2 = hipStreamSynchronize(h->stream);
+            if (e != hipSuccess || e2 != hipSuccess)
+                rc = fail(HC_ERR_DEVICE, "hc_set_filter: base vectors: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+        }
+    }
+    if (rc != HC_OK) filter_off(h);              // refused: off
+    return rc;
+}
+
+int hc_get_filter_stats(hc_handle *h, double *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_get_filter_stats: bad argument");
+    return table_copy(h, h->filt, ensure_filter, hipMemcpyDeviceToHost, table, n_entries, "hc_get_filter_stats");
+}
+
+int hc_set_filter_stats(hc_handle *h, const double *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_set_filter_stats: bad argument");
+    return table_copy(h, h->filt, ensure_filter, hipMemcpyHostToDevice, const_cast<double *>(table), n_entries,
+                      "hc_set_filter_stats");
+}
+
+// the last assimilation's buffers (test hooks): a device -> host copy of `count` entries
+}  // extern "C"
+namespace {
+template <typename T>
+int filter_hook(hc_handle *h, const DevBuf<T> &b, void *out, size_t count, const char *who)
+{
+    if (!h || !out) return fail(HC_ERR_ARG, "%s: bad argument", who);
+    if (h->filt_stride <= 0 || !h->filt_done) return fail(HC_ERR_ARG, "%s: no assimilation since hc_set_filter", who);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(out, b.p, count * sizeof(T), hipMemcpyDeviceToHost));
+    return HC_OK;
+}
+}  // namespace
+extern "C" {
+
+int hc_get_filter_ancestors(hc_handle *h, int64_t *ancestors)
+{
+    return filter_hook(h, h->filt_anc, ancestors, (size_t)h->n_members, "hc_get_filter_ancestors");
+}
+
+int hc_get_filter_weights(hc_handle *h, int64_t *q)
+{
+    return filter_hook(h, h->filt_q, q, (size_t)h->n_points * h->p.dim_d, "hc_get_filter_weights");
+}
+
+int hc_get_filter_draw(hc_handle *h, int64_t *r)
+{
+    if (!h || !r) return fail(HC_ERR_ARG, "hc_get_filter_draw: bad argument");
+    std::vector<unsigned long long> qr((size_t)2 * h->n_points);
+    if (int rc = filter_hook(h, h->filt_qr, qr.data(), qr.size(), "hc_get_filter_draw")) return rc;
+    for (int p = 0; p < h->n_points; p++) r[p] = (int64_t)qr[(size_t)2 * p + 1];
+    return HC_OK;
+}
+
+int hc_get_filter_base(hc_handle *h, double *base, int64_t first, int64_t count)
+{
+    if (!h || !base || first < 0 || count < 0 || first + count > h->n_members || !h->filt_host())
+        return fail(HC_ERR_ARG, "hc_get_filter_base: bad argument (a Philox run with the particle filter on)");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const int D = h->p.dim_d;
+    HIP_TRY(hipMemcpy(base, h->base.p + (size_t)first * D, (size_t)count * D * 8, hipMemcpyDeviceToHost));
+    return HC_OK;
+}
+
+int hc_set_filter_base(hc_handle *h, const double *base)
+{
+    if (!h || !base || !h->filt_host())
+        return fail(HC_ERR_ARG, "hc_set_filter_base: bad argument (a Philox run with the particle filter on)");
+    const size_t n = (size_t)h->n_members * h->p.dim_d;
+    for (size_t i = 0; i < n; i++)
+        if (!std::isfinite(base[i])) return fail(HC_ERR_ARG, "hc_set_filter_base: entry %zu is not finite", i);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(h->base.p, base, n * 8, hipMemcpyHostToDevice));
+    return HC_OK;
+}
+
 // The path's one collective without torch: a single process that drives several devices (one handle each) sums the
 // handles' moment tables over RCCL.  RCCL is bound at run time (dlopen), so the library loads on boxes without it and
 // a process that already carries an RCCL (torch's) keeps using that one.
@@ -1944,6 +2491,9 @@ int hc_set_noise_scale(hc_handle *h, const double *scale, int64_t first, int64_t
     if (!h || !scale || first < 0 || count < 0 || first + count > h->n_members || !h->nscale.p)
         return fail(HC_ERR_ARG, "hc_set_noise_scale: bad argument");
     if (!h->philox) return fail(HC_ERR_ARG, "hc_set_noise_scale: call hc_set_noise_philox first (it resets the scales to 1)");
+    if (h->filt_host())
+        return fail(HC_ERR_ARG, "hc_set_noise_scale: the particle filter is on and the base vectors carry the damping "
+                                "(set the scales before hc_set_filter, or the vectors with hc_set_filter_base)");
     for (int64_t k = 0; k < count; k++)
         if (!(scale[k] > 0.0) || !(scale[k] <= 1.0))
             return fail(HC_ERR_ARG, "noise scale %lld = %g is not a product of 0.8 factors in (0, 1]", (long long)(first + k), scale[k]);
@@ -1957,6 +2507,11 @@ int hc_set_point_member_bases(hc_handle *h, const int64_t *base)
 {
     if (!h) return fail(HC_ERR_ARG, "NULL handle");
     if (!h->have_column) return fail(HC_ERR_ARG, "hc_set_column must come first");
+    if (h->filt_stride > 0) {                    // the points' stream keys change: the filter is off
+        HIP_TRY(hipSetDevice(h->device));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        filter_off(h);
+    }
     h->base_host.clear();
     if (base) {
         for (int k = 0; k < h->n_points; k++)

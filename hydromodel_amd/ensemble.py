@@ -9,7 +9,7 @@ all-reduce of the per-row water-table moments (see :func:`allreduce_moments`).
 import numpy as np
 
 from .digest import inverse_retention
-from .stepper import EnsembleStepper, moments_to_mean_std, wtd_distribution
+from .stepper import EnsembleStepper, filter_summary, moments_to_mean_std, wtd_distribution
 
 
 def pressure_head(cols, theta):
@@ -96,11 +96,14 @@ class _Run:
     states, fluxes and abs_error every solved row) accumulated on the device: :meth:`profile_stats`.
     wtd_hist_stride > 0: per-row histograms of the members' water-table index every ``wtd_hist_stride``-th row, counted on
     the device: :meth:`wtd_distribution` (quantiles, CRPS against the well).
+    filter_stride > 0: a bootstrap particle filter on the well's water table every ``filter_stride``-th row with an
+    observation (``filter_sigma_cm``: the observation error; ``filter_seed``: default the run's seed): the tables above
+    describe the forecast, the states continue from the analysis; :meth:`filter_summary` (ESS, log marginal likelihood).
     ``_lead`` is the leading shape of the per-point tables: () for an ensemble, (P,) for a sweep."""
 
     _lead = ()
 
-    def _start_tables(self, profile_stride, wtd_hist_stride):
+    def _start_tables(self, profile_stride, wtd_hist_stride, filter_stride=0, filter_sigma_cm=None, filter_seed=None):
         self.profile_stride = int(profile_stride)
         if self.profile_stride:
             self.stepper.set_profile_stats(self.profile_stride)
@@ -108,6 +111,11 @@ class _Run:
         self.wtd_hist_stride = int(wtd_hist_stride)
         if self.wtd_hist_stride:
             self.stepper.set_wtd_hist(self.wtd_hist_stride)
+        self.filter_stride = int(filter_stride or 0)
+        self.filter_sigma_cm = float(filter_sigma_cm) if self.filter_stride else None
+        self.filter_seed = (self.seed if filter_seed is None else int(filter_seed)) if self.filter_stride else None
+        if self.filter_stride:
+            self.stepper.set_filter(self.filter_stride, self.filter_sigma_cm, self.filter_seed)
 
     def advance(self, n_rows, **kw):
         """Solve the next ``n_rows`` forcing rows for every member."""
@@ -142,6 +150,17 @@ class _Run:
         return wtd_distribution(t, self.forcing.wtd_obs, levels, self.cols.dz, self.cols.z, self.device,
                                 self.wtd_hist_stride)
 
+    def filter_table(self):
+        """[n_arow][4] float64 (count, ESS, log-likelihood increment, survivors per assimilation slot); a sweep: [P][n_arow][4]."""
+        return self.stepper.filter_table().reshape(self._lead + (-1, 4))
+
+    def filter_summary(self, table=None):
+        """The filter's record (stepper.filter_summary): ``rows``, ``count``, ``ess``, ``loglik_rows``, ``survivors`` over
+        the assimilated rows and ``loglik``, the log marginal likelihood of the well record (log cm^-1 summed over the rows),
+        with a leading [P] for a sweep; ``table``: e.g. the one assembled over ranks."""
+        t = self.filter_table() if table is None else table
+        return filter_summary(t, self.filter_stride, self.filter_sigma_cm)
+
     def close(self):
         self.stepper.close()
 
@@ -154,13 +173,15 @@ class EnsembleSimulation(_Run):
     #1 base vector, then one vector per refresh row (simulation.py:426,561,601) -- and uploaded per launch.
     spinup="shared" (default): one spin-up (global member 0's first draw) broadcast to all members;
     spinup="member": every member spins up with its own first draw (`spinup_members_on_gpu`).
-    profile_stride, wtd_hist_stride: the optional tables (:class:`_Run`).
+    profile_stride, wtd_hist_stride, filter_stride / filter_sigma_cm / filter_seed: the optional tables and the particle
+    filter (:class:`_Run`).
     """
 
     def __init__(self, cols, forcing, n_members, seed=0, device=0, member_offset=0, psi0=None, flags=None,
-                 noise="philox", spinup="shared", profile_stride=0, wtd_hist_stride=0):
+                 noise="philox", spinup="shared", profile_stride=0, wtd_hist_stride=0, filter_stride=0,
+                 filter_sigma_cm=None, filter_seed=None):
         self._start(cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup)
-        self._start_tables(profile_stride, wtd_hist_stride)
+        self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed)
 
     def _start(self, cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup):
         if noise not in ("philox", "numpy") or spinup not in ("shared", "member"):
@@ -257,6 +278,13 @@ class EnsembleSimulation(_Run):
         if self.wtd_hist_stride:
             arrays["wtd_hist_stride"] = np.array(self.wtd_hist_stride, dtype=np.int64)
             arrays["wtd_hist"] = self.stepper.wtd_hist_table()
+        if self.filter_stride:
+            # the base vectors carry the damping and the ancestry of a filtered run (noise_scale no longer follows it)
+            arrays["filter_stride"] = np.array(self.filter_stride, dtype=np.int64)
+            arrays["filter_sigma_cm"] = np.array(self.filter_sigma_cm, dtype=np.float64)
+            arrays["filter_seed"] = np.array(self.filter_seed, dtype=np.uint64)
+            arrays["filter_table"] = self.stepper.filter_table()
+            arrays["filter_base"] = self.stepper.filter_base()
         path = Path(path)
         if hdf5io.available() and path.suffix != ".npz":
             hdf5io.write(path, arrays)
@@ -282,11 +310,18 @@ class EnsembleSimulation(_Run):
         psi = np.asarray(data["psi"], dtype=float).reshape(n, D)
         stride = int(data["profile_stride"]) if "profile_stride" in data else 0
         hist_stride = int(data["wtd_hist_stride"]) if "wtd_hist_stride" in data else 0
+        filt = int(data["filter_stride"]) if "filter_stride" in data else 0
+        fkw = dict(filter_stride=filt, filter_sigma_cm=float(data["filter_sigma_cm"]),
+                   filter_seed=int(data["filter_seed"])) if filt else {}
         sim = cls(cols, forcing, n, seed=int(data["seed"]), device=device, member_offset=int(data["member_offset"]),
                   psi0=np.asarray(data["initial_cond"], dtype=float).reshape(-1)[:D], flags=flags, profile_stride=stride,
-                  wtd_hist_stride=hist_stride)
+                  wtd_hist_stride=hist_stride, **fkw)
         sim.stepper.set_state(psi if n > 1 else psi[0])
-        sim.stepper.set_noise_scale(np.asarray(data["noise_scale"], dtype=float).reshape(n))
+        if filt:
+            sim.stepper.set_filter_table(np.asarray(data["filter_table"], dtype=np.float64))
+            sim.stepper.set_filter_base(np.asarray(data["filter_base"], dtype=np.float64).reshape(n, D))
+        else:
+            sim.stepper.set_noise_scale(np.asarray(data["noise_scale"], dtype=float).reshape(n))
         sim.stepper.set_moments(np.asarray(data["moments"], dtype=np.int64))
         if stride:
             sim.stepper.set_profile_table(np.asarray(data["profile_table"], dtype=np.int64))
@@ -383,7 +418,8 @@ class SweepSimulation(_Run):
     result is broadcast to the point's members."""
 
     def __init__(self, cols_list, forcing, n_members, seed=0, device=0, first_point=0, flags=None, psi0=None,
-                 point_ids=None, profile_stride=0, wtd_hist_stride=0):
+                 point_ids=None, profile_stride=0, wtd_hist_stride=0, filter_stride=0, filter_sigma_cm=None,
+                 filter_seed=None):
         self.points = list(cols_list)
         self.P, self.n = len(self.points), int(n_members)
         self._lead = (self.P,)
@@ -410,7 +446,7 @@ class SweepSimulation(_Run):
         self.stepper.set_noise_philox(self.seed, self.member_offset)
         if self.P > 1:
             self.stepper.set_point_member_bases(self.bases)
-        self._start_tables(profile_stride, wtd_hist_stride)
+        self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed)
         self.next_row, self.kernel_ms, self.launches = 1, 0.0, 0
 
     def _spinup(self, flags):

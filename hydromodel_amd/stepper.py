@@ -76,6 +76,7 @@ class EnsembleStepper:
         self.last_launches = 0
         self.profile_stride = 0
         self.wtd_hist_stride = 0
+        self.filter_stride, self.filter_sigma_cm, self.filter_seed = 0, 0.0, 0
         if profile_stride:
             self.set_profile_stats(profile_stride)
 
@@ -114,6 +115,7 @@ class EnsembleStepper:
         if base.shape != (self.N, self.D):
             raise ValueError(f"base noise must be [{self.N}, {self.D}]")
         L.check(self.lib.hc_set_noise_host(self.h, L.dptr(base)))
+        self._filter_off()
 
     def get_noise_base(self, first=0, count=None):
         count = self.N - first if count is None else count
@@ -123,6 +125,7 @@ class EnsembleStepper:
 
     def set_noise_philox(self, seed, member_offset=0):
         L.check(self.lib.hc_set_noise_philox(self.h, int(seed), int(member_offset)))
+        self._filter_off()
 
     def philox_normals(self, member, draw):
         out = np.empty(self.D)
@@ -211,6 +214,7 @@ class EnsembleStepper:
         if bases.shape != (self.P,):
             raise ValueError(f"need one member base per parameter point ({self.P})")
         L.check(self.lib.hc_set_point_member_bases(self.h, L.lptr(bases)))
+        self._filter_off()
 
     def point_costs(self):
         """RHS evaluations spent on each parameter point's members so far ([P]; zeros for a single point)."""
@@ -308,6 +312,67 @@ class EnsembleStepper:
 
     def reset_wtd_hist(self):
         L.check(self.lib.hc_reset_wtd_hist(self.h))
+
+    # -- particle filter on the well's water table (include/hydrocol.h hc_set_filter) ----------------------------------
+    def set_filter(self, stride, sigma_cm=None, seed=0):
+        """Resample the members on every ``stride``-th forcing row that has an observation (0 = off): weights from the
+        Gaussian likelihood of the observed water table (``sigma_cm``), systematic resampling per parameter point.  The
+        tables accumulate the forecast; the states after the call are the analysis.  In a Philox run this fills the base
+        noise vectors: call it after any spin-up and noise-scale restore."""
+        stride = int(stride)
+        if stride < 0:
+            raise ValueError(f"filter stride must be >= 0, got {stride}")
+        sigma = float(sigma_cm) if stride else 0.0
+        if stride and not (np.isfinite(sigma) and sigma > 0.0):
+            raise ValueError(f"filter sigma_cm = {sigma_cm!r} must be finite and > 0")
+        self._filter_off()                                    # hc_set_filter turns it off first, and leaves it off if it refuses
+        L.check(self.lib.hc_set_filter(self.h, stride, sigma, int(seed) & 0xFFFFFFFFFFFFFFFF))
+        self.filter_stride, self.filter_sigma_cm, self.filter_seed = stride, sigma, int(seed)
+
+    def _filter_off(self):
+        """The library turned the filter off (a new noise source or new point keys, include/hydrocol.h): so does this side."""
+        self.filter_stride, self.filter_sigma_cm, self.filter_seed = 0, 0.0, 0
+
+    def filter_table(self):
+        """[P][n_arow][4] float64: count, ESS, log-likelihood increment, survivors per assimilation slot (slot j <-> row
+        j stride; count 0 and NaN where nothing was assimilated)."""
+        t = np.zeros((self.P, stride_rows(self.T, self.filter_stride), 4))
+        L.check(self.lib.hc_get_filter_stats(self.h, L.dptr(t), t.size))
+        return t
+
+    def set_filter_table(self, table):
+        t = L.as_f64(table).reshape(-1)
+        L.check(self.lib.hc_set_filter_stats(self.h, L.dptr(t), t.size))
+
+    def filter_base(self):
+        """[N][D] base noise vectors of a filtered Philox run (what resampling carries from ancestor to slot)."""
+        out = np.empty((self.N, self.D))
+        L.check(self.lib.hc_get_filter_base(self.h, L.dptr(out), 0, self.N))
+        return out
+
+    def set_filter_base(self, base):
+        base = L.as_f64(base)
+        if base.shape != (self.N, self.D):
+            raise ValueError(f"base noise must be [{self.N}, {self.D}]")
+        L.check(self.lib.hc_set_filter_base(self.h, L.dptr(base)))
+
+    def filter_ancestors(self):
+        """[N] int64: the handle-local member each slot took its state from at the last assimilation (test hook)."""
+        out = np.zeros(self.N, dtype=np.int64)
+        L.check(self.lib.hc_get_filter_ancestors(self.h, L.lptr(out)))
+        return out
+
+    def filter_weights(self):
+        """[P][D] int64: q_b of the last assimilation (test hook)."""
+        out = np.zeros((self.P, self.D), dtype=np.int64)
+        L.check(self.lib.hc_get_filter_weights(self.h, L.lptr(out)))
+        return out
+
+    def filter_draw(self):
+        """[P] int64: the systematic offset r of the last assimilation (test hook)."""
+        out = np.zeros(self.P, dtype=np.int64)
+        L.check(self.lib.hc_get_filter_draw(self.h, L.lptr(out)))
+        return out
 
     # -- hooks ----------------------------------------------------------------------
     def spinup(self, zwtd_cm, z0_cm, forcing_row=0, max_iterations=1500):
@@ -501,6 +566,47 @@ def wtd_distribution(hist, obs_idx, levels, dz, z, device=0, stride=1):
     return {"rows": rows, "count": count, "quantile_idx": qidx.reshape(lead + (n_hrow, lv.size)),
             "quantile_cm": qcm.reshape(lead + (n_hrow, lv.size)), "crps_cm": crps, "crps_mean_cm": crps_mean,
             "levels": lv}
+
+
+# ---- particle filter on the host (include/hydrocol.h hc_set_filter) ----------------------------------------------------
+FILTER_Q_ONE = 1 << 31
+
+
+def filter_slot_ranges(q_members, r):
+    """[N_p] (k0, k1) slot ranges of systematic resampling with Python integers: member m (C_m = exclusive prefix sum of
+    q in member order, Q = sum q) fills k in [ceil((C_m N_p - r) / Q), ceil(((C_m + q_m) N_p - r) / Q))."""
+    q = [int(v) for v in q_members]
+    n, Q, r = len(q), sum(q), int(r)
+    out, c = [], 0
+    for qm in q:
+        out.append((-((r - c * n) // Q), -((r - (c + qm) * n) // Q)))
+        c += qm
+    return out
+
+
+def filter_ancestors_of(q_members, r):
+    """[N_p] ancestor of every slot (point-local member index) from :func:`filter_slot_ranges`."""
+    anc = np.full(len(q_members), -1, dtype=np.int64)
+    for m, (k0, k1) in enumerate(filter_slot_ranges(q_members, r)):
+        anc[k0:k1] = m
+    return anc
+
+
+def filter_summary(table, stride, sigma_cm):
+    """The filter's record from its [..., n_arow, 4] table: ``rows`` (forcing row of every assimilated slot), ``count``,
+    ``ess``, ``loglik_rows`` (the increments), ``survivors`` [..., R] over the slots any point assimilated, and ``loglik``
+    [...] = the sum of the increments in row order; ``stride``, ``sigma_cm``."""
+    t = np.asarray(table, dtype=np.float64)
+    used = (t[..., 0] > 0).reshape(-1, t.shape[-2]).any(axis=0)
+    slots = np.flatnonzero(used)
+    sel = t[..., slots, :]
+    inc = sel[..., 2]
+    loglik = np.zeros(inc.shape[:-1])
+    for j in range(inc.shape[-1]):                      # row order
+        loglik = loglik + np.where(sel[..., j, 0] > 0, inc[..., j], 0.0)
+    return {"rows": slots.astype(np.int64) * int(stride), "count": sel[..., 0].astype(np.int64), "ess": sel[..., 1],
+            "loglik_rows": inc, "survivors": np.nan_to_num(sel[..., 3]).astype(np.int64),
+            "loglik": loglik if loglik.ndim else float(loglik), "stride": int(stride), "sigma_cm": float(sigma_cm)}
 
 
 def allreduce_handles(steppers):

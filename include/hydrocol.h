@@ -39,6 +39,9 @@
  *   hc_set_wtd_hist, hc_get_wtd_hist, hc_set_wtd_hist_table, hc_reset_wtd_hist, hc_wtd_distribution
  *                      <- wtd_est / abs_error per row (src/simulation.py:612-615) as the ensemble's distribution:
  *                         per-row histograms of the water-table index, quantiles and the CRPS against the well
+ *   hc_set_filter, hc_get/set_filter_stats, hc_get/set_filter_base, hc_get_filter_ancestors/weights/draw
+ *                      <- (new) the ensemble conditioned on wtd_obs (src/simulation.py:582-612): a bootstrap particle filter,
+ *                         and the log marginal likelihood of the well record per parameter point
  *
  * Conventions: every function returns 0 on success or a negative hc_status; nothing throws
  * or aborts across the boundary; hc_last_error() gives the thread-local message.  Host
@@ -306,6 +309,59 @@ int hc_reset_wtd_hist(hc_handle *h);
 int hc_wtd_distribution(int device, const int32_t *hist, const int32_t *obs_idx, int64_t n_rows, int32_t D,
                         const double *levels, int32_t n_levels, double dz, int64_t *count, int32_t *quantile_idx,
                         double *crps_cm);
+
+/* Particle filter on the well's water table (bootstrap filter, systematic resampling in exact integers).
+ *   Assimilation rows: r >= 1, r % stride == 0 and wtd_obs[r] >= 0 (wtd_obs as it stands when hc_step_rows reaches the row:
+ *   hc_set_forcing_row before the row's step sets or removes its observation).  Slot j <-> row j stride,
+ *   n_arow = (n_forcing_rows - 1) / stride + 1; slot 0 stays empty.  A launch ends on every assimilation row (results do not
+ *   depend on launch length); spin-up solves are never filtered.
+ *   Order at an assimilation row: the row is solved; every table on the handle (moments, profile statistics, histograms)
+ *   accumulates it -- they describe the FORECAST ensemble; then the filter resamples.  After the call hc_get_state returns
+ *   the ANALYSIS; psi_rows_out and wtd_out hold the forecast of the row.
+ *   Weights, per parameter point p (members [p N_p, (p + 1) N_p)), o = wtd_obs[r], b = a member's water-table index
+ *   (the index hc_step_args.wtd_out returns), n_b = members of p in bin b, all in fp64 without contraction:
+ *     t_b = dz * (double)(b - o) / sigma_cm;  l_b = -0.5 * (t_b * t_b);  s = max l_b over the bins with n_b > 0;
+ *     q_b = floor(2^31 * exp(l_b - s)) for n_b > 0, q_b = 0 for an empty bin: q = 2^31 at the nearest occupied bin, and a
+ *     bin more than ~6.5 sigma further from the well than that gets q = 0 (truncation: such members leave no offspring).
+ *   Resampling, member order within the point: C_m = exclusive prefix sum of q_m = q_{b_m} (int64), Q = sum q_m;
+ *   x = one 64-bit Philox4x32-10 value (the first two output words, word 1 high) under the key filter seed, counter
+ *   (0xFFFFFFFF, row, key_lo, key_hi) with key = the point's first global member id (hc_set_point_member_bases; one point:
+ *   member_offset) -- a noise counter's first word is a depth index / 2, so the two never meet; r = floor(x Q / 2^64).
+ *   Slot k takes the member m with C_m <= floor((k Q + r) / N_p) < C_m + q_m: member m fills
+ *   k in [ceil((C_m N_p - r) / Q), ceil(((C_m + q_m) N_p - r) / Q)) (128-bit intermediates; the ranges partition [0, N_p)).
+ *   All integers: the ancestry depends on no reduction order, launch length, point order or rank count.  With equal weights
+ *   (sigma_cm = 1e30) it is the identity.
+ *   A member's Markov state is (psi, base noise vector): slot k takes both from its ancestor.  Refresh vectors stay keyed by
+ *   the slot's own stream.  Host noise: h->base is gathered with psi; the caller keeps drawing slot k's refresh vectors
+ *   from slot k's generator.  Philox noise: with the filter on the step kernel runs its caller-noise path; the library
+ *   fills the base vectors once, in hc_set_filter, as z * scale (z = the kernel's draw-0 normal of the slot, scale =
+ *   hc_set_noise_scale's value, one rounding), and each launch's refresh vectors from the slot's stream and the row's draw
+ *   index (a launch stages at most ~4 GiB of them).  The x0.8 retry damping then follows the host-noise semantics
+ *   (applied to the base vector in place, src/richards_pde.py:522), which are the reference's.
+ *   Diagnostics, float64 [P][n_arow][4] per point and slot: count = sum_b n_b; ESS = (sum n_b q_b)^2 / sum n_b q_b^2 (exact
+ *   128-bit sums, the quotient from a double-double correction, within 2 ulp of the exact ratio); the log-likelihood increment
+ *   s + log(W / count) - log(sigma_cm) - 0.5 * log(2 pi), W = sum_b n_b exp(l_b - s) summed in increasing b (log cm^-1: the
+ *   Gaussian density of the observed depth given the member's, averaged over the members); survivors = members with at
+ *   least one offspring.  Slots without an assimilation hold count = 0 and NaN.  A point's log marginal likelihood is the
+ *   sum of its increments in row order (on the host).
+ * hc_set_filter: stride 0 = off; otherwise (re)creates the table, and in a Philox run fills the base vectors.  Needs column,
+ *   forcing, members and noise source; sigma_cm finite and > 0; at most 2^31 - 1 members per point, 2^32 - 1 rows.
+ *   A later hc_set_column / hc_add_point / hc_set_point_member_bases, hc_set_members, hc_set_noise_host or
+ *   hc_set_noise_philox turns the filter off; hc_set_forcing re-creates the table (count 0, NaN) when the row count changes.
+ *   With the filter on in a Philox run, hc_spinup / spin-up rows and hc_set_noise_scale are refused (the base vectors carry
+ *   the damping: set scales and do spin-ups before hc_set_filter) and hc_get_noise_scale no longer follows the run.
+ * hc_get/set_filter_stats: the table (P n_arow 4 entries; checkpoints, the assembly of a sweep over ranks).
+ * hc_get/set_filter_base: the device base vectors [n_members][D] of a filtered Philox run (resume).
+ * Test hooks of the last assimilation: ancestors [n_members] int64 (handle-local member index of each slot's ancestor),
+ *   weights [P][D] int64 (q_b), draw [P] int64 (r). */
+int hc_set_filter(hc_handle *h, int32_t stride, double sigma_cm, uint64_t seed);
+int hc_get_filter_stats(hc_handle *h, double *table, int64_t n_entries);
+int hc_set_filter_stats(hc_handle *h, const double *table, int64_t n_entries);
+int hc_get_filter_base(hc_handle *h, double *base, int64_t first_member, int64_t count);
+int hc_set_filter_base(hc_handle *h, const double *base);
+int hc_get_filter_ancestors(hc_handle *h, int64_t *ancestors);
+int hc_get_filter_weights(hc_handle *h, int64_t *q);
+int hc_get_filter_draw(hc_handle *h, int64_t *r);
 
 /* The path's one collective inside the library, for a single process that drives several devices with
  * one handle each: every handle's moment table is replaced by the sum over all n handles (ncclAllReduce, ncclInt64,
