@@ -100,6 +100,12 @@ EXPORTS = {
     "hc_get_filter_ancestors": ([C.c_void_p, _lp], C.c_int),
     "hc_get_filter_weights": ([C.c_void_p, _lp], C.c_int),
     "hc_get_filter_draw": ([C.c_void_p, _lp], C.c_int),
+    "hc_set_enkf": ([C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_uint64], C.c_int),
+    "hc_get_enkf_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),
+    "hc_set_enkf_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),
+    "hc_get_enkf_gain": ([C.c_void_p, _dp], C.c_int),
+    "hc_get_enkf_y": ([C.c_void_p, _dp], C.c_int),
+    "hc_get_enkf_eps": ([C.c_void_p, _dp], C.c_int),
     "hc_rhs": ([C.c_void_p, C.c_int64, C.c_int32, _dp, _dp], C.c_int),
     "hc_model_nodes": ([C.c_void_p, _dp, _dp], C.c_int),
     "hc_plugin_eval": ([C.c_int, C.POINTER(ColumnParams), C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp],

@@ -43,6 +43,16 @@ unknown keys, only membership of the 12 is checked):
   (the log marginal likelihood of the well record, log cm^-1) and ``filter_sigma_cm`` (a sweep: a leading ``[P]`` axis), and
   the run ends with `` [Ensemble xN] filter log-likelihood = ... over R rows`` (a sweep: the best point).  A single-point
   ensemble on several GPUs is refused (resampling would move states between ranks).
+* ``"Ensemble": {..., "EnKF": {"Stride": 48, "Sigma_cm": 10.0, "Localisation_cm": 0, "Seed": s}}``: a stochastic ensemble
+  Kalman filter on the well's continuous water table (include/hydrocol.h hc_set_enkf) -- on every 48th forcing row (default
+  48; 0 = off) that has an observation each member's psi moves by the sample covariance with the water table, per parameter
+  point, on the GPU (``Sigma_cm``, required: finite and > 0; ``Localisation_cm``: the Gaspari-Cohn half-width, default 0 =
+  none; ``Seed``: default the ensemble's seed).  Not together with ``"Filter"``.  Moments, profiles and histograms describe
+  the forecast.  Added to ``<Output_Name>_ensemble.h5``: ``enkf_rows``, ``enkf_count``, ``enkf_prior_mean_cm``,
+  ``enkf_prior_std_cm``, ``enkf_innovation_cm``, ``enkf_post_mean_cm``, ``enkf_post_std_cm``, ``enkf_loglik_rows``,
+  ``enkf_rejected`` ``[R]``, ``enkf_loglik``, ``enkf_sigma_cm`` and ``enkf_localisation_cm`` (a sweep: a leading ``[P]``
+  axis), and the run ends with `` [Ensemble xN] EnKF log-likelihood = ... over R rows`` (a sweep: the best point).  A
+  single-point ensemble on several GPUs is refused (the covariances would need a sum over ranks).
 * ``"Ensemble": {"repair_predict": true}`` with ``Simulation_Flags.PREDICT``: run the repaired predictive lateral flow
    instead of raising the reference's ``TypeError``.
 """
@@ -102,6 +112,7 @@ def main(params_file=None, data_file=None, seed=None, device=0, gpus=None, _sett
         n_gpus = multigpu.requested_gpus(gpus, params)
         if params.get("Ensemble"):
             filter_settings(params["Ensemble"], n_gpus)     # so does a bad Filter block
+            enkf_settings(params["Ensemble"], n_gpus)       # and a bad EnKF block
         ranks = multigpu.Ranks(expect=n_gpus if (n_gpus > 1 or multigpu.in_rank()) else None)
         if ranks.world > 1:
             device = ranks.device_index()
@@ -159,6 +170,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     from .ensemble import EnsembleSimulation
     dist_stride, dist_levels = distribution_settings(ens)
     filt = filter_settings(ens, ranks.world)
+    enkf = enkf_settings(ens, ranks.world)
     cols = ColumnTables(params, load_site_well(params))
     forcing = ForcingDigest(params, water_data, cols)
     if cols.flags["PREDICT"] and not ens.get("repair_predict"):
@@ -167,7 +179,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     days = int(ens.get("Days", (forcing.dim_t - 1) // 48))
     rows = min(days * 48, forcing.dim_t - 1)
     if ens.get("Points"):
-        return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels, filt)
+        return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels, filt,
+                          enkf)
     lo, hi = multigpu.shard(n_members, ranks.rank, ranks.world)
     if hi <= lo:
         raise ValueError(f" Ensemble: {n_members} members do not shard over {ranks.world} GPUs (a rank would be empty).")
@@ -175,7 +188,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     sim = EnsembleSimulation(cols, forcing, hi - lo, seed=int(ens.get("Seed", 0)), device=device, member_offset=lo,
                              noise=str(ens.get("Noise", "philox")).lower(),
                              spinup=str(ens.get("Spinup", "shared")).lower(), profile_stride=stride,
-                             wtd_hist_stride=dist_stride, **_filter_kwargs(filt))
+                             wtd_hist_stride=dist_stride, **_filter_kwargs(filt), **_enkf_kwargs(enkf))
     label = f"Ensemble x{n_members}"
     _step_all(sim, rows, label, ranks)
     # the run's one collective: int64 (count, sum idx, sum idx^2) per row, exact and order-independent
@@ -204,6 +217,9 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     extra.update(tables)
     ftables, filter_line = _reduce_filter(ranks, sim, [0], 1, forcing.dim_t, filt, label, keep_points=False)
     extra.update(ftables)
+    etables, enkf_line = _reduce_enkf(ranks, sim, [0], 1, forcing.dim_t, enkf, label, keep_points=False,
+                                         z0_cm=cols.z[0])
+    extra.update(etables)
     arrays = dict(moments=moments, wtd_mean_cm=mean_cm, wtd_std_cm=std_cm, rows=np.array(rows),
                   members=np.array(n_members), gpus=np.array(ranks.world), initial_cond=psi0, **extra)
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "ensemble water-table statistics", ranks)
@@ -211,6 +227,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
         print(crps_line)
     if filter_line:
         print(filter_line)
+    if enkf_line:
+        print(enkf_line)
     sim.close()
 
 
@@ -283,6 +301,85 @@ def filter_settings(ens, n_gpus=1):
         raise ValueError(f" Ensemble: Filter with one parameter point runs on one GPU ({n_gpus} requested): resampling "
                          f"would move members between ranks.")
     return stride, float(sigma), (None if seed is None else int(seed))
+
+
+ENKF_KEYS = ("Stride", "Sigma_cm", "Localisation_cm", "Seed")
+
+
+def enkf_settings(ens, n_gpus=1):
+    """Ensemble.EnKF -> (stride, sigma_cm, localisation_cm, seed or None = the ensemble's seed); (0, None, None, None)
+    when absent or off.  Pure: runs before any GPU call, and a bad value is a ValueError (message + exit status 1).  Refused
+    together with a "Filter" block, and for a single-point ensemble on more than one GPU (its covariances would need a sum
+    over the ranks)."""
+    import math
+    from numbers import Integral, Real
+    block = ens.get("EnKF")
+    if block is None:
+        return 0, None, None, None
+    if not isinstance(block, dict):
+        raise ValueError(f" Ensemble: EnKF = {block!r} must be an object such as {{\"Stride\": 48, \"Sigma_cm\": 10.0}}.")
+    unknown = sorted(set(block) - set(ENKF_KEYS))
+    if unknown:
+        raise ValueError(f" Ensemble: EnKF has unknown keys {unknown} (known: {list(ENKF_KEYS)}).")
+    stride = block.get("Stride", 48)
+    if (isinstance(stride, bool) or not isinstance(stride, Real) or not math.isfinite(stride) or stride != int(stride)
+            or stride < 0 or stride > (1 << 31) - 1):
+        raise ValueError(f" Ensemble: EnKF.Stride = {stride!r} must be a row stride >= 0 (0: off).")
+    if "Sigma_cm" not in block:
+        raise ValueError(" Ensemble: EnKF.Sigma_cm (the observation error of the well, cm) is required.")
+    sigma = block["Sigma_cm"]
+    if isinstance(sigma, bool) or not isinstance(sigma, Real) or not math.isfinite(sigma) or not sigma > 0:
+        raise ValueError(f" Ensemble: EnKF.Sigma_cm = {sigma!r} must be a finite number > 0.")
+    loc = block.get("Localisation_cm", 0)
+    if isinstance(loc, bool) or not isinstance(loc, Real) or not math.isfinite(loc) or not loc >= 0:
+        raise ValueError(f" Ensemble: EnKF.Localisation_cm = {loc!r} must be a finite number >= 0 (0: none).")
+    seed = block.get("Seed")
+    if seed is not None and (isinstance(seed, bool) or not isinstance(seed, Integral) or not 0 <= seed < (1 << 64)):
+        raise ValueError(f" Ensemble: EnKF.Seed = {seed!r} must be an integer in [0, 2^64).")
+    stride = int(stride)
+    if not stride:
+        return 0, None, None, None
+    if ens.get("Filter") is not None:
+        raise ValueError(" Ensemble: \"Filter\" and \"EnKF\" exclude each other: choose one.")
+    if not ens.get("Points") and int(n_gpus) > 1:
+        raise ValueError(f" Ensemble: EnKF with one parameter point runs on one GPU ({n_gpus} requested): its "
+                         f"covariances would need a sum over the ranks.")
+    return stride, float(sigma), float(loc), (None if seed is None else int(seed))
+
+
+def _enkf_kwargs(enkf):
+    stride, sigma, loc, seed = enkf
+    return dict(enkf_stride=stride, enkf_sigma_cm=sigma, enkf_localisation_cm=loc, enkf_seed=seed) if stride else {}
+
+
+def _reduce_enkf(ranks, sim, ids, P, T, enkf, label, keep_points, z0_cm):
+    """The EnKF's datasets from this rank's handle ``sim`` (None: no points), its points ``ids`` placed in the run's [P]
+    table and summed over the ranks (float64 as int64 bits: ``multigpu.place_points``), and the closing line (rank 0).
+    The means are given at the well's depths (``z0_cm`` = z[0] + the table's depths from the top node)."""
+    import numpy as np
+    from .multigpu import place_points
+    from .stepper import ENKF_WIDTH, enkf_summary, stride_rows
+    stride, sigma, loc, _ = enkf
+    if not stride:
+        return {}, None
+    n_arow = stride_rows(T, stride)
+    local = sim.enkf_table().reshape(-1, n_arow, ENKF_WIDTH) if sim is not None else np.zeros((0, n_arow, ENKF_WIDTH))
+    table = place_points(local, ids, P, ranks)
+    summary = enkf_summary(table if keep_points else table[0], stride, sigma, float(z0_cm))
+    out = {f"enkf_{k}": summary[k] for k in ("rows", "count", "prior_mean_cm", "prior_std_cm", "innovation_cm",
+                                             "post_mean_cm", "post_std_cm", "loglik_rows", "rejected")}
+    out.update(enkf_loglik=np.asarray(summary["loglik"], dtype=np.float64), enkf_sigma_cm=np.array(sigma, dtype=np.float64),
+               enkf_localisation_cm=np.array(loc, dtype=np.float64))
+    n = int(summary["rows"].size)
+    if ranks.rank != 0:
+        return out, None
+    if keep_points:
+        ll = np.asarray(summary["loglik"], dtype=np.float64)
+        best = int(np.nanargmax(ll)) if np.isfinite(ll).any() else 0
+        line = f" [{label}] EnKF log-likelihood: best point {best} = {ll[best]:.3f} over {n} rows"
+    else:
+        line = f" [{label}] EnKF log-likelihood = {float(summary['loglik']):.3f} over {n} rows"
+    return out, line
 
 
 def _filter_kwargs(filt):
@@ -407,7 +504,7 @@ def _reduce_optional(ranks, sim, ids, cols_all, forcing, stride, dist_stride, di
 
 
 def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride=0, dist_levels=None,
-               filt=(0, None, None)):
+               filt=(0, None, None), enkf=(0, None, None, None)):
     """Parameter points x members: this rank's points in one handle (ensemble.SweepSimulation), the whole table assembled
     over the ranks (multigpu.assemble_points)."""
     import numpy as np
@@ -433,7 +530,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     label = f"Sweep {P} points x{n_members}"
     if mine:
         sim = SweepSimulation(points, forcing, n_members, seed=int(ens.get("Seed", 0)), device=device, point_ids=mine,
-                              profile_stride=stride, wtd_hist_stride=dist_stride, **_filter_kwargs(filt))
+                              profile_stride=stride, wtd_hist_stride=dist_stride, **_filter_kwargs(filt),
+                              **_enkf_kwargs(enkf))
         _step_all(sim, rows, label, ranks)
         table = sim.moments()
         for j, k in enumerate(mine):
@@ -449,6 +547,9 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     arrays.update(tables)
     ftables, filter_line = _reduce_filter(ranks, sim, mine, P, T, filt, label, keep_points=True)
     arrays.update(ftables)
+    etables, enkf_line = _reduce_enkf(ranks, sim, mine, P, T, enkf, label, keep_points=True,
+                                         z0_cm=cols_all[0].z[0])
+    arrays.update(etables)
     if sim is not None:
         sim.close()
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "sweep's water-table statistics", ranks)
@@ -456,6 +557,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
         print(crps_line)
     if filter_line:
         print(filter_line)
+    if enkf_line:
+        print(enkf_line)
 
 
 def run_cli(argv=None):
@@ -475,8 +578,9 @@ def run_cli(argv=None):
         settings = _read_parameters(args.params)
         n_gpus = multigpu.requested_gpus(args.gpus, settings)
         if settings.get("Ensemble") and n_gpus > 1 and not multigpu.in_rank():
-            try:                                    # a bad Filter block ends the command before any rank starts
+            try:                                    # a bad Filter or EnKF block ends the command before any rank starts
                 filter_settings(settings["Ensemble"], n_gpus)
+                enkf_settings(settings["Ensemble"], n_gpus)
             except ValueError as bad:
                 print(bad)
                 sys.exit(1)

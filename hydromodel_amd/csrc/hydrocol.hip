@@ -176,6 +176,16 @@ struct hc_handle {
     DevBuf<unsigned long long> filt_qr, filt_surv;
     std::vector<long long> filt_rows_host;
     std::vector<int> h_wtd_obs;
+    // ensemble Kalman filter on the well's water table (hc_set_enkf): diagnostics float64 [P][n_arow][8] keyed by
+    // (points, rows, stride); per member the forecast y, eps, the posterior y and the rejection flag; per point the y
+    // statistics {mean, v}, the column means and the gain (the last analysis: test hooks); the tile partials
+    int enkf_stride = 0;         // 0: off
+    double enkf_sigma = 0.0, enkf_loc = 0.0;
+    uint64_t enkf_seed = 0;
+    bool enkf_done = false;      // an analysis has run since the EnKF was set
+    AccTable<double> enkf{"entries"};
+    DevBuf<double> enkf_y, enkf_eps, enkf_ypost, enkf_ys, enkf_mean, enkf_gain, enkf_part;
+    DevBuf<int> enkf_rej;
     int n_cu = 256;
     double jac_reject = NUM_JAC_DIFF_REJECT;
 };
@@ -779,10 +789,244 @@ __global__ void filter_philox_fill_kernel(double *out, long long n_vec, const lo
     }
 }
 
-__global__ void filter_stats_init_kernel(double *stats, size_t n)
+// a diagnostics table of `width` entries per slot, created as count 0 and NaN (the particle filter's and the EnKF's)
+__global__ void stats_init_kernel(double *stats, size_t n, int width)
 {
     const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < n) stats[k] = k % 4 == 0 ? 0.0 : __builtin_nan("");
+    if (k < n) stats[k] = k % width == 0 ? 0.0 : __builtin_nan("");
+}
+
+// ---- ensemble Kalman filter on the well's water table (hc_set_enkf, include/hydrocol.h)
+// Depths are measured from the top node, z_i = i dz: the C-ABI knows no z[0], and every quantity but the two means of
+// the diagnostics is a difference of depths (the host adds z[0] to those).  Every sum over a point's members runs in an
+// order fixed by N_p alone -- tiles of ENKF_TILE members summed in member order, then the tile partials in tile order;
+// the y statistics: thread t of one block takes members t, t + ENKF_THREADS, ... in order, then a fixed tree; the tile
+// partials of a node: thread t takes tiles t, t + ENKF_THREADS, ... in order, then the same tree -- and no
+// floating-point atomics, so the analysis is the same at any launch length, point order or member split.  Contraction
+// is off throughout.
+constexpr int ENKF_TILE = 256;                         // members per partial of the column sums
+constexpr int ENKF_THREADS = 1024;                     // the per-point y statistics and the sums of the tile partials
+constexpr int ENKF_SLOTS = HC_MAX_DEPTH_NODES / WAVE;  // depth nodes per lane of the update (one wave per member)
+constexpr int ENKF_WIDTH = 8;                          // diagnostics per point and slot
+
+// eps_k: one standard normal of Philox4x32-10 under the EnKF seed at counter (0xFFFFFFFE, row, gid_lo, gid_hi), with
+// the Box-Muller step of philox_normal (its cosine branch).  A noise counter's first word is a depth index / 2 and the
+// particle filter's draw has 0xFFFFFFFF: the three never meet.
+__device__ __forceinline__ double enkf_normal(unsigned long long seed, unsigned long long gid, unsigned row)
+{
+#pragma clang fp contract(off)
+    uint32_t r[4];
+    philox4x32_10(0xFFFFFFFEu, row, (uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    const uint64_t a = ((uint64_t)r[1] << 32) | r[0], b = ((uint64_t)r[3] << 32) | r[2];
+    const double u1 = ((double)(a >> 11) + 0.5) * (1.0 / 9007199254740992.0);
+    const double u2 = ((double)(b >> 11) + 0.5) * (1.0 / 9007199254740992.0);
+    double s, c;
+    sincospi(2.0 * u2, &s, &c);
+    return sqrt(-2.0 * log(u1)) * c;
+}
+
+// the continuous water table of a column whose find_wtd index is b: where psi crosses psi_sat between nodes b - 1 and b,
+// the linear interpolation of the crossing, in (z[b-1], z[b]]; else z[b]
+__device__ __forceinline__ double enkf_y_of(int b, double lo, double hi, double psat, double dz)
+{
+#pragma clang fp contract(off)
+    if (b >= 1 && lo < psat && psat <= hi) return (double)(b - 1) * dz + dz * (psat - lo) / (hi - lo);
+    return (double)b * dz;
+}
+
+// Gaspari & Cohn (1999) eq. 4.10, the fifth-order taper with support 2 (r = distance / L)
+__device__ __forceinline__ double gaspari_cohn(double r)
+{
+#pragma clang fp contract(off)
+    if (r <= 1.0) return (((-0.25 * r + 0.5) * r + 0.625) * r - 5.0 / 3.0) * r * r + 1.0;
+    if (r <= 2.0) return ((((r / 12.0 - 0.5) * r + 0.625) * r + 5.0 / 3.0) * r - 5.0) * r + 4.0 - 2.0 / (3.0 * r);
+    return 0.0;
+}
+
+// y_k of every member from the index the step kernel wrote (wtd_u16's row) and the two nodes around it
+__global__ void enkf_obs_kernel(const unsigned short *w, const double *psi, const ColumnDev *P, long long n_members,
+                                long long mpp, int D, double dz, double *y)
+{
+    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n_members) return;
+    const int b = (int)w[m] < D ? (int)w[m] : D - 1;
+    const double *col = psi + (size_t)m * D;
+    y[m] = enkf_y_of(b, b >= 1 ? col[b - 1] : 0.0, col[b], P[m / mpp].psi_sat, dz);
+}
+
+// the sum over the block's threads in a fixed tree (every thread gets it)
+__device__ double enkf_block_sum(double v, double *sh)
+{
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = ENKF_THREADS / 2; s > 0; s >>= 1) {
+        if (threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    const double r = sh[0];
+    __syncthreads();
+    return r;
+}
+
+// One block per point: the mean of y and sum (y - mean)^2 / (N_p - 1) (0 for one member), two passes: ys[p] = {mean, v}.
+// With `stats` (the posterior y): the diagnostics' posterior mean, std and the count of rejected members.
+__global__ __launch_bounds__(ENKF_THREADS) void enkf_ystats_kernel(const double *y, const int *rej, long long mpp,
+                                                                   double *ys, double *stats, long long n_arow,
+                                                                   long long slot)
+{
+#pragma clang fp contract(off)
+    __shared__ double sh[ENKF_THREADS];
+    const long long p = blockIdx.x, first = p * mpp;
+    double s = 0.0;
+#pragma unroll 8
+    for (long long k = threadIdx.x; k < mpp; k += ENKF_THREADS) s += y[first + k];
+    const double mean = enkf_block_sum(s, sh) / (double)mpp;
+    double q = 0.0, nr = 0.0;
+#pragma unroll 8
+    for (long long k = threadIdx.x; k < mpp; k += ENKF_THREADS) {
+        const double a = y[first + k] - mean;
+        q += a * a;
+        if (rej) nr += (double)rej[first + k];
+    }
+    const double ss = enkf_block_sum(q, sh);
+    const double n_rej = enkf_block_sum(nr, sh);
+    if (threadIdx.x == 0) {
+        const double v = mpp > 1 ? ss / (double)(mpp - 1) : 0.0;
+        ys[2 * p] = mean;
+        ys[2 * p + 1] = v;
+        if (stats) {
+            double *st = stats + ((size_t)p * n_arow + slot) * ENKF_WIDTH;
+            st[5] = mean;
+            st[6] = sqrt(v);
+            st[7] = n_rej;
+        }
+    }
+}
+
+// partial[p][t][d]: the sum over tile t (ENKF_TILE members of point p) in member order of psi_dk (mean == NULL) or of
+// (psi_dk - mean_d)(y_k - ybar).  Thread d owns node d, so every member's row is one coalesced read of the block.
+__global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void enkf_col_partial_kernel(const double *psi, const double *y,
+                                                                              const double *ys, const double *mean,
+                                                                              long long mpp, int D, long long n_tiles,
+                                                                              double *partial)
+{
+#pragma clang fp contract(off)
+    const long long p = blockIdx.y, t = blockIdx.x;
+    const int d = threadIdx.x;
+    if (d >= D) return;
+    const long long m0 = p * mpp + t * ENKF_TILE;
+    const long long m1 = p * mpp + ((t + 1) * ENKF_TILE < mpp ? (t + 1) * ENKF_TILE : mpp);
+    double s = 0.0;
+    if (!mean) {
+#pragma unroll 8
+        for (long long m = m0; m < m1; m++) s += psi[(size_t)m * D + d];
+    } else {
+        const double md = mean[(size_t)p * D + d], yb = ys[2 * p];
+#pragma unroll 8
+        for (long long m = m0; m < m1; m++) s += (psi[(size_t)m * D + d] - md) * (y[m] - yb);
+    }
+    partial[((size_t)p * n_tiles + t) * D + d] = s;
+}
+
+// One block per node d and point p: the tile partials summed (thread t: tiles t, t + ENKF_THREADS, ... in order, then a
+// fixed tree).  gain == NULL: the column mean mean[p][d].  Otherwise c_d, the taper rho_d = GC(|z_d - ybar| / L) (L = 0:
+// 1) and K[p][d] = rho_d c_d / (v + sigma^2); block (0, p)'s thread 0 writes the prior entries of the diagnostics row
+// (count, ybar, sqrt v, innovation, log-likelihood increment).
+__global__ __launch_bounds__(ENKF_THREADS) void enkf_col_finish_kernel(const double *partial, long long n_tiles,
+                                                                       long long mpp, int D, const double *ys,
+                                                                       double *mean, double *gain, double sigma,
+                                                                       double loc, double z_obs, double dz, double *stats,
+                                                                       long long n_arow, long long slot)
+{
+#pragma clang fp contract(off)
+    __shared__ double sh[ENKF_THREADS];
+    const long long p = blockIdx.y;
+    const int d = blockIdx.x;
+    const double yb = ys[2 * p], s2 = ys[2 * p + 1] + sigma * sigma;
+    if (gain && blockIdx.x == 0 && threadIdx.x == 0) {
+        const double innov = z_obs - yb;
+        double *st = stats + ((size_t)p * n_arow + slot) * ENKF_WIDTH;
+        st[0] = (double)mpp;
+        st[1] = yb;
+        st[2] = sqrt(ys[2 * p + 1]);
+        st[3] = innov;
+        st[4] = -0.5 * log(2.0 * M_PI * s2) - 0.5 * (innov * innov) / s2;
+    }
+    double part = 0.0;
+    for (long long t = threadIdx.x; t < n_tiles; t += ENKF_THREADS) part += partial[((size_t)p * n_tiles + t) * D + d];
+    const double s = enkf_block_sum(part, sh);
+    if (threadIdx.x != 0) return;
+    if (!gain) {
+        mean[(size_t)p * D + d] = s / (double)mpp;
+        return;
+    }
+    const double c = mpp > 1 ? s / (double)(mpp - 1) : 0.0;
+    const double rho = loc > 0.0 ? gaspari_cohn(fabs((double)d * dz - yb) / loc) : 1.0;
+    gain[(size_t)p * D + d] = rho * c / s2;
+}
+
+// One wave per member: eps_k, o_k = z[o] + sigma eps_k, psi_dk + K_d (o_k - y_k) on every node, stored only when every
+// entry is finite (else the forecast stays and the member is counted as rejected); then the find_wtd index and the
+// posterior y of the column it kept.
+__global__ __launch_bounds__(256) void enkf_update_kernel(double *psi, const double *y, const double *gain,
+                                                          const ColumnDev *P, long long n_members, long long mpp, int D,
+                                                          double dz, double z_obs, double sigma, unsigned long long seed,
+                                                          const long long *point_base, long long member_offset,
+                                                          unsigned row, double *eps_out, double *y_post, int *rej)
+{
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x % WAVE;
+    const long long waves = (long long)gridDim.x * (blockDim.x / WAVE);
+    for (long long m = (long long)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE; m < n_members; m += waves) {
+        const long long p = m / mpp;
+        const unsigned long long gid = point_base ? (unsigned long long)(point_base[p] + m % mpp)
+                                                  : (unsigned long long)(member_offset + m);
+        const double eps = enkf_normal(seed, gid, row);
+        const double innov = (z_obs + sigma * eps) - y[m];
+        const double *K = gain + (size_t)p * D;
+        double *col = psi + (size_t)m * D;
+        double v[ENKF_SLOTS], a[ENKF_SLOTS];
+        bool ok = true;
+#pragma unroll
+        for (int c = 0; c < ENKF_SLOTS; c++) {
+            const int d = c * WAVE + lane;
+            v[c] = d < D ? col[d] : 0.0;
+            a[c] = d < D ? v[c] + K[d] * innov : 0.0;
+            ok = ok && isfinite(a[c]);
+        }
+        const bool keep = __all(ok);
+        if (keep) {
+#pragma unroll
+            for (int c = 0; c < ENKF_SLOTS; c++) {
+                const int d = c * WAVE + lane;
+                if (d < D) col[d] = a[c];
+                v[c] = a[c];
+            }
+        }
+        // find_wtd of the kept column (the step kernel's rule): below the deepest node with psi < psi_sat, clamped
+        const double psat = P[p].psi_sat;
+        int deepest = -1;
+#pragma unroll
+        for (int c = 0; c < ENKF_SLOTS; c++) {
+            const int d = c * WAVE + lane;
+            const unsigned long long u = __ballot(d < D && !(v[c] >= psat));
+            if (u) deepest = c * WAVE + 63 - __clzll((long long)u);
+        }
+        const int b = deepest < 0 ? 0 : (deepest + 1 < D - 1 ? deepest + 1 : D - 1);
+        const int bl = b >= 1 ? b - 1 : 0;
+        double hi = 0.0, lo = 0.0;
+#pragma unroll
+        for (int c = 0; c < ENKF_SLOTS; c++) {
+            const double x = __shfl(v[c], b % WAVE), xl = __shfl(v[c], bl % WAVE);
+            if (c == b / WAVE) hi = x;
+            if (c == bl / WAVE) lo = xl;
+        }
+        if (lane == 0) {
+            eps_out[m] = eps;
+            y_post[m] = enkf_y_of(b, lo, hi, psat, dz);
+            rej[m] = keep ? 0 : 1;
+        }
+    }
 }
 
 __global__ void widen_u16(const unsigned short *in, int *out, size_t n)
@@ -1082,8 +1326,8 @@ int ensure_filter(hc_handle *h)
     const int64_t n = (int64_t)h->n_points * filter_rows(h) * 4;
     if (int rc = t.ensure(h->n_points, h->n_rows, h->filt_stride, n)) return rc;
     if (fresh) {
-        hipLaunchKernelGGL(filter_stats_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, t.buf.p,
-                           (size_t)n);
+        hipLaunchKernelGGL(stats_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, t.buf.p,
+                           (size_t)n, 4);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(h->stream));
     }
@@ -1099,6 +1343,41 @@ void filter_off(hc_handle *h)
     h->psi_alt.release(); h->base_alt.release();
     h->filt_q.release(); h->filt_anc.release(); h->filt_tiles.release(); h->filt_rows.release();
     h->filt_qr.release(); h->filt_surv.release();
+}
+
+// the EnKF's diagnostics (hc_set_enkf): [P][n_arow][8] float64, created as count 0 and NaN
+int64_t enkf_rows(const hc_handle *h) { return (h->n_rows - 1) / h->enkf_stride + 1; }
+int ensure_enkf(hc_handle *h)
+{
+    if (h->enkf_stride <= 0) return fail(HC_ERR_ARG, "the EnKF is off (hc_set_enkf)");
+    if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
+    AccTable<double> &t = h->enkf;
+    const bool fresh = !(t.key[0] == h->n_points && t.key[1] == h->n_rows && t.key[2] == h->enkf_stride);
+    const int64_t n = (int64_t)h->n_points * enkf_rows(h) * ENKF_WIDTH;
+    if (int rc = t.ensure(h->n_points, h->n_rows, h->enkf_stride, n)) return rc;
+    if (fresh) {
+        hipLaunchKernelGGL(stats_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, t.buf.p,
+                           (size_t)n, ENKF_WIDTH);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    return HC_OK;
+}
+
+void enkf_off(hc_handle *h)
+{
+    h->enkf_stride = 0;
+    h->enkf_done = false;
+    h->enkf.release();
+    h->enkf_y.release(); h->enkf_eps.release(); h->enkf_ypost.release(); h->enkf_ys.release();
+    h->enkf_mean.release(); h->enkf_gain.release(); h->enkf_part.release(); h->enkf_rej.release();
+}
+
+// what turns both filters off: new points, members or noise source (include/hydrocol.h hc_set_filter, hc_set_enkf)
+void assimilation_off(hc_handle *h)
+{
+    filter_off(h);
+    enkf_off(h);
 }
 
 // The bodies of the table entry points: the table as `ensure` leaves it (its rules and refusals), a size check when the
@@ -1324,7 +1603,7 @@ int hc_destroy(hc_handle *h)
     h->point_base.release(); h->point_order.release(); h->point_cost.release();
     h->daylight.release(); h->refresh.release(); h->wtd_u16.release(); h->moments.release(); h->counters.release();
     h->prof.release(); h->hist.release();
-    filter_off(h);
+    assimilation_off(h);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1423,9 +1702,9 @@ static int build_point(hc_handle *h, const hc_column_params *p, const double *no
     } else {
         h->special = h->special && special;
     }
-    if (h->filt_stride > 0) {                    // the points change: the filter is off
+    if (h->filt_stride > 0 || h->enkf_stride > 0) {   // the points change: the filters are off
         (void)hipStreamSynchronize(h->stream);
-        filter_off(h);
+        assimilation_off(h);
     }
     h->P_host.push_back(P);
     h->tab_host.insert(h->tab_host.end(), tab.begin(), tab.end());
@@ -1552,7 +1831,7 @@ int hc_set_members(hc_handle *h, int64_t n_members)
     if (!h->have_column) return fail(HC_ERR_ARG, "hc_set_column must come first");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    filter_off(h);
+    assimilation_off(h);
     const size_t n = (size_t)n_members * h->p.dim_d;
     if (h->psi.ensure(n) || h->nscale.ensure((size_t)n_members)) return HC_ERR_DEVICE;
     hipLaunchKernelGGL(fill_d, dim3((unsigned)((n_members + 255) / 256)), dim3(256), 0, h->stream, h->nscale.p, 1.0,
@@ -1607,7 +1886,7 @@ int hc_set_noise_host(hc_handle *h, const double *base)
     if (h->n_members <= 0) return fail(HC_ERR_ARG, "hc_set_members must come first");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    filter_off(h);
+    assimilation_off(h);
     const size_t n = (size_t)h->n_members * h->p.dim_d;
     if (h->base.ensure(n)) return HC_ERR_DEVICE;
     HIP_TRY(hipMemcpy(h->base.p, base, n * 8, hipMemcpyHostToDevice));
@@ -1633,7 +1912,7 @@ int hc_set_noise_philox(hc_handle *h, uint64_t seed, int64_t member_offset)
     if (h->n_members <= 0) return fail(HC_ERR_ARG, "hc_set_members must come first");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    filter_off(h);
+    assimilation_off(h);
     hipLaunchKernelGGL(fill_d, dim3((unsigned)((h->n_members + 255) / 256)), dim3(256), 0, h->stream, h->nscale.p,
                        1.0, (size_t)h->n_members);
     HIP_TRY(hipGetLastError());
@@ -1756,13 +2035,17 @@ struct Chunk {
 // a filtered Philox run stages the launch's refresh vectors (N D doubles each) on the device: about 4 GiB at most
 constexpr int64_t FILT_FRESH_BYTES = int64_t(4) << 30;
 
+// the stride of whichever filter is on (the particle filter and the EnKF exclude each other), 0: none
+int64_t da_stride(const hc_handle *h) { return h->filt_stride > 0 ? h->filt_stride : h->enkf_stride; }
+
 bool is_assimilation_row(const hc_handle *h, int64_t row)
 {
-    return h->filt_stride > 0 && row >= 1 && row % h->filt_stride == 0 && h->h_wtd_obs[(size_t)row] >= 0;
+    const int64_t s = da_stride(h);
+    return s > 0 && row >= 1 && row % s == 0 && h->h_wtd_obs[(size_t)row] >= 0;
 }
 
-// The launch after `done` rows of the request.  With the filter on, a launch ends on the next assimilation row and, in a
-// filtered Philox run, holds at most as many refresh rows as FILT_FRESH_BYTES admits.
+// The launch after `done` rows of the request.  With a filter on, a launch ends on the next assimilation row and, in a
+// Philox run with the particle filter, holds at most as many refresh rows as FILT_FRESH_BYTES admits.
 Chunk plan_chunk(const hc_handle *h, const hc_step_args *a, int64_t done, bool prof_on)
 {
     const int64_t N = h->n_members, D = h->p.dim_d;
@@ -1777,8 +2060,8 @@ Chunk plan_chunk(const hc_handle *h, const hc_step_args *a, int64_t done, bool p
     Chunk c;
     c.rows = (int)std::min<int64_t>(per_launch, a->n_rows - done);
     c.row0 = a->spinup ? a->row_begin : a->row_begin + done;
-    if (h->filt_stride > 0 && !a->spinup) {
-        const int64_t s = h->filt_stride;
+    if (da_stride(h) > 0 && !a->spinup) {
+        const int64_t s = da_stride(h);
         for (int64_t r = std::max<int64_t>(s, (c.row0 + s - 1) / s * s); r < c.row0 + c.rows; r += s)
             if (is_assimilation_row(h, r)) {
                 c.rows = (int)(r - c.row0 + 1);
@@ -1975,6 +2258,56 @@ int assimilate(hc_handle *h, const Chunk &c)
     return HC_OK;
 }
 
+// The EnKF's analysis at the launch's last row (its water-table indices are wtd_u16's last row), in place on psi: y per
+// member; per point ybar and v, the column means, then c_d, the gain and the prior diagnostics; the update with eps and
+// the posterior y per member; the posterior diagnostics.  Three passes over psi (two reads, one read + write).
+int enkf_analyse(hc_handle *h, const Chunk &c)
+{
+    const int64_t N = h->n_members, D = h->p.dim_d, P = h->n_points, mpp = N / P;
+    const int64_t row = c.row0 + c.rows - 1, slot = row / h->enkf_stride, n_arow = enkf_rows(h);
+    const int64_t n_tiles = (mpp + ENKF_TILE - 1) / ENKF_TILE;
+    if (h->enkf_y.ensure((size_t)N) || h->enkf_eps.ensure((size_t)N) || h->enkf_ypost.ensure((size_t)N) ||
+        h->enkf_rej.ensure((size_t)N) || h->enkf_ys.ensure((size_t)(2 * P)) || h->enkf_mean.ensure((size_t)(P * D)) ||
+        h->enkf_gain.ensure((size_t)(P * D)) || h->enkf_part.ensure((size_t)(P * n_tiles * D)))
+        return HC_ERR_DEVICE;
+    const unsigned short *w = h->wtd_u16.p + (size_t)(c.rows - 1) * N;
+    const double dz = h->p.dz, z_obs = (double)h->h_wtd_obs[(size_t)row] * dz;
+    double *st = h->enkf.buf.p;
+    hipLaunchKernelGGL(enkf_obs_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, w, h->psi.p, h->Pdev.p,
+                       (long long)N, (long long)mpp, (int)D, dz, h->enkf_y.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(enkf_ystats_kernel, dim3((unsigned)P), dim3(ENKF_THREADS), 0, h->stream, h->enkf_y.p, nullptr,
+                       (long long)mpp, h->enkf_ys.p, nullptr, (long long)n_arow, (long long)slot);
+    HIP_TRY(hipGetLastError());
+    const dim3 tiles((unsigned)n_tiles, (unsigned)P), cols((unsigned)((D + WAVE - 1) / WAVE * WAVE));
+    const dim3 fin((unsigned)D, (unsigned)P);
+    hipLaunchKernelGGL(enkf_col_partial_kernel, tiles, cols, 0, h->stream, h->psi.p, h->enkf_y.p, h->enkf_ys.p, nullptr,
+                       (long long)mpp, (int)D, (long long)n_tiles, h->enkf_part.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(enkf_col_finish_kernel, fin, dim3(ENKF_THREADS), 0, h->stream, h->enkf_part.p, (long long)n_tiles,
+                       (long long)mpp, (int)D, h->enkf_ys.p, h->enkf_mean.p, nullptr, h->enkf_sigma, h->enkf_loc, z_obs, dz,
+                       st, (long long)n_arow, (long long)slot);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(enkf_col_partial_kernel, tiles, cols, 0, h->stream, h->psi.p, h->enkf_y.p, h->enkf_ys.p,
+                       h->enkf_mean.p, (long long)mpp, (int)D, (long long)n_tiles, h->enkf_part.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(enkf_col_finish_kernel, fin, dim3(ENKF_THREADS), 0, h->stream, h->enkf_part.p, (long long)n_tiles,
+                       (long long)mpp, (int)D, h->enkf_ys.p, nullptr, h->enkf_gain.p, h->enkf_sigma, h->enkf_loc, z_obs,
+                       dz, st, (long long)n_arow, (long long)slot);
+    HIP_TRY(hipGetLastError());
+    const unsigned blocks = (unsigned)std::min<int64_t>((N + 3) / 4, (int64_t)h->n_cu * 8);
+    hipLaunchKernelGGL(enkf_update_kernel, dim3(blocks), dim3(256), 0, h->stream, h->psi.p, h->enkf_y.p, h->enkf_gain.p,
+                       h->Pdev.p, (long long)N, (long long)mpp, (int)D, dz, z_obs, h->enkf_sigma,
+                       (unsigned long long)h->enkf_seed, P > 1 ? h->point_base.p : nullptr, (long long)h->member_offset,
+                       (unsigned)row, h->enkf_eps.p, h->enkf_ypost.p, h->enkf_rej.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(enkf_ystats_kernel, dim3((unsigned)P), dim3(ENKF_THREADS), 0, h->stream, h->enkf_ypost.p,
+                       h->enkf_rej.p, (long long)mpp, h->enkf_ys.p, st, (long long)n_arow, (long long)slot);
+    HIP_TRY(hipGetLastError());
+    h->enkf_done = true;
+    return HC_OK;
+}
+
 // After the launches of a call: a split-column mailbox exchange that timed out invalidates the results.  An attempt that
 // exhausts the kernel's iteration budget is abandoned like a solve that gave up (the x0.8 retry rule applies); it is
 // counted ([2], last place in [3]) and only fatal on request.
@@ -2020,6 +2353,8 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
         return fail(HC_ERR_ARG, "spin-up solves with the particle filter on in a Philox run: set the filter after the spin-up");
     const bool filt_on = h->filt_stride > 0 && !a->spinup;
     if (filt_on && (rc = ensure_filter(h))) return rc;
+    const bool enkf_on = h->enkf_stride > 0 && !a->spinup;   // (the EnKF: spin-up solves are never analysed either)
+    if (enkf_on && (rc = ensure_enkf(h))) return rc;
     int64_t fresh_consumed = 0;
     for (int64_t done = 0; done < a->n_rows;) {
         const Chunk c = plan_chunk(h, a, done, prof_on);
@@ -2029,6 +2364,7 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
         if ((rc = accumulate(h, A, a, c, prof_on, hist_on))) return rc;
         if ((rc = copy_outputs(h, a, c, done))) return rc;
         if (filt_on && is_assimilation_row(h, c.row0 + c.rows - 1) && (rc = assimilate(h, c))) return rc;
+        if (enkf_on && is_assimilation_row(h, c.row0 + c.rows - 1) && (rc = enkf_analyse(h, c))) return rc;
         HIP_TRY(hipStreamSynchronize(h->stream));
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
@@ -2291,6 +2627,8 @@ int hc_wtd_distribution(int device, const int32_t *hist, const int32_t *obs_idx,
 int hc_set_filter(hc_handle *h, int32_t stride, double sigma_cm, uint64_t seed)
 {
     if (!h || stride < 0) return fail(HC_ERR_ARG, "hc_set_filter: bad argument");
+    if (stride > 0 && h->enkf_stride > 0)
+        return fail(HC_ERR_ARG, "hc_set_filter: the EnKF is on (hc_set_enkf with stride 0 turns it off)");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
     filter_off(h);
@@ -2397,6 +2735,70 @@ int hc_set_filter_base(hc_handle *h, const double *base)
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipMemcpy(h->base.p, base, n * 8, hipMemcpyHostToDevice));
     return HC_OK;
+}
+
+int hc_set_enkf(hc_handle *h, int32_t stride, double sigma_cm, double localisation_cm, uint64_t seed)
+{
+    if (!h || stride < 0) return fail(HC_ERR_ARG, "hc_set_enkf: bad argument");
+    if (stride > 0 && h->filt_stride > 0)
+        return fail(HC_ERR_ARG, "hc_set_enkf: the particle filter is on (hc_set_filter with stride 0 turns it off)");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    enkf_off(h);
+    if (stride == 0) return HC_OK;
+    if (!(std::isfinite(sigma_cm) && sigma_cm > 0.0))
+        return fail(HC_ERR_ARG, "hc_set_enkf: sigma_cm = %g must be finite and > 0", sigma_cm);
+    if (!(std::isfinite(localisation_cm) && localisation_cm >= 0.0))
+        return fail(HC_ERR_ARG, "hc_set_enkf: localisation_cm = %g must be finite and >= 0", localisation_cm);
+    StepArgs A;
+    if (int rc = fill_args(h, A)) return rc;     // column, forcing, members and noise are in place; point keys uploaded
+    if (h->n_rows > (int64_t)UINT32_MAX) return fail(HC_ERR_ARG, "hc_set_enkf: %lld forcing rows exceed 2^32 - 1", (long long)h->n_rows);
+    h->enkf_stride = stride;
+    h->enkf_sigma = sigma_cm;
+    h->enkf_loc = localisation_cm;
+    h->enkf_seed = seed;
+    const int rc = ensure_enkf(h);
+    if (rc != HC_OK) enkf_off(h);                // refused: off
+    return rc;
+}
+
+int hc_get_enkf_stats(hc_handle *h, double *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_get_enkf_stats: bad argument");
+    return table_copy(h, h->enkf, ensure_enkf, hipMemcpyDeviceToHost, table, n_entries, "hc_get_enkf_stats");
+}
+
+int hc_set_enkf_stats(hc_handle *h, const double *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_set_enkf_stats: bad argument");
+    return table_copy(h, h->enkf, ensure_enkf, hipMemcpyHostToDevice, const_cast<double *>(table), n_entries,
+                      "hc_set_enkf_stats");
+}
+
+// the last analysis's buffers (test hooks)
+static int enkf_hook(hc_handle *h, const double *src, double *out, size_t count, const char *who)
+{
+    if (!h || !out) return fail(HC_ERR_ARG, "%s: bad argument", who);
+    if (h->enkf_stride <= 0 || !h->enkf_done) return fail(HC_ERR_ARG, "%s: no analysis since hc_set_enkf", who);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(out, src, count * 8, hipMemcpyDeviceToHost));
+    return HC_OK;
+}
+
+int hc_get_enkf_gain(hc_handle *h, double *gain)
+{
+    return enkf_hook(h, h ? h->enkf_gain.p : nullptr, gain, h ? (size_t)h->n_points * h->p.dim_d : 0, "hc_get_enkf_gain");
+}
+
+int hc_get_enkf_y(hc_handle *h, double *y)
+{
+    return enkf_hook(h, h ? h->enkf_y.p : nullptr, y, h ? (size_t)h->n_members : 0, "hc_get_enkf_y");
+}
+
+int hc_get_enkf_eps(hc_handle *h, double *eps)
+{
+    return enkf_hook(h, h ? h->enkf_eps.p : nullptr, eps, h ? (size_t)h->n_members : 0, "hc_get_enkf_eps");
 }
 
 // The path's one collective without torch: a single process that drives several devices (one handle each) sums the
@@ -2507,10 +2909,10 @@ int hc_set_point_member_bases(hc_handle *h, const int64_t *base)
 {
     if (!h) return fail(HC_ERR_ARG, "NULL handle");
     if (!h->have_column) return fail(HC_ERR_ARG, "hc_set_column must come first");
-    if (h->filt_stride > 0) {                    // the points' stream keys change: the filter is off
+    if (h->filt_stride > 0 || h->enkf_stride > 0) {   // the points' stream keys change: the filters are off
         HIP_TRY(hipSetDevice(h->device));
         HIP_TRY(hipStreamSynchronize(h->stream));
-        filter_off(h);
+        assimilation_off(h);
     }
     h->base_host.clear();
     if (base) {

@@ -9,7 +9,7 @@ all-reduce of the per-row water-table moments (see :func:`allreduce_moments`).
 import numpy as np
 
 from .digest import inverse_retention
-from .stepper import EnsembleStepper, filter_summary, moments_to_mean_std, wtd_distribution
+from .stepper import ENKF_WIDTH, EnsembleStepper, enkf_summary, filter_summary, moments_to_mean_std, wtd_distribution
 
 
 def pressure_head(cols, theta):
@@ -99,11 +99,15 @@ class _Run:
     filter_stride > 0: a bootstrap particle filter on the well's water table every ``filter_stride``-th row with an
     observation (``filter_sigma_cm``: the observation error; ``filter_seed``: default the run's seed): the tables above
     describe the forecast, the states continue from the analysis; :meth:`filter_summary` (ESS, log marginal likelihood).
+    enkf_stride > 0: a stochastic ensemble Kalman filter on the well's continuous water table instead (``enkf_sigma_cm``:
+    the observation error; ``enkf_localisation_cm``: the Gaspari-Cohn half-width, 0 = none; ``enkf_seed``: default the
+    run's seed), with the same forecast / analysis order; :meth:`enkf_summary` (log marginal likelihood).
     ``_lead`` is the leading shape of the per-point tables: () for an ensemble, (P,) for a sweep."""
 
     _lead = ()
 
-    def _start_tables(self, profile_stride, wtd_hist_stride, filter_stride=0, filter_sigma_cm=None, filter_seed=None):
+    def _start_tables(self, profile_stride, wtd_hist_stride, filter_stride=0, filter_sigma_cm=None, filter_seed=None,
+                      enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None):
         self.profile_stride = int(profile_stride)
         if self.profile_stride:
             self.stepper.set_profile_stats(self.profile_stride)
@@ -116,6 +120,12 @@ class _Run:
         self.filter_seed = (self.seed if filter_seed is None else int(filter_seed)) if self.filter_stride else None
         if self.filter_stride:
             self.stepper.set_filter(self.filter_stride, self.filter_sigma_cm, self.filter_seed)
+        self.enkf_stride = int(enkf_stride or 0)
+        self.enkf_sigma_cm = float(enkf_sigma_cm) if self.enkf_stride else None
+        self.enkf_localisation_cm = float(enkf_localisation_cm or 0.0) if self.enkf_stride else None
+        self.enkf_seed = (self.seed if enkf_seed is None else int(enkf_seed)) if self.enkf_stride else None
+        if self.enkf_stride:
+            self.stepper.set_enkf(self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed)
 
     def advance(self, n_rows, **kw):
         """Solve the next ``n_rows`` forcing rows for every member."""
@@ -161,6 +171,18 @@ class _Run:
         t = self.filter_table() if table is None else table
         return filter_summary(t, self.filter_stride, self.filter_sigma_cm)
 
+    def enkf_table(self):
+        """[n_arow][8] float64 (include/hydrocol.h hc_set_enkf; depths from the top node); a sweep: [P][n_arow][8]."""
+        return self.stepper.enkf_table().reshape(self._lead + (-1, ENKF_WIDTH))
+
+    def enkf_summary(self, table=None):
+        """The EnKF's record (stepper.enkf_summary, means at the well's depths): ``rows``, ``count``, ``prior_mean_cm``,
+        ``prior_std_cm``, ``innovation_cm``, ``loglik_rows``, ``post_mean_cm``, ``post_std_cm``, ``rejected`` over the
+        analysed rows and ``loglik``, the log marginal likelihood of the well record (log cm^-1), with a leading [P] for a
+        sweep; ``table``: e.g. the one assembled over ranks."""
+        t = self.enkf_table() if table is None else table
+        return enkf_summary(t, self.enkf_stride, self.enkf_sigma_cm, float(self.cols.z[0]))
+
     def close(self):
         self.stepper.close()
 
@@ -173,15 +195,17 @@ class EnsembleSimulation(_Run):
     #1 base vector, then one vector per refresh row (simulation.py:426,561,601) -- and uploaded per launch.
     spinup="shared" (default): one spin-up (global member 0's first draw) broadcast to all members;
     spinup="member": every member spins up with its own first draw (`spinup_members_on_gpu`).
-    profile_stride, wtd_hist_stride, filter_stride / filter_sigma_cm / filter_seed: the optional tables and the particle
-    filter (:class:`_Run`).
+    profile_stride, wtd_hist_stride, filter_stride / filter_sigma_cm / filter_seed, enkf_stride / enkf_sigma_cm /
+    enkf_localisation_cm / enkf_seed: the optional tables, the particle filter and the EnKF (:class:`_Run`).
     """
 
     def __init__(self, cols, forcing, n_members, seed=0, device=0, member_offset=0, psi0=None, flags=None,
                  noise="philox", spinup="shared", profile_stride=0, wtd_hist_stride=0, filter_stride=0,
-                 filter_sigma_cm=None, filter_seed=None):
+                 filter_sigma_cm=None, filter_seed=None, enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0,
+                 enkf_seed=None):
         self._start(cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup)
-        self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed)
+        self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
+                           enkf_sigma_cm, enkf_localisation_cm, enkf_seed)
 
     def _start(self, cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup):
         if noise not in ("philox", "numpy") or spinup not in ("shared", "member"):
@@ -285,6 +309,12 @@ class EnsembleSimulation(_Run):
             arrays["filter_seed"] = np.array(self.filter_seed, dtype=np.uint64)
             arrays["filter_table"] = self.stepper.filter_table()
             arrays["filter_base"] = self.stepper.filter_base()
+        if self.enkf_stride:
+            arrays["enkf_stride"] = np.array(self.enkf_stride, dtype=np.int64)
+            arrays["enkf_sigma_cm"] = np.array(self.enkf_sigma_cm, dtype=np.float64)
+            arrays["enkf_localisation_cm"] = np.array(self.enkf_localisation_cm, dtype=np.float64)
+            arrays["enkf_seed"] = np.array(self.enkf_seed, dtype=np.uint64)
+            arrays["enkf_table"] = self.stepper.enkf_table()
         path = Path(path)
         if hdf5io.available() and path.suffix != ".npz":
             hdf5io.write(path, arrays)
@@ -313,6 +343,10 @@ class EnsembleSimulation(_Run):
         filt = int(data["filter_stride"]) if "filter_stride" in data else 0
         fkw = dict(filter_stride=filt, filter_sigma_cm=float(data["filter_sigma_cm"]),
                    filter_seed=int(data["filter_seed"])) if filt else {}
+        enkf = int(data["enkf_stride"]) if "enkf_stride" in data else 0
+        if enkf:
+            fkw.update(enkf_stride=enkf, enkf_sigma_cm=float(data["enkf_sigma_cm"]),
+                       enkf_localisation_cm=float(data["enkf_localisation_cm"]), enkf_seed=int(data["enkf_seed"]))
         sim = cls(cols, forcing, n, seed=int(data["seed"]), device=device, member_offset=int(data["member_offset"]),
                   psi0=np.asarray(data["initial_cond"], dtype=float).reshape(-1)[:D], flags=flags, profile_stride=stride,
                   wtd_hist_stride=hist_stride, **fkw)
@@ -322,6 +356,8 @@ class EnsembleSimulation(_Run):
             sim.stepper.set_filter_base(np.asarray(data["filter_base"], dtype=np.float64).reshape(n, D))
         else:
             sim.stepper.set_noise_scale(np.asarray(data["noise_scale"], dtype=float).reshape(n))
+        if enkf:
+            sim.stepper.set_enkf_table(np.asarray(data["enkf_table"], dtype=np.float64))
         sim.stepper.set_moments(np.asarray(data["moments"], dtype=np.int64))
         if stride:
             sim.stepper.set_profile_table(np.asarray(data["profile_table"], dtype=np.int64))
@@ -419,7 +455,7 @@ class SweepSimulation(_Run):
 
     def __init__(self, cols_list, forcing, n_members, seed=0, device=0, first_point=0, flags=None, psi0=None,
                  point_ids=None, profile_stride=0, wtd_hist_stride=0, filter_stride=0, filter_sigma_cm=None,
-                 filter_seed=None):
+                 filter_seed=None, enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None):
         self.points = list(cols_list)
         self.P, self.n = len(self.points), int(n_members)
         self._lead = (self.P,)
@@ -446,7 +482,8 @@ class SweepSimulation(_Run):
         self.stepper.set_noise_philox(self.seed, self.member_offset)
         if self.P > 1:
             self.stepper.set_point_member_bases(self.bases)
-        self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed)
+        self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
+                           enkf_sigma_cm, enkf_localisation_cm, enkf_seed)
         self.next_row, self.kernel_ms, self.launches = 1, 0.0, 0
 
     def _spinup(self, flags):

@@ -77,6 +77,7 @@ class EnsembleStepper:
         self.profile_stride = 0
         self.wtd_hist_stride = 0
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = 0, 0.0, 0
+        self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
         if profile_stride:
             self.set_profile_stats(profile_stride)
 
@@ -325,13 +326,15 @@ class EnsembleStepper:
         sigma = float(sigma_cm) if stride else 0.0
         if stride and not (np.isfinite(sigma) and sigma > 0.0):
             raise ValueError(f"filter sigma_cm = {sigma_cm!r} must be finite and > 0")
-        self._filter_off()                                    # hc_set_filter turns it off first, and leaves it off if it refuses
+        self.filter_stride, self.filter_sigma_cm, self.filter_seed = 0, 0.0, 0   # hc_set_filter turns it off first,
+        #                                                                            and leaves it off if it refuses
         L.check(self.lib.hc_set_filter(self.h, stride, sigma, int(seed) & 0xFFFFFFFFFFFFFFFF))
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = stride, sigma, int(seed)
 
     def _filter_off(self):
-        """The library turned the filter off (a new noise source or new point keys, include/hydrocol.h): so does this side."""
+        """The library turned the filters off (a new noise source or new point keys, include/hydrocol.h): so does this side."""
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = 0, 0.0, 0
+        self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
 
     def filter_table(self):
         """[P][n_arow][4] float64: count, ESS, log-likelihood increment, survivors per assimilation slot (slot j <-> row
@@ -372,6 +375,57 @@ class EnsembleStepper:
         """[P] int64: the systematic offset r of the last assimilation (test hook)."""
         out = np.zeros(self.P, dtype=np.int64)
         L.check(self.lib.hc_get_filter_draw(self.h, L.lptr(out)))
+        return out
+
+    # -- ensemble Kalman filter on the well's water table (include/hydrocol.h hc_set_enkf) ------------------------------
+    def set_enkf(self, stride, sigma_cm=None, localisation_cm=0.0, seed=0):
+        """Update the members on every ``stride``-th forcing row that has an observation (0 = off): a stochastic EnKF on
+        the continuous water table y (``sigma_cm``: the observation error; ``localisation_cm``: the Gaspari-Cohn half-width
+        L, 0 = none).  The tables accumulate the forecast; the states after the call are the analysis.  Refused while the
+        particle filter is on."""
+        stride = int(stride)
+        if stride < 0:
+            raise ValueError(f"EnKF stride must be >= 0, got {stride}")
+        sigma = float(sigma_cm) if stride else 0.0
+        loc = float(localisation_cm) if stride else 0.0
+        if stride and not (np.isfinite(sigma) and sigma > 0.0):
+            raise ValueError(f"EnKF sigma_cm = {sigma_cm!r} must be finite and > 0")
+        if stride and not (np.isfinite(loc) and loc >= 0.0):
+            raise ValueError(f"EnKF localisation_cm = {localisation_cm!r} must be finite and >= 0")
+        if stride and self.filter_stride:
+            raise ValueError("the particle filter is on: the EnKF and the filter exclude each other")
+        self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
+        L.check(self.lib.hc_set_enkf(self.h, stride, sigma, loc, int(seed) & 0xFFFFFFFFFFFFFFFF))
+        self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = stride, sigma, loc, int(seed)
+
+    def enkf_table(self):
+        """[P][n_arow][8] float64 per analysis slot (slot j <-> row j stride): count, prior mean and std of y, innovation,
+        log-likelihood increment, posterior mean and std of y, rejected members; count 0 and NaN where nothing was
+        analysed.  Depths from the top node (z[i] - z[0])."""
+        t = np.zeros((self.P, stride_rows(self.T, self.enkf_stride), ENKF_WIDTH))
+        L.check(self.lib.hc_get_enkf_stats(self.h, L.dptr(t), t.size))
+        return t
+
+    def set_enkf_table(self, table):
+        t = L.as_f64(table).reshape(-1)
+        L.check(self.lib.hc_set_enkf_stats(self.h, L.dptr(t), t.size))
+
+    def enkf_gain(self):
+        """[P][D] the gain K_d of the last analysis (test hook)."""
+        out = np.zeros((self.P, self.D))
+        L.check(self.lib.hc_get_enkf_gain(self.h, L.dptr(out)))
+        return out
+
+    def enkf_y(self):
+        """[N] the forecast y_k of the last analysis, cm from the top node (test hook)."""
+        out = np.zeros(self.N)
+        L.check(self.lib.hc_get_enkf_y(self.h, L.dptr(out)))
+        return out
+
+    def enkf_eps(self):
+        """[N] the observation perturbations eps_k of the last analysis (test hook)."""
+        out = np.zeros(self.N)
+        L.check(self.lib.hc_get_enkf_eps(self.h, L.dptr(out)))
         return out
 
     # -- hooks ----------------------------------------------------------------------
@@ -607,6 +661,41 @@ def filter_summary(table, stride, sigma_cm):
     return {"rows": slots.astype(np.int64) * int(stride), "count": sel[..., 0].astype(np.int64), "ess": sel[..., 1],
             "loglik_rows": inc, "survivors": np.nan_to_num(sel[..., 3]).astype(np.int64),
             "loglik": loglik if loglik.ndim else float(loglik), "stride": int(stride), "sigma_cm": float(sigma_cm)}
+
+
+# ---- ensemble Kalman filter on the host (include/hydrocol.h hc_set_enkf) -----------------------------------------------
+ENKF_WIDTH = 8
+
+
+def gaspari_cohn(r):
+    """The Gaspari & Cohn (1999, eq. 4.10) fifth-order taper of r = distance / L: 1 at 0, 0 from r = 2 on, continuous
+    with continuous derivatives (the device's evaluation order, float64)."""
+    r = np.asarray(r, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inner = (((-0.25 * r + 0.5) * r + 0.625) * r - 5.0 / 3.0) * r * r + 1.0
+        outer = ((((r / 12.0 - 0.5) * r + 0.625) * r + 5.0 / 3.0) * r - 5.0) * r + 4.0 - 2.0 / (3.0 * r)
+    out = np.where(r <= 1.0, inner, np.where(r <= 2.0, outer, 0.0))
+    return out if out.ndim else float(out)
+
+
+def enkf_summary(table, stride, sigma_cm, z0_cm=0.0):
+    """The EnKF's record from its [..., n_arow, 8] table: ``rows`` (forcing row of every analysed slot), ``count``,
+    ``prior_mean_cm``, ``prior_std_cm``, ``innovation_cm``, ``loglik_rows`` (the increments), ``post_mean_cm``,
+    ``post_std_cm``, ``rejected`` [..., R] over the slots any point analysed, and ``loglik`` [...] = the sum of the
+    increments in row order; the means are moved from the top node to ``z0_cm`` (the well's z[0])."""
+    t = np.asarray(table, dtype=np.float64)
+    used = (t[..., 0] > 0).reshape(-1, t.shape[-2]).any(axis=0)
+    slots = np.flatnonzero(used)
+    sel = t[..., slots, :]
+    inc = sel[..., 4]
+    loglik = np.zeros(inc.shape[:-1])
+    for j in range(inc.shape[-1]):                      # row order
+        loglik = loglik + np.where(sel[..., j, 0] > 0, inc[..., j], 0.0)
+    return {"rows": slots.astype(np.int64) * int(stride), "count": sel[..., 0].astype(np.int64),
+            "prior_mean_cm": sel[..., 1] + z0_cm, "prior_std_cm": sel[..., 2], "innovation_cm": sel[..., 3],
+            "loglik_rows": inc, "post_mean_cm": sel[..., 5] + z0_cm, "post_std_cm": sel[..., 6],
+            "rejected": np.nan_to_num(sel[..., 7]).astype(np.int64), "loglik": loglik if loglik.ndim else float(loglik),
+            "stride": int(stride), "sigma_cm": float(sigma_cm)}
 
 
 def allreduce_handles(steppers):

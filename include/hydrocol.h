@@ -42,6 +42,8 @@
  *   hc_set_filter, hc_get/set_filter_stats, hc_get/set_filter_base, hc_get_filter_ancestors/weights/draw
  *                      <- (new) the ensemble conditioned on wtd_obs (src/simulation.py:582-612): a bootstrap particle filter,
  *                         and the log marginal likelihood of the well record per parameter point
+ *   hc_set_enkf, hc_get/set_enkf_stats, hc_get_enkf_gain/y/eps
+ *                      <- (new) the same conditioning by a stochastic ensemble Kalman filter on a continuous water table
  *
  * Conventions: every function returns 0 on success or a negative hc_status; nothing throws
  * or aborts across the boundary; hc_last_error() gives the thread-local message.  Host
@@ -362,6 +364,55 @@ int hc_set_filter_base(hc_handle *h, const double *base);
 int hc_get_filter_ancestors(hc_handle *h, int64_t *ancestors);
 int hc_get_filter_weights(hc_handle *h, int64_t *q);
 int hc_get_filter_draw(hc_handle *h, int64_t *r);
+
+/* Ensemble Kalman filter on the well's water table (stochastic EnKF: perturbed observations, Evensen 1994 / Burgers et al.
+ * 1998).  It moves every member's psi by the sample covariance between psi and the observed quantity; noise is untouched.
+ *   Analysis rows, launches and order: as for hc_set_filter -- r >= 1, r % stride == 0 and wtd_obs[r] >= 0 (as it stands
+ *   when hc_step_rows reaches the row); slot j <-> row j stride, n_arow = (n_forcing_rows - 1) / stride + 1, slot 0 stays
+ *   empty; a launch ends on every analysis row; spin-up solves are never analysed.  The row is solved, every table
+ *   accumulates it (the FORECAST), then the analysis updates psi: psi_rows_out and wtd_out hold the forecast of the row,
+ *   hc_get_state returns the ANALYSIS.
+ *   Depths: z_i = i dz, measured from the top node (the C-ABI has no z[0]; only the two means of the diagnostics depend on
+ *   it, and the host adds the well's z[0] to them).
+ *   Observation operator, per member (a continuous water table): b = the member's find_wtd index (the index wtd_out returns);
+ *     y = z[b-1] + dz * (psi_sat - psi[b-1]) / (psi[b] - psi[b-1])   if b >= 1 and psi[b-1] < psi_sat <= psi[b],
+ *     y = z[b]                                                        otherwise,
+ *   psi_sat of the member's point.  So y lies in (z[b-1], z[b]] and varies below one cell, where the reference's z[wtd_est]
+ *   (src/simulation.py:612-615) is discrete: a deliberate deviation, the filter needs the spread the index cannot give.
+ *   Perturbed observations: o = wtd_obs[r]; member k sees o_k = z[o] + sigma_cm eps_k, eps_k one standard normal of
+ *   Philox4x32-10 under the EnKF seed at counter (0xFFFFFFFE, r, key_lo, key_hi), key = the member's GLOBAL id
+ *   (member_offset + m; a sweep: the point's base + j), the first two output words (word 1 high) through the Box-Muller step
+ *   of the noise (its cosine branch).  A noise counter's first word is a depth index / 2 and the particle filter's is
+ *   0xFFFFFFFF: the three never meet.  eps_k depends on no launch length, member split or point order.
+ *   Per point p (N_p members), fp64 without contraction:
+ *     ybar, psibar_d = the member means; v = sum (y_k - ybar)^2 / (N_p - 1); c_d = sum (psi_dk - psibar_d)(y_k - ybar) / (N_p - 1)
+ *     (two passes: means, then anomalies; N_p = 1: v = c = 0);
+ *     rho_d = GC(|z_d - ybar| / L), the Gaspari-Cohn fifth-order taper with support 2 L (L = localisation_cm; L = 0: rho = 1);
+ *     K_d = rho_d c_d / (v + sigma_cm^2);  psi_dk <- psi_dk + K_d (o_k - y_k) on all D nodes.
+ *   A member whose updated column has a non-finite entry keeps its forecast and is counted as rejected.  Base noise
+ *   vectors, noise scales and draw counters are not touched (no caller-noise path: Philox runs keep their in-kernel noise).
+ *   Reproducibility: every sum over a point's members runs in an order fixed by N_p alone (the column sums in tiles of 256
+ *   members in member order, then the tile partials by 1024 threads in tile-strided order and a fixed tree; the sums of y
+ *   by 1024 threads in member-strided order and the same tree), no floating-point atomics: the analysis is the same to the bit at any launch length, point order, dealing of a
+ *   sweep's points to handles or ranks, and from run to run.
+ *   Diagnostics, float64 [P][n_arow][8] per point and slot: count = N_p; prior mean ybar (cm from z[0]); prior std sqrt(v)
+ *   (cm); innovation z[o] - ybar (cm); log-likelihood increment -0.5 log(2 pi (v + sigma^2)) - 0.5 (z[o] - ybar)^2 /
+ *   (v + sigma^2) (log cm^-1, the particle filter's unit); posterior mean and std of y (the same operator and sums on the
+ *   analysis states); rejected members.  Slots without an analysis hold count = 0 and NaN.  A point's log marginal
+ *   likelihood is the sum of its increments in row order (on the host).
+ * hc_set_enkf: stride 0 = off; otherwise (re)creates the table.  Needs column, forcing, members and noise source;
+ *   sigma_cm finite and > 0; localisation_cm finite and >= 0; at most 2^32 - 1 rows.  HC_ERR_ARG while the particle filter
+ *   is on (and hc_set_filter with a stride > 0 while the EnKF is on).  A later hc_set_column / hc_add_point /
+ *   hc_set_point_member_bases, hc_set_members, hc_set_noise_host or hc_set_noise_philox turns it off; hc_set_forcing
+ *   re-creates the table (count 0, NaN) when the row count changes.
+ * hc_get/set_enkf_stats: the table (P n_arow 8 entries; checkpoints, the assembly of a sweep over ranks).
+ * Test hooks of the last analysis: gain [P][D] (K_d), y [n_members] (the forecast y_k), eps [n_members]. */
+int hc_set_enkf(hc_handle *h, int32_t stride, double sigma_cm, double localisation_cm, uint64_t seed);
+int hc_get_enkf_stats(hc_handle *h, double *table, int64_t n_entries);
+int hc_set_enkf_stats(hc_handle *h, const double *table, int64_t n_entries);
+int hc_get_enkf_gain(hc_handle *h, double *gain);
+int hc_get_enkf_y(hc_handle *h, double *y);
+int hc_get_enkf_eps(hc_handle *h, double *eps);
 
 /* The path's one collective inside the library, for a single process that drives several devices with
  * one handle each: every handle's moment table is replaced by the sum over all n handles (ncclAllReduce, ncclInt64,
