@@ -106,6 +106,13 @@ EXPORTS = {
     "hc_get_enkf_gain": ([C.c_void_p, _dp], C.c_int),
     "hc_get_enkf_y": ([C.c_void_p, _dp], C.c_int),
     "hc_get_enkf_eps": ([C.c_void_p, _dp], C.c_int),
+    "hc_set_enkf_soil_moisture": ([C.c_void_p, C.c_int32, _ip, _dp, _dp], C.c_int),
+    "hc_get_enkf_sm_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),
+    "hc_set_enkf_sm_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),
+    "hc_get_enkf_sm_width": ([C.c_void_p, _ip], C.c_int),
+    "hc_get_enkf_sm_y": ([C.c_void_p, _dp], C.c_int),
+    "hc_get_enkf_sm_gain": ([C.c_void_p, _dp], C.c_int),
+    "hc_get_enkf_sm_eps": ([C.c_void_p, _dp], C.c_int),
     "hc_rhs": ([C.c_void_p, C.c_int64, C.c_int32, _dp, _dp], C.c_int),
     "hc_model_nodes": ([C.c_void_p, _dp, _dp], C.c_int),
     "hc_plugin_eval": ([C.c_int, C.POINTER(ColumnParams), C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp],

@@ -53,6 +53,16 @@ unknown keys, only membership of the 12 is checked):
   ``enkf_rejected`` ``[R]``, ``enkf_loglik``, ``enkf_sigma_cm`` and ``enkf_localisation_cm`` (a sweep: a leading ``[P]``
   axis), and the run ends with `` [Ensemble xN] EnKF log-likelihood = ... over R rows`` (a sweep: the best point).  A
   single-point ensemble on several GPUs is refused (the covariances would need a sum over ranks).
+* ``"EnKF": {..., "Soil_Moisture": {"Filename": "sm.csv", "Depths_cm": [30, 60, 120], "Sigma": 0.02}}``: a soil-moisture
+  record joins the well in the EnKF's analyses (include/hydrocol.h hc_set_enkf_soil_moisture).  The CSV is header-less
+  ``ID, Datenum, VWC_1, ..., VWC_m`` (as the forcing), one row per forcing row with the same ``Datenum``; an empty field or
+  NaN is no observation, values lie in [0, 1].  A depth maps to the first node with ``z >= depth`` (the well's rule,
+  src/simulation.py:255) and must lie in [z[0], z[D-1]]; at most 8 depths; ``Sigma`` (m^3/m^3, finite and > 0) is one
+  number or one per depth.  Added to ``<Output_Name>_ensemble.h5``: ``enkf_sm_depths_cm``, ``enkf_sm_nodes``,
+  ``enkf_sm_sigma`` ``[m]`` and, over the ``enkf_rows`` ``[R]``, ``enkf_sm_observed``, ``enkf_sm_obs``,
+  ``enkf_sm_prior_mean``, ``enkf_sm_prior_std``, ``enkf_sm_post_mean``, ``enkf_sm_post_std`` ``[R][m]`` (NaN on rows with
+  no sensor value; a sweep: a leading ``[P]`` axis), and the run ends with
+  `` [Ensemble xN] soil-moisture forecast RMSE = ... over R rows`` (the prior mean theta against the record).
 * ``"Ensemble": {"repair_predict": true}`` with ``Simulation_Flags.PREDICT``: run the repaired predictive lateral flow
    instead of raising the reference's ``TypeError``.
 """
@@ -113,6 +123,7 @@ def main(params_file=None, data_file=None, seed=None, device=0, gpus=None, _sett
         if params.get("Ensemble"):
             filter_settings(params["Ensemble"], n_gpus)     # so does a bad Filter block
             enkf_settings(params["Ensemble"], n_gpus)       # and a bad EnKF block
+            soil_moisture_settings(params["Ensemble"], n_gpus)
         ranks = multigpu.Ranks(expect=n_gpus if (n_gpus > 1 or multigpu.in_rank()) else None)
         if ranks.world > 1:
             device = ranks.device_index()
@@ -171,8 +182,10 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     dist_stride, dist_levels = distribution_settings(ens)
     filt = filter_settings(ens, ranks.world)
     enkf = enkf_settings(ens, ranks.world)
+    sm = soil_moisture_settings(ens, ranks.world)
     cols = ColumnTables(params, load_site_well(params))
     forcing = ForcingDigest(params, water_data, cols)
+    record = soil_moisture_record_of(sm, cols, water_data)      # before any GPU call
     if cols.flags["PREDICT"] and not ens.get("repair_predict"):
         raise TypeError("'numpy.float64' object cannot be interpreted as an integer")     # richards_pde.py:327-330
     n_members = int(ens.get("Members", 4096))
@@ -180,7 +193,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     rows = min(days * 48, forcing.dim_t - 1)
     if ens.get("Points"):
         return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels, filt,
-                          enkf)
+                          enkf, record)
     lo, hi = multigpu.shard(n_members, ranks.rank, ranks.world)
     if hi <= lo:
         raise ValueError(f" Ensemble: {n_members} members do not shard over {ranks.world} GPUs (a rank would be empty).")
@@ -188,7 +201,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     sim = EnsembleSimulation(cols, forcing, hi - lo, seed=int(ens.get("Seed", 0)), device=device, member_offset=lo,
                              noise=str(ens.get("Noise", "philox")).lower(),
                              spinup=str(ens.get("Spinup", "shared")).lower(), profile_stride=stride,
-                             wtd_hist_stride=dist_stride, **_filter_kwargs(filt), **_enkf_kwargs(enkf))
+                             wtd_hist_stride=dist_stride, **_filter_kwargs(filt), **_enkf_kwargs(enkf, record))
     label = f"Ensemble x{n_members}"
     _step_all(sim, rows, label, ranks)
     # the run's one collective: int64 (count, sum idx, sum idx^2) per row, exact and order-independent
@@ -220,6 +233,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     etables, enkf_line = _reduce_enkf(ranks, sim, [0], 1, forcing.dim_t, enkf, label, keep_points=False,
                                          z0_cm=cols.z[0])
     extra.update(etables)
+    stables, sm_line = _reduce_enkf_sm(ranks, sim, [0], 1, forcing.dim_t, enkf, record, label, keep_points=False)
+    extra.update(stables)
     arrays = dict(moments=moments, wtd_mean_cm=mean_cm, wtd_std_cm=std_cm, rows=np.array(rows),
                   members=np.array(n_members), gpus=np.array(ranks.world), initial_cond=psi0, **extra)
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "ensemble water-table statistics", ranks)
@@ -229,6 +244,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
         print(filter_line)
     if enkf_line:
         print(enkf_line)
+    if sm_line:
+        print(sm_line)
     sim.close()
 
 
@@ -303,7 +320,7 @@ def filter_settings(ens, n_gpus=1):
     return stride, float(sigma), (None if seed is None else int(seed))
 
 
-ENKF_KEYS = ("Stride", "Sigma_cm", "Localisation_cm", "Seed")
+ENKF_KEYS = ("Stride", "Sigma_cm", "Localisation_cm", "Seed", "Soil_Moisture")
 
 
 def enkf_settings(ens, n_gpus=1):
@@ -347,9 +364,153 @@ def enkf_settings(ens, n_gpus=1):
     return stride, float(sigma), float(loc), (None if seed is None else int(seed))
 
 
-def _enkf_kwargs(enkf):
+def _enkf_kwargs(enkf, record=None):
     stride, sigma, loc, seed = enkf
-    return dict(enkf_stride=stride, enkf_sigma_cm=sigma, enkf_localisation_cm=loc, enkf_seed=seed) if stride else {}
+    if not stride:
+        return {}
+    kw = dict(enkf_stride=stride, enkf_sigma_cm=sigma, enkf_localisation_cm=loc, enkf_seed=seed)
+    if record is not None:
+        kw["enkf_soil_moisture"] = record
+    return kw
+
+
+SM_KEYS = ("Filename", "Depths_cm", "Sigma")
+SM_MAX_DEPTHS = 8
+
+
+def soil_moisture_settings(ens, n_gpus=1):
+    """Ensemble.EnKF.Soil_Moisture -> (filename, depths_cm tuple, sigma tuple per depth), or None when absent.  Pure, like
+    :func:`enkf_settings` (which it runs first: its refusals -- a "Filter" block, one point on several GPUs -- hold): a
+    bad value is a ValueError (message + exit status 1).  Needs an active EnKF.  The depths are checked against the column
+    and the file is read later (:func:`soil_moisture_record_of`)."""
+    import math
+    from numbers import Real
+    if "Soil_Moisture" in ens:
+        raise ValueError(" Ensemble: Soil_Moisture belongs inside the \"EnKF\" block.")
+    block = ens.get("EnKF")
+    if not isinstance(block, dict) or block.get("Soil_Moisture") is None:
+        enkf_settings(ens, n_gpus)
+        return None
+    stride = enkf_settings(ens, n_gpus)[0]
+    sm = block["Soil_Moisture"]
+    if not stride:
+        raise ValueError(" Ensemble: EnKF.Soil_Moisture needs an active EnKF (EnKF.Stride > 0).")
+    if not isinstance(sm, dict):
+        raise ValueError(f" Ensemble: EnKF.Soil_Moisture = {sm!r} must be an object such as "
+                         f"{{\"Filename\": \"sm.csv\", \"Depths_cm\": [30, 60], \"Sigma\": 0.02}}.")
+    unknown = sorted(set(sm) - set(SM_KEYS))
+    if unknown:
+        raise ValueError(f" Ensemble: EnKF.Soil_Moisture has unknown keys {unknown} (known: {list(SM_KEYS)}).")
+    name = sm.get("Filename")
+    if not isinstance(name, str) or not name:
+        raise ValueError(f" Ensemble: EnKF.Soil_Moisture.Filename = {name!r} must name the sensor CSV.")
+
+    def number(x):
+        return not isinstance(x, bool) and isinstance(x, Real) and math.isfinite(x)
+
+    depths = sm.get("Depths_cm")
+    if not isinstance(depths, (list, tuple)) or not depths or not all(number(d) for d in depths):
+        raise ValueError(f" Ensemble: EnKF.Soil_Moisture.Depths_cm = {depths!r} must be a non-empty list of finite "
+                         f"depths (cm).")
+    if len(depths) > SM_MAX_DEPTHS:
+        raise ValueError(f" Ensemble: EnKF.Soil_Moisture.Depths_cm has {len(depths)} depths, at most {SM_MAX_DEPTHS}.")
+    if "Sigma" not in sm:
+        raise ValueError(" Ensemble: EnKF.Soil_Moisture.Sigma (the sensors' error, m^3/m^3) is required.")
+    sigma = sm["Sigma"]
+    sig = list(sigma) if isinstance(sigma, (list, tuple)) else [sigma] * len(depths)
+    if len(sig) != len(depths) or not all(number(x) and x > 0 for x in sig):
+        raise ValueError(f" Ensemble: EnKF.Soil_Moisture.Sigma = {sigma!r} must be a finite number > 0 or one per depth "
+                         f"({len(depths)}).")
+    return name, tuple(float(d) for d in depths), tuple(float(x) for x in sig)
+
+
+def read_soil_moisture_csv(path, datenum, n_depths):
+    """The header-less sensor CSV ``ID, Datenum, VWC_1, ..., VWC_m`` -> values [T][m] (NaN = none).  It must have one row
+    per forcing row with the forcing's ``Datenum`` (within 1e-6 day) and m value columns in [0, 1] (or empty / NaN)."""
+    import numpy as np
+    datenum = np.asarray(datenum, dtype=np.float64)
+    rows = []
+    with open(path, "r") as fh:
+        for k, line in enumerate(fh):
+            if not line.strip():
+                continue
+            fields = [f.strip() for f in line.rstrip("\r\n").split(",")]
+            if len(fields) != 2 + n_depths:
+                raise ValueError(f" Soil moisture: {path} row {k + 1} has {len(fields)} fields, expected "
+                                 f"{2 + n_depths} (ID, Datenum and {n_depths} values).")
+            try:
+                rows.append([float(f) if f else float("nan") for f in fields[1:]])
+            except ValueError:
+                raise ValueError(f" Soil moisture: {path} row {k + 1} holds a field that is not a number.") from None
+    table = np.array(rows, dtype=np.float64).reshape(-1, 1 + n_depths)
+    if table.shape[0] != datenum.size:
+        raise ValueError(f" Soil moisture: {path} has {table.shape[0]} rows, the forcing {datenum.size}.")
+    bad = np.flatnonzero(~(np.abs(table[:, 0] - datenum) <= 1e-6))
+    if bad.size:
+        raise ValueError(f" Soil moisture: {path} row {int(bad[0]) + 1} has Datenum {float(table[bad[0], 0])!r}, the forcing "
+                         f"{float(datenum[bad[0]])!r}.")
+    values = table[:, 1:]
+    out = ~np.isnan(values) & ~((values >= 0.0) & (values <= 1.0))
+    if out.any():
+        r, c = np.argwhere(out)[0]
+        raise ValueError(f" Soil moisture: {path} row {int(r) + 1} value {int(c) + 1} = {float(values[r, c])!r} lies outside [0, 1].")
+    return values
+
+
+def soil_moisture_record_of(sm, cols, water_data):
+    """The EnKF's sensor record (stepper.soil_moisture_record) of the settings ``sm`` on the column ``cols``: the depths
+    mapped to nodes (refused outside the column) and the CSV read against the forcing's Datenum.  None without sensors."""
+    from .stepper import sensor_nodes, soil_moisture_record
+    if sm is None:
+        return None
+    name, depths, sigma = sm
+    try:
+        sensor_nodes(cols.z, depths)
+    except ValueError as bad:
+        raise ValueError(f" Ensemble: EnKF.Soil_Moisture.Depths_cm: {bad}.") from None
+    if not Path(name).exists():
+        raise ValueError(f" Soil moisture: the sensor file {name} does not exist.")
+    values = read_soil_moisture_csv(name, water_data["Datenum"].to_numpy(), len(depths))
+    return soil_moisture_record(cols.z, depths, values, sigma)
+
+
+SM_DATASETS = ("observed", "obs", "prior_mean", "prior_std", "post_mean", "post_std")
+
+
+def _reduce_enkf_sm(ranks, sim, ids, P, T, enkf, record, label, keep_points):
+    """The sensors' datasets from this rank's handle over the EnKF's analysed rows (its ``enkf_rows``), the [P] table
+    placed and summed over the ranks like the EnKF's (float64 as int64 bits), and the closing line (rank 0)."""
+    import numpy as np
+    from .multigpu import place_points
+    from .stepper import ENKF_WIDTH, SM_WIDTH, enkf_sm_summary, stride_rows
+    stride = enkf[0]
+    if not stride or record is None:
+        return {}, None
+    n = int(np.asarray(record["nodes"]).size)
+    n_arow = stride_rows(T, stride)
+    local = sim.enkf_sm_table().reshape(-1, n_arow, n, SM_WIDTH) if sim is not None else np.zeros((0, n_arow, n, SM_WIDTH))
+    table = place_points(local, ids, P, ranks)
+    etab = sim.enkf_table().reshape(-1, n_arow, ENKF_WIDTH) if sim is not None else np.zeros((0, n_arow, ENKF_WIDTH))
+    used = place_points(etab, ids, P, ranks)[..., 0] > 0
+    slots = np.flatnonzero(used.any(axis=0))               # the enkf_rows of _reduce_enkf
+    sel = table[:, slots] if keep_points else table[0, slots]
+    out = {"enkf_sm_depths_cm": np.asarray(record["depths_cm"], dtype=np.float64),
+           "enkf_sm_nodes": np.asarray(record["nodes"], dtype=np.int32),
+           "enkf_sm_sigma": np.asarray(record["sigma"], dtype=np.float64)}
+    for j, k in enumerate(SM_DATASETS):
+        v = sel[..., j]
+        out[f"enkf_sm_{k}"] = (v == 1.0).astype(np.int8) if k == "observed" else v
+    summary = enkf_sm_summary(table if keep_points else table[0], stride, record["sigma"])
+    if ranks.rank != 0:
+        return out, None
+    rows = int(summary["rows"].size)
+    if keep_points:
+        r = np.asarray(summary["rmse_all"], dtype=np.float64)
+        best = int(np.nanargmin(r)) if np.isfinite(r).any() else 0
+        line = f" [{label}] soil-moisture forecast RMSE: best point {best} = {r[best]:.5f} over {rows} rows"
+    else:
+        line = f" [{label}] soil-moisture forecast RMSE = {float(summary['rmse_all']):.5f} over {rows} rows"
+    return out, line
 
 
 def _reduce_enkf(ranks, sim, ids, P, T, enkf, label, keep_points, z0_cm):
@@ -504,7 +665,7 @@ def _reduce_optional(ranks, sim, ids, cols_all, forcing, stride, dist_stride, di
 
 
 def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride=0, dist_levels=None,
-               filt=(0, None, None), enkf=(0, None, None, None)):
+               filt=(0, None, None), enkf=(0, None, None, None), record=None):
     """Parameter points x members: this rank's points in one handle (ensemble.SweepSimulation), the whole table assembled
     over the ranks (multigpu.assemble_points)."""
     import numpy as np
@@ -531,7 +692,7 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     if mine:
         sim = SweepSimulation(points, forcing, n_members, seed=int(ens.get("Seed", 0)), device=device, point_ids=mine,
                               profile_stride=stride, wtd_hist_stride=dist_stride, **_filter_kwargs(filt),
-                              **_enkf_kwargs(enkf))
+                              **_enkf_kwargs(enkf, record))
         _step_all(sim, rows, label, ranks)
         table = sim.moments()
         for j, k in enumerate(mine):
@@ -550,6 +711,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     etables, enkf_line = _reduce_enkf(ranks, sim, mine, P, T, enkf, label, keep_points=True,
                                          z0_cm=cols_all[0].z[0])
     arrays.update(etables)
+    stables, sm_line = _reduce_enkf_sm(ranks, sim, mine, P, T, enkf, record, label, keep_points=True)
+    arrays.update(stables)
     if sim is not None:
         sim.close()
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "sweep's water-table statistics", ranks)
@@ -559,6 +722,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
         print(filter_line)
     if enkf_line:
         print(enkf_line)
+    if sm_line:
+        print(sm_line)
 
 
 def run_cli(argv=None):
@@ -581,6 +746,7 @@ def run_cli(argv=None):
             try:                                    # a bad Filter or EnKF block ends the command before any rank starts
                 filter_settings(settings["Ensemble"], n_gpus)
                 enkf_settings(settings["Ensemble"], n_gpus)
+                soil_moisture_settings(settings["Ensemble"], n_gpus)
             except ValueError as bad:
                 print(bad)
                 sys.exit(1)

@@ -186,6 +186,17 @@ struct hc_handle {
     AccTable<double> enkf{"entries"};
     DevBuf<double> enkf_y, enkf_eps, enkf_ypost, enkf_ys, enkf_mean, enkf_gain, enkf_part;
     DevBuf<int> enkf_rej;
+    // soil-moisture sensors in the EnKF analysis (hc_set_enkf_soil_moisture): the record on the host (nodes, sigma,
+    // values [sm_rows][sm_n], NaN = none); diagnostics float64 [P][n_arow][sm_n][6] keyed like the EnKF's; per member the
+    // observations Y [N][m'], the posterior (y, theta..., rejected) and the sensors' eps [N][sm_n]; per point the raw sums
+    // of both passes and the gain [P][D][m'] (the last analysis: test hooks, sm_width = its m', 0 = no sensor on it)
+    int sm_n = 0;                // 0: no record
+    int64_t sm_rows = 0;
+    std::vector<int> sm_nodes;
+    std::vector<double> sm_sigma, sm_values;
+    int sm_width = 0;
+    AccTable<double> sm{"entries"};
+    DevBuf<double> sm_Y, sm_Ypost, sm_eps, sm_gain, sm_s1, sm_s2, sm_part;
     int n_cu = 256;
     double jac_reject = NUM_JAC_DIFF_REJECT;
 };
@@ -812,6 +823,21 @@ constexpr int ENKF_WIDTH = 8;                          // diagnostics per point 
 // eps_k: one standard normal of Philox4x32-10 under the EnKF seed at counter (0xFFFFFFFE, row, gid_lo, gid_hi), with
 // the Box-Muller step of philox_normal (its cosine branch).  A noise counter's first word is a depth index / 2 and the
 // particle filter's draw has 0xFFFFFFFF: the three never meet.
+// enkf_normal_at: the same step at counter (word0, row, gid_lo, gid_hi) -- the soil-moisture sensors' 0xFFFFFFF0 + i.
+__device__ __forceinline__ double enkf_normal_at(uint32_t word0, unsigned long long seed, unsigned long long gid,
+                                                 unsigned row)
+{
+#pragma clang fp contract(off)
+    uint32_t r[4];
+    philox4x32_10(word0, row, (uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    const uint64_t a = ((uint64_t)r[1] << 32) | r[0], b = ((uint64_t)r[3] << 32) | r[2];
+    const double u1 = ((double)(a >> 11) + 0.5) * (1.0 / 9007199254740992.0);
+    const double u2 = ((double)(b >> 11) + 0.5) * (1.0 / 9007199254740992.0);
+    double s, c;
+    sincospi(2.0 * u2, &s, &c);
+    return sqrt(-2.0 * log(u1)) * c;
+}
+
 __device__ __forceinline__ double enkf_normal(unsigned long long seed, unsigned long long gid, unsigned row)
 {
 #pragma clang fp contract(off)
@@ -1026,6 +1052,333 @@ __global__ __launch_bounds__(256) void enkf_update_kernel(double *psi, const dou
             y_post[m] = enkf_y_of(b, lo, hi, psat, dz);
             rej[m] = keep ? 0 : 1;
         }
+    }
+}
+
+// ---- soil-moisture sensors in the EnKF analysis (hc_set_enkf_soil_moisture, include/hydrocol.h)
+// A row with at least one sensor value runs a batch analysis of m' = 1 + m_s observations per member: the well's y, then
+// the theta of the present sensors at their nodes.  The sums follow the scalar path's rule -- tiles of ENKF_TILE members in
+// member order, the tile partials by ENKF_THREADS threads in tile-strided order and a fixed tree -- for every column at
+// once; the small m' x m' system is factorised by one thread per point.  Contraction is off throughout (but inside the
+// cell model, which keeps the code generation of model_nodes_kernel).
+constexpr int SM_MAX = 8;                              // sensors in a record
+constexpr int SM_OBS = SM_MAX + 1;                     // observations per member: the well, then the sensors present
+constexpr int SM_WIDTH = 6;                            // sensor diagnostics per point, slot and sensor
+
+// the sensors that have a value on one analysis row, in record order (a kernel argument)
+struct SmRow {
+    int m;                     // present sensors m_s (m' = m_s + 1)
+    int n;                     // sensors in the record
+    int sensor[SM_MAX];        // record index of present sensor k
+    int node[SM_MAX];
+    double obs[SM_MAX];
+    double sigma[SM_MAX];
+};
+
+// theta of one cell as model_nodes_kernel computes it (theta has no noise term)
+__device__ __forceinline__ double sm_theta(const ColumnDev &P, const double *nt, int D, int j, double psi, int special)
+{
+    const double por = nt[j], meank = nt[D + j], noisec = nt[2 * D + j];
+    const double mk = meank == 0.0 ? 1.0e-7 : meank;
+    double th, K, C, kb, pf;
+    if (special)
+        model_cell<true>(P, psi, por, 1.0 / (por - P.theta_res), log(mk), 1.0 / (mk * mk), noisec, 0.0, th, K, C, kb, pf);
+    else
+        model_cell<false>(P, psi, por, 1.0 / (por - P.theta_res), log(mk), 1.0 / (mk * mk), noisec, 0.0, th, K, C, kb, pf);
+    return th;
+}
+
+// Y[m][1 + k] = theta of member m at the node of present sensor k, Y[m][0] = y_m (enkf_obs_kernel's; y == NULL: left
+// alone), rows of `width` entries: the forecast's Y (width m') and the posterior's (y, theta..., rejected)
+__global__ void sm_obs_kernel(const double *psi, const double *y, const ColumnDev *P, const double *node_tabs,
+                              int special, long long n_members, long long mpp, int D, const SmRow s, double *Y, int width)
+{
+    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n_members) return;
+    const long long p = m / mpp;
+    const double *nt = node_tabs + (size_t)p * 3 * D;
+    if (y) Y[(size_t)m * width] = y[m];
+    for (int k = 0; k < s.m; k++)
+        Y[(size_t)m * width + 1 + k] = sm_theta(P[p], nt, D, s.node[k], psi[(size_t)m * D + s.node[k]], special);
+}
+
+// Column sums of X = (psi_0 .. psi_{Dc-1}, Y_0 .. Y_{W-1}) (Dc = 0: Y alone), C = Dc + W columns, tile t of point p:
+//   sums == NULL: partial[p][t][j] = sum over the tile in member order of X_j;
+//   otherwise:    partial[p][t][j][i] = sum of (X_j - xbar_j)(Y_i - ybar_i), the means = sums[p][.] / N_p.
+// Thread j owns column j: every member's psi row is one coalesced read of the block.
+__global__ __launch_bounds__(HC_MAX_DEPTH_NODES + WAVE) void sm_partial_kernel(const double *psi, const double *Y, int W,
+                                                                               const double *sums, long long mpp, int Dc,
+                                                                               long long n_tiles, double *partial)
+{
+#pragma clang fp contract(off)
+    const long long p = blockIdx.y, t = blockIdx.x;
+    const int j = threadIdx.x, C = Dc + W;
+    if (j >= C) return;
+    const long long m0 = p * mpp + t * ENKF_TILE;
+    const long long m1 = p * mpp + ((t + 1) * ENKF_TILE < mpp ? (t + 1) * ENKF_TILE : mpp);
+    const double *x = j < Dc ? psi + j : Y + (j - Dc);
+    const long long xs = j < Dc ? Dc : W;
+    if (!sums) {
+        double s = 0.0;
+#pragma unroll 8
+        for (long long m = m0; m < m1; m++) s += x[(size_t)m * xs];
+        partial[((size_t)p * n_tiles + t) * C + j] = s;
+        return;
+    }
+    const double *S = sums + (size_t)p * C;
+    const double xb = S[j] / (double)mpp;
+    double yb[SM_OBS + 1], acc[SM_OBS + 1];
+#pragma unroll
+    for (int i = 0; i < SM_OBS + 1; i++) {
+        yb[i] = i < W ? S[Dc + i] / (double)mpp : 0.0;
+        acc[i] = 0.0;
+    }
+    for (long long m = m0; m < m1; m++) {
+        const double a = x[(size_t)m * xs] - xb;
+        const double *ym = Y + (size_t)m * W;
+#pragma unroll
+        for (int i = 0; i < SM_OBS + 1; i++)
+            if (i < W) acc[i] += a * (ym[i] - yb[i]);
+    }
+    double *out = partial + (((size_t)p * n_tiles + t) * C + j) * W;
+#pragma unroll
+    for (int i = 0; i < SM_OBS + 1; i++)
+        if (i < W) out[i] = acc[i];
+}
+
+// sums[p][c] = the tile partials of column c summed (thread t: tiles t, t + ENKF_THREADS, ... in order, then a fixed tree)
+__global__ __launch_bounds__(ENKF_THREADS) void sm_finish_kernel(const double *partial, long long n_tiles, int n_cols,
+                                                                 double *sums)
+{
+#pragma clang fp contract(off)
+    __shared__ double sh[ENKF_THREADS];
+    const long long p = blockIdx.y;
+    const int c = blockIdx.x;
+    double part = 0.0;
+    for (long long t = threadIdx.x; t < n_tiles; t += ENKF_THREADS) part += partial[((size_t)p * n_tiles + t) * n_cols + c];
+    const double s = enkf_block_sum(part, sh);
+    if (threadIdx.x == 0) sums[(size_t)p * n_cols + c] = s;
+}
+
+// L L^T = A (n x n, row-major, lower triangle read), in a fixed order; false when a pivot is not finite and > 0
+__device__ bool sm_cholesky(const double *A, int n, double *L)
+{
+#pragma clang fp contract(off)
+    for (int j = 0; j < n; j++) {
+        double d = A[j * SM_OBS + j];
+        for (int k = 0; k < j; k++) d -= L[j * SM_OBS + k] * L[j * SM_OBS + k];
+        if (!(d > 0.0) || !isfinite(d)) return false;
+        const double ljj = sqrt(d);
+        L[j * SM_OBS + j] = ljj;
+        for (int i = j + 1; i < n; i++) {
+            double v = A[i * SM_OBS + j];
+            for (int k = 0; k < j; k++) v -= L[i * SM_OBS + k] * L[j * SM_OBS + k];
+            L[i * SM_OBS + j] = v / ljj;
+        }
+    }
+    return true;
+}
+
+// One block per point, thread d = node d.  Thread 0: ybar, C_YY, the tapered S = rho o C_YY + R and its Cholesky factor;
+// the untapered C_YY + R for the joint log-density; the prior diagnostics (EnKF entries 0-4, the sensors' first four).
+// Then thread d: K_d = (rho_d o c_d) S^-1 by a forward and a backward substitution; K_d0 also goes to the scalar gain.
+__global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void sm_gain_kernel(const double *s1, const double *s2, long long mpp,
+                                                                     int D, const SmRow s, double sigma, double loc,
+                                                                     double z_obs, double dz, double *gain,
+                                                                     double *gain_well, double *stats, double *sm_stats,
+                                                                     long long n_arow, long long slot)
+{
+#pragma clang fp contract(off)
+    // the working sets live in LDS (dynamically indexed: in registers they would go to scratch)
+    __shared__ double Ls[SM_OBS * SM_OBS], Lu[SM_OBS * SM_OBS], A[SM_OBS * SM_OBS], cyy[SM_OBS * SM_OBS];
+    __shared__ double zeta[SM_OBS], yb[SM_OBS], r2[SM_OBS], dl[SM_OBS], w[SM_OBS];
+    __shared__ double U[HC_MAX_DEPTH_NODES][SM_OBS];   // thread d's substitutions
+    __shared__ int ok;
+    const long long p = blockIdx.x;
+    const int W = s.m + 1, C = D + W;
+    const double *S1 = s1 + (size_t)p * C, *S2 = s2 + (size_t)p * C * W;
+    const double n1 = mpp > 1 ? (double)(mpp - 1) : 0.0;
+    if (threadIdx.x == 0) {
+        for (int i = 0; i < W; i++) {
+            yb[i] = S1[D + i] / (double)mpp;
+            r2[i] = i == 0 ? sigma * sigma : s.sigma[i - 1] * s.sigma[i - 1];
+            dl[i] = (i == 0 ? z_obs : s.obs[i - 1]) - yb[i];
+            zeta[i] = i == 0 ? yb[0] : (double)s.node[i - 1] * dz;
+        }
+        for (int i = 0; i < W; i++)
+            for (int k = 0; k < W; k++) cyy[i * SM_OBS + k] = mpp > 1 ? S2[(size_t)(D + i) * W + k] / n1 : 0.0;
+        for (int i = 0; i < W; i++)
+            for (int k = 0; k < W; k++) {
+                const double rho = loc > 0.0 ? gaspari_cohn(fabs(zeta[i] - zeta[k]) / loc) : 1.0;
+                A[i * SM_OBS + k] = rho * cyy[i * SM_OBS + k] + (i == k ? r2[i] : 0.0);
+            }
+        ok = sm_cholesky(A, W, Ls) ? 1 : 0;
+        // log N(obs; ybar, C_YY + R) = -0.5 (m' log 2 pi + log det + |L^-1 (obs - ybar)|^2)
+        for (int i = 0; i < W; i++)
+            for (int k = 0; k < W; k++) A[i * SM_OBS + k] = cyy[i * SM_OBS + k] + (i == k ? r2[i] : 0.0);
+        double ll = __builtin_nan("");
+        if (sm_cholesky(A, W, Lu)) {
+            double logdet = 0.0, q = 0.0;
+            for (int i = 0; i < W; i++) {
+                double v = dl[i];
+                for (int k = 0; k < i; k++) v -= Lu[i * SM_OBS + k] * w[k];
+                w[i] = v / Lu[i * SM_OBS + i];
+                logdet += log(Lu[i * SM_OBS + i]);
+                q += w[i] * w[i];
+            }
+            ll = -0.5 * ((double)W * log(2.0 * M_PI) + 2.0 * logdet + q);
+        }
+        double *st = stats + ((size_t)p * n_arow + slot) * ENKF_WIDTH;
+        st[0] = (double)mpp;
+        st[1] = yb[0];
+        st[2] = sqrt(cyy[0]);
+        st[3] = dl[0];
+        st[4] = ll;
+        double *ss = sm_stats + ((size_t)p * n_arow + slot) * s.n * SM_WIDTH;
+        for (int i = 0; i < s.n; i++) ss[i * SM_WIDTH] = 0.0;      // observed: 0 unless present (the rest stays NaN)
+        for (int k = 0; k < s.m; k++) {
+            double *e = ss + s.sensor[k] * SM_WIDTH;
+            e[0] = 1.0;
+            e[1] = s.obs[k];
+            e[2] = yb[k + 1];
+            e[3] = sqrt(cyy[(k + 1) * SM_OBS + k + 1]);
+        }
+    }
+    __syncthreads();
+    const int d = threadIdx.x;
+    if (d >= D) return;
+    double *K = gain + ((size_t)p * D + d) * W;
+    if (!ok) {
+        for (int i = 0; i < W; i++) K[i] = __builtin_nan("");
+        gain_well[(size_t)p * D + d] = __builtin_nan("");
+        return;
+    }
+    double *u = U[d];
+    for (int i = 0; i < W; i++) {
+        const double rho = loc > 0.0 ? gaspari_cohn(fabs((double)d * dz - zeta[i]) / loc) : 1.0;
+        double v = rho * (mpp > 1 ? S2[(size_t)d * W + i] / n1 : 0.0);
+        for (int k = 0; k < i; k++) v -= Ls[i * SM_OBS + k] * u[k];
+        u[i] = v / Ls[i * SM_OBS + i];
+    }
+    for (int i = W - 1; i >= 0; i--) {
+        double v = u[i];
+        for (int k = i + 1; k < W; k++) v -= Ls[k * SM_OBS + i] * u[k];
+        u[i] = v / Ls[i * SM_OBS + i];
+    }
+    for (int i = 0; i < W; i++) K[i] = u[i];
+    gain_well[(size_t)p * D + d] = u[0];
+}
+
+// One wave per member: the well's eps (enkf_normal) and the sensors' (lane i < n: counter word 0xFFFFFFF0 + i), the
+// innovations o_k - Y_k, psi_dk + sum_i K_di (o_ki - Y_ki) (i in order) on every node, stored only when every entry is
+// finite (as enkf_update_kernel); then the find_wtd index and the posterior y of the column it kept: Ypost[m] = (y, ...,
+// rejected) (sm_obs_kernel fills in the posterior theta).
+__global__ __launch_bounds__(256) void sm_update_kernel(double *psi, const double *Y, const double *gain,
+                                                        const ColumnDev *P, long long n_members, long long mpp, int D, double dz,
+                                                        double z_obs, double sigma, const SmRow s,
+                                                        unsigned long long seed, const long long *point_base,
+                                                        long long member_offset, unsigned row, double *eps_out,
+                                                        double *sm_eps, double *Ypost)
+{
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x % WAVE;
+    const int W = s.m + 1;
+    const long long waves = (long long)gridDim.x * (blockDim.x / WAVE);
+    for (long long m = (long long)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE; m < n_members; m += waves) {
+        const long long p = m / mpp;
+        const unsigned long long gid = point_base ? (unsigned long long)(point_base[p] + m % mpp)
+                                                  : (unsigned long long)(member_offset + m);
+        const double eps = enkf_normal(seed, gid, row);
+        const double e_mine = lane < s.n ? enkf_normal_at(0xFFFFFFF0u + (unsigned)lane, seed, gid, row) : 0.0;
+        // lane i holds innovation i: the well's on lane 0, present sensor k's on lane 1 + k
+        const double *Ym = Y + (size_t)m * W;
+        double my_dl = lane == 0 ? (z_obs + sigma * eps) - Ym[0] : 0.0;
+        for (int k = 0; k < s.m; k++) {
+            const double e = __shfl(e_mine, s.sensor[k]);
+            if (lane == 1 + k) my_dl = (s.obs[k] + s.sigma[k] * e) - Ym[1 + k];
+        }
+        const double *K = gain + (size_t)p * D * W;
+        double *col = psi + (size_t)m * D;
+        double v[ENKF_SLOTS], a[ENKF_SLOTS];
+#pragma unroll
+        for (int c = 0; c < ENKF_SLOTS; c++) {
+            const int d = c * WAVE + lane;
+            v[c] = d < D ? col[d] : 0.0;
+            a[c] = 0.0;
+        }
+#pragma unroll 1
+        for (int i = 0; i < W; i++) {                // the increments K_d . (o - Y), summed in i order
+            const double di = __shfl(my_dl, i);
+#pragma unroll
+            for (int c = 0; c < ENKF_SLOTS; c++) {
+                const int d = c * WAVE + lane;
+                const double t = d < D ? K[(size_t)d * W + i] * di : 0.0;
+                a[c] = i == 0 ? t : a[c] + t;
+            }
+        }
+        bool ok = true;
+#pragma unroll
+        for (int c = 0; c < ENKF_SLOTS; c++) {
+            const int d = c * WAVE + lane;
+            a[c] = d < D ? v[c] + a[c] : 0.0;
+            ok = ok && isfinite(a[c]);
+        }
+        const bool keep = __all(ok);
+        if (keep) {
+#pragma unroll
+            for (int c = 0; c < ENKF_SLOTS; c++) {
+                const int d = c * WAVE + lane;
+                if (d < D) col[d] = a[c];
+                v[c] = a[c];
+            }
+        }
+        const double psat = P[p].psi_sat;
+        int deepest = -1;
+#pragma unroll
+        for (int c = 0; c < ENKF_SLOTS; c++) {
+            const int d = c * WAVE + lane;
+            const unsigned long long u = __ballot(d < D && !(v[c] >= psat));
+            if (u) deepest = c * WAVE + 63 - __clzll((long long)u);
+        }
+        const int b = deepest < 0 ? 0 : (deepest + 1 < D - 1 ? deepest + 1 : D - 1);
+        const int bl = b >= 1 ? b - 1 : 0;
+        double hi = 0.0, lo = 0.0;
+#pragma unroll
+        for (int c = 0; c < ENKF_SLOTS; c++) {
+            const double x = __shfl(v[c], b % WAVE), xl = __shfl(v[c], bl % WAVE);
+            if (c == b / WAVE) hi = x;
+            if (c == bl / WAVE) lo = xl;
+        }
+        double *out = Ypost + (size_t)m * (W + 1);
+        if (lane < s.n) sm_eps[(size_t)m * s.n + lane] = e_mine;
+        if (lane == 0) {
+            eps_out[m] = eps;
+            out[0] = enkf_y_of(b, lo, hi, psat, dz);
+            out[W] = keep ? 0.0 : 1.0;
+        }
+    }
+}
+
+// One thread per point: the posterior diagnostics from the raw sums of Ypost (s1 [P][W + 1], s2 [P][W + 1][W + 1]): the
+// EnKF's entries 5-7 and the sensors' posterior mean and std.
+__global__ void sm_post_kernel(const double *s1, const double *s2, long long n_points, long long mpp, const SmRow s,
+                               double *stats, double *sm_stats, long long n_arow, long long slot)
+{
+#pragma clang fp contract(off)
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_points) return;
+    const int V = s.m + 2;
+    const double *S1 = s1 + (size_t)p * V, *S2 = s2 + (size_t)p * V * V;
+    const double n1 = (double)(mpp - 1);
+    double *st = stats + ((size_t)p * n_arow + slot) * ENKF_WIDTH;
+    st[5] = S1[0] / (double)mpp;
+    st[6] = sqrt(mpp > 1 ? S2[0] / n1 : 0.0);
+    st[7] = S1[V - 1];
+    double *ss = sm_stats + ((size_t)p * n_arow + slot) * s.n * SM_WIDTH;
+    for (int k = 0; k < s.m; k++) {
+        double *e = ss + s.sensor[k] * SM_WIDTH;
+        e[4] = S1[k + 1] / (double)mpp;
+        e[5] = sqrt(mpp > 1 ? S2[(size_t)(k + 1) * V + k + 1] / n1 : 0.0);
     }
 }
 
@@ -1364,6 +1717,38 @@ int ensure_enkf(hc_handle *h)
     return HC_OK;
 }
 
+// the sensor diagnostics (hc_set_enkf_soil_moisture): [P][n_arow][n][6] float64, created as NaN
+int ensure_sm(hc_handle *h)
+{
+    if (h->sm_n <= 0) return fail(HC_ERR_ARG, "no soil-moisture record (hc_set_enkf_soil_moisture)");
+    if (int rc = ensure_enkf(h)) return rc;
+    if (h->sm_rows != h->n_rows)
+        return fail(HC_ERR_ARG, "the soil-moisture record has %lld rows, the forcing %lld: set the record again",
+                    (long long)h->sm_rows, (long long)h->n_rows);
+    AccTable<double> &t = h->sm;
+    const bool fresh = !(t.key[0] == h->n_points && t.key[1] == h->n_rows && t.key[2] == h->enkf_stride);
+    const int64_t n = (int64_t)h->n_points * enkf_rows(h) * h->sm_n * SM_WIDTH;
+    if (int rc = t.ensure(h->n_points, h->n_rows, h->enkf_stride, n)) return rc;
+    if (fresh) {
+        hipLaunchKernelGGL(fill_d, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, t.buf.p,
+                           __builtin_nan(""), (size_t)n);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    return HC_OK;
+}
+
+void sm_off(hc_handle *h)
+{
+    h->sm_n = 0;
+    h->sm_rows = 0;
+    h->sm_width = 0;
+    h->sm_nodes.clear(); h->sm_sigma.clear(); h->sm_values.clear();
+    h->sm.release();
+    h->sm_Y.release(); h->sm_Ypost.release(); h->sm_eps.release(); h->sm_gain.release();
+    h->sm_s1.release(); h->sm_s2.release(); h->sm_part.release();
+}
+
 void enkf_off(hc_handle *h)
 {
     h->enkf_stride = 0;
@@ -1371,6 +1756,7 @@ void enkf_off(hc_handle *h)
     h->enkf.release();
     h->enkf_y.release(); h->enkf_eps.release(); h->enkf_ypost.release(); h->enkf_ys.release();
     h->enkf_mean.release(); h->enkf_gain.release(); h->enkf_part.release(); h->enkf_rej.release();
+    sm_off(h);
 }
 
 // what turns both filters off: new points, members or noise source (include/hydrocol.h hc_set_filter, hc_set_enkf)
@@ -2265,6 +2651,7 @@ int enkf_analyse(hc_handle *h, const Chunk &c)
 {
     const int64_t N = h->n_members, D = h->p.dim_d, P = h->n_points, mpp = N / P;
     const int64_t row = c.row0 + c.rows - 1, slot = row / h->enkf_stride, n_arow = enkf_rows(h);
+    h->sm_width = 0;
     const int64_t n_tiles = (mpp + ENKF_TILE - 1) / ENKF_TILE;
     if (h->enkf_y.ensure((size_t)N) || h->enkf_eps.ensure((size_t)N) || h->enkf_ypost.ensure((size_t)N) ||
         h->enkf_rej.ensure((size_t)N) || h->enkf_ys.ensure((size_t)(2 * P)) || h->enkf_mean.ensure((size_t)(P * D)) ||
@@ -2305,6 +2692,101 @@ int enkf_analyse(hc_handle *h, const Chunk &c)
                        h->enkf_rej.p, (long long)mpp, h->enkf_ys.p, st, (long long)n_arow, (long long)slot);
     HIP_TRY(hipGetLastError());
     h->enkf_done = true;
+    return HC_OK;
+}
+
+// The sensors with a value on `row`, in record order
+SmRow sm_row(const hc_handle *h, int64_t row)
+{
+    SmRow s{};
+    s.n = h->sm_n;
+    for (int i = 0; i < h->sm_n; i++) {
+        const double v = h->sm_values[(size_t)row * h->sm_n + i];
+        if (std::isnan(v)) continue;
+        s.sensor[s.m] = i;
+        s.node[s.m] = h->sm_nodes[(size_t)i];
+        s.obs[s.m] = v;
+        s.sigma[s.m] = h->sm_sigma[(size_t)i];
+        s.m++;
+    }
+    return s;
+}
+
+// The batch analysis of a row with sensor values (m' = 1 + s.m observations per member), in place on psi: y and theta
+// per member; per point the column and observation sums, then the anomaly products (two passes over psi); the gain and
+// the prior diagnostics; the update with eps and the posterior (y, theta, rejected) per member (one read + write of psi);
+// the posterior sums and diagnostics.
+int enkf_analyse_sm(hc_handle *h, const Chunk &c, const SmRow &s)
+{
+    const int64_t N = h->n_members, D = h->p.dim_d, P = h->n_points, mpp = N / P;
+    const int64_t row = c.row0 + c.rows - 1, slot = row / h->enkf_stride, n_arow = enkf_rows(h);
+    const int64_t n_tiles = (mpp + ENKF_TILE - 1) / ENKF_TILE;
+    const int W = s.m + 1, V = W + 1;
+    const int64_t C = D + W;
+    if (h->enkf_y.ensure((size_t)N) || h->enkf_eps.ensure((size_t)N) || h->enkf_gain.ensure((size_t)(P * D)) ||
+        h->sm_Y.ensure((size_t)(N * SM_OBS)) || h->sm_Ypost.ensure((size_t)(N * (SM_OBS + 1))) ||
+        h->sm_eps.ensure((size_t)(N * SM_MAX)) || h->sm_gain.ensure((size_t)(P * D * SM_OBS)) ||
+        h->sm_s1.ensure((size_t)(P * (HC_MAX_DEPTH_NODES + SM_OBS))) ||
+        h->sm_s2.ensure((size_t)(P * (HC_MAX_DEPTH_NODES + SM_OBS) * SM_OBS)) ||
+        h->sm_part.ensure((size_t)(P * n_tiles * (HC_MAX_DEPTH_NODES + SM_OBS) * SM_OBS)))
+        return HC_ERR_DEVICE;
+    const unsigned short *w = h->wtd_u16.p + (size_t)(c.rows - 1) * N;
+    const double dz = h->p.dz, z_obs = (double)h->h_wtd_obs[(size_t)row] * dz;
+    const int special = (int)h->use_special();
+    const long long ll_mpp = (long long)mpp, ll_tiles = (long long)n_tiles;
+    hipLaunchKernelGGL(enkf_obs_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, w, h->psi.p, h->Pdev.p,
+                       (long long)N, ll_mpp, (int)D, dz, h->enkf_y.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(sm_obs_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, h->psi.p, h->enkf_y.p,
+                       h->Pdev.p, h->node_tabs.p, special, (long long)N, ll_mpp, (int)D, s, h->sm_Y.p, W);
+    HIP_TRY(hipGetLastError());
+    // prior: the sums of (psi, Y), then the products of their anomalies with Y's
+    const dim3 tiles((unsigned)n_tiles, (unsigned)P);
+    const dim3 cols_prior((unsigned)((C + WAVE - 1) / WAVE * WAVE)), cols_post((unsigned)WAVE);
+    hipLaunchKernelGGL(sm_partial_kernel, tiles, cols_prior, 0, h->stream, h->psi.p, h->sm_Y.p, W, nullptr, ll_mpp,
+                       (int)D, ll_tiles, h->sm_part.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(sm_finish_kernel, dim3((unsigned)C, (unsigned)P), dim3(ENKF_THREADS), 0, h->stream, h->sm_part.p,
+                       ll_tiles, (int)C, h->sm_s1.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(sm_partial_kernel, tiles, cols_prior, 0, h->stream, h->psi.p, h->sm_Y.p, W, h->sm_s1.p, ll_mpp,
+                       (int)D, ll_tiles, h->sm_part.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(sm_finish_kernel, dim3((unsigned)(C * W), (unsigned)P), dim3(ENKF_THREADS), 0, h->stream,
+                       h->sm_part.p, ll_tiles, (int)(C * W), h->sm_s2.p);
+    HIP_TRY(hipGetLastError());
+    double *st = h->enkf.buf.p, *sst = h->sm.buf.p;
+    hipLaunchKernelGGL(sm_gain_kernel, dim3((unsigned)P), dim3((unsigned)((D + WAVE - 1) / WAVE * WAVE)), 0, h->stream,
+                       h->sm_s1.p, h->sm_s2.p, ll_mpp, (int)D, s, h->enkf_sigma, h->enkf_loc, z_obs, dz, h->sm_gain.p,
+                       h->enkf_gain.p, st, sst, (long long)n_arow, (long long)slot);
+    HIP_TRY(hipGetLastError());
+    const unsigned blocks = (unsigned)std::min<int64_t>((N + 3) / 4, (int64_t)h->n_cu * 8);
+    hipLaunchKernelGGL(sm_update_kernel, dim3(blocks), dim3(256), 0, h->stream, h->psi.p, h->sm_Y.p, h->sm_gain.p,
+                       h->Pdev.p, (long long)N, ll_mpp, (int)D, dz, z_obs, h->enkf_sigma, s,
+                       (unsigned long long)h->enkf_seed, P > 1 ? h->point_base.p : nullptr, (long long)h->member_offset,
+                       (unsigned)row, h->enkf_eps.p, h->sm_eps.p, h->sm_Ypost.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(sm_obs_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, h->psi.p, nullptr,
+                       h->Pdev.p, h->node_tabs.p, special, (long long)N, ll_mpp, (int)D, s, h->sm_Ypost.p, V);
+    HIP_TRY(hipGetLastError());
+    // posterior: the same two passes over (y, theta, rejected) alone
+    hipLaunchKernelGGL(sm_partial_kernel, tiles, cols_post, 0, h->stream, nullptr, h->sm_Ypost.p, V, nullptr, ll_mpp, 0,
+                       ll_tiles, h->sm_part.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(sm_finish_kernel, dim3((unsigned)V, (unsigned)P), dim3(ENKF_THREADS), 0, h->stream, h->sm_part.p,
+                       ll_tiles, V, h->sm_s1.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(sm_partial_kernel, tiles, cols_post, 0, h->stream, nullptr, h->sm_Ypost.p, V, h->sm_s1.p, ll_mpp,
+                       0, ll_tiles, h->sm_part.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(sm_finish_kernel, dim3((unsigned)(V * V), (unsigned)P), dim3(ENKF_THREADS), 0, h->stream,
+                       h->sm_part.p, ll_tiles, V * V, h->sm_s2.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(sm_post_kernel, dim3((unsigned)((P + 63) / 64)), dim3(64), 0, h->stream, h->sm_s1.p, h->sm_s2.p,
+                       (long long)P, ll_mpp, s, st, sst, (long long)n_arow, (long long)slot);
+    HIP_TRY(hipGetLastError());
+    h->enkf_done = true;
+    h->sm_width = W;
     return HC_OK;
 }
 
@@ -2355,6 +2837,7 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
     if (filt_on && (rc = ensure_filter(h))) return rc;
     const bool enkf_on = h->enkf_stride > 0 && !a->spinup;   // (the EnKF: spin-up solves are never analysed either)
     if (enkf_on && (rc = ensure_enkf(h))) return rc;
+    if (enkf_on && h->sm_n > 0 && (rc = ensure_sm(h))) return rc;
     int64_t fresh_consumed = 0;
     for (int64_t done = 0; done < a->n_rows;) {
         const Chunk c = plan_chunk(h, a, done, prof_on);
@@ -2364,7 +2847,10 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
         if ((rc = accumulate(h, A, a, c, prof_on, hist_on))) return rc;
         if ((rc = copy_outputs(h, a, c, done))) return rc;
         if (filt_on && is_assimilation_row(h, c.row0 + c.rows - 1) && (rc = assimilate(h, c))) return rc;
-        if (enkf_on && is_assimilation_row(h, c.row0 + c.rows - 1) && (rc = enkf_analyse(h, c))) return rc;
+        if (enkf_on && is_assimilation_row(h, c.row0 + c.rows - 1)) {
+            const SmRow s = h->sm_n > 0 ? sm_row(h, c.row0 + c.rows - 1) : SmRow{};
+            if ((rc = s.m > 0 ? enkf_analyse_sm(h, c, s) : enkf_analyse(h, c))) return rc;
+        }
         HIP_TRY(hipStreamSynchronize(h->stream));
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
@@ -2799,6 +3285,90 @@ int hc_get_enkf_y(hc_handle *h, double *y)
 int hc_get_enkf_eps(hc_handle *h, double *eps)
 {
     return enkf_hook(h, h ? h->enkf_eps.p : nullptr, eps, h ? (size_t)h->n_members : 0, "hc_get_enkf_eps");
+}
+
+int hc_set_enkf_soil_moisture(hc_handle *h, int32_t n_sensors, const int32_t *nodes, const double *values,
+                              const double *sigma)
+{
+    if (!h || n_sensors < 0) return fail(HC_ERR_ARG, "hc_set_enkf_soil_moisture: bad argument");
+    if (n_sensors > SM_MAX)
+        return fail(HC_ERR_ARG, "hc_set_enkf_soil_moisture: %d sensors, at most %d", (int)n_sensors, SM_MAX);
+    if (n_sensors > 0 && h->filt_stride > 0)
+        return fail(HC_ERR_ARG, "hc_set_enkf_soil_moisture: the particle filter is on");
+    if (n_sensors > 0 && h->enkf_stride <= 0)
+        return fail(HC_ERR_ARG, "hc_set_enkf_soil_moisture: the EnKF is off (hc_set_enkf comes first)");
+    if (n_sensors > 0 && (!nodes || !values || !sigma)) return fail(HC_ERR_ARG, "hc_set_enkf_soil_moisture: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    sm_off(h);
+    if (n_sensors == 0) return HC_OK;
+    const int D = h->p.dim_d;
+    for (int i = 0; i < n_sensors; i++) {
+        if (nodes[i] < 0 || nodes[i] >= D)
+            return fail(HC_ERR_ARG, "hc_set_enkf_soil_moisture: node %d of sensor %d outside [0, %d)", (int)nodes[i], i, D);
+        if (!(std::isfinite(sigma[i]) && sigma[i] > 0.0))
+            return fail(HC_ERR_ARG, "hc_set_enkf_soil_moisture: sigma %g of sensor %d must be finite and > 0", sigma[i], i);
+    }
+    const size_t n = (size_t)h->n_rows * n_sensors;
+    for (size_t k = 0; k < n; k++)
+        if (!std::isnan(values[k]) && !(values[k] >= 0.0 && values[k] <= 1.0))
+            return fail(HC_ERR_ARG, "hc_set_enkf_soil_moisture: value %g (row %lld, sensor %d) outside [0, 1]", values[k],
+                        (long long)(k / n_sensors), (int)(k % n_sensors));
+    h->sm_nodes.assign(nodes, nodes + n_sensors);
+    h->sm_sigma.assign(sigma, sigma + n_sensors);
+    h->sm_values.assign(values, values + n);
+    h->sm_rows = h->n_rows;
+    h->sm_n = n_sensors;
+    const int rc = ensure_sm(h);
+    if (rc != HC_OK) sm_off(h);                  // refused: off
+    return rc;
+}
+
+int hc_get_enkf_sm_stats(hc_handle *h, double *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_get_enkf_sm_stats: bad argument");
+    return table_copy(h, h->sm, ensure_sm, hipMemcpyDeviceToHost, table, n_entries, "hc_get_enkf_sm_stats");
+}
+
+int hc_set_enkf_sm_stats(hc_handle *h, const double *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_set_enkf_sm_stats: bad argument");
+    return table_copy(h, h->sm, ensure_sm, hipMemcpyHostToDevice, const_cast<double *>(table), n_entries,
+                      "hc_set_enkf_sm_stats");
+}
+
+int hc_get_enkf_sm_width(hc_handle *h, int32_t *width)
+{
+    if (!h || !width) return fail(HC_ERR_ARG, "hc_get_enkf_sm_width: bad argument");
+    *width = h->sm_n > 0 ? h->sm_width : 0;
+    return HC_OK;
+}
+
+// the last analysis's buffers when it had sensor values (test hooks)
+static int sm_hook(hc_handle *h, const double *src, double *out, size_t count, const char *who)
+{
+    if (!h || !out) return fail(HC_ERR_ARG, "%s: bad argument", who);
+    if (h->sm_n <= 0 || h->sm_width <= 0) return fail(HC_ERR_ARG, "%s: the last analysis had no sensor value", who);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(out, src, count * 8, hipMemcpyDeviceToHost));
+    return HC_OK;
+}
+
+int hc_get_enkf_sm_y(hc_handle *h, double *y)
+{
+    return sm_hook(h, h ? h->sm_Y.p : nullptr, y, h ? (size_t)h->n_members * h->sm_width : 0, "hc_get_enkf_sm_y");
+}
+
+int hc_get_enkf_sm_gain(hc_handle *h, double *gain)
+{
+    return sm_hook(h, h ? h->sm_gain.p : nullptr, gain, h ? (size_t)h->n_points * h->p.dim_d * h->sm_width : 0,
+                   "hc_get_enkf_sm_gain");
+}
+
+int hc_get_enkf_sm_eps(hc_handle *h, double *eps)
+{
+    return sm_hook(h, h ? h->sm_eps.p : nullptr, eps, h ? (size_t)h->n_members * h->sm_n : 0, "hc_get_enkf_sm_eps");
 }
 
 // The path's one collective without torch: a single process that drives several devices (one handle each) sums the

@@ -9,7 +9,8 @@ all-reduce of the per-row water-table moments (see :func:`allreduce_moments`).
 import numpy as np
 
 from .digest import inverse_retention
-from .stepper import ENKF_WIDTH, EnsembleStepper, enkf_summary, filter_summary, moments_to_mean_std, wtd_distribution
+from .stepper import (ENKF_WIDTH, SM_WIDTH, EnsembleStepper, enkf_sm_summary, enkf_summary, filter_summary,
+                      moments_to_mean_std, wtd_distribution)
 
 
 def pressure_head(cols, theta):
@@ -102,12 +103,16 @@ class _Run:
     enkf_stride > 0: a stochastic ensemble Kalman filter on the well's continuous water table instead (``enkf_sigma_cm``:
     the observation error; ``enkf_localisation_cm``: the Gaspari-Cohn half-width, 0 = none; ``enkf_seed``: default the
     run's seed), with the same forecast / analysis order; :meth:`enkf_summary` (log marginal likelihood).
+    enkf_soil_moisture: a soil-moisture record (stepper.soil_moisture_record: ``nodes``, ``values`` [T][n], ``sigma``,
+    ``depths_cm``) that joins the well in the EnKF's analyses; :meth:`enkf_sm_table`, the ``sm_*`` keys of
+    :meth:`enkf_summary`.
     ``_lead`` is the leading shape of the per-point tables: () for an ensemble, (P,) for a sweep."""
 
     _lead = ()
 
     def _start_tables(self, profile_stride, wtd_hist_stride, filter_stride=0, filter_sigma_cm=None, filter_seed=None,
-                      enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None):
+                      enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None,
+                      enkf_soil_moisture=None):
         self.profile_stride = int(profile_stride)
         if self.profile_stride:
             self.stepper.set_profile_stats(self.profile_stride)
@@ -126,6 +131,12 @@ class _Run:
         self.enkf_seed = (self.seed if enkf_seed is None else int(enkf_seed)) if self.enkf_stride else None
         if self.enkf_stride:
             self.stepper.set_enkf(self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed)
+        self.enkf_soil_moisture = enkf_soil_moisture if self.enkf_stride else None
+        if enkf_soil_moisture is not None and not self.enkf_stride:
+            raise ValueError("enkf_soil_moisture needs the EnKF (enkf_stride > 0)")
+        if self.enkf_soil_moisture is not None:
+            sm = self.enkf_soil_moisture
+            self.stepper.set_enkf_soil_moisture(sm["nodes"], sm["values"], sm["sigma"])
 
     def advance(self, n_rows, **kw):
         """Solve the next ``n_rows`` forcing rows for every member."""
@@ -175,13 +186,26 @@ class _Run:
         """[n_arow][8] float64 (include/hydrocol.h hc_set_enkf; depths from the top node); a sweep: [P][n_arow][8]."""
         return self.stepper.enkf_table().reshape(self._lead + (-1, ENKF_WIDTH))
 
-    def enkf_summary(self, table=None):
+    def enkf_summary(self, table=None, sm_table=None):
         """The EnKF's record (stepper.enkf_summary, means at the well's depths): ``rows``, ``count``, ``prior_mean_cm``,
         ``prior_std_cm``, ``innovation_cm``, ``loglik_rows``, ``post_mean_cm``, ``post_std_cm``, ``rejected`` over the
         analysed rows and ``loglik``, the log marginal likelihood of the well record (log cm^-1), with a leading [P] for a
         sweep; ``table``: e.g. the one assembled over ranks."""
         t = self.enkf_table() if table is None else table
-        return enkf_summary(t, self.enkf_stride, self.enkf_sigma_cm, float(self.cols.z[0]))
+        out = enkf_summary(t, self.enkf_stride, self.enkf_sigma_cm, float(self.cols.z[0]))
+        if self.enkf_soil_moisture is not None:
+            out.update(("sm_" + k, v) for k, v in self.enkf_sm_summary(sm_table).items())
+        return out
+
+    def enkf_sm_table(self):
+        """[n_arow][n][6] float64 (include/hydrocol.h hc_set_enkf_soil_moisture); a sweep: [P][n_arow][n][6]."""
+        return self.stepper.enkf_sm_table().reshape(self._lead + (-1, self.stepper.enkf_sm_n, SM_WIDTH))
+
+    def enkf_sm_summary(self, table=None):
+        """stepper.enkf_sm_summary of the sensor table (``table``: e.g. the one assembled over ranks): per sensor the
+        forecast RMSE of the mean against the record (``rmse``) and the mean innovation, over the joint analyses."""
+        t = self.enkf_sm_table() if table is None else table
+        return enkf_sm_summary(t, self.enkf_stride, self.enkf_soil_moisture["sigma"])
 
     def close(self):
         self.stepper.close()
@@ -202,10 +226,10 @@ class EnsembleSimulation(_Run):
     def __init__(self, cols, forcing, n_members, seed=0, device=0, member_offset=0, psi0=None, flags=None,
                  noise="philox", spinup="shared", profile_stride=0, wtd_hist_stride=0, filter_stride=0,
                  filter_sigma_cm=None, filter_seed=None, enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0,
-                 enkf_seed=None):
+                 enkf_seed=None, enkf_soil_moisture=None):
         self._start(cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup)
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
-                           enkf_sigma_cm, enkf_localisation_cm, enkf_seed)
+                           enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture)
 
     def _start(self, cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup):
         if noise not in ("philox", "numpy") or spinup not in ("shared", "member"):
@@ -315,6 +339,9 @@ class EnsembleSimulation(_Run):
             arrays["enkf_localisation_cm"] = np.array(self.enkf_localisation_cm, dtype=np.float64)
             arrays["enkf_seed"] = np.array(self.enkf_seed, dtype=np.uint64)
             arrays["enkf_table"] = self.stepper.enkf_table()
+            if self.enkf_soil_moisture is not None:       # the record itself is supplied again at restore
+                arrays["enkf_sm_nodes"] = np.asarray(self.enkf_soil_moisture["nodes"], dtype=np.int32)
+                arrays["enkf_sm_table"] = self.stepper.enkf_sm_table()
         path = Path(path)
         if hdf5io.available() and path.suffix != ".npz":
             hdf5io.write(path, arrays)
@@ -324,8 +351,9 @@ class EnsembleSimulation(_Run):
         return path
 
     @classmethod
-    def restore(cls, path, cols, forcing, device=0, flags=None):
-        """A new ensemble (new handle) continuing the one ``dump`` wrote: same members, same streams, same row."""
+    def restore(cls, path, cols, forcing, device=0, flags=None, enkf_soil_moisture=None):
+        """A new ensemble (new handle) continuing the one ``dump`` wrote: same members, same streams, same row.  A run with
+        a soil-moisture record needs it again (``enkf_soil_moisture``, like the forcing); its sensor table is restored."""
         from pathlib import Path
         from . import hdf5io
         path = Path(path)
@@ -347,6 +375,15 @@ class EnsembleSimulation(_Run):
         if enkf:
             fkw.update(enkf_stride=enkf, enkf_sigma_cm=float(data["enkf_sigma_cm"]),
                        enkf_localisation_cm=float(data["enkf_localisation_cm"]), enkf_seed=int(data["enkf_seed"]))
+        has_sm = enkf and "enkf_sm_table" in data
+        if has_sm != (enkf_soil_moisture is not None):
+            raise ValueError(f" EnsembleSimulation: {path} was written {'with' if has_sm else 'without'} a soil-moisture "
+                             f"record: pass {'the same record' if has_sm else 'none'} as enkf_soil_moisture.")
+        if has_sm and not np.array_equal(np.asarray(data["enkf_sm_nodes"]).reshape(-1),
+                                          np.asarray(enkf_soil_moisture["nodes"]).reshape(-1)):
+            raise ValueError(f" EnsembleSimulation: {path} has sensors at other nodes than enkf_soil_moisture.")
+        if has_sm:
+            fkw.update(enkf_soil_moisture=enkf_soil_moisture)
         sim = cls(cols, forcing, n, seed=int(data["seed"]), device=device, member_offset=int(data["member_offset"]),
                   psi0=np.asarray(data["initial_cond"], dtype=float).reshape(-1)[:D], flags=flags, profile_stride=stride,
                   wtd_hist_stride=hist_stride, **fkw)
@@ -358,6 +395,8 @@ class EnsembleSimulation(_Run):
             sim.stepper.set_noise_scale(np.asarray(data["noise_scale"], dtype=float).reshape(n))
         if enkf:
             sim.stepper.set_enkf_table(np.asarray(data["enkf_table"], dtype=np.float64))
+        if has_sm:
+            sim.stepper.set_enkf_sm_table(np.asarray(data["enkf_sm_table"], dtype=np.float64))
         sim.stepper.set_moments(np.asarray(data["moments"], dtype=np.int64))
         if stride:
             sim.stepper.set_profile_table(np.asarray(data["profile_table"], dtype=np.int64))
@@ -455,7 +494,8 @@ class SweepSimulation(_Run):
 
     def __init__(self, cols_list, forcing, n_members, seed=0, device=0, first_point=0, flags=None, psi0=None,
                  point_ids=None, profile_stride=0, wtd_hist_stride=0, filter_stride=0, filter_sigma_cm=None,
-                 filter_seed=None, enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None):
+                 filter_seed=None, enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None,
+                 enkf_soil_moisture=None):
         self.points = list(cols_list)
         self.P, self.n = len(self.points), int(n_members)
         self._lead = (self.P,)
@@ -483,7 +523,7 @@ class SweepSimulation(_Run):
         if self.P > 1:
             self.stepper.set_point_member_bases(self.bases)
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
-                           enkf_sigma_cm, enkf_localisation_cm, enkf_seed)
+                           enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture)
         self.next_row, self.kernel_ms, self.launches = 1, 0.0, 0
 
     def _spinup(self, flags):

@@ -78,6 +78,7 @@ class EnsembleStepper:
         self.wtd_hist_stride = 0
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = 0, 0.0, 0
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
+        self.enkf_sm_nodes = None
         if profile_stride:
             self.set_profile_stats(profile_stride)
 
@@ -335,6 +336,7 @@ class EnsembleStepper:
         """The library turned the filters off (a new noise source or new point keys, include/hydrocol.h): so does this side."""
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = 0, 0.0, 0
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
+        self.enkf_sm_nodes = None
 
     def filter_table(self):
         """[P][n_arow][4] float64: count, ESS, log-likelihood increment, survivors per assimilation slot (slot j <-> row
@@ -395,6 +397,7 @@ class EnsembleStepper:
         if stride and self.filter_stride:
             raise ValueError("the particle filter is on: the EnKF and the filter exclude each other")
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
+        self.enkf_sm_nodes = None                             # hc_set_enkf removes the sensor record
         L.check(self.lib.hc_set_enkf(self.h, stride, sigma, loc, int(seed) & 0xFFFFFFFFFFFFFFFF))
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = stride, sigma, loc, int(seed)
 
@@ -426,6 +429,64 @@ class EnsembleStepper:
         """[N] the observation perturbations eps_k of the last analysis (test hook)."""
         out = np.zeros(self.N)
         L.check(self.lib.hc_get_enkf_eps(self.h, L.dptr(out)))
+        return out
+
+    # -- soil-moisture sensors in the EnKF analysis (include/hydrocol.h hc_set_enkf_soil_moisture) ----------------------
+    def set_enkf_soil_moisture(self, nodes, values=None, sigma=None):
+        """Add a record of volumetric water content at the depth nodes ``nodes`` (at most 8) to the EnKF's analyses:
+        ``values`` [T][n] in [0, 1], NaN = no observation on that row; ``sigma`` the sensors' error (m^3/m^3), one number
+        or one per sensor.  ``nodes`` empty or None removes the record.  The EnKF must be on (:meth:`set_enkf` first; it
+        removes the record again)."""
+        nodes = np.ascontiguousarray([] if nodes is None else nodes, dtype=np.int32).reshape(-1)
+        n = int(nodes.size)
+        self.enkf_sm_nodes = None
+        if n == 0:
+            L.check(self.lib.hc_set_enkf_soil_moisture(self.h, 0, None, None, None))
+            return
+        v = L.as_f64(values).reshape(self.T, n) if np.size(values) == self.T * n else None
+        if v is None:
+            raise ValueError(f"soil-moisture values must hold [{self.T}][{n}] entries, got {np.shape(values)}")
+        sg = L.as_f64(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (n,)).copy())
+        L.check(self.lib.hc_set_enkf_soil_moisture(self.h, n, L.iptr(nodes), L.dptr(v), L.dptr(sg)))
+        self.enkf_sm_nodes = nodes.copy()
+
+    @property
+    def enkf_sm_n(self):
+        return 0 if self.enkf_sm_nodes is None else int(self.enkf_sm_nodes.size)
+
+    def enkf_sm_table(self):
+        """[P][n_arow][n][6] float64 per analysis slot and sensor: observed (0/1), observation, prior mean and std of
+        theta, posterior mean and std of theta; NaN where the slot took no joint analysis (and after observed = 0)."""
+        t = np.zeros((self.P, stride_rows(self.T, self.enkf_stride), self.enkf_sm_n, SM_WIDTH))
+        L.check(self.lib.hc_get_enkf_sm_stats(self.h, L.dptr(t), t.size))
+        return t
+
+    def set_enkf_sm_table(self, table):
+        t = L.as_f64(table).reshape(-1)
+        L.check(self.lib.hc_set_enkf_sm_stats(self.h, L.dptr(t), t.size))
+
+    def enkf_sm_width(self):
+        """m' = 1 + the sensors present on the last analysis (0: it had none; test hook)."""
+        w = np.zeros(1, dtype=np.int32)
+        L.check(self.lib.hc_get_enkf_sm_width(self.h, L.iptr(w)))
+        return int(w[0])
+
+    def enkf_sm_y(self):
+        """[N][m'] the observations Y_k of the last analysis: the well's y (cm from the top node), then theta (test hook)."""
+        out = np.zeros((self.N, self.enkf_sm_width()))
+        L.check(self.lib.hc_get_enkf_sm_y(self.h, L.dptr(out)))
+        return out
+
+    def enkf_sm_gain(self):
+        """[P][D][m'] the gain K of the last analysis (test hook)."""
+        out = np.zeros((self.P, self.D, self.enkf_sm_width()))
+        L.check(self.lib.hc_get_enkf_sm_gain(self.h, L.dptr(out)))
+        return out
+
+    def enkf_sm_eps(self):
+        """[N][n] the sensors' observation perturbations of the last analysis, every sensor of the record (test hook)."""
+        out = np.zeros((self.N, self.enkf_sm_n))
+        L.check(self.lib.hc_get_enkf_sm_eps(self.h, L.dptr(out)))
         return out
 
     # -- hooks ----------------------------------------------------------------------
@@ -696,6 +757,58 @@ def enkf_summary(table, stride, sigma_cm, z0_cm=0.0):
             "loglik_rows": inc, "post_mean_cm": sel[..., 5] + z0_cm, "post_std_cm": sel[..., 6],
             "rejected": np.nan_to_num(sel[..., 7]).astype(np.int64), "loglik": loglik if loglik.ndim else float(loglik),
             "stride": int(stride), "sigma_cm": float(sigma_cm)}
+
+
+# ---- soil-moisture sensors in the EnKF (include/hydrocol.h hc_set_enkf_soil_moisture) ----------------------------------
+SM_WIDTH = 6
+SM_MAX_SENSORS = 8
+
+
+def sensor_nodes(z, depths_cm):
+    """The node of every sensor depth by the reference's rule for the well (src/simulation.py:255): the first z >= depth.
+    A depth outside [z[0], z[D-1]] is a ValueError."""
+    z = np.asarray(z, dtype=np.float64)
+    out = []
+    for d in depths_cm:
+        d = float(d)
+        if not (np.isfinite(d) and z[0] <= d <= z[-1]):
+            raise ValueError(f"sensor depth {d!r} cm lies outside the column [{float(z[0])!r}, {float(z[-1])!r}] cm")
+        out.append(int(np.flatnonzero(z >= d)[0]))
+    return np.array(out, dtype=np.int32)
+
+
+def soil_moisture_record(z, depths_cm, values, sigma):
+    """The ``enkf_soil_moisture=`` argument of EnsembleSimulation / SweepSimulation: ``depths_cm`` [n] (mapped to nodes
+    by :func:`sensor_nodes`), ``values`` [T][n] (NaN = none), ``sigma`` one number or [n]."""
+    depths = np.asarray(depths_cm, dtype=np.float64).reshape(-1)
+    sg = np.broadcast_to(np.asarray(sigma, dtype=np.float64), depths.shape).copy()
+    return {"depths_cm": depths, "nodes": sensor_nodes(z, depths), "sigma": sg,
+            "values": np.asarray(values, dtype=np.float64).reshape(-1, depths.size)}
+
+
+def enkf_sm_summary(table, stride, sigma):
+    """The sensors' record from the [..., n_arow, n, 6] table, over the slots that took a
+    joint analysis at any point: ``rows`` [R], ``observed`` [..., R, n] (bool), ``obs``, ``prior_mean``, ``prior_std``,
+    ``post_mean``, ``post_std`` [..., R, n]; per sensor [..., n]: ``rmse`` (forecast: the prior mean against the
+    observation over the rows it was observed; NaN if never), ``mean_innovation`` (observation - prior mean), ``n_obs``;
+    ``rmse_all`` [...] over every (row, sensor) observed."""
+    t = np.asarray(table, dtype=np.float64)
+    n = t.shape[-2]
+    used = np.isfinite(t[..., 0]).reshape(-1, t.shape[-3], n).any(axis=(0, 2)) if t.size else np.zeros(t.shape[-3], bool)
+    slots = np.flatnonzero(used)
+    sel = t[..., slots, :, :]
+    observed = sel[..., 0] == 1.0
+    innov = np.where(observed, sel[..., 1] - sel[..., 2], 0.0)
+    cnt = observed.sum(axis=-2)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rmse = np.sqrt((innov * innov).sum(axis=-2) / cnt)
+        mean_innov = innov.sum(axis=-2) / cnt
+        rmse_all = np.sqrt((innov * innov).sum(axis=(-2, -1)) / cnt.sum(axis=-1))
+    return {"rows": slots.astype(np.int64) * int(stride), "observed": observed, "obs": sel[..., 1],
+            "prior_mean": sel[..., 2], "prior_std": sel[..., 3], "post_mean": sel[..., 4], "post_std": sel[..., 5],
+            "rmse": rmse, "mean_innovation": mean_innov, "n_obs": cnt.astype(np.int64),
+            "rmse_all": rmse_all if np.ndim(rmse_all) else float(rmse_all), "stride": int(stride),
+            "sigma": np.asarray(sigma, dtype=np.float64)}
 
 
 def allreduce_handles(steppers):

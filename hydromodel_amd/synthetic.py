@@ -95,3 +95,35 @@ def default_parameters():
         "Simulation_Flags": {"SPINUP": False, "ET": True, "LF": True,
                              "HLIFT": False, "PREDICT": False},
     }
+
+
+def synthetic_soil_moisture(theta, sigma, seed=0, rows=None, n_rows=None):
+    """Sensor values for a twin experiment: ``theta`` [R][m] (a truth member's theta at the sensor nodes on the forcing
+    rows ``rows``, default 0 .. R-1) plus N(0, sigma^2) noise (``sigma``: one number or [m]) from
+    ``numpy.random.default_rng(seed)``, clipped to [0, 1]; a [n_rows][m] table (default R rows) that is NaN (no observation)
+    on every other row."""
+    theta = np.asarray(theta, dtype=np.float64)
+    R, m = theta.shape
+    rows = np.arange(R) if rows is None else np.asarray(rows, dtype=np.int64)
+    n_rows = R if n_rows is None else int(n_rows)
+    noise = np.random.default_rng(seed).standard_normal((R, m)) * np.broadcast_to(np.asarray(sigma, float), (m,))
+    out = np.full((n_rows, m), np.nan)
+    out[rows] = np.clip(theta + noise, 0.0, 1.0)
+    return out
+
+
+def write_soil_moisture_csv(path, values, datenum=None):
+    """Write the header-less sensor CSV ``ID, Datenum, VWC_1, ..., VWC_m`` of the EnKF's "Soil_Moisture" block: one row
+    per forcing row (``datenum``: default the synthetic forcing's, :func:`synthetic_forcing`), an empty field where
+    ``values`` [T][m] is NaN."""
+    values = np.asarray(values, dtype=np.float64)
+    if datenum is None:
+        datenum = DATENUM0 + np.arange(values.shape[0]) / float(ROWS_PER_DAY)
+    datenum = np.asarray(datenum, dtype=np.float64)
+    if datenum.size != values.shape[0]:
+        raise ValueError(f"{values.shape[0]} rows of values against {datenum.size} Datenum values")
+    with open(path, "w") as fh:
+        for i in range(values.shape[0]):
+            cells = ",".join("" if np.isnan(v) else repr(float(v)) for v in values[i])
+            fh.write(f"{i + 1:d},{float(datenum[i])!r},{cells}\n")
+    return Path(path)

@@ -44,6 +44,8 @@
  *                         and the log marginal likelihood of the well record per parameter point
  *   hc_set_enkf, hc_get/set_enkf_stats, hc_get_enkf_gain/y/eps
  *                      <- (new) the same conditioning by a stochastic ensemble Kalman filter on a continuous water table
+ *   hc_set_enkf_soil_moisture, hc_get/set_enkf_sm_stats, hc_get_enkf_sm_width/y/gain/eps
+ *                      <- (new) theta_vol (src/simulation.py:623) at sensor depths joins the well in the EnKF's analysis
  *
  * Conventions: every function returns 0 on success or a negative hc_status; nothing throws
  * or aborts across the boundary; hc_last_error() gives the thread-local message.  Host
@@ -413,6 +415,53 @@ int hc_set_enkf_stats(hc_handle *h, const double *table, int64_t n_entries);
 int hc_get_enkf_gain(hc_handle *h, double *gain);
 int hc_get_enkf_y(hc_handle *h, double *y);
 int hc_get_enkf_eps(hc_handle *h, double *eps);
+
+/* Soil-moisture sensors in the EnKF analysis: a record of volumetric water content at n_sensors (<= 8) nodes joins the
+ * well on the analysis rows of hc_set_enkf (the rows themselves do not change: r >= 1, r % stride == 0, wtd_obs[r] >= 0).
+ *   values [n_forcing_rows][n_sensors] (m^3/m^3, in [0, 1]; NaN = no observation), nodes [n_sensors] in [0, D), sigma
+ *   [n_sensors] the sensors' error standard deviations (finite, > 0).
+ *   A row with no sensor value runs the scalar analysis of hc_set_enkf unchanged (an all-NaN record: the well-only run to
+ *   the bit).  A row with m_s >= 1 sensor values runs one batch update per point of m' = 1 + m_s observations, in a fixed
+ *   order: the well, then the present sensors in record order.
+ *   Observations per member: Y_k = (y_k, theta_k[j_1], ...): y_k the water table of hc_set_enkf; theta_k[j] the cell model
+ *   at node j on the forecast psi (the bits of hc_model_nodes' theta; theta has no noise term).
+ *   Perturbed observations: o_k = (z[o] + sigma_cm eps_k, theta_obs,i + sigma_i eps_k,i); eps_k as for hc_set_enkf (counter
+ *   (0xFFFFFFFE, r, key)); sensor i of the RECORD draws at counter (0xFFFFFFF0 + i, r, key_lo, key_hi) under the EnKF seed
+ *   and the member's global id, through the same Box-Muller step, whether it is present on the row or not.  Noise
+ *   counters (first word a depth index / 2), the particle filter's (0xFFFFFFFF) and these never meet.
+ *   Per point p (N_p members), fp64 without contraction, two passes (means, then anomalies), /(N_p - 1) (N_p = 1: 0):
+ *     Ybar, C_YY (m' x m'), C_psiY (D x m');
+ *     taper (L = localisation_cm > 0; L = 0: rho = 1): rho_{d,i} = GC(|z_d - zeta_i| / L), rho_{i,i'} = GC(|zeta_i - zeta_i'|
+ *     / L), zeta = ybar for the well and z[j_i] for a sensor;
+ *     K = (rho o C_psiY)(rho o C_YY + R)^-1, R = diag(sigma_cm^2, sigma_i^2): a Cholesky factor of the m' x m' matrix in a
+ *     fixed order (one thread per point), then per node a forward and a backward substitution; a pivot that is not finite
+ *     and > 0 gives a NaN gain (every member then keeps its forecast and counts as rejected);
+ *     psi_k <- psi_k + K (o_k - Y_k), the m' terms summed in i order; a member whose updated column has a non-finite entry
+ *     keeps its forecast and is counted as rejected.
+ *   Reproducibility: every member sum runs in tiles of 256 members in member order, then the tile partials by 1024 threads
+ *   in tile-strided order and a fixed tree (the rule of hc_set_enkf, for every column), no floating-point atomics: the same
+ *   bits at any launch length, point order, dealing of a sweep's points to handles or ranks.
+ *   The EnKF's table on such a row: entries 0-3 and 5-7 keep their meaning (the well's y; the posterior from the analysis
+ *   states); entry 4 is the JOINT Gaussian log-density of the observed vector under N(Ybar, C_YY + R), untapered, in
+ *   log cm^-1 (m^3/m^3)^-m_s.
+ *   Sensor diagnostics, float64 [P][n_arow][n_sensors][6]: observed (0/1), observation, prior mean and std of theta, posterior
+ *   mean and std of theta (the analysis states, rejected members at their forecast).  A sensor without a value on an analysed
+ *   row: observed = 0, the rest NaN; every entry of a slot without a joint analysis (none, or the scalar path): NaN.
+ * hc_set_enkf_soil_moisture: n_sensors = 0 removes the record; otherwise (re)creates the table (NaN).  Needs the EnKF on
+ *   (hc_set_enkf first); HC_ERR_ARG while the particle filter is on.  Turned off by whatever turns the EnKF off (hc_set_enkf
+ *   included).  hc_step_rows refuses while the record's row count differs from the forcing's.
+ * hc_get/set_enkf_sm_stats: the sensor table (P n_arow n_sensors 6 entries; checkpoints, the assembly of a sweep over ranks).
+ * Test hooks of the last analysis, when it had sensor values: hc_get_enkf_sm_width (m', 0: the last analysis had none),
+ *   y [n_members][m'] (Y_k), gain [P][D][m'] (K), eps [n_members][n_sensors] (every sensor of the record).  On such a row
+ *   hc_get_enkf_y / eps hold the well's y_k and eps_k, hc_get_enkf_gain the well's column of K. */
+int hc_set_enkf_soil_moisture(hc_handle *h, int32_t n_sensors, const int32_t *nodes, const double *values,
+                              const double *sigma);
+int hc_get_enkf_sm_stats(hc_handle *h, double *table, int64_t n_entries);
+int hc_set_enkf_sm_stats(hc_handle *h, const double *table, int64_t n_entries);
+int hc_get_enkf_sm_width(hc_handle *h, int32_t *width);
+int hc_get_enkf_sm_y(hc_handle *h, double *y);
+int hc_get_enkf_sm_gain(hc_handle *h, double *gain);
+int hc_get_enkf_sm_eps(hc_handle *h, double *eps);
 
 /* The path's one collective inside the library, for a single process that drives several devices with
  * one handle each: every handle's moment table is replaced by the sum over all n handles (ncclAllReduce, ncclInt64,

@@ -1,0 +1,126 @@
+"""What soil-moisture sensors add to the ensemble Kalman filter (hc_set_enkf_soil_moisture): column-days/s of the
+bench-size ensemble without the EnKF, with the well-only EnKF, and with the well plus sensors every 48th row (one
+analysis a day), one handle each, back to back on one GPU.
+
+    python tools/enkf_sm_cost.py [--members 262144] [--depth 300] [--days 30] [--warmup 1] [--runs 0,48s,0,48s]
+                                 [--sensors 30,60,120] [--sigma 10] [--sm-sigma 0.02] [--localisation 0] [--json out.json]
+
+The set-up of tools/enkf_cost.py: synthetic 10-year forcing, Philox noise, the shared initial condition of the well's
+digest, W warm-up days, then K timed days, the library's own launch length; the timed figure is wall time around
+hc_step_rows.  A run is a stride (0: no EnKF, 48: the well alone) or a stride with the suffix "s" (the well and the
+sensors at --sensors cm, every sensor observed on every analysis row: theta of the initial profile at its node, held
+fixed -- the cost does not depend on the values).  `sm_ms_per_analysis` is a sensor run's `other_ms` over the plain
+runs', per analysis; `kept` is a run's rate over the mean of the stride-0 runs.  Under `rocprofv3 --kernel-trace --stats`
+run it with --runs 48s --days 1 --warmup 0 for the per-kernel time of the analyses.  Prints one JSON line.
+"""
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+REPO = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(REPO))
+
+
+def run(cols, forcing, psi0, members, stride, sigma, loc, warmup_days, days, spread_cm=0.0, seed=2024, sensors=None):
+    from hydromodel_amd.stepper import EnsembleStepper, enkf_sm_summary, enkf_summary
+    st = EnsembleStepper(cols, forcing, members)
+    try:
+        if spread_cm:
+            off = np.random.default_rng(seed).uniform(-spread_cm, spread_cm, size=members)
+            st.set_state(np.asarray(psi0)[None, :] + off[:, None])
+        else:
+            st.set_state(psi0)
+        st.set_noise_philox(seed, 0)
+        if stride:
+            st.set_enkf(stride, sigma, loc, seed)
+        if stride and sensors is not None:
+            st.set_enkf_soil_moisture(sensors["nodes"], sensors["values"], sensors["sigma"])
+        row = 1
+        if warmup_days:
+            st.step_rows(row, 48 * warmup_days)
+            row += 48 * warmup_days
+        st.lib.hc_synchronize(st.h)
+        t0 = time.perf_counter()
+        out = st.step_rows(row, 48 * days)
+        st.lib.hc_synchronize(st.h)
+        wall = time.perf_counter() - t0
+        rec = {"stride": stride, "sensors": 0 if sensors is None else len(sensors["nodes"]), "wall_s": wall, "step_kernel_ms": out["kernel_ms"], "launches": out["launches"],
+               "other_ms": 1e3 * wall - out["kernel_ms"], "column_days_per_s": members * days / wall}
+        if stride:
+            s = enkf_summary(st.enkf_table()[0], stride, sigma)
+            timed = s["rows"] >= row
+            rec["analyses"] = int(timed.sum())
+            rec["prior_std_cm_median"] = float(np.median(s["prior_std_cm"][timed])) if timed.any() else None
+            rec["post_std_cm_median"] = float(np.median(s["post_std_cm"][timed])) if timed.any() else None
+            rec["rejected"] = int(s["rejected"].sum())
+            rec["loglik"] = s["loglik"]
+            if sensors is not None:
+                sm = enkf_sm_summary(st.enkf_sm_table()[0], stride, sensors["sigma"])
+                rec["sm_forecast_rmse"] = sm["rmse"].tolist()
+                rec["sm_post_std_median"] = np.nanmedian(sm["post_std"], axis=0).tolist() if sm["rows"].size else None
+        return rec
+    finally:
+        st.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--members", type=int, default=262144)
+    ap.add_argument("--depth", type=int, default=300)
+    ap.add_argument("--days", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--years", type=int, default=10)
+    ap.add_argument("--runs", default="0,48s,0,48s")
+    ap.add_argument("--sensors", default="30,60,120")
+    ap.add_argument("--sm-sigma", type=float, default=0.02)
+    ap.add_argument("--sigma", type=float, default=10.0)
+    ap.add_argument("--localisation", type=float, default=0.0)
+    ap.add_argument("--spread-cm", type=float, default=0.0)
+    ap.add_argument("--json", default="")
+    args = ap.parse_args()
+    from hydromodel_amd.digest import ColumnTables, ForcingDigest
+    from hydromodel_amd.ensemble import pressure_head
+    from hydromodel_amd.synthetic import default_parameters, synthetic_forcing_frame, synthetic_well
+    params = default_parameters()
+    cols = ColumnTables(params, synthetic_well(args.depth))
+    forcing = ForcingDigest(params, synthetic_forcing_frame(args.years), cols)
+    fixture = REPO / "tests" / "golden" / f"g1_tables_{args.depth}.npz"
+    psi0 = np.load(fixture)["initial_cond"] if fixture.exists() else pressure_head(cols, cols.por_raw)[0]
+    from hydromodel_amd.stepper import EnsembleStepper, soil_moisture_record
+    depths = [float(d) for d in args.sensors.split(",")]
+    probe = EnsembleStepper(cols, forcing, 1)
+    try:
+        probe.set_state(psi0)
+        probe.set_noise_philox(2024, 0)
+        theta0 = probe.model_nodes()["theta"][0]
+    finally:
+        probe.close()
+    rec = soil_moisture_record(cols.z, depths, np.zeros((forcing.dim_t, len(depths))), args.sm_sigma)
+    rec["values"][:] = theta0[rec["nodes"]][None, :]
+    recs = [run(cols, forcing, psi0, args.members, int(s.rstrip("s")), args.sigma, args.localisation, args.warmup,
+                args.days, args.spread_cm, sensors=rec if s.endswith("s") else None)
+            for s in args.runs.split(",")]
+    base = [r for r in recs if r["stride"] == 0]
+    if base:
+        rate = float(np.mean([r["column_days_per_s"] for r in base]))
+        other = float(np.mean([r["other_ms"] for r in base]))
+        for r in recs:
+            r["kept"] = r["column_days_per_s"] / rate
+            if r["stride"] and r.get("analyses"):
+                r["sm_ms_per_analysis" if r["sensors"] else "enkf_ms_per_analysis"] = (r["other_ms"] - other) / r["analyses"]
+    line = json.dumps({"members": args.members, "depth": args.depth, "days": args.days, "sigma_cm": args.sigma,
+                       "localisation_cm": args.localisation, "spread_cm": args.spread_cm, "sensors_cm": depths,
+                       "sensor_nodes": rec["nodes"].tolist(), "sm_sigma": args.sm_sigma,
+                       "runs": recs})
+    print(line)
+    if args.json:
+        Path(args.json).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.json).write_text(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
