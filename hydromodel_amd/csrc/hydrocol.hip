@@ -176,27 +176,26 @@ struct hc_handle {
     DevBuf<unsigned long long> filt_qr, filt_surv;
     std::vector<long long> filt_rows_host;
     std::vector<int> h_wtd_obs;
-    // ensemble Kalman filter on the well's water table (hc_set_enkf): diagnostics float64 [P][n_arow][8] keyed by
-    // (points, rows, stride); per member the forecast y, eps, the posterior y and the rejection flag; per point the y
-    // statistics {mean, v}, the column means and the gain (the last analysis: test hooks); the tile partials
+    // ensemble Kalman filter (hc_set_enkf): diagnostics float64 [P][n_arow][8] keyed by (points, rows, stride); per
+    // member the observations Y [N][m'] (the well's y first), the well's eps, the sensors' eps [N][sm_n] and the
+    // posterior (y, theta..., rejected); per point the raw sums of both passes and the gain [P][m'][D] (the last
+    // analysis: test hooks); the tile partials
     int enkf_stride = 0;         // 0: off
     double enkf_sigma = 0.0, enkf_loc = 0.0;
     uint64_t enkf_seed = 0;
     bool enkf_done = false;      // an analysis has run since the EnKF was set
+    int enkf_width = 0;          // its m' (the rows of Y and the gain)
     AccTable<double> enkf{"entries"};
-    DevBuf<double> enkf_y, enkf_eps, enkf_ypost, enkf_ys, enkf_mean, enkf_gain, enkf_part;
-    DevBuf<int> enkf_rej;
+    DevBuf<double> enkf_Y, enkf_eps, enkf_eps_s, enkf_Ypost, enkf_gain, enkf_s1, enkf_s2, enkf_part;
     // soil-moisture sensors in the EnKF analysis (hc_set_enkf_soil_moisture): the record on the host (nodes, sigma,
-    // values [sm_rows][sm_n], NaN = none); diagnostics float64 [P][n_arow][sm_n][6] keyed like the EnKF's; per member the
-    // observations Y [N][m'], the posterior (y, theta..., rejected) and the sensors' eps [N][sm_n]; per point the raw sums
-    // of both passes and the gain [P][D][m'] (the last analysis: test hooks, sm_width = its m', 0 = no sensor on it)
+    // values [sm_rows][sm_n], NaN = none); diagnostics float64 [P][n_arow][sm_n][6] keyed like the EnKF's; sm_width =
+    // the last analysis's m', 0 = no sensor on it
     int sm_n = 0;                // 0: no record
     int64_t sm_rows = 0;
     std::vector<int> sm_nodes;
     std::vector<double> sm_sigma, sm_values;
     int sm_width = 0;
     AccTable<double> sm{"entries"};
-    DevBuf<double> sm_Y, sm_Ypost, sm_eps, sm_gain, sm_s1, sm_s2, sm_part;
     int n_cu = 256;
     double jac_reject = NUM_JAC_DIFF_REJECT;
 };
@@ -800,49 +799,51 @@ __global__ void filter_philox_fill_kernel(double *out, long long n_vec, const lo
     }
 }
 
-// a diagnostics table of `width` entries per slot, created as count 0 and NaN (the particle filter's and the EnKF's)
+// a diagnostics table of `width` entries per slot, created as NaN but for each slot's first entry, the count, created as 0
+// (the particle filter's and the EnKF's); width 0: all NaN (the sensors')
 __global__ void stats_init_kernel(double *stats, size_t n, int width)
 {
     const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < n) stats[k] = k % width == 0 ? 0.0 : __builtin_nan("");
+    if (k < n) stats[k] = width > 0 && k % width == 0 ? 0.0 : __builtin_nan("");
 }
 
-// ---- ensemble Kalman filter on the well's water table (hc_set_enkf, include/hydrocol.h)
-// Depths are measured from the top node, z_i = i dz: the C-ABI knows no z[0], and every quantity but the two means of
-// the diagnostics is a difference of depths (the host adds z[0] to those).  Every sum over a point's members runs in an
-// order fixed by N_p alone -- tiles of ENKF_TILE members summed in member order, then the tile partials in tile order;
-// the y statistics: thread t of one block takes members t, t + ENKF_THREADS, ... in order, then a fixed tree; the tile
-// partials of a node: thread t takes tiles t, t + ENKF_THREADS, ... in order, then the same tree -- and no
-// floating-point atomics, so the analysis is the same at any launch length, point order or member split.  Contraction
-// is off throughout.
+// ---- ensemble Kalman filter (hc_set_enkf, hc_set_enkf_soil_moisture; include/hydrocol.h)
+// An analysis row runs a batch analysis of m' = 1 + m_s observations per member: the well's y, then the theta of the
+// soil-moisture sensors with a value on the row (m_s = 0: the well alone).  Depths are measured from the top node,
+// z_i = i dz: the C-ABI knows no z[0], and every quantity but the two means of the diagnostics is a difference of depths
+// (the host adds z[0] to those).  Every sum over a point's members runs in an order fixed by N_p alone -- tiles of
+// ENKF_TILE members summed in member order, then the tile partials by ENKF_THREADS threads in tile-strided order and a
+// fixed tree, for every column at once -- and no floating-point atomics, so the analysis is the same at any launch
+// length, point order or member split.  The small m' x m' system is factorised by one thread per point.  Contraction is
+// off throughout (but inside the cell model, which keeps the code generation of model_nodes_kernel).
 constexpr int ENKF_TILE = 256;                         // members per partial of the column sums
-constexpr int ENKF_THREADS = 1024;                     // the per-point y statistics and the sums of the tile partials
+constexpr int ENKF_THREADS = 1024;                     // the sums of the tile partials
 constexpr int ENKF_SLOTS = HC_MAX_DEPTH_NODES / WAVE;  // depth nodes per lane of the update (one wave per member)
 constexpr int ENKF_WIDTH = 8;                          // diagnostics per point and slot
+constexpr int ENKF_SENSORS = 8;                        // sensors in a record
+constexpr int ENKF_OBS = ENKF_SENSORS + 1;             // observations per member: the well, then the sensors present
+constexpr int ENKF_SENSOR_WIDTH = 6;                   // sensor diagnostics per point, slot and sensor
 
-// eps_k: one standard normal of Philox4x32-10 under the EnKF seed at counter (0xFFFFFFFE, row, gid_lo, gid_hi), with
-// the Box-Muller step of philox_normal (its cosine branch).  A noise counter's first word is a depth index / 2 and the
-// particle filter's draw has 0xFFFFFFFF: the three never meet.
-// enkf_normal_at: the same step at counter (word0, row, gid_lo, gid_hi) -- the soil-moisture sensors' 0xFFFFFFF0 + i.
+// the observations of one analysis row beyond the well's, in record order (a kernel argument).  A row without a sensor
+// value (m = 0) is the well alone and leaves everything of the sensors -- their draws, their table -- untouched.
+struct EnkfRow {
+    int m;                     // present sensors m_s (m' = m_s + 1)
+    int n;                     // sensors drawn for and recorded: the record's, 0 when m = 0
+    int sensor[ENKF_SENSORS];  // record index of present sensor k
+    int node[ENKF_SENSORS];
+    double obs[ENKF_SENSORS];
+    double sigma[ENKF_SENSORS];
+};
+
+// One standard normal of Philox4x32-10 under the EnKF seed at counter (word0, row, gid_lo, gid_hi), with the Box-Muller
+// step of philox_normal (its cosine branch): the well's eps_k at word0 = 0xFFFFFFFE, sensor i's at 0xFFFFFFF0 + i.  A noise
+// counter's first word is a depth index / 2 and the particle filter's draw has 0xFFFFFFFF: they never meet.
 __device__ __forceinline__ double enkf_normal_at(uint32_t word0, unsigned long long seed, unsigned long long gid,
                                                  unsigned row)
 {
 #pragma clang fp contract(off)
     uint32_t r[4];
     philox4x32_10(word0, row, (uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), r);
-    const uint64_t a = ((uint64_t)r[1] << 32) | r[0], b = ((uint64_t)r[3] << 32) | r[2];
-    const double u1 = ((double)(a >> 11) + 0.5) * (1.0 / 9007199254740992.0);
-    const double u2 = ((double)(b >> 11) + 0.5) * (1.0 / 9007199254740992.0);
-    double s, c;
-    sincospi(2.0 * u2, &s, &c);
-    return sqrt(-2.0 * log(u1)) * c;
-}
-
-__device__ __forceinline__ double enkf_normal(unsigned long long seed, unsigned long long gid, unsigned row)
-{
-#pragma clang fp contract(off)
-    uint32_t r[4];
-    philox4x32_10(0xFFFFFFFEu, row, (uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), r);
     const uint64_t a = ((uint64_t)r[1] << 32) | r[0], b = ((uint64_t)r[3] << 32) | r[2];
     const double u1 = ((double)(a >> 11) + 0.5) * (1.0 / 9007199254740992.0);
     const double u2 = ((double)(b >> 11) + 0.5) * (1.0 / 9007199254740992.0);
@@ -869,15 +870,16 @@ __device__ __forceinline__ double gaspari_cohn(double r)
     return 0.0;
 }
 
-// y_k of every member from the index the step kernel wrote (wtd_u16's row) and the two nodes around it
+// Y[m][0] = y_m of every member (rows of `width` entries) from the index the step kernel wrote (wtd_u16's row) and the two
+// nodes around it
 __global__ void enkf_obs_kernel(const unsigned short *w, const double *psi, const ColumnDev *P, long long n_members,
-                                long long mpp, int D, double dz, double *y)
+                                long long mpp, int D, double dz, double *Y, int width)
 {
     const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= n_members) return;
     const int b = (int)w[m] < D ? (int)w[m] : D - 1;
     const double *col = psi + (size_t)m * D;
-    y[m] = enkf_y_of(b, b >= 1 ? col[b - 1] : 0.0, col[b], P[m / mpp].psi_sat, dz);
+    Y[(size_t)m * width] = enkf_y_of(b, b >= 1 ? col[b - 1] : 0.0, col[b], P[m / mpp].psi_sat, dz);
 }
 
 // the sum over the block's threads in a fixed tree (every thread gets it)
@@ -894,189 +896,8 @@ __device__ double enkf_block_sum(double v, double *sh)
     return r;
 }
 
-// One block per point: the mean of y and sum (y - mean)^2 / (N_p - 1) (0 for one member), two passes: ys[p] = {mean, v}.
-// With `stats` (the posterior y): the diagnostics' posterior mean, std and the count of rejected members.
-__global__ __launch_bounds__(ENKF_THREADS) void enkf_ystats_kernel(const double *y, const int *rej, long long mpp,
-                                                                   double *ys, double *stats, long long n_arow,
-                                                                   long long slot)
-{
-#pragma clang fp contract(off)
-    __shared__ double sh[ENKF_THREADS];
-    const long long p = blockIdx.x, first = p * mpp;
-    double s = 0.0;
-#pragma unroll 8
-    for (long long k = threadIdx.x; k < mpp; k += ENKF_THREADS) s += y[first + k];
-    const double mean = enkf_block_sum(s, sh) / (double)mpp;
-    double q = 0.0, nr = 0.0;
-#pragma unroll 8
-    for (long long k = threadIdx.x; k < mpp; k += ENKF_THREADS) {
-        const double a = y[first + k] - mean;
-        q += a * a;
-        if (rej) nr += (double)rej[first + k];
-    }
-    const double ss = enkf_block_sum(q, sh);
-    const double n_rej = enkf_block_sum(nr, sh);
-    if (threadIdx.x == 0) {
-        const double v = mpp > 1 ? ss / (double)(mpp - 1) : 0.0;
-        ys[2 * p] = mean;
-        ys[2 * p + 1] = v;
-        if (stats) {
-            double *st = stats + ((size_t)p * n_arow + slot) * ENKF_WIDTH;
-            st[5] = mean;
-            st[6] = sqrt(v);
-            st[7] = n_rej;
-        }
-    }
-}
-
-// partial[p][t][d]: the sum over tile t (ENKF_TILE members of point p) in member order of psi_dk (mean == NULL) or of
-// (psi_dk - mean_d)(y_k - ybar).  Thread d owns node d, so every member's row is one coalesced read of the block.
-__global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void enkf_col_partial_kernel(const double *psi, const double *y,
-                                                                              const double *ys, const double *mean,
-                                                                              long long mpp, int D, long long n_tiles,
-                                                                              double *partial)
-{
-#pragma clang fp contract(off)
-    const long long p = blockIdx.y, t = blockIdx.x;
-    const int d = threadIdx.x;
-    if (d >= D) return;
-    const long long m0 = p * mpp + t * ENKF_TILE;
-    const long long m1 = p * mpp + ((t + 1) * ENKF_TILE < mpp ? (t + 1) * ENKF_TILE : mpp);
-    double s = 0.0;
-    if (!mean) {
-#pragma unroll 8
-        for (long long m = m0; m < m1; m++) s += psi[(size_t)m * D + d];
-    } else {
-        const double md = mean[(size_t)p * D + d], yb = ys[2 * p];
-#pragma unroll 8
-        for (long long m = m0; m < m1; m++) s += (psi[(size_t)m * D + d] - md) * (y[m] - yb);
-    }
-    partial[((size_t)p * n_tiles + t) * D + d] = s;
-}
-
-// One block per node d and point p: the tile partials summed (thread t: tiles t, t + ENKF_THREADS, ... in order, then a
-// fixed tree).  gain == NULL: the column mean mean[p][d].  Otherwise c_d, the taper rho_d = GC(|z_d - ybar| / L) (L = 0:
-// 1) and K[p][d] = rho_d c_d / (v + sigma^2); block (0, p)'s thread 0 writes the prior entries of the diagnostics row
-// (count, ybar, sqrt v, innovation, log-likelihood increment).
-__global__ __launch_bounds__(ENKF_THREADS) void enkf_col_finish_kernel(const double *partial, long long n_tiles,
-                                                                       long long mpp, int D, const double *ys,
-                                                                       double *mean, double *gain, double sigma,
-                                                                       double loc, double z_obs, double dz, double *stats,
-                                                                       long long n_arow, long long slot)
-{
-#pragma clang fp contract(off)
-    __shared__ double sh[ENKF_THREADS];
-    const long long p = blockIdx.y;
-    const int d = blockIdx.x;
-    const double yb = ys[2 * p], s2 = ys[2 * p + 1] + sigma * sigma;
-    if (gain && blockIdx.x == 0 && threadIdx.x == 0) {
-        const double innov = z_obs - yb;
-        double *st = stats + ((size_t)p * n_arow + slot) * ENKF_WIDTH;
-        st[0] = (double)mpp;
-        st[1] = yb;
-        st[2] = sqrt(ys[2 * p + 1]);
-        st[3] = innov;
-        st[4] = -0.5 * log(2.0 * M_PI * s2) - 0.5 * (innov * innov) / s2;
-    }
-    double part = 0.0;
-    for (long long t = threadIdx.x; t < n_tiles; t += ENKF_THREADS) part += partial[((size_t)p * n_tiles + t) * D + d];
-    const double s = enkf_block_sum(part, sh);
-    if (threadIdx.x != 0) return;
-    if (!gain) {
-        mean[(size_t)p * D + d] = s / (double)mpp;
-        return;
-    }
-    const double c = mpp > 1 ? s / (double)(mpp - 1) : 0.0;
-    const double rho = loc > 0.0 ? gaspari_cohn(fabs((double)d * dz - yb) / loc) : 1.0;
-    gain[(size_t)p * D + d] = rho * c / s2;
-}
-
-// One wave per member: eps_k, o_k = z[o] + sigma eps_k, psi_dk + K_d (o_k - y_k) on every node, stored only when every
-// entry is finite (else the forecast stays and the member is counted as rejected); then the find_wtd index and the
-// posterior y of the column it kept.
-__global__ __launch_bounds__(256) void enkf_update_kernel(double *psi, const double *y, const double *gain,
-                                                          const ColumnDev *P, long long n_members, long long mpp, int D,
-                                                          double dz, double z_obs, double sigma, unsigned long long seed,
-                                                          const long long *point_base, long long member_offset,
-                                                          unsigned row, double *eps_out, double *y_post, int *rej)
-{
-#pragma clang fp contract(off)
-    const int lane = threadIdx.x % WAVE;
-    const long long waves = (long long)gridDim.x * (blockDim.x / WAVE);
-    for (long long m = (long long)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE; m < n_members; m += waves) {
-        const long long p = m / mpp;
-        const unsigned long long gid = point_base ? (unsigned long long)(point_base[p] + m % mpp)
-                                                  : (unsigned long long)(member_offset + m);
-        const double eps = enkf_normal(seed, gid, row);
-        const double innov = (z_obs + sigma * eps) - y[m];
-        const double *K = gain + (size_t)p * D;
-        double *col = psi + (size_t)m * D;
-        double v[ENKF_SLOTS], a[ENKF_SLOTS];
-        bool ok = true;
-#pragma unroll
-        for (int c = 0; c < ENKF_SLOTS; c++) {
-            const int d = c * WAVE + lane;
-            v[c] = d < D ? col[d] : 0.0;
-            a[c] = d < D ? v[c] + K[d] * innov : 0.0;
-            ok = ok && isfinite(a[c]);
-        }
-        const bool keep = __all(ok);
-        if (keep) {
-#pragma unroll
-            for (int c = 0; c < ENKF_SLOTS; c++) {
-                const int d = c * WAVE + lane;
-                if (d < D) col[d] = a[c];
-                v[c] = a[c];
-            }
-        }
-        // find_wtd of the kept column (the step kernel's rule): below the deepest node with psi < psi_sat, clamped
-        const double psat = P[p].psi_sat;
-        int deepest = -1;
-#pragma unroll
-        for (int c = 0; c < ENKF_SLOTS; c++) {
-            const int d = c * WAVE + lane;
-            const unsigned long long u = __ballot(d < D && !(v[c] >= psat));
-            if (u) deepest = c * WAVE + 63 - __clzll((long long)u);
-        }
-        const int b = deepest < 0 ? 0 : (deepest + 1 < D - 1 ? deepest + 1 : D - 1);
-        const int bl = b >= 1 ? b - 1 : 0;
-        double hi = 0.0, lo = 0.0;
-#pragma unroll
-        for (int c = 0; c < ENKF_SLOTS; c++) {
-            const double x = __shfl(v[c], b % WAVE), xl = __shfl(v[c], bl % WAVE);
-            if (c == b / WAVE) hi = x;
-            if (c == bl / WAVE) lo = xl;
-        }
-        if (lane == 0) {
-            eps_out[m] = eps;
-            y_post[m] = enkf_y_of(b, lo, hi, psat, dz);
-            rej[m] = keep ? 0 : 1;
-        }
-    }
-}
-
-// ---- soil-moisture sensors in the EnKF analysis (hc_set_enkf_soil_moisture, include/hydrocol.h)
-// A row with at least one sensor value runs a batch analysis of m' = 1 + m_s observations per member: the well's y, then
-// the theta of the present sensors at their nodes.  The sums follow the scalar path's rule -- tiles of ENKF_TILE members in
-// member order, the tile partials by ENKF_THREADS threads in tile-strided order and a fixed tree -- for every column at
-// once; the small m' x m' system is factorised by one thread per point.  Contraction is off throughout (but inside the
-// cell model, which keeps the code generation of model_nodes_kernel).
-constexpr int SM_MAX = 8;                              // sensors in a record
-constexpr int SM_OBS = SM_MAX + 1;                     // observations per member: the well, then the sensors present
-constexpr int SM_WIDTH = 6;                            // sensor diagnostics per point, slot and sensor
-
-// the sensors that have a value on one analysis row, in record order (a kernel argument)
-struct SmRow {
-    int m;                     // present sensors m_s (m' = m_s + 1)
-    int n;                     // sensors in the record
-    int sensor[SM_MAX];        // record index of present sensor k
-    int node[SM_MAX];
-    double obs[SM_MAX];
-    double sigma[SM_MAX];
-};
-
 // theta of one cell as model_nodes_kernel computes it (theta has no noise term)
-__device__ __forceinline__ double sm_theta(const ColumnDev &P, const double *nt, int D, int j, double psi, int special)
+__device__ __forceinline__ double enkf_theta(const ColumnDev &P, const double *nt, int D, int j, double psi, int special)
 {
     const double por = nt[j], meank = nt[D + j], noisec = nt[2 * D + j];
     const double mk = meank == 0.0 ? 1.0e-7 : meank;
@@ -1088,27 +909,26 @@ __device__ __forceinline__ double sm_theta(const ColumnDev &P, const double *nt,
     return th;
 }
 
-// Y[m][1 + k] = theta of member m at the node of present sensor k, Y[m][0] = y_m (enkf_obs_kernel's; y == NULL: left
-// alone), rows of `width` entries: the forecast's Y (width m') and the posterior's (y, theta..., rejected)
-__global__ void sm_obs_kernel(const double *psi, const double *y, const ColumnDev *P, const double *node_tabs,
-                              int special, long long n_members, long long mpp, int D, const SmRow s, double *Y, int width)
+// Y[m][1 + k] = theta of member m at the node of present sensor k, rows of `width` entries: the forecast's Y (width m')
+// and the posterior's (y, theta..., rejected)
+__global__ void enkf_theta_kernel(const double *psi, const ColumnDev *P, const double *node_tabs, int special,
+                                  long long n_members, long long mpp, int D, const EnkfRow s, double *Y, int width)
 {
     const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= n_members) return;
     const long long p = m / mpp;
     const double *nt = node_tabs + (size_t)p * 3 * D;
-    if (y) Y[(size_t)m * width] = y[m];
     for (int k = 0; k < s.m; k++)
-        Y[(size_t)m * width + 1 + k] = sm_theta(P[p], nt, D, s.node[k], psi[(size_t)m * D + s.node[k]], special);
+        Y[(size_t)m * width + 1 + k] = enkf_theta(P[p], nt, D, s.node[k], psi[(size_t)m * D + s.node[k]], special);
 }
 
 // Column sums of X = (psi_0 .. psi_{Dc-1}, Y_0 .. Y_{W-1}) (Dc = 0: Y alone), C = Dc + W columns, tile t of point p:
 //   sums == NULL: partial[p][t][j] = sum over the tile in member order of X_j;
 //   otherwise:    partial[p][t][j][i] = sum of (X_j - xbar_j)(Y_i - ybar_i), the means = sums[p][.] / N_p.
 // Thread j owns column j: every member's psi row is one coalesced read of the block.
-__global__ __launch_bounds__(HC_MAX_DEPTH_NODES + WAVE) void sm_partial_kernel(const double *psi, const double *Y, int W,
-                                                                               const double *sums, long long mpp, int Dc,
-                                                                               long long n_tiles, double *partial)
+__global__ __launch_bounds__(HC_MAX_DEPTH_NODES + WAVE) void enkf_partial_kernel(const double *psi, const double *Y, int W,
+                                                                                 const double *sums, long long mpp, int Dc,
+                                                                                 long long n_tiles, double *partial)
 {
 #pragma clang fp contract(off)
     const long long p = blockIdx.y, t = blockIdx.x;
@@ -1127,9 +947,9 @@ __global__ __launch_bounds__(HC_MAX_DEPTH_NODES + WAVE) void sm_partial_kernel(c
     }
     const double *S = sums + (size_t)p * C;
     const double xb = S[j] / (double)mpp;
-    double yb[SM_OBS + 1], acc[SM_OBS + 1];
+    double yb[ENKF_OBS + 1], acc[ENKF_OBS + 1];
 #pragma unroll
-    for (int i = 0; i < SM_OBS + 1; i++) {
+    for (int i = 0; i < ENKF_OBS + 1; i++) {
         yb[i] = i < W ? S[Dc + i] / (double)mpp : 0.0;
         acc[i] = 0.0;
     }
@@ -1137,18 +957,18 @@ __global__ __launch_bounds__(HC_MAX_DEPTH_NODES + WAVE) void sm_partial_kernel(c
         const double a = x[(size_t)m * xs] - xb;
         const double *ym = Y + (size_t)m * W;
 #pragma unroll
-        for (int i = 0; i < SM_OBS + 1; i++)
+        for (int i = 0; i < ENKF_OBS + 1; i++)
             if (i < W) acc[i] += a * (ym[i] - yb[i]);
     }
     double *out = partial + (((size_t)p * n_tiles + t) * C + j) * W;
 #pragma unroll
-    for (int i = 0; i < SM_OBS + 1; i++)
+    for (int i = 0; i < ENKF_OBS + 1; i++)
         if (i < W) out[i] = acc[i];
 }
 
 // sums[p][c] = the tile partials of column c summed (thread t: tiles t, t + ENKF_THREADS, ... in order, then a fixed tree)
-__global__ __launch_bounds__(ENKF_THREADS) void sm_finish_kernel(const double *partial, long long n_tiles, int n_cols,
-                                                                 double *sums)
+__global__ __launch_bounds__(ENKF_THREADS) void enkf_finish_kernel(const double *partial, long long n_tiles, int n_cols,
+                                                                   double *sums)
 {
 #pragma clang fp contract(off)
     __shared__ double sh[ENKF_THREADS];
@@ -1161,19 +981,19 @@ __global__ __launch_bounds__(ENKF_THREADS) void sm_finish_kernel(const double *p
 }
 
 // L L^T = A (n x n, row-major, lower triangle read), in a fixed order; false when a pivot is not finite and > 0
-__device__ bool sm_cholesky(const double *A, int n, double *L)
+__device__ bool enkf_cholesky(const double *A, int n, double *L)
 {
 #pragma clang fp contract(off)
     for (int j = 0; j < n; j++) {
-        double d = A[j * SM_OBS + j];
-        for (int k = 0; k < j; k++) d -= L[j * SM_OBS + k] * L[j * SM_OBS + k];
+        double d = A[j * ENKF_OBS + j];
+        for (int k = 0; k < j; k++) d -= L[j * ENKF_OBS + k] * L[j * ENKF_OBS + k];
         if (!(d > 0.0) || !isfinite(d)) return false;
         const double ljj = sqrt(d);
-        L[j * SM_OBS + j] = ljj;
+        L[j * ENKF_OBS + j] = ljj;
         for (int i = j + 1; i < n; i++) {
-            double v = A[i * SM_OBS + j];
-            for (int k = 0; k < j; k++) v -= L[i * SM_OBS + k] * L[j * SM_OBS + k];
-            L[i * SM_OBS + j] = v / ljj;
+            double v = A[i * ENKF_OBS + j];
+            for (int k = 0; k < j; k++) v -= L[i * ENKF_OBS + k] * L[j * ENKF_OBS + k];
+            L[i * ENKF_OBS + j] = v / ljj;
         }
     }
     return true;
@@ -1181,18 +1001,18 @@ __device__ bool sm_cholesky(const double *A, int n, double *L)
 
 // One block per point, thread d = node d.  Thread 0: ybar, C_YY, the tapered S = rho o C_YY + R and its Cholesky factor;
 // the untapered C_YY + R for the joint log-density; the prior diagnostics (EnKF entries 0-4, the sensors' first four).
-// Then thread d: K_d = (rho_d o c_d) S^-1 by a forward and a backward substitution; K_d0 also goes to the scalar gain.
-__global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void sm_gain_kernel(const double *s1, const double *s2, long long mpp,
-                                                                     int D, const SmRow s, double sigma, double loc,
-                                                                     double z_obs, double dz, double *gain,
-                                                                     double *gain_well, double *stats, double *sm_stats,
-                                                                     long long n_arow, long long slot)
+// Then thread d: K_d = (rho_d o c_d) S^-1 by a forward and a backward substitution, into gain[p][i][d].
+__global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void enkf_gain_kernel(const double *s1, const double *s2, long long mpp,
+                                                                       int D, const EnkfRow s, double sigma, double loc,
+                                                                       double z_obs, double dz, double *gain,
+                                                                       double *stats, double *sm_stats, long long n_arow,
+                                                                       long long slot)
 {
 #pragma clang fp contract(off)
     // the working sets live in LDS (dynamically indexed: in registers they would go to scratch)
-    __shared__ double Ls[SM_OBS * SM_OBS], Lu[SM_OBS * SM_OBS], A[SM_OBS * SM_OBS], cyy[SM_OBS * SM_OBS];
-    __shared__ double zeta[SM_OBS], yb[SM_OBS], r2[SM_OBS], dl[SM_OBS], w[SM_OBS];
-    __shared__ double U[HC_MAX_DEPTH_NODES][SM_OBS];   // thread d's substitutions
+    __shared__ double Ls[ENKF_OBS * ENKF_OBS], Lu[ENKF_OBS * ENKF_OBS], A[ENKF_OBS * ENKF_OBS], cyy[ENKF_OBS * ENKF_OBS];
+    __shared__ double zeta[ENKF_OBS], yb[ENKF_OBS], r2[ENKF_OBS], dl[ENKF_OBS], w[ENKF_OBS];
+    __shared__ double U[HC_MAX_DEPTH_NODES][ENKF_OBS];   // thread d's substitutions
     __shared__ int ok;
     const long long p = blockIdx.x;
     const int W = s.m + 1, C = D + W;
@@ -1206,24 +1026,24 @@ __global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void sm_gain_kernel(const doubl
             zeta[i] = i == 0 ? yb[0] : (double)s.node[i - 1] * dz;
         }
         for (int i = 0; i < W; i++)
-            for (int k = 0; k < W; k++) cyy[i * SM_OBS + k] = mpp > 1 ? S2[(size_t)(D + i) * W + k] / n1 : 0.0;
+            for (int k = 0; k < W; k++) cyy[i * ENKF_OBS + k] = mpp > 1 ? S2[(size_t)(D + i) * W + k] / n1 : 0.0;
         for (int i = 0; i < W; i++)
             for (int k = 0; k < W; k++) {
                 const double rho = loc > 0.0 ? gaspari_cohn(fabs(zeta[i] - zeta[k]) / loc) : 1.0;
-                A[i * SM_OBS + k] = rho * cyy[i * SM_OBS + k] + (i == k ? r2[i] : 0.0);
+                A[i * ENKF_OBS + k] = rho * cyy[i * ENKF_OBS + k] + (i == k ? r2[i] : 0.0);
             }
-        ok = sm_cholesky(A, W, Ls) ? 1 : 0;
+        ok = enkf_cholesky(A, W, Ls) ? 1 : 0;
         // log N(obs; ybar, C_YY + R) = -0.5 (m' log 2 pi + log det + |L^-1 (obs - ybar)|^2)
         for (int i = 0; i < W; i++)
-            for (int k = 0; k < W; k++) A[i * SM_OBS + k] = cyy[i * SM_OBS + k] + (i == k ? r2[i] : 0.0);
+            for (int k = 0; k < W; k++) A[i * ENKF_OBS + k] = cyy[i * ENKF_OBS + k] + (i == k ? r2[i] : 0.0);
         double ll = __builtin_nan("");
-        if (sm_cholesky(A, W, Lu)) {
+        if (enkf_cholesky(A, W, Lu)) {
             double logdet = 0.0, q = 0.0;
             for (int i = 0; i < W; i++) {
                 double v = dl[i];
-                for (int k = 0; k < i; k++) v -= Lu[i * SM_OBS + k] * w[k];
-                w[i] = v / Lu[i * SM_OBS + i];
-                logdet += log(Lu[i * SM_OBS + i]);
+                for (int k = 0; k < i; k++) v -= Lu[i * ENKF_OBS + k] * w[k];
+                w[i] = v / Lu[i * ENKF_OBS + i];
+                logdet += log(Lu[i * ENKF_OBS + i]);
                 q += w[i] * w[i];
             }
             ll = -0.5 * ((double)W * log(2.0 * M_PI) + 2.0 * logdet + q);
@@ -1234,110 +1054,148 @@ __global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void sm_gain_kernel(const doubl
         st[2] = sqrt(cyy[0]);
         st[3] = dl[0];
         st[4] = ll;
-        double *ss = sm_stats + ((size_t)p * n_arow + slot) * s.n * SM_WIDTH;
-        for (int i = 0; i < s.n; i++) ss[i * SM_WIDTH] = 0.0;      // observed: 0 unless present (the rest stays NaN)
-        for (int k = 0; k < s.m; k++) {
-            double *e = ss + s.sensor[k] * SM_WIDTH;
-            e[0] = 1.0;
-            e[1] = s.obs[k];
-            e[2] = yb[k + 1];
-            e[3] = sqrt(cyy[(k + 1) * SM_OBS + k + 1]);
+        if (s.m > 0) {
+            double *ss = sm_stats + ((size_t)p * n_arow + slot) * s.n * ENKF_SENSOR_WIDTH;
+            for (int i = 0; i < s.n; i++) ss[i * ENKF_SENSOR_WIDTH] = 0.0;      // observed: 0 unless present (the rest stays NaN)
+            for (int k = 0; k < s.m; k++) {
+                double *e = ss + s.sensor[k] * ENKF_SENSOR_WIDTH;
+                e[0] = 1.0;
+                e[1] = s.obs[k];
+                e[2] = yb[k + 1];
+                e[3] = sqrt(cyy[(k + 1) * ENKF_OBS + k + 1]);
+            }
         }
     }
     __syncthreads();
     const int d = threadIdx.x;
     if (d >= D) return;
-    double *K = gain + ((size_t)p * D + d) * W;
+    double *K = gain + (size_t)p * W * D + d;
     if (!ok) {
-        for (int i = 0; i < W; i++) K[i] = __builtin_nan("");
-        gain_well[(size_t)p * D + d] = __builtin_nan("");
+        for (int i = 0; i < W; i++) K[(size_t)i * D] = __builtin_nan("");
         return;
     }
     double *u = U[d];
     for (int i = 0; i < W; i++) {
         const double rho = loc > 0.0 ? gaspari_cohn(fabs((double)d * dz - zeta[i]) / loc) : 1.0;
         double v = rho * (mpp > 1 ? S2[(size_t)d * W + i] / n1 : 0.0);
-        for (int k = 0; k < i; k++) v -= Ls[i * SM_OBS + k] * u[k];
-        u[i] = v / Ls[i * SM_OBS + i];
+        for (int k = 0; k < i; k++) v -= Ls[i * ENKF_OBS + k] * u[k];
+        u[i] = v / Ls[i * ENKF_OBS + i];
     }
     for (int i = W - 1; i >= 0; i--) {
         double v = u[i];
-        for (int k = i + 1; k < W; k++) v -= Ls[k * SM_OBS + i] * u[k];
-        u[i] = v / Ls[i * SM_OBS + i];
+        for (int k = i + 1; k < W; k++) v -= Ls[k * ENKF_OBS + i] * u[k];
+        u[i] = v / Ls[i * ENKF_OBS + i];
     }
-    for (int i = 0; i < W; i++) K[i] = u[i];
-    gain_well[(size_t)p * D + d] = u[0];
+    for (int i = 0; i < W; i++) K[(size_t)i * D] = u[i];
 }
 
-// One wave per member: the well's eps (enkf_normal) and the sensors' (lane i < n: counter word 0xFFFFFFF0 + i), the
-// innovations o_k - Y_k, psi_dk + sum_i K_di (o_ki - Y_ki) (i in order) on every node, stored only when every entry is
-// finite (as enkf_update_kernel); then the find_wtd index and the posterior y of the column it kept: Ypost[m] = (y, ...,
-// rejected) (sm_obs_kernel fills in the posterior theta).
-__global__ __launch_bounds__(256) void sm_update_kernel(double *psi, const double *Y, const double *gain,
-                                                        const ColumnDev *P, long long n_members, long long mpp, int D, double dz,
-                                                        double z_obs, double sigma, const SmRow s,
-                                                        unsigned long long seed, const long long *point_base,
-                                                        long long member_offset, unsigned row, double *eps_out,
-                                                        double *sm_eps, double *Ypost)
+// lane i's v, for every lane of the wave, in scalar registers (v_readlane reads lane i whichever lanes are active)
+__device__ __forceinline__ double lane_value(double v, int i)
+{
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, i);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), i);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+// eps_k of every member, and sensor i's (i < n) into eps_s [N][n] (one thread per member)
+__global__ void enkf_draw_kernel(long long n_members, long long mpp, unsigned long long seed, const long long *point_base,
+                                 long long member_offset, unsigned row, int n, double *eps, double *eps_s)
+{
+    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n_members) return;
+    const unsigned long long gid = point_base ? (unsigned long long)(point_base[m / mpp] + m % mpp)
+                                              : (unsigned long long)(member_offset + m);
+    eps[m] = enkf_normal_at(0xFFFFFFFEu, seed, gid, row);
+    for (int i = 0; i < n; i++) eps_s[(size_t)m * n + i] = enkf_normal_at(0xFFFFFFF0u + (unsigned)i, seed, gid, row);
+}
+
+// One wave per member: the innovations o_k - Y_k from the draws of enkf_draw_kernel, psi_dk + sum_i K_di (o_ki - Y_ki)
+// (i in order) on every node, stored only when every entry is finite (else the forecast stays and the member is counted
+// as rejected); then the find_wtd index and the posterior y of the column it kept: Ypost[m] = (y, ..., rejected)
+// (enkf_theta_kernel fills in the posterior theta).
+__global__ __launch_bounds__(256) void enkf_update_kernel(double *psi, const double *Y, const double *gain,
+                                                          const ColumnDev *P, long long n_members, long long mpp, int D,
+                                                          double dz, double z_obs, double sigma, const EnkfRow s,
+                                                          const double *eps, const double *eps_s, double *Ypost)
 {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x % WAVE;
     const int W = s.m + 1;
+    // lane 1 + k holds present sensor k: its record index, observation and sigma
+    int my_sensor = 0;
+    double my_obs = 0.0, my_sigma = 0.0;
+#pragma unroll
+    for (int k = 0; k < ENKF_SENSORS; k++)
+        if (k < s.m && lane == 1 + k) my_sensor = s.sensor[k], my_obs = s.obs[k], my_sigma = s.sigma[k];
     const long long waves = (long long)gridDim.x * (blockDim.x / WAVE);
     for (long long m = (long long)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE; m < n_members; m += waves) {
         const long long p = m / mpp;
-        const unsigned long long gid = point_base ? (unsigned long long)(point_base[p] + m % mpp)
-                                                  : (unsigned long long)(member_offset + m);
-        const double eps = enkf_normal(seed, gid, row);
-        const double e_mine = lane < s.n ? enkf_normal_at(0xFFFFFFF0u + (unsigned)lane, seed, gid, row) : 0.0;
-        // lane i holds innovation i: the well's on lane 0, present sensor k's on lane 1 + k
-        const double *Ym = Y + (size_t)m * W;
-        double my_dl = lane == 0 ? (z_obs + sigma * eps) - Ym[0] : 0.0;
-        for (int k = 0; k < s.m; k++) {
-            const double e = __shfl(e_mine, s.sensor[k]);
-            if (lane == 1 + k) my_dl = (s.obs[k] + s.sigma[k] * e) - Ym[1 + k];
-        }
-        const double *K = gain + (size_t)p * D * W;
+        // a: the column; inc: the well's gain, then the increments sum_i K_di (o_i - Y_i) summed in i order, one gain
+        // row at a time with the loads of all its slots in flight; then a = psi_d + inc
+        const double *K = gain + (size_t)p * W * D;
         double *col = psi + (size_t)m * D;
-        double v[ENKF_SLOTS], a[ENKF_SLOTS];
+        double a[ENKF_SLOTS], inc[ENKF_SLOTS];
 #pragma unroll
         for (int c = 0; c < ENKF_SLOTS; c++) {
             const int d = c * WAVE + lane;
-            v[c] = d < D ? col[d] : 0.0;
             a[c] = 0.0;
+            inc[c] = 0.0;
+            if (d < D) {
+                a[c] = col[d];
+                inc[c] = K[d];
+            }
         }
+        // lane i holds innovation i: the well's on lane 0 (dl0, on every lane too), present sensor k's on lane 1 + k
+        const double *Ym = Y + (size_t)m * W;
+        const double dl0 = (z_obs + sigma * eps[m]) - Ym[0];
+        const double my_dl = lane == 0  ? dl0
+                             : lane < W ? (my_obs + my_sigma * eps_s[(size_t)m * s.n + my_sensor]) - Ym[lane]
+                                        : 0.0;
+#pragma unroll
+        for (int c = 0; c < ENKF_SLOTS; c++) inc[c] = inc[c] * dl0;
 #pragma unroll 1
-        for (int i = 0; i < W; i++) {                // the increments K_d . (o - Y), summed in i order
-            const double di = __shfl(my_dl, i);
+        for (int i = 1; i < W; i++) {
+            const double di = lane_value(my_dl, i);
+            double k[ENKF_SLOTS];
 #pragma unroll
             for (int c = 0; c < ENKF_SLOTS; c++) {
                 const int d = c * WAVE + lane;
-                const double t = d < D ? K[(size_t)d * W + i] * di : 0.0;
-                a[c] = i == 0 ? t : a[c] + t;
+                k[c] = d < D ? K[(size_t)i * D + d] : 0.0;
             }
+#pragma unroll
+            for (int c = 0; c < ENKF_SLOTS; c++) inc[c] = inc[c] + k[c] * di;
         }
         bool ok = true;
 #pragma unroll
         for (int c = 0; c < ENKF_SLOTS; c++) {
             const int d = c * WAVE + lane;
-            a[c] = d < D ? v[c] + a[c] : 0.0;
+            if (d < D) a[c] = a[c] + inc[c];
             ok = ok && isfinite(a[c]);
         }
+        // a becomes the column the member keeps: the analysis, or the forecast read back (a branch on the wave-uniform
+        // keep around each loop: one inside them costs 16 VGPRs of copies and a wave of occupancy)
         const bool keep = __all(ok);
         if (keep) {
 #pragma unroll
             for (int c = 0; c < ENKF_SLOTS; c++) {
                 const int d = c * WAVE + lane;
                 if (d < D) col[d] = a[c];
-                v[c] = a[c];
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < ENKF_SLOTS; c++) {
+                const int d = c * WAVE + lane;
+                a[c] = d < D ? col[d] : 0.0;
             }
         }
+        // find_wtd of the kept column (the step kernel's rule): below the deepest node with psi < psi_sat, clamped
         const double psat = P[p].psi_sat;
         int deepest = -1;
 #pragma unroll
         for (int c = 0; c < ENKF_SLOTS; c++) {
             const int d = c * WAVE + lane;
-            const unsigned long long u = __ballot(d < D && !(v[c] >= psat));
+            const unsigned long long u = __ballot(d < D && !(a[c] >= psat));
             if (u) deepest = c * WAVE + 63 - __clzll((long long)u);
         }
         const int b = deepest < 0 ? 0 : (deepest + 1 < D - 1 ? deepest + 1 : D - 1);
@@ -1345,14 +1203,12 @@ __global__ __launch_bounds__(256) void sm_update_kernel(double *psi, const doubl
         double hi = 0.0, lo = 0.0;
 #pragma unroll
         for (int c = 0; c < ENKF_SLOTS; c++) {
-            const double x = __shfl(v[c], b % WAVE), xl = __shfl(v[c], bl % WAVE);
+            const double x = __shfl(a[c], b % WAVE), xl = __shfl(a[c], bl % WAVE);
             if (c == b / WAVE) hi = x;
             if (c == bl / WAVE) lo = xl;
         }
         double *out = Ypost + (size_t)m * (W + 1);
-        if (lane < s.n) sm_eps[(size_t)m * s.n + lane] = e_mine;
         if (lane == 0) {
-            eps_out[m] = eps;
             out[0] = enkf_y_of(b, lo, hi, psat, dz);
             out[W] = keep ? 0.0 : 1.0;
         }
@@ -1361,8 +1217,8 @@ __global__ __launch_bounds__(256) void sm_update_kernel(double *psi, const doubl
 
 // One thread per point: the posterior diagnostics from the raw sums of Ypost (s1 [P][W + 1], s2 [P][W + 1][W + 1]): the
 // EnKF's entries 5-7 and the sensors' posterior mean and std.
-__global__ void sm_post_kernel(const double *s1, const double *s2, long long n_points, long long mpp, const SmRow s,
-                               double *stats, double *sm_stats, long long n_arow, long long slot)
+__global__ void enkf_post_kernel(const double *s1, const double *s2, long long n_points, long long mpp, const EnkfRow s,
+                                 double *stats, double *sm_stats, long long n_arow, long long slot)
 {
 #pragma clang fp contract(off)
     const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1374,9 +1230,8 @@ __global__ void sm_post_kernel(const double *s1, const double *s2, long long n_p
     st[5] = S1[0] / (double)mpp;
     st[6] = sqrt(mpp > 1 ? S2[0] / n1 : 0.0);
     st[7] = S1[V - 1];
-    double *ss = sm_stats + ((size_t)p * n_arow + slot) * s.n * SM_WIDTH;
     for (int k = 0; k < s.m; k++) {
-        double *e = ss + s.sensor[k] * SM_WIDTH;
+        double *e = sm_stats + (((size_t)p * n_arow + slot) * s.n + s.sensor[k]) * ENKF_SENSOR_WIDTH;
         e[4] = S1[k + 1] / (double)mpp;
         e[5] = sqrt(mpp > 1 ? S2[(size_t)(k + 1) * V + k + 1] / n1 : 0.0);
     }
@@ -1668,23 +1523,29 @@ int ensure_hist(hc_handle *h)
     return h->hist.ensure(h->n_points, h->n_rows, h->p.dim_d, hist_entries(h));
 }
 
+// An assimilation table keyed by (points, rows, stride): `per_row` entries per point and analysis row (every stride-th
+// row), created on a fresh key as NaN with each slot's count 0 (`width` entries a slot; 0: all NaN)
+int ensure_da_table(hc_handle *h, AccTable<double> &t, int64_t stride, int64_t per_row, int width)
+{
+    const bool fresh = !(t.key[0] == h->n_points && t.key[1] == h->n_rows && t.key[2] == stride);
+    const int64_t n = (int64_t)h->n_points * ((h->n_rows - 1) / stride + 1) * per_row;
+    if (int rc = t.ensure(h->n_points, h->n_rows, stride, n)) return rc;
+    if (fresh) {
+        hipLaunchKernelGGL(stats_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, t.buf.p,
+                           (size_t)n, width);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    return HC_OK;
+}
+
 // the particle filter's diagnostics (hc_set_filter): [P][n_arow][4] float64, created as count 0 and NaN
 int64_t filter_rows(const hc_handle *h) { return (h->n_rows - 1) / h->filt_stride + 1; }
 int ensure_filter(hc_handle *h)
 {
     if (h->filt_stride <= 0) return fail(HC_ERR_ARG, "the particle filter is off (hc_set_filter)");
     if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
-    AccTable<double> &t = h->filt;
-    const bool fresh = !(t.key[0] == h->n_points && t.key[1] == h->n_rows && t.key[2] == h->filt_stride);
-    const int64_t n = (int64_t)h->n_points * filter_rows(h) * 4;
-    if (int rc = t.ensure(h->n_points, h->n_rows, h->filt_stride, n)) return rc;
-    if (fresh) {
-        hipLaunchKernelGGL(stats_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, t.buf.p,
-                           (size_t)n, 4);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    return HC_OK;
+    return ensure_da_table(h, h->filt, h->filt_stride, 4, 4);
 }
 
 // what turns the filter off: new points, members or noise source (include/hydrocol.h hc_set_filter)
@@ -1704,17 +1565,7 @@ int ensure_enkf(hc_handle *h)
 {
     if (h->enkf_stride <= 0) return fail(HC_ERR_ARG, "the EnKF is off (hc_set_enkf)");
     if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
-    AccTable<double> &t = h->enkf;
-    const bool fresh = !(t.key[0] == h->n_points && t.key[1] == h->n_rows && t.key[2] == h->enkf_stride);
-    const int64_t n = (int64_t)h->n_points * enkf_rows(h) * ENKF_WIDTH;
-    if (int rc = t.ensure(h->n_points, h->n_rows, h->enkf_stride, n)) return rc;
-    if (fresh) {
-        hipLaunchKernelGGL(stats_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, t.buf.p,
-                           (size_t)n, ENKF_WIDTH);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    return HC_OK;
+    return ensure_da_table(h, h->enkf, h->enkf_stride, ENKF_WIDTH, ENKF_WIDTH);
 }
 
 // the sensor diagnostics (hc_set_enkf_soil_moisture): [P][n_arow][n][6] float64, created as NaN
@@ -1725,17 +1576,7 @@ int ensure_sm(hc_handle *h)
     if (h->sm_rows != h->n_rows)
         return fail(HC_ERR_ARG, "the soil-moisture record has %lld rows, the forcing %lld: set the record again",
                     (long long)h->sm_rows, (long long)h->n_rows);
-    AccTable<double> &t = h->sm;
-    const bool fresh = !(t.key[0] == h->n_points && t.key[1] == h->n_rows && t.key[2] == h->enkf_stride);
-    const int64_t n = (int64_t)h->n_points * enkf_rows(h) * h->sm_n * SM_WIDTH;
-    if (int rc = t.ensure(h->n_points, h->n_rows, h->enkf_stride, n)) return rc;
-    if (fresh) {
-        hipLaunchKernelGGL(fill_d, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, t.buf.p,
-                           __builtin_nan(""), (size_t)n);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    return HC_OK;
+    return ensure_da_table(h, h->sm, h->enkf_stride, (int64_t)h->sm_n * ENKF_SENSOR_WIDTH, 0);
 }
 
 void sm_off(hc_handle *h)
@@ -1745,17 +1586,17 @@ void sm_off(hc_handle *h)
     h->sm_width = 0;
     h->sm_nodes.clear(); h->sm_sigma.clear(); h->sm_values.clear();
     h->sm.release();
-    h->sm_Y.release(); h->sm_Ypost.release(); h->sm_eps.release(); h->sm_gain.release();
-    h->sm_s1.release(); h->sm_s2.release(); h->sm_part.release();
+    h->enkf_eps_s.release();
 }
 
 void enkf_off(hc_handle *h)
 {
     h->enkf_stride = 0;
     h->enkf_done = false;
+    h->enkf_width = 0;
     h->enkf.release();
-    h->enkf_y.release(); h->enkf_eps.release(); h->enkf_ypost.release(); h->enkf_ys.release();
-    h->enkf_mean.release(); h->enkf_gain.release(); h->enkf_part.release(); h->enkf_rej.release();
+    h->enkf_Y.release(); h->enkf_eps.release(); h->enkf_Ypost.release(); h->enkf_gain.release();
+    h->enkf_s1.release(); h->enkf_s2.release(); h->enkf_part.release();
     sm_off(h);
 }
 
@@ -2644,62 +2485,10 @@ int assimilate(hc_handle *h, const Chunk &c)
     return HC_OK;
 }
 
-// The EnKF's analysis at the launch's last row (its water-table indices are wtd_u16's last row), in place on psi: y per
-// member; per point ybar and v, the column means, then c_d, the gain and the prior diagnostics; the update with eps and
-// the posterior y per member; the posterior diagnostics.  Three passes over psi (two reads, one read + write).
-int enkf_analyse(hc_handle *h, const Chunk &c)
+// The observations of `row` beyond the well's: the sensors with a value, in record order
+EnkfRow enkf_row(const hc_handle *h, int64_t row)
 {
-    const int64_t N = h->n_members, D = h->p.dim_d, P = h->n_points, mpp = N / P;
-    const int64_t row = c.row0 + c.rows - 1, slot = row / h->enkf_stride, n_arow = enkf_rows(h);
-    h->sm_width = 0;
-    const int64_t n_tiles = (mpp + ENKF_TILE - 1) / ENKF_TILE;
-    if (h->enkf_y.ensure((size_t)N) || h->enkf_eps.ensure((size_t)N) || h->enkf_ypost.ensure((size_t)N) ||
-        h->enkf_rej.ensure((size_t)N) || h->enkf_ys.ensure((size_t)(2 * P)) || h->enkf_mean.ensure((size_t)(P * D)) ||
-        h->enkf_gain.ensure((size_t)(P * D)) || h->enkf_part.ensure((size_t)(P * n_tiles * D)))
-        return HC_ERR_DEVICE;
-    const unsigned short *w = h->wtd_u16.p + (size_t)(c.rows - 1) * N;
-    const double dz = h->p.dz, z_obs = (double)h->h_wtd_obs[(size_t)row] * dz;
-    double *st = h->enkf.buf.p;
-    hipLaunchKernelGGL(enkf_obs_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, w, h->psi.p, h->Pdev.p,
-                       (long long)N, (long long)mpp, (int)D, dz, h->enkf_y.p);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(enkf_ystats_kernel, dim3((unsigned)P), dim3(ENKF_THREADS), 0, h->stream, h->enkf_y.p, nullptr,
-                       (long long)mpp, h->enkf_ys.p, nullptr, (long long)n_arow, (long long)slot);
-    HIP_TRY(hipGetLastError());
-    const dim3 tiles((unsigned)n_tiles, (unsigned)P), cols((unsigned)((D + WAVE - 1) / WAVE * WAVE));
-    const dim3 fin((unsigned)D, (unsigned)P);
-    hipLaunchKernelGGL(enkf_col_partial_kernel, tiles, cols, 0, h->stream, h->psi.p, h->enkf_y.p, h->enkf_ys.p, nullptr,
-                       (long long)mpp, (int)D, (long long)n_tiles, h->enkf_part.p);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(enkf_col_finish_kernel, fin, dim3(ENKF_THREADS), 0, h->stream, h->enkf_part.p, (long long)n_tiles,
-                       (long long)mpp, (int)D, h->enkf_ys.p, h->enkf_mean.p, nullptr, h->enkf_sigma, h->enkf_loc, z_obs, dz,
-                       st, (long long)n_arow, (long long)slot);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(enkf_col_partial_kernel, tiles, cols, 0, h->stream, h->psi.p, h->enkf_y.p, h->enkf_ys.p,
-                       h->enkf_mean.p, (long long)mpp, (int)D, (long long)n_tiles, h->enkf_part.p);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(enkf_col_finish_kernel, fin, dim3(ENKF_THREADS), 0, h->stream, h->enkf_part.p, (long long)n_tiles,
-                       (long long)mpp, (int)D, h->enkf_ys.p, nullptr, h->enkf_gain.p, h->enkf_sigma, h->enkf_loc, z_obs,
-                       dz, st, (long long)n_arow, (long long)slot);
-    HIP_TRY(hipGetLastError());
-    const unsigned blocks = (unsigned)std::min<int64_t>((N + 3) / 4, (int64_t)h->n_cu * 8);
-    hipLaunchKernelGGL(enkf_update_kernel, dim3(blocks), dim3(256), 0, h->stream, h->psi.p, h->enkf_y.p, h->enkf_gain.p,
-                       h->Pdev.p, (long long)N, (long long)mpp, (int)D, dz, z_obs, h->enkf_sigma,
-                       (unsigned long long)h->enkf_seed, P > 1 ? h->point_base.p : nullptr, (long long)h->member_offset,
-                       (unsigned)row, h->enkf_eps.p, h->enkf_ypost.p, h->enkf_rej.p);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(enkf_ystats_kernel, dim3((unsigned)P), dim3(ENKF_THREADS), 0, h->stream, h->enkf_ypost.p,
-                       h->enkf_rej.p, (long long)mpp, h->enkf_ys.p, st, (long long)n_arow, (long long)slot);
-    HIP_TRY(hipGetLastError());
-    h->enkf_done = true;
-    return HC_OK;
-}
-
-// The sensors with a value on `row`, in record order
-SmRow sm_row(const hc_handle *h, int64_t row)
-{
-    SmRow s{};
-    s.n = h->sm_n;
+    EnkfRow s{};
     for (int i = 0; i < h->sm_n; i++) {
         const double v = h->sm_values[(size_t)row * h->sm_n + i];
         if (std::isnan(v)) continue;
@@ -2709,84 +2498,94 @@ SmRow sm_row(const hc_handle *h, int64_t row)
         s.sigma[s.m] = h->sm_sigma[(size_t)i];
         s.m++;
     }
+    s.n = s.m > 0 ? h->sm_n : 0;
     return s;
 }
 
-// The batch analysis of a row with sensor values (m' = 1 + s.m observations per member), in place on psi: y and theta
-// per member; per point the column and observation sums, then the anomaly products (two passes over psi); the gain and
-// the prior diagnostics; the update with eps and the posterior (y, theta, rejected) per member (one read + write of psi);
-// the posterior sums and diagnostics.
-int enkf_analyse_sm(hc_handle *h, const Chunk &c, const SmRow &s)
+// The EnKF's analysis at the launch's last row (its water-table indices are wtd_u16's last row), m' = 1 + s.m
+// observations per member, in place on psi: y and theta per member; per point the column and observation sums, then the
+// anomaly products (two passes over psi); the gain and the prior diagnostics; the update with eps and the posterior (y,
+// theta, rejected) per member (one read + write of psi); the posterior sums and diagnostics.  Scratch is sized by the
+// record's largest m', 1 + sm_n.
+int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
 {
     const int64_t N = h->n_members, D = h->p.dim_d, P = h->n_points, mpp = N / P;
     const int64_t row = c.row0 + c.rows - 1, slot = row / h->enkf_stride, n_arow = enkf_rows(h);
     const int64_t n_tiles = (mpp + ENKF_TILE - 1) / ENKF_TILE;
     const int W = s.m + 1, V = W + 1;
-    const int64_t C = D + W;
-    if (h->enkf_y.ensure((size_t)N) || h->enkf_eps.ensure((size_t)N) || h->enkf_gain.ensure((size_t)(P * D)) ||
-        h->sm_Y.ensure((size_t)(N * SM_OBS)) || h->sm_Ypost.ensure((size_t)(N * (SM_OBS + 1))) ||
-        h->sm_eps.ensure((size_t)(N * SM_MAX)) || h->sm_gain.ensure((size_t)(P * D * SM_OBS)) ||
-        h->sm_s1.ensure((size_t)(P * (HC_MAX_DEPTH_NODES + SM_OBS))) ||
-        h->sm_s2.ensure((size_t)(P * (HC_MAX_DEPTH_NODES + SM_OBS) * SM_OBS)) ||
-        h->sm_part.ensure((size_t)(P * n_tiles * (HC_MAX_DEPTH_NODES + SM_OBS) * SM_OBS)))
+    const int64_t C = D + W, Wx = 1 + h->sm_n, Cx = D + Wx;
+    const int64_t cols_x = std::max(Cx * Wx, (Wx + 1) * (Wx + 1));   // the widest pass: the prior products or the posterior's
+    if (h->enkf_Y.ensure((size_t)(N * Wx)) || h->enkf_eps.ensure((size_t)N) ||
+        h->enkf_eps_s.ensure((size_t)(N * h->sm_n)) || h->enkf_Ypost.ensure((size_t)(N * (Wx + 1))) ||
+        h->enkf_gain.ensure((size_t)(P * Wx * D)) || h->enkf_s1.ensure((size_t)(P * Cx)) ||
+        h->enkf_s2.ensure((size_t)(P * cols_x)) || h->enkf_part.ensure((size_t)(P * n_tiles * cols_x)))
         return HC_ERR_DEVICE;
     const unsigned short *w = h->wtd_u16.p + (size_t)(c.rows - 1) * N;
     const double dz = h->p.dz, z_obs = (double)h->h_wtd_obs[(size_t)row] * dz;
     const int special = (int)h->use_special();
     const long long ll_mpp = (long long)mpp, ll_tiles = (long long)n_tiles;
-    hipLaunchKernelGGL(enkf_obs_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, w, h->psi.p, h->Pdev.p,
-                       (long long)N, ll_mpp, (int)D, dz, h->enkf_y.p);
+    const dim3 members((unsigned)((N + 255) / 256));
+    hipLaunchKernelGGL(enkf_obs_kernel, members, dim3(256), 0, h->stream, w, h->psi.p, h->Pdev.p, (long long)N, ll_mpp,
+                       (int)D, dz, h->enkf_Y.p, W);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(sm_obs_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, h->psi.p, h->enkf_y.p,
-                       h->Pdev.p, h->node_tabs.p, special, (long long)N, ll_mpp, (int)D, s, h->sm_Y.p, W);
-    HIP_TRY(hipGetLastError());
+    if (s.m > 0) {
+        hipLaunchKernelGGL(enkf_theta_kernel, members, dim3(256), 0, h->stream, h->psi.p, h->Pdev.p, h->node_tabs.p, special,
+                           (long long)N, ll_mpp, (int)D, s, h->enkf_Y.p, W);
+        HIP_TRY(hipGetLastError());
+    }
     // prior: the sums of (psi, Y), then the products of their anomalies with Y's
     const dim3 tiles((unsigned)n_tiles, (unsigned)P);
     const dim3 cols_prior((unsigned)((C + WAVE - 1) / WAVE * WAVE)), cols_post((unsigned)WAVE);
-    hipLaunchKernelGGL(sm_partial_kernel, tiles, cols_prior, 0, h->stream, h->psi.p, h->sm_Y.p, W, nullptr, ll_mpp,
-                       (int)D, ll_tiles, h->sm_part.p);
+    hipLaunchKernelGGL(enkf_partial_kernel, tiles, cols_prior, 0, h->stream, h->psi.p, h->enkf_Y.p, W, nullptr, ll_mpp,
+                       (int)D, ll_tiles, h->enkf_part.p);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(sm_finish_kernel, dim3((unsigned)C, (unsigned)P), dim3(ENKF_THREADS), 0, h->stream, h->sm_part.p,
-                       ll_tiles, (int)C, h->sm_s1.p);
+    hipLaunchKernelGGL(enkf_finish_kernel, dim3((unsigned)C, (unsigned)P), dim3(ENKF_THREADS), 0, h->stream,
+                       h->enkf_part.p, ll_tiles, (int)C, h->enkf_s1.p);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(sm_partial_kernel, tiles, cols_prior, 0, h->stream, h->psi.p, h->sm_Y.p, W, h->sm_s1.p, ll_mpp,
-                       (int)D, ll_tiles, h->sm_part.p);
+    hipLaunchKernelGGL(enkf_partial_kernel, tiles, cols_prior, 0, h->stream, h->psi.p, h->enkf_Y.p, W, h->enkf_s1.p,
+                       ll_mpp, (int)D, ll_tiles, h->enkf_part.p);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(sm_finish_kernel, dim3((unsigned)(C * W), (unsigned)P), dim3(ENKF_THREADS), 0, h->stream,
-                       h->sm_part.p, ll_tiles, (int)(C * W), h->sm_s2.p);
+    hipLaunchKernelGGL(enkf_finish_kernel, dim3((unsigned)(C * W), (unsigned)P), dim3(ENKF_THREADS), 0, h->stream,
+                       h->enkf_part.p, ll_tiles, (int)(C * W), h->enkf_s2.p);
     HIP_TRY(hipGetLastError());
     double *st = h->enkf.buf.p, *sst = h->sm.buf.p;
-    hipLaunchKernelGGL(sm_gain_kernel, dim3((unsigned)P), dim3((unsigned)((D + WAVE - 1) / WAVE * WAVE)), 0, h->stream,
-                       h->sm_s1.p, h->sm_s2.p, ll_mpp, (int)D, s, h->enkf_sigma, h->enkf_loc, z_obs, dz, h->sm_gain.p,
+    hipLaunchKernelGGL(enkf_gain_kernel, dim3((unsigned)P), dim3((unsigned)((D + WAVE - 1) / WAVE * WAVE)), 0, h->stream,
+                       h->enkf_s1.p, h->enkf_s2.p, ll_mpp, (int)D, s, h->enkf_sigma, h->enkf_loc, z_obs, dz,
                        h->enkf_gain.p, st, sst, (long long)n_arow, (long long)slot);
     HIP_TRY(hipGetLastError());
-    const unsigned blocks = (unsigned)std::min<int64_t>((N + 3) / 4, (int64_t)h->n_cu * 8);
-    hipLaunchKernelGGL(sm_update_kernel, dim3(blocks), dim3(256), 0, h->stream, h->psi.p, h->sm_Y.p, h->sm_gain.p,
-                       h->Pdev.p, (long long)N, ll_mpp, (int)D, dz, z_obs, h->enkf_sigma, s,
+    hipLaunchKernelGGL(enkf_draw_kernel, members, dim3(256), 0, h->stream, (long long)N, ll_mpp,
                        (unsigned long long)h->enkf_seed, P > 1 ? h->point_base.p : nullptr, (long long)h->member_offset,
-                       (unsigned)row, h->enkf_eps.p, h->sm_eps.p, h->sm_Ypost.p);
+                       (unsigned)row, s.n, h->enkf_eps.p, h->enkf_eps_s.p);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(sm_obs_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, h->psi.p, nullptr,
-                       h->Pdev.p, h->node_tabs.p, special, (long long)N, ll_mpp, (int)D, s, h->sm_Ypost.p, V);
+    const unsigned blocks = (unsigned)std::min<int64_t>((N + 3) / 4, (int64_t)h->n_cu * 8);
+    hipLaunchKernelGGL(enkf_update_kernel, dim3(blocks), dim3(256), 0, h->stream, h->psi.p, h->enkf_Y.p, h->enkf_gain.p,
+                       h->Pdev.p, (long long)N, ll_mpp, (int)D, dz, z_obs, h->enkf_sigma, s, h->enkf_eps.p,
+                       h->enkf_eps_s.p, h->enkf_Ypost.p);
     HIP_TRY(hipGetLastError());
+    if (s.m > 0) {
+        hipLaunchKernelGGL(enkf_theta_kernel, members, dim3(256), 0, h->stream, h->psi.p, h->Pdev.p, h->node_tabs.p, special,
+                           (long long)N, ll_mpp, (int)D, s, h->enkf_Ypost.p, V);
+        HIP_TRY(hipGetLastError());
+    }
     // posterior: the same two passes over (y, theta, rejected) alone
-    hipLaunchKernelGGL(sm_partial_kernel, tiles, cols_post, 0, h->stream, nullptr, h->sm_Ypost.p, V, nullptr, ll_mpp, 0,
-                       ll_tiles, h->sm_part.p);
+    hipLaunchKernelGGL(enkf_partial_kernel, tiles, cols_post, 0, h->stream, nullptr, h->enkf_Ypost.p, V, nullptr, ll_mpp,
+                       0, ll_tiles, h->enkf_part.p);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(sm_finish_kernel, dim3((unsigned)V, (unsigned)P), dim3(ENKF_THREADS), 0, h->stream, h->sm_part.p,
-                       ll_tiles, V, h->sm_s1.p);
+    hipLaunchKernelGGL(enkf_finish_kernel, dim3((unsigned)V, (unsigned)P), dim3(ENKF_THREADS), 0, h->stream,
+                       h->enkf_part.p, ll_tiles, V, h->enkf_s1.p);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(sm_partial_kernel, tiles, cols_post, 0, h->stream, nullptr, h->sm_Ypost.p, V, h->sm_s1.p, ll_mpp,
-                       0, ll_tiles, h->sm_part.p);
+    hipLaunchKernelGGL(enkf_partial_kernel, tiles, cols_post, 0, h->stream, nullptr, h->enkf_Ypost.p, V, h->enkf_s1.p,
+                       ll_mpp, 0, ll_tiles, h->enkf_part.p);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(sm_finish_kernel, dim3((unsigned)(V * V), (unsigned)P), dim3(ENKF_THREADS), 0, h->stream,
-                       h->sm_part.p, ll_tiles, V * V, h->sm_s2.p);
+    hipLaunchKernelGGL(enkf_finish_kernel, dim3((unsigned)(V * V), (unsigned)P), dim3(ENKF_THREADS), 0, h->stream,
+                       h->enkf_part.p, ll_tiles, V * V, h->enkf_s2.p);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(sm_post_kernel, dim3((unsigned)((P + 63) / 64)), dim3(64), 0, h->stream, h->sm_s1.p, h->sm_s2.p,
-                       (long long)P, ll_mpp, s, st, sst, (long long)n_arow, (long long)slot);
+    hipLaunchKernelGGL(enkf_post_kernel, dim3((unsigned)((P + 63) / 64)), dim3(64), 0, h->stream, h->enkf_s1.p,
+                       h->enkf_s2.p, (long long)P, ll_mpp, s, st, sst, (long long)n_arow, (long long)slot);
     HIP_TRY(hipGetLastError());
     h->enkf_done = true;
-    h->sm_width = W;
+    h->enkf_width = W;
+    h->sm_width = s.m > 0 ? W : 0;
     return HC_OK;
 }
 
@@ -2847,10 +2646,9 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
         if ((rc = accumulate(h, A, a, c, prof_on, hist_on))) return rc;
         if ((rc = copy_outputs(h, a, c, done))) return rc;
         if (filt_on && is_assimilation_row(h, c.row0 + c.rows - 1) && (rc = assimilate(h, c))) return rc;
-        if (enkf_on && is_assimilation_row(h, c.row0 + c.rows - 1)) {
-            const SmRow s = h->sm_n > 0 ? sm_row(h, c.row0 + c.rows - 1) : SmRow{};
-            if ((rc = s.m > 0 ? enkf_analyse_sm(h, c, s) : enkf_analyse(h, c))) return rc;
-        }
+        if (enkf_on && is_assimilation_row(h, c.row0 + c.rows - 1) &&
+            (rc = enkf_analyse(h, c, enkf_row(h, c.row0 + c.rows - 1))))
+            return rc;
         HIP_TRY(hipStreamSynchronize(h->stream));
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
@@ -3261,38 +3059,48 @@ int hc_set_enkf_stats(hc_handle *h, const double *table, int64_t n_entries)
                       "hc_set_enkf_stats");
 }
 
-// the last analysis's buffers (test hooks)
-static int enkf_hook(hc_handle *h, const double *src, double *out, size_t count, const char *who)
+// the last analysis's buffers (test hooks): `rows` rows of `len` doubles, `pitch` apart on the device
+static int enkf_hook(hc_handle *h, const double *src, double *out, size_t rows, size_t len, size_t pitch, const char *who)
 {
     if (!h || !out) return fail(HC_ERR_ARG, "%s: bad argument", who);
     if (h->enkf_stride <= 0 || !h->enkf_done) return fail(HC_ERR_ARG, "%s: no analysis since hc_set_enkf", who);
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(out, src, count * 8, hipMemcpyDeviceToHost));
+    if (pitch == len) {
+        HIP_TRY(hipMemcpy(out, src, rows * len * 8, hipMemcpyDeviceToHost));
+        return HC_OK;
+    }
+    std::vector<double> all((rows - 1) * pitch + len);
+    HIP_TRY(hipMemcpy(all.data(), src, all.size() * 8, hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < rows; r++) std::copy_n(all.data() + r * pitch, len, out + r * len);
     return HC_OK;
 }
 
+// the well's column of the gain [P][m'][D] and of Y [N][m']
 int hc_get_enkf_gain(hc_handle *h, double *gain)
 {
-    return enkf_hook(h, h ? h->enkf_gain.p : nullptr, gain, h ? (size_t)h->n_points * h->p.dim_d : 0, "hc_get_enkf_gain");
+    const size_t P = h ? (size_t)h->n_points : 0, D = h ? (size_t)h->p.dim_d : 0;
+    return enkf_hook(h, h ? h->enkf_gain.p : nullptr, gain, P, D, h ? h->enkf_width * D : 0, "hc_get_enkf_gain");
 }
 
 int hc_get_enkf_y(hc_handle *h, double *y)
 {
-    return enkf_hook(h, h ? h->enkf_y.p : nullptr, y, h ? (size_t)h->n_members : 0, "hc_get_enkf_y");
+    return enkf_hook(h, h ? h->enkf_Y.p : nullptr, y, h ? (size_t)h->n_members : 0, 1, h ? h->enkf_width : 0,
+                     "hc_get_enkf_y");
 }
 
 int hc_get_enkf_eps(hc_handle *h, double *eps)
 {
-    return enkf_hook(h, h ? h->enkf_eps.p : nullptr, eps, h ? (size_t)h->n_members : 0, "hc_get_enkf_eps");
+    return enkf_hook(h, h ? h->enkf_eps.p : nullptr, eps, 1, h ? (size_t)h->n_members : 0, h ? (size_t)h->n_members : 0,
+                     "hc_get_enkf_eps");
 }
 
 int hc_set_enkf_soil_moisture(hc_handle *h, int32_t n_sensors, const int32_t *nodes, const double *values,
                               const double *sigma)
 {
     if (!h || n_sensors < 0) return fail(HC_ERR_ARG, "hc_set_enkf_soil_moisture: bad argument");
-    if (n_sensors > SM_MAX)
-        return fail(HC_ERR_ARG, "hc_set_enkf_soil_moisture: %d sensors, at most %d", (int)n_sensors, SM_MAX);
+    if (n_sensors > ENKF_SENSORS)
+        return fail(HC_ERR_ARG, "hc_set_enkf_soil_moisture: %d sensors, at most %d", (int)n_sensors, ENKF_SENSORS);
     if (n_sensors > 0 && h->filt_stride > 0)
         return fail(HC_ERR_ARG, "hc_set_enkf_soil_moisture: the particle filter is on");
     if (n_sensors > 0 && h->enkf_stride <= 0)
@@ -3345,30 +3153,40 @@ int hc_get_enkf_sm_width(hc_handle *h, int32_t *width)
 }
 
 // the last analysis's buffers when it had sensor values (test hooks)
-static int sm_hook(hc_handle *h, const double *src, double *out, size_t count, const char *who)
+static int sm_check(hc_handle *h, const double *out, const char *who)
 {
     if (!h || !out) return fail(HC_ERR_ARG, "%s: bad argument", who);
     if (h->sm_n <= 0 || h->sm_width <= 0) return fail(HC_ERR_ARG, "%s: the last analysis had no sensor value", who);
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(out, src, count * 8, hipMemcpyDeviceToHost));
     return HC_OK;
+}
+
+static int sm_hook(hc_handle *h, const double *src, double *out, size_t count, const char *who)
+{
+    if (int rc = sm_check(h, out, who)) return rc;
+    return enkf_hook(h, src, out, 1, count, count, who);
 }
 
 int hc_get_enkf_sm_y(hc_handle *h, double *y)
 {
-    return sm_hook(h, h ? h->sm_Y.p : nullptr, y, h ? (size_t)h->n_members * h->sm_width : 0, "hc_get_enkf_sm_y");
+    return sm_hook(h, h ? h->enkf_Y.p : nullptr, y, h ? (size_t)h->n_members * h->sm_width : 0, "hc_get_enkf_sm_y");
 }
 
+// the gain is [P][m'][D] on the device, [P][D][m'] at the C-ABI
 int hc_get_enkf_sm_gain(hc_handle *h, double *gain)
 {
-    return sm_hook(h, h ? h->sm_gain.p : nullptr, gain, h ? (size_t)h->n_points * h->p.dim_d * h->sm_width : 0,
-                   "hc_get_enkf_sm_gain");
+    if (int rc = sm_check(h, gain, "hc_get_enkf_sm_gain")) return rc;
+    const size_t P = (size_t)h->n_points, D = (size_t)h->p.dim_d, W = (size_t)h->sm_width;
+    std::vector<double> k(P * W * D);
+    if (int rc = enkf_hook(h, h->enkf_gain.p, k.data(), 1, k.size(), k.size(), "hc_get_enkf_sm_gain")) return rc;
+    for (size_t p = 0; p < P; p++)
+        for (size_t i = 0; i < W; i++)
+            for (size_t d = 0; d < D; d++) gain[(p * D + d) * W + i] = k[(p * W + i) * D + d];
+    return HC_OK;
 }
 
 int hc_get_enkf_sm_eps(hc_handle *h, double *eps)
 {
-    return sm_hook(h, h ? h->sm_eps.p : nullptr, eps, h ? (size_t)h->n_members * h->sm_n : 0, "hc_get_enkf_sm_eps");
+    return sm_hook(h, h ? h->enkf_eps_s.p : nullptr, eps, h ? (size_t)h->n_members * h->sm_n : 0, "hc_get_enkf_sm_eps");
 }
 
 // The path's one collective without torch: a single process that drives several devices (one handle each) sums the

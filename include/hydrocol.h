@@ -393,10 +393,10 @@ int hc_get_filter_draw(hc_handle *h, int64_t *r);
  *     K_d = rho_d c_d / (v + sigma_cm^2);  psi_dk <- psi_dk + K_d (o_k - y_k) on all D nodes.
  *   A member whose updated column has a non-finite entry keeps its forecast and is counted as rejected.  Base noise
  *   vectors, noise scales and draw counters are not touched (no caller-noise path: Philox runs keep their in-kernel noise).
- *   Reproducibility: every sum over a point's members runs in an order fixed by N_p alone (the column sums in tiles of 256
- *   members in member order, then the tile partials by 1024 threads in tile-strided order and a fixed tree; the sums of y
- *   by 1024 threads in member-strided order and the same tree), no floating-point atomics: the analysis is the same to the bit at any launch length, point order, dealing of a
- *   sweep's points to handles or ranks, and from run to run.
+ *   Reproducibility: every sum over a point's members runs in an order fixed by N_p alone (tiles of 256 members in member
+ *   order, then the tile partials by 1024 threads in tile-strided order and a fixed tree, for the columns and y alike), no
+ *   floating-point atomics: the analysis is the same to the bit at any launch length, point order, dealing of a sweep's
+ *   points to handles or ranks, and from run to run.
  *   Diagnostics, float64 [P][n_arow][8] per point and slot: count = N_p; prior mean ybar (cm from z[0]); prior std sqrt(v)
  *   (cm); innovation z[o] - ybar (cm); log-likelihood increment -0.5 log(2 pi (v + sigma^2)) - 0.5 (z[o] - ybar)^2 /
  *   (v + sigma^2) (log cm^-1, the particle filter's unit); posterior mean and std of y (the same operator and sums on the
@@ -420,7 +420,7 @@ int hc_get_enkf_eps(hc_handle *h, double *eps);
  * well on the analysis rows of hc_set_enkf (the rows themselves do not change: r >= 1, r % stride == 0, wtd_obs[r] >= 0).
  *   values [n_forcing_rows][n_sensors] (m^3/m^3, in [0, 1]; NaN = no observation), nodes [n_sensors] in [0, D), sigma
  *   [n_sensors] the sensors' error standard deviations (finite, > 0).
- *   A row with no sensor value runs the scalar analysis of hc_set_enkf unchanged (an all-NaN record: the well-only run to
+ *   A row with no sensor value runs the m' = 1 case, the analysis of hc_set_enkf (an all-NaN record: the well-only run to
  *   the bit).  A row with m_s >= 1 sensor values runs one batch update per point of m' = 1 + m_s observations, in a fixed
  *   order: the well, then the present sensors in record order.
  *   Observations per member: Y_k = (y_k, theta_k[j_1], ...): y_k the water table of hc_set_enkf; theta_k[j] the cell model
@@ -446,7 +446,7 @@ int hc_get_enkf_eps(hc_handle *h, double *eps);
  *   log cm^-1 (m^3/m^3)^-m_s.
  *   Sensor diagnostics, float64 [P][n_arow][n_sensors][6]: observed (0/1), observation, prior mean and std of theta, posterior
  *   mean and std of theta (the analysis states, rejected members at their forecast).  A sensor without a value on an analysed
- *   row: observed = 0, the rest NaN; every entry of a slot without a joint analysis (none, or the scalar path): NaN.
+ *   row: observed = 0, the rest NaN; every entry of a slot without a joint analysis (none, or no sensor value on the row): NaN.
  * hc_set_enkf_soil_moisture: n_sensors = 0 removes the record; otherwise (re)creates the table (NaN).  Needs the EnKF on
  *   (hc_set_enkf first); HC_ERR_ARG while the particle filter is on.  Turned off by whatever turns the EnKF off (hc_set_enkf
  *   included).  hc_step_rows refuses while the record's row count differs from the forcing's.

@@ -144,8 +144,8 @@ def test_an_all_nan_record_is_the_well_only_run():
 def test_sensors_of_huge_error_give_the_well_only_analysis():
     """sigma_i = 1e6 after ONE analysis.  The sensors' columns of the gain are K_di ~ c_{d,theta_i} / sigma_i^2 and their
     innovations ~ sigma_i eps_i, so their share of the increment is at most sum_i sd(psi_d) sd(theta_i) |eps_i| / sigma_i
-    (|corr| <= 1), and their effect on the well's column is smaller still, O(sd(theta)^2 / sigma_i^2).  The joint path sums
-    in other orders than the scalar one: 1e-9 relative on top covers that rounding.  The tolerance per node is
+    (|corr| <= 1), and their effect on the well's column is smaller still, O(sd(theta)^2 / sigma_i^2).  The well-only run
+    solves an m' = 1 system, this one an m' = 4 system: 1e-9 relative on top covers that rounding.  The tolerance per node is
     2 sum_i sd(psi_d) sd(theta_i) max_k |eps_ki| / sigma_i + 1e-9 (1 + |psi|)."""
     N, well, big = 200, 1, 1.0e6
     ref = _run(well, N, 48, hist=False)
@@ -186,7 +186,7 @@ def _point_handle(ids, rows_per_launch=0):
         st.set_wtd_hist(48)
         st.set_enkf(24, 2.0 * st.cols.dz, 40.0, 9)
         v = _record(st.T, [8, 30], [0.22, 0.26], rows=(24, 72, 120))
-        v[48] = [0.2, np.nan]                                   # one sensor; 96, 144: the scalar path
+        v[48] = [0.2, np.nan]                                   # one sensor; 96, 144: the well alone (m' = 1)
         st.set_enkf_soil_moisture([8, 30], v, [0.02, 0.03])
         st.step_rows(1, 150)
         n = len(ids)

@@ -1,17 +1,23 @@
-"""What soil-moisture sensors add to the ensemble Kalman filter (hc_set_enkf_soil_moisture): column-days/s of the
-bench-size ensemble without the EnKF, with the well-only EnKF, and with the well plus sensors every 48th row (one
-analysis a day), one handle each, back to back on one GPU.
+"""What the ensemble Kalman filter costs (hc_set_enkf, hc_set_enkf_soil_moisture): column-days/s of the bench-size
+ensemble without the EnKF, with the well-only EnKF, and with the well plus sensors every 48th row (one analysis a day),
+one handle each, back to back on one GPU.
 
     python tools/enkf_sm_cost.py [--members 262144] [--depth 300] [--days 30] [--warmup 1] [--runs 0,48s,0,48s]
-                                 [--sensors 30,60,120] [--sigma 10] [--sm-sigma 0.02] [--localisation 0] [--json out.json]
+                                 [--sensors 30,60,120] [--sigma 10] [--sm-sigma 0.02] [--localisation 0] [--spread-cm 0]
+                                 [--json out.json]
 
-The set-up of tools/enkf_cost.py: synthetic 10-year forcing, Philox noise, the shared initial condition of the well's
-digest, W warm-up days, then K timed days, the library's own launch length; the timed figure is wall time around
-hc_step_rows.  A run is a stride (0: no EnKF, 48: the well alone) or a stride with the suffix "s" (the well and the
-sensors at --sensors cm, every sensor observed on every analysis row: theta of the initial profile at its node, held
-fixed -- the cost does not depend on the values).  `sm_ms_per_analysis` is a sensor run's `other_ms` over the plain
-runs', per analysis; `kept` is a run's rate over the mean of the stride-0 runs.  Under `rocprofv3 --kernel-trace --stats`
-run it with --runs 48s --days 1 --warmup 0 for the per-kernel time of the analyses.  Prints one JSON line.
+Same set-up as tools/filter_cost.py and bench.py's timed region: synthetic 10-year forcing, Philox noise, the shared
+initial condition of the well's digest (tests/golden/g1_tables_<depth>.npz where it exists, else the hydrostatic profile),
+W warm-up days, then K timed days, the library's own launch length.  The timed figure is wall time around hc_step_rows:
+the step launches AND everything behind them -- with the EnKF, the observation, reduction, gain and update kernels.
+`step_kernel_ms` is the step kernel alone (HIP events around its launches), so `other_ms` = wall - step kernel is what the
+rest costs; `enkf_ms_per_analysis` (well-only runs) and `sm_ms_per_analysis` (sensor runs) are a run's `other_ms` over the
+stride-0 runs', per analysis.  A run is a stride (0: no EnKF, 48: the well alone) or a stride with the suffix "s" (the
+well and the sensors at --sensors cm, every sensor observed on every analysis row: theta of the initial profile at its
+node, held fixed -- the cost does not depend on the values); a run may be listed more than once (e.g. 0,48,0,48 to
+alternate); `kept` is a run's rate over the mean of the stride-0 runs.  --spread-cm W starts every member from the
+initial profile shifted by its own offset, uniform over +-W cm.  Under `rocprofv3 --kernel-trace --stats` run it with
+--runs 48s (or 48) --days 1 --warmup 0 for the per-kernel time of the analyses.  Prints one JSON line.
 """
 import argparse
 import json
