@@ -18,11 +18,14 @@ all-reduce of the per-row water-table moments over RCCL -- runs after the timed 
 round-robin ("strong" scaling: the grid is fixed), all of a rank's points advance in ONE launch per day.
 
 Prints ONE JSON line (rank 0).  roofline.achieved uses the algorithmic bytes of SURVEY.md §8d, (16*D + 16) B per
-column-step, over the step kernel's mean launch duration measured with HIP events on the library's stream.  More legs
-run AFTER the timed region on rank 0 of a one-GPU ensemble run: `sustained` -- 16 384 members through the first 365 days
-of the same (10-year, quiet) digest; `sustained_heavy` -- 16 384 members through the whole 1-YEAR forcing, ten times the
-evapo-transpiration per row, the regime with failed BDF attempts; `cpu_baseline` -- the C oracle (oracle/, a port of the
-same algorithm) on every host core this process may use, for >= 30 s.
+column-step, over the step kernel's mean launch duration measured with HIP events on the library's stream.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.  --full adds
+the legs that take runs of their own, AFTER the timed region on rank 0 of a one-GPU ensemble run (each can be left out
+with its --no-* option): `sustained` -- 65 536 members through the first 365 days of the same (10-year, quiet) digest;
+`sustained_heavy` -- 65 536 members through 120 days of the 1-YEAR forcing, ten times the evapo-transpiration per row,
+the regime with failed BDF attempts; `n1e6` -- 1 048 576 members in one handle; `cpu_baseline` -- the C oracle (oracle/,
+a port of the same algorithm) on every host core this process may use, for >= 30 s.  Without --full they are null.
 
 --dump-outputs DIR writes what the last timed step computed (member states, water-table statistics of its rows) as
 DIR/<name>.npy in float64, read after the timed region (`dump_outputs`).  The inputs depend on the arguments alone
@@ -79,7 +82,7 @@ def pmc_constants(depth, model):
     return rec, rec["source"]
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None,
@@ -92,6 +95,9 @@ def parse():
     ap.add_argument("--years", type=int, default=None, help="forcing length (default: 10 for the ensemble, 1 for the sweep)")
     ap.add_argument("--points", type=int, default=512, help="sweep: grid points, a cube (n x a0 x psi_sat)")
     ap.add_argument("--seed", type=int, default=2024)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the sustained, sustained_heavy, n1e6 and cpu_baseline legs "
+                         "(rank 0 of a one-GPU ensemble run; the --no-* options below leave single legs out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=30.0, help="wall time of the CPU leg (BASELINE.md §3: >= 30 s)")
     ap.add_argument("--no-sustained", action="store_true")
@@ -111,7 +117,7 @@ def parse():
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float64): "
                          "the states of a fixed, seeded sample of members and the water-table statistics of its rows")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps is not None and args.steps < 1:
         ap.error("--steps must be >= 1")
     if args.warmup < 0:
@@ -591,7 +597,7 @@ def run_ensemble(args, rank, world, dev, dist):
         if world > 1:
             dist.destroy_process_group()
         raise SystemExit(f"the reduced moment table counts {members_seen} members, expected {N} x {world}")
-    solo = rank == 0 and world == 1
+    solo = rank == 0 and world == 1 and args.full
     out["sustained"] = (sustained_leg(cols, forcing, psi0, args.sustained_members, args.sustained_days, args.seed,
                                       local_rank, f"the same {args.years}-year digest")
                         if solo and not args.no_sustained else None)

@@ -78,3 +78,10 @@ def test_dump_of_a_sweep_keeps_the_points(tmp_path):
 def test_steps_below_one_are_refused():
     p = subprocess.run([sys.executable, "bench.py", "--steps", "0"], cwd=REPO, capture_output=True, text=True, timeout=120)
     assert p.returncode != 0 and "--steps must be >= 1" in p.stderr
+
+
+def test_the_extra_legs_wait_for_full():
+    """A plain run is the headline alone; --full asks for the legs after it."""
+    import bench
+    assert bench.parse([]).full is False
+    assert bench.parse(["--full"]).full is True

@@ -22,7 +22,7 @@ def _run(cmd, timeout=600):
 
 
 def test_bench_contract_one_rank():
-    out = _run([sys.executable, "bench.py", "--members", "4096", "--steps", "2", "--warmup", "1", "--cpu-seconds", "4",
+    out = _run([sys.executable, "bench.py", "--full", "--members", "4096", "--steps", "2", "--warmup", "1", "--cpu-seconds", "4",
                 "--sustained-members", "2048", "--sustained-days", "3", "--heavy-members", "1024", "--heavy-days", "2",
                 "--n1e6-members", "8192", "--n1e6-days", "2"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -73,6 +73,18 @@ def test_bench_contract_one_rank():
     assert su["unit"] == "column-days/s" and su["members"] == 2048 and su["days"] == 3 and su["value"] > 1e3
     assert su["failed_attempts"] >= 0 and su["guard_trips"] >= 0 and 1 <= su["launches"] <= 3
     assert out["value"] / c["value"] > 10            # a reported baseline, not a target -- but it must be the same unit
+
+
+def test_bench_plain_run_is_the_headline_alone():
+    """Without --full the line carries the headline and what the timed steps measured; the legs that take runs of their
+    own (sustained, sustained_heavy, n1e6, cpu_baseline) are not run and say so with null."""
+    out = _run([sys.executable, "bench.py", "--members", "4096", "--steps", "2", "--warmup", "1"])
+    assert out["metric"] == "ensemble column-days/sec" and out["unit"] == "column-days/s" and out["dtype"] == "f64"
+    assert out["higher_is_better"] is True and out["steps"] == 2 and out["warmup"] == 1 and out["value"] > 1e4
+    assert abs(out["value"] - 4096 / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"]
+    assert out["roofline"]["launches"] == 2 and out["members_in_reduced_moments"] == 4096
+    for key in ("sustained", "sustained_heavy", "n1e6", "cpu_baseline"):
+        assert key in out and out[key] is None, key
 
 
 def test_bench_two_ranks_share_the_moments():

@@ -11,7 +11,7 @@ export HC_PROF_MEMBERS=32768
 bash tools/dev/ab_depths.sh $OUT/ab_alias.txt "241 300 361" hydromodel_amd/csrc/libhydrocol.so tools/dev/_ab/lib_r5j.so tools/dev/_ab/lib_r5j0.so > /dev/null 2>&1
 cat $OUT/ab_alias.txt
 timeout -k 10 300 python3 tools/prof_phases.py tools/dev/_ab/lib_prof_two.so 8192 > $OUT/phases_d300.txt 2>&1; cat $OUT/phases_d300.txt
-timeout -k 10 900 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc $?"; python3 -c "
+timeout -k 10 900 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc $?"; python3 -c "
 import json
 d=json.load(open('$OUT/bench.json'))
 print({k:d[k] for k in ('value','ms_per_step')})

@@ -9,7 +9,7 @@ echo "== config 2 (4 096 members x D = 200, the year): rows per launch 768 (toda
 timeout -k 10 300 python3 tools/dev/cfg2_bench.py 768 1536 3072 6144
 for rpl in 48 192 768; do
   echo "== 65 536 members x D = 300 x 120 days of the 1-year forcing, HYDROCOL_ROWS_PER_LAUNCH=$rpl"
-  HYDROCOL_ROWS_PER_LAUNCH=$rpl timeout -k 10 300 python3 bench.py --no-sustained --no-n1e6 --no-cpu-baseline --steps 2 --members 4096 2>/dev/null | python3 -c "
+  HYDROCOL_ROWS_PER_LAUNCH=$rpl timeout -k 10 300 python3 bench.py --full --no-sustained --no-n1e6 --no-cpu-baseline --steps 2 --members 4096 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); h=d.get('sustained_heavy'); print('sustained_heavy', h and round(h['value']), h and h.get('launches'))"
 done

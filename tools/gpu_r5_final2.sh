@@ -6,7 +6,7 @@ OUT=$ROOT/gpurun_out/${1:-r5j2}
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd $ROOT
-timeout -k 10 900 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc $?"
+timeout -k 10 900 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc $?"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python3 bench.py --no-sustained --no-heavy --no-n1e6 --no-cpu-baseline > $OUT/bench_kt.json 2> $OUT/bench_kt.err; echo "bench under rocprofv3 rc $?"
 timeout -k 10 600 python3 bench.py --workload sweep > $OUT/bench_sweep.json 2> $OUT/bench_sweep.err; echo "sweep rc $?"
 timeout -k 10 300 python3 tools/prof_phases.py tools/dev/_ab/lib_prof_two.so 8192 > $OUT/phases_d300.txt 2>&1

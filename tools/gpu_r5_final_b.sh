@@ -7,7 +7,7 @@ mkdir -p $OUT
 cd $ROOT
 export TMPDIR=/tmp
 timeout -k 10 900 python3 -m pytest tests -m gpu -q > $OUT/pytest.log 2>&1; echo "pytest rc $?"; tail -3 $OUT/pytest.log
-timeout -k 10 900 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc $?"
+timeout -k 10 900 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc $?"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python3 bench.py --no-sustained --no-heavy --no-n1e6 --no-cpu-baseline > $OUT/bench_kt.json 2> $OUT/bench_kt.err; echo "bench under rocprofv3 rc $?"
 timeout -k 10 300 python3 tools/dev/cfg2_bench.py 0 48 17472 > $OUT/cfg2.json 2>&1; cat $OUT/cfg2.json
 timeout -k 10 400 python3 tools/soak.py 65536 300 1 > $OUT/soak_65536_d300_1yr.txt 2>&1; tail -3 $OUT/soak_65536_d300_1yr.txt
