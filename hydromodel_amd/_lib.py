@@ -113,6 +113,11 @@ EXPORTS = {
     "hc_get_enkf_sm_y": ([C.c_void_p, _dp], C.c_int),
     "hc_get_enkf_sm_gain": ([C.c_void_p, _dp], C.c_int),
     "hc_get_enkf_sm_eps": ([C.c_void_p, _dp], C.c_int),
+    "hc_set_enkf_method": ([C.c_void_p, C.c_int32, C.c_double], C.c_int),
+    "hc_get_enkf_method": ([C.c_void_p, _ip, _dp], C.c_int),
+    "hc_get_enkf_sqrt_gain": ([C.c_void_p, _dp], C.c_int),
+    "hc_get_enkf_sqrt_shift": ([C.c_void_p, _dp], C.c_int),
+    "hc_get_enkf_relaxation": ([C.c_void_p, _dp, _dp, _dp], C.c_int),
     "hc_rhs": ([C.c_void_p, C.c_int64, C.c_int32, _dp, _dp], C.c_int),
     "hc_model_nodes": ([C.c_void_p, _dp, _dp], C.c_int),
     "hc_plugin_eval": ([C.c_int, C.POINTER(ColumnParams), C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp],

@@ -63,6 +63,13 @@ unknown keys, only membership of the 12 is checked):
   ``enkf_sm_prior_mean``, ``enkf_sm_prior_std``, ``enkf_sm_post_mean``, ``enkf_sm_post_std`` ``[R][m]`` (NaN on rows with
   no sensor value; a sweep: a leading ``[P]`` axis), and the run ends with
   `` [Ensemble xN] soil-moisture forecast RMSE = ... over R rows`` (the prior mean theta against the record).
+* ``"EnKF": {..., "Method": "sqrt", "Relaxation": 0.5}``: the analysis scheme of the EnKF (include/hydrocol.h
+  hc_set_enkf_method).  ``Method``: ``"stochastic"`` (perturbed observations, the default) or ``"sqrt"``, the deterministic
+  square-root analysis of Whitaker & Hamill (2002): the mean moves by the Kalman gain, the anomalies by a reduced gain,
+  nothing is drawn (``Seed`` no longer matters).  ``Relaxation``: the relaxation to prior spread alpha, a finite number in
+  [0, 1] (default 0 = none), for either method: after each analysis every node's spread is (1 - alpha) sigma_a + alpha
+  sigma_b, and the posterior datasets describe the relaxed ensemble.  Added to ``<Output_Name>_ensemble.h5`` when either
+  is given: ``enkf_method`` (0 = stochastic, 1 = sqrt) and ``enkf_relaxation``.
 * ``"Ensemble": {"repair_predict": true}`` with ``Simulation_Flags.PREDICT``: run the repaired predictive lateral flow
    instead of raising the reference's ``TypeError``.
 """
@@ -124,6 +131,7 @@ def main(params_file=None, data_file=None, seed=None, device=0, gpus=None, _sett
             filter_settings(params["Ensemble"], n_gpus)     # so does a bad Filter block
             enkf_settings(params["Ensemble"], n_gpus)       # and a bad EnKF block
             soil_moisture_settings(params["Ensemble"], n_gpus)
+            enkf_method_settings(params["Ensemble"])
         ranks = multigpu.Ranks(expect=n_gpus if (n_gpus > 1 or multigpu.in_rank()) else None)
         if ranks.world > 1:
             device = ranks.device_index()
@@ -183,6 +191,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     filt = filter_settings(ens, ranks.world)
     enkf = enkf_settings(ens, ranks.world)
     sm = soil_moisture_settings(ens, ranks.world)
+    scheme = enkf_method_settings(ens)
     cols = ColumnTables(params, load_site_well(params))
     forcing = ForcingDigest(params, water_data, cols)
     record = soil_moisture_record_of(sm, cols, water_data)      # before any GPU call
@@ -193,7 +202,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     rows = min(days * 48, forcing.dim_t - 1)
     if ens.get("Points"):
         return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels, filt,
-                          enkf, record)
+                          enkf, record, scheme)
     lo, hi = multigpu.shard(n_members, ranks.rank, ranks.world)
     if hi <= lo:
         raise ValueError(f" Ensemble: {n_members} members do not shard over {ranks.world} GPUs (a rank would be empty).")
@@ -201,7 +210,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     sim = EnsembleSimulation(cols, forcing, hi - lo, seed=int(ens.get("Seed", 0)), device=device, member_offset=lo,
                              noise=str(ens.get("Noise", "philox")).lower(),
                              spinup=str(ens.get("Spinup", "shared")).lower(), profile_stride=stride,
-                             wtd_hist_stride=dist_stride, **_filter_kwargs(filt), **_enkf_kwargs(enkf, record))
+                             wtd_hist_stride=dist_stride, **_filter_kwargs(filt), **_enkf_kwargs(enkf, record, scheme))
     label = f"Ensemble x{n_members}"
     _step_all(sim, rows, label, ranks)
     # the run's one collective: int64 (count, sum idx, sum idx^2) per row, exact and order-independent
@@ -233,6 +242,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     etables, enkf_line = _reduce_enkf(ranks, sim, [0], 1, forcing.dim_t, enkf, label, keep_points=False,
                                          z0_cm=cols.z[0])
     extra.update(etables)
+    extra.update(_enkf_method_arrays(enkf, scheme))
     stables, sm_line = _reduce_enkf_sm(ranks, sim, [0], 1, forcing.dim_t, enkf, record, label, keep_points=False)
     extra.update(stables)
     arrays = dict(moments=moments, wtd_mean_cm=mean_cm, wtd_std_cm=std_cm, rows=np.array(rows),
@@ -320,7 +330,7 @@ def filter_settings(ens, n_gpus=1):
     return stride, float(sigma), (None if seed is None else int(seed))
 
 
-ENKF_KEYS = ("Stride", "Sigma_cm", "Localisation_cm", "Seed", "Soil_Moisture")
+ENKF_KEYS = ("Stride", "Sigma_cm", "Localisation_cm", "Seed", "Soil_Moisture", "Method", "Relaxation")
 
 
 def enkf_settings(ens, n_gpus=1):
@@ -364,14 +374,49 @@ def enkf_settings(ens, n_gpus=1):
     return stride, float(sigma), float(loc), (None if seed is None else int(seed))
 
 
-def _enkf_kwargs(enkf, record=None):
+ENKF_METHOD_NAMES = ("stochastic", "sqrt")
+
+
+def enkf_method_settings(ens):
+    """Ensemble.EnKF.Method / Relaxation -> (method, relaxation), or None when neither key is given (the run and its
+    file are then those of a block without them).  Pure, like :func:`enkf_settings`: a bad value is a ValueError (message
+    + exit status 1).  Needs an active EnKF."""
+    import math
+    from numbers import Real
+    block = ens.get("EnKF")
+    if not isinstance(block, dict) or ("Method" not in block and "Relaxation" not in block):
+        return None
+    method = block.get("Method", "stochastic")
+    if not isinstance(method, str) or method not in ENKF_METHOD_NAMES:
+        raise ValueError(f" Ensemble: EnKF.Method = {method!r} must be one of {list(ENKF_METHOD_NAMES)}.")
+    alpha = block.get("Relaxation", 0.0)
+    if isinstance(alpha, bool) or not isinstance(alpha, Real) or not math.isfinite(alpha) or not 0 <= alpha <= 1:
+        raise ValueError(f" Ensemble: EnKF.Relaxation = {alpha!r} must be a finite number in [0, 1] (0: none).")
+    stride = block.get("Stride", 48)
+    if isinstance(stride, Real) and not isinstance(stride, bool) and stride == 0:
+        raise ValueError(" Ensemble: EnKF.Method / EnKF.Relaxation need an active EnKF (EnKF.Stride > 0).")
+    return method, float(alpha)
+
+
+def _enkf_kwargs(enkf, record=None, scheme=None):
     stride, sigma, loc, seed = enkf
     if not stride:
         return {}
     kw = dict(enkf_stride=stride, enkf_sigma_cm=sigma, enkf_localisation_cm=loc, enkf_seed=seed)
     if record is not None:
         kw["enkf_soil_moisture"] = record
+    if scheme is not None:
+        kw.update(enkf_method=scheme[0], enkf_relaxation=scheme[1])
     return kw
+
+
+def _enkf_method_arrays(enkf, scheme):
+    """``enkf_method`` (0 = stochastic, 1 = sqrt) and ``enkf_relaxation``, when the block names either."""
+    import numpy as np
+    if not enkf[0] or scheme is None:
+        return {}
+    return {"enkf_method": np.array(ENKF_METHOD_NAMES.index(scheme[0]), dtype=np.int8),
+            "enkf_relaxation": np.array(scheme[1], dtype=np.float64)}
 
 
 SM_KEYS = ("Filename", "Depths_cm", "Sigma")
@@ -665,7 +710,7 @@ def _reduce_optional(ranks, sim, ids, cols_all, forcing, stride, dist_stride, di
 
 
 def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride=0, dist_levels=None,
-               filt=(0, None, None), enkf=(0, None, None, None), record=None):
+               filt=(0, None, None), enkf=(0, None, None, None), record=None, scheme=None):
     """Parameter points x members: this rank's points in one handle (ensemble.SweepSimulation), the whole table assembled
     over the ranks (multigpu.assemble_points)."""
     import numpy as np
@@ -692,7 +737,7 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     if mine:
         sim = SweepSimulation(points, forcing, n_members, seed=int(ens.get("Seed", 0)), device=device, point_ids=mine,
                               profile_stride=stride, wtd_hist_stride=dist_stride, **_filter_kwargs(filt),
-                              **_enkf_kwargs(enkf, record))
+                              **_enkf_kwargs(enkf, record, scheme))
         _step_all(sim, rows, label, ranks)
         table = sim.moments()
         for j, k in enumerate(mine):
@@ -713,6 +758,7 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     arrays.update(etables)
     stables, sm_line = _reduce_enkf_sm(ranks, sim, mine, P, T, enkf, record, label, keep_points=True)
     arrays.update(stables)
+    arrays.update(_enkf_method_arrays(enkf, scheme))
     if sim is not None:
         sim.close()
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "sweep's water-table statistics", ranks)
@@ -747,6 +793,7 @@ def run_cli(argv=None):
                 filter_settings(settings["Ensemble"], n_gpus)
                 enkf_settings(settings["Ensemble"], n_gpus)
                 soil_moisture_settings(settings["Ensemble"], n_gpus)
+                enkf_method_settings(settings["Ensemble"])
             except ValueError as bad:
                 print(bad)
                 sys.exit(1)

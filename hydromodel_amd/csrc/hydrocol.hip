@@ -187,6 +187,16 @@ struct hc_handle {
     int enkf_width = 0;          // its m' (the rows of Y and the gain)
     AccTable<double> enkf{"entries"};
     DevBuf<double> enkf_Y, enkf_eps, enkf_eps_s, enkf_Ypost, enkf_gain, enkf_s1, enkf_s2, enkf_part;
+    // the analysis scheme (hc_set_enkf_method): 0 = perturbed observations, 1 = square root (the reduced gain [P][m'][D]
+    // and the mean's increment [P][D] of the last analysis: test hooks); relaxation to prior spread alpha (> 0: the
+    // tile partials and sums of the squared psi anomalies before / after the update, the sums of the analysis columns,
+    // and (sigma_b, sigma_a, f, the analysis's mean) [4][P][D] of the last analysis: test hooks); what the last
+    // analysis ran with
+    int enkf_method = 0;
+    double enkf_alpha = 0.0;
+    int enkf_last_method = 0;
+    bool enkf_last_relaxed = false;
+    DevBuf<double> enkf_rgain, enkf_dbar, enkf_part_sq, enkf_sq_b, enkf_sq_a, enkf_mean_a, enkf_relax;
     // soil-moisture sensors in the EnKF analysis (hc_set_enkf_soil_moisture): the record on the host (nodes, sigma,
     // values [sm_rows][sm_n], NaN = none); diagnostics float64 [P][n_arow][sm_n][6] keyed like the EnKF's; sm_width =
     // the last analysis's m', 0 = no sensor on it
@@ -924,11 +934,15 @@ __global__ void enkf_theta_kernel(const double *psi, const ColumnDev *P, const d
 
 // Column sums of X = (psi_0 .. psi_{Dc-1}, Y_0 .. Y_{W-1}) (Dc = 0: Y alone), C = Dc + W columns, tile t of point p:
 //   sums == NULL: partial[p][t][j] = sum over the tile in member order of X_j;
-//   otherwise:    partial[p][t][j][i] = sum of (X_j - xbar_j)(Y_i - ybar_i), the means = sums[p][.] / N_p.
+//   otherwise:    partial[p][t][j][i] = sum of (X_j - xbar_j)(Y_i - ybar_i), the means = sums[p][.] / N_p; and with
+//                 SQUARE (the relaxation to prior spread): square[p][t][j] = sum of (psi_j - psibar_j)^2, j < Dc.
+//                 A template parameter: the plain kernel keeps its instructions.
 // Thread j owns column j: every member's psi row is one coalesced read of the block.
+template <bool SQUARE>
 __global__ __launch_bounds__(HC_MAX_DEPTH_NODES + WAVE) void enkf_partial_kernel(const double *psi, const double *Y, int W,
                                                                                  const double *sums, long long mpp, int Dc,
-                                                                                 long long n_tiles, double *partial)
+                                                                                 long long n_tiles, double *partial,
+                                                                                 double *square)
 {
 #pragma clang fp contract(off)
     const long long p = blockIdx.y, t = blockIdx.x;
@@ -953,13 +967,16 @@ __global__ __launch_bounds__(HC_MAX_DEPTH_NODES + WAVE) void enkf_partial_kernel
         yb[i] = i < W ? S[Dc + i] / (double)mpp : 0.0;
         acc[i] = 0.0;
     }
+    double sq = 0.0;
     for (long long m = m0; m < m1; m++) {
         const double a = x[(size_t)m * xs] - xb;
         const double *ym = Y + (size_t)m * W;
 #pragma unroll
         for (int i = 0; i < ENKF_OBS + 1; i++)
             if (i < W) acc[i] += a * (ym[i] - yb[i]);
+        if (SQUARE) sq += a * a;
     }
+    if (SQUARE && j < Dc) square[((size_t)p * n_tiles + t) * Dc + j] = sq;
     double *out = partial + (((size_t)p * n_tiles + t) * C + j) * W;
 #pragma unroll
     for (int i = 0; i < ENKF_OBS + 1; i++)
@@ -1001,12 +1018,15 @@ __device__ bool enkf_cholesky(const double *A, int n, double *L)
 
 // One block per point, thread d = node d.  Thread 0: ybar, C_YY, the tapered S = rho o C_YY + R and its Cholesky factor;
 // the untapered C_YY + R for the joint log-density; the prior diagnostics (EnKF entries 0-4, the sensors' first four).
-// Then thread d: K_d = (rho_d o c_d) S^-1 by a forward and a backward substitution, into gain[p][i][d].
+// Then thread d: K_d = (rho_d o c_d) S^-1 by a forward and a backward substitution, into gain[p][i][d].  The square-root
+// analysis (rgain != NULL) also takes the mean's increment dbar[p][d] = sum_i K_di (o_i - Ybar_i), i in order, and the
+// reduced gain Kr_d = (rho_d o c_d) L^-T (L + R^1/2)^-1 into rgain[p][i][d]: the forward substitution once more, then a
+// backward substitution with the lower-triangular L + R^1/2 (the same LDS working set).
 __global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void enkf_gain_kernel(const double *s1, const double *s2, long long mpp,
                                                                        int D, const EnkfRow s, double sigma, double loc,
                                                                        double z_obs, double dz, double *gain,
                                                                        double *stats, double *sm_stats, long long n_arow,
-                                                                       long long slot)
+                                                                       long long slot, double *rgain, double *dbar)
 {
 #pragma clang fp contract(off)
     // the working sets live in LDS (dynamically indexed: in registers they would go to scratch)
@@ -1070,8 +1090,13 @@ __global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void enkf_gain_kernel(const dou
     const int d = threadIdx.x;
     if (d >= D) return;
     double *K = gain + (size_t)p * W * D + d;
+    double *Kr = rgain ? rgain + (size_t)p * W * D + d : nullptr;
     if (!ok) {
         for (int i = 0; i < W; i++) K[(size_t)i * D] = __builtin_nan("");
+        if (Kr) {
+            for (int i = 0; i < W; i++) Kr[(size_t)i * D] = __builtin_nan("");
+            dbar[(size_t)p * D + d] = __builtin_nan("");
+        }
         return;
     }
     double *u = U[d];
@@ -1087,6 +1112,24 @@ __global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void enkf_gain_kernel(const dou
         u[i] = v / Ls[i * ENKF_OBS + i];
     }
     for (int i = 0; i < W; i++) K[(size_t)i * D] = u[i];
+    if (!Kr) return;
+    double inc = 0.0;
+    for (int i = 0; i < W; i++) inc += u[i] * dl[i];
+    dbar[(size_t)p * D + d] = inc;
+    for (int i = 0; i < W; i++) {
+        const double rho = loc > 0.0 ? gaspari_cohn(fabs((double)d * dz - zeta[i]) / loc) : 1.0;
+        double v = rho * (mpp > 1 ? S2[(size_t)d * W + i] / n1 : 0.0);
+        for (int k = 0; k < i; k++) v -= Ls[i * ENKF_OBS + k] * u[k];
+        u[i] = v / Ls[i * ENKF_OBS + i];
+    }
+    // x (L + R^1/2) = u: x_i = (u_i - sum_{k > i} (L + R^1/2)_ki x_k) / (L_ii + r_i), r_i = sqrt(r2_i) (off the diagonal
+    // L + R^1/2 is L)
+    for (int i = W - 1; i >= 0; i--) {
+        double v = u[i];
+        for (int k = i + 1; k < W; k++) v -= Ls[k * ENKF_OBS + i] * u[k];
+        u[i] = v / (Ls[i * ENKF_OBS + i] + sqrt(r2[i]));
+    }
+    for (int i = 0; i < W; i++) Kr[(size_t)i * D] = u[i];
 }
 
 // lane i's v, for every lane of the wave, in scalar registers (v_readlane reads lane i whichever lanes are active)
@@ -1212,6 +1255,195 @@ __global__ __launch_bounds__(256) void enkf_update_kernel(double *psi, const dou
             out[0] = enkf_y_of(b, lo, hi, psat, dz);
             out[W] = keep ? 0.0 : 1.0;
         }
+    }
+}
+
+// ---- the square-root analysis and the relaxation to prior spread (hc_set_enkf_method)
+// What the two kernels below share.  A wave holds a member's column in a (node c * WAVE + lane in a[c], 0 past D).
+// enkf_keep_column: `next` is stored and becomes a when every entry of it is finite (the wave's vote); else a stays.
+__device__ __forceinline__ bool enkf_keep_column(double (&a)[ENKF_SLOTS], const double (&next)[ENKF_SLOTS], double *col,
+                                                 int lane, int D)
+{
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < ENKF_SLOTS; c++) ok = ok && isfinite(next[c]);
+    const bool keep = __all(ok);
+    if (keep) {
+#pragma unroll
+        for (int c = 0; c < ENKF_SLOTS; c++) {
+            const int d = c * WAVE + lane;
+            a[c] = next[c];
+            if (d < D) col[d] = next[c];
+        }
+    }
+    return keep;
+}
+
+// enkf_column_y: find_wtd of the column (the step kernel's rule: below the deepest node with psi < psi_sat, clamped)
+// and its y, on every lane
+__device__ __forceinline__ double enkf_column_y(const double (&a)[ENKF_SLOTS], int lane, int D, double psat, double dz)
+{
+    int deepest = -1;
+#pragma unroll
+    for (int c = 0; c < ENKF_SLOTS; c++) {
+        const int d = c * WAVE + lane;
+        const unsigned long long u = __ballot(d < D && !(a[c] >= psat));
+        if (u) deepest = c * WAVE + 63 - __clzll((long long)u);
+    }
+    const int b = deepest < 0 ? 0 : (deepest + 1 < D - 1 ? deepest + 1 : D - 1);
+    const int bl = b >= 1 ? b - 1 : 0;
+    double hi = 0.0, lo = 0.0;
+#pragma unroll
+    for (int c = 0; c < ENKF_SLOTS; c++) {
+        const double x = __shfl(a[c], b % WAVE), xl = __shfl(a[c], bl % WAVE);
+        if (c == b / WAVE) hi = x;
+        if (c == bl / WAVE) lo = xl;
+    }
+    return enkf_y_of(b, lo, hi, psat, dz);
+}
+
+// The square-root update (Whitaker & Hamill 2002), one wave per member like enkf_update_kernel: psi_dk + dbar_d +
+// sum_i Kr_di (Ybar_i - Y_ki), i in order (Ybar from the prior sums s1 [P][D + m']), one gain row at a time with the
+// loads of all its slots in flight; the same vote, find_wtd and Ypost[m] = (y, ..., rejected).  Nothing is drawn.
+// want_y = 0: the relaxation follows and writes y.
+__global__ __launch_bounds__(256) void enkf_sqrt_update_kernel(double *psi, const double *Y, const double *rgain,
+                                                               const double *dbar, const double *s1, const ColumnDev *P,
+                                                               long long n_members, long long mpp, int D, double dz,
+                                                               int W, int want_y, double *Ypost)
+{
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x % WAVE;
+    const long long waves = (long long)gridDim.x * (blockDim.x / WAVE);
+    for (long long m = (long long)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE; m < n_members; m += waves) {
+        const long long p = m / mpp;
+        const double *K = rgain + (size_t)p * W * D, *db = dbar + (size_t)p * D;
+        double *col = psi + (size_t)m * D;
+        double a[ENKF_SLOTS], inc[ENKF_SLOTS], k0[ENKF_SLOTS];
+#pragma unroll
+        for (int c = 0; c < ENKF_SLOTS; c++) {
+            const int d = c * WAVE + lane;
+            a[c] = 0.0;
+            inc[c] = 0.0;
+            k0[c] = 0.0;
+            if (d < D) {
+                a[c] = col[d];
+                inc[c] = db[d];
+                k0[c] = K[d];
+            }
+        }
+        // lane i holds Ybar_i - Y_ki
+        const double my_dl = lane < W ? s1[(size_t)p * (D + W) + D + lane] / (double)mpp - Y[(size_t)m * W + lane] : 0.0;
+        const double d0 = lane_value(my_dl, 0);
+#pragma unroll
+        for (int c = 0; c < ENKF_SLOTS; c++) inc[c] = inc[c] + k0[c] * d0;
+#pragma unroll 1
+        for (int i = 1; i < W; i++) {
+            const double di = lane_value(my_dl, i);
+            double k[ENKF_SLOTS];
+#pragma unroll
+            for (int c = 0; c < ENKF_SLOTS; c++) {
+                const int d = c * WAVE + lane;
+                k[c] = d < D ? K[(size_t)i * D + d] : 0.0;
+            }
+#pragma unroll
+            for (int c = 0; c < ENKF_SLOTS; c++) inc[c] = inc[c] + k[c] * di;
+        }
+#pragma unroll
+        for (int c = 0; c < ENKF_SLOTS; c++) inc[c] = a[c] + inc[c];
+        const bool keep = enkf_keep_column(a, inc, col, lane, D);
+        double *out = Ypost + (size_t)m * (W + 1);
+        if (want_y) {
+            const double y = enkf_column_y(a, lane, D, P[p].psi_sat, dz);
+            if (lane == 0) out[0] = y;
+        }
+        if (lane == 0) out[W] = keep ? 0.0 : 1.0;
+    }
+}
+
+// The spread of the analysis columns, tile t of point p, thread d = node d, by the tile rule of enkf_partial_kernel.
+// The columns are taken relative to the point's first member, x = psi_d - psi_d[member 0]:
+//   sums == NULL: partial[p][t][d] = sum over the tile in member order of x;
+//   otherwise:    partial[p][t][d] = sum of (x - xbar)^2, xbar = sums[p][d] / N_p.
+// So a node on which every member agrees (a saturated tail) has x = 0, the mean psi_d[member 0] and sigma_a = 0 exactly,
+// where the plain sum of N equal values rounds.
+__global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void enkf_spread_kernel(const double *psi, const double *sums,
+                                                                         long long mpp, int D, long long n_tiles,
+                                                                         double *partial)
+{
+#pragma clang fp contract(off)
+    const long long p = blockIdx.y, t = blockIdx.x;
+    const int d = threadIdx.x;
+    if (d >= D) return;
+    const long long m0 = p * mpp + t * ENKF_TILE;
+    const long long m1 = p * mpp + ((t + 1) * ENKF_TILE < mpp ? (t + 1) * ENKF_TILE : mpp);
+    const double *x = psi + d;
+    const double x0 = x[(size_t)(p * mpp) * D];
+    double s = 0.0;
+    if (!sums) {
+#pragma unroll 8
+        for (long long m = m0; m < m1; m++) s += x[(size_t)m * D] - x0;
+    } else {
+        const double xb = sums[(size_t)p * D + d] / (double)mpp;
+#pragma unroll 8
+        for (long long m = m0; m < m1; m++) {
+            const double a = (x[(size_t)m * D] - x0) - xb;
+            s += a * a;
+        }
+    }
+    partial[((size_t)p * n_tiles + t) * D + d] = s;
+}
+
+// Relaxation to prior spread (Whitaker & Hamill 2012), one thread per point and node: from the sums of the squared psi
+// anomalies before and after the update, sigma_b, sigma_a (N_p - 1; N_p = 1: 0) and f = 1 + alpha (sigma_b - sigma_a) /
+// sigma_a; f = 1 where sigma_a is 0 or not finite and for a point whose factorisation failed (a NaN gain); the mean of
+// the analysis, psi_d[member 0] + sums / N_p (enkf_spread_kernel).  relax = (sigma_b, sigma_a, f, mean), [P][D] each.
+__global__ void enkf_relax_factor_kernel(const double *sq_b, const double *sq_a, const double *sums, const double *psi,
+                                         const double *gain, long long n_points, long long mpp, int D, int W, double alpha,
+                                         double *relax)
+{
+#pragma clang fp contract(off)
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x, n = n_points * D;
+    if (k >= n) return;
+    const long long p = k / D;
+    const double n1 = (double)(mpp - 1);
+    const double sb = mpp > 1 ? sqrt(sq_b[k] / n1) : 0.0, sa = mpp > 1 ? sqrt(sq_a[k] / n1) : 0.0;
+    double f = 1.0;
+    if (sa > 0.0 && isfinite(sa) && isfinite(gain[(size_t)p * W * D])) f = 1.0 + alpha * (sb - sa) / sa;
+    relax[k] = sb;
+    relax[n + k] = sa;
+    relax[2 * n + k] = f;
+    relax[3 * n + k] = psi[(size_t)(p * mpp) * D + k % D] + sums[k] / (double)mpp;
+}
+
+// One wave per member: psi_dk <- mean_d + f_d (psi_dk - mean_d) (the analysis's mean [P][D]; a node with f_d = 1
+// stays as it is), stored only when every entry is finite (else the member keeps its unrelaxed analysis); then find_wtd
+// and y of the column it kept into Ypost[m][0] (rows of `width` entries).
+__global__ __launch_bounds__(256) void enkf_relax_kernel(double *psi, const double *means, const double *factor,
+                                                         const ColumnDev *P, long long n_members, long long mpp, int D,
+                                                         double dz, int width, double *Ypost)
+{
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x % WAVE;
+    const long long waves = (long long)gridDim.x * (blockDim.x / WAVE);
+    for (long long m = (long long)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE; m < n_members; m += waves) {
+        const long long p = m / mpp;
+        const double *S = means + (size_t)p * D, *F = factor + (size_t)p * D;
+        double *col = psi + (size_t)m * D;
+        double a[ENKF_SLOTS], r[ENKF_SLOTS];
+#pragma unroll
+        for (int c = 0; c < ENKF_SLOTS; c++) {
+            const int d = c * WAVE + lane;
+            a[c] = 0.0;
+            r[c] = 0.0;
+            if (d < D) {
+                const double mean = S[d], f = F[d];
+                a[c] = col[d];
+                r[c] = f == 1.0 ? a[c] : mean + f * (a[c] - mean);
+            }
+        }
+        enkf_keep_column(a, r, col, lane, D);
+        const double y = enkf_column_y(a, lane, D, P[p].psi_sat, dz);
+        if (lane == 0) Ypost[(size_t)m * width] = y;
     }
 }
 
@@ -1597,6 +1829,12 @@ void enkf_off(hc_handle *h)
     h->enkf.release();
     h->enkf_Y.release(); h->enkf_eps.release(); h->enkf_Ypost.release(); h->enkf_gain.release();
     h->enkf_s1.release(); h->enkf_s2.release(); h->enkf_part.release();
+    h->enkf_method = 0;
+    h->enkf_alpha = 0.0;
+    h->enkf_last_method = 0;
+    h->enkf_last_relaxed = false;
+    h->enkf_rgain.release(); h->enkf_dbar.release(); h->enkf_part_sq.release(); h->enkf_sq_b.release();
+    h->enkf_sq_a.release(); h->enkf_mean_a.release(); h->enkf_relax.release();
     sm_off(h);
 }
 
@@ -2506,7 +2744,10 @@ EnkfRow enkf_row(const hc_handle *h, int64_t row)
 // observations per member, in place on psi: y and theta per member; per point the column and observation sums, then the
 // anomaly products (two passes over psi); the gain and the prior diagnostics; the update with eps and the posterior (y,
 // theta, rejected) per member (one read + write of psi); the posterior sums and diagnostics.  Scratch is sized by the
-// record's largest m', 1 + sm_n.
+// record's largest m', 1 + sm_n.  hc_set_enkf_method: the square-root scheme swaps the draws and the update for its own
+// (the gain kernel adds the reduced gain and the mean's increment); a relaxation alpha > 0 takes the squared psi
+// anomalies along in the second prior pass, sums the analysis columns and their squared anomalies (two more passes over
+// psi), relaxes (one read + write) and only then forms the posterior.
 int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
 {
     const int64_t N = h->n_members, D = h->p.dim_d, P = h->n_points, mpp = N / P;
@@ -2519,6 +2760,12 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
         h->enkf_eps_s.ensure((size_t)(N * h->sm_n)) || h->enkf_Ypost.ensure((size_t)(N * (Wx + 1))) ||
         h->enkf_gain.ensure((size_t)(P * Wx * D)) || h->enkf_s1.ensure((size_t)(P * Cx)) ||
         h->enkf_s2.ensure((size_t)(P * cols_x)) || h->enkf_part.ensure((size_t)(P * n_tiles * cols_x)))
+        return HC_ERR_DEVICE;
+    const bool root = h->enkf_method == 1, relax = h->enkf_alpha > 0.0;
+    if (root && (h->enkf_rgain.ensure((size_t)(P * Wx * D)) || h->enkf_dbar.ensure((size_t)(P * D)))) return HC_ERR_DEVICE;
+    if (relax && (h->enkf_part_sq.ensure((size_t)(P * n_tiles * D)) || h->enkf_sq_b.ensure((size_t)(P * D)) ||
+                  h->enkf_sq_a.ensure((size_t)(P * D)) || h->enkf_mean_a.ensure((size_t)(P * D)) ||
+                  h->enkf_relax.ensure((size_t)(4 * P * D))))
         return HC_ERR_DEVICE;
     const unsigned short *w = h->wtd_u16.p + (size_t)(c.rows - 1) * N;
     const double dz = h->p.dz, z_obs = (double)h->h_wtd_obs[(size_t)row] * dz;
@@ -2536,46 +2783,87 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
     // prior: the sums of (psi, Y), then the products of their anomalies with Y's
     const dim3 tiles((unsigned)n_tiles, (unsigned)P);
     const dim3 cols_prior((unsigned)((C + WAVE - 1) / WAVE * WAVE)), cols_post((unsigned)WAVE);
-    hipLaunchKernelGGL(enkf_partial_kernel, tiles, cols_prior, 0, h->stream, h->psi.p, h->enkf_Y.p, W, nullptr, ll_mpp,
-                       (int)D, ll_tiles, h->enkf_part.p);
+    hipLaunchKernelGGL(enkf_partial_kernel<false>, tiles, cols_prior, 0, h->stream, h->psi.p, h->enkf_Y.p, W, nullptr, ll_mpp,
+                       (int)D, ll_tiles, h->enkf_part.p, nullptr);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(enkf_finish_kernel, dim3((unsigned)C, (unsigned)P), dim3(ENKF_THREADS), 0, h->stream,
                        h->enkf_part.p, ll_tiles, (int)C, h->enkf_s1.p);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(enkf_partial_kernel, tiles, cols_prior, 0, h->stream, h->psi.p, h->enkf_Y.p, W, h->enkf_s1.p,
-                       ll_mpp, (int)D, ll_tiles, h->enkf_part.p);
+    if (relax)
+        hipLaunchKernelGGL(enkf_partial_kernel<true>, tiles, cols_prior, 0, h->stream, h->psi.p, h->enkf_Y.p, W,
+                           h->enkf_s1.p, ll_mpp, (int)D, ll_tiles, h->enkf_part.p, h->enkf_part_sq.p);
+    else
+        hipLaunchKernelGGL(enkf_partial_kernel<false>, tiles, cols_prior, 0, h->stream, h->psi.p, h->enkf_Y.p, W,
+                           h->enkf_s1.p, ll_mpp, (int)D, ll_tiles, h->enkf_part.p, nullptr);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(enkf_finish_kernel, dim3((unsigned)(C * W), (unsigned)P), dim3(ENKF_THREADS), 0, h->stream,
                        h->enkf_part.p, ll_tiles, (int)(C * W), h->enkf_s2.p);
     HIP_TRY(hipGetLastError());
+    if (relax) {
+        hipLaunchKernelGGL(enkf_finish_kernel, dim3((unsigned)D, (unsigned)P), dim3(ENKF_THREADS), 0, h->stream,
+                           h->enkf_part_sq.p, ll_tiles, (int)D, h->enkf_sq_b.p);
+        HIP_TRY(hipGetLastError());
+    }
     double *st = h->enkf.buf.p, *sst = h->sm.buf.p;
     hipLaunchKernelGGL(enkf_gain_kernel, dim3((unsigned)P), dim3((unsigned)((D + WAVE - 1) / WAVE * WAVE)), 0, h->stream,
                        h->enkf_s1.p, h->enkf_s2.p, ll_mpp, (int)D, s, h->enkf_sigma, h->enkf_loc, z_obs, dz,
-                       h->enkf_gain.p, st, sst, (long long)n_arow, (long long)slot);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(enkf_draw_kernel, members, dim3(256), 0, h->stream, (long long)N, ll_mpp,
-                       (unsigned long long)h->enkf_seed, P > 1 ? h->point_base.p : nullptr, (long long)h->member_offset,
-                       (unsigned)row, s.n, h->enkf_eps.p, h->enkf_eps_s.p);
+                       h->enkf_gain.p, st, sst, (long long)n_arow, (long long)slot, root ? h->enkf_rgain.p : nullptr,
+                       root ? h->enkf_dbar.p : nullptr);
     HIP_TRY(hipGetLastError());
     const unsigned blocks = (unsigned)std::min<int64_t>((N + 3) / 4, (int64_t)h->n_cu * 8);
-    hipLaunchKernelGGL(enkf_update_kernel, dim3(blocks), dim3(256), 0, h->stream, h->psi.p, h->enkf_Y.p, h->enkf_gain.p,
-                       h->Pdev.p, (long long)N, ll_mpp, (int)D, dz, z_obs, h->enkf_sigma, s, h->enkf_eps.p,
-                       h->enkf_eps_s.p, h->enkf_Ypost.p);
-    HIP_TRY(hipGetLastError());
+    if (root) {
+        hipLaunchKernelGGL(enkf_sqrt_update_kernel, dim3(blocks), dim3(256), 0, h->stream, h->psi.p, h->enkf_Y.p,
+                           h->enkf_rgain.p, h->enkf_dbar.p, h->enkf_s1.p, h->Pdev.p, (long long)N, ll_mpp, (int)D, dz, W,
+                           relax ? 0 : 1, h->enkf_Ypost.p);
+        HIP_TRY(hipGetLastError());
+    } else {
+        hipLaunchKernelGGL(enkf_draw_kernel, members, dim3(256), 0, h->stream, (long long)N, ll_mpp,
+                           (unsigned long long)h->enkf_seed, P > 1 ? h->point_base.p : nullptr,
+                           (long long)h->member_offset, (unsigned)row, s.n, h->enkf_eps.p, h->enkf_eps_s.p);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(enkf_update_kernel, dim3(blocks), dim3(256), 0, h->stream, h->psi.p, h->enkf_Y.p,
+                           h->enkf_gain.p, h->Pdev.p, (long long)N, ll_mpp, (int)D, dz, z_obs, h->enkf_sigma, s,
+                           h->enkf_eps.p, h->enkf_eps_s.p, h->enkf_Ypost.p);
+        HIP_TRY(hipGetLastError());
+    }
+    if (relax) {
+        // the analysis columns' sums, then their squared anomalies; the factors; the relaxed columns and their y
+        const dim3 cols_psi((unsigned)((D + WAVE - 1) / WAVE * WAVE));
+        hipLaunchKernelGGL(enkf_spread_kernel, tiles, cols_psi, 0, h->stream, h->psi.p, nullptr, ll_mpp, (int)D, ll_tiles,
+                           h->enkf_part_sq.p);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(enkf_finish_kernel, dim3((unsigned)D, (unsigned)P), dim3(ENKF_THREADS), 0, h->stream,
+                           h->enkf_part_sq.p, ll_tiles, (int)D, h->enkf_mean_a.p);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(enkf_spread_kernel, tiles, cols_psi, 0, h->stream, h->psi.p, h->enkf_mean_a.p, ll_mpp, (int)D,
+                           ll_tiles, h->enkf_part_sq.p);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(enkf_finish_kernel, dim3((unsigned)D, (unsigned)P), dim3(ENKF_THREADS), 0, h->stream,
+                           h->enkf_part_sq.p, ll_tiles, (int)D, h->enkf_sq_a.p);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(enkf_relax_factor_kernel, dim3((unsigned)((P * D + 255) / 256)), dim3(256), 0, h->stream,
+                           h->enkf_sq_b.p, h->enkf_sq_a.p, h->enkf_mean_a.p, h->psi.p, h->enkf_gain.p, (long long)P, ll_mpp,
+                           (int)D, W, h->enkf_alpha, h->enkf_relax.p);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(enkf_relax_kernel, dim3(blocks), dim3(256), 0, h->stream, h->psi.p,
+                           h->enkf_relax.p + (size_t)(3 * P * D), h->enkf_relax.p + (size_t)(2 * P * D), h->Pdev.p, (long long)N, ll_mpp, (int)D, dz, V,
+                           h->enkf_Ypost.p);
+        HIP_TRY(hipGetLastError());
+    }
     if (s.m > 0) {
         hipLaunchKernelGGL(enkf_theta_kernel, members, dim3(256), 0, h->stream, h->psi.p, h->Pdev.p, h->node_tabs.p, special,
                            (long long)N, ll_mpp, (int)D, s, h->enkf_Ypost.p, V);
         HIP_TRY(hipGetLastError());
     }
     // posterior: the same two passes over (y, theta, rejected) alone
-    hipLaunchKernelGGL(enkf_partial_kernel, tiles, cols_post, 0, h->stream, nullptr, h->enkf_Ypost.p, V, nullptr, ll_mpp,
-                       0, ll_tiles, h->enkf_part.p);
+    hipLaunchKernelGGL(enkf_partial_kernel<false>, tiles, cols_post, 0, h->stream, nullptr, h->enkf_Ypost.p, V, nullptr, ll_mpp,
+                       0, ll_tiles, h->enkf_part.p, nullptr);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(enkf_finish_kernel, dim3((unsigned)V, (unsigned)P), dim3(ENKF_THREADS), 0, h->stream,
                        h->enkf_part.p, ll_tiles, V, h->enkf_s1.p);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(enkf_partial_kernel, tiles, cols_post, 0, h->stream, nullptr, h->enkf_Ypost.p, V, h->enkf_s1.p,
-                       ll_mpp, 0, ll_tiles, h->enkf_part.p);
+    hipLaunchKernelGGL(enkf_partial_kernel<false>, tiles, cols_post, 0, h->stream, nullptr, h->enkf_Ypost.p, V, h->enkf_s1.p,
+                       ll_mpp, 0, ll_tiles, h->enkf_part.p, nullptr);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(enkf_finish_kernel, dim3((unsigned)(V * V), (unsigned)P), dim3(ENKF_THREADS), 0, h->stream,
                        h->enkf_part.p, ll_tiles, V * V, h->enkf_s2.p);
@@ -2585,6 +2873,8 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
     HIP_TRY(hipGetLastError());
     h->enkf_done = true;
     h->enkf_width = W;
+    h->enkf_last_method = h->enkf_method;
+    h->enkf_last_relaxed = relax;
     h->sm_width = s.m > 0 ? W : 0;
     return HC_OK;
 }
@@ -3089,8 +3379,17 @@ int hc_get_enkf_y(hc_handle *h, double *y)
                      "hc_get_enkf_y");
 }
 
+// the square-root analysis draws nothing: its eps do not exist
+static int eps_check(hc_handle *h, const char *who)
+{
+    if (h && h->enkf_stride > 0 && h->enkf_done && h->enkf_last_method == 1)
+        return fail(HC_ERR_ARG, "%s: the last analysis was the square-root one, which draws nothing", who);
+    return HC_OK;
+}
+
 int hc_get_enkf_eps(hc_handle *h, double *eps)
 {
+    if (int rc = eps_check(h, "hc_get_enkf_eps")) return rc;
     return enkf_hook(h, h ? h->enkf_eps.p : nullptr, eps, 1, h ? (size_t)h->n_members : 0, h ? (size_t)h->n_members : 0,
                      "hc_get_enkf_eps");
 }
@@ -3186,7 +3485,65 @@ int hc_get_enkf_sm_gain(hc_handle *h, double *gain)
 
 int hc_get_enkf_sm_eps(hc_handle *h, double *eps)
 {
+    if (int rc = eps_check(h, "hc_get_enkf_sm_eps")) return rc;
     return sm_hook(h, h ? h->enkf_eps_s.p : nullptr, eps, h ? (size_t)h->n_members * h->sm_n : 0, "hc_get_enkf_sm_eps");
+}
+
+int hc_set_enkf_method(hc_handle *h, int32_t method, double relaxation)
+{
+    if (!h) return fail(HC_ERR_ARG, "hc_set_enkf_method: bad argument");
+    if (h->enkf_stride <= 0) return fail(HC_ERR_ARG, "hc_set_enkf_method: the EnKF is off (hc_set_enkf comes first)");
+    if (method != 0 && method != 1)
+        return fail(HC_ERR_ARG, "hc_set_enkf_method: method = %d must be 0 (stochastic) or 1 (square root)", (int)method);
+    if (!(std::isfinite(relaxation) && relaxation >= 0.0 && relaxation <= 1.0))
+        return fail(HC_ERR_ARG, "hc_set_enkf_method: relaxation = %g must be finite and in [0, 1]", relaxation);
+    h->enkf_method = method;
+    h->enkf_alpha = relaxation;
+    return HC_OK;
+}
+
+int hc_get_enkf_method(hc_handle *h, int32_t *method, double *relaxation)
+{
+    if (!h || !method || !relaxation) return fail(HC_ERR_ARG, "hc_get_enkf_method: bad argument");
+    *method = h->enkf_stride > 0 ? h->enkf_method : 0;
+    *relaxation = h->enkf_stride > 0 ? h->enkf_alpha : 0.0;
+    return HC_OK;
+}
+
+// the reduced gain is [P][m'][D] on the device, [P][D][m'] at the C-ABI (as hc_get_enkf_sm_gain)
+int hc_get_enkf_sqrt_gain(hc_handle *h, double *gain)
+{
+    if (!h || !gain) return fail(HC_ERR_ARG, "hc_get_enkf_sqrt_gain: bad argument");
+    if (h->enkf_stride <= 0 || !h->enkf_done || h->enkf_last_method != 1)
+        return fail(HC_ERR_ARG, "hc_get_enkf_sqrt_gain: no square-root analysis since hc_set_enkf");
+    const size_t P = (size_t)h->n_points, D = (size_t)h->p.dim_d, W = (size_t)h->enkf_width;
+    std::vector<double> k(P * W * D);
+    if (int rc = enkf_hook(h, h->enkf_rgain.p, k.data(), 1, k.size(), k.size(), "hc_get_enkf_sqrt_gain")) return rc;
+    for (size_t p = 0; p < P; p++)
+        for (size_t i = 0; i < W; i++)
+            for (size_t d = 0; d < D; d++) gain[(p * D + d) * W + i] = k[(p * W + i) * D + d];
+    return HC_OK;
+}
+
+int hc_get_enkf_sqrt_shift(hc_handle *h, double *shift)
+{
+    if (!h || !shift) return fail(HC_ERR_ARG, "hc_get_enkf_sqrt_shift: bad argument");
+    if (h->enkf_stride <= 0 || !h->enkf_done || h->enkf_last_method != 1)
+        return fail(HC_ERR_ARG, "hc_get_enkf_sqrt_shift: no square-root analysis since hc_set_enkf");
+    const size_t n = (size_t)h->n_points * h->p.dim_d;
+    return enkf_hook(h, h->enkf_dbar.p, shift, 1, n, n, "hc_get_enkf_sqrt_shift");
+}
+
+int hc_get_enkf_relaxation(hc_handle *h, double *sigma_b, double *sigma_a, double *factor)
+{
+    if (!h || !sigma_b || !sigma_a || !factor) return fail(HC_ERR_ARG, "hc_get_enkf_relaxation: bad argument");
+    if (h->enkf_stride <= 0 || !h->enkf_done || !h->enkf_last_relaxed)
+        return fail(HC_ERR_ARG, "hc_get_enkf_relaxation: no relaxed analysis since hc_set_enkf");
+    const size_t n = (size_t)h->n_points * h->p.dim_d;
+    double *out[3] = {sigma_b, sigma_a, factor};
+    for (int k = 0; k < 3; k++)
+        if (int rc = enkf_hook(h, h->enkf_relax.p + k * n, out[k], 1, n, n, "hc_get_enkf_relaxation")) return rc;
+    return HC_OK;
 }
 
 // The path's one collective without torch: a single process that drives several devices (one handle each) sums the

@@ -9,7 +9,7 @@ all-reduce of the per-row water-table moments (see :func:`allreduce_moments`).
 import numpy as np
 
 from .digest import inverse_retention
-from .stepper import (ENKF_WIDTH, SM_WIDTH, EnsembleStepper, enkf_sm_summary, enkf_summary, filter_summary,
+from .stepper import (ENKF_METHODS, ENKF_WIDTH, SM_WIDTH, EnsembleStepper, enkf_sm_summary, enkf_summary, filter_summary,
                       moments_to_mean_std, wtd_distribution)
 
 
@@ -106,13 +106,16 @@ class _Run:
     enkf_soil_moisture: a soil-moisture record (stepper.soil_moisture_record: ``nodes``, ``values`` [T][n], ``sigma``,
     ``depths_cm``) that joins the well in the EnKF's analyses; :meth:`enkf_sm_table`, the ``sm_*`` keys of
     :meth:`enkf_summary`.
+    enkf_method: "stochastic" (perturbed observations, the default) or "sqrt" (the deterministic square-root analysis);
+    enkf_relaxation: the relaxation to prior spread alpha in [0, 1] (default 0 = none) of either
+    (include/hydrocol.h hc_set_enkf_method); both need the EnKF.
     ``_lead`` is the leading shape of the per-point tables: () for an ensemble, (P,) for a sweep."""
 
     _lead = ()
 
     def _start_tables(self, profile_stride, wtd_hist_stride, filter_stride=0, filter_sigma_cm=None, filter_seed=None,
                       enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None,
-                      enkf_soil_moisture=None):
+                      enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0):
         self.profile_stride = int(profile_stride)
         if self.profile_stride:
             self.stepper.set_profile_stats(self.profile_stride)
@@ -137,6 +140,11 @@ class _Run:
         if self.enkf_soil_moisture is not None:
             sm = self.enkf_soil_moisture
             self.stepper.set_enkf_soil_moisture(sm["nodes"], sm["values"], sm["sigma"])
+        self.enkf_method, self.enkf_relaxation = str(enkf_method), float(enkf_relaxation)
+        if (self.enkf_method, self.enkf_relaxation) != ("stochastic", 0.0):
+            if not self.enkf_stride:
+                raise ValueError("enkf_method / enkf_relaxation need the EnKF (enkf_stride > 0)")
+            self.stepper.set_enkf_method(self.enkf_method, self.enkf_relaxation)
 
     def advance(self, n_rows, **kw):
         """Solve the next ``n_rows`` forcing rows for every member."""
@@ -190,9 +198,10 @@ class _Run:
         """The EnKF's record (stepper.enkf_summary, means at the well's depths): ``rows``, ``count``, ``prior_mean_cm``,
         ``prior_std_cm``, ``innovation_cm``, ``loglik_rows``, ``post_mean_cm``, ``post_std_cm``, ``rejected`` over the
         analysed rows and ``loglik``, the log marginal likelihood of the well record (log cm^-1), with a leading [P] for a
-        sweep; ``table``: e.g. the one assembled over ranks."""
+        sweep, and the analysis scheme, ``method`` and ``relaxation``; ``table``: e.g. the one assembled over ranks."""
         t = self.enkf_table() if table is None else table
         out = enkf_summary(t, self.enkf_stride, self.enkf_sigma_cm, float(self.cols.z[0]))
+        out.update(method=self.enkf_method, relaxation=self.enkf_relaxation)
         if self.enkf_soil_moisture is not None:
             out.update(("sm_" + k, v) for k, v in self.enkf_sm_summary(sm_table).items())
         return out
@@ -226,10 +235,11 @@ class EnsembleSimulation(_Run):
     def __init__(self, cols, forcing, n_members, seed=0, device=0, member_offset=0, psi0=None, flags=None,
                  noise="philox", spinup="shared", profile_stride=0, wtd_hist_stride=0, filter_stride=0,
                  filter_sigma_cm=None, filter_seed=None, enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0,
-                 enkf_seed=None, enkf_soil_moisture=None):
+                 enkf_seed=None, enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0):
         self._start(cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup)
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
-                           enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture)
+                           enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
+                           enkf_relaxation)
 
     def _start(self, cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup):
         if noise not in ("philox", "numpy") or spinup not in ("shared", "member"):
@@ -339,6 +349,9 @@ class EnsembleSimulation(_Run):
             arrays["enkf_localisation_cm"] = np.array(self.enkf_localisation_cm, dtype=np.float64)
             arrays["enkf_seed"] = np.array(self.enkf_seed, dtype=np.uint64)
             arrays["enkf_table"] = self.stepper.enkf_table()
+            if (self.enkf_method, self.enkf_relaxation) != ("stochastic", 0.0):     # (a default run keeps its key set)
+                arrays["enkf_method"] = np.array(ENKF_METHODS.index(self.enkf_method), dtype=np.int64)
+                arrays["enkf_relaxation"] = np.array(self.enkf_relaxation, dtype=np.float64)
             if self.enkf_soil_moisture is not None:       # the record itself is supplied again at restore
                 arrays["enkf_sm_nodes"] = np.asarray(self.enkf_soil_moisture["nodes"], dtype=np.int32)
                 arrays["enkf_sm_table"] = self.stepper.enkf_sm_table()
@@ -375,6 +388,8 @@ class EnsembleSimulation(_Run):
         if enkf:
             fkw.update(enkf_stride=enkf, enkf_sigma_cm=float(data["enkf_sigma_cm"]),
                        enkf_localisation_cm=float(data["enkf_localisation_cm"]), enkf_seed=int(data["enkf_seed"]))
+        if enkf and "enkf_method" in data:
+            fkw.update(enkf_method=ENKF_METHODS[int(data["enkf_method"])], enkf_relaxation=float(data["enkf_relaxation"]))
         has_sm = enkf and "enkf_sm_table" in data
         if has_sm != (enkf_soil_moisture is not None):
             raise ValueError(f" EnsembleSimulation: {path} was written {'with' if has_sm else 'without'} a soil-moisture "
@@ -495,7 +510,7 @@ class SweepSimulation(_Run):
     def __init__(self, cols_list, forcing, n_members, seed=0, device=0, first_point=0, flags=None, psi0=None,
                  point_ids=None, profile_stride=0, wtd_hist_stride=0, filter_stride=0, filter_sigma_cm=None,
                  filter_seed=None, enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None,
-                 enkf_soil_moisture=None):
+                 enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0):
         self.points = list(cols_list)
         self.P, self.n = len(self.points), int(n_members)
         self._lead = (self.P,)
@@ -523,7 +538,8 @@ class SweepSimulation(_Run):
         if self.P > 1:
             self.stepper.set_point_member_bases(self.bases)
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
-                           enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture)
+                           enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
+                           enkf_relaxation)
         self.next_row, self.kernel_ms, self.launches = 1, 0.0, 0
 
     def _spinup(self, flags):

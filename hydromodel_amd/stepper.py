@@ -79,6 +79,7 @@ class EnsembleStepper:
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = 0, 0.0, 0
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
         self.enkf_sm_nodes = None
+        self.enkf_method, self.enkf_relaxation = "stochastic", 0.0
         if profile_stride:
             self.set_profile_stats(profile_stride)
 
@@ -337,6 +338,7 @@ class EnsembleStepper:
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = 0, 0.0, 0
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
         self.enkf_sm_nodes = None
+        self.enkf_method, self.enkf_relaxation = "stochastic", 0.0
 
     def filter_table(self):
         """[P][n_arow][4] float64: count, ESS, log-likelihood increment, survivors per assimilation slot (slot j <-> row
@@ -398,6 +400,7 @@ class EnsembleStepper:
             raise ValueError("the particle filter is on: the EnKF and the filter exclude each other")
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
         self.enkf_sm_nodes = None                             # hc_set_enkf removes the sensor record
+        self.enkf_method, self.enkf_relaxation = "stochastic", 0.0       # ... and resets the analysis scheme
         L.check(self.lib.hc_set_enkf(self.h, stride, sigma, loc, int(seed) & 0xFFFFFFFFFFFFFFFF))
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = stride, sigma, loc, int(seed)
 
@@ -430,6 +433,48 @@ class EnsembleStepper:
         out = np.zeros(self.N)
         L.check(self.lib.hc_get_enkf_eps(self.h, L.dptr(out)))
         return out
+
+    # -- the EnKF's analysis scheme and relaxation to prior spread (include/hydrocol.h hc_set_enkf_method) --------------
+    def set_enkf_method(self, method="stochastic", relaxation=0.0):
+        """``method``: "stochastic" (perturbed observations) or "sqrt" (the deterministic square-root analysis: nothing
+        is drawn, the EnKF seed does not matter); ``relaxation``: the RTPS factor alpha in [0, 1] (0 = none): after each
+        analysis every node's spread becomes (1 - alpha) sigma_a + alpha sigma_b.  The EnKF must be on (:meth:`set_enkf`
+        first; it resets both)."""
+        if method not in ENKF_METHODS:
+            raise ValueError(f"EnKF method = {method!r} must be one of {list(ENKF_METHODS)}")
+        alpha = float(relaxation)
+        if not (np.isfinite(alpha) and 0.0 <= alpha <= 1.0):
+            raise ValueError(f"EnKF relaxation = {relaxation!r} must be a finite number in [0, 1]")
+        L.check(self.lib.hc_set_enkf_method(self.h, ENKF_METHODS.index(method), alpha))
+        self.enkf_method, self.enkf_relaxation = method, alpha
+
+    def get_enkf_method(self):
+        """(method, relaxation) as the library holds them."""
+        m, a = np.zeros(1, dtype=np.int32), np.zeros(1)
+        L.check(self.lib.hc_get_enkf_method(self.h, L.iptr(m), L.dptr(a)))
+        return ENKF_METHODS[int(m[0])], float(a[0])
+
+    def enkf_width(self):
+        """m' of the last analysis: 1 + the sensors present on it."""
+        return self.enkf_sm_width() or 1
+
+    def enkf_sqrt_gain(self):
+        """[P][D][m'] the reduced gain of the last analysis, a square-root one (test hook)."""
+        out = np.zeros((self.P, self.D, self.enkf_width()))
+        L.check(self.lib.hc_get_enkf_sqrt_gain(self.h, L.dptr(out)))
+        return out
+
+    def enkf_sqrt_shift(self):
+        """[P][D] the mean's increment of the last analysis, a square-root one (test hook)."""
+        out = np.zeros((self.P, self.D))
+        L.check(self.lib.hc_get_enkf_sqrt_shift(self.h, L.dptr(out)))
+        return out
+
+    def enkf_relaxation_factors(self):
+        """(sigma_b, sigma_a, f), [P][D] each, of the last analysis, a relaxed one (test hook)."""
+        out = np.zeros((3, self.P, self.D))
+        L.check(self.lib.hc_get_enkf_relaxation(self.h, L.dptr(out[0]), L.dptr(out[1]), L.dptr(out[2])))
+        return out[0], out[1], out[2]
 
     # -- soil-moisture sensors in the EnKF analysis (include/hydrocol.h hc_set_enkf_soil_moisture) ----------------------
     def set_enkf_soil_moisture(self, nodes, values=None, sigma=None):
@@ -726,6 +771,7 @@ def filter_summary(table, stride, sigma_cm):
 
 # ---- ensemble Kalman filter on the host (include/hydrocol.h hc_set_enkf) -----------------------------------------------
 ENKF_WIDTH = 8
+ENKF_METHODS = ("stochastic", "sqrt")      # hc_set_enkf_method's 0 and 1
 
 
 def gaspari_cohn(r):

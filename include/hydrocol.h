@@ -46,6 +46,9 @@
  *                      <- (new) the same conditioning by a stochastic ensemble Kalman filter on a continuous water table
  *   hc_set_enkf_soil_moisture, hc_get/set_enkf_sm_stats, hc_get_enkf_sm_width/y/gain/eps
  *                      <- (new) theta_vol (src/simulation.py:623) at sensor depths joins the well in the EnKF's analysis
+ *   hc_set/get_enkf_method, hc_get_enkf_sqrt_gain/shift, hc_get_enkf_relaxation
+ *                      <- (new) the EnKF's analysis scheme (perturbed observations or square root) and its relaxation to
+ *                         prior spread
  *
  * Conventions: every function returns 0 on success or a negative hc_status; nothing throws
  * or aborts across the boundary; hc_last_error() gives the thread-local message.  Host
@@ -462,6 +465,50 @@ int hc_get_enkf_sm_width(hc_handle *h, int32_t *width);
 int hc_get_enkf_sm_y(hc_handle *h, double *y);
 int hc_get_enkf_sm_gain(hc_handle *h, double *gain);
 int hc_get_enkf_sm_eps(hc_handle *h, double *eps);
+
+/* The EnKF's analysis scheme and its relaxation to prior spread, for every analysis row of hc_set_enkf (well alone or
+ * with sensors, m' = 1 + m_s).  Notation per point as above: N_p members, Ybar, the tapered cross-covariance row c_d =
+ * (rho o C_psiY)_d, S = rho o C_YY + R = L L^T (the Cholesky factor of the gain), K_d = c_d S^-1, o = (z[o], theta_obs,i)
+ * the UNPERTURBED observations, R^1/2 = diag(sigma_cm, sigma_i).
+ *   method 0, stochastic: the perturbed-observation update of hc_set_enkf / hc_set_enkf_soil_moisture.
+ *   method 1, square root (Whitaker & Hamill 2002, eq. 10, with the Cholesky factor as the square root of S): the mean
+ *   moves by the Kalman gain, the anomalies by a reduced gain, nothing is drawn:
+ *     dbar_d  = sum_i K_di (o_i - Ybar_i)                       (i in order)
+ *     Kr_d    = c_d L^-T (L + R^1/2)^-1                         (the forward substitution of K_d, then a backward
+ *                                                                substitution with the lower-triangular L + R^1/2)
+ *     psi_dk <- psi_dk + dbar_d + sum_i Kr_di (Ybar_i - Y_ki)   (i in order)
+ *   For m' = 1: Kr = K / (1 + sqrt(sigma^2 / s)).  No Philox counter is consumed: the analysis does not depend on the
+ *   EnKF seed.  A failed factorisation gives NaN (K, Kr, dbar) and every member is rejected, as for method 0; the vote
+ *   on a member's column (a non-finite entry: the forecast stays, counted as rejected) is the same.  The
+ *   log-likelihood, the prior diagnostics and the rejection rule describe the forecast and do not change.
+ *   relaxation = alpha in [0, 1] (RTPS, Whitaker & Hamill 2012), either method: after the update, per point and node d,
+ *   over the columns the members kept,
+ *     sigma_b_d, sigma_a_d = the sample std (N_p - 1) of psi_d before / after the update (two passes each: mean, then
+ *                            squared anomalies; N_p = 1: 0; after the update the columns are summed relative to the
+ *                            point's first member, so that a node on which every member agrees -- a saturated tail --
+ *                            has sigma_a = 0 exactly and is left alone),
+ *     f_d = 1 + alpha (sigma_b_d - sigma_a_d) / sigma_a_d   (f_d = 1 where sigma_a_d is 0 or not finite, where N_p = 1,
+ *                                                            and for a point whose factorisation failed),
+ *     psi_dk <- psibar_d + f_d (psi_dk - psibar_d), psibar_d the mean after the update; a node with f_d = 1 keeps its
+ *     bits; a member whose relaxed column has a non-finite entry keeps its unrelaxed analysis (it is not counted as
+ *     rejected).
+ *   so that the node's std becomes (1 - alpha) sigma_a + alpha sigma_b.  The posterior entries of both tables (the
+ *   EnKF's 5-7, the sensors' posterior mean and std) then describe the RELAXED ensemble.  Every sum follows the tile rule
+ *   of hc_set_enkf (tiles of 256 members in member order, 1024 threads in tile-strided order, a fixed tree, no
+ *   floating-point atomics, contraction off): the same bits at any launch length, point order or member split.
+ *   With (0, 0), the state after hc_set_enkf, an analysis is that of hc_set_enkf to the bit and launches nothing more.
+ * hc_set_enkf_method: needs the EnKF on (hc_set_enkf first); HC_ERR_ARG for another method, or a relaxation outside
+ *   [0, 1] or not finite.  Reset to (0, 0) by whatever turns the EnKF off or re-creates it (hc_set_enkf included), like
+ *   the sensor record.  hc_get_enkf_method: the two settings ((0, 0) while the EnKF is off).
+ * Test hooks of the last analysis: hc_get_enkf_sqrt_gain [P][D][m'] (Kr) and hc_get_enkf_sqrt_shift [P][D] (dbar),
+ *   HC_ERR_ARG unless it was a square-root analysis; hc_get_enkf_relaxation: sigma_b, sigma_a and f, [P][D] each,
+ *   HC_ERR_ARG unless it relaxed.  hc_get_enkf_gain / hc_get_enkf_sm_gain keep returning K.  After a square-root
+ *   analysis hc_get_enkf_eps / hc_get_enkf_sm_eps fail (HC_ERR_ARG), like a call before any analysis. */
+int hc_set_enkf_method(hc_handle *h, int32_t method, double relaxation);
+int hc_get_enkf_method(hc_handle *h, int32_t *method, double *relaxation);
+int hc_get_enkf_sqrt_gain(hc_handle *h, double *gain);
+int hc_get_enkf_sqrt_shift(hc_handle *h, double *shift);
+int hc_get_enkf_relaxation(hc_handle *h, double *sigma_b, double *sigma_a, double *factor);
 
 /* The path's one collective inside the library, for a single process that drives several devices with
  * one handle each: every handle's moment table is replaced by the sum over all n handles (ncclAllReduce, ncclInt64,

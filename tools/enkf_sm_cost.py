@@ -4,7 +4,7 @@ one handle each, back to back on one GPU.
 
     python tools/enkf_sm_cost.py [--members 262144] [--depth 300] [--days 30] [--warmup 1] [--runs 0,48s,0,48s]
                                  [--sensors 30,60,120] [--sigma 10] [--sm-sigma 0.02] [--localisation 0] [--spread-cm 0]
-                                 [--json out.json]
+                                 [--method stochastic|sqrt] [--relaxation 0] [--json out.json]
 
 Same set-up as tools/filter_cost.py and bench.py's timed region: synthetic 10-year forcing, Philox noise, the shared
 initial condition of the well's digest (tests/golden/g1_tables_<depth>.npz where it exists, else the hydrostatic profile),
@@ -17,7 +17,8 @@ well and the sensors at --sensors cm, every sensor observed on every analysis ro
 node, held fixed -- the cost does not depend on the values); a run may be listed more than once (e.g. 0,48,0,48 to
 alternate); `kept` is a run's rate over the mean of the stride-0 runs.  --spread-cm W starts every member from the
 initial profile shifted by its own offset, uniform over +-W cm.  Under `rocprofv3 --kernel-trace --stats` run it with
---runs 48s (or 48) --days 1 --warmup 0 for the per-kernel time of the analyses.  Prints one JSON line.
+--runs 48s (or 48) --days 1 --warmup 0 for the per-kernel time of the analyses.  --method / --relaxation: the analysis
+scheme of every EnKF run (hc_set_enkf_method; the defaults do not call it).  Prints one JSON line.
 """
 import argparse
 import json
@@ -31,7 +32,8 @@ REPO = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(REPO))
 
 
-def run(cols, forcing, psi0, members, stride, sigma, loc, warmup_days, days, spread_cm=0.0, seed=2024, sensors=None):
+def run(cols, forcing, psi0, members, stride, sigma, loc, warmup_days, days, spread_cm=0.0, seed=2024, sensors=None,
+        method="stochastic", relaxation=0.0):
     from hydromodel_amd.stepper import EnsembleStepper, enkf_sm_summary, enkf_summary
     st = EnsembleStepper(cols, forcing, members)
     try:
@@ -45,6 +47,8 @@ def run(cols, forcing, psi0, members, stride, sigma, loc, warmup_days, days, spr
             st.set_enkf(stride, sigma, loc, seed)
         if stride and sensors is not None:
             st.set_enkf_soil_moisture(sensors["nodes"], sensors["values"], sensors["sigma"])
+        if stride and (method, relaxation) != ("stochastic", 0.0):
+            st.set_enkf_method(method, relaxation)
         row = 1
         if warmup_days:
             st.step_rows(row, 48 * warmup_days)
@@ -86,6 +90,8 @@ def main():
     ap.add_argument("--sigma", type=float, default=10.0)
     ap.add_argument("--localisation", type=float, default=0.0)
     ap.add_argument("--spread-cm", type=float, default=0.0)
+    ap.add_argument("--method", default="stochastic", choices=("stochastic", "sqrt"))
+    ap.add_argument("--relaxation", type=float, default=0.0)
     ap.add_argument("--json", default="")
     args = ap.parse_args()
     from hydromodel_amd.digest import ColumnTables, ForcingDigest
@@ -108,7 +114,8 @@ def main():
     rec = soil_moisture_record(cols.z, depths, np.zeros((forcing.dim_t, len(depths))), args.sm_sigma)
     rec["values"][:] = theta0[rec["nodes"]][None, :]
     recs = [run(cols, forcing, psi0, args.members, int(s.rstrip("s")), args.sigma, args.localisation, args.warmup,
-                args.days, args.spread_cm, sensors=rec if s.endswith("s") else None)
+                args.days, args.spread_cm, sensors=rec if s.endswith("s") else None, method=args.method,
+                relaxation=args.relaxation)
             for s in args.runs.split(",")]
     base = [r for r in recs if r["stride"] == 0]
     if base:
@@ -120,7 +127,8 @@ def main():
                 r["sm_ms_per_analysis" if r["sensors"] else "enkf_ms_per_analysis"] = (r["other_ms"] - other) / r["analyses"]
     line = json.dumps({"members": args.members, "depth": args.depth, "days": args.days, "sigma_cm": args.sigma,
                        "localisation_cm": args.localisation, "spread_cm": args.spread_cm, "sensors_cm": depths,
-                       "sensor_nodes": rec["nodes"].tolist(), "sm_sigma": args.sm_sigma,
+                       "sensor_nodes": rec["nodes"].tolist(), "sm_sigma": args.sm_sigma, "method": args.method,
+                       "relaxation": args.relaxation,
                        "runs": recs})
     print(line)
     if args.json:
