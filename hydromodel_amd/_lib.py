@@ -118,6 +118,16 @@ EXPORTS = {
     "hc_get_enkf_sqrt_gain": ([C.c_void_p, _dp], C.c_int),
     "hc_get_enkf_sqrt_shift": ([C.c_void_p, _dp], C.c_int),
     "hc_get_enkf_relaxation": ([C.c_void_p, _dp, _dp, _dp], C.c_int),
+    "hc_set_enkf_window": ([C.c_void_p, C.c_int32, _ip], C.c_int),
+    "hc_get_enkf_window_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),
+    "hc_set_enkf_window_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),
+    "hc_get_enkf_window_capture": ([C.c_void_p, _dp, _lp], C.c_int),
+    "hc_set_enkf_window_capture": ([C.c_void_p, _dp, _lp], C.c_int),
+    "hc_get_enkf_width": ([C.c_void_p, _ip], C.c_int),
+    "hc_get_enkf_window_width": ([C.c_void_p, _ip, _ip], C.c_int),
+    "hc_get_enkf_window_y": ([C.c_void_p, _dp], C.c_int),
+    "hc_get_enkf_window_eps": ([C.c_void_p, _dp], C.c_int),
+    "hc_get_enkf_window_gain": ([C.c_void_p, _dp], C.c_int),
     "hc_rhs": ([C.c_void_p, C.c_int64, C.c_int32, _dp, _dp], C.c_int),
     "hc_model_nodes": ([C.c_void_p, _dp, _dp], C.c_int),
     "hc_plugin_eval": ([C.c_int, C.POINTER(ColumnParams), C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp],

@@ -70,6 +70,15 @@ unknown keys, only membership of the 12 is checked):
   [0, 1] (default 0 = none), for either method: after each analysis every node's spread is (1 - alpha) sigma_a + alpha
   sigma_b, and the posterior datasets describe the relaxed ensemble.  Added to ``<Output_Name>_ensemble.h5`` when either
   is given: ``enkf_method`` (0 = stochastic, 1 = sqrt) and ``enkf_relaxation``.
+* ``"EnKF": {..., "Window_Offsets": [12, 24, 36]}``: the well's record inside the window (the asynchronous EnKF of Sakov,
+  Evensen & Bertino 2010; include/hydrocol.h hc_set_enkf_window).  Each entry is a number of rows before the analysis
+  row: distinct integers in [1, ``Stride``), at most 8, and at most 8 together with the ``Soil_Moisture`` depths.  On such a
+  row, if it has an observation, every member's water table is recorded when the row is solved, and joins the next
+  analysis as one more well observation (error ``Sigma_cm``, errors taken as uncorrelated).  Without the key, or with an
+  empty list, nothing changes.  Added to ``<Output_Name>_ensemble.h5``: ``enkf_window_offsets`` ``[n]`` (ascending) and,
+  over the ``enkf_rows`` ``[R]``, ``enkf_window_observed``, ``enkf_window_obs_cm``, ``enkf_window_prior_mean_cm``,
+  ``enkf_window_prior_std_cm``, ``enkf_window_innovation_cm`` ``[R][n]`` (NaN where the offset's row took no part; a sweep:
+  a leading ``[P]`` axis), and the run ends with `` [Ensemble xN] EnKF window: K lagged observations over R rows``.
 * ``"Ensemble": {"repair_predict": true}`` with ``Simulation_Flags.PREDICT``: run the repaired predictive lateral flow
    instead of raising the reference's ``TypeError``.
 """
@@ -132,6 +141,7 @@ def main(params_file=None, data_file=None, seed=None, device=0, gpus=None, _sett
             enkf_settings(params["Ensemble"], n_gpus)       # and a bad EnKF block
             soil_moisture_settings(params["Ensemble"], n_gpus)
             enkf_method_settings(params["Ensemble"])
+            enkf_window_settings(params["Ensemble"])
         ranks = multigpu.Ranks(expect=n_gpus if (n_gpus > 1 or multigpu.in_rank()) else None)
         if ranks.world > 1:
             device = ranks.device_index()
@@ -192,6 +202,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     enkf = enkf_settings(ens, ranks.world)
     sm = soil_moisture_settings(ens, ranks.world)
     scheme = enkf_method_settings(ens)
+    window = enkf_window_settings(ens)
     cols = ColumnTables(params, load_site_well(params))
     forcing = ForcingDigest(params, water_data, cols)
     record = soil_moisture_record_of(sm, cols, water_data)      # before any GPU call
@@ -202,7 +213,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     rows = min(days * 48, forcing.dim_t - 1)
     if ens.get("Points"):
         return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels, filt,
-                          enkf, record, scheme)
+                          enkf, record, scheme, window)
     lo, hi = multigpu.shard(n_members, ranks.rank, ranks.world)
     if hi <= lo:
         raise ValueError(f" Ensemble: {n_members} members do not shard over {ranks.world} GPUs (a rank would be empty).")
@@ -210,7 +221,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     sim = EnsembleSimulation(cols, forcing, hi - lo, seed=int(ens.get("Seed", 0)), device=device, member_offset=lo,
                              noise=str(ens.get("Noise", "philox")).lower(),
                              spinup=str(ens.get("Spinup", "shared")).lower(), profile_stride=stride,
-                             wtd_hist_stride=dist_stride, **_filter_kwargs(filt), **_enkf_kwargs(enkf, record, scheme))
+                             wtd_hist_stride=dist_stride, **_filter_kwargs(filt), **_enkf_kwargs(enkf, record, scheme, window))
     label = f"Ensemble x{n_members}"
     _step_all(sim, rows, label, ranks)
     # the run's one collective: int64 (count, sum idx, sum idx^2) per row, exact and order-independent
@@ -245,6 +256,9 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     extra.update(_enkf_method_arrays(enkf, scheme))
     stables, sm_line = _reduce_enkf_sm(ranks, sim, [0], 1, forcing.dim_t, enkf, record, label, keep_points=False)
     extra.update(stables)
+    wtables, window_line = _reduce_enkf_window(ranks, sim, [0], 1, forcing.dim_t, enkf, window, label, keep_points=False,
+                                               z0_cm=cols.z[0])
+    extra.update(wtables)
     arrays = dict(moments=moments, wtd_mean_cm=mean_cm, wtd_std_cm=std_cm, rows=np.array(rows),
                   members=np.array(n_members), gpus=np.array(ranks.world), initial_cond=psi0, **extra)
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "ensemble water-table statistics", ranks)
@@ -256,6 +270,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
         print(enkf_line)
     if sm_line:
         print(sm_line)
+    if window_line:
+        print(window_line)
     sim.close()
 
 
@@ -330,7 +346,7 @@ def filter_settings(ens, n_gpus=1):
     return stride, float(sigma), (None if seed is None else int(seed))
 
 
-ENKF_KEYS = ("Stride", "Sigma_cm", "Localisation_cm", "Seed", "Soil_Moisture", "Method", "Relaxation")
+ENKF_KEYS = ("Stride", "Sigma_cm", "Localisation_cm", "Seed", "Soil_Moisture", "Method", "Relaxation", "Window_Offsets")
 
 
 def enkf_settings(ens, n_gpus=1):
@@ -398,7 +414,60 @@ def enkf_method_settings(ens):
     return method, float(alpha)
 
 
-def _enkf_kwargs(enkf, record=None, scheme=None):
+def enkf_window_settings(ens):
+    """Ensemble.EnKF.Window_Offsets -> the offsets as an ascending tuple, or None when the key is absent or the list empty
+    (the run, its file and its lines are then those of a block without it).  Pure, like :func:`enkf_settings`: a bad
+    value is a ValueError (message + exit status 1): not a list; an entry that is not an integer (a boolean, a float) or
+    outside [1, Stride); a repeated entry; more than 8, alone or together with the Soil_Moisture depths.  Needs an active
+    EnKF."""
+    from numbers import Real
+    from .stepper import enkf_window_settings as window_of
+    block = ens.get("EnKF")
+    if not isinstance(block, dict) or block.get("Window_Offsets") is None:
+        return None
+    stride = block.get("Stride", 48)
+    stride = int(stride) if isinstance(stride, Real) and not isinstance(stride, bool) and stride == int(stride) else 0
+    if not stride:
+        raise ValueError(" Ensemble: EnKF.Window_Offsets needs an active EnKF (EnKF.Stride > 0).")
+    sm = block.get("Soil_Moisture")
+    depths = sm.get("Depths_cm") if isinstance(sm, dict) else None
+    try:
+        off = window_of(block["Window_Offsets"], stride, len(depths) if isinstance(depths, (list, tuple)) else 0)
+    except ValueError as bad:
+        raise ValueError(f" Ensemble: {bad}.") from None
+    return off or None
+
+
+def _reduce_enkf_window(ranks, sim, ids, P, T, enkf, window, label, keep_points, z0_cm):
+    """The window's datasets from this rank's handle over the EnKF's analysed rows (its ``enkf_rows``), the [P] table
+    placed and summed over the ranks like the EnKF's (float64 as int64 bits), and the closing line (rank 0)."""
+    import numpy as np
+    from .multigpu import place_points
+    from .stepper import ENKF_WIDTH, WINDOW_WIDTH, stride_rows
+    stride = enkf[0]
+    if not stride or not window:
+        return {}, None
+    n, n_arow = len(window), stride_rows(T, stride)
+    local = (sim.enkf_window_table().reshape(-1, n_arow, n, WINDOW_WIDTH) if sim is not None
+             else np.zeros((0, n_arow, n, WINDOW_WIDTH)))
+    table = place_points(local, ids, P, ranks)
+    etab = sim.enkf_table().reshape(-1, n_arow, ENKF_WIDTH) if sim is not None else np.zeros((0, n_arow, ENKF_WIDTH))
+    used = place_points(etab, ids, P, ranks)[..., 0] > 0
+    slots = np.flatnonzero(used.any(axis=0))               # the enkf_rows of _reduce_enkf
+    sel = table[:, slots] if keep_points else table[0, slots]
+    observed = sel[..., 0] == 1.0
+    out = {"enkf_window_offsets": np.asarray(window, dtype=np.int64), "enkf_window_observed": observed.astype(np.int8),
+           "enkf_window_obs_cm": sel[..., 1] + float(z0_cm), "enkf_window_prior_mean_cm": sel[..., 2] + float(z0_cm),
+           "enkf_window_prior_std_cm": sel[..., 3], "enkf_window_innovation_cm": sel[..., 1] - sel[..., 2]}
+    if ranks.rank != 0:
+        return out, None
+    first = table[0, slots, :, 0] == 1.0                   # the record is the same for every point
+    line = (f" [{label}] EnKF window: {int(first.sum())} lagged observations over {int(first.any(axis=-1).sum())} rows "
+            f"(offsets {list(window)})")
+    return out, line
+
+
+def _enkf_kwargs(enkf, record=None, scheme=None, window=None):
     stride, sigma, loc, seed = enkf
     if not stride:
         return {}
@@ -407,6 +476,8 @@ def _enkf_kwargs(enkf, record=None, scheme=None):
         kw["enkf_soil_moisture"] = record
     if scheme is not None:
         kw.update(enkf_method=scheme[0], enkf_relaxation=scheme[1])
+    if window:
+        kw["enkf_window_offsets"] = window
     return kw
 
 
@@ -710,7 +781,7 @@ def _reduce_optional(ranks, sim, ids, cols_all, forcing, stride, dist_stride, di
 
 
 def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride=0, dist_levels=None,
-               filt=(0, None, None), enkf=(0, None, None, None), record=None, scheme=None):
+               filt=(0, None, None), enkf=(0, None, None, None), record=None, scheme=None, window=None):
     """Parameter points x members: this rank's points in one handle (ensemble.SweepSimulation), the whole table assembled
     over the ranks (multigpu.assemble_points)."""
     import numpy as np
@@ -737,7 +808,7 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     if mine:
         sim = SweepSimulation(points, forcing, n_members, seed=int(ens.get("Seed", 0)), device=device, point_ids=mine,
                               profile_stride=stride, wtd_hist_stride=dist_stride, **_filter_kwargs(filt),
-                              **_enkf_kwargs(enkf, record, scheme))
+                              **_enkf_kwargs(enkf, record, scheme, window))
         _step_all(sim, rows, label, ranks)
         table = sim.moments()
         for j, k in enumerate(mine):
@@ -759,6 +830,9 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     stables, sm_line = _reduce_enkf_sm(ranks, sim, mine, P, T, enkf, record, label, keep_points=True)
     arrays.update(stables)
     arrays.update(_enkf_method_arrays(enkf, scheme))
+    wtables, window_line = _reduce_enkf_window(ranks, sim, mine, P, T, enkf, window, label, keep_points=True,
+                                               z0_cm=cols_all[0].z[0])
+    arrays.update(wtables)
     if sim is not None:
         sim.close()
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "sweep's water-table statistics", ranks)
@@ -770,6 +844,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
         print(enkf_line)
     if sm_line:
         print(sm_line)
+    if window_line:
+        print(window_line)
 
 
 def run_cli(argv=None):
@@ -794,6 +870,7 @@ def run_cli(argv=None):
                 enkf_settings(settings["Ensemble"], n_gpus)
                 soil_moisture_settings(settings["Ensemble"], n_gpus)
                 enkf_method_settings(settings["Ensemble"])
+                enkf_window_settings(settings["Ensemble"])
             except ValueError as bad:
                 print(bad)
                 sys.exit(1)

@@ -206,6 +206,16 @@ struct hc_handle {
     std::vector<double> sm_sigma, sm_values;
     int sm_width = 0;
     AccTable<double> sm{"entries"};
+    // the well's record inside the window (hc_set_enkf_window): the offsets, ascending; each member's y of the lagged
+    // rows [win_n][N] and the row each slot holds (-1: none; cleared by the analysis); diagnostics float64
+    // [P][n_arow][win_n][4] keyed like the EnKF's; the last analysis's lagged columns (their slots, in column order) and
+    // draws [N][m_w]
+    int win_n = 0;
+    std::vector<int> win_off;
+    std::vector<int64_t> win_row;
+    DevBuf<double> win_y, enkf_eps_w;
+    std::vector<int> win_last;
+    AccTable<double> win{"entries"};
     int n_cu = 256;
     double jac_reject = NUM_JAC_DIFF_REJECT;
 };
@@ -834,15 +844,23 @@ constexpr int ENKF_SENSORS = 8;                        // sensors in a record
 constexpr int ENKF_OBS = ENKF_SENSORS + 1;             // observations per member: the well, then the sensors present
 constexpr int ENKF_SENSOR_WIDTH = 6;                   // sensor diagnostics per point, slot and sensor
 
-// the observations of one analysis row beyond the well's, in record order (a kernel argument).  A row without a sensor
-// value (m = 0) is the well alone and leaves everything of the sensors -- their draws, their table -- untouched.
+constexpr int ENKF_WINDOW_WIDTH = 4;                   // window diagnostics per point, slot and offset
+
+// the observations of one analysis row beyond the well's (a kernel argument): the present sensors in record order, then
+// the present lagged rows of the window by ascending offset (hc_set_enkf_window).  A row without a sensor value (ms = 0)
+// leaves everything of the sensors -- their draws, their table -- untouched, and so does one without a lagged row
+// (m = ms) for the window.  A lagged column k >= ms is a well-type observation: obs[k] = z[wtd_obs[r_j]] is also the
+// centre of its taper, sigma[k] the well's sigma_cm, wrow[k] = r_j the row word of its draw.
 struct EnkfRow {
-    int m;                     // present sensors m_s (m' = m_s + 1)
-    int n;                     // sensors drawn for and recorded: the record's, 0 when m = 0
-    int sensor[ENKF_SENSORS];  // record index of present sensor k
+    int m;                     // columns beyond the well's, m_s + m_w (m' = m + 1)
+    int n;                     // sensors drawn for and recorded: the record's, 0 when ms = 0
+    int sensor[ENKF_SENSORS];  // record index of present sensor k; k >= ms: the offset's index
     int node[ENKF_SENSORS];
     double obs[ENKF_SENSORS];
     double sigma[ENKF_SENSORS];
+    int ms;                    // present sensors m_s
+    int nw;                    // offsets recorded: the window's, 0 when m = ms
+    unsigned wrow[ENKF_SENSORS];
 };
 
 // One standard normal of Philox4x32-10 under the EnKF seed at counter (word0, row, gid_lo, gid_hi), with the Box-Muller
@@ -928,8 +946,17 @@ __global__ void enkf_theta_kernel(const double *psi, const ColumnDev *P, const d
     if (m >= n_members) return;
     const long long p = m / mpp;
     const double *nt = node_tabs + (size_t)p * 3 * D;
-    for (int k = 0; k < s.m; k++)
+    for (int k = 0; k < s.ms; k++)
         Y[(size_t)m * width + 1 + k] = enkf_theta(P[p], nt, D, s.node[k], psi[(size_t)m * D + s.node[k]], special);
+}
+
+// Y[m][1 + k] = the y that member m had on lagged row k (k >= ms), as enkf_obs_kernel left it in the window's buffer
+// [offsets][N] when that row was solved
+__global__ void enkf_window_gather_kernel(const double *win_y, long long n_members, const EnkfRow s, double *Y, int width)
+{
+    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n_members) return;
+    for (int k = s.ms; k < s.m; k++) Y[(size_t)m * width + 1 + k] = win_y[(size_t)s.sensor[k] * n_members + m];
 }
 
 // Column sums of X = (psi_0 .. psi_{Dc-1}, Y_0 .. Y_{W-1}) (Dc = 0: Y alone), C = Dc + W columns, tile t of point p:
@@ -1026,7 +1053,8 @@ __global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void enkf_gain_kernel(const dou
                                                                        int D, const EnkfRow s, double sigma, double loc,
                                                                        double z_obs, double dz, double *gain,
                                                                        double *stats, double *sm_stats, long long n_arow,
-                                                                       long long slot, double *rgain, double *dbar)
+                                                                       long long slot, double *rgain, double *dbar,
+                                                                       double *win_stats)
 {
 #pragma clang fp contract(off)
     // the working sets live in LDS (dynamically indexed: in registers they would go to scratch)
@@ -1043,7 +1071,7 @@ __global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void enkf_gain_kernel(const dou
             yb[i] = S1[D + i] / (double)mpp;
             r2[i] = i == 0 ? sigma * sigma : s.sigma[i - 1] * s.sigma[i - 1];
             dl[i] = (i == 0 ? z_obs : s.obs[i - 1]) - yb[i];
-            zeta[i] = i == 0 ? yb[0] : (double)s.node[i - 1] * dz;
+            zeta[i] = i == 0 ? yb[0] : i <= s.ms ? (double)s.node[i - 1] * dz : s.obs[i - 1];
         }
         for (int i = 0; i < W; i++)
             for (int k = 0; k < W; k++) cyy[i * ENKF_OBS + k] = mpp > 1 ? S2[(size_t)(D + i) * W + k] / n1 : 0.0;
@@ -1074,11 +1102,22 @@ __global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void enkf_gain_kernel(const dou
         st[2] = sqrt(cyy[0]);
         st[3] = dl[0];
         st[4] = ll;
-        if (s.m > 0) {
+        if (s.ms > 0) {
             double *ss = sm_stats + ((size_t)p * n_arow + slot) * s.n * ENKF_SENSOR_WIDTH;
             for (int i = 0; i < s.n; i++) ss[i * ENKF_SENSOR_WIDTH] = 0.0;      // observed: 0 unless present (the rest stays NaN)
-            for (int k = 0; k < s.m; k++) {
+            for (int k = 0; k < s.ms; k++) {
                 double *e = ss + s.sensor[k] * ENKF_SENSOR_WIDTH;
+                e[0] = 1.0;
+                e[1] = s.obs[k];
+                e[2] = yb[k + 1];
+                e[3] = sqrt(cyy[(k + 1) * ENKF_OBS + k + 1]);
+            }
+        }
+        if (s.m > s.ms) {
+            double *ws = win_stats + ((size_t)p * n_arow + slot) * s.nw * ENKF_WINDOW_WIDTH;
+            for (int i = 0; i < s.nw; i++) ws[i * ENKF_WINDOW_WIDTH] = 0.0;     // observed: 0 unless present (the rest stays NaN)
+            for (int k = s.ms; k < s.m; k++) {
+                double *e = ws + s.sensor[k] * ENKF_WINDOW_WIDTH;
                 e[0] = 1.0;
                 e[1] = s.obs[k];
                 e[2] = yb[k + 1];
@@ -1153,6 +1192,20 @@ __global__ void enkf_draw_kernel(long long n_members, long long mpp, unsigned lo
     for (int i = 0; i < n; i++) eps_s[(size_t)m * n + i] = enkf_normal_at(0xFFFFFFF0u + (unsigned)i, seed, gid, row);
 }
 
+// eps of the lagged columns, [N][m_w] in column order: the well's own normal with the lagged row in the row word -- the
+// draw the well would have had on that row, which is never an analysis row (an offset is below the stride)
+__global__ void enkf_window_draw_kernel(long long n_members, long long mpp, unsigned long long seed,
+                                        const long long *point_base, long long member_offset, const EnkfRow s,
+                                        double *eps_w)
+{
+    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n_members) return;
+    const unsigned long long gid = point_base ? (unsigned long long)(point_base[m / mpp] + m % mpp)
+                                              : (unsigned long long)(member_offset + m);
+    const int mw = s.m - s.ms;
+    for (int k = 0; k < mw; k++) eps_w[(size_t)m * mw + k] = enkf_normal_at(0xFFFFFFFEu, seed, gid, s.wrow[s.ms + k]);
+}
+
 // One wave per member: the innovations o_k - Y_k from the draws of enkf_draw_kernel, psi_dk + sum_i K_di (o_ki - Y_ki)
 // (i in order) on every node, stored only when every entry is finite (else the forecast stays and the member is counted
 // as rejected); then the find_wtd index and the posterior y of the column it kept: Ypost[m] = (y, ..., rejected)
@@ -1160,17 +1213,19 @@ __global__ void enkf_draw_kernel(long long n_members, long long mpp, unsigned lo
 __global__ __launch_bounds__(256) void enkf_update_kernel(double *psi, const double *Y, const double *gain,
                                                           const ColumnDev *P, long long n_members, long long mpp, int D,
                                                           double dz, double z_obs, double sigma, const EnkfRow s,
-                                                          const double *eps, const double *eps_s, double *Ypost)
+                                                          const double *eps, const double *eps_s,
+                                                          const double *eps_w, double *Ypost)
 {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x % WAVE;
-    const int W = s.m + 1;
-    // lane 1 + k holds present sensor k: its record index, observation and sigma
+    const int W = s.m + 1, V = s.ms + 2, mw = s.m - s.ms;
+    // lane 1 + k holds column k beyond the well's: present sensor k's record index, observation and sigma; a lagged
+    // row's (k >= ms) place among the lagged columns instead of the index
     int my_sensor = 0;
     double my_obs = 0.0, my_sigma = 0.0;
 #pragma unroll
     for (int k = 0; k < ENKF_SENSORS; k++)
-        if (k < s.m && lane == 1 + k) my_sensor = s.sensor[k], my_obs = s.obs[k], my_sigma = s.sigma[k];
+        if (k < s.m && lane == 1 + k) my_sensor = k < s.ms ? s.sensor[k] : k - s.ms, my_obs = s.obs[k], my_sigma = s.sigma[k];
     const long long waves = (long long)gridDim.x * (blockDim.x / WAVE);
     for (long long m = (long long)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE; m < n_members; m += waves) {
         const long long p = m / mpp;
@@ -1192,9 +1247,10 @@ __global__ __launch_bounds__(256) void enkf_update_kernel(double *psi, const dou
         // lane i holds innovation i: the well's on lane 0 (dl0, on every lane too), present sensor k's on lane 1 + k
         const double *Ym = Y + (size_t)m * W;
         const double dl0 = (z_obs + sigma * eps[m]) - Ym[0];
-        const double my_dl = lane == 0  ? dl0
-                             : lane < W ? (my_obs + my_sigma * eps_s[(size_t)m * s.n + my_sensor]) - Ym[lane]
-                                        : 0.0;
+        const double my_dl = lane == 0      ? dl0
+                             : lane <= s.ms ? (my_obs + my_sigma * eps_s[(size_t)m * s.n + my_sensor]) - Ym[lane]
+                             : lane < W     ? (my_obs + my_sigma * eps_w[(size_t)m * mw + my_sensor]) - Ym[lane]
+                                            : 0.0;
 #pragma unroll
         for (int c = 0; c < ENKF_SLOTS; c++) inc[c] = inc[c] * dl0;
 #pragma unroll 1
@@ -1250,10 +1306,10 @@ __global__ __launch_bounds__(256) void enkf_update_kernel(double *psi, const dou
             if (c == b / WAVE) hi = x;
             if (c == bl / WAVE) lo = xl;
         }
-        double *out = Ypost + (size_t)m * (W + 1);
+        double *out = Ypost + (size_t)m * V;
         if (lane == 0) {
             out[0] = enkf_y_of(b, lo, hi, psat, dz);
-            out[W] = keep ? 0.0 : 1.0;
+            out[V - 1] = keep ? 0.0 : 1.0;
         }
     }
 }
@@ -1309,7 +1365,7 @@ __device__ __forceinline__ double enkf_column_y(const double (&a)[ENKF_SLOTS], i
 __global__ __launch_bounds__(256) void enkf_sqrt_update_kernel(double *psi, const double *Y, const double *rgain,
                                                                const double *dbar, const double *s1, const ColumnDev *P,
                                                                long long n_members, long long mpp, int D, double dz,
-                                                               int W, int want_y, double *Ypost)
+                                                               int W, int V, int want_y, double *Ypost)
 {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x % WAVE;
@@ -1351,12 +1407,12 @@ __global__ __launch_bounds__(256) void enkf_sqrt_update_kernel(double *psi, cons
 #pragma unroll
         for (int c = 0; c < ENKF_SLOTS; c++) inc[c] = a[c] + inc[c];
         const bool keep = enkf_keep_column(a, inc, col, lane, D);
-        double *out = Ypost + (size_t)m * (W + 1);
+        double *out = Ypost + (size_t)m * V;
         if (want_y) {
             const double y = enkf_column_y(a, lane, D, P[p].psi_sat, dz);
             if (lane == 0) out[0] = y;
         }
-        if (lane == 0) out[W] = keep ? 0.0 : 1.0;
+        if (lane == 0) out[V - 1] = keep ? 0.0 : 1.0;
     }
 }
 
@@ -1455,14 +1511,14 @@ __global__ void enkf_post_kernel(const double *s1, const double *s2, long long n
 #pragma clang fp contract(off)
     const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n_points) return;
-    const int V = s.m + 2;
+    const int V = s.ms + 2;
     const double *S1 = s1 + (size_t)p * V, *S2 = s2 + (size_t)p * V * V;
     const double n1 = (double)(mpp - 1);
     double *st = stats + ((size_t)p * n_arow + slot) * ENKF_WIDTH;
     st[5] = S1[0] / (double)mpp;
     st[6] = sqrt(mpp > 1 ? S2[0] / n1 : 0.0);
     st[7] = S1[V - 1];
-    for (int k = 0; k < s.m; k++) {
+    for (int k = 0; k < s.ms; k++) {
         double *e = sm_stats + (((size_t)p * n_arow + slot) * s.n + s.sensor[k]) * ENKF_SENSOR_WIDTH;
         e[4] = S1[k + 1] / (double)mpp;
         e[5] = sqrt(mpp > 1 ? S2[(size_t)(k + 1) * V + k + 1] / n1 : 0.0);
@@ -1811,6 +1867,22 @@ int ensure_sm(hc_handle *h)
     return ensure_da_table(h, h->sm, h->enkf_stride, (int64_t)h->sm_n * ENKF_SENSOR_WIDTH, 0);
 }
 
+// the window's diagnostics (hc_set_enkf_window): [P][n_arow][n][4] float64, created as NaN
+int ensure_win(hc_handle *h)
+{
+    if (h->win_n <= 0) return fail(HC_ERR_ARG, "no window offsets (hc_set_enkf_window)");
+    if (int rc = ensure_enkf(h)) return rc;
+    return ensure_da_table(h, h->win, h->enkf_stride, (int64_t)h->win_n * ENKF_WINDOW_WIDTH, 0);
+}
+
+void win_off(hc_handle *h)
+{
+    h->win_n = 0;
+    h->win_off.clear(); h->win_row.clear(); h->win_last.clear();
+    h->win.release();
+    h->win_y.release(); h->enkf_eps_w.release();
+}
+
 void sm_off(hc_handle *h)
 {
     h->sm_n = 0;
@@ -1836,6 +1908,7 @@ void enkf_off(hc_handle *h)
     h->enkf_rgain.release(); h->enkf_dbar.release(); h->enkf_part_sq.release(); h->enkf_sq_b.release();
     h->enkf_sq_a.release(); h->enkf_mean_a.release(); h->enkf_relax.release();
     sm_off(h);
+    win_off(h);
 }
 
 // what turns both filters off: new points, members or noise source (include/hydrocol.h hc_set_filter, hc_set_enkf)
@@ -2509,8 +2582,21 @@ bool is_assimilation_row(const hc_handle *h, int64_t row)
     return s > 0 && row >= 1 && row % s == 0 && h->h_wtd_obs[(size_t)row] >= 0;
 }
 
+// The offset slot that lagged row `row` fills for the analysis row after it (hc_set_enkf_window), -1: none.  The row
+// takes part when it is >= 1 and has an observation, and the analysis row is one as things stand.
+int window_slot(const hc_handle *h, int64_t row)
+{
+    if (h->win_n <= 0 || h->enkf_stride <= 0 || row < 1 || h->h_wtd_obs[(size_t)row] < 0) return -1;
+    const int64_t s = h->enkf_stride, r = (row / s + 1) * s;
+    if (r >= h->n_rows || !is_assimilation_row(h, r)) return -1;
+    for (int j = 0; j < h->win_n; j++)
+        if (h->win_off[(size_t)j] == r - row) return j;
+    return -1;
+}
+
 // The launch after `done` rows of the request.  With a filter on, a launch ends on the next assimilation row and, in a
-// Philox run with the particle filter, holds at most as many refresh rows as FILT_FRESH_BYTES admits.
+// Philox run with the particle filter, holds at most as many refresh rows as FILT_FRESH_BYTES admits; with the EnKF's
+// window on it ends on the next lagged row that takes part.
 Chunk plan_chunk(const hc_handle *h, const hc_step_args *a, int64_t done, bool prof_on)
 {
     const int64_t N = h->n_members, D = h->p.dim_d;
@@ -2532,6 +2618,12 @@ Chunk plan_chunk(const hc_handle *h, const hc_step_args *a, int64_t done, bool p
                 c.rows = (int)(r - c.row0 + 1);
                 break;
             }
+        if (h->win_n > 0)
+            for (int r = 0; r < c.rows; r++)
+                if (window_slot(h, c.row0 + r) >= 0) {
+                    c.rows = r + 1;
+                    break;
+                }
         if (h->filt_host()) {
             const int64_t cap = std::max<int64_t>(1, FILT_FRESH_BYTES / (N * D * 8));
             int64_t n_fresh = 0;
@@ -2723,7 +2815,8 @@ int assimilate(hc_handle *h, const Chunk &c)
     return HC_OK;
 }
 
-// The observations of `row` beyond the well's: the sensors with a value, in record order
+// The observations of `row` beyond the well's: the sensors with a value, in record order, then the lagged rows of the
+// window that were captured for this analysis, by ascending offset
 EnkfRow enkf_row(const hc_handle *h, int64_t row)
 {
     EnkfRow s{};
@@ -2736,8 +2829,32 @@ EnkfRow enkf_row(const hc_handle *h, int64_t row)
         s.sigma[s.m] = h->sm_sigma[(size_t)i];
         s.m++;
     }
-    s.n = s.m > 0 ? h->sm_n : 0;
+    s.ms = s.m;
+    s.n = s.ms > 0 ? h->sm_n : 0;
+    for (int j = 0; j < h->win_n; j++) {
+        const int64_t rj = row - h->win_off[(size_t)j];
+        if (rj < 1 || h->h_wtd_obs[(size_t)rj] < 0 || h->win_row[(size_t)j] != rj) continue;
+        s.sensor[s.m] = j;
+        s.obs[s.m] = (double)h->h_wtd_obs[(size_t)rj] * h->p.dz;
+        s.sigma[s.m] = h->enkf_sigma;
+        s.wrow[s.m] = (unsigned)rj;
+        s.m++;
+    }
+    s.nw = s.m > s.ms ? h->win_n : 0;
     return s;
+}
+
+// The lagged row the launch ended on: every member's y into the window's buffer, by the analysis's own kernel
+int enkf_capture(hc_handle *h, const Chunk &c, int slot)
+{
+    const int64_t N = h->n_members, D = h->p.dim_d;
+    if (h->win_y.ensure((size_t)(h->win_n * N))) return HC_ERR_DEVICE;
+    const unsigned short *w = h->wtd_u16.p + (size_t)(c.rows - 1) * N;
+    hipLaunchKernelGGL(enkf_obs_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, w, h->psi.p, h->Pdev.p,
+                       (long long)N, (long long)(N / h->n_points), (int)D, h->p.dz, h->win_y.p + (size_t)slot * N, 1);
+    HIP_TRY(hipGetLastError());
+    h->win_row[(size_t)slot] = c.row0 + c.rows - 1;
+    return HC_OK;
 }
 
 // The EnKF's analysis at the launch's last row (its water-table indices are wtd_u16's last row), m' = 1 + s.m
@@ -2753,11 +2870,12 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
     const int64_t N = h->n_members, D = h->p.dim_d, P = h->n_points, mpp = N / P;
     const int64_t row = c.row0 + c.rows - 1, slot = row / h->enkf_stride, n_arow = enkf_rows(h);
     const int64_t n_tiles = (mpp + ENKF_TILE - 1) / ENKF_TILE;
-    const int W = s.m + 1, V = W + 1;
-    const int64_t C = D + W, Wx = 1 + h->sm_n, Cx = D + Wx;
+    const int W = s.m + 1, V = s.ms + 2, mw = s.m - s.ms;
+    const int64_t C = D + W, Wx = 1 + h->sm_n + h->win_n, Cx = D + Wx;
     const int64_t cols_x = std::max(Cx * Wx, (Wx + 1) * (Wx + 1));   // the widest pass: the prior products or the posterior's
     if (h->enkf_Y.ensure((size_t)(N * Wx)) || h->enkf_eps.ensure((size_t)N) ||
-        h->enkf_eps_s.ensure((size_t)(N * h->sm_n)) || h->enkf_Ypost.ensure((size_t)(N * (Wx + 1))) ||
+        h->enkf_eps_s.ensure((size_t)(N * h->sm_n)) || h->enkf_eps_w.ensure((size_t)(N * h->win_n)) ||
+        h->enkf_Ypost.ensure((size_t)(N * (Wx + 1))) ||
         h->enkf_gain.ensure((size_t)(P * Wx * D)) || h->enkf_s1.ensure((size_t)(P * Cx)) ||
         h->enkf_s2.ensure((size_t)(P * cols_x)) || h->enkf_part.ensure((size_t)(P * n_tiles * cols_x)))
         return HC_ERR_DEVICE;
@@ -2775,9 +2893,14 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
     hipLaunchKernelGGL(enkf_obs_kernel, members, dim3(256), 0, h->stream, w, h->psi.p, h->Pdev.p, (long long)N, ll_mpp,
                        (int)D, dz, h->enkf_Y.p, W);
     HIP_TRY(hipGetLastError());
-    if (s.m > 0) {
+    if (s.ms > 0) {
         hipLaunchKernelGGL(enkf_theta_kernel, members, dim3(256), 0, h->stream, h->psi.p, h->Pdev.p, h->node_tabs.p, special,
                            (long long)N, ll_mpp, (int)D, s, h->enkf_Y.p, W);
+        HIP_TRY(hipGetLastError());
+    }
+    if (mw > 0) {
+        hipLaunchKernelGGL(enkf_window_gather_kernel, members, dim3(256), 0, h->stream, h->win_y.p, (long long)N, s,
+                           h->enkf_Y.p, W);
         HIP_TRY(hipGetLastError());
     }
     // prior: the sums of (psi, Y), then the products of their anomalies with Y's
@@ -2804,16 +2927,16 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
                            h->enkf_part_sq.p, ll_tiles, (int)D, h->enkf_sq_b.p);
         HIP_TRY(hipGetLastError());
     }
-    double *st = h->enkf.buf.p, *sst = h->sm.buf.p;
+    double *st = h->enkf.buf.p, *sst = h->sm.buf.p, *wst = h->win.buf.p;
     hipLaunchKernelGGL(enkf_gain_kernel, dim3((unsigned)P), dim3((unsigned)((D + WAVE - 1) / WAVE * WAVE)), 0, h->stream,
                        h->enkf_s1.p, h->enkf_s2.p, ll_mpp, (int)D, s, h->enkf_sigma, h->enkf_loc, z_obs, dz,
                        h->enkf_gain.p, st, sst, (long long)n_arow, (long long)slot, root ? h->enkf_rgain.p : nullptr,
-                       root ? h->enkf_dbar.p : nullptr);
+                       root ? h->enkf_dbar.p : nullptr, wst);
     HIP_TRY(hipGetLastError());
     const unsigned blocks = (unsigned)std::min<int64_t>((N + 3) / 4, (int64_t)h->n_cu * 8);
     if (root) {
         hipLaunchKernelGGL(enkf_sqrt_update_kernel, dim3(blocks), dim3(256), 0, h->stream, h->psi.p, h->enkf_Y.p,
-                           h->enkf_rgain.p, h->enkf_dbar.p, h->enkf_s1.p, h->Pdev.p, (long long)N, ll_mpp, (int)D, dz, W,
+                           h->enkf_rgain.p, h->enkf_dbar.p, h->enkf_s1.p, h->Pdev.p, (long long)N, ll_mpp, (int)D, dz, W, V,
                            relax ? 0 : 1, h->enkf_Ypost.p);
         HIP_TRY(hipGetLastError());
     } else {
@@ -2821,9 +2944,15 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
                            (unsigned long long)h->enkf_seed, P > 1 ? h->point_base.p : nullptr,
                            (long long)h->member_offset, (unsigned)row, s.n, h->enkf_eps.p, h->enkf_eps_s.p);
         HIP_TRY(hipGetLastError());
+        if (mw > 0) {
+            hipLaunchKernelGGL(enkf_window_draw_kernel, members, dim3(256), 0, h->stream, (long long)N, ll_mpp,
+                               (unsigned long long)h->enkf_seed, P > 1 ? h->point_base.p : nullptr,
+                               (long long)h->member_offset, s, h->enkf_eps_w.p);
+            HIP_TRY(hipGetLastError());
+        }
         hipLaunchKernelGGL(enkf_update_kernel, dim3(blocks), dim3(256), 0, h->stream, h->psi.p, h->enkf_Y.p,
                            h->enkf_gain.p, h->Pdev.p, (long long)N, ll_mpp, (int)D, dz, z_obs, h->enkf_sigma, s,
-                           h->enkf_eps.p, h->enkf_eps_s.p, h->enkf_Ypost.p);
+                           h->enkf_eps.p, h->enkf_eps_s.p, h->enkf_eps_w.p, h->enkf_Ypost.p);
         HIP_TRY(hipGetLastError());
     }
     if (relax) {
@@ -2850,7 +2979,7 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
                            h->enkf_Ypost.p);
         HIP_TRY(hipGetLastError());
     }
-    if (s.m > 0) {
+    if (s.ms > 0) {
         hipLaunchKernelGGL(enkf_theta_kernel, members, dim3(256), 0, h->stream, h->psi.p, h->Pdev.p, h->node_tabs.p, special,
                            (long long)N, ll_mpp, (int)D, s, h->enkf_Ypost.p, V);
         HIP_TRY(hipGetLastError());
@@ -2875,7 +3004,9 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
     h->enkf_width = W;
     h->enkf_last_method = h->enkf_method;
     h->enkf_last_relaxed = relax;
-    h->sm_width = s.m > 0 ? W : 0;
+    h->sm_width = s.ms > 0 ? 1 + s.ms : 0;
+    h->win_last.assign(s.sensor + s.ms, s.sensor + s.m);
+    std::fill(h->win_row.begin(), h->win_row.end(), (int64_t)-1);   // the captured rows are spent
     return HC_OK;
 }
 
@@ -2927,6 +3058,7 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
     const bool enkf_on = h->enkf_stride > 0 && !a->spinup;   // (the EnKF: spin-up solves are never analysed either)
     if (enkf_on && (rc = ensure_enkf(h))) return rc;
     if (enkf_on && h->sm_n > 0 && (rc = ensure_sm(h))) return rc;
+    if (enkf_on && h->win_n > 0 && (rc = ensure_win(h))) return rc;
     int64_t fresh_consumed = 0;
     for (int64_t done = 0; done < a->n_rows;) {
         const Chunk c = plan_chunk(h, a, done, prof_on);
@@ -2939,6 +3071,8 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
         if (enkf_on && is_assimilation_row(h, c.row0 + c.rows - 1) &&
             (rc = enkf_analyse(h, c, enkf_row(h, c.row0 + c.rows - 1))))
             return rc;
+        if (const int wslot = enkf_on ? window_slot(h, c.row0 + c.rows - 1) : -1; wslot >= 0)
+            if ((rc = enkf_capture(h, c, wslot))) return rc;
         HIP_TRY(hipStreamSynchronize(h->stream));
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
@@ -3405,6 +3539,9 @@ int hc_set_enkf_soil_moisture(hc_handle *h, int32_t n_sensors, const int32_t *no
     if (n_sensors > 0 && h->enkf_stride <= 0)
         return fail(HC_ERR_ARG, "hc_set_enkf_soil_moisture: the EnKF is off (hc_set_enkf comes first)");
     if (n_sensors > 0 && (!nodes || !values || !sigma)) return fail(HC_ERR_ARG, "hc_set_enkf_soil_moisture: bad argument");
+    if (n_sensors + h->win_n > ENKF_SENSORS)
+        return fail(HC_ERR_ARG, "hc_set_enkf_soil_moisture: %d sensors and %d window offsets, at most %d together",
+                    (int)n_sensors, h->win_n, ENKF_SENSORS);
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
     sm_off(h);
@@ -3465,28 +3602,161 @@ static int sm_hook(hc_handle *h, const double *src, double *out, size_t count, c
     return enkf_hook(h, src, out, 1, count, count, who);
 }
 
+// the well's and the sensors' columns of Y [N][m']
 int hc_get_enkf_sm_y(hc_handle *h, double *y)
 {
-    return sm_hook(h, h ? h->enkf_Y.p : nullptr, y, h ? (size_t)h->n_members * h->sm_width : 0, "hc_get_enkf_sm_y");
+    if (int rc = sm_check(h, y, "hc_get_enkf_sm_y")) return rc;
+    return enkf_hook(h, h->enkf_Y.p, y, (size_t)h->n_members, (size_t)h->sm_width, (size_t)h->enkf_width, "hc_get_enkf_sm_y");
 }
 
-// the gain is [P][m'][D] on the device, [P][D][m'] at the C-ABI
+// the gain is [P][m'][D] on the device, [P][D][.] at the C-ABI: its first `cols` columns
+static int gain_hook(hc_handle *h, double *gain, size_t cols, const char *who)
+{
+    const size_t P = (size_t)h->n_points, D = (size_t)h->p.dim_d, W = (size_t)h->enkf_width;
+    std::vector<double> k(P * W * D);
+    if (int rc = enkf_hook(h, h->enkf_gain.p, k.data(), 1, k.size(), k.size(), who)) return rc;
+    for (size_t p = 0; p < P; p++)
+        for (size_t i = 0; i < cols; i++)
+            for (size_t d = 0; d < D; d++) gain[(p * D + d) * cols + i] = k[(p * W + i) * D + d];
+    return HC_OK;
+}
+
 int hc_get_enkf_sm_gain(hc_handle *h, double *gain)
 {
     if (int rc = sm_check(h, gain, "hc_get_enkf_sm_gain")) return rc;
-    const size_t P = (size_t)h->n_points, D = (size_t)h->p.dim_d, W = (size_t)h->sm_width;
-    std::vector<double> k(P * W * D);
-    if (int rc = enkf_hook(h, h->enkf_gain.p, k.data(), 1, k.size(), k.size(), "hc_get_enkf_sm_gain")) return rc;
-    for (size_t p = 0; p < P; p++)
-        for (size_t i = 0; i < W; i++)
-            for (size_t d = 0; d < D; d++) gain[(p * D + d) * W + i] = k[(p * W + i) * D + d];
-    return HC_OK;
+    return gain_hook(h, gain, (size_t)h->sm_width, "hc_get_enkf_sm_gain");
 }
 
 int hc_get_enkf_sm_eps(hc_handle *h, double *eps)
 {
     if (int rc = eps_check(h, "hc_get_enkf_sm_eps")) return rc;
     return sm_hook(h, h ? h->enkf_eps_s.p : nullptr, eps, h ? (size_t)h->n_members * h->sm_n : 0, "hc_get_enkf_sm_eps");
+}
+
+int hc_set_enkf_window(hc_handle *h, int32_t n_offsets, const int32_t *offsets)
+{
+    if (!h || n_offsets < 0 || (n_offsets > 0 && !offsets)) return fail(HC_ERR_ARG, "hc_set_enkf_window: bad argument");
+    if (n_offsets > ENKF_SENSORS)
+        return fail(HC_ERR_ARG, "hc_set_enkf_window: %d offsets, at most %d", (int)n_offsets, ENKF_SENSORS);
+    if (n_offsets > 0 && h->enkf_stride <= 0)
+        return fail(HC_ERR_ARG, "hc_set_enkf_window: the EnKF is off (hc_set_enkf comes first)");
+    if (n_offsets + h->sm_n > ENKF_SENSORS)
+        return fail(HC_ERR_ARG, "hc_set_enkf_window: %d offsets and %d sensors, at most %d together", (int)n_offsets,
+                    h->sm_n, ENKF_SENSORS);
+    std::vector<int> off(offsets, offsets + n_offsets);
+    std::sort(off.begin(), off.end());
+    for (int j = 0; j < n_offsets; j++) {
+        if (off[(size_t)j] < 1 || off[(size_t)j] >= h->enkf_stride)
+            return fail(HC_ERR_ARG, "hc_set_enkf_window: offset %d outside [1, %d) (the stride)", off[(size_t)j],
+                        h->enkf_stride);
+        if (j > 0 && off[(size_t)j] == off[(size_t)j - 1])
+            return fail(HC_ERR_ARG, "hc_set_enkf_window: offset %d twice", off[(size_t)j]);
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    win_off(h);
+    if (n_offsets == 0) return HC_OK;
+    h->win_n = n_offsets;
+    h->win_off = off;
+    h->win_row.assign((size_t)n_offsets, (int64_t)-1);
+    const int rc = ensure_win(h);
+    if (rc != HC_OK) win_off(h);                 // refused: off
+    return rc;
+}
+
+int hc_get_enkf_window_stats(hc_handle *h, double *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_get_enkf_window_stats: bad argument");
+    return table_copy(h, h->win, ensure_win, hipMemcpyDeviceToHost, table, n_entries, "hc_get_enkf_window_stats");
+}
+
+int hc_set_enkf_window_stats(hc_handle *h, const double *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_set_enkf_window_stats: bad argument");
+    return table_copy(h, h->win, ensure_win, hipMemcpyHostToDevice, const_cast<double *>(table), n_entries,
+                      "hc_set_enkf_window_stats");
+}
+
+// what the window holds for the coming analysis: checkpoints
+int hc_get_enkf_window_capture(hc_handle *h, double *y, int64_t *rows)
+{
+    if (!h || !y || !rows) return fail(HC_ERR_ARG, "hc_get_enkf_window_capture: bad argument");
+    if (h->win_n <= 0) return fail(HC_ERR_ARG, "hc_get_enkf_window_capture: no window offsets (hc_set_enkf_window)");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const size_t N = (size_t)h->n_members;
+    for (int j = 0; j < h->win_n; j++) {
+        rows[j] = h->win_row[(size_t)j];
+        if (rows[j] >= 0)
+            HIP_TRY(hipMemcpy(y + (size_t)j * N, h->win_y.p + (size_t)j * N, N * 8, hipMemcpyDeviceToHost));
+        else
+            std::fill_n(y + (size_t)j * N, N, 0.0);
+    }
+    return HC_OK;
+}
+
+int hc_set_enkf_window_capture(hc_handle *h, const double *y, const int64_t *rows)
+{
+    if (!h || !y || !rows) return fail(HC_ERR_ARG, "hc_set_enkf_window_capture: bad argument");
+    if (h->win_n <= 0) return fail(HC_ERR_ARG, "hc_set_enkf_window_capture: no window offsets (hc_set_enkf_window)");
+    const size_t N = (size_t)h->n_members;
+    for (int j = 0; j < h->win_n; j++)
+        if (rows[j] < -1 || rows[j] >= h->n_rows)
+            return fail(HC_ERR_ARG, "hc_set_enkf_window_capture: row %lld of offset %d outside [-1, %lld)", (long long)rows[j],
+                        h->win_off[(size_t)j], (long long)h->n_rows);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->win_y.ensure((size_t)h->win_n * N)) return HC_ERR_DEVICE;
+    HIP_TRY(hipMemcpy(h->win_y.p, y, (size_t)h->win_n * N * 8, hipMemcpyHostToDevice));
+    h->win_row.assign(rows, rows + h->win_n);
+    return HC_OK;
+}
+
+int hc_get_enkf_width(hc_handle *h, int32_t *width)
+{
+    if (!h || !width) return fail(HC_ERR_ARG, "hc_get_enkf_width: bad argument");
+    *width = h->enkf_stride > 0 && h->enkf_done ? h->enkf_width : 0;
+    return HC_OK;
+}
+
+int hc_get_enkf_window_width(hc_handle *h, int32_t *width, int32_t *slots)
+{
+    if (!h || !width) return fail(HC_ERR_ARG, "hc_get_enkf_window_width: bad argument");
+    const bool any = h->enkf_stride > 0 && h->enkf_done && h->win_n > 0;
+    *width = any ? (int32_t)h->win_last.size() : 0;
+    if (slots)
+        for (int k = 0; k < *width; k++) slots[k] = h->win_last[(size_t)k];
+    return HC_OK;
+}
+
+// the last analysis's buffers when it had lagged columns (test hooks)
+static int win_check(hc_handle *h, const double *out, const char *who)
+{
+    if (!h || !out) return fail(HC_ERR_ARG, "%s: bad argument", who);
+    if (h->win_n <= 0 || h->win_last.empty()) return fail(HC_ERR_ARG, "%s: the last analysis had no lagged row", who);
+    return HC_OK;
+}
+
+int hc_get_enkf_window_y(hc_handle *h, double *y)
+{
+    if (int rc = win_check(h, y, "hc_get_enkf_window_y")) return rc;
+    const size_t mw = h->win_last.size(), W = (size_t)h->enkf_width;
+    return enkf_hook(h, h->enkf_Y.p + (W - mw), y, (size_t)h->n_members, mw, W, "hc_get_enkf_window_y");
+}
+
+int hc_get_enkf_window_eps(hc_handle *h, double *eps)
+{
+    if (int rc = eps_check(h, "hc_get_enkf_window_eps")) return rc;
+    if (int rc = win_check(h, eps, "hc_get_enkf_window_eps")) return rc;
+    const size_t n = (size_t)h->n_members * h->win_last.size();
+    return enkf_hook(h, h->enkf_eps_w.p, eps, 1, n, n, "hc_get_enkf_window_eps");
+}
+
+int hc_get_enkf_window_gain(hc_handle *h, double *gain)
+{
+    if (!h || !gain) return fail(HC_ERR_ARG, "hc_get_enkf_window_gain: bad argument");
+    if (h->enkf_stride <= 0 || !h->enkf_done) return fail(HC_ERR_ARG, "hc_get_enkf_window_gain: no analysis since hc_set_enkf");
+    return gain_hook(h, gain, (size_t)h->enkf_width, "hc_get_enkf_window_gain");
 }
 
 int hc_set_enkf_method(hc_handle *h, int32_t method, double relaxation)

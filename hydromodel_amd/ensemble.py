@@ -9,7 +9,8 @@ all-reduce of the per-row water-table moments (see :func:`allreduce_moments`).
 import numpy as np
 
 from .digest import inverse_retention
-from .stepper import (ENKF_METHODS, ENKF_WIDTH, SM_WIDTH, EnsembleStepper, enkf_sm_summary, enkf_summary, filter_summary,
+from .stepper import (ENKF_METHODS, ENKF_WIDTH, SM_WIDTH, WINDOW_WIDTH, EnsembleStepper, enkf_sm_summary, enkf_summary,
+                      enkf_window_settings, enkf_window_summary, filter_summary,
                       moments_to_mean_std, wtd_distribution)
 
 
@@ -109,13 +110,16 @@ class _Run:
     enkf_method: "stochastic" (perturbed observations, the default) or "sqrt" (the deterministic square-root analysis);
     enkf_relaxation: the relaxation to prior spread alpha in [0, 1] (default 0 = none) of either
     (include/hydrocol.h hc_set_enkf_method); both need the EnKF.
+    enkf_window_offsets: rows before each analysis row (integers in [1, enkf_stride), e.g. (12, 24, 36)) on which the
+    well's record joins that analysis too -- the asynchronous EnKF (include/hydrocol.h hc_set_enkf_window);
+    :meth:`enkf_window_table`, the ``window_*`` keys of :meth:`enkf_summary`.
     ``_lead`` is the leading shape of the per-point tables: () for an ensemble, (P,) for a sweep."""
 
     _lead = ()
 
     def _start_tables(self, profile_stride, wtd_hist_stride, filter_stride=0, filter_sigma_cm=None, filter_seed=None,
                       enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None,
-                      enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0):
+                      enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=()):
         self.profile_stride = int(profile_stride)
         if self.profile_stride:
             self.stepper.set_profile_stats(self.profile_stride)
@@ -145,6 +149,9 @@ class _Run:
             if not self.enkf_stride:
                 raise ValueError("enkf_method / enkf_relaxation need the EnKF (enkf_stride > 0)")
             self.stepper.set_enkf_method(self.enkf_method, self.enkf_relaxation)
+        self.enkf_window_offsets = enkf_window_settings(enkf_window_offsets, self.enkf_stride, self.stepper.enkf_sm_n)
+        if self.enkf_window_offsets:
+            self.stepper.set_enkf_window(self.enkf_window_offsets)
 
     def advance(self, n_rows, **kw):
         """Solve the next ``n_rows`` forcing rows for every member."""
@@ -194,17 +201,30 @@ class _Run:
         """[n_arow][8] float64 (include/hydrocol.h hc_set_enkf; depths from the top node); a sweep: [P][n_arow][8]."""
         return self.stepper.enkf_table().reshape(self._lead + (-1, ENKF_WIDTH))
 
-    def enkf_summary(self, table=None, sm_table=None):
+    def enkf_summary(self, table=None, sm_table=None, window_table=None):
         """The EnKF's record (stepper.enkf_summary, means at the well's depths): ``rows``, ``count``, ``prior_mean_cm``,
         ``prior_std_cm``, ``innovation_cm``, ``loglik_rows``, ``post_mean_cm``, ``post_std_cm``, ``rejected`` over the
         analysed rows and ``loglik``, the log marginal likelihood of the well record (log cm^-1), with a leading [P] for a
-        sweep, and the analysis scheme, ``method`` and ``relaxation``; ``table``: e.g. the one assembled over ranks."""
+        sweep, and the analysis scheme, ``method`` and ``relaxation``; ``table``: e.g. the one assembled over ranks.
+        With a window the ``window_*`` keys of :meth:`enkf_window_summary` too."""
         t = self.enkf_table() if table is None else table
         out = enkf_summary(t, self.enkf_stride, self.enkf_sigma_cm, float(self.cols.z[0]))
         out.update(method=self.enkf_method, relaxation=self.enkf_relaxation)
         if self.enkf_soil_moisture is not None:
             out.update(("sm_" + k, v) for k, v in self.enkf_sm_summary(sm_table).items())
+        if self.enkf_window_offsets:
+            out.update(("window_" + k, v) for k, v in self.enkf_window_summary(window_table).items())
         return out
+
+    def enkf_window_table(self):
+        """[n_arow][n][4] float64 (include/hydrocol.h hc_set_enkf_window); a sweep: [P][n_arow][n][4]."""
+        return self.stepper.enkf_window_table().reshape(self._lead + (-1, len(self.enkf_window_offsets), WINDOW_WIDTH))
+
+    def enkf_window_summary(self, table=None):
+        """stepper.enkf_window_summary of the window's table (``table``: e.g. the one assembled over ranks): per
+        analysis row and offset the lagged observation, the prior of the recorded y and the innovation."""
+        t = self.enkf_window_table() if table is None else table
+        return enkf_window_summary(t, self.enkf_stride, self.enkf_window_offsets, float(self.cols.z[0]))
 
     def enkf_sm_table(self):
         """[n_arow][n][6] float64 (include/hydrocol.h hc_set_enkf_soil_moisture); a sweep: [P][n_arow][n][6]."""
@@ -235,11 +255,12 @@ class EnsembleSimulation(_Run):
     def __init__(self, cols, forcing, n_members, seed=0, device=0, member_offset=0, psi0=None, flags=None,
                  noise="philox", spinup="shared", profile_stride=0, wtd_hist_stride=0, filter_stride=0,
                  filter_sigma_cm=None, filter_seed=None, enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0,
-                 enkf_seed=None, enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0):
+                 enkf_seed=None, enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0,
+                 enkf_window_offsets=()):
         self._start(cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup)
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
-                           enkf_relaxation)
+                           enkf_relaxation, enkf_window_offsets)
 
     def _start(self, cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup):
         if noise not in ("philox", "numpy") or spinup not in ("shared", "member"):
@@ -355,6 +376,11 @@ class EnsembleSimulation(_Run):
             if self.enkf_soil_moisture is not None:       # the record itself is supplied again at restore
                 arrays["enkf_sm_nodes"] = np.asarray(self.enkf_soil_moisture["nodes"], dtype=np.int32)
                 arrays["enkf_sm_table"] = self.stepper.enkf_sm_table()
+            if self.enkf_window_offsets:                  # what was recorded for the coming analysis travels along
+                y, rows = self.stepper.enkf_window_capture()
+                arrays["enkf_window_offsets"] = np.asarray(self.enkf_window_offsets, dtype=np.int64)
+                arrays["enkf_window_table"] = self.stepper.enkf_window_table()
+                arrays["enkf_window_y"], arrays["enkf_window_rows"] = y, rows
         path = Path(path)
         if hdf5io.available() and path.suffix != ".npz":
             hdf5io.write(path, arrays)
@@ -399,6 +425,9 @@ class EnsembleSimulation(_Run):
             raise ValueError(f" EnsembleSimulation: {path} has sensors at other nodes than enkf_soil_moisture.")
         if has_sm:
             fkw.update(enkf_soil_moisture=enkf_soil_moisture)
+        has_win = enkf and "enkf_window_offsets" in data
+        if has_win:
+            fkw.update(enkf_window_offsets=tuple(int(o) for o in np.asarray(data["enkf_window_offsets"]).reshape(-1)))
         sim = cls(cols, forcing, n, seed=int(data["seed"]), device=device, member_offset=int(data["member_offset"]),
                   psi0=np.asarray(data["initial_cond"], dtype=float).reshape(-1)[:D], flags=flags, profile_stride=stride,
                   wtd_hist_stride=hist_stride, **fkw)
@@ -412,6 +441,10 @@ class EnsembleSimulation(_Run):
             sim.stepper.set_enkf_table(np.asarray(data["enkf_table"], dtype=np.float64))
         if has_sm:
             sim.stepper.set_enkf_sm_table(np.asarray(data["enkf_sm_table"], dtype=np.float64))
+        if has_win:
+            sim.stepper.set_enkf_window_table(np.asarray(data["enkf_window_table"], dtype=np.float64))
+            sim.stepper.set_enkf_window_capture(np.asarray(data["enkf_window_y"], dtype=np.float64).reshape(-1, n),
+                                                np.asarray(data["enkf_window_rows"], dtype=np.int64))
         sim.stepper.set_moments(np.asarray(data["moments"], dtype=np.int64))
         if stride:
             sim.stepper.set_profile_table(np.asarray(data["profile_table"], dtype=np.int64))
@@ -510,7 +543,7 @@ class SweepSimulation(_Run):
     def __init__(self, cols_list, forcing, n_members, seed=0, device=0, first_point=0, flags=None, psi0=None,
                  point_ids=None, profile_stride=0, wtd_hist_stride=0, filter_stride=0, filter_sigma_cm=None,
                  filter_seed=None, enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None,
-                 enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0):
+                 enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=()):
         self.points = list(cols_list)
         self.P, self.n = len(self.points), int(n_members)
         self._lead = (self.P,)
@@ -539,7 +572,7 @@ class SweepSimulation(_Run):
             self.stepper.set_point_member_bases(self.bases)
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
-                           enkf_relaxation)
+                           enkf_relaxation, enkf_window_offsets)
         self.next_row, self.kernel_ms, self.launches = 1, 0.0, 0
 
     def _spinup(self, flags):

@@ -80,6 +80,7 @@ class EnsembleStepper:
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
         self.enkf_sm_nodes = None
         self.enkf_method, self.enkf_relaxation = "stochastic", 0.0
+        self.enkf_window_offsets = ()
         if profile_stride:
             self.set_profile_stats(profile_stride)
 
@@ -339,6 +340,7 @@ class EnsembleStepper:
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
         self.enkf_sm_nodes = None
         self.enkf_method, self.enkf_relaxation = "stochastic", 0.0
+        self.enkf_window_offsets = ()
 
     def filter_table(self):
         """[P][n_arow][4] float64: count, ESS, log-likelihood increment, survivors per assimilation slot (slot j <-> row
@@ -401,6 +403,7 @@ class EnsembleStepper:
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
         self.enkf_sm_nodes = None                             # hc_set_enkf removes the sensor record
         self.enkf_method, self.enkf_relaxation = "stochastic", 0.0       # ... and resets the analysis scheme
+        self.enkf_window_offsets = ()                         # ... and turns the window off
         L.check(self.lib.hc_set_enkf(self.h, stride, sigma, loc, int(seed) & 0xFFFFFFFFFFFFFFFF))
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = stride, sigma, loc, int(seed)
 
@@ -455,8 +458,10 @@ class EnsembleStepper:
         return ENKF_METHODS[int(m[0])], float(a[0])
 
     def enkf_width(self):
-        """m' of the last analysis: 1 + the sensors present on it."""
-        return self.enkf_sm_width() or 1
+        """m' of the last analysis: 1 + the sensors and the lagged rows present on it."""
+        w = np.zeros(1, dtype=np.int32)
+        L.check(self.lib.hc_get_enkf_width(self.h, L.iptr(w)))
+        return int(w[0]) or 1
 
     def enkf_sqrt_gain(self):
         """[P][D][m'] the reduced gain of the last analysis, a square-root one (test hook)."""
@@ -532,6 +537,69 @@ class EnsembleStepper:
         """[N][n] the sensors' observation perturbations of the last analysis, every sensor of the record (test hook)."""
         out = np.zeros((self.N, self.enkf_sm_n))
         L.check(self.lib.hc_get_enkf_sm_eps(self.h, L.dptr(out)))
+        return out
+
+    # -- the well's record inside the window (include/hydrocol.h hc_set_enkf_window) -------------------------------------
+    def set_enkf_window(self, offsets=()):
+        """Asynchronous EnKF: every member's y on the rows ``offsets`` before an analysis row (integers in [1, stride),
+        distinct, at most 8 together with the sensors) is recorded when the row is solved and joins that analysis as a
+        further well-type observation.  Empty or None turns it off.  The EnKF must be on (:meth:`set_enkf` first; it
+        turns the window off again)."""
+        off = enkf_window_settings(offsets, self.enkf_stride, self.enkf_sm_n)
+        self.enkf_window_offsets = ()
+        a = np.ascontiguousarray(off, dtype=np.int32)
+        L.check(self.lib.hc_set_enkf_window(self.h, a.size, L.iptr(a) if a.size else None))
+        self.enkf_window_offsets = off
+
+    @property
+    def enkf_window_n(self):
+        return len(self.enkf_window_offsets)
+
+    def enkf_window_table(self):
+        """[P][n_arow][n][4] float64 per analysis slot and offset: observed (0/1), observation, prior mean and std of the
+        recorded y (cm from the top node); NaN where the slot's analysis had no lagged row (and after observed = 0)."""
+        t = np.zeros((self.P, stride_rows(self.T, self.enkf_stride), self.enkf_window_n, WINDOW_WIDTH))
+        L.check(self.lib.hc_get_enkf_window_stats(self.h, L.dptr(t), t.size))
+        return t
+
+    def set_enkf_window_table(self, table):
+        t = L.as_f64(table).reshape(-1)
+        L.check(self.lib.hc_set_enkf_window_stats(self.h, L.dptr(t), t.size))
+
+    def enkf_window_capture(self):
+        """(y [n][N], rows [n] int64): what the window holds for the coming analysis (row -1: nothing; checkpoints)."""
+        y, rows = np.zeros((self.enkf_window_n, self.N)), np.zeros(self.enkf_window_n, dtype=np.int64)
+        L.check(self.lib.hc_get_enkf_window_capture(self.h, L.dptr(y), L.lptr(rows)))
+        return y, rows
+
+    def set_enkf_window_capture(self, y, rows):
+        y, rows = L.as_f64(y), np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        if y.shape != (self.enkf_window_n, self.N) or rows.size != self.enkf_window_n:
+            raise ValueError(f"the window's capture must be [{self.enkf_window_n}, {self.N}] with as many rows")
+        L.check(self.lib.hc_set_enkf_window_capture(self.h, L.dptr(y), L.lptr(rows)))
+
+    def enkf_window_slots(self):
+        """The indices into ``enkf_window_offsets`` of the last analysis's lagged columns, in column order (test hook)."""
+        w, slots = np.zeros(1, dtype=np.int32), np.zeros(SM_MAX_SENSORS, dtype=np.int32)
+        L.check(self.lib.hc_get_enkf_window_width(self.h, L.iptr(w), L.iptr(slots)))
+        return slots[:int(w[0])].copy()
+
+    def enkf_window_y(self):
+        """[N][m_w] the recorded y of the last analysis's lagged columns, cm from the top node (test hook)."""
+        out = np.zeros((self.N, self.enkf_window_slots().size))
+        L.check(self.lib.hc_get_enkf_window_y(self.h, L.dptr(out)))
+        return out
+
+    def enkf_window_eps(self):
+        """[N][m_w] the perturbations of the last analysis's lagged columns (test hook)."""
+        out = np.zeros((self.N, self.enkf_window_slots().size))
+        L.check(self.lib.hc_get_enkf_window_eps(self.h, L.dptr(out)))
+        return out
+
+    def enkf_full_gain(self):
+        """[P][D][m'] the gain K of the last analysis, every column: well, sensors, lagged rows (test hook)."""
+        out = np.zeros((self.P, self.D, self.enkf_width()))
+        L.check(self.lib.hc_get_enkf_window_gain(self.h, L.dptr(out)))
         return out
 
     # -- hooks ----------------------------------------------------------------------
@@ -855,6 +923,58 @@ def enkf_sm_summary(table, stride, sigma):
             "rmse": rmse, "mean_innovation": mean_innov, "n_obs": cnt.astype(np.int64),
             "rmse_all": rmse_all if np.ndim(rmse_all) else float(rmse_all), "stride": int(stride),
             "sigma": np.asarray(sigma, dtype=np.float64)}
+
+
+# ---- the well's record inside the window (include/hydrocol.h hc_set_enkf_window) ---------------------------------------
+WINDOW_WIDTH = 4
+
+
+def enkf_window_settings(offsets, stride, n_sensors=0):
+    """The window's offsets as a tuple in ascending order (``()``: off).  A ValueError unless ``offsets`` is a list or
+    tuple of distinct integers in [1, stride) -- no booleans, no floats -- of at most 8 entries, at most 8 together with
+    ``n_sensors`` soil-moisture sensors; any offset needs the EnKF (stride > 0)."""
+    if offsets is None:
+        return ()
+    if not isinstance(offsets, (list, tuple)):
+        raise ValueError(f"EnKF Window_Offsets = {offsets!r} must be a list of integers")
+    for o in offsets:
+        if isinstance(o, (bool, np.bool_)) or not isinstance(o, (int, np.integer)):
+            raise ValueError(f"EnKF Window_Offsets: {o!r} is not an integer")
+    off = tuple(sorted(int(o) for o in offsets))
+    if not off:
+        return ()
+    stride = int(stride or 0)
+    if stride <= 0:
+        raise ValueError("EnKF Window_Offsets need the EnKF (Stride > 0)")
+    for o in off:
+        if not 1 <= o < stride:
+            raise ValueError(f"EnKF Window_Offsets: {o} lies outside [1, {stride}) (rows before the analysis row, below Stride)")
+    if len(set(off)) != len(off):
+        raise ValueError(f"EnKF Window_Offsets = {list(off)} repeats an offset")
+    if len(off) > SM_MAX_SENSORS:
+        raise ValueError(f"EnKF Window_Offsets: {len(off)} offsets, at most {SM_MAX_SENSORS}")
+    if len(off) + int(n_sensors) > SM_MAX_SENSORS:
+        raise ValueError(f"EnKF Window_Offsets: {len(off)} offsets and {int(n_sensors)} soil-moisture sensors, at most "
+                         f"{SM_MAX_SENSORS} together")
+    return off
+
+
+def enkf_window_summary(table, stride, offsets, z0_cm=0.0):
+    """The window's record from the [..., n_arow, n, 4] table, over the slots whose analysis had a lagged row at any
+    point: ``rows`` [R] (the analysis rows), ``offsets`` [n], ``observed`` [..., R, n] (bool), ``obs_cm``,
+    ``prior_mean_cm`` (both moved from the top node to ``z0_cm``), ``prior_std_cm``, ``innovation_cm`` [..., R, n];
+    ``n_obs`` = the lagged observations assimilated (at any one point), ``n_rows`` = the analysis rows that took any."""
+    t = np.asarray(table, dtype=np.float64)
+    n = t.shape[-2]
+    used = np.isfinite(t[..., 0]).reshape(-1, t.shape[-3], n).any(axis=(0, 2)) if t.size else np.zeros(t.shape[-3], bool)
+    slots = np.flatnonzero(used)
+    sel = t[..., slots, :, :]
+    observed = sel[..., 0] == 1.0
+    first = observed.reshape((-1,) + observed.shape[-2:])[0] if observed.size else observed.reshape(0, n)
+    return {"rows": slots.astype(np.int64) * int(stride), "offsets": np.asarray(offsets, dtype=np.int64),
+            "observed": observed, "obs_cm": sel[..., 1] + z0_cm, "prior_mean_cm": sel[..., 2] + z0_cm,
+            "prior_std_cm": sel[..., 3], "innovation_cm": sel[..., 1] - sel[..., 2],
+            "n_obs": int(first.sum()), "n_rows": int(first.any(axis=-1).sum())}
 
 
 def allreduce_handles(steppers):

@@ -49,6 +49,9 @@
  *   hc_set/get_enkf_method, hc_get_enkf_sqrt_gain/shift, hc_get_enkf_relaxation
  *                      <- (new) the EnKF's analysis scheme (perturbed observations or square root) and its relaxation to
  *                         prior spread
+ *   hc_set_enkf_window, hc_get/set_enkf_window_stats, hc_get/set_enkf_window_capture, hc_get_enkf_width,
+ *   hc_get_enkf_window_width/y/eps/gain
+ *                      <- (new) the well's record at rows inside the analysis window joins the analysis (asynchronous EnKF)
  *
  * Conventions: every function returns 0 on success or a negative hc_status; nothing throws
  * or aborts across the boundary; hc_last_error() gives the thread-local message.  Host
@@ -509,6 +512,53 @@ int hc_get_enkf_method(hc_handle *h, int32_t *method, double *relaxation);
 int hc_get_enkf_sqrt_gain(hc_handle *h, double *gain);
 int hc_get_enkf_sqrt_shift(hc_handle *h, double *shift);
 int hc_get_enkf_relaxation(hc_handle *h, double *sigma_b, double *sigma_a, double *factor);
+
+/* The well's record inside the window (asynchronous EnKF, Sakov, Evensen & Bertino 2010): at chosen rows before an
+ * analysis row each member's y is recorded when the row is solved, and at the analysis those values join the batch as
+ * further columns of Y, so that the members' present states are updated with the covariance between psi now and y then.
+ * No state is stored, no row is solved twice, the step kernels are not involved.
+ *   offsets [n_offsets] (<= 8, and n_offsets + n_sensors <= 8 so that m' <= 9): rows before the analysis row, integers in
+ *   [1, stride), distinct; kept in ascending order.  For analysis row r and offset o the lagged row r_j = r - o takes
+ *   part when r_j >= 1 and wtd_obs[r_j] >= 0 (the row was solved and has an observation); otherwise it is absent on that
+ *   analysis, like a sensor without a value.
+ *   Capture: a launch ends on every lagged row that takes part (and whose analysis row is one, as wtd_obs stands); then
+ *   y_k of every member -- the operator and the bits of hc_set_enkf, hc_get_enkf_y on that row -- goes into a device
+ *   buffer [n_offsets][n_members], which the analysis empties.  A lagged row solved before hc_set_enkf_window, or by
+ *   another handle, is absent unless hc_set_enkf_window_capture brought it.
+ *   Analysis at r: Y_k = (y_k, theta_k[j_1], ..., y_k(r_j1), ...), m' = 1 + m_s + m_w columns: the well at r, the present
+ *   sensors in record order, the present lagged rows by ascending offset.  A lagged column is a well-type observation:
+ *   o = z[wtd_obs[r_j]], error sigma_cm (R stays diagonal: correlated errors of the well's record are not modelled),
+ *   zeta = z[wtd_obs[r_j]] -- its own observed depth -- in the taper of hc_set_enkf_soil_moisture, and in the stochastic
+ *   scheme eps_k at counter (0xFFFFFFFE, r_j, key_lo, key_hi): the draw the well would have had on row r_j, which is never
+ *   an analysis row (o < stride), so no draw is used twice.  The square-root scheme draws nothing.  Gain, reduced gain,
+ *   update, the vote on a member's column, relaxation and the posterior diagnostics run as on any m'-wide row; the
+ *   EnKF's entry 4 is the joint log-density of everything assimilated on the row (log cm^-(1 + m_w) (m^3/m^3)^-m_s).
+ *   Moments, profiles and histograms keep describing the forecast.  The same bits at any launch length, point order or
+ *   dealing of a sweep's points to handles or ranks.
+ *   Window diagnostics, float64 [P][n_arow][n_offsets][4]: observed (0/1), observation z[wtd_obs[r_j]], prior mean and std
+ *   of the recorded y (cm from the top node; the host adds z[0] to the first two).  An offset absent on an analysis with
+ *   lagged rows: observed = 0, the rest NaN; every entry of a slot whose analysis had no lagged row: NaN.
+ * hc_set_enkf_window: n_offsets = 0 turns it off: analyses, launches and tables are then those of hc_set_enkf to the bit.
+ *   Needs the EnKF on (hc_set_enkf first); HC_ERR_ARG for an offset outside [1, stride), a repeated one, or too many
+ *   (hc_set_enkf_soil_moisture refuses likewise when the sensors come second).  Turned off by whatever turns the EnKF off
+ *   (hc_set_enkf included).  (Re)creates the table (NaN) and empties the buffer.
+ * hc_get/set_enkf_window_stats: the table (P n_arow n_offsets 4 entries; checkpoints, the assembly of a sweep over ranks).
+ * hc_get/set_enkf_window_capture: y [n_offsets][n_members] and rows [n_offsets], the lagged row each offset holds for the
+ *   coming analysis (-1: none; its y reads 0): what a checkpoint between a capture and its analysis must carry.
+ * Test hooks of the last analysis: hc_get_enkf_width (m', 0: none yet); hc_get_enkf_window_width (m_w and, slots != NULL,
+ *   the offsets' indices of the lagged columns in column order); when m_w > 0: y [n_members][m_w], eps [n_members][m_w]
+ *   (HC_ERR_ARG after a square-root analysis); hc_get_enkf_window_gain: K [P][D][m'], every column, on any analysed row.
+ *   hc_get_enkf_y / eps / gain and the hc_get_enkf_sm_* hooks keep returning the well's and the sensors' columns. */
+int hc_set_enkf_window(hc_handle *h, int32_t n_offsets, const int32_t *offsets);
+int hc_get_enkf_window_stats(hc_handle *h, double *table, int64_t n_entries);
+int hc_set_enkf_window_stats(hc_handle *h, const double *table, int64_t n_entries);
+int hc_get_enkf_window_capture(hc_handle *h, double *y, int64_t *rows);
+int hc_set_enkf_window_capture(hc_handle *h, const double *y, const int64_t *rows);
+int hc_get_enkf_width(hc_handle *h, int32_t *width);
+int hc_get_enkf_window_width(hc_handle *h, int32_t *width, int32_t *slots);
+int hc_get_enkf_window_y(hc_handle *h, double *y);
+int hc_get_enkf_window_eps(hc_handle *h, double *eps);
+int hc_get_enkf_window_gain(hc_handle *h, double *gain);
 
 /* The path's one collective inside the library, for a single process that drives several devices with
  * one handle each: every handle's moment table is replaced by the sum over all n handles (ncclAllReduce, ncclInt64,

@@ -4,7 +4,7 @@ one handle each, back to back on one GPU.
 
     python tools/enkf_sm_cost.py [--members 262144] [--depth 300] [--days 30] [--warmup 1] [--runs 0,48s,0,48s]
                                  [--sensors 30,60,120] [--sigma 10] [--sm-sigma 0.02] [--localisation 0] [--spread-cm 0]
-                                 [--method stochastic|sqrt] [--relaxation 0] [--json out.json]
+                                 [--method stochastic|sqrt] [--relaxation 0] [--offsets 12,24,36] [--json out.json]
 
 Same set-up as tools/filter_cost.py and bench.py's timed region: synthetic 10-year forcing, Philox noise, the shared
 initial condition of the well's digest (tests/golden/g1_tables_<depth>.npz where it exists, else the hydrostatic profile),
@@ -18,7 +18,10 @@ node, held fixed -- the cost does not depend on the values); a run may be listed
 alternate); `kept` is a run's rate over the mean of the stride-0 runs.  --spread-cm W starts every member from the
 initial profile shifted by its own offset, uniform over +-W cm.  Under `rocprofv3 --kernel-trace --stats` run it with
 --runs 48s (or 48) --days 1 --warmup 0 for the per-kernel time of the analyses.  --method / --relaxation: the analysis
-scheme of every EnKF run (hc_set_enkf_method; the defaults do not call it).  Prints one JSON line.
+scheme of every EnKF run (hc_set_enkf_method; the defaults do not call it).  --offsets: the well's record inside the
+window (hc_set_enkf_window) for the runs with the suffix "w" (48w, 48sw): each offset's row ends a launch and records
+y, so `launches` grows and the step kernel runs in shorter pieces -- `step_kernel_ms` against the stride-0 runs' is what
+the cuts cost the step kernel, `window_ms_per_analysis` what everything else costs.  Prints one JSON line.
 """
 import argparse
 import json
@@ -33,7 +36,7 @@ sys.path.insert(0, str(REPO))
 
 
 def run(cols, forcing, psi0, members, stride, sigma, loc, warmup_days, days, spread_cm=0.0, seed=2024, sensors=None,
-        method="stochastic", relaxation=0.0):
+        method="stochastic", relaxation=0.0, offsets=()):
     from hydromodel_amd.stepper import EnsembleStepper, enkf_sm_summary, enkf_summary
     st = EnsembleStepper(cols, forcing, members)
     try:
@@ -49,6 +52,8 @@ def run(cols, forcing, psi0, members, stride, sigma, loc, warmup_days, days, spr
             st.set_enkf_soil_moisture(sensors["nodes"], sensors["values"], sensors["sigma"])
         if stride and (method, relaxation) != ("stochastic", 0.0):
             st.set_enkf_method(method, relaxation)
+        if stride and offsets:
+            st.set_enkf_window(offsets)
         row = 1
         if warmup_days:
             st.step_rows(row, 48 * warmup_days)
@@ -59,7 +64,8 @@ def run(cols, forcing, psi0, members, stride, sigma, loc, warmup_days, days, spr
         st.lib.hc_synchronize(st.h)
         wall = time.perf_counter() - t0
         rec = {"stride": stride, "sensors": 0 if sensors is None else len(sensors["nodes"]), "wall_s": wall, "step_kernel_ms": out["kernel_ms"], "launches": out["launches"],
-               "other_ms": 1e3 * wall - out["kernel_ms"], "column_days_per_s": members * days / wall}
+               "other_ms": 1e3 * wall - out["kernel_ms"], "column_days_per_s": members * days / wall,
+               "offsets": list(offsets) if stride else []}
         if stride:
             s = enkf_summary(st.enkf_table()[0], stride, sigma)
             timed = s["rows"] >= row
@@ -68,6 +74,8 @@ def run(cols, forcing, psi0, members, stride, sigma, loc, warmup_days, days, spr
             rec["post_std_cm_median"] = float(np.median(s["post_std_cm"][timed])) if timed.any() else None
             rec["rejected"] = int(s["rejected"].sum())
             rec["loglik"] = s["loglik"]
+            if offsets:
+                rec["lagged_observations"] = int(np.nansum(st.enkf_window_table()[0, :, :, 0]))
             if sensors is not None:
                 sm = enkf_sm_summary(st.enkf_sm_table()[0], stride, sensors["sigma"])
                 rec["sm_forecast_rmse"] = sm["rmse"].tolist()
@@ -92,6 +100,7 @@ def main():
     ap.add_argument("--spread-cm", type=float, default=0.0)
     ap.add_argument("--method", default="stochastic", choices=("stochastic", "sqrt"))
     ap.add_argument("--relaxation", type=float, default=0.0)
+    ap.add_argument("--offsets", default="12,24,36")
     ap.add_argument("--json", default="")
     args = ap.parse_args()
     from hydromodel_amd.digest import ColumnTables, ForcingDigest
@@ -113,9 +122,10 @@ def main():
         probe.close()
     rec = soil_moisture_record(cols.z, depths, np.zeros((forcing.dim_t, len(depths))), args.sm_sigma)
     rec["values"][:] = theta0[rec["nodes"]][None, :]
-    recs = [run(cols, forcing, psi0, args.members, int(s.rstrip("s")), args.sigma, args.localisation, args.warmup,
-                args.days, args.spread_cm, sensors=rec if s.endswith("s") else None, method=args.method,
-                relaxation=args.relaxation)
+    offsets = tuple(int(o) for o in args.offsets.split(",") if o)
+    recs = [run(cols, forcing, psi0, args.members, int(s.rstrip("sw")), args.sigma, args.localisation, args.warmup,
+                args.days, args.spread_cm, sensors=rec if "s" in s else None, method=args.method,
+                relaxation=args.relaxation, offsets=offsets if "w" in s else ())
             for s in args.runs.split(",")]
     base = [r for r in recs if r["stride"] == 0]
     if base:
@@ -124,7 +134,8 @@ def main():
         for r in recs:
             r["kept"] = r["column_days_per_s"] / rate
             if r["stride"] and r.get("analyses"):
-                r["sm_ms_per_analysis" if r["sensors"] else "enkf_ms_per_analysis"] = (r["other_ms"] - other) / r["analyses"]
+                key = "window_ms_per_analysis" if r["offsets"] else "sm_ms_per_analysis" if r["sensors"] else "enkf_ms_per_analysis"
+                r[key] = (r["other_ms"] - other) / r["analyses"]
     line = json.dumps({"members": args.members, "depth": args.depth, "days": args.days, "sigma_cm": args.sigma,
                        "localisation_cm": args.localisation, "spread_cm": args.spread_cm, "sensors_cm": depths,
                        "sensor_nodes": rec["nodes"].tolist(), "sm_sigma": args.sm_sigma, "method": args.method,
