@@ -4,6 +4,7 @@ There is no CPU path: if the shared library is missing, or no gfx950 device is v
 the calls below raise.  Build with ``python -c "import __graft_entry__ as g; g.build()"``.
 """
 import ctypes as C
+import sys
 from pathlib import Path
 
 import numpy as np
@@ -44,6 +45,9 @@ class SpinupArgs(C.Structure):
     _fields_ = [("forcing_row", C.c_int64), ("max_iterations", C.c_int32), ("zwtd_cm", C.c_double),
                 ("z0_cm", C.c_double), ("iterations_out", _ip), ("kernel_ms", C.c_double)]
 
+
+# hc_enkf_exchange_fn: (ctx, device_buf, n_words, first_word, count_words) -> 0 = ok
+EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64)
 
 EXPORTS = {
     "hc_create": ([C.c_int, C.POINTER(C.c_void_p)], C.c_int),
@@ -128,6 +132,9 @@ EXPORTS = {
     "hc_get_enkf_window_y": ([C.c_void_p, _dp], C.c_int),
     "hc_get_enkf_window_eps": ([C.c_void_p, _dp], C.c_int),
     "hc_get_enkf_window_gain": ([C.c_void_p, _dp], C.c_int),
+    "hc_get_enkf_shard_words": ([C.c_void_p, C.c_int64, _lp], C.c_int),
+    "hc_set_enkf_shard": ([C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, EXCHANGE_FN, C.c_void_p], C.c_int),
+    "hc_get_enkf_shard": ([C.c_void_p, _lp, _lp], C.c_int),
     "hc_rhs": ([C.c_void_p, C.c_int64, C.c_int32, _dp, _dp], C.c_int),
     "hc_model_nodes": ([C.c_void_p, _dp, _dp], C.c_int),
     "hc_plugin_eval": ([C.c_int, C.POINTER(ColumnParams), C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
@@ -135,11 +142,25 @@ EXPORTS = {
 }
 
 _lib = None
+_torch_first = False        # torch was in the process before the library: the two use ONE HIP runtime (torch's)
 
 
-def load():
-    """Load libhydrocol.so; raises if it has not been built."""
-    global _lib
+def load(with_torch=False):
+    """Load libhydrocol.so; raises if it has not been built.
+
+    ``with_torch``: the caller will hand the library device memory that torch allocated (hc_set_enkf_shard's buffer).
+    torch ships a HIP runtime of its own, and the loader gives the library that one only when torch is in the process
+    first; loaded the other way round, the process holds two runtimes and torch's finds no GPU.  So torch is imported
+    here before the library, and a process that loaded the library before torch is an error, not a second runtime."""
+    global _lib, _torch_first
+    if with_torch and _lib is None:
+        import torch  # noqa: F401
+    if _lib is None:
+        _torch_first = "torch" in sys.modules
+    if with_torch and not _torch_first:
+        raise HcError("libhydrocol was loaded before torch, so torch would bring a second HIP runtime into this process: "
+                      "import torch before the first hydromodel_amd handle is made (EnsembleSimulation(enkf_shard=...) "
+                      "and the CLI do so themselves)")
     if _lib is None:
         if not LIB_PATH.exists():
             raise HcError(f"{LIB_PATH} is missing: the HIP extension has not been built "

@@ -52,7 +52,13 @@ unknown keys, only membership of the 12 is checked):
   ``enkf_prior_std_cm``, ``enkf_innovation_cm``, ``enkf_post_mean_cm``, ``enkf_post_std_cm``, ``enkf_loglik_rows``,
   ``enkf_rejected`` ``[R]``, ``enkf_loglik``, ``enkf_sigma_cm`` and ``enkf_localisation_cm`` (a sweep: a leading ``[P]``
   axis), and the run ends with `` [Ensemble xN] EnKF log-likelihood = ... over R rows`` (a sweep: the best point).  A
-  single-point ensemble on several GPUs is refused (the covariances would need a sum over ranks).
+  single-point ensemble on several GPUs is refused (the covariances would need a sum over ranks) unless the block is
+  sharded:
+* ``"EnKF": {..., "Sharded": true}``: a single-point ensemble's EnKF on ``--gpus N`` (include/hydrocol.h
+  hc_set_enkf_shard).  The members are dealt in whole tiles of 256 (``multigpu.shard_tiles``: at least N tiles), every
+  analysis gathers the ranks' tile partials before each of its reductions, and the states, tables, closing lines and the
+  file are those of the one-GPU run to the bit (``gpus`` apart); the EnKF's tables are rank 0's.  ``false`` or no key:
+  the refusal above.  A sweep accepts and ignores the key.  Added to the file when the key is given: ``enkf_sharded``.
 * ``"EnKF": {..., "Soil_Moisture": {"Filename": "sm.csv", "Depths_cm": [30, 60, 120], "Sigma": 0.02}}``: a soil-moisture
   record joins the well in the EnKF's analyses (include/hydrocol.h hc_set_enkf_soil_moisture).  The CSV is header-less
   ``ID, Datenum, VWC_1, ..., VWC_m`` (as the forcing), one row per forcing row with the same ``Datenum``; an empty field or
@@ -214,14 +220,22 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     if ens.get("Points"):
         return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels, filt,
                           enkf, record, scheme, window)
-    lo, hi = multigpu.shard(n_members, ranks.rank, ranks.world)
+    sharded = enkf_sharded(ens)
+    if sharded:
+        # whole tiles of the EnKF's sums per rank, and the analyses gather them: the one-rank run on any number of GPUs
+        lo, hi = multigpu.shard_tiles(n_members, ranks.rank, ranks.world)
+        shard_kw = dict(enkf_shard=(n_members, multigpu.ShardExchange(ranks)))
+    else:
+        lo, hi = multigpu.shard(n_members, ranks.rank, ranks.world)
+        shard_kw = {}
     if hi <= lo:
         raise ValueError(f" Ensemble: {n_members} members do not shard over {ranks.world} GPUs (a rank would be empty).")
     stride = _profile_stride(ens)
     sim = EnsembleSimulation(cols, forcing, hi - lo, seed=int(ens.get("Seed", 0)), device=device, member_offset=lo,
                              noise=str(ens.get("Noise", "philox")).lower(),
                              spinup=str(ens.get("Spinup", "shared")).lower(), profile_stride=stride,
-                             wtd_hist_stride=dist_stride, **_filter_kwargs(filt), **_enkf_kwargs(enkf, record, scheme, window))
+                             wtd_hist_stride=dist_stride, **_filter_kwargs(filt), **_enkf_kwargs(enkf, record, scheme, window),
+                             **shard_kw)
     label = f"Ensemble x{n_members}"
     _step_all(sim, rows, label, ranks)
     # the run's one collective: int64 (count, sum idx, sum idx^2) per row, exact and order-independent
@@ -250,13 +264,18 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     extra.update(tables)
     ftables, filter_line = _reduce_filter(ranks, sim, [0], 1, forcing.dim_t, filt, label, keep_points=False)
     extra.update(ftables)
-    etables, enkf_line = _reduce_enkf(ranks, sim, [0], 1, forcing.dim_t, enkf, label, keep_points=False,
+    # the EnKF's tables describe the one point: every rank of a sharded run holds the same ones, and rank 0's are taken
+    # (placed by it alone; a sum over the ranks would count them world times)
+    eids = [0] if ranks.rank == 0 else []
+    etables, enkf_line = _reduce_enkf(ranks, sim, eids, 1, forcing.dim_t, enkf, label, keep_points=False,
                                          z0_cm=cols.z[0])
     extra.update(etables)
     extra.update(_enkf_method_arrays(enkf, scheme))
-    stables, sm_line = _reduce_enkf_sm(ranks, sim, [0], 1, forcing.dim_t, enkf, record, label, keep_points=False)
+    if sharded is not None:
+        extra["enkf_sharded"] = np.array(1 if sharded else 0, dtype=np.int8)
+    stables, sm_line = _reduce_enkf_sm(ranks, sim, eids, 1, forcing.dim_t, enkf, record, label, keep_points=False)
     extra.update(stables)
-    wtables, window_line = _reduce_enkf_window(ranks, sim, [0], 1, forcing.dim_t, enkf, window, label, keep_points=False,
+    wtables, window_line = _reduce_enkf_window(ranks, sim, eids, 1, forcing.dim_t, enkf, window, label, keep_points=False,
                                                z0_cm=cols.z[0])
     extra.update(wtables)
     arrays = dict(moments=moments, wtd_mean_cm=mean_cm, wtd_std_cm=std_cm, rows=np.array(rows),
@@ -346,14 +365,15 @@ def filter_settings(ens, n_gpus=1):
     return stride, float(sigma), (None if seed is None else int(seed))
 
 
-ENKF_KEYS = ("Stride", "Sigma_cm", "Localisation_cm", "Seed", "Soil_Moisture", "Method", "Relaxation", "Window_Offsets")
+ENKF_KEYS = ("Stride", "Sigma_cm", "Localisation_cm", "Seed", "Soil_Moisture", "Method", "Relaxation", "Window_Offsets",
+             "Sharded")
 
 
 def enkf_settings(ens, n_gpus=1):
     """Ensemble.EnKF -> (stride, sigma_cm, localisation_cm, seed or None = the ensemble's seed); (0, None, None, None)
     when absent or off.  Pure: runs before any GPU call, and a bad value is a ValueError (message + exit status 1).  Refused
     together with a "Filter" block, and for a single-point ensemble on more than one GPU (its covariances would need a sum
-    over the ranks)."""
+    over the ranks) unless the block says ``"Sharded": true`` (:func:`enkf_sharded`)."""
     import math
     from numbers import Integral, Real
     block = ens.get("EnKF")
@@ -384,10 +404,24 @@ def enkf_settings(ens, n_gpus=1):
         return 0, None, None, None
     if ens.get("Filter") is not None:
         raise ValueError(" Ensemble: \"Filter\" and \"EnKF\" exclude each other: choose one.")
-    if not ens.get("Points") and int(n_gpus) > 1:
+    sharded = block.get("Sharded", False)
+    if not isinstance(sharded, bool):
+        raise ValueError(f" Ensemble: EnKF.Sharded = {sharded!r} must be true or false.")
+    if not ens.get("Points") and int(n_gpus) > 1 and not sharded:
         raise ValueError(f" Ensemble: EnKF with one parameter point runs on one GPU ({n_gpus} requested): its "
                          f"covariances would need a sum over the ranks.")
     return stride, float(sigma), float(loc), (None if seed is None else int(seed))
+
+
+def enkf_sharded(ens):
+    """Ensemble.EnKF.Sharded -> True / False, or None when the key is not given (or the EnKF is off).  With true a
+    single-point ensemble's members are dealt to the GPUs in whole tiles of 256 and every analysis gathers the ranks' tile
+    partials, so the run is the one-GPU run to the bit (include/hydrocol.h hc_set_enkf_shard); a sweep ignores it (its
+    points are dealt whole).  Checked by :func:`enkf_settings`."""
+    block = ens.get("EnKF")
+    if not isinstance(block, dict) or "Sharded" not in block or not enkf_settings(ens)[0]:
+        return None
+    return bool(block["Sharded"])
 
 
 ENKF_METHOD_NAMES = ("stochastic", "sqrt")

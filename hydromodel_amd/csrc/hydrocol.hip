@@ -216,6 +216,13 @@ struct hc_handle {
     DevBuf<double> win_y, enkf_eps_w;
     std::vector<int> win_last;
     AccTable<double> win{"entries"};
+    // one point's members on several handles (hc_set_enkf_shard): the point's member count (0: off) and this handle's
+    // first member in it; the caller's exchange buffer and callback; the point's first member's analysis column [D]
+    int64_t shard_global = 0, shard_first = 0, shard_words = 0;
+    double *shard_buf = nullptr;
+    hc_enkf_exchange_fn shard_fn = nullptr;
+    void *shard_ctx = nullptr;
+    DevBuf<double> enkf_first;
     int n_cu = 256;
     double jac_reject = NUM_JAC_DIFF_REJECT;
 };
@@ -1010,6 +1017,53 @@ __global__ __launch_bounds__(HC_MAX_DEPTH_NODES + WAVE) void enkf_partial_kernel
         if (i < W) out[i] = acc[i];
 }
 
+// enkf_partial_kernel for a handle that holds a part of one point's members (hc_set_enkf_shard): its mpp members are the
+// tiles tile0, tile0 + 1, ... of a point with np members and n_tiles tiles -- the means divide by np, and tile t's
+// partials go to tile tile0 + t of the point's layout [n_tiles][...].  The offset is uniform over the block: thread j's
+// stores stay as coalesced as they were.
+template <bool SQUARE>
+__global__ __launch_bounds__(HC_MAX_DEPTH_NODES + WAVE) void enkf_partial_shard_kernel(
+    const double *psi, const double *Y, int W, const double *sums, long long mpp, int Dc, long long n_tiles,
+    double *partial, double *square, long long np, long long tile0)
+{
+#pragma clang fp contract(off)
+    const long long t = blockIdx.x, to = tile0 + t;
+    const int j = threadIdx.x, C = Dc + W;
+    if (j >= C) return;
+    const long long m0 = t * ENKF_TILE;
+    const long long m1 = (t + 1) * ENKF_TILE < mpp ? (t + 1) * ENKF_TILE : mpp;
+    const double *x = j < Dc ? psi + j : Y + (j - Dc);
+    const long long xs = j < Dc ? Dc : W;
+    if (!sums) {
+        double s = 0.0;
+#pragma unroll 8
+        for (long long m = m0; m < m1; m++) s += x[(size_t)m * xs];
+        partial[(size_t)to * C + j] = s;
+        return;
+    }
+    const double xb = sums[j] / (double)np;
+    double yb[ENKF_OBS + 1], acc[ENKF_OBS + 1];
+#pragma unroll
+    for (int i = 0; i < ENKF_OBS + 1; i++) {
+        yb[i] = i < W ? sums[Dc + i] / (double)np : 0.0;
+        acc[i] = 0.0;
+    }
+    double sq = 0.0;
+    for (long long m = m0; m < m1; m++) {
+        const double a = x[(size_t)m * xs] - xb;
+        const double *ym = Y + (size_t)m * W;
+#pragma unroll
+        for (int i = 0; i < ENKF_OBS + 1; i++)
+            if (i < W) acc[i] += a * (ym[i] - yb[i]);
+        if (SQUARE) sq += a * a;
+    }
+    if (SQUARE && j < Dc) square[(size_t)to * Dc + j] = sq;
+    double *out = partial + ((size_t)to * C + j) * W;
+#pragma unroll
+    for (int i = 0; i < ENKF_OBS + 1; i++)
+        if (i < W) out[i] = acc[i];
+}
+
 // sums[p][c] = the tile partials of column c summed (thread t: tiles t, t + ENKF_THREADS, ... in order, then a fixed tree)
 __global__ __launch_bounds__(ENKF_THREADS) void enkf_finish_kernel(const double *partial, long long n_tiles, int n_cols,
                                                                    double *sums)
@@ -1447,6 +1501,43 @@ __global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void enkf_spread_kernel(const d
         }
     }
     partial[((size_t)p * n_tiles + t) * D + d] = s;
+}
+
+// enkf_spread_kernel for a handle that holds a part of one point's members (hc_set_enkf_shard; the tiles, np and tile0
+// of enkf_partial_shard_kernel): the point's first member's column is `first` [D], which another handle may hold.
+__global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void enkf_spread_shard_kernel(const double *psi, const double *sums,
+                                                                               long long mpp, int D, long long n_tiles,
+                                                                               double *partial, const double *first,
+                                                                               long long np, long long tile0)
+{
+#pragma clang fp contract(off)
+    const long long t = blockIdx.x;
+    const int d = threadIdx.x;
+    if (d >= D) return;
+    const long long m0 = t * ENKF_TILE;
+    const long long m1 = (t + 1) * ENKF_TILE < mpp ? (t + 1) * ENKF_TILE : mpp;
+    const double *x = psi + d;
+    const double x0 = first[d];
+    double s = 0.0;
+    if (!sums) {
+#pragma unroll 8
+        for (long long m = m0; m < m1; m++) s += x[(size_t)m * D] - x0;
+    } else {
+        const double xb = sums[d] / (double)np;
+#pragma unroll 8
+        for (long long m = m0; m < m1; m++) {
+            const double a = (x[(size_t)m * D] - x0) - xb;
+            s += a * a;
+        }
+    }
+    partial[(size_t)(tile0 + t) * D + d] = s;
+}
+
+// the point's first member's column, by the handle that holds it, into the exchange buffer (hc_set_enkf_shard)
+__global__ void enkf_first_member_kernel(const double *psi, int D, double *first)
+{
+    const int d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d < D) first[d] = psi[d];
 }
 
 // Relaxation to prior spread (Whitaker & Hamill 2012), one thread per point and node: from the sums of the squared psi
@@ -1893,8 +1984,27 @@ void sm_off(hc_handle *h)
     h->enkf_eps_s.release();
 }
 
+void shard_off(hc_handle *h)
+{
+    h->shard_global = h->shard_first = h->shard_words = 0;
+    h->shard_buf = nullptr;
+    h->shard_fn = nullptr;
+    h->shard_ctx = nullptr;
+    h->enkf_first.release();
+}
+
+// what a sharded analysis of a point with n_global members gathers at most, in doubles: the global tile count times the
+// widest pass as the record and the window stand -- the prior products with the squared psi anomalies the relaxation
+// takes along, or the posterior's
+int64_t shard_words_needed(const hc_handle *h, int64_t n_global)
+{
+    const int64_t D = h->p.dim_d, Wx = 1 + h->sm_n + h->win_n, n_tiles = (n_global + ENKF_TILE - 1) / ENKF_TILE;
+    return n_tiles * std::max((D + Wx) * Wx + D, (Wx + 1) * (Wx + 1));
+}
+
 void enkf_off(hc_handle *h)
 {
+    shard_off(h);
     h->enkf_stride = 0;
     h->enkf_done = false;
     h->enkf_width = 0;
@@ -2857,6 +2967,17 @@ int enkf_capture(hc_handle *h, const Chunk &c, int slot)
     return HC_OK;
 }
 
+// Before a reduction of a sharded analysis (hc_set_enkf_shard): the handle's words of the pass are written, the stream is
+// drained and the caller's callback gathers everyone else's into place.  A callback that fails fails the step.
+int enkf_exchange(hc_handle *h, double *pass, int64_t n_words, int64_t first_word, int64_t count_words)
+{
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const int rc = h->shard_fn(h->shard_ctx, pass, n_words, first_word, count_words);
+    if (rc) return fail(HC_ERR_DEVICE, "the EnKF shard's exchange callback returned %d (words [%lld, %lld) of %lld)", rc,
+                        (long long)first_word, (long long)(first_word + count_words), (long long)n_words);
+    return HC_OK;
+}
+
 // The EnKF's analysis at the launch's last row (its water-table indices are wtd_u16's last row), m' = 1 + s.m
 // observations per member, in place on psi: y and theta per member; per point the column and observation sums, then the
 // anomaly products (two passes over psi); the gain and the prior diagnostics; the update with eps and the posterior (y,
@@ -2864,31 +2985,80 @@ int enkf_capture(hc_handle *h, const Chunk &c, int slot)
 // record's largest m', 1 + sm_n.  hc_set_enkf_method: the square-root scheme swaps the draws and the update for its own
 // (the gain kernel adds the reduced gain and the mean's increment); a relaxation alpha > 0 takes the squared psi
 // anomalies along in the second prior pass, sums the analysis columns and their squared anomalies (two more passes over
-// psi), relaxes (one read + write) and only then forms the posterior.
+// psi), relaxes (one read + write) and only then forms the posterior.  hc_set_enkf_shard: the handle's members are a part
+// of the point's; every partial pass writes the handle's tiles into the pass's global layout in the caller's buffer and
+// every reduction gathers the other handles' first (one callback each; one more for the point's first member's column
+// under relaxation), so the sums -- and everything after them -- are those of the one handle that holds every member.
 int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
 {
     const int64_t N = h->n_members, D = h->p.dim_d, P = h->n_points, mpp = N / P;
     const int64_t row = c.row0 + c.rows - 1, slot = row / h->enkf_stride, n_arow = enkf_rows(h);
-    const int64_t n_tiles = (mpp + ENKF_TILE - 1) / ENKF_TILE;
+    // hc_set_enkf_shard: the handle's members are tiles tile0 ... of a point with np members and n_tiles tiles; every
+    // reduction gathers the other handles' partials first (reduce below).  Off: np = mpp, the handle's own tiles.
+    const bool shard = h->shard_global > 0;
+    const int64_t np = shard ? h->shard_global : mpp, tile0 = shard ? h->shard_first / ENKF_TILE : 0;
+    const int64_t my_tiles = (mpp + ENKF_TILE - 1) / ENKF_TILE, n_tiles = (np + ENKF_TILE - 1) / ENKF_TILE;
     const int W = s.m + 1, V = s.ms + 2, mw = s.m - s.ms;
     const int64_t C = D + W, Wx = 1 + h->sm_n + h->win_n, Cx = D + Wx;
+    if (shard && h->shard_words < shard_words_needed(h, np))
+        return fail(HC_ERR_ARG, "the shard's buffer holds %lld doubles, the analysis needs %lld (sensors or a window set "
+                    "after hc_set_enkf_shard: set the shard again)", (long long)h->shard_words,
+                    (long long)shard_words_needed(h, np));
     const int64_t cols_x = std::max(Cx * Wx, (Wx + 1) * (Wx + 1));   // the widest pass: the prior products or the posterior's
     if (h->enkf_Y.ensure((size_t)(N * Wx)) || h->enkf_eps.ensure((size_t)N) ||
         h->enkf_eps_s.ensure((size_t)(N * h->sm_n)) || h->enkf_eps_w.ensure((size_t)(N * h->win_n)) ||
         h->enkf_Ypost.ensure((size_t)(N * (Wx + 1))) ||
         h->enkf_gain.ensure((size_t)(P * Wx * D)) || h->enkf_s1.ensure((size_t)(P * Cx)) ||
-        h->enkf_s2.ensure((size_t)(P * cols_x)) || h->enkf_part.ensure((size_t)(P * n_tiles * cols_x)))
+        h->enkf_s2.ensure((size_t)(P * cols_x)) || (!shard && h->enkf_part.ensure((size_t)(P * n_tiles * cols_x))))
         return HC_ERR_DEVICE;
     const bool root = h->enkf_method == 1, relax = h->enkf_alpha > 0.0;
     if (root && (h->enkf_rgain.ensure((size_t)(P * Wx * D)) || h->enkf_dbar.ensure((size_t)(P * D)))) return HC_ERR_DEVICE;
-    if (relax && (h->enkf_part_sq.ensure((size_t)(P * n_tiles * D)) || h->enkf_sq_b.ensure((size_t)(P * D)) ||
+    if (relax && ((!shard && h->enkf_part_sq.ensure((size_t)(P * n_tiles * D))) || h->enkf_sq_b.ensure((size_t)(P * D)) ||
+                  (shard && h->enkf_first.ensure((size_t)D)) ||
                   h->enkf_sq_a.ensure((size_t)(P * D)) || h->enkf_mean_a.ensure((size_t)(P * D)) ||
                   h->enkf_relax.ensure((size_t)(4 * P * D))))
         return HC_ERR_DEVICE;
     const unsigned short *w = h->wtd_u16.p + (size_t)(c.rows - 1) * N;
     const double dz = h->p.dz, z_obs = (double)h->h_wtd_obs[(size_t)row] * dz;
     const int special = (int)h->use_special();
-    const long long ll_mpp = (long long)mpp, ll_tiles = (long long)n_tiles;
+    const long long ll_mpp = (long long)mpp, ll_tiles = (long long)n_tiles, ll_np = (long long)np, ll_tile0 = (long long)tile0;
+    // the tile partials: the handle's own buffers, or the passes' global layouts in the caller's (the squared anomalies
+    // behind the prior products they travel with)
+    double *const part = shard ? h->shard_buf : h->enkf_part.p;
+    double *const part_sq_b = shard ? h->shard_buf + (size_t)(n_tiles * C * W) : h->enkf_part_sq.p;
+    double *const part_sq = shard ? h->shard_buf : h->enkf_part_sq.p;
+    const long long draw_offset = (long long)(shard ? h->shard_first : h->member_offset);
+    const dim3 tiles((unsigned)my_tiles, (unsigned)P);
+    // the tile partials of one pass (enkf_partial_kernel's arguments; its sharded form at the handle's tile offset)
+    auto partials = [&](bool square, const double *psi, const double *Y, int width, const double *sums, int Dc,
+                        dim3 threads, double *out, double *out_sq) {
+        if (shard && square)
+            hipLaunchKernelGGL(enkf_partial_shard_kernel<true>, tiles, threads, 0, h->stream, psi, Y, width, sums, ll_mpp,
+                               Dc, ll_tiles, out, out_sq, ll_np, ll_tile0);
+        else if (shard)
+            hipLaunchKernelGGL(enkf_partial_shard_kernel<false>, tiles, threads, 0, h->stream, psi, Y, width, sums, ll_mpp,
+                               Dc, ll_tiles, out, out_sq, ll_np, ll_tile0);
+        else if (square)
+            hipLaunchKernelGGL(enkf_partial_kernel<true>, tiles, threads, 0, h->stream, psi, Y, width, sums, ll_mpp, Dc,
+                               ll_tiles, out, out_sq);
+        else
+            hipLaunchKernelGGL(enkf_partial_kernel<false>, tiles, threads, 0, h->stream, psi, Y, width, sums, ll_mpp, Dc,
+                               ll_tiles, out, out_sq);
+        return hipGetLastError();
+    };
+    // sums[p][c] of a pass of `cols` columns from its tile partials; sharded: the stream drained and the other handles'
+    // tiles gathered first (a copy: the partials are the ones one handle would have formed)
+    auto reduce = [&](double *pass, int64_t cols, double *sums) -> int {
+        if (shard)
+            if (int rc = enkf_exchange(h, pass, n_tiles * cols, tile0 * cols, my_tiles * cols)) return rc;
+        hipLaunchKernelGGL(enkf_finish_kernel, dim3((unsigned)cols, (unsigned)P), dim3(ENKF_THREADS), 0, h->stream, pass,
+                           ll_tiles, (int)cols, sums);
+        HIP_TRY(hipGetLastError());
+        return HC_OK;
+    };
+    // (the kernels that take N_p alone -- the gain, the posterior -- get np; so do the square-root update and the
+    //  relaxation's factors, which also index the points by m / N_p: a sharded handle holds one point, m / np = 0)
+    int rc = HC_OK;
     const dim3 members((unsigned)((N + 255) / 256));
     hipLaunchKernelGGL(enkf_obs_kernel, members, dim3(256), 0, h->stream, w, h->psi.p, h->Pdev.p, (long long)N, ll_mpp,
                        (int)D, dz, h->enkf_Y.p, W);
@@ -2904,50 +3074,33 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
         HIP_TRY(hipGetLastError());
     }
     // prior: the sums of (psi, Y), then the products of their anomalies with Y's
-    const dim3 tiles((unsigned)n_tiles, (unsigned)P);
     const dim3 cols_prior((unsigned)((C + WAVE - 1) / WAVE * WAVE)), cols_post((unsigned)WAVE);
-    hipLaunchKernelGGL(enkf_partial_kernel<false>, tiles, cols_prior, 0, h->stream, h->psi.p, h->enkf_Y.p, W, nullptr, ll_mpp,
-                       (int)D, ll_tiles, h->enkf_part.p, nullptr);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(enkf_finish_kernel, dim3((unsigned)C, (unsigned)P), dim3(ENKF_THREADS), 0, h->stream,
-                       h->enkf_part.p, ll_tiles, (int)C, h->enkf_s1.p);
-    HIP_TRY(hipGetLastError());
-    if (relax)
-        hipLaunchKernelGGL(enkf_partial_kernel<true>, tiles, cols_prior, 0, h->stream, h->psi.p, h->enkf_Y.p, W,
-                           h->enkf_s1.p, ll_mpp, (int)D, ll_tiles, h->enkf_part.p, h->enkf_part_sq.p);
-    else
-        hipLaunchKernelGGL(enkf_partial_kernel<false>, tiles, cols_prior, 0, h->stream, h->psi.p, h->enkf_Y.p, W,
-                           h->enkf_s1.p, ll_mpp, (int)D, ll_tiles, h->enkf_part.p, nullptr);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(enkf_finish_kernel, dim3((unsigned)(C * W), (unsigned)P), dim3(ENKF_THREADS), 0, h->stream,
-                       h->enkf_part.p, ll_tiles, (int)(C * W), h->enkf_s2.p);
-    HIP_TRY(hipGetLastError());
-    if (relax) {
-        hipLaunchKernelGGL(enkf_finish_kernel, dim3((unsigned)D, (unsigned)P), dim3(ENKF_THREADS), 0, h->stream,
-                           h->enkf_part_sq.p, ll_tiles, (int)D, h->enkf_sq_b.p);
-        HIP_TRY(hipGetLastError());
-    }
+    HIP_TRY(partials(false, h->psi.p, h->enkf_Y.p, W, nullptr, (int)D, cols_prior, part, nullptr));
+    if ((rc = reduce(part, C, h->enkf_s1.p))) return rc;
+    HIP_TRY(partials(relax, h->psi.p, h->enkf_Y.p, W, h->enkf_s1.p, (int)D, cols_prior, part, relax ? part_sq_b : nullptr));
+    if ((rc = reduce(part, C * W, h->enkf_s2.p))) return rc;
+    if (relax && (rc = reduce(part_sq_b, D, h->enkf_sq_b.p))) return rc;
     double *st = h->enkf.buf.p, *sst = h->sm.buf.p, *wst = h->win.buf.p;
     hipLaunchKernelGGL(enkf_gain_kernel, dim3((unsigned)P), dim3((unsigned)((D + WAVE - 1) / WAVE * WAVE)), 0, h->stream,
-                       h->enkf_s1.p, h->enkf_s2.p, ll_mpp, (int)D, s, h->enkf_sigma, h->enkf_loc, z_obs, dz,
+                       h->enkf_s1.p, h->enkf_s2.p, ll_np, (int)D, s, h->enkf_sigma, h->enkf_loc, z_obs, dz,
                        h->enkf_gain.p, st, sst, (long long)n_arow, (long long)slot, root ? h->enkf_rgain.p : nullptr,
                        root ? h->enkf_dbar.p : nullptr, wst);
     HIP_TRY(hipGetLastError());
     const unsigned blocks = (unsigned)std::min<int64_t>((N + 3) / 4, (int64_t)h->n_cu * 8);
     if (root) {
         hipLaunchKernelGGL(enkf_sqrt_update_kernel, dim3(blocks), dim3(256), 0, h->stream, h->psi.p, h->enkf_Y.p,
-                           h->enkf_rgain.p, h->enkf_dbar.p, h->enkf_s1.p, h->Pdev.p, (long long)N, ll_mpp, (int)D, dz, W, V,
+                           h->enkf_rgain.p, h->enkf_dbar.p, h->enkf_s1.p, h->Pdev.p, (long long)N, ll_np, (int)D, dz, W, V,
                            relax ? 0 : 1, h->enkf_Ypost.p);
         HIP_TRY(hipGetLastError());
     } else {
         hipLaunchKernelGGL(enkf_draw_kernel, members, dim3(256), 0, h->stream, (long long)N, ll_mpp,
                            (unsigned long long)h->enkf_seed, P > 1 ? h->point_base.p : nullptr,
-                           (long long)h->member_offset, (unsigned)row, s.n, h->enkf_eps.p, h->enkf_eps_s.p);
+                           draw_offset, (unsigned)row, s.n, h->enkf_eps.p, h->enkf_eps_s.p);
         HIP_TRY(hipGetLastError());
         if (mw > 0) {
             hipLaunchKernelGGL(enkf_window_draw_kernel, members, dim3(256), 0, h->stream, (long long)N, ll_mpp,
                                (unsigned long long)h->enkf_seed, P > 1 ? h->point_base.p : nullptr,
-                               (long long)h->member_offset, s, h->enkf_eps_w.p);
+                               draw_offset, s, h->enkf_eps_w.p);
             HIP_TRY(hipGetLastError());
         }
         hipLaunchKernelGGL(enkf_update_kernel, dim3(blocks), dim3(256), 0, h->stream, h->psi.p, h->enkf_Y.p,
@@ -2958,21 +3111,33 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
     if (relax) {
         // the analysis columns' sums, then their squared anomalies; the factors; the relaxed columns and their y
         const dim3 cols_psi((unsigned)((D + WAVE - 1) / WAVE * WAVE));
-        hipLaunchKernelGGL(enkf_spread_kernel, tiles, cols_psi, 0, h->stream, h->psi.p, nullptr, ll_mpp, (int)D, ll_tiles,
-                           h->enkf_part_sq.p);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(enkf_finish_kernel, dim3((unsigned)D, (unsigned)P), dim3(ENKF_THREADS), 0, h->stream,
-                           h->enkf_part_sq.p, ll_tiles, (int)D, h->enkf_mean_a.p);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(enkf_spread_kernel, tiles, cols_psi, 0, h->stream, h->psi.p, h->enkf_mean_a.p, ll_mpp, (int)D,
-                           ll_tiles, h->enkf_part_sq.p);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(enkf_finish_kernel, dim3((unsigned)D, (unsigned)P), dim3(ENKF_THREADS), 0, h->stream,
-                           h->enkf_part_sq.p, ll_tiles, (int)D, h->enkf_sq_a.p);
-        HIP_TRY(hipGetLastError());
+        auto spread = [&](const double *sums) {
+            if (shard)
+                hipLaunchKernelGGL(enkf_spread_shard_kernel, tiles, cols_psi, 0, h->stream, h->psi.p, sums, ll_mpp, (int)D,
+                                   ll_tiles, part_sq, h->enkf_first.p, ll_np, ll_tile0);
+            else
+                hipLaunchKernelGGL(enkf_spread_kernel, tiles, cols_psi, 0, h->stream, h->psi.p, sums, ll_mpp, (int)D,
+                                   ll_tiles, part_sq);
+            return hipGetLastError();
+        };
+        if (shard) {
+            // the point's first member's analysis column, from the handle that holds it, to every handle
+            const bool mine = h->shard_first == 0;
+            if (mine) {
+                hipLaunchKernelGGL(enkf_first_member_kernel, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, h->stream,
+                                   h->psi.p, (int)D, h->shard_buf);
+                HIP_TRY(hipGetLastError());
+            }
+            if ((rc = enkf_exchange(h, h->shard_buf, D, 0, mine ? D : 0))) return rc;
+            HIP_TRY(hipMemcpyAsync(h->enkf_first.p, h->shard_buf, (size_t)D * 8, hipMemcpyDeviceToDevice, h->stream));
+        }
+        HIP_TRY(spread(nullptr));
+        if ((rc = reduce(part_sq, D, h->enkf_mean_a.p))) return rc;
+        HIP_TRY(spread(h->enkf_mean_a.p));
+        if ((rc = reduce(part_sq, D, h->enkf_sq_a.p))) return rc;
         hipLaunchKernelGGL(enkf_relax_factor_kernel, dim3((unsigned)((P * D + 255) / 256)), dim3(256), 0, h->stream,
-                           h->enkf_sq_b.p, h->enkf_sq_a.p, h->enkf_mean_a.p, h->psi.p, h->enkf_gain.p, (long long)P, ll_mpp,
-                           (int)D, W, h->enkf_alpha, h->enkf_relax.p);
+                           h->enkf_sq_b.p, h->enkf_sq_a.p, h->enkf_mean_a.p, shard ? h->enkf_first.p : h->psi.p,
+                           h->enkf_gain.p, (long long)P, ll_np, (int)D, W, h->enkf_alpha, h->enkf_relax.p);
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(enkf_relax_kernel, dim3(blocks), dim3(256), 0, h->stream, h->psi.p,
                            h->enkf_relax.p + (size_t)(3 * P * D), h->enkf_relax.p + (size_t)(2 * P * D), h->Pdev.p, (long long)N, ll_mpp, (int)D, dz, V,
@@ -2985,20 +3150,12 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
         HIP_TRY(hipGetLastError());
     }
     // posterior: the same two passes over (y, theta, rejected) alone
-    hipLaunchKernelGGL(enkf_partial_kernel<false>, tiles, cols_post, 0, h->stream, nullptr, h->enkf_Ypost.p, V, nullptr, ll_mpp,
-                       0, ll_tiles, h->enkf_part.p, nullptr);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(enkf_finish_kernel, dim3((unsigned)V, (unsigned)P), dim3(ENKF_THREADS), 0, h->stream,
-                       h->enkf_part.p, ll_tiles, V, h->enkf_s1.p);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(enkf_partial_kernel<false>, tiles, cols_post, 0, h->stream, nullptr, h->enkf_Ypost.p, V, h->enkf_s1.p,
-                       ll_mpp, 0, ll_tiles, h->enkf_part.p, nullptr);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(enkf_finish_kernel, dim3((unsigned)(V * V), (unsigned)P), dim3(ENKF_THREADS), 0, h->stream,
-                       h->enkf_part.p, ll_tiles, V * V, h->enkf_s2.p);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(partials(false, nullptr, h->enkf_Ypost.p, V, nullptr, 0, cols_post, part, nullptr));
+    if ((rc = reduce(part, V, h->enkf_s1.p))) return rc;
+    HIP_TRY(partials(false, nullptr, h->enkf_Ypost.p, V, h->enkf_s1.p, 0, cols_post, part, nullptr));
+    if ((rc = reduce(part, V * V, h->enkf_s2.p))) return rc;
     hipLaunchKernelGGL(enkf_post_kernel, dim3((unsigned)((P + 63) / 64)), dim3(64), 0, h->stream, h->enkf_s1.p,
-                       h->enkf_s2.p, (long long)P, ll_mpp, s, st, sst, (long long)n_arow, (long long)slot);
+                       h->enkf_s2.p, (long long)P, ll_np, s, st, sst, (long long)n_arow, (long long)slot);
     HIP_TRY(hipGetLastError());
     h->enkf_done = true;
     h->enkf_width = W;
@@ -3757,6 +3914,62 @@ int hc_get_enkf_window_gain(hc_handle *h, double *gain)
     if (!h || !gain) return fail(HC_ERR_ARG, "hc_get_enkf_window_gain: bad argument");
     if (h->enkf_stride <= 0 || !h->enkf_done) return fail(HC_ERR_ARG, "hc_get_enkf_window_gain: no analysis since hc_set_enkf");
     return gain_hook(h, gain, (size_t)h->enkf_width, "hc_get_enkf_window_gain");
+}
+
+int hc_get_enkf_shard_words(hc_handle *h, int64_t n_global, int64_t *n_words)
+{
+    if (!h || !n_words || n_global < 1) return fail(HC_ERR_ARG, "hc_get_enkf_shard_words: bad argument");
+    if (h->enkf_stride <= 0) return fail(HC_ERR_ARG, "hc_get_enkf_shard_words: the EnKF is off (hc_set_enkf)");
+    *n_words = shard_words_needed(h, n_global);
+    return HC_OK;
+}
+
+int hc_set_enkf_shard(hc_handle *h, int64_t n_global, int64_t first_global, void *device_buf, int64_t n_words,
+                      hc_enkf_exchange_fn fn, void *ctx)
+{
+    if (!h || n_global < 0) return fail(HC_ERR_ARG, "hc_set_enkf_shard: bad argument");
+    if (n_global == 0) {
+        shard_off(h);
+        return HC_OK;
+    }
+    if (h->enkf_stride <= 0) return fail(HC_ERR_ARG, "hc_set_enkf_shard: the EnKF is off (hc_set_enkf comes first)");
+    if (h->n_points > 1)
+        return fail(HC_ERR_ARG, "hc_set_enkf_shard: the handle holds %d points (a shard is a part of one point's members)",
+                    h->n_points);
+    const int64_t N = h->n_members;
+    if (first_global < 0 || first_global % ENKF_TILE != 0)
+        return fail(HC_ERR_ARG, "hc_set_enkf_shard: first_global = %lld must be a multiple of %d", (long long)first_global,
+                    ENKF_TILE);
+    if (first_global + N > n_global)
+        return fail(HC_ERR_ARG, "hc_set_enkf_shard: members [%lld, %lld) lie outside the point's %lld",
+                    (long long)first_global, (long long)(first_global + N), (long long)n_global);
+    if (first_global + N < n_global && N % ENKF_TILE != 0)
+        return fail(HC_ERR_ARG, "hc_set_enkf_shard: %lld members on a shard that is not the point's last must be a "
+                    "multiple of %d", (long long)N, ENKF_TILE);
+    if (h->philox && h->member_offset != first_global)
+        return fail(HC_ERR_ARG, "hc_set_enkf_shard: first_global = %lld, but hc_set_noise_philox keys the members from %lld",
+                    (long long)first_global, (long long)h->member_offset);
+    if (!device_buf || !fn) return fail(HC_ERR_ARG, "hc_set_enkf_shard: NULL buffer or callback");
+    if (n_words < shard_words_needed(h, n_global))
+        return fail(HC_ERR_ARG, "hc_set_enkf_shard: a buffer of %lld doubles, %lld needed (hc_get_enkf_shard_words)",
+                    (long long)n_words, (long long)shard_words_needed(h, n_global));
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->shard_global = n_global;
+    h->shard_first = first_global;
+    h->shard_buf = static_cast<double *>(device_buf);
+    h->shard_words = n_words;
+    h->shard_fn = fn;
+    h->shard_ctx = ctx;
+    return HC_OK;
+}
+
+int hc_get_enkf_shard(hc_handle *h, int64_t *n_global, int64_t *first_global)
+{
+    if (!h || !n_global || !first_global) return fail(HC_ERR_ARG, "hc_get_enkf_shard: bad argument");
+    *n_global = h->shard_global;
+    *first_global = h->shard_first;
+    return HC_OK;
 }
 
 int hc_set_enkf_method(hc_handle *h, int32_t method, double relaxation)

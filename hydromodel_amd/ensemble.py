@@ -250,17 +250,31 @@ class EnsembleSimulation(_Run):
     spinup="member": every member spins up with its own first draw (`spinup_members_on_gpu`).
     profile_stride, wtd_hist_stride, filter_stride / filter_sigma_cm / filter_seed, enkf_stride / enkf_sigma_cm /
     enkf_localisation_cm / enkf_seed: the optional tables, the particle filter and the EnKF (:class:`_Run`).
+    enkf_shard=(n_global, exchange): these members are [member_offset, member_offset + N) of an ensemble of ``n_global``
+    whose other members run elsewhere, and the EnKF analyses the whole of it (include/hydrocol.h hc_set_enkf_shard;
+    ``exchange``: e.g. a ``multigpu.ShardExchange``).  member_offset must be a multiple of 256, and so must N unless the
+    block is the ensemble's last.  Set up by the run: a checkpoint does not carry it.
     """
 
     def __init__(self, cols, forcing, n_members, seed=0, device=0, member_offset=0, psi0=None, flags=None,
                  noise="philox", spinup="shared", profile_stride=0, wtd_hist_stride=0, filter_stride=0,
                  filter_sigma_cm=None, filter_seed=None, enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0,
                  enkf_seed=None, enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0,
-                 enkf_window_offsets=()):
+                 enkf_window_offsets=(), enkf_shard=None):
+        if enkf_shard is not None:
+            from . import _lib
+            _lib.load(with_torch=True)             # torch before the library: the shard's buffer is a torch tensor
         self._start(cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup)
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
                            enkf_relaxation, enkf_window_offsets)
+        self.enkf_shard = None
+        if enkf_shard is not None:
+            if not self.enkf_stride:
+                raise ValueError("enkf_shard needs the EnKF (enkf_stride > 0)")
+            n_global, exchange = enkf_shard
+            self.stepper.set_enkf_shard(n_global, self.member_offset, exchange)      # (after the sensors and the window)
+            self.enkf_shard = (int(n_global), self.member_offset)
 
     def _start(self, cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup):
         if noise not in ("philox", "numpy") or spinup not in ("shared", "member"):

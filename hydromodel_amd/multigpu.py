@@ -7,7 +7,9 @@ a GPU, never a re-exec -- and every rank runs its share with no communication wh
 
 * ensemble: rank r owns the contiguous member block ``shard(N, r, world)``; the Philox stream is keyed by the GLOBAL
   member id, the shared initial condition is global member 0's spin-up on every rank, and ONE int64 all-reduce of the
-  per-row water-table moments ``[3][T]`` ends the run (RCCL over xGMI with the nccl backend);
+  per-row water-table moments ``[3][T]`` ends the run (RCCL over xGMI with the nccl backend); with a sharded EnKF
+  (``"EnKF": {"Sharded": true}``) the members are dealt in whole tiles (:func:`shard_tiles`) and every analysis gathers
+  the ranks' tile partials before each of its reductions (:class:`ShardExchange`), so the analyses are the one-rank run's;
 * sweep (BASELINE config 5): whole points are dealt round-robin (``ensemble.deal_points``); every rank places ITS points
   in zeroed ``[P][3][T]`` / ``[P][D]`` / ``[P]`` tables and one all-reduce each assembles them (:func:`place_points`: float64
   tables travel as their int64 bits, so the assembled file holds every point's bits exactly as the rank that ran it
@@ -107,6 +109,64 @@ def shard(n_members, rank, world):
     base, extra = divmod(n, w)
     lo = r * base + min(r, extra)
     return lo, lo + base + (1 if r < extra else 0)
+
+
+def shard_tiles(n_members, rank, world, tile=256):
+    """[lo, hi): the contiguous member block of rank `rank` when whole tiles of `tile` members are dealt (the EnKF's sums
+    are formed tile by tile: a sharded analysis needs every block to start on a tile boundary, include/hydrocol.h
+    hc_set_enkf_shard).  The tiles are dealt as evenly as :func:`shard` deals members, the ranks that get one more being
+    the last ones -- the last tile may be partial, so the blocks differ by at most one tile of members.  A rank left
+    without a member is a ValueError."""
+    n, r, w, t = int(n_members), int(rank), int(world), int(tile)
+    n_tiles = -(-n // t)
+    base, extra = divmod(n_tiles, w)
+    lo = r * base + max(0, r - (w - extra))
+    hi = lo + base + (1 if r >= w - extra else 0)
+    lo, hi = lo * t, min(hi * t, n)
+    if hi <= lo:
+        raise ValueError(f" Ensemble: {n} members are {n_tiles} tiles of {t}: they do not shard over {w} GPUs "
+                         f"(a rank would be empty).")
+    return lo, hi
+
+
+class ShardExchange:
+    """The gather of a sharded EnKF analysis over the ranks (``EnsembleStepper.set_enkf_shard``'s ``exchange``): called
+    with ``block``, a float64 tensor whose words [first, first + count) are this rank's, it returns with every other
+    rank's words in place.  The ranks' blocks differ in size (and one rank alone contributes the point's first member),
+    so each call first gathers the (first, count) pairs and pads the blocks to the largest: one regular all-gather.  Copies
+    only: every bit arrives as it was written.  nccl gathers on the device tensor; gloo (ranks sharing a card in a
+    rehearsal, CPU tensors in a test) stages through the host.  One rank: the identity."""
+
+    def __init__(self, ranks):
+        self.ranks = ranks
+        self.calls = 0
+
+    def __call__(self, block, first, count):
+        import torch
+        self.calls += 1
+        dist, world = self.ranks.dist, self.ranks.world
+        if dist is None or world == 1:
+            return
+        on_device = self.ranks.backend == "nccl"
+        where = block.device if on_device else torch.device("cpu")
+        meta = torch.tensor([int(first), int(count)], dtype=torch.int64, device=where)
+        metas = [torch.zeros_like(meta) for _ in range(world)]
+        dist.all_gather(metas, meta)
+        spans = [tuple(int(v) for v in m.tolist()) for m in metas]
+        if any(f < 0 or c < 0 or f + c > block.numel() for f, c in spans):
+            raise RuntimeError(f" EnKF shard exchange: the ranks' word ranges {spans} do not fit {block.numel()} words.")
+        widest = max(c for _, c in spans)
+        if widest == 0:
+            return
+        mine = torch.zeros(widest, dtype=torch.float64, device=where)
+        mine[:count] = block[first:first + count].to(where)
+        parts = [torch.empty_like(mine) for _ in range(world)]
+        dist.all_gather(parts, mine)
+        for r, (f, c) in enumerate(spans):
+            if r != self.ranks.rank and c:
+                block[f:f + c] = parts[r][:c].to(block.device)
+        if block.is_cuda:
+            torch.cuda.synchronize(block.device)          # in place before the library's stream reads it
 
 
 def place_points(local, point_ids, n_points, ranks=None):

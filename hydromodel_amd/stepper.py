@@ -81,6 +81,8 @@ class EnsembleStepper:
         self.enkf_sm_nodes = None
         self.enkf_method, self.enkf_relaxation = "stochastic", 0.0
         self.enkf_window_offsets = ()
+        self.device = int(device)
+        self.enkf_shard, self._shard_keep, self._shard_error = None, None, None
         if profile_stride:
             self.set_profile_stats(profile_stride)
 
@@ -169,7 +171,11 @@ class EnsembleStepper:
         if want_diag:
             out["diag"] = np.zeros((n_rows, self.N, 2))
             a.diag_out = L.dptr(out["diag"])
-        L.check(self.lib.hc_step_rows(self.h, C.byref(a)))
+        rc = self.lib.hc_step_rows(self.h, C.byref(a))
+        failure, self._shard_error = self._shard_error, None
+        if rc and failure is not None:             # the shard's exchange raised inside the call (set_enkf_shard)
+            raise L.HcError(f"libhydrocol status {rc}: {self.lib.hc_last_error().decode()}") from failure
+        L.check(rc)
         if want_stats:
             # slot 5 of the C-ABI record = refresh flag | failed attempts << 8 (include/hydrocol.h)
             out["failed"] = out["stats"][:, :, 5] >> 8
@@ -341,6 +347,7 @@ class EnsembleStepper:
         self.enkf_sm_nodes = None
         self.enkf_method, self.enkf_relaxation = "stochastic", 0.0
         self.enkf_window_offsets = ()
+        self.enkf_shard = None
 
     def filter_table(self):
         """[P][n_arow][4] float64: count, ESS, log-likelihood increment, survivors per assimilation slot (slot j <-> row
@@ -404,6 +411,7 @@ class EnsembleStepper:
         self.enkf_sm_nodes = None                             # hc_set_enkf removes the sensor record
         self.enkf_method, self.enkf_relaxation = "stochastic", 0.0       # ... and resets the analysis scheme
         self.enkf_window_offsets = ()                         # ... and turns the window off
+        self.enkf_shard = None                                # ... and the sharding
         L.check(self.lib.hc_set_enkf(self.h, stride, sigma, loc, int(seed) & 0xFFFFFFFFFFFFFFFF))
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = stride, sigma, loc, int(seed)
 
@@ -601,6 +609,54 @@ class EnsembleStepper:
         out = np.zeros((self.P, self.D, self.enkf_width()))
         L.check(self.lib.hc_get_enkf_window_gain(self.h, L.dptr(out)))
         return out
+
+    # -- one point's members on several handles (include/hydrocol.h hc_set_enkf_shard) ----------------------------------
+    def enkf_shard_words(self, n_global):
+        """Doubles the shard's exchange buffer must hold for ``n_global`` members, as the sensors and the window stand."""
+        n = np.zeros(1, dtype=np.int64)
+        L.check(self.lib.hc_get_enkf_shard_words(self.h, int(n_global), L.lptr(n)))
+        return int(n[0])
+
+    def set_enkf_shard(self, n_global, first_global=0, exchange=None):
+        """This handle holds members [first_global, first_global + N) of a point with ``n_global`` members: its analyses
+        become those of the whole ensemble, to the bit.  ``exchange(block, first_word, count_words)`` is called before
+        each of the analysis's reductions with ``block``, a float64 device tensor (a view of the handle's exchange buffer)
+        whose words [first_word, first_word + count_words) are this handle's; on return everyone else's must be in place
+        (:class:`multigpu.ShardExchange`; None: nothing to gather, for a handle that holds every member).  An exception it
+        raises fails the step.  ``n_global`` = 0 turns sharding off.  The EnKF, its sensors and its window come first.
+        torch must have been imported before this process made its first handle (``_lib.load``)."""
+        n_global, first = int(n_global), int(first_global)
+        self._shard_keep = None
+        if not n_global:
+            L.check(self.lib.hc_set_enkf_shard(self.h, 0, 0, None, 0, L.EXCHANGE_FN(), None))
+            self.enkf_shard = None
+            return
+        L.load(with_torch=True)                    # the buffer is torch's: one HIP runtime must serve both
+        import torch
+        buf = torch.zeros(max(self.enkf_shard_words(n_global), 1), dtype=torch.float64,
+                          device=torch.device("cuda", self.device))
+        base = buf.data_ptr()
+
+        def call(_ctx, ptr, n_words, first_word, count_words):
+            try:                                   # nothing may propagate through the C frames
+                if exchange is not None:
+                    at = (int(ptr) - base) // 8
+                    exchange(buf[at:at + n_words], int(first_word), int(count_words))
+                return 0
+            except BaseException as e:  # noqa: BLE001
+                self._shard_error = e
+                return 1
+
+        fn = L.EXCHANGE_FN(call)
+        L.check(self.lib.hc_set_enkf_shard(self.h, n_global, first, C.c_void_p(base), buf.numel(), fn, None))
+        self._shard_keep = (buf, fn, call)         # alive as long as the handle may call them
+        self.enkf_shard = (n_global, first)
+
+    def get_enkf_shard(self):
+        """(n_global, first_global) as the library holds them; (0, 0): off."""
+        n, f = np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int64)
+        L.check(self.lib.hc_get_enkf_shard(self.h, L.lptr(n), L.lptr(f)))
+        return int(n[0]), int(f[0])
 
     # -- hooks ----------------------------------------------------------------------
     def spinup(self, zwtd_cm, z0_cm, forcing_row=0, max_iterations=1500):

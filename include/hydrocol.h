@@ -560,6 +560,44 @@ int hc_get_enkf_window_y(hc_handle *h, double *y);
 int hc_get_enkf_window_eps(hc_handle *h, double *eps);
 int hc_get_enkf_window_gain(hc_handle *h, double *gain);
 
+/* One point's members on several handles (a single-point ensemble over several GPUs): the handle holds members
+ * [first_global, first_global + n_members) of a point with n_global members, and its analyses are those of the one handle
+ * that holds them all, to the bit.  Every sum over the members is formed as partials of tiles of 256 consecutive members
+ * in member order and reduced in an order fixed by the tile count alone; a shard that starts on a tile boundary forms
+ * exactly the partials the whole ensemble would have formed for its tiles, so the shards only have to gather them.
+ *   Before each of the analysis's reductions -- the prior sums, the prior products, the squared prior anomalies, the
+ *   analysis columns' sums and their squared anomalies (relaxation only), the posterior sums and products -- the handle
+ *   writes its tiles' partials at their place in the global layout [n_tiles_global][columns] of the pass inside
+ *   device_buf, drains its stream and calls fn(ctx, pass, n_words, first_word, count_words): `pass` points into device_buf
+ *   at the pass's layout of n_words doubles, of which [first_word, first_word + count_words) are this handle's.  On
+ *   return (0 = ok) every other handle's words must be in place and visible on the device: a gather (copy), never
+ *   arithmetic.  The reduction then runs over all n_tiles_global tiles on every handle alike, so sums, gains and every
+ *   diagnostics table (EnKF, sensors, window) are identical on all of them.  Every mean and variance divides by n_global
+ *   or n_global - 1.  The relaxation's spread is summed relative to the point's first member: the handle with
+ *   first_global = 0 contributes that member's analysis column (one more call of fn: n_words = D, its count_words = D,
+ *   everyone else's 0).  All handles of a point must analyse the same rows with the same settings, or the calls do not
+ *   pair up.  A non-zero return of fn fails hc_step_rows with HC_ERR_DEVICE (the states are then unusable).
+ *   The draws of the stochastic scheme are keyed by first_global + m; with hc_set_noise_philox its member_offset must
+ *   equal first_global (HC_ERR_ARG), so that the model noise is the whole ensemble's too.  The window's capture stays
+ *   per handle (only the handle's own members' y).  The test hooks return the handle's own members for y / eps and the
+ *   same gains on every handle; the count entry of the EnKF's table is n_global.
+ * hc_get_enkf_shard_words: what device_buf must hold for n_global members, in doubles: the global tile count times the
+ *   widest pass as the sensors and the window stand (the prior products [D + m'][m'] plus the squared anomalies [D] that
+ *   travel with them under relaxation, or the posterior's), and at least D.  Set the sensors and the window first: an
+ *   analysis that finds the buffer too small fails with HC_ERR_ARG.
+ * hc_set_enkf_shard: device_buf is caller-owned memory on the handle's device (the idiom of hc_export_moments), alive
+ *   while the shard is set.  Needs the EnKF on; HC_ERR_ARG for more than one point on the handle, first_global % 256 != 0,
+ *   n_members % 256 != 0 on a shard that is not the last (first_global + n_members < n_global), first_global + n_members >
+ *   n_global, n_words < hc_get_enkf_shard_words, a NULL buffer or callback.  n_global = 0 turns sharding off; so does
+ *   whatever turns the EnKF off.  With sharding off nothing changes: no launch, no synchronisation, the same kernels.
+ *   n_global = n_members with first_global = 0 and a callback that does nothing gives the unsharded bits.
+ * hc_get_enkf_shard: n_global (0: off) and first_global. */
+typedef int (*hc_enkf_exchange_fn)(void *ctx, void *device_buf, int64_t n_words, int64_t first_word, int64_t count_words);
+int hc_get_enkf_shard_words(hc_handle *h, int64_t n_global, int64_t *n_words);
+int hc_set_enkf_shard(hc_handle *h, int64_t n_global, int64_t first_global, void *device_buf, int64_t n_words,
+                      hc_enkf_exchange_fn fn, void *ctx);
+int hc_get_enkf_shard(hc_handle *h, int64_t *n_global, int64_t *first_global);
+
 /* The path's one collective inside the library, for a single process that drives several devices with
  * one handle each: every handle's moment table is replaced by the sum over all n handles (ncclAllReduce, ncclInt64,
  * ncclSum over RCCL / xGMI, in place on device memory, on the handles' own streams).  Integer sums: the result does not

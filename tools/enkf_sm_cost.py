@@ -21,7 +21,10 @@ initial profile shifted by its own offset, uniform over +-W cm.  Under `rocprofv
 scheme of every EnKF run (hc_set_enkf_method; the defaults do not call it).  --offsets: the well's record inside the
 window (hc_set_enkf_window) for the runs with the suffix "w" (48w, 48sw): each offset's row ends a launch and records
 y, so `launches` grows and the step kernel runs in shorter pieces -- `step_kernel_ms` against the stride-0 runs' is what
-the cuts cost the step kernel, `window_ms_per_analysis` what everything else costs.  Prints one JSON line.
+the cuts cost the step kernel, `window_ms_per_analysis` what everything else costs.  The suffix "g" (48g, 48sg) runs the
+analysis sharded with the handle holding every member and nothing to gather (hc_set_enkf_shard, identity exchange):
+`shard_ms_per_analysis` against the same run without "g" is what the global layout and the stream drains before each
+reduction cost.  Prints one JSON line.
 """
 import argparse
 import json
@@ -36,7 +39,7 @@ sys.path.insert(0, str(REPO))
 
 
 def run(cols, forcing, psi0, members, stride, sigma, loc, warmup_days, days, spread_cm=0.0, seed=2024, sensors=None,
-        method="stochastic", relaxation=0.0, offsets=()):
+        method="stochastic", relaxation=0.0, offsets=(), shard=False):
     from hydromodel_amd.stepper import EnsembleStepper, enkf_sm_summary, enkf_summary
     st = EnsembleStepper(cols, forcing, members)
     try:
@@ -54,6 +57,8 @@ def run(cols, forcing, psi0, members, stride, sigma, loc, warmup_days, days, spr
             st.set_enkf_method(method, relaxation)
         if stride and offsets:
             st.set_enkf_window(offsets)
+        if stride and shard:
+            st.set_enkf_shard(members, 0, None)
         row = 1
         if warmup_days:
             st.step_rows(row, 48 * warmup_days)
@@ -65,7 +70,7 @@ def run(cols, forcing, psi0, members, stride, sigma, loc, warmup_days, days, spr
         wall = time.perf_counter() - t0
         rec = {"stride": stride, "sensors": 0 if sensors is None else len(sensors["nodes"]), "wall_s": wall, "step_kernel_ms": out["kernel_ms"], "launches": out["launches"],
                "other_ms": 1e3 * wall - out["kernel_ms"], "column_days_per_s": members * days / wall,
-               "offsets": list(offsets) if stride else []}
+               "offsets": list(offsets) if stride else [], "shard": bool(stride and shard)}
         if stride:
             s = enkf_summary(st.enkf_table()[0], stride, sigma)
             timed = s["rows"] >= row
@@ -103,6 +108,9 @@ def main():
     ap.add_argument("--offsets", default="12,24,36")
     ap.add_argument("--json", default="")
     args = ap.parse_args()
+    if "g" in args.runs:
+        from hydromodel_amd import _lib
+        _lib.load(with_torch=True)      # the shard's buffer is a torch tensor: torch before the library
     from hydromodel_amd.digest import ColumnTables, ForcingDigest
     from hydromodel_amd.ensemble import pressure_head
     from hydromodel_amd.synthetic import default_parameters, synthetic_forcing_frame, synthetic_well
@@ -123,9 +131,9 @@ def main():
     rec = soil_moisture_record(cols.z, depths, np.zeros((forcing.dim_t, len(depths))), args.sm_sigma)
     rec["values"][:] = theta0[rec["nodes"]][None, :]
     offsets = tuple(int(o) for o in args.offsets.split(",") if o)
-    recs = [run(cols, forcing, psi0, args.members, int(s.rstrip("sw")), args.sigma, args.localisation, args.warmup,
+    recs = [run(cols, forcing, psi0, args.members, int(s.rstrip("swg")), args.sigma, args.localisation, args.warmup,
                 args.days, args.spread_cm, sensors=rec if "s" in s else None, method=args.method,
-                relaxation=args.relaxation, offsets=offsets if "w" in s else ())
+                relaxation=args.relaxation, offsets=offsets if "w" in s else (), shard="g" in s)
             for s in args.runs.split(",")]
     base = [r for r in recs if r["stride"] == 0]
     if base:
@@ -134,7 +142,7 @@ def main():
         for r in recs:
             r["kept"] = r["column_days_per_s"] / rate
             if r["stride"] and r.get("analyses"):
-                key = "window_ms_per_analysis" if r["offsets"] else "sm_ms_per_analysis" if r["sensors"] else "enkf_ms_per_analysis"
+                key = "shard_ms_per_analysis" if r["shard"] else "window_ms_per_analysis" if r["offsets"] else "sm_ms_per_analysis" if r["sensors"] else "enkf_ms_per_analysis"
                 r[key] = (r["other_ms"] - other) / r["analyses"]
     line = json.dumps({"members": args.members, "depth": args.depth, "days": args.days, "sigma_cm": args.sigma,
                        "localisation_cm": args.localisation, "spread_cm": args.spread_cm, "sensors_cm": depths,
