@@ -966,20 +966,23 @@ __global__ void enkf_window_gather_kernel(const double *win_y, long long n_membe
     for (int k = s.ms; k < s.m; k++) Y[(size_t)m * width + 1 + k] = win_y[(size_t)s.sensor[k] * n_members + m];
 }
 
-// Column sums of X = (psi_0 .. psi_{Dc-1}, Y_0 .. Y_{W-1}) (Dc = 0: Y alone), C = Dc + W columns, tile t of point p:
-//   sums == NULL: partial[p][t][j] = sum over the tile in member order of X_j;
-//   otherwise:    partial[p][t][j][i] = sum of (X_j - xbar_j)(Y_i - ybar_i), the means = sums[p][.] / N_p; and with
-//                 SQUARE (the relaxation to prior spread): square[p][t][j] = sum of (psi_j - psibar_j)^2, j < Dc.
-//                 A template parameter: the plain kernel keeps its instructions.
-// Thread j owns column j: every member's psi row is one coalesced read of the block.
+// Column sums of X = (psi_0 .. psi_{Dc-1}, Y_0 .. Y_{W-1}) (Dc = 0: Y alone), C = Dc + W columns.  Block (t, p) takes
+// tile t of point p's mpp members on this handle; they are tiles tile0, tile0 + 1, ... of a point with np members and
+// n_tiles tiles (the whole point: np = mpp, tile0 = 0; hc_set_enkf_shard: a part of it, and p = 0), to = tile0 + t:
+//   sums == NULL: partial[p][to][j] = sum over the tile in member order of X_j;
+//   otherwise:    partial[p][to][j][i] = sum of (X_j - xbar_j)(Y_i - ybar_i), the means = sums[p][.] / np; and with
+//                 SQUARE (the relaxation to prior spread): square[p][to][j] = sum of (psi_j - psibar_j)^2, j < Dc.
+// Thread j owns column j: every member's psi row is one coalesced read of the block, and the tile offset is uniform
+// over the block, so its stores are coalesced wherever the tile lands.
 template <bool SQUARE>
 __global__ __launch_bounds__(HC_MAX_DEPTH_NODES + WAVE) void enkf_partial_kernel(const double *psi, const double *Y, int W,
                                                                                  const double *sums, long long mpp, int Dc,
                                                                                  long long n_tiles, double *partial,
-                                                                                 double *square)
+                                                                                 double *square, long long np,
+                                                                                 long long tile0)
 {
 #pragma clang fp contract(off)
-    const long long p = blockIdx.y, t = blockIdx.x;
+    const long long p = blockIdx.y, t = blockIdx.x, to = tile0 + t;
     const int j = threadIdx.x, C = Dc + W;
     if (j >= C) return;
     const long long m0 = p * mpp + t * ENKF_TILE;
@@ -990,15 +993,15 @@ __global__ __launch_bounds__(HC_MAX_DEPTH_NODES + WAVE) void enkf_partial_kernel
         double s = 0.0;
 #pragma unroll 8
         for (long long m = m0; m < m1; m++) s += x[(size_t)m * xs];
-        partial[((size_t)p * n_tiles + t) * C + j] = s;
+        partial[((size_t)p * n_tiles + to) * C + j] = s;
         return;
     }
     const double *S = sums + (size_t)p * C;
-    const double xb = S[j] / (double)mpp;
+    const double xb = S[j] / (double)np;
     double yb[ENKF_OBS + 1], acc[ENKF_OBS + 1];
 #pragma unroll
     for (int i = 0; i < ENKF_OBS + 1; i++) {
-        yb[i] = i < W ? S[Dc + i] / (double)mpp : 0.0;
+        yb[i] = i < W ? S[Dc + i] / (double)np : 0.0;
         acc[i] = 0.0;
     }
     double sq = 0.0;
@@ -1010,55 +1013,8 @@ __global__ __launch_bounds__(HC_MAX_DEPTH_NODES + WAVE) void enkf_partial_kernel
             if (i < W) acc[i] += a * (ym[i] - yb[i]);
         if (SQUARE) sq += a * a;
     }
-    if (SQUARE && j < Dc) square[((size_t)p * n_tiles + t) * Dc + j] = sq;
-    double *out = partial + (((size_t)p * n_tiles + t) * C + j) * W;
-#pragma unroll
-    for (int i = 0; i < ENKF_OBS + 1; i++)
-        if (i < W) out[i] = acc[i];
-}
-
-// enkf_partial_kernel for a handle that holds a part of one point's members (hc_set_enkf_shard): its mpp members are the
-// tiles tile0, tile0 + 1, ... of a point with np members and n_tiles tiles -- the means divide by np, and tile t's
-// partials go to tile tile0 + t of the point's layout [n_tiles][...].  The offset is uniform over the block: thread j's
-// stores stay as coalesced as they were.
-template <bool SQUARE>
-__global__ __launch_bounds__(HC_MAX_DEPTH_NODES + WAVE) void enkf_partial_shard_kernel(
-    const double *psi, const double *Y, int W, const double *sums, long long mpp, int Dc, long long n_tiles,
-    double *partial, double *square, long long np, long long tile0)
-{
-#pragma clang fp contract(off)
-    const long long t = blockIdx.x, to = tile0 + t;
-    const int j = threadIdx.x, C = Dc + W;
-    if (j >= C) return;
-    const long long m0 = t * ENKF_TILE;
-    const long long m1 = (t + 1) * ENKF_TILE < mpp ? (t + 1) * ENKF_TILE : mpp;
-    const double *x = j < Dc ? psi + j : Y + (j - Dc);
-    const long long xs = j < Dc ? Dc : W;
-    if (!sums) {
-        double s = 0.0;
-#pragma unroll 8
-        for (long long m = m0; m < m1; m++) s += x[(size_t)m * xs];
-        partial[(size_t)to * C + j] = s;
-        return;
-    }
-    const double xb = sums[j] / (double)np;
-    double yb[ENKF_OBS + 1], acc[ENKF_OBS + 1];
-#pragma unroll
-    for (int i = 0; i < ENKF_OBS + 1; i++) {
-        yb[i] = i < W ? sums[Dc + i] / (double)np : 0.0;
-        acc[i] = 0.0;
-    }
-    double sq = 0.0;
-    for (long long m = m0; m < m1; m++) {
-        const double a = x[(size_t)m * xs] - xb;
-        const double *ym = Y + (size_t)m * W;
-#pragma unroll
-        for (int i = 0; i < ENKF_OBS + 1; i++)
-            if (i < W) acc[i] += a * (ym[i] - yb[i]);
-        if (SQUARE) sq += a * a;
-    }
-    if (SQUARE && j < Dc) square[(size_t)to * Dc + j] = sq;
-    double *out = partial + ((size_t)to * C + j) * W;
+    if (SQUARE && j < Dc) square[((size_t)p * n_tiles + to) * Dc + j] = sq;
+    double *out = partial + (((size_t)p * n_tiles + to) * C + j) * W;
 #pragma unroll
     for (int i = 0; i < ENKF_OBS + 1; i++)
         if (i < W) out[i] = acc[i];
@@ -1260,117 +1216,11 @@ __global__ void enkf_window_draw_kernel(long long n_members, long long mpp, unsi
     for (int k = 0; k < mw; k++) eps_w[(size_t)m * mw + k] = enkf_normal_at(0xFFFFFFFEu, seed, gid, s.wrow[s.ms + k]);
 }
 
-// One wave per member: the innovations o_k - Y_k from the draws of enkf_draw_kernel, psi_dk + sum_i K_di (o_ki - Y_ki)
-// (i in order) on every node, stored only when every entry is finite (else the forecast stays and the member is counted
-// as rejected); then the find_wtd index and the posterior y of the column it kept: Ypost[m] = (y, ..., rejected)
-// (enkf_theta_kernel fills in the posterior theta).
-__global__ __launch_bounds__(256) void enkf_update_kernel(double *psi, const double *Y, const double *gain,
-                                                          const ColumnDev *P, long long n_members, long long mpp, int D,
-                                                          double dz, double z_obs, double sigma, const EnkfRow s,
-                                                          const double *eps, const double *eps_s,
-                                                          const double *eps_w, double *Ypost)
-{
-#pragma clang fp contract(off)
-    const int lane = threadIdx.x % WAVE;
-    const int W = s.m + 1, V = s.ms + 2, mw = s.m - s.ms;
-    // lane 1 + k holds column k beyond the well's: present sensor k's record index, observation and sigma; a lagged
-    // row's (k >= ms) place among the lagged columns instead of the index
-    int my_sensor = 0;
-    double my_obs = 0.0, my_sigma = 0.0;
-#pragma unroll
-    for (int k = 0; k < ENKF_SENSORS; k++)
-        if (k < s.m && lane == 1 + k) my_sensor = k < s.ms ? s.sensor[k] : k - s.ms, my_obs = s.obs[k], my_sigma = s.sigma[k];
-    const long long waves = (long long)gridDim.x * (blockDim.x / WAVE);
-    for (long long m = (long long)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE; m < n_members; m += waves) {
-        const long long p = m / mpp;
-        // a: the column; inc: the well's gain, then the increments sum_i K_di (o_i - Y_i) summed in i order, one gain
-        // row at a time with the loads of all its slots in flight; then a = psi_d + inc
-        const double *K = gain + (size_t)p * W * D;
-        double *col = psi + (size_t)m * D;
-        double a[ENKF_SLOTS], inc[ENKF_SLOTS];
-#pragma unroll
-        for (int c = 0; c < ENKF_SLOTS; c++) {
-            const int d = c * WAVE + lane;
-            a[c] = 0.0;
-            inc[c] = 0.0;
-            if (d < D) {
-                a[c] = col[d];
-                inc[c] = K[d];
-            }
-        }
-        // lane i holds innovation i: the well's on lane 0 (dl0, on every lane too), present sensor k's on lane 1 + k
-        const double *Ym = Y + (size_t)m * W;
-        const double dl0 = (z_obs + sigma * eps[m]) - Ym[0];
-        const double my_dl = lane == 0      ? dl0
-                             : lane <= s.ms ? (my_obs + my_sigma * eps_s[(size_t)m * s.n + my_sensor]) - Ym[lane]
-                             : lane < W     ? (my_obs + my_sigma * eps_w[(size_t)m * mw + my_sensor]) - Ym[lane]
-                                            : 0.0;
-#pragma unroll
-        for (int c = 0; c < ENKF_SLOTS; c++) inc[c] = inc[c] * dl0;
-#pragma unroll 1
-        for (int i = 1; i < W; i++) {
-            const double di = lane_value(my_dl, i);
-            double k[ENKF_SLOTS];
-#pragma unroll
-            for (int c = 0; c < ENKF_SLOTS; c++) {
-                const int d = c * WAVE + lane;
-                k[c] = d < D ? K[(size_t)i * D + d] : 0.0;
-            }
-#pragma unroll
-            for (int c = 0; c < ENKF_SLOTS; c++) inc[c] = inc[c] + k[c] * di;
-        }
-        bool ok = true;
-#pragma unroll
-        for (int c = 0; c < ENKF_SLOTS; c++) {
-            const int d = c * WAVE + lane;
-            if (d < D) a[c] = a[c] + inc[c];
-            ok = ok && isfinite(a[c]);
-        }
-        // a becomes the column the member keeps: the analysis, or the forecast read back (a branch on the wave-uniform
-        // keep around each loop: one inside them costs 16 VGPRs of copies and a wave of occupancy)
-        const bool keep = __all(ok);
-        if (keep) {
-#pragma unroll
-            for (int c = 0; c < ENKF_SLOTS; c++) {
-                const int d = c * WAVE + lane;
-                if (d < D) col[d] = a[c];
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < ENKF_SLOTS; c++) {
-                const int d = c * WAVE + lane;
-                a[c] = d < D ? col[d] : 0.0;
-            }
-        }
-        // find_wtd of the kept column (the step kernel's rule): below the deepest node with psi < psi_sat, clamped
-        const double psat = P[p].psi_sat;
-        int deepest = -1;
-#pragma unroll
-        for (int c = 0; c < ENKF_SLOTS; c++) {
-            const int d = c * WAVE + lane;
-            const unsigned long long u = __ballot(d < D && !(a[c] >= psat));
-            if (u) deepest = c * WAVE + 63 - __clzll((long long)u);
-        }
-        const int b = deepest < 0 ? 0 : (deepest + 1 < D - 1 ? deepest + 1 : D - 1);
-        const int bl = b >= 1 ? b - 1 : 0;
-        double hi = 0.0, lo = 0.0;
-#pragma unroll
-        for (int c = 0; c < ENKF_SLOTS; c++) {
-            const double x = __shfl(a[c], b % WAVE), xl = __shfl(a[c], bl % WAVE);
-            if (c == b / WAVE) hi = x;
-            if (c == bl / WAVE) lo = xl;
-        }
-        double *out = Ypost + (size_t)m * V;
-        if (lane == 0) {
-            out[0] = enkf_y_of(b, lo, hi, psat, dz);
-            out[V - 1] = keep ? 0.0 : 1.0;
-        }
-    }
-}
-
-// ---- the square-root analysis and the relaxation to prior spread (hc_set_enkf_method)
-// What the two kernels below share.  A wave holds a member's column in a (node c * WAVE + lane in a[c], 0 past D).
+// ---- one wave per member: the update of either scheme and the relaxation to prior spread
+// A wave holds a member's column in a (node c * WAVE + lane in a[c], 0 past D).
 // enkf_keep_column: `next` is stored and becomes a when every entry of it is finite (the wave's vote); else a stays.
+// (The branch on the wave-uniform keep goes around the slot loop: one inside it costs 16 VGPRs of copies and a wave of
+// occupancy.)
 __device__ __forceinline__ bool enkf_keep_column(double (&a)[ENKF_SLOTS], const double (&next)[ENKF_SLOTS], double *col,
                                                  int lane, int D)
 {
@@ -1412,10 +1262,93 @@ __device__ __forceinline__ double enkf_column_y(const double (&a)[ENKF_SLOTS], i
     return enkf_y_of(b, lo, hi, psat, dz);
 }
 
-// The square-root update (Whitaker & Hamill 2002), one wave per member like enkf_update_kernel: psi_dk + dbar_d +
-// sum_i Kr_di (Ybar_i - Y_ki), i in order (Ybar from the prior sums s1 [P][D + m']), one gain row at a time with the
-// loads of all its slots in flight; the same vote, find_wtd and Ypost[m] = (y, ..., rejected).  Nothing is drawn.
-// want_y = 0: the relaxation follows and writes y.
+// The update of both schemes for the wave's member: psi_d + inc_d on every node of its column col, where inc = start +
+// sum_{i >= 1} K_id dl_i summed in i order, one row of the point's gain K [W][D] at a time with the loads of all its
+// slots in flight; lane i holds dl_i in my_dl, and start is K_0d dl_0, or with SHIFT shift_d + K_0d dl_0.
+// Invariant of the padding: a slot past D holds 0.0 in a and in the candidate column, so the vote and find_wtd are
+// decided by the nodes below D alone.  psi_d + inc_d is therefore formed below D only; past D inc is a sum of 0 * dl_i,
+// which is NaN when an innovation is not finite.  Such an innovation also makes every node below D non-finite (K_id dl_i
+// is then inf or NaN for every d), so the member is rejected whether or not the padding is looked at.  The column is
+// stored only when every entry is finite (else the forecast stays and the member is counted as rejected); then the
+// find_wtd index and the y of the column it kept: out = Ypost[m] = (y, ..., rejected), V entries (enkf_theta_kernel
+// fills in the posterior theta).  want_y = 0: the relaxation follows and writes y.
+template <bool SHIFT>
+__device__ __forceinline__ void enkf_update_column(double *col, const double *K, const double *shift, int W, double my_dl,
+                                                   int lane, int D, double psat, double dz, int want_y, double *out, int V)
+{
+#pragma clang fp contract(off)
+    double a[ENKF_SLOTS], inc[ENKF_SLOTS], k0[ENKF_SLOTS];
+#pragma unroll
+    for (int c = 0; c < ENKF_SLOTS; c++) {
+        const int d = c * WAVE + lane;
+        a[c] = 0.0;
+        inc[c] = 0.0;
+        k0[c] = 0.0;
+        if (d < D) {
+            a[c] = col[d];
+            if (SHIFT) inc[c] = shift[d];
+            k0[c] = K[d];
+        }
+    }
+    const double dl0 = lane_value(my_dl, 0);
+#pragma unroll
+    for (int c = 0; c < ENKF_SLOTS; c++) inc[c] = SHIFT ? inc[c] + k0[c] * dl0 : k0[c] * dl0;
+#pragma unroll 1
+    for (int i = 1; i < W; i++) {
+        const double di = lane_value(my_dl, i);
+        double k[ENKF_SLOTS];
+#pragma unroll
+        for (int c = 0; c < ENKF_SLOTS; c++) {
+            const int d = c * WAVE + lane;
+            k[c] = d < D ? K[(size_t)i * D + d] : 0.0;
+        }
+#pragma unroll
+        for (int c = 0; c < ENKF_SLOTS; c++) inc[c] = inc[c] + k[c] * di;
+    }
+#pragma unroll
+    for (int c = 0; c < ENKF_SLOTS; c++) inc[c] = c * WAVE + lane < D ? a[c] + inc[c] : 0.0;
+    const bool keep = enkf_keep_column(a, inc, col, lane, D);
+    if (want_y) {
+        const double y = enkf_column_y(a, lane, D, psat, dz);
+        if (lane == 0) out[0] = y;
+    }
+    if (lane == 0) out[V - 1] = keep ? 0.0 : 1.0;
+}
+
+// The stochastic update, one wave per member: lane i's innovation is o_i + sigma_i eps_ki - Y_ki from the draws of
+// enkf_draw_kernel (and enkf_window_draw_kernel): the well's on lane 0, present sensor k's and then the lagged rows' on
+// lane 1 + k.
+__global__ __launch_bounds__(256) void enkf_update_kernel(double *psi, const double *Y, const double *gain,
+                                                          const ColumnDev *P, long long n_members, long long mpp, int D,
+                                                          double dz, double z_obs, double sigma, const EnkfRow s,
+                                                          const double *eps, const double *eps_s,
+                                                          const double *eps_w, int want_y, double *Ypost)
+{
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x % WAVE;
+    const int W = s.m + 1, V = s.ms + 2, mw = s.m - s.ms;
+    // lane 1 + k holds column k beyond the well's: present sensor k's record index, observation and sigma; a lagged
+    // row's (k >= ms) place among the lagged columns instead of the index
+    int my_sensor = 0;
+    double my_obs = 0.0, my_sigma = 0.0;
+#pragma unroll
+    for (int k = 0; k < ENKF_SENSORS; k++)
+        if (k < s.m && lane == 1 + k) my_sensor = k < s.ms ? s.sensor[k] : k - s.ms, my_obs = s.obs[k], my_sigma = s.sigma[k];
+    const long long waves = (long long)gridDim.x * (blockDim.x / WAVE);
+    for (long long m = (long long)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE; m < n_members; m += waves) {
+        const long long p = m / mpp;
+        const double *Ym = Y + (size_t)m * W;
+        const double my_dl = lane == 0      ? (z_obs + sigma * eps[m]) - Ym[0]
+                             : lane <= s.ms ? (my_obs + my_sigma * eps_s[(size_t)m * s.n + my_sensor]) - Ym[lane]
+                             : lane < W     ? (my_obs + my_sigma * eps_w[(size_t)m * mw + my_sensor]) - Ym[lane]
+                                            : 0.0;
+        enkf_update_column<false>(psi + (size_t)m * D, gain + (size_t)p * W * D, nullptr, W, my_dl, lane, D, P[p].psi_sat,
+                                  dz, want_y, Ypost + (size_t)m * V, V);
+    }
+}
+
+// The square-root update (Whitaker & Hamill 2002), one wave per member: the reduced gain, the mean's increment dbar as
+// the shift, and lane i's innovation Ybar_i - Y_ki (Ybar from the prior sums s1 [P][D + m']).  Nothing is drawn.
 __global__ __launch_bounds__(256) void enkf_sqrt_update_kernel(double *psi, const double *Y, const double *rgain,
                                                                const double *dbar, const double *s1, const ColumnDev *P,
                                                                long long n_members, long long mpp, int D, double dz,
@@ -1426,59 +1359,24 @@ __global__ __launch_bounds__(256) void enkf_sqrt_update_kernel(double *psi, cons
     const long long waves = (long long)gridDim.x * (blockDim.x / WAVE);
     for (long long m = (long long)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE; m < n_members; m += waves) {
         const long long p = m / mpp;
-        const double *K = rgain + (size_t)p * W * D, *db = dbar + (size_t)p * D;
-        double *col = psi + (size_t)m * D;
-        double a[ENKF_SLOTS], inc[ENKF_SLOTS], k0[ENKF_SLOTS];
-#pragma unroll
-        for (int c = 0; c < ENKF_SLOTS; c++) {
-            const int d = c * WAVE + lane;
-            a[c] = 0.0;
-            inc[c] = 0.0;
-            k0[c] = 0.0;
-            if (d < D) {
-                a[c] = col[d];
-                inc[c] = db[d];
-                k0[c] = K[d];
-            }
-        }
-        // lane i holds Ybar_i - Y_ki
         const double my_dl = lane < W ? s1[(size_t)p * (D + W) + D + lane] / (double)mpp - Y[(size_t)m * W + lane] : 0.0;
-        const double d0 = lane_value(my_dl, 0);
-#pragma unroll
-        for (int c = 0; c < ENKF_SLOTS; c++) inc[c] = inc[c] + k0[c] * d0;
-#pragma unroll 1
-        for (int i = 1; i < W; i++) {
-            const double di = lane_value(my_dl, i);
-            double k[ENKF_SLOTS];
-#pragma unroll
-            for (int c = 0; c < ENKF_SLOTS; c++) {
-                const int d = c * WAVE + lane;
-                k[c] = d < D ? K[(size_t)i * D + d] : 0.0;
-            }
-#pragma unroll
-            for (int c = 0; c < ENKF_SLOTS; c++) inc[c] = inc[c] + k[c] * di;
-        }
-#pragma unroll
-        for (int c = 0; c < ENKF_SLOTS; c++) inc[c] = a[c] + inc[c];
-        const bool keep = enkf_keep_column(a, inc, col, lane, D);
-        double *out = Ypost + (size_t)m * V;
-        if (want_y) {
-            const double y = enkf_column_y(a, lane, D, P[p].psi_sat, dz);
-            if (lane == 0) out[0] = y;
-        }
-        if (lane == 0) out[V - 1] = keep ? 0.0 : 1.0;
+        enkf_update_column<true>(psi + (size_t)m * D, rgain + (size_t)p * W * D, dbar + (size_t)p * D, W, my_dl, lane, D,
+                                 P[p].psi_sat, dz, want_y, Ypost + (size_t)m * V, V);
     }
 }
 
-// The spread of the analysis columns, tile t of point p, thread d = node d, by the tile rule of enkf_partial_kernel.
-// The columns are taken relative to the point's first member, x = psi_d - psi_d[member 0]:
-//   sums == NULL: partial[p][t][d] = sum over the tile in member order of x;
-//   otherwise:    partial[p][t][d] = sum of (x - xbar)^2, xbar = sums[p][d] / N_p.
+// The spread of the analysis columns, thread d = node d, by the tile rule of enkf_partial_kernel (its mpp, np, tile0
+// and to = tile0 + t).  The columns are taken relative to the point's first member, x = psi_d - psi_d[member 0]:
+//   sums == NULL: partial[p][to][d] = sum over the tile in member order of x;
+//   otherwise:    partial[p][to][d] = sum of (x - xbar)^2, xbar = sums[p][d] / np.
 // So a node on which every member agrees (a saturated tail) has x = 0, the mean psi_d[member 0] and sigma_a = 0 exactly,
-// where the plain sum of N equal values rounds.
+// where the plain sum of N equal values rounds.  Point p's first member's column is first + p * first_stride: psi and
+// mpp * D, or the copy another handle contributed and 0 (hc_set_enkf_shard).
 __global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void enkf_spread_kernel(const double *psi, const double *sums,
                                                                          long long mpp, int D, long long n_tiles,
-                                                                         double *partial)
+                                                                         double *partial, const double *first,
+                                                                         long long first_stride, long long np,
+                                                                         long long tile0)
 {
 #pragma clang fp contract(off)
     const long long p = blockIdx.y, t = blockIdx.x;
@@ -1487,50 +1385,20 @@ __global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void enkf_spread_kernel(const d
     const long long m0 = p * mpp + t * ENKF_TILE;
     const long long m1 = p * mpp + ((t + 1) * ENKF_TILE < mpp ? (t + 1) * ENKF_TILE : mpp);
     const double *x = psi + d;
-    const double x0 = x[(size_t)(p * mpp) * D];
+    const double x0 = first[(size_t)(p * first_stride) + d];
     double s = 0.0;
     if (!sums) {
 #pragma unroll 8
         for (long long m = m0; m < m1; m++) s += x[(size_t)m * D] - x0;
     } else {
-        const double xb = sums[(size_t)p * D + d] / (double)mpp;
+        const double xb = sums[(size_t)p * D + d] / (double)np;
 #pragma unroll 8
         for (long long m = m0; m < m1; m++) {
             const double a = (x[(size_t)m * D] - x0) - xb;
             s += a * a;
         }
     }
-    partial[((size_t)p * n_tiles + t) * D + d] = s;
-}
-
-// enkf_spread_kernel for a handle that holds a part of one point's members (hc_set_enkf_shard; the tiles, np and tile0
-// of enkf_partial_shard_kernel): the point's first member's column is `first` [D], which another handle may hold.
-__global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void enkf_spread_shard_kernel(const double *psi, const double *sums,
-                                                                               long long mpp, int D, long long n_tiles,
-                                                                               double *partial, const double *first,
-                                                                               long long np, long long tile0)
-{
-#pragma clang fp contract(off)
-    const long long t = blockIdx.x;
-    const int d = threadIdx.x;
-    if (d >= D) return;
-    const long long m0 = t * ENKF_TILE;
-    const long long m1 = (t + 1) * ENKF_TILE < mpp ? (t + 1) * ENKF_TILE : mpp;
-    const double *x = psi + d;
-    const double x0 = first[d];
-    double s = 0.0;
-    if (!sums) {
-#pragma unroll 8
-        for (long long m = m0; m < m1; m++) s += x[(size_t)m * D] - x0;
-    } else {
-        const double xb = sums[d] / (double)np;
-#pragma unroll 8
-        for (long long m = m0; m < m1; m++) {
-            const double a = (x[(size_t)m * D] - x0) - xb;
-            s += a * a;
-        }
-    }
-    partial[(size_t)(tile0 + t) * D + d] = s;
+    partial[((size_t)p * n_tiles + tile0 + t) * D + d] = s;
 }
 
 // the point's first member's column, by the handle that holds it, into the exchange buffer (hc_set_enkf_shard)
@@ -2985,10 +2853,12 @@ int enkf_exchange(hc_handle *h, double *pass, int64_t n_words, int64_t first_wor
 // record's largest m', 1 + sm_n.  hc_set_enkf_method: the square-root scheme swaps the draws and the update for its own
 // (the gain kernel adds the reduced gain and the mean's increment); a relaxation alpha > 0 takes the squared psi
 // anomalies along in the second prior pass, sums the analysis columns and their squared anomalies (two more passes over
-// psi), relaxes (one read + write) and only then forms the posterior.  hc_set_enkf_shard: the handle's members are a part
-// of the point's; every partial pass writes the handle's tiles into the pass's global layout in the caller's buffer and
-// every reduction gathers the other handles' first (one callback each; one more for the point's first member's column
-// under relaxation), so the sums -- and everything after them -- are those of the one handle that holds every member.
+// psi), relaxes (one read + write, which also writes y: the update before it skips that) and only then forms the
+// posterior.  The partial and spread kernels take the point's size np and the handle's tile offset tile0: (mpp, 0)
+// unless hc_set_enkf_shard made the handle's members a part of the point's; then every partial pass writes the handle's
+// tiles into the pass's global layout in the caller's buffer and every reduction gathers the other handles' first (one
+// callback each; one more for the point's first member's column under relaxation), so the sums -- and everything after
+// them -- are those of the one handle that holds every member.
 int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
 {
     const int64_t N = h->n_members, D = h->p.dim_d, P = h->n_points, mpp = N / P;
@@ -3029,21 +2899,15 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
     double *const part_sq = shard ? h->shard_buf : h->enkf_part_sq.p;
     const long long draw_offset = (long long)(shard ? h->shard_first : h->member_offset);
     const dim3 tiles((unsigned)my_tiles, (unsigned)P);
-    // the tile partials of one pass (enkf_partial_kernel's arguments; its sharded form at the handle's tile offset)
+    // the tile partials of one pass (enkf_partial_kernel's arguments), at the handle's tile offset
     auto partials = [&](bool square, const double *psi, const double *Y, int width, const double *sums, int Dc,
                         dim3 threads, double *out, double *out_sq) {
-        if (shard && square)
-            hipLaunchKernelGGL(enkf_partial_shard_kernel<true>, tiles, threads, 0, h->stream, psi, Y, width, sums, ll_mpp,
-                               Dc, ll_tiles, out, out_sq, ll_np, ll_tile0);
-        else if (shard)
-            hipLaunchKernelGGL(enkf_partial_shard_kernel<false>, tiles, threads, 0, h->stream, psi, Y, width, sums, ll_mpp,
-                               Dc, ll_tiles, out, out_sq, ll_np, ll_tile0);
-        else if (square)
+        if (square)
             hipLaunchKernelGGL(enkf_partial_kernel<true>, tiles, threads, 0, h->stream, psi, Y, width, sums, ll_mpp, Dc,
-                               ll_tiles, out, out_sq);
+                               ll_tiles, out, out_sq, ll_np, ll_tile0);
         else
             hipLaunchKernelGGL(enkf_partial_kernel<false>, tiles, threads, 0, h->stream, psi, Y, width, sums, ll_mpp, Dc,
-                               ll_tiles, out, out_sq);
+                               ll_tiles, out, out_sq, ll_np, ll_tile0);
         return hipGetLastError();
     };
     // sums[p][c] of a pass of `cols` columns from its tile partials; sharded: the stream drained and the other handles'
@@ -3105,19 +2969,17 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
         }
         hipLaunchKernelGGL(enkf_update_kernel, dim3(blocks), dim3(256), 0, h->stream, h->psi.p, h->enkf_Y.p,
                            h->enkf_gain.p, h->Pdev.p, (long long)N, ll_mpp, (int)D, dz, z_obs, h->enkf_sigma, s,
-                           h->enkf_eps.p, h->enkf_eps_s.p, h->enkf_eps_w.p, h->enkf_Ypost.p);
+                           h->enkf_eps.p, h->enkf_eps_s.p, h->enkf_eps_w.p, relax ? 0 : 1, h->enkf_Ypost.p);
         HIP_TRY(hipGetLastError());
     }
     if (relax) {
         // the analysis columns' sums, then their squared anomalies; the factors; the relaxed columns and their y
         const dim3 cols_psi((unsigned)((D + WAVE - 1) / WAVE * WAVE));
+        // (each point's first member's column: its own in psi, or the copy the exchange below brings)
         auto spread = [&](const double *sums) {
-            if (shard)
-                hipLaunchKernelGGL(enkf_spread_shard_kernel, tiles, cols_psi, 0, h->stream, h->psi.p, sums, ll_mpp, (int)D,
-                                   ll_tiles, part_sq, h->enkf_first.p, ll_np, ll_tile0);
-            else
-                hipLaunchKernelGGL(enkf_spread_kernel, tiles, cols_psi, 0, h->stream, h->psi.p, sums, ll_mpp, (int)D,
-                                   ll_tiles, part_sq);
+            hipLaunchKernelGGL(enkf_spread_kernel, tiles, cols_psi, 0, h->stream, h->psi.p, sums, ll_mpp, (int)D, ll_tiles,
+                               part_sq, shard ? h->enkf_first.p : h->psi.p, shard ? 0LL : ll_mpp * (long long)D, ll_np,
+                               ll_tile0);
             return hipGetLastError();
         };
         if (shard) {
@@ -3766,12 +3628,12 @@ int hc_get_enkf_sm_y(hc_handle *h, double *y)
     return enkf_hook(h, h->enkf_Y.p, y, (size_t)h->n_members, (size_t)h->sm_width, (size_t)h->enkf_width, "hc_get_enkf_sm_y");
 }
 
-// the gain is [P][m'][D] on the device, [P][D][.] at the C-ABI: its first `cols` columns
-static int gain_hook(hc_handle *h, double *gain, size_t cols, const char *who)
+// a gain (`dev`: the gain or the reduced gain) is [P][m'][D] on the device, [P][D][.] at the C-ABI: its first `cols` columns
+static int gain_hook(hc_handle *h, const double *dev, double *gain, size_t cols, const char *who)
 {
     const size_t P = (size_t)h->n_points, D = (size_t)h->p.dim_d, W = (size_t)h->enkf_width;
     std::vector<double> k(P * W * D);
-    if (int rc = enkf_hook(h, h->enkf_gain.p, k.data(), 1, k.size(), k.size(), who)) return rc;
+    if (int rc = enkf_hook(h, dev, k.data(), 1, k.size(), k.size(), who)) return rc;
     for (size_t p = 0; p < P; p++)
         for (size_t i = 0; i < cols; i++)
             for (size_t d = 0; d < D; d++) gain[(p * D + d) * cols + i] = k[(p * W + i) * D + d];
@@ -3781,7 +3643,7 @@ static int gain_hook(hc_handle *h, double *gain, size_t cols, const char *who)
 int hc_get_enkf_sm_gain(hc_handle *h, double *gain)
 {
     if (int rc = sm_check(h, gain, "hc_get_enkf_sm_gain")) return rc;
-    return gain_hook(h, gain, (size_t)h->sm_width, "hc_get_enkf_sm_gain");
+    return gain_hook(h, h->enkf_gain.p, gain, (size_t)h->sm_width, "hc_get_enkf_sm_gain");
 }
 
 int hc_get_enkf_sm_eps(hc_handle *h, double *eps)
@@ -3913,7 +3775,7 @@ int hc_get_enkf_window_gain(hc_handle *h, double *gain)
 {
     if (!h || !gain) return fail(HC_ERR_ARG, "hc_get_enkf_window_gain: bad argument");
     if (h->enkf_stride <= 0 || !h->enkf_done) return fail(HC_ERR_ARG, "hc_get_enkf_window_gain: no analysis since hc_set_enkf");
-    return gain_hook(h, gain, (size_t)h->enkf_width, "hc_get_enkf_window_gain");
+    return gain_hook(h, h->enkf_gain.p, gain, (size_t)h->enkf_width, "hc_get_enkf_window_gain");
 }
 
 int hc_get_enkf_shard_words(hc_handle *h, int64_t n_global, int64_t *n_words)
@@ -3999,13 +3861,7 @@ int hc_get_enkf_sqrt_gain(hc_handle *h, double *gain)
     if (!h || !gain) return fail(HC_ERR_ARG, "hc_get_enkf_sqrt_gain: bad argument");
     if (h->enkf_stride <= 0 || !h->enkf_done || h->enkf_last_method != 1)
         return fail(HC_ERR_ARG, "hc_get_enkf_sqrt_gain: no square-root analysis since hc_set_enkf");
-    const size_t P = (size_t)h->n_points, D = (size_t)h->p.dim_d, W = (size_t)h->enkf_width;
-    std::vector<double> k(P * W * D);
-    if (int rc = enkf_hook(h, h->enkf_rgain.p, k.data(), 1, k.size(), k.size(), "hc_get_enkf_sqrt_gain")) return rc;
-    for (size_t p = 0; p < P; p++)
-        for (size_t i = 0; i < W; i++)
-            for (size_t d = 0; d < D; d++) gain[(p * D + d) * W + i] = k[(p * W + i) * D + d];
-    return HC_OK;
+    return gain_hook(h, h->enkf_rgain.p, gain, (size_t)h->enkf_width, "hc_get_enkf_sqrt_gain");
 }
 
 int hc_get_enkf_sqrt_shift(hc_handle *h, double *shift)
