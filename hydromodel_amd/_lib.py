@@ -49,6 +49,9 @@ class SpinupArgs(C.Structure):
 # hc_enkf_exchange_fn: (ctx, device_buf, n_words, first_word, count_words) -> 0 = ok
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64)
 
+# hc_filter_route_fn: (ctx, send, send_words[n_shards], recv, recv_words[n_shards]) -> 0 = ok
+ROUTE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, _lp, C.c_void_p, _lp)
+
 EXPORTS = {
     "hc_create": ([C.c_int, C.POINTER(C.c_void_p)], C.c_int),
     "hc_destroy": ([C.c_void_p], C.c_int),
@@ -135,6 +138,10 @@ EXPORTS = {
     "hc_get_enkf_shard_words": ([C.c_void_p, C.c_int64, _lp], C.c_int),
     "hc_set_enkf_shard": ([C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, EXCHANGE_FN, C.c_void_p], C.c_int),
     "hc_get_enkf_shard": ([C.c_void_p, _lp, _lp], C.c_int),
+    "hc_get_filter_shard_words": ([C.c_void_p, C.c_int32, _lp, C.c_int32, _lp], C.c_int),
+    "hc_set_filter_shard": ([C.c_void_p, C.c_int32, _lp, C.c_int32, C.c_void_p, C.c_int64, EXCHANGE_FN, ROUTE_FN, C.c_void_p],
+                            C.c_int),
+    "hc_get_filter_shard": ([C.c_void_p, _ip, _ip, _lp], C.c_int),
     "hc_rhs": ([C.c_void_p, C.c_int64, C.c_int32, _dp, _dp], C.c_int),
     "hc_model_nodes": ([C.c_void_p, _dp, _dp], C.c_int),
     "hc_plugin_eval": ([C.c_int, C.POINTER(ColumnParams), C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
@@ -148,7 +155,8 @@ _torch_first = False        # torch was in the process before the library: the t
 def load(with_torch=False):
     """Load libhydrocol.so; raises if it has not been built.
 
-    ``with_torch``: the caller will hand the library device memory that torch allocated (hc_set_enkf_shard's buffer).
+    ``with_torch``: the caller will hand the library device memory that torch allocated (the buffer of hc_set_enkf_shard
+    or hc_set_filter_shard).
     torch ships a HIP runtime of its own, and the loader gives the library that one only when torch is in the process
     first; loaded the other way round, the process holds two runtimes and torch's finds no GPU.  So torch is imported
     here before the library, and a process that loaded the library before torch is an error, not a second runtime."""

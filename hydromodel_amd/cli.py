@@ -42,7 +42,13 @@ unknown keys, only membership of the 12 is checked):
   ``filter_rows``, ``filter_count``, ``filter_ess``, ``filter_loglik_rows``, ``filter_survivors`` ``[R]``, ``filter_loglik``
   (the log marginal likelihood of the well record, log cm^-1) and ``filter_sigma_cm`` (a sweep: a leading ``[P]`` axis), and
   the run ends with `` [Ensemble xN] filter log-likelihood = ... over R rows`` (a sweep: the best point).  A single-point
-  ensemble on several GPUs is refused (resampling would move states between ranks).
+  ensemble on several GPUs is refused (resampling would move states between ranks) unless the block is sharded:
+* ``"Filter": {..., "Sharded": true}``: a single-point ensemble's particle filter on ``--gpus N`` (include/hydrocol.h
+  hc_set_filter_shard).  The members are dealt by ``multigpu.shard`` (any split), every assimilation gathers the members'
+  water-table indices, every rank forms the whole ancestry, and the columns whose ancestor lives on another rank are
+  exchanged; the states, tables, closing lines and the file are those of the one-GPU run to the bit (``gpus`` apart); the
+  filter's tables are rank 0's.  ``false`` or no key: the refusal above.  A sweep accepts and ignores the key.  Added to
+  the file when the key is given: ``filter_sharded``.
 * ``"Ensemble": {..., "EnKF": {"Stride": 48, "Sigma_cm": 10.0, "Localisation_cm": 0, "Seed": s}}``: a stochastic ensemble
   Kalman filter on the well's continuous water table (include/hydrocol.h hc_set_enkf) -- on every 48th forcing row (default
   48; 0 = off) that has an observation each member's psi moves by the sample covariance with the water table, per parameter
@@ -221,10 +227,16 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
         return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels, filt,
                           enkf, record, scheme, window)
     sharded = enkf_sharded(ens)
+    fsharded = filter_sharded(ens)
     if sharded:
         # whole tiles of the EnKF's sums per rank, and the analyses gather them: the one-rank run on any number of GPUs
         lo, hi = multigpu.shard_tiles(n_members, ranks.rank, ranks.world)
         shard_kw = dict(enkf_shard=(n_members, multigpu.ShardExchange(ranks)))
+    elif fsharded:
+        # any split will do: every rank forms the whole ancestry and the ranks exchange the columns that change hands
+        bounds = [0] + [multigpu.shard(n_members, r, ranks.world)[1] for r in range(ranks.world)]
+        lo, hi = bounds[ranks.rank], bounds[ranks.rank + 1]
+        shard_kw = dict(filter_shard=(bounds, ranks.rank, multigpu.ShardExchange(ranks)))
     else:
         lo, hi = multigpu.shard(n_members, ranks.rank, ranks.world)
         shard_kw = {}
@@ -262,11 +274,13 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     tables, crps_line = _reduce_optional(ranks, sim, [0], [cols], forcing, stride, dist_stride, dist_levels, device,
                                          label, keep_points=False)
     extra.update(tables)
-    ftables, filter_line = _reduce_filter(ranks, sim, [0], 1, forcing.dim_t, filt, label, keep_points=False)
-    extra.update(ftables)
-    # the EnKF's tables describe the one point: every rank of a sharded run holds the same ones, and rank 0's are taken
+    # the filters' tables describe the one point: every rank of a sharded run holds the same ones, and rank 0's are taken
     # (placed by it alone; a sum over the ranks would count them world times)
     eids = [0] if ranks.rank == 0 else []
+    ftables, filter_line = _reduce_filter(ranks, sim, eids, 1, forcing.dim_t, filt, label, keep_points=False)
+    extra.update(ftables)
+    if fsharded is not None:
+        extra["filter_sharded"] = np.array(1 if fsharded else 0, dtype=np.int8)
     etables, enkf_line = _reduce_enkf(ranks, sim, eids, 1, forcing.dim_t, enkf, label, keep_points=False,
                                          z0_cm=cols.z[0])
     extra.update(etables)
@@ -326,13 +340,14 @@ def distribution_settings(ens):
     return (stride, tuple(float(q) for q in levels)) if stride else (0, None)
 
 
-FILTER_KEYS = ("Stride", "Sigma_cm", "Seed")
+FILTER_KEYS = ("Stride", "Sigma_cm", "Seed", "Sharded")
 
 
 def filter_settings(ens, n_gpus=1):
     """Ensemble.Filter -> (stride, sigma_cm, seed or None = the ensemble's seed); (0, None, None) when absent or off.  Pure:
     runs before any GPU call, and a bad value is a ValueError (message + exit status 1).  A single-point ensemble on more
-    than one GPU is refused: resampling would have to move states between ranks."""
+    than one GPU is refused -- resampling would have to move states between ranks -- unless the block says
+    ``"Sharded": true`` (:func:`filter_sharded`)."""
     import math
     from numbers import Integral, Real
     block = ens.get("Filter")
@@ -356,13 +371,27 @@ def filter_settings(ens, n_gpus=1):
     seed = block.get("Seed")
     if seed is not None and (isinstance(seed, bool) or not isinstance(seed, Integral) or not 0 <= seed < (1 << 64)):
         raise ValueError(f" Ensemble: Filter.Seed = {seed!r} must be an integer in [0, 2^64).")
+    sharded = block.get("Sharded", False)
+    if not isinstance(sharded, bool):
+        raise ValueError(f" Ensemble: Filter.Sharded = {sharded!r} must be true or false.")
     stride = int(stride)
     if not stride:
         return 0, None, None
-    if not ens.get("Points") and int(n_gpus) > 1:
+    if not ens.get("Points") and int(n_gpus) > 1 and not sharded:
         raise ValueError(f" Ensemble: Filter with one parameter point runs on one GPU ({n_gpus} requested): resampling "
                          f"would move members between ranks.")
     return stride, float(sigma), (None if seed is None else int(seed))
+
+
+def filter_sharded(ens):
+    """Ensemble.Filter.Sharded -> True / False, or None when the key is not given (or the filter is off).  With true a
+    single-point ensemble's members are dealt to the GPUs, every assimilation gathers their water-table indices and the
+    ranks exchange the columns whose ancestor lives elsewhere, so the run is the one-GPU run to the bit (include/hydrocol.h
+    hc_set_filter_shard); a sweep ignores it (its points are dealt whole).  Checked by :func:`filter_settings`."""
+    block = ens.get("Filter")
+    if not isinstance(block, dict) or "Sharded" not in block or not filter_settings(ens)[0]:
+        return None
+    return bool(block["Sharded"])
 
 
 ENKF_KEYS = ("Stride", "Sigma_cm", "Localisation_cm", "Seed", "Soil_Moisture", "Method", "Relaxation", "Window_Offsets",

@@ -176,6 +176,23 @@ struct hc_handle {
     DevBuf<unsigned long long> filt_qr, filt_surv;
     std::vector<long long> filt_rows_host;
     std::vector<int> h_wtd_obs;
+    // one point's members on several handles (hc_set_filter_shard): the shard count (0: off), this handle's index and the
+    // bounds b_0 = 0 < ... < b_S = n_global, on the host and on the device; the caller's buffer -- the gathered
+    // water-table indices [n_global], the send region [(n + S - 1) 2 D] and the receive region [n 2 D], in 8-byte
+    // words -- and callbacks; the gathered indices narrowed for the ancestry kernels, every slot's rank among the
+    // distinct ancestors, the routing table [6][S] (received / sent members per shard, their offsets in the regions,
+    // the first slot of each run), the members to pack and every slot's source
+    int fs_n = 0, fs_index = 0;
+    std::vector<long long> fs_bounds;
+    int64_t fs_words = 0;
+    long long *fs_buf = nullptr;
+    hc_enkf_exchange_fn fs_gather = nullptr;
+    hc_filter_route_fn fs_route = nullptr;
+    void *fs_ctx = nullptr;
+    DevBuf<long long> fs_bounds_dev, fs_rank, fs_table, fs_list, fs_src;
+    DevBuf<unsigned short> fs_w;
+    std::vector<long long> fs_counts;
+    std::vector<int64_t> fs_send_words, fs_recv_words;
     // ensemble Kalman filter (hc_set_enkf): diagnostics float64 [P][n_arow][8] keyed by (points, rows, stride); per
     // member the observations Y [N][m'] (the well's y first), the well's eps, the sensors' eps [N][sm_n] and the
     // posterior (y, theta..., rejected); per point the raw sums of both passes and the gain [P][m'][D] (the last
@@ -805,6 +822,173 @@ __global__ void filter_gather_kernel(const long long *anc, const double *psi, co
         const size_t src = (size_t)(a >= 0 && a < n_members ? a : k) * D + e % D;     // (every slot is filled: a guard)
         psi_out[e] = psi[src];
         if (base) base_out[e] = base[src];
+    }
+}
+
+// ---- one point's members on several handles (hc_set_filter_shard, include/hydrocol.h): integers and 8-byte copies only.
+// Every handle computes the point's whole ancestry anc[n_global] from the gathered water-table indices.  Systematic
+// resampling is monotone -- anc[k] is non-decreasing in k -- so equal ancestors are neighbours, the slots of a shard
+// that take their column from another shard's members form one run, and both ends of a transfer derive the same list
+// of members (the distinct ancestors of the run, ascending) from the same table.
+
+// the handle's water-table indices of the row as 8-byte words at their place in the gathered vector
+__global__ void filter_shard_index_kernel(const unsigned short *w, long long n, long long *idx)
+{
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n) idx[k] = (long long)w[k];
+}
+
+// ... and the gathered vector as the ancestry kernels read it
+__global__ void filter_shard_narrow_kernel(const long long *idx, long long n_global, unsigned short *w)
+{
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n_global) w[k] = (unsigned short)idx[k];
+}
+
+// Slot k opens a run when k = 0 or anc[k] != anc[k - 1].  rank == NULL: the runs opened in each tile of FILT_TILE slots
+// -> tiles[t]; else, tiles[] being their exclusive prefix sums (filter_tile_scan_kernel), rank[k] = the runs opened in
+// [0, k], less one: the index of anc[k] among the distinct ancestors.
+__global__ __launch_bounds__(FILT_THREADS) void filter_shard_rank_kernel(const long long *anc, long long n_global,
+                                                                         long long *tiles, long long *rank)
+{
+    const long long k0 = (long long)blockIdx.x * FILT_TILE + (long long)threadIdx.x * FILT_PER_THREAD;
+    long long prev = k0 > 0 && k0 < n_global ? anc[k0 - 1] : -1, v = 0;
+    bool opens[FILT_PER_THREAD];
+    for (int j = 0; j < FILT_PER_THREAD; j++) {
+        const long long k = k0 + j;
+        opens[j] = false;
+        if (k < n_global) {
+            const long long a = anc[k];
+            opens[j] = k == 0 || a != prev;
+            prev = a;
+        }
+        v += opens[j] ? 1 : 0;
+    }
+    long long total;
+    const long long before = block_exclusive_scan(v, total);
+    if (!rank) {
+        if (threadIdx.x == 0) tiles[blockIdx.x] = total;
+        return;
+    }
+    long long c = tiles[blockIdx.x] + before;
+    for (int j = 0; j < FILT_PER_THREAD; j++) {
+        const long long k = k0 + j;
+        c += opens[j] ? 1 : 0;
+        if (k < n_global) rank[k] = c - 1;
+    }
+}
+
+// the first index in [lo, hi) of the non-decreasing a[] whose entry is >= v (hi: none)
+__device__ __forceinline__ long long filter_lower_bound(const long long *a, long long lo, long long hi, long long v)
+{
+    while (lo < hi) {
+        const long long mid = lo + (hi - lo) / 2;
+        if (a[mid] < v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// the shard that holds member (or slot) v: bounds[s] <= v < bounds[s + 1]
+__device__ __forceinline__ int filter_shard_of(const long long *bounds, int S, long long v)
+{
+    return (int)filter_lower_bound(bounds + 1, 0, S - 1, v + 1);
+}
+
+// the distinct ancestors that the slots [k0, k1) have in [m0, m1), and the first such slot
+__device__ __forceinline__ long long filter_run(const long long *anc, const long long *rank, long long k0, long long k1,
+                                                long long m0, long long m1, long long &lo)
+{
+    lo = filter_lower_bound(anc, k0, k1, m0);
+    const long long hi = filter_lower_bound(anc, lo, k1, m1);
+    return hi > lo ? rank[hi - 1] - rank[lo] + 1 : 0;
+}
+
+// The routing table [6][S] of shard `me`, one thread per other shard s: the members it receives from s (rows 0 and 2)
+// and sends to s (rows 1 and 3), and the first slot of either run (rows 4 and 5).  filter_tile_scan_kernel then turns
+// rows 2 and 3 into the offsets of the blocks in the receive and the send region, in members.
+__global__ void filter_route_kernel(const long long *anc, const long long *rank, const long long *bounds, int S, int me,
+                                    long long *table)
+{
+    const long long first = bounds[me], last = bounds[me + 1];
+    for (int s = blockIdx.x * blockDim.x + threadIdx.x; s < S; s += gridDim.x * blockDim.x) {
+        long long lo_r = first, lo_s = bounds[s], n_r = 0, n_s = 0;
+        if (s != me) {
+            n_r = filter_run(anc, rank, first, last, bounds[s], bounds[s + 1], lo_r);
+            n_s = filter_run(anc, rank, bounds[s], bounds[s + 1], first, last, lo_s);
+        }
+        table[s] = table[2 * S + s] = n_r;
+        table[S + s] = table[3 * S + s] = n_s;
+        table[4 * S + s] = lo_r;
+        table[5 * S + s] = lo_s;
+    }
+}
+
+// Every slot of the point, from the routing table.  One of the handle's own: its source, src[k - first] = the local
+// member, or -1 - j for entry j of the receive region.  Another shard's slot that opens a run of one of the handle's
+// members: that member into the list of columns to pack, at the run's place in the destination's block.  (A table that
+// is not an ancestry -- a gather that did not deliver -- writes nothing out of bounds: such a slot keeps its own column.)
+__global__ void filter_route_fill_kernel(const long long *anc, const long long *rank, const long long *bounds, int S, int me,
+                                         const long long *table, long long n_global, long long *list, long long list_cap,
+                                         long long *src)
+{
+    const long long first = bounds[me], last = bounds[me + 1], n = last - first;
+    for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < n_global; k += (long long)gridDim.x * blockDim.x) {
+        const long long a = anc[k];
+        const bool local = a >= first && a < last;
+        if (k >= first && k < last) {
+            long long from = k - first;
+            if (local) {
+                from = a - first;
+            } else if (a >= 0 && a < n_global) {
+                const int s = filter_shard_of(bounds, S, a);
+                const long long lo = table[4 * S + s];
+                const long long j = lo <= k ? table[2 * S + s] + rank[k] - rank[lo] : -1;
+                if (j >= 0 && j < n) from = -1 - j;
+            }
+            src[k - first] = from;
+        } else if (local) {
+            const int d = filter_shard_of(bounds, S, k);
+            if (k == bounds[d] || anc[k - 1] != a) {
+                const long long lo = table[5 * S + d];
+                const long long j = lo <= k ? table[3 * S + d] + rank[k] - rank[lo] : -1;
+                if (j >= 0 && j < list_cap) list[j] = a - first;
+            }
+        }
+    }
+}
+
+// the listed members' columns into the send region, psi[D] then base[D] per member, as 8-byte words
+__global__ void filter_pack_kernel(const long long *list, const long long *table, int S, long long list_cap, long long n,
+                                   const long long *psi, const long long *base, long long *send, int D)
+{
+    long long n_list = table[3 * S + S - 1] + table[S + S - 1];
+    n_list = n_list < list_cap ? n_list : list_cap;
+    const size_t total = (size_t)(n_list > 0 ? n_list : 0) * 2 * D;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const long long m = list[e / (2 * (size_t)D)];
+        const int c = (int)(e % (2 * (size_t)D));
+        if (m < 0 || m >= n) continue;
+        send[e] = c < D ? psi[(size_t)m * D + c] : base[(size_t)m * D + (c - D)];
+    }
+}
+
+// slot k takes psi and base from the handle's own member src[k], or from entry -1 - src[k] of the receive region
+// (into the second buffers, as filter_gather_kernel does)
+__global__ void filter_shard_gather_kernel(const long long *src, const long long *psi, const long long *base,
+                                           const long long *recv, long long *psi_out, long long *base_out, long long n, int D)
+{
+    const size_t total = (size_t)n * D;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const long long s = src[e / D];
+        const size_t i = e % D;
+        if (s >= 0) {
+            psi_out[e] = psi[(size_t)s * D + i];
+            base_out[e] = base[(size_t)s * D + i];
+        } else {
+            const size_t at = (size_t)(-1 - s) * 2 * D + i;
+            psi_out[e] = recv[at];
+            base_out[e] = recv[at + D];
+        }
     }
 }
 
@@ -1795,9 +1979,39 @@ int ensure_filter(hc_handle *h)
     return ensure_da_table(h, h->filt, h->filt_stride, 4, 4);
 }
 
+void filter_shard_off(hc_handle *h)
+{
+    h->fs_n = h->fs_index = 0;
+    h->fs_words = 0;
+    h->fs_buf = nullptr;
+    h->fs_gather = nullptr;
+    h->fs_route = nullptr;
+    h->fs_ctx = nullptr;
+    h->fs_bounds.clear(); h->fs_counts.clear(); h->fs_send_words.clear(); h->fs_recv_words.clear();
+    h->fs_bounds_dev.release(); h->fs_rank.release(); h->fs_table.release(); h->fs_list.release(); h->fs_src.release();
+    h->fs_w.release();
+}
+
+// The caller's buffer of a shard of n members of a point with n_global, in 8-byte words: the gathered water-table
+// indices [n_global], then the send region and the receive region.  The ancestry is monotone, so a shard's slots have
+// at most n distinct ancestors elsewhere, and the runs of its own members in the other shards' slots hold at most
+// n + S - 1 (two neighbouring destinations may both take the member their runs meet in).
+struct FilterShardLayout {
+    int64_t send, recv, words;         // the regions' offsets, the total
+};
+FilterShardLayout filter_shard_layout(int64_t n_global, int64_t n, int64_t S, int64_t D)
+{
+    FilterShardLayout L;
+    L.send = n_global;
+    L.recv = L.send + (n + S - 1) * 2 * D;
+    L.words = L.recv + n * 2 * D;
+    return L;
+}
+
 // what turns the filter off: new points, members or noise source (include/hydrocol.h hc_set_filter)
 void filter_off(hc_handle *h)
 {
+    filter_shard_off(h);
     h->filt_stride = 0;
     h->filt_done = false;
     h->filt.release();
@@ -2747,22 +2961,114 @@ int copy_outputs(hc_handle *h, hc_step_args *a, const Chunk &c, int64_t done)
     return HC_OK;
 }
 
+// A callback of a sharded assimilation (hc_set_filter_shard) runs on a drained stream; one that fails fails the step.
+int filter_shard_call(hc_handle *h, const char *what, int rc)
+{
+    if (rc) return fail(HC_ERR_DEVICE, "the filter shard's %s callback returned %d (shard %d of %d)", what, rc, h->fs_index,
+                        h->fs_n);
+    return HC_OK;
+}
+
+// The routing of a sharded assimilation, after the ancestry of the whole point: every slot's rank among the distinct
+// ancestors, the routing table, the columns to send packed, the counts on the host, the caller's exchange, and the
+// handle's slots gathered from its own members and the receive region into the second buffers.
+int filter_shard_resample(hc_handle *h, int64_t n_tiles)
+{
+    const int64_t N = h->n_members, D = h->p.dim_d, S = h->fs_n, me = h->fs_index, np = h->fs_bounds[(size_t)S];
+    const FilterShardLayout L = filter_shard_layout(np, N, S, D);
+    const long long *anc = h->filt_anc.p, *bounds = h->fs_bounds_dev.p;
+    long long *const send = h->fs_buf + L.send, *const recv = h->fs_buf + L.recv;
+    const long long list_cap = (long long)(N + S - 1);
+    hipLaunchKernelGGL(filter_shard_rank_kernel, dim3((unsigned)n_tiles), dim3(FILT_THREADS), 0, h->stream, anc, (long long)np,
+                       h->filt_tiles.p, (long long *)nullptr);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(filter_tile_scan_kernel, dim3(1), dim3(FILT_THREADS), 0, h->stream, (long long)n_tiles,
+                       h->filt_tiles.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(filter_shard_rank_kernel, dim3((unsigned)n_tiles), dim3(FILT_THREADS), 0, h->stream, anc, (long long)np,
+                       h->filt_tiles.p, h->fs_rank.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(filter_route_kernel, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, h->stream, anc, h->fs_rank.p,
+                       bounds, (int)S, (int)me, h->fs_table.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(filter_tile_scan_kernel, dim3(2), dim3(FILT_THREADS), 0, h->stream, (long long)S,
+                       h->fs_table.p + 2 * S);
+    HIP_TRY(hipGetLastError());
+    const unsigned slot_blocks = (unsigned)std::min<int64_t>((np + 255) / 256, (int64_t)h->n_cu * 64);
+    hipLaunchKernelGGL(filter_route_fill_kernel, dim3(slot_blocks), dim3(256), 0, h->stream, anc, h->fs_rank.p, bounds, (int)S,
+                       (int)me, h->fs_table.p, (long long)np, h->fs_list.p, list_cap, h->fs_src.p);
+    HIP_TRY(hipGetLastError());
+    const long long *psi = reinterpret_cast<const long long *>(h->psi.p), *base = reinterpret_cast<const long long *>(h->base.p);
+    const size_t most = (size_t)list_cap * 2 * D, total = (size_t)N * D;
+    hipLaunchKernelGGL(filter_pack_kernel, dim3((unsigned)std::min<size_t>((most + 255) / 256, (size_t)h->n_cu * 64)), dim3(256),
+                       0, h->stream, h->fs_list.p, h->fs_table.p, (int)S, list_cap, (long long)N, psi, base, send, (int)D);
+    HIP_TRY(hipGetLastError());
+    h->fs_counts.resize((size_t)(2 * S));
+    HIP_TRY(hipMemcpyAsync(h->fs_counts.data(), h->fs_table.p, (size_t)(2 * S) * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->fs_recv_words.resize((size_t)S);
+    h->fs_send_words.resize((size_t)S);
+    int64_t n_recv = 0, n_send = 0;
+    for (int64_t s = 0; s < S; s++) {
+        n_recv += h->fs_counts[(size_t)s];
+        n_send += h->fs_counts[(size_t)(S + s)];
+        h->fs_recv_words[(size_t)s] = h->fs_counts[(size_t)s] * 2 * D;
+        h->fs_send_words[(size_t)s] = h->fs_counts[(size_t)(S + s)] * 2 * D;
+    }
+    if (n_recv > N || n_send > list_cap)
+        return fail(HC_ERR_DEVICE, "the filter shard's gathered water-table indices give no monotone ancestry (%lld columns "
+                    "to receive, %lld to send, %lld members): the gather callback did not deliver", (long long)n_recv,
+                    (long long)n_send, (long long)N);
+    if (int rc = filter_shard_call(h, "routing", h->fs_route(h->fs_ctx, send, h->fs_send_words.data(), recv,
+                                                             h->fs_recv_words.data())))
+        return rc;
+    hipLaunchKernelGGL(filter_shard_gather_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, (size_t)h->n_cu * 64)),
+                       dim3(256), 0, h->stream, h->fs_src.p, psi, base, recv, reinterpret_cast<long long *>(h->psi_alt.p),
+                       reinterpret_cast<long long *>(h->base_alt.p), (long long)N, (int)D);
+    HIP_TRY(hipGetLastError());
+    return HC_OK;
+}
+
 // The assimilation at the launch's last row (its water-table indices are wtd_u16's last row): weights, diagnostics and
 // draw per point, the member prefix scan, the slot fill, then psi and base gathered into the second buffers and swapped in.
+// hc_set_filter_shard: the handle's members are a part of a point of np members; the water-table indices of all of them
+// are gathered first (one callback), the same kernels form the whole point's ancestry on every handle, and the gather
+// takes the columns of ancestors on other handles from the caller's exchange (filter_shard_resample).
 int assimilate(hc_handle *h, const Chunk &c)
 {
-    const int64_t N = h->n_members, D = h->p.dim_d, P = h->n_points, mpp = N / P;
+    const int64_t N = h->n_members, D = h->p.dim_d, P = h->n_points;
+    const bool shard = h->fs_n > 0;
+    const int64_t first = shard ? h->fs_bounds[(size_t)h->fs_index] : 0;
+    const int64_t mpp = shard ? h->fs_bounds[(size_t)h->fs_n] : N / P;
     const int64_t row = c.row0 + c.rows - 1, slot = row / h->filt_stride, n_arow = filter_rows(h);
     const int64_t n_tiles = (mpp + FILT_TILE - 1) / FILT_TILE;
     if (h->filt_q.ensure((size_t)(P * D)) || h->filt_qr.ensure((size_t)(2 * P)) || h->filt_surv.ensure((size_t)P) ||
-        h->filt_tiles.ensure((size_t)(P * n_tiles)) || h->filt_anc.ensure((size_t)N) || h->psi_alt.ensure((size_t)(N * D)))
+        h->filt_tiles.ensure((size_t)(P * n_tiles)) || h->filt_anc.ensure((size_t)(P * mpp)) ||
+        h->psi_alt.ensure((size_t)(N * D)))
         return HC_ERR_DEVICE;
     if (h->base.ensure((size_t)(N * D)) || h->base_alt.ensure((size_t)(N * D))) return HC_ERR_DEVICE;
     const unsigned short *w = h->wtd_u16.p + (size_t)(c.rows - 1) * N;
+    // the draw's key: the point's first global member id (a Philox shard's members are keyed from its own first one)
+    long long key = (long long)h->member_offset;
+    if (shard) {
+        if (h->fs_w.ensure((size_t)mpp) || h->fs_rank.ensure((size_t)mpp) || h->fs_table.ensure((size_t)(6 * h->fs_n)) ||
+            h->fs_list.ensure((size_t)(N + h->fs_n - 1)) || h->fs_src.ensure((size_t)N))
+            return HC_ERR_DEVICE;
+        hipLaunchKernelGGL(filter_shard_index_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, w,
+                           (long long)N, h->fs_buf + first);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if (int rc = filter_shard_call(h, "gather", h->fs_gather(h->fs_ctx, h->fs_buf, mpp, first, N))) return rc;
+        hipLaunchKernelGGL(filter_shard_narrow_kernel, dim3((unsigned)((mpp + 255) / 256)), dim3(256), 0, h->stream,
+                           h->fs_buf, (long long)mpp, h->fs_w.p);
+        HIP_TRY(hipGetLastError());
+        w = h->fs_w.p;
+        if (h->philox) key -= first;
+    }
     const long long *pbase = P > 1 ? h->point_base.p : nullptr;
     hipLaunchKernelGGL(filter_weights_kernel, dim3((unsigned)P), dim3(FILT_THREADS), 0, h->stream, w, (long long)mpp,
                        (int)D, h->h_wtd_obs[(size_t)row], h->p.dz, h->filt_sigma, (unsigned long long)h->filt_seed, pbase,
-                       (long long)h->member_offset, (unsigned)row, (long long)n_arow, (long long)slot, h->filt_q.p,
+                       key, (unsigned)row, (long long)n_arow, (long long)slot, h->filt_q.p,
                        h->filt_qr.p, h->filt.buf.p, h->filt_surv.p);
     HIP_TRY(hipGetLastError());
     const dim3 tiles((unsigned)n_tiles, (unsigned)P);
@@ -2772,18 +3078,22 @@ int assimilate(hc_handle *h, const Chunk &c)
     hipLaunchKernelGGL(filter_tile_scan_kernel, dim3((unsigned)P), dim3(FILT_THREADS), 0, h->stream, (long long)n_tiles,
                        h->filt_tiles.p);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemsetAsync(h->filt_anc.p, 0xFF, (size_t)N * 8, h->stream));
+    HIP_TRY(hipMemsetAsync(h->filt_anc.p, 0xFF, (size_t)(P * mpp) * 8, h->stream));
     hipLaunchKernelGGL(filter_fill_kernel, tiles, dim3(FILT_THREADS), 0, h->stream, w, h->filt_q.p, (long long)mpp, (int)D,
                        (long long)n_tiles, h->filt_tiles.p, h->filt_qr.p, h->filt_anc.p, h->filt_surv.p);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(filter_survivors_kernel, dim3((unsigned)((P + 63) / 64)), dim3(64), 0, h->stream, h->filt_surv.p,
                        (int)P, (long long)n_arow, (long long)slot, h->filt.buf.p);
     HIP_TRY(hipGetLastError());
-    const size_t total = (size_t)N * D;
-    const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)h->n_cu * 64);
-    hipLaunchKernelGGL(filter_gather_kernel, dim3(blocks), dim3(256), 0, h->stream, h->filt_anc.p, h->psi.p, h->base.p,
-                       h->psi_alt.p, h->base_alt.p, (long long)N, (int)D);
-    HIP_TRY(hipGetLastError());
+    if (shard) {
+        if (int rc = filter_shard_resample(h, n_tiles)) return rc;
+    } else {
+        const size_t total = (size_t)N * D;
+        const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)h->n_cu * 64);
+        hipLaunchKernelGGL(filter_gather_kernel, dim3(blocks), dim3(256), 0, h->stream, h->filt_anc.p, h->psi.p, h->base.p,
+                           h->psi_alt.p, h->base_alt.p, (long long)N, (int)D);
+        HIP_TRY(hipGetLastError());
+    }
     std::swap(h->psi, h->psi_alt);
     std::swap(h->base, h->base_alt);
     // the rest of this hc_step_rows call launches on the analysis (fill_args took the pointers before the swap)
@@ -3409,13 +3719,13 @@ int hc_set_filter_stats(hc_handle *h, const double *table, int64_t n_entries)
 }  // extern "C"
 namespace {
 template <typename T>
-int filter_hook(hc_handle *h, const DevBuf<T> &b, void *out, size_t count, const char *who)
+int filter_hook(hc_handle *h, const DevBuf<T> &b, void *out, size_t count, const char *who, size_t first = 0)
 {
     if (!h || !out) return fail(HC_ERR_ARG, "%s: bad argument", who);
     if (h->filt_stride <= 0 || !h->filt_done) return fail(HC_ERR_ARG, "%s: no assimilation since hc_set_filter", who);
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(out, b.p, count * sizeof(T), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, b.p + first, count * sizeof(T), hipMemcpyDeviceToHost));
     return HC_OK;
 }
 }  // namespace
@@ -3423,7 +3733,9 @@ extern "C" {
 
 int hc_get_filter_ancestors(hc_handle *h, int64_t *ancestors)
 {
-    return filter_hook(h, h->filt_anc, ancestors, (size_t)h->n_members, "hc_get_filter_ancestors");
+    // (hc_set_filter_shard: the table is the whole point's, in global ids; the handle's own slots of it)
+    const size_t first = h && h->fs_n > 0 ? (size_t)h->fs_bounds[(size_t)h->fs_index] : 0;
+    return filter_hook(h, h->filt_anc, ancestors, h ? (size_t)h->n_members : 0, "hc_get_filter_ancestors", first);
 }
 
 int hc_get_filter_weights(hc_handle *h, int64_t *q)
@@ -3461,6 +3773,83 @@ int hc_set_filter_base(hc_handle *h, const double *base)
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipMemcpy(h->base.p, base, n * 8, hipMemcpyHostToDevice));
+    return HC_OK;
+}
+
+}  // extern "C"
+namespace {
+// the argument checks the two shard entry points share; n_global through *np
+int filter_shard_check(const hc_handle *h, int32_t n_shards, const int64_t *bounds, int32_t index, const char *who, int64_t *np)
+{
+    if (h->filt_stride <= 0) return fail(HC_ERR_ARG, "%s: the particle filter is off (hc_set_filter comes first)", who);
+    if (h->n_points > 1)
+        return fail(HC_ERR_ARG, "%s: the handle holds %d points (a shard is a part of one point's members)", who, h->n_points);
+    if (n_shards < 1 || !bounds) return fail(HC_ERR_ARG, "%s: bad argument", who);
+    if (bounds[0] != 0) return fail(HC_ERR_ARG, "%s: bounds[0] = %lld, the bounds must start at 0", who, (long long)bounds[0]);
+    for (int32_t s = 0; s < n_shards; s++)
+        if (bounds[s + 1] <= bounds[s])
+            return fail(HC_ERR_ARG, "%s: bounds[%d] = %lld after %lld, the bounds must be strictly increasing", who, s + 1,
+                        (long long)bounds[s + 1], (long long)bounds[s]);
+    if (index < 0 || index >= n_shards)
+        return fail(HC_ERR_ARG, "%s: index = %d lies outside [0, %d)", who, index, n_shards);
+    if (bounds[n_shards] > INT32_MAX)
+        return fail(HC_ERR_ARG, "%s: %lld members of the point exceed 2^31 - 1", who, (long long)bounds[n_shards]);
+    if (h->n_members != bounds[index + 1] - bounds[index])
+        return fail(HC_ERR_ARG, "%s: the handle holds %lld members, shard %d has [%lld, %lld)", who, (long long)h->n_members,
+                    index, (long long)bounds[index], (long long)bounds[index + 1]);
+    if (h->philox && h->member_offset != bounds[index])
+        return fail(HC_ERR_ARG, "%s: shard %d starts at member %lld, but hc_set_noise_philox keys the members from %lld", who,
+                    index, (long long)bounds[index], (long long)h->member_offset);
+    *np = bounds[n_shards];
+    return HC_OK;
+}
+}  // namespace
+extern "C" {
+
+int hc_get_filter_shard_words(hc_handle *h, int32_t n_shards, const int64_t *bounds, int32_t index, int64_t *n_words)
+{
+    if (!h || !n_words) return fail(HC_ERR_ARG, "hc_get_filter_shard_words: bad argument");
+    int64_t np = 0;
+    if (int rc = filter_shard_check(h, n_shards, bounds, index, "hc_get_filter_shard_words", &np)) return rc;
+    *n_words = filter_shard_layout(np, h->n_members, n_shards, h->p.dim_d).words;
+    return HC_OK;
+}
+
+int hc_set_filter_shard(hc_handle *h, int32_t n_shards, const int64_t *bounds, int32_t index, void *device_buf,
+                        int64_t n_words, hc_enkf_exchange_fn gather, hc_filter_route_fn route, void *ctx)
+{
+    if (!h || n_shards < 0) return fail(HC_ERR_ARG, "hc_set_filter_shard: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    filter_shard_off(h);
+    if (n_shards == 0) return HC_OK;
+    int64_t np = 0;
+    if (int rc = filter_shard_check(h, n_shards, bounds, index, "hc_set_filter_shard", &np)) return rc;
+    if (!device_buf || !gather || !route) return fail(HC_ERR_ARG, "hc_set_filter_shard: NULL buffer or callback");
+    const int64_t need = filter_shard_layout(np, h->n_members, n_shards, h->p.dim_d).words;
+    if (n_words < need)
+        return fail(HC_ERR_ARG, "hc_set_filter_shard: a buffer of %lld words, %lld needed (hc_get_filter_shard_words)",
+                    (long long)n_words, (long long)need);
+    std::vector<long long> b(bounds, bounds + n_shards + 1);
+    if (h->fs_bounds_dev.ensure(b.size())) return HC_ERR_DEVICE;
+    HIP_TRY(hipMemcpy(h->fs_bounds_dev.p, b.data(), b.size() * 8, hipMemcpyHostToDevice));
+    h->fs_bounds = b;
+    h->fs_n = n_shards;
+    h->fs_index = index;
+    h->fs_buf = static_cast<long long *>(device_buf);
+    h->fs_words = n_words;
+    h->fs_gather = gather;
+    h->fs_route = route;
+    h->fs_ctx = ctx;
+    return HC_OK;
+}
+
+int hc_get_filter_shard(hc_handle *h, int32_t *n_shards, int32_t *index, int64_t *n_global)
+{
+    if (!h || !n_shards || !index || !n_global) return fail(HC_ERR_ARG, "hc_get_filter_shard: bad argument");
+    *n_shards = h->fs_n;
+    *index = h->fs_index;
+    *n_global = h->fs_n > 0 ? (int64_t)h->fs_bounds[(size_t)h->fs_n] : 0;
     return HC_OK;
 }
 

@@ -254,14 +254,20 @@ class EnsembleSimulation(_Run):
     whose other members run elsewhere, and the EnKF analyses the whole of it (include/hydrocol.h hc_set_enkf_shard;
     ``exchange``: e.g. a ``multigpu.ShardExchange``).  member_offset must be a multiple of 256, and so must N unless the
     block is the ensemble's last.  Set up by the run: a checkpoint does not carry it.
+    filter_shard=(bounds, index, exchange): these members are block ``index`` of an ensemble split at ``bounds`` whose
+    other blocks run elsewhere, and the particle filter resamples the whole of it (include/hydrocol.h
+    hc_set_filter_shard; ``exchange``: e.g. a ``multigpu.ShardExchange``).  member_offset must be ``bounds[index]``.
+    Needs filter_stride; like enkf_shard it is set up by the run.
     """
 
     def __init__(self, cols, forcing, n_members, seed=0, device=0, member_offset=0, psi0=None, flags=None,
                  noise="philox", spinup="shared", profile_stride=0, wtd_hist_stride=0, filter_stride=0,
                  filter_sigma_cm=None, filter_seed=None, enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0,
                  enkf_seed=None, enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0,
-                 enkf_window_offsets=(), enkf_shard=None):
-        if enkf_shard is not None:
+                 enkf_window_offsets=(), enkf_shard=None, filter_shard=None):
+        if filter_shard is not None and not int(filter_stride or 0):
+            raise ValueError("filter_shard needs the particle filter (filter_stride > 0)")
+        if enkf_shard is not None or filter_shard is not None:
             from . import _lib
             _lib.load(with_torch=True)             # torch before the library: the shard's buffer is a torch tensor
         self._start(cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup)
@@ -275,6 +281,11 @@ class EnsembleSimulation(_Run):
             n_global, exchange = enkf_shard
             self.stepper.set_enkf_shard(n_global, self.member_offset, exchange)      # (after the sensors and the window)
             self.enkf_shard = (int(n_global), self.member_offset)
+        self.filter_shard = None
+        if filter_shard is not None:
+            bounds, index, exchange = filter_shard
+            self.stepper.set_filter_shard(bounds, index, exchange)
+            self.filter_shard = self.stepper.filter_shard
 
     def _start(self, cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup):
         if noise not in ("philox", "numpy") or spinup not in ("shared", "member"):

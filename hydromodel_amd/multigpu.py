@@ -10,6 +10,9 @@ a GPU, never a re-exec -- and every rank runs its share with no communication wh
   per-row water-table moments ``[3][T]`` ends the run (RCCL over xGMI with the nccl backend); with a sharded EnKF
   (``"EnKF": {"Sharded": true}``) the members are dealt in whole tiles (:func:`shard_tiles`) and every analysis gathers
   the ranks' tile partials before each of its reductions (:class:`ShardExchange`), so the analyses are the one-rank run's;
+  with a sharded particle filter (``"Filter": {"Sharded": true}``) the members are dealt by :func:`shard`, every
+  assimilation gathers the members' water-table indices and then moves the columns whose ancestor lives on another rank
+  (:meth:`ShardExchange.route`), so the resampled ensemble is the one-rank run's;
 * sweep (BASELINE config 5): whole points are dealt round-robin (``ensemble.deal_points``); every rank places ITS points
   in zeroed ``[P][3][T]`` / ``[P][D]`` / ``[P]`` tables and one all-reduce each assembles them (:func:`place_points`: float64
   tables travel as their int64 bits, so the assembled file holds every point's bits exactly as the rank that ran it
@@ -130,16 +133,19 @@ def shard_tiles(n_members, rank, world, tile=256):
 
 
 class ShardExchange:
-    """The gather of a sharded EnKF analysis over the ranks (``EnsembleStepper.set_enkf_shard``'s ``exchange``): called
+    """The gather of a sharded EnKF analysis over the ranks (``EnsembleStepper.set_enkf_shard``'s ``exchange``; also the
+    index gather of a sharded particle filter, ``set_filter_shard``, whose column exchange is :meth:`route`): called
     with ``block``, a float64 tensor whose words [first, first + count) are this rank's, it returns with every other
     rank's words in place.  The ranks' blocks differ in size (and one rank alone contributes the point's first member),
     so each call first gathers the (first, count) pairs and pads the blocks to the largest: one regular all-gather.  Copies
     only: every bit arrives as it was written.  nccl gathers on the device tensor; gloo (ranks sharing a card in a
     rehearsal, CPU tensors in a test) stages through the host.  One rank: the identity."""
 
-    def __init__(self, ranks):
+    def __init__(self, ranks, padded=False):
         self.ranks = ranks
         self.calls = 0
+        self.routes, self.routed_words = 0, 0          # route() calls, and the words this rank sent in them
+        self.padded = padded
 
     def __call__(self, block, first, count):
         import torch
@@ -167,6 +173,53 @@ class ShardExchange:
                 block[f:f + c] = parts[r][:c].to(block.device)
         if block.is_cuda:
             torch.cuda.synchronize(block.device)          # in place before the library's stream reads it
+
+    def route(self, send, send_words, recv, recv_words):
+        """The column exchange of a sharded particle-filter assimilation (``EnsembleStepper.set_filter_shard``): a variable
+        all-to-all of float64 words.  ``send`` holds this rank's blocks for the ranks one after the other,
+        ``send_words[r]`` words for rank r; on return ``recv`` holds the blocks from them, ``recv_words[r]`` words from
+        rank r.  Both ends derived the counts from the same ancestor table, so none travels.  nccl: on the device tensors;
+        gloo: staged through the host.  ``padded``: the same exchange for a gloo without a variable all-to-all -- the
+        counts gathered, then one all-gather of the send regions padded to the longest."""
+        import torch
+        self.routes += 1
+        self.routed_words += int(sum(send_words))
+        dist, world, me = self.ranks.dist, self.ranks.world, self.ranks.rank
+        out, back = [int(v) for v in send_words], [int(v) for v in recv_words]
+        if len(out) != world or len(back) != world or out[me] or back[me]:
+            raise RuntimeError(f" Filter shard routing: counts {out} / {back} do not belong to rank {me} of {world}.")
+        if send.numel() != sum(out) or recv.numel() != sum(back):
+            raise RuntimeError(f" Filter shard routing: regions of {send.numel()} / {recv.numel()} words, counts {out} / {back}.")
+        if dist is None or world == 1:
+            return
+        if self.ranks.backend == "nccl":
+            dist.all_to_all_single(recv, send, back, out)
+            torch.cuda.synchronize(recv.device)
+            return
+        host_in, host_out = send.cpu(), torch.empty(recv.numel(), dtype=torch.float64)
+        if not self.padded:
+            dist.all_to_all_single(host_out, host_in, back, out)
+        else:
+            counts = torch.tensor(out, dtype=torch.int64)
+            table = [torch.zeros_like(counts) for _ in range(world)]
+            dist.all_gather(table, counts)
+            table = [[int(v) for v in t.tolist()] for t in table]
+            if [table[r][me] for r in range(world)] != back:
+                raise RuntimeError(f" Filter shard routing: rank {me} expects {back}, the ranks send {table}.")
+            widest = max(sum(t) for t in table)
+            if widest:
+                mine = torch.zeros(widest, dtype=torch.float64)
+                mine[:host_in.numel()] = host_in
+                parts = [torch.empty_like(mine) for _ in range(world)]
+                dist.all_gather(parts, mine)
+                at = 0
+                for r in range(world):
+                    skip = sum(table[r][:me])
+                    host_out[at:at + back[r]] = parts[r][skip:skip + back[r]]
+                    at += back[r]
+        recv.copy_(host_out)
+        if recv.is_cuda:
+            torch.cuda.synchronize(recv.device)
 
 
 def place_points(local, point_ids, n_points, ranks=None):

@@ -83,6 +83,7 @@ class EnsembleStepper:
         self.enkf_window_offsets = ()
         self.device = int(device)
         self.enkf_shard, self._shard_keep, self._shard_error = None, None, None
+        self.filter_shard, self._filter_shard_keep = None, None
         if profile_stride:
             self.set_profile_stats(profile_stride)
 
@@ -173,7 +174,8 @@ class EnsembleStepper:
             a.diag_out = L.dptr(out["diag"])
         rc = self.lib.hc_step_rows(self.h, C.byref(a))
         failure, self._shard_error = self._shard_error, None
-        if rc and failure is not None:             # the shard's exchange raised inside the call (set_enkf_shard)
+        if rc and failure is not None:             # the shard's exchange raised inside the call (set_enkf_shard,
+            #                                            set_filter_shard)
             raise L.HcError(f"libhydrocol status {rc}: {self.lib.hc_last_error().decode()}") from failure
         L.check(rc)
         if want_stats:
@@ -337,6 +339,7 @@ class EnsembleStepper:
             raise ValueError(f"filter sigma_cm = {sigma_cm!r} must be finite and > 0")
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = 0, 0.0, 0   # hc_set_filter turns it off first,
         #                                                                            and leaves it off if it refuses
+        self.filter_shard, self._filter_shard_keep = None, None                  # ... and the sharding with it
         L.check(self.lib.hc_set_filter(self.h, stride, sigma, int(seed) & 0xFFFFFFFFFFFFFFFF))
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = stride, sigma, int(seed)
 
@@ -348,6 +351,7 @@ class EnsembleStepper:
         self.enkf_method, self.enkf_relaxation = "stochastic", 0.0
         self.enkf_window_offsets = ()
         self.enkf_shard = None
+        self.filter_shard, self._filter_shard_keep = None, None
 
     def filter_table(self):
         """[P][n_arow][4] float64: count, ESS, log-likelihood increment, survivors per assimilation slot (slot j <-> row
@@ -373,7 +377,8 @@ class EnsembleStepper:
         L.check(self.lib.hc_set_filter_base(self.h, L.dptr(base)))
 
     def filter_ancestors(self):
-        """[N] int64: the handle-local member each slot took its state from at the last assimilation (test hook)."""
+        """[N] int64: the handle-local member each slot took its state from at the last assimilation (test hook); with
+        :meth:`set_filter_shard` the global member id."""
         out = np.zeros(self.N, dtype=np.int64)
         L.check(self.lib.hc_get_filter_ancestors(self.h, L.lptr(out)))
         return out
@@ -389,6 +394,74 @@ class EnsembleStepper:
         out = np.zeros(self.P, dtype=np.int64)
         L.check(self.lib.hc_get_filter_draw(self.h, L.lptr(out)))
         return out
+
+    # -- one point's members on several handles, particle filter (include/hydrocol.h hc_set_filter_shard) ----------------
+    def filter_shard_words(self, bounds, index):
+        """8-byte words the shard's buffer must hold: the index vector, the send and the receive region."""
+        b = np.ascontiguousarray(bounds, dtype=np.int64)
+        n = np.zeros(1, dtype=np.int64)
+        L.check(self.lib.hc_get_filter_shard_words(self.h, b.size - 1, L.lptr(b), int(index), L.lptr(n)))
+        return int(n[0])
+
+    def set_filter_shard(self, bounds, index=0, exchange=None):
+        """This handle is shard ``index`` of a point whose members are split at ``bounds`` (``[0, b_1, ..., n_global]``):
+        the handles' assimilations together become the whole ensemble's, to the bit.  Per assimilation the library calls
+        ``exchange(block, first_word, count_words)`` -- ``block`` a float64 device tensor of n_global words holding 8-byte
+        integers, of which [first_word, first_word + count_words) are this handle's; on return everyone else's must be in
+        place -- and then ``exchange.route(send, send_words, recv, recv_words)``: ``send`` holds the blocks for the other
+        shards one after the other, ``send_words[s]`` words for shard s, and on return ``recv`` must hold the blocks from
+        them, ``recv_words[s]`` words from shard s (:class:`multigpu.ShardExchange`; None: nothing to exchange, for a
+        handle that holds every member).  The words are bit patterns: copy them, nothing else.  An exception either call
+        raises fails the step.  ``bounds`` = None turns sharding off.  The particle filter comes first.  torch must have
+        been imported before this process made its first handle (``_lib.load``)."""
+        self._filter_shard_keep = None
+        if bounds is None:
+            L.check(self.lib.hc_set_filter_shard(self.h, 0, None, 0, None, 0, L.EXCHANGE_FN(), L.ROUTE_FN(), None))
+            self.filter_shard = None
+            return
+        b = np.ascontiguousarray(bounds, dtype=np.int64).reshape(-1)
+        n_shards, index = b.size - 1, int(index)
+        L.load(with_torch=True)                    # the buffer is torch's: one HIP runtime must serve both
+        import torch
+        self.filter_shard = None
+        buf = torch.zeros(max(self.filter_shard_words(b, index), 1), dtype=torch.float64,
+                          device=torch.device("cuda", self.device))
+        base = buf.data_ptr()
+
+        def view(ptr, n_words):
+            at = (int(ptr) - base) // 8
+            return buf[at:at + n_words]
+
+        def gather(_ctx, ptr, n_words, first_word, count_words):
+            try:                                   # nothing may propagate through the C frames
+                if exchange is not None:
+                    exchange(view(ptr, n_words), int(first_word), int(count_words))
+                return 0
+            except BaseException as e:  # noqa: BLE001
+                self._shard_error = e
+                return 1
+
+        def route(_ctx, send, send_words, recv, recv_words):
+            try:
+                if exchange is not None:
+                    out, back = [int(send_words[s]) for s in range(n_shards)], [int(recv_words[s]) for s in range(n_shards)]
+                    exchange.route(view(send, sum(out)), out, view(recv, sum(back)), back)
+                return 0
+            except BaseException as e:  # noqa: BLE001
+                self._shard_error = e
+                return 1
+
+        fns = (L.EXCHANGE_FN(gather), L.ROUTE_FN(route))
+        L.check(self.lib.hc_set_filter_shard(self.h, n_shards, L.lptr(b), index, C.c_void_p(base), buf.numel(), fns[0],
+                                             fns[1], None))
+        self._filter_shard_keep = (buf, fns, gather, route)        # alive as long as the handle may call them
+        self.filter_shard = (tuple(int(v) for v in b), index)
+
+    def get_filter_shard(self):
+        """(n_shards, index, n_global) as the library holds them; (0, 0, 0): off."""
+        n, i, g = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int64)
+        L.check(self.lib.hc_get_filter_shard(self.h, L.iptr(n), L.iptr(i), L.lptr(g)))
+        return int(n[0]), int(i[0]), int(g[0])
 
     # -- ensemble Kalman filter on the well's water table (include/hydrocol.h hc_set_enkf) ------------------------------
     def set_enkf(self, stride, sigma_cm=None, localisation_cm=0.0, seed=0):
@@ -874,6 +947,24 @@ def filter_ancestors_of(q_members, r):
     for m, (k0, k1) in enumerate(filter_slot_ranges(q_members, r)):
         anc[k0:k1] = m
     return anc
+
+
+def filter_routes(ancestors, bounds):
+    """The columns a sharded resampling moves (include/hydrocol.h hc_set_filter_shard), restated with NumPy:
+    ``(send, recv)`` with ``send[s][d]`` = the global ids of the members shard s sends to shard d -- the distinct ancestors
+    of d's slots [bounds[d], bounds[d + 1]) that lie in s's range, ascending; empty for d = s -- and ``recv[d][s]`` the
+    same list seen from the receiver.  ``ancestors`` [n_global]: the global ancestor of every slot."""
+    anc = np.asarray(ancestors, dtype=np.int64)
+    b = [int(v) for v in bounds]
+    S = len(b) - 1
+    send = [[np.zeros(0, dtype=np.int64) for _ in range(S)] for _ in range(S)]
+    for d in range(S):
+        mine = np.unique(anc[b[d]:b[d + 1]])
+        for s in range(S):
+            if s != d:
+                send[s][d] = mine[(mine >= b[s]) & (mine < b[s + 1])]
+    recv = [[send[s][d] for s in range(S)] for d in range(S)]
+    return send, recv
 
 
 def filter_summary(table, stride, sigma_cm):

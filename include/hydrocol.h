@@ -52,6 +52,9 @@
  *   hc_set_enkf_window, hc_get/set_enkf_window_stats, hc_get/set_enkf_window_capture, hc_get_enkf_width,
  *   hc_get_enkf_window_width/y/eps/gain
  *                      <- (new) the well's record at rows inside the analysis window joins the analysis (asynchronous EnKF)
+ *   hc_set/get_enkf_shard, hc_get_enkf_shard_words, hc_set/get_filter_shard, hc_get_filter_shard_words
+ *                      <- (new) one point's members on several handles: the EnKF's analyses and the particle filter's
+ *                         resampling are those of the one handle that holds every member
  *
  * Conventions: every function returns 0 on success or a negative hc_status; nothing throws
  * or aborts across the boundary; hc_last_error() gives the thread-local message.  Host
@@ -362,8 +365,8 @@ int hc_wtd_distribution(int device, const int32_t *hist, const int32_t *obs_idx,
  *   the damping: set scales and do spin-ups before hc_set_filter) and hc_get_noise_scale no longer follows the run.
  * hc_get/set_filter_stats: the table (P n_arow 4 entries; checkpoints, the assembly of a sweep over ranks).
  * hc_get/set_filter_base: the device base vectors [n_members][D] of a filtered Philox run (resume).
- * Test hooks of the last assimilation: ancestors [n_members] int64 (handle-local member index of each slot's ancestor),
- *   weights [P][D] int64 (q_b), draw [P] int64 (r). */
+ * Test hooks of the last assimilation: ancestors [n_members] int64 (handle-local member index of each slot's ancestor;
+ *   hc_set_filter_shard: the global one), weights [P][D] int64 (q_b), draw [P] int64 (r). */
 int hc_set_filter(hc_handle *h, int32_t stride, double sigma_cm, uint64_t seed);
 int hc_get_filter_stats(hc_handle *h, double *table, int64_t n_entries);
 int hc_set_filter_stats(hc_handle *h, const double *table, int64_t n_entries);
@@ -597,6 +600,52 @@ int hc_get_enkf_shard_words(hc_handle *h, int64_t n_global, int64_t *n_words);
 int hc_set_enkf_shard(hc_handle *h, int64_t n_global, int64_t first_global, void *device_buf, int64_t n_words,
                       hc_enkf_exchange_fn fn, void *ctx);
 int hc_get_enkf_shard(hc_handle *h, int64_t *n_global, int64_t *first_global);
+
+/* One point's members on several handles, particle filter: the handle is shard `index` of n_shards and holds members
+ * [b_index, b_index+1) of a point with n_global = b_S members, bounds b_0 = 0 < b_1 < ... < b_S (any bounds: no alignment,
+ * a shard of one member is legal).  The handles' assimilations together are the assimilation of the one handle that
+ * holds every member, to the bit: states, base noise vectors, the diagnostics table, weights, draw and ancestry.
+ * Everything the ancestry depends on is an integer function of the members' water-table indices on the row, and
+ * systematic resampling is monotone -- the ancestor of slot k is non-decreasing in k -- so a shard's slots need an
+ * ordered run of ancestors, and two shards' runs share at most one member.
+ *   Order at an assimilation row, after the row is solved and the tables have accumulated the forecast:
+ *   1. the handle writes its members' water-table indices as 8-byte integers at words [b_index, b_index+1) of device_buf,
+ *      drains its stream and calls gather(ctx, device_buf, n_global, b_index, n_members); on return (0 = ok) every other
+ *      handle's words must be in place and visible on the device (a copy);
+ *   2. the kernels of hc_set_filter run over the gathered vector with N_p = n_global; the draw's key is the point's first
+ *      global member id (hc_set_noise_philox: member_offset - b_index = 0; host noise: member_offset as it stands).  Every
+ *      handle obtains the same q_b, Q, r, diagnostics row (count = n_global) and ancestor table anc[n_global];
+ *   3. from anc and the bounds alone the handle derives, per other shard s, the members it receives from s -- the distinct
+ *      ancestors of its own slots that lie in [b_s, b_s+1), ascending -- and the members it sends to s -- the distinct
+ *      ancestors of s's slots that lie in its own range, ascending; both ends derive the same lists, none travels.  It
+ *      packs, per destination in shard order and per listed member, psi[D] then the base noise vector [D] (2 D words)
+ *      into the send region, drains its stream and calls route(ctx, send, send_words, recv, recv_words): send_words[s] /
+ *      recv_words[s] = the 8-byte words for / from shard s (0 for s = index), the blocks contiguous in shard order from
+ *      `send` / `recv` (both inside device_buf).  On return (0 = ok) the block of every source must be in the receive
+ *      region and visible on the device (a copy: the words are bit patterns);
+ *   4. slot k takes psi and base from the handle's own member anc[k] - b_index, or from the receive region.
+ *   Both callbacks are called once per assimilation on every handle, also when nothing is routed (equal weights, Q = 0:
+ *   the ancestry is the identity), so the handles' calls pair up.  All handles of a point must assimilate the same rows
+ *   with the same settings.  A non-zero return of either callback fails hc_step_rows with HC_ERR_DEVICE (the states are
+ *   then unusable).  No floating-point arithmetic on this path.  Sensors are not part of the particle filter; a sweep's
+ *   points are dealt whole.
+ * hc_get_filter_shard_words: what device_buf must hold, in 8-byte words: the index vector n_global, the send region
+ *   (n_members + n_shards - 1) 2 D and the receive region n_members 2 D (monotonicity bounds both).
+ * hc_set_filter_shard: device_buf is caller-owned memory on the handle's device, alive while the shard is set.  Needs the
+ *   particle filter on; HC_ERR_ARG for more than one point on the handle, bounds that do not start at 0 or do not increase
+ *   strictly, index outside [0, n_shards), n_members != b_index+1 - b_index, n_global > 2^31 - 1, in a Philox run
+ *   member_offset != b_index (the model noise and the base vectors must be the whole ensemble's), a NULL buffer or
+ *   callback, n_words < hc_get_filter_shard_words.  A refused call leaves sharding off.  n_shards = 0 turns sharding off;
+ *   so does whatever turns the filter off, hc_set_filter itself included.  With sharding off nothing changes: the same
+ *   kernels and launches, no synchronisation.  n_shards = 1 with callbacks that do nothing gives the unsharded bits.
+ * hc_get_filter_shard: n_shards (0: off), index and n_global.
+ * While sharded, hc_get_filter_ancestors returns the GLOBAL member id of the ancestor of each of the handle's own slots
+ *   ([n_members]); weights and draw are the same on every handle. */
+typedef int (*hc_filter_route_fn)(void *ctx, void *send, const int64_t *send_words, void *recv, const int64_t *recv_words);
+int hc_get_filter_shard_words(hc_handle *h, int32_t n_shards, const int64_t *bounds, int32_t index, int64_t *n_words);
+int hc_set_filter_shard(hc_handle *h, int32_t n_shards, const int64_t *bounds, int32_t index, void *device_buf,
+                        int64_t n_words, hc_enkf_exchange_fn gather, hc_filter_route_fn route, void *ctx);
+int hc_get_filter_shard(hc_handle *h, int32_t *n_shards, int32_t *index, int64_t *n_global);
 
 /* The path's one collective inside the library, for a single process that drives several devices with
  * one handle each: every handle's moment table is replaced by the sum over all n handles (ncclAllReduce, ncclInt64,
