@@ -107,6 +107,13 @@ EXPORTS = {
     "hc_get_filter_ancestors": ([C.c_void_p, _lp], C.c_int),
     "hc_get_filter_weights": ([C.c_void_p, _lp], C.c_int),
     "hc_get_filter_draw": ([C.c_void_p, _lp], C.c_int),
+    "hc_set_filter_soil_moisture": ([C.c_void_p, C.c_int32, _ip, _dp, _dp], C.c_int),
+    "hc_get_filter_sm_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),
+    "hc_set_filter_sm_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),
+    "hc_get_filter_sm_width": ([C.c_void_p, _ip], C.c_int),
+    "hc_get_filter_member_weights": ([C.c_void_p, _lp], C.c_int),
+    "hc_get_filter_loglik": ([C.c_void_p, _dp], C.c_int),
+    "hc_get_filter_sm_theta": ([C.c_void_p, _dp], C.c_int),
     "hc_set_enkf": ([C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_uint64], C.c_int),
     "hc_get_enkf_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),
     "hc_set_enkf_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),

@@ -49,6 +49,17 @@ unknown keys, only membership of the 12 is checked):
   exchanged; the states, tables, closing lines and the file are those of the one-GPU run to the bit (``gpus`` apart); the
   filter's tables are rank 0's.  ``false`` or no key: the refusal above.  A sweep accepts and ignores the key.  Added to
   the file when the key is given: ``filter_sharded``.
+* ``"Filter": {..., "Soil_Moisture": {"Filename": "sm.csv", "Depths_cm": [30, 60, 120], "Sigma": 0.02}}``: a soil-moisture
+  record joins the well in the filter's weights (include/hydrocol.h hc_set_filter_soil_moisture): on a row with sensor
+  values every member is weighted by the joint Gaussian likelihood of the well and of theta at the sensors' nodes, so the
+  weights belong to a member and not to a 5 cm bin.  The block, its CSV and its refusals are those of ``EnKF.Soil_Moisture``
+  below.  Not together with ``"Sharded": true`` on a single-point run (the sharded filter gathers water-table indices
+  only); a sweep on any number of GPUs takes it.  Added to the file: ``filter_sm_depths_cm``, ``filter_sm_nodes``,
+  ``filter_sm_sigma`` ``[m]`` and, over the ``filter_rows`` ``[R]``, ``filter_sm_observed``, ``filter_sm_obs``,
+  ``filter_sm_prior_mean``, ``filter_sm_prior_std``, ``filter_sm_post_mean``, ``filter_sm_post_std`` ``[R][m]`` (the
+  forecast ensemble and the resampled one; NaN on rows with no sensor value; a sweep: a leading ``[P]`` axis);
+  ``filter_loglik_rows`` holds the joint increment on sensor rows, and the run ends with
+  `` [Ensemble xN] soil-moisture forecast RMSE = ... over R rows``.
 * ``"Ensemble": {..., "EnKF": {"Stride": 48, "Sigma_cm": 10.0, "Localisation_cm": 0, "Seed": s}}``: a stochastic ensemble
   Kalman filter on the well's continuous water table (include/hydrocol.h hc_set_enkf) -- on every 48th forcing row (default
   48; 0 = off) that has an observation each member's psi moves by the sample covariance with the water table, per parameter
@@ -152,6 +163,7 @@ def main(params_file=None, data_file=None, seed=None, device=0, gpus=None, _sett
             filter_settings(params["Ensemble"], n_gpus)     # so does a bad Filter block
             enkf_settings(params["Ensemble"], n_gpus)       # and a bad EnKF block
             soil_moisture_settings(params["Ensemble"], n_gpus)
+            soil_moisture_settings(params["Ensemble"], n_gpus, "Filter")
             enkf_method_settings(params["Ensemble"])
             enkf_window_settings(params["Ensemble"])
         ranks = multigpu.Ranks(expect=n_gpus if (n_gpus > 1 or multigpu.in_rank()) else None)
@@ -213,11 +225,13 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     filt = filter_settings(ens, ranks.world)
     enkf = enkf_settings(ens, ranks.world)
     sm = soil_moisture_settings(ens, ranks.world)
+    fsm = soil_moisture_settings(ens, ranks.world, "Filter")
     scheme = enkf_method_settings(ens)
     window = enkf_window_settings(ens)
     cols = ColumnTables(params, load_site_well(params))
     forcing = ForcingDigest(params, water_data, cols)
     record = soil_moisture_record_of(sm, cols, water_data)      # before any GPU call
+    frecord = soil_moisture_record_of(fsm, cols, water_data, "Filter")
     if cols.flags["PREDICT"] and not ens.get("repair_predict"):
         raise TypeError("'numpy.float64' object cannot be interpreted as an integer")     # richards_pde.py:327-330
     n_members = int(ens.get("Members", 4096))
@@ -225,7 +239,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     rows = min(days * 48, forcing.dim_t - 1)
     if ens.get("Points"):
         return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels, filt,
-                          enkf, record, scheme, window)
+                          enkf, record, scheme, window, frecord)
     sharded = enkf_sharded(ens)
     fsharded = filter_sharded(ens)
     if sharded:
@@ -246,8 +260,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     sim = EnsembleSimulation(cols, forcing, hi - lo, seed=int(ens.get("Seed", 0)), device=device, member_offset=lo,
                              noise=str(ens.get("Noise", "philox")).lower(),
                              spinup=str(ens.get("Spinup", "shared")).lower(), profile_stride=stride,
-                             wtd_hist_stride=dist_stride, **_filter_kwargs(filt), **_enkf_kwargs(enkf, record, scheme, window),
-                             **shard_kw)
+                             wtd_hist_stride=dist_stride, **_filter_kwargs(filt, frecord),
+                             **_enkf_kwargs(enkf, record, scheme, window), **shard_kw)
     label = f"Ensemble x{n_members}"
     _step_all(sim, rows, label, ranks)
     # the run's one collective: int64 (count, sum idx, sum idx^2) per row, exact and order-independent
@@ -279,6 +293,9 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     eids = [0] if ranks.rank == 0 else []
     ftables, filter_line = _reduce_filter(ranks, sim, eids, 1, forcing.dim_t, filt, label, keep_points=False)
     extra.update(ftables)
+    fstables, fsm_line = _reduce_sm(ranks, sim, eids, 1, forcing.dim_t, filt[0], frecord, label, keep_points=False,
+                                    owner="filter")
+    extra.update(fstables)
     if fsharded is not None:
         extra["filter_sharded"] = np.array(1 if fsharded else 0, dtype=np.int8)
     etables, enkf_line = _reduce_enkf(ranks, sim, eids, 1, forcing.dim_t, enkf, label, keep_points=False,
@@ -287,7 +304,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     extra.update(_enkf_method_arrays(enkf, scheme))
     if sharded is not None:
         extra["enkf_sharded"] = np.array(1 if sharded else 0, dtype=np.int8)
-    stables, sm_line = _reduce_enkf_sm(ranks, sim, eids, 1, forcing.dim_t, enkf, record, label, keep_points=False)
+    stables, sm_line = _reduce_sm(ranks, sim, eids, 1, forcing.dim_t, enkf[0], record, label, keep_points=False)
     extra.update(stables)
     wtables, window_line = _reduce_enkf_window(ranks, sim, eids, 1, forcing.dim_t, enkf, window, label, keep_points=False,
                                                z0_cm=cols.z[0])
@@ -299,6 +316,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
         print(crps_line)
     if filter_line:
         print(filter_line)
+    if fsm_line:
+        print(fsm_line)
     if enkf_line:
         print(enkf_line)
     if sm_line:
@@ -340,7 +359,7 @@ def distribution_settings(ens):
     return (stride, tuple(float(q) for q in levels)) if stride else (0, None)
 
 
-FILTER_KEYS = ("Stride", "Sigma_cm", "Seed", "Sharded")
+FILTER_KEYS = ("Stride", "Sigma_cm", "Seed", "Sharded", "Soil_Moisture")
 
 
 def filter_settings(ens, n_gpus=1):
@@ -557,48 +576,56 @@ SM_KEYS = ("Filename", "Depths_cm", "Sigma")
 SM_MAX_DEPTHS = 8
 
 
-def soil_moisture_settings(ens, n_gpus=1):
-    """Ensemble.EnKF.Soil_Moisture -> (filename, depths_cm tuple, sigma tuple per depth), or None when absent.  Pure, like
-    :func:`enkf_settings` (which it runs first: its refusals -- a "Filter" block, one point on several GPUs -- hold): a
-    bad value is a ValueError (message + exit status 1).  Needs an active EnKF.  The depths are checked against the column
-    and the file is read later (:func:`soil_moisture_record_of`)."""
+def soil_moisture_settings(ens, n_gpus=1, owner="EnKF"):
+    """Ensemble.EnKF.Soil_Moisture (``owner`` = "Filter": Ensemble.Filter.Soil_Moisture, the same block) -> (filename,
+    depths_cm tuple, sigma tuple per depth), or None when absent.  Pure, like :func:`enkf_settings` / :func:`filter_settings`
+    (the owner's, which it runs first: its refusals -- "Filter" with "EnKF", one point on several GPUs -- hold): a bad value
+    is a ValueError (message + exit status 1).  Needs the owner active.  The filter's record is refused together with
+    ``"Sharded": true`` on a single-point run.  The depths are checked against the column and the file is read later
+    (:func:`soil_moisture_record_of`)."""
     import math
     from numbers import Real
     if "Soil_Moisture" in ens:
-        raise ValueError(" Ensemble: Soil_Moisture belongs inside the \"EnKF\" block.")
-    block = ens.get("EnKF")
+        raise ValueError(" Ensemble: Soil_Moisture belongs inside the \"EnKF\" block (or the \"Filter\" block).")
+    settings = enkf_settings if owner == "EnKF" else filter_settings
+    block = ens.get(owner)
     if not isinstance(block, dict) or block.get("Soil_Moisture") is None:
-        enkf_settings(ens, n_gpus)
+        settings(ens, n_gpus)
         return None
-    stride = enkf_settings(ens, n_gpus)[0]
+    stride = settings(ens, n_gpus)[0]
     sm = block["Soil_Moisture"]
     if not stride:
-        raise ValueError(" Ensemble: EnKF.Soil_Moisture needs an active EnKF (EnKF.Stride > 0).")
+        what = "EnKF" if owner == "EnKF" else "filter"
+        raise ValueError(f" Ensemble: {owner}.Soil_Moisture needs an active {what} ({owner}.Stride > 0).")
+    if owner == "Filter" and not ens.get("Points") and block.get("Sharded", False):
+        raise ValueError(" Ensemble: Filter.Soil_Moisture is not available with \"Sharded\": true: the sharded filter "
+                         "gathers the members' water-table indices only, and the sensors' weights need every member's "
+                         "state on one GPU (a sweep's points are dealt whole and take the record).")
     if not isinstance(sm, dict):
-        raise ValueError(f" Ensemble: EnKF.Soil_Moisture = {sm!r} must be an object such as "
+        raise ValueError(f" Ensemble: {owner}.Soil_Moisture = {sm!r} must be an object such as "
                          f"{{\"Filename\": \"sm.csv\", \"Depths_cm\": [30, 60], \"Sigma\": 0.02}}.")
     unknown = sorted(set(sm) - set(SM_KEYS))
     if unknown:
-        raise ValueError(f" Ensemble: EnKF.Soil_Moisture has unknown keys {unknown} (known: {list(SM_KEYS)}).")
+        raise ValueError(f" Ensemble: {owner}.Soil_Moisture has unknown keys {unknown} (known: {list(SM_KEYS)}).")
     name = sm.get("Filename")
     if not isinstance(name, str) or not name:
-        raise ValueError(f" Ensemble: EnKF.Soil_Moisture.Filename = {name!r} must name the sensor CSV.")
+        raise ValueError(f" Ensemble: {owner}.Soil_Moisture.Filename = {name!r} must name the sensor CSV.")
 
     def number(x):
         return not isinstance(x, bool) and isinstance(x, Real) and math.isfinite(x)
 
     depths = sm.get("Depths_cm")
     if not isinstance(depths, (list, tuple)) or not depths or not all(number(d) for d in depths):
-        raise ValueError(f" Ensemble: EnKF.Soil_Moisture.Depths_cm = {depths!r} must be a non-empty list of finite "
+        raise ValueError(f" Ensemble: {owner}.Soil_Moisture.Depths_cm = {depths!r} must be a non-empty list of finite "
                          f"depths (cm).")
     if len(depths) > SM_MAX_DEPTHS:
-        raise ValueError(f" Ensemble: EnKF.Soil_Moisture.Depths_cm has {len(depths)} depths, at most {SM_MAX_DEPTHS}.")
+        raise ValueError(f" Ensemble: {owner}.Soil_Moisture.Depths_cm has {len(depths)} depths, at most {SM_MAX_DEPTHS}.")
     if "Sigma" not in sm:
-        raise ValueError(" Ensemble: EnKF.Soil_Moisture.Sigma (the sensors' error, m^3/m^3) is required.")
+        raise ValueError(f" Ensemble: {owner}.Soil_Moisture.Sigma (the sensors' error, m^3/m^3) is required.")
     sigma = sm["Sigma"]
     sig = list(sigma) if isinstance(sigma, (list, tuple)) else [sigma] * len(depths)
     if len(sig) != len(depths) or not all(number(x) and x > 0 for x in sig):
-        raise ValueError(f" Ensemble: EnKF.Soil_Moisture.Sigma = {sigma!r} must be a finite number > 0 or one per depth "
+        raise ValueError(f" Ensemble: {owner}.Soil_Moisture.Sigma = {sigma!r} must be a finite number > 0 or one per depth "
                          f"({len(depths)}).")
     return name, tuple(float(d) for d in depths), tuple(float(x) for x in sig)
 
@@ -636,9 +663,10 @@ def read_soil_moisture_csv(path, datenum, n_depths):
     return values
 
 
-def soil_moisture_record_of(sm, cols, water_data):
-    """The EnKF's sensor record (stepper.soil_moisture_record) of the settings ``sm`` on the column ``cols``: the depths
-    mapped to nodes (refused outside the column) and the CSV read against the forcing's Datenum.  None without sensors."""
+def soil_moisture_record_of(sm, cols, water_data, owner="EnKF"):
+    """The sensor record (stepper.soil_moisture_record) of the ``owner`` block's settings ``sm`` on the column ``cols``: the
+    depths mapped to nodes (refused outside the column) and the CSV read against the forcing's Datenum.  None without
+    sensors."""
     from .stepper import sensor_nodes, soil_moisture_record
     if sm is None:
         return None
@@ -646,7 +674,7 @@ def soil_moisture_record_of(sm, cols, water_data):
     try:
         sensor_nodes(cols.z, depths)
     except ValueError as bad:
-        raise ValueError(f" Ensemble: EnKF.Soil_Moisture.Depths_cm: {bad}.") from None
+        raise ValueError(f" Ensemble: {owner}.Soil_Moisture.Depths_cm: {bad}.") from None
     if not Path(name).exists():
         raise ValueError(f" Soil moisture: the sensor file {name} does not exist.")
     values = read_soil_moisture_csv(name, water_data["Datenum"].to_numpy(), len(depths))
@@ -656,29 +684,31 @@ def soil_moisture_record_of(sm, cols, water_data):
 SM_DATASETS = ("observed", "obs", "prior_mean", "prior_std", "post_mean", "post_std")
 
 
-def _reduce_enkf_sm(ranks, sim, ids, P, T, enkf, record, label, keep_points):
-    """The sensors' datasets from this rank's handle over the EnKF's analysed rows (its ``enkf_rows``), the [P] table
-    placed and summed over the ranks like the EnKF's (float64 as int64 bits), and the closing line (rank 0)."""
+def _reduce_sm(ranks, sim, ids, P, T, stride, record, label, keep_points, owner="enkf"):
+    """The sensors' datasets (``owner``: "enkf" or "filter", the prefix of the datasets and of the handle's tables) from
+    this rank's handle over the owner's assimilated rows (its ``enkf_rows`` / ``filter_rows``), the [P] table placed and
+    summed over the ranks like the owner's (float64 as int64 bits), and the closing line (rank 0)."""
     import numpy as np
     from .multigpu import place_points
     from .stepper import ENKF_WIDTH, SM_WIDTH, enkf_sm_summary, stride_rows
-    stride = enkf[0]
     if not stride or record is None:
         return {}, None
     n = int(np.asarray(record["nodes"]).size)
     n_arow = stride_rows(T, stride)
-    local = sim.enkf_sm_table().reshape(-1, n_arow, n, SM_WIDTH) if sim is not None else np.zeros((0, n_arow, n, SM_WIDTH))
+    width = ENKF_WIDTH if owner == "enkf" else 4
+    local = (getattr(sim, owner + "_sm_table")().reshape(-1, n_arow, n, SM_WIDTH) if sim is not None
+             else np.zeros((0, n_arow, n, SM_WIDTH)))
     table = place_points(local, ids, P, ranks)
-    etab = sim.enkf_table().reshape(-1, n_arow, ENKF_WIDTH) if sim is not None else np.zeros((0, n_arow, ENKF_WIDTH))
+    etab = getattr(sim, owner + "_table")().reshape(-1, n_arow, width) if sim is not None else np.zeros((0, n_arow, width))
     used = place_points(etab, ids, P, ranks)[..., 0] > 0
-    slots = np.flatnonzero(used.any(axis=0))               # the enkf_rows of _reduce_enkf
+    slots = np.flatnonzero(used.any(axis=0))               # the enkf_rows of _reduce_enkf, the filter_rows of _reduce_filter
     sel = table[:, slots] if keep_points else table[0, slots]
-    out = {"enkf_sm_depths_cm": np.asarray(record["depths_cm"], dtype=np.float64),
-           "enkf_sm_nodes": np.asarray(record["nodes"], dtype=np.int32),
-           "enkf_sm_sigma": np.asarray(record["sigma"], dtype=np.float64)}
+    out = {f"{owner}_sm_depths_cm": np.asarray(record["depths_cm"], dtype=np.float64),
+           f"{owner}_sm_nodes": np.asarray(record["nodes"], dtype=np.int32),
+           f"{owner}_sm_sigma": np.asarray(record["sigma"], dtype=np.float64)}
     for j, k in enumerate(SM_DATASETS):
         v = sel[..., j]
-        out[f"enkf_sm_{k}"] = (v == 1.0).astype(np.int8) if k == "observed" else v
+        out[f"{owner}_sm_{k}"] = (v == 1.0).astype(np.int8) if k == "observed" else v
     summary = enkf_sm_summary(table if keep_points else table[0], stride, record["sigma"])
     if ranks.rank != 0:
         return out, None
@@ -722,9 +752,14 @@ def _reduce_enkf(ranks, sim, ids, P, T, enkf, label, keep_points, z0_cm):
     return out, line
 
 
-def _filter_kwargs(filt):
+def _filter_kwargs(filt, record=None):
     stride, sigma, seed = filt
-    return dict(filter_stride=stride, filter_sigma_cm=sigma, filter_seed=seed) if stride else {}
+    if not stride:
+        return {}
+    kw = dict(filter_stride=stride, filter_sigma_cm=sigma, filter_seed=seed)
+    if record is not None:
+        kw["filter_soil_moisture"] = record
+    return kw
 
 
 def _reduce_filter(ranks, sim, ids, P, T, filt, label, keep_points):
@@ -844,7 +879,7 @@ def _reduce_optional(ranks, sim, ids, cols_all, forcing, stride, dist_stride, di
 
 
 def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride=0, dist_levels=None,
-               filt=(0, None, None), enkf=(0, None, None, None), record=None, scheme=None, window=None):
+               filt=(0, None, None), enkf=(0, None, None, None), record=None, scheme=None, window=None, frecord=None):
     """Parameter points x members: this rank's points in one handle (ensemble.SweepSimulation), the whole table assembled
     over the ranks (multigpu.assemble_points)."""
     import numpy as np
@@ -870,7 +905,7 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     label = f"Sweep {P} points x{n_members}"
     if mine:
         sim = SweepSimulation(points, forcing, n_members, seed=int(ens.get("Seed", 0)), device=device, point_ids=mine,
-                              profile_stride=stride, wtd_hist_stride=dist_stride, **_filter_kwargs(filt),
+                              profile_stride=stride, wtd_hist_stride=dist_stride, **_filter_kwargs(filt, frecord),
                               **_enkf_kwargs(enkf, record, scheme, window))
         _step_all(sim, rows, label, ranks)
         table = sim.moments()
@@ -887,10 +922,12 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     arrays.update(tables)
     ftables, filter_line = _reduce_filter(ranks, sim, mine, P, T, filt, label, keep_points=True)
     arrays.update(ftables)
+    fstables, fsm_line = _reduce_sm(ranks, sim, mine, P, T, filt[0], frecord, label, keep_points=True, owner="filter")
+    arrays.update(fstables)
     etables, enkf_line = _reduce_enkf(ranks, sim, mine, P, T, enkf, label, keep_points=True,
                                          z0_cm=cols_all[0].z[0])
     arrays.update(etables)
-    stables, sm_line = _reduce_enkf_sm(ranks, sim, mine, P, T, enkf, record, label, keep_points=True)
+    stables, sm_line = _reduce_sm(ranks, sim, mine, P, T, enkf[0], record, label, keep_points=True)
     arrays.update(stables)
     arrays.update(_enkf_method_arrays(enkf, scheme))
     wtables, window_line = _reduce_enkf_window(ranks, sim, mine, P, T, enkf, window, label, keep_points=True,
@@ -903,6 +940,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
         print(crps_line)
     if filter_line:
         print(filter_line)
+    if fsm_line:
+        print(fsm_line)
     if enkf_line:
         print(enkf_line)
     if sm_line:
@@ -932,6 +971,7 @@ def run_cli(argv=None):
                 filter_settings(settings["Ensemble"], n_gpus)
                 enkf_settings(settings["Ensemble"], n_gpus)
                 soil_moisture_settings(settings["Ensemble"], n_gpus)
+                soil_moisture_settings(settings["Ensemble"], n_gpus, "Filter")
                 enkf_method_settings(settings["Ensemble"])
                 enkf_window_settings(settings["Ensemble"])
             except ValueError as bad:

@@ -176,6 +176,20 @@ struct hc_handle {
     DevBuf<unsigned long long> filt_qr, filt_surv;
     std::vector<long long> filt_rows_host;
     std::vector<int> h_wtd_obs;
+    // soil-moisture sensors in the particle filter (hc_set_filter_soil_moisture): the record on the host, as the EnKF's;
+    // diagnostics float64 [P][n_arow][fsm_n][6] keyed like the filter's; fsm_width = the last assimilation's m_s, 0 =
+    // it took the bin path.  Per member (the last assimilation: test hooks) the weight q_m and the row (l_m, theta of
+    // the present sensors, exp(l_m - s)); per point and tile of FILT_TILE members the largest l_m, the integer sums
+    // (Q, sum q^2 in two words, count) and the partials of the column sums; per point s and the columns' sums and means
+    int fsm_n = 0;               // 0: no record
+    int64_t fsm_rows = 0;
+    std::vector<int> fsm_nodes;
+    std::vector<double> fsm_sigma, fsm_values;
+    int fsm_width = 0;
+    AccTable<double> fsm{"entries"};
+    DevBuf<long long> filt_qm;
+    DevBuf<double> filt_Y, filt_lmax, filt_part, filt_sums;
+    DevBuf<unsigned long long> filt_ipart;
     // one point's members on several handles (hc_set_filter_shard): the shard count (0: off), this handle's index and the
     // bounds b_0 = 0 < ... < b_S = n_global, on the host and on the device; the caller's buffer -- the gathered
     // water-table indices [n_global], the send region [(n + S - 1) 2 D] and the receive region [n 2 D], in 8-byte
@@ -603,6 +617,33 @@ __device__ __forceinline__ unsigned long long filter_philox64(unsigned long long
     return ((unsigned long long)r[1] << 32) | r[0];
 }
 
+// ESS = Q^2 / sum q_m^2 (the sum in two 64-bit words): both exact, the quotient from a double-double correction (within
+// 2 ulp)
+__device__ __forceinline__ double filter_ess(unsigned long long Q, unsigned long long b_hi, unsigned long long b_lo)
+{
+#pragma clang fp contract(off)
+    double a_hi, a_lo, d_hi, d_lo;
+    u128_to_dd(__umul64hi(Q, Q), Q * Q, a_hi, a_lo);
+    u128_to_dd(b_hi, b_lo, d_hi, d_lo);
+    const double q1 = a_hi / d_hi;
+    const double rr = fma(-q1, d_hi, a_hi) + a_lo - q1 * d_lo;
+    return q1 + rr / d_hi;
+}
+
+// point p's draw: qr[p] = {Q, r} with r = floor(x Q / 2^64) < Q, x the Philox value under the point's key; the
+// survivors' counter cleared
+__device__ __forceinline__ void filter_draw(unsigned long long seed, const long long *point_base, long long member_offset,
+                                            long long p, long long members_per_point, unsigned row, unsigned long long Q,
+                                            unsigned long long *qr, unsigned long long *surv)
+{
+    const unsigned long long key = point_base ? (unsigned long long)point_base[p]
+                                              : (unsigned long long)(member_offset + p * members_per_point);
+    const unsigned long long x = filter_philox64(seed, key, row);
+    qr[2 * p] = Q;
+    qr[2 * p + 1] = __umul64hi(x, Q);
+    surv[p] = 0;
+}
+
 // One block per point: bin counts n_b of the assimilation row's water-table indices (grouped by ballots as in
 // wtd_hist_kernel), then one thread forms s, q_b, W, the exact sums of the ESS, the increment and the draw.
 // qr[p] = {Q, r}; stats row = {count, ESS, increment, survivors (written by filter_fill_kernel's finish)}.
@@ -662,33 +703,31 @@ __global__ __launch_bounds__(FILT_THREADS) void filter_weights_kernel(
         double *st = stats + ((size_t)p * n_arow + slot) * 4;
         st[0] = (double)n;
         if (n > 0 && Q > 0) {
-            // ESS = Q^2 / sum n_b q_b^2: both exact, the quotient from a double-double correction (within 2 ulp)
-            double a_hi, a_lo, d_hi, d_lo;
-            u128_to_dd(__umul64hi(Q, Q), Q * Q, a_hi, a_lo);
-            u128_to_dd(b_hi, b_lo, d_hi, d_lo);
-            const double q1 = a_hi / d_hi;
-            const double rr = fma(-q1, d_hi, a_hi) + a_lo - q1 * d_lo;
-            st[1] = q1 + rr / d_hi;
+            st[1] = filter_ess(Q, b_hi, b_lo);
             st[2] = s + log(W / (double)n) - log(sigma) - 0.5 * log(2.0 * M_PI);
         } else {
             st[1] = __builtin_nan("");
             st[2] = __builtin_nan("");
         }
-        const unsigned long long key = point_base ? (unsigned long long)point_base[p]
-                                                  : (unsigned long long)(member_offset + p * members_per_point);
-        const unsigned long long x = filter_philox64(seed, key, row);
-        qr[2 * p] = Q;
-        qr[2 * p + 1] = __umul64hi(x, Q);                      // r = floor(x Q / 2^64) < Q
-        surv[p] = 0;
+        filter_draw(seed, point_base, member_offset, p, members_per_point, row, Q, qr, surv);
     }
     __syncthreads();
     for (int b = threadIdx.x; b < D; b += FILT_THREADS) q_out[(size_t)p * D + b] = qsh[b];
 }
 
+// q_m of member k (handle-local) = q_{b_m} from the point's bin table q; w == NULL: the per-member weights of a sensor row
+// (filter_member_weights_kernel), q being the handle's vector [n_members] then (filter_point_q)
 __device__ __forceinline__ long long filter_q(const unsigned short *w, const long long *q, int D, long long k)
 {
+    if (!w) return q[k];
     const int b = (int)w[k];
     return b < D ? q[b] : 0;
+}
+
+// the table filter_q reads for point p: its row of the bin table [P][D], or the per-member vector as a whole
+__device__ __forceinline__ const long long *filter_point_q(const unsigned short *w, const long long *q_all, int D, long long p)
+{
+    return w ? q_all + (size_t)p * D : q_all;
 }
 
 // inclusive wave64 scan of one value per lane (shuffles), then the block's exclusive offsets through LDS
@@ -719,7 +758,7 @@ __global__ __launch_bounds__(FILT_THREADS) void filter_tile_sum_kernel(const uns
                                                                        long long *tiles)
 {
     const long long p = blockIdx.y, t = blockIdx.x;
-    const long long *q = q_all + (size_t)p * D;
+    const long long *q = filter_point_q(w, q_all, D, p);
     const long long first = p * members_per_point, m0 = t * FILT_TILE;
     long long v = 0;
     for (int j = 0; j < FILT_PER_THREAD; j++) {
@@ -762,7 +801,7 @@ __global__ __launch_bounds__(FILT_THREADS) void filter_fill_kernel(const unsigne
                                                                    long long *anc, unsigned long long *surv)
 {
     const long long p = blockIdx.y, t = blockIdx.x;
-    const long long *q = q_all + (size_t)p * D;
+    const long long *q = filter_point_q(w, q_all, D, p);
     const long long first = p * members_per_point, m0 = t * FILT_TILE + (long long)threadIdx.x * FILT_PER_THREAD;
     const unsigned long long Q = qr[2 * p], r = qr[2 * p + 1], Np = (unsigned long long)members_per_point;
     long long qm[FILT_PER_THREAD], v = 0;
@@ -1668,6 +1707,265 @@ __global__ void enkf_post_kernel(const double *s1, const double *s2, long long n
     }
 }
 
+// ---- soil-moisture sensors in the particle filter (hc_set_filter_soil_moisture, include/hydrocol.h)
+// A row with sensor values weighs every member by itself.  Y [N][m_s + 2] holds per member l_m, theta at the nodes of the
+// present sensors (enkf_theta_kernel writes columns 1 ... m_s) and e_m = exp(l_m - s).  A block is one tile of the prefix
+// scan: FILT_THREADS threads with FILT_PER_THREAD consecutive members each.  Every floating-point sum over a point's
+// members runs in the one order of filter_tile_partial_kernel and filter_column_sum -- fixed by N_p alone, no
+// floating-point atomics; maxima and integer sums do not depend on an order.  Contraction is off throughout.
+constexpr int FILT_COLS = ENKF_SENSORS + 1;            // the columns summed: theta of the present sensors, then e
+
+// the largest v of the block's threads (every thread gets it)
+__device__ double filter_block_max(double v)
+{
+    __shared__ double sh[FILT_THREADS];
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = FILT_THREADS / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] = sh[threadIdx.x + o] > sh[threadIdx.x] ? sh[threadIdx.x + o] : sh[threadIdx.x];
+        __syncthreads();
+    }
+    const double r = sh[0];
+    __syncthreads();
+    return r;
+}
+
+// a member is counted when its water table lies in the column and its log-likelihood is finite
+__device__ __forceinline__ bool filter_counted(int b, int D, double l) { return b < D && isfinite(l); }
+
+// Y[m][0] = l_m = -0.5 (t_w^2 + sum over the present sensors, in record order, of ((theta_m,i - theta_obs,i) / sigma_i)^2)
+// with the well's t_w = dz (b_m - o) / sigma_cm; lmax[p][t] = the largest l_m of the tile's counted members (-inf: none)
+__global__ __launch_bounds__(FILT_THREADS) void filter_loglik_kernel(const unsigned short *w, long long members_per_point,
+                                                                     int D, int obs, double dz, double sigma,
+                                                                     const EnkfRow s, double *Y, long long n_tiles,
+                                                                     double *lmax)
+{
+#pragma clang fp contract(off)
+    const long long p = blockIdx.y, t = blockIdx.x;
+    const int width = s.ms + 2;
+    double best = -INFINITY;
+    for (int j = 0; j < FILT_PER_THREAD; j++) {
+        const long long m = t * FILT_TILE + (long long)threadIdx.x * FILT_PER_THREAD + j;
+        if (m >= members_per_point) continue;
+        const size_t k = (size_t)(p * members_per_point + m);
+        const int b = (int)w[k];
+        double *y = Y + k * width;
+        const double tw = dz * (double)(b - obs) / sigma;
+        double a = tw * tw;
+        for (int i = 0; i < s.ms; i++) {
+            const double u = (y[1 + i] - s.obs[i]) / s.sigma[i];
+            a += u * u;
+        }
+        const double l = -0.5 * a;
+        y[0] = l;
+        if (filter_counted(b, D, l)) best = l > best ? l : best;
+    }
+    best = filter_block_max(best);
+    if (threadIdx.x == 0) lmax[(size_t)p * n_tiles + t] = best;
+}
+
+// s = the largest lmax[p][.]; per member e_m = exp(l_m - s) -> Y[m][ms + 1] and q_m = floor(2^31 e_m) -> qm[m] (0 and 0
+// for a member that is not counted); ipart[p][t] = the tile's {sum q, sum q^2 low word, high word, members counted};
+// smax[p] = s
+__global__ __launch_bounds__(FILT_THREADS) void filter_member_weights_kernel(const unsigned short *w,
+                                                                             long long members_per_point, int D, int ms,
+                                                                             long long n_tiles, const double *lmax,
+                                                                             double *Y, long long *qm,
+                                                                             unsigned long long *ipart, double *smax)
+{
+#pragma clang fp contract(off)
+    __shared__ unsigned long long part[FILT_THREADS / WAVE][4];
+    const long long p = blockIdx.y, t = blockIdx.x;
+    const int width = ms + 2;
+    double s = -INFINITY;
+    for (long long u = threadIdx.x; u < n_tiles; u += FILT_THREADS) {
+        const double v = lmax[(size_t)p * n_tiles + u];
+        s = v > s ? v : s;
+    }
+    s = filter_block_max(s);
+    unsigned long long Q = 0, hi = 0, lo = 0, n = 0;
+    for (int j = 0; j < FILT_PER_THREAD; j++) {
+        const long long m = t * FILT_TILE + (long long)threadIdx.x * FILT_PER_THREAD + j;
+        if (m >= members_per_point) continue;
+        const size_t k = (size_t)(p * members_per_point + m);
+        double *y = Y + k * width;
+        double e = 0.0;
+        long long q = 0;
+        if (filter_counted((int)w[k], D, y[0])) {
+            e = exp(y[0] - s);
+            q = (long long)floor(0x1p31 * e);                  // 2^31 at the likeliest member, 0 below ~2^-31
+            n++;
+        }
+        y[ms + 1] = e;
+        qm[k] = q;
+        const unsigned long long uq = (unsigned long long)q;
+        Q += uq;                                               // < 2^31 members x 2^31
+        add_u128(hi, lo, 0ull, uq * uq);                       // each < 2^62
+    }
+    for (int o = WAVE / 2; o > 0; o >>= 1) {
+        const unsigned long long ohi = __shfl_xor(hi, o), olo = __shfl_xor(lo, o);
+        add_u128(hi, lo, ohi, olo);
+        Q += __shfl_xor(Q, o);
+        n += __shfl_xor(n, o);
+    }
+    const int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
+    if (lane == 0) {
+        part[wave][0] = Q;
+        part[wave][1] = lo;
+        part[wave][2] = hi;
+        part[wave][3] = n;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        Q = n = hi = lo = 0;
+        for (int u = 0; u < FILT_THREADS / WAVE; u++) {
+            Q += part[u][0];
+            add_u128(hi, lo, part[u][2], part[u][1]);
+            n += part[u][3];
+        }
+        unsigned long long *out = ipart + ((size_t)p * n_tiles + t) * 4;
+        out[0] = Q;
+        out[1] = lo;
+        out[2] = hi;
+        out[3] = n;
+        if (t == 0) smax[p] = s;
+    }
+}
+
+// partial[p][t][c] = the sum over tile t of point p of f(Y[src][col0 + c]), c < n_cols.  src = the member itself, or (anc)
+// the ancestor of the slot; f(x) = x, or (mean) (x - mean[p][c])^2.  The order: every thread its FILT_PER_THREAD
+// consecutive members, in member order from 0.0; then the block's FILT_THREADS threads in a tree of halving strides
+// (thread i takes thread i + 128's, then i + 64's, ...).  Members past the point's end add 0.0.
+__global__ __launch_bounds__(FILT_THREADS) void filter_tile_partial_kernel(const double *Y, int width, int col0, int n_cols,
+                                                                           const long long *anc, const double *mean,
+                                                                           long long members_per_point, long long n_members,
+                                                                           long long n_tiles, double *partial)
+{
+#pragma clang fp contract(off)
+    __shared__ double sh[FILT_THREADS];
+    const long long p = blockIdx.y, t = blockIdx.x;
+    long long src[FILT_PER_THREAD];
+    for (int j = 0; j < FILT_PER_THREAD; j++) {
+        const long long m = t * FILT_TILE + (long long)threadIdx.x * FILT_PER_THREAD + j;
+        src[j] = -1;
+        if (m < members_per_point) {
+            const long long k = p * members_per_point + m, a = anc ? anc[k] : k;
+            src[j] = a >= 0 && a < n_members ? a : k;          // (every slot is filled: a guard)
+        }
+    }
+    for (int c = 0; c < n_cols; c++) {
+        const double mu = mean ? mean[(size_t)p * FILT_COLS + c] : 0.0;
+        double v = 0.0;
+        for (int j = 0; j < FILT_PER_THREAD; j++) {
+            if (src[j] < 0) continue;
+            const double x = Y[(size_t)src[j] * width + col0 + c];
+            if (mean) {
+                const double d = x - mu;
+                v += d * d;
+            } else {
+                v += x;
+            }
+        }
+        sh[threadIdx.x] = v;
+        __syncthreads();
+        for (int o = FILT_THREADS / 2; o > 0; o >>= 1) {
+            if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) partial[((size_t)p * n_tiles + t) * n_cols + c] = sh[0];
+        __syncthreads();
+    }
+}
+
+// column c's tile partials of point p, tiles ascending from 0.0
+__device__ __forceinline__ double filter_column_sum(const double *partial, long long p, long long n_tiles, int n_cols, int c)
+{
+#pragma clang fp contract(off)
+    double v = 0.0;
+    for (long long t = 0; t < n_tiles; t++) v += partial[((size_t)p * n_tiles + t) * n_cols + c];
+    return v;
+}
+
+// One block per point after the weights, the partials being those of (theta of the present sensors, e).  Thread c < ms:
+// sensor c's observed, observation and forecast mean (also -> mean[p][c]); a thread per absent sensor of the record:
+// observed = 0, the rest NaN; thread 0: W, the exact integer sums, the filter's count, ESS and increment, and the draw.
+__global__ void filter_member_finish_kernel(const double *partial, const unsigned long long *ipart, const double *smax,
+                                            long long n_tiles, long long members_per_point, const EnkfRow s, double sigma,
+                                            unsigned long long seed, const long long *point_base, long long member_offset,
+                                            unsigned row, long long n_arow, long long slot, unsigned long long *qr,
+                                            double *stats, unsigned long long *surv, double *mean, double *sm_stats)
+{
+#pragma clang fp contract(off)
+    const long long p = blockIdx.x;
+    const int c = threadIdx.x, n_cols = s.ms + 1;
+    double *sm = sm_stats + ((size_t)p * n_arow + slot) * s.n * ENKF_SENSOR_WIDTH;
+    if (c < s.ms) {
+        const double mu = filter_column_sum(partial, p, n_tiles, n_cols, c) / (double)members_per_point;
+        mean[(size_t)p * FILT_COLS + c] = mu;
+        double *e = sm + (size_t)s.sensor[c] * ENKF_SENSOR_WIDTH;
+        e[0] = 1.0;
+        e[1] = s.obs[c];
+        e[2] = mu;
+    }
+    if (c < s.n) {
+        bool present = false;
+        for (int k = 0; k < s.ms; k++) present = present || s.sensor[k] == c;
+        if (!present) {
+            double *e = sm + (size_t)c * ENKF_SENSOR_WIDTH;
+            e[0] = 0.0;
+            for (int k = 1; k < ENKF_SENSOR_WIDTH; k++) e[k] = __builtin_nan("");
+        }
+    }
+    if (c != 0) return;
+    const double W = filter_column_sum(partial, p, n_tiles, n_cols, s.ms);
+    unsigned long long Q = 0, b_hi = 0, b_lo = 0, n = 0;
+    for (long long t = 0; t < n_tiles; t++) {
+        const unsigned long long *in = ipart + ((size_t)p * n_tiles + t) * 4;
+        Q += in[0];
+        add_u128(b_hi, b_lo, in[2], in[1]);
+        n += in[3];
+    }
+    double *st = stats + ((size_t)p * n_arow + slot) * 4;
+    st[0] = (double)n;
+    if (n > 0 && Q > 0) {
+        st[1] = filter_ess(Q, b_hi, b_lo);
+        double inc = smax[p] + log(W / (double)n) - log(sigma);
+        for (int k = 0; k < s.ms; k++) inc -= log(s.sigma[k]);
+        st[2] = inc - 0.5 * (double)(1 + s.ms) * log(2.0 * M_PI);
+    } else {
+        st[1] = __builtin_nan("");
+        st[2] = __builtin_nan("");
+    }
+    filter_draw(seed, point_base, member_offset, p, members_per_point, row, Q, qr, surv);
+}
+
+// One block per point, thread c < ms, from the partials of the present sensors' columns: entry = 4, the posterior mean
+// (also -> mean[p][c]); entry = 3 or 5, a std from the squared deviations, / (N_p - 1) (N_p = 1: 0)
+__global__ void filter_sm_moment_kernel(const double *partial, long long n_tiles, long long members_per_point,
+                                        const EnkfRow s, int entry, long long n_arow, long long slot, double *mean,
+                                        double *sm_stats)
+{
+#pragma clang fp contract(off)
+    const long long p = blockIdx.x;
+    const int c = threadIdx.x;
+    if (c >= s.ms) return;
+    const double v = filter_column_sum(partial, p, n_tiles, s.ms, c);
+    double *e = sm_stats + (((size_t)p * n_arow + slot) * s.n + s.sensor[c]) * ENKF_SENSOR_WIDTH;
+    if (entry == 4) {
+        e[4] = mean[(size_t)p * FILT_COLS + c] = v / (double)members_per_point;
+    } else {
+        e[entry] = sqrt(members_per_point > 1 ? v / (double)(members_per_point - 1) : 0.0);
+    }
+}
+
+// a bin-path row of a filter with a record: the per-member weights q_{b_m} (hc_get_filter_member_weights)
+__global__ void filter_expand_weights_kernel(const unsigned short *w, const long long *q_all, long long members_per_point,
+                                             long long n_members, int D, long long *qm)
+{
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n_members) qm[k] = filter_q(w, q_all + (size_t)(k / members_per_point) * D, D, k);
+}
+
 __global__ void widen_u16(const unsigned short *in, int *out, size_t n)
 {
     size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2008,10 +2306,33 @@ FilterShardLayout filter_shard_layout(int64_t n_global, int64_t n, int64_t S, in
     return L;
 }
 
+// the filter's sensor diagnostics (hc_set_filter_soil_moisture): [P][n_arow][n][6] float64, created as NaN
+int ensure_fsm(hc_handle *h)
+{
+    if (h->fsm_n <= 0) return fail(HC_ERR_ARG, "no soil-moisture record (hc_set_filter_soil_moisture)");
+    if (int rc = ensure_filter(h)) return rc;
+    if (h->fsm_rows != h->n_rows)
+        return fail(HC_ERR_ARG, "the soil-moisture record has %lld rows, the forcing %lld: set the record again",
+                    (long long)h->fsm_rows, (long long)h->n_rows);
+    return ensure_da_table(h, h->fsm, h->filt_stride, (int64_t)h->fsm_n * ENKF_SENSOR_WIDTH, 0);
+}
+
+void fsm_off(hc_handle *h)
+{
+    h->fsm_n = 0;
+    h->fsm_rows = 0;
+    h->fsm_width = 0;
+    h->fsm_nodes.clear(); h->fsm_sigma.clear(); h->fsm_values.clear();
+    h->fsm.release();
+    h->filt_qm.release(); h->filt_Y.release(); h->filt_lmax.release(); h->filt_part.release(); h->filt_sums.release();
+    h->filt_ipart.release();
+}
+
 // what turns the filter off: new points, members or noise source (include/hydrocol.h hc_set_filter)
 void filter_off(hc_handle *h)
 {
     filter_shard_off(h);
+    fsm_off(h);
     h->filt_stride = 0;
     h->filt_done = false;
     h->filt.release();
@@ -3029,6 +3350,79 @@ int filter_shard_resample(hc_handle *h, int64_t n_tiles)
     return HC_OK;
 }
 
+// one entry of the sensor table from a pass over the present sensors' theta: the squared deviations from the means on
+// the device (entries 3 and 5: a std), or the sums (entry 4: the posterior mean); anc: over the resampled slots
+int filter_sm_moment(hc_handle *h, const EnkfRow &s, const long long *anc, int entry, int64_t n_tiles, int64_t n_arow,
+                     int64_t slot)
+{
+    const int64_t N = h->n_members, P = h->n_points, mpp = N / P;
+    hipLaunchKernelGGL(filter_tile_partial_kernel, dim3((unsigned)n_tiles, (unsigned)P), dim3(FILT_THREADS), 0, h->stream,
+                       h->filt_Y.p, s.ms + 2, 1, s.ms, anc, entry == 4 ? (const double *)nullptr : h->filt_sums.p,
+                       (long long)mpp, (long long)N, (long long)n_tiles, h->filt_part.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(filter_sm_moment_kernel, dim3((unsigned)P), dim3(WAVE), 0, h->stream, h->filt_part.p,
+                       (long long)n_tiles, (long long)mpp, s, entry, (long long)n_arow, (long long)slot, h->filt_sums.p,
+                       h->fsm.buf.p);
+    HIP_TRY(hipGetLastError());
+    return HC_OK;
+}
+
+// the sensors of a record (the EnKF's or the particle filter's) with a value on `row`, in record order
+EnkfRow sensor_row(int n, const std::vector<int> &nodes, const std::vector<double> &sigma, const std::vector<double> &values,
+                   int64_t row)
+{
+    EnkfRow s{};
+    for (int i = 0; i < n; i++) {
+        const double v = values[(size_t)row * n + i];
+        if (std::isnan(v)) continue;
+        s.sensor[s.m] = i;
+        s.node[s.m] = nodes[(size_t)i];
+        s.obs[s.m] = v;
+        s.sigma[s.m] = sigma[(size_t)i];
+        s.m++;
+    }
+    s.ms = s.m;
+    s.n = s.ms > 0 ? n : 0;
+    return s;
+}
+
+// A sensor row's weights (hc_set_filter_soil_moisture) in place of filter_weights_kernel's: theta and l_m per member, the
+// tiles' maxima, e_m and q_m per member with the tiles' integer sums, the partials of (theta, e), then per point the
+// diagnostics, the forecast means and the draw, and the forecast spread in a second pass about the means
+int filter_member_weights(hc_handle *h, const Chunk &c, const EnkfRow &s, const long long *pbase, long long key)
+{
+    const int64_t N = h->n_members, D = h->p.dim_d, P = h->n_points, mpp = N / P;
+    const int64_t row = c.row0 + c.rows - 1, slot = row / h->filt_stride, n_arow = filter_rows(h);
+    const int64_t n_tiles = (mpp + FILT_TILE - 1) / FILT_TILE;
+    const int width = s.ms + 2;
+    if (h->filt_qm.ensure((size_t)N) || h->filt_Y.ensure((size_t)(N * (h->fsm_n + 2))) ||
+        h->filt_lmax.ensure((size_t)(P * n_tiles)) || h->filt_ipart.ensure((size_t)(P * n_tiles * 4)) ||
+        h->filt_part.ensure((size_t)(P * n_tiles * FILT_COLS)) || h->filt_sums.ensure((size_t)(P * (FILT_COLS + 1))))
+        return HC_ERR_DEVICE;
+    const unsigned short *w = h->wtd_u16.p + (size_t)(c.rows - 1) * N;
+    double *const Y = h->filt_Y.p, *const mean = h->filt_sums.p, *const smax = h->filt_sums.p + (size_t)(P * FILT_COLS);
+    const dim3 tiles((unsigned)n_tiles, (unsigned)P);
+    hipLaunchKernelGGL(enkf_theta_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, h->psi.p, h->Pdev.p,
+                       h->node_tabs.p, (int)h->use_special(), (long long)N, (long long)mpp, (int)D, s, Y, width);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(filter_loglik_kernel, tiles, dim3(FILT_THREADS), 0, h->stream, w, (long long)mpp, (int)D,
+                       h->h_wtd_obs[(size_t)row], h->p.dz, h->filt_sigma, s, Y, (long long)n_tiles, h->filt_lmax.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(filter_member_weights_kernel, tiles, dim3(FILT_THREADS), 0, h->stream, w, (long long)mpp, (int)D, s.ms,
+                       (long long)n_tiles, h->filt_lmax.p, Y, h->filt_qm.p, h->filt_ipart.p, smax);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(filter_tile_partial_kernel, tiles, dim3(FILT_THREADS), 0, h->stream, Y, width, 1, s.ms + 1,
+                       (const long long *)nullptr, (const double *)nullptr, (long long)mpp, (long long)N, (long long)n_tiles,
+                       h->filt_part.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(filter_member_finish_kernel, dim3((unsigned)P), dim3(WAVE), 0, h->stream, h->filt_part.p,
+                       h->filt_ipart.p, smax, (long long)n_tiles, (long long)mpp, s, h->filt_sigma,
+                       (unsigned long long)h->filt_seed, pbase, key, (unsigned)row, (long long)n_arow, (long long)slot,
+                       h->filt_qr.p, h->filt.buf.p, h->filt_surv.p, mean, h->fsm.buf.p);
+    HIP_TRY(hipGetLastError());
+    return filter_sm_moment(h, s, nullptr, 3, n_tiles, n_arow, slot);
+}
+
 // The assimilation at the launch's last row (its water-table indices are wtd_u16's last row): weights, diagnostics and
 // draw per point, the member prefix scan, the slot fill, then psi and base gathered into the second buffers and swapped in.
 // hc_set_filter_shard: the handle's members are a part of a point of np members; the water-table indices of all of them
@@ -3066,20 +3460,37 @@ int assimilate(hc_handle *h, const Chunk &c)
         if (h->philox) key -= first;
     }
     const long long *pbase = P > 1 ? h->point_base.p : nullptr;
-    hipLaunchKernelGGL(filter_weights_kernel, dim3((unsigned)P), dim3(FILT_THREADS), 0, h->stream, w, (long long)mpp,
-                       (int)D, h->h_wtd_obs[(size_t)row], h->p.dz, h->filt_sigma, (unsigned long long)h->filt_seed, pbase,
-                       key, (unsigned)row, (long long)n_arow, (long long)slot, h->filt_q.p,
-                       h->filt_qr.p, h->filt.buf.p, h->filt_surv.p);
-    HIP_TRY(hipGetLastError());
+    // a row with sensor values (hc_set_filter_soil_moisture; never sharded): a weight per member, and the scan below reads
+    // it directly (a null w) in place of the bin's
+    const EnkfRow s = sensor_row(h->fsm_n, h->fsm_nodes, h->fsm_sigma, h->fsm_values, row);
+    const long long *q = h->filt_q.p;
+    if (s.ms > 0) {
+        if (int rc = filter_member_weights(h, c, s, pbase, key)) return rc;
+        HIP_TRY(hipMemsetAsync(h->filt_q.p, 0, (size_t)(P * D) * 8, h->stream));
+        w = nullptr;
+        q = h->filt_qm.p;
+    } else {
+        hipLaunchKernelGGL(filter_weights_kernel, dim3((unsigned)P), dim3(FILT_THREADS), 0, h->stream, w, (long long)mpp,
+                           (int)D, h->h_wtd_obs[(size_t)row], h->p.dz, h->filt_sigma, (unsigned long long)h->filt_seed, pbase,
+                           key, (unsigned)row, (long long)n_arow, (long long)slot, h->filt_q.p,
+                           h->filt_qr.p, h->filt.buf.p, h->filt_surv.p);
+        HIP_TRY(hipGetLastError());
+        if (h->fsm_n > 0) {
+            if (h->filt_qm.ensure((size_t)N)) return HC_ERR_DEVICE;
+            hipLaunchKernelGGL(filter_expand_weights_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, w,
+                               h->filt_q.p, (long long)mpp, (long long)N, (int)D, h->filt_qm.p);
+            HIP_TRY(hipGetLastError());
+        }
+    }
     const dim3 tiles((unsigned)n_tiles, (unsigned)P);
-    hipLaunchKernelGGL(filter_tile_sum_kernel, tiles, dim3(FILT_THREADS), 0, h->stream, w, h->filt_q.p, (long long)mpp,
+    hipLaunchKernelGGL(filter_tile_sum_kernel, tiles, dim3(FILT_THREADS), 0, h->stream, w, q, (long long)mpp,
                        (int)D, (long long)n_tiles, h->filt_tiles.p);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(filter_tile_scan_kernel, dim3((unsigned)P), dim3(FILT_THREADS), 0, h->stream, (long long)n_tiles,
                        h->filt_tiles.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemsetAsync(h->filt_anc.p, 0xFF, (size_t)(P * mpp) * 8, h->stream));
-    hipLaunchKernelGGL(filter_fill_kernel, tiles, dim3(FILT_THREADS), 0, h->stream, w, h->filt_q.p, (long long)mpp, (int)D,
+    hipLaunchKernelGGL(filter_fill_kernel, tiles, dim3(FILT_THREADS), 0, h->stream, w, q, (long long)mpp, (int)D,
                        (long long)n_tiles, h->filt_tiles.p, h->filt_qr.p, h->filt_anc.p, h->filt_surv.p);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(filter_survivors_kernel, dim3((unsigned)((P + 63) / 64)), dim3(64), 0, h->stream, h->filt_surv.p,
@@ -3094,6 +3505,12 @@ int assimilate(hc_handle *h, const Chunk &c)
                            h->psi_alt.p, h->base_alt.p, (long long)N, (int)D);
         HIP_TRY(hipGetLastError());
     }
+    if (s.ms > 0) {
+        // the sensors' posterior over the resampled slots, theta[anc[k]]: theta is a function of the copied column
+        if (int rc = filter_sm_moment(h, s, h->filt_anc.p, 4, n_tiles, n_arow, slot)) return rc;
+        if (int rc = filter_sm_moment(h, s, h->filt_anc.p, 5, n_tiles, n_arow, slot)) return rc;
+    }
+    h->fsm_width = s.ms;
     std::swap(h->psi, h->psi_alt);
     std::swap(h->base, h->base_alt);
     // the rest of this hc_step_rows call launches on the analysis (fill_args took the pointers before the swap)
@@ -3107,18 +3524,7 @@ int assimilate(hc_handle *h, const Chunk &c)
 // window that were captured for this analysis, by ascending offset
 EnkfRow enkf_row(const hc_handle *h, int64_t row)
 {
-    EnkfRow s{};
-    for (int i = 0; i < h->sm_n; i++) {
-        const double v = h->sm_values[(size_t)row * h->sm_n + i];
-        if (std::isnan(v)) continue;
-        s.sensor[s.m] = i;
-        s.node[s.m] = h->sm_nodes[(size_t)i];
-        s.obs[s.m] = v;
-        s.sigma[s.m] = h->sm_sigma[(size_t)i];
-        s.m++;
-    }
-    s.ms = s.m;
-    s.n = s.ms > 0 ? h->sm_n : 0;
+    EnkfRow s = sensor_row(h->sm_n, h->sm_nodes, h->sm_sigma, h->sm_values, row);
     for (int j = 0; j < h->win_n; j++) {
         const int64_t rj = row - h->win_off[(size_t)j];
         if (rj < 1 || h->h_wtd_obs[(size_t)rj] < 0 || h->win_row[(size_t)j] != rj) continue;
@@ -3384,6 +3790,7 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
         return fail(HC_ERR_ARG, "spin-up solves with the particle filter on in a Philox run: set the filter after the spin-up");
     const bool filt_on = h->filt_stride > 0 && !a->spinup;
     if (filt_on && (rc = ensure_filter(h))) return rc;
+    if (filt_on && h->fsm_n > 0 && (rc = ensure_fsm(h))) return rc;
     const bool enkf_on = h->enkf_stride > 0 && !a->spinup;   // (the EnKF: spin-up solves are never analysed either)
     if (enkf_on && (rc = ensure_enkf(h))) return rc;
     if (enkf_on && h->sm_n > 0 && (rc = ensure_sm(h))) return rc;
@@ -3718,6 +4125,26 @@ int hc_set_filter_stats(hc_handle *h, const double *table, int64_t n_entries)
 // the last assimilation's buffers (test hooks): a device -> host copy of `count` entries
 }  // extern "C"
 namespace {
+// what a soil-moisture record must satisfy, the EnKF's and the particle filter's alike: nodes in the column, sigma finite
+// and > 0, values in [0, 1] or NaN
+int sm_record_check(const hc_handle *h, const char *who, int32_t n_sensors, const int32_t *nodes, const double *values,
+                           const double *sigma)
+{
+    const int D = h->p.dim_d;
+    for (int i = 0; i < n_sensors; i++) {
+        if (nodes[i] < 0 || nodes[i] >= D)
+            return fail(HC_ERR_ARG, "%s: node %d of sensor %d outside [0, %d)", who, (int)nodes[i], i, D);
+        if (!(std::isfinite(sigma[i]) && sigma[i] > 0.0))
+            return fail(HC_ERR_ARG, "%s: sigma %g of sensor %d must be finite and > 0", who, sigma[i], i);
+    }
+    const size_t n = (size_t)h->n_rows * n_sensors;
+    for (size_t k = 0; k < n; k++)
+        if (!std::isnan(values[k]) && !(values[k] >= 0.0 && values[k] <= 1.0))
+            return fail(HC_ERR_ARG, "%s: value %g (row %lld, sensor %d) outside [0, 1]", who, values[k],
+                        (long long)(k / n_sensors), (int)(k % n_sensors));
+    return HC_OK;
+}
+
 template <typename T>
 int filter_hook(hc_handle *h, const DevBuf<T> &b, void *out, size_t count, const char *who, size_t first = 0)
 {
@@ -3776,6 +4203,80 @@ int hc_set_filter_base(hc_handle *h, const double *base)
     return HC_OK;
 }
 
+int hc_set_filter_soil_moisture(hc_handle *h, int32_t n_sensors, const int32_t *nodes, const double *values,
+                                const double *sigma)
+{
+    if (!h || n_sensors < 0) return fail(HC_ERR_ARG, "hc_set_filter_soil_moisture: bad argument");
+    if (n_sensors > ENKF_SENSORS)
+        return fail(HC_ERR_ARG, "hc_set_filter_soil_moisture: %d sensors, at most %d", (int)n_sensors, ENKF_SENSORS);
+    if (n_sensors > 0 && h->enkf_stride > 0)
+        return fail(HC_ERR_ARG, "hc_set_filter_soil_moisture: the EnKF is on (its record: hc_set_enkf_soil_moisture)");
+    if (n_sensors > 0 && h->filt_stride <= 0)
+        return fail(HC_ERR_ARG, "hc_set_filter_soil_moisture: the particle filter is off (hc_set_filter comes first)");
+    if (n_sensors > 0 && h->fs_n > 0)
+        return fail(HC_ERR_ARG, "hc_set_filter_soil_moisture: the filter is sharded (hc_set_filter_shard), and the sharded "
+                                "filter gathers water-table indices only: a record needs every member of a point on one handle");
+    if (n_sensors > 0 && (!nodes || !values || !sigma)) return fail(HC_ERR_ARG, "hc_set_filter_soil_moisture: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    fsm_off(h);
+    if (n_sensors == 0) return HC_OK;
+    if (int rc = sm_record_check(h, "hc_set_filter_soil_moisture", n_sensors, nodes, values, sigma)) return rc;
+    h->fsm_nodes.assign(nodes, nodes + n_sensors);
+    h->fsm_sigma.assign(sigma, sigma + n_sensors);
+    h->fsm_values.assign(values, values + (size_t)h->n_rows * n_sensors);
+    h->fsm_rows = h->n_rows;
+    h->fsm_n = n_sensors;
+    const int rc = ensure_fsm(h);
+    if (rc != HC_OK) fsm_off(h);                 // refused: off
+    return rc;
+}
+
+int hc_get_filter_sm_stats(hc_handle *h, double *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_get_filter_sm_stats: bad argument");
+    return table_copy(h, h->fsm, ensure_fsm, hipMemcpyDeviceToHost, table, n_entries, "hc_get_filter_sm_stats");
+}
+
+int hc_set_filter_sm_stats(hc_handle *h, const double *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_set_filter_sm_stats: bad argument");
+    return table_copy(h, h->fsm, ensure_fsm, hipMemcpyHostToDevice, const_cast<double *>(table), n_entries,
+                      "hc_set_filter_sm_stats");
+}
+
+int hc_get_filter_sm_width(hc_handle *h, int32_t *width)
+{
+    if (!h || !width) return fail(HC_ERR_ARG, "hc_get_filter_sm_width: bad argument");
+    *width = h->fsm_n > 0 ? h->fsm_width : 0;
+    return HC_OK;
+}
+
+int hc_get_filter_member_weights(hc_handle *h, int64_t *q)
+{
+    if (h && h->fsm_n <= 0) return fail(HC_ERR_ARG, "hc_get_filter_member_weights: no soil-moisture record");
+    return filter_hook(h, h->filt_qm, q, h ? (size_t)h->n_members : 0, "hc_get_filter_member_weights");
+}
+
+// columns [col0, col0 + cols) of the last sensor row's Y [N][m_s + 2]
+static int filter_sm_hook(hc_handle *h, double *out, int col0, int cols, const char *who)
+{
+    if (!h || !out) return fail(HC_ERR_ARG, "%s: bad argument", who);
+    if (h->fsm_n <= 0 || h->fsm_width <= 0) return fail(HC_ERR_ARG, "%s: the last assimilation had no sensor value", who);
+    const size_t N = (size_t)h->n_members, width = (size_t)h->fsm_width + 2;
+    std::vector<double> all(N * width);
+    if (int rc = filter_hook(h, h->filt_Y, all.data(), all.size(), who)) return rc;
+    for (size_t m = 0; m < N; m++) std::copy_n(all.data() + m * width + col0, cols, out + m * cols);
+    return HC_OK;
+}
+
+int hc_get_filter_loglik(hc_handle *h, double *l) { return filter_sm_hook(h, l, 0, 1, "hc_get_filter_loglik"); }
+
+int hc_get_filter_sm_theta(hc_handle *h, double *theta)
+{
+    return filter_sm_hook(h, theta, 1, h ? h->fsm_width : 0, "hc_get_filter_sm_theta");
+}
+
 }  // extern "C"
 namespace {
 // the argument checks the two shard entry points share; n_global through *np
@@ -3825,6 +4326,9 @@ int hc_set_filter_shard(hc_handle *h, int32_t n_shards, const int64_t *bounds, i
     if (n_shards == 0) return HC_OK;
     int64_t np = 0;
     if (int rc = filter_shard_check(h, n_shards, bounds, index, "hc_set_filter_shard", &np)) return rc;
+    if (h->fsm_n > 0)
+        return fail(HC_ERR_ARG, "hc_set_filter_shard: a soil-moisture record is set (hc_set_filter_soil_moisture), and the "
+                                "sharded filter gathers water-table indices only");
     if (!device_buf || !gather || !route) return fail(HC_ERR_ARG, "hc_set_filter_shard: NULL buffer or callback");
     const int64_t need = filter_shard_layout(np, h->n_members, n_shards, h->p.dim_d).words;
     if (n_words < need)
@@ -3954,18 +4458,8 @@ int hc_set_enkf_soil_moisture(hc_handle *h, int32_t n_sensors, const int32_t *no
     HIP_TRY(hipStreamSynchronize(h->stream));
     sm_off(h);
     if (n_sensors == 0) return HC_OK;
-    const int D = h->p.dim_d;
-    for (int i = 0; i < n_sensors; i++) {
-        if (nodes[i] < 0 || nodes[i] >= D)
-            return fail(HC_ERR_ARG, "hc_set_enkf_soil_moisture: node %d of sensor %d outside [0, %d)", (int)nodes[i], i, D);
-        if (!(std::isfinite(sigma[i]) && sigma[i] > 0.0))
-            return fail(HC_ERR_ARG, "hc_set_enkf_soil_moisture: sigma %g of sensor %d must be finite and > 0", sigma[i], i);
-    }
+    if (int rc = sm_record_check(h, "hc_set_enkf_soil_moisture", n_sensors, nodes, values, sigma)) return rc;
     const size_t n = (size_t)h->n_rows * n_sensors;
-    for (size_t k = 0; k < n; k++)
-        if (!std::isnan(values[k]) && !(values[k] >= 0.0 && values[k] <= 1.0))
-            return fail(HC_ERR_ARG, "hc_set_enkf_soil_moisture: value %g (row %lld, sensor %d) outside [0, 1]", values[k],
-                        (long long)(k / n_sensors), (int)(k % n_sensors));
     h->sm_nodes.assign(nodes, nodes + n_sensors);
     h->sm_sigma.assign(sigma, sigma + n_sensors);
     h->sm_values.assign(values, values + n);

@@ -10,7 +10,7 @@ import numpy as np
 
 from .digest import inverse_retention
 from .stepper import (ENKF_METHODS, ENKF_WIDTH, SM_WIDTH, WINDOW_WIDTH, EnsembleStepper, enkf_sm_summary, enkf_summary,
-                      enkf_window_settings, enkf_window_summary, filter_summary,
+                      enkf_window_settings, enkf_window_summary, filter_sm_summary, filter_summary,
                       moments_to_mean_std, wtd_distribution)
 
 
@@ -101,6 +101,9 @@ class _Run:
     filter_stride > 0: a bootstrap particle filter on the well's water table every ``filter_stride``-th row with an
     observation (``filter_sigma_cm``: the observation error; ``filter_seed``: default the run's seed): the tables above
     describe the forecast, the states continue from the analysis; :meth:`filter_summary` (ESS, log marginal likelihood).
+    filter_soil_moisture: a soil-moisture record (stepper.soil_moisture_record) that joins the well in the filter's
+    weights, which then belong to a member and not to a 5 cm bin (include/hydrocol.h hc_set_filter_soil_moisture);
+    :meth:`filter_sm_table`, the ``sm_*`` keys of :meth:`filter_summary`.
     enkf_stride > 0: a stochastic ensemble Kalman filter on the well's continuous water table instead (``enkf_sigma_cm``:
     the observation error; ``enkf_localisation_cm``: the Gaspari-Cohn half-width, 0 = none; ``enkf_seed``: default the
     run's seed), with the same forecast / analysis order; :meth:`enkf_summary` (log marginal likelihood).
@@ -119,7 +122,8 @@ class _Run:
 
     def _start_tables(self, profile_stride, wtd_hist_stride, filter_stride=0, filter_sigma_cm=None, filter_seed=None,
                       enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None,
-                      enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=()):
+                      enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=(),
+                      filter_soil_moisture=None):
         self.profile_stride = int(profile_stride)
         if self.profile_stride:
             self.stepper.set_profile_stats(self.profile_stride)
@@ -132,6 +136,12 @@ class _Run:
         self.filter_seed = (self.seed if filter_seed is None else int(filter_seed)) if self.filter_stride else None
         if self.filter_stride:
             self.stepper.set_filter(self.filter_stride, self.filter_sigma_cm, self.filter_seed)
+        self.filter_soil_moisture = filter_soil_moisture
+        if filter_soil_moisture is not None:
+            if not self.filter_stride:
+                raise ValueError("filter_soil_moisture needs the particle filter (filter_stride > 0)")
+            sm = filter_soil_moisture
+            self.stepper.set_filter_soil_moisture(sm["nodes"], sm["values"], sm["sigma"])
         self.enkf_stride = int(enkf_stride or 0)
         self.enkf_sigma_cm = float(enkf_sigma_cm) if self.enkf_stride else None
         self.enkf_localisation_cm = float(enkf_localisation_cm or 0.0) if self.enkf_stride else None
@@ -190,12 +200,25 @@ class _Run:
         """[n_arow][4] float64 (count, ESS, log-likelihood increment, survivors per assimilation slot); a sweep: [P][n_arow][4]."""
         return self.stepper.filter_table().reshape(self._lead + (-1, 4))
 
-    def filter_summary(self, table=None):
+    def filter_summary(self, table=None, sm_table=None):
         """The filter's record (stepper.filter_summary): ``rows``, ``count``, ``ess``, ``loglik_rows``, ``survivors`` over
         the assimilated rows and ``loglik``, the log marginal likelihood of the well record (log cm^-1 summed over the rows),
-        with a leading [P] for a sweep; ``table``: e.g. the one assembled over ranks."""
+        with a leading [P] for a sweep; ``table``: e.g. the one assembled over ranks.  With a soil-moisture record the
+        increments of the sensor rows are the joint ones, and the ``sm_*`` keys of :meth:`filter_sm_summary` come along."""
         t = self.filter_table() if table is None else table
-        return filter_summary(t, self.filter_stride, self.filter_sigma_cm)
+        out = filter_summary(t, self.filter_stride, self.filter_sigma_cm)
+        if self.filter_soil_moisture is not None:
+            out.update(("sm_" + k, v) for k, v in self.filter_sm_summary(sm_table).items())
+        return out
+
+    def filter_sm_table(self):
+        """[n_arow][n][6] float64 (include/hydrocol.h hc_set_filter_soil_moisture); a sweep: [P][n_arow][n][6]."""
+        return self.stepper.filter_sm_table().reshape(self._lead + (-1, self.stepper.filter_sm_n, SM_WIDTH))
+
+    def filter_sm_summary(self, table=None):
+        """stepper.filter_sm_summary of the filter's sensor table (``table``: e.g. the one assembled over ranks)."""
+        t = self.filter_sm_table() if table is None else table
+        return filter_sm_summary(t, self.filter_stride, self.filter_soil_moisture["sigma"])
 
     def enkf_table(self):
         """[n_arow][8] float64 (include/hydrocol.h hc_set_enkf; depths from the top node); a sweep: [P][n_arow][8]."""
@@ -264,16 +287,19 @@ class EnsembleSimulation(_Run):
                  noise="philox", spinup="shared", profile_stride=0, wtd_hist_stride=0, filter_stride=0,
                  filter_sigma_cm=None, filter_seed=None, enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0,
                  enkf_seed=None, enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0,
-                 enkf_window_offsets=(), enkf_shard=None, filter_shard=None):
+                 enkf_window_offsets=(), enkf_shard=None, filter_shard=None, filter_soil_moisture=None):
         if filter_shard is not None and not int(filter_stride or 0):
             raise ValueError("filter_shard needs the particle filter (filter_stride > 0)")
+        if filter_shard is not None and filter_soil_moisture is not None:
+            raise ValueError("filter_shard and filter_soil_moisture exclude each other: the sharded filter gathers "
+                             "water-table indices only")
         if enkf_shard is not None or filter_shard is not None:
             from . import _lib
             _lib.load(with_torch=True)             # torch before the library: the shard's buffer is a torch tensor
         self._start(cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup)
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
-                           enkf_relaxation, enkf_window_offsets)
+                           enkf_relaxation, enkf_window_offsets, filter_soil_moisture)
         self.enkf_shard = None
         if enkf_shard is not None:
             if not self.enkf_stride:
@@ -389,6 +415,9 @@ class EnsembleSimulation(_Run):
             arrays["filter_seed"] = np.array(self.filter_seed, dtype=np.uint64)
             arrays["filter_table"] = self.stepper.filter_table()
             arrays["filter_base"] = self.stepper.filter_base()
+            if self.filter_soil_moisture is not None:     # the record itself is supplied again at restore
+                arrays["filter_sm_nodes"] = np.asarray(self.filter_soil_moisture["nodes"], dtype=np.int32)
+                arrays["filter_sm_table"] = self.stepper.filter_sm_table()
         if self.enkf_stride:
             arrays["enkf_stride"] = np.array(self.enkf_stride, dtype=np.int64)
             arrays["enkf_sigma_cm"] = np.array(self.enkf_sigma_cm, dtype=np.float64)
@@ -415,9 +444,10 @@ class EnsembleSimulation(_Run):
         return path
 
     @classmethod
-    def restore(cls, path, cols, forcing, device=0, flags=None, enkf_soil_moisture=None):
+    def restore(cls, path, cols, forcing, device=0, flags=None, enkf_soil_moisture=None, filter_soil_moisture=None):
         """A new ensemble (new handle) continuing the one ``dump`` wrote: same members, same streams, same row.  A run with
-        a soil-moisture record needs it again (``enkf_soil_moisture``, like the forcing); its sensor table is restored."""
+        a soil-moisture record needs it again (``enkf_soil_moisture`` or ``filter_soil_moisture``, like the forcing); its
+        sensor table is restored."""
         from pathlib import Path
         from . import hdf5io
         path = Path(path)
@@ -441,15 +471,22 @@ class EnsembleSimulation(_Run):
                        enkf_localisation_cm=float(data["enkf_localisation_cm"]), enkf_seed=int(data["enkf_seed"]))
         if enkf and "enkf_method" in data:
             fkw.update(enkf_method=ENKF_METHODS[int(data["enkf_method"])], enkf_relaxation=float(data["enkf_relaxation"]))
-        has_sm = enkf and "enkf_sm_table" in data
-        if has_sm != (enkf_soil_moisture is not None):
-            raise ValueError(f" EnsembleSimulation: {path} was written {'with' if has_sm else 'without'} a soil-moisture "
-                             f"record: pass {'the same record' if has_sm else 'none'} as enkf_soil_moisture.")
-        if has_sm and not np.array_equal(np.asarray(data["enkf_sm_nodes"]).reshape(-1),
-                                          np.asarray(enkf_soil_moisture["nodes"]).reshape(-1)):
-            raise ValueError(f" EnsembleSimulation: {path} has sensors at other nodes than enkf_soil_moisture.")
-        if has_sm:
-            fkw.update(enkf_soil_moisture=enkf_soil_moisture)
+        def record(on, prefix, given):
+            """Whether the checkpoint holds the sensor table of ``prefix``'s record; the record given must match it."""
+            has = bool(on) and prefix + "_sm_table" in data
+            arg = prefix + "_soil_moisture"
+            if has != (given is not None):
+                raise ValueError(f" EnsembleSimulation: {path} was written {'with' if has else 'without'} a soil-moisture "
+                                 f"record: pass {'the same record' if has else 'none'} as {arg}.")
+            if has and not np.array_equal(np.asarray(data[prefix + "_sm_nodes"]).reshape(-1),
+                                          np.asarray(given["nodes"]).reshape(-1)):
+                raise ValueError(f" EnsembleSimulation: {path} has sensors at other nodes than {arg}.")
+            if has:
+                fkw[arg] = given
+            return has
+
+        has_sm = record(enkf, "enkf", enkf_soil_moisture)
+        has_fsm = record(filt, "filter", filter_soil_moisture)
         has_win = enkf and "enkf_window_offsets" in data
         if has_win:
             fkw.update(enkf_window_offsets=tuple(int(o) for o in np.asarray(data["enkf_window_offsets"]).reshape(-1)))
@@ -460,6 +497,8 @@ class EnsembleSimulation(_Run):
         if filt:
             sim.stepper.set_filter_table(np.asarray(data["filter_table"], dtype=np.float64))
             sim.stepper.set_filter_base(np.asarray(data["filter_base"], dtype=np.float64).reshape(n, D))
+            if has_fsm:
+                sim.stepper.set_filter_sm_table(np.asarray(data["filter_sm_table"], dtype=np.float64))
         else:
             sim.stepper.set_noise_scale(np.asarray(data["noise_scale"], dtype=float).reshape(n))
         if enkf:
@@ -568,7 +607,8 @@ class SweepSimulation(_Run):
     def __init__(self, cols_list, forcing, n_members, seed=0, device=0, first_point=0, flags=None, psi0=None,
                  point_ids=None, profile_stride=0, wtd_hist_stride=0, filter_stride=0, filter_sigma_cm=None,
                  filter_seed=None, enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None,
-                 enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=()):
+                 enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=(),
+                 filter_soil_moisture=None):
         self.points = list(cols_list)
         self.P, self.n = len(self.points), int(n_members)
         self._lead = (self.P,)
@@ -597,7 +637,7 @@ class SweepSimulation(_Run):
             self.stepper.set_point_member_bases(self.bases)
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
-                           enkf_relaxation, enkf_window_offsets)
+                           enkf_relaxation, enkf_window_offsets, filter_soil_moisture)
         self.next_row, self.kernel_ms, self.launches = 1, 0.0, 0
 
     def _spinup(self, flags):

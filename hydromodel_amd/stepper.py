@@ -77,6 +77,7 @@ class EnsembleStepper:
         self.profile_stride = 0
         self.wtd_hist_stride = 0
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = 0, 0.0, 0
+        self.filter_sm_nodes = None
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
         self.enkf_sm_nodes = None
         self.enkf_method, self.enkf_relaxation = "stochastic", 0.0
@@ -340,12 +341,14 @@ class EnsembleStepper:
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = 0, 0.0, 0   # hc_set_filter turns it off first,
         #                                                                            and leaves it off if it refuses
         self.filter_shard, self._filter_shard_keep = None, None                  # ... and the sharding with it
+        self.filter_sm_nodes = None                                              # ... and the sensor record
         L.check(self.lib.hc_set_filter(self.h, stride, sigma, int(seed) & 0xFFFFFFFFFFFFFFFF))
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = stride, sigma, int(seed)
 
     def _filter_off(self):
         """The library turned the filters off (a new noise source or new point keys, include/hydrocol.h): so does this side."""
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = 0, 0.0, 0
+        self.filter_sm_nodes = None
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
         self.enkf_sm_nodes = None
         self.enkf_method, self.enkf_relaxation = "stochastic", 0.0
@@ -393,6 +396,73 @@ class EnsembleStepper:
         """[P] int64: the systematic offset r of the last assimilation (test hook)."""
         out = np.zeros(self.P, dtype=np.int64)
         L.check(self.lib.hc_get_filter_draw(self.h, L.lptr(out)))
+        return out
+
+    # -- soil-moisture sensors in the particle filter (include/hydrocol.h hc_set_filter_soil_moisture) -------------------
+    def _sm_record(self, nodes, values, sigma):
+        """(nodes int32 [n], values [T][n], sigma [n]) of a soil-moisture record as the library takes it; n = 0: none."""
+        nodes = np.ascontiguousarray([] if nodes is None else nodes, dtype=np.int32).reshape(-1)
+        n = int(nodes.size)
+        if n == 0:
+            return nodes, None, None
+        v = L.as_f64(values).reshape(self.T, n) if np.size(values) == self.T * n else None
+        if v is None:
+            raise ValueError(f"soil-moisture values must hold [{self.T}][{n}] entries, got {np.shape(values)}")
+        return nodes, v, L.as_f64(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (n,)).copy())
+
+    def set_filter_soil_moisture(self, nodes, values=None, sigma=None):
+        """Add a record of volumetric water content at the depth nodes ``nodes`` (at most 8) to the particle filter's
+        weights, which then belong to a member and not to a bin: ``values`` [T][n] in [0, 1], NaN = no observation on that
+        row; ``sigma`` the sensors' error (m^3/m^3), one number or one per sensor.  ``nodes`` empty or None removes the
+        record.  The filter must be on (:meth:`set_filter` first; it removes the record again) and not sharded."""
+        nodes, v, sg = self._sm_record(nodes, values, sigma)
+        self.filter_sm_nodes = None
+        if nodes.size == 0:
+            L.check(self.lib.hc_set_filter_soil_moisture(self.h, 0, None, None, None))
+            return
+        L.check(self.lib.hc_set_filter_soil_moisture(self.h, int(nodes.size), L.iptr(nodes), L.dptr(v), L.dptr(sg)))
+        self.filter_sm_nodes = nodes.copy()
+
+    @property
+    def filter_sm_n(self):
+        return 0 if self.filter_sm_nodes is None else int(self.filter_sm_nodes.size)
+
+    def filter_sm_table(self):
+        """[P][n_arow][n][6] float64 per assimilation slot and sensor: observed (0/1), observation, forecast mean and std
+        of theta, posterior mean and std of theta over the resampled slots; NaN where the slot had no sensor value (and
+        after observed = 0)."""
+        t = np.zeros((self.P, stride_rows(self.T, self.filter_stride), self.filter_sm_n, SM_WIDTH))
+        L.check(self.lib.hc_get_filter_sm_stats(self.h, L.dptr(t), t.size))
+        return t
+
+    def set_filter_sm_table(self, table):
+        t = L.as_f64(table).reshape(-1)
+        L.check(self.lib.hc_set_filter_sm_stats(self.h, L.dptr(t), t.size))
+
+    def filter_sm_width(self):
+        """m_s = the sensors present on the last assimilation (0: it took the bin path; test hook)."""
+        w = np.zeros(1, dtype=np.int32)
+        L.check(self.lib.hc_get_filter_sm_width(self.h, L.iptr(w)))
+        return int(w[0])
+
+    def filter_member_weights(self):
+        """[N] int64: q_m of the last assimilation, with a record set (after a bin-path row q of the member's bin; test
+        hook)."""
+        out = np.zeros(self.N, dtype=np.int64)
+        L.check(self.lib.hc_get_filter_member_weights(self.h, L.lptr(out)))
+        return out
+
+    def filter_loglik(self):
+        """[N] l_m of the last assimilation, a sensor row (test hook)."""
+        out = np.zeros(self.N)
+        L.check(self.lib.hc_get_filter_loglik(self.h, L.dptr(out)))
+        return out
+
+    def filter_sm_theta(self):
+        """[N][m_s] theta of every member's forecast at the nodes of the sensors present on the last assimilation (test
+        hook)."""
+        out = np.zeros((self.N, self.filter_sm_width()))
+        L.check(self.lib.hc_get_filter_sm_theta(self.h, L.dptr(out)))
         return out
 
     # -- one point's members on several handles, particle filter (include/hydrocol.h hc_set_filter_shard) ----------------
@@ -568,17 +638,12 @@ class EnsembleStepper:
         ``values`` [T][n] in [0, 1], NaN = no observation on that row; ``sigma`` the sensors' error (m^3/m^3), one number
         or one per sensor.  ``nodes`` empty or None removes the record.  The EnKF must be on (:meth:`set_enkf` first; it
         removes the record again)."""
-        nodes = np.ascontiguousarray([] if nodes is None else nodes, dtype=np.int32).reshape(-1)
-        n = int(nodes.size)
+        nodes, v, sg = self._sm_record(nodes, values, sigma)
         self.enkf_sm_nodes = None
-        if n == 0:
+        if nodes.size == 0:
             L.check(self.lib.hc_set_enkf_soil_moisture(self.h, 0, None, None, None))
             return
-        v = L.as_f64(values).reshape(self.T, n) if np.size(values) == self.T * n else None
-        if v is None:
-            raise ValueError(f"soil-moisture values must hold [{self.T}][{n}] entries, got {np.shape(values)}")
-        sg = L.as_f64(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (n,)).copy())
-        L.check(self.lib.hc_set_enkf_soil_moisture(self.h, n, L.iptr(nodes), L.dptr(v), L.dptr(sg)))
+        L.check(self.lib.hc_set_enkf_soil_moisture(self.h, int(nodes.size), L.iptr(nodes), L.dptr(v), L.dptr(sg)))
         self.enkf_sm_nodes = nodes.copy()
 
     @property
@@ -949,6 +1014,45 @@ def filter_ancestors_of(q_members, r):
     return anc
 
 
+def filter_member_loglik(w, theta, obs_idx, theta_obs, dz, sigma_cm, sigma):
+    """[N] l_m of a sensor row (include/hydrocol.h hc_set_filter_soil_moisture), the device's IEEE operations in its order:
+    ``w`` [N] water-table indices, ``theta`` [N][m_s] at the present sensors' nodes, ``obs_idx`` the well's index,
+    ``theta_obs`` and ``sigma`` [m_s] the present sensors' values and errors in record order."""
+    w = np.asarray(w, dtype=np.int64)
+    theta = np.asarray(theta, dtype=np.float64).reshape(w.size, -1)
+    theta_obs, sigma = (np.asarray(v, dtype=np.float64).reshape(-1) for v in (theta_obs, sigma))
+    t = np.float64(dz) * (w - int(obs_idx)).astype(np.float64) / np.float64(sigma_cm)
+    a = t * t
+    with np.errstate(under="ignore", over="ignore"):
+        for i in range(theta.shape[1]):
+            u = (theta[:, i] - theta_obs[i]) / sigma[i]
+            a = a + u * u
+    return -0.5 * a
+
+
+def filter_tile_sum(x):
+    """The sum of ``x`` [N_p] (or of every column of [N_p][c]) in the order of the filter's sensor rows (include/hydrocol.h
+    hc_set_filter_soil_moisture): tiles of 1024 consecutive members, 256 threads with 4 consecutive members each from 0.0,
+    a tree of halving strides over the threads, the tiles ascending from 0.0; members past N_p add 0.0."""
+    x = np.asarray(x, dtype=np.float64)
+    cols = x.reshape(x.shape[0], -1)
+    n_tiles = -(-cols.shape[0] // 1024)
+    pad = np.zeros((n_tiles * 1024, cols.shape[1]))
+    pad[:cols.shape[0]] = cols
+    per = pad.reshape(n_tiles, 256, 4, -1)
+    th = np.zeros((n_tiles, 256, cols.shape[1]))
+    for j in range(4):
+        th = th + per[:, :, j]
+    o = 128
+    while o:
+        th[:, :o] = th[:, :o] + th[:, o:2 * o]
+        o //= 2
+    total = np.zeros(cols.shape[1])
+    for t in range(n_tiles):
+        total = total + th[t, 0]
+    return total.reshape(x.shape[1:]) if x.ndim > 1 else float(total[0])
+
+
 def filter_routes(ancestors, bounds):
     """The columns a sharded resampling moves (include/hydrocol.h hc_set_filter_shard), restated with NumPy:
     ``(send, recv)`` with ``send[s][d]`` = the global ids of the members shard s sends to shard d -- the distinct ancestors
@@ -1039,7 +1143,7 @@ def sensor_nodes(z, depths_cm):
 
 
 def soil_moisture_record(z, depths_cm, values, sigma):
-    """The ``enkf_soil_moisture=`` argument of EnsembleSimulation / SweepSimulation: ``depths_cm`` [n] (mapped to nodes
+    """The ``enkf_soil_moisture=`` / ``filter_soil_moisture=`` argument of EnsembleSimulation / SweepSimulation: ``depths_cm`` [n] (mapped to nodes
     by :func:`sensor_nodes`), ``values`` [T][n] (NaN = none), ``sigma`` one number or [n]."""
     depths = np.asarray(depths_cm, dtype=np.float64).reshape(-1)
     sg = np.broadcast_to(np.asarray(sigma, dtype=np.float64), depths.shape).copy()
@@ -1070,6 +1174,13 @@ def enkf_sm_summary(table, stride, sigma):
             "rmse": rmse, "mean_innovation": mean_innov, "n_obs": cnt.astype(np.int64),
             "rmse_all": rmse_all if np.ndim(rmse_all) else float(rmse_all), "stride": int(stride),
             "sigma": np.asarray(sigma, dtype=np.float64)}
+
+
+def filter_sm_summary(table, stride, sigma):
+    """The particle filter's sensor record (include/hydrocol.h hc_set_filter_soil_moisture) from its [..., n_arow, n, 6]
+    table: the keys of :func:`enkf_sm_summary`, the layout being the same -- ``prior_*`` the forecast ensemble,
+    ``post_*`` the resampled one, the RMSE the forecast mean's over the observed rows."""
+    return enkf_sm_summary(table, stride, sigma)
 
 
 # ---- the well's record inside the window (include/hydrocol.h hc_set_enkf_window) ---------------------------------------

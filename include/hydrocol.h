@@ -39,7 +39,8 @@
  *   hc_set_wtd_hist, hc_get_wtd_hist, hc_set_wtd_hist_table, hc_reset_wtd_hist, hc_wtd_distribution
  *                      <- wtd_est / abs_error per row (src/simulation.py:612-615) as the ensemble's distribution:
  *                         per-row histograms of the water-table index, quantiles and the CRPS against the well
- *   hc_set_filter, hc_get/set_filter_stats, hc_get/set_filter_base, hc_get_filter_ancestors/weights/draw
+ *   hc_set_filter, hc_get/set_filter_stats, hc_get/set_filter_base, hc_get_filter_ancestors/weights/draw,
+ *   hc_set_filter_soil_moisture, hc_get/set_filter_sm_stats, hc_get_filter_sm_width/member_weights/loglik/sm_theta
  *                      <- (new) the ensemble conditioned on wtd_obs (src/simulation.py:582-612): a bootstrap particle filter,
  *                         and the log marginal likelihood of the well record per parameter point
  *   hc_set_enkf, hc_get/set_enkf_stats, hc_get_enkf_gain/y/eps
@@ -376,6 +377,55 @@ int hc_get_filter_ancestors(hc_handle *h, int64_t *ancestors);
 int hc_get_filter_weights(hc_handle *h, int64_t *q);
 int hc_get_filter_draw(hc_handle *h, int64_t *r);
 
+/* Soil-moisture sensors in the particle filter: a record of volumetric water content at up to 8 depth nodes joins the well
+ * in the weights, which then belong to a member and not to a bin.  values [n_forcing_rows][n_sensors], NaN = no observation
+ * on that row; sigma [n_sensors] (m^3/m^3) finite and > 0; nodes in [0, D).
+ *   Assimilation rows do not change: r >= 1, r % stride == 0 and wtd_obs[r] >= 0.  A row on which no sensor has a value runs
+ *   the bin path of hc_set_filter untouched: an all-NaN record gives the well-only run to the bit (states, table, hooks).
+ *   A row with m_s >= 1 sensor values, per parameter point p (N_p members, member order), fp64 without contraction:
+ *     theta_m,i = the reference's theta_vol of member m's forecast psi at the node of present sensor i (the cell model of
+ *     hc_model_nodes, to its bits; theta has no noise term);
+ *     t_w = dz * (double)(b_m - o) / sigma_cm;  a = t_w * t_w;  for each present sensor in record order:
+ *     u = (theta_m,i - theta_obs,i) / sigma_i;  a += u * u;  then l_m = -0.5 * a;
+ *     a member with b_m >= D or a non-finite l_m is not counted and gets q_m = 0; s = max l_m over the counted members;
+ *     e_m = exp(l_m - s);  q_m = floor(2^31 * e_m): 2^31 at the likeliest member.
+ *   Resampling: C_m, Q, the draw r (the same Philox counter) and the slot ranges as for hc_set_filter, on q_m as it stands:
+ *   the ancestry is an integer function of q_m, and q_m of nothing but the member's own column and the point's s (a maximum:
+ *   no order).
+ *   Sums over a point's members, the one order of every floating-point sum on this path (fixed by N_p alone, no
+ *   floating-point atomics): tiles of 1024 consecutive members; within a tile, 256 threads take 4 consecutive members each,
+ *   summed in member order from 0.0; the 256 thread sums are combined in a tree of halving strides (x_i += x_{i + 128}, then
+ *   x_i += x_{i + 64}, ... x_0 += x_1); the tile sums are added in ascending tile order from 0.0.  Members past N_p add 0.0.
+ *   The filter's table on such a row: count = the counted members; ESS = Q^2 / sum q_m^2 (exact sums, as for hc_set_filter);
+ *   the increment, in this order,
+ *     s + log(W / count) - log(sigma_cm) - log(sigma_i) for each present sensor in record order
+ *       - 0.5 * (double)(1 + m_s) * log(2 pi),   W = sum e_m over the counted members (the order above; others add 0.0):
+ *   the joint Gaussian density of the observed vector given the member's, averaged over the members, in
+ *   log cm^-1 (m^3/m^3)^-m_s; survivors as before.  The table is the same bits at any launch length and point order.
+ *   Sensor diagnostics, float64 [P][n_arow][n_sensors][6]: observed (0/1), observation, forecast mean of theta (sum / N_p),
+ *   forecast std of theta (two passes: squared deviations from that mean, / (N_p - 1), 0 for N_p = 1), posterior mean and std
+ *   of theta over the resampled slots, theta_{anc[k]} (theta is a function of the copied column), every sum in the order
+ *   above.  A sensor without a value on a sensor row: observed = 0, the rest NaN; a slot without a sensor row: all NaN.
+ * hc_set_filter_soil_moisture: n_sensors = 0 removes the record; otherwise (re)creates the sensor table (NaN).  Needs the
+ *   particle filter on (hc_set_filter first); HC_ERR_ARG while the EnKF is on, for more than 8 sensors, a node outside the
+ *   column, a sigma that is not finite and > 0, a value outside [0, 1].  Whatever turns the filter off removes the record
+ *   (hc_set_filter included).  hc_step_rows refuses while the record's row count differs from the forcing's.
+ *   With a record set hc_set_filter_shard is refused, and with sharding set so is the record (HC_ERR_ARG either way): the
+ *   sharded filter gathers water-table indices only.  A sweep dealt by whole points runs on any number of handles.
+ * hc_get/set_filter_sm_stats: the sensor table (P n_arow n_sensors 6 entries; checkpoints, the assembly of a sweep over ranks).
+ * Test hooks of the last assimilation, with a record set: hc_get_filter_sm_width (m_s; 0: it took the bin path),
+ *   hc_get_filter_member_weights (q_m [n_members] int64; after a bin-path row q_{b_m}); after a sensor row also
+ *   hc_get_filter_loglik (l_m [n_members]) and hc_get_filter_sm_theta ([n_members][m_s]), and hc_get_filter_weights (the
+ *   bin table) is zero. */
+int hc_set_filter_soil_moisture(hc_handle *h, int32_t n_sensors, const int32_t *nodes, const double *values,
+                                const double *sigma);
+int hc_get_filter_sm_stats(hc_handle *h, double *table, int64_t n_entries);
+int hc_set_filter_sm_stats(hc_handle *h, const double *table, int64_t n_entries);
+int hc_get_filter_sm_width(hc_handle *h, int32_t *width);
+int hc_get_filter_member_weights(hc_handle *h, int64_t *q);
+int hc_get_filter_loglik(hc_handle *h, double *l);
+int hc_get_filter_sm_theta(hc_handle *h, double *theta);
+
 /* Ensemble Kalman filter on the well's water table (stochastic EnKF: perturbed observations, Evensen 1994 / Burgers et al.
  * 1998).  It moves every member's psi by the sample covariance between psi and the observed quantity; noise is untouched.
  *   Analysis rows, launches and order: as for hc_set_filter -- r >= 1, r % stride == 0 and wtd_obs[r] >= 0 (as it stands
@@ -627,8 +677,8 @@ int hc_get_enkf_shard(hc_handle *h, int64_t *n_global, int64_t *first_global);
  *   Both callbacks are called once per assimilation on every handle, also when nothing is routed (equal weights, Q = 0:
  *   the ancestry is the identity), so the handles' calls pair up.  All handles of a point must assimilate the same rows
  *   with the same settings.  A non-zero return of either callback fails hc_step_rows with HC_ERR_DEVICE (the states are
- *   then unusable).  No floating-point arithmetic on this path.  Sensors are not part of the particle filter; a sweep's
- *   points are dealt whole.
+ *   then unusable).  No floating-point arithmetic on this path.  A soil-moisture record (hc_set_filter_soil_moisture) and sharding
+ *   exclude each other: only water-table indices are gathered; a sweep's points are dealt whole.
  * hc_get_filter_shard_words: what device_buf must hold, in 8-byte words: the index vector n_global, the send region
  *   (n_members + n_shards - 1) 2 D and the receive region n_members 2 D (monotonicity bounds both).
  * hc_set_filter_shard: device_buf is caller-owned memory on the handle's device, alive while the shard is set.  Needs the

@@ -2,7 +2,7 @@
 assimilations every 48th row (one a day), one handle each, back to back on one GPU.
 
     python tools/filter_cost.py [--members 262144] [--depth 300] [--days 30] [--warmup 1] [--strides 0,48]
-                                [--sigma 10] [--spread-cm 0] [--json out.json]
+                                [--sigma 10] [--spread-cm 0] [--sensors 0,0] [--json out.json]
 
 Same set-up as tools/wtd_dist_cost.py and bench.py's timed region: synthetic 10-year forcing, Philox noise, the shared
 initial condition of the well's digest (tests/golden/g1_tables_<depth>.npz where it exists, else the hydrostatic profile),
@@ -13,7 +13,9 @@ weights, scan, fill and gather kernels.  `step_kernel_ms` is the step kernel alo
 the unfiltered one's, per assimilation.  A stride may be listed more than once (e.g. 0,48,0,48 to alternate); `kept` is a
 run's rate over the mean of the stride-0 runs.  --spread-cm W starts every member from the initial profile shifted by its
 own offset, uniform over +-W cm: water tables in many bins, unequal weights, and (small sigma) the weight on a few members
-whose slot ranges are long.  Prints one JSON line.
+whose slot ranges are long.  --sensors lists, run by run like --strides, how many soil-moisture sensors join the well
+(hc_set_filter_soil_moisture: nodes 6, 12, 24, ..., a reading of 0.25 with error --sensor-sigma on every assimilation row,
+so every assimilation takes the per-member path).  Prints one JSON line.
 """
 import argparse
 import json
@@ -27,7 +29,8 @@ REPO = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(REPO))
 
 
-def run(cols, forcing, psi0, members, stride, sigma, warmup_days, days, spread_cm=0.0, seed=2024):
+def run(cols, forcing, psi0, members, stride, sigma, warmup_days, days, spread_cm=0.0, seed=2024, sensors=0,
+        sensor_sigma=0.05):
     from hydromodel_amd.stepper import EnsembleStepper, filter_summary
     st = EnsembleStepper(cols, forcing, members)
     try:
@@ -39,6 +42,10 @@ def run(cols, forcing, psi0, members, stride, sigma, warmup_days, days, spread_c
         st.set_noise_philox(seed, 0)
         if stride:
             st.set_filter(stride, sigma, seed)
+        if stride and sensors:
+            values = np.full((forcing.dim_t, sensors), np.nan)
+            values[::stride] = 0.25
+            st.set_filter_soil_moisture([6 * (1 << i) for i in range(sensors)], values, sensor_sigma)
         row = 1
         if warmup_days:
             st.step_rows(row, 48 * warmup_days)
@@ -48,7 +55,7 @@ def run(cols, forcing, psi0, members, stride, sigma, warmup_days, days, spread_c
         out = st.step_rows(row, 48 * days)
         st.lib.hc_synchronize(st.h)
         wall = time.perf_counter() - t0
-        rec = {"stride": stride, "wall_s": wall, "step_kernel_ms": out["kernel_ms"], "launches": out["launches"],
+        rec = {"stride": stride, "sensors": sensors if stride else 0, "wall_s": wall, "step_kernel_ms": out["kernel_ms"], "launches": out["launches"],
                "other_ms": 1e3 * wall - out["kernel_ms"], "column_days_per_s": members * days / wall}
         if stride:
             s = filter_summary(st.filter_table()[0], stride, sigma)
@@ -74,6 +81,8 @@ def main():
     ap.add_argument("--strides", default="0,48")
     ap.add_argument("--sigma", type=float, default=10.0)
     ap.add_argument("--spread-cm", type=float, default=0.0)
+    ap.add_argument("--sensors", default="")
+    ap.add_argument("--sensor-sigma", type=float, default=0.05)
     ap.add_argument("--json", default="")
     args = ap.parse_args()
     from hydromodel_amd.digest import ColumnTables, ForcingDigest
@@ -84,8 +93,12 @@ def main():
     forcing = ForcingDigest(params, synthetic_forcing_frame(args.years), cols)
     fixture = REPO / "tests" / "golden" / f"g1_tables_{args.depth}.npz"
     psi0 = np.load(fixture)["initial_cond"] if fixture.exists() else pressure_head(cols, cols.por_raw)[0]
-    recs = [run(cols, forcing, psi0, args.members, int(s), args.sigma, args.warmup, args.days, args.spread_cm)
-            for s in args.strides.split(",")]
+    strides = [int(s) for s in args.strides.split(",")]
+    sensors = [int(s) for s in args.sensors.split(",")] if args.sensors else [0] * len(strides)
+    if len(sensors) != len(strides):
+        ap.error("--sensors lists one count per entry of --strides")
+    recs = [run(cols, forcing, psi0, args.members, s, args.sigma, args.warmup, args.days, args.spread_cm, sensors=n,
+                sensor_sigma=args.sensor_sigma) for s, n in zip(strides, sensors)]
     base = [r for r in recs if r["stride"] == 0]
     if base:
         rate = float(np.mean([r["column_days_per_s"] for r in base]))
