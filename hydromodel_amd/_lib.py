@@ -98,6 +98,12 @@ EXPORTS = {
     "hc_get_wtd_hist": ([C.c_void_p, _ip, C.c_int64], C.c_int),
     "hc_set_wtd_hist_table": ([C.c_void_p, _ip, C.c_int64], C.c_int),
     "hc_reset_wtd_hist": ([C.c_void_p], C.c_int),
+    "hc_set_theta_hist": ([C.c_void_p, C.c_int32], C.c_int),
+    "hc_get_theta_hist": ([C.c_void_p, _ip, C.c_int64], C.c_int),
+    "hc_set_theta_hist_table": ([C.c_void_p, _ip, C.c_int64], C.c_int),
+    "hc_reset_theta_hist": ([C.c_void_p], C.c_int),
+    "hc_get_theta_hist_outside": ([C.c_void_p, C.POINTER(C.c_uint64)], C.c_int),
+    "hc_get_theta_hist_bins": ([C.c_void_p, _ip], C.c_int),
     "hc_wtd_distribution": ([C.c_int, _ip, _ip, C.c_int64, C.c_int32, _dp, C.c_int32, C.c_double, _lp, _ip, _dp], C.c_int),
     "hc_set_filter": ([C.c_void_p, C.c_int32, C.c_double, C.c_uint64], C.c_int),
     "hc_get_filter_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),

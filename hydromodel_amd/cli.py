@@ -26,6 +26,15 @@ unknown keys, only membership of the 12 is checked):
   ``[T_out][D]``, and for every solved row those of ``transpiration`` / ``lateral_flow`` and ``abs_error_mean`` ``[T]``
   (simulation.py:658-671; ``<key>_mean`` / ``<key>_std``, with ``profile_rows`` and ``profile_count``), added to
   ``<Output_Name>_ensemble.h5`` (a sweep: a leading ``[P]`` axis).  The integer tables are all-reduced with the moments.
+* ``"Ensemble": {..., "Profiles": 48, "Profile_Distribution": {"Bins": 128, "Quantiles": [0.05, 0.5, 0.95]}}``: the members'
+  ``theta_vol`` counted per node on the GPU on the profile rows (include/hydrocol.h hc_set_theta_hist) -- an exact integer
+  histogram over ``Bins`` (32, 64 or 128; default 128) equal bins of [0, 1], summed over the ranks like the moments -- and
+  from it the quantile bands of theta(z): per level, row and node the centre of the first bin whose cumulative count
+  reaches the level's rank (``Quantiles``, required: as ``Distribution.Quantiles``, at most 16, the same rank rule).  Needs
+  ``"Profiles"`` >= 1.  Added to ``<Output_Name>_ensemble.h5``: ``theta_hist`` ``[T_out][D][B]`` int32,
+  ``theta_hist_rows``, ``theta_hist_count``, ``theta_hist_bins``, ``theta_hist_outside`` (values that were NaN or outside
+  [0, 1]: none in a sound run), ``theta_quantile_levels`` and ``theta_quantile`` ``[T_out][L][D]`` (a sweep: a leading
+  ``[P]`` axis), and the run ends with the line `` [Ensemble xN] theta bands: L levels on R rows, B bins``.
 * ``"Ensemble": {..., "Distribution": {"Stride": 48, "Quantiles": [0.05, 0.5, 0.95]}}``: the members' water-table index
   counted per row on the GPU -- every 48th forcing row (default 48; 0 = off) a histogram over the depth grid, summed over
   the ranks like the moments -- and from it the quantile depths (NumPy's ``method="inverted_cdf"``; default levels 0.05,
@@ -158,6 +167,7 @@ def main(params_file=None, data_file=None, seed=None, device=0, gpus=None, _sett
     try:
         if params.get("Ensemble"):
             distribution_settings(params["Ensemble"])      # a bad Distribution block fails before any GPU is touched
+            profile_distribution_settings(params["Ensemble"])
         n_gpus = multigpu.requested_gpus(gpus, params)
         if params.get("Ensemble"):
             filter_settings(params["Ensemble"], n_gpus)     # so does a bad Filter block
@@ -222,6 +232,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     from .digest import ColumnTables, ForcingDigest, load_site_well
     from .ensemble import EnsembleSimulation
     dist_stride, dist_levels = distribution_settings(ens)
+    theta = profile_distribution_settings(ens)
     filt = filter_settings(ens, ranks.world)
     enkf = enkf_settings(ens, ranks.world)
     sm = soil_moisture_settings(ens, ranks.world)
@@ -239,7 +250,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     rows = min(days * 48, forcing.dim_t - 1)
     if ens.get("Points"):
         return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels, filt,
-                          enkf, record, scheme, window, frecord)
+                          enkf, record, scheme, window, frecord, theta)
     sharded = enkf_sharded(ens)
     fsharded = filter_sharded(ens)
     if sharded:
@@ -260,7 +271,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     sim = EnsembleSimulation(cols, forcing, hi - lo, seed=int(ens.get("Seed", 0)), device=device, member_offset=lo,
                              noise=str(ens.get("Noise", "philox")).lower(),
                              spinup=str(ens.get("Spinup", "shared")).lower(), profile_stride=stride,
-                             wtd_hist_stride=dist_stride, **_filter_kwargs(filt, frecord),
+                             wtd_hist_stride=dist_stride, theta_hist_bins=theta[0], **_filter_kwargs(filt, frecord),
                              **_enkf_kwargs(enkf, record, scheme, window), **shard_kw)
     label = f"Ensemble x{n_members}"
     _step_all(sim, rows, label, ranks)
@@ -288,6 +299,9 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     tables, crps_line = _reduce_optional(ranks, sim, [0], [cols], forcing, stride, dist_stride, dist_levels, device,
                                          label, keep_points=False)
     extra.update(tables)
+    ttables, theta_line = _reduce_theta(ranks, sim, [0], 1, forcing.dim_t, cols.dim_d, stride, theta, label,
+                                        keep_points=False)
+    extra.update(ttables)
     # the filters' tables describe the one point: every rank of a sharded run holds the same ones, and rank 0's are taken
     # (placed by it alone; a sum over the ranks would count them world times)
     eids = [0] if ranks.rank == 0 else []
@@ -324,6 +338,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
         print(sm_line)
     if window_line:
         print(window_line)
+    if theta_line:
+        print(theta_line)
     sim.close()
 
 
@@ -357,6 +373,49 @@ def distribution_settings(ens):
             raise ValueError(f" Ensemble: Distribution.Quantiles: {q!r} lies outside [0, 1].")
     stride = int(stride)
     return (stride, tuple(float(q) for q in levels)) if stride else (0, None)
+
+
+PROFILE_DISTRIBUTION_KEYS = ("Bins", "Quantiles")
+
+
+def profile_distribution_settings(ens):
+    """Ensemble.Profile_Distribution -> (bins, quantile levels); (0, None) when absent.  Pure: runs before any GPU call, and
+    a bad value is a ValueError (message + exit status 1).  The histograms live on the profile rows, so the block needs
+    ``"Profiles"`` >= 1."""
+    import math
+    from numbers import Real
+    block = ens.get("Profile_Distribution")
+    if block is None:
+        return 0, None
+    if not isinstance(block, dict):
+        raise ValueError(f" Ensemble: Profile_Distribution = {block!r} must be an object such as "
+                         f"{{\"Bins\": 128, \"Quantiles\": [0.05, 0.5, 0.95]}}.")
+    unknown = sorted(set(block) - set(PROFILE_DISTRIBUTION_KEYS))
+    if unknown:
+        raise ValueError(f" Ensemble: Profile_Distribution has unknown keys {unknown} "
+                         f"(known: {list(PROFILE_DISTRIBUTION_KEYS)}).")
+    profiles = ens.get("Profiles", 0)
+    if (isinstance(profiles, bool) or not isinstance(profiles, Real) or not math.isfinite(profiles)
+            or profiles != int(profiles) or profiles < 1):
+        raise ValueError(f" Ensemble: Profile_Distribution needs the profile rows: Profiles = {profiles!r} must be a row "
+                         f"stride >= 1.")
+    bins = block.get("Bins", 128)
+    if isinstance(bins, bool) or not isinstance(bins, Real) or bins not in (32, 64, 128):
+        raise ValueError(f" Ensemble: Profile_Distribution.Bins = {bins!r} must be 32, 64 or 128.")
+    if "Quantiles" not in block:
+        raise ValueError(" Ensemble: Profile_Distribution.Quantiles (a list of levels in [0, 1]) is required.")
+    levels = block["Quantiles"]
+    if not isinstance(levels, (list, tuple)) or not levels:
+        raise ValueError(f" Ensemble: Profile_Distribution.Quantiles = {levels!r} must be a non-empty list of levels in "
+                         f"[0, 1].")
+    if len(levels) > 16:
+        raise ValueError(f" Ensemble: Profile_Distribution.Quantiles holds {len(levels)} levels; at most 16 are supported.")
+    for q in levels:
+        if isinstance(q, bool) or not isinstance(q, Real) or not math.isfinite(q):
+            raise ValueError(f" Ensemble: Profile_Distribution.Quantiles: {q!r} is not a number.")
+        if not 0.0 <= q <= 1.0:
+            raise ValueError(f" Ensemble: Profile_Distribution.Quantiles: {q!r} lies outside [0, 1].")
+    return int(bins), tuple(float(q) for q in levels)
 
 
 FILTER_KEYS = ("Stride", "Sigma_cm", "Seed", "Sharded", "Soil_Moisture")
@@ -878,8 +937,40 @@ def _reduce_optional(ranks, sim, ids, cols_all, forcing, stride, dist_stride, di
     return out, crps_line
 
 
+def _reduce_theta(ranks, sim, ids, P, T, D, stride, theta, label, keep_points):
+    """The soil-moisture histograms (``theta``: bins, levels) from this rank's handle ``sim`` (None: no points), its points
+    ``ids`` placed in the run's [P] table and summed over the ranks like the water-table histograms -- int32 counts as
+    int64, the outside count with them -- then the quantile bands and the closing line (rank 0)."""
+    import numpy as np
+    from .multigpu import place_points
+    from .stepper import stride_rows, theta_distribution
+    bins, levels = theta
+    if not bins:
+        return {}, None
+    local = (sim.stepper.theta_hist_table() if sim is not None else
+             np.zeros((0, stride_rows(T, stride), D, bins), dtype=np.int32))
+    hist = place_points(local, ids, P, ranks)
+    outside = int(ranks.allreduce_sum(np.array([sim.stepper.theta_hist_outside() if sim is not None else 0],
+                                               dtype=np.int64))[0])
+    hist = hist if keep_points else hist[0]
+    if ranks.rank != 0:
+        return {}, None
+    dist = theta_distribution(hist, levels, bins, stride)
+    out = {"theta_hist": np.asarray(hist, dtype=np.int32), "theta_hist_rows": np.asarray(dist["rows"], dtype=np.int64),
+           "theta_hist_count": np.asarray(dist["count"], dtype=np.int64), "theta_hist_bins": np.array(bins, dtype=np.int64),
+           "theta_hist_outside": np.array(outside, dtype=np.int64),
+           "theta_quantile_levels": np.asarray(dist["levels"], dtype=np.float64),
+           "theta_quantile": np.asarray(dist["quantiles"], dtype=np.float64)}
+    n = int((np.asarray(dist["count"]).reshape(-1, dist["rows"].size) > 0).any(axis=0).sum())
+    line = f" [{label}] theta bands: {len(levels)} levels on {n} rows, {bins} bins"
+    if outside:
+        line += f" ({outside} values outside [0, 1])"
+    return out, line
+
+
 def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride=0, dist_levels=None,
-               filt=(0, None, None), enkf=(0, None, None, None), record=None, scheme=None, window=None, frecord=None):
+               filt=(0, None, None), enkf=(0, None, None, None), record=None, scheme=None, window=None, frecord=None,
+               theta=(0, None)):
     """Parameter points x members: this rank's points in one handle (ensemble.SweepSimulation), the whole table assembled
     over the ranks (multigpu.assemble_points)."""
     import numpy as np
@@ -905,8 +996,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     label = f"Sweep {P} points x{n_members}"
     if mine:
         sim = SweepSimulation(points, forcing, n_members, seed=int(ens.get("Seed", 0)), device=device, point_ids=mine,
-                              profile_stride=stride, wtd_hist_stride=dist_stride, **_filter_kwargs(filt, frecord),
-                              **_enkf_kwargs(enkf, record, scheme, window))
+                              profile_stride=stride, wtd_hist_stride=dist_stride, theta_hist_bins=theta[0],
+                              **_filter_kwargs(filt, frecord), **_enkf_kwargs(enkf, record, scheme, window))
         _step_all(sim, rows, label, ranks)
         table = sim.moments()
         for j, k in enumerate(mine):
@@ -920,6 +1011,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     tables, crps_line = _reduce_optional(ranks, sim, mine, cols_all, forcing, stride, dist_stride, dist_levels, device,
                                          label, keep_points=True)
     arrays.update(tables)
+    ttables, theta_line = _reduce_theta(ranks, sim, mine, P, T, ref.dim_d, stride, theta, label, keep_points=True)
+    arrays.update(ttables)
     ftables, filter_line = _reduce_filter(ranks, sim, mine, P, T, filt, label, keep_points=True)
     arrays.update(ftables)
     fstables, fsm_line = _reduce_sm(ranks, sim, mine, P, T, filt[0], frecord, label, keep_points=True, owner="filter")
@@ -948,6 +1041,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
         print(sm_line)
     if window_line:
         print(window_line)
+    if theta_line:
+        print(theta_line)
 
 
 def run_cli(argv=None):

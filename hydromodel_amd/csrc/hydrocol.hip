@@ -72,7 +72,7 @@ struct DevBuf {
 };
 
 // A table the handle accumulates over the members -- the per-row water-table moments, the profile statistics, the
-// water-table histograms: its device buffer and the shape key it was made for.  `ensure` re-creates it, zeroed, when the
+// water-table and soil-moisture histograms: its device buffer and the shape key it was made for.  `ensure` re-creates it, zeroed, when the
 // key changed or after `invalidate`.
 template <typename T>
 struct AccTable {
@@ -162,6 +162,10 @@ struct hc_handle {
     // ensemble water-table histograms (hc_set_wtd_hist): int32 [P][n_hrow][D], keyed like the profile table
     int hist_stride = 0;         // 0: off
     AccTable<int> hist{"entries"};
+    // ensemble soil-moisture histograms (hc_set_theta_hist): int32 [P][n_prow][D][B] and the outside count in two more
+    // entries, on the profile rows and keyed like the profile table
+    int thist_bins = 0;          // 0: off
+    AccTable<int> thist{"entries"};
     // particle filter on the well's water table (hc_set_filter): diagnostics float64 [P][n_arow][4] keyed by
     // (points, rows, stride), the second state / base buffers of the gather, the last assimilation's q_b, {Q, r} and
     // ancestors (test hooks), and the host copy of wtd_obs that decides which rows are assimilated
@@ -379,6 +383,70 @@ __global__ __launch_bounds__(PROF_TILE * PROF_WAVES) void profile_kernel(
     if (ovf) atomicAdd(ovf_word, (unsigned long long)ovf);
     if (blockIdx.x == 0 && threadIdx.x == 0)
         atomicAdd(reinterpret_cast<unsigned long long *>(pcnt + (size_t)point * n_prow + prow), (unsigned long long)(m1 - m0));
+}
+
+// ---- ensemble soil-moisture histograms (hc_set_theta_hist, include/hydrocol.h)
+// theta of one profile row, counted per node: profile_kernel's shape (grid x = 64-node tiles, y = member slices of one
+// point, z = point; lane = node, wave w reads members w, w + 4, ... of its slice, every load 64 contiguous doubles of one
+// member's row) and its theta.  The block counts in LDS, bin-major: uint32 [B][64], word b 64 + lane.  Lane l of a
+// ds_add_u32 is then on bank l of its half-wave whatever bins the members fall in, so lanes never share an address or a
+// bank (the opposite of wtd_hist_kernel, whose lanes share one address and are grouped by ballot first); only the four
+// waves of a block meet, through the LDS atomic.  B = 128 is 32 KiB a block, the most that leaves four or five blocks to
+// a CU.  The members of one node sit in a few bins, so after the barrier only the nonzero counters go to the table, with
+// int32 atomics (integer adds: order-independent), and the block's outside count with one 64-bit atomic when there is
+// any.  Lanes past the column take no part; an empty slice writes nothing.
+__global__ __launch_bounds__(PROF_TILE * PROF_WAVES) void theta_hist_kernel(
+    const StepArgs A, const double *node_tabs, int special, const double *stage, const int *wtd_obs, long long row,
+    long long prow, long long n_prow, int snapshot, long long members_per_block, int B, int *hist,
+    unsigned long long *outside_word)
+{
+    if (!snapshot && wtd_obs[row] < 0) return;
+    const int D = A.D;
+    const int lane = threadIdx.x % PROF_TILE, wave = threadIdx.x / PROF_TILE;
+    const int i = blockIdx.x * PROF_TILE + lane;
+    const long long point = blockIdx.z;
+    const long long end = (point + 1) * A.members_per_point;
+    const long long m0 = point * A.members_per_point + (long long)blockIdx.y * members_per_block;
+    const long long m1 = m0 + members_per_block < end ? m0 + members_per_block : end;
+    if (m0 >= m1) return;                    // (the whole block: nothing is shared yet)
+    extern __shared__ unsigned theta_bins[];     // [B][PROF_TILE]
+    __shared__ unsigned outside_sum;
+    const int words = B * PROF_TILE;
+    for (int k = threadIdx.x; k < words; k += PROF_TILE * PROF_WAVES) theta_bins[k] = 0;
+    if (threadIdx.x == 0) outside_sum = 0;
+    __syncthreads();
+    if (i < D) {
+        const ColumnDev P = A.P[point];
+        const double *nt = node_tabs + (size_t)point * 3 * D;
+        const double por = nt[i], meank = nt[D + i], noisec = nt[2 * D + i];
+        const double mk = meank == 0.0 ? 1.0e-7 : meank;
+        const double rdelta = 1.0 / (por - P.theta_res), logm = log(mk), invm2 = 1.0 / (mk * mk);
+        const double nb = (double)B;
+        unsigned outside = 0;
+        for (long long m = m0 + wave; m < m1; m += PROF_WAVES) {
+            const double psi = stage[(size_t)m * D + i];
+            double th, K, C, kb, pf;
+            if (special)
+                model_cell<true>(P, psi, por, rdelta, logm, invm2, noisec, 0.0, th, K, C, kb, pf);
+            else
+                model_cell<false>(P, psi, por, rdelta, logm, invm2, noisec, 0.0, th, K, C, kb, pf);
+            if (th >= 0.0 && th <= 1.0) {    // (false for a NaN)
+                const int b = th == 1.0 ? B - 1 : (int)(th * nb);      // theta B is exact: B is a power of two
+                atomicAdd(&theta_bins[b * PROF_TILE + lane], 1u);
+            } else {
+                outside++;
+            }
+        }
+        if (outside) atomicAdd(&outside_sum, outside);
+    }
+    __syncthreads();
+    int *t = hist + ((size_t)point * n_prow + prow) * D * B;
+    for (int k = threadIdx.x; k < words; k += PROF_TILE * PROF_WAVES) {
+        const unsigned c = theta_bins[k];
+        const int node = blockIdx.x * PROF_TILE + k % PROF_TILE;
+        if (c && node < D) atomicAdd(t + (size_t)node * B + k / PROF_TILE, (int)c);
+    }
+    if (threadIdx.x == 0 && outside_sum) atomicAdd(outside_word, (unsigned long long)outside_sum);
 }
 
 // transpiration / lateral flow of every solved row of a launch, the member count and sum |obs - wtd| (abs_error in grid
@@ -2252,6 +2320,27 @@ int ensure_hist(hc_handle *h)
     return h->hist.ensure(h->n_points, h->n_rows, h->p.dim_d, hist_entries(h));
 }
 
+// the soil-moisture histogram table (hc_set_theta_hist): [P][n_prow][D][B] int32 on the profile rows, then the outside
+// count (one uint64 in two entries; the bins before it are a multiple of 32 entries, so it is 8-byte aligned)
+int64_t thist_bins_total(const hc_handle *h)
+{
+    return (int64_t)h->n_points * prof_layout(h).n_prow * h->p.dim_d * h->thist_bins;
+}
+int ensure_thist(hc_handle *h)
+{
+    if (h->thist_bins <= 0) return fail(HC_ERR_ARG, "soil-moisture histograms are off (hc_set_theta_hist)");
+    if (h->prof_stride <= 0)
+        return fail(HC_ERR_ARG, "soil-moisture histograms need the profile statistics (hc_set_profile_stats)");
+    if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
+    if (h->n_members / std::max(h->n_points, 1) > INT32_MAX)
+        return fail(HC_ERR_ARG, "soil-moisture histograms: %lld members per point do not fit an int32 bin",
+                    (long long)(h->n_members / std::max(h->n_points, 1)));
+    if (thist_bins_total(h) > HC_WTD_HIST_MAX_ENTRIES)
+        return fail(HC_ERR_ARG, "soil-moisture histograms: %lld entries exceed HC_WTD_HIST_MAX_ENTRIES (take a longer "
+                    "profile stride or fewer bins)", (long long)thist_bins_total(h));
+    return h->thist.ensure(h->n_points, h->n_rows, h->p.dim_d, thist_bins_total(h) + 2);
+}
+
 // An assimilation table keyed by (points, rows, stride): `per_row` entries per point and analysis row (every stride-th
 // row), created on a fresh key as NaN with each slot's count 0 (`width` entries a slot; 0: all NaN)
 int ensure_da_table(hc_handle *h, AccTable<double> &t, int64_t stride, int64_t per_row, int width)
@@ -2653,7 +2742,7 @@ int hc_destroy(hc_handle *h)
     h->Pdev.release(); h->iodev.release();
     h->point_base.release(); h->point_order.release(); h->point_cost.release();
     h->daylight.release(); h->refresh.release(); h->wtd_u16.release(); h->moments.release(); h->counters.release();
-    h->prof.release(); h->hist.release();
+    h->prof.release(); h->hist.release(); h->thist.release();
     assimilation_off(h);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -3024,6 +3113,22 @@ int launch_profile(hc_handle *h, const StepArgs &A, const ProfLayout &L, const d
     return HC_OK;
 }
 
+// the soil-moisture histogram of the same row, from the same states, on the same grid
+int launch_theta_hist(hc_handle *h, const StepArgs &A, const ProfLayout &L, const double *stage, int64_t row, int snapshot)
+{
+    const long long mpp = h->n_members / h->n_points;
+    const dim3 grid((unsigned)((h->p.dim_d + PROF_TILE - 1) / PROF_TILE),
+                    (unsigned)((mpp + PROF_MEMBERS_PER_BLOCK - 1) / PROF_MEMBERS_PER_BLOCK), (unsigned)h->n_points);
+    const int B = h->thist_bins;
+    int *t = h->thist.buf.p;
+    hipLaunchKernelGGL(theta_hist_kernel, grid, dim3(PROF_TILE * PROF_WAVES), (size_t)B * PROF_TILE * sizeof(unsigned),
+                       h->stream, A, h->node_tabs.p, (int)h->use_special(), stage, h->wtd_obs.p, (long long)row,
+                       (long long)(row / h->prof_stride), (long long)L.n_prow, snapshot, PROF_MEMBERS_PER_BLOCK, B, t,
+                       reinterpret_cast<unsigned long long *>(t + (h->thist.n - 2)));
+    HIP_TRY(hipGetLastError());
+    return HC_OK;
+}
+
 constexpr long long HIST_MEMBERS_PER_BLOCK = 4096;
 
 // the histogram rows among launch rows [row0, row0 + chunk) of the water-table indices in wtd_u16
@@ -3247,6 +3352,8 @@ int accumulate(hc_handle *h, const StepArgs &A, const hc_step_args *a, const Chu
         if (!c.stage_all && !(c.end_on_profile && r == c.rows - 1))
             return fail(HC_ERR_DEVICE, "profile row %lld not staged (internal error)", (long long)(c.row0 + r));
         if (int rc = launch_profile(h, A, PL, stage, c.row0 + r, 0)) return rc;
+        if (h->thist_bins > 0)
+            if (int rc = launch_theta_hist(h, A, PL, stage, c.row0 + r, 0)) return rc;
     }
     long long *t = h->prof.buf.p;
     hipLaunchKernelGGL(flux_stats_kernel, dim3(c.rows, h->n_points), dim3(256), 0, h->stream, h->diag.p, h->wtd_u16.p,
@@ -3785,6 +3892,7 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
     // each launch): spin-up solves accumulate nothing
     const bool prof_on = h->prof_stride > 0 && !a->spinup, hist_on = h->hist_stride > 0 && !a->spinup;
     if ((prof_on && (rc = ensure_prof(h))) || (hist_on && (rc = ensure_hist(h)))) return rc;
+    if (prof_on && h->thist_bins > 0 && (rc = ensure_thist(h))) return rc;
     // the particle filter (hc_set_filter): spin-up solves are never filtered
     if (a->spinup && h->filt_host())
         return fail(HC_ERR_ARG, "spin-up solves with the particle filter on in a Philox run: set the filter after the spin-up");
@@ -3945,6 +4053,8 @@ int hc_set_profile_stats(hc_handle *h, int32_t stride)
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->prof_stride = stride;
     h->prof.release();           // re-created, zeroed, when on
+    h->thist_bins = 0;           // the soil-moisture histograms are keyed to the profile rows: off
+    h->thist.release();
     return stride == 0 ? HC_OK : ensure_prof(h);
 }
 
@@ -3967,7 +4077,11 @@ int hc_profile_snapshot(hc_handle *h, int64_t row)
         return fail(HC_ERR_ARG, "hc_profile_snapshot: row %lld is not a profile row (stride %d, %lld rows)", (long long)row,
                     h->prof_stride, (long long)h->n_rows);
     HIP_TRY(hipSetDevice(h->device));
+    if (h->thist_bins > 0)
+        if (int rc2 = ensure_thist(h)) return rc2;
     if (int rc2 = launch_profile(h, A, prof_layout(h), h->psi.p, row, 1)) return rc2;
+    if (h->thist_bins > 0)
+        if (int rc2 = launch_theta_hist(h, A, prof_layout(h), h->psi.p, row, 1)) return rc2;
     HIP_TRY(hipStreamSynchronize(h->stream));
     return HC_OK;
 }
@@ -4037,6 +4151,59 @@ int hc_reset_wtd_hist(hc_handle *h)
 {
     if (!h) return fail(HC_ERR_ARG, "hc_reset_wtd_hist: bad argument");
     return table_reset(h, h->hist, ensure_hist);
+}
+
+int hc_set_theta_hist(hc_handle *h, int32_t n_bins)
+{
+    if (!h) return fail(HC_ERR_ARG, "hc_set_theta_hist: bad argument");
+    if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->thist.release();          // re-created, zeroed, when on
+    h->thist_bins = 0;
+    if (n_bins == 0) return HC_OK;
+    if (n_bins != 32 && n_bins != 64 && n_bins != 128)
+        return fail(HC_ERR_ARG, "hc_set_theta_hist: %d bins (32, 64 or 128; 0 = off)", (int)n_bins);
+    h->thist_bins = n_bins;
+    const int rc = ensure_thist(h);          // (its refusals come before anything is allocated)
+    if (rc != HC_OK) h->thist_bins = 0, h->thist.release();      // refused: off
+    return rc;
+}
+
+int hc_get_theta_hist(hc_handle *h, int32_t *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_get_theta_hist: bad argument");
+    return table_copy(h, h->thist, ensure_thist, hipMemcpyDeviceToHost, table, n_entries, "hc_get_theta_hist");
+}
+
+int hc_set_theta_hist_table(hc_handle *h, const int32_t *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_set_theta_hist_table: bad argument");
+    return table_copy(h, h->thist, ensure_thist, hipMemcpyHostToDevice, const_cast<int32_t *>(table), n_entries,
+                      "hc_set_theta_hist_table");
+}
+
+int hc_reset_theta_hist(hc_handle *h)
+{
+    if (!h) return fail(HC_ERR_ARG, "hc_reset_theta_hist: bad argument");
+    return table_reset(h, h->thist, ensure_thist);
+}
+
+int hc_get_theta_hist_outside(hc_handle *h, uint64_t *count)
+{
+    if (!h || !count) return fail(HC_ERR_ARG, "hc_get_theta_hist_outside: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = ensure_thist(h)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(count, h->thist.buf.p + (h->thist.n - 2), 8, hipMemcpyDeviceToHost));
+    return HC_OK;
+}
+
+int hc_get_theta_hist_bins(hc_handle *h, int32_t *n_bins)
+{
+    if (!h || !n_bins) return fail(HC_ERR_ARG, "hc_get_theta_hist_bins: bad argument");
+    *n_bins = h->thist_bins;
+    return HC_OK;
 }
 
 int hc_wtd_distribution(int device, const int32_t *hist, const int32_t *obs_idx, int64_t n_rows, int32_t D,

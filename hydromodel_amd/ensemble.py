@@ -11,7 +11,7 @@ import numpy as np
 from .digest import inverse_retention
 from .stepper import (ENKF_METHODS, ENKF_WIDTH, SM_WIDTH, WINDOW_WIDTH, EnsembleStepper, enkf_sm_summary, enkf_summary,
                       enkf_window_settings, enkf_window_summary, filter_sm_summary, filter_summary,
-                      moments_to_mean_std, wtd_distribution)
+                      moments_to_mean_std, theta_distribution, wtd_distribution)
 
 
 def pressure_head(cols, theta):
@@ -96,6 +96,8 @@ class _Run:
 
     profile_stride > 0: ensemble profile statistics (psi, theta every ``profile_stride``-th row from row 0 = the initial
     states, fluxes and abs_error every solved row) accumulated on the device: :meth:`profile_stats`.
+    theta_hist_bins > 0 (32, 64 or 128; needs profile_stride): exact histograms of theta_vol at every node of the profile
+    rows, counted on the device: :meth:`theta_distribution` (quantile bands of theta(z)).
     wtd_hist_stride > 0: per-row histograms of the members' water-table index every ``wtd_hist_stride``-th row, counted on
     the device: :meth:`wtd_distribution` (quantiles, CRPS against the well).
     filter_stride > 0: a bootstrap particle filter on the well's water table every ``filter_stride``-th row with an
@@ -123,10 +125,15 @@ class _Run:
     def _start_tables(self, profile_stride, wtd_hist_stride, filter_stride=0, filter_sigma_cm=None, filter_seed=None,
                       enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None,
                       enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=(),
-                      filter_soil_moisture=None):
+                      filter_soil_moisture=None, theta_hist_bins=0):
         self.profile_stride = int(profile_stride)
+        self.theta_hist_bins = int(theta_hist_bins or 0)
+        if self.theta_hist_bins and not self.profile_stride:
+            raise ValueError("theta_hist_bins needs the profile statistics (profile_stride > 0)")
         if self.profile_stride:
             self.stepper.set_profile_stats(self.profile_stride)
+            if self.theta_hist_bins:
+                self.stepper.set_theta_hist(self.theta_hist_bins)
             self.stepper.profile_snapshot(0)       # psi[0], theta_vol[0]: the state before any solve
         self.wtd_hist_stride = int(wtd_hist_stride)
         if self.wtd_hist_stride:
@@ -183,6 +190,17 @@ class _Run:
         abs_error_mean [T], rows, count (stepper.profile_tables_to_stats), with a leading [P] axis when the handle holds
         several points; ``table``: e.g. the sum over ranks."""
         return self.stepper.profile_stats(table)
+
+    def theta_hist_table(self):
+        """[n_prow][D][B] int32: members per bin of theta at every node of every profile row (stepper.theta_hist_of); a
+        sweep: [P][n_prow][D][B]."""
+        return self.stepper.theta_hist_table().reshape(self._lead + (-1, self.cols.dim_d, self.theta_hist_bins))
+
+    def theta_distribution(self, levels=(0.05, 0.25, 0.5, 0.75, 0.95), table=None):
+        """Quantile bands of theta(z) per profile row (stepper.theta_distribution), with the leading shape of the table;
+        ``table``: e.g. the sum over ranks.  Other levels need no rerun."""
+        t = self.theta_hist_table() if table is None else table
+        return theta_distribution(t, levels, self.theta_hist_bins, self.profile_stride)
 
     def wtd_hist_table(self):
         """[n_hrow][D] int32: members per water-table index on every histogram row (stepper.wtd_hist_rows); a sweep:
@@ -271,7 +289,7 @@ class EnsembleSimulation(_Run):
     #1 base vector, then one vector per refresh row (simulation.py:426,561,601) -- and uploaded per launch.
     spinup="shared" (default): one spin-up (global member 0's first draw) broadcast to all members;
     spinup="member": every member spins up with its own first draw (`spinup_members_on_gpu`).
-    profile_stride, wtd_hist_stride, filter_stride / filter_sigma_cm / filter_seed, enkf_stride / enkf_sigma_cm /
+    profile_stride, theta_hist_bins, wtd_hist_stride, filter_stride / filter_sigma_cm / filter_seed, enkf_stride / enkf_sigma_cm /
     enkf_localisation_cm / enkf_seed: the optional tables, the particle filter and the EnKF (:class:`_Run`).
     enkf_shard=(n_global, exchange): these members are [member_offset, member_offset + N) of an ensemble of ``n_global``
     whose other members run elsewhere, and the EnKF analyses the whole of it (include/hydrocol.h hc_set_enkf_shard;
@@ -287,7 +305,8 @@ class EnsembleSimulation(_Run):
                  noise="philox", spinup="shared", profile_stride=0, wtd_hist_stride=0, filter_stride=0,
                  filter_sigma_cm=None, filter_seed=None, enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0,
                  enkf_seed=None, enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0,
-                 enkf_window_offsets=(), enkf_shard=None, filter_shard=None, filter_soil_moisture=None):
+                 enkf_window_offsets=(), enkf_shard=None, filter_shard=None, filter_soil_moisture=None,
+                 theta_hist_bins=0):
         if filter_shard is not None and not int(filter_stride or 0):
             raise ValueError("filter_shard needs the particle filter (filter_stride > 0)")
         if filter_shard is not None and filter_soil_moisture is not None:
@@ -299,7 +318,7 @@ class EnsembleSimulation(_Run):
         self._start(cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup)
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
-                           enkf_relaxation, enkf_window_offsets, filter_soil_moisture)
+                           enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins)
         self.enkf_shard = None
         if enkf_shard is not None:
             if not self.enkf_stride:
@@ -405,6 +424,10 @@ class EnsembleSimulation(_Run):
         if self.profile_stride:
             arrays["profile_stride"] = np.array(self.profile_stride, dtype=np.int64)
             arrays["profile_table"] = self.stepper.profile_table()
+        if self.theta_hist_bins:
+            arrays["theta_hist_bins"] = np.array(self.theta_hist_bins, dtype=np.int64)
+            arrays["theta_hist"] = self.stepper.theta_hist_table()
+            arrays["theta_hist_outside"] = np.array(self.stepper.theta_hist_outside(), dtype=np.uint64)
         if self.wtd_hist_stride:
             arrays["wtd_hist_stride"] = np.array(self.wtd_hist_stride, dtype=np.int64)
             arrays["wtd_hist"] = self.stepper.wtd_hist_table()
@@ -462,6 +485,7 @@ class EnsembleSimulation(_Run):
         psi = np.asarray(data["psi"], dtype=float).reshape(n, D)
         stride = int(data["profile_stride"]) if "profile_stride" in data else 0
         hist_stride = int(data["wtd_hist_stride"]) if "wtd_hist_stride" in data else 0
+        theta_bins = int(data["theta_hist_bins"]) if "theta_hist_bins" in data else 0
         filt = int(data["filter_stride"]) if "filter_stride" in data else 0
         fkw = dict(filter_stride=filt, filter_sigma_cm=float(data["filter_sigma_cm"]),
                    filter_seed=int(data["filter_seed"])) if filt else {}
@@ -492,7 +516,7 @@ class EnsembleSimulation(_Run):
             fkw.update(enkf_window_offsets=tuple(int(o) for o in np.asarray(data["enkf_window_offsets"]).reshape(-1)))
         sim = cls(cols, forcing, n, seed=int(data["seed"]), device=device, member_offset=int(data["member_offset"]),
                   psi0=np.asarray(data["initial_cond"], dtype=float).reshape(-1)[:D], flags=flags, profile_stride=stride,
-                  wtd_hist_stride=hist_stride, **fkw)
+                  wtd_hist_stride=hist_stride, theta_hist_bins=theta_bins, **fkw)
         sim.stepper.set_state(psi if n > 1 else psi[0])
         if filt:
             sim.stepper.set_filter_table(np.asarray(data["filter_table"], dtype=np.float64))
@@ -512,6 +536,8 @@ class EnsembleSimulation(_Run):
         sim.stepper.set_moments(np.asarray(data["moments"], dtype=np.int64))
         if stride:
             sim.stepper.set_profile_table(np.asarray(data["profile_table"], dtype=np.int64))
+        if theta_bins:
+            sim.stepper.set_theta_hist_table(np.asarray(data["theta_hist"]), int(data["theta_hist_outside"]))
         if hist_stride:
             sim.stepper.set_wtd_hist_table(np.asarray(data["wtd_hist"]))
         sim.next_row = int(data["next_row"])
@@ -608,7 +634,7 @@ class SweepSimulation(_Run):
                  point_ids=None, profile_stride=0, wtd_hist_stride=0, filter_stride=0, filter_sigma_cm=None,
                  filter_seed=None, enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None,
                  enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=(),
-                 filter_soil_moisture=None):
+                 filter_soil_moisture=None, theta_hist_bins=0):
         self.points = list(cols_list)
         self.P, self.n = len(self.points), int(n_members)
         self._lead = (self.P,)
@@ -637,7 +663,7 @@ class SweepSimulation(_Run):
             self.stepper.set_point_member_bases(self.bases)
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
-                           enkf_relaxation, enkf_window_offsets, filter_soil_moisture)
+                           enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins)
         self.next_row, self.kernel_ms, self.launches = 1, 0.0, 0
 
     def _spinup(self, flags):

@@ -76,6 +76,7 @@ class EnsembleStepper:
         self.last_launches = 0
         self.profile_stride = 0
         self.wtd_hist_stride = 0
+        self.theta_hist_bins = 0
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = 0, 0.0, 0
         self.filter_sm_nodes = None
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
@@ -263,6 +264,7 @@ class EnsembleStepper:
             raise ValueError(f"profile stride must be >= 0, got {stride}")
         L.check(self.lib.hc_set_profile_stats(self.h, stride))
         self.profile_stride = stride
+        self.theta_hist_bins = 0          # keyed to the profile rows: the library turned it off
 
     def profile_snapshot(self, row=0):
         L.check(self.lib.hc_profile_snapshot(self.h, int(row)))
@@ -325,6 +327,45 @@ class EnsembleStepper:
 
     def reset_wtd_hist(self):
         L.check(self.lib.hc_reset_wtd_hist(self.h))
+
+    # -- ensemble soil-moisture histograms (include/hydrocol.h hc_set_theta_hist) ---------------------------------------
+    def set_theta_hist(self, bins):
+        """Count every member's theta_vol at every node of the profile rows into ``bins`` (32, 64 or 128) equal bins of
+        [0, 1] (0 = off); needs :meth:`set_profile_stats`, and comes before :meth:`profile_snapshot` for row 0 to be
+        counted."""
+        bins = int(bins)
+        self.theta_hist_bins = 0
+        L.check(self.lib.hc_set_theta_hist(self.h, bins))
+        self.theta_hist_bins = bins
+
+    def _theta_hist_raw(self):
+        t = np.zeros(self.P * stride_rows(self.T, self.profile_stride) * self.D * self.theta_hist_bins + 2, dtype=np.int32)
+        L.check(self.lib.hc_get_theta_hist(self.h, L.iptr(t), t.size))
+        return t
+
+    def theta_hist_table(self):
+        """[P][n_prow][D][B] int32: members of each point per bin of theta, node and profile row (:func:`theta_hist_of`)."""
+        return self._theta_hist_raw()[:-2].reshape(self.P, -1, self.D, self.theta_hist_bins)
+
+    def set_theta_hist_table(self, table, outside=0):
+        """Install a table (a checkpoint's, a sum over handles) and the outside count that goes with it."""
+        t = np.asarray(table)
+        if t.size and (t.min() < 0 or t.max() > INT32_MAX):
+            raise ValueError("histogram counts must lie in [0, 2^31 - 1]")
+        if not 0 <= int(outside) < 1 << 64:
+            raise ValueError("the outside count must lie in [0, 2^64)")
+        tail = np.array([int(outside)], dtype=np.uint64).view(np.int32)
+        t = np.concatenate([np.ascontiguousarray(t, dtype=np.int32).reshape(-1), tail])
+        L.check(self.lib.hc_set_theta_hist_table(self.h, L.iptr(t), t.size))
+
+    def reset_theta_hist(self):
+        L.check(self.lib.hc_reset_theta_hist(self.h))
+
+    def theta_hist_outside(self):
+        """Members' values that fell in no bin (theta NaN, below 0 or above 1) since the table was made."""
+        out = C.c_uint64()
+        L.check(self.lib.hc_get_theta_hist_outside(self.h, C.byref(out)))
+        return int(out.value)
 
     # -- particle filter on the well's water table (include/hydrocol.h hc_set_filter) ----------------------------------
     def set_filter(self, stride, sigma_cm=None, seed=0):
@@ -988,6 +1029,62 @@ def wtd_distribution(hist, obs_idx, levels, dz, z, device=0, stride=1):
     return {"rows": rows, "count": count, "quantile_idx": qidx.reshape(lead + (n_hrow, lv.size)),
             "quantile_cm": qcm.reshape(lead + (n_hrow, lv.size)), "crps_cm": crps, "crps_mean_cm": crps_mean,
             "levels": lv}
+
+
+# ---- soil-moisture distributions (include/hydrocol.h hc_set_theta_hist) ------------------------------------------------
+THETA_HIST_BINS = (32, 64, 128)
+
+
+def theta_hist_of(theta, bins):
+    """The device's binning of one row restated: ``theta`` [N][D] -> (hist [D][bins] int64, outside).  A value goes to bin
+    floor(theta bins) (theta bins is exact: bins is a power of two), 1.0 to the last bin; NaN, values below 0 and above 1
+    go to no bin and are counted in ``outside``."""
+    bins = int(bins)
+    if bins not in THETA_HIST_BINS:
+        raise ValueError(f"theta histograms have 32, 64 or 128 bins, not {bins}")
+    th = np.asarray(theta, dtype=np.float64)
+    th = th.reshape(-1, th.shape[-1])
+    inside = (th >= 0.0) & (th <= 1.0)
+    with np.errstate(invalid="ignore"):
+        b = np.where(th == 1.0, bins - 1, np.floor(np.where(inside, th, 0.0) * bins)).astype(np.int64)
+    hist = np.zeros((th.shape[1], bins), dtype=np.int64)
+    node = np.broadcast_to(np.arange(th.shape[1]), th.shape)
+    np.add.at(hist, (node[inside], b[inside]), 1)
+    return hist, int((~inside).sum())
+
+
+def theta_distribution(hist, levels, bins=None, stride=1):
+    """Quantile bands of theta(z) from histograms ``hist`` [..., R, D, B] (one table, or [P] of them), in NumPy integers.
+    Level p of a row and node is the centre (b + 0.5) / B of the first bin b whose cumulative count reaches
+    k = max(1, ceil(n p)) in fp64 -- the rank of :func:`wtd_distribution`, numpy.quantile(..., method="inverted_cdf") on the
+    bin index.  Returns ``rows`` [R], ``count`` [..., R] (members per row: every node holds as many, but for values outside
+    the bins), ``quantiles`` [..., R, L, D] (NaN where a node counted nobody), ``levels`` and ``saturated_fraction``
+    [..., R, D]: the share of the node's members in its highest bin occupied on any row of the table -- the bin that holds
+    the node's porosity once any member has been saturated there."""
+    hist = np.asarray(hist)
+    if hist.ndim < 3:
+        raise ValueError(f"histograms must be [..., R, D, B], got shape {hist.shape}")
+    B = hist.shape[-1]
+    if B not in THETA_HIST_BINS or (bins is not None and int(bins) != B):
+        raise ValueError(f"histograms of {B} bins (32, 64 or 128{'' if bins is None else f'; {bins} were named'})")
+    if hist.size and hist.min() < 0:
+        raise ValueError("histogram counts must be >= 0")
+    lv = np.asarray(levels, dtype=np.float64).reshape(-1)
+    if lv.size > WTD_MAX_LEVELS or not np.all((lv >= 0.0) & (lv <= 1.0)):
+        raise ValueError(f"at most {WTD_MAX_LEVELS} quantile levels, each in [0, 1]: got {lv.tolist()}")
+    h = hist.astype(np.int64)
+    cum = np.cumsum(h, axis=-1)                                     # [..., R, D, B]
+    n = cum[..., -1]                                                # [..., R, D]
+    k = np.maximum(1, np.ceil(n[..., None, :].astype(np.float64) * lv[:, None]).astype(np.int64))     # [..., R, L, D]
+    idx = (cum[..., None, :, :] < k[..., None]).sum(axis=-1)        # bins whose cumulative count stays below k
+    q = np.where(n[..., None, :] > 0, (np.minimum(idx, B - 1) + 0.5) / B, np.nan)
+    occupied = h.sum(axis=-3) > 0                                   # [..., D, B] over the rows
+    top = B - 1 - np.argmax(occupied[..., ::-1], axis=-1)           # [..., D]: highest occupied bin (B - 1 if none)
+    in_top = np.take_along_axis(h, np.broadcast_to(top[..., None, :, None], h.shape[:-1] + (1,)), axis=-1)[..., 0]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        sat = np.where(n > 0, in_top / np.maximum(n, 1), np.nan)
+    return {"rows": np.arange(hist.shape[-3], dtype=np.int64) * int(stride), "count": n.max(axis=-1), "quantiles": q,
+            "levels": lv, "saturated_fraction": sat}
 
 
 # ---- particle filter on the host (include/hydrocol.h hc_set_filter) ----------------------------------------------------

@@ -39,6 +39,10 @@
  *   hc_set_wtd_hist, hc_get_wtd_hist, hc_set_wtd_hist_table, hc_reset_wtd_hist, hc_wtd_distribution
  *                      <- wtd_est / abs_error per row (src/simulation.py:612-615) as the ensemble's distribution:
  *                         per-row histograms of the water-table index, quantiles and the CRPS against the well
+ *   hc_set_theta_hist, hc_get_theta_hist, hc_set_theta_hist_table, hc_reset_theta_hist, hc_get_theta_hist_outside,
+ *   hc_get_theta_hist_bins
+ *                      <- theta_vol (src/simulation.py:623) as the ensemble's distribution: per-node histograms of theta on
+ *                         the profile rows, from which the host forms quantile bands of theta(z)
  *   hc_set_filter, hc_get/set_filter_stats, hc_get/set_filter_base, hc_get_filter_ancestors/weights/draw,
  *   hc_set_filter_soil_moisture, hc_get/set_filter_sm_stats, hc_get_filter_sm_width/member_weights/loglik/sm_theta
  *                      <- (new) the ensemble conditioned on wtd_obs (src/simulation.py:582-612): a bootstrap particle filter,
@@ -323,6 +327,32 @@ int hc_reset_wtd_hist(hc_handle *h);
 int hc_wtd_distribution(int device, const int32_t *hist, const int32_t *obs_idx, int64_t n_rows, int32_t D,
                         const double *levels, int32_t n_levels, double dz, int64_t *count, int32_t *quantile_idx,
                         double *crps_cm);
+
+/* Ensemble soil-moisture distribution: theta_vol of the profile rows (hc_set_profile_stats, which must be on) as exact
+ * integer histograms per node.  theta above the water table is a saturating function of psi and the members pile up at the
+ * porosity below it, so a mean +- sigma band can leave [theta_res, porosity]; the histogram makes no such assumption.
+ *   rows: the profile rows, at the profile stride (slot j <-> row j stride, n_prow slots); row 0 is counted by
+ *   hc_profile_snapshot, the others by hc_step_rows from the states the profile statistics read.  Skipped rows (wtd_obs < 0)
+ *   count no members; spin-up solves accumulate nothing.
+ *   bins: B = 32, 64 or 128.  theta is the cell model's theta_vol of the member's psi at the node, with no noise term: the
+ *   value the profile statistics quantise and hc_model_nodes returns, bit for bit.  A member adds one to bin
+ *   b = floor(theta B) of its node (theta B is exact in fp64: the bin depends on theta's bits alone); theta == 1.0 goes to
+ *   bin B - 1; a theta that is NaN, below 0 or above 1 goes to no bin and adds one to the `outside` count.
+ *   table (int32): hist [P][n_prow][D][B], then the outside count as one uint64 in two more entries (low word first):
+ *   P n_prow D B + 2 entries.  Integer adds only: the table does not depend on launch length, member split, point order or
+ *   the number of handles / ranks summed.
+ * hc_set_theta_hist: n_bins 0 = off (default); 32, 64 or 128 (re)creates the table zeroed.  HC_ERR_ARG (and off) when the
+ * profile statistics are off, for any other bin count, for a table of more than HC_WTD_HIST_MAX_ENTRIES bins or a point of
+ * more than 2^31 - 1 members.  hc_set_profile_stats turns it off: it re-creates what the histogram is keyed to.  Like the
+ * profile table it is re-created, zeroed, when the points, the forcing rows or the depth change.  get / set take the
+ * table's size in entries and fail on any other.  The step kernels are the same with the table on or off, and with it off
+ * nothing is launched for it. */
+int hc_set_theta_hist(hc_handle *h, int32_t n_bins);
+int hc_get_theta_hist(hc_handle *h, int32_t *table, int64_t n_entries);
+int hc_set_theta_hist_table(hc_handle *h, const int32_t *table, int64_t n_entries);   /* checkpoint / resume, rank sums */
+int hc_reset_theta_hist(hc_handle *h);
+int hc_get_theta_hist_outside(hc_handle *h, uint64_t *count);
+int hc_get_theta_hist_bins(hc_handle *h, int32_t *n_bins);   /* 0: off */
 
 /* Particle filter on the well's water table (bootstrap filter, systematic resampling in exact integers).
  *   Assimilation rows: r >= 1, r % stride == 0 and wtd_obs[r] >= 0 (wtd_obs as it stands when hc_step_rows reaches the row:
