@@ -35,6 +35,20 @@ unknown keys, only membership of the 12 is checked):
   ``theta_hist_rows``, ``theta_hist_count``, ``theta_hist_bins``, ``theta_hist_outside`` (values that were NaN or outside
   [0, 1]: none in a sound run), ``theta_quantile_levels`` and ``theta_quantile`` ``[T_out][L][D]`` (a sweep: a leading
   ``[P]`` axis), and the run ends with the line `` [Ensemble xN] theta bands: L levels on R rows, B bins``.
+* ``"Ensemble": {..., "Profiles": 48, "Storage": {"Layers_cm": [[0, 100], [100, 300]], "Bins": 128, "Quantiles": [0.05,
+  0.5, 0.95]}}``: the water each depth layer stores, in cm, reduced per member on the GPU on the profile rows
+  (include/hydrocol.h hc_set_layer_storage): S = dz sum theta_vol over the nodes with top <= z < bottom (at most 8 layers,
+  which may overlap; each must hold a node), then the ensemble's mean and sigma from exact integer sums -- the nodes of a
+  column covary, so neither follows from the per-node profile statistics.  ``Bins`` (optional: a power of two in 32 .. 1024)
+  adds the histogram of each layer's mean theta and, with ``Quantiles`` (optional, default 0.05, 0.25, 0.5, 0.75, 0.95;
+  at most 16, the rank rule of ``Distribution.Quantiles``), the quantile bands in cm; ``Quantiles`` without ``Bins`` is
+  refused.  Needs ``"Profiles"`` >= 1.  The tables are summed over the ranks like the moments.  Added to
+  ``<Output_Name>_ensemble.h5``: ``storage_layers_cm``, ``storage_nodes`` ``[L][2]``, ``storage_rows``, ``storage_count``,
+  ``storage_mean_cm``, ``storage_std_cm`` ``[T_out][L]``, ``storage_overflow`` (values the quantisation clamped or that
+  were NaN: none in a sound run) and, with ``Bins``, ``storage_hist`` ``[T_out][L][B]`` int32,
+  ``storage_hist_bins``, ``storage_hist_outside``, ``storage_quantile_levels`` and ``storage_quantile_cm``
+  ``[T_out][Lv][L]`` (a sweep: a leading ``[P]`` axis on the per-row datasets), and the run ends with the line
+  `` [Ensemble xN] storage: L layers on R rows``.
 * ``"Ensemble": {..., "Distribution": {"Stride": 48, "Quantiles": [0.05, 0.5, 0.95]}}``: the members' water-table index
   counted per row on the GPU -- every 48th forcing row (default 48; 0 = off) a histogram over the depth grid, summed over
   the ranks like the moments -- and from it the quantile depths (NumPy's ``method="inverted_cdf"``; default levels 0.05,
@@ -168,6 +182,7 @@ def main(params_file=None, data_file=None, seed=None, device=0, gpus=None, _sett
         if params.get("Ensemble"):
             distribution_settings(params["Ensemble"])      # a bad Distribution block fails before any GPU is touched
             profile_distribution_settings(params["Ensemble"])
+            storage_settings(params["Ensemble"])
         n_gpus = multigpu.requested_gpus(gpus, params)
         if params.get("Ensemble"):
             filter_settings(params["Ensemble"], n_gpus)     # so does a bad Filter block
@@ -233,6 +248,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     from .ensemble import EnsembleSimulation
     dist_stride, dist_levels = distribution_settings(ens)
     theta = profile_distribution_settings(ens)
+    storage = storage_settings(ens)
     filt = filter_settings(ens, ranks.world)
     enkf = enkf_settings(ens, ranks.world)
     sm = soil_moisture_settings(ens, ranks.world)
@@ -242,6 +258,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     cols = ColumnTables(params, load_site_well(params))
     forcing = ForcingDigest(params, water_data, cols)
     record = soil_moisture_record_of(sm, cols, water_data)      # before any GPU call
+    storage_ranges(storage, cols)                               # (its refusals too)
     frecord = soil_moisture_record_of(fsm, cols, water_data, "Filter")
     if cols.flags["PREDICT"] and not ens.get("repair_predict"):
         raise TypeError("'numpy.float64' object cannot be interpreted as an integer")     # richards_pde.py:327-330
@@ -250,7 +267,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     rows = min(days * 48, forcing.dim_t - 1)
     if ens.get("Points"):
         return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels, filt,
-                          enkf, record, scheme, window, frecord, theta)
+                          enkf, record, scheme, window, frecord, theta, storage)
     sharded = enkf_sharded(ens)
     fsharded = filter_sharded(ens)
     if sharded:
@@ -272,7 +289,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
                              noise=str(ens.get("Noise", "philox")).lower(),
                              spinup=str(ens.get("Spinup", "shared")).lower(), profile_stride=stride,
                              wtd_hist_stride=dist_stride, theta_hist_bins=theta[0], **_filter_kwargs(filt, frecord),
-                             **_enkf_kwargs(enkf, record, scheme, window), **shard_kw)
+                             **_enkf_kwargs(enkf, record, scheme, window), **_storage_kwargs(storage), **shard_kw)
     label = f"Ensemble x{n_members}"
     _step_all(sim, rows, label, ranks)
     # the run's one collective: int64 (count, sum idx, sum idx^2) per row, exact and order-independent
@@ -302,6 +319,9 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     ttables, theta_line = _reduce_theta(ranks, sim, [0], 1, forcing.dim_t, cols.dim_d, stride, theta, label,
                                         keep_points=False)
     extra.update(ttables)
+    stor_tables, storage_line = _reduce_storage(ranks, sim, [0], 1, forcing.dim_t, cols, stride, storage, label,
+                                                keep_points=False)
+    extra.update(stor_tables)
     # the filters' tables describe the one point: every rank of a sharded run holds the same ones, and rank 0's are taken
     # (placed by it alone; a sum over the ranks would count them world times)
     eids = [0] if ranks.rank == 0 else []
@@ -340,6 +360,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
         print(window_line)
     if theta_line:
         print(theta_line)
+    if storage_line:
+        print(storage_line)
     sim.close()
 
 
@@ -416,6 +438,79 @@ def profile_distribution_settings(ens):
         if not 0.0 <= q <= 1.0:
             raise ValueError(f" Ensemble: Profile_Distribution.Quantiles: {q!r} lies outside [0, 1].")
     return int(bins), tuple(float(q) for q in levels)
+
+
+STORAGE_KEYS = ("Layers_cm", "Bins", "Quantiles")
+
+
+def storage_settings(ens):
+    """Ensemble.Storage -> (layers_cm, bins, quantile levels or None); None when absent.  Pure: runs before any GPU call,
+    and a bad value is a ValueError (message + exit status 1).  The tables live on the profile rows, so the block needs
+    ``"Profiles"`` >= 1.  ``Bins`` is optional (0: moments only); ``Quantiles`` needs it."""
+    import math
+    from numbers import Real
+    block = ens.get("Storage")
+    if block is None:
+        return None
+    if not isinstance(block, dict):
+        raise ValueError(f" Ensemble: Storage = {block!r} must be an object such as "
+                         f"{{\"Layers_cm\": [[0, 100], [100, 300]], \"Bins\": 128, \"Quantiles\": [0.05, 0.5, 0.95]}}.")
+    unknown = sorted(set(block) - set(STORAGE_KEYS))
+    if unknown:
+        raise ValueError(f" Ensemble: Storage has unknown keys {unknown} (known: {list(STORAGE_KEYS)}).")
+    profiles = ens.get("Profiles", 0)
+    if (isinstance(profiles, bool) or not isinstance(profiles, Real) or not math.isfinite(profiles)
+            or profiles != int(profiles) or profiles < 1):
+        raise ValueError(f" Ensemble: Storage needs the profile rows: Profiles = {profiles!r} must be a row stride >= 1.")
+    layers = block.get("Layers_cm")
+    if not isinstance(layers, (list, tuple)) or not 1 <= len(layers) <= 8:
+        raise ValueError(f" Ensemble: Storage.Layers_cm = {layers!r} must be a list of 1 to 8 [top, bottom] pairs in cm.")
+    for lay in layers:
+        if (not isinstance(lay, (list, tuple)) or len(lay) != 2
+                or any(isinstance(v, bool) or not isinstance(v, Real) or not math.isfinite(v) for v in lay)):
+            raise ValueError(f" Ensemble: Storage.Layers_cm: {lay!r} is not a [top, bottom] pair of numbers in cm.")
+        if not lay[0] < lay[1]:
+            raise ValueError(f" Ensemble: Storage.Layers_cm: {lay!r} must have top < bottom.")
+    bins = block.get("Bins", 0)
+    if "Bins" in block and (isinstance(bins, bool) or not isinstance(bins, Real) or bins not in (32, 64, 128, 256, 512, 1024)):
+        raise ValueError(f" Ensemble: Storage.Bins = {bins!r} must be a power of two in 32 .. 1024.")
+    if "Quantiles" in block and not bins:
+        raise ValueError(" Ensemble: Storage.Quantiles needs Storage.Bins (the bands come from the histogram).")
+    levels = None
+    if bins:
+        levels = block.get("Quantiles", list(DEFAULT_QUANTILES))
+        if not isinstance(levels, (list, tuple)) or not levels:
+            raise ValueError(f" Ensemble: Storage.Quantiles = {levels!r} must be a non-empty list of levels in [0, 1].")
+        if len(levels) > 16:
+            raise ValueError(f" Ensemble: Storage.Quantiles holds {len(levels)} levels; at most 16 are supported.")
+        for q in levels:
+            if isinstance(q, bool) or not isinstance(q, Real) or not math.isfinite(q):
+                raise ValueError(f" Ensemble: Storage.Quantiles: {q!r} is not a number.")
+            if not 0.0 <= q <= 1.0:
+                raise ValueError(f" Ensemble: Storage.Quantiles: {q!r} lies outside [0, 1].")
+        levels = tuple(float(q) for q in levels)
+    return tuple((float(a), float(b)) for a, b in layers), int(bins), levels
+
+
+def storage_ranges(storage, cols):
+    """The node ranges of the block's layers on the column's grid (stepper.layer_ranges), with its refusals in the CLI's
+    words: a layer that holds no node, or one of 4096 cm or more.  None without a block."""
+    from .stepper import STORAGE_MAX_CM, layer_ranges
+    if storage is None:
+        return None
+    try:
+        ranges = layer_ranges(cols.z, storage[0])
+    except ValueError as bad:
+        raise ValueError(f" Ensemble: Storage.Layers_cm: {bad}.") from None
+    for lay, (i0, i1) in zip(storage[0], ranges):
+        if (int(i1) - int(i0)) * float(cols.dz) >= STORAGE_MAX_CM:
+            raise ValueError(f" Ensemble: Storage.Layers_cm: {list(lay)!r} holds {(int(i1) - int(i0)) * float(cols.dz):g} cm "
+                             f"of column; a layer must stay below {STORAGE_MAX_CM:g} cm.")
+    return ranges
+
+
+def _storage_kwargs(storage):
+    return {} if storage is None else dict(storage_layers_cm=storage[0], storage_bins=storage[1])
 
 
 FILTER_KEYS = ("Stride", "Sigma_cm", "Seed", "Sharded", "Soil_Moisture")
@@ -968,9 +1063,58 @@ def _reduce_theta(ranks, sim, ids, P, T, D, stride, theta, label, keep_points):
     return out, line
 
 
+def _reduce_storage(ranks, sim, ids, P, T, cols, stride, storage, label, keep_points):
+    """The layer-storage tables (``storage``: layers, bins, levels) from this rank's handle ``sim`` (None: no points), its
+    points ``ids`` placed in the run's [P] tables and summed over the ranks like the profile table and the soil-moisture
+    histograms -- the overflow and outside counts with them -- then mean, sigma, the quantile bands and the closing line
+    (rank 0)."""
+    import numpy as np
+    from .multigpu import place_points
+    from .stepper import (layer_storage_distribution, layer_storage_stats, layer_storage_table_layout,
+                          split_layer_storage_table, stride_rows)
+    if storage is None:
+        return {}, None
+    layers, bins, levels = storage
+    ranges = storage_ranges(storage, cols)
+    L = len(ranges)
+    local = (sim.storage_table() if sim is not None else
+             np.zeros(layer_storage_table_layout(0, T, L, stride)["words"][0], dtype=np.int64))
+    parts = split_layer_storage_table(local, len(ids), T, L, stride)
+    table = ranks.allreduce_sum(np.concatenate([place_points(parts["stor"], ids, P).reshape(-1),
+                                                place_points(parts["scnt"], ids, P).reshape(-1), parts["ovf"]]))
+    if bins:
+        lhist = (sim.stepper.layer_storage_hist_table() if sim is not None else
+                 np.zeros((0, stride_rows(T, stride), L, bins), dtype=np.int32))
+        hist = place_points(lhist, ids, P, ranks)
+        outside = int(ranks.allreduce_sum(np.array([sim.stepper.layer_storage_outside() if sim is not None else 0],
+                                                   dtype=np.int64))[0])
+    if ranks.rank != 0:
+        return {}, None
+    stats = layer_storage_stats(table, P, T, L, stride)
+    lead = (lambda v: v[None]) if keep_points and P == 1 else (lambda v: v)
+    out = {"storage_layers_cm": np.asarray(layers, dtype=np.float64), "storage_nodes": np.asarray(ranges, dtype=np.int64),
+           "storage_rows": np.asarray(stats["rows"], dtype=np.int64),
+           "storage_count": np.asarray(lead(stats["count"]), dtype=np.int64),
+           "storage_mean_cm": np.asarray(lead(stats["mean_cm"]), dtype=np.float64),
+           "storage_std_cm": np.asarray(lead(stats["std_cm"]), dtype=np.float64),
+           "storage_overflow": np.array(stats["overflow"], dtype=np.int64)}
+    if bins:
+        hist = hist if keep_points else hist[0]
+        dist = layer_storage_distribution(hist, ranges, cols.dz, levels, stride)
+        out.update({"storage_hist": np.asarray(hist, dtype=np.int32), "storage_hist_bins": np.array(bins, dtype=np.int64),
+                    "storage_hist_outside": np.array(outside, dtype=np.int64),
+                    "storage_quantile_levels": np.asarray(dist["levels"], dtype=np.float64),
+                    "storage_quantile_cm": np.asarray(dist["quantiles_cm"], dtype=np.float64)})
+    n = int((np.asarray(stats["count"]).reshape(-1, stats["rows"].size) > 0).any(axis=0).sum())
+    line = f" [{label}] storage: {L} layers on {n} rows"
+    if stats["overflow"] or (bins and outside):
+        line += f" ({stats['overflow']} values clamped, {outside if bins else 0} layer means outside [0, 1])"
+    return out, line
+
+
 def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride=0, dist_levels=None,
                filt=(0, None, None), enkf=(0, None, None, None), record=None, scheme=None, window=None, frecord=None,
-               theta=(0, None)):
+               theta=(0, None), storage=None):
     """Parameter points x members: this rank's points in one handle (ensemble.SweepSimulation), the whole table assembled
     over the ranks (multigpu.assemble_points)."""
     import numpy as np
@@ -997,7 +1141,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     if mine:
         sim = SweepSimulation(points, forcing, n_members, seed=int(ens.get("Seed", 0)), device=device, point_ids=mine,
                               profile_stride=stride, wtd_hist_stride=dist_stride, theta_hist_bins=theta[0],
-                              **_filter_kwargs(filt, frecord), **_enkf_kwargs(enkf, record, scheme, window))
+                              **_filter_kwargs(filt, frecord), **_enkf_kwargs(enkf, record, scheme, window),
+                              **_storage_kwargs(storage))
         _step_all(sim, rows, label, ranks)
         table = sim.moments()
         for j, k in enumerate(mine):
@@ -1013,6 +1158,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     arrays.update(tables)
     ttables, theta_line = _reduce_theta(ranks, sim, mine, P, T, ref.dim_d, stride, theta, label, keep_points=True)
     arrays.update(ttables)
+    stor_tables, storage_line = _reduce_storage(ranks, sim, mine, P, T, ref, stride, storage, label, keep_points=True)
+    arrays.update(stor_tables)
     ftables, filter_line = _reduce_filter(ranks, sim, mine, P, T, filt, label, keep_points=True)
     arrays.update(ftables)
     fstables, fsm_line = _reduce_sm(ranks, sim, mine, P, T, filt[0], frecord, label, keep_points=True, owner="filter")
@@ -1043,6 +1190,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
         print(window_line)
     if theta_line:
         print(theta_line)
+    if storage_line:
+        print(storage_line)
 
 
 def run_cli(argv=None):

@@ -166,6 +166,14 @@ struct hc_handle {
     // entries, on the profile rows and keyed like the profile table
     int thist_bins = 0;          // 0: off
     AccTable<int> thist{"entries"};
+    // ensemble soil-water storage by depth layer (hc_set_layer_storage): the int64 moments [P][n_prow][L][5], scnt, ovf and,
+    // with bins, the int32 histograms [P][n_prow][L][B] + the outside count; on the profile rows, keyed like the profile table
+    int stor_layers = 0;         // 0: off
+    int stor_bins = 0;           // 0: no histogram
+    long long stor_grid_y = 65535;   // most member slices of a point in one launch (HYDROCOL_DEBUG_STORAGE_GRID_Y: fewer)
+    int stor_range[HC_STORAGE_MAX_LAYERS][2] = {};
+    AccTable<long long> stor{"words"};
+    AccTable<int> shist{"entries"};
     // particle filter on the well's water table (hc_set_filter): diagnostics float64 [P][n_arow][4] keyed by
     // (points, rows, stride), the second state / base buffers of the gather, the last assimilation's q_b, {Q, r} and
     // ancestors (test hooks), and the host copy of wtd_obs that decides which rows are assimilated
@@ -447,6 +455,132 @@ __global__ __launch_bounds__(PROF_TILE * PROF_WAVES) void theta_hist_kernel(
         if (c && node < D) atomicAdd(t + (size_t)node * B + k / PROF_TILE, (int)c);
     }
     if (threadIdx.x == 0 && outside_sum) atomicAdd(outside_word, (unsigned long long)outside_sum);
+}
+
+// ---- ensemble soil-water storage by depth layer (hc_set_layer_storage, include/hydrocol.h)
+// the layers of a handle as a kernel argument: node ranges [i0, i1), and [lo, hi) = the nodes any layer holds
+struct StorLayers {
+    int n, lo, hi;
+    int i0[HC_STORAGE_MAX_LAYERS], i1[HC_STORAGE_MAX_LAYERS];
+};
+
+// One profile row's storage per member and layer: the transpose of profile_kernel.  Grid y = member slices of one point
+// (block y takes slices y, y + gridDim.y, ...: the grid is capped, a point of any size is served), z = point; wave w of a
+// block takes members m0 + w, m0 + w + 4, ... of a slice and its lanes stride over the nodes, so every load is 64
+// contiguous doubles of one member's row (only the nodes some layer holds are read).  theta reads one node constant, the
+// porosity (model_cell's inv_delta is unused, logm, invm2, noisec and the noise feed K_bkg alone, which is dead code
+// here as in profile_kernel): the block keeps por [D] in LDS, read with lane = consecutive double, and hands model_cell
+// zeros for the rest.  Lane j adds theta_i, i mod 64 == j ascending, into one accumulator per
+// layer; a node outside the layer adds 0.0, which leaves an accumulator that started at 0.0 as it is, bit for bit (it is
+// never -0.0).  The 64 lane sums meet by halving strides; lane 0's is T (the order of include/hydrocol.h).  Lane l then
+// owns layer l: it quantises S = dz T and keeps the wave's five words in registers, and adds one to bin floor(u B) of the
+// block's LDS histogram, uint32 [L][B] -- one LDS add per wave, member and layer, on the lanes' own addresses; two waves
+// meet on a bin only through the LDS atomic.  After the barrier L x 5 threads add the four waves' words to the table and
+// the nonzero bins go to the histogram, all with integer atomics (order-independent); no floating-point atomic anywhere.
+__global__ __launch_bounds__(PROF_TILE * PROF_WAVES) void layer_storage_kernel(
+    const StepArgs A, const double *node_tabs, int special, const double *stage, const int *wtd_obs, long long row,
+    long long prow, long long n_prow, int snapshot, long long members_per_block, const StorLayers Ly, int B,
+    long long *stor, long long *scnt, unsigned long long *ovf_word, int *hist, unsigned long long *outside_word)
+{
+#pragma clang fp contract(off)
+    if (!snapshot && wtd_obs[row] < 0) return;
+    const int D = A.D, L = Ly.n;
+    const int lane = threadIdx.x % PROF_TILE, wave = threadIdx.x / PROF_TILE;
+    const long long point = blockIdx.z;
+    const long long end = (point + 1) * A.members_per_point;
+    const long long slice0 = point * A.members_per_point + (long long)blockIdx.y * members_per_block;
+    const long long hop = (long long)gridDim.y * members_per_block;      // to the block's next slice
+    if (slice0 >= end) return;               // (the whole block: nothing is shared yet)
+    extern __shared__ double stor_lds[];     // por [D], then the bins uint32 [L][B]
+    double *por = stor_lds;
+    unsigned *bins = reinterpret_cast<unsigned *>(stor_lds + D);
+    __shared__ long long part[PROF_WAVES][HC_STORAGE_MAX_LAYERS][HC_PROF_WORDS];
+    __shared__ unsigned outside_sum, ovf_sum;
+    const ColumnDev P = A.P[point];
+    for (int i = Ly.lo + (int)threadIdx.x; i < Ly.hi; i += PROF_TILE * PROF_WAVES) por[i] = node_tabs[(size_t)point * 3 * D + i];
+    for (int k = threadIdx.x; k < L * B; k += PROF_TILE * PROF_WAVES) bins[k] = 0;
+    if (threadIdx.x == 0) outside_sum = 0, ovf_sum = 0;
+    __syncthreads();
+
+    long long words[HC_PROF_WORDS] = {};     // lane l < L: the wave's sums of layer l
+    unsigned ovf = 0, outside = 0;
+    int own_n = 1;                           // nodes of the lane's own layer (selects: a kernel argument is not indexed by the lane)
+#pragma unroll
+    for (int l = 0; l < HC_STORAGE_MAX_LAYERS; l++) own_n = (lane == l && l < L) ? Ly.i1[l] - Ly.i0[l] : own_n;
+    const double s_stor = ldexp(1.0, HC_PROF_SCALE_STORAGE), dz = P.dz, nb = (double)B;
+    const int first = Ly.lo / PROF_TILE * PROF_TILE + lane;      // lane j takes nodes i mod 64 == j
+    long long counted = 0;                   // members of the block's slices
+    for (long long m0 = slice0; m0 < end; m0 += hop) {
+        const long long m1 = m0 + members_per_block < end ? m0 + members_per_block : end;
+        counted += m1 - m0;
+        for (long long m = m0 + wave; m < m1; m += PROF_WAVES) {
+            const double *psi_m = stage + (size_t)m * D;
+            double x[HC_STORAGE_MAX_LAYERS];
+#pragma unroll
+            for (int l = 0; l < HC_STORAGE_MAX_LAYERS; l++) x[l] = 0.0;
+            for (int i = first; i < Ly.hi; i += PROF_TILE) {
+                if (i < Ly.lo) continue;
+                double th, K, C, kb, pf;
+                if (special)
+                    model_cell<true>(P, psi_m[i], por[i], 0.0, 0.0, 0.0, 0.0, 0.0, th, K, C, kb, pf);
+                else
+                    model_cell<false>(P, psi_m[i], por[i], 0.0, 0.0, 0.0, 0.0, 0.0, th, K, C, kb, pf);
+#pragma unroll
+                for (int l = 0; l < HC_STORAGE_MAX_LAYERS; l++)
+                    if (l < L) x[l] += (i >= Ly.i0[l] && i < Ly.i1[l]) ? th : 0.0;
+            }
+            double T = 0.0;
+#pragma unroll
+            for (int l = 0; l < HC_STORAGE_MAX_LAYERS; l++) {
+                if (l < L) {                     // (wave-uniform)
+                    double v = x[l];
+#pragma unroll
+                    for (int s = PROF_TILE / 2; s > 0; s >>= 1) v += __shfl_down(v, s, PROF_TILE);
+                    const double t = __shfl(v, 0, PROF_TILE);
+                    T = lane == l ? t : T;
+                }
+            }
+            if (lane < L) {
+                prof_add(words, prof_quantise(dz * T, s_stor, ovf));
+                if (B > 0) {
+                    const double u = T / (double)own_n;
+                    if (u >= 0.0 && u <= 1.0) {      // (false for a NaN)
+                        const int b = u == 1.0 ? B - 1 : (int)(u * nb);    // u B is exact: B is a power of two
+                        atomicAdd(&bins[lane * B + b], 1u);
+                    } else {
+                        outside++;
+                    }
+                }
+            }
+        }
+    }
+    if (lane < L) {
+#pragma unroll
+        for (int k = 0; k < HC_PROF_WORDS; k++) part[wave][lane][k] = words[k];
+        if (ovf) atomicAdd(&ovf_sum, ovf);
+        if (outside) atomicAdd(&outside_sum, outside);
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < L * HC_PROF_WORDS) {
+        const int l = threadIdx.x / HC_PROF_WORDS, k = threadIdx.x % HC_PROF_WORDS;
+        long long sum = 0;
+#pragma unroll
+        for (int v = 0; v < PROF_WAVES; v++) sum += part[v][l][k];
+        atomicAdd(reinterpret_cast<unsigned long long *>(stor + (((size_t)point * n_prow + prow) * L + l) * HC_PROF_WORDS + k),
+                  (unsigned long long)sum);
+    }
+    if (B > 0) {
+        int *t = hist + ((size_t)point * n_prow + prow) * L * B;
+        for (int k = threadIdx.x; k < L * B; k += PROF_TILE * PROF_WAVES) {
+            const unsigned c = bins[k];
+            if (c) atomicAdd(t + k, (int)c);
+        }
+    }
+    if (threadIdx.x == 0) {
+        atomicAdd(reinterpret_cast<unsigned long long *>(scnt + (size_t)point * n_prow + prow), (unsigned long long)counted);
+        if (ovf_sum) atomicAdd(ovf_word, (unsigned long long)ovf_sum);
+        if (B > 0 && outside_sum) atomicAdd(outside_word, (unsigned long long)outside_sum);
+    }
 }
 
 // transpiration / lateral flow of every solved row of a launch, the member count and sum |obs - wtd| (abs_error in grid
@@ -2341,6 +2475,50 @@ int ensure_thist(hc_handle *h)
     return h->thist.ensure(h->n_points, h->n_rows, h->p.dim_d, thist_bins_total(h) + 2);
 }
 
+// the layer-storage tables (hc_set_layer_storage): int64 stor [P][n_prow][L][5], scnt [P][n_prow], ovf [1]; with bins the
+// int32 hist [P][n_prow][L][B] and the outside count (one uint64 in two entries, 8-byte aligned behind a multiple of 32)
+struct StorLayout {
+    int64_t scnt = 0, ovf = 0, words = 0, bins = 0;
+};
+StorLayout stor_layout(const hc_handle *h)
+{
+    StorLayout S;
+    const int64_t slots = (int64_t)h->n_points * prof_layout(h).n_prow;
+    S.scnt = slots * h->stor_layers * HC_PROF_WORDS;
+    S.ovf = S.scnt + slots;
+    S.words = S.ovf + 1;
+    S.bins = slots * h->stor_layers * h->stor_bins;
+    return S;
+}
+int ensure_stor(hc_handle *h)
+{
+    if (h->stor_layers <= 0) return fail(HC_ERR_ARG, "layer storage is off (hc_set_layer_storage)");
+    if (h->prof_stride <= 0) return fail(HC_ERR_ARG, "layer storage needs the profile statistics (hc_set_profile_stats)");
+    if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
+    for (int l = 0; l < h->stor_layers; l++) {
+        const int i0 = h->stor_range[l][0], i1 = h->stor_range[l][1];
+        if (i0 < 0 || i0 >= i1 || i1 > h->p.dim_d)
+            return fail(HC_ERR_ARG, "layer storage: layer %d is [%d, %d), not a range of nodes 0 <= i0 < i1 <= %d", l, i0, i1,
+                        (int)h->p.dim_d);
+        if ((double)(i1 - i0) * h->p.dz >= HC_STORAGE_MAX_CM)
+            return fail(HC_ERR_ARG, "layer storage: layer %d is %g cm thick (less than %g cm fit the moments)", l,
+                        (double)(i1 - i0) * h->p.dz, HC_STORAGE_MAX_CM);
+    }
+    if (h->n_members / std::max(h->n_points, 1) > INT32_MAX)
+        return fail(HC_ERR_ARG, "layer storage: %lld members per point do not fit an int32 bin",
+                    (long long)(h->n_members / std::max(h->n_points, 1)));
+    const StorLayout S = stor_layout(h);
+    if (S.bins > HC_WTD_HIST_MAX_ENTRIES)
+        return fail(HC_ERR_ARG, "layer storage: %lld histogram entries exceed HC_WTD_HIST_MAX_ENTRIES", (long long)S.bins);
+    if (int rc = h->stor.ensure(h->n_points, h->n_rows, h->p.dim_d, S.words)) return rc;
+    return h->stor_bins > 0 ? h->shist.ensure(h->n_points, h->n_rows, h->p.dim_d, S.bins + 2) : HC_OK;
+}
+int ensure_stor_hist(hc_handle *h)
+{
+    if (int rc = ensure_stor(h)) return rc;
+    return h->stor_bins > 0 ? HC_OK : fail(HC_ERR_ARG, "layer storage has no histogram (hc_set_layer_storage with n_bins = 0)");
+}
+
 // An assimilation table keyed by (points, rows, stride): `per_row` entries per point and analysis row (every stride-th
 // row), created on a fresh key as NaN with each slot's count 0 (`width` entries a slot; 0: all NaN)
 int ensure_da_table(hc_handle *h, AccTable<double> &t, int64_t stride, int64_t per_row, int width)
@@ -2720,6 +2898,8 @@ int hc_create(int device_ordinal, hc_handle **out)
     if (const char *sv = getenv("HYDROCOL_SCIPY_152")) h->scipy_152 = atoi(sv) != 0;     // (the whole product at once: CLI, Simulation)
     if (const char *mi = getenv("HYDROCOL_DEBUG_MAX_ITER"))    // test hook: forces abandoned attempts
         if (atoi(mi) > 0) h->max_phase_iterations = atoi(mi);
+    if (const char *gy = getenv("HYDROCOL_DEBUG_STORAGE_GRID_Y"))     // test hook: blocks of layer_storage_kernel take several slices
+        if (atoi(gy) > 0) h->stor_grid_y = std::min(h->stor_grid_y, (long long)atoi(gy));
     const char *jr = getenv("HYDROCOL_DEBUG_JAC_REJECT");   // test hook: exercises num_jac's retry branch
     if (jr && atof(jr) > 0.0) h->jac_reject = atof(jr);
     *out = h;
@@ -2742,7 +2922,7 @@ int hc_destroy(hc_handle *h)
     h->Pdev.release(); h->iodev.release();
     h->point_base.release(); h->point_order.release(); h->point_cost.release();
     h->daylight.release(); h->refresh.release(); h->wtd_u16.release(); h->moments.release(); h->counters.release();
-    h->prof.release(); h->hist.release(); h->thist.release();
+    h->prof.release(); h->hist.release(); h->thist.release(); h->stor.release(); h->shist.release();
     assimilation_off(h);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -3129,6 +3309,36 @@ int launch_theta_hist(hc_handle *h, const StepArgs &A, const ProfLayout &L, cons
     return HC_OK;
 }
 
+// the layer storage of the same row, from the same states: a block per slice of STOR_MEMBERS_PER_BLOCK members (a wave
+// reads whole rows, so the slices are short: 32 members a wave make the block's set-up negligible and give a
+// 262 144-member point 2048 blocks); beyond stor_grid_y = 65 535 slices (8.4 M members a point) a block takes several, so
+// that grid y stays within what the runtime launches and a block's uint32 LDS counters within 2^31 / 65 535 members
+constexpr long long STOR_MEMBERS_PER_BLOCK = 128;
+int launch_layer_storage(hc_handle *h, const StepArgs &A, const ProfLayout &L, const double *stage, int64_t row, int snapshot)
+{
+    const long long mpp = h->n_members / h->n_points;
+    const dim3 grid(1, (unsigned)std::min((mpp + STOR_MEMBERS_PER_BLOCK - 1) / STOR_MEMBERS_PER_BLOCK, h->stor_grid_y),
+                    (unsigned)h->n_points);
+    StorLayers Ly{};
+    Ly.n = h->stor_layers, Ly.lo = h->p.dim_d, Ly.hi = 0;
+    for (int l = 0; l < Ly.n; l++) {
+        Ly.i0[l] = h->stor_range[l][0], Ly.i1[l] = h->stor_range[l][1];
+        Ly.lo = std::min(Ly.lo, Ly.i0[l]), Ly.hi = std::max(Ly.hi, Ly.i1[l]);
+    }
+    const StorLayout S = stor_layout(h);
+    const int B = h->stor_bins;
+    long long *t = h->stor.buf.p;
+    int *hist = B > 0 ? h->shist.buf.p : nullptr;
+    const size_t lds = (size_t)h->p.dim_d * sizeof(double) + (size_t)Ly.n * B * sizeof(unsigned);
+    hipLaunchKernelGGL(layer_storage_kernel, grid, dim3(PROF_TILE * PROF_WAVES), lds, h->stream, A, h->node_tabs.p,
+                       (int)h->use_special(), stage, h->wtd_obs.p, (long long)row, (long long)(row / h->prof_stride),
+                       (long long)L.n_prow, snapshot, STOR_MEMBERS_PER_BLOCK, Ly, B, t, t + S.scnt,
+                       reinterpret_cast<unsigned long long *>(t + S.ovf), hist,
+                       reinterpret_cast<unsigned long long *>(B > 0 ? hist + S.bins : nullptr));
+    HIP_TRY(hipGetLastError());
+    return HC_OK;
+}
+
 constexpr long long HIST_MEMBERS_PER_BLOCK = 4096;
 
 // the histogram rows among launch rows [row0, row0 + chunk) of the water-table indices in wtd_u16
@@ -3354,6 +3564,8 @@ int accumulate(hc_handle *h, const StepArgs &A, const hc_step_args *a, const Chu
         if (int rc = launch_profile(h, A, PL, stage, c.row0 + r, 0)) return rc;
         if (h->thist_bins > 0)
             if (int rc = launch_theta_hist(h, A, PL, stage, c.row0 + r, 0)) return rc;
+        if (h->stor_layers > 0)
+            if (int rc = launch_layer_storage(h, A, PL, stage, c.row0 + r, 0)) return rc;
     }
     long long *t = h->prof.buf.p;
     hipLaunchKernelGGL(flux_stats_kernel, dim3(c.rows, h->n_points), dim3(256), 0, h->stream, h->diag.p, h->wtd_u16.p,
@@ -3893,6 +4105,7 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
     const bool prof_on = h->prof_stride > 0 && !a->spinup, hist_on = h->hist_stride > 0 && !a->spinup;
     if ((prof_on && (rc = ensure_prof(h))) || (hist_on && (rc = ensure_hist(h)))) return rc;
     if (prof_on && h->thist_bins > 0 && (rc = ensure_thist(h))) return rc;
+    if (prof_on && h->stor_layers > 0 && (rc = ensure_stor(h))) return rc;
     // the particle filter (hc_set_filter): spin-up solves are never filtered
     if (a->spinup && h->filt_host())
         return fail(HC_ERR_ARG, "spin-up solves with the particle filter on in a Philox run: set the filter after the spin-up");
@@ -4055,6 +4268,8 @@ int hc_set_profile_stats(hc_handle *h, int32_t stride)
     h->prof.release();           // re-created, zeroed, when on
     h->thist_bins = 0;           // the soil-moisture histograms are keyed to the profile rows: off
     h->thist.release();
+    h->stor_layers = h->stor_bins = 0;       // and so is the layer storage
+    h->stor.release(), h->shist.release();
     return stride == 0 ? HC_OK : ensure_prof(h);
 }
 
@@ -4079,9 +4294,13 @@ int hc_profile_snapshot(hc_handle *h, int64_t row)
     HIP_TRY(hipSetDevice(h->device));
     if (h->thist_bins > 0)
         if (int rc2 = ensure_thist(h)) return rc2;
+    if (h->stor_layers > 0)
+        if (int rc2 = ensure_stor(h)) return rc2;
     if (int rc2 = launch_profile(h, A, prof_layout(h), h->psi.p, row, 1)) return rc2;
     if (h->thist_bins > 0)
         if (int rc2 = launch_theta_hist(h, A, prof_layout(h), h->psi.p, row, 1)) return rc2;
+    if (h->stor_layers > 0)
+        if (int rc2 = launch_layer_storage(h, A, prof_layout(h), h->psi.p, row, 1)) return rc2;
     HIP_TRY(hipStreamSynchronize(h->stream));
     return HC_OK;
 }
@@ -4203,6 +4422,104 @@ int hc_get_theta_hist_bins(hc_handle *h, int32_t *n_bins)
 {
     if (!h || !n_bins) return fail(HC_ERR_ARG, "hc_get_theta_hist_bins: bad argument");
     *n_bins = h->thist_bins;
+    return HC_OK;
+}
+
+int hc_set_layer_storage(hc_handle *h, int32_t n_layers, const int32_t *ranges, int32_t n_bins)
+{
+    if (!h || (n_layers > 0 && !ranges)) return fail(HC_ERR_ARG, "hc_set_layer_storage: bad argument");
+    if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->stor.release(), h->shist.release();   // re-created, zeroed, when on
+    h->stor_layers = h->stor_bins = 0;
+    if (n_layers == 0) return HC_OK;
+    if (n_layers < 0 || n_layers > HC_STORAGE_MAX_LAYERS)
+        return fail(HC_ERR_ARG, "hc_set_layer_storage: %d layers (1 to %d; 0 = off)", (int)n_layers, HC_STORAGE_MAX_LAYERS);
+    if (n_bins != 0 && (n_bins < 32 || n_bins > 1024 || (n_bins & (n_bins - 1))))
+        return fail(HC_ERR_ARG, "hc_set_layer_storage: %d bins (a power of two in 32 .. 1024; 0 = no histogram)", (int)n_bins);
+    for (int l = 0; l < n_layers; l++) h->stor_range[l][0] = ranges[2 * l], h->stor_range[l][1] = ranges[2 * l + 1];
+    h->stor_layers = n_layers, h->stor_bins = n_bins;
+    const int rc = ensure_stor(h);           // (its refusals come before anything is allocated)
+    if (rc != HC_OK) h->stor_layers = h->stor_bins = 0, h->stor.release(), h->shist.release();      // refused: off
+    return rc;
+}
+
+int hc_get_layer_storage_words(hc_handle *h, int64_t *n_words)
+{
+    if (!h || !n_words) return fail(HC_ERR_ARG, "hc_get_layer_storage_words: bad argument");
+    if (int rc = ensure_stor(h)) return rc;
+    *n_words = h->stor.n;
+    return HC_OK;
+}
+
+int hc_get_layer_storage(hc_handle *h, int64_t *table, int64_t n_words)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_get_layer_storage: bad argument");
+    return table_copy(h, h->stor, ensure_stor, hipMemcpyDeviceToHost, table, n_words, "hc_get_layer_storage");
+}
+
+int hc_set_layer_storage_tables(hc_handle *h, const int64_t *table, int64_t n_words)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_set_layer_storage_tables: bad argument");
+    return table_copy(h, h->stor, ensure_stor, hipMemcpyHostToDevice, const_cast<int64_t *>(table), n_words,
+                      "hc_set_layer_storage_tables");
+}
+
+int hc_export_layer_storage(hc_handle *h, void *device_dst, int64_t n_words)
+{
+    if (!h || !device_dst) return fail(HC_ERR_ARG, "hc_export_layer_storage: bad argument");
+    return table_copy(h, h->stor, ensure_stor, hipMemcpyDeviceToDevice, device_dst, n_words, "hc_export_layer_storage");
+}
+
+int hc_get_layer_storage_hist(hc_handle *h, int32_t *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_get_layer_storage_hist: bad argument");
+    return table_copy(h, h->shist, ensure_stor_hist, hipMemcpyDeviceToHost, table, n_entries, "hc_get_layer_storage_hist");
+}
+
+int hc_set_layer_storage_hist_table(hc_handle *h, const int32_t *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_set_layer_storage_hist_table: bad argument");
+    return table_copy(h, h->shist, ensure_stor_hist, hipMemcpyHostToDevice, const_cast<int32_t *>(table), n_entries,
+                      "hc_set_layer_storage_hist_table");
+}
+
+int hc_reset_layer_storage(hc_handle *h)
+{
+    if (!h) return fail(HC_ERR_ARG, "hc_reset_layer_storage: bad argument");
+    h->shist.invalidate();
+    return table_reset(h, h->stor, ensure_stor);
+}
+
+int hc_get_layer_storage_outside(hc_handle *h, uint64_t *count)
+{
+    if (!h || !count) return fail(HC_ERR_ARG, "hc_get_layer_storage_outside: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = ensure_stor(h)) return rc;
+    *count = 0;
+    if (h->stor_bins == 0) return HC_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(count, h->shist.buf.p + (h->shist.n - 2), 8, hipMemcpyDeviceToHost));
+    return HC_OK;
+}
+
+int hc_get_layer_storage_overflow(hc_handle *h, uint64_t *count)
+{
+    if (!h || !count) return fail(HC_ERR_ARG, "hc_get_layer_storage_overflow: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = ensure_stor(h)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(count, h->stor.buf.p + stor_layout(h).ovf, 8, hipMemcpyDeviceToHost));
+    return HC_OK;
+}
+
+int hc_get_layer_storage_layout(hc_handle *h, int32_t *n_layers, int32_t *n_bins, int32_t *ranges)
+{
+    if (!h || !n_layers || !n_bins || !ranges) return fail(HC_ERR_ARG, "hc_get_layer_storage_layout: bad argument");
+    *n_layers = h->stor_layers, *n_bins = h->stor_bins;
+    for (int l = 0; l < HC_STORAGE_MAX_LAYERS; l++)
+        ranges[2 * l] = l < h->stor_layers ? h->stor_range[l][0] : 0, ranges[2 * l + 1] = l < h->stor_layers ? h->stor_range[l][1] : 0;
     return HC_OK;
 }
 

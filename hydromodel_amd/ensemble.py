@@ -11,7 +11,7 @@ import numpy as np
 from .digest import inverse_retention
 from .stepper import (ENKF_METHODS, ENKF_WIDTH, SM_WIDTH, WINDOW_WIDTH, EnsembleStepper, enkf_sm_summary, enkf_summary,
                       enkf_window_settings, enkf_window_summary, filter_sm_summary, filter_summary,
-                      moments_to_mean_std, theta_distribution, wtd_distribution)
+                      layer_ranges, layer_storage_distribution, moments_to_mean_std, theta_distribution, wtd_distribution)
 
 
 def pressure_head(cols, theta):
@@ -98,6 +98,9 @@ class _Run:
     states, fluxes and abs_error every solved row) accumulated on the device: :meth:`profile_stats`.
     theta_hist_bins > 0 (32, 64 or 128; needs profile_stride): exact histograms of theta_vol at every node of the profile
     rows, counted on the device: :meth:`theta_distribution` (quantile bands of theta(z)).
+    storage_layers_cm (needs profile_stride): depth layers [(top, bottom), ...] in cm (stepper.layer_ranges) whose water
+    storage dz sum theta is reduced per member on the device on the profile rows: :meth:`storage_stats` (mean and sigma in
+    cm) and, with ``storage_bins`` (a power of two in 32 .. 1024), :meth:`storage_distribution` (quantile bands in cm).
     wtd_hist_stride > 0: per-row histograms of the members' water-table index every ``wtd_hist_stride``-th row, counted on
     the device: :meth:`wtd_distribution` (quantiles, CRPS against the well).
     filter_stride > 0: a bootstrap particle filter on the well's water table every ``filter_stride``-th row with an
@@ -125,8 +128,16 @@ class _Run:
     def _start_tables(self, profile_stride, wtd_hist_stride, filter_stride=0, filter_sigma_cm=None, filter_seed=None,
                       enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None,
                       enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=(),
-                      filter_soil_moisture=None, theta_hist_bins=0):
+                      filter_soil_moisture=None, theta_hist_bins=0, storage_layers_cm=None, storage_bins=0):
         self.profile_stride = int(profile_stride)
+        self.storage_layers_cm = None if storage_layers_cm is None or len(storage_layers_cm) == 0 else \
+            np.asarray(storage_layers_cm, dtype=np.float64).reshape(-1, 2)
+        self.storage_bins = int(storage_bins or 0) if self.storage_layers_cm is not None else 0
+        if storage_bins and self.storage_layers_cm is None:
+            raise ValueError("storage_bins needs storage_layers_cm")
+        if self.storage_layers_cm is not None and not self.profile_stride:
+            raise ValueError("storage_layers_cm needs the profile statistics (profile_stride > 0)")
+        self.storage_ranges = None if self.storage_layers_cm is None else layer_ranges(self.cols.z, self.storage_layers_cm)
         self.theta_hist_bins = int(theta_hist_bins or 0)
         if self.theta_hist_bins and not self.profile_stride:
             raise ValueError("theta_hist_bins needs the profile statistics (profile_stride > 0)")
@@ -134,6 +145,8 @@ class _Run:
             self.stepper.set_profile_stats(self.profile_stride)
             if self.theta_hist_bins:
                 self.stepper.set_theta_hist(self.theta_hist_bins)
+            if self.storage_ranges is not None:
+                self.stepper.set_layer_storage(self.storage_ranges, self.storage_bins)
             self.stepper.profile_snapshot(0)       # psi[0], theta_vol[0]: the state before any solve
         self.wtd_hist_stride = int(wtd_hist_stride)
         if self.wtd_hist_stride:
@@ -201,6 +214,27 @@ class _Run:
         ``table``: e.g. the sum over ranks.  Other levels need no rerun."""
         t = self.theta_hist_table() if table is None else table
         return theta_distribution(t, levels, self.theta_hist_bins, self.profile_stride)
+
+    def storage_table(self):
+        """The raw int64 moments table of the layer storage (stepper.layer_storage_table_layout)."""
+        return self.stepper.layer_storage_table()
+
+    def storage_stats(self, table=None):
+        """Mean and sigma of every layer's storage in cm per profile row, [T_out][L] (a sweep: [P][T_out][L]), with rows and
+        count (stepper.layer_storage_stats); ``table``: e.g. the sum over ranks."""
+        out = self.stepper.layer_storage_stats(table)
+        out["layers_cm"], out["nodes"] = self.storage_layers_cm.copy(), self.storage_ranges.copy()
+        return out
+
+    def storage_hist_table(self):
+        """[n_prow][L][B] int32: members per bin of each layer's mean theta on every profile row; a sweep: [P][n_prow][L][B]."""
+        return self.stepper.layer_storage_hist_table().reshape(self._lead + (-1, len(self.storage_ranges), self.storage_bins))
+
+    def storage_distribution(self, levels=(0.05, 0.25, 0.5, 0.75, 0.95), table=None):
+        """Quantile bands of every layer's storage in cm per profile row (stepper.layer_storage_distribution), with the
+        leading shape of the table; ``table``: e.g. the sum over ranks.  Other levels need no rerun."""
+        t = self.storage_hist_table() if table is None else table
+        return layer_storage_distribution(t, self.storage_ranges, self.cols.dz, levels, self.profile_stride)
 
     def wtd_hist_table(self):
         """[n_hrow][D] int32: members per water-table index on every histogram row (stepper.wtd_hist_rows); a sweep:
@@ -289,7 +323,7 @@ class EnsembleSimulation(_Run):
     #1 base vector, then one vector per refresh row (simulation.py:426,561,601) -- and uploaded per launch.
     spinup="shared" (default): one spin-up (global member 0's first draw) broadcast to all members;
     spinup="member": every member spins up with its own first draw (`spinup_members_on_gpu`).
-    profile_stride, theta_hist_bins, wtd_hist_stride, filter_stride / filter_sigma_cm / filter_seed, enkf_stride / enkf_sigma_cm /
+    profile_stride, theta_hist_bins, storage_layers_cm / storage_bins, wtd_hist_stride, filter_stride / filter_sigma_cm / filter_seed, enkf_stride / enkf_sigma_cm /
     enkf_localisation_cm / enkf_seed: the optional tables, the particle filter and the EnKF (:class:`_Run`).
     enkf_shard=(n_global, exchange): these members are [member_offset, member_offset + N) of an ensemble of ``n_global``
     whose other members run elsewhere, and the EnKF analyses the whole of it (include/hydrocol.h hc_set_enkf_shard;
@@ -306,7 +340,7 @@ class EnsembleSimulation(_Run):
                  filter_sigma_cm=None, filter_seed=None, enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0,
                  enkf_seed=None, enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0,
                  enkf_window_offsets=(), enkf_shard=None, filter_shard=None, filter_soil_moisture=None,
-                 theta_hist_bins=0):
+                 theta_hist_bins=0, storage_layers_cm=None, storage_bins=0):
         if filter_shard is not None and not int(filter_stride or 0):
             raise ValueError("filter_shard needs the particle filter (filter_stride > 0)")
         if filter_shard is not None and filter_soil_moisture is not None:
@@ -318,7 +352,8 @@ class EnsembleSimulation(_Run):
         self._start(cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup)
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
-                           enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins)
+                           enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins, storage_layers_cm,
+                           storage_bins)
         self.enkf_shard = None
         if enkf_shard is not None:
             if not self.enkf_stride:
@@ -428,6 +463,13 @@ class EnsembleSimulation(_Run):
             arrays["theta_hist_bins"] = np.array(self.theta_hist_bins, dtype=np.int64)
             arrays["theta_hist"] = self.stepper.theta_hist_table()
             arrays["theta_hist_outside"] = np.array(self.stepper.theta_hist_outside(), dtype=np.uint64)
+        if self.storage_ranges is not None:
+            arrays["storage_layers_cm"] = self.storage_layers_cm
+            arrays["storage_bins"] = np.array(self.storage_bins, dtype=np.int64)
+            arrays["storage_table"] = self.stepper.layer_storage_table()
+            if self.storage_bins:
+                arrays["storage_hist"] = self.stepper.layer_storage_hist_table()
+                arrays["storage_hist_outside"] = np.array(self.stepper.layer_storage_outside(), dtype=np.uint64)
         if self.wtd_hist_stride:
             arrays["wtd_hist_stride"] = np.array(self.wtd_hist_stride, dtype=np.int64)
             arrays["wtd_hist"] = self.stepper.wtd_hist_table()
@@ -486,6 +528,10 @@ class EnsembleSimulation(_Run):
         stride = int(data["profile_stride"]) if "profile_stride" in data else 0
         hist_stride = int(data["wtd_hist_stride"]) if "wtd_hist_stride" in data else 0
         theta_bins = int(data["theta_hist_bins"]) if "theta_hist_bins" in data else 0
+        storage = "storage_layers_cm" in data
+        if storage:
+            fkw_storage = dict(storage_layers_cm=np.asarray(data["storage_layers_cm"], dtype=np.float64).reshape(-1, 2),
+                               storage_bins=int(data["storage_bins"]))
         filt = int(data["filter_stride"]) if "filter_stride" in data else 0
         fkw = dict(filter_stride=filt, filter_sigma_cm=float(data["filter_sigma_cm"]),
                    filter_seed=int(data["filter_seed"])) if filt else {}
@@ -516,7 +562,7 @@ class EnsembleSimulation(_Run):
             fkw.update(enkf_window_offsets=tuple(int(o) for o in np.asarray(data["enkf_window_offsets"]).reshape(-1)))
         sim = cls(cols, forcing, n, seed=int(data["seed"]), device=device, member_offset=int(data["member_offset"]),
                   psi0=np.asarray(data["initial_cond"], dtype=float).reshape(-1)[:D], flags=flags, profile_stride=stride,
-                  wtd_hist_stride=hist_stride, theta_hist_bins=theta_bins, **fkw)
+                  wtd_hist_stride=hist_stride, theta_hist_bins=theta_bins, **(fkw_storage if storage else {}), **fkw)
         sim.stepper.set_state(psi if n > 1 else psi[0])
         if filt:
             sim.stepper.set_filter_table(np.asarray(data["filter_table"], dtype=np.float64))
@@ -538,6 +584,10 @@ class EnsembleSimulation(_Run):
             sim.stepper.set_profile_table(np.asarray(data["profile_table"], dtype=np.int64))
         if theta_bins:
             sim.stepper.set_theta_hist_table(np.asarray(data["theta_hist"]), int(data["theta_hist_outside"]))
+        if storage:
+            sim.stepper.set_layer_storage_table(np.asarray(data["storage_table"], dtype=np.int64))
+            if sim.storage_bins:
+                sim.stepper.set_layer_storage_hist_table(np.asarray(data["storage_hist"]), int(data["storage_hist_outside"]))
         if hist_stride:
             sim.stepper.set_wtd_hist_table(np.asarray(data["wtd_hist"]))
         sim.next_row = int(data["next_row"])
@@ -634,7 +684,7 @@ class SweepSimulation(_Run):
                  point_ids=None, profile_stride=0, wtd_hist_stride=0, filter_stride=0, filter_sigma_cm=None,
                  filter_seed=None, enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None,
                  enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=(),
-                 filter_soil_moisture=None, theta_hist_bins=0):
+                 filter_soil_moisture=None, theta_hist_bins=0, storage_layers_cm=None, storage_bins=0):
         self.points = list(cols_list)
         self.P, self.n = len(self.points), int(n_members)
         self._lead = (self.P,)
@@ -663,7 +713,8 @@ class SweepSimulation(_Run):
             self.stepper.set_point_member_bases(self.bases)
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
-                           enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins)
+                           enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins, storage_layers_cm,
+                           storage_bins)
         self.next_row, self.kernel_ms, self.launches = 1, 0.0, 0
 
     def _spinup(self, flags):

@@ -77,6 +77,7 @@ class EnsembleStepper:
         self.profile_stride = 0
         self.wtd_hist_stride = 0
         self.theta_hist_bins = 0
+        self.storage_ranges, self.storage_bins = np.zeros((0, 2), dtype=np.int32), 0
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = 0, 0.0, 0
         self.filter_sm_nodes = None
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
@@ -265,6 +266,7 @@ class EnsembleStepper:
         L.check(self.lib.hc_set_profile_stats(self.h, stride))
         self.profile_stride = stride
         self.theta_hist_bins = 0          # keyed to the profile rows: the library turned it off
+        self.storage_ranges, self.storage_bins = np.zeros((0, 2), dtype=np.int32), 0      # ... and the layer storage
 
     def profile_snapshot(self, row=0):
         L.check(self.lib.hc_profile_snapshot(self.h, int(row)))
@@ -366,6 +368,86 @@ class EnsembleStepper:
         out = C.c_uint64()
         L.check(self.lib.hc_get_theta_hist_outside(self.h, C.byref(out)))
         return int(out.value)
+
+    # -- ensemble soil-water storage by depth layer (include/hydrocol.h hc_set_layer_storage) ---------------------------
+    def set_layer_storage(self, ranges, bins=0):
+        """Accumulate every member's storage dz sum theta over the node ranges ``ranges`` [L][2] = (i0, i1) (see
+        :func:`layer_ranges`) on the profile rows: exact moments, and with ``bins`` (a power of two in 32 .. 1024) the
+        histogram of the layer's mean theta.  No ranges = off.  Needs :meth:`set_profile_stats`, and comes before
+        :meth:`profile_snapshot` for row 0 to be counted."""
+        r = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(-1, 2))
+        if r.size and (r.min() < -INT32_MAX or r.max() > INT32_MAX):
+            raise ValueError("layer ranges must be node indices")
+        r32 = np.ascontiguousarray(r, dtype=np.int32)
+        self.storage_ranges, self.storage_bins = np.zeros((0, 2), dtype=np.int32), 0
+        L.check(self.lib.hc_set_layer_storage(self.h, r32.shape[0], L.iptr(r32), int(bins)))
+        self.storage_ranges, self.storage_bins = r32, int(bins) if r32.shape[0] else 0
+
+    def layer_storage_layout(self):
+        """(ranges [L][2], bins) as the library holds them."""
+        n, b = C.c_int32(), C.c_int32()
+        r = np.zeros((STORAGE_MAX_LAYERS, 2), dtype=np.int32)
+        L.check(self.lib.hc_get_layer_storage_layout(self.h, C.byref(n), C.byref(b), L.iptr(r)))
+        return r[:n.value].copy(), int(b.value)
+
+    def layer_storage_words(self):
+        n = C.c_int64()
+        L.check(self.lib.hc_get_layer_storage_words(self.h, C.byref(n)))
+        return int(n.value)
+
+    def layer_storage_table(self):
+        """The raw int64 moments table (layout: :func:`layer_storage_table_layout`)."""
+        t = np.zeros(self.layer_storage_words(), dtype=np.int64)
+        L.check(self.lib.hc_get_layer_storage(self.h, L.lptr(t), t.size))
+        return t
+
+    def set_layer_storage_table(self, table):
+        t = np.ascontiguousarray(table, dtype=np.int64).reshape(-1)
+        L.check(self.lib.hc_set_layer_storage_tables(self.h, L.lptr(t), t.size))
+
+    def export_layer_storage(self, device_ptr):
+        """Copy the moments table device-to-device to ``device_ptr`` (``layer_storage_words()`` int64 on this device)."""
+        L.check(self.lib.hc_export_layer_storage(self.h, C.c_void_p(int(device_ptr)), self.layer_storage_words()))
+
+    def _layer_storage_hist_raw(self):
+        n = self.P * stride_rows(self.T, self.profile_stride) * len(self.storage_ranges) * self.storage_bins
+        t = np.zeros(n + 2, dtype=np.int32)
+        L.check(self.lib.hc_get_layer_storage_hist(self.h, L.iptr(t), t.size))
+        return t
+
+    def layer_storage_hist_table(self):
+        """[P][n_prow][L][B] int32: members of each point per bin of the layer's mean theta and profile row."""
+        return self._layer_storage_hist_raw()[:-2].reshape(self.P, -1, len(self.storage_ranges), self.storage_bins)
+
+    def set_layer_storage_hist_table(self, table, outside=0):
+        """Install a histogram table (a checkpoint's, a sum over handles) and the outside count that goes with it."""
+        t = np.asarray(table)
+        if t.size and (t.min() < 0 or t.max() > INT32_MAX):
+            raise ValueError("histogram counts must lie in [0, 2^31 - 1]")
+        if not 0 <= int(outside) < 1 << 64:
+            raise ValueError("the outside count must lie in [0, 2^64)")
+        tail = np.array([int(outside)], dtype=np.uint64).view(np.int32)
+        t = np.concatenate([np.ascontiguousarray(t, dtype=np.int32).reshape(-1), tail])
+        L.check(self.lib.hc_set_layer_storage_hist_table(self.h, L.iptr(t), t.size))
+
+    def reset_layer_storage(self):
+        L.check(self.lib.hc_reset_layer_storage(self.h))
+
+    def layer_storage_outside(self):
+        """Members' layer means that fell in no bin (NaN, below 0 or above 1) since the tables were made."""
+        out = C.c_uint64()
+        L.check(self.lib.hc_get_layer_storage_outside(self.h, C.byref(out)))
+        return int(out.value)
+
+    def layer_storage_overflow(self):
+        out = C.c_uint64()
+        L.check(self.lib.hc_get_layer_storage_overflow(self.h, C.byref(out)))
+        return int(out.value)
+
+    def layer_storage_stats(self, table=None):
+        """Mean / sigma [cm] of ``layer_storage_table()`` (or of ``table``, e.g. summed over ranks): :func:`layer_storage_stats`."""
+        t = self.layer_storage_table() if table is None else table
+        return layer_storage_stats(t, self.P, self.T, len(self.storage_ranges), self.profile_stride)
 
     # -- particle filter on the well's water table (include/hydrocol.h hc_set_filter) ----------------------------------
     def set_filter(self, stride, sigma_cm=None, seed=0):
@@ -1085,6 +1167,164 @@ def theta_distribution(hist, levels, bins=None, stride=1):
         sat = np.where(n > 0, in_top / np.maximum(n, 1), np.nan)
     return {"rows": np.arange(hist.shape[-3], dtype=np.int64) * int(stride), "count": n.max(axis=-1), "quantiles": q,
             "levels": lv, "saturated_fraction": sat}
+
+
+# ---- soil-water storage by depth layer (include/hydrocol.h hc_set_layer_storage) --------------------------------------
+STORAGE_MAX_LAYERS = 8
+STORAGE_BINS = (32, 64, 128, 256, 512, 1024)
+STORAGE_MAX_CM = 4096.0
+PROF_SCALE_STORAGE = 28
+
+
+def layer_ranges(z, layers_cm):
+    """Node ranges [L][2] = (i0, i1) of the depth layers ``layers_cm`` = [(top, bottom), ...] in cm on the grid ``z``
+    (ascending): layer l holds the nodes with top <= z_i < bottom.  ValueError for more than 8 layers, for top >= bottom and
+    for a layer that holds no node."""
+    z = np.asarray(z, dtype=np.float64).reshape(-1)
+    layers = [tuple(float(v) for v in np.asarray(lay, dtype=np.float64).reshape(-1)) for lay in layers_cm]
+    if not 1 <= len(layers) <= STORAGE_MAX_LAYERS:
+        raise ValueError(f"1 to {STORAGE_MAX_LAYERS} storage layers, got {len(layers)}")
+    out = []
+    for lay in layers:
+        if len(lay) != 2 or not all(np.isfinite(lay)) or lay[0] >= lay[1]:
+            raise ValueError(f"a storage layer is (top, bottom) in cm with top < bottom, got {lay!r}")
+        i0, i1 = int(np.searchsorted(z, lay[0], side="left")), int(np.searchsorted(z, lay[1], side="left"))
+        if i0 >= i1:
+            raise ValueError(f"storage layer {lay!r} cm holds no node of the column [{float(z[0])!r}, {float(z[-1])!r}] cm")
+        out.append((i0, i1))
+    return np.array(out, dtype=np.int32)
+
+
+def _check_ranges(ranges, D):
+    r = np.asarray(ranges, dtype=np.int64).reshape(-1, 2)
+    if not 1 <= r.shape[0] <= STORAGE_MAX_LAYERS or np.any(r[:, 0] < 0) or np.any(r[:, 0] >= r[:, 1]) or np.any(r[:, 1] > D):
+        raise ValueError(f"1 to {STORAGE_MAX_LAYERS} node ranges [i0, i1) with 0 <= i0 < i1 <= {D}, got {r.tolist()}")
+    return r
+
+
+def layer_storage_of(theta, ranges, dz):
+    """The device's per-member reduction restated: ``theta`` [N][D] -> (S [N][L] in cm, u [N][L]).  T is summed in the
+    order of include/hydrocol.h, fixed by (i0, i1) alone: x_j (j = 0..63) starts at 0.0 and adds theta_i of the layer's
+    nodes with i mod 64 == j in ascending i; then x_j += x_{j+32}, x_j += x_{j+16}, ..., x_0 += x_1.  S = dz T,
+    u = T / (i1 - i0).  Equal to the device's bits."""
+    th = np.asarray(theta, dtype=np.float64)
+    th = th.reshape(-1, th.shape[-1])
+    r = _check_ranges(ranges, th.shape[1])
+    S, u = np.zeros((th.shape[0], len(r))), np.zeros((th.shape[0], len(r)))
+    for l, (i0, i1) in enumerate(r):
+        x = np.zeros((th.shape[0], 64))
+        for i in range(int(i0), int(i1)):
+            x[:, i % 64] = x[:, i % 64] + th[:, i]
+        s = 32
+        while s:
+            x[:, :s] = x[:, :s] + x[:, s:2 * s]
+            s //= 2
+        S[:, l], u[:, l] = float(dz) * x[:, 0], x[:, 0] / float(i1 - i0)
+    return S, u
+
+
+def layer_storage_hist_of(u, bins):
+    """The device's binning of one row's layer means ``u`` [N][L] -> (hist [L][bins] int64, outside): bin floor(u bins)
+    (exact: bins is a power of two), 1.0 to the last bin; NaN, values below 0 and above 1 go to no bin."""
+    bins = int(bins)
+    if bins not in STORAGE_BINS:
+        raise ValueError(f"storage histograms have a power of two in 32 .. 1024 bins, not {bins}")
+    u = np.asarray(u, dtype=np.float64)
+    inside = (u >= 0.0) & (u <= 1.0)
+    with np.errstate(invalid="ignore"):
+        b = np.where(u == 1.0, bins - 1, np.floor(np.where(inside, u, 0.0) * bins)).astype(np.int64)
+    hist = np.zeros((u.shape[1], bins), dtype=np.int64)
+    layer = np.broadcast_to(np.arange(u.shape[1]), u.shape)
+    np.add.at(hist, (layer[inside], b[inside]), 1)
+    return hist, int((~inside).sum())
+
+
+def layer_storage_table_layout(P, T, L, stride):
+    """{part: (offset, shape)} of the int64 table: stor [P][T_out][L][5], scnt [P][T_out], ovf [1]."""
+    n_prow = stride_rows(T, stride)
+    out, off = {}, 0
+    for name, shape in (("stor", (P, n_prow, L, PROF_WORDS)), ("scnt", (P, n_prow)), ("ovf", (1,))):
+        out[name] = (off, shape)
+        off += int(np.prod(shape))
+    out["words"] = (off, ())
+    return out
+
+
+def split_layer_storage_table(table, P, T, L, stride):
+    """Views of the parts of a flat moments table (see :func:`layer_storage_table_layout`)."""
+    t = np.asarray(table, dtype=np.int64).reshape(-1)
+    lay = layer_storage_table_layout(P, T, L, stride)
+    if t.size != lay["words"][0]:
+        raise ValueError(f"layer-storage table of {t.size} words, the layout has {lay['words'][0]}")
+    return {k: t[o:o + int(np.prod(sh))].reshape(sh) for k, (o, sh) in lay.items() if k != "words"}
+
+
+def layer_storage_tables_of(theta_rows, ranges, dz, bins=0, counted=None):
+    """Both tables of one point from the members' theta on every profile row, ``theta_rows`` [R][N][D] (``counted`` [R]
+    bool: rows that count their members; default all): the flat int64 moments table (stor [1][R][L][5], scnt, ovf) and,
+    with ``bins``, (hist [R][L][bins] int32, outside) -- else (None, 0).  The device's tables, bit for bit."""
+    th = np.asarray(theta_rows, dtype=np.float64)
+    R, N, D = th.shape
+    r = _check_ranges(ranges, D)
+    counted = np.ones(R, dtype=bool) if counted is None else np.asarray(counted, dtype=bool)
+    stor = np.zeros((1, R, len(r), PROF_WORDS), dtype=np.int64)
+    scnt, ovf, outside = np.zeros((1, R), dtype=np.int64), 0, 0
+    hist = np.zeros((R, len(r), int(bins)), dtype=np.int64) if bins else None
+    for j in range(R):
+        if not counted[j]:
+            continue
+        S, u = layer_storage_of(th[j], r, dz)
+        q, bad = profile_quantise(S, PROF_SCALE_STORAGE)
+        stor[0, j] = profile_words_of(q).astype(object).sum(axis=0).astype(np.int64)
+        scnt[0, j], ovf = N, ovf + bad
+        if bins:
+            hist[j], out = layer_storage_hist_of(u, bins)
+            outside += out
+    table = np.concatenate([stor.reshape(-1), scnt.reshape(-1), np.array([ovf], dtype=np.int64)])
+    return table, (hist.astype(np.int32) if bins else None, outside)
+
+
+def layer_storage_stats(table, P, T, L, stride):
+    """Mean and population sigma of the storage [cm] from a moments table, as :func:`profile_tables_to_stats` forms them
+    (exact integers, rounded once): ``mean_cm``, ``std_cm`` [P][T_out][L] (NaN where no member was counted), ``count``
+    [P][T_out], ``rows`` [T_out] and ``overflow``.  The leading [P] axis is dropped for a single point."""
+    parts = split_layer_storage_table(table, P, T, L, stride)
+    out = {}
+    out["mean_cm"], out["std_cm"] = limbs_to_mean_std(parts["scnt"][..., None], parts["stor"], PROF_SCALE_STORAGE)
+    out["count"] = parts["scnt"].copy()
+    if P == 1:
+        out = {k: v[0] for k, v in out.items()}
+    out["rows"] = np.arange(parts["scnt"].shape[1], dtype=np.int64) * int(stride)
+    out["overflow"] = int(parts["ovf"][0])
+    return out
+
+
+def layer_storage_distribution(hist, ranges, dz, levels, stride=1):
+    """Quantile bands of the storage from histograms ``hist`` [..., R, L, B] of the layers' mean theta, in NumPy integers.
+    Level p of a row and layer is the centre (b + 0.5) / B of the first bin b whose cumulative count reaches
+    k = max(1, ceil(n p)) in fp64 -- the rank of :func:`theta_distribution`, numpy.quantile(..., method="inverted_cdf") on
+    the bin index -- times the layer's thickness (i1 - i0) dz: ``quantiles_cm`` [..., R, Lv, L] (NaN where nobody was
+    counted), with ``rows`` [R], ``count`` [..., R, L], ``levels`` and ``thickness_cm`` [L]."""
+    hist = np.asarray(hist)
+    if hist.ndim < 3:
+        raise ValueError(f"histograms must be [..., R, L, B], got shape {hist.shape}")
+    B = hist.shape[-1]
+    r = np.asarray(ranges, dtype=np.int64).reshape(-1, 2)
+    if B not in STORAGE_BINS or r.shape[0] != hist.shape[-2]:
+        raise ValueError(f"histograms of {hist.shape[-2]} layers and {B} bins for {r.shape[0]} ranges (a power of two in 32 .. 1024 bins)")
+    if hist.size and hist.min() < 0:
+        raise ValueError("histogram counts must be >= 0")
+    lv = np.asarray(levels, dtype=np.float64).reshape(-1)
+    if lv.size > WTD_MAX_LEVELS or not np.all((lv >= 0.0) & (lv <= 1.0)):
+        raise ValueError(f"at most {WTD_MAX_LEVELS} quantile levels, each in [0, 1]: got {lv.tolist()}")
+    thick = (r[:, 1] - r[:, 0]).astype(np.float64) * float(dz)
+    cum = np.cumsum(hist.astype(np.int64), axis=-1)                 # [..., R, L, B]
+    n = cum[..., -1]                                                # [..., R, L]
+    k = np.maximum(1, np.ceil(n[..., None, :].astype(np.float64) * lv[:, None]).astype(np.int64))     # [..., R, Lv, L]
+    idx = (cum[..., None, :, :] < k[..., None]).sum(axis=-1)        # bins whose cumulative count stays below k
+    q = np.where(n[..., None, :] > 0, (np.minimum(idx, B - 1) + 0.5) / B * thick, np.nan)
+    return {"rows": np.arange(hist.shape[-3], dtype=np.int64) * int(stride), "count": n, "quantiles_cm": q, "levels": lv,
+            "thickness_cm": thick}
 
 
 # ---- particle filter on the host (include/hydrocol.h hc_set_filter) ----------------------------------------------------

@@ -43,6 +43,11 @@
  *   hc_get_theta_hist_bins
  *                      <- theta_vol (src/simulation.py:623) as the ensemble's distribution: per-node histograms of theta on
  *                         the profile rows, from which the host forms quantile bands of theta(z)
+ *   hc_set_layer_storage, hc_get_layer_storage_words, hc_get_layer_storage, hc_set_layer_storage_tables,
+ *   hc_export_layer_storage, hc_get_layer_storage_hist, hc_set_layer_storage_hist_table, hc_reset_layer_storage,
+ *   hc_get_layer_storage_outside, hc_get_layer_storage_overflow, hc_get_layer_storage_layout
+ *                      <- (new) dz * sum of theta_vol (src/simulation.py:623) over a depth layer, per member: the water a
+ *                         root zone or the whole column stores, as the ensemble's mean, sigma and histogram on the profile rows
  *   hc_set_filter, hc_get/set_filter_stats, hc_get/set_filter_base, hc_get_filter_ancestors/weights/draw,
  *   hc_set_filter_soil_moisture, hc_get/set_filter_sm_stats, hc_get_filter_sm_width/member_weights/loglik/sm_theta
  *                      <- (new) the ensemble conditioned on wtd_obs (src/simulation.py:582-612): a bootstrap particle filter,
@@ -353,6 +358,56 @@ int hc_set_theta_hist_table(hc_handle *h, const int32_t *table, int64_t n_entrie
 int hc_reset_theta_hist(hc_handle *h);
 int hc_get_theta_hist_outside(hc_handle *h, uint64_t *count);
 int hc_get_theta_hist_bins(hc_handle *h, int32_t *n_bins);   /* 0: off */
+
+/* Ensemble soil-water storage by depth layer: how much water [cm] each member holds between two depths, on the profile rows
+ * (hc_set_profile_stats, which must be on), as exact integer moments and histograms over the members.  The nodes of a
+ * column covary (one wetting front moves them together), so neither the per-node sigma nor the per-node histograms give a
+ * layer's spread: the sum over depth is taken per member, before anything is reduced over the members.
+ *   layers: L <= HC_STORAGE_MAX_LAYERS node ranges [i0_l, i1_l), 0 <= i0 < i1 <= D; layers may overlap or nest.
+ *   rows: the profile rows, at the profile stride (slot j <-> row j stride, n_prow slots); row 0 is counted by
+ *   hc_profile_snapshot, the others by hc_step_rows from the states the profile statistics read.  Skipped rows (wtd_obs < 0)
+ *   count no members; spin-up solves accumulate nothing.
+ *   per member m and layer l: T = sum_{i0 <= i < i1} theta_{m,i}, theta the cell model's theta_vol of the member's psi at the
+ *   node with no noise term (the value the profile statistics quantise and hc_model_nodes returns, bit for bit);
+ *   S = dz * T, the storage [cm of water]; u = T / (double)(i1 - i0), the layer's mean theta.  fp64, nothing contracted.
+ *   The sum's order is fixed by (i0, i1) alone -- not by D, the launch length or the wave that got the member:
+ *     x_j, j = 0..63, starts at 0.0 and adds theta_i of the layer's nodes with i mod 64 == j in ascending i;
+ *     then x_j += x_{j+32} (j < 32), x_j += x_{j+16} (j < 16), ..., x_0 += x_1; T = x_0.
+ *   moments (int64 table), in this order:
+ *     stor [P][n_prow][L][5]   q = rint(S * 2^HC_PROF_SCALE_STORAGE), |q| <= HC_PROF_Q_MAX: word 0 sum q, words 1..4 the
+ *                              20-bit limbs of sum q^2, as the profile statistics
+ *     scnt [P][n_prow]         members counted in each row
+ *     ovf  [1]                 values clamped by the quantisation or NaN
+ *     P n_prow (5 L + 1) + 1 words.  |S| < 2^12 cm fits: a layer of (i1 - i0) dz >= 4096 cm is refused, so only a NaN (or a
+ *     theta outside [0, 1]) can overflow.
+ *   histogram (int32 table; n_bins = 0: none): hist [P][n_prow][L][B], B a power of two in 32 .. 1024, then the outside
+ *     count as one uint64 in two more entries (low word first).  A member adds one to bin floor(u B) of its layer (u B is
+ *     exact in fp64); u == 1.0 goes to bin B - 1; a u that is NaN, below 0 or above 1 goes to no bin and adds one to `outside`.
+ *   Integer adds only across members: both tables are the same bits at any launch length, member split, point order and
+ *   number of handles / ranks summed.
+ * hc_set_layer_storage: n_layers 0 = off (default); otherwise (re)creates both tables zeroed.  `ranges` is [L][2] =
+ * (i0, i1).  HC_ERR_ARG (and off) when the profile statistics are off, for more than HC_STORAGE_MAX_LAYERS layers, an empty
+ * or out-of-column range, a layer of 4096 cm or more, any other bin count or a point of more than 2^31 - 1 members.
+ * hc_set_profile_stats turns it off.  Like the profile table both tables are re-created, zeroed, when the points, the
+ * forcing rows or the depth change (and refused then, if a range no longer fits the column).  get / set / export take the
+ * table's size in words (hc_get_layer_storage_words) or entries (P n_prow L B + 2) and fail on any other; the histogram
+ * calls fail when there is none.  hc_reset_layer_storage zeroes both.  hc_get_layer_storage_layout returns L, B and the
+ * ranges ([HC_STORAGE_MAX_LAYERS][2], the first L filled).  The step kernels are the same with the tables on or off, and
+ * with them off nothing is launched for them. */
+#define HC_STORAGE_MAX_LAYERS 8
+#define HC_PROF_SCALE_STORAGE 28    /* storage [cm]: 2^-28 cm steps, |S| < 2^12 cm                                  */
+#define HC_STORAGE_MAX_CM 4096.0
+int hc_set_layer_storage(hc_handle *h, int32_t n_layers, const int32_t *ranges, int32_t n_bins);
+int hc_get_layer_storage_words(hc_handle *h, int64_t *n_words);
+int hc_get_layer_storage(hc_handle *h, int64_t *table, int64_t n_words);
+int hc_set_layer_storage_tables(hc_handle *h, const int64_t *table, int64_t n_words);   /* checkpoint / resume, rank sums */
+int hc_export_layer_storage(hc_handle *h, void *device_dst, int64_t n_words);           /* as hc_export_profile_stats */
+int hc_get_layer_storage_hist(hc_handle *h, int32_t *table, int64_t n_entries);
+int hc_set_layer_storage_hist_table(hc_handle *h, const int32_t *table, int64_t n_entries);
+int hc_reset_layer_storage(hc_handle *h);
+int hc_get_layer_storage_outside(hc_handle *h, uint64_t *count);    /* 0 without a histogram */
+int hc_get_layer_storage_overflow(hc_handle *h, uint64_t *count);   /* the ovf slot */
+int hc_get_layer_storage_layout(hc_handle *h, int32_t *n_layers, int32_t *n_bins, int32_t *ranges);
 
 /* Particle filter on the well's water table (bootstrap filter, systematic resampling in exact integers).
  *   Assimilation rows: r >= 1, r % stride == 0 and wtd_obs[r] >= 0 (wtd_obs as it stands when hc_step_rows reaches the row:
