@@ -49,6 +49,28 @@ unknown keys, only membership of the 12 is checked):
   ``storage_hist_bins``, ``storage_hist_outside``, ``storage_quantile_levels`` and ``storage_quantile_cm``
   ``[T_out][Lv][L]`` (a sweep: a leading ``[P]`` axis on the per-row datasets), and the run ends with the line
   `` [Ensemble xN] storage: L layers on R rows``.
+* ``"Ensemble": {..., "Periods": {"Rows": 1440, "Shallower_than_cm": [100, 200], "Bins": 128, "Transpiration_max_cm": 16,
+  "Lateral_flow_max_cm": 4, "Quantiles": [0.05, 0.5, 0.95]}}``: period totals per member, reduced on the GPU at the end of
+  every period (include/hydrocol.h hc_set_period_totals): each member's transpiration and lateral flow summed over the
+  period's solved rows, its shallowest and deepest water table and the rows on which the water table stood at or above
+  each depth of ``Shallower_than_cm`` (optional, at most 4, mapped to the first node at or below the depth), then the
+  ensemble's mean and sigma from exact integer sums -- a member's rows are correlated in time, so none of these follows
+  from the per-row tables.  Exactly one of ``Rows`` (a period every so many rows, 1 .. 2^20) and ``Calendar``
+  (``"month"`` or ``"year"``: a period ends on the last row of each calendar month or year of the record's Datenum).
+  ``Bins`` (optional: a power of two in 32 .. 1024) adds histograms of the flux totals over [0, max) cm
+  (``Transpiration_max_cm``, default 16, and ``Lateral_flow_max_cm``, default 4: powers of two in 2^-8 .. 2^12) and of both
+  extremes over the depth grid and, with ``Quantiles`` (optional, default 0.05, 0.25, 0.5, 0.75, 0.95; at most 16, the
+  rank rule of ``Distribution.Quantiles``), their quantiles; the three keys need ``Bins``.  Periods that end after the
+  run's last row are dropped.  Needs no ``"Profiles"``.  Refused with ``"Filter": {"Sharded": true}`` on a single-point
+  run (the routed columns do not carry the members' accumulators).  The tables are summed over the ranks like the
+  moments.  Added to ``<Output_Name>_ensemble.h5``: ``period_end_rows``, ``period_solved_rows``, ``period_count``,
+  ``period_{transpiration,lateral_flow,wtd_shallowest,wtd_deepest}_{mean,std}_cm`` ``[n_period]``,
+  ``period_thresholds_cm``, ``period_threshold_nodes``, ``period_below_rows_{mean,std}`` and
+  ``period_below_fraction_mean`` ``[n_period][n_thresholds]``, ``period_overflow`` and, with ``Bins``,
+  ``period_hist_flux`` ``[n_period][2][B]`` and ``period_hist_wtd`` ``[n_period][2][D]`` int32, ``period_hist_outside``,
+  ``period_quantile_levels`` and ``period_{transpiration,lateral_flow,wtd_shallowest,wtd_deepest}_quantile_cm``
+  ``[n_period][Lv]`` (a sweep: a leading ``[P]`` axis on the per-period statistics), and the run ends with the line
+  `` [Ensemble xN] periods: R periods, K quantities``.
 * ``"Ensemble": {..., "Distribution": {"Stride": 48, "Quantiles": [0.05, 0.5, 0.95]}}``: the members' water-table index
   counted per row on the GPU -- every 48th forcing row (default 48; 0 = off) a histogram over the depth grid, summed over
   the ranks like the moments -- and from it the quantile depths (NumPy's ``method="inverted_cdf"``; default levels 0.05,
@@ -183,6 +205,7 @@ def main(params_file=None, data_file=None, seed=None, device=0, gpus=None, _sett
             distribution_settings(params["Ensemble"])      # a bad Distribution block fails before any GPU is touched
             profile_distribution_settings(params["Ensemble"])
             storage_settings(params["Ensemble"])
+            period_settings(params["Ensemble"])
         n_gpus = multigpu.requested_gpus(gpus, params)
         if params.get("Ensemble"):
             filter_settings(params["Ensemble"], n_gpus)     # so does a bad Filter block
@@ -249,6 +272,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     dist_stride, dist_levels = distribution_settings(ens)
     theta = profile_distribution_settings(ens)
     storage = storage_settings(ens)
+    periods = period_settings(ens)
     filt = filter_settings(ens, ranks.world)
     enkf = enkf_settings(ens, ranks.world)
     sm = soil_moisture_settings(ens, ranks.world)
@@ -265,9 +289,10 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     n_members = int(ens.get("Members", 4096))
     days = int(ens.get("Days", (forcing.dim_t - 1) // 48))
     rows = min(days * 48, forcing.dim_t - 1)
+    plan = period_plan(periods, cols, forcing, rows)            # before any GPU call, like the storage's ranges
     if ens.get("Points"):
         return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels, filt,
-                          enkf, record, scheme, window, frecord, theta, storage)
+                          enkf, record, scheme, window, frecord, theta, storage, periods, plan)
     sharded = enkf_sharded(ens)
     fsharded = filter_sharded(ens)
     if sharded:
@@ -289,7 +314,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
                              noise=str(ens.get("Noise", "philox")).lower(),
                              spinup=str(ens.get("Spinup", "shared")).lower(), profile_stride=stride,
                              wtd_hist_stride=dist_stride, theta_hist_bins=theta[0], **_filter_kwargs(filt, frecord),
-                             **_enkf_kwargs(enkf, record, scheme, window), **_storage_kwargs(storage), **shard_kw)
+                             **_enkf_kwargs(enkf, record, scheme, window), **_storage_kwargs(storage),
+                             **_period_kwargs(periods, plan), **shard_kw)
     label = f"Ensemble x{n_members}"
     _step_all(sim, rows, label, ranks)
     # the run's one collective: int64 (count, sum idx, sum idx^2) per row, exact and order-independent
@@ -322,6 +348,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     stor_tables, storage_line = _reduce_storage(ranks, sim, [0], 1, forcing.dim_t, cols, stride, storage, label,
                                                 keep_points=False)
     extra.update(stor_tables)
+    ptables, period_line = _reduce_periods(ranks, sim, [0], 1, cols, forcing, periods, plan, label, keep_points=False)
+    extra.update(ptables)
     # the filters' tables describe the one point: every rank of a sharded run holds the same ones, and rank 0's are taken
     # (placed by it alone; a sum over the ranks would count them world times)
     eids = [0] if ranks.rank == 0 else []
@@ -362,6 +390,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
         print(theta_line)
     if storage_line:
         print(storage_line)
+    if period_line:
+        print(period_line)
     sim.close()
 
 
@@ -511,6 +541,120 @@ def storage_ranges(storage, cols):
 
 def _storage_kwargs(storage):
     return {} if storage is None else dict(storage_layers_cm=storage[0], storage_bins=storage[1])
+
+
+PERIOD_KEYS = ("Rows", "Calendar", "Shallower_than_cm", "Bins", "Transpiration_max_cm", "Lateral_flow_max_cm", "Quantiles")
+
+
+def period_settings(ens):
+    """Ensemble.Periods -> {"rows", "calendar", "thresholds_cm", "bins", "flux_max_cm", "levels"}; None when absent.
+    Pure: runs before any GPU call, and a bad value is a ValueError (message + exit status 1).  Exactly one of ``Rows`` and
+    ``Calendar``; ``Bins`` is optional (0: moments only), and ``Quantiles`` and the two ``..._max_cm`` keys need it.
+    Refused with a sharded particle filter on a single-point run."""
+    import math
+    from numbers import Real
+    from .stepper import PERIOD_MAX_ROWS, PERIOD_MAX_THRESHOLDS, flux_max_log2_of
+    block = ens.get("Periods")
+    if block is None:
+        return None
+    if not isinstance(block, dict):
+        raise ValueError(f" Ensemble: Periods = {block!r} must be an object such as "
+                         f"{{\"Rows\": 1440, \"Shallower_than_cm\": [100, 200], \"Bins\": 128}}.")
+    unknown = sorted(set(block) - set(PERIOD_KEYS))
+    if unknown:
+        raise ValueError(f" Ensemble: Periods has unknown keys {unknown} (known: {list(PERIOD_KEYS)}).")
+    if ("Rows" in block) == ("Calendar" in block):
+        raise ValueError(" Ensemble: Periods needs exactly one of Rows (a period every so many rows) and Calendar "
+                         "(\"month\" or \"year\").")
+    rows = calendar = None
+    if "Rows" in block:
+        rows = block["Rows"]
+        if (isinstance(rows, bool) or not isinstance(rows, Real) or not math.isfinite(rows) or rows != int(rows)
+                or not 1 <= rows <= PERIOD_MAX_ROWS):
+            raise ValueError(f" Ensemble: Periods.Rows = {rows!r} must be a whole number of rows in 1 .. {PERIOD_MAX_ROWS}.")
+        rows = int(rows)
+    else:
+        calendar = block["Calendar"]
+        if calendar not in ("month", "year"):
+            raise ValueError(f" Ensemble: Periods.Calendar = {calendar!r} must be \"month\" or \"year\".")
+    depths = block.get("Shallower_than_cm", [])
+    if not isinstance(depths, (list, tuple)) or len(depths) > PERIOD_MAX_THRESHOLDS:
+        raise ValueError(f" Ensemble: Periods.Shallower_than_cm = {depths!r} must be a list of at most "
+                         f"{PERIOD_MAX_THRESHOLDS} depths in cm.")
+    for d in depths:
+        if isinstance(d, bool) or not isinstance(d, Real) or not math.isfinite(d):
+            raise ValueError(f" Ensemble: Periods.Shallower_than_cm: {d!r} is not a depth in cm.")
+    bins = block.get("Bins", 0)
+    if "Bins" in block and (isinstance(bins, bool) or not isinstance(bins, Real) or bins not in (32, 64, 128, 256, 512, 1024)):
+        raise ValueError(f" Ensemble: Periods.Bins = {bins!r} must be a power of two in 32 .. 1024.")
+    for key in ("Quantiles", "Transpiration_max_cm", "Lateral_flow_max_cm"):
+        if key in block and not bins:
+            raise ValueError(f" Ensemble: Periods.{key} needs Periods.Bins (it belongs to the histograms).")
+    levels = flux_max = None
+    if bins:
+        flux_max = []
+        for key, default in (("Transpiration_max_cm", 16), ("Lateral_flow_max_cm", 4)):
+            v = block.get(key, default)
+            try:
+                if isinstance(v, bool) or not isinstance(v, Real):
+                    raise ValueError
+                flux_max_log2_of(v)
+            except ValueError:
+                raise ValueError(f" Ensemble: Periods.{key} = {v!r} must be a power of two in 2^-8 .. 2^12 cm.") from None
+            flux_max.append(float(v))
+        levels = block.get("Quantiles", list(DEFAULT_QUANTILES))
+        if not isinstance(levels, (list, tuple)) or not levels:
+            raise ValueError(f" Ensemble: Periods.Quantiles = {levels!r} must be a non-empty list of levels in [0, 1].")
+        if len(levels) > 16:
+            raise ValueError(f" Ensemble: Periods.Quantiles holds {len(levels)} levels; at most 16 are supported.")
+        for q in levels:
+            if isinstance(q, bool) or not isinstance(q, Real) or not math.isfinite(q):
+                raise ValueError(f" Ensemble: Periods.Quantiles: {q!r} is not a number.")
+            if not 0.0 <= q <= 1.0:
+                raise ValueError(f" Ensemble: Periods.Quantiles: {q!r} lies outside [0, 1].")
+        levels = tuple(float(q) for q in levels)
+    filt = ens.get("Filter")
+    if isinstance(filt, dict) and filt.get("Sharded") and filt.get("Stride") and not ens.get("Points"):
+        raise ValueError(" Ensemble: Periods with \"Filter\": {\"Sharded\": true}: the columns the ranks exchange do not carry "
+                         "the members' period accumulators; run the filter unsharded.")
+    return {"rows": rows, "calendar": calendar, "thresholds_cm": tuple(float(d) for d in depths), "bins": int(bins),
+            "flux_max_cm": None if flux_max is None else tuple(flux_max), "levels": levels}
+
+
+def period_plan(periods, cols, forcing, run_rows):
+    """(end rows, threshold nodes) of the block on this record and column (stepper.period_ends, stepper.sensor_nodes), with
+    their refusals in the CLI's words: a depth outside the column, no period that ends within the run's rows, too many or
+    too long periods.  Periods that end after the run's last row are dropped.  None without a block."""
+    from .stepper import PERIOD_MAX_PERIODS, PERIOD_MAX_ROWS, period_ends, sensor_nodes
+    import numpy as np
+    if periods is None:
+        return None
+    try:
+        nodes = sensor_nodes(cols.z, periods["thresholds_cm"])
+    except ValueError as bad:
+        raise ValueError(f" Ensemble: Periods.Shallower_than_cm: {bad}.") from None
+    if periods["rows"] is not None:
+        ends = period_ends(forcing.dim_t, rows=periods["rows"])
+    else:
+        ends = period_ends(forcing.dim_t, datenum=forcing.datenum, calendar=periods["calendar"])
+    ends = ends[ends <= int(run_rows)]
+    if ends.size == 0:
+        raise ValueError(f" Ensemble: Periods: no period ends within the run's {int(run_rows)} rows.")
+    if ends.size > PERIOD_MAX_PERIODS:
+        raise ValueError(f" Ensemble: Periods: {ends.size} periods; at most {PERIOD_MAX_PERIODS} are supported.")
+    longest = int(np.diff(np.concatenate([[0], ends])).max())
+    if longest > PERIOD_MAX_ROWS:
+        raise ValueError(f" Ensemble: Periods: a period of {longest} rows; at most {PERIOD_MAX_ROWS} are supported.")
+    return ends, nodes
+
+
+def _period_kwargs(periods, plan):
+    if periods is None:
+        return {}
+    kw = dict(period_ends=plan[0], period_thresholds_cm=periods["thresholds_cm"], period_bins=periods["bins"])
+    if periods["bins"]:
+        kw["period_flux_max_cm"] = periods["flux_max_cm"]
+    return kw
 
 
 FILTER_KEYS = ("Stride", "Sigma_cm", "Seed", "Sharded", "Soil_Moisture")
@@ -1112,9 +1256,68 @@ def _reduce_storage(ranks, sim, ids, P, T, cols, stride, storage, label, keep_po
     return out, line
 
 
+def _reduce_periods(ranks, sim, ids, P, cols, forcing, periods, plan, label, keep_points):
+    """The period-totals tables (``periods``: the block's settings, ``plan``: end rows and threshold nodes) from this rank's
+    handle ``sim`` (None: no points), its points ``ids`` placed in the run's [P] tables and summed over the ranks like the
+    storage tables -- the overflow and outside counts with them -- then the statistics, the quantiles and the closing line
+    (rank 0)."""
+    import numpy as np
+    from .multigpu import place_points
+    from .stepper import (flux_max_log2_of, period_totals_distribution, period_totals_stats, period_totals_table_layout,
+                          split_period_totals_table)
+    if periods is None:
+        return {}, None
+    ends, nodes = plan
+    n_period, K, bins, D = len(ends), 4 + len(nodes), periods["bins"], cols.dim_d
+    local = (sim.period_table() if sim is not None else
+             np.zeros(period_totals_table_layout(0, n_period, K)["words"][0], dtype=np.int64))
+    parts = split_period_totals_table(local, len(ids), n_period, K)
+    table = ranks.allreduce_sum(np.concatenate([place_points(parts["pmom"], ids, P).reshape(-1),
+                                                place_points(parts["pcnt"], ids, P).reshape(-1), parts["ovf"]]))
+    if bins:
+        lf, lw = (sim.stepper.period_totals_hists() if sim is not None else
+                  (np.zeros((0, n_period, 2, bins), dtype=np.int32), np.zeros((0, n_period, 2, D), dtype=np.int32)))
+        hist_flux, hist_wtd = place_points(lf, ids, P, ranks), place_points(lw, ids, P, ranks)
+        outside = int(ranks.allreduce_sum(np.array([sim.stepper.period_totals_outside() if sim is not None else 0],
+                                                   dtype=np.int64))[0])
+    if ranks.rank != 0:
+        return {}, None
+    stats = period_totals_stats(table, P, ends, len(nodes), float(cols.z[0]), cols.dz, forcing.wtd_obs)
+    lead = (lambda v: v[None]) if keep_points and P == 1 else (lambda v: v)
+    out = {"period_end_rows": np.asarray(ends, dtype=np.int64),
+           "period_solved_rows": np.asarray(stats["solved_rows"], dtype=np.int64),
+           "period_count": np.asarray(lead(stats["count"]), dtype=np.int64),
+           "period_thresholds_cm": np.asarray(periods["thresholds_cm"], dtype=np.float64),
+           "period_threshold_nodes": np.asarray(nodes, dtype=np.int64),
+           "period_overflow": np.array(stats["overflow"], dtype=np.int64)}
+    for name in ("transpiration", "lateral_flow", "wtd_shallowest", "wtd_deepest"):
+        for what in ("mean_cm", "std_cm"):
+            out[f"period_{name}_{what}"] = np.asarray(lead(stats[f"{name}_{what}"]), dtype=np.float64)
+    for what in ("below_rows_mean", "below_rows_std", "below_fraction_mean"):
+        out["period_" + what] = np.asarray(lead(stats[what]), dtype=np.float64)
+    if bins:
+        if not keep_points:
+            hist_flux, hist_wtd = hist_flux[0], hist_wtd[0]
+        dist = period_totals_distribution(hist_flux, hist_wtd, periods["levels"],
+                                          [flux_max_log2_of(v) for v in periods["flux_max_cm"]], float(cols.z[0]), cols.dz)
+        out.update({"period_hist_flux": np.asarray(hist_flux, dtype=np.int32),
+                    "period_hist_wtd": np.asarray(hist_wtd, dtype=np.int32),
+                    "period_hist_bins": np.array(bins, dtype=np.int64),
+                    "period_hist_flux_max_cm": np.asarray(periods["flux_max_cm"], dtype=np.float64),
+                    "period_hist_outside": np.array(outside, dtype=np.int64),
+                    "period_quantile_levels": np.asarray(dist["levels"], dtype=np.float64)})
+        for name in ("transpiration", "lateral_flow", "wtd_shallowest", "wtd_deepest"):
+            out[f"period_{name}_quantile_cm"] = np.asarray(dist[f"{name}_quantile_cm"], dtype=np.float64)
+    n = int((np.asarray(stats["count"]).reshape(-1, n_period) > 0).any(axis=0).sum())
+    line = f" [{label}] periods: {n} periods, {K} quantities"
+    if stats["overflow"] or (bins and outside):
+        line += f" ({stats['overflow']} values clamped, {outside if bins else 0} totals outside their histogram)"
+    return out, line
+
+
 def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride=0, dist_levels=None,
                filt=(0, None, None), enkf=(0, None, None, None), record=None, scheme=None, window=None, frecord=None,
-               theta=(0, None), storage=None):
+               theta=(0, None), storage=None, periods=None, plan=None):
     """Parameter points x members: this rank's points in one handle (ensemble.SweepSimulation), the whole table assembled
     over the ranks (multigpu.assemble_points)."""
     import numpy as np
@@ -1142,7 +1345,7 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
         sim = SweepSimulation(points, forcing, n_members, seed=int(ens.get("Seed", 0)), device=device, point_ids=mine,
                               profile_stride=stride, wtd_hist_stride=dist_stride, theta_hist_bins=theta[0],
                               **_filter_kwargs(filt, frecord), **_enkf_kwargs(enkf, record, scheme, window),
-                              **_storage_kwargs(storage))
+                              **_storage_kwargs(storage), **_period_kwargs(periods, plan))
         _step_all(sim, rows, label, ranks)
         table = sim.moments()
         for j, k in enumerate(mine):
@@ -1160,6 +1363,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     arrays.update(ttables)
     stor_tables, storage_line = _reduce_storage(ranks, sim, mine, P, T, ref, stride, storage, label, keep_points=True)
     arrays.update(stor_tables)
+    ptables, period_line = _reduce_periods(ranks, sim, mine, P, ref, forcing, periods, plan, label, keep_points=True)
+    arrays.update(ptables)
     ftables, filter_line = _reduce_filter(ranks, sim, mine, P, T, filt, label, keep_points=True)
     arrays.update(ftables)
     fstables, fsm_line = _reduce_sm(ranks, sim, mine, P, T, filt[0], frecord, label, keep_points=True, owner="filter")
@@ -1192,6 +1397,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
         print(theta_line)
     if storage_line:
         print(storage_line)
+    if period_line:
+        print(period_line)
 
 
 def run_cli(argv=None):

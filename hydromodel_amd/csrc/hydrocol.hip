@@ -174,6 +174,19 @@ struct hc_handle {
     int stor_range[HC_STORAGE_MAX_LAYERS][2] = {};
     AccTable<long long> stor{"words"};
     AccTable<int> shist{"entries"};
+    // period totals per member (hc_set_period_totals): the periods' inclusive end rows, the threshold nodes, the flux
+    // histograms' bin count and range exponents; the members' int64 accumulators [K][N] keyed by (N, K) and their second
+    // buffer for the particle filter's ancestry; the int64 table pmom [P][n_period][K][5], pcnt, ovf and, with bins, the
+    // int32 table phist_flux [P][n_period][2][B], phist_wtd [P][n_period][2][D] + the outside count, keyed like the profile table
+    int per_n = 0;               // 0: off
+    std::vector<int64_t> per_end;
+    int per_nthr = 0, per_bins = 0;
+    int per_thr[HC_PERIOD_MAX_THRESHOLDS] = {};
+    int per_fexp[2] = {};
+    AccTable<long long> pacc{"words"};
+    DevBuf<long long> pacc_alt;
+    AccTable<long long> pmom{"words"};
+    AccTable<int> phist{"entries"};
     // particle filter on the well's water table (hc_set_filter): diagnostics float64 [P][n_arow][4] keyed by
     // (points, rows, stride), the second state / base buffers of the gather, the last assimilation's q_b, {Q, r} and
     // ancestors (test hooks), and the host copy of wtd_obs that decides which rows are assimilated
@@ -679,6 +692,196 @@ __global__ __launch_bounds__(HIST_THREADS) void wtd_hist_kernel(const unsigned s
     for (int b = threadIdx.x; b < D; b += HIST_THREADS) {
         const unsigned c = bins[b];
         if (c) atomicAdd(t + b, (int)c);
+    }
+}
+
+// ---- period totals per member (hc_set_period_totals, include/hydrocol.h): integers only
+constexpr int PERIOD_K = 4 + HC_PERIOD_MAX_THRESHOLDS;     // the accumulators a member carries at most
+constexpr int PERIOD_THREADS = 256;
+constexpr long long PERIOD_WTD_NONE = 65535;               // wtd_shallowest of a member with no solved row yet
+struct PeriodThresholds {
+    int n;
+    int node[HC_PERIOD_MAX_THRESHOLDS];
+};
+
+// The launch's rows [0, rows) (forcing rows row0 ...) added to the members' accumulators acc [K][N]: one thread per
+// member.  Per row a wave reads 64 x 16 contiguous bytes of diag [rows][N][2] and 64 x 2 of wtd [rows][N]; the K running
+// values stay in registers over the rows, ascending, and the accumulators are read and written once per launch (each
+// of the K planes coalesced).  A skipped row (wtd_obs < 0, wave-uniform) adds nothing.
+__global__ __launch_bounds__(PERIOD_THREADS) void period_accumulate_kernel(
+    const double *diag, const unsigned short *wtd, const int *wtd_obs, long long n_members, long long row0, int rows,
+    const PeriodThresholds Th, long long *acc, unsigned long long *ovf_word)
+{
+    const long long m = (long long)blockIdx.x * PERIOD_THREADS + threadIdx.x;
+    if (m >= n_members) return;
+    const double s_flux = ldexp(1.0, HC_PROF_SCALE_FLUX);
+    long long flux0 = 0, flux1 = 0;
+    int lo = (int)PERIOD_WTD_NONE, hi = 0;
+    int below[HC_PERIOD_MAX_THRESHOLDS] = {};
+    unsigned ovf = 0;
+    for (int r = 0; r < rows; r++) {
+        if (wtd_obs[row0 + r] < 0) continue;
+        const size_t e = (size_t)r * n_members + m;
+        const double2 d = reinterpret_cast<const double2 *>(diag)[e];
+        const int w = (int)wtd[e];
+        flux0 += prof_quantise(d.x, s_flux, ovf);
+        flux1 += prof_quantise(d.y, s_flux, ovf);
+        lo = w < lo ? w : lo;
+        hi = w > hi ? w : hi;
+#pragma unroll
+        for (int j = 0; j < HC_PERIOD_MAX_THRESHOLDS; j++) below[j] += (j < Th.n && w <= Th.node[j]) ? 1 : 0;
+    }
+    long long *a = acc + m;
+    a[0] += flux0;
+    a[n_members] += flux1;
+    const long long lo0 = a[2 * n_members], hi0 = a[3 * n_members];
+    a[2 * n_members] = lo < lo0 ? lo : lo0;
+    a[3 * n_members] = hi > hi0 ? hi : hi0;
+#pragma unroll
+    for (int j = 0; j < HC_PERIOD_MAX_THRESHOLDS; j++)
+        if (j < Th.n) a[(size_t)(4 + j) * n_members] += below[j];
+    if (ovf) atomicAdd(ovf_word, (unsigned long long)ovf);
+}
+
+// one to bin b of every lane that has one (b >= 0), grouped as wtd_hist_kernel groups them: the members of a point sit in
+// a handful of bins, so a ds_add_u32 per lane would serialise on a few addresses; one ballot per distinct bin and one
+// lane adds the group's size.  Every lane of the wave calls it.
+__device__ __forceinline__ void period_bin_add(unsigned *bins, int b, int lane)
+{
+    unsigned long long pending = __ballot(b >= 0);
+    while (pending) {
+        const int leader = __ffsll((long long)pending) - 1;
+        const int v = __builtin_amdgcn_readlane(b, leader);
+        const unsigned long long same = __ballot(b == v) & pending;
+        if (lane == leader) atomicAdd(&bins[v], (unsigned)__popcll(same));
+        pending &= ~same;
+    }
+}
+
+// The end of period `period`: grid x = member slices of one point, y = point.  A member with a solved row in the period
+// (wtd_shallowest != 65535) enters the moments pmom [P][n_period][K][5] -- the flux totals as v = A >> 12 (floor; 2^-20
+// cm), clamped to HC_PROF_Q_MAX and counted, indices and counts as they are -- through prof_add in registers, cross-lane
+// shuffles, LDS and int64 atomics, and, with B > 0, the block's LDS histograms uint32 [2][B] (bin (v B) >> sh_q of
+// 0 <= v < 2^sh_q, sh_q = 20 + e_q; others count as outside) and [2][D] (shallowest, deepest index).  Only nonzero bins
+// go to the tables (int32 atomics).  Every member's accumulators are reset.
+__global__ __launch_bounds__(PERIOD_THREADS) void period_reduce_kernel(
+    long long *acc, long long n_members, long long members_per_point, long long members_per_block, long long period,
+    long long n_period, int K, int B, int D, int sh0, int sh1, long long *pmom, long long *pcnt,
+    unsigned long long *ovf_word, int *hist_flux, int *hist_wtd, unsigned long long *outside_word)
+{
+    extern __shared__ unsigned period_bins[];        // flux [2][B], then wtd [2][D]
+    __shared__ long long part[PERIOD_THREADS / WAVE][PERIOD_K][HC_PROF_WORDS];
+    __shared__ long long cnt_part[PERIOD_THREADS / WAVE];
+    __shared__ unsigned ovf_sum, outside_sum;
+    const int n_bins = B > 0 ? 2 * (B + D) : 0;
+    for (int b = threadIdx.x; b < n_bins; b += PERIOD_THREADS) period_bins[b] = 0;
+    if (threadIdx.x == 0) ovf_sum = 0, outside_sum = 0;
+    __syncthreads();
+    const long long point = blockIdx.y;
+    const long long end = (point + 1) * members_per_point;
+    const long long m0 = point * members_per_point + (long long)blockIdx.x * members_per_block;
+    const long long m1 = m0 + members_per_block < end ? m0 + members_per_block : end;
+    const int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
+    const long long qmax = HC_PROF_Q_MAX;
+    long long words[PERIOD_K][HC_PROF_WORDS] = {};
+    long long counted = 0;
+    unsigned ovf = 0, outside = 0;
+    // wave-uniform trip count: every lane of a wave runs the ballots of every round
+    for (long long k0 = m0 + (threadIdx.x - lane); k0 < m1; k0 += PERIOD_THREADS) {
+        const long long m = k0 + lane;
+        const bool live = m < m1;
+        long long a[PERIOD_K];
+#pragma unroll
+        for (int k = 0; k < PERIOD_K; k++) a[k] = (live && k < K) ? acc[(size_t)k * n_members + m] : 0;
+        int bin[4] = {-1, -1, -1, -1};
+        if (live && a[2] != PERIOD_WTD_NONE) {
+            counted++;
+#pragma unroll
+            for (int q = 0; q < 2; q++) {
+                long long v = a[q] >> 12;            // floor(A / 4096)
+                if (v > qmax) v = qmax, ovf++;
+                if (v < -qmax) v = -qmax, ovf++;
+                prof_add(words[q], v);
+                if (B > 0) {
+                    const int sh = q ? sh1 : sh0;
+                    if (v >= 0 && v < (1LL << sh))
+                        bin[q] = q * B + (int)((v * B) >> sh);
+                    else
+                        outside++;
+                }
+            }
+#pragma unroll
+            for (int k = 2; k < PERIOD_K; k++)
+                if (k < K) prof_add(words[k], a[k]);
+            if (B > 0) {
+#pragma unroll
+                for (int q = 0; q < 2; q++) {
+                    if (a[2 + q] >= 0 && a[2 + q] < D)
+                        bin[2 + q] = 2 * B + q * D + (int)a[2 + q];
+                    else
+                        outside++;
+                }
+            }
+        }
+        if (live) {
+#pragma unroll
+            for (int k = 0; k < PERIOD_K; k++)
+                if (k < K) acc[(size_t)k * n_members + m] = k == 2 ? PERIOD_WTD_NONE : 0;
+        }
+        if (B > 0) {
+#pragma unroll
+            for (int q = 0; q < 4; q++) period_bin_add(period_bins, bin[q], lane);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < PERIOD_K; k++) {
+        if (k < K) {
+#pragma unroll
+            for (int w = 0; w < HC_PROF_WORDS; w++) {
+                long long v = words[k][w];
+                for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+                if (lane == 0) part[wave][k][w] = v;
+            }
+        }
+    }
+    for (int o = WAVE / 2; o > 0; o >>= 1) counted += __shfl_xor(counted, o);
+    if (lane == 0) cnt_part[wave] = counted;
+    if (ovf) atomicAdd(&ovf_sum, ovf);
+    if (outside) atomicAdd(&outside_sum, outside);
+    __syncthreads();
+    const size_t slot = (size_t)point * n_period + period;
+    if ((int)threadIdx.x < K * HC_PROF_WORDS) {
+        const int k = threadIdx.x / HC_PROF_WORDS, w = threadIdx.x % HC_PROF_WORDS;
+        long long sum = 0;
+#pragma unroll
+        for (int u = 0; u < PERIOD_THREADS / WAVE; u++) sum += part[u][k][w];
+        if (sum) atomicAdd(reinterpret_cast<unsigned long long *>(pmom + (slot * K + k) * HC_PROF_WORDS + w), (unsigned long long)sum);
+    }
+    if (B > 0) {
+        int *tf = hist_flux + slot * 2 * B, *tw = hist_wtd + slot * 2 * D;
+        for (int b = threadIdx.x; b < n_bins; b += PERIOD_THREADS) {
+            const unsigned c = period_bins[b];
+            if (c) atomicAdd(b < 2 * B ? tf + b : tw + (b - 2 * B), (int)c);
+        }
+    }
+    if (threadIdx.x == 0) {
+        long long n = 0;
+#pragma unroll
+        for (int u = 0; u < PERIOD_THREADS / WAVE; u++) n += cnt_part[u];
+        if (n) atomicAdd(reinterpret_cast<unsigned long long *>(pcnt + slot), (unsigned long long)n);
+        if (ovf_sum) atomicAdd(ovf_word, (unsigned long long)ovf_sum);
+        if (B > 0 && outside_sum) atomicAdd(outside_word, (unsigned long long)outside_sum);
+    }
+}
+
+// the particle filter's ancestry applied to the accumulators, next to filter_gather_kernel: slot m takes the K values of
+// its ancestor (into the second buffer; the host swaps it in), each plane read through anc and written coalesced
+__global__ void period_gather_kernel(const long long *anc, const long long *acc, long long *acc_out, long long n_members, int K)
+{
+    const size_t total = (size_t)n_members * K;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const long long m = (long long)(e % n_members), a = anc[m];
+        acc_out[e] = acc[e - m + (a >= 0 && a < n_members ? a : m)];     // (every slot is filled: a guard)
     }
 }
 
@@ -2519,6 +2722,68 @@ int ensure_stor_hist(hc_handle *h)
     return h->stor_bins > 0 ? HC_OK : fail(HC_ERR_ARG, "layer storage has no histogram (hc_set_layer_storage with n_bins = 0)");
 }
 
+// the period-totals tables (hc_set_period_totals): int64 pmom [P][n_period][K][5], pcnt [P][n_period], ovf [1]; with bins
+// the int32 phist_flux [P][n_period][2][B], phist_wtd [P][n_period][2][D] and the outside count (one uint64 in two
+// entries, 8-byte aligned behind an even count)
+struct PeriodLayout {
+    int K = 0;
+    int64_t pcnt = 0, ovf = 0, words = 0, wtd = 0, entries = 0;
+};
+PeriodLayout period_layout(const hc_handle *h)
+{
+    PeriodLayout L;
+    const int64_t slots = (int64_t)h->n_points * h->per_n;
+    L.K = 4 + h->per_nthr;
+    L.pcnt = slots * L.K * HC_PROF_WORDS;
+    L.ovf = L.pcnt + slots;
+    L.words = L.ovf + 1;
+    L.wtd = slots * 2 * h->per_bins;
+    L.entries = h->per_bins > 0 ? slots * 2 * ((int64_t)h->per_bins + h->p.dim_d) : 0;
+    return L;
+}
+int ensure_period(hc_handle *h)
+{
+    if (h->per_n <= 0) return fail(HC_ERR_ARG, "period totals are off (hc_set_period_totals)");
+    if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
+    if (h->per_end.back() >= h->n_rows)
+        return fail(HC_ERR_ARG, "period totals: the last end row %lld is not below the %lld forcing rows",
+                    (long long)h->per_end.back(), (long long)h->n_rows);
+    for (int j = 0; j < h->per_nthr; j++)
+        if (h->per_thr[j] < 0 || h->per_thr[j] >= h->p.dim_d)
+            return fail(HC_ERR_ARG, "period totals: threshold node %d is outside the column's %d nodes", h->per_thr[j],
+                        (int)h->p.dim_d);
+    if (h->fs_n > 0)
+        return fail(HC_ERR_ARG, "period totals with a sharded particle filter (hc_set_filter_shard): the routed columns do "
+                                "not carry the members' accumulators");
+    if (h->n_members / std::max(h->n_points, 1) > INT32_MAX)
+        return fail(HC_ERR_ARG, "period totals: %lld members per point do not fit an int32 bin",
+                    (long long)(h->n_members / std::max(h->n_points, 1)));
+    const PeriodLayout L = period_layout(h);
+    if (L.entries > HC_WTD_HIST_MAX_ENTRIES)
+        return fail(HC_ERR_ARG, "period totals: %lld histogram entries exceed HC_WTD_HIST_MAX_ENTRIES", (long long)L.entries);
+    if (int rc = h->pmom.ensure(h->n_points, h->n_rows, h->p.dim_d, L.words)) return rc;
+    if (h->per_bins > 0)
+        if (int rc = h->phist.ensure(h->n_points, h->n_rows, h->p.dim_d, L.entries + 2)) return rc;
+    const int64_t N = h->n_members;
+    if (N > 0 && !(h->pacc.key[0] == N && h->pacc.key[1] == L.K && h->pacc.key[2] == 0)) {
+        // fresh accumulators: sums and counts 0, the minimum 65535, the maximum 0
+        if (int rc = h->pacc.ensure(N, L.K, 0, N * L.K)) return rc;
+        const std::vector<long long> none((size_t)N, PERIOD_WTD_NONE);
+        HIP_TRY(hipMemcpy(h->pacc.buf.p + 2 * N, none.data(), (size_t)N * 8, hipMemcpyHostToDevice));
+    }
+    return HC_OK;
+}
+int ensure_period_hist(hc_handle *h)
+{
+    if (int rc = ensure_period(h)) return rc;
+    return h->per_bins > 0 ? HC_OK : fail(HC_ERR_ARG, "period totals have no histograms (hc_set_period_totals with n_bins = 0)");
+}
+int ensure_period_acc(hc_handle *h)
+{
+    if (int rc = ensure_period(h)) return rc;
+    return h->n_members > 0 ? HC_OK : fail(HC_ERR_ARG, "period totals: no members yet (hc_set_members / hc_set_state)");
+}
+
 // An assimilation table keyed by (points, rows, stride): `per_row` entries per point and analysis row (every stride-th
 // row), created on a fresh key as NaN with each slot's count 0 (`width` entries a slot; 0: all NaN)
 int ensure_da_table(hc_handle *h, AccTable<double> &t, int64_t stride, int64_t per_row, int width)
@@ -2923,6 +3188,7 @@ int hc_destroy(hc_handle *h)
     h->point_base.release(); h->point_order.release(); h->point_cost.release();
     h->daylight.release(); h->refresh.release(); h->wtd_u16.release(); h->moments.release(); h->counters.release();
     h->prof.release(); h->hist.release(); h->thist.release(); h->stor.release(); h->shist.release();
+    h->pacc.release(); h->pacc_alt.release(); h->pmom.release(); h->phist.release();
     assimilation_off(h);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -3339,6 +3605,48 @@ int launch_layer_storage(hc_handle *h, const StepArgs &A, const ProfLayout &L, c
     return HC_OK;
 }
 
+// the period (index into per_end) that forcing row `row` belongs to, -1: after the last end
+int64_t period_of(const hc_handle *h, int64_t row)
+{
+    const auto it = std::lower_bound(h->per_end.begin(), h->per_end.end(), row);
+    return it == h->per_end.end() ? -1 : (int64_t)(it - h->per_end.begin());
+}
+
+// The launch's rows [row0, row0 + rows) added to the members' accumulators (plan_chunk ended the launch on the period's
+// end row at the latest, so they lie in one period) and, when the launch ends on the end row, the period reduced over
+// the members of each point: slices of PERIOD_MEMBERS_PER_BLOCK members (four a thread) give a 262 144-member point
+// 256 blocks, one a CU
+constexpr long long PERIOD_MEMBERS_PER_BLOCK = 1024;
+int launch_period(hc_handle *h, int64_t row0, int rows)
+{
+    const int64_t p = period_of(h, row0);
+    if (p < 0) return HC_OK;
+    const int64_t end_row = h->per_end[(size_t)p], N = h->n_members;
+    const PeriodLayout L = period_layout(h);
+    long long *t = h->pmom.buf.p;
+    unsigned long long *ovf = reinterpret_cast<unsigned long long *>(t + L.ovf);
+    PeriodThresholds Th{};
+    Th.n = h->per_nthr;
+    for (int j = 0; j < Th.n; j++) Th.node[j] = h->per_thr[j];
+    const int n = (int)std::min<int64_t>(rows, end_row - row0 + 1);
+    hipLaunchKernelGGL(period_accumulate_kernel, dim3((unsigned)((N + PERIOD_THREADS - 1) / PERIOD_THREADS)),
+                       dim3(PERIOD_THREADS), 0, h->stream, h->diag.p, h->wtd_u16.p, h->wtd_obs.p, (long long)N,
+                       (long long)row0, n, Th, h->pacc.buf.p, ovf);
+    HIP_TRY(hipGetLastError());
+    if (row0 + rows - 1 < end_row) return HC_OK;
+    const long long mpp = N / h->n_points;
+    const int B = h->per_bins, D = (int)h->p.dim_d;
+    int *hist = B > 0 ? h->phist.buf.p : nullptr;
+    const dim3 grid((unsigned)((mpp + PERIOD_MEMBERS_PER_BLOCK - 1) / PERIOD_MEMBERS_PER_BLOCK), (unsigned)h->n_points);
+    const size_t lds = B > 0 ? (size_t)2 * (B + D) * sizeof(unsigned) : 0;
+    hipLaunchKernelGGL(period_reduce_kernel, grid, dim3(PERIOD_THREADS), lds, h->stream, h->pacc.buf.p, (long long)N, mpp,
+                       PERIOD_MEMBERS_PER_BLOCK, (long long)p, (long long)h->per_n, L.K, B, D, 20 + h->per_fexp[0],
+                       20 + h->per_fexp[1], t, t + L.pcnt, ovf, hist, B > 0 ? hist + L.wtd : nullptr,
+                       reinterpret_cast<unsigned long long *>(B > 0 ? hist + L.entries : nullptr));
+    HIP_TRY(hipGetLastError());
+    return HC_OK;
+}
+
 constexpr long long HIST_MEMBERS_PER_BLOCK = 4096;
 
 // the histogram rows among launch rows [row0, row0 + chunk) of the water-table indices in wtd_u16
@@ -3462,8 +3770,15 @@ Chunk plan_chunk(const hc_handle *h, const hc_step_args *a, int64_t done, bool p
                 }
         }
     }
+    const int64_t diag_row = N * 2 * 8;
+    if (h->per_n > 0 && !a->spinup) {
+        // period totals (hc_set_period_totals): a launch ends on the period's end row, and diag is staged as for the profiles
+        if (const int64_t p = period_of(h, c.row0); p >= 0)
+            c.rows = (int)std::min<int64_t>(c.rows, h->per_end[(size_t)p] - c.row0 + 1);
+        c.rows = (int)std::min<int64_t>(c.rows, std::max<int64_t>(1, PROF_DIAG_BYTES / diag_row));
+    }
     if (!prof_on) return c;
-    const int64_t s = h->prof_stride, diag_row = N * 2 * 8, row_bytes = N * D * 8;
+    const int64_t s = h->prof_stride, row_bytes = N * D * 8;
     c.rows = (int)std::min<int64_t>(c.rows, std::max<int64_t>(1, PROF_DIAG_BYTES / diag_row));
     const int64_t cap_rows = std::max<int64_t>(1, (PROF_STAGE_BYTES - (int64_t)c.rows * diag_row) / row_bytes);
     if (a->psi_rows_out) {
@@ -3513,14 +3828,15 @@ int stage_noise(hc_handle *h, const hc_step_args *a, const Chunk &c, int64_t con
 }
 
 // the launch's staging buffers and IoArgs, the points' walk order, and the step kernel between the two timing events
-int launch_chunk(hc_handle *h, StepArgs &A, const hc_step_args *a, const Chunk &c, bool prof_on)
+// (diag_on: the profile statistics or the period totals read the launch's diag)
+int launch_chunk(hc_handle *h, StepArgs &A, const hc_step_args *a, const Chunk &c, bool diag_on)
 {
     const int64_t N = h->n_members, D = h->p.dim_d;
     const size_t rows = (size_t)c.rows;
     if (h->wtd_u16.ensure(rows * N)) return HC_ERR_DEVICE;
     if (a->stats_out && h->stats.ensure(rows * N * 6)) return HC_ERR_DEVICE;
     if (a->psi_rows_out && h->psi_rows.ensure(rows * N * D)) return HC_ERR_DEVICE;
-    if ((a->diag_out || prof_on) && h->diag.ensure(rows * N * 2)) return HC_ERR_DEVICE;
+    if ((a->diag_out || diag_on) && h->diag.ensure(rows * N * 2)) return HC_ERR_DEVICE;
     if (c.stage_all && h->psi_rows.ensure(rows * N * D)) return HC_ERR_DEVICE;
     h->io_host.fresh = h->fresh.p;
     h->io_host.row_begin = c.row0;
@@ -3529,7 +3845,7 @@ int launch_chunk(hc_handle *h, StepArgs &A, const hc_step_args *a, const Chunk &
     h->io_host.wtd_u16 = h->wtd_u16.p;
     h->io_host.stats = a->stats_out ? h->stats.p : nullptr;
     h->io_host.psi_rows = (a->psi_rows_out || c.stage_all) ? h->psi_rows.p : nullptr;
-    h->io_host.diag = (a->diag_out || prof_on) ? h->diag.p : nullptr;
+    h->io_host.diag = (a->diag_out || diag_on) ? h->diag.p : nullptr;
     if (int rc = push_io(h)) return rc;
     if (h->n_points > 1) {
         HIP_TRY(hipMemcpyAsync(h->point_order.p, h->order_host.data(), (size_t)h->n_points * 4, hipMemcpyHostToDevice,
@@ -3554,6 +3870,8 @@ int accumulate(hc_handle *h, const StepArgs &A, const hc_step_args *a, const Chu
     }
     if (hist_on)
         if (int rc = launch_hist(h, c.row0, c.rows)) return rc;
+    if (h->per_n > 0 && !a->spinup)
+        if (int rc = launch_period(h, c.row0, c.rows)) return rc;
     if (!prof_on) return HC_OK;
     const ProfLayout PL = prof_layout(h);
     for (int r = 0; r < c.rows; r++) {
@@ -3823,6 +4141,16 @@ int assimilate(hc_handle *h, const Chunk &c)
         hipLaunchKernelGGL(filter_gather_kernel, dim3(blocks), dim3(256), 0, h->stream, h->filt_anc.p, h->psi.p, h->base.p,
                            h->psi_alt.p, h->base_alt.p, (long long)N, (int)D);
         HIP_TRY(hipGetLastError());
+        if (h->per_n > 0) {
+            // the members' period accumulators travel with their states (the period's path estimate)
+            const int K = period_layout(h).K;
+            if (h->pacc_alt.ensure((size_t)(N * K))) return HC_ERR_DEVICE;
+            const unsigned pblocks = (unsigned)std::min<size_t>(((size_t)N * K + 255) / 256, (size_t)h->n_cu * 64);
+            hipLaunchKernelGGL(period_gather_kernel, dim3(pblocks), dim3(256), 0, h->stream, h->filt_anc.p, h->pacc.buf.p,
+                               h->pacc_alt.p, (long long)N, K);
+            HIP_TRY(hipGetLastError());
+            std::swap(h->pacc.buf, h->pacc_alt);
+        }
     }
     if (s.ms > 0) {
         // the sensors' posterior over the resampled slots, theta[anc[k]]: theta is a function of the copied column
@@ -4106,6 +4434,8 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
     if ((prof_on && (rc = ensure_prof(h))) || (hist_on && (rc = ensure_hist(h)))) return rc;
     if (prof_on && h->thist_bins > 0 && (rc = ensure_thist(h))) return rc;
     if (prof_on && h->stor_layers > 0 && (rc = ensure_stor(h))) return rc;
+    const bool per_on = h->per_n > 0 && !a->spinup;       // period totals (hc_set_period_totals)
+    if (per_on && (rc = ensure_period(h))) return rc;
     // the particle filter (hc_set_filter): spin-up solves are never filtered
     if (a->spinup && h->filt_host())
         return fail(HC_ERR_ARG, "spin-up solves with the particle filter on in a Philox run: set the filter after the spin-up");
@@ -4121,7 +4451,7 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
         const Chunk c = plan_chunk(h, a, done, prof_on);
         int n_fresh = 0;
         if ((rc = stage_noise(h, a, c, fresh_consumed, n_fresh))) return rc;
-        if ((rc = launch_chunk(h, A, a, c, prof_on))) return rc;
+        if ((rc = launch_chunk(h, A, a, c, prof_on || per_on))) return rc;
         if ((rc = accumulate(h, A, a, c, prof_on, hist_on))) return rc;
         if ((rc = copy_outputs(h, a, c, done))) return rc;
         if (filt_on && is_assimilation_row(h, c.row0 + c.rows - 1) && (rc = assimilate(h, c))) return rc;
@@ -4523,6 +4853,153 @@ int hc_get_layer_storage_layout(hc_handle *h, int32_t *n_layers, int32_t *n_bins
     return HC_OK;
 }
 
+void period_off(hc_handle *h)
+{
+    h->per_n = h->per_nthr = h->per_bins = 0;
+    h->per_end.clear();
+    h->pacc.release(), h->pacc_alt.release(), h->pmom.release(), h->phist.release();
+}
+
+int hc_set_period_totals(hc_handle *h, int32_t n_periods, const int64_t *end_rows, int32_t n_thresholds,
+                         const int32_t *threshold_nodes, int32_t n_bins, const int32_t *flux_max_log2)
+{
+    if (!h || (n_periods > 0 && !end_rows) || (n_periods > 0 && n_thresholds > 0 && !threshold_nodes))
+        return fail(HC_ERR_ARG, "hc_set_period_totals: bad argument");
+    if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    period_off(h);               // the tables and the accumulators are re-created when on
+    if (n_periods == 0) return HC_OK;
+    if (n_periods < 0 || n_periods > HC_PERIOD_MAX_PERIODS)
+        return fail(HC_ERR_ARG, "hc_set_period_totals: %d periods (1 to %d; 0 = off)", (int)n_periods, HC_PERIOD_MAX_PERIODS);
+    for (int p = 0; p < n_periods; p++) {
+        const int64_t prev = p > 0 ? end_rows[p - 1] : 0;
+        if (end_rows[p] < 1 || end_rows[p] >= h->n_rows || end_rows[p] <= prev)
+            return fail(HC_ERR_ARG, "hc_set_period_totals: end row %lld of period %d (ascending rows in [1, %lld))",
+                        (long long)end_rows[p], p, (long long)h->n_rows);
+        if (end_rows[p] - prev > HC_PERIOD_MAX_ROWS)
+            return fail(HC_ERR_ARG, "hc_set_period_totals: period %d holds %lld rows (at most %d)", p,
+                        (long long)(end_rows[p] - prev), HC_PERIOD_MAX_ROWS);
+    }
+    if (n_thresholds < 0 || n_thresholds > HC_PERIOD_MAX_THRESHOLDS)
+        return fail(HC_ERR_ARG, "hc_set_period_totals: %d thresholds (0 to %d)", (int)n_thresholds, HC_PERIOD_MAX_THRESHOLDS);
+    if (n_bins != 0 && (n_bins < 32 || n_bins > 1024 || (n_bins & (n_bins - 1))))
+        return fail(HC_ERR_ARG, "hc_set_period_totals: %d bins (a power of two in 32 .. 1024; 0 = no histograms)", (int)n_bins);
+    if (n_bins != 0 && !flux_max_log2) return fail(HC_ERR_ARG, "hc_set_period_totals: histograms need flux_max_log2");
+    for (int q = 0; q < 2 && n_bins != 0; q++)
+        if (flux_max_log2[q] < -8 || flux_max_log2[q] > 12)
+            return fail(HC_ERR_ARG, "hc_set_period_totals: flux_max_log2[%d] = %d (-8 .. 12: 2^e cm)", q, (int)flux_max_log2[q]);
+    h->per_end.assign(end_rows, end_rows + n_periods);
+    for (int j = 0; j < n_thresholds; j++) h->per_thr[j] = threshold_nodes[j];
+    for (int q = 0; q < 2; q++) h->per_fexp[q] = n_bins != 0 ? flux_max_log2[q] : 0;
+    h->per_n = n_periods, h->per_nthr = n_thresholds, h->per_bins = n_bins;
+    const int rc = ensure_period(h);         // (its refusals come before anything is allocated)
+    if (rc != HC_OK) period_off(h);          // refused: off
+    return rc;
+}
+
+int hc_get_period_totals_words(hc_handle *h, int64_t *n_words)
+{
+    if (!h || !n_words) return fail(HC_ERR_ARG, "hc_get_period_totals_words: bad argument");
+    if (int rc = ensure_period(h)) return rc;
+    *n_words = h->pmom.n;
+    return HC_OK;
+}
+
+int hc_get_period_totals(hc_handle *h, int64_t *table, int64_t n_words)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_get_period_totals: bad argument");
+    return table_copy(h, h->pmom, ensure_period, hipMemcpyDeviceToHost, table, n_words, "hc_get_period_totals");
+}
+
+int hc_set_period_totals_tables(hc_handle *h, const int64_t *table, int64_t n_words)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_set_period_totals_tables: bad argument");
+    return table_copy(h, h->pmom, ensure_period, hipMemcpyHostToDevice, const_cast<int64_t *>(table), n_words,
+                      "hc_set_period_totals_tables");
+}
+
+int hc_export_period_totals(hc_handle *h, void *device_dst, int64_t n_words)
+{
+    if (!h || !device_dst) return fail(HC_ERR_ARG, "hc_export_period_totals: bad argument");
+    return table_copy(h, h->pmom, ensure_period, hipMemcpyDeviceToDevice, device_dst, n_words, "hc_export_period_totals");
+}
+
+int hc_get_period_totals_hist(hc_handle *h, int32_t *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_get_period_totals_hist: bad argument");
+    return table_copy(h, h->phist, ensure_period_hist, hipMemcpyDeviceToHost, table, n_entries, "hc_get_period_totals_hist");
+}
+
+int hc_set_period_totals_hist_table(hc_handle *h, const int32_t *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_set_period_totals_hist_table: bad argument");
+    return table_copy(h, h->phist, ensure_period_hist, hipMemcpyHostToDevice, const_cast<int32_t *>(table), n_entries,
+                      "hc_set_period_totals_hist_table");
+}
+
+int hc_export_period_totals_hist(hc_handle *h, void *device_dst, int64_t n_entries)
+{
+    if (!h || !device_dst) return fail(HC_ERR_ARG, "hc_export_period_totals_hist: bad argument");
+    return table_copy(h, h->phist, ensure_period_hist, hipMemcpyDeviceToDevice, device_dst, n_entries,
+                      "hc_export_period_totals_hist");
+}
+
+int hc_get_period_totals_acc(hc_handle *h, int64_t *acc, int64_t n_words)
+{
+    if (!h || !acc) return fail(HC_ERR_ARG, "hc_get_period_totals_acc: bad argument");
+    return table_copy(h, h->pacc, ensure_period_acc, hipMemcpyDeviceToHost, acc, n_words, "hc_get_period_totals_acc");
+}
+
+int hc_set_period_totals_acc(hc_handle *h, const int64_t *acc, int64_t n_words)
+{
+    if (!h || !acc) return fail(HC_ERR_ARG, "hc_set_period_totals_acc: bad argument");
+    return table_copy(h, h->pacc, ensure_period_acc, hipMemcpyHostToDevice, const_cast<int64_t *>(acc), n_words,
+                      "hc_set_period_totals_acc");
+}
+
+int hc_reset_period_totals(hc_handle *h)
+{
+    if (!h) return fail(HC_ERR_ARG, "hc_reset_period_totals: bad argument");
+    h->phist.invalidate(), h->pacc.invalidate();
+    return table_reset(h, h->pmom, ensure_period);
+}
+
+int hc_get_period_totals_outside(hc_handle *h, uint64_t *count)
+{
+    if (!h || !count) return fail(HC_ERR_ARG, "hc_get_period_totals_outside: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = ensure_period(h)) return rc;
+    *count = 0;
+    if (h->per_bins == 0) return HC_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(count, h->phist.buf.p + (h->phist.n - 2), 8, hipMemcpyDeviceToHost));
+    return HC_OK;
+}
+
+int hc_get_period_totals_overflow(hc_handle *h, uint64_t *count)
+{
+    if (!h || !count) return fail(HC_ERR_ARG, "hc_get_period_totals_overflow: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = ensure_period(h)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(count, h->pmom.buf.p + period_layout(h).ovf, 8, hipMemcpyDeviceToHost));
+    return HC_OK;
+}
+
+int hc_get_period_totals_layout(hc_handle *h, int32_t *n_periods, int32_t *n_thresholds, int32_t *n_bins,
+                                int32_t *threshold_nodes, int32_t *flux_max_log2, int64_t *end_rows, int64_t n_end_rows)
+{
+    if (!h || !n_periods || !n_thresholds || !n_bins || !threshold_nodes || !flux_max_log2)
+        return fail(HC_ERR_ARG, "hc_get_period_totals_layout: bad argument");
+    *n_periods = h->per_n, *n_thresholds = h->per_nthr, *n_bins = h->per_bins;
+    for (int j = 0; j < HC_PERIOD_MAX_THRESHOLDS; j++) threshold_nodes[j] = j < h->per_nthr ? h->per_thr[j] : 0;
+    for (int q = 0; q < 2; q++) flux_max_log2[q] = h->per_fexp[q];
+    if (end_rows)
+        for (int64_t p = 0; p < std::min<int64_t>(n_end_rows, h->per_n); p++) end_rows[p] = h->per_end[(size_t)p];
+    return HC_OK;
+}
+
 int hc_wtd_distribution(int device, const int32_t *hist, const int32_t *obs_idx, int64_t n_rows, int32_t D,
                         const double *levels, int32_t n_levels, double dz, int64_t *count, int32_t *quantile_idx,
                         double *crps_cm)
@@ -4813,6 +5290,9 @@ int hc_set_filter_shard(hc_handle *h, int32_t n_shards, const int64_t *bounds, i
     if (h->fsm_n > 0)
         return fail(HC_ERR_ARG, "hc_set_filter_shard: a soil-moisture record is set (hc_set_filter_soil_moisture), and the "
                                 "sharded filter gathers water-table indices only");
+    if (h->per_n > 0)
+        return fail(HC_ERR_ARG, "hc_set_filter_shard: period totals are set (hc_set_period_totals), and the routed columns do "
+                                "not carry the members' accumulators");
     if (!device_buf || !gather || !route) return fail(HC_ERR_ARG, "hc_set_filter_shard: NULL buffer or callback");
     const int64_t need = filter_shard_layout(np, h->n_members, n_shards, h->p.dim_d).words;
     if (n_words < need)

@@ -11,7 +11,8 @@ import numpy as np
 from .digest import inverse_retention
 from .stepper import (ENKF_METHODS, ENKF_WIDTH, SM_WIDTH, WINDOW_WIDTH, EnsembleStepper, enkf_sm_summary, enkf_summary,
                       enkf_window_settings, enkf_window_summary, filter_sm_summary, filter_summary,
-                      layer_ranges, layer_storage_distribution, moments_to_mean_std, theta_distribution, wtd_distribution)
+                      flux_max_log2_of, layer_ranges, layer_storage_distribution, moments_to_mean_std, period_totals_distribution,
+                      sensor_nodes, theta_distribution, wtd_distribution)
 
 
 def pressure_head(cols, theta):
@@ -101,6 +102,12 @@ class _Run:
     storage_layers_cm (needs profile_stride): depth layers [(top, bottom), ...] in cm (stepper.layer_ranges) whose water
     storage dz sum theta is reduced per member on the device on the profile rows: :meth:`storage_stats` (mean and sigma in
     cm) and, with ``storage_bins`` (a power of two in 32 .. 1024), :meth:`storage_distribution` (quantile bands in cm).
+    period_ends: the inclusive end rows of periods (stepper.period_ends) over which every member's transpiration and
+    lateral flow are summed, its shallowest and deepest water table kept and the rows counted on which the water table
+    stood at or above each of ``period_thresholds_cm`` (at most 4 depths, mapped to nodes like a sensor's), reduced over
+    the members on the device at every end row: :meth:`period_stats` and, with ``period_bins`` (a power of two in
+    32 .. 1024) and ``period_flux_max_cm`` = the histograms' upper ends (transpiration, lateral flow), each a power of two
+    in 2^-8 .. 2^12 cm, :meth:`period_distribution`.  Needs no profile statistics.
     wtd_hist_stride > 0: per-row histograms of the members' water-table index every ``wtd_hist_stride``-th row, counted on
     the device: :meth:`wtd_distribution` (quantiles, CRPS against the well).
     filter_stride > 0: a bootstrap particle filter on the well's water table every ``filter_stride``-th row with an
@@ -215,6 +222,48 @@ class _Run:
         t = self.theta_hist_table() if table is None else table
         return theta_distribution(t, levels, self.theta_hist_bins, self.profile_stride)
 
+    def _start_periods(self, period_ends, period_thresholds_cm, period_bins, period_flux_max_cm):
+        self.period_ends = None if period_ends is None or len(period_ends) == 0 else \
+            np.asarray(period_ends, dtype=np.int64).reshape(-1)
+        on = self.period_ends is not None
+        if not on and (len(period_thresholds_cm or ()) or period_bins):
+            raise ValueError("period_thresholds_cm / period_bins need period_ends")
+        self.period_thresholds_cm = np.asarray(period_thresholds_cm if on and period_thresholds_cm is not None else [],
+                                               dtype=np.float64).reshape(-1)
+        self.period_bins = int(period_bins or 0) if on else 0
+        self.period_flux_max_cm = tuple(float(v) for v in period_flux_max_cm) if self.period_bins else None
+        if self.period_bins and len(self.period_flux_max_cm) != 2:
+            raise ValueError("period_flux_max_cm is (transpiration, lateral flow)")
+        self.period_threshold_nodes = sensor_nodes(self.cols.z, self.period_thresholds_cm) if on else None
+        if on:
+            fexp = [flux_max_log2_of(v) for v in self.period_flux_max_cm] if self.period_bins else (0, 0)
+            self.stepper.set_period_totals(self.period_ends, self.period_threshold_nodes, self.period_bins, fexp)
+
+    def period_table(self):
+        """The raw int64 moments table of the period totals (stepper.period_totals_table_layout)."""
+        return self.stepper.period_totals_table()
+
+    def period_hists(self):
+        """(phist_flux [n_period][2][B], phist_wtd [n_period][2][D]) int32; a sweep: a leading [P] axis."""
+        hf, hw = self.stepper.period_totals_hists()
+        return hf.reshape(self._lead + hf.shape[1:]), hw.reshape(self._lead + hw.shape[1:])
+
+    def period_stats(self, table=None):
+        """Mean and sigma over the members of every period's transpiration and lateral-flow totals [cm], shallowest and
+        deepest water table [cm depth] and rows at or above each threshold, [n_period] (a sweep: [P][n_period]), with
+        end_rows, solved_rows and count (stepper.period_totals_stats); ``table``: e.g. the sum over ranks."""
+        out = self.stepper.period_totals_stats(table)
+        out["thresholds_cm"], out["threshold_nodes"] = self.period_thresholds_cm.copy(), self.period_threshold_nodes.copy()
+        return out
+
+    def period_distribution(self, levels=(0.05, 0.25, 0.5, 0.75, 0.95), tables=None):
+        """Quantiles over the members of every period's flux totals [cm] and water-table extremes [cm depth]
+        (stepper.period_totals_distribution); ``tables`` = (phist_flux, phist_wtd): e.g. the sums over ranks.  Other
+        levels need no rerun."""
+        hf, hw = self.period_hists() if tables is None else tables
+        return period_totals_distribution(hf, hw, levels, self.stepper.period_flux_max_log2, float(self.cols.z[0]),
+                                          self.cols.dz)
+
     def storage_table(self):
         """The raw int64 moments table of the layer storage (stepper.layer_storage_table_layout)."""
         return self.stepper.layer_storage_table()
@@ -323,7 +372,8 @@ class EnsembleSimulation(_Run):
     #1 base vector, then one vector per refresh row (simulation.py:426,561,601) -- and uploaded per launch.
     spinup="shared" (default): one spin-up (global member 0's first draw) broadcast to all members;
     spinup="member": every member spins up with its own first draw (`spinup_members_on_gpu`).
-    profile_stride, theta_hist_bins, storage_layers_cm / storage_bins, wtd_hist_stride, filter_stride / filter_sigma_cm / filter_seed, enkf_stride / enkf_sigma_cm /
+    profile_stride, theta_hist_bins, storage_layers_cm / storage_bins, period_ends / period_thresholds_cm / period_bins /
+    period_flux_max_cm, wtd_hist_stride, filter_stride / filter_sigma_cm / filter_seed, enkf_stride / enkf_sigma_cm /
     enkf_localisation_cm / enkf_seed: the optional tables, the particle filter and the EnKF (:class:`_Run`).
     enkf_shard=(n_global, exchange): these members are [member_offset, member_offset + N) of an ensemble of ``n_global``
     whose other members run elsewhere, and the EnKF analyses the whole of it (include/hydrocol.h hc_set_enkf_shard;
@@ -340,7 +390,11 @@ class EnsembleSimulation(_Run):
                  filter_sigma_cm=None, filter_seed=None, enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0,
                  enkf_seed=None, enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0,
                  enkf_window_offsets=(), enkf_shard=None, filter_shard=None, filter_soil_moisture=None,
-                 theta_hist_bins=0, storage_layers_cm=None, storage_bins=0):
+                 theta_hist_bins=0, storage_layers_cm=None, storage_bins=0, period_ends=None, period_thresholds_cm=(),
+                 period_bins=0, period_flux_max_cm=(16.0, 4.0)):
+        if filter_shard is not None and period_ends is not None and len(period_ends):
+            raise ValueError("period_ends and filter_shard exclude each other: the sharded filter routes the members' "
+                             "columns, which do not carry the period accumulators")
         if filter_shard is not None and not int(filter_stride or 0):
             raise ValueError("filter_shard needs the particle filter (filter_stride > 0)")
         if filter_shard is not None and filter_soil_moisture is not None:
@@ -354,6 +408,7 @@ class EnsembleSimulation(_Run):
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
                            enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins, storage_layers_cm,
                            storage_bins)
+        self._start_periods(period_ends, period_thresholds_cm, period_bins, period_flux_max_cm)
         self.enkf_shard = None
         if enkf_shard is not None:
             if not self.enkf_stride:
@@ -470,6 +525,17 @@ class EnsembleSimulation(_Run):
             if self.storage_bins:
                 arrays["storage_hist"] = self.stepper.layer_storage_hist_table()
                 arrays["storage_hist_outside"] = np.array(self.stepper.layer_storage_outside(), dtype=np.uint64)
+        if self.period_ends is not None:
+            # the members' accumulators travel too: a restore in the middle of a period continues it
+            arrays["period_ends"] = self.period_ends
+            arrays["period_thresholds_cm"] = self.period_thresholds_cm
+            arrays["period_bins"] = np.array(self.period_bins, dtype=np.int64)
+            arrays["period_table"] = self.stepper.period_totals_table()
+            arrays["period_acc"] = self.stepper.period_totals_acc()
+            if self.period_bins:
+                arrays["period_flux_max_cm"] = np.asarray(self.period_flux_max_cm, dtype=np.float64)
+                arrays["period_hist"] = self.stepper.period_totals_hist_raw()[:-2]
+                arrays["period_hist_outside"] = np.array(self.stepper.period_totals_outside(), dtype=np.uint64)
         if self.wtd_hist_stride:
             arrays["wtd_hist_stride"] = np.array(self.wtd_hist_stride, dtype=np.int64)
             arrays["wtd_hist"] = self.stepper.wtd_hist_table()
@@ -535,6 +601,13 @@ class EnsembleSimulation(_Run):
         filt = int(data["filter_stride"]) if "filter_stride" in data else 0
         fkw = dict(filter_stride=filt, filter_sigma_cm=float(data["filter_sigma_cm"]),
                    filter_seed=int(data["filter_seed"])) if filt else {}
+        periods = "period_ends" in data
+        if periods:
+            fkw.update(period_ends=np.asarray(data["period_ends"], dtype=np.int64).reshape(-1),
+                       period_thresholds_cm=np.asarray(data["period_thresholds_cm"], dtype=np.float64).reshape(-1),
+                       period_bins=int(data["period_bins"]))
+            if int(data["period_bins"]):
+                fkw.update(period_flux_max_cm=tuple(np.asarray(data["period_flux_max_cm"], dtype=np.float64).reshape(-1)))
         enkf = int(data["enkf_stride"]) if "enkf_stride" in data else 0
         if enkf:
             fkw.update(enkf_stride=enkf, enkf_sigma_cm=float(data["enkf_sigma_cm"]),
@@ -588,6 +661,12 @@ class EnsembleSimulation(_Run):
             sim.stepper.set_layer_storage_table(np.asarray(data["storage_table"], dtype=np.int64))
             if sim.storage_bins:
                 sim.stepper.set_layer_storage_hist_table(np.asarray(data["storage_hist"]), int(data["storage_hist_outside"]))
+        if periods:
+            sim.stepper.set_period_totals_table(np.asarray(data["period_table"], dtype=np.int64))
+            sim.stepper.set_period_totals_acc(np.asarray(data["period_acc"], dtype=np.int64))
+            if sim.period_bins:
+                hf, hw = np.split(np.asarray(data["period_hist"]).reshape(-1), [len(sim.period_ends) * 2 * sim.period_bins])
+                sim.stepper.set_period_totals_hists(hf, hw, int(data["period_hist_outside"]))
         if hist_stride:
             sim.stepper.set_wtd_hist_table(np.asarray(data["wtd_hist"]))
         sim.next_row = int(data["next_row"])
@@ -684,7 +763,8 @@ class SweepSimulation(_Run):
                  point_ids=None, profile_stride=0, wtd_hist_stride=0, filter_stride=0, filter_sigma_cm=None,
                  filter_seed=None, enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None,
                  enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=(),
-                 filter_soil_moisture=None, theta_hist_bins=0, storage_layers_cm=None, storage_bins=0):
+                 filter_soil_moisture=None, theta_hist_bins=0, storage_layers_cm=None, storage_bins=0, period_ends=None,
+                 period_thresholds_cm=(), period_bins=0, period_flux_max_cm=(16.0, 4.0)):
         self.points = list(cols_list)
         self.P, self.n = len(self.points), int(n_members)
         self._lead = (self.P,)
@@ -715,6 +795,7 @@ class SweepSimulation(_Run):
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
                            enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins, storage_layers_cm,
                            storage_bins)
+        self._start_periods(period_ends, period_thresholds_cm, period_bins, period_flux_max_cm)
         self.next_row, self.kernel_ms, self.launches = 1, 0.0, 0
 
     def _spinup(self, flags):

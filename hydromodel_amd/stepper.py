@@ -78,6 +78,8 @@ class EnsembleStepper:
         self.wtd_hist_stride = 0
         self.theta_hist_bins = 0
         self.storage_ranges, self.storage_bins = np.zeros((0, 2), dtype=np.int32), 0
+        self.period_ends, self.period_threshold_nodes = np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int32)
+        self.period_bins, self.period_flux_max_log2 = 0, (0, 0)
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = 0, 0.0, 0
         self.filter_sm_nodes = None
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
@@ -448,6 +450,120 @@ class EnsembleStepper:
         """Mean / sigma [cm] of ``layer_storage_table()`` (or of ``table``, e.g. summed over ranks): :func:`layer_storage_stats`."""
         t = self.layer_storage_table() if table is None else table
         return layer_storage_stats(t, self.P, self.T, len(self.storage_ranges), self.profile_stride)
+
+    # -- period totals per member (include/hydrocol.h hc_set_period_totals) ---------------------------------------------
+    def set_period_totals(self, ends, threshold_nodes=(), bins=0, flux_max_log2=(0, 0)):
+        """Accumulate per member, over the periods that end on the forcing rows ``ends`` (ascending, inclusive; see
+        :func:`period_ends`), the transpiration and lateral-flow totals, the shallowest and deepest water-table index
+        and the rows with the water table at or above each of ``threshold_nodes`` (at most 4); reduce them over the
+        members of each point at every end row: exact moments and, with ``bins`` (a power of two in 32 .. 1024),
+        histograms of the flux totals over [0, 2^e) cm, e = ``flux_max_log2`` (transpiration, lateral flow), and of both
+        extremes.  No ends = off."""
+        e = np.ascontiguousarray(np.asarray(ends, dtype=np.int64).reshape(-1))
+        t = np.asarray(threshold_nodes, dtype=np.int64).reshape(-1)
+        f = np.asarray(flux_max_log2, dtype=np.int64).reshape(-1)
+        if f.size != 2:
+            raise ValueError("flux_max_log2 is (transpiration, lateral flow)")
+        if (t.size and np.abs(t).max() > INT32_MAX) or np.abs(f).max() > INT32_MAX or e.size > INT32_MAX:
+            raise ValueError("threshold nodes are node indices, flux_max_log2 exponents in -8 .. 12")
+        t32, f32 = np.ascontiguousarray(t, dtype=np.int32), np.ascontiguousarray(f, dtype=np.int32)
+        self.period_ends, self.period_threshold_nodes = np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int32)
+        self.period_bins, self.period_flux_max_log2 = 0, (0, 0)
+        L.check(self.lib.hc_set_period_totals(self.h, e.size, L.lptr(e), t32.size, L.iptr(t32), int(bins), L.iptr(f32)))
+        if e.size:
+            self.period_ends, self.period_threshold_nodes = e, t32
+            self.period_bins, self.period_flux_max_log2 = int(bins), ((int(f[0]), int(f[1])) if bins else (0, 0))
+
+    def period_totals_layout(self):
+        """(ends, threshold_nodes, bins, flux_max_log2) as the library holds them."""
+        n, k, b = C.c_int32(), C.c_int32(), C.c_int32()
+        thr, fx = np.zeros(PERIOD_MAX_THRESHOLDS, dtype=np.int32), np.zeros(2, dtype=np.int32)
+        L.check(self.lib.hc_get_period_totals_layout(self.h, C.byref(n), C.byref(k), C.byref(b), L.iptr(thr), L.iptr(fx), None, 0))
+        ends = np.zeros(n.value, dtype=np.int64)
+        L.check(self.lib.hc_get_period_totals_layout(self.h, C.byref(n), C.byref(k), C.byref(b), L.iptr(thr), L.iptr(fx),
+                                                     L.lptr(ends), ends.size))
+        return ends, thr[:k.value].copy(), int(b.value), (int(fx[0]), int(fx[1]))
+
+    @property
+    def period_k(self):
+        return 4 + len(self.period_threshold_nodes)
+
+    def period_totals_words(self):
+        n = C.c_int64()
+        L.check(self.lib.hc_get_period_totals_words(self.h, C.byref(n)))
+        return int(n.value)
+
+    def period_totals_table(self):
+        """The raw int64 moments table (layout: :func:`period_totals_table_layout`)."""
+        t = np.zeros(self.period_totals_words(), dtype=np.int64)
+        L.check(self.lib.hc_get_period_totals(self.h, L.lptr(t), t.size))
+        return t
+
+    def set_period_totals_table(self, table):
+        t = np.ascontiguousarray(table, dtype=np.int64).reshape(-1)
+        L.check(self.lib.hc_set_period_totals_tables(self.h, L.lptr(t), t.size))
+
+    def export_period_totals(self, device_ptr):
+        """Copy the moments table device-to-device to ``device_ptr`` (``period_totals_words()`` int64 on this device)."""
+        L.check(self.lib.hc_export_period_totals(self.h, C.c_void_p(int(device_ptr)), self.period_totals_words()))
+
+    def period_totals_hist_entries(self):
+        return self.P * len(self.period_ends) * 2 * (self.period_bins + self.D) + 2
+
+    def period_totals_hist_raw(self):
+        """The raw int32 histogram table: phist_flux, phist_wtd, then the outside count in two entries."""
+        t = np.zeros(self.period_totals_hist_entries(), dtype=np.int32)
+        L.check(self.lib.hc_get_period_totals_hist(self.h, L.iptr(t), t.size))
+        return t
+
+    def period_totals_hists(self):
+        """(phist_flux [P][n_period][2][B], phist_wtd [P][n_period][2][D]) int32: members of each point per bin."""
+        return split_period_hist(self.period_totals_hist_raw()[:-2], self.P, len(self.period_ends), self.period_bins, self.D)
+
+    def set_period_totals_hists(self, hist_flux, hist_wtd, outside=0):
+        """Install both histograms (a checkpoint's, a sum over handles) and the outside count that goes with them."""
+        t = np.concatenate([np.asarray(hist_flux).reshape(-1), np.asarray(hist_wtd).reshape(-1)])
+        if t.size and (t.min() < 0 or t.max() > INT32_MAX):
+            raise ValueError("histogram counts must lie in [0, 2^31 - 1]")
+        if not 0 <= int(outside) < 1 << 64:
+            raise ValueError("the outside count must lie in [0, 2^64)")
+        tail = np.array([int(outside)], dtype=np.uint64).view(np.int32)
+        t = np.concatenate([np.ascontiguousarray(t, dtype=np.int32), tail])
+        L.check(self.lib.hc_set_period_totals_hist_table(self.h, L.iptr(t), t.size))
+
+    def export_period_totals_hist(self, device_ptr):
+        L.check(self.lib.hc_export_period_totals_hist(self.h, C.c_void_p(int(device_ptr)), self.period_totals_hist_entries()))
+
+    def period_totals_acc(self):
+        """The members' accumulators [K][N] int64 as they stand (the running period's; reset values after an end row)."""
+        a = np.zeros((self.period_k, self.N), dtype=np.int64)
+        L.check(self.lib.hc_get_period_totals_acc(self.h, L.lptr(a), a.size))
+        return a
+
+    def set_period_totals_acc(self, acc):
+        a = np.ascontiguousarray(acc, dtype=np.int64).reshape(-1)
+        L.check(self.lib.hc_set_period_totals_acc(self.h, L.lptr(a), a.size))
+
+    def reset_period_totals(self):
+        L.check(self.lib.hc_reset_period_totals(self.h))
+
+    def period_totals_outside(self):
+        """Members' values that fell in no bin of their histogram since the tables were made."""
+        out = C.c_uint64()
+        L.check(self.lib.hc_get_period_totals_outside(self.h, C.byref(out)))
+        return int(out.value)
+
+    def period_totals_overflow(self):
+        out = C.c_uint64()
+        L.check(self.lib.hc_get_period_totals_overflow(self.h, C.byref(out)))
+        return int(out.value)
+
+    def period_totals_stats(self, table=None):
+        """The science arrays of ``period_totals_table()`` (or of ``table``, e.g. summed over ranks):
+        :func:`period_totals_stats`."""
+        t = self.period_totals_table() if table is None else table
+        return period_totals_stats(t, self.P, self.period_ends, len(self.period_threshold_nodes), float(self.cols.z[0]),
+                                   float(self.params.dz), self.forcing.wtd_obs)
 
     # -- particle filter on the well's water table (include/hydrocol.h hc_set_filter) ----------------------------------
     def set_filter(self, stride, sigma_cm=None, seed=0):
@@ -1325,6 +1441,240 @@ def layer_storage_distribution(hist, ranges, dz, levels, stride=1):
     q = np.where(n[..., None, :] > 0, (np.minimum(idx, B - 1) + 0.5) / B * thick, np.nan)
     return {"rows": np.arange(hist.shape[-3], dtype=np.int64) * int(stride), "count": n, "quantiles_cm": q, "levels": lv,
             "thickness_cm": thick}
+
+
+# ---- period totals per member (include/hydrocol.h hc_set_period_totals) ------------------------------------------------
+PERIOD_MAX_PERIODS = 4096
+PERIOD_MAX_ROWS = 1 << 20
+PERIOD_MAX_THRESHOLDS = 4
+PERIOD_WTD_NONE = 65535
+PERIOD_FLUX_SHIFT = 12                   # flux totals enter the moments as A >> 12: units of 2^-20 cm
+PERIOD_SCALE_TOTAL = PROF_SCALE_FLUX - PERIOD_FLUX_SHIFT
+
+
+def flux_max_log2_of(max_cm):
+    """e of a flux histogram's upper end ``max_cm`` = 2^e cm, e an integer in -8 .. 12; anything else is a ValueError."""
+    v = float(max_cm)
+    m, e = np.frexp(v) if np.isfinite(v) and v > 0 else (0.0, 0)
+    if m != 0.5 or not -8 <= int(e) - 1 <= 12:
+        raise ValueError(f"a flux histogram's upper end is a power of two in 2^-8 .. 2^12 cm, got {max_cm!r}")
+    return int(e) - 1
+
+
+def period_ends(T, rows=None, datenum=None, calendar=None):
+    """The inclusive end rows of the periods of a record of ``T`` forcing rows (row 0 is the initial state; period 0
+    starts at row 1).  ``rows=n``: every n-th row, n, 2 n, ... below T (rows after the last end belong to no period).
+    ``datenum=`` the record's Datenum [T] (days, 719529 = 1970-01-01) with ``calendar="month"`` or ``"year"``: the last
+    row of every calendar month or year -- row r >= 1 whose successor lies in another one; the record's last row counts
+    when one more time step would leave its month or year."""
+    T = int(T)
+    if (rows is None) == (calendar is None):
+        raise ValueError("exactly one of rows= and calendar=")
+    if rows is not None:
+        rows = int(rows)
+        if not 1 <= rows <= PERIOD_MAX_ROWS:
+            raise ValueError(f"a period holds 1 to {PERIOD_MAX_ROWS} rows, got {rows}")
+        return np.arange(rows, T, rows, dtype=np.int64)
+    if calendar not in ("month", "year"):
+        raise ValueError(f"calendar is \"month\" or \"year\", got {calendar!r}")
+    dn = np.asarray(datenum, dtype=np.float64).reshape(-1)
+    if dn.size != T or T < 2 or not np.all(np.isfinite(dn)) or np.any(np.diff(dn) <= 0):
+        raise ValueError(f"calendar periods need the record's {T} ascending Datenum values")
+    dn = np.append(dn, dn[-1] + (dn[-1] - dn[-2]))
+    days = np.floor(dn + 1e-6).astype(np.int64) - 719529
+    key = days.astype("datetime64[D]").astype("datetime64[M]" if calendar == "month" else "datetime64[Y]").astype(np.int64)
+    r = np.flatnonzero(key[:-1] != key[1:])
+    return r[r >= 1].astype(np.int64)
+
+
+def _check_period_ends(ends, T=None):
+    e = np.asarray(ends, dtype=np.int64).reshape(-1)
+    if not 1 <= e.size <= PERIOD_MAX_PERIODS:
+        raise ValueError(f"1 to {PERIOD_MAX_PERIODS} periods, got {e.size}")
+    if e[0] < 1 or np.any(np.diff(e) <= 0) or (T is not None and e[-1] >= T):
+        raise ValueError("period end rows ascend strictly within [1, n_rows)")
+    if np.any(np.diff(np.concatenate([[0], e])) > PERIOD_MAX_ROWS):
+        raise ValueError(f"a period holds at most {PERIOD_MAX_ROWS} rows")
+    return e
+
+
+def period_solved_rows(wtd_obs, ends):
+    """Rows of every period that are solved (wtd_obs >= 0): [n_period] int64."""
+    e = _check_period_ends(ends)
+    solved = np.concatenate([[0], np.cumsum(np.asarray(wtd_obs)[1:e[-1] + 1] >= 0)]).astype(np.int64)     # solved rows in [1, r]
+    return np.diff(np.concatenate([[0], solved[e]]))
+
+
+def period_totals_table_layout(P, n_period, K):
+    """{part: (offset, shape)} of the int64 table: pmom [P][n_period][K][5], pcnt [P][n_period], ovf [1]."""
+    out, off = {}, 0
+    for name, shape in (("pmom", (P, n_period, K, PROF_WORDS)), ("pcnt", (P, n_period)), ("ovf", (1,))):
+        out[name] = (off, shape)
+        off += int(np.prod(shape))
+    out["words"] = (off, ())
+    return out
+
+
+def split_period_totals_table(table, P, n_period, K):
+    """Views of the parts of a flat moments table (see :func:`period_totals_table_layout`)."""
+    t = np.asarray(table, dtype=np.int64).reshape(-1)
+    lay = period_totals_table_layout(P, n_period, K)
+    if t.size != lay["words"][0]:
+        raise ValueError(f"period-totals table of {t.size} words, the layout has {lay['words'][0]}")
+    return {k: t[o:o + int(np.prod(sh))].reshape(sh) for k, (o, sh) in lay.items() if k != "words"}
+
+
+def split_period_hist(entries, P, n_period, B, D):
+    """(phist_flux [P][n_period][2][B], phist_wtd [P][n_period][2][D]) of the histogram table without its two last entries."""
+    t = np.asarray(entries).reshape(-1)
+    nf = P * n_period * 2 * B
+    if t.size != nf + P * n_period * 2 * D:
+        raise ValueError(f"period histograms of {t.size} entries, the layout has {nf + P * n_period * 2 * D}")
+    return t[:nf].reshape(P, n_period, 2, B), t[nf:].reshape(P, n_period, 2, D)
+
+
+def period_totals_of(diag_rows, wtd_rows, wtd_obs, ends, threshold_nodes=(), bins=0, flux_max_log2=(0, 0), ancestors=None,
+                     D=None, row_begin=1, acc=None):
+    """The device's period totals of one point restated in NumPy integers.  ``diag_rows`` [R][N][2] and ``wtd_rows``
+    [R][N] are what the launches stored for forcing rows row_begin ... row_begin + R - 1, ``wtd_obs`` [T] the forcing's.
+    ``ancestors`` {row: anc [N]}: the particle filter's resampling after that row (after the row's reduction).  ``acc``
+    [K][N]: the accumulators to start from (default: reset).  Returns ``acc`` [K][N] as they stand after the last row,
+    ``acc_at_end`` [n_period][K][N] (each period's before its reset; reset values where the end was not reached),
+    ``table`` (flat int64: pmom [1][n_period][K][5], pcnt, ovf), ``hist_flux`` [n_period][2][bins] and ``hist_wtd``
+    [n_period][2][D] int32 (None without bins), ``outside``, ``overflow``.  The device's tables, bit for bit."""
+    diag = np.asarray(diag_rows, dtype=np.float64)
+    wtd = np.asarray(wtd_rows, dtype=np.int64)
+    R, N = wtd.shape
+    e = _check_period_ends(ends)
+    thr = np.asarray(threshold_nodes, dtype=np.int64).reshape(-1)
+    if thr.size > PERIOD_MAX_THRESHOLDS:
+        raise ValueError(f"at most {PERIOD_MAX_THRESHOLDS} thresholds")
+    bins = int(bins)
+    if bins and (bins not in STORAGE_BINS or D is None):
+        raise ValueError("period histograms have a power of two in 32 .. 1024 bins and need the depth D")
+    K, n_period = 4 + thr.size, e.size
+
+    def fresh():
+        a = np.zeros((K, N), dtype=np.int64)
+        a[2] = PERIOD_WTD_NONE
+        return a
+
+    acc = fresh() if acc is None else np.array(acc, dtype=np.int64).reshape(K, N)
+    acc_at_end = np.stack([fresh() for _ in range(n_period)])
+    pmom = np.zeros((1, n_period, K, PROF_WORDS), dtype=np.int64)
+    pcnt = np.zeros((1, n_period), dtype=np.int64)
+    hist_flux = np.zeros((n_period, 2, bins), dtype=np.int64) if bins else None
+    hist_wtd = np.zeros((n_period, 2, int(D)), dtype=np.int64) if bins else None
+    ovf = outside = 0
+    for r in range(R):
+        row = int(row_begin) + r
+        p = int(np.searchsorted(e, row, side="left"))
+        if p >= n_period:
+            break
+        if wtd_obs[row] >= 0:
+            q, bad = profile_quantise(diag[r], PROF_SCALE_FLUX)
+            ovf += bad
+            acc[0] += q[:, 0]
+            acc[1] += q[:, 1]
+            acc[2] = np.minimum(acc[2], wtd[r])
+            acc[3] = np.maximum(acc[3], wtd[r])
+            for j, t in enumerate(thr):
+                acc[4 + j] += wtd[r] <= t
+        if row == e[p]:
+            acc_at_end[p] = acc
+            inn = acc[2] != PERIOD_WTD_NONE
+            v = acc[:, inn].copy()
+            v[:2] >>= PERIOD_FLUX_SHIFT                        # floor(A / 4096): an arithmetic shift
+            ovf += int((np.abs(v[:2]) > PROF_Q_MAX).sum())
+            v[:2] = np.clip(v[:2], -PROF_Q_MAX, PROF_Q_MAX)
+            pmom[0, p] = profile_words_of(v).astype(object).sum(axis=1).astype(np.int64) if v.shape[1] else 0
+            pcnt[0, p] = v.shape[1]
+            if bins:
+                for q in range(2):
+                    sh = 20 + int(flux_max_log2[q])
+                    ok = (v[q] >= 0) & (v[q] < (1 << sh))
+                    np.add.at(hist_flux[p, q], (v[q][ok] * bins) >> sh, 1)
+                    okw = (v[2 + q] >= 0) & (v[2 + q] < int(D))
+                    np.add.at(hist_wtd[p, q], v[2 + q][okw], 1)
+                    outside += int((~ok).sum()) + int((~okw).sum())
+            acc = fresh()
+        if ancestors is not None and row in ancestors:
+            acc = acc[:, np.asarray(ancestors[row], dtype=np.int64)]
+    table = np.concatenate([pmom.reshape(-1), pcnt.reshape(-1), np.array([ovf], dtype=np.int64)])
+    return {"acc": acc, "acc_at_end": acc_at_end, "table": table, "overflow": ovf, "outside": outside,
+            "hist_flux": hist_flux.astype(np.int32) if bins else None, "hist_wtd": hist_wtd.astype(np.int32) if bins else None}
+
+
+def period_totals_stats(table, P, ends, n_thresholds, z0, dz, wtd_obs=None):
+    """The science arrays of a period-totals moments table, formed as :func:`limbs_to_mean_std` forms them (exact
+    integers, rounded once): ``transpiration_{mean,std}_cm``, ``lateral_flow_{mean,std}_cm`` [P][n_period] (the members'
+    totals over the period), ``wtd_shallowest_{mean,std}_cm`` and ``wtd_deepest_{mean,std}_cm`` (depth z0 + dz idx; the
+    sigma is dz times the index's), ``below_rows_{mean,std}`` [P][n_period][n_thresholds] (rows with the water table at
+    or above the threshold node) and, with ``wtd_obs``, ``below_fraction_mean`` (of the period's solved rows) and
+    ``solved_rows`` [n_period]; ``count`` [P][n_period], ``end_rows`` and ``overflow``.  NaN where nobody was counted.
+    The leading [P] axis is dropped for a single point."""
+    e = _check_period_ends(ends)
+    parts = split_period_totals_table(table, P, e.size, 4 + int(n_thresholds))
+    cnt, w = parts["pcnt"], parts["pmom"]
+    out = {}
+    for k, name in enumerate(("transpiration", "lateral_flow")):
+        out[name + "_mean_cm"], out[name + "_std_cm"] = limbs_to_mean_std(cnt, w[:, :, k], PERIOD_SCALE_TOTAL)
+    for k, name in ((2, "wtd_shallowest"), (3, "wtd_deepest")):
+        m, sd = limbs_to_mean_std(cnt, w[:, :, k], 0)
+        out[name + "_mean_cm"], out[name + "_std_cm"] = float(z0) + float(dz) * m, float(dz) * sd
+    out["below_rows_mean"], out["below_rows_std"] = limbs_to_mean_std(cnt[..., None], w[:, :, 4:], 0)
+    solved = None if wtd_obs is None else period_solved_rows(wtd_obs, e)
+    if solved is not None:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["below_fraction_mean"] = np.where(solved[None, :, None] > 0,
+                                                  out["below_rows_mean"] / np.maximum(solved, 1)[None, :, None], np.nan)
+    out["count"] = cnt.copy()
+    if P == 1:
+        out = {k: v[0] for k, v in out.items()}
+    if solved is not None:
+        out["solved_rows"] = solved
+    out["end_rows"] = e.copy()
+    out["overflow"] = int(parts["ovf"][0])
+    return out
+
+
+def _rank_bins(hist, lv):
+    """First bin whose cumulative count reaches k = max(1, ceil(n p)): hist [..., B], lv [Lv] -> (idx [..., Lv], n [...])."""
+    cum = np.cumsum(np.asarray(hist).astype(np.int64), axis=-1)
+    n = cum[..., -1]
+    k = np.maximum(1, np.ceil(n[..., None].astype(np.float64) * lv).astype(np.int64))
+    idx = (cum[..., None, :] < k[..., None]).sum(axis=-1)
+    return np.minimum(idx, cum.shape[-1] - 1), n
+
+
+def period_totals_distribution(hist_flux, hist_wtd, levels, flux_max_log2, z0, dz):
+    """Quantiles of the members' period totals from the histograms ``hist_flux`` [..., n_period, 2, B] and ``hist_wtd``
+    [..., n_period, 2, D], in NumPy integers.  Level p is the first bin b whose cumulative count reaches
+    k = max(1, ceil(n p)) in fp64 -- the rank of :func:`theta_distribution`, numpy.quantile(..., method="inverted_cdf")
+    on the bin index: the bin centre (b + 0.5) 2^e / B cm for the fluxes, the node depth z0 + dz b for the extremes.
+    ``transpiration_quantile_cm``, ``lateral_flow_quantile_cm``, ``wtd_shallowest_quantile_cm``, ``wtd_deepest_quantile_cm``
+    [..., n_period, Lv] (NaN where nobody was binned), ``count`` [..., n_period] (of the shallowest index) and ``levels``."""
+    hf, hw = np.asarray(hist_flux), np.asarray(hist_wtd)
+    if hf.ndim < 3 or hw.ndim < 3 or hf.shape[-2] != 2 or hw.shape[-2] != 2 or hf.shape[:-1] != hw.shape[:-1]:
+        raise ValueError(f"histograms must be [..., n_period, 2, B] and [..., n_period, 2, D], got {hf.shape} and {hw.shape}")
+    B = hf.shape[-1]
+    if B not in STORAGE_BINS:
+        raise ValueError(f"period histograms have a power of two in 32 .. 1024 bins, not {B}")
+    if (hf.size and hf.min() < 0) or (hw.size and hw.min() < 0):
+        raise ValueError("histogram counts must be >= 0")
+    lv = np.asarray(levels, dtype=np.float64).reshape(-1)
+    if lv.size > WTD_MAX_LEVELS or not np.all((lv >= 0.0) & (lv <= 1.0)):
+        raise ValueError(f"at most {WTD_MAX_LEVELS} quantile levels, each in [0, 1]: got {lv.tolist()}")
+    out = {"levels": lv}
+    idx, n = _rank_bins(hf, lv)                                        # [..., n_period, 2, Lv]
+    for q, name in enumerate(("transpiration", "lateral_flow")):
+        width = 2.0 ** int(flux_max_log2[q]) / B
+        out[name + "_quantile_cm"] = np.where(n[..., q, None] > 0, (idx[..., q, :] + 0.5) * width, np.nan)
+    idx, n = _rank_bins(hw, lv)
+    for q, name in enumerate(("wtd_shallowest", "wtd_deepest")):
+        out[name + "_quantile_cm"] = np.where(n[..., q, None] > 0, float(z0) + float(dz) * idx[..., q, :], np.nan)
+    out["count"] = n[..., 0]
+    return out
 
 
 # ---- particle filter on the host (include/hydrocol.h hc_set_filter) ----------------------------------------------------

@@ -48,6 +48,12 @@
  *   hc_get_layer_storage_outside, hc_get_layer_storage_overflow, hc_get_layer_storage_layout
  *                      <- (new) dz * sum of theta_vol (src/simulation.py:623) over a depth layer, per member: the water a
  *                         root zone or the whole column stores, as the ensemble's mean, sigma and histogram on the profile rows
+ *   hc_set_period_totals, hc_get_period_totals_words, hc_get_period_totals, hc_set_period_totals_tables,
+ *   hc_export_period_totals, hc_get/set/export_period_totals_hist(_table), hc_get/set_period_totals_acc,
+ *   hc_reset_period_totals, hc_get_period_totals_outside/overflow/layout
+ *                      <- (new) the "cumulative output" transpiration and lateral_flow (src/simulation.py:628-630) summed
+ *                         per member over a period of rows, the period's water-table extremes and hydroperiod, as the
+ *                         ensemble's mean, sigma and histograms
  *   hc_set_filter, hc_get/set_filter_stats, hc_get/set_filter_base, hc_get_filter_ancestors/weights/draw,
  *   hc_set_filter_soil_moisture, hc_get/set_filter_sm_stats, hc_get_filter_sm_width/member_weights/loglik/sm_theta
  *                      <- (new) the ensemble conditioned on wtd_obs (src/simulation.py:582-612): a bootstrap particle filter,
@@ -408,6 +414,73 @@ int hc_reset_layer_storage(hc_handle *h);
 int hc_get_layer_storage_outside(hc_handle *h, uint64_t *count);    /* 0 without a histogram */
 int hc_get_layer_storage_overflow(hc_handle *h, uint64_t *count);   /* the ovf slot */
 int hc_get_layer_storage_layout(hc_handle *h, int32_t *n_layers, int32_t *n_bins, int32_t *ranges);
+
+/* Period totals per member: what each member's transpiration and lateral flow sum to over a period of forcing rows (a
+ * month, a season, a year), how shallow and how deep its water table got in the period and on how many rows it stood at or
+ * above a depth (the hydroperiod), as exact integer moments and histograms over the members.  The rows of one member are
+ * correlated in time (one wetting front, one water table), so neither the per-row sigmas nor the per-row histograms give
+ * a period's spread: the rows are aggregated per member first, and only then is anything reduced over the members.
+ *   periods: n_period <= HC_PERIOD_MAX_PERIODS inclusive end rows e_0 < e_1 < ..., 1 <= e_p < n_rows.  Period p covers the
+ *   forcing rows (e_{p-1}, e_p], period 0 starts at row 1, each holds at most HC_PERIOD_MAX_ROWS rows; rows after the last
+ *   end belong to no period.  A skipped row (wtd_obs < 0) adds nothing but still closes a period when it is an end row.
+ *   Spin-up solves accumulate nothing.  hc_step_rows ends a launch on every end row (states do not depend on it).
+ *   accumulators (int64 [K][N], K = 4 + n_thresholds <= 8, member m of plane k at k N + m), from the diag and the
+ *   water-table index the row's launch stored for member m:
+ *     0  transpiration   sum over the period's solved rows of q = rint(diag[.,0] * 2^HC_PROF_SCALE_FLUX), |q| <=
+ *                        HC_PROF_Q_MAX (the profile statistics' rule; a clamped or NaN value adds one to ovf)
+ *     1  lateral_flow    the same of diag[.,1]
+ *     2  wtd_shallowest  the smallest water-table index of the period's solved rows (65535: none yet)
+ *     3  wtd_deepest     the largest (0: none yet)
+ *     4 + j              the solved rows with water-table index <= threshold_nodes[j]
+ *   At the end of a period, from the members that had a solved row in it (wtd_shallowest != 65535), per point:
+ *   moments (int64 table), in this order:
+ *     pmom [P][n_period][K][5]  word 0 the sum of v, words 1..4 the 20-bit limbs of the sum of v^2, as the profile
+ *                               statistics; v = A >> 12 = floor(A / 4096) for the two flux totals (units of 2^-20 cm,
+ *                               clamped to |v| <= HC_PROF_Q_MAX and counted in ovf), v = A for the indices and counts
+ *     pcnt [P][n_period]        the members counted (0 for a period with no solved row)
+ *     ovf  [1]
+ *     P n_period (5 K + 1) + 1 words.
+ *   histograms (int32 table; n_bins = 0: none), in this order:
+ *     phist_flux [P][n_period][2][B]  B a power of two in 32 .. 1024 over [0, 2^e_q) cm, e_q = flux_max_log2[q] in
+ *                                     -8 .. 12: bin (v B) >> (20 + e_q) for 0 <= v < 2^(20 + e_q), any other v adds one
+ *                                     to `outside`
+ *     phist_wtd  [P][n_period][2][D]  the shallowest and the deepest index of each member
+ *     then `outside` as one uint64 in two more entries (low word first): P n_period 2 (B + D) + 2 entries.
+ *   The threshold counts have moments only.  After the reduction the members' accumulators are reset (0, 0, 65535, 0,
+ *   0 ...).  On an assimilation row the reduction runs before the resampling or the analysis: the tables describe the
+ *   forecast.  The particle filter's resampling copies an ancestor's accumulators with its state (acc_out[k][m] =
+ *   acc_in[k][anc[m]]: the filter's path estimate); EnKF members persist.  Integer adds only: the tables are the same
+ *   bits at any launch length, member split, point order and number of handles / ranks summed.
+ * hc_set_period_totals: n_periods 0 = off (default); otherwise (re)creates the tables zeroed and the accumulators reset.
+ * HC_ERR_ARG (and off) for ends that do not ascend or lie outside [1, n_rows), more than HC_PERIOD_MAX_PERIODS periods or
+ * HC_PERIOD_MAX_ROWS rows in one, more than HC_PERIOD_MAX_THRESHOLDS thresholds, a threshold node outside the column, any
+ * other bin count or exponent, and while a sharded particle filter is set (hc_set_filter_shard, which in turn refuses
+ * while period totals are set: the routed columns do not carry the accumulators).  The tables are re-created, zeroed,
+ * when the points, the forcing rows or the depth change, the accumulators when the member count does.  get / set /
+ * export take the size in words (hc_get_period_totals_words; K N for the accumulators) or entries and fail on any other;
+ * the histogram calls fail when there is none.  hc_reset_period_totals zeroes the tables and resets the accumulators.
+ * hc_get_period_totals_layout returns the counts, the threshold nodes ([HC_PERIOD_MAX_THRESHOLDS]), the exponents ([2])
+ * and, if end_rows is not NULL, the first n_end_rows end rows.  The step kernels are the same with the tables on or off
+ * (a launch stores diag as it does for the profile statistics), and with them off nothing is launched or allocated. */
+#define HC_PERIOD_MAX_PERIODS 4096
+#define HC_PERIOD_MAX_ROWS (1 << 20)
+#define HC_PERIOD_MAX_THRESHOLDS 4
+int hc_set_period_totals(hc_handle *h, int32_t n_periods, const int64_t *end_rows, int32_t n_thresholds,
+                         const int32_t *threshold_nodes, int32_t n_bins, const int32_t *flux_max_log2);
+int hc_get_period_totals_words(hc_handle *h, int64_t *n_words);
+int hc_get_period_totals(hc_handle *h, int64_t *table, int64_t n_words);
+int hc_set_period_totals_tables(hc_handle *h, const int64_t *table, int64_t n_words);   /* checkpoint / resume, rank sums */
+int hc_export_period_totals(hc_handle *h, void *device_dst, int64_t n_words);           /* as hc_export_profile_stats */
+int hc_get_period_totals_hist(hc_handle *h, int32_t *table, int64_t n_entries);
+int hc_set_period_totals_hist_table(hc_handle *h, const int32_t *table, int64_t n_entries);
+int hc_export_period_totals_hist(hc_handle *h, void *device_dst, int64_t n_entries);
+int hc_get_period_totals_acc(hc_handle *h, int64_t *acc, int64_t n_words);              /* [K][N], for checkpoints */
+int hc_set_period_totals_acc(hc_handle *h, const int64_t *acc, int64_t n_words);
+int hc_reset_period_totals(hc_handle *h);
+int hc_get_period_totals_outside(hc_handle *h, uint64_t *count);    /* 0 without histograms */
+int hc_get_period_totals_overflow(hc_handle *h, uint64_t *count);   /* the ovf slot */
+int hc_get_period_totals_layout(hc_handle *h, int32_t *n_periods, int32_t *n_thresholds, int32_t *n_bins,
+                                int32_t *threshold_nodes, int32_t *flux_max_log2, int64_t *end_rows, int64_t n_end_rows);
 
 /* Particle filter on the well's water table (bootstrap filter, systematic resampling in exact integers).
  *   Assimilation rows: r >= 1, r % stride == 0 and wtd_obs[r] >= 0 (wtd_obs as it stands when hc_step_rows reaches the row:
