@@ -94,6 +94,14 @@ unknown keys, only membership of the 12 is checked):
   exchanged; the states, tables, closing lines and the file are those of the one-GPU run to the bit (``gpus`` apart); the
   filter's tables are rank 0's.  ``false`` or no key: the refusal above.  A sweep accepts and ignores the key.  Added to
   the file when the key is given: ``filter_sharded``.
+* ``"Filter": {..., "ESS_floor": 0.1}``: hold the effective sample size of every resampling above that fraction of the
+  counted members (0 < f < 1; include/hydrocol.h hc_set_filter_tempering): per row and point the weights are raised to the
+  largest exponent beta = k / 1024 of a bisection in exact integers that keeps it there -- the observation error inflated
+  by 1 / sqrt(beta) where the stated one would spend the ensemble's diversity on one row.  ``filter_ess`` and
+  ``filter_loglik_rows`` keep scoring the forecast with the stated error; ``filter_survivors`` counts the resampling that
+  happened.  With ``Soil_Moisture``, ``Sharded``, a sweep and either noise source.  Added to the file: ``filter_ess_floor``
+  and, over the ``filter_rows`` ``[R]``, ``filter_beta``, ``filter_ess_tempered``, ``filter_ess_target`` (a sweep: a leading
+  ``[P]`` axis), and the run ends with `` [Ensemble xN] filter tempering: K of R rows tempered, smallest beta = ...``.
 * ``"Filter": {..., "Soil_Moisture": {"Filename": "sm.csv", "Depths_cm": [30, 60, 120], "Sigma": 0.02}}``: a soil-moisture
   record joins the well in the filter's weights (include/hydrocol.h hc_set_filter_soil_moisture): on a row with sensor
   values every member is weighted by the joint Gaussian likelihood of the well and of theta at the sensors' nodes, so the
@@ -274,6 +282,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     storage = storage_settings(ens)
     periods = period_settings(ens)
     filt = filter_settings(ens, ranks.world)
+    ess_floor = filter_ess_floor(ens)
     enkf = enkf_settings(ens, ranks.world)
     sm = soil_moisture_settings(ens, ranks.world)
     fsm = soil_moisture_settings(ens, ranks.world, "Filter")
@@ -292,7 +301,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     plan = period_plan(periods, cols, forcing, rows)            # before any GPU call, like the storage's ranges
     if ens.get("Points"):
         return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels, filt,
-                          enkf, record, scheme, window, frecord, theta, storage, periods, plan)
+                          enkf, record, scheme, window, frecord, theta, storage, periods, plan, ess_floor)
     sharded = enkf_sharded(ens)
     fsharded = filter_sharded(ens)
     if sharded:
@@ -313,7 +322,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     sim = EnsembleSimulation(cols, forcing, hi - lo, seed=int(ens.get("Seed", 0)), device=device, member_offset=lo,
                              noise=str(ens.get("Noise", "philox")).lower(),
                              spinup=str(ens.get("Spinup", "shared")).lower(), profile_stride=stride,
-                             wtd_hist_stride=dist_stride, theta_hist_bins=theta[0], **_filter_kwargs(filt, frecord),
+                             wtd_hist_stride=dist_stride, theta_hist_bins=theta[0],
+                             **_filter_kwargs(filt, frecord, ess_floor),
                              **_enkf_kwargs(enkf, record, scheme, window), **_storage_kwargs(storage),
                              **_period_kwargs(periods, plan), **shard_kw)
     label = f"Ensemble x{n_members}"
@@ -353,7 +363,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     # the filters' tables describe the one point: every rank of a sharded run holds the same ones, and rank 0's are taken
     # (placed by it alone; a sum over the ranks would count them world times)
     eids = [0] if ranks.rank == 0 else []
-    ftables, filter_line = _reduce_filter(ranks, sim, eids, 1, forcing.dim_t, filt, label, keep_points=False)
+    ftables, filter_line = _reduce_filter(ranks, sim, eids, 1, forcing.dim_t, filt, label, keep_points=False,
+                                          ess_floor=ess_floor)
     extra.update(ftables)
     fstables, fsm_line = _reduce_sm(ranks, sim, eids, 1, forcing.dim_t, filt[0], frecord, label, keep_points=False,
                                     owner="filter")
@@ -657,16 +668,18 @@ def _period_kwargs(periods, plan):
     return kw
 
 
-FILTER_KEYS = ("Stride", "Sigma_cm", "Seed", "Sharded", "Soil_Moisture")
+FILTER_KEYS = ("Stride", "Sigma_cm", "Seed", "Sharded", "Soil_Moisture", "ESS_floor")
 
 
 def filter_settings(ens, n_gpus=1):
     """Ensemble.Filter -> (stride, sigma_cm, seed or None = the ensemble's seed); (0, None, None) when absent or off.  Pure:
     runs before any GPU call, and a bad value is a ValueError (message + exit status 1).  A single-point ensemble on more
     than one GPU is refused -- resampling would have to move states between ranks -- unless the block says
-    ``"Sharded": true`` (:func:`filter_sharded`)."""
+    ``"Sharded": true`` (:func:`filter_sharded`).  ``ESS_floor`` (:func:`filter_ess_floor`) is checked here too."""
     import math
     from numbers import Integral, Real
+    if "ESS_floor" in ens:
+        raise ValueError(" Ensemble: ESS_floor belongs inside the \"Filter\" block.")
     block = ens.get("Filter")
     if block is None:
         return 0, None, None
@@ -692,12 +705,29 @@ def filter_settings(ens, n_gpus=1):
     if not isinstance(sharded, bool):
         raise ValueError(f" Ensemble: Filter.Sharded = {sharded!r} must be true or false.")
     stride = int(stride)
+    if "ESS_floor" in block:
+        floor = block["ESS_floor"]
+        if isinstance(floor, bool) or not isinstance(floor, Real) or not math.isfinite(floor) or not 0 < floor < 1:
+            raise ValueError(f" Ensemble: Filter.ESS_floor = {floor!r} must be a finite number with 0 < ESS_floor < 1.")
+        if not stride:
+            raise ValueError(" Ensemble: Filter.ESS_floor needs an active filter (Filter.Stride > 0).")
     if not stride:
         return 0, None, None
     if not ens.get("Points") and int(n_gpus) > 1 and not sharded:
         raise ValueError(f" Ensemble: Filter with one parameter point runs on one GPU ({n_gpus} requested): resampling "
                          f"would move members between ranks.")
     return stride, float(sigma), (None if seed is None else int(seed))
+
+
+def filter_ess_floor(ens):
+    """Ensemble.Filter.ESS_floor -> the floor f (0 < f < 1) below which the effective sample size of a resampling is not
+    allowed to fall, as a fraction of the counted members (include/hydrocol.h hc_set_filter_tempering), or None when the
+    key is not given.  Checked by :func:`filter_settings`, which this runs first."""
+    filter_settings(ens)
+    block = ens.get("Filter")
+    if not isinstance(block, dict) or "ESS_floor" not in block:
+        return None
+    return float(block["ESS_floor"])
 
 
 def filter_sharded(ens):
@@ -1050,19 +1080,22 @@ def _reduce_enkf(ranks, sim, ids, P, T, enkf, label, keep_points, z0_cm):
     return out, line
 
 
-def _filter_kwargs(filt, record=None):
+def _filter_kwargs(filt, record=None, ess_floor=None):
     stride, sigma, seed = filt
     if not stride:
         return {}
     kw = dict(filter_stride=stride, filter_sigma_cm=sigma, filter_seed=seed)
     if record is not None:
         kw["filter_soil_moisture"] = record
+    if ess_floor is not None:
+        kw["filter_ess_floor"] = ess_floor
     return kw
 
 
-def _reduce_filter(ranks, sim, ids, P, T, filt, label, keep_points):
+def _reduce_filter(ranks, sim, ids, P, T, filt, label, keep_points, ess_floor=None):
     """The filter's datasets from this rank's handle ``sim`` (None: no points), its points ``ids`` placed in the run's [P]
-    table and summed over the ranks (float64 as int64 bits: ``multigpu.place_points``), and the closing line (rank 0)."""
+    table and summed over the ranks (float64 as int64 bits: ``multigpu.place_points``), and the closing line (rank 0).
+    ``ess_floor`` (Filter.ESS_floor): the tempering's table likewise, its datasets and a second closing line."""
     import numpy as np
     from .multigpu import place_points
     from .stepper import filter_summary, stride_rows
@@ -1072,11 +1105,19 @@ def _reduce_filter(ranks, sim, ids, P, T, filt, label, keep_points):
     n_arow = stride_rows(T, stride)
     local = sim.filter_table().reshape(-1, n_arow, 4) if sim is not None else np.zeros((0, n_arow, 4))
     table = place_points(local, ids, P, ranks)
-    summary = filter_summary(table if keep_points else table[0], stride, sigma)
+    ttable = None
+    if ess_floor is not None:
+        tlocal = sim.filter_temper_table().reshape(-1, n_arow, 4) if sim is not None else np.zeros((0, n_arow, 4))
+        ttable = place_points(tlocal, ids, P, ranks)
+        ttable = ttable if keep_points else ttable[0]
+    summary = filter_summary(table if keep_points else table[0], stride, sigma, temper_table=ttable)
     out = {"filter_rows": summary["rows"], "filter_count": summary["count"], "filter_ess": summary["ess"],
            "filter_loglik_rows": summary["loglik_rows"], "filter_survivors": summary["survivors"],
            "filter_loglik": np.asarray(summary["loglik"], dtype=np.float64),
            "filter_sigma_cm": np.array(sigma, dtype=np.float64)}
+    if ess_floor is not None:
+        out.update(filter_ess_floor=np.array(ess_floor, dtype=np.float64), filter_beta=summary["beta"],
+                   filter_ess_tempered=summary["ess_tempered"], filter_ess_target=summary["ess_target"])
     n = int(summary["rows"].size)
     if ranks.rank != 0:
         return out, None
@@ -1086,6 +1127,12 @@ def _reduce_filter(ranks, sim, ids, P, T, filt, label, keep_points):
         line = f" [{label}] filter log-likelihood: best point {best} = {ll[best]:.3f} over {n} rows"
     else:
         line = f" [{label}] filter log-likelihood = {float(summary['loglik']):.3f} over {n} rows"
+    if ess_floor is not None:
+        # (a sweep: the rows on which any point was tempered, the smallest beta of any point)
+        beta = np.asarray(summary["beta"], dtype=np.float64).reshape(-1, n)
+        k = int((beta < 1.0).any(axis=0).sum())
+        least = float(np.nanmin(beta)) if np.isfinite(beta).any() else float("nan")
+        line += f"\n [{label}] filter tempering: {k} of {n} rows tempered, smallest beta = {least:.6g}"
     return out, line
 
 
@@ -1317,7 +1364,7 @@ def _reduce_periods(ranks, sim, ids, P, cols, forcing, periods, plan, label, kee
 
 def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride=0, dist_levels=None,
                filt=(0, None, None), enkf=(0, None, None, None), record=None, scheme=None, window=None, frecord=None,
-               theta=(0, None), storage=None, periods=None, plan=None):
+               theta=(0, None), storage=None, periods=None, plan=None, ess_floor=None):
     """Parameter points x members: this rank's points in one handle (ensemble.SweepSimulation), the whole table assembled
     over the ranks (multigpu.assemble_points)."""
     import numpy as np
@@ -1344,7 +1391,7 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     if mine:
         sim = SweepSimulation(points, forcing, n_members, seed=int(ens.get("Seed", 0)), device=device, point_ids=mine,
                               profile_stride=stride, wtd_hist_stride=dist_stride, theta_hist_bins=theta[0],
-                              **_filter_kwargs(filt, frecord), **_enkf_kwargs(enkf, record, scheme, window),
+                              **_filter_kwargs(filt, frecord, ess_floor), **_enkf_kwargs(enkf, record, scheme, window),
                               **_storage_kwargs(storage), **_period_kwargs(periods, plan))
         _step_all(sim, rows, label, ranks)
         table = sim.moments()
@@ -1365,7 +1412,7 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     arrays.update(stor_tables)
     ptables, period_line = _reduce_periods(ranks, sim, mine, P, ref, forcing, periods, plan, label, keep_points=True)
     arrays.update(ptables)
-    ftables, filter_line = _reduce_filter(ranks, sim, mine, P, T, filt, label, keep_points=True)
+    ftables, filter_line = _reduce_filter(ranks, sim, mine, P, T, filt, label, keep_points=True, ess_floor=ess_floor)
     arrays.update(ftables)
     fstables, fsm_line = _reduce_sm(ranks, sim, mine, P, T, filt[0], frecord, label, keep_points=True, owner="filter")
     arrays.update(fstables)

@@ -215,6 +215,13 @@ struct hc_handle {
     DevBuf<long long> filt_qm;
     DevBuf<double> filt_Y, filt_lmax, filt_part, filt_sums;
     DevBuf<unsigned long long> filt_ipart;
+    // tempered weights (hc_set_filter_tempering): the ESS floor (0: off); the table float64 [P][n_arow][4] keyed like the
+    // filter's; the last assimilation's trials [P][11][4] (test hook); on a sensor row every point's search state and the
+    // tiles' integer sums of one trial
+    double filt_floor = 0.0;
+    AccTable<double> ftemp{"entries"};
+    DevBuf<long long> filt_trials, filt_tstate;
+    DevBuf<unsigned long long> filt_tpart;
     // one point's members on several handles (hc_set_filter_shard): the shard count (0: off), this handle's index and the
     // bounds b_0 = 0 < ... < b_S = n_global, on the host and on the device; the caller's buffer -- the gathered
     // water-table indices [n_global], the send region [(n + S - 1) 2 D] and the receive region [n 2 D], in 8-byte
@@ -2371,6 +2378,320 @@ __global__ void filter_expand_weights_kernel(const unsigned short *w, const long
     if (k < n_members) qm[k] = filter_q(w, q_all + (size_t)(k / members_per_point) * D, D, k);
 }
 
+// ---- tempered weights (hc_set_filter_tempering, include/hydrocol.h)
+// After the weight kernels, per point: the largest k of a bisection over beta_k = k / 1024 for which the weights
+// q = floor(2^31 exp(beta_k (l - s))) keep Q^2 >= T sum q^2.  Q, sum q^2 and the comparison are exact integers, so k
+// depends on no order.  The only floating-point arithmetic is the exp of a weight and the ESS quotient of the table;
+// contraction is off.
+constexpr int TEMPER_STEPS = 1024;                     // beta_k = k / TEMPER_STEPS
+constexpr int TEMPER_TRIALS = 11;                      // k = 1024, then ten halvings of [0, 1024]
+constexpr int TEMPER_WIDTH = 4;                        // table entries per point and slot; words per trial of the hook
+// a point's search on a sensor row, int64 words: the k of the next trial (the result once done), lo, hi, done (2: the row
+// is not tempered for want of members), trials evaluated, T, then Q and sum q^2 (low, high word) at lo
+constexpr int TEMPER_STATE = 9;
+
+// T = min(n, max(1, ceil(f n)))
+__device__ __forceinline__ long long temper_target(double f, long long n)
+{
+#pragma clang fp contract(off)
+    long long T = (long long)ceil(f * (double)n);
+    T = T < 1 ? 1 : T;
+    return T < n ? T : n;
+}
+
+// q at beta_k of a counted member or an occupied bin, d = l - s: the product rounded once; k = 1024 multiplies by 1.0
+__device__ __forceinline__ long long temper_q(int k, double d)
+{
+#pragma clang fp contract(off)
+    const double beta = (double)k / (double)TEMPER_STEPS;
+    const double a = beta * d;
+    return (long long)floor(0x1p31 * exp(a));
+}
+
+// Q^2 >= T S, both sides exact: Q < 2^62, T < 2^31, S < 2^93
+__device__ __forceinline__ bool temper_ok(unsigned long long Q, unsigned long long s_hi, unsigned long long s_lo, long long T)
+{
+    const unsigned __int128 S = ((unsigned __int128)s_hi << 64) | s_lo;
+    return (unsigned __int128)Q * Q >= (unsigned __int128)(unsigned long long)T * S;
+}
+
+// the block's sums of (Q, S): wave shuffles, then LDS; every thread gets them
+__device__ __forceinline__ void temper_block_sum(unsigned long long &Q, unsigned long long &hi, unsigned long long &lo)
+{
+    __shared__ unsigned long long part[FILT_THREADS / WAVE][3];
+    for (int o = WAVE / 2; o > 0; o >>= 1) {
+        const unsigned long long ohi = __shfl_xor(hi, o), olo = __shfl_xor(lo, o);
+        add_u128(hi, lo, ohi, olo);
+        Q += __shfl_xor(Q, o);
+    }
+    if (threadIdx.x % WAVE == 0) {
+        part[threadIdx.x / WAVE][0] = Q;
+        part[threadIdx.x / WAVE][1] = lo;
+        part[threadIdx.x / WAVE][2] = hi;
+    }
+    __syncthreads();
+    Q = hi = lo = 0;
+    for (int u = 0; u < FILT_THREADS / WAVE; u++) {
+        Q += part[u][0];
+        add_u128(hi, lo, part[u][2], part[u][1]);
+    }
+    __syncthreads();              // part may be reused by the next call
+}
+
+// One step of the procedure after trial `n_done` at k gave (Q, S): the trial recorded, {lo, hi} and the sums at lo
+// updated.  Returns the next k, or the result with done set.
+struct TemperSearch {
+    long long k, lo, hi, done, trials, T;
+    unsigned long long q_lo, s_lo_lo, s_lo_hi;         // Q_k and S_k at k = lo (k = 0: n 2^31, n 2^62)
+};
+__device__ __forceinline__ void temper_step(TemperSearch &t, unsigned long long Q, unsigned long long s_hi,
+                                            unsigned long long s_lo, long long *trial_row)
+{
+    trial_row[0] = t.k;
+    trial_row[1] = (long long)Q;
+    trial_row[2] = (long long)s_lo;
+    trial_row[3] = (long long)s_hi;
+    const bool ok = temper_ok(Q, s_hi, s_lo, t.T);
+    if (t.trials == 0 && ok) {
+        t.lo = t.hi = TEMPER_STEPS;
+        t.q_lo = Q, t.s_lo_lo = s_lo, t.s_lo_hi = s_hi;
+    } else if (t.trials > 0 && ok) {
+        t.lo = t.k;
+        t.q_lo = Q, t.s_lo_lo = s_lo, t.s_lo_hi = s_hi;
+    } else if (t.trials > 0) {
+        t.hi = t.k;
+    }                                                  // (trial 0 failed: lo = 0 and hi = 1024 as created)
+    t.trials++;
+    t.done = t.hi - t.lo > 1 ? 0 : 1;
+    t.k = t.done ? t.lo : (t.lo + t.hi) >> 1;
+}
+__device__ __forceinline__ TemperSearch temper_begin(long long n, double floor_f)
+{
+    TemperSearch t;
+    t.k = TEMPER_STEPS, t.lo = 0, t.hi = TEMPER_STEPS, t.done = 0, t.trials = 0;
+    t.T = temper_target(floor_f, n);
+    t.q_lo = (unsigned long long)n << 31;
+    const unsigned __int128 s0 = (unsigned __int128)(unsigned long long)n << 62;
+    t.s_lo_lo = (unsigned long long)s0, t.s_lo_hi = (unsigned long long)(s0 >> 64);
+    return t;
+}
+
+// the table's row of a point: beta, the ESS at beta, T, the trials evaluated; not tempered (no counted member): NaN
+__device__ __forceinline__ void temper_stats(const TemperSearch &t, bool tempered, double *st)
+{
+#pragma clang fp contract(off)
+    if (!tempered) {
+        for (int e = 0; e < TEMPER_WIDTH; e++) st[e] = __builtin_nan("");
+        return;
+    }
+    st[0] = (double)t.k / (double)TEMPER_STEPS;
+    st[1] = filter_ess(t.q_lo, t.s_lo_hi, t.s_lo_lo);
+    st[2] = (double)t.T;
+    st[3] = (double)t.trials;
+}
+
+// the draw of filter_draw on the tempered sum: the same Philox value x, qr[p] = {Q_k, floor(x Q_k / 2^64)}
+__device__ __forceinline__ void temper_draw(unsigned long long seed, const long long *point_base, long long member_offset,
+                                            long long p, long long members_per_point, unsigned row, unsigned long long Q,
+                                            unsigned long long *qr)
+{
+    const unsigned long long key = point_base ? (unsigned long long)point_base[p]
+                                              : (unsigned long long)(member_offset + p * members_per_point);
+    const unsigned long long x = filter_philox64(seed, key, row);
+    qr[2 * p] = Q;
+    qr[2 * p + 1] = __umul64hi(x, Q);
+}
+
+// The bin path, one block per point after filter_weights_kernel: the row's bin counts n_b as that kernel forms them,
+// d_b = l_b - s in LDS, and every trial inside the block -- the threads stride over the D bins with private sums, the
+// block adds them, thread 0 compares and publishes the next k through LDS.  k < 1024: the point's bin table and draw are
+// rewritten.  Every loop's trip count is block-uniform.
+__global__ __launch_bounds__(FILT_THREADS) void filter_temper_bins_kernel(
+    const unsigned short *w, long long members_per_point, int D, int obs, double dz, double sigma, double floor_f,
+    unsigned long long seed, const long long *point_base, long long member_offset, unsigned row, long long n_arow,
+    long long slot, long long *q_out, unsigned long long *qr, double *tstats, long long *trials)
+{
+#pragma clang fp contract(off)
+    __shared__ unsigned bins[HC_MAX_DEPTH_NODES];
+    __shared__ double dsh[HC_MAX_DEPTH_NODES];
+    __shared__ long long ctl[2];                       // the next k, done
+    for (int b = threadIdx.x; b < D; b += FILT_THREADS) bins[b] = 0;
+    __syncthreads();
+    const long long p = blockIdx.x;
+    const long long m0 = p * members_per_point, m1 = m0 + members_per_point;
+    const int lane = threadIdx.x % WAVE;
+    for (long long k0 = m0 + (threadIdx.x - lane); k0 < m1; k0 += FILT_THREADS) {
+        const long long k = k0 + lane;
+        const int b = k < m1 ? (int)w[k] : -1;
+        unsigned long long pending = __ballot(b >= 0 && b < D);
+        while (pending) {
+            const int leader = __ffsll((long long)pending) - 1;
+            const int v = __builtin_amdgcn_readlane(b, leader);
+            const unsigned long long same = __ballot(b == v) & pending;
+            if (lane == leader) atomicAdd(&bins[v], (unsigned)__popcll(same));
+            pending &= ~same;
+        }
+    }
+    __syncthreads();
+    // l_b as filter_weights_kernel forms it; s = the largest over the occupied bins; n = the members counted
+    double best = -INFINITY;
+    unsigned long long n = 0, zero_hi = 0, zero_lo = 0;
+    for (int b = threadIdx.x; b < D; b += FILT_THREADS) {
+        const double t = dz * (double)(b - obs) / sigma;
+        const double l = -0.5 * (t * t);
+        dsh[b] = l;
+        if (bins[b]) {
+            best = l > best ? l : best;
+            n += bins[b];
+        }
+    }
+    const double s = filter_block_max(best);
+    temper_block_sum(n, zero_hi, zero_lo);
+    for (int b = threadIdx.x; b < D; b += FILT_THREADS) dsh[b] = dsh[b] - s;
+    __syncthreads();
+    long long *tr = trials + (size_t)p * TEMPER_TRIALS * TEMPER_WIDTH;
+    double *st = tstats + ((size_t)p * n_arow + slot) * TEMPER_WIDTH;
+    TemperSearch t = temper_begin((long long)n, floor_f);          // (thread 0's copy is the one that advances)
+    if (n == 0) {
+        if (threadIdx.x == 0) {
+            for (int e = 0; e < TEMPER_TRIALS * TEMPER_WIDTH; e++) tr[e] = e % TEMPER_WIDTH == 0 ? -1 : 0;
+            temper_stats(t, false, st);
+        }
+        return;
+    }
+    int k = TEMPER_STEPS;
+    for (int trial = 0; trial < TEMPER_TRIALS; trial++) {
+        unsigned long long Q = 0, hi = 0, lo = 0;
+        for (int b = threadIdx.x; b < D; b += FILT_THREADS) {
+            const unsigned long long nb = bins[b];
+            if (nb) {
+                const unsigned long long uq = (unsigned long long)temper_q(k, dsh[b]);
+                Q += nb * uq;                                      // < 2^31 members x 2^31
+                const unsigned long long sq = uq * uq;             // < 2^62
+                add_u128(hi, lo, __umul64hi(sq, nb), sq * nb);
+            }
+        }
+        temper_block_sum(Q, hi, lo);
+        if (threadIdx.x == 0) {
+            temper_step(t, Q, hi, lo, tr + trial * TEMPER_WIDTH);
+            ctl[0] = t.k;
+            ctl[1] = t.done;
+        }
+        __syncthreads();
+        k = (int)ctl[0];
+        const bool done = ctl[1] != 0;
+        __syncthreads();
+        if (done) break;
+    }
+    if (threadIdx.x == 0) {
+        for (int e = (int)t.trials * TEMPER_WIDTH; e < TEMPER_TRIALS * TEMPER_WIDTH; e++) tr[e] = e % TEMPER_WIDTH == 0 ? -1 : 0;
+        temper_stats(t, true, st);
+        if (k < TEMPER_STEPS) temper_draw(seed, point_base, member_offset, p, members_per_point, row, t.q_lo, qr);
+    }
+    if (k < TEMPER_STEPS)
+        for (int b = threadIdx.x; b < D; b += FILT_THREADS) q_out[(size_t)p * D + b] = bins[b] ? temper_q(k, dsh[b]) : 0;
+}
+
+// A sensor row, one trial's sums on the prefix scan's tiling: block (t, p) reads l_m and the index of its tile's
+// members, takes the point's k from the search's state and writes the tile's {Q, S low, S high}.  A point that is done
+// exits at once.
+__global__ __launch_bounds__(FILT_THREADS) void filter_temper_sum_kernel(const unsigned short *w, long long members_per_point,
+                                                                         int D, int width, long long n_tiles,
+                                                                         const double *Y, const double *smax,
+                                                                         const long long *state, unsigned long long *tpart)
+{
+#pragma clang fp contract(off)
+    const long long p = blockIdx.y, t = blockIdx.x;
+    const long long *st = state + (size_t)p * TEMPER_STATE;
+    if (st[3]) return;
+    const int k = (int)st[0];
+    const double s = smax[p];
+    unsigned long long Q = 0, hi = 0, lo = 0;
+    for (int j = 0; j < FILT_PER_THREAD; j++) {
+        const long long m = t * FILT_TILE + (long long)threadIdx.x * FILT_PER_THREAD + j;
+        if (m >= members_per_point) continue;
+        const size_t i = (size_t)(p * members_per_point + m);
+        const double l = Y[i * width];
+        if (!filter_counted((int)w[i], D, l)) continue;
+        const unsigned long long uq = (unsigned long long)temper_q(k, l - s);
+        Q += uq;
+        add_u128(hi, lo, 0ull, uq * uq);
+    }
+    temper_block_sum(Q, hi, lo);
+    if (threadIdx.x == 0) {
+        unsigned long long *out = tpart + ((size_t)p * n_tiles + t) * 3;
+        out[0] = Q;
+        out[1] = lo;
+        out[2] = hi;
+    }
+}
+
+// ... and the decision, one block per point: the tiles' sums added (integers: no order), compared, {lo, hi} updated and
+// the trial recorded.  first: trial 0 at k = 1024 on the sums filter_member_weights_kernel left (four words a tile, the
+// last the members counted), which also creates the state and the hook's rows.
+__global__ __launch_bounds__(FILT_THREADS) void filter_temper_decide_kernel(const unsigned long long *part, int stride,
+                                                                            long long n_tiles, int first, double floor_f,
+                                                                            long long *state, long long *trials)
+{
+    const long long p = blockIdx.x;
+    long long *sw = state + (size_t)p * TEMPER_STATE;
+    if (!first && sw[3]) return;
+    unsigned long long Q = 0, hi = 0, lo = 0, n = 0, n_hi = 0, n_lo = 0;
+    for (long long u = threadIdx.x; u < n_tiles; u += FILT_THREADS) {
+        const unsigned long long *in = part + ((size_t)p * n_tiles + u) * stride;
+        Q += in[0];
+        add_u128(hi, lo, in[2], in[1]);
+        if (first) n += in[3];
+    }
+    temper_block_sum(Q, hi, lo);
+    if (first) temper_block_sum(n, n_hi, n_lo);
+    if (threadIdx.x != 0) return;
+    long long *tr = trials + (size_t)p * TEMPER_TRIALS * TEMPER_WIDTH;
+    TemperSearch t;
+    if (first) {
+        for (int e = 0; e < TEMPER_TRIALS * TEMPER_WIDTH; e++) tr[e] = e % TEMPER_WIDTH == 0 ? -1 : 0;
+        t = temper_begin((long long)n, floor_f);
+        if (n == 0 || Q == 0) t.done = 2;
+    } else {
+        t.k = sw[0], t.lo = sw[1], t.hi = sw[2], t.done = sw[3], t.trials = sw[4], t.T = sw[5];
+        t.q_lo = (unsigned long long)sw[6], t.s_lo_lo = (unsigned long long)sw[7], t.s_lo_hi = (unsigned long long)sw[8];
+    }
+    if (!t.done) temper_step(t, Q, hi, lo, tr + t.trials * TEMPER_WIDTH);
+    sw[0] = t.k, sw[1] = t.lo, sw[2] = t.hi, sw[3] = t.done, sw[4] = t.trials, sw[5] = t.T;
+    sw[6] = (long long)t.q_lo, sw[7] = (long long)t.s_lo_lo, sw[8] = (long long)t.s_lo_hi;
+}
+
+// ... and the result, on the tiling again: the table's row and, for a point with k < 1024, its members' q_m and its draw
+// rewritten.  Y[m][m_s + 1] = exp(l_m - s) stays: W and the increment were formed from it.
+__global__ __launch_bounds__(FILT_THREADS) void filter_temper_apply_kernel(
+    const unsigned short *w, long long members_per_point, int D, int width, const double *Y, const double *smax,
+    const long long *state, unsigned long long seed, const long long *point_base, long long member_offset, unsigned row,
+    long long n_arow, long long slot, long long *qm, unsigned long long *qr, double *tstats)
+{
+#pragma clang fp contract(off)
+    const long long p = blockIdx.y, t = blockIdx.x;
+    const long long *sw = state + (size_t)p * TEMPER_STATE;
+    const bool tempered = sw[3] == 1;
+    const int k = (int)sw[0];
+    if (t == 0 && threadIdx.x == 0) {
+        TemperSearch ts;
+        ts.k = sw[0], ts.lo = sw[1], ts.hi = sw[2], ts.done = sw[3], ts.trials = sw[4], ts.T = sw[5];
+        ts.q_lo = (unsigned long long)sw[6], ts.s_lo_lo = (unsigned long long)sw[7], ts.s_lo_hi = (unsigned long long)sw[8];
+        temper_stats(ts, tempered, tstats + ((size_t)p * n_arow + slot) * TEMPER_WIDTH);
+        if (tempered && k < TEMPER_STEPS)
+            temper_draw(seed, point_base, member_offset, p, members_per_point, row, ts.q_lo, qr);
+    }
+    if (!tempered || k >= TEMPER_STEPS) return;
+    const double s = smax[p];
+    for (int j = 0; j < FILT_PER_THREAD; j++) {
+        const long long m = t * FILT_TILE + (long long)threadIdx.x * FILT_PER_THREAD + j;
+        if (m >= members_per_point) continue;
+        const size_t i = (size_t)(p * members_per_point + m);
+        const double l = Y[i * width];
+        qm[i] = filter_counted((int)w[i], D, l) ? temper_q(k, l - s) : 0;
+    }
+}
+
 __global__ void widen_u16(const unsigned short *in, int *out, size_t n)
 {
     size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2849,6 +3170,21 @@ int ensure_fsm(hc_handle *h)
     return ensure_da_table(h, h->fsm, h->filt_stride, (int64_t)h->fsm_n * ENKF_SENSOR_WIDTH, 0);
 }
 
+// the table of the tempered weights (hc_set_filter_tempering): [P][n_arow][4] float64, created as NaN
+int ensure_ftemp(hc_handle *h)
+{
+    if (h->filt_floor <= 0.0) return fail(HC_ERR_ARG, "the filter's weights are not tempered (hc_set_filter_tempering)");
+    if (int rc = ensure_filter(h)) return rc;
+    return ensure_da_table(h, h->ftemp, h->filt_stride, TEMPER_WIDTH, 0);
+}
+
+void temper_off(hc_handle *h)
+{
+    h->filt_floor = 0.0;
+    h->ftemp.release();
+    h->filt_trials.release(); h->filt_tstate.release(); h->filt_tpart.release();
+}
+
 void fsm_off(hc_handle *h)
 {
     h->fsm_n = 0;
@@ -2865,6 +3201,7 @@ void filter_off(hc_handle *h)
 {
     filter_shard_off(h);
     fsm_off(h);
+    temper_off(h);
     h->filt_stride = 0;
     h->filt_done = false;
     h->filt.release();
@@ -4060,6 +4397,46 @@ int filter_member_weights(hc_handle *h, const Chunk &c, const EnkfRow &s, const 
     return filter_sm_moment(h, s, nullptr, 3, n_tiles, n_arow, slot);
 }
 
+// The tempering of a row's weights (hc_set_filter_tempering) after its weight kernels, w being the indices they read.
+// The bin path: one kernel, every trial inside the block.  A sensor row (ms > 0): trial 0 on the tile sums the weights
+// left, then ten pairs of sums and decision enqueued unconditionally -- no host synchronisation; a point that is done
+// exits at once -- and the result applied to q_m and the draw.
+int filter_temper(hc_handle *h, const unsigned short *w, int ms, int64_t mpp, int64_t n_tiles, int64_t row,
+                  const long long *pbase, long long key)
+{
+    const int64_t D = h->p.dim_d, P = h->n_points, slot = row / h->filt_stride, n_arow = filter_rows(h);
+    if (h->filt_trials.ensure((size_t)(P * TEMPER_TRIALS * TEMPER_WIDTH))) return HC_ERR_DEVICE;
+    if (ms == 0) {
+        hipLaunchKernelGGL(filter_temper_bins_kernel, dim3((unsigned)P), dim3(FILT_THREADS), 0, h->stream, w, (long long)mpp,
+                           (int)D, h->h_wtd_obs[(size_t)row], h->p.dz, h->filt_sigma, h->filt_floor,
+                           (unsigned long long)h->filt_seed, pbase, key, (unsigned)row, (long long)n_arow, (long long)slot,
+                           h->filt_q.p, h->filt_qr.p, h->ftemp.buf.p, h->filt_trials.p);
+        HIP_TRY(hipGetLastError());
+        return HC_OK;
+    }
+    if (h->filt_tstate.ensure((size_t)(P * TEMPER_STATE)) || h->filt_tpart.ensure((size_t)(P * n_tiles * 3)))
+        return HC_ERR_DEVICE;
+    const int width = ms + 2;
+    const double *smax = h->filt_sums.p + (size_t)(P * FILT_COLS);
+    const dim3 tiles((unsigned)n_tiles, (unsigned)P);
+    hipLaunchKernelGGL(filter_temper_decide_kernel, dim3((unsigned)P), dim3(FILT_THREADS), 0, h->stream, h->filt_ipart.p, 4,
+                       (long long)n_tiles, 1, h->filt_floor, h->filt_tstate.p, h->filt_trials.p);
+    HIP_TRY(hipGetLastError());
+    for (int trial = 1; trial < TEMPER_TRIALS; trial++) {
+        hipLaunchKernelGGL(filter_temper_sum_kernel, tiles, dim3(FILT_THREADS), 0, h->stream, w, (long long)mpp, (int)D, width,
+                           (long long)n_tiles, h->filt_Y.p, smax, h->filt_tstate.p, h->filt_tpart.p);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(filter_temper_decide_kernel, dim3((unsigned)P), dim3(FILT_THREADS), 0, h->stream, h->filt_tpart.p,
+                           3, (long long)n_tiles, 0, h->filt_floor, h->filt_tstate.p, h->filt_trials.p);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(filter_temper_apply_kernel, tiles, dim3(FILT_THREADS), 0, h->stream, w, (long long)mpp, (int)D, width,
+                       h->filt_Y.p, smax, h->filt_tstate.p, (unsigned long long)h->filt_seed, pbase, key, (unsigned)row,
+                       (long long)n_arow, (long long)slot, h->filt_qm.p, h->filt_qr.p, h->ftemp.buf.p);
+    HIP_TRY(hipGetLastError());
+    return HC_OK;
+}
+
 // The assimilation at the launch's last row (its water-table indices are wtd_u16's last row): weights, diagnostics and
 // draw per point, the member prefix scan, the slot fill, then psi and base gathered into the second buffers and swapped in.
 // hc_set_filter_shard: the handle's members are a part of a point of np members; the water-table indices of all of them
@@ -4103,6 +4480,8 @@ int assimilate(hc_handle *h, const Chunk &c)
     const long long *q = h->filt_q.p;
     if (s.ms > 0) {
         if (int rc = filter_member_weights(h, c, s, pbase, key)) return rc;
+        if (h->filt_floor > 0.0)
+            if (int rc = filter_temper(h, w, s.ms, mpp, n_tiles, row, pbase, key)) return rc;
         HIP_TRY(hipMemsetAsync(h->filt_q.p, 0, (size_t)(P * D) * 8, h->stream));
         w = nullptr;
         q = h->filt_qm.p;
@@ -4112,6 +4491,8 @@ int assimilate(hc_handle *h, const Chunk &c)
                            key, (unsigned)row, (long long)n_arow, (long long)slot, h->filt_q.p,
                            h->filt_qr.p, h->filt.buf.p, h->filt_surv.p);
         HIP_TRY(hipGetLastError());
+        if (h->filt_floor > 0.0)
+            if (int rc = filter_temper(h, w, 0, mpp, n_tiles, row, pbase, key)) return rc;
         if (h->fsm_n > 0) {
             if (h->filt_qm.ensure((size_t)N)) return HC_ERR_DEVICE;
             hipLaunchKernelGGL(filter_expand_weights_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, w,
@@ -4442,6 +4823,7 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
     const bool filt_on = h->filt_stride > 0 && !a->spinup;
     if (filt_on && (rc = ensure_filter(h))) return rc;
     if (filt_on && h->fsm_n > 0 && (rc = ensure_fsm(h))) return rc;
+    if (filt_on && h->filt_floor > 0.0 && (rc = ensure_ftemp(h))) return rc;
     const bool enkf_on = h->enkf_stride > 0 && !a->spinup;   // (the EnKF: spin-up solves are never analysed either)
     if (enkf_on && (rc = ensure_enkf(h))) return rc;
     if (enkf_on && h->sm_n > 0 && (rc = ensure_sm(h))) return rc;
@@ -5204,6 +5586,43 @@ int hc_set_filter_sm_stats(hc_handle *h, const double *table, int64_t n_entries)
     if (!h || !table) return fail(HC_ERR_ARG, "hc_set_filter_sm_stats: bad argument");
     return table_copy(h, h->fsm, ensure_fsm, hipMemcpyHostToDevice, const_cast<double *>(table), n_entries,
                       "hc_set_filter_sm_stats");
+}
+
+int hc_set_filter_tempering(hc_handle *h, double ess_floor)
+{
+    if (!h) return fail(HC_ERR_ARG, "hc_set_filter_tempering: bad argument");
+    if (ess_floor != 0.0 && !(std::isfinite(ess_floor) && ess_floor > 0.0 && ess_floor < 1.0))
+        return fail(HC_ERR_ARG, "hc_set_filter_tempering: ess_floor = %g must be 0 (off) or finite with 0 < f < 1", ess_floor);
+    if (ess_floor != 0.0 && h->filt_stride <= 0)
+        return fail(HC_ERR_ARG, "hc_set_filter_tempering: the particle filter is off (hc_set_filter comes first)");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    temper_off(h);
+    if (ess_floor == 0.0) return HC_OK;
+    h->filt_floor = ess_floor;
+    const int rc = ensure_ftemp(h);
+    if (rc != HC_OK) temper_off(h);              // refused: off
+    return rc;
+}
+
+int hc_get_filter_temper_stats(hc_handle *h, double *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_get_filter_temper_stats: bad argument");
+    return table_copy(h, h->ftemp, ensure_ftemp, hipMemcpyDeviceToHost, table, n_entries, "hc_get_filter_temper_stats");
+}
+
+int hc_set_filter_temper_stats(hc_handle *h, const double *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_set_filter_temper_stats: bad argument");
+    return table_copy(h, h->ftemp, ensure_ftemp, hipMemcpyHostToDevice, const_cast<double *>(table), n_entries,
+                      "hc_set_filter_temper_stats");
+}
+
+int hc_get_filter_temper_trials(hc_handle *h, int64_t *trials)
+{
+    if (h && h->filt_floor <= 0.0) return fail(HC_ERR_ARG, "hc_get_filter_temper_trials: the weights are not tempered");
+    return filter_hook(h, h->filt_trials, trials, h ? (size_t)h->n_points * TEMPER_TRIALS * TEMPER_WIDTH : 0,
+                       "hc_get_filter_temper_trials");
 }
 
 int hc_get_filter_sm_width(hc_handle *h, int32_t *width)

@@ -116,6 +116,9 @@ class _Run:
     filter_soil_moisture: a soil-moisture record (stepper.soil_moisture_record) that joins the well in the filter's
     weights, which then belong to a member and not to a 5 cm bin (include/hydrocol.h hc_set_filter_soil_moisture);
     :meth:`filter_sm_table`, the ``sm_*`` keys of :meth:`filter_summary`.
+    filter_ess_floor: 0 < f < 1 holds the effective sample size of every resampling above f times the counted members by
+    tempering the weights (include/hydrocol.h hc_set_filter_tempering); :meth:`filter_temper_table`, and
+    :meth:`filter_summary` gains ``beta``, ``ess_tempered``, ``ess_target`` and ``tempered_rows``.
     enkf_stride > 0: a stochastic ensemble Kalman filter on the well's continuous water table instead (``enkf_sigma_cm``:
     the observation error; ``enkf_localisation_cm``: the Gaspari-Cohn half-width, 0 = none; ``enkf_seed``: default the
     run's seed), with the same forecast / analysis order; :meth:`enkf_summary` (log marginal likelihood).
@@ -135,7 +138,8 @@ class _Run:
     def _start_tables(self, profile_stride, wtd_hist_stride, filter_stride=0, filter_sigma_cm=None, filter_seed=None,
                       enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None,
                       enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=(),
-                      filter_soil_moisture=None, theta_hist_bins=0, storage_layers_cm=None, storage_bins=0):
+                      filter_soil_moisture=None, theta_hist_bins=0, storage_layers_cm=None, storage_bins=0,
+                      filter_ess_floor=0.0):
         self.profile_stride = int(profile_stride)
         self.storage_layers_cm = None if storage_layers_cm is None or len(storage_layers_cm) == 0 else \
             np.asarray(storage_layers_cm, dtype=np.float64).reshape(-1, 2)
@@ -169,6 +173,11 @@ class _Run:
                 raise ValueError("filter_soil_moisture needs the particle filter (filter_stride > 0)")
             sm = filter_soil_moisture
             self.stepper.set_filter_soil_moisture(sm["nodes"], sm["values"], sm["sigma"])
+        self.filter_ess_floor = float(filter_ess_floor or 0.0)
+        if self.filter_ess_floor:
+            if not self.filter_stride:
+                raise ValueError("filter_ess_floor needs the particle filter (filter_stride > 0)")
+            self.stepper.set_filter_tempering(self.filter_ess_floor)
         self.enkf_stride = int(enkf_stride or 0)
         self.enkf_sigma_cm = float(enkf_sigma_cm) if self.enkf_stride else None
         self.enkf_localisation_cm = float(enkf_localisation_cm or 0.0) if self.enkf_stride else None
@@ -301,13 +310,22 @@ class _Run:
         """[n_arow][4] float64 (count, ESS, log-likelihood increment, survivors per assimilation slot); a sweep: [P][n_arow][4]."""
         return self.stepper.filter_table().reshape(self._lead + (-1, 4))
 
-    def filter_summary(self, table=None, sm_table=None):
+    def filter_temper_table(self):
+        """[n_arow][4] float64 (beta, the ESS at beta, the target, the trials; include/hydrocol.h
+        hc_set_filter_tempering); a sweep: [P][n_arow][4]."""
+        return self.stepper.filter_temper_table().reshape(self._lead + (-1, 4))
+
+    def filter_summary(self, table=None, sm_table=None, temper_table=None):
         """The filter's record (stepper.filter_summary): ``rows``, ``count``, ``ess``, ``loglik_rows``, ``survivors`` over
         the assimilated rows and ``loglik``, the log marginal likelihood of the well record (log cm^-1 summed over the rows),
         with a leading [P] for a sweep; ``table``: e.g. the one assembled over ranks.  With a soil-moisture record the
-        increments of the sensor rows are the joint ones, and the ``sm_*`` keys of :meth:`filter_sm_summary` come along."""
+        increments of the sensor rows are the joint ones, and the ``sm_*`` keys of :meth:`filter_sm_summary` come along.
+        With ``filter_ess_floor`` the tempering's ``beta``, ``ess_tempered``, ``ess_target`` and ``tempered_rows`` too
+        (``temper_table``: as ``table``)."""
         t = self.filter_table() if table is None else table
-        out = filter_summary(t, self.filter_stride, self.filter_sigma_cm)
+        if getattr(self, "filter_ess_floor", 0.0) and temper_table is None:      # (0.0: a run started without the setting)
+            temper_table = self.filter_temper_table()
+        out = filter_summary(t, self.filter_stride, self.filter_sigma_cm, temper_table=temper_table)
         if self.filter_soil_moisture is not None:
             out.update(("sm_" + k, v) for k, v in self.filter_sm_summary(sm_table).items())
         return out
@@ -391,7 +409,7 @@ class EnsembleSimulation(_Run):
                  enkf_seed=None, enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0,
                  enkf_window_offsets=(), enkf_shard=None, filter_shard=None, filter_soil_moisture=None,
                  theta_hist_bins=0, storage_layers_cm=None, storage_bins=0, period_ends=None, period_thresholds_cm=(),
-                 period_bins=0, period_flux_max_cm=(16.0, 4.0)):
+                 period_bins=0, period_flux_max_cm=(16.0, 4.0), filter_ess_floor=0.0):
         if filter_shard is not None and period_ends is not None and len(period_ends):
             raise ValueError("period_ends and filter_shard exclude each other: the sharded filter routes the members' "
                              "columns, which do not carry the period accumulators")
@@ -407,7 +425,7 @@ class EnsembleSimulation(_Run):
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
                            enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins, storage_layers_cm,
-                           storage_bins)
+                           storage_bins, filter_ess_floor)
         self._start_periods(period_ends, period_thresholds_cm, period_bins, period_flux_max_cm)
         self.enkf_shard = None
         if enkf_shard is not None:
@@ -549,6 +567,9 @@ class EnsembleSimulation(_Run):
             if self.filter_soil_moisture is not None:     # the record itself is supplied again at restore
                 arrays["filter_sm_nodes"] = np.asarray(self.filter_soil_moisture["nodes"], dtype=np.int32)
                 arrays["filter_sm_table"] = self.stepper.filter_sm_table()
+            if self.filter_ess_floor:                     # (an untempered run keeps its key set)
+                arrays["filter_ess_floor"] = np.array(self.filter_ess_floor, dtype=np.float64)
+                arrays["filter_temper_table"] = self.stepper.filter_temper_table()
         if self.enkf_stride:
             arrays["enkf_stride"] = np.array(self.enkf_stride, dtype=np.int64)
             arrays["enkf_sigma_cm"] = np.array(self.enkf_sigma_cm, dtype=np.float64)
@@ -601,6 +622,9 @@ class EnsembleSimulation(_Run):
         filt = int(data["filter_stride"]) if "filter_stride" in data else 0
         fkw = dict(filter_stride=filt, filter_sigma_cm=float(data["filter_sigma_cm"]),
                    filter_seed=int(data["filter_seed"])) if filt else {}
+        tempered = bool(filt) and "filter_ess_floor" in data
+        if tempered:
+            fkw.update(filter_ess_floor=float(data["filter_ess_floor"]))
         periods = "period_ends" in data
         if periods:
             fkw.update(period_ends=np.asarray(data["period_ends"], dtype=np.int64).reshape(-1),
@@ -642,6 +666,8 @@ class EnsembleSimulation(_Run):
             sim.stepper.set_filter_base(np.asarray(data["filter_base"], dtype=np.float64).reshape(n, D))
             if has_fsm:
                 sim.stepper.set_filter_sm_table(np.asarray(data["filter_sm_table"], dtype=np.float64))
+            if tempered:
+                sim.stepper.set_filter_temper_table(np.asarray(data["filter_temper_table"], dtype=np.float64))
         else:
             sim.stepper.set_noise_scale(np.asarray(data["noise_scale"], dtype=float).reshape(n))
         if enkf:
@@ -764,7 +790,7 @@ class SweepSimulation(_Run):
                  filter_seed=None, enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None,
                  enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=(),
                  filter_soil_moisture=None, theta_hist_bins=0, storage_layers_cm=None, storage_bins=0, period_ends=None,
-                 period_thresholds_cm=(), period_bins=0, period_flux_max_cm=(16.0, 4.0)):
+                 period_thresholds_cm=(), period_bins=0, period_flux_max_cm=(16.0, 4.0), filter_ess_floor=0.0):
         self.points = list(cols_list)
         self.P, self.n = len(self.points), int(n_members)
         self._lead = (self.P,)
@@ -794,7 +820,7 @@ class SweepSimulation(_Run):
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
                            enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins, storage_layers_cm,
-                           storage_bins)
+                           storage_bins, filter_ess_floor)
         self._start_periods(period_ends, period_thresholds_cm, period_bins, period_flux_max_cm)
         self.next_row, self.kernel_ms, self.launches = 1, 0.0, 0
 

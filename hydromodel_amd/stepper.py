@@ -82,6 +82,7 @@ class EnsembleStepper:
         self.period_bins, self.period_flux_max_log2 = 0, (0, 0)
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = 0, 0.0, 0
         self.filter_sm_nodes = None
+        self.filter_ess_floor = 0.0
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
         self.enkf_sm_nodes = None
         self.enkf_method, self.enkf_relaxation = "stochastic", 0.0
@@ -581,6 +582,7 @@ class EnsembleStepper:
         #                                                                            and leaves it off if it refuses
         self.filter_shard, self._filter_shard_keep = None, None                  # ... and the sharding with it
         self.filter_sm_nodes = None                                              # ... and the sensor record
+        self.filter_ess_floor = 0.0                                              # ... and the tempering
         L.check(self.lib.hc_set_filter(self.h, stride, sigma, int(seed) & 0xFFFFFFFFFFFFFFFF))
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = stride, sigma, int(seed)
 
@@ -588,6 +590,7 @@ class EnsembleStepper:
         """The library turned the filters off (a new noise source or new point keys, include/hydrocol.h): so does this side."""
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = 0, 0.0, 0
         self.filter_sm_nodes = None
+        self.filter_ess_floor = 0.0
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
         self.enkf_sm_nodes = None
         self.enkf_method, self.enkf_relaxation = "stochastic", 0.0
@@ -635,6 +638,37 @@ class EnsembleStepper:
         """[P] int64: the systematic offset r of the last assimilation (test hook)."""
         out = np.zeros(self.P, dtype=np.int64)
         L.check(self.lib.hc_get_filter_draw(self.h, L.lptr(out)))
+        return out
+
+    # -- tempered weights (include/hydrocol.h hc_set_filter_tempering) ---------------------------------------------------
+    def set_filter_tempering(self, ess_floor):
+        """Hold the effective sample size of every resampling above ``ess_floor`` (a fraction of the counted members,
+        0 < f < 1; 0 = off): the weights are raised to the largest exponent beta = k / 1024 of a bisection that keeps it
+        there.  The filter's table keeps scoring the forecast with the stated error.  The filter must be on
+        (:meth:`set_filter` first; it removes the tempering again)."""
+        f = float(ess_floor)
+        if f != 0.0 and not (np.isfinite(f) and 0.0 < f < 1.0):
+            raise ValueError(f"filter ess_floor = {ess_floor!r} must be 0 (off) or finite with 0 < f < 1")
+        self.filter_ess_floor = 0.0
+        L.check(self.lib.hc_set_filter_tempering(self.h, f))
+        self.filter_ess_floor = f
+
+    def filter_temper_table(self):
+        """[P][n_arow][4] float64: beta, the ESS at beta, the target T and the trials evaluated per assimilation slot (NaN
+        where nothing was assimilated or no member was counted)."""
+        t = np.zeros((self.P, stride_rows(self.T, self.filter_stride), TEMPER_WIDTH))
+        L.check(self.lib.hc_get_filter_temper_stats(self.h, L.dptr(t), t.size))
+        return t
+
+    def set_filter_temper_table(self, table):
+        t = L.as_f64(table).reshape(-1)
+        L.check(self.lib.hc_set_filter_temper_stats(self.h, L.dptr(t), t.size))
+
+    def filter_temper_trials(self):
+        """[P][11][4] int64: {k, Q_k, S_k low word, S_k high word} of the last assimilation's trials in trial order,
+        unused rows k = -1 (test hook)."""
+        out = np.zeros((self.P, TEMPER_TRIALS, TEMPER_WIDTH), dtype=np.int64)
+        L.check(self.lib.hc_get_filter_temper_trials(self.h, L.lptr(out)))
         return out
 
     # -- soil-moisture sensors in the particle filter (include/hydrocol.h hc_set_filter_soil_moisture) -------------------
@@ -1758,10 +1792,77 @@ def filter_routes(ancestors, bounds):
     return send, recv
 
 
-def filter_summary(table, stride, sigma_cm):
+# ---- tempered weights on the host (include/hydrocol.h hc_set_filter_tempering) -----------------------------------------
+TEMPER_STEPS = 1024
+TEMPER_TRIALS = 11
+TEMPER_WIDTH = 4
+
+
+def filter_temper_target(ess_floor, n):
+    """T = min(n, max(1, ceil(f n))), the product in fp64 as the device forms it."""
+    n = int(n)
+    return min(n, max(1, int(np.ceil(np.float64(ess_floor) * np.float64(n)))))
+
+
+def filter_temper_ok(Q, S, T):
+    """Q^2 >= T S in Python integers."""
+    return int(Q) * int(Q) >= int(T) * int(S)
+
+
+def filter_temper_weights(l, counted, k):
+    """[n] int64 q(k) = floor(2^31 exp((k / 1024) (l - s))) of the counted entries (s = their largest l), 0 elsewhere:
+    the difference and the product rounded once each."""
+    l = np.asarray(l, dtype=np.float64).reshape(-1)
+    counted = np.asarray(counted, dtype=bool).reshape(-1)
+    q = np.zeros(l.size, dtype=np.int64)
+    if counted.any():
+        d = l[counted] - l[counted].max()
+        a = np.float64(int(k) / TEMPER_STEPS) * d
+        with np.errstate(under="ignore"):
+            q[counted] = np.floor(np.float64(FILTER_Q_ONE) * np.exp(a)).astype(np.int64)
+    return q
+
+
+def filter_temper_of(l, counted, ess_floor, n_b=None):
+    """The tempering of one point's weights restated with NumPy and Python integers: ``l`` the log-likelihoods (per
+    member, or per bin with the bin counts ``n_b``), ``counted`` which of them count (a bin: n_b > 0).  Returns
+    ``(k, trials, q)``: the procedure's k (beta = k / 1024), its trials ``[(k, Q_k, S_k), ...]`` in order and the weights
+    q(k) [n] int64; ``(None, [], zeros)`` when nothing is counted (the row is not tempered)."""
+    l = np.asarray(l, dtype=np.float64).reshape(-1)
+    counted = np.asarray(counted, dtype=bool).reshape(-1)
+    mult = [1] * l.size if n_b is None else [int(v) for v in np.asarray(n_b).reshape(-1)]
+    n = sum(m for m, c in zip(mult, counted) if c)
+    if n == 0:
+        return None, [], np.zeros(l.size, dtype=np.int64)
+    T = filter_temper_target(ess_floor, n)
+    trials = []
+
+    def ok(k):
+        q = [int(v) for v in filter_temper_weights(l, counted, k)]
+        Q = sum(m * v for m, v in zip(mult, q))
+        S = sum(m * v * v for m, v in zip(mult, q))
+        trials.append((k, Q, S))
+        return filter_temper_ok(Q, S, T)
+
+    k = TEMPER_STEPS
+    if not ok(TEMPER_STEPS):
+        lo, hi = 0, TEMPER_STEPS
+        while hi - lo > 1:
+            mid = (lo + hi) >> 1
+            if ok(mid):
+                lo = mid
+            else:
+                hi = mid
+        k = lo
+    return k, trials, filter_temper_weights(l, counted, k)
+
+
+def filter_summary(table, stride, sigma_cm, temper_table=None):
     """The filter's record from its [..., n_arow, 4] table: ``rows`` (forcing row of every assimilated slot), ``count``,
     ``ess``, ``loglik_rows`` (the increments), ``survivors`` [..., R] over the slots any point assimilated, and ``loglik``
-    [...] = the sum of the increments in row order; ``stride``, ``sigma_cm``."""
+    [...] = the sum of the increments in row order; ``stride``, ``sigma_cm``.  With the tempering's table
+    (``temper_table`` [..., n_arow, 4]) also ``beta``, ``ess_tempered``, ``ess_target`` [..., R] and ``tempered_rows``
+    [...] = the rows resampled with beta < 1."""
     t = np.asarray(table, dtype=np.float64)
     used = (t[..., 0] > 0).reshape(-1, t.shape[-2]).any(axis=0)
     slots = np.flatnonzero(used)
@@ -1770,9 +1871,15 @@ def filter_summary(table, stride, sigma_cm):
     loglik = np.zeros(inc.shape[:-1])
     for j in range(inc.shape[-1]):                      # row order
         loglik = loglik + np.where(sel[..., j, 0] > 0, inc[..., j], 0.0)
-    return {"rows": slots.astype(np.int64) * int(stride), "count": sel[..., 0].astype(np.int64), "ess": sel[..., 1],
-            "loglik_rows": inc, "survivors": np.nan_to_num(sel[..., 3]).astype(np.int64),
-            "loglik": loglik if loglik.ndim else float(loglik), "stride": int(stride), "sigma_cm": float(sigma_cm)}
+    out = {"rows": slots.astype(np.int64) * int(stride), "count": sel[..., 0].astype(np.int64), "ess": sel[..., 1],
+           "loglik_rows": inc, "survivors": np.nan_to_num(sel[..., 3]).astype(np.int64),
+           "loglik": loglik if loglik.ndim else float(loglik), "stride": int(stride), "sigma_cm": float(sigma_cm)}
+    if temper_table is not None:
+        tt = np.asarray(temper_table, dtype=np.float64)[..., slots, :]
+        tempered = (tt[..., 0] < 1.0).sum(axis=-1)
+        out.update(beta=tt[..., 0], ess_tempered=tt[..., 1], ess_target=tt[..., 2],
+                   tempered_rows=tempered if tempered.ndim else int(tempered))
+    return out
 
 
 # ---- ensemble Kalman filter on the host (include/hydrocol.h hc_set_enkf) -----------------------------------------------

@@ -56,6 +56,7 @@
  *                         ensemble's mean, sigma and histograms
  *   hc_set_filter, hc_get/set_filter_stats, hc_get/set_filter_base, hc_get_filter_ancestors/weights/draw,
  *   hc_set_filter_soil_moisture, hc_get/set_filter_sm_stats, hc_get_filter_sm_width/member_weights/loglik/sm_theta
+ *   hc_set_filter_tempering, hc_get/set_filter_temper_stats, hc_get_filter_temper_trials
  *                      <- (new) the ensemble conditioned on wtd_obs (src/simulation.py:582-612): a bootstrap particle filter,
  *                         and the log marginal likelihood of the well record per parameter point
  *   hc_set_enkf, hc_get/set_enkf_stats, hc_get_enkf_gain/y/eps
@@ -534,6 +535,44 @@ int hc_set_filter_base(hc_handle *h, const double *base);
 int hc_get_filter_ancestors(hc_handle *h, int64_t *ancestors);
 int hc_get_filter_weights(hc_handle *h, int64_t *q);
 int hc_get_filter_draw(hc_handle *h, int64_t *r);
+
+/* Tempered weights: hold the effective sample size of every resampling above a floor (Poterjoy's beta-regularisation of
+ * the localised particle filter, 2016 / 2019; equivalently the observation error inflated by 1 / sqrt(beta), per row and
+ * point).  On an assimilation row the weight kernels above (or the sensor rows' below) run first and are untouched: count
+ * n, s, l_b per occupied bin (l_m per counted member on a sensor row), q at beta = 1, and entries 0-2 of the filter's
+ * table -- count, ESS and increment stay those of the stated observation error, so the log-likelihood stays comparable
+ * between tempered and untempered runs.  Entry 3 (survivors) counts the resampling that actually happened.  Then, per
+ * parameter point, in exact integers but for the exp of a weight:
+ *   T = min(n, max(1, (int64) ceil(ess_floor * (double) n)));
+ *   for k in 0 ... 1024, beta_k = k / 1024 (exact): q(k) = floor(2^31 * exp(beta_k * (l - s))) for a counted member or an
+ *   occupied bin -- l - s and the product each rounded once, no contraction -- and 0 otherwise; q(1024) are the bits above;
+ *   Q_k = sum q(k), S_k = sum q(k)^2 over the members (a bin counts n_b times): Q_k exact in 64 bits, S_k in 128;
+ *   ok(k) <=> Q_k * Q_k >= T * S_k, both sides exact in 128 bits (Q_k < 2^62, T < 2^31, S_k < 2^93); ok(0) always holds.
+ *   Trial 0 is k = 1024: if ok, beta = 1 and nothing is rewritten -- the weights, {Q, r}, the ancestry and everything
+ *   downstream are the untempered run's bits.  Otherwise lo = 0, hi = 1024 and, while hi - lo > 1: mid = (lo + hi) >> 1;
+ *   ok(mid) ? lo = mid : hi = mid -- ten more trials (512, ...) -- and k = lo.  k is DEFINED as the outcome of this
+ *   procedure (the floors make ESS(beta) not strictly monotone).
+ *   k < 1024: the point's weights become q(k) (the bin table q_b, or q_m of a sensor row) and its draw
+ *   {Q_k, floor(x * Q_k / 2^64)} with the same Philox value x (same counter: no new randomness); the prefix scan, the slot
+ *   fill, the survivors, the gather, the sharded routing, the period accumulators' gather and the sensors' posterior moments
+ *   run on these values as they run without tempering.  k = 0: the observation is ignored on that row.  exp(l_m - s) of a
+ *   sensor row (hc_get_filter_loglik's neighbour column, the source of W) is not rewritten.
+ *   A row with n = 0 is not tempered.  k depends on no launch length, member split, point order or rank count.
+ *   The table, float64 [P][n_arow][4] per point and slot: beta = k / 1024; the ESS at beta = Q_k^2 / S_k (the quotient of
+ *   the filter's table; at beta = 1 that table's ESS to the bit); T; the trials evaluated (1 or 11).  Slots without an
+ *   assimilation and rows that were not tempered hold NaN.
+ * hc_set_filter_tempering: ess_floor = 0 turns tempering off (the default: nothing is launched or allocated); otherwise
+ *   finite with 0 < ess_floor < 1 (HC_ERR_ARG else) and the particle filter on (hc_set_filter first).  Whatever turns the
+ *   filter off removes it, hc_set_filter included.  Valid with a soil-moisture record, a sweep, either noise source, period
+ *   totals and hc_set_filter_shard (every handle runs the same kernels on the same gathered indices and finds the same k).
+ * hc_get/set_filter_temper_stats: the table (P n_arow 4 entries; checkpoints, the assembly of a sweep over ranks).
+ * Test hook of the last assimilation: hc_get_filter_temper_trials, int64 [P][11][4] = {k, Q_k, S_k low word, S_k high
+ *   word} in trial order, unused rows k = -1 (a row that was not tempered: all of them).  hc_get_filter_weights,
+ *   hc_get_filter_member_weights and hc_get_filter_draw return what the resampling used. */
+int hc_set_filter_tempering(hc_handle *h, double ess_floor);
+int hc_get_filter_temper_stats(hc_handle *h, double *table, int64_t n_entries);
+int hc_set_filter_temper_stats(hc_handle *h, const double *table, int64_t n_entries);
+int hc_get_filter_temper_trials(hc_handle *h, int64_t *trials);
 
 /* Soil-moisture sensors in the particle filter: a record of volumetric water content at up to 8 depth nodes joins the well
  * in the weights, which then belong to a member and not to a bin.  values [n_forcing_rows][n_sensors], NaN = no observation

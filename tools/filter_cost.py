@@ -2,7 +2,7 @@
 assimilations every 48th row (one a day), one handle each, back to back on one GPU.
 
     python tools/filter_cost.py [--members 262144] [--depth 300] [--days 30] [--warmup 1] [--strides 0,48]
-                                [--sigma 10] [--spread-cm 0] [--sensors 0,0] [--json out.json]
+                                [--sigma 10] [--spread-cm 0] [--sensors 0,0] [--ess-floor 0,0.5] [--json out.json]
 
 Same set-up as tools/wtd_dist_cost.py and bench.py's timed region: synthetic 10-year forcing, Philox noise, the shared
 initial condition of the well's digest (tests/golden/g1_tables_<depth>.npz where it exists, else the hydrostatic profile),
@@ -15,7 +15,10 @@ run's rate over the mean of the stride-0 runs.  --spread-cm W starts every membe
 own offset, uniform over +-W cm: water tables in many bins, unequal weights, and (small sigma) the weight on a few members
 whose slot ranges are long.  --sensors lists, run by run like --strides, how many soil-moisture sensors join the well
 (hc_set_filter_soil_moisture: nodes 6, 12, 24, ..., a reading of 0.25 with error --sensor-sigma on every assimilation row,
-so every assimilation takes the per-member path).  Prints one JSON line.
+so every assimilation takes the per-member path; one count serves every run).  --ess-floor lists, run by run, the floor
+of the tempered weights (hc_set_filter_tempering; 0 = off, the untempered path): `tempered_rows` and `beta_min` over the
+timed assimilations, and -- when no run has stride 0 -- `kept` and `temper_ms_per_assimilation` are taken against the
+mean of the runs with floor 0.  Prints one JSON line.
 """
 import argparse
 import json
@@ -30,7 +33,7 @@ sys.path.insert(0, str(REPO))
 
 
 def run(cols, forcing, psi0, members, stride, sigma, warmup_days, days, spread_cm=0.0, seed=2024, sensors=0,
-        sensor_sigma=0.05):
+        sensor_sigma=0.05, ess_floor=0.0):
     from hydromodel_amd.stepper import EnsembleStepper, filter_summary
     st = EnsembleStepper(cols, forcing, members)
     try:
@@ -46,6 +49,8 @@ def run(cols, forcing, psi0, members, stride, sigma, warmup_days, days, spread_c
             values = np.full((forcing.dim_t, sensors), np.nan)
             values[::stride] = 0.25
             st.set_filter_soil_moisture([6 * (1 << i) for i in range(sensors)], values, sensor_sigma)
+        if stride and ess_floor:
+            st.set_filter_tempering(ess_floor)
         row = 1
         if warmup_days:
             st.step_rows(row, 48 * warmup_days)
@@ -55,7 +60,7 @@ def run(cols, forcing, psi0, members, stride, sigma, warmup_days, days, spread_c
         out = st.step_rows(row, 48 * days)
         st.lib.hc_synchronize(st.h)
         wall = time.perf_counter() - t0
-        rec = {"stride": stride, "sensors": sensors if stride else 0, "wall_s": wall, "step_kernel_ms": out["kernel_ms"], "launches": out["launches"],
+        rec = {"stride": stride, "sensors": sensors if stride else 0, "ess_floor": ess_floor if stride else 0.0, "wall_s": wall, "step_kernel_ms": out["kernel_ms"], "launches": out["launches"],
                "other_ms": 1e3 * wall - out["kernel_ms"], "column_days_per_s": members * days / wall}
         if stride:
             s = filter_summary(st.filter_table()[0], stride, sigma)
@@ -64,6 +69,10 @@ def run(cols, forcing, psi0, members, stride, sigma, warmup_days, days, spread_c
             rec["ess_median"] = float(np.median(s["ess"][timed])) if timed.any() else None
             rec["survivors_median"] = float(np.median(s["survivors"][timed])) if timed.any() else None
             rec["loglik"] = s["loglik"]
+            if ess_floor:
+                beta = st.filter_temper_table()[0, s["rows"] // stride, 0][timed]
+                rec["tempered_rows"] = int((beta < 1.0).sum())
+                rec["beta_min"] = float(np.nanmin(beta)) if timed.any() else None
             if timed.any():
                 rec["longest_range"] = int(np.bincount(st.filter_ancestors(), minlength=members).max())   # the last one
         return rec
@@ -83,6 +92,7 @@ def main():
     ap.add_argument("--spread-cm", type=float, default=0.0)
     ap.add_argument("--sensors", default="")
     ap.add_argument("--sensor-sigma", type=float, default=0.05)
+    ap.add_argument("--ess-floor", default="")
     ap.add_argument("--json", default="")
     args = ap.parse_args()
     from hydromodel_amd.digest import ColumnTables, ForcingDigest
@@ -95,10 +105,15 @@ def main():
     psi0 = np.load(fixture)["initial_cond"] if fixture.exists() else pressure_head(cols, cols.por_raw)[0]
     strides = [int(s) for s in args.strides.split(",")]
     sensors = [int(s) for s in args.sensors.split(",")] if args.sensors else [0] * len(strides)
+    if len(sensors) == 1:
+        sensors = sensors * len(strides)
     if len(sensors) != len(strides):
         ap.error("--sensors lists one count per entry of --strides")
+    floors = [float(s) for s in args.ess_floor.split(",")] if args.ess_floor else [0.0] * len(strides)
+    if len(floors) != len(strides):
+        ap.error("--ess-floor lists one floor per entry of --strides")
     recs = [run(cols, forcing, psi0, args.members, s, args.sigma, args.warmup, args.days, args.spread_cm, sensors=n,
-                sensor_sigma=args.sensor_sigma) for s, n in zip(strides, sensors)]
+                sensor_sigma=args.sensor_sigma, ess_floor=f) for s, n, f in zip(strides, sensors, floors)]
     base = [r for r in recs if r["stride"] == 0]
     if base:
         rate = float(np.mean([r["column_days_per_s"] for r in base]))
@@ -107,6 +122,15 @@ def main():
             r["kept"] = r["column_days_per_s"] / rate
             if r["stride"] and r.get("assimilations"):
                 r["filter_ms_per_assimilation"] = (r["other_ms"] - other) / r["assimilations"]
+    untempered = [r for r in recs if r["stride"] and not r["ess_floor"]]
+    if not base and untempered:
+        rate = float(np.mean([r["column_days_per_s"] for r in untempered]))
+        other = float(np.mean([r["other_ms"] for r in untempered]))
+        for r in recs:
+            r["kept"] = r["column_days_per_s"] / rate
+            r["other_ms_per_assimilation"] = r["other_ms"] / max(r.get("assimilations", 0), 1)
+            if r["ess_floor"] and r.get("assimilations"):
+                r["temper_ms_per_assimilation"] = (r["other_ms"] - other) / r["assimilations"]
     line = json.dumps({"members": args.members, "depth": args.depth, "days": args.days, "sigma_cm": args.sigma, "spread_cm": args.spread_cm,
                        "runs": recs})
     print(line)
