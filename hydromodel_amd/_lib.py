@@ -145,6 +145,12 @@ EXPORTS = {
     "hc_get_filter_member_weights": ([C.c_void_p, _lp], C.c_int),
     "hc_get_filter_loglik": ([C.c_void_p, _dp], C.c_int),
     "hc_get_filter_sm_theta": ([C.c_void_p, _dp], C.c_int),
+    "hc_set_filter_window": ([C.c_void_p, C.c_int32, _ip], C.c_int),
+    "hc_get_filter_window_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),
+    "hc_set_filter_window_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),
+    "hc_get_filter_window_capture": ([C.c_void_p, _ip, _lp], C.c_int),
+    "hc_set_filter_window_capture": ([C.c_void_p, _ip, _lp], C.c_int),
+    "hc_get_filter_window_width": ([C.c_void_p, _ip, _ip], C.c_int),
     "hc_set_filter_tempering": ([C.c_void_p, C.c_double], C.c_int),
     "hc_get_filter_temper_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),
     "hc_set_filter_temper_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),

@@ -102,6 +102,15 @@ unknown keys, only membership of the 12 is checked):
   happened.  With ``Soil_Moisture``, ``Sharded``, a sweep and either noise source.  Added to the file: ``filter_ess_floor``
   and, over the ``filter_rows`` ``[R]``, ``filter_beta``, ``filter_ess_tempered``, ``filter_ess_target`` (a sweep: a leading
   ``[P]`` axis), and the run ends with `` [Ensemble xN] filter tempering: K of R rows tempered, smallest beta = ...``.
+* ``"Filter": {..., "Window_Offsets": [12, 24, 36]}``: the well's record inside the window (include/hydrocol.h
+  hc_set_filter_window), the counterpart of ``EnKF.Window_Offsets`` with its rules.  Each entry is a number of rows before
+  the assimilation row; nothing is resampled in between, so every member's weight becomes the likelihood of all the
+  observations its trajectory passed, and ``filter_loglik_rows`` the joint increment.  Not together with ``"Sharded": true``
+  on a single-point run (the sharded filter gathers the indices of the assimilation row only).  Without the key, or with an
+  empty list, nothing changes.  Added to the file: ``filter_window_offsets`` ``[n]`` (ascending) and, over the
+  ``filter_rows`` ``[R]``, ``filter_window_observed``, ``filter_window_obs_cm``, ``filter_window_prior_mean_cm``,
+  ``filter_window_prior_std_cm`` ``[R][n]`` (NaN where the offset's row took no part; a sweep: a leading ``[P]`` axis), and
+  the run ends with `` [Ensemble xN] filter window: K lagged observations over R rows``.
 * ``"Filter": {..., "Soil_Moisture": {"Filename": "sm.csv", "Depths_cm": [30, 60, 120], "Sigma": 0.02}}``: a soil-moisture
   record joins the well in the filter's weights (include/hydrocol.h hc_set_filter_soil_moisture): on a row with sensor
   values every member is weighted by the joint Gaussian likelihood of the well and of theta at the sensors' nodes, so the
@@ -222,6 +231,7 @@ def main(params_file=None, data_file=None, seed=None, device=0, gpus=None, _sett
             soil_moisture_settings(params["Ensemble"], n_gpus, "Filter")
             enkf_method_settings(params["Ensemble"])
             enkf_window_settings(params["Ensemble"])
+            filter_window_settings(params["Ensemble"])
         ranks = multigpu.Ranks(expect=n_gpus if (n_gpus > 1 or multigpu.in_rank()) else None)
         if ranks.world > 1:
             device = ranks.device_index()
@@ -288,6 +298,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     fsm = soil_moisture_settings(ens, ranks.world, "Filter")
     scheme = enkf_method_settings(ens)
     window = enkf_window_settings(ens)
+    fwindow = filter_window_settings(ens)
     cols = ColumnTables(params, load_site_well(params))
     forcing = ForcingDigest(params, water_data, cols)
     record = soil_moisture_record_of(sm, cols, water_data)      # before any GPU call
@@ -301,7 +312,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     plan = period_plan(periods, cols, forcing, rows)            # before any GPU call, like the storage's ranges
     if ens.get("Points"):
         return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels, filt,
-                          enkf, record, scheme, window, frecord, theta, storage, periods, plan, ess_floor)
+                          enkf, record, scheme, window, frecord, theta, storage, periods, plan, ess_floor, fwindow)
     sharded = enkf_sharded(ens)
     fsharded = filter_sharded(ens)
     if sharded:
@@ -323,7 +334,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
                              noise=str(ens.get("Noise", "philox")).lower(),
                              spinup=str(ens.get("Spinup", "shared")).lower(), profile_stride=stride,
                              wtd_hist_stride=dist_stride, theta_hist_bins=theta[0],
-                             **_filter_kwargs(filt, frecord, ess_floor),
+                             **_filter_kwargs(filt, frecord, ess_floor, fwindow),
                              **_enkf_kwargs(enkf, record, scheme, window), **_storage_kwargs(storage),
                              **_period_kwargs(periods, plan), **shard_kw)
     label = f"Ensemble x{n_members}"
@@ -369,6 +380,9 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     fstables, fsm_line = _reduce_sm(ranks, sim, eids, 1, forcing.dim_t, filt[0], frecord, label, keep_points=False,
                                     owner="filter")
     extra.update(fstables)
+    fwtables, fwindow_line = _reduce_filter_window(ranks, sim, eids, 1, forcing.dim_t, filt, fwindow, label,
+                                                   keep_points=False, z0_cm=cols.z[0])
+    extra.update(fwtables)
     if fsharded is not None:
         extra["filter_sharded"] = np.array(1 if fsharded else 0, dtype=np.int8)
     etables, enkf_line = _reduce_enkf(ranks, sim, eids, 1, forcing.dim_t, enkf, label, keep_points=False,
@@ -391,6 +405,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
         print(filter_line)
     if fsm_line:
         print(fsm_line)
+    if fwindow_line:
+        print(fwindow_line)
     if enkf_line:
         print(enkf_line)
     if sm_line:
@@ -668,18 +684,21 @@ def _period_kwargs(periods, plan):
     return kw
 
 
-FILTER_KEYS = ("Stride", "Sigma_cm", "Seed", "Sharded", "Soil_Moisture", "ESS_floor")
+FILTER_KEYS = ("Stride", "Sigma_cm", "Seed", "Sharded", "Soil_Moisture", "ESS_floor", "Window_Offsets")
 
 
 def filter_settings(ens, n_gpus=1):
     """Ensemble.Filter -> (stride, sigma_cm, seed or None = the ensemble's seed); (0, None, None) when absent or off.  Pure:
     runs before any GPU call, and a bad value is a ValueError (message + exit status 1).  A single-point ensemble on more
     than one GPU is refused -- resampling would have to move states between ranks -- unless the block says
-    ``"Sharded": true`` (:func:`filter_sharded`).  ``ESS_floor`` (:func:`filter_ess_floor`) is checked here too."""
+    ``"Sharded": true`` (:func:`filter_sharded`).  ``ESS_floor`` (:func:`filter_ess_floor`) is checked here too;
+    ``Window_Offsets`` by :func:`filter_window_settings`."""
     import math
     from numbers import Integral, Real
     if "ESS_floor" in ens:
         raise ValueError(" Ensemble: ESS_floor belongs inside the \"Filter\" block.")
+    if "Window_Offsets" in ens:
+        raise ValueError(" Ensemble: Window_Offsets belongs inside the \"Filter\" or the \"EnKF\" block.")
     block = ens.get("Filter")
     if block is None:
         return 0, None, None
@@ -728,6 +747,62 @@ def filter_ess_floor(ens):
     if not isinstance(block, dict) or "ESS_floor" not in block:
         return None
     return float(block["ESS_floor"])
+
+
+def filter_window_settings(ens):
+    """Ensemble.Filter.Window_Offsets -> the offsets as an ascending tuple, or None when the key is absent or the list empty
+    (the run, its file and its lines are then those of a block without it).  Pure, like :func:`filter_settings`: a bad
+    value is a ValueError (message + exit status 1), by the rules and in the words of :func:`enkf_window_settings`.  Needs
+    an active filter; refused together with ``"Sharded": true`` on a single-point run."""
+    from numbers import Real
+    from .stepper import filter_window_settings as window_of
+    if "Window_Offsets" in ens:
+        raise ValueError(" Ensemble: Window_Offsets belongs inside the \"Filter\" or the \"EnKF\" block.")
+    block = ens.get("Filter")
+    if not isinstance(block, dict) or block.get("Window_Offsets") is None:
+        return None
+    stride = block.get("Stride", 48)
+    stride = int(stride) if isinstance(stride, Real) and not isinstance(stride, bool) and stride == int(stride) else 0
+    if not stride:
+        raise ValueError(" Ensemble: Filter.Window_Offsets needs an active filter (Filter.Stride > 0).")
+    sm = block.get("Soil_Moisture")
+    depths = sm.get("Depths_cm") if isinstance(sm, dict) else None
+    try:
+        off = window_of(block["Window_Offsets"], stride, len(depths) if isinstance(depths, (list, tuple)) else 0)
+    except ValueError as bad:
+        raise ValueError(f" Ensemble: {bad}.") from None
+    if off and not ens.get("Points") and block.get("Sharded", False):
+        raise ValueError(" Ensemble: Filter.Window_Offsets is not available with \"Sharded\": true: the sharded filter "
+                         "gathers the members' water-table indices of the assimilation row only.")
+    return off or None
+
+
+def _reduce_filter_window(ranks, sim, ids, P, T, filt, window, label, keep_points, z0_cm):
+    """The window's datasets from this rank's handle over the filter's assimilated rows (its ``filter_rows``), the [P]
+    table placed and summed over the ranks like the filter's (float64 as int64 bits), and the closing line (rank 0)."""
+    import numpy as np
+    from .multigpu import place_points
+    from .stepper import WINDOW_WIDTH, stride_rows
+    stride = filt[0]
+    if not stride or not window:
+        return {}, None
+    n, n_arow = len(window), stride_rows(T, stride)
+    local = (sim.filter_window_table().reshape(-1, n_arow, n, WINDOW_WIDTH) if sim is not None
+             else np.zeros((0, n_arow, n, WINDOW_WIDTH)))
+    table = place_points(local, ids, P, ranks)
+    ftab = sim.filter_table().reshape(-1, n_arow, 4) if sim is not None else np.zeros((0, n_arow, 4))
+    used = place_points(ftab, ids, P, ranks)[..., 0] > 0
+    slots = np.flatnonzero(used.any(axis=0))               # the filter_rows of _reduce_filter
+    sel = table[:, slots] if keep_points else table[0, slots]
+    observed = sel[..., 0] == 1.0
+    out = {"filter_window_offsets": np.asarray(window, dtype=np.int64), "filter_window_observed": observed.astype(np.int8),
+           "filter_window_obs_cm": sel[..., 1] + float(z0_cm), "filter_window_prior_mean_cm": sel[..., 2] + float(z0_cm),
+           "filter_window_prior_std_cm": sel[..., 3]}
+    if ranks.rank != 0:
+        return out, None
+    first = table[0, slots, :, 0] == 1.0                   # the record is the same for every point
+    line = f" [{label}] filter window: {int(first.sum())} lagged observations over {int(first.any(axis=-1).sum())} rows"
+    return out, line
 
 
 def filter_sharded(ens):
@@ -1080,7 +1155,7 @@ def _reduce_enkf(ranks, sim, ids, P, T, enkf, label, keep_points, z0_cm):
     return out, line
 
 
-def _filter_kwargs(filt, record=None, ess_floor=None):
+def _filter_kwargs(filt, record=None, ess_floor=None, window=None):
     stride, sigma, seed = filt
     if not stride:
         return {}
@@ -1089,6 +1164,8 @@ def _filter_kwargs(filt, record=None, ess_floor=None):
         kw["filter_soil_moisture"] = record
     if ess_floor is not None:
         kw["filter_ess_floor"] = ess_floor
+    if window:
+        kw["filter_window_offsets"] = window
     return kw
 
 
@@ -1364,7 +1441,7 @@ def _reduce_periods(ranks, sim, ids, P, cols, forcing, periods, plan, label, kee
 
 def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride=0, dist_levels=None,
                filt=(0, None, None), enkf=(0, None, None, None), record=None, scheme=None, window=None, frecord=None,
-               theta=(0, None), storage=None, periods=None, plan=None, ess_floor=None):
+               theta=(0, None), storage=None, periods=None, plan=None, ess_floor=None, fwindow=None):
     """Parameter points x members: this rank's points in one handle (ensemble.SweepSimulation), the whole table assembled
     over the ranks (multigpu.assemble_points)."""
     import numpy as np
@@ -1391,7 +1468,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     if mine:
         sim = SweepSimulation(points, forcing, n_members, seed=int(ens.get("Seed", 0)), device=device, point_ids=mine,
                               profile_stride=stride, wtd_hist_stride=dist_stride, theta_hist_bins=theta[0],
-                              **_filter_kwargs(filt, frecord, ess_floor), **_enkf_kwargs(enkf, record, scheme, window),
+                              **_filter_kwargs(filt, frecord, ess_floor, fwindow),
+                              **_enkf_kwargs(enkf, record, scheme, window),
                               **_storage_kwargs(storage), **_period_kwargs(periods, plan))
         _step_all(sim, rows, label, ranks)
         table = sim.moments()
@@ -1416,6 +1494,9 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     arrays.update(ftables)
     fstables, fsm_line = _reduce_sm(ranks, sim, mine, P, T, filt[0], frecord, label, keep_points=True, owner="filter")
     arrays.update(fstables)
+    fwtables, fwindow_line = _reduce_filter_window(ranks, sim, mine, P, T, filt, fwindow, label, keep_points=True,
+                                                   z0_cm=cols_all[0].z[0])
+    arrays.update(fwtables)
     etables, enkf_line = _reduce_enkf(ranks, sim, mine, P, T, enkf, label, keep_points=True,
                                          z0_cm=cols_all[0].z[0])
     arrays.update(etables)
@@ -1434,6 +1515,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
         print(filter_line)
     if fsm_line:
         print(fsm_line)
+    if fwindow_line:
+        print(fwindow_line)
     if enkf_line:
         print(enkf_line)
     if sm_line:
@@ -1472,6 +1555,7 @@ def run_cli(argv=None):
                 soil_moisture_settings(settings["Ensemble"], n_gpus, "Filter")
                 enkf_method_settings(settings["Ensemble"])
                 enkf_window_settings(settings["Ensemble"])
+                filter_window_settings(settings["Ensemble"])
             except ValueError as bad:
                 print(bad)
                 sys.exit(1)

@@ -222,6 +222,19 @@ struct hc_handle {
     AccTable<double> ftemp{"entries"};
     DevBuf<long long> filt_trials, filt_tstate;
     DevBuf<unsigned long long> filt_tpart;
+    // the well's record inside the window (hc_set_filter_window): the offsets, ascending; each member's water-table index
+    // on the lagged rows [fwin_n][N] and the row each slot holds (-1: none; cleared by the assimilation); diagnostics
+    // float64 [P][n_arow][fwin_n][4] keyed like the filter's; the last assimilation's lagged columns (their slots, in
+    // column order); per member the largest of its indices on a windowed row (what counts it).  filt_ycols = the width
+    // of Y on the last assimilation, m_s + m_w + 2 (0: it took the bin path)
+    int fwin_n = 0;
+    std::vector<int> fwin_off;
+    std::vector<int64_t> fwin_row;
+    DevBuf<int> fwin_b;
+    std::vector<int> fwin_last;
+    AccTable<double> fwin{"entries"};
+    DevBuf<unsigned short> fwin_wmax;
+    int filt_ycols = 0;
     // one point's members on several handles (hc_set_filter_shard): the shard count (0: off), this handle's index and the
     // bounds b_0 = 0 < ... < b_S = n_global, on the host and on the device; the caller's buffer -- the gathered
     // water-table indices [n_global], the send region [(n + S - 1) 2 D] and the receive region [n 2 D], in 8-byte
@@ -2146,21 +2159,26 @@ __device__ double filter_block_max(double v)
 __device__ __forceinline__ bool filter_counted(int b, int D, double l) { return b < D && isfinite(l); }
 
 // Y[m][0] = l_m = -0.5 (t_w^2 + sum over the present sensors, in record order, of ((theta_m,i - theta_obs,i) / sigma_i)^2)
-// with the well's t_w = dz (b_m - o) / sigma_cm; lmax[p][t] = the largest l_m of the tile's counted members (-inf: none)
+// with the well's t_w = dz (b_m - o) / sigma_cm; lmax[p][t] = the largest l_m of the tile's counted members (-inf: none).
+// hc_set_filter_window: the present lagged rows follow the sensors by ascending offset, column i >= ms with the member's
+// index b_m(r_j) = lag[slot][m] of that row (window_capture_kernel) and the row's observed index s.node[i]:
+// t_j = dz (b_m(r_j) - o_j) / sigma_cm, a += t_j^2, and Y[m][1 + i] = dz b_m(r_j), the lagged depth the diagnostics sum.
+// wmax[m] = the largest of the member's indices (lagged columns only): it is counted when every one lies in the column.
 __global__ __launch_bounds__(FILT_THREADS) void filter_loglik_kernel(const unsigned short *w, long long members_per_point,
                                                                      int D, int obs, double dz, double sigma,
                                                                      const EnkfRow s, double *Y, long long n_tiles,
-                                                                     double *lmax)
+                                                                     double *lmax, const int *lag, long long n_members,
+                                                                     unsigned short *wmax)
 {
 #pragma clang fp contract(off)
     const long long p = blockIdx.y, t = blockIdx.x;
-    const int width = s.ms + 2;
+    const int width = s.m + 2;
     double best = -INFINITY;
     for (int j = 0; j < FILT_PER_THREAD; j++) {
         const long long m = t * FILT_TILE + (long long)threadIdx.x * FILT_PER_THREAD + j;
         if (m >= members_per_point) continue;
         const size_t k = (size_t)(p * members_per_point + m);
-        const int b = (int)w[k];
+        int b = (int)w[k];
         double *y = Y + k * width;
         const double tw = dz * (double)(b - obs) / sigma;
         double a = tw * tw;
@@ -2168,8 +2186,16 @@ __global__ __launch_bounds__(FILT_THREADS) void filter_loglik_kernel(const unsig
             const double u = (y[1 + i] - s.obs[i]) / s.sigma[i];
             a += u * u;
         }
+        for (int i = s.ms; i < s.m; i++) {
+            const int bj = lag[(size_t)s.sensor[i] * n_members + k];
+            const double tj = dz * (double)(bj - s.node[i]) / sigma;
+            a += tj * tj;
+            y[1 + i] = dz * (double)bj;
+            b = bj > b ? bj : b;
+        }
         const double l = -0.5 * a;
         y[0] = l;
+        if (s.m > s.ms) wmax[k] = (unsigned short)b;
         if (filter_counted(b, D, l)) best = l > best ? l : best;
     }
     best = filter_block_max(best);
@@ -2178,7 +2204,8 @@ __global__ __launch_bounds__(FILT_THREADS) void filter_loglik_kernel(const unsig
 
 // s = the largest lmax[p][.]; per member e_m = exp(l_m - s) -> Y[m][ms + 1] and q_m = floor(2^31 e_m) -> qm[m] (0 and 0
 // for a member that is not counted); ipart[p][t] = the tile's {sum q, sum q^2 low word, high word, members counted};
-// smax[p] = s
+// smax[p] = s.  (ms: the columns between l and e -- the present sensors and, hc_set_filter_window, the lagged rows; w is
+// then the members' largest indices)
 __global__ __launch_bounds__(FILT_THREADS) void filter_member_weights_kernel(const unsigned short *w,
                                                                              long long members_per_point, int D, int ms,
                                                                              long long n_tiles, const double *lmax,
@@ -2298,23 +2325,27 @@ __device__ __forceinline__ double filter_column_sum(const double *partial, long 
     return v;
 }
 
-// One block per point after the weights, the partials being those of (theta of the present sensors, e).  Thread c < ms:
-// sensor c's observed, observation and forecast mean (also -> mean[p][c]); a thread per absent sensor of the record:
-// observed = 0, the rest NaN; thread 0: W, the exact integer sums, the filter's count, ESS and increment, and the draw.
+// One block per point after the weights, the partials being those of (theta of the present sensors, the depths of the
+// present lagged rows, e).  Thread c < ms: sensor c's observed, observation and forecast mean (also -> mean[p][c]); a
+// thread per absent sensor of the record: observed = 0, the rest NaN; thread ms <= c < m: the same for lagged column c in
+// the window's table, and a thread per absent offset; thread 0: W, the exact integer sums, the filter's count, ESS and
+// increment, and the draw.
 __global__ void filter_member_finish_kernel(const double *partial, const unsigned long long *ipart, const double *smax,
                                             long long n_tiles, long long members_per_point, const EnkfRow s, double sigma,
                                             unsigned long long seed, const long long *point_base, long long member_offset,
                                             unsigned row, long long n_arow, long long slot, unsigned long long *qr,
-                                            double *stats, unsigned long long *surv, double *mean, double *sm_stats)
+                                            double *stats, unsigned long long *surv, double *mean, double *sm_stats,
+                                            double *win_stats)
 {
 #pragma clang fp contract(off)
     const long long p = blockIdx.x;
-    const int c = threadIdx.x, n_cols = s.ms + 1;
+    const int c = threadIdx.x, n_cols = s.m + 1;
     double *sm = sm_stats + ((size_t)p * n_arow + slot) * s.n * ENKF_SENSOR_WIDTH;
-    if (c < s.ms) {
+    double *wn = win_stats + ((size_t)p * n_arow + slot) * s.nw * ENKF_WINDOW_WIDTH;
+    if (c < s.m) {
         const double mu = filter_column_sum(partial, p, n_tiles, n_cols, c) / (double)members_per_point;
         mean[(size_t)p * FILT_COLS + c] = mu;
-        double *e = sm + (size_t)s.sensor[c] * ENKF_SENSOR_WIDTH;
+        double *e = c < s.ms ? sm + (size_t)s.sensor[c] * ENKF_SENSOR_WIDTH : wn + (size_t)s.sensor[c] * ENKF_WINDOW_WIDTH;
         e[0] = 1.0;
         e[1] = s.obs[c];
         e[2] = mu;
@@ -2328,8 +2359,17 @@ __global__ void filter_member_finish_kernel(const double *partial, const unsigne
             for (int k = 1; k < ENKF_SENSOR_WIDTH; k++) e[k] = __builtin_nan("");
         }
     }
+    if (c < s.nw) {
+        bool present = false;
+        for (int k = s.ms; k < s.m; k++) present = present || s.sensor[k] == c;
+        if (!present) {
+            double *e = wn + (size_t)c * ENKF_WINDOW_WIDTH;
+            e[0] = 0.0;
+            for (int k = 1; k < ENKF_WINDOW_WIDTH; k++) e[k] = __builtin_nan("");
+        }
+    }
     if (c != 0) return;
-    const double W = filter_column_sum(partial, p, n_tiles, n_cols, s.ms);
+    const double W = filter_column_sum(partial, p, n_tiles, n_cols, s.m);
     unsigned long long Q = 0, b_hi = 0, b_lo = 0, n = 0;
     for (long long t = 0; t < n_tiles; t++) {
         const unsigned long long *in = ipart + ((size_t)p * n_tiles + t) * 4;
@@ -2342,8 +2382,8 @@ __global__ void filter_member_finish_kernel(const double *partial, const unsigne
     if (n > 0 && Q > 0) {
         st[1] = filter_ess(Q, b_hi, b_lo);
         double inc = smax[p] + log(W / (double)n) - log(sigma);
-        for (int k = 0; k < s.ms; k++) inc -= log(s.sigma[k]);
-        st[2] = inc - 0.5 * (double)(1 + s.ms) * log(2.0 * M_PI);
+        for (int k = 0; k < s.m; k++) inc -= log(s.sigma[k]);      // (a lagged column's is the well's sigma_cm)
+        st[2] = inc - 0.5 * (double)(1 + s.m) * log(2.0 * M_PI);
     } else {
         st[1] = __builtin_nan("");
         st[2] = __builtin_nan("");
@@ -2351,18 +2391,20 @@ __global__ void filter_member_finish_kernel(const double *partial, const unsigne
     filter_draw(seed, point_base, member_offset, p, members_per_point, row, Q, qr, surv);
 }
 
-// One block per point, thread c < ms, from the partials of the present sensors' columns: entry = 4, the posterior mean
-// (also -> mean[p][c]); entry = 3 or 5, a std from the squared deviations, / (N_p - 1) (N_p = 1: 0)
+// One block per point, thread c < n_cols, from the partials of the first n_cols columns after l: entry = 4, the posterior
+// mean (also -> mean[p][c]); entry = 3 or 5, a std from the squared deviations, / (N_p - 1) (N_p = 1: 0).  A column
+// c >= ms is a lagged row's (hc_set_filter_window; entry 3 only): its forecast std goes to the window's table.
 __global__ void filter_sm_moment_kernel(const double *partial, long long n_tiles, long long members_per_point,
-                                        const EnkfRow s, int entry, long long n_arow, long long slot, double *mean,
-                                        double *sm_stats)
+                                        const EnkfRow s, int n_cols, int entry, long long n_arow, long long slot,
+                                        double *mean, double *sm_stats, double *win_stats)
 {
 #pragma clang fp contract(off)
     const long long p = blockIdx.x;
     const int c = threadIdx.x;
-    if (c >= s.ms) return;
-    const double v = filter_column_sum(partial, p, n_tiles, s.ms, c);
-    double *e = sm_stats + (((size_t)p * n_arow + slot) * s.n + s.sensor[c]) * ENKF_SENSOR_WIDTH;
+    if (c >= n_cols) return;
+    const double v = filter_column_sum(partial, p, n_tiles, n_cols, c);
+    double *e = c < s.ms ? sm_stats + (((size_t)p * n_arow + slot) * s.n + s.sensor[c]) * ENKF_SENSOR_WIDTH
+                         : win_stats + (((size_t)p * n_arow + slot) * s.nw + s.sensor[c]) * ENKF_WINDOW_WIDTH;
     if (entry == 4) {
         e[4] = mean[(size_t)p * FILT_COLS + c] = v / (double)members_per_point;
     } else {
@@ -2376,6 +2418,14 @@ __global__ void filter_expand_weights_kernel(const unsigned short *w, const long
 {
     const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (k < n_members) qm[k] = filter_q(w, q_all + (size_t)(k / members_per_point) * D, D, k);
+}
+
+// the lagged row a launch ended on (hc_set_filter_window): every member's water-table index of that row, widened, into the
+// offset's row of the window's buffer [n_offsets][N]
+__global__ void window_capture_kernel(const unsigned short *w, long long n_members, int *out)
+{
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n_members) out[k] = (int)w[k];
 }
 
 // ---- tempered weights (hc_set_filter_tempering, include/hydrocol.h)
@@ -3178,6 +3228,27 @@ int ensure_ftemp(hc_handle *h)
     return ensure_da_table(h, h->ftemp, h->filt_stride, TEMPER_WIDTH, 0);
 }
 
+// the window's diagnostics (hc_set_filter_window): [P][n_arow][n][4] float64, created as NaN
+int ensure_fwin(hc_handle *h)
+{
+    if (h->fwin_n <= 0) return fail(HC_ERR_ARG, "no window offsets (hc_set_filter_window)");
+    if (int rc = ensure_filter(h)) return rc;
+    return ensure_da_table(h, h->fwin, h->filt_stride, (int64_t)h->fwin_n * ENKF_WINDOW_WIDTH, 0);
+}
+
+void fwin_off(hc_handle *h)
+{
+    h->fwin_n = 0;
+    h->filt_ycols = 0;
+    h->fwin_off.clear(); h->fwin_row.clear(); h->fwin_last.clear();
+    h->fwin.release();
+    h->fwin_b.release(); h->fwin_wmax.release();
+    if (h->fsm_n <= 0) {
+        h->filt_qm.release(); h->filt_Y.release(); h->filt_lmax.release(); h->filt_part.release(); h->filt_sums.release();
+        h->filt_ipart.release();
+    }
+}
+
 void temper_off(hc_handle *h)
 {
     h->filt_floor = 0.0;
@@ -3190,6 +3261,7 @@ void fsm_off(hc_handle *h)
     h->fsm_n = 0;
     h->fsm_rows = 0;
     h->fsm_width = 0;
+    h->filt_ycols = 0;
     h->fsm_nodes.clear(); h->fsm_sigma.clear(); h->fsm_values.clear();
     h->fsm.release();
     h->filt_qm.release(); h->filt_Y.release(); h->filt_lmax.release(); h->filt_part.release(); h->filt_sums.release();
@@ -3201,6 +3273,7 @@ void filter_off(hc_handle *h)
 {
     filter_shard_off(h);
     fsm_off(h);
+    fwin_off(h);
     temper_off(h);
     h->filt_stride = 0;
     h->filt_done = false;
@@ -4055,21 +4128,27 @@ bool is_assimilation_row(const hc_handle *h, int64_t row)
     return s > 0 && row >= 1 && row % s == 0 && h->h_wtd_obs[(size_t)row] >= 0;
 }
 
-// The offset slot that lagged row `row` fills for the analysis row after it (hc_set_enkf_window), -1: none.  The row
-// takes part when it is >= 1 and has an observation, and the analysis row is one as things stand.
+// the window's offsets of whichever filter is on (hc_set_filter_window, hc_set_enkf_window), empty: none
+const std::vector<int> &da_window(const hc_handle *h) { return h->filt_stride > 0 ? h->fwin_off : h->win_off; }
+
+// The offset slot that lagged row `row` fills for the assimilation row after it (hc_set_enkf_window,
+// hc_set_filter_window), -1: none.  The row takes part when it is >= 1 and has an observation, and the assimilation row
+// is one as things stand.
 int window_slot(const hc_handle *h, int64_t row)
 {
-    if (h->win_n <= 0 || h->enkf_stride <= 0 || row < 1 || h->h_wtd_obs[(size_t)row] < 0) return -1;
-    const int64_t s = h->enkf_stride, r = (row / s + 1) * s;
+    const std::vector<int> &off = da_window(h);
+    const int64_t s = da_stride(h);
+    if (off.empty() || s <= 0 || row < 1 || h->h_wtd_obs[(size_t)row] < 0) return -1;
+    const int64_t r = (row / s + 1) * s;
     if (r >= h->n_rows || !is_assimilation_row(h, r)) return -1;
-    for (int j = 0; j < h->win_n; j++)
-        if (h->win_off[(size_t)j] == r - row) return j;
+    for (size_t j = 0; j < off.size(); j++)
+        if (off[j] == r - row) return (int)j;
     return -1;
 }
 
 // The launch after `done` rows of the request.  With a filter on, a launch ends on the next assimilation row and, in a
-// Philox run with the particle filter, holds at most as many refresh rows as FILT_FRESH_BYTES admits; with the EnKF's
-// window on it ends on the next lagged row that takes part.
+// Philox run with the particle filter, holds at most as many refresh rows as FILT_FRESH_BYTES admits; with either
+// filter's window on it ends on the next lagged row that takes part.
 Chunk plan_chunk(const hc_handle *h, const hc_step_args *a, int64_t done, bool prof_on)
 {
     const int64_t N = h->n_members, D = h->p.dim_d;
@@ -4091,7 +4170,7 @@ Chunk plan_chunk(const hc_handle *h, const hc_step_args *a, int64_t done, bool p
                 c.rows = (int)(r - c.row0 + 1);
                 break;
             }
-        if (h->win_n > 0)
+        if (!da_window(h).empty())
             for (int r = 0; r < c.rows; r++)
                 if (window_slot(h, c.row0 + r) >= 0) {
                     c.rows = r + 1;
@@ -4325,18 +4404,21 @@ int filter_shard_resample(hc_handle *h, int64_t n_tiles)
 }
 
 // one entry of the sensor table from a pass over the present sensors' theta: the squared deviations from the means on
-// the device (entries 3 and 5: a std), or the sums (entry 4: the posterior mean); anc: over the resampled slots
+// the device (entries 3 and 5: a std), or the sums (entry 4: the posterior mean); anc: over the resampled slots.  The
+// forecast's std (entry 3) takes the lagged depths of the window along, into the window's table.
 int filter_sm_moment(hc_handle *h, const EnkfRow &s, const long long *anc, int entry, int64_t n_tiles, int64_t n_arow,
                      int64_t slot)
 {
     const int64_t N = h->n_members, P = h->n_points, mpp = N / P;
+    const int n_cols = entry == 3 ? s.m : s.ms;
+    if (n_cols == 0) return HC_OK;
     hipLaunchKernelGGL(filter_tile_partial_kernel, dim3((unsigned)n_tiles, (unsigned)P), dim3(FILT_THREADS), 0, h->stream,
-                       h->filt_Y.p, s.ms + 2, 1, s.ms, anc, entry == 4 ? (const double *)nullptr : h->filt_sums.p,
+                       h->filt_Y.p, s.m + 2, 1, n_cols, anc, entry == 4 ? (const double *)nullptr : h->filt_sums.p,
                        (long long)mpp, (long long)N, (long long)n_tiles, h->filt_part.p);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(filter_sm_moment_kernel, dim3((unsigned)P), dim3(WAVE), 0, h->stream, h->filt_part.p,
-                       (long long)n_tiles, (long long)mpp, s, entry, (long long)n_arow, (long long)slot, h->filt_sums.p,
-                       h->fsm.buf.p);
+                       (long long)n_tiles, (long long)mpp, s, n_cols, entry, (long long)n_arow, (long long)slot,
+                       h->filt_sums.p, h->fsm.buf.p, h->fwin.buf.p);
     HIP_TRY(hipGetLastError());
     return HC_OK;
 }
@@ -4360,45 +4442,86 @@ EnkfRow sensor_row(int n, const std::vector<int> &nodes, const std::vector<doubl
     return s;
 }
 
+// The observations of assimilation row `row` beyond the well's: the sensors with a value, in record order, then the lagged
+// rows of the window that were captured for it, by ascending offset (node = the lagged row's observed index)
+EnkfRow filter_row(const hc_handle *h, int64_t row)
+{
+    EnkfRow s = sensor_row(h->fsm_n, h->fsm_nodes, h->fsm_sigma, h->fsm_values, row);
+    for (int j = 0; j < h->fwin_n; j++) {
+        const int64_t rj = row - h->fwin_off[(size_t)j];
+        if (rj < 1 || h->h_wtd_obs[(size_t)rj] < 0 || h->fwin_row[(size_t)j] != rj) continue;
+        s.sensor[s.m] = j;
+        s.node[s.m] = h->h_wtd_obs[(size_t)rj];
+        s.obs[s.m] = h->p.dz * (double)h->h_wtd_obs[(size_t)rj];
+        s.sigma[s.m] = h->filt_sigma;
+        s.wrow[s.m] = (unsigned)rj;
+        s.m++;
+    }
+    s.nw = s.m > s.ms ? h->fwin_n : 0;
+    return s;
+}
+
+// The lagged row the launch ended on (hc_set_filter_window): every member's water-table index into the window's buffer
+int filter_capture(hc_handle *h, const Chunk &c, int slot)
+{
+    const int64_t N = h->n_members;
+    if (h->fwin_b.ensure((size_t)(h->fwin_n * N))) return HC_ERR_DEVICE;
+    const unsigned short *w = h->wtd_u16.p + (size_t)(c.rows - 1) * N;
+    hipLaunchKernelGGL(window_capture_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, w, (long long)N,
+                       h->fwin_b.p + (size_t)slot * N);
+    HIP_TRY(hipGetLastError());
+    h->fwin_row[(size_t)slot] = c.row0 + c.rows - 1;
+    return HC_OK;
+}
+
 // A sensor row's weights (hc_set_filter_soil_moisture) in place of filter_weights_kernel's: theta and l_m per member, the
 // tiles' maxima, e_m and q_m per member with the tiles' integer sums, the partials of (theta, e), then per point the
-// diagnostics, the forecast means and the draw, and the forecast spread in a second pass about the means
+// diagnostics, the forecast means and the draw, and the forecast spread in a second pass about the means.  A row with
+// lagged rows of the window (hc_set_filter_window) runs the same kernels with their columns between theta and e, also
+// when no sensor has a value; what counts a member is then the largest of its indices (fwin_wmax).
 int filter_member_weights(hc_handle *h, const Chunk &c, const EnkfRow &s, const long long *pbase, long long key)
 {
     const int64_t N = h->n_members, D = h->p.dim_d, P = h->n_points, mpp = N / P;
     const int64_t row = c.row0 + c.rows - 1, slot = row / h->filt_stride, n_arow = filter_rows(h);
     const int64_t n_tiles = (mpp + FILT_TILE - 1) / FILT_TILE;
-    const int width = s.ms + 2;
-    if (h->filt_qm.ensure((size_t)N) || h->filt_Y.ensure((size_t)(N * (h->fsm_n + 2))) ||
+    const int width = s.m + 2;
+    const bool lagged = s.m > s.ms;
+    if (lagged && h->fwin_wmax.ensure((size_t)N)) return HC_ERR_DEVICE;
+    if (h->filt_qm.ensure((size_t)N) || h->filt_Y.ensure((size_t)(N * (h->fsm_n + h->fwin_n + 2))) ||
         h->filt_lmax.ensure((size_t)(P * n_tiles)) || h->filt_ipart.ensure((size_t)(P * n_tiles * 4)) ||
         h->filt_part.ensure((size_t)(P * n_tiles * FILT_COLS)) || h->filt_sums.ensure((size_t)(P * (FILT_COLS + 1))))
         return HC_ERR_DEVICE;
     const unsigned short *w = h->wtd_u16.p + (size_t)(c.rows - 1) * N;
     double *const Y = h->filt_Y.p, *const mean = h->filt_sums.p, *const smax = h->filt_sums.p + (size_t)(P * FILT_COLS);
     const dim3 tiles((unsigned)n_tiles, (unsigned)P);
-    hipLaunchKernelGGL(enkf_theta_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, h->psi.p, h->Pdev.p,
-                       h->node_tabs.p, (int)h->use_special(), (long long)N, (long long)mpp, (int)D, s, Y, width);
-    HIP_TRY(hipGetLastError());
+    if (s.ms > 0) {
+        hipLaunchKernelGGL(enkf_theta_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, h->psi.p, h->Pdev.p,
+                           h->node_tabs.p, (int)h->use_special(), (long long)N, (long long)mpp, (int)D, s, Y, width);
+        HIP_TRY(hipGetLastError());
+    }
     hipLaunchKernelGGL(filter_loglik_kernel, tiles, dim3(FILT_THREADS), 0, h->stream, w, (long long)mpp, (int)D,
-                       h->h_wtd_obs[(size_t)row], h->p.dz, h->filt_sigma, s, Y, (long long)n_tiles, h->filt_lmax.p);
+                       h->h_wtd_obs[(size_t)row], h->p.dz, h->filt_sigma, s, Y, (long long)n_tiles, h->filt_lmax.p,
+                       (const int *)h->fwin_b.p, (long long)N, h->fwin_wmax.p);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(filter_member_weights_kernel, tiles, dim3(FILT_THREADS), 0, h->stream, w, (long long)mpp, (int)D, s.ms,
+    if (lagged) w = h->fwin_wmax.p;
+    hipLaunchKernelGGL(filter_member_weights_kernel, tiles, dim3(FILT_THREADS), 0, h->stream, w, (long long)mpp, (int)D, s.m,
                        (long long)n_tiles, h->filt_lmax.p, Y, h->filt_qm.p, h->filt_ipart.p, smax);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(filter_tile_partial_kernel, tiles, dim3(FILT_THREADS), 0, h->stream, Y, width, 1, s.ms + 1,
+    hipLaunchKernelGGL(filter_tile_partial_kernel, tiles, dim3(FILT_THREADS), 0, h->stream, Y, width, 1, s.m + 1,
                        (const long long *)nullptr, (const double *)nullptr, (long long)mpp, (long long)N, (long long)n_tiles,
                        h->filt_part.p);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(filter_member_finish_kernel, dim3((unsigned)P), dim3(WAVE), 0, h->stream, h->filt_part.p,
                        h->filt_ipart.p, smax, (long long)n_tiles, (long long)mpp, s, h->filt_sigma,
                        (unsigned long long)h->filt_seed, pbase, key, (unsigned)row, (long long)n_arow, (long long)slot,
-                       h->filt_qr.p, h->filt.buf.p, h->filt_surv.p, mean, h->fsm.buf.p);
+                       h->filt_qr.p, h->filt.buf.p, h->filt_surv.p, mean, h->fsm.buf.p, h->fwin.buf.p);
     HIP_TRY(hipGetLastError());
     return filter_sm_moment(h, s, nullptr, 3, n_tiles, n_arow, slot);
 }
 
 // The tempering of a row's weights (hc_set_filter_tempering) after its weight kernels, w being the indices they read.
-// The bin path: one kernel, every trial inside the block.  A sensor row (ms > 0): trial 0 on the tile sums the weights
+// The bin path: one kernel, every trial inside the block.  A per-member row (ms > 0 columns between l and e: sensors and
+// lagged rows; w then the indices that count a member): trial 0 on the tile sums the weights
 // left, then ten pairs of sums and decision enqueued unconditionally -- no host synchronisation; a point that is done
 // exits at once -- and the result applied to q_m and the draw.
 int filter_temper(hc_handle *h, const unsigned short *w, int ms, int64_t mpp, int64_t n_tiles, int64_t row,
@@ -4475,13 +4598,13 @@ int assimilate(hc_handle *h, const Chunk &c)
     }
     const long long *pbase = P > 1 ? h->point_base.p : nullptr;
     // a row with sensor values (hc_set_filter_soil_moisture; never sharded): a weight per member, and the scan below reads
-    // it directly (a null w) in place of the bin's
-    const EnkfRow s = sensor_row(h->fsm_n, h->fsm_nodes, h->fsm_sigma, h->fsm_values, row);
+    // it directly (a null w) in place of the bin's; so does a row with lagged rows of the window (hc_set_filter_window)
+    const EnkfRow s = filter_row(h, row);
     const long long *q = h->filt_q.p;
-    if (s.ms > 0) {
+    if (s.m > 0) {
         if (int rc = filter_member_weights(h, c, s, pbase, key)) return rc;
         if (h->filt_floor > 0.0)
-            if (int rc = filter_temper(h, w, s.ms, mpp, n_tiles, row, pbase, key)) return rc;
+            if (int rc = filter_temper(h, s.m > s.ms ? h->fwin_wmax.p : w, s.m, mpp, n_tiles, row, pbase, key)) return rc;
         HIP_TRY(hipMemsetAsync(h->filt_q.p, 0, (size_t)(P * D) * 8, h->stream));
         w = nullptr;
         q = h->filt_qm.p;
@@ -4493,7 +4616,7 @@ int assimilate(hc_handle *h, const Chunk &c)
         HIP_TRY(hipGetLastError());
         if (h->filt_floor > 0.0)
             if (int rc = filter_temper(h, w, 0, mpp, n_tiles, row, pbase, key)) return rc;
-        if (h->fsm_n > 0) {
+        if (h->fsm_n > 0 || h->fwin_n > 0) {
             if (h->filt_qm.ensure((size_t)N)) return HC_ERR_DEVICE;
             hipLaunchKernelGGL(filter_expand_weights_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, w,
                                h->filt_q.p, (long long)mpp, (long long)N, (int)D, h->filt_qm.p);
@@ -4539,6 +4662,10 @@ int assimilate(hc_handle *h, const Chunk &c)
         if (int rc = filter_sm_moment(h, s, h->filt_anc.p, 5, n_tiles, n_arow, slot)) return rc;
     }
     h->fsm_width = s.ms;
+    h->filt_ycols = s.m > 0 ? s.m + 2 : 0;
+    // the window's buffer is spent: the lagged columns this row took (test hook), every slot empty
+    h->fwin_last.assign(s.sensor + s.ms, s.sensor + s.m);
+    std::fill(h->fwin_row.begin(), h->fwin_row.end(), (int64_t)-1);
     std::swap(h->psi, h->psi_alt);
     std::swap(h->base, h->base_alt);
     // the rest of this hc_step_rows call launches on the analysis (fill_args took the pointers before the swap)
@@ -4824,6 +4951,7 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
     if (filt_on && (rc = ensure_filter(h))) return rc;
     if (filt_on && h->fsm_n > 0 && (rc = ensure_fsm(h))) return rc;
     if (filt_on && h->filt_floor > 0.0 && (rc = ensure_ftemp(h))) return rc;
+    if (filt_on && h->fwin_n > 0 && (rc = ensure_fwin(h))) return rc;
     const bool enkf_on = h->enkf_stride > 0 && !a->spinup;   // (the EnKF: spin-up solves are never analysed either)
     if (enkf_on && (rc = ensure_enkf(h))) return rc;
     if (enkf_on && h->sm_n > 0 && (rc = ensure_sm(h))) return rc;
@@ -4842,6 +4970,8 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
             return rc;
         if (const int wslot = enkf_on ? window_slot(h, c.row0 + c.rows - 1) : -1; wslot >= 0)
             if ((rc = enkf_capture(h, c, wslot))) return rc;
+        if (const int wslot = filt_on ? window_slot(h, c.row0 + c.rows - 1) : -1; wslot >= 0)
+            if ((rc = filter_capture(h, c, wslot))) return rc;
         HIP_TRY(hipStreamSynchronize(h->stream));
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
@@ -5559,6 +5689,9 @@ int hc_set_filter_soil_moisture(hc_handle *h, int32_t n_sensors, const int32_t *
     if (n_sensors > 0 && h->fs_n > 0)
         return fail(HC_ERR_ARG, "hc_set_filter_soil_moisture: the filter is sharded (hc_set_filter_shard), and the sharded "
                                 "filter gathers water-table indices only: a record needs every member of a point on one handle");
+    if (n_sensors + h->fwin_n > ENKF_SENSORS)
+        return fail(HC_ERR_ARG, "hc_set_filter_soil_moisture: %d sensors and %d window offsets, at most %d together",
+                    (int)n_sensors, h->fwin_n, ENKF_SENSORS);
     if (n_sensors > 0 && (!nodes || !values || !sigma)) return fail(HC_ERR_ARG, "hc_set_filter_soil_moisture: bad argument");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -5634,16 +5767,18 @@ int hc_get_filter_sm_width(hc_handle *h, int32_t *width)
 
 int hc_get_filter_member_weights(hc_handle *h, int64_t *q)
 {
-    if (h && h->fsm_n <= 0) return fail(HC_ERR_ARG, "hc_get_filter_member_weights: no soil-moisture record");
+    if (h && h->fsm_n <= 0 && h->fwin_n <= 0)
+        return fail(HC_ERR_ARG, "hc_get_filter_member_weights: no soil-moisture record");
     return filter_hook(h, h->filt_qm, q, h ? (size_t)h->n_members : 0, "hc_get_filter_member_weights");
 }
 
-// columns [col0, col0 + cols) of the last sensor row's Y [N][m_s + 2]
+// columns [col0, col0 + cols) of the last per-member row's Y [N][m_s + m_w + 2]
 static int filter_sm_hook(hc_handle *h, double *out, int col0, int cols, const char *who)
 {
     if (!h || !out) return fail(HC_ERR_ARG, "%s: bad argument", who);
-    if (h->fsm_n <= 0 || h->fsm_width <= 0) return fail(HC_ERR_ARG, "%s: the last assimilation had no sensor value", who);
-    const size_t N = (size_t)h->n_members, width = (size_t)h->fsm_width + 2;
+    if (h->filt_ycols <= 0 || (col0 > 0 && h->fsm_width <= 0))
+        return fail(HC_ERR_ARG, "%s: the last assimilation had no sensor value", who);
+    const size_t N = (size_t)h->n_members, width = (size_t)h->filt_ycols;
     std::vector<double> all(N * width);
     if (int rc = filter_hook(h, h->filt_Y, all.data(), all.size(), who)) return rc;
     for (size_t m = 0; m < N; m++) std::copy_n(all.data() + m * width + col0, cols, out + m * cols);
@@ -5655,6 +5790,103 @@ int hc_get_filter_loglik(hc_handle *h, double *l) { return filter_sm_hook(h, l, 
 int hc_get_filter_sm_theta(hc_handle *h, double *theta)
 {
     return filter_sm_hook(h, theta, 1, h ? h->fsm_width : 0, "hc_get_filter_sm_theta");
+}
+
+int hc_set_filter_window(hc_handle *h, int32_t n_offsets, const int32_t *offsets)
+{
+    if (!h || n_offsets < 0 || (n_offsets > 0 && !offsets)) return fail(HC_ERR_ARG, "hc_set_filter_window: bad argument");
+    if (n_offsets > ENKF_SENSORS)
+        return fail(HC_ERR_ARG, "hc_set_filter_window: %d offsets, at most %d", (int)n_offsets, ENKF_SENSORS);
+    if (n_offsets > 0 && h->enkf_stride > 0)
+        return fail(HC_ERR_ARG, "hc_set_filter_window: the EnKF is on (its window: hc_set_enkf_window)");
+    if (n_offsets > 0 && h->filt_stride <= 0)
+        return fail(HC_ERR_ARG, "hc_set_filter_window: the particle filter is off (hc_set_filter comes first)");
+    if (n_offsets > 0 && h->fs_n > 0)
+        return fail(HC_ERR_ARG, "hc_set_filter_window: the filter is sharded (hc_set_filter_shard), and the sharded filter "
+                                "gathers the water-table indices of the assimilation row only");
+    if (n_offsets + h->fsm_n > ENKF_SENSORS)
+        return fail(HC_ERR_ARG, "hc_set_filter_window: %d offsets and %d sensors, at most %d together", (int)n_offsets,
+                    h->fsm_n, ENKF_SENSORS);
+    std::vector<int> off(offsets, offsets + n_offsets);
+    std::sort(off.begin(), off.end());
+    for (int j = 0; j < n_offsets; j++) {
+        if (off[(size_t)j] < 1 || off[(size_t)j] >= h->filt_stride)
+            return fail(HC_ERR_ARG, "hc_set_filter_window: offset %d outside [1, %d) (the stride)", off[(size_t)j],
+                        h->filt_stride);
+        if (j > 0 && off[(size_t)j] == off[(size_t)j - 1])
+            return fail(HC_ERR_ARG, "hc_set_filter_window: offset %d twice", off[(size_t)j]);
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    fwin_off(h);
+    if (n_offsets == 0) return HC_OK;
+    h->fwin_n = n_offsets;
+    h->fwin_off = off;
+    h->fwin_row.assign((size_t)n_offsets, (int64_t)-1);
+    const int rc = ensure_fwin(h);
+    if (rc != HC_OK) fwin_off(h);                // refused: off
+    return rc;
+}
+
+int hc_get_filter_window_stats(hc_handle *h, double *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_get_filter_window_stats: bad argument");
+    return table_copy(h, h->fwin, ensure_fwin, hipMemcpyDeviceToHost, table, n_entries, "hc_get_filter_window_stats");
+}
+
+int hc_set_filter_window_stats(hc_handle *h, const double *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_set_filter_window_stats: bad argument");
+    return table_copy(h, h->fwin, ensure_fwin, hipMemcpyHostToDevice, const_cast<double *>(table), n_entries,
+                      "hc_set_filter_window_stats");
+}
+
+// what the window holds for the coming assimilation: checkpoints
+int hc_get_filter_window_capture(hc_handle *h, int32_t *b, int64_t *rows)
+{
+    if (!h || !b || !rows) return fail(HC_ERR_ARG, "hc_get_filter_window_capture: bad argument");
+    if (h->fwin_n <= 0) return fail(HC_ERR_ARG, "hc_get_filter_window_capture: no window offsets (hc_set_filter_window)");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const size_t N = (size_t)h->n_members;
+    for (int j = 0; j < h->fwin_n; j++) {
+        rows[j] = h->fwin_row[(size_t)j];
+        if (rows[j] >= 0)
+            HIP_TRY(hipMemcpy(b + (size_t)j * N, h->fwin_b.p + (size_t)j * N, N * 4, hipMemcpyDeviceToHost));
+        else
+            std::fill_n(b + (size_t)j * N, N, 0);
+    }
+    return HC_OK;
+}
+
+int hc_set_filter_window_capture(hc_handle *h, const int32_t *b, const int64_t *rows)
+{
+    if (!h || !b || !rows) return fail(HC_ERR_ARG, "hc_set_filter_window_capture: bad argument");
+    if (h->fwin_n <= 0) return fail(HC_ERR_ARG, "hc_set_filter_window_capture: no window offsets (hc_set_filter_window)");
+    const size_t N = (size_t)h->n_members;
+    for (int j = 0; j < h->fwin_n; j++)
+        if (rows[j] < -1 || rows[j] >= h->n_rows)
+            return fail(HC_ERR_ARG, "hc_set_filter_window_capture: row %lld of offset %d outside [-1, %lld)",
+                        (long long)rows[j], h->fwin_off[(size_t)j], (long long)h->n_rows);
+    for (size_t k = 0; k < (size_t)h->fwin_n * N; k++)
+        if (b[k] < 0 || b[k] > 65535)
+            return fail(HC_ERR_ARG, "hc_set_filter_window_capture: index %d (entry %zu) outside [0, 65535]", (int)b[k], k);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->fwin_b.ensure((size_t)h->fwin_n * N)) return HC_ERR_DEVICE;
+    HIP_TRY(hipMemcpy(h->fwin_b.p, b, (size_t)h->fwin_n * N * 4, hipMemcpyHostToDevice));
+    h->fwin_row.assign(rows, rows + h->fwin_n);
+    return HC_OK;
+}
+
+int hc_get_filter_window_width(hc_handle *h, int32_t *width, int32_t *slots)
+{
+    if (!h || !width) return fail(HC_ERR_ARG, "hc_get_filter_window_width: bad argument");
+    const bool any = h->filt_stride > 0 && h->filt_done && h->fwin_n > 0;
+    *width = any ? (int32_t)h->fwin_last.size() : 0;
+    if (slots)
+        for (int k = 0; k < *width; k++) slots[k] = h->fwin_last[(size_t)k];
+    return HC_OK;
 }
 
 }  // extern "C"
@@ -5709,6 +5941,9 @@ int hc_set_filter_shard(hc_handle *h, int32_t n_shards, const int64_t *bounds, i
     if (h->fsm_n > 0)
         return fail(HC_ERR_ARG, "hc_set_filter_shard: a soil-moisture record is set (hc_set_filter_soil_moisture), and the "
                                 "sharded filter gathers water-table indices only");
+    if (h->fwin_n > 0)
+        return fail(HC_ERR_ARG, "hc_set_filter_shard: window offsets are set (hc_set_filter_window), and the sharded filter "
+                                "gathers the water-table indices of the assimilation row only");
     if (h->per_n > 0)
         return fail(HC_ERR_ARG, "hc_set_filter_shard: period totals are set (hc_set_period_totals), and the routed columns do "
                                 "not carry the members' accumulators");

@@ -11,6 +11,7 @@ import numpy as np
 from .digest import inverse_retention
 from .stepper import (ENKF_METHODS, ENKF_WIDTH, SM_WIDTH, WINDOW_WIDTH, EnsembleStepper, enkf_sm_summary, enkf_summary,
                       enkf_window_settings, enkf_window_summary, filter_sm_summary, filter_summary,
+                      filter_window_settings, filter_window_summary,
                       flux_max_log2_of, layer_ranges, layer_storage_distribution, moments_to_mean_std, period_totals_distribution,
                       sensor_nodes, theta_distribution, wtd_distribution)
 
@@ -119,6 +120,10 @@ class _Run:
     filter_ess_floor: 0 < f < 1 holds the effective sample size of every resampling above f times the counted members by
     tempering the weights (include/hydrocol.h hc_set_filter_tempering); :meth:`filter_temper_table`, and
     :meth:`filter_summary` gains ``beta``, ``ess_tempered``, ``ess_target`` and ``tempered_rows``.
+    filter_window_offsets: rows before each assimilation row (integers in [1, filter_stride), e.g. (12, 24, 36)) whose
+    observation of the well joins the members' weights too: nothing is resampled in between, so a member's weight is the
+    likelihood of everything its trajectory passed (include/hydrocol.h hc_set_filter_window);
+    :meth:`filter_window_table`, the ``window_*`` keys of :meth:`filter_summary`.
     enkf_stride > 0: a stochastic ensemble Kalman filter on the well's continuous water table instead (``enkf_sigma_cm``:
     the observation error; ``enkf_localisation_cm``: the Gaspari-Cohn half-width, 0 = none; ``enkf_seed``: default the
     run's seed), with the same forecast / analysis order; :meth:`enkf_summary` (log marginal likelihood).
@@ -139,7 +144,7 @@ class _Run:
                       enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None,
                       enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=(),
                       filter_soil_moisture=None, theta_hist_bins=0, storage_layers_cm=None, storage_bins=0,
-                      filter_ess_floor=0.0):
+                      filter_ess_floor=0.0, filter_window_offsets=()):
         self.profile_stride = int(profile_stride)
         self.storage_layers_cm = None if storage_layers_cm is None or len(storage_layers_cm) == 0 else \
             np.asarray(storage_layers_cm, dtype=np.float64).reshape(-1, 2)
@@ -178,6 +183,10 @@ class _Run:
             if not self.filter_stride:
                 raise ValueError("filter_ess_floor needs the particle filter (filter_stride > 0)")
             self.stepper.set_filter_tempering(self.filter_ess_floor)
+        self.filter_window_offsets = filter_window_settings(filter_window_offsets, self.filter_stride,
+                                                            self.stepper.filter_sm_n)
+        if self.filter_window_offsets:
+            self.stepper.set_filter_window(self.filter_window_offsets)
         self.enkf_stride = int(enkf_stride or 0)
         self.enkf_sigma_cm = float(enkf_sigma_cm) if self.enkf_stride else None
         self.enkf_localisation_cm = float(enkf_localisation_cm or 0.0) if self.enkf_stride else None
@@ -315,20 +324,33 @@ class _Run:
         hc_set_filter_tempering); a sweep: [P][n_arow][4]."""
         return self.stepper.filter_temper_table().reshape(self._lead + (-1, 4))
 
-    def filter_summary(self, table=None, sm_table=None, temper_table=None):
+    def filter_summary(self, table=None, sm_table=None, temper_table=None, window_table=None):
         """The filter's record (stepper.filter_summary): ``rows``, ``count``, ``ess``, ``loglik_rows``, ``survivors`` over
         the assimilated rows and ``loglik``, the log marginal likelihood of the well record (log cm^-1 summed over the rows),
         with a leading [P] for a sweep; ``table``: e.g. the one assembled over ranks.  With a soil-moisture record the
         increments of the sensor rows are the joint ones, and the ``sm_*`` keys of :meth:`filter_sm_summary` come along.
         With ``filter_ess_floor`` the tempering's ``beta``, ``ess_tempered``, ``ess_target`` and ``tempered_rows`` too
-        (``temper_table``: as ``table``)."""
+        (``temper_table``: as ``table``).  With a window the ``window_*`` keys of :meth:`filter_window_summary` too."""
         t = self.filter_table() if table is None else table
         if getattr(self, "filter_ess_floor", 0.0) and temper_table is None:      # (0.0: a run started without the setting)
             temper_table = self.filter_temper_table()
         out = filter_summary(t, self.filter_stride, self.filter_sigma_cm, temper_table=temper_table)
         if self.filter_soil_moisture is not None:
             out.update(("sm_" + k, v) for k, v in self.filter_sm_summary(sm_table).items())
+        if getattr(self, "filter_window_offsets", ()):
+            out.update(("window_" + k, v) for k, v in self.filter_window_summary(window_table).items())
         return out
+
+    def filter_window_table(self):
+        """[n_arow][n][4] float64 (include/hydrocol.h hc_set_filter_window); a sweep: [P][n_arow][n][4]."""
+        return self.stepper.filter_window_table().reshape(self._lead + (-1, len(self.filter_window_offsets), WINDOW_WIDTH))
+
+    def filter_window_summary(self, table=None):
+        """stepper.filter_window_summary of the window's table (``table``: e.g. the one assembled over ranks): per
+        assimilation row and offset the lagged observation, the forecast of the members' water table there and the
+        innovation."""
+        t = self.filter_window_table() if table is None else table
+        return filter_window_summary(t, self.filter_stride, self.filter_window_offsets, float(self.cols.z[0]))
 
     def filter_sm_table(self):
         """[n_arow][n][6] float64 (include/hydrocol.h hc_set_filter_soil_moisture); a sweep: [P][n_arow][n][6]."""
@@ -409,7 +431,10 @@ class EnsembleSimulation(_Run):
                  enkf_seed=None, enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0,
                  enkf_window_offsets=(), enkf_shard=None, filter_shard=None, filter_soil_moisture=None,
                  theta_hist_bins=0, storage_layers_cm=None, storage_bins=0, period_ends=None, period_thresholds_cm=(),
-                 period_bins=0, period_flux_max_cm=(16.0, 4.0), filter_ess_floor=0.0):
+                 period_bins=0, period_flux_max_cm=(16.0, 4.0), filter_ess_floor=0.0, filter_window_offsets=()):
+        if filter_shard is not None and filter_window_offsets is not None and len(filter_window_offsets):
+            raise ValueError("filter_shard and filter_window_offsets exclude each other: the sharded filter gathers the "
+                             "water-table indices of the assimilation row only")
         if filter_shard is not None and period_ends is not None and len(period_ends):
             raise ValueError("period_ends and filter_shard exclude each other: the sharded filter routes the members' "
                              "columns, which do not carry the period accumulators")
@@ -425,7 +450,7 @@ class EnsembleSimulation(_Run):
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
                            enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins, storage_layers_cm,
-                           storage_bins, filter_ess_floor)
+                           storage_bins, filter_ess_floor, filter_window_offsets)
         self._start_periods(period_ends, period_thresholds_cm, period_bins, period_flux_max_cm)
         self.enkf_shard = None
         if enkf_shard is not None:
@@ -570,6 +595,11 @@ class EnsembleSimulation(_Run):
             if self.filter_ess_floor:                     # (an untempered run keeps its key set)
                 arrays["filter_ess_floor"] = np.array(self.filter_ess_floor, dtype=np.float64)
                 arrays["filter_temper_table"] = self.stepper.filter_temper_table()
+            if self.filter_window_offsets:                # what was recorded for the coming assimilation travels along
+                b, rows = self.stepper.filter_window_capture()
+                arrays["filter_window_offsets"] = np.asarray(self.filter_window_offsets, dtype=np.int64)
+                arrays["filter_window_table"] = self.stepper.filter_window_table()
+                arrays["filter_window_index"], arrays["filter_window_rows"] = b, rows
         if self.enkf_stride:
             arrays["enkf_stride"] = np.array(self.enkf_stride, dtype=np.int64)
             arrays["enkf_sigma_cm"] = np.array(self.enkf_sigma_cm, dtype=np.float64)
@@ -654,6 +684,9 @@ class EnsembleSimulation(_Run):
 
         has_sm = record(enkf, "enkf", enkf_soil_moisture)
         has_fsm = record(filt, "filter", filter_soil_moisture)
+        has_fwin = bool(filt) and "filter_window_offsets" in data
+        if has_fwin:
+            fkw.update(filter_window_offsets=tuple(int(o) for o in np.asarray(data["filter_window_offsets"]).reshape(-1)))
         has_win = enkf and "enkf_window_offsets" in data
         if has_win:
             fkw.update(enkf_window_offsets=tuple(int(o) for o in np.asarray(data["enkf_window_offsets"]).reshape(-1)))
@@ -668,6 +701,10 @@ class EnsembleSimulation(_Run):
                 sim.stepper.set_filter_sm_table(np.asarray(data["filter_sm_table"], dtype=np.float64))
             if tempered:
                 sim.stepper.set_filter_temper_table(np.asarray(data["filter_temper_table"], dtype=np.float64))
+            if has_fwin:
+                sim.stepper.set_filter_window_table(np.asarray(data["filter_window_table"], dtype=np.float64))
+                sim.stepper.set_filter_window_capture(np.asarray(data["filter_window_index"], dtype=np.int32).reshape(-1, n),
+                                                      np.asarray(data["filter_window_rows"], dtype=np.int64))
         else:
             sim.stepper.set_noise_scale(np.asarray(data["noise_scale"], dtype=float).reshape(n))
         if enkf:
@@ -790,7 +827,8 @@ class SweepSimulation(_Run):
                  filter_seed=None, enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None,
                  enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=(),
                  filter_soil_moisture=None, theta_hist_bins=0, storage_layers_cm=None, storage_bins=0, period_ends=None,
-                 period_thresholds_cm=(), period_bins=0, period_flux_max_cm=(16.0, 4.0), filter_ess_floor=0.0):
+                 period_thresholds_cm=(), period_bins=0, period_flux_max_cm=(16.0, 4.0), filter_ess_floor=0.0,
+                 filter_window_offsets=()):
         self.points = list(cols_list)
         self.P, self.n = len(self.points), int(n_members)
         self._lead = (self.P,)
@@ -820,7 +858,7 @@ class SweepSimulation(_Run):
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
                            enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins, storage_layers_cm,
-                           storage_bins, filter_ess_floor)
+                           storage_bins, filter_ess_floor, filter_window_offsets)
         self._start_periods(period_ends, period_thresholds_cm, period_bins, period_flux_max_cm)
         self.next_row, self.kernel_ms, self.launches = 1, 0.0, 0
 

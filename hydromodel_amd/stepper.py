@@ -83,6 +83,7 @@ class EnsembleStepper:
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = 0, 0.0, 0
         self.filter_sm_nodes = None
         self.filter_ess_floor = 0.0
+        self.filter_window_offsets = ()
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
         self.enkf_sm_nodes = None
         self.enkf_method, self.enkf_relaxation = "stochastic", 0.0
@@ -583,6 +584,7 @@ class EnsembleStepper:
         self.filter_shard, self._filter_shard_keep = None, None                  # ... and the sharding with it
         self.filter_sm_nodes = None                                              # ... and the sensor record
         self.filter_ess_floor = 0.0                                              # ... and the tempering
+        self.filter_window_offsets = ()                                          # ... and the window
         L.check(self.lib.hc_set_filter(self.h, stride, sigma, int(seed) & 0xFFFFFFFFFFFFFFFF))
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = stride, sigma, int(seed)
 
@@ -591,6 +593,7 @@ class EnsembleStepper:
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = 0, 0.0, 0
         self.filter_sm_nodes = None
         self.filter_ess_floor = 0.0
+        self.filter_window_offsets = ()
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
         self.enkf_sm_nodes = None
         self.enkf_method, self.enkf_relaxation = "stochastic", 0.0
@@ -737,6 +740,57 @@ class EnsembleStepper:
         out = np.zeros((self.N, self.filter_sm_width()))
         L.check(self.lib.hc_get_filter_sm_theta(self.h, L.dptr(out)))
         return out
+
+    # -- the well's record inside the window, particle filter (include/hydrocol.h hc_set_filter_window) ------------------
+    def set_filter_window(self, offsets=()):
+        """Every member's water-table index on the rows ``offsets`` before an assimilation row (integers in [1, stride),
+        distinct, at most 8 together with the sensors) is recorded when the row is solved and joins that row's weight as a
+        further well-type term: the weight is then the likelihood of everything the member's trajectory passed since the
+        last resampling.  Empty or None turns it off.  The filter must be on (:meth:`set_filter` first; it turns the
+        window off again) and not sharded."""
+        off = filter_window_settings(offsets, self.filter_stride, self.filter_sm_n)
+        self.filter_window_offsets = ()
+        a = np.ascontiguousarray(off, dtype=np.int32)
+        L.check(self.lib.hc_set_filter_window(self.h, a.size, L.iptr(a) if a.size else None))
+        self.filter_window_offsets = off
+
+    @property
+    def filter_window_n(self):
+        return len(self.filter_window_offsets)
+
+    def filter_window_table(self):
+        """[P][n_arow][n][4] float64 per assimilation slot and offset: observed (0/1), observation, forecast mean and std
+        of the members' water-table depth on the lagged row (cm from the top node); NaN where the slot's assimilation had
+        no lagged row (and after observed = 0)."""
+        t = np.zeros((self.P, stride_rows(self.T, self.filter_stride), self.filter_window_n, WINDOW_WIDTH))
+        L.check(self.lib.hc_get_filter_window_stats(self.h, L.dptr(t), t.size))
+        return t
+
+    def set_filter_window_table(self, table):
+        t = L.as_f64(table).reshape(-1)
+        L.check(self.lib.hc_set_filter_window_stats(self.h, L.dptr(t), t.size))
+
+    def filter_window_capture(self):
+        """(b [n][N] int32, rows [n] int64): the water-table indices the window holds for the coming assimilation (row
+        -1: nothing; checkpoints)."""
+        b = np.zeros((self.filter_window_n, self.N), dtype=np.int32)
+        rows = np.zeros(self.filter_window_n, dtype=np.int64)
+        L.check(self.lib.hc_get_filter_window_capture(self.h, L.iptr(b), L.lptr(rows)))
+        return b, rows
+
+    def set_filter_window_capture(self, b, rows):
+        b = np.ascontiguousarray(b, dtype=np.int32)
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        if b.shape != (self.filter_window_n, self.N) or rows.size != self.filter_window_n:
+            raise ValueError(f"the window's capture must be [{self.filter_window_n}, {self.N}] with as many rows")
+        L.check(self.lib.hc_set_filter_window_capture(self.h, L.iptr(b), L.lptr(rows)))
+
+    def filter_window_slots(self):
+        """The indices into ``filter_window_offsets`` of the last assimilation's lagged columns, in column order (test
+        hook)."""
+        w, slots = np.zeros(1, dtype=np.int32), np.zeros(SM_MAX_SENSORS, dtype=np.int32)
+        L.check(self.lib.hc_get_filter_window_width(self.h, L.iptr(w), L.iptr(slots)))
+        return slots[:int(w[0])].copy()
 
     # -- one point's members on several handles, particle filter (include/hydrocol.h hc_set_filter_shard) ----------------
     def filter_shard_words(self, bounds, index):
@@ -1735,10 +1789,12 @@ def filter_ancestors_of(q_members, r):
     return anc
 
 
-def filter_member_loglik(w, theta, obs_idx, theta_obs, dz, sigma_cm, sigma):
+def filter_member_loglik(w, theta, obs_idx, theta_obs, dz, sigma_cm, sigma, lag_w=None, lag_obs_idx=None):
     """[N] l_m of a sensor row (include/hydrocol.h hc_set_filter_soil_moisture), the device's IEEE operations in its order:
     ``w`` [N] water-table indices, ``theta`` [N][m_s] at the present sensors' nodes, ``obs_idx`` the well's index,
-    ``theta_obs`` and ``sigma`` [m_s] the present sensors' values and errors in record order."""
+    ``theta_obs`` and ``sigma`` [m_s] the present sensors' values and errors in record order.  With a window
+    (hc_set_filter_window) ``lag_w`` [N][m_w] the members' indices on the present lagged rows by ascending offset and
+    ``lag_obs_idx`` [m_w] the indices observed there: their terms follow the sensors'."""
     w = np.asarray(w, dtype=np.int64)
     theta = np.asarray(theta, dtype=np.float64).reshape(w.size, -1)
     theta_obs, sigma = (np.asarray(v, dtype=np.float64).reshape(-1) for v in (theta_obs, sigma))
@@ -1748,6 +1804,14 @@ def filter_member_loglik(w, theta, obs_idx, theta_obs, dz, sigma_cm, sigma):
         for i in range(theta.shape[1]):
             u = (theta[:, i] - theta_obs[i]) / sigma[i]
             a = a + u * u
+        if lag_w is not None:
+            lag_w = np.asarray(lag_w, dtype=np.int64).reshape(w.size, -1)
+            lag_obs = np.asarray(lag_obs_idx, dtype=np.int64).reshape(-1)
+            if lag_obs.size != lag_w.shape[1]:
+                raise ValueError(f"{lag_w.shape[1]} lagged columns, {lag_obs.size} observed indices")
+            for j in range(lag_w.shape[1]):
+                tj = np.float64(dz) * (lag_w[:, j] - int(lag_obs[j])).astype(np.float64) / np.float64(sigma_cm)
+                a = a + tj * tj
     return -0.5 * a
 
 
@@ -1981,34 +2045,40 @@ def filter_sm_summary(table, stride, sigma):
 WINDOW_WIDTH = 4
 
 
-def enkf_window_settings(offsets, stride, n_sensors=0):
+def enkf_window_settings(offsets, stride, n_sensors=0, who="EnKF", filt="the EnKF"):
     """The window's offsets as a tuple in ascending order (``()``: off).  A ValueError unless ``offsets`` is a list or
     tuple of distinct integers in [1, stride) -- no booleans, no floats -- of at most 8 entries, at most 8 together with
-    ``n_sensors`` soil-moisture sensors; any offset needs the EnKF (stride > 0)."""
+    ``n_sensors`` soil-moisture sensors; any offset needs the EnKF (stride > 0).  ``who`` and ``filt`` name the block and
+    the filter in the messages (:func:`filter_window_settings`: the particle filter's window, the same rules)."""
     if offsets is None:
         return ()
     if not isinstance(offsets, (list, tuple)):
-        raise ValueError(f"EnKF Window_Offsets = {offsets!r} must be a list of integers")
+        raise ValueError(f"{who} Window_Offsets = {offsets!r} must be a list of integers")
     for o in offsets:
         if isinstance(o, (bool, np.bool_)) or not isinstance(o, (int, np.integer)):
-            raise ValueError(f"EnKF Window_Offsets: {o!r} is not an integer")
+            raise ValueError(f"{who} Window_Offsets: {o!r} is not an integer")
     off = tuple(sorted(int(o) for o in offsets))
     if not off:
         return ()
     stride = int(stride or 0)
     if stride <= 0:
-        raise ValueError("EnKF Window_Offsets need the EnKF (Stride > 0)")
+        raise ValueError(f"{who} Window_Offsets need {filt} (Stride > 0)")
     for o in off:
         if not 1 <= o < stride:
-            raise ValueError(f"EnKF Window_Offsets: {o} lies outside [1, {stride}) (rows before the analysis row, below Stride)")
+            raise ValueError(f"{who} Window_Offsets: {o} lies outside [1, {stride}) (rows before the analysis row, below Stride)")
     if len(set(off)) != len(off):
-        raise ValueError(f"EnKF Window_Offsets = {list(off)} repeats an offset")
+        raise ValueError(f"{who} Window_Offsets = {list(off)} repeats an offset")
     if len(off) > SM_MAX_SENSORS:
-        raise ValueError(f"EnKF Window_Offsets: {len(off)} offsets, at most {SM_MAX_SENSORS}")
+        raise ValueError(f"{who} Window_Offsets: {len(off)} offsets, at most {SM_MAX_SENSORS}")
     if len(off) + int(n_sensors) > SM_MAX_SENSORS:
-        raise ValueError(f"EnKF Window_Offsets: {len(off)} offsets and {int(n_sensors)} soil-moisture sensors, at most "
+        raise ValueError(f"{who} Window_Offsets: {len(off)} offsets and {int(n_sensors)} soil-moisture sensors, at most "
                          f"{SM_MAX_SENSORS} together")
     return off
+
+
+def filter_window_settings(offsets, stride, n_sensors=0):
+    """:func:`enkf_window_settings` for the particle filter's window (include/hydrocol.h hc_set_filter_window)."""
+    return enkf_window_settings(offsets, stride, n_sensors, who="Filter", filt="the particle filter")
 
 
 def enkf_window_summary(table, stride, offsets, z0_cm=0.0):
@@ -2027,6 +2097,13 @@ def enkf_window_summary(table, stride, offsets, z0_cm=0.0):
             "observed": observed, "obs_cm": sel[..., 1] + z0_cm, "prior_mean_cm": sel[..., 2] + z0_cm,
             "prior_std_cm": sel[..., 3], "innovation_cm": sel[..., 1] - sel[..., 2],
             "n_obs": int(first.sum()), "n_rows": int(first.any(axis=-1).sum())}
+
+
+def filter_window_summary(table, stride, offsets, z0_cm=0.0):
+    """The particle filter's window record from its [..., n_arow, n, 4] table: the keys of :func:`enkf_window_summary`, the
+    layout being the same -- ``prior_*`` the forecast ensemble's water-table depth on the lagged row, ``n_obs`` the lagged
+    observations weighed, ``n_rows`` the assimilation rows that took any."""
+    return enkf_window_summary(table, stride, offsets, z0_cm)
 
 
 def allreduce_handles(steppers):

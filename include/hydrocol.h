@@ -623,6 +623,60 @@ int hc_get_filter_member_weights(hc_handle *h, int64_t *q);
 int hc_get_filter_loglik(hc_handle *h, double *l);
 int hc_get_filter_sm_theta(hc_handle *h, double *theta);
 
+/* The well's record inside the window, particle filter (sequential importance sampling with delayed resampling): nothing
+ * is resampled between two assimilation rows, so slot k is one trajectory over the whole window, and its importance weight
+ * at the assimilation row is the product of the likelihoods of every observation that trajectory passed.  At chosen rows
+ * before an assimilation row each member's water-table index is recorded when the row is solved, and at the assimilation
+ * those indices join the member's weight as further well-type terms.  The mean of the products is still the unbiased
+ * estimate of the window's marginal likelihood.  No state is stored, no row is solved twice, the step kernels are not
+ * involved.  The counterpart of hc_set_enkf_window, with its rules.
+ *   offsets [n_offsets] (<= 8, and n_offsets + n_sensors <= 8): rows before the assimilation row, integers in [1, stride),
+ *   distinct; kept in ascending order.  For assimilation row r and offset o the lagged row r_j = r - o takes part when
+ *   r_j >= 1, wtd_obs[r_j] >= 0 and r is an assimilation row, all as wtd_obs stands; otherwise it is absent on that
+ *   assimilation, like a sensor without a value.
+ *   Capture: a launch ends on every lagged row that takes part; then b_m(r_j) of every member -- the index wtd_out returns
+ *   for that row -- goes into a device buffer [n_offsets][n_members] with rows [n_offsets] beside it (-1: none), which the
+ *   assimilation empties.  A lagged row solved before hc_set_filter_window, or by another handle, is absent unless
+ *   hc_set_filter_window_capture brought it.
+ *   Weights at r with m_w >= 1 present lagged rows: the row takes the per-member path of hc_set_filter_soil_moisture, also
+ *   when no sensor has a value (m_s = 0); fp64 without contraction:
+ *     t_w = dz * (double)(b_m - o) / sigma_cm;  a = t_w * t_w;  the present sensors' u * u in record order, as there;
+ *     then for each present lagged row by ascending offset:
+ *     t_j = dz * (double)(b_m(r_j) - wtd_obs[r_j]) / sigma_cm;  a += t_j * t_j;  then l_m = -0.5 * a;
+ *     a member whose index on r or on any present lagged row is >= D, or whose l_m is not finite, is not counted and gets
+ *     q_m = 0.  s, e_m, q_m, the exact integer sums and the ESS, the draw (the same Philox counter), the scan, the fill and
+ *     the gather, tempering (on l_m - s), the period accumulators' gather and the sensors' posterior moments run unchanged
+ *     on that l_m.  R stays diagonal: correlated errors of the well's record are not modelled.
+ *   The increment, in this order: s + log(W / count) - log(sigma_cm), - log(sigma_i) for each present sensor in record
+ *     order, - log(sigma_cm) once for each present lagged row by ascending offset,
+ *     - 0.5 * (double)(1 + m_s + m_w) * log(2 pi): the joint log-density of everything the window's trajectories passed
+ *     (log cm^-(1 + m_w) (m^3/m^3)^-m_s).
+ *   A row on which no lagged row takes part runs exactly the path it runs without a window: the bin path, or the sensor
+ *   path.  The same bits at any launch length, point order or dealing of a sweep's points to handles or ranks.
+ *   Window diagnostics, float64 [P][n_arow][n_offsets][4]: observed (0/1), observation dz * wtd_obs[r_j], forecast mean
+ *   (sum / N_p) and std (two passes, / (N_p - 1), 0 for N_p = 1) of dz * (double)b_m(r_j) over the point's N_p members,
+ *   every sum in the tile order of the sensor rows (cm from the top node; the host adds z[0] to the observation and the
+ *   mean).  An offset absent on a row that has lagged rows: observed = 0, the rest NaN; a slot without any lagged row: NaN.
+ * hc_set_filter_window: n_offsets = 0 turns it off: every bit, launch and allocation is then that of hc_set_filter.  Needs
+ *   the particle filter on (hc_set_filter first); HC_ERR_ARG for an offset outside [1, stride), a repeated one, too many
+ *   (hc_set_filter_soil_moisture refuses likewise when the sensors come second), while the EnKF is on, and while
+ *   hc_set_filter_shard is set -- which is refused in turn while a window is set: the sharded filter gathers the indices
+ *   of the assimilation row only.  Whatever turns the filter off removes the window (hc_set_filter included).
+ *   (Re)creates the table (NaN) and empties the buffer.
+ * hc_get/set_filter_window_stats: the table (P n_arow n_offsets 4 entries; checkpoints, the assembly of a sweep over ranks).
+ * hc_get/set_filter_window_capture: b int32 [n_offsets][n_members] and rows [n_offsets], the lagged row each offset holds
+ *   for the coming assimilation (-1: none; its indices read 0): what a checkpoint between a capture and its assimilation
+ *   must carry.  Indices lie in [0, 65535] (HC_ERR_ARG else).
+ * Test hooks of the last assimilation: hc_get_filter_window_width (m_w and, slots != NULL, the offsets' indices of the
+ *   lagged columns in column order); hc_get_filter_loglik and hc_get_filter_member_weights keep returning l_m and q_m,
+ *   also with a window and no soil-moisture record. */
+int hc_set_filter_window(hc_handle *h, int32_t n_offsets, const int32_t *offsets);
+int hc_get_filter_window_stats(hc_handle *h, double *table, int64_t n_entries);
+int hc_set_filter_window_stats(hc_handle *h, const double *table, int64_t n_entries);
+int hc_get_filter_window_capture(hc_handle *h, int32_t *b, int64_t *rows);
+int hc_set_filter_window_capture(hc_handle *h, const int32_t *b, const int64_t *rows);
+int hc_get_filter_window_width(hc_handle *h, int32_t *width, int32_t *slots);
+
 /* Ensemble Kalman filter on the well's water table (stochastic EnKF: perturbed observations, Evensen 1994 / Burgers et al.
  * 1998).  It moves every member's psi by the sample covariance between psi and the observed quantity; noise is untouched.
  *   Analysis rows, launches and order: as for hc_set_filter -- r >= 1, r % stride == 0 and wtd_obs[r] >= 0 (as it stands

@@ -2,7 +2,8 @@
 assimilations every 48th row (one a day), one handle each, back to back on one GPU.
 
     python tools/filter_cost.py [--members 262144] [--depth 300] [--days 30] [--warmup 1] [--strides 0,48]
-                                [--sigma 10] [--spread-cm 0] [--sensors 0,0] [--ess-floor 0,0.5] [--json out.json]
+                                [--sigma 10] [--spread-cm 0] [--sensors 0,0] [--ess-floor 0,0.5] [--window 0,1]
+                                [--window-offsets 12,24,36] [--json out.json]
 
 Same set-up as tools/wtd_dist_cost.py and bench.py's timed region: synthetic 10-year forcing, Philox noise, the shared
 initial condition of the well's digest (tests/golden/g1_tables_<depth>.npz where it exists, else the hydrostatic profile),
@@ -18,7 +19,9 @@ whose slot ranges are long.  --sensors lists, run by run like --strides, how man
 so every assimilation takes the per-member path; one count serves every run).  --ess-floor lists, run by run, the floor
 of the tempered weights (hc_set_filter_tempering; 0 = off, the untempered path): `tempered_rows` and `beta_min` over the
 timed assimilations, and -- when no run has stride 0 -- `kept` and `temper_ms_per_assimilation` are taken against the
-mean of the runs with floor 0.  Prints one JSON line.
+mean of the runs with floor 0.  --window lists, run by run, whether the well's record inside the window joins the weights
+(hc_set_filter_window with --window-offsets; 1 = on): `lagged_per_assimilation`, and -- when no run has stride 0 and no
+floor is set -- `kept` and `window_ms_per_assimilation` against the mean of the runs without a window.  Prints one JSON line.
 """
 import argparse
 import json
@@ -33,7 +36,7 @@ sys.path.insert(0, str(REPO))
 
 
 def run(cols, forcing, psi0, members, stride, sigma, warmup_days, days, spread_cm=0.0, seed=2024, sensors=0,
-        sensor_sigma=0.05, ess_floor=0.0):
+        sensor_sigma=0.05, ess_floor=0.0, window=()):
     from hydromodel_amd.stepper import EnsembleStepper, filter_summary
     st = EnsembleStepper(cols, forcing, members)
     try:
@@ -51,6 +54,8 @@ def run(cols, forcing, psi0, members, stride, sigma, warmup_days, days, spread_c
             st.set_filter_soil_moisture([6 * (1 << i) for i in range(sensors)], values, sensor_sigma)
         if stride and ess_floor:
             st.set_filter_tempering(ess_floor)
+        if stride and window:
+            st.set_filter_window(window)
         row = 1
         if warmup_days:
             st.step_rows(row, 48 * warmup_days)
@@ -60,7 +65,8 @@ def run(cols, forcing, psi0, members, stride, sigma, warmup_days, days, spread_c
         out = st.step_rows(row, 48 * days)
         st.lib.hc_synchronize(st.h)
         wall = time.perf_counter() - t0
-        rec = {"stride": stride, "sensors": sensors if stride else 0, "ess_floor": ess_floor if stride else 0.0, "wall_s": wall, "step_kernel_ms": out["kernel_ms"], "launches": out["launches"],
+        rec = {"stride": stride, "sensors": sensors if stride else 0, "ess_floor": ess_floor if stride else 0.0,
+               "window": list(window) if stride else [], "wall_s": wall, "step_kernel_ms": out["kernel_ms"], "launches": out["launches"],
                "other_ms": 1e3 * wall - out["kernel_ms"], "column_days_per_s": members * days / wall}
         if stride:
             s = filter_summary(st.filter_table()[0], stride, sigma)
@@ -73,6 +79,9 @@ def run(cols, forcing, psi0, members, stride, sigma, warmup_days, days, spread_c
                 beta = st.filter_temper_table()[0, s["rows"] // stride, 0][timed]
                 rec["tempered_rows"] = int((beta < 1.0).sum())
                 rec["beta_min"] = float(np.nanmin(beta)) if timed.any() else None
+            if window:
+                wt = st.filter_window_table()[0, s["rows"] // stride, :, 0][timed]
+                rec["lagged_per_assimilation"] = float((wt == 1.0).sum() / max(int(timed.sum()), 1))
             if timed.any():
                 rec["longest_range"] = int(np.bincount(st.filter_ancestors(), minlength=members).max())   # the last one
         return rec
@@ -93,6 +102,8 @@ def main():
     ap.add_argument("--sensors", default="")
     ap.add_argument("--sensor-sigma", type=float, default=0.05)
     ap.add_argument("--ess-floor", default="")
+    ap.add_argument("--window", default="")
+    ap.add_argument("--window-offsets", default="12,24,36")
     ap.add_argument("--json", default="")
     args = ap.parse_args()
     from hydromodel_amd.digest import ColumnTables, ForcingDigest
@@ -112,8 +123,13 @@ def main():
     floors = [float(s) for s in args.ess_floor.split(",")] if args.ess_floor else [0.0] * len(strides)
     if len(floors) != len(strides):
         ap.error("--ess-floor lists one floor per entry of --strides")
+    offsets = tuple(int(o) for o in args.window_offsets.split(","))
+    windows = [offsets if int(w) else () for w in args.window.split(",")] if args.window else [()] * len(strides)
+    if len(windows) != len(strides):
+        ap.error("--window lists one flag per entry of --strides")
     recs = [run(cols, forcing, psi0, args.members, s, args.sigma, args.warmup, args.days, args.spread_cm, sensors=n,
-                sensor_sigma=args.sensor_sigma, ess_floor=f) for s, n, f in zip(strides, sensors, floors)]
+                sensor_sigma=args.sensor_sigma, ess_floor=f, window=w)
+            for s, n, f, w in zip(strides, sensors, floors, windows)]
     base = [r for r in recs if r["stride"] == 0]
     if base:
         rate = float(np.mean([r["column_days_per_s"] for r in base]))
@@ -131,6 +147,16 @@ def main():
             r["other_ms_per_assimilation"] = r["other_ms"] / max(r.get("assimilations", 0), 1)
             if r["ess_floor"] and r.get("assimilations"):
                 r["temper_ms_per_assimilation"] = (r["other_ms"] - other) / r["assimilations"]
+    plain = [r for r in recs if r["stride"] and not r["ess_floor"] and not r["window"]]
+    if not base and plain and any(r["window"] for r in recs) and not any(r["ess_floor"] for r in recs):
+        rate = float(np.mean([r["column_days_per_s"] for r in plain]))
+        other = float(np.mean([r["other_ms"] for r in plain]))
+        step = float(np.mean([r["step_kernel_ms"] for r in plain]))
+        for r in recs:
+            r["kept"] = r["column_days_per_s"] / rate
+            if r["window"] and r.get("assimilations"):
+                r["window_ms_per_assimilation"] = (r["other_ms"] - other) / r["assimilations"]
+                r["window_step_kernel_ms_per_assimilation"] = (r["step_kernel_ms"] - step) / r["assimilations"]
     line = json.dumps({"members": args.members, "depth": args.depth, "days": args.days, "sigma_cm": args.sigma, "spread_cm": args.spread_cm,
                        "runs": recs})
     print(line)
