@@ -104,6 +104,13 @@ def _analysis_numpy(psi, y, eps, obs, dz, sigma, loc, mpp):
     (1, 1, 2500, 0.0), (1, 2, 2500, 80.0),                 # not a multiple of 64 or of a 256-member tile
 ])
 def test_analysis_against_numpy(well, P, mpp, loc, noise):
+    _check_analysis(well, P, mpp, loc, noise)
+
+
+def _check_analysis(well, P, mpp, loc, noise, find_wtd=_find_wtd, y_of=_y_of, analysis=_analysis_numpy, eps_members=None,
+                    mean_std=lambda x: (x.mean(), x.std(ddof=1))):
+    """``find_wtd``, ``y_of``, ``analysis``, ``mean_std``: the restatements (a large ensemble passes forms without a loop
+    over the members and with long sums); ``eps_members``: the members whose draw is restated (None: every member)."""
     N = P * mpp
     st, cols, forcing = _stepper(well, N, P, noise)
     D, dz, sigma, seed = cols.dim_d, cols.dz, 5.0, 11
@@ -122,13 +129,15 @@ def test_analysis_against_numpy(well, P, mpp, loc, noise):
     finally:
         st.close()
     w, forecast = out["wtd"][0].astype(np.int64), out["psi"][0]
-    assert np.array_equal(_find_wtd(forecast, psat), w)                      # b is the row's wtd_out
-    y_np = _y_of(forecast, w, psat, dz)
+    assert np.array_equal(find_wtd(forecast, psat), w)                       # b is the row's wtd_out
+    y_np = y_of(forecast, w, psat, dz)
     assert np.all(np.abs(y - y_np) <= 1e-12 * (1.0 + np.abs(y_np)))
     assert np.unique(y).size > np.unique(w).size                            # spread below one cell: a continuous y
-    eps_np = np.array([_eps_restated(seed, m, 48) for m in range(N)])         # one handle: global id = m
-    assert np.all(np.abs(eps - eps_np) <= 1e-13 * (1.0 + np.abs(eps_np)))
-    K_np, post_np = _analysis_numpy(forecast, y, eps, obs, dz, sigma, loc, mpp)
+    members = np.arange(N) if eps_members is None else np.asarray(eps_members)
+    eps_np = np.array([_eps_restated(seed, int(m), 48) for m in members])    # one handle: global id = m
+    assert eps.shape == (N,) and np.isfinite(eps).all()
+    assert np.all(np.abs(eps[members] - eps_np) <= 1e-13 * (1.0 + np.abs(eps_np)))
+    K_np, post_np = analysis(forecast, y, eps, obs, dz, sigma, loc, mpp)
     assert np.all(np.abs(K - K_np) <= 1e-10 * np.abs(K_np).max() + 1e-300)
     assert np.abs(K).max() > 0.0
     assert np.all(np.abs(post - post_np) <= 1e-9 * (1.0 + np.abs(post_np)))
@@ -136,16 +145,18 @@ def test_analysis_against_numpy(well, P, mpp, loc, noise):
     for p in range(P):
         sl = slice(p * mpp, (p + 1) * mpp)
         t = table[p, 1]
-        yb, v = y[sl].mean(), y[sl].var(ddof=1)
+        yb, sd = mean_std(y[sl])
+        v = sd * sd
         assert t[0] == mpp and t[7] == 0
-        assert abs(t[1] - yb) <= 1e-12 * abs(yb) and abs(t[2] - np.sqrt(v)) <= 1e-10 * np.sqrt(v)
+        assert abs(t[1] - yb) <= 1e-12 * abs(yb) and abs(t[2] - sd) <= 1e-10 * sd
         assert abs(t[3] - (obs * dz - yb)) <= 1e-10 * (1.0 + abs(t[3]))
         s2 = v + sigma * sigma
         inc = -0.5 * np.log(2.0 * np.pi * s2) - 0.5 * (obs * dz - yb) ** 2 / s2
         assert abs(t[4] - inc) <= 1e-10 * max(1.0, abs(inc))
-        y_post = _y_of(post[sl], _find_wtd(post[sl], psat), psat, dz)
-        assert abs(t[5] - y_post.mean()) <= 1e-9 * (1.0 + abs(y_post.mean()))
-        assert abs(t[6] - y_post.std(ddof=1)) <= 1e-9 * (1.0 + y_post.std(ddof=1))
+        y_post = y_of(post[sl], find_wtd(post[sl], psat), psat, dz)
+        yb_post, sd_post = mean_std(y_post)
+        assert abs(t[5] - yb_post) <= 1e-9 * (1.0 + abs(yb_post))
+        assert abs(t[6] - sd_post) <= 1e-9 * (1.0 + sd_post)
         assert np.isnan(table[p, 2:, 1:]).all() and np.all(table[p, 2:, 0] == 0)
 
 

@@ -60,13 +60,14 @@ class CardExchange:
         return exchange
 
 
-def _handle(lo, hi, case, exchange="unsharded", n_global=N):
-    """Members [lo, hi) of the ensemble, set up as ``case`` says; ``exchange`` = "unsharded": no hc_set_enkf_shard."""
+def _handle(lo, hi, case, exchange="unsharded", n_global=N, well=WELL):
+    """Members [lo, hi) of the ensemble of ``n_global``, set up as ``case`` says; ``exchange`` = "unsharded": no
+    hc_set_enkf_shard."""
     from hydromodel_amd.stepper import EnsembleStepper
     method, alpha, sensors, window, loc = CASES[case]
-    _, cols, forcing = digest(WELL)
+    _, cols, forcing = digest(well)
     st = EnsembleStepper(cols, forcing, hi - lo)
-    st.set_state(_spread(golden(f"g1_tables_{WELL}.npz")["initial_cond"], N)[lo:hi])
+    st.set_state(_spread(golden(f"g1_tables_{well}.npz")["initial_cond"], n_global)[lo:hi])
     st.set_noise_philox(SEED, lo)
     st.set_enkf(STRIDE, 2.0 * cols.dz, loc, 3)
     if sensors:
@@ -90,15 +91,18 @@ def _results(st, case):
     return out
 
 
-def _run_together(bounds, case):
-    """One handle per block of ``bounds`` stepping ROWS rows at once; every handle's results, in block order."""
+def _run_together(bounds, case, rows=ROWS, n_global=N, well=WELL, look=None):
+    """One handle per block of ``bounds`` stepping ``rows`` rows at once; every handle's results, in block order.
+    ``look(handles)`` is called before they step."""
     card = CardExchange(len(bounds))
-    handles = [_handle(lo, hi, case, card.of(k)) for k, (lo, hi) in enumerate(bounds)]
+    handles = [_handle(lo, hi, case, card.of(k), n_global, well) for k, (lo, hi) in enumerate(bounds)]
+    if look:
+        look(handles)
     failures = [None] * len(bounds)
 
     def work(k):
         try:
-            handles[k].step_rows(1, ROWS)
+            handles[k].step_rows(1, rows)
         except BaseException as e:  # noqa: BLE001
             failures[k] = e
             card.barrier.abort()                                    # the others must not wait for this one

@@ -29,6 +29,13 @@ VARIANTS = [("sqrt", 0.0), ("sqrt", 0.5), ("stochastic", 0.5)]
     (1, 2, 100, 0.0, 0), (300, 1, 2500, 50.0, 0),             # ... and the well alone
 ])
 def test_analysis_against_numpy(well, P, mpp, loc, n_s, noise, method, alpha):
+    _check_analysis(well, P, mpp, loc, n_s, noise, method, alpha)
+
+
+def _check_analysis(well, P, mpp, loc, n_s, noise, method, alpha, find_wtd=_find_wtd, y_of=_y_of,
+                    sqrt_analysis=sqrt_analysis_restated, analysis=analysis_restated, rtps=rtps_restated,
+                    mean_std=lambda x: (x.mean(), x.std(ddof=1)), std_columns=lambda x: x.std(axis=0, ddof=1)):
+    """The restatements are arguments: a large ensemble passes forms without a loop over the members and with long sums."""
     N = P * mpp
     st, cols, forcing = _stepper(well, N, P, noise)
     D, dz, sigma, seed = cols.dim_d, cols.dz, 5.0, 11
@@ -77,7 +84,7 @@ def test_analysis_against_numpy(well, P, mpp, loc, n_s, noise, method, alpha):
         assert got.shape == want.shape and err <= 1e-10, (tag, err)
 
     if method == "sqrt":
-        res = sqrt_analysis_restated(forecast, Y, o, R, zeta_nodes, dz, loc, mpp)
+        res = sqrt_analysis(forecast, Y, o, R, zeta_nodes, dz, loc, mpp)
         close(K, res["K"], "K")
         close(Kr, res["Kr"], "Kr")
         close(dbar, res["dbar"], "dbar")
@@ -86,11 +93,11 @@ def test_analysis_against_numpy(well, P, mpp, loc, n_s, noise, method, alpha):
             assert np.all(np.abs(Kr) <= np.abs(K))
     else:
         E = np.concatenate([eps_w[:, None], eps_s[:, present]], axis=1)
-        res = analysis_restated(forecast, Y, E, o, R, zeta_nodes, dz, loc, mpp)
+        res = analysis(forecast, Y, E, o, R, zeta_nodes, dz, loc, mpp)
         close(K, res["K"], "K")
     want = res["post"]
     if alpha:
-        sb_np, sa_np, f_np, want = rtps_restated(forecast, res["post"], alpha, mpp)
+        sb_np, sa_np, f_np, want = rtps(forecast, res["post"], alpha, mpp)
         close(sb, sb_np, "sigma_b")
         close(sa, sa_np, "sigma_a")
         assert np.all(np.abs(f - f_np) <= 1e-9 * np.abs(f_np)) and np.isfinite(f).all()
@@ -98,7 +105,7 @@ def test_analysis_against_numpy(well, P, mpp, loc, n_s, noise, method, alpha):
         for p in range(P):
             sl = slice(p * mpp, (p + 1) * mpp)
             blend = (1.0 - alpha) * sa[p] + alpha * sb[p]
-            assert np.abs(post[sl].std(axis=0, ddof=1) - blend).max() <= 1e-9 * sb[p].max()
+            assert np.abs(std_columns(post[sl]) - blend).max() <= 1e-9 * sb[p].max()
     err = float(np.max(np.abs(post - want) / (1.0 + np.abs(want))))
     print(f" states: {err:.1e}")
     assert err <= 1e-9
@@ -108,13 +115,15 @@ def test_analysis_against_numpy(well, P, mpp, loc, n_s, noise, method, alpha):
         t = table[p, 1]
         assert t[0] == mpp and t[7] == 0
         assert abs(t[1] - res["ybar"][p, 0]) <= 1e-12 * abs(res["ybar"][p, 0])
-        y_post = _y_of(post[sl], _find_wtd(post[sl], psat), psat, dz)        # the posterior describes the FINAL states
-        assert abs(t[5] - y_post.mean()) <= 1e-9 * (1.0 + abs(y_post.mean()))
-        assert abs(t[6] - y_post.std(ddof=1)) <= 1e-9 * (1.0 + y_post.std(ddof=1))
+        y_post = y_of(post[sl], find_wtd(post[sl], psat), psat, dz)          # the posterior describes the FINAL states
+        yb_post, sd_post = mean_std(y_post)
+        assert abs(t[5] - yb_post) <= 1e-9 * (1.0 + abs(yb_post))
+        assert abs(t[6] - sd_post) <= 1e-9 * (1.0 + sd_post)
         for k, i in enumerate(present):
             tp = theta_post[sl, k]
             s = smt[p, 1, i]
-            assert s[0] == 1.0 and abs(s[4] - tp.mean()) <= 1e-12 and abs(s[5] - tp.std(ddof=1)) <= 1e-10
+            tp_mean, tp_sd = mean_std(tp)
+            assert s[0] == 1.0 and abs(s[4] - tp_mean) <= 1e-12 and abs(s[5] - tp_sd) <= 1e-10
 
 
 def _run(well, N, rows, scheme=None, seed=3, sensors=True, P=1):

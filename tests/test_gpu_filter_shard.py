@@ -70,10 +70,11 @@ class CardExchange:
         return Exchange()
 
 
-def _initial(kind):
-    psi0 = golden(f"g1_tables_{WELL}.npz")["initial_cond"]
+def _initial(kind, n=N, well=WELL):
+    psi0 = golden(f"g1_tables_{well}.npz")["initial_cond"]
     if kind == "spread":
-        return _spread(psi0, N)
+        return _spread(psi0, n)
+    assert n == N, kind
     # "lower half": the water tables of members [0, 512) start within a cell of each other, those of members
     # [512, 1000) more than half a metre deeper
     # "one survivor": member 300 alone (a shard of its own in THREE) starts there
@@ -86,28 +87,29 @@ def _initial(kind):
 HALF_SHIFT_CM = 60.0
 
 
-def _handle(lo, hi, shard=None, sigma=None, noise="philox", initial="spread"):
-    """Members [lo, hi) of the ensemble; ``shard`` = (bounds, index, exchange) or None: no hc_set_filter_shard."""
+def _handle(lo, hi, shard=None, sigma=None, noise="philox", initial="spread", n=N, well=WELL):
+    """Members [lo, hi) of the ensemble of ``n``; ``shard`` = (bounds, index, exchange) or None: no hc_set_filter_shard."""
     from hydromodel_amd.stepper import EnsembleStepper
-    _, cols, forcing = digest(WELL)
+    _, cols, forcing = digest(well)
     st = EnsembleStepper(cols, forcing, hi - lo)
-    st.set_state(_initial(initial)[lo:hi])
+    st.set_state(_initial(initial, n, well)[lo:hi])
     if noise == "philox":
         st.set_noise_philox(SEED, lo)
     else:
-        st.set_noise_host(np.random.default_rng(SEED).standard_normal((N, cols.dim_d))[lo:hi])
+        st.set_noise_host(np.random.default_rng(SEED).standard_normal((n, cols.dim_d))[lo:hi])
     st.set_filter(STRIDE, 2.0 * cols.dz if sigma is None else sigma, FSEED)
     if shard is not None:
         st.set_filter_shard(*shard)
     return st
 
 
-def _step(st, lo, hi, rows, noise):
-    """rows [1, rows] in two calls (a call's refresh vectors, host noise: the handle's members of the ensemble's)"""
+def _step(st, lo, hi, rows, noise, n_all=N):
+    """rows [1, rows] in two calls (a call's refresh vectors, host noise: the handle's members of the ensemble's
+    ``n_all``)"""
     for r0, n in ((1, rows // 2), (1 + rows // 2, rows - rows // 2)):
         kw = {}
         if noise == "numpy":
-            fresh = np.random.default_rng(1000 + r0).standard_normal((st.n_refresh(r0, n), N, st.D))
+            fresh = np.random.default_rng(1000 + r0).standard_normal((st.n_refresh(r0, n), n_all, st.D))
             kw["fresh_noise"] = np.ascontiguousarray(fresh[:, lo:hi])
         st.step_rows(r0, n, **kw)
 
@@ -134,18 +136,19 @@ def _whole(sigma=None, noise="philox", initial="spread", rows=ROWS):
     return _WHOLE[key]
 
 
-def _run_together(bounds, sigma=None, noise="philox", initial="spread", rows=ROWS, exchange_of=None):
+def _run_together(bounds, sigma=None, noise="philox", initial="spread", rows=ROWS, exchange_of=None, well=WELL):
     """One handle per block of ``bounds`` stepping the rows at once: (every handle's results in block order, the card,
     the handles' failures)."""
     S = len(bounds) - 1
     card = CardExchange(S)
     make = exchange_of or CardExchange.of
-    handles = [_handle(bounds[k], bounds[k + 1], (bounds, k, make(card, k)), sigma, noise, initial) for k in range(S)]
+    handles = [_handle(bounds[k], bounds[k + 1], (bounds, k, make(card, k)), sigma, noise, initial, bounds[-1], well)
+               for k in range(S)]
     failures = [None] * S
 
     def work(k):
         try:
-            _step(handles[k], bounds[k], bounds[k + 1], rows, noise)
+            _step(handles[k], bounds[k], bounds[k + 1], rows, noise, bounds[-1])
         except BaseException as e:  # noqa: BLE001
             failures[k] = e
             card.barrier.abort()                                    # the others must not wait for this one
