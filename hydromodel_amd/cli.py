@@ -754,27 +754,13 @@ def filter_window_settings(ens):
     (the run, its file and its lines are then those of a block without it).  Pure, like :func:`filter_settings`: a bad
     value is a ValueError (message + exit status 1), by the rules and in the words of :func:`enkf_window_settings`.  Needs
     an active filter; refused together with ``"Sharded": true`` on a single-point run."""
-    from numbers import Real
-    from .stepper import filter_window_settings as window_of
     if "Window_Offsets" in ens:
         raise ValueError(" Ensemble: Window_Offsets belongs inside the \"Filter\" or the \"EnKF\" block.")
-    block = ens.get("Filter")
-    if not isinstance(block, dict) or block.get("Window_Offsets") is None:
-        return None
-    stride = block.get("Stride", 48)
-    stride = int(stride) if isinstance(stride, Real) and not isinstance(stride, bool) and stride == int(stride) else 0
-    if not stride:
-        raise ValueError(" Ensemble: Filter.Window_Offsets needs an active filter (Filter.Stride > 0).")
-    sm = block.get("Soil_Moisture")
-    depths = sm.get("Depths_cm") if isinstance(sm, dict) else None
-    try:
-        off = window_of(block["Window_Offsets"], stride, len(depths) if isinstance(depths, (list, tuple)) else 0)
-    except ValueError as bad:
-        raise ValueError(f" Ensemble: {bad}.") from None
-    if off and not ens.get("Points") and block.get("Sharded", False):
+    off = _window_settings(ens, "Filter")
+    if off and not ens.get("Points") and ens["Filter"].get("Sharded", False):
         raise ValueError(" Ensemble: Filter.Window_Offsets is not available with \"Sharded\": true: the sharded filter "
                          "gathers the members' water-table indices of the assimilation row only.")
-    return off or None
+    return off
 
 
 def _reduce_filter_window(ranks, sim, ids, P, T, filt, window, label, keep_points, z0_cm):
@@ -905,15 +891,23 @@ def enkf_window_settings(ens):
     value is a ValueError (message + exit status 1): not a list; an entry that is not an integer (a boolean, a float) or
     outside [1, Stride); a repeated entry; more than 8, alone or together with the Soil_Moisture depths.  Needs an active
     EnKF."""
+    return _window_settings(ens, "EnKF")
+
+
+def _window_settings(ens, owner):
+    """The body of :func:`enkf_window_settings` (``owner`` = "EnKF") and :func:`filter_window_settings` ("Filter"): the
+    owner's block read, its offsets checked against its stride and its Soil_Moisture depths."""
     from numbers import Real
-    from .stepper import enkf_window_settings as window_of
-    block = ens.get("EnKF")
+    from . import stepper
+    window_of = stepper.enkf_window_settings if owner == "EnKF" else stepper.filter_window_settings
+    block = ens.get(owner)
     if not isinstance(block, dict) or block.get("Window_Offsets") is None:
         return None
     stride = block.get("Stride", 48)
     stride = int(stride) if isinstance(stride, Real) and not isinstance(stride, bool) and stride == int(stride) else 0
     if not stride:
-        raise ValueError(" Ensemble: EnKF.Window_Offsets needs an active EnKF (EnKF.Stride > 0).")
+        what = "EnKF" if owner == "EnKF" else "filter"
+        raise ValueError(f" Ensemble: {owner}.Window_Offsets needs an active {what} ({owner}.Stride > 0).")
     sm = block.get("Soil_Moisture")
     depths = sm.get("Depths_cm") if isinstance(sm, dict) else None
     try:

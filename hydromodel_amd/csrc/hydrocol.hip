@@ -93,6 +93,49 @@ struct AccTable {
     void release() { buf.release(), invalidate(); }
 };
 
+// A filter's soil-moisture record (hc_set_filter_soil_moisture, hc_set_enkf_soil_moisture) on the host: nodes, sigma and
+// values [rows][n] (NaN = none); its diagnostics float64 [P][n_arow][n][6], keyed like the owner's table.  `width` is
+// the owner's own account of its last assimilation: the particle filter's m_s (0 = it took the bin path), the EnKF's
+// m' = 1 + m_s (0 = no sensor on it).
+struct SmRecord {
+    int n = 0;                   // 0: no record
+    int64_t rows = 0;
+    std::vector<int> nodes;
+    std::vector<double> sigma, values;
+    int width = 0;
+    AccTable<double> table{"entries"};
+    void clear()
+    {
+        n = width = 0;
+        rows = 0;
+        nodes.clear(); sigma.clear(); values.clear();
+        table.release();
+    }
+};
+
+// The well's record inside a filter's window (hc_set_filter_window, hc_set_enkf_window): the offsets, ascending; what
+// the owner keeps per member of the lagged rows, `cap` [n][N] (the particle filter: water-table indices, the EnKF: y),
+// and the row each slot holds (-1: none; cleared by the assimilation); diagnostics float64 [P][n_arow][n][4], keyed
+// like the owner's table; the last assimilation's lagged columns (their slots, in column order)
+struct WindowBase {
+    int n = 0;                   // 0: no window
+    std::vector<int> off;
+    std::vector<int64_t> row;
+    std::vector<int> last;
+    AccTable<double> table{"entries"};
+};
+template <typename T>
+struct Window : WindowBase {
+    DevBuf<T> cap;
+    void clear()
+    {
+        n = 0;
+        off.clear(); row.clear(); last.clear();
+        table.release();
+        cap.release();
+    }
+};
+
 }  // namespace
 
 struct hc_handle {
@@ -201,17 +244,11 @@ struct hc_handle {
     DevBuf<unsigned long long> filt_qr, filt_surv;
     std::vector<long long> filt_rows_host;
     std::vector<int> h_wtd_obs;
-    // soil-moisture sensors in the particle filter (hc_set_filter_soil_moisture): the record on the host, as the EnKF's;
-    // diagnostics float64 [P][n_arow][fsm_n][6] keyed like the filter's; fsm_width = the last assimilation's m_s, 0 =
-    // it took the bin path.  Per member (the last assimilation: test hooks) the weight q_m and the row (l_m, theta of
-    // the present sensors, exp(l_m - s)); per point and tile of FILT_TILE members the largest l_m, the integer sums
-    // (Q, sum q^2 in two words, count) and the partials of the column sums; per point s and the columns' sums and means
-    int fsm_n = 0;               // 0: no record
-    int64_t fsm_rows = 0;
-    std::vector<int> fsm_nodes;
-    std::vector<double> fsm_sigma, fsm_values;
-    int fsm_width = 0;
-    AccTable<double> fsm{"entries"};
+    // soil-moisture sensors in the particle filter (hc_set_filter_soil_moisture): the record.  Per member (the last
+    // assimilation: test hooks) the weight q_m and the row (l_m, theta of the present sensors, exp(l_m - s)); per point
+    // and tile of FILT_TILE members the largest l_m, the integer sums (Q, sum q^2 in two words, count) and the partials
+    // of the column sums; per point s and the columns' sums and means
+    SmRecord filt_sm;
     DevBuf<long long> filt_qm;
     DevBuf<double> filt_Y, filt_lmax, filt_part, filt_sums;
     DevBuf<unsigned long long> filt_ipart;
@@ -222,17 +259,10 @@ struct hc_handle {
     AccTable<double> ftemp{"entries"};
     DevBuf<long long> filt_trials, filt_tstate;
     DevBuf<unsigned long long> filt_tpart;
-    // the well's record inside the window (hc_set_filter_window): the offsets, ascending; each member's water-table index
-    // on the lagged rows [fwin_n][N] and the row each slot holds (-1: none; cleared by the assimilation); diagnostics
-    // float64 [P][n_arow][fwin_n][4] keyed like the filter's; the last assimilation's lagged columns (their slots, in
-    // column order); per member the largest of its indices on a windowed row (what counts it).  filt_ycols = the width
+    // the well's record inside the window (hc_set_filter_window): the window, of each member's water-table index on the
+    // lagged rows; per member the largest of its indices on a windowed row (what counts it).  filt_ycols = the width
     // of Y on the last assimilation, m_s + m_w + 2 (0: it took the bin path)
-    int fwin_n = 0;
-    std::vector<int> fwin_off;
-    std::vector<int64_t> fwin_row;
-    DevBuf<int> fwin_b;
-    std::vector<int> fwin_last;
-    AccTable<double> fwin{"entries"};
+    Window<int> filt_win;
     DevBuf<unsigned short> fwin_wmax;
     int filt_ycols = 0;
     // one point's members on several handles (hc_set_filter_shard): the shard count (0: off), this handle's index and the
@@ -253,7 +283,7 @@ struct hc_handle {
     std::vector<long long> fs_counts;
     std::vector<int64_t> fs_send_words, fs_recv_words;
     // ensemble Kalman filter (hc_set_enkf): diagnostics float64 [P][n_arow][8] keyed by (points, rows, stride); per
-    // member the observations Y [N][m'] (the well's y first), the well's eps, the sensors' eps [N][sm_n] and the
+    // member the observations Y [N][m'] (the well's y first), the well's eps, the sensors' eps [N][n_s] and the
     // posterior (y, theta..., rejected); per point the raw sums of both passes and the gain [P][m'][D] (the last
     // analysis: test hooks); the tile partials
     int enkf_stride = 0;         // 0: off
@@ -273,25 +303,12 @@ struct hc_handle {
     int enkf_last_method = 0;
     bool enkf_last_relaxed = false;
     DevBuf<double> enkf_rgain, enkf_dbar, enkf_part_sq, enkf_sq_b, enkf_sq_a, enkf_mean_a, enkf_relax;
-    // soil-moisture sensors in the EnKF analysis (hc_set_enkf_soil_moisture): the record on the host (nodes, sigma,
-    // values [sm_rows][sm_n], NaN = none); diagnostics float64 [P][n_arow][sm_n][6] keyed like the EnKF's; sm_width =
-    // the last analysis's m', 0 = no sensor on it
-    int sm_n = 0;                // 0: no record
-    int64_t sm_rows = 0;
-    std::vector<int> sm_nodes;
-    std::vector<double> sm_sigma, sm_values;
-    int sm_width = 0;
-    AccTable<double> sm{"entries"};
-    // the well's record inside the window (hc_set_enkf_window): the offsets, ascending; each member's y of the lagged
-    // rows [win_n][N] and the row each slot holds (-1: none; cleared by the analysis); diagnostics float64
-    // [P][n_arow][win_n][4] keyed like the EnKF's; the last analysis's lagged columns (their slots, in column order) and
-    // draws [N][m_w]
-    int win_n = 0;
-    std::vector<int> win_off;
-    std::vector<int64_t> win_row;
-    DevBuf<double> win_y, enkf_eps_w;
-    std::vector<int> win_last;
-    AccTable<double> win{"entries"};
+    // soil-moisture sensors in the EnKF analysis (hc_set_enkf_soil_moisture): the record
+    SmRecord enkf_sm;
+    // the well's record inside the window (hc_set_enkf_window): the window, of each member's y on the lagged rows; the
+    // last analysis's draws [N][m_w]
+    Window<double> enkf_win;
+    DevBuf<double> enkf_eps_w;
     // one point's members on several handles (hc_set_enkf_shard): the point's member count (0: off) and this handle's
     // first member in it; the caller's exchange buffer and callback; the point's first member's analysis column [D]
     int64_t shard_global = 0, shard_first = 0, shard_words = 0;
@@ -3171,8 +3188,26 @@ int ensure_da_table(hc_handle *h, AccTable<double> &t, int64_t stride, int64_t p
     return HC_OK;
 }
 
+// A record's diagnostics, [P][n_arow][n][6] float64, and a window's, [P][n_arow][n][4], both created as NaN: `owner`
+// ensures the filter's own table (ensure_filter, ensure_enkf), `stride` is its stride, `setter` the entry point that
+// sets the record or the window
+int ensure_record(hc_handle *h, SmRecord &r, int (*owner)(hc_handle *), int64_t stride, const char *setter)
+{
+    if (r.n <= 0) return fail(HC_ERR_ARG, "no soil-moisture record (%s)", setter);
+    if (int rc = owner(h)) return rc;
+    if (r.rows != h->n_rows)
+        return fail(HC_ERR_ARG, "the soil-moisture record has %lld rows, the forcing %lld: set the record again",
+                    (long long)r.rows, (long long)h->n_rows);
+    return ensure_da_table(h, r.table, stride, (int64_t)r.n * ENKF_SENSOR_WIDTH, 0);
+}
+int ensure_window(hc_handle *h, WindowBase &w, int (*owner)(hc_handle *), int64_t stride, const char *setter)
+{
+    if (w.n <= 0) return fail(HC_ERR_ARG, "no window offsets (%s)", setter);
+    if (int rc = owner(h)) return rc;
+    return ensure_da_table(h, w.table, stride, (int64_t)w.n * ENKF_WINDOW_WIDTH, 0);
+}
+
 // the particle filter's diagnostics (hc_set_filter): [P][n_arow][4] float64, created as count 0 and NaN
-int64_t filter_rows(const hc_handle *h) { return (h->n_rows - 1) / h->filt_stride + 1; }
 int ensure_filter(hc_handle *h)
 {
     if (h->filt_stride <= 0) return fail(HC_ERR_ARG, "the particle filter is off (hc_set_filter)");
@@ -3209,15 +3244,9 @@ FilterShardLayout filter_shard_layout(int64_t n_global, int64_t n, int64_t S, in
     return L;
 }
 
-// the filter's sensor diagnostics (hc_set_filter_soil_moisture): [P][n_arow][n][6] float64, created as NaN
 int ensure_fsm(hc_handle *h)
 {
-    if (h->fsm_n <= 0) return fail(HC_ERR_ARG, "no soil-moisture record (hc_set_filter_soil_moisture)");
-    if (int rc = ensure_filter(h)) return rc;
-    if (h->fsm_rows != h->n_rows)
-        return fail(HC_ERR_ARG, "the soil-moisture record has %lld rows, the forcing %lld: set the record again",
-                    (long long)h->fsm_rows, (long long)h->n_rows);
-    return ensure_da_table(h, h->fsm, h->filt_stride, (int64_t)h->fsm_n * ENKF_SENSOR_WIDTH, 0);
+    return ensure_record(h, h->filt_sm, ensure_filter, h->filt_stride, "hc_set_filter_soil_moisture");
 }
 
 // the table of the tempered weights (hc_set_filter_tempering): [P][n_arow][4] float64, created as NaN
@@ -3228,22 +3257,14 @@ int ensure_ftemp(hc_handle *h)
     return ensure_da_table(h, h->ftemp, h->filt_stride, TEMPER_WIDTH, 0);
 }
 
-// the window's diagnostics (hc_set_filter_window): [P][n_arow][n][4] float64, created as NaN
-int ensure_fwin(hc_handle *h)
-{
-    if (h->fwin_n <= 0) return fail(HC_ERR_ARG, "no window offsets (hc_set_filter_window)");
-    if (int rc = ensure_filter(h)) return rc;
-    return ensure_da_table(h, h->fwin, h->filt_stride, (int64_t)h->fwin_n * ENKF_WINDOW_WIDTH, 0);
-}
+int ensure_fwin(hc_handle *h) { return ensure_window(h, h->filt_win, ensure_filter, h->filt_stride, "hc_set_filter_window"); }
 
 void fwin_off(hc_handle *h)
 {
-    h->fwin_n = 0;
+    h->filt_win.clear();
     h->filt_ycols = 0;
-    h->fwin_off.clear(); h->fwin_row.clear(); h->fwin_last.clear();
-    h->fwin.release();
-    h->fwin_b.release(); h->fwin_wmax.release();
-    if (h->fsm_n <= 0) {
+    h->fwin_wmax.release();
+    if (h->filt_sm.n <= 0) {
         h->filt_qm.release(); h->filt_Y.release(); h->filt_lmax.release(); h->filt_part.release(); h->filt_sums.release();
         h->filt_ipart.release();
     }
@@ -3258,12 +3279,8 @@ void temper_off(hc_handle *h)
 
 void fsm_off(hc_handle *h)
 {
-    h->fsm_n = 0;
-    h->fsm_rows = 0;
-    h->fsm_width = 0;
+    h->filt_sm.clear();
     h->filt_ycols = 0;
-    h->fsm_nodes.clear(); h->fsm_sigma.clear(); h->fsm_values.clear();
-    h->fsm.release();
     h->filt_qm.release(); h->filt_Y.release(); h->filt_lmax.release(); h->filt_part.release(); h->filt_sums.release();
     h->filt_ipart.release();
 }
@@ -3284,7 +3301,6 @@ void filter_off(hc_handle *h)
 }
 
 // the EnKF's diagnostics (hc_set_enkf): [P][n_arow][8] float64, created as count 0 and NaN
-int64_t enkf_rows(const hc_handle *h) { return (h->n_rows - 1) / h->enkf_stride + 1; }
 int ensure_enkf(hc_handle *h)
 {
     if (h->enkf_stride <= 0) return fail(HC_ERR_ARG, "the EnKF is off (hc_set_enkf)");
@@ -3292,40 +3308,18 @@ int ensure_enkf(hc_handle *h)
     return ensure_da_table(h, h->enkf, h->enkf_stride, ENKF_WIDTH, ENKF_WIDTH);
 }
 
-// the sensor diagnostics (hc_set_enkf_soil_moisture): [P][n_arow][n][6] float64, created as NaN
-int ensure_sm(hc_handle *h)
-{
-    if (h->sm_n <= 0) return fail(HC_ERR_ARG, "no soil-moisture record (hc_set_enkf_soil_moisture)");
-    if (int rc = ensure_enkf(h)) return rc;
-    if (h->sm_rows != h->n_rows)
-        return fail(HC_ERR_ARG, "the soil-moisture record has %lld rows, the forcing %lld: set the record again",
-                    (long long)h->sm_rows, (long long)h->n_rows);
-    return ensure_da_table(h, h->sm, h->enkf_stride, (int64_t)h->sm_n * ENKF_SENSOR_WIDTH, 0);
-}
-
-// the window's diagnostics (hc_set_enkf_window): [P][n_arow][n][4] float64, created as NaN
-int ensure_win(hc_handle *h)
-{
-    if (h->win_n <= 0) return fail(HC_ERR_ARG, "no window offsets (hc_set_enkf_window)");
-    if (int rc = ensure_enkf(h)) return rc;
-    return ensure_da_table(h, h->win, h->enkf_stride, (int64_t)h->win_n * ENKF_WINDOW_WIDTH, 0);
-}
+int ensure_sm(hc_handle *h) { return ensure_record(h, h->enkf_sm, ensure_enkf, h->enkf_stride, "hc_set_enkf_soil_moisture"); }
+int ensure_win(hc_handle *h) { return ensure_window(h, h->enkf_win, ensure_enkf, h->enkf_stride, "hc_set_enkf_window"); }
 
 void win_off(hc_handle *h)
 {
-    h->win_n = 0;
-    h->win_off.clear(); h->win_row.clear(); h->win_last.clear();
-    h->win.release();
-    h->win_y.release(); h->enkf_eps_w.release();
+    h->enkf_win.clear();
+    h->enkf_eps_w.release();
 }
 
 void sm_off(hc_handle *h)
 {
-    h->sm_n = 0;
-    h->sm_rows = 0;
-    h->sm_width = 0;
-    h->sm_nodes.clear(); h->sm_sigma.clear(); h->sm_values.clear();
-    h->sm.release();
+    h->enkf_sm.clear();
     h->enkf_eps_s.release();
 }
 
@@ -3343,7 +3337,7 @@ void shard_off(hc_handle *h)
 // takes along, or the posterior's
 int64_t shard_words_needed(const hc_handle *h, int64_t n_global)
 {
-    const int64_t D = h->p.dim_d, Wx = 1 + h->sm_n + h->win_n, n_tiles = (n_global + ENKF_TILE - 1) / ENKF_TILE;
+    const int64_t D = h->p.dim_d, Wx = 1 + h->enkf_sm.n + h->enkf_win.n, n_tiles = (n_global + ENKF_TILE - 1) / ENKF_TILE;
     return n_tiles * std::max((D + Wx) * Wx + D, (Wx + 1) * (Wx + 1));
 }
 
@@ -3372,6 +3366,21 @@ void assimilation_off(hc_handle *h)
     filter_off(h);
     enkf_off(h);
 }
+
+// The filter that is on (the particle filter and the EnKF exclude each other): its stride (0: neither), its record and
+// window, what ensures their tables, and its analysis rows (every stride-th row)
+struct Assim {
+    int64_t stride;
+    const SmRecord &sm;
+    const WindowBase &win;
+    int (*ensure_sm)(hc_handle *), (*ensure_win)(hc_handle *);
+};
+Assim assim(const hc_handle *h)
+{
+    if (h->filt_stride > 0) return {h->filt_stride, h->filt_sm, h->filt_win, ensure_fsm, ensure_fwin};
+    return {h->enkf_stride, h->enkf_sm, h->enkf_win, ensure_sm, ensure_win};
+}
+int64_t assim_rows(const hc_handle *h) { return (h->n_rows - 1) / assim(h).stride + 1; }
 
 // The bodies of the table entry points: the table as `ensure` leaves it (its rules and refusals), a size check when the
 // caller names one (n >= 0), the stream drained, one copy of the whole table: host -> table, table -> host or
@@ -4119,25 +4128,19 @@ struct Chunk {
 // a filtered Philox run stages the launch's refresh vectors (N D doubles each) on the device: about 4 GiB at most
 constexpr int64_t FILT_FRESH_BYTES = int64_t(4) << 30;
 
-// the stride of whichever filter is on (the particle filter and the EnKF exclude each other), 0: none
-int64_t da_stride(const hc_handle *h) { return h->filt_stride > 0 ? h->filt_stride : h->enkf_stride; }
-
 bool is_assimilation_row(const hc_handle *h, int64_t row)
 {
-    const int64_t s = da_stride(h);
+    const int64_t s = assim(h).stride;
     return s > 0 && row >= 1 && row % s == 0 && h->h_wtd_obs[(size_t)row] >= 0;
 }
-
-// the window's offsets of whichever filter is on (hc_set_filter_window, hc_set_enkf_window), empty: none
-const std::vector<int> &da_window(const hc_handle *h) { return h->filt_stride > 0 ? h->fwin_off : h->win_off; }
 
 // The offset slot that lagged row `row` fills for the assimilation row after it (hc_set_enkf_window,
 // hc_set_filter_window), -1: none.  The row takes part when it is >= 1 and has an observation, and the assimilation row
 // is one as things stand.
 int window_slot(const hc_handle *h, int64_t row)
 {
-    const std::vector<int> &off = da_window(h);
-    const int64_t s = da_stride(h);
+    const std::vector<int> &off = assim(h).win.off;
+    const int64_t s = assim(h).stride;
     if (off.empty() || s <= 0 || row < 1 || h->h_wtd_obs[(size_t)row] < 0) return -1;
     const int64_t r = (row / s + 1) * s;
     if (r >= h->n_rows || !is_assimilation_row(h, r)) return -1;
@@ -4163,14 +4166,13 @@ Chunk plan_chunk(const hc_handle *h, const hc_step_args *a, int64_t done, bool p
     Chunk c;
     c.rows = (int)std::min<int64_t>(per_launch, a->n_rows - done);
     c.row0 = a->spinup ? a->row_begin : a->row_begin + done;
-    if (da_stride(h) > 0 && !a->spinup) {
-        const int64_t s = da_stride(h);
+    if (const int64_t s = assim(h).stride; s > 0 && !a->spinup) {
         for (int64_t r = std::max<int64_t>(s, (c.row0 + s - 1) / s * s); r < c.row0 + c.rows; r += s)
             if (is_assimilation_row(h, r)) {
                 c.rows = (int)(r - c.row0 + 1);
                 break;
             }
-        if (!da_window(h).empty())
+        if (assim(h).win.n > 0)
             for (int r = 0; r < c.rows; r++)
                 if (window_slot(h, c.row0 + r) >= 0) {
                     c.rows = r + 1;
@@ -4418,46 +4420,39 @@ int filter_sm_moment(hc_handle *h, const EnkfRow &s, const long long *anc, int e
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(filter_sm_moment_kernel, dim3((unsigned)P), dim3(WAVE), 0, h->stream, h->filt_part.p,
                        (long long)n_tiles, (long long)mpp, s, n_cols, entry, (long long)n_arow, (long long)slot,
-                       h->filt_sums.p, h->fsm.buf.p, h->fwin.buf.p);
+                       h->filt_sums.p, h->filt_sm.table.buf.p, h->filt_win.table.buf.p);
     HIP_TRY(hipGetLastError());
     return HC_OK;
 }
 
-// the sensors of a record (the EnKF's or the particle filter's) with a value on `row`, in record order
-EnkfRow sensor_row(int n, const std::vector<int> &nodes, const std::vector<double> &sigma, const std::vector<double> &values,
-                   int64_t row)
+// The observations of assimilation row `row` beyond the well's: the record's sensors with a value, in record order, then
+// the lagged rows of the window that were captured for it, by ascending offset: well-type columns of the well's sigma,
+// node = the lagged row's observed index (which only the particle filter's kernels read: the EnKF's stop at ms)
+EnkfRow assim_row(const hc_handle *h, const SmRecord &r, const WindowBase &w, double well_sigma, int64_t row)
 {
     EnkfRow s{};
-    for (int i = 0; i < n; i++) {
-        const double v = values[(size_t)row * n + i];
+    for (int i = 0; i < r.n; i++) {
+        const double v = r.values[(size_t)row * r.n + i];
         if (std::isnan(v)) continue;
         s.sensor[s.m] = i;
-        s.node[s.m] = nodes[(size_t)i];
+        s.node[s.m] = r.nodes[(size_t)i];
         s.obs[s.m] = v;
-        s.sigma[s.m] = sigma[(size_t)i];
+        s.sigma[s.m] = r.sigma[(size_t)i];
         s.m++;
     }
     s.ms = s.m;
-    s.n = s.ms > 0 ? n : 0;
-    return s;
-}
-
-// The observations of assimilation row `row` beyond the well's: the sensors with a value, in record order, then the lagged
-// rows of the window that were captured for it, by ascending offset (node = the lagged row's observed index)
-EnkfRow filter_row(const hc_handle *h, int64_t row)
-{
-    EnkfRow s = sensor_row(h->fsm_n, h->fsm_nodes, h->fsm_sigma, h->fsm_values, row);
-    for (int j = 0; j < h->fwin_n; j++) {
-        const int64_t rj = row - h->fwin_off[(size_t)j];
-        if (rj < 1 || h->h_wtd_obs[(size_t)rj] < 0 || h->fwin_row[(size_t)j] != rj) continue;
+    s.n = s.ms > 0 ? r.n : 0;
+    for (int j = 0; j < w.n; j++) {
+        const int64_t rj = row - w.off[(size_t)j];
+        if (rj < 1 || h->h_wtd_obs[(size_t)rj] < 0 || w.row[(size_t)j] != rj) continue;
         s.sensor[s.m] = j;
         s.node[s.m] = h->h_wtd_obs[(size_t)rj];
         s.obs[s.m] = h->p.dz * (double)h->h_wtd_obs[(size_t)rj];
-        s.sigma[s.m] = h->filt_sigma;
+        s.sigma[s.m] = well_sigma;
         s.wrow[s.m] = (unsigned)rj;
         s.m++;
     }
-    s.nw = s.m > s.ms ? h->fwin_n : 0;
+    s.nw = s.m > s.ms ? w.n : 0;
     return s;
 }
 
@@ -4465,12 +4460,12 @@ EnkfRow filter_row(const hc_handle *h, int64_t row)
 int filter_capture(hc_handle *h, const Chunk &c, int slot)
 {
     const int64_t N = h->n_members;
-    if (h->fwin_b.ensure((size_t)(h->fwin_n * N))) return HC_ERR_DEVICE;
+    if (h->filt_win.cap.ensure((size_t)(h->filt_win.n * N))) return HC_ERR_DEVICE;
     const unsigned short *w = h->wtd_u16.p + (size_t)(c.rows - 1) * N;
     hipLaunchKernelGGL(window_capture_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, w, (long long)N,
-                       h->fwin_b.p + (size_t)slot * N);
+                       h->filt_win.cap.p + (size_t)slot * N);
     HIP_TRY(hipGetLastError());
-    h->fwin_row[(size_t)slot] = c.row0 + c.rows - 1;
+    h->filt_win.row[(size_t)slot] = c.row0 + c.rows - 1;
     return HC_OK;
 }
 
@@ -4482,12 +4477,12 @@ int filter_capture(hc_handle *h, const Chunk &c, int slot)
 int filter_member_weights(hc_handle *h, const Chunk &c, const EnkfRow &s, const long long *pbase, long long key)
 {
     const int64_t N = h->n_members, D = h->p.dim_d, P = h->n_points, mpp = N / P;
-    const int64_t row = c.row0 + c.rows - 1, slot = row / h->filt_stride, n_arow = filter_rows(h);
+    const int64_t row = c.row0 + c.rows - 1, slot = row / h->filt_stride, n_arow = assim_rows(h);
     const int64_t n_tiles = (mpp + FILT_TILE - 1) / FILT_TILE;
     const int width = s.m + 2;
     const bool lagged = s.m > s.ms;
     if (lagged && h->fwin_wmax.ensure((size_t)N)) return HC_ERR_DEVICE;
-    if (h->filt_qm.ensure((size_t)N) || h->filt_Y.ensure((size_t)(N * (h->fsm_n + h->fwin_n + 2))) ||
+    if (h->filt_qm.ensure((size_t)N) || h->filt_Y.ensure((size_t)(N * (h->filt_sm.n + h->filt_win.n + 2))) ||
         h->filt_lmax.ensure((size_t)(P * n_tiles)) || h->filt_ipart.ensure((size_t)(P * n_tiles * 4)) ||
         h->filt_part.ensure((size_t)(P * n_tiles * FILT_COLS)) || h->filt_sums.ensure((size_t)(P * (FILT_COLS + 1))))
         return HC_ERR_DEVICE;
@@ -4501,7 +4496,7 @@ int filter_member_weights(hc_handle *h, const Chunk &c, const EnkfRow &s, const 
     }
     hipLaunchKernelGGL(filter_loglik_kernel, tiles, dim3(FILT_THREADS), 0, h->stream, w, (long long)mpp, (int)D,
                        h->h_wtd_obs[(size_t)row], h->p.dz, h->filt_sigma, s, Y, (long long)n_tiles, h->filt_lmax.p,
-                       (const int *)h->fwin_b.p, (long long)N, h->fwin_wmax.p);
+                       (const int *)h->filt_win.cap.p, (long long)N, h->fwin_wmax.p);
     HIP_TRY(hipGetLastError());
     if (lagged) w = h->fwin_wmax.p;
     hipLaunchKernelGGL(filter_member_weights_kernel, tiles, dim3(FILT_THREADS), 0, h->stream, w, (long long)mpp, (int)D, s.m,
@@ -4514,7 +4509,7 @@ int filter_member_weights(hc_handle *h, const Chunk &c, const EnkfRow &s, const 
     hipLaunchKernelGGL(filter_member_finish_kernel, dim3((unsigned)P), dim3(WAVE), 0, h->stream, h->filt_part.p,
                        h->filt_ipart.p, smax, (long long)n_tiles, (long long)mpp, s, h->filt_sigma,
                        (unsigned long long)h->filt_seed, pbase, key, (unsigned)row, (long long)n_arow, (long long)slot,
-                       h->filt_qr.p, h->filt.buf.p, h->filt_surv.p, mean, h->fsm.buf.p, h->fwin.buf.p);
+                       h->filt_qr.p, h->filt.buf.p, h->filt_surv.p, mean, h->filt_sm.table.buf.p, h->filt_win.table.buf.p);
     HIP_TRY(hipGetLastError());
     return filter_sm_moment(h, s, nullptr, 3, n_tiles, n_arow, slot);
 }
@@ -4527,7 +4522,7 @@ int filter_member_weights(hc_handle *h, const Chunk &c, const EnkfRow &s, const 
 int filter_temper(hc_handle *h, const unsigned short *w, int ms, int64_t mpp, int64_t n_tiles, int64_t row,
                   const long long *pbase, long long key)
 {
-    const int64_t D = h->p.dim_d, P = h->n_points, slot = row / h->filt_stride, n_arow = filter_rows(h);
+    const int64_t D = h->p.dim_d, P = h->n_points, slot = row / h->filt_stride, n_arow = assim_rows(h);
     if (h->filt_trials.ensure((size_t)(P * TEMPER_TRIALS * TEMPER_WIDTH))) return HC_ERR_DEVICE;
     if (ms == 0) {
         hipLaunchKernelGGL(filter_temper_bins_kernel, dim3((unsigned)P), dim3(FILT_THREADS), 0, h->stream, w, (long long)mpp,
@@ -4571,7 +4566,7 @@ int assimilate(hc_handle *h, const Chunk &c)
     const bool shard = h->fs_n > 0;
     const int64_t first = shard ? h->fs_bounds[(size_t)h->fs_index] : 0;
     const int64_t mpp = shard ? h->fs_bounds[(size_t)h->fs_n] : N / P;
-    const int64_t row = c.row0 + c.rows - 1, slot = row / h->filt_stride, n_arow = filter_rows(h);
+    const int64_t row = c.row0 + c.rows - 1, slot = row / h->filt_stride, n_arow = assim_rows(h);
     const int64_t n_tiles = (mpp + FILT_TILE - 1) / FILT_TILE;
     if (h->filt_q.ensure((size_t)(P * D)) || h->filt_qr.ensure((size_t)(2 * P)) || h->filt_surv.ensure((size_t)P) ||
         h->filt_tiles.ensure((size_t)(P * n_tiles)) || h->filt_anc.ensure((size_t)(P * mpp)) ||
@@ -4599,7 +4594,7 @@ int assimilate(hc_handle *h, const Chunk &c)
     const long long *pbase = P > 1 ? h->point_base.p : nullptr;
     // a row with sensor values (hc_set_filter_soil_moisture; never sharded): a weight per member, and the scan below reads
     // it directly (a null w) in place of the bin's; so does a row with lagged rows of the window (hc_set_filter_window)
-    const EnkfRow s = filter_row(h, row);
+    const EnkfRow s = assim_row(h, h->filt_sm, h->filt_win, h->filt_sigma, row);
     const long long *q = h->filt_q.p;
     if (s.m > 0) {
         if (int rc = filter_member_weights(h, c, s, pbase, key)) return rc;
@@ -4616,7 +4611,7 @@ int assimilate(hc_handle *h, const Chunk &c)
         HIP_TRY(hipGetLastError());
         if (h->filt_floor > 0.0)
             if (int rc = filter_temper(h, w, 0, mpp, n_tiles, row, pbase, key)) return rc;
-        if (h->fsm_n > 0 || h->fwin_n > 0) {
+        if (h->filt_sm.n > 0 || h->filt_win.n > 0) {
             if (h->filt_qm.ensure((size_t)N)) return HC_ERR_DEVICE;
             hipLaunchKernelGGL(filter_expand_weights_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, w,
                                h->filt_q.p, (long long)mpp, (long long)N, (int)D, h->filt_qm.p);
@@ -4661,11 +4656,11 @@ int assimilate(hc_handle *h, const Chunk &c)
         if (int rc = filter_sm_moment(h, s, h->filt_anc.p, 4, n_tiles, n_arow, slot)) return rc;
         if (int rc = filter_sm_moment(h, s, h->filt_anc.p, 5, n_tiles, n_arow, slot)) return rc;
     }
-    h->fsm_width = s.ms;
+    h->filt_sm.width = s.ms;
     h->filt_ycols = s.m > 0 ? s.m + 2 : 0;
     // the window's buffer is spent: the lagged columns this row took (test hook), every slot empty
-    h->fwin_last.assign(s.sensor + s.ms, s.sensor + s.m);
-    std::fill(h->fwin_row.begin(), h->fwin_row.end(), (int64_t)-1);
+    h->filt_win.last.assign(s.sensor + s.ms, s.sensor + s.m);
+    std::fill(h->filt_win.row.begin(), h->filt_win.row.end(), (int64_t)-1);
     std::swap(h->psi, h->psi_alt);
     std::swap(h->base, h->base_alt);
     // the rest of this hc_step_rows call launches on the analysis (fill_args took the pointers before the swap)
@@ -4675,34 +4670,16 @@ int assimilate(hc_handle *h, const Chunk &c)
     return HC_OK;
 }
 
-// The observations of `row` beyond the well's: the sensors with a value, in record order, then the lagged rows of the
-// window that were captured for this analysis, by ascending offset
-EnkfRow enkf_row(const hc_handle *h, int64_t row)
-{
-    EnkfRow s = sensor_row(h->sm_n, h->sm_nodes, h->sm_sigma, h->sm_values, row);
-    for (int j = 0; j < h->win_n; j++) {
-        const int64_t rj = row - h->win_off[(size_t)j];
-        if (rj < 1 || h->h_wtd_obs[(size_t)rj] < 0 || h->win_row[(size_t)j] != rj) continue;
-        s.sensor[s.m] = j;
-        s.obs[s.m] = (double)h->h_wtd_obs[(size_t)rj] * h->p.dz;
-        s.sigma[s.m] = h->enkf_sigma;
-        s.wrow[s.m] = (unsigned)rj;
-        s.m++;
-    }
-    s.nw = s.m > s.ms ? h->win_n : 0;
-    return s;
-}
-
 // The lagged row the launch ended on: every member's y into the window's buffer, by the analysis's own kernel
 int enkf_capture(hc_handle *h, const Chunk &c, int slot)
 {
     const int64_t N = h->n_members, D = h->p.dim_d;
-    if (h->win_y.ensure((size_t)(h->win_n * N))) return HC_ERR_DEVICE;
+    if (h->enkf_win.cap.ensure((size_t)(h->enkf_win.n * N))) return HC_ERR_DEVICE;
     const unsigned short *w = h->wtd_u16.p + (size_t)(c.rows - 1) * N;
     hipLaunchKernelGGL(enkf_obs_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, w, h->psi.p, h->Pdev.p,
-                       (long long)N, (long long)(N / h->n_points), (int)D, h->p.dz, h->win_y.p + (size_t)slot * N, 1);
+                       (long long)N, (long long)(N / h->n_points), (int)D, h->p.dz, h->enkf_win.cap.p + (size_t)slot * N, 1);
     HIP_TRY(hipGetLastError());
-    h->win_row[(size_t)slot] = c.row0 + c.rows - 1;
+    h->enkf_win.row[(size_t)slot] = c.row0 + c.rows - 1;
     return HC_OK;
 }
 
@@ -4721,7 +4698,7 @@ int enkf_exchange(hc_handle *h, double *pass, int64_t n_words, int64_t first_wor
 // observations per member, in place on psi: y and theta per member; per point the column and observation sums, then the
 // anomaly products (two passes over psi); the gain and the prior diagnostics; the update with eps and the posterior (y,
 // theta, rejected) per member (one read + write of psi); the posterior sums and diagnostics.  Scratch is sized by the
-// record's largest m', 1 + sm_n.  hc_set_enkf_method: the square-root scheme swaps the draws and the update for its own
+// record's largest m', 1 + n_s.  hc_set_enkf_method: the square-root scheme swaps the draws and the update for its own
 // (the gain kernel adds the reduced gain and the mean's increment); a relaxation alpha > 0 takes the squared psi
 // anomalies along in the second prior pass, sums the analysis columns and their squared anomalies (two more passes over
 // psi), relaxes (one read + write, which also writes y: the update before it skips that) and only then forms the
@@ -4733,21 +4710,21 @@ int enkf_exchange(hc_handle *h, double *pass, int64_t n_words, int64_t first_wor
 int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
 {
     const int64_t N = h->n_members, D = h->p.dim_d, P = h->n_points, mpp = N / P;
-    const int64_t row = c.row0 + c.rows - 1, slot = row / h->enkf_stride, n_arow = enkf_rows(h);
+    const int64_t row = c.row0 + c.rows - 1, slot = row / h->enkf_stride, n_arow = assim_rows(h);
     // hc_set_enkf_shard: the handle's members are tiles tile0 ... of a point with np members and n_tiles tiles; every
     // reduction gathers the other handles' partials first (reduce below).  Off: np = mpp, the handle's own tiles.
     const bool shard = h->shard_global > 0;
     const int64_t np = shard ? h->shard_global : mpp, tile0 = shard ? h->shard_first / ENKF_TILE : 0;
     const int64_t my_tiles = (mpp + ENKF_TILE - 1) / ENKF_TILE, n_tiles = (np + ENKF_TILE - 1) / ENKF_TILE;
     const int W = s.m + 1, V = s.ms + 2, mw = s.m - s.ms;
-    const int64_t C = D + W, Wx = 1 + h->sm_n + h->win_n, Cx = D + Wx;
+    const int64_t C = D + W, Wx = 1 + h->enkf_sm.n + h->enkf_win.n, Cx = D + Wx;
     if (shard && h->shard_words < shard_words_needed(h, np))
         return fail(HC_ERR_ARG, "the shard's buffer holds %lld doubles, the analysis needs %lld (sensors or a window set "
                     "after hc_set_enkf_shard: set the shard again)", (long long)h->shard_words,
                     (long long)shard_words_needed(h, np));
     const int64_t cols_x = std::max(Cx * Wx, (Wx + 1) * (Wx + 1));   // the widest pass: the prior products or the posterior's
     if (h->enkf_Y.ensure((size_t)(N * Wx)) || h->enkf_eps.ensure((size_t)N) ||
-        h->enkf_eps_s.ensure((size_t)(N * h->sm_n)) || h->enkf_eps_w.ensure((size_t)(N * h->win_n)) ||
+        h->enkf_eps_s.ensure((size_t)(N * h->enkf_sm.n)) || h->enkf_eps_w.ensure((size_t)(N * h->enkf_win.n)) ||
         h->enkf_Ypost.ensure((size_t)(N * (Wx + 1))) ||
         h->enkf_gain.ensure((size_t)(P * Wx * D)) || h->enkf_s1.ensure((size_t)(P * Cx)) ||
         h->enkf_s2.ensure((size_t)(P * cols_x)) || (!shard && h->enkf_part.ensure((size_t)(P * n_tiles * cols_x))))
@@ -4804,7 +4781,7 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
         HIP_TRY(hipGetLastError());
     }
     if (mw > 0) {
-        hipLaunchKernelGGL(enkf_window_gather_kernel, members, dim3(256), 0, h->stream, h->win_y.p, (long long)N, s,
+        hipLaunchKernelGGL(enkf_window_gather_kernel, members, dim3(256), 0, h->stream, h->enkf_win.cap.p, (long long)N, s,
                            h->enkf_Y.p, W);
         HIP_TRY(hipGetLastError());
     }
@@ -4815,7 +4792,7 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
     HIP_TRY(partials(relax, h->psi.p, h->enkf_Y.p, W, h->enkf_s1.p, (int)D, cols_prior, part, relax ? part_sq_b : nullptr));
     if ((rc = reduce(part, C * W, h->enkf_s2.p))) return rc;
     if (relax && (rc = reduce(part_sq_b, D, h->enkf_sq_b.p))) return rc;
-    double *st = h->enkf.buf.p, *sst = h->sm.buf.p, *wst = h->win.buf.p;
+    double *st = h->enkf.buf.p, *sst = h->enkf_sm.table.buf.p, *wst = h->enkf_win.table.buf.p;
     hipLaunchKernelGGL(enkf_gain_kernel, dim3((unsigned)P), dim3((unsigned)((D + WAVE - 1) / WAVE * WAVE)), 0, h->stream,
                        h->enkf_s1.p, h->enkf_s2.p, ll_np, (int)D, s, h->enkf_sigma, h->enkf_loc, z_obs, dz,
                        h->enkf_gain.p, st, sst, (long long)n_arow, (long long)slot, root ? h->enkf_rgain.p : nullptr,
@@ -4894,9 +4871,9 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
     h->enkf_width = W;
     h->enkf_last_method = h->enkf_method;
     h->enkf_last_relaxed = relax;
-    h->sm_width = s.ms > 0 ? 1 + s.ms : 0;
-    h->win_last.assign(s.sensor + s.ms, s.sensor + s.m);
-    std::fill(h->win_row.begin(), h->win_row.end(), (int64_t)-1);   // the captured rows are spent
+    h->enkf_sm.width = s.ms > 0 ? 1 + s.ms : 0;
+    h->enkf_win.last.assign(s.sensor + s.ms, s.sensor + s.m);
+    std::fill(h->enkf_win.row.begin(), h->enkf_win.row.end(), (int64_t)-1);   // the captured rows are spent
     return HC_OK;
 }
 
@@ -4948,14 +4925,13 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
     if (a->spinup && h->filt_host())
         return fail(HC_ERR_ARG, "spin-up solves with the particle filter on in a Philox run: set the filter after the spin-up");
     const bool filt_on = h->filt_stride > 0 && !a->spinup;
-    if (filt_on && (rc = ensure_filter(h))) return rc;
-    if (filt_on && h->fsm_n > 0 && (rc = ensure_fsm(h))) return rc;
-    if (filt_on && h->filt_floor > 0.0 && (rc = ensure_ftemp(h))) return rc;
-    if (filt_on && h->fwin_n > 0 && (rc = ensure_fwin(h))) return rc;
     const bool enkf_on = h->enkf_stride > 0 && !a->spinup;   // (the EnKF: spin-up solves are never analysed either)
-    if (enkf_on && (rc = ensure_enkf(h))) return rc;
-    if (enkf_on && h->sm_n > 0 && (rc = ensure_sm(h))) return rc;
-    if (enkf_on && h->win_n > 0 && (rc = ensure_win(h))) return rc;
+    if ((filt_on && (rc = ensure_filter(h))) || (enkf_on && (rc = ensure_enkf(h)))) return rc;
+    const Assim da = assim(h);                               // whichever is on: its record's and its window's tables
+    const bool da_on = filt_on || enkf_on;
+    if (da_on && da.sm.n > 0 && (rc = da.ensure_sm(h))) return rc;
+    if (filt_on && h->filt_floor > 0.0 && (rc = ensure_ftemp(h))) return rc;
+    if (da_on && da.win.n > 0 && (rc = da.ensure_win(h))) return rc;
     int64_t fresh_consumed = 0;
     for (int64_t done = 0; done < a->n_rows;) {
         const Chunk c = plan_chunk(h, a, done, prof_on);
@@ -4964,14 +4940,13 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
         if ((rc = launch_chunk(h, A, a, c, prof_on || per_on))) return rc;
         if ((rc = accumulate(h, A, a, c, prof_on, hist_on))) return rc;
         if ((rc = copy_outputs(h, a, c, done))) return rc;
-        if (filt_on && is_assimilation_row(h, c.row0 + c.rows - 1) && (rc = assimilate(h, c))) return rc;
-        if (enkf_on && is_assimilation_row(h, c.row0 + c.rows - 1) &&
-            (rc = enkf_analyse(h, c, enkf_row(h, c.row0 + c.rows - 1))))
+        const int64_t last = c.row0 + c.rows - 1;
+        if (filt_on && is_assimilation_row(h, last) && (rc = assimilate(h, c))) return rc;
+        if (enkf_on && is_assimilation_row(h, last) &&
+            (rc = enkf_analyse(h, c, assim_row(h, h->enkf_sm, h->enkf_win, h->enkf_sigma, last))))
             return rc;
-        if (const int wslot = enkf_on ? window_slot(h, c.row0 + c.rows - 1) : -1; wslot >= 0)
-            if ((rc = enkf_capture(h, c, wslot))) return rc;
-        if (const int wslot = filt_on ? window_slot(h, c.row0 + c.rows - 1) : -1; wslot >= 0)
-            if ((rc = filter_capture(h, c, wslot))) return rc;
+        if (const int wslot = da_on ? window_slot(h, last) : -1; wslot >= 0)
+            if ((rc = filt_on ? filter_capture(h, c, wslot) : enkf_capture(h, c, wslot))) return rc;
         HIP_TRY(hipStreamSynchronize(h->stream));
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, h->ev0, h->ev1));
@@ -5618,6 +5593,107 @@ int sm_record_check(const hc_handle *h, const char *who, int32_t n_sensors, cons
     return HC_OK;
 }
 
+// The bodies hc_set_filter_soil_moisture and hc_set_enkf_soil_moisture share, after the owner's own refusals: the
+// arguments, against the owner's window of `n_window` offsets too; the stream drained; the record cleared by the owner's
+// `off` (with what else the owner releases) and, with sensors, stored, its table made by the owner's `ensure`
+int record_set(hc_handle *h, SmRecord &r, int n_window, void (*off)(hc_handle *), int (*ensure)(hc_handle *),
+               const char *who, int32_t n_sensors, const int32_t *nodes, const double *values, const double *sigma)
+{
+    if (n_sensors > 0 && (!nodes || !values || !sigma)) return fail(HC_ERR_ARG, "%s: bad argument", who);
+    if (n_sensors + n_window > ENKF_SENSORS)
+        return fail(HC_ERR_ARG, "%s: %d sensors and %d window offsets, at most %d together", who, (int)n_sensors, n_window,
+                    ENKF_SENSORS);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    off(h);
+    if (n_sensors == 0) return HC_OK;
+    if (int rc = sm_record_check(h, who, n_sensors, nodes, values, sigma)) return rc;
+    r.nodes.assign(nodes, nodes + n_sensors);
+    r.sigma.assign(sigma, sigma + n_sensors);
+    r.values.assign(values, values + (size_t)h->n_rows * n_sensors);
+    r.rows = h->n_rows;
+    r.n = n_sensors;
+    const int rc = ensure(h);
+    if (rc != HC_OK) off(h);                     // refused: off
+    return rc;
+}
+
+// ... and hc_set_filter_window and hc_set_enkf_window: the offsets against the owner's record of `n_sensors` sensors and
+// its stride, sorted; then as above
+int window_set(hc_handle *h, WindowBase &w, int n_sensors, int stride, void (*off)(hc_handle *), int (*ensure)(hc_handle *),
+               const char *who, int32_t n_offsets, const int32_t *offsets)
+{
+    if (n_offsets + n_sensors > ENKF_SENSORS)
+        return fail(HC_ERR_ARG, "%s: %d offsets and %d sensors, at most %d together", who, (int)n_offsets, n_sensors,
+                    ENKF_SENSORS);
+    std::vector<int> sorted(offsets, offsets + n_offsets);
+    std::sort(sorted.begin(), sorted.end());
+    for (int j = 0; j < n_offsets; j++) {
+        if (sorted[(size_t)j] < 1 || sorted[(size_t)j] >= stride)
+            return fail(HC_ERR_ARG, "%s: offset %d outside [1, %d) (the stride)", who, sorted[(size_t)j], stride);
+        if (j > 0 && sorted[(size_t)j] == sorted[(size_t)j - 1])
+            return fail(HC_ERR_ARG, "%s: offset %d twice", who, sorted[(size_t)j]);
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    off(h);
+    if (n_offsets == 0) return HC_OK;
+    w.n = n_offsets;
+    w.off = sorted;
+    w.row.assign((size_t)n_offsets, (int64_t)-1);
+    const int rc = ensure(h);
+    if (rc != HC_OK) off(h);                     // refused: off
+    return rc;
+}
+
+// What a window holds for the coming assimilation (checkpoints): out, an empty slot as zeros; the checks of what comes
+// in (`setter`: the entry point that sets the window); in
+template <typename T>
+int window_capture_get(hc_handle *h, const Window<T> &w, const char *who, const char *setter, T *cap, int64_t *rows)
+{
+    if (w.n <= 0) return fail(HC_ERR_ARG, "%s: no window offsets (%s)", who, setter);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const size_t N = (size_t)h->n_members;
+    for (int j = 0; j < w.n; j++) {
+        rows[j] = w.row[(size_t)j];
+        if (rows[j] >= 0)
+            HIP_TRY(hipMemcpy(cap + (size_t)j * N, w.cap.p + (size_t)j * N, N * sizeof(T), hipMemcpyDeviceToHost));
+        else
+            std::fill_n(cap + (size_t)j * N, N, T(0));
+    }
+    return HC_OK;
+}
+int window_capture_check(const hc_handle *h, const WindowBase &w, const char *who, const char *setter, const int64_t *rows)
+{
+    if (w.n <= 0) return fail(HC_ERR_ARG, "%s: no window offsets (%s)", who, setter);
+    for (int j = 0; j < w.n; j++)
+        if (rows[j] < -1 || rows[j] >= h->n_rows)
+            return fail(HC_ERR_ARG, "%s: row %lld of offset %d outside [-1, %lld)", who, (long long)rows[j], w.off[(size_t)j],
+                        (long long)h->n_rows);
+    return HC_OK;
+}
+template <typename T>
+int window_capture_set(hc_handle *h, Window<T> &w, const T *cap, const int64_t *rows)
+{
+    const size_t n = (size_t)w.n * h->n_members;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (w.cap.ensure(n)) return HC_ERR_DEVICE;
+    HIP_TRY(hipMemcpy(w.cap.p, cap, n * sizeof(T), hipMemcpyHostToDevice));
+    w.row.assign(rows, rows + w.n);
+    return HC_OK;
+}
+
+// the lagged columns of the owner's last assimilation (`done`: it is on and one has run), their slots in column order
+int window_width(const WindowBase &w, bool done, int32_t *width, int32_t *slots)
+{
+    *width = done && w.n > 0 ? (int32_t)w.last.size() : 0;
+    if (slots)
+        for (int k = 0; k < *width; k++) slots[k] = w.last[(size_t)k];
+    return HC_OK;
+}
+
 template <typename T>
 int filter_hook(hc_handle *h, const DevBuf<T> &b, void *out, size_t count, const char *who, size_t first = 0)
 {
@@ -5689,35 +5765,20 @@ int hc_set_filter_soil_moisture(hc_handle *h, int32_t n_sensors, const int32_t *
     if (n_sensors > 0 && h->fs_n > 0)
         return fail(HC_ERR_ARG, "hc_set_filter_soil_moisture: the filter is sharded (hc_set_filter_shard), and the sharded "
                                 "filter gathers water-table indices only: a record needs every member of a point on one handle");
-    if (n_sensors + h->fwin_n > ENKF_SENSORS)
-        return fail(HC_ERR_ARG, "hc_set_filter_soil_moisture: %d sensors and %d window offsets, at most %d together",
-                    (int)n_sensors, h->fwin_n, ENKF_SENSORS);
-    if (n_sensors > 0 && (!nodes || !values || !sigma)) return fail(HC_ERR_ARG, "hc_set_filter_soil_moisture: bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    fsm_off(h);
-    if (n_sensors == 0) return HC_OK;
-    if (int rc = sm_record_check(h, "hc_set_filter_soil_moisture", n_sensors, nodes, values, sigma)) return rc;
-    h->fsm_nodes.assign(nodes, nodes + n_sensors);
-    h->fsm_sigma.assign(sigma, sigma + n_sensors);
-    h->fsm_values.assign(values, values + (size_t)h->n_rows * n_sensors);
-    h->fsm_rows = h->n_rows;
-    h->fsm_n = n_sensors;
-    const int rc = ensure_fsm(h);
-    if (rc != HC_OK) fsm_off(h);                 // refused: off
-    return rc;
+    return record_set(h, h->filt_sm, h->filt_win.n, fsm_off, ensure_fsm, "hc_set_filter_soil_moisture", n_sensors, nodes,
+                      values, sigma);
 }
 
 int hc_get_filter_sm_stats(hc_handle *h, double *table, int64_t n_entries)
 {
     if (!h || !table) return fail(HC_ERR_ARG, "hc_get_filter_sm_stats: bad argument");
-    return table_copy(h, h->fsm, ensure_fsm, hipMemcpyDeviceToHost, table, n_entries, "hc_get_filter_sm_stats");
+    return table_copy(h, h->filt_sm.table, ensure_fsm, hipMemcpyDeviceToHost, table, n_entries, "hc_get_filter_sm_stats");
 }
 
 int hc_set_filter_sm_stats(hc_handle *h, const double *table, int64_t n_entries)
 {
     if (!h || !table) return fail(HC_ERR_ARG, "hc_set_filter_sm_stats: bad argument");
-    return table_copy(h, h->fsm, ensure_fsm, hipMemcpyHostToDevice, const_cast<double *>(table), n_entries,
+    return table_copy(h, h->filt_sm.table, ensure_fsm, hipMemcpyHostToDevice, const_cast<double *>(table), n_entries,
                       "hc_set_filter_sm_stats");
 }
 
@@ -5761,13 +5822,13 @@ int hc_get_filter_temper_trials(hc_handle *h, int64_t *trials)
 int hc_get_filter_sm_width(hc_handle *h, int32_t *width)
 {
     if (!h || !width) return fail(HC_ERR_ARG, "hc_get_filter_sm_width: bad argument");
-    *width = h->fsm_n > 0 ? h->fsm_width : 0;
+    *width = h->filt_sm.n > 0 ? h->filt_sm.width : 0;
     return HC_OK;
 }
 
 int hc_get_filter_member_weights(hc_handle *h, int64_t *q)
 {
-    if (h && h->fsm_n <= 0 && h->fwin_n <= 0)
+    if (h && h->filt_sm.n <= 0 && h->filt_win.n <= 0)
         return fail(HC_ERR_ARG, "hc_get_filter_member_weights: no soil-moisture record");
     return filter_hook(h, h->filt_qm, q, h ? (size_t)h->n_members : 0, "hc_get_filter_member_weights");
 }
@@ -5776,7 +5837,7 @@ int hc_get_filter_member_weights(hc_handle *h, int64_t *q)
 static int filter_sm_hook(hc_handle *h, double *out, int col0, int cols, const char *who)
 {
     if (!h || !out) return fail(HC_ERR_ARG, "%s: bad argument", who);
-    if (h->filt_ycols <= 0 || (col0 > 0 && h->fsm_width <= 0))
+    if (h->filt_ycols <= 0 || (col0 > 0 && h->filt_sm.width <= 0))
         return fail(HC_ERR_ARG, "%s: the last assimilation had no sensor value", who);
     const size_t N = (size_t)h->n_members, width = (size_t)h->filt_ycols;
     std::vector<double> all(N * width);
@@ -5789,7 +5850,7 @@ int hc_get_filter_loglik(hc_handle *h, double *l) { return filter_sm_hook(h, l, 
 
 int hc_get_filter_sm_theta(hc_handle *h, double *theta)
 {
-    return filter_sm_hook(h, theta, 1, h ? h->fsm_width : 0, "hc_get_filter_sm_theta");
+    return filter_sm_hook(h, theta, 1, h ? h->filt_sm.width : 0, "hc_get_filter_sm_theta");
 }
 
 int hc_set_filter_window(hc_handle *h, int32_t n_offsets, const int32_t *offsets)
@@ -5804,89 +5865,43 @@ int hc_set_filter_window(hc_handle *h, int32_t n_offsets, const int32_t *offsets
     if (n_offsets > 0 && h->fs_n > 0)
         return fail(HC_ERR_ARG, "hc_set_filter_window: the filter is sharded (hc_set_filter_shard), and the sharded filter "
                                 "gathers the water-table indices of the assimilation row only");
-    if (n_offsets + h->fsm_n > ENKF_SENSORS)
-        return fail(HC_ERR_ARG, "hc_set_filter_window: %d offsets and %d sensors, at most %d together", (int)n_offsets,
-                    h->fsm_n, ENKF_SENSORS);
-    std::vector<int> off(offsets, offsets + n_offsets);
-    std::sort(off.begin(), off.end());
-    for (int j = 0; j < n_offsets; j++) {
-        if (off[(size_t)j] < 1 || off[(size_t)j] >= h->filt_stride)
-            return fail(HC_ERR_ARG, "hc_set_filter_window: offset %d outside [1, %d) (the stride)", off[(size_t)j],
-                        h->filt_stride);
-        if (j > 0 && off[(size_t)j] == off[(size_t)j - 1])
-            return fail(HC_ERR_ARG, "hc_set_filter_window: offset %d twice", off[(size_t)j]);
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    fwin_off(h);
-    if (n_offsets == 0) return HC_OK;
-    h->fwin_n = n_offsets;
-    h->fwin_off = off;
-    h->fwin_row.assign((size_t)n_offsets, (int64_t)-1);
-    const int rc = ensure_fwin(h);
-    if (rc != HC_OK) fwin_off(h);                // refused: off
-    return rc;
+    return window_set(h, h->filt_win, h->filt_sm.n, h->filt_stride, fwin_off, ensure_fwin, "hc_set_filter_window", n_offsets,
+                      offsets);
 }
 
 int hc_get_filter_window_stats(hc_handle *h, double *table, int64_t n_entries)
 {
     if (!h || !table) return fail(HC_ERR_ARG, "hc_get_filter_window_stats: bad argument");
-    return table_copy(h, h->fwin, ensure_fwin, hipMemcpyDeviceToHost, table, n_entries, "hc_get_filter_window_stats");
+    return table_copy(h, h->filt_win.table, ensure_fwin, hipMemcpyDeviceToHost, table, n_entries, "hc_get_filter_window_stats");
 }
 
 int hc_set_filter_window_stats(hc_handle *h, const double *table, int64_t n_entries)
 {
     if (!h || !table) return fail(HC_ERR_ARG, "hc_set_filter_window_stats: bad argument");
-    return table_copy(h, h->fwin, ensure_fwin, hipMemcpyHostToDevice, const_cast<double *>(table), n_entries,
+    return table_copy(h, h->filt_win.table, ensure_fwin, hipMemcpyHostToDevice, const_cast<double *>(table), n_entries,
                       "hc_set_filter_window_stats");
 }
 
-// what the window holds for the coming assimilation: checkpoints
 int hc_get_filter_window_capture(hc_handle *h, int32_t *b, int64_t *rows)
 {
     if (!h || !b || !rows) return fail(HC_ERR_ARG, "hc_get_filter_window_capture: bad argument");
-    if (h->fwin_n <= 0) return fail(HC_ERR_ARG, "hc_get_filter_window_capture: no window offsets (hc_set_filter_window)");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    const size_t N = (size_t)h->n_members;
-    for (int j = 0; j < h->fwin_n; j++) {
-        rows[j] = h->fwin_row[(size_t)j];
-        if (rows[j] >= 0)
-            HIP_TRY(hipMemcpy(b + (size_t)j * N, h->fwin_b.p + (size_t)j * N, N * 4, hipMemcpyDeviceToHost));
-        else
-            std::fill_n(b + (size_t)j * N, N, 0);
-    }
-    return HC_OK;
+    return window_capture_get(h, h->filt_win, "hc_get_filter_window_capture", "hc_set_filter_window", b, rows);
 }
 
 int hc_set_filter_window_capture(hc_handle *h, const int32_t *b, const int64_t *rows)
 {
     if (!h || !b || !rows) return fail(HC_ERR_ARG, "hc_set_filter_window_capture: bad argument");
-    if (h->fwin_n <= 0) return fail(HC_ERR_ARG, "hc_set_filter_window_capture: no window offsets (hc_set_filter_window)");
-    const size_t N = (size_t)h->n_members;
-    for (int j = 0; j < h->fwin_n; j++)
-        if (rows[j] < -1 || rows[j] >= h->n_rows)
-            return fail(HC_ERR_ARG, "hc_set_filter_window_capture: row %lld of offset %d outside [-1, %lld)",
-                        (long long)rows[j], h->fwin_off[(size_t)j], (long long)h->n_rows);
-    for (size_t k = 0; k < (size_t)h->fwin_n * N; k++)
+    if (int rc = window_capture_check(h, h->filt_win, "hc_set_filter_window_capture", "hc_set_filter_window", rows)) return rc;
+    for (size_t k = 0; k < (size_t)h->filt_win.n * h->n_members; k++)
         if (b[k] < 0 || b[k] > 65535)
             return fail(HC_ERR_ARG, "hc_set_filter_window_capture: index %d (entry %zu) outside [0, 65535]", (int)b[k], k);
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->fwin_b.ensure((size_t)h->fwin_n * N)) return HC_ERR_DEVICE;
-    HIP_TRY(hipMemcpy(h->fwin_b.p, b, (size_t)h->fwin_n * N * 4, hipMemcpyHostToDevice));
-    h->fwin_row.assign(rows, rows + h->fwin_n);
-    return HC_OK;
+    return window_capture_set(h, h->filt_win, b, rows);
 }
 
 int hc_get_filter_window_width(hc_handle *h, int32_t *width, int32_t *slots)
 {
     if (!h || !width) return fail(HC_ERR_ARG, "hc_get_filter_window_width: bad argument");
-    const bool any = h->filt_stride > 0 && h->filt_done && h->fwin_n > 0;
-    *width = any ? (int32_t)h->fwin_last.size() : 0;
-    if (slots)
-        for (int k = 0; k < *width; k++) slots[k] = h->fwin_last[(size_t)k];
-    return HC_OK;
+    return window_width(h->filt_win, h->filt_stride > 0 && h->filt_done, width, slots);
 }
 
 }  // extern "C"
@@ -5938,10 +5953,10 @@ int hc_set_filter_shard(hc_handle *h, int32_t n_shards, const int64_t *bounds, i
     if (n_shards == 0) return HC_OK;
     int64_t np = 0;
     if (int rc = filter_shard_check(h, n_shards, bounds, index, "hc_set_filter_shard", &np)) return rc;
-    if (h->fsm_n > 0)
+    if (h->filt_sm.n > 0)
         return fail(HC_ERR_ARG, "hc_set_filter_shard: a soil-moisture record is set (hc_set_filter_soil_moisture), and the "
                                 "sharded filter gathers water-table indices only");
-    if (h->fwin_n > 0)
+    if (h->filt_win.n > 0)
         return fail(HC_ERR_ARG, "hc_set_filter_shard: window offsets are set (hc_set_filter_window), and the sharded filter "
                                 "gathers the water-table indices of the assimilation row only");
     if (h->per_n > 0)
@@ -6068,43 +6083,27 @@ int hc_set_enkf_soil_moisture(hc_handle *h, int32_t n_sensors, const int32_t *no
         return fail(HC_ERR_ARG, "hc_set_enkf_soil_moisture: the particle filter is on");
     if (n_sensors > 0 && h->enkf_stride <= 0)
         return fail(HC_ERR_ARG, "hc_set_enkf_soil_moisture: the EnKF is off (hc_set_enkf comes first)");
-    if (n_sensors > 0 && (!nodes || !values || !sigma)) return fail(HC_ERR_ARG, "hc_set_enkf_soil_moisture: bad argument");
-    if (n_sensors + h->win_n > ENKF_SENSORS)
-        return fail(HC_ERR_ARG, "hc_set_enkf_soil_moisture: %d sensors and %d window offsets, at most %d together",
-                    (int)n_sensors, h->win_n, ENKF_SENSORS);
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    sm_off(h);
-    if (n_sensors == 0) return HC_OK;
-    if (int rc = sm_record_check(h, "hc_set_enkf_soil_moisture", n_sensors, nodes, values, sigma)) return rc;
-    const size_t n = (size_t)h->n_rows * n_sensors;
-    h->sm_nodes.assign(nodes, nodes + n_sensors);
-    h->sm_sigma.assign(sigma, sigma + n_sensors);
-    h->sm_values.assign(values, values + n);
-    h->sm_rows = h->n_rows;
-    h->sm_n = n_sensors;
-    const int rc = ensure_sm(h);
-    if (rc != HC_OK) sm_off(h);                  // refused: off
-    return rc;
+    return record_set(h, h->enkf_sm, h->enkf_win.n, sm_off, ensure_sm, "hc_set_enkf_soil_moisture", n_sensors, nodes, values,
+                      sigma);
 }
 
 int hc_get_enkf_sm_stats(hc_handle *h, double *table, int64_t n_entries)
 {
     if (!h || !table) return fail(HC_ERR_ARG, "hc_get_enkf_sm_stats: bad argument");
-    return table_copy(h, h->sm, ensure_sm, hipMemcpyDeviceToHost, table, n_entries, "hc_get_enkf_sm_stats");
+    return table_copy(h, h->enkf_sm.table, ensure_sm, hipMemcpyDeviceToHost, table, n_entries, "hc_get_enkf_sm_stats");
 }
 
 int hc_set_enkf_sm_stats(hc_handle *h, const double *table, int64_t n_entries)
 {
     if (!h || !table) return fail(HC_ERR_ARG, "hc_set_enkf_sm_stats: bad argument");
-    return table_copy(h, h->sm, ensure_sm, hipMemcpyHostToDevice, const_cast<double *>(table), n_entries,
+    return table_copy(h, h->enkf_sm.table, ensure_sm, hipMemcpyHostToDevice, const_cast<double *>(table), n_entries,
                       "hc_set_enkf_sm_stats");
 }
 
 int hc_get_enkf_sm_width(hc_handle *h, int32_t *width)
 {
     if (!h || !width) return fail(HC_ERR_ARG, "hc_get_enkf_sm_width: bad argument");
-    *width = h->sm_n > 0 ? h->sm_width : 0;
+    *width = h->enkf_sm.n > 0 ? h->enkf_sm.width : 0;
     return HC_OK;
 }
 
@@ -6112,7 +6111,7 @@ int hc_get_enkf_sm_width(hc_handle *h, int32_t *width)
 static int sm_check(hc_handle *h, const double *out, const char *who)
 {
     if (!h || !out) return fail(HC_ERR_ARG, "%s: bad argument", who);
-    if (h->sm_n <= 0 || h->sm_width <= 0) return fail(HC_ERR_ARG, "%s: the last analysis had no sensor value", who);
+    if (h->enkf_sm.n <= 0 || h->enkf_sm.width <= 0) return fail(HC_ERR_ARG, "%s: the last analysis had no sensor value", who);
     return HC_OK;
 }
 
@@ -6126,7 +6125,7 @@ static int sm_hook(hc_handle *h, const double *src, double *out, size_t count, c
 int hc_get_enkf_sm_y(hc_handle *h, double *y)
 {
     if (int rc = sm_check(h, y, "hc_get_enkf_sm_y")) return rc;
-    return enkf_hook(h, h->enkf_Y.p, y, (size_t)h->n_members, (size_t)h->sm_width, (size_t)h->enkf_width, "hc_get_enkf_sm_y");
+    return enkf_hook(h, h->enkf_Y.p, y, (size_t)h->n_members, (size_t)h->enkf_sm.width, (size_t)h->enkf_width, "hc_get_enkf_sm_y");
 }
 
 // a gain (`dev`: the gain or the reduced gain) is [P][m'][D] on the device, [P][D][.] at the C-ABI: its first `cols` columns
@@ -6144,13 +6143,13 @@ static int gain_hook(hc_handle *h, const double *dev, double *gain, size_t cols,
 int hc_get_enkf_sm_gain(hc_handle *h, double *gain)
 {
     if (int rc = sm_check(h, gain, "hc_get_enkf_sm_gain")) return rc;
-    return gain_hook(h, h->enkf_gain.p, gain, (size_t)h->sm_width, "hc_get_enkf_sm_gain");
+    return gain_hook(h, h->enkf_gain.p, gain, (size_t)h->enkf_sm.width, "hc_get_enkf_sm_gain");
 }
 
 int hc_get_enkf_sm_eps(hc_handle *h, double *eps)
 {
     if (int rc = eps_check(h, "hc_get_enkf_sm_eps")) return rc;
-    return sm_hook(h, h ? h->enkf_eps_s.p : nullptr, eps, h ? (size_t)h->n_members * h->sm_n : 0, "hc_get_enkf_sm_eps");
+    return sm_hook(h, h ? h->enkf_eps_s.p : nullptr, eps, h ? (size_t)h->n_members * h->enkf_sm.n : 0, "hc_get_enkf_sm_eps");
 }
 
 int hc_set_enkf_window(hc_handle *h, int32_t n_offsets, const int32_t *offsets)
@@ -6160,76 +6159,34 @@ int hc_set_enkf_window(hc_handle *h, int32_t n_offsets, const int32_t *offsets)
         return fail(HC_ERR_ARG, "hc_set_enkf_window: %d offsets, at most %d", (int)n_offsets, ENKF_SENSORS);
     if (n_offsets > 0 && h->enkf_stride <= 0)
         return fail(HC_ERR_ARG, "hc_set_enkf_window: the EnKF is off (hc_set_enkf comes first)");
-    if (n_offsets + h->sm_n > ENKF_SENSORS)
-        return fail(HC_ERR_ARG, "hc_set_enkf_window: %d offsets and %d sensors, at most %d together", (int)n_offsets,
-                    h->sm_n, ENKF_SENSORS);
-    std::vector<int> off(offsets, offsets + n_offsets);
-    std::sort(off.begin(), off.end());
-    for (int j = 0; j < n_offsets; j++) {
-        if (off[(size_t)j] < 1 || off[(size_t)j] >= h->enkf_stride)
-            return fail(HC_ERR_ARG, "hc_set_enkf_window: offset %d outside [1, %d) (the stride)", off[(size_t)j],
-                        h->enkf_stride);
-        if (j > 0 && off[(size_t)j] == off[(size_t)j - 1])
-            return fail(HC_ERR_ARG, "hc_set_enkf_window: offset %d twice", off[(size_t)j]);
-    }
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    win_off(h);
-    if (n_offsets == 0) return HC_OK;
-    h->win_n = n_offsets;
-    h->win_off = off;
-    h->win_row.assign((size_t)n_offsets, (int64_t)-1);
-    const int rc = ensure_win(h);
-    if (rc != HC_OK) win_off(h);                 // refused: off
-    return rc;
+    return window_set(h, h->enkf_win, h->enkf_sm.n, h->enkf_stride, win_off, ensure_win, "hc_set_enkf_window", n_offsets,
+                      offsets);
 }
 
 int hc_get_enkf_window_stats(hc_handle *h, double *table, int64_t n_entries)
 {
     if (!h || !table) return fail(HC_ERR_ARG, "hc_get_enkf_window_stats: bad argument");
-    return table_copy(h, h->win, ensure_win, hipMemcpyDeviceToHost, table, n_entries, "hc_get_enkf_window_stats");
+    return table_copy(h, h->enkf_win.table, ensure_win, hipMemcpyDeviceToHost, table, n_entries, "hc_get_enkf_window_stats");
 }
 
 int hc_set_enkf_window_stats(hc_handle *h, const double *table, int64_t n_entries)
 {
     if (!h || !table) return fail(HC_ERR_ARG, "hc_set_enkf_window_stats: bad argument");
-    return table_copy(h, h->win, ensure_win, hipMemcpyHostToDevice, const_cast<double *>(table), n_entries,
+    return table_copy(h, h->enkf_win.table, ensure_win, hipMemcpyHostToDevice, const_cast<double *>(table), n_entries,
                       "hc_set_enkf_window_stats");
 }
 
-// what the window holds for the coming analysis: checkpoints
 int hc_get_enkf_window_capture(hc_handle *h, double *y, int64_t *rows)
 {
     if (!h || !y || !rows) return fail(HC_ERR_ARG, "hc_get_enkf_window_capture: bad argument");
-    if (h->win_n <= 0) return fail(HC_ERR_ARG, "hc_get_enkf_window_capture: no window offsets (hc_set_enkf_window)");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    const size_t N = (size_t)h->n_members;
-    for (int j = 0; j < h->win_n; j++) {
-        rows[j] = h->win_row[(size_t)j];
-        if (rows[j] >= 0)
-            HIP_TRY(hipMemcpy(y + (size_t)j * N, h->win_y.p + (size_t)j * N, N * 8, hipMemcpyDeviceToHost));
-        else
-            std::fill_n(y + (size_t)j * N, N, 0.0);
-    }
-    return HC_OK;
+    return window_capture_get(h, h->enkf_win, "hc_get_enkf_window_capture", "hc_set_enkf_window", y, rows);
 }
 
 int hc_set_enkf_window_capture(hc_handle *h, const double *y, const int64_t *rows)
 {
     if (!h || !y || !rows) return fail(HC_ERR_ARG, "hc_set_enkf_window_capture: bad argument");
-    if (h->win_n <= 0) return fail(HC_ERR_ARG, "hc_set_enkf_window_capture: no window offsets (hc_set_enkf_window)");
-    const size_t N = (size_t)h->n_members;
-    for (int j = 0; j < h->win_n; j++)
-        if (rows[j] < -1 || rows[j] >= h->n_rows)
-            return fail(HC_ERR_ARG, "hc_set_enkf_window_capture: row %lld of offset %d outside [-1, %lld)", (long long)rows[j],
-                        h->win_off[(size_t)j], (long long)h->n_rows);
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->win_y.ensure((size_t)h->win_n * N)) return HC_ERR_DEVICE;
-    HIP_TRY(hipMemcpy(h->win_y.p, y, (size_t)h->win_n * N * 8, hipMemcpyHostToDevice));
-    h->win_row.assign(rows, rows + h->win_n);
-    return HC_OK;
+    if (int rc = window_capture_check(h, h->enkf_win, "hc_set_enkf_window_capture", "hc_set_enkf_window", rows)) return rc;
+    return window_capture_set(h, h->enkf_win, y, rows);
 }
 
 int hc_get_enkf_width(hc_handle *h, int32_t *width)
@@ -6242,25 +6199,21 @@ int hc_get_enkf_width(hc_handle *h, int32_t *width)
 int hc_get_enkf_window_width(hc_handle *h, int32_t *width, int32_t *slots)
 {
     if (!h || !width) return fail(HC_ERR_ARG, "hc_get_enkf_window_width: bad argument");
-    const bool any = h->enkf_stride > 0 && h->enkf_done && h->win_n > 0;
-    *width = any ? (int32_t)h->win_last.size() : 0;
-    if (slots)
-        for (int k = 0; k < *width; k++) slots[k] = h->win_last[(size_t)k];
-    return HC_OK;
+    return window_width(h->enkf_win, h->enkf_stride > 0 && h->enkf_done, width, slots);
 }
 
 // the last analysis's buffers when it had lagged columns (test hooks)
 static int win_check(hc_handle *h, const double *out, const char *who)
 {
     if (!h || !out) return fail(HC_ERR_ARG, "%s: bad argument", who);
-    if (h->win_n <= 0 || h->win_last.empty()) return fail(HC_ERR_ARG, "%s: the last analysis had no lagged row", who);
+    if (h->enkf_win.n <= 0 || h->enkf_win.last.empty()) return fail(HC_ERR_ARG, "%s: the last analysis had no lagged row", who);
     return HC_OK;
 }
 
 int hc_get_enkf_window_y(hc_handle *h, double *y)
 {
     if (int rc = win_check(h, y, "hc_get_enkf_window_y")) return rc;
-    const size_t mw = h->win_last.size(), W = (size_t)h->enkf_width;
+    const size_t mw = h->enkf_win.last.size(), W = (size_t)h->enkf_width;
     return enkf_hook(h, h->enkf_Y.p + (W - mw), y, (size_t)h->n_members, mw, W, "hc_get_enkf_window_y");
 }
 
@@ -6268,7 +6221,7 @@ int hc_get_enkf_window_eps(hc_handle *h, double *eps)
 {
     if (int rc = eps_check(h, "hc_get_enkf_window_eps")) return rc;
     if (int rc = win_check(h, eps, "hc_get_enkf_window_eps")) return rc;
-    const size_t n = (size_t)h->n_members * h->win_last.size();
+    const size_t n = (size_t)h->n_members * h->enkf_win.last.size();
     return enkf_hook(h, h->enkf_eps_w.p, eps, 1, n, n, "hc_get_enkf_window_eps");
 }
 

@@ -473,6 +473,45 @@ def test_refusals_and_what_turns_the_window_off():
         st.close()
 
 
+def _enkf_with_record_and_window():
+    """One point, 64 members of well 1, the EnKF on with a two-sensor record and the offsets (12, 24, 36); no row stepped."""
+    st, _, _ = _stepper(1, 64)
+    st.set_enkf(48, 5.0, 0.0, 1)
+    st.set_enkf_soil_moisture([6, 45], _record(st.T, [6, 45], [0.24, 0.36]), 0.02)
+    st.set_enkf_window([12, 24, 36])
+    return st
+
+
+def test_the_particle_filters_off_calls_leave_the_enkfs_record_and_window_alone():
+    from hydromodel_amd import _lib as L
+    st = _enkf_with_record_and_window()
+    try:
+        L.check(st.lib.hc_set_filter_soil_moisture(st.h, 0, None, None, None))
+        L.check(st.lib.hc_set_filter_window(st.h, 0, None))
+        n_arow = (st.T - 1) // 48 + 1
+        sm, wt = st.enkf_sm_table(), st.enkf_window_table()
+        assert sm.shape == (1, n_arow, 2, 6) and np.isnan(sm).all()
+        assert wt.shape == (1, n_arow, 3, 4) and np.isnan(wt).all()
+        assert st.enkf_window_capture()[1].tolist() == [-1, -1, -1]
+    finally:
+        st.close()
+
+
+def test_nothing_of_the_enkfs_carries_over_to_the_particle_filter():
+    from hydromodel_amd import _lib as L
+    st = _enkf_with_record_and_window()
+    try:
+        st.set_enkf(0)
+        st.set_filter(48, 5.0, 1)
+        assert st.filter_sm_width() == 0
+        with pytest.raises(L.HcError, match="no soil-moisture record"):
+            L.check(st.lib.hc_get_filter_sm_stats(st.h, L.dptr(np.zeros(1)), -1))
+        with pytest.raises(L.HcError, match="no window offsets"):
+            st.filter_window_capture()
+    finally:
+        st.close()
+
+
 def test_cli_window_offsets_writes_the_datasets(tmp_path, monkeypatch, capsys):
     from hydromodel_amd import cli
     from hydromodel_amd.simulation import loadResults

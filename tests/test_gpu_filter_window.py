@@ -459,6 +459,45 @@ def test_refusals_and_what_turns_the_window_off():
         st.close()
 
 
+def _filter_with_record_and_window():
+    """One point, 64 members of well 1, the filter on with the two-sensor record and the offsets (12, 24, 36); no row stepped."""
+    st, _, _ = _stepper(1, 64)
+    st.set_filter(48, 5.0, 1)
+    st.set_filter_soil_moisture(NODES, _record(st.T, VALUES), SIGMAS)
+    st.set_filter_window(OFFSETS)
+    return st
+
+
+def test_the_enkfs_off_calls_leave_the_filters_record_and_window_alone():
+    from hydromodel_amd._lib import check
+    st = _filter_with_record_and_window()
+    try:
+        check(st.lib.hc_set_enkf_soil_moisture(st.h, 0, None, None, None))
+        check(st.lib.hc_set_enkf_window(st.h, 0, None))
+        n_arow = (st.T - 1) // 48 + 1
+        sm, wt = st.filter_sm_table(), st.filter_window_table()
+        assert sm.shape == (1, n_arow, 2, 6) and np.isnan(sm).all()
+        assert wt.shape == (1, n_arow, 3, 4) and np.isnan(wt).all()
+        assert st.filter_window_capture()[1].tolist() == [-1, -1, -1]
+    finally:
+        st.close()
+
+
+def test_nothing_of_the_filters_carries_over_to_the_enkf():
+    from hydromodel_amd._lib import HcError, check, dptr
+    st = _filter_with_record_and_window()
+    try:
+        st.set_filter(0)
+        st.set_enkf(48, 5.0, 0.0, 1)
+        assert st.enkf_sm_width() == 0
+        with pytest.raises(HcError, match="no soil-moisture record"):
+            check(st.lib.hc_get_enkf_sm_stats(st.h, dptr(np.zeros(1)), -1))
+        with pytest.raises(HcError, match="no window offsets"):
+            st.enkf_window_capture()
+    finally:
+        st.close()
+
+
 # ---- 8. checkpoint -----------------------------------------------------------------------------------------------------
 def test_dump_between_a_capture_and_its_assimilation_resumes_bit_for_bit(tmp_path):
     from hydromodel_amd.ensemble import EnsembleSimulation
