@@ -155,6 +155,17 @@ unknown keys, only membership of the 12 is checked):
   [0, 1] (default 0 = none), for either method: after each analysis every node's spread is (1 - alpha) sigma_a + alpha
   sigma_b, and the posterior datasets describe the relaxed ensemble.  Added to ``<Output_Name>_ensemble.h5`` when either
   is given: ``enkf_method`` (0 = stochastic, 1 = sqrt) and ``enkf_relaxation``.
+* ``"EnKF": {..., "Noise_Field": true}`` or ``{"Noise_Field": {"Relaxation": 0.5}}``: every analysis also updates each
+  member's base noise vector -- its conductivity field -- together with its state, from the same observations, draws and
+  factor (include/hydrocol.h hc_set_enkf_noise_field).  The vectors' anomalies are relaxed to prior spread with the
+  given ``Relaxation`` (``true``: the block's); parameters regain no spread from the dynamics, so without one a long run
+  collapses the field.  Refused: outside an EnKF block with ``Stride`` > 0, a value that is neither a bool nor an object
+  with the one key ``Relaxation``, a relaxation outside [0, 1], and ``"Sharded": true`` on a single-point run (the
+  exchanged partials cover psi only).  Without the key, or with ``false``, nothing changes.  Added to
+  ``<Output_Name>_ensemble.h5``: ``enkf_noise_field`` (1), ``enkf_noise_relaxation`` and, over the ``enkf_rows`` ``[R]``,
+  ``enkf_noise_prior_mean``, ``enkf_noise_prior_std``, ``enkf_noise_post_mean``, ``enkf_noise_post_std`` ``[R][D]`` and
+  ``enkf_noise_rejected`` ``[R]`` (a sweep: a leading ``[P]`` axis), and the run ends with `` [Ensemble xN] EnKF noise
+  field: posterior spread ... of prior over R rows`` (the mean over nodes and rows of sigma_post / sigma_prior).
 * ``"EnKF": {..., "Window_Offsets": [12, 24, 36]}``: the well's record inside the window (the asynchronous EnKF of Sakov,
   Evensen & Bertino 2010; include/hydrocol.h hc_set_enkf_window).  Each entry is a number of rows before the analysis
   row: distinct integers in [1, ``Stride``), at most 8, and at most 8 together with the ``Soil_Moisture`` depths.  On such a
@@ -231,6 +242,7 @@ def main(params_file=None, data_file=None, seed=None, device=0, gpus=None, _sett
             soil_moisture_settings(params["Ensemble"], n_gpus, "Filter")
             enkf_method_settings(params["Ensemble"])
             enkf_window_settings(params["Ensemble"])
+            enkf_noise_settings(params["Ensemble"])
             filter_window_settings(params["Ensemble"])
         ranks = multigpu.Ranks(expect=n_gpus if (n_gpus > 1 or multigpu.in_rank()) else None)
         if ranks.world > 1:
@@ -298,6 +310,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     fsm = soil_moisture_settings(ens, ranks.world, "Filter")
     scheme = enkf_method_settings(ens)
     window = enkf_window_settings(ens)
+    noise_alpha = enkf_noise_settings(ens)
     fwindow = filter_window_settings(ens)
     cols = ColumnTables(params, load_site_well(params))
     forcing = ForcingDigest(params, water_data, cols)
@@ -312,7 +325,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     plan = period_plan(periods, cols, forcing, rows)            # before any GPU call, like the storage's ranges
     if ens.get("Points"):
         return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels, filt,
-                          enkf, record, scheme, window, frecord, theta, storage, periods, plan, ess_floor, fwindow)
+                          enkf, record, scheme, window, frecord, theta, storage, periods, plan, ess_floor, fwindow,
+                          noise_alpha)
     sharded = enkf_sharded(ens)
     fsharded = filter_sharded(ens)
     if sharded:
@@ -335,7 +349,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
                              spinup=str(ens.get("Spinup", "shared")).lower(), profile_stride=stride,
                              wtd_hist_stride=dist_stride, theta_hist_bins=theta[0],
                              **_filter_kwargs(filt, frecord, ess_floor, fwindow),
-                             **_enkf_kwargs(enkf, record, scheme, window), **_storage_kwargs(storage),
+                             **_enkf_kwargs(enkf, record, scheme, window, noise_alpha), **_storage_kwargs(storage),
                              **_period_kwargs(periods, plan), **shard_kw)
     label = f"Ensemble x{n_members}"
     _step_all(sim, rows, label, ranks)
@@ -396,6 +410,9 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     wtables, window_line = _reduce_enkf_window(ranks, sim, eids, 1, forcing.dim_t, enkf, window, label, keep_points=False,
                                                z0_cm=cols.z[0])
     extra.update(wtables)
+    ntables, noise_line = _reduce_enkf_noise(ranks, sim, eids, 1, forcing.dim_t, cols.dim_d, enkf, noise_alpha, label,
+                                             keep_points=False)
+    extra.update(ntables)
     arrays = dict(moments=moments, wtd_mean_cm=mean_cm, wtd_std_cm=std_cm, rows=np.array(rows),
                   members=np.array(n_members), gpus=np.array(ranks.world), initial_cond=psi0, **extra)
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "ensemble water-table statistics", ranks)
@@ -413,6 +430,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
         print(sm_line)
     if window_line:
         print(window_line)
+    if noise_line:
+        print(noise_line)
     if theta_line:
         print(theta_line)
     if storage_line:
@@ -803,7 +822,7 @@ def filter_sharded(ens):
 
 
 ENKF_KEYS = ("Stride", "Sigma_cm", "Localisation_cm", "Seed", "Soil_Moisture", "Method", "Relaxation", "Window_Offsets",
-             "Sharded")
+             "Sharded", "Noise_Field")
 
 
 def enkf_settings(ens, n_gpus=1):
@@ -885,6 +904,62 @@ def enkf_method_settings(ens):
     return method, float(alpha)
 
 
+def enkf_noise_settings(ens):
+    """Ensemble.EnKF.Noise_Field -> the relaxation of the noise field's anomalies, or None when the key is absent or false
+    (the run, its file and its lines are then those of a block without it).  ``true``: the block's ``Relaxation`` (0
+    without one); ``{"Relaxation": a}``: a.  Pure, like :func:`enkf_settings`: a bad value is a ValueError (message + exit
+    status 1): a value that is neither a bool nor an object with the one key ``Relaxation``; a relaxation outside [0, 1]
+    or a bool; a block whose Stride is 0; ``"Sharded": true`` on a single-point run (a sweep ignores Sharded)."""
+    from numbers import Real
+    from .stepper import noise_field_settings
+    block = ens.get("EnKF")
+    if not isinstance(block, dict) or "Noise_Field" not in block:
+        if "Noise_Field" in ens:
+            raise ValueError(" Ensemble: Noise_Field belongs inside the \"EnKF\" block.")
+        return None
+    inherited = block.get("Relaxation", 0.0)
+    inherited = float(inherited) if isinstance(inherited, Real) and not isinstance(inherited, bool) else 0.0
+    value = block["Noise_Field"]
+    if value is None or (isinstance(value, dict) and list(value) != ["Relaxation"]):
+        raise ValueError(f" Ensemble: EnKF.Noise_Field = {value!r} must be true, false or {{\"Relaxation\": a}}.")
+    try:
+        alpha = noise_field_settings(value, inherited if 0.0 <= inherited <= 1.0 else 0.0)
+    except ValueError as bad:
+        raise ValueError(f" Ensemble: EnKF.{bad}.") from None
+    if alpha is None:
+        return None
+    stride = block.get("Stride", 48)
+    if isinstance(stride, Real) and not isinstance(stride, bool) and stride == 0:
+        raise ValueError(" Ensemble: EnKF.Noise_Field needs an active EnKF (EnKF.Stride > 0).")
+    if block.get("Sharded") is True and not ens.get("Points"):
+        raise ValueError(" Ensemble: EnKF.Noise_Field with \"Sharded\": true: the partials the ranks exchange cover psi "
+                         "only, not the noise field.")
+    return alpha
+
+
+def _reduce_enkf_noise(ranks, sim, ids, P, T, D, enkf, noise_alpha, label, keep_points):
+    """The noise field's datasets from this rank's handle over the EnKF's analysed rows (its ``enkf_rows``), the [P]
+    table placed and summed over the ranks like the EnKF's (float64 as int64 bits), and the closing line (rank 0)."""
+    import numpy as np
+    from .multigpu import place_points
+    from .stepper import enkf_noise_summary, stride_rows
+    stride = enkf[0]
+    if not stride or noise_alpha is None:
+        return {}, None
+    n_arow, width = stride_rows(T, stride), 4 * D + 1
+    local = sim.enkf_noise_table().reshape(-1, n_arow, width) if sim is not None else np.zeros((0, n_arow, width))
+    table = place_points(local, ids, P, ranks)
+    summary = enkf_noise_summary(table if keep_points else table[0], stride, noise_alpha, D)
+    out = {"enkf_noise_field": np.array(1, dtype=np.int8), "enkf_noise_relaxation": np.array(noise_alpha, dtype=np.float64)}
+    out.update(("enkf_" + k, summary[k]) for k in ("noise_prior_mean", "noise_prior_std", "noise_post_mean",
+                                                    "noise_post_std", "noise_rejected"))
+    if ranks.rank != 0:
+        return out, None
+    line = (f" [{label}] EnKF noise field: posterior spread {summary['noise_spread_ratio']:.4f} of prior over "
+            f"{int(summary['rows'].size)} rows")
+    return out, line
+
+
 def enkf_window_settings(ens):
     """Ensemble.EnKF.Window_Offsets -> the offsets as an ascending tuple, or None when the key is absent or the list empty
     (the run, its file and its lines are then those of a block without it).  Pure, like :func:`enkf_settings`: a bad
@@ -946,7 +1021,7 @@ def _reduce_enkf_window(ranks, sim, ids, P, T, enkf, window, label, keep_points,
     return out, line
 
 
-def _enkf_kwargs(enkf, record=None, scheme=None, window=None):
+def _enkf_kwargs(enkf, record=None, scheme=None, window=None, noise_alpha=None):
     stride, sigma, loc, seed = enkf
     if not stride:
         return {}
@@ -957,6 +1032,8 @@ def _enkf_kwargs(enkf, record=None, scheme=None, window=None):
         kw.update(enkf_method=scheme[0], enkf_relaxation=scheme[1])
     if window:
         kw["enkf_window_offsets"] = window
+    if noise_alpha is not None:
+        kw["enkf_noise_field"] = {"relaxation": noise_alpha}
     return kw
 
 
@@ -1435,7 +1512,7 @@ def _reduce_periods(ranks, sim, ids, P, cols, forcing, periods, plan, label, kee
 
 def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride=0, dist_levels=None,
                filt=(0, None, None), enkf=(0, None, None, None), record=None, scheme=None, window=None, frecord=None,
-               theta=(0, None), storage=None, periods=None, plan=None, ess_floor=None, fwindow=None):
+               theta=(0, None), storage=None, periods=None, plan=None, ess_floor=None, fwindow=None, noise_alpha=None):
     """Parameter points x members: this rank's points in one handle (ensemble.SweepSimulation), the whole table assembled
     over the ranks (multigpu.assemble_points)."""
     import numpy as np
@@ -1463,7 +1540,7 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
         sim = SweepSimulation(points, forcing, n_members, seed=int(ens.get("Seed", 0)), device=device, point_ids=mine,
                               profile_stride=stride, wtd_hist_stride=dist_stride, theta_hist_bins=theta[0],
                               **_filter_kwargs(filt, frecord, ess_floor, fwindow),
-                              **_enkf_kwargs(enkf, record, scheme, window),
+                              **_enkf_kwargs(enkf, record, scheme, window, noise_alpha),
                               **_storage_kwargs(storage), **_period_kwargs(periods, plan))
         _step_all(sim, rows, label, ranks)
         table = sim.moments()
@@ -1500,6 +1577,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     wtables, window_line = _reduce_enkf_window(ranks, sim, mine, P, T, enkf, window, label, keep_points=True,
                                                z0_cm=cols_all[0].z[0])
     arrays.update(wtables)
+    ntables, noise_line = _reduce_enkf_noise(ranks, sim, mine, P, T, ref.dim_d, enkf, noise_alpha, label, keep_points=True)
+    arrays.update(ntables)
     if sim is not None:
         sim.close()
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "sweep's water-table statistics", ranks)
@@ -1517,6 +1596,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
         print(sm_line)
     if window_line:
         print(window_line)
+    if noise_line:
+        print(noise_line)
     if theta_line:
         print(theta_line)
     if storage_line:
@@ -1549,6 +1630,7 @@ def run_cli(argv=None):
                 soil_moisture_settings(settings["Ensemble"], n_gpus, "Filter")
                 enkf_method_settings(settings["Ensemble"])
                 enkf_window_settings(settings["Ensemble"])
+                enkf_noise_settings(settings["Ensemble"])
                 filter_window_settings(settings["Ensemble"])
             except ValueError as bad:
                 print(bad)

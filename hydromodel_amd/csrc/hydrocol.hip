@@ -316,6 +316,16 @@ struct hc_handle {
     hc_enkf_exchange_fn shard_fn = nullptr;
     void *shard_ctx = nullptr;
     DevBuf<double> enkf_first;
+    // the members' base noise vectors in the analysis (hc_set_enkf_noise_field): on / off and the relaxation of their
+    // anomalies; diagnostics float64 [P][n_arow][4 D + 1] keyed like the EnKF's; per point the raw sums of both prior
+    // passes over (z, Y), the gain [P][m'][D] (square root: the reduced gain and the mean's increment), the squared
+    // anomalies before / after, the sums of the analysed vectors, (sigma_b, sigma_a, f, mean) [4][P][D]; per member
+    // whether its updated vector was refused, and that flag's sum per point
+    bool enkf_nz = false, nz_done = false;   // on; an analysis has updated the vectors since it was set
+    double enkf_nz_alpha = 0.0;
+    bool noise_host() const { return (filt_stride > 0 || enkf_nz) && philox; }   // filt_host(), or the noise field's twin
+    AccTable<double> enkf_nzt{"entries"};
+    DevBuf<double> nz_s1, nz_s2, nz_gain, nz_rgain, nz_dbar, nz_sq_b, nz_sq_a, nz_mean_a, nz_relax, nz_rej, nz_rejsum;
     int n_cu = 256;
     double jac_reject = NUM_JAC_DIFF_REJECT;
 };
@@ -1724,6 +1734,8 @@ __device__ bool enkf_cholesky(const double *A, int n, double *L)
 // analysis (rgain != NULL) also takes the mean's increment dbar[p][d] = sum_i K_di (o_i - Ybar_i), i in order, and the
 // reduced gain Kr_d = (rho_d o c_d) L^-T (L + R^1/2)^-1 into rgain[p][i][d]: the forward substitution once more, then a
 // backward substitution with the lower-triangular L + R^1/2 (the same LDS working set).
+// stats == NULL (the noise field's gain, hc_set_enkf_noise_field: s1 and s2 are the sums over (z, Y), whose Y block is
+// the state's to the bit, and so is the factor): no table is written.
 __global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void enkf_gain_kernel(const double *s1, const double *s2, long long mpp,
                                                                        int D, const EnkfRow s, double sigma, double loc,
                                                                        double z_obs, double dz, double *gain,
@@ -1757,10 +1769,10 @@ __global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void enkf_gain_kernel(const dou
             }
         ok = enkf_cholesky(A, W, Ls) ? 1 : 0;
         // log N(obs; ybar, C_YY + R) = -0.5 (m' log 2 pi + log det + |L^-1 (obs - ybar)|^2)
-        for (int i = 0; i < W; i++)
+        for (int i = 0; stats && i < W; i++)
             for (int k = 0; k < W; k++) A[i * ENKF_OBS + k] = cyy[i * ENKF_OBS + k] + (i == k ? r2[i] : 0.0);
         double ll = __builtin_nan("");
-        if (enkf_cholesky(A, W, Lu)) {
+        if (stats && enkf_cholesky(A, W, Lu)) {
             double logdet = 0.0, q = 0.0;
             for (int i = 0; i < W; i++) {
                 double v = dl[i];
@@ -1771,13 +1783,15 @@ __global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void enkf_gain_kernel(const dou
             }
             ll = -0.5 * ((double)W * log(2.0 * M_PI) + 2.0 * logdet + q);
         }
-        double *st = stats + ((size_t)p * n_arow + slot) * ENKF_WIDTH;
-        st[0] = (double)mpp;
-        st[1] = yb[0];
-        st[2] = sqrt(cyy[0]);
-        st[3] = dl[0];
-        st[4] = ll;
-        if (s.ms > 0) {
+        if (stats) {
+            double *st = stats + ((size_t)p * n_arow + slot) * ENKF_WIDTH;
+            st[0] = (double)mpp;
+            st[1] = yb[0];
+            st[2] = sqrt(cyy[0]);
+            st[3] = dl[0];
+            st[4] = ll;
+        }
+        if (stats && s.ms > 0) {
             double *ss = sm_stats + ((size_t)p * n_arow + slot) * s.n * ENKF_SENSOR_WIDTH;
             for (int i = 0; i < s.n; i++) ss[i * ENKF_SENSOR_WIDTH] = 0.0;      // observed: 0 unless present (the rest stays NaN)
             for (int k = 0; k < s.ms; k++) {
@@ -1788,7 +1802,7 @@ __global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void enkf_gain_kernel(const dou
                 e[3] = sqrt(cyy[(k + 1) * ENKF_OBS + k + 1]);
             }
         }
-        if (s.m > s.ms) {
+        if (stats && s.m > s.ms) {
             double *ws = win_stats + ((size_t)p * n_arow + slot) * s.nw * ENKF_WINDOW_WIDTH;
             for (int i = 0; i < s.nw; i++) ws[i * ENKF_WINDOW_WIDTH] = 0.0;     // observed: 0 unless present (the rest stays NaN)
             for (int k = s.ms; k < s.m; k++) {
@@ -1937,7 +1951,9 @@ __device__ __forceinline__ double enkf_column_y(const double (&a)[ENKF_SLOTS], i
 // stored only when every entry is finite (else the forecast stays and the member is counted as rejected); then the
 // find_wtd index and the y of the column it kept: out = Ypost[m] = (y, ..., rejected), V entries (enkf_theta_kernel
 // fills in the posterior theta).  want_y = 0: the relaxation follows and writes y.
-template <bool SHIFT>
+// STATE = false: col is the member's base noise vector (hc_set_enkf_noise_field), which has no water table: the vote
+// stays, the tail does not, and out[0] = 1.0 when the vector was refused, else 0.0.
+template <bool SHIFT, bool STATE>
 __device__ __forceinline__ void enkf_update_column(double *col, const double *K, const double *shift, int W, double my_dl,
                                                    int lane, int D, double psat, double dz, int want_y, double *out, int V)
 {
@@ -1973,6 +1989,10 @@ __device__ __forceinline__ void enkf_update_column(double *col, const double *K,
 #pragma unroll
     for (int c = 0; c < ENKF_SLOTS; c++) inc[c] = c * WAVE + lane < D ? a[c] + inc[c] : 0.0;
     const bool keep = enkf_keep_column(a, inc, col, lane, D);
+    if (!STATE) {
+        if (lane == 0) out[0] = keep ? 0.0 : 1.0;
+        return;
+    }
     if (want_y) {
         const double y = enkf_column_y(a, lane, D, psat, dz);
         if (lane == 0) out[0] = y;
@@ -1983,11 +2003,15 @@ __device__ __forceinline__ void enkf_update_column(double *col, const double *K,
 // The stochastic update, one wave per member: lane i's innovation is o_i + sigma_i eps_ki - Y_ki from the draws of
 // enkf_draw_kernel (and enkf_window_draw_kernel): the well's on lane 0, present sensor k's and then the lagged rows' on
 // lane 1 + k.
+// STATE = false updates the members' base noise vectors (psi = the base array, gain = their gain) after the state's
+// update, with the same innovations: a member whose state was refused (Ypost[m][V - 1] != 0) keeps its vector to the
+// bit, and refused[m] = 1.0 for a member whose updated vector was not finite (it keeps the old one), else 0.0.
+template <bool STATE>
 __global__ __launch_bounds__(256) void enkf_update_kernel(double *psi, const double *Y, const double *gain,
                                                           const ColumnDev *P, long long n_members, long long mpp, int D,
                                                           double dz, double z_obs, double sigma, const EnkfRow s,
                                                           const double *eps, const double *eps_s,
-                                                          const double *eps_w, int want_y, double *Ypost)
+                                                          const double *eps_w, int want_y, double *Ypost, double *refused)
 {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x % WAVE;
@@ -2007,17 +2031,23 @@ __global__ __launch_bounds__(256) void enkf_update_kernel(double *psi, const dou
                              : lane <= s.ms ? (my_obs + my_sigma * eps_s[(size_t)m * s.n + my_sensor]) - Ym[lane]
                              : lane < W     ? (my_obs + my_sigma * eps_w[(size_t)m * mw + my_sensor]) - Ym[lane]
                                             : 0.0;
-        enkf_update_column<false>(psi + (size_t)m * D, gain + (size_t)p * W * D, nullptr, W, my_dl, lane, D, P[p].psi_sat,
-                                  dz, want_y, Ypost + (size_t)m * V, V);
+        if (!STATE && Ypost[(size_t)m * V + V - 1] != 0.0) {
+            if (lane == 0) refused[m] = 0.0;
+            continue;
+        }
+        enkf_update_column<false, STATE>(psi + (size_t)m * D, gain + (size_t)p * W * D, nullptr, W, my_dl, lane, D,
+                                         P[p].psi_sat, dz, want_y, STATE ? Ypost + (size_t)m * V : refused + m, V);
     }
 }
 
 // The square-root update (Whitaker & Hamill 2002), one wave per member: the reduced gain, the mean's increment dbar as
 // the shift, and lane i's innovation Ybar_i - Y_ki (Ybar from the prior sums s1 [P][D + m']).  Nothing is drawn.
+// STATE = false: the base noise vectors, as in enkf_update_kernel.
+template <bool STATE>
 __global__ __launch_bounds__(256) void enkf_sqrt_update_kernel(double *psi, const double *Y, const double *rgain,
                                                                const double *dbar, const double *s1, const ColumnDev *P,
                                                                long long n_members, long long mpp, int D, double dz,
-                                                               int W, int V, int want_y, double *Ypost)
+                                                               int W, int V, int want_y, double *Ypost, double *refused)
 {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x % WAVE;
@@ -2025,8 +2055,12 @@ __global__ __launch_bounds__(256) void enkf_sqrt_update_kernel(double *psi, cons
     for (long long m = (long long)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE; m < n_members; m += waves) {
         const long long p = m / mpp;
         const double my_dl = lane < W ? s1[(size_t)p * (D + W) + D + lane] / (double)mpp - Y[(size_t)m * W + lane] : 0.0;
-        enkf_update_column<true>(psi + (size_t)m * D, rgain + (size_t)p * W * D, dbar + (size_t)p * D, W, my_dl, lane, D,
-                                 P[p].psi_sat, dz, want_y, Ypost + (size_t)m * V, V);
+        if (!STATE && Ypost[(size_t)m * V + V - 1] != 0.0) {
+            if (lane == 0) refused[m] = 0.0;
+            continue;
+        }
+        enkf_update_column<true, STATE>(psi + (size_t)m * D, rgain + (size_t)p * W * D, dbar + (size_t)p * D, W, my_dl, lane,
+                                        D, P[p].psi_sat, dz, want_y, STATE ? Ypost + (size_t)m * V : refused + m, V);
     }
 }
 
@@ -2097,16 +2131,20 @@ __global__ void enkf_relax_factor_kernel(const double *sq_b, const double *sq_a,
 
 // One wave per member: psi_dk <- mean_d + f_d (psi_dk - mean_d) (the analysis's mean [P][D]; a node with f_d = 1
 // stays as it is), stored only when every entry is finite (else the member keeps its unrelaxed analysis); then find_wtd
-// and y of the column it kept into Ypost[m][0] (rows of `width` entries).
+// and y of the column it kept into Ypost[m][0] (rows of `width` entries).  STATE = false: the base noise vectors; no y,
+// and a member whose state's analysis was refused (Ypost[m][width - 1] != 0), or whose own updated vector was
+// (refused[m] != 0), is left alone.
+template <bool STATE>
 __global__ __launch_bounds__(256) void enkf_relax_kernel(double *psi, const double *means, const double *factor,
                                                          const ColumnDev *P, long long n_members, long long mpp, int D,
-                                                         double dz, int width, double *Ypost)
+                                                         double dz, int width, double *Ypost, const double *refused)
 {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x % WAVE;
     const long long waves = (long long)gridDim.x * (blockDim.x / WAVE);
     for (long long m = (long long)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE; m < n_members; m += waves) {
         const long long p = m / mpp;
+        if (!STATE && (Ypost[(size_t)m * width + width - 1] != 0.0 || refused[m] != 0.0)) continue;
         const double *S = means + (size_t)p * D, *F = factor + (size_t)p * D;
         double *col = psi + (size_t)m * D;
         double a[ENKF_SLOTS], r[ENKF_SLOTS];
@@ -2122,9 +2160,33 @@ __global__ __launch_bounds__(256) void enkf_relax_kernel(double *psi, const doub
             }
         }
         enkf_keep_column(a, r, col, lane, D);
-        const double y = enkf_column_y(a, lane, D, P[p].psi_sat, dz);
-        if (lane == 0) Ypost[(size_t)m * width] = y;
+        if (STATE) {
+            const double y = enkf_column_y(a, lane, D, P[p].psi_sat, dz);
+            if (lane == 0) Ypost[(size_t)m * width] = y;
+        }
     }
+}
+
+// The noise field's diagnostics, one thread per point and node: the prior mean and std of z_d from the prior sums
+// (s1 [P][D + m'], the squared anomalies sq_b), the posterior's -- after the relaxation -- from the spread passes (z_d of
+// the point's first member + sums / N_p; sq_a), into table[p][slot][4][D]; node 0's thread adds the point's refused
+// count behind them.
+__global__ void enkf_noise_diag_kernel(const double *s1, const double *sq_b, const double *sums, const double *sq_a,
+                                       const double *base, const double *rejsum, long long n_points, long long mpp, int D,
+                                       int W, double *table, long long n_arow, long long slot)
+{
+#pragma clang fp contract(off)
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_points * D) return;
+    const long long p = k / D;
+    const int d = (int)(k % D);
+    const double n1 = (double)(mpp - 1);
+    double *t = table + ((size_t)p * n_arow + slot) * (4 * (size_t)D + 1);
+    t[d] = s1[(size_t)p * (D + W) + d] / (double)mpp;
+    t[D + d] = mpp > 1 ? sqrt(sq_b[k] / n1) : 0.0;
+    t[2 * D + d] = base[(size_t)(p * mpp) * D + d] + sums[k] / (double)mpp;
+    t[3 * D + d] = mpp > 1 ? sqrt(sq_a[k] / n1) : 0.0;
+    if (d == 0) t[4 * (size_t)D] = rejsum[p];
 }
 
 // One thread per point: the posterior diagnostics from the raw sums of Ypost (s1 [P][W + 1], s2 [P][W + 1][W + 1]): the
@@ -3308,6 +3370,14 @@ int ensure_enkf(hc_handle *h)
     return ensure_da_table(h, h->enkf, h->enkf_stride, ENKF_WIDTH, ENKF_WIDTH);
 }
 
+// the noise field's diagnostics (hc_set_enkf_noise_field): [P][n_arow][4 D + 1] float64, created as NaN
+int ensure_nz(hc_handle *h)
+{
+    if (!h->enkf_nz) return fail(HC_ERR_ARG, "the noise field is off (hc_set_enkf_noise_field)");
+    if (int rc = ensure_enkf(h)) return rc;
+    return ensure_da_table(h, h->enkf_nzt, h->enkf_stride, 4 * (int64_t)h->p.dim_d + 1, 0);
+}
+
 int ensure_sm(hc_handle *h) { return ensure_record(h, h->enkf_sm, ensure_enkf, h->enkf_stride, "hc_set_enkf_soil_moisture"); }
 int ensure_win(hc_handle *h) { return ensure_window(h, h->enkf_win, ensure_enkf, h->enkf_stride, "hc_set_enkf_window"); }
 
@@ -3341,9 +3411,20 @@ int64_t shard_words_needed(const hc_handle *h, int64_t n_global)
     return n_tiles * std::max((D + Wx) * Wx + D, (Wx + 1) * (Wx + 1));
 }
 
+void nz_off(hc_handle *h)
+{
+    h->enkf_nz = h->nz_done = false;
+    h->enkf_nz_alpha = 0.0;
+    h->enkf_nzt.release();
+    h->nz_s1.release(); h->nz_s2.release(); h->nz_gain.release(); h->nz_rgain.release(); h->nz_dbar.release();
+    h->nz_sq_b.release(); h->nz_sq_a.release(); h->nz_mean_a.release(); h->nz_relax.release(); h->nz_rej.release();
+    h->nz_rejsum.release();
+}
+
 void enkf_off(hc_handle *h)
 {
     shard_off(h);
+    nz_off(h);
     h->enkf_stride = 0;
     h->enkf_done = false;
     h->enkf_width = 0;
@@ -3476,7 +3557,7 @@ int fill_args(hc_handle *h, StepArgs &A)
     A.n_members = h->n_members;
     A.D = h->P.D;
     A.n_groups = h->P.n_groups;
-    A.host_noise = h->philox && !h->filt_host() ? 0 : 1;   // a filtered Philox run hands its normals over as caller noise
+    A.host_noise = h->philox && !h->noise_host() ? 0 : 1;   // a filtered Philox run hands its normals over as caller noise
     A.psi_sat = h->P.psi_sat;
     A.jac_reject = h->jac_reject;
     A.max_phase_iterations = h->max_phase_iterations;
@@ -3628,6 +3709,13 @@ static int build_point(hc_handle *h, const hc_column_params *p, const double *no
         return fail(HC_ERR_ARG, "a parameter point must share dim_d, n_groups and dz with point 0");
     // low_lim = k - (sat_cells - 1) must stay inside the k-cell slice pde_fun sees: sat_cells >= 1
     if (p->flag_predict && p->sat_cells < 1) return fail(HC_ERR_ARG, "PREDICT mode: sat_cells = %d, must be >= 1", p->sat_cells);
+    // delta = por - theta_res divides the effective saturation: with delta <= 0 a saturated cell would silently get K = 0
+    for (int i = 0; i < D; i++)
+        if (!(node_tabs[i] > p->theta_res))
+            return fail(HC_ERR_ARG, "node %d: porosity %g is not above theta_res = %g", i, node_tabs[i], p->theta_res);
+    for (int i = 0; i < D - 1; i++)
+        if (!(mid_tabs[i] > p->theta_res))
+            return fail(HC_ERR_ARG, "cell %d: porosity %g is not above theta_res = %g", i, mid_tabs[i], p->theta_res);
     ColumnDev P{};
     P.D = D; P.model = p->model; P.flag_et = p->flag_et; P.flag_lf = p->flag_lf; P.flag_hlift = p->flag_hlift;
     P.n_root_first = p->n_root_first; P.n_root_int = p->n_root_int; P.n_groups = p->n_groups;
@@ -4178,7 +4266,7 @@ Chunk plan_chunk(const hc_handle *h, const hc_step_args *a, int64_t done, bool p
                     c.rows = r + 1;
                     break;
                 }
-        if (h->filt_host()) {
+        if (h->noise_host()) {
             const int64_t cap = std::max<int64_t>(1, FILT_FRESH_BYTES / (N * D * 8));
             int64_t n_fresh = 0;
             for (int r = 0; r < c.rows; r++)
@@ -4220,7 +4308,7 @@ int stage_noise(hc_handle *h, const hc_step_args *a, const Chunk &c, int64_t con
     if (!a->spinup)
         for (int r = 0; r < c.rows; r++) n_fresh += h->h_refresh[(size_t)(c.row0 + r)] ? 1 : 0;
     if (n_fresh == 0) return HC_OK;
-    if (h->filt_host()) {
+    if (h->noise_host()) {
         // the kernel's own normals of the launch's refresh rows, keyed by each slot's stream and the row's draw index
         h->filt_rows_host.clear();
         for (int r = 0; r < c.rows; r++)
@@ -4736,6 +4824,16 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
                   h->enkf_sq_a.ensure((size_t)(P * D)) || h->enkf_mean_a.ensure((size_t)(P * D)) ||
                   h->enkf_relax.ensure((size_t)(4 * P * D))))
         return HC_ERR_DEVICE;
+    if (h->enkf_nz) {
+        if (shard) return fail(HC_ERR_ARG, "the noise field with a sharded analysis: the exchanged partials cover psi only");
+        if (h->enkf_part_sq.ensure((size_t)(P * n_tiles * D)) || h->nz_s1.ensure((size_t)(P * Cx)) ||
+            h->nz_s2.ensure((size_t)(P * Cx * Wx)) || h->nz_gain.ensure((size_t)(P * Wx * D)) ||
+            h->nz_sq_b.ensure((size_t)(P * D)) || h->nz_sq_a.ensure((size_t)(P * D)) || h->nz_mean_a.ensure((size_t)(P * D)) ||
+            h->nz_rej.ensure((size_t)N) || h->nz_rejsum.ensure((size_t)P) ||
+            (root && (h->nz_rgain.ensure((size_t)(P * Wx * D)) || h->nz_dbar.ensure((size_t)(P * D)))) ||
+            (h->enkf_nz_alpha > 0.0 && h->nz_relax.ensure((size_t)(4 * P * D))))
+            return HC_ERR_DEVICE;
+    }
     const unsigned short *w = h->wtd_u16.p + (size_t)(c.rows - 1) * N;
     const double dz = h->p.dz, z_obs = (double)h->h_wtd_obs[(size_t)row] * dz;
     const int special = (int)h->use_special();
@@ -4800,9 +4898,9 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
     HIP_TRY(hipGetLastError());
     const unsigned blocks = (unsigned)std::min<int64_t>((N + 3) / 4, (int64_t)h->n_cu * 8);
     if (root) {
-        hipLaunchKernelGGL(enkf_sqrt_update_kernel, dim3(blocks), dim3(256), 0, h->stream, h->psi.p, h->enkf_Y.p,
+        hipLaunchKernelGGL(enkf_sqrt_update_kernel<true>, dim3(blocks), dim3(256), 0, h->stream, h->psi.p, h->enkf_Y.p,
                            h->enkf_rgain.p, h->enkf_dbar.p, h->enkf_s1.p, h->Pdev.p, (long long)N, ll_np, (int)D, dz, W, V,
-                           relax ? 0 : 1, h->enkf_Ypost.p);
+                           relax ? 0 : 1, h->enkf_Ypost.p, nullptr);
         HIP_TRY(hipGetLastError());
     } else {
         hipLaunchKernelGGL(enkf_draw_kernel, members, dim3(256), 0, h->stream, (long long)N, ll_mpp,
@@ -4815,9 +4913,9 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
                                draw_offset, s, h->enkf_eps_w.p);
             HIP_TRY(hipGetLastError());
         }
-        hipLaunchKernelGGL(enkf_update_kernel, dim3(blocks), dim3(256), 0, h->stream, h->psi.p, h->enkf_Y.p,
+        hipLaunchKernelGGL(enkf_update_kernel<true>, dim3(blocks), dim3(256), 0, h->stream, h->psi.p, h->enkf_Y.p,
                            h->enkf_gain.p, h->Pdev.p, (long long)N, ll_mpp, (int)D, dz, z_obs, h->enkf_sigma, s,
-                           h->enkf_eps.p, h->enkf_eps_s.p, h->enkf_eps_w.p, relax ? 0 : 1, h->enkf_Ypost.p);
+                           h->enkf_eps.p, h->enkf_eps_s.p, h->enkf_eps_w.p, relax ? 0 : 1, h->enkf_Ypost.p, nullptr);
         HIP_TRY(hipGetLastError());
     }
     if (relax) {
@@ -4849,10 +4947,67 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
                            h->enkf_sq_b.p, h->enkf_sq_a.p, h->enkf_mean_a.p, shard ? h->enkf_first.p : h->psi.p,
                            h->enkf_gain.p, (long long)P, ll_np, (int)D, W, h->enkf_alpha, h->enkf_relax.p);
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(enkf_relax_kernel, dim3(blocks), dim3(256), 0, h->stream, h->psi.p,
+        hipLaunchKernelGGL(enkf_relax_kernel<true>, dim3(blocks), dim3(256), 0, h->stream, h->psi.p,
                            h->enkf_relax.p + (size_t)(3 * P * D), h->enkf_relax.p + (size_t)(2 * P * D), h->Pdev.p, (long long)N, ll_mpp, (int)D, dz, V,
-                           h->enkf_Ypost.p);
+                           h->enkf_Ypost.p, nullptr);
         HIP_TRY(hipGetLastError());
+    }
+    if (h->enkf_nz) {
+        // the noise field (hc_set_enkf_noise_field): the base vectors z take the state's place in the same passes -- the
+        // sums of (z, Y) and their anomaly products (with the squared anomalies: the prior std), the gain from the same
+        // factor, the update with the same innovations (Y is still the forecast's; Ypost holds the refused flags), the
+        // relaxation with its own alpha, and the spread of what is left for the table
+        double *const z = h->base.p;
+        const dim3 cols_z((unsigned)((D + WAVE - 1) / WAVE * WAVE));
+        auto spread_z = [&](const double *sums) {
+            hipLaunchKernelGGL(enkf_spread_kernel, tiles, cols_z, 0, h->stream, z, sums, ll_mpp, (int)D, ll_tiles,
+                               h->enkf_part_sq.p, z, ll_mpp * (long long)D, ll_np, ll_tile0);
+            return hipGetLastError();
+        };
+        HIP_TRY(partials(false, z, h->enkf_Y.p, W, nullptr, (int)D, cols_prior, part, nullptr));
+        if ((rc = reduce(part, C, h->nz_s1.p))) return rc;
+        HIP_TRY(partials(true, z, h->enkf_Y.p, W, h->nz_s1.p, (int)D, cols_prior, part, h->enkf_part_sq.p));
+        if ((rc = reduce(part, C * W, h->nz_s2.p))) return rc;
+        if ((rc = reduce(h->enkf_part_sq.p, D, h->nz_sq_b.p))) return rc;
+        hipLaunchKernelGGL(enkf_gain_kernel, dim3((unsigned)P), dim3((unsigned)((D + WAVE - 1) / WAVE * WAVE)), 0, h->stream,
+                           h->nz_s1.p, h->nz_s2.p, ll_np, (int)D, s, h->enkf_sigma, h->enkf_loc, z_obs, dz, h->nz_gain.p,
+                           nullptr, nullptr, (long long)n_arow, (long long)slot, root ? h->nz_rgain.p : nullptr,
+                           root ? h->nz_dbar.p : nullptr, nullptr);
+        HIP_TRY(hipGetLastError());
+        if (root)
+            hipLaunchKernelGGL(enkf_sqrt_update_kernel<false>, dim3(blocks), dim3(256), 0, h->stream, z, h->enkf_Y.p,
+                               h->nz_rgain.p, h->nz_dbar.p, h->nz_s1.p, h->Pdev.p, (long long)N, ll_np, (int)D, dz, W, V, 0,
+                               h->enkf_Ypost.p, h->nz_rej.p);
+        else
+            hipLaunchKernelGGL(enkf_update_kernel<false>, dim3(blocks), dim3(256), 0, h->stream, z, h->enkf_Y.p,
+                               h->nz_gain.p, h->Pdev.p, (long long)N, ll_mpp, (int)D, dz, z_obs, h->enkf_sigma, s,
+                               h->enkf_eps.p, h->enkf_eps_s.p, h->enkf_eps_w.p, 0, h->enkf_Ypost.p, h->nz_rej.p);
+        HIP_TRY(hipGetLastError());
+        if (h->enkf_nz_alpha > 0.0) {
+            HIP_TRY(spread_z(nullptr));
+            if ((rc = reduce(h->enkf_part_sq.p, D, h->nz_mean_a.p))) return rc;
+            HIP_TRY(spread_z(h->nz_mean_a.p));
+            if ((rc = reduce(h->enkf_part_sq.p, D, h->nz_sq_a.p))) return rc;
+            hipLaunchKernelGGL(enkf_relax_factor_kernel, dim3((unsigned)((P * D + 255) / 256)), dim3(256), 0, h->stream,
+                               h->nz_sq_b.p, h->nz_sq_a.p, h->nz_mean_a.p, z, h->nz_gain.p, (long long)P, ll_np, (int)D, W,
+                               h->enkf_nz_alpha, h->nz_relax.p);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(enkf_relax_kernel<false>, dim3(blocks), dim3(256), 0, h->stream, z,
+                               h->nz_relax.p + (size_t)(3 * P * D), h->nz_relax.p + (size_t)(2 * P * D), h->Pdev.p,
+                               (long long)N, ll_mpp, (int)D, dz, V, h->enkf_Ypost.p, h->nz_rej.p);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(spread_z(nullptr));
+        if ((rc = reduce(h->enkf_part_sq.p, D, h->nz_mean_a.p))) return rc;
+        HIP_TRY(spread_z(h->nz_mean_a.p));
+        if ((rc = reduce(h->enkf_part_sq.p, D, h->nz_sq_a.p))) return rc;
+        HIP_TRY(partials(false, nullptr, h->nz_rej.p, 1, nullptr, 0, cols_post, part, nullptr));
+        if ((rc = reduce(part, 1, h->nz_rejsum.p))) return rc;
+        hipLaunchKernelGGL(enkf_noise_diag_kernel, dim3((unsigned)((P * D + 255) / 256)), dim3(256), 0, h->stream,
+                           h->nz_s1.p, h->nz_sq_b.p, h->nz_mean_a.p, h->nz_sq_a.p, z, h->nz_rejsum.p, (long long)P, ll_np,
+                           (int)D, W, h->enkf_nzt.buf.p, (long long)n_arow, (long long)slot);
+        HIP_TRY(hipGetLastError());
+        h->nz_done = true;
     }
     if (s.ms > 0) {
         hipLaunchKernelGGL(enkf_theta_kernel, members, dim3(256), 0, h->stream, h->psi.p, h->Pdev.p, h->node_tabs.p, special,
@@ -4924,9 +5079,12 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
     // the particle filter (hc_set_filter): spin-up solves are never filtered
     if (a->spinup && h->filt_host())
         return fail(HC_ERR_ARG, "spin-up solves with the particle filter on in a Philox run: set the filter after the spin-up");
+    if (a->spinup && h->noise_host())
+        return fail(HC_ERR_ARG, "spin-up solves with the EnKF's noise field on in a Philox run: set it after the spin-up");
     const bool filt_on = h->filt_stride > 0 && !a->spinup;
     const bool enkf_on = h->enkf_stride > 0 && !a->spinup;   // (the EnKF: spin-up solves are never analysed either)
     if ((filt_on && (rc = ensure_filter(h))) || (enkf_on && (rc = ensure_enkf(h)))) return rc;
+    if (enkf_on && h->enkf_nz && (rc = ensure_nz(h))) return rc;
     const Assim da = assim(h);                               // whichever is on: its record's and its window's tables
     const bool da_on = filt_on || enkf_on;
     if (da_on && da.sm.n > 0 && (rc = da.ensure_sm(h))) return rc;
@@ -4977,6 +5135,8 @@ int hc_spinup(hc_handle *h, hc_spinup_args *a)
     if (a->max_iterations < 1 || a->max_iterations > 1000000) return fail(HC_ERR_ARG, "max_iterations out of range");
     if (h->filt_host())
         return fail(HC_ERR_ARG, "hc_spinup with the particle filter on in a Philox run: set the filter after the spin-up");
+    if (h->noise_host())
+        return fail(HC_ERR_ARG, "hc_spinup with the EnKF's noise field on in a Philox run: set it after the spin-up");
     HIP_TRY(hipSetDevice(h->device));
     const int64_t N = h->n_members;
     if (h->spin_iters.ensure((size_t)N)) return HC_ERR_DEVICE;
@@ -6249,6 +6409,9 @@ int hc_set_enkf_shard(hc_handle *h, int64_t n_global, int64_t first_global, void
         return HC_OK;
     }
     if (h->enkf_stride <= 0) return fail(HC_ERR_ARG, "hc_set_enkf_shard: the EnKF is off (hc_set_enkf comes first)");
+    if (h->enkf_nz)
+        return fail(HC_ERR_ARG, "hc_set_enkf_shard: the noise field is on (hc_set_enkf_noise_field), and the exchanged "
+                                "partials cover psi only");
     if (h->n_points > 1)
         return fail(HC_ERR_ARG, "hc_set_enkf_shard: the handle holds %d points (a shard is a part of one point's members)",
                     h->n_points);
@@ -6336,6 +6499,117 @@ int hc_get_enkf_relaxation(hc_handle *h, double *sigma_b, double *sigma_a, doubl
     double *out[3] = {sigma_b, sigma_a, factor};
     for (int k = 0; k < 3; k++)
         if (int rc = enkf_hook(h, h->enkf_relax.p + k * n, out[k], 1, n, n, "hc_get_enkf_relaxation")) return rc;
+    return HC_OK;
+}
+
+// ---- the noise field in the analysis (include/hydrocol.h)
+int hc_set_enkf_noise_field(hc_handle *h, int32_t on, double relaxation)
+{
+    if (!h || (on != 0 && on != 1)) return fail(HC_ERR_ARG, "hc_set_enkf_noise_field: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (!on) {
+        nz_off(h);
+        return HC_OK;
+    }
+    if (h->enkf_stride <= 0) return fail(HC_ERR_ARG, "hc_set_enkf_noise_field: the EnKF is off (hc_set_enkf comes first)");
+    if (h->shard_global > 0)
+        return fail(HC_ERR_ARG, "hc_set_enkf_noise_field: the analysis is sharded (hc_set_enkf_shard), and the exchanged "
+                                "partials cover psi only");
+    if (!(std::isfinite(relaxation) && relaxation >= 0.0 && relaxation <= 1.0))
+        return fail(HC_ERR_ARG, "hc_set_enkf_noise_field: relaxation = %g must be finite and in [0, 1]", relaxation);
+    StepArgs A;
+    if (int rc = fill_args(h, A)) return rc;     // column, forcing, members and noise are in place; point keys uploaded
+    const bool was_on = h->enkf_nz;
+    h->enkf_nz = true;
+    h->enkf_nz_alpha = relaxation;
+    int rc = ensure_nz(h);
+    if (rc == HC_OK && h->philox && !was_on) {
+        // as hc_set_filter: the base vectors the kernel's Philox path would build, from here on carried like the caller's
+        const size_t total = (size_t)h->n_members * h->p.dim_d;
+        rc = h->base.ensure(total);
+        if (rc == HC_OK) {
+            const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)h->n_cu * 64);
+            hipLaunchKernelGGL(filter_philox_fill_kernel, dim3(blocks), dim3(256), 0, h->stream, h->base.p, 1ll, nullptr,
+                               h->draw_idx.p, (unsigned long long)h->seed, (long long)h->member_offset,
+                               h->n_points > 1 ? h->point_base.p : nullptr, (long long)A.members_per_point,
+                               (long long)h->n_members, h->p.dim_d, h->nscale.p);
+            const hipError_t e = hipGetLastError();
+            const hipError_t e2 = hipStreamSynchronize(h->stream);
+            if (e != hipSuccess || e2 != hipSuccess)
+                rc = fail(HC_ERR_DEVICE, "hc_set_enkf_noise_field: base vectors: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+        }
+    }
+    if (rc != HC_OK) nz_off(h);                  // refused: off
+    return rc;
+}
+
+int hc_get_enkf_noise_field(hc_handle *h, int32_t *on, double *relaxation)
+{
+    if (!h || !on || !relaxation) return fail(HC_ERR_ARG, "hc_get_enkf_noise_field: bad argument");
+    *on = h->enkf_nz ? 1 : 0;
+    *relaxation = h->enkf_nz ? h->enkf_nz_alpha : 0.0;
+    return HC_OK;
+}
+
+int hc_get_enkf_noise_stats(hc_handle *h, double *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_get_enkf_noise_stats: bad argument");
+    return table_copy(h, h->enkf_nzt, ensure_nz, hipMemcpyDeviceToHost, table, n_entries, "hc_get_enkf_noise_stats");
+}
+
+int hc_set_enkf_noise_stats(hc_handle *h, const double *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_set_enkf_noise_stats: bad argument");
+    return table_copy(h, h->enkf_nzt, ensure_nz, hipMemcpyHostToDevice, const_cast<double *>(table), n_entries,
+                      "hc_set_enkf_noise_stats");
+}
+
+// the last analysis's gain for the vectors, [P][m'][D] as on the device (and the square-root run's reduced gain; its
+// shift [P][D])
+static int nz_hook(hc_handle *h, const DevBuf<double> *src, double *out, bool root, bool shift, const char *who)
+{
+    if (!h || !out) return fail(HC_ERR_ARG, "%s: bad argument", who);
+    if (!h->enkf_nz || !h->nz_done || !h->enkf_done) return fail(HC_ERR_ARG, "%s: no analysis since hc_set_enkf_noise_field", who);
+    if (root && h->enkf_last_method != 1) return fail(HC_ERR_ARG, "%s: no square-root analysis since hc_set_enkf", who);
+    const size_t n = (size_t)h->n_points * h->p.dim_d * (shift ? 1 : (size_t)h->enkf_width);
+    return enkf_hook(h, src->p, out, 1, n, n, who);
+}
+
+int hc_get_enkf_noise_gain(hc_handle *h, double *gain)
+{
+    return nz_hook(h, h ? &h->nz_gain : nullptr, gain, false, false, "hc_get_enkf_noise_gain");
+}
+
+int hc_get_enkf_noise_sqrt_gain(hc_handle *h, double *gain)
+{
+    return nz_hook(h, h ? &h->nz_rgain : nullptr, gain, true, false, "hc_get_enkf_noise_sqrt_gain");
+}
+
+int hc_get_enkf_noise_sqrt_shift(hc_handle *h, double *shift)
+{
+    return nz_hook(h, h ? &h->nz_dbar : nullptr, shift, true, true, "hc_get_enkf_noise_sqrt_shift");
+}
+
+int hc_get_enkf_noise_base(hc_handle *h, double *base, int64_t first, int64_t count)
+{
+    if (!h || !base || first < 0 || count < 0 || first + count > h->n_members || !(h->enkf_nz && h->philox))
+        return fail(HC_ERR_ARG, "hc_get_enkf_noise_base: bad argument (a Philox run with the EnKF's noise field on)");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const int D = h->p.dim_d;
+    HIP_TRY(hipMemcpy(base, h->base.p + (size_t)first * D, (size_t)count * D * 8, hipMemcpyDeviceToHost));
+    return HC_OK;
+}
+
+int hc_set_enkf_noise_base(hc_handle *h, const double *base)
+{
+    if (!h || !base || !(h->enkf_nz && h->philox))
+        return fail(HC_ERR_ARG, "hc_set_enkf_noise_base: bad argument (a Philox run with the EnKF's noise field on)");
+    const size_t n = (size_t)h->n_members * h->p.dim_d;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(h->base.p, base, n * 8, hipMemcpyHostToDevice));
     return HC_OK;
 }
 
@@ -6434,6 +6708,9 @@ int hc_set_noise_scale(hc_handle *h, const double *scale, int64_t first, int64_t
     if (h->filt_host())
         return fail(HC_ERR_ARG, "hc_set_noise_scale: the particle filter is on and the base vectors carry the damping "
                                 "(set the scales before hc_set_filter, or the vectors with hc_set_filter_base)");
+    if (h->noise_host())
+        return fail(HC_ERR_ARG, "hc_set_noise_scale: the EnKF's noise field is on and the base vectors carry the damping "
+                                "(set the scales before hc_set_enkf_noise_field, or the vectors with hc_set_enkf_noise_base)");
     for (int64_t k = 0; k < count; k++)
         if (!(scale[k] > 0.0) || !(scale[k] <= 1.0))
             return fail(HC_ERR_ARG, "noise scale %lld = %g is not a product of 0.8 factors in (0, 1]", (long long)(first + k), scale[k]);

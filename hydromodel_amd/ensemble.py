@@ -9,6 +9,7 @@ all-reduce of the per-row water-table moments (see :func:`allreduce_moments`).
 import numpy as np
 
 from .digest import inverse_retention
+from .stepper import enkf_noise_summary, noise_field_settings
 from .stepper import (ENKF_METHODS, ENKF_WIDTH, SM_WIDTH, WINDOW_WIDTH, EnsembleStepper, enkf_sm_summary, enkf_summary,
                       enkf_window_settings, enkf_window_summary, filter_sm_summary, filter_summary,
                       filter_window_settings, filter_window_summary,
@@ -133,6 +134,10 @@ class _Run:
     enkf_method: "stochastic" (perturbed observations, the default) or "sqrt" (the deterministic square-root analysis);
     enkf_relaxation: the relaxation to prior spread alpha in [0, 1] (default 0 = none) of either
     (include/hydrocol.h hc_set_enkf_method); both need the EnKF.
+    enkf_noise_field: True or {"relaxation": a}: every analysis also updates the members' base noise vectors -- their
+    conductivity fields -- with the same observations, draws and factor (include/hydrocol.h hc_set_enkf_noise_field),
+    relaxed to prior spread with ``a`` (default: enkf_relaxation); the ``noise_*`` keys of :meth:`enkf_summary`.
+    Parameters regain no spread from the dynamics: without a relaxation a long run collapses the field.
     enkf_window_offsets: rows before each analysis row (integers in [1, enkf_stride), e.g. (12, 24, 36)) on which the
     well's record joins that analysis too -- the asynchronous EnKF (include/hydrocol.h hc_set_enkf_window);
     :meth:`enkf_window_table`, the ``window_*`` keys of :meth:`enkf_summary`.
@@ -144,7 +149,7 @@ class _Run:
                       enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None,
                       enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=(),
                       filter_soil_moisture=None, theta_hist_bins=0, storage_layers_cm=None, storage_bins=0,
-                      filter_ess_floor=0.0, filter_window_offsets=()):
+                      filter_ess_floor=0.0, filter_window_offsets=(), enkf_noise_field=None):
         self.profile_stride = int(profile_stride)
         self.storage_layers_cm = None if storage_layers_cm is None or len(storage_layers_cm) == 0 else \
             np.asarray(storage_layers_cm, dtype=np.float64).reshape(-1, 2)
@@ -207,6 +212,21 @@ class _Run:
         self.enkf_window_offsets = enkf_window_settings(enkf_window_offsets, self.enkf_stride, self.stepper.enkf_sm_n)
         if self.enkf_window_offsets:
             self.stepper.set_enkf_window(self.enkf_window_offsets)
+        # the noise field (after any spin-up: a Philox run then takes the caller-noise path); None: off
+        self.enkf_noise_relaxation = noise_field_settings(enkf_noise_field, self.enkf_relaxation)
+        if self.enkf_noise_relaxation is not None:
+            if not self.enkf_stride:
+                raise ValueError("enkf_noise_field needs the EnKF (enkf_stride > 0)")
+            self.stepper.set_enkf_noise_field(True, self.enkf_noise_relaxation)
+
+    def enkf_noise_table(self):
+        """[n_arow][4 D + 1] float64 (include/hydrocol.h hc_set_enkf_noise_field); a sweep: [P][n_arow][4 D + 1]."""
+        return self.stepper.enkf_noise_table().reshape(self._lead + (-1, 4 * self.cols.dim_d + 1))
+
+    def enkf_noise_summary(self, table=None):
+        """stepper.enkf_noise_summary of the noise field's table (``table``: e.g. the one assembled over ranks)."""
+        t = self.enkf_noise_table() if table is None else table
+        return enkf_noise_summary(t, self.enkf_stride, self.enkf_noise_relaxation, self.cols.dim_d)
 
     def advance(self, n_rows, **kw):
         """Solve the next ``n_rows`` forcing rows for every member."""
@@ -365,7 +385,7 @@ class _Run:
         """[n_arow][8] float64 (include/hydrocol.h hc_set_enkf; depths from the top node); a sweep: [P][n_arow][8]."""
         return self.stepper.enkf_table().reshape(self._lead + (-1, ENKF_WIDTH))
 
-    def enkf_summary(self, table=None, sm_table=None, window_table=None):
+    def enkf_summary(self, table=None, sm_table=None, window_table=None, noise_table=None):
         """The EnKF's record (stepper.enkf_summary, means at the well's depths): ``rows``, ``count``, ``prior_mean_cm``,
         ``prior_std_cm``, ``innovation_cm``, ``loglik_rows``, ``post_mean_cm``, ``post_std_cm``, ``rejected`` over the
         analysed rows and ``loglik``, the log marginal likelihood of the well record (log cm^-1), with a leading [P] for a
@@ -378,6 +398,8 @@ class _Run:
             out.update(("sm_" + k, v) for k, v in self.enkf_sm_summary(sm_table).items())
         if self.enkf_window_offsets:
             out.update(("window_" + k, v) for k, v in self.enkf_window_summary(window_table).items())
+        if self.enkf_noise_relaxation is not None:      # the noise_* keys (include/hydrocol.h hc_set_enkf_noise_field)
+            out.update((k, v) for k, v in self.enkf_noise_summary(noise_table).items() if k.startswith("noise_"))
         return out
 
     def enkf_window_table(self):
@@ -431,7 +453,10 @@ class EnsembleSimulation(_Run):
                  enkf_seed=None, enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0,
                  enkf_window_offsets=(), enkf_shard=None, filter_shard=None, filter_soil_moisture=None,
                  theta_hist_bins=0, storage_layers_cm=None, storage_bins=0, period_ends=None, period_thresholds_cm=(),
-                 period_bins=0, period_flux_max_cm=(16.0, 4.0), filter_ess_floor=0.0, filter_window_offsets=()):
+                 period_bins=0, period_flux_max_cm=(16.0, 4.0), filter_ess_floor=0.0, filter_window_offsets=(),
+                 enkf_noise_field=None):
+        if enkf_shard is not None and noise_field_settings(enkf_noise_field, 0.0) is not None:
+            raise ValueError("enkf_shard and enkf_noise_field exclude each other: the exchanged partials cover psi only")
         if filter_shard is not None and filter_window_offsets is not None and len(filter_window_offsets):
             raise ValueError("filter_shard and filter_window_offsets exclude each other: the sharded filter gathers the "
                              "water-table indices of the assimilation row only")
@@ -450,7 +475,7 @@ class EnsembleSimulation(_Run):
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
                            enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins, storage_layers_cm,
-                           storage_bins, filter_ess_floor, filter_window_offsets)
+                           storage_bins, filter_ess_floor, filter_window_offsets, enkf_noise_field)
         self._start_periods(period_ends, period_thresholds_cm, period_bins, period_flux_max_cm)
         self.enkf_shard = None
         if enkf_shard is not None:
@@ -617,6 +642,10 @@ class EnsembleSimulation(_Run):
                 arrays["enkf_window_offsets"] = np.asarray(self.enkf_window_offsets, dtype=np.int64)
                 arrays["enkf_window_table"] = self.stepper.enkf_window_table()
                 arrays["enkf_window_y"], arrays["enkf_window_rows"] = y, rows
+            if self.enkf_noise_relaxation is not None:    # the analysed vectors carry the damping too (as a filtered run's)
+                arrays["enkf_noise_relaxation"] = np.array(self.enkf_noise_relaxation, dtype=np.float64)
+                arrays["enkf_noise_table"] = self.stepper.enkf_noise_table()
+                arrays["enkf_noise_base"] = self.stepper.enkf_noise_base()
         path = Path(path)
         if hdf5io.available() and path.suffix != ".npz":
             hdf5io.write(path, arrays)
@@ -668,6 +697,9 @@ class EnsembleSimulation(_Run):
                        enkf_localisation_cm=float(data["enkf_localisation_cm"]), enkf_seed=int(data["enkf_seed"]))
         if enkf and "enkf_method" in data:
             fkw.update(enkf_method=ENKF_METHODS[int(data["enkf_method"])], enkf_relaxation=float(data["enkf_relaxation"]))
+        has_nz = bool(enkf) and "enkf_noise_relaxation" in data
+        if has_nz:
+            fkw.update(enkf_noise_field={"relaxation": float(data["enkf_noise_relaxation"])})
         def record(on, prefix, given):
             """Whether the checkpoint holds the sensor table of ``prefix``'s record; the record given must match it."""
             has = bool(on) and prefix + "_sm_table" in data
@@ -705,6 +737,9 @@ class EnsembleSimulation(_Run):
                 sim.stepper.set_filter_window_table(np.asarray(data["filter_window_table"], dtype=np.float64))
                 sim.stepper.set_filter_window_capture(np.asarray(data["filter_window_index"], dtype=np.int32).reshape(-1, n),
                                                       np.asarray(data["filter_window_rows"], dtype=np.int64))
+        elif has_nz:
+            sim.stepper.set_enkf_noise_table(np.asarray(data["enkf_noise_table"], dtype=np.float64))
+            sim.stepper.set_enkf_noise_base(np.asarray(data["enkf_noise_base"], dtype=np.float64).reshape(n, D))
         else:
             sim.stepper.set_noise_scale(np.asarray(data["noise_scale"], dtype=float).reshape(n))
         if enkf:
@@ -828,7 +863,7 @@ class SweepSimulation(_Run):
                  enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=(),
                  filter_soil_moisture=None, theta_hist_bins=0, storage_layers_cm=None, storage_bins=0, period_ends=None,
                  period_thresholds_cm=(), period_bins=0, period_flux_max_cm=(16.0, 4.0), filter_ess_floor=0.0,
-                 filter_window_offsets=()):
+                 filter_window_offsets=(), enkf_noise_field=None):
         self.points = list(cols_list)
         self.P, self.n = len(self.points), int(n_members)
         self._lead = (self.P,)
@@ -858,7 +893,7 @@ class SweepSimulation(_Run):
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
                            enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins, storage_layers_cm,
-                           storage_bins, filter_ess_floor, filter_window_offsets)
+                           storage_bins, filter_ess_floor, filter_window_offsets, enkf_noise_field)
         self._start_periods(period_ends, period_thresholds_cm, period_bins, period_flux_max_cm)
         self.next_row, self.kernel_ms, self.launches = 1, 0.0, 0
 

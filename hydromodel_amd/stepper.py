@@ -88,6 +88,8 @@ class EnsembleStepper:
         self.enkf_sm_nodes = None
         self.enkf_method, self.enkf_relaxation = "stochastic", 0.0
         self.enkf_window_offsets = ()
+        self.enkf_noise_field, self.enkf_noise_relaxation = False, 0.0
+        self.philox = False
         self.device = int(device)
         self.enkf_shard, self._shard_keep, self._shard_error = None, None, None
         self.filter_shard, self._filter_shard_keep = None, None
@@ -129,6 +131,7 @@ class EnsembleStepper:
         if base.shape != (self.N, self.D):
             raise ValueError(f"base noise must be [{self.N}, {self.D}]")
         L.check(self.lib.hc_set_noise_host(self.h, L.dptr(base)))
+        self.philox = False
         self._filter_off()
 
     def get_noise_base(self, first=0, count=None):
@@ -139,6 +142,7 @@ class EnsembleStepper:
 
     def set_noise_philox(self, seed, member_offset=0):
         L.check(self.lib.hc_set_noise_philox(self.h, int(seed), int(member_offset)))
+        self.philox = True
         self._filter_off()
 
     def philox_normals(self, member, draw):
@@ -599,6 +603,7 @@ class EnsembleStepper:
         self.enkf_method, self.enkf_relaxation = "stochastic", 0.0
         self.enkf_window_offsets = ()
         self.enkf_shard = None
+        self.enkf_noise_field, self.enkf_noise_relaxation = False, 0.0
         self.filter_shard, self._filter_shard_keep = None, None
 
     def filter_table(self):
@@ -882,6 +887,7 @@ class EnsembleStepper:
         self.enkf_method, self.enkf_relaxation = "stochastic", 0.0       # ... and resets the analysis scheme
         self.enkf_window_offsets = ()                         # ... and turns the window off
         self.enkf_shard = None                                # ... and the sharding
+        self.enkf_noise_field, self.enkf_noise_relaxation = False, 0.0   # ... and the noise field
         L.check(self.lib.hc_set_enkf(self.h, stride, sigma, loc, int(seed) & 0xFFFFFFFFFFFFFFFF))
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = stride, sigma, loc, int(seed)
 
@@ -958,6 +964,74 @@ class EnsembleStepper:
         out = np.zeros((3, self.P, self.D))
         L.check(self.lib.hc_get_enkf_relaxation(self.h, L.dptr(out[0]), L.dptr(out[1]), L.dptr(out[2])))
         return out[0], out[1], out[2]
+
+    # -- the noise field in the EnKF analysis (include/hydrocol.h hc_set_enkf_noise_field) ------------------------------
+    def set_enkf_noise_field(self, on=True, relaxation=None):
+        """Update every member's base noise vector -- its conductivity field -- together with its psi on every analysis
+        row, from the same observations, draws and factor; ``relaxation``: the RTPS factor of the vectors' anomalies in
+        [0, 1] (default: the one of :meth:`set_enkf_method`).  The EnKF must be on and not sharded.  In a Philox run the
+        handle then feeds the step kernel its own normals as caller noise: set it after the spin-up, and
+        :meth:`set_noise_scale` is refused while it is on."""
+        on = bool(on)
+        alpha = noise_field_relaxation(self.enkf_relaxation if relaxation is None else relaxation) if on else 0.0
+        if on and not self.enkf_stride:
+            raise ValueError("the noise field needs the EnKF on (set_enkf first)")
+        if on and self.enkf_shard is not None:
+            raise ValueError("the noise field with a sharded analysis: the exchanged partials cover psi only")
+        L.check(self.lib.hc_set_enkf_noise_field(self.h, int(on), alpha))
+        self.enkf_noise_field, self.enkf_noise_relaxation = on, alpha
+
+    def get_enkf_noise_field(self):
+        """(on, relaxation) as the library holds them."""
+        m, a = np.zeros(1, dtype=np.int32), np.zeros(1)
+        L.check(self.lib.hc_get_enkf_noise_field(self.h, L.iptr(m), L.dptr(a)))
+        return bool(m[0]), float(a[0])
+
+    def enkf_noise_table(self):
+        """[P][n_arow][4 D + 1] float64 per analysis slot: the prior mean and std of every node's z, the mean and std
+        after the relaxation, then the members whose updated vector was refused; NaN where nothing was analysed
+        (:func:`split_enkf_noise_table`)."""
+        t = np.zeros((self.P, stride_rows(self.T, self.enkf_stride), 4 * self.D + 1))
+        L.check(self.lib.hc_get_enkf_noise_stats(self.h, L.dptr(t), t.size))
+        return t
+
+    def set_enkf_noise_table(self, table):
+        t = L.as_f64(table).reshape(-1)
+        L.check(self.lib.hc_set_enkf_noise_stats(self.h, L.dptr(t), t.size))
+
+    def enkf_noise_gain(self):
+        """[P][m'][D] the vectors' gain of the last analysis (test hook)."""
+        out = np.zeros((self.P, self.enkf_width(), self.D))
+        L.check(self.lib.hc_get_enkf_noise_gain(self.h, L.dptr(out)))
+        return out
+
+    def enkf_noise_sqrt_gain(self):
+        """[P][m'][D] the vectors' reduced gain of the last analysis, a square-root one (test hook)."""
+        out = np.zeros((self.P, self.enkf_width(), self.D))
+        L.check(self.lib.hc_get_enkf_noise_sqrt_gain(self.h, L.dptr(out)))
+        return out
+
+    def enkf_noise_sqrt_shift(self):
+        """[P][D] the shift of the vectors' mean in the last analysis, a square-root one (test hook)."""
+        out = np.zeros((self.P, self.D))
+        L.check(self.lib.hc_get_enkf_noise_sqrt_shift(self.h, L.dptr(out)))
+        return out
+
+    def enkf_noise_base(self):
+        """[N][D] the members' base noise vectors: a Philox run's with the noise field on, else the caller's
+        (:meth:`get_noise_base`)."""
+        if not self.philox:
+            return self.get_noise_base()
+        out = np.zeros((self.N, self.D))
+        L.check(self.lib.hc_get_enkf_noise_base(self.h, L.dptr(out), 0, self.N))
+        return out
+
+    def set_enkf_noise_base(self, base):
+        """Replace a Philox run's base noise vectors (a checkpoint taken with the noise field on)."""
+        base = L.as_f64(base)
+        if base.shape != (self.N, self.D):
+            raise ValueError(f"base must be [{self.N}][{self.D}], got {base.shape}")
+        L.check(self.lib.hc_set_enkf_noise_base(self.h, L.dptr(base)))
 
     # -- soil-moisture sensors in the EnKF analysis (include/hydrocol.h hc_set_enkf_soil_moisture) ----------------------
     def set_enkf_soil_moisture(self, nodes, values=None, sigma=None):
@@ -1980,6 +2054,136 @@ def enkf_summary(table, stride, sigma_cm, z0_cm=0.0):
             "loglik_rows": inc, "post_mean_cm": sel[..., 5] + z0_cm, "post_std_cm": sel[..., 6],
             "rejected": np.nan_to_num(sel[..., 7]).astype(np.int64), "loglik": loglik if loglik.ndim else float(loglik),
             "stride": int(stride), "sigma_cm": float(sigma_cm)}
+
+
+# ---- the noise field in the EnKF (include/hydrocol.h hc_set_enkf_noise_field) ------------------------------------------
+def noise_field_relaxation(value):
+    """The noise field's relaxation: a finite number in [0, 1], not a bool."""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise ValueError(f"Noise_Field relaxation = {value!r} must be a number in [0, 1]")
+    a = float(value)
+    if not (np.isfinite(a) and 0.0 <= a <= 1.0):
+        raise ValueError(f"Noise_Field relaxation = {value!r} must be a finite number in [0, 1]")
+    return a
+
+
+def noise_field_settings(value, block_relaxation=0.0):
+    """The ``Noise_Field`` key of an EnKF block / the ``enkf_noise_field=`` argument: None or False -> None (off); True
+    -> the block's relaxation; {"Relaxation": a} (or "relaxation") -> a.  Anything else is a ValueError."""
+    if value is None or value is False:
+        return None
+    if value is True:
+        return noise_field_relaxation(block_relaxation)
+    if isinstance(value, dict) and len(value) == 1 and next(iter(value)) in ("Relaxation", "relaxation"):
+        return noise_field_relaxation(next(iter(value.values())))
+    raise ValueError(f"Noise_Field = {value!r} must be true, false or {{\"Relaxation\": a}}")
+
+
+def split_enkf_noise_table(table, D):
+    """[..., n_arow, 4 D + 1] -> (stats [..., n_arow, 4, D]: prior mean, prior std, posterior mean, posterior std of
+    every node's z; rejected [..., n_arow])."""
+    t = np.asarray(table, dtype=np.float64)
+    return t[..., :4 * D].reshape(t.shape[:-1] + (4, D)), t[..., 4 * D]
+
+
+def _enkf_gains_of(x, Y, obs, sigma, zeta, dz, loc, want_sqrt):
+    """One point: K [D][m'] = (rho o C_xY)(rho o C_YY + R)^-1 of the columns x [N][D] against Y [N][m'], and for the
+    square-root scheme the reduced gain and the mean's shift."""
+    N, D = x.shape
+    W = Y.shape[1]
+    yb = Y.mean(axis=0)
+    A = Y - yb
+    n1 = N - 1
+    cyy = A.T @ A / n1 if N > 1 else np.zeros((W, W))
+    cxy = (x - x.mean(axis=0)).T @ A / n1 if N > 1 else np.zeros((D, W))
+    zt = np.concatenate([[yb[0]], np.asarray(zeta, dtype=np.float64).reshape(-1)])
+    depth = np.arange(D) * float(dz)
+    if loc > 0:
+        rho_yy = gaspari_cohn(np.abs(zt[:, None] - zt[None, :]) / loc)
+        rho_xy = gaspari_cohn(np.abs(depth[:, None] - zt[None, :]) / loc)
+    else:
+        rho_yy, rho_xy = np.ones((W, W)), np.ones((D, W))
+    R = np.asarray(sigma, dtype=np.float64) ** 2
+    Lc = np.linalg.cholesky(rho_yy * cyy + np.diag(R))
+    u = np.linalg.solve(Lc, (rho_xy * cxy).T)
+    K = np.linalg.solve(Lc.T, u).T
+    if not want_sqrt:
+        return K, None, None, yb
+    Kr = np.linalg.solve((Lc + np.diag(np.sqrt(R))).T, u).T
+    return K, Kr, K @ (np.asarray(obs, dtype=np.float64) - yb), yb
+
+
+def enkf_noise_analysis_of(psi_f, z_f, Y, obs, sigma, eps=None, zeta=(), dz=1.0, localisation_cm=0.0,
+                           method="stochastic", relaxation=0.0):
+    """The noise field's analysis for ONE point in float64 NumPy (include/hydrocol.h hc_set_enkf_noise_field): from the
+    forecast states ``psi_f`` [N][D], base vectors ``z_f`` [N][D], observations of the members ``Y`` [N][m'] (the well's
+    y first), the observed values ``obs`` and their errors ``sigma`` [m'], and for the stochastic scheme the draws ``eps``
+    [N][m']; ``zeta`` [m' - 1]: the taper centres of the columns beyond the well's, cm from the top node.
+
+    K^z = (rho o C_zY)(rho o C_YY + R)^-1; z + (obs + sigma eps - Y) K^z^T, or with "sqrt" z + shift + (Ybar - Y) Kr^T.
+    A member whose psi analysis (the same formula on psi_f) has a non-finite entry keeps its z; one whose updated z has
+    a non-finite entry keeps its old z and is ``rejected``.  Then the anomalies are relaxed: f_d = 1 + a (sigma_b -
+    sigma_a) / sigma_a (1 where sigma_a is 0 or not finite), over every member (those that kept their z included), and
+    applied to the members that took their update.
+
+    Returns ``K`` [m'][D] (and ``Kr``, ``shift`` with "sqrt"), ``z`` [N][D] the analysed vectors, ``rejected`` and
+    ``psi_rejected`` [N] bool, ``sigma_b``, ``sigma_a``, ``factor`` [D], and ``stats`` [4][D]: prior mean and std,
+    posterior (relaxed) mean and std."""
+    if method not in ENKF_METHODS:
+        raise ValueError(f"EnKF method = {method!r} must be one of {list(ENKF_METHODS)}")
+    psi_f, z_f, Y = (np.asarray(a, dtype=np.float64) for a in (psi_f, z_f, Y))
+    obs, sigma = np.asarray(obs, dtype=np.float64).reshape(-1), np.asarray(sigma, dtype=np.float64).reshape(-1)
+    alpha = noise_field_relaxation(relaxation)
+    N, D = z_f.shape
+    root = method == "sqrt"
+    with np.errstate(all="ignore"):
+        def increments(x):
+            K, Kr, shift, yb = _enkf_gains_of(x, Y, obs, sigma, zeta, dz, float(localisation_cm), root)
+            if root:
+                return K, Kr, shift, shift[None, :] + (yb[None, :] - Y) @ Kr.T
+            return K, None, None, ((obs[None, :] + sigma[None, :] * np.asarray(eps, dtype=np.float64)) - Y) @ K.T
+        psi_rej = ~np.isfinite(psi_f + increments(psi_f)[3]).all(axis=1)
+        K, Kr, shift, inc = increments(z_f)
+        cand = z_f + inc
+        rej = ~np.isfinite(cand).all(axis=1) & ~psi_rej
+        z = np.where((rej | psi_rej)[:, None], z_f, cand)
+        sb = z_f.std(axis=0, ddof=1) if N > 1 else np.zeros(D)
+        sa = z.std(axis=0, ddof=1) if N > 1 else np.zeros(D)
+        f = np.ones(D)
+        if alpha > 0.0:
+            good = (sa > 0) & np.isfinite(sa) & np.isfinite(K[0, 0])
+            f = np.where(good, 1.0 + alpha * (sb - sa) / np.where(good, sa, 1.0), 1.0)
+            mean = z.mean(axis=0)
+            relaxed = np.where(f[None, :] == 1.0, z, mean[None, :] + f[None, :] * (z - mean[None, :]))
+            keep = np.isfinite(relaxed).all(axis=1) & ~psi_rej & ~rej
+            z = np.where(keep[:, None], relaxed, z)
+        stats = np.stack([z_f.mean(axis=0), sb, z.mean(axis=0), z.std(axis=0, ddof=1) if N > 1 else np.zeros(D)])
+    out = {"K": K.T.copy(), "z": z, "rejected": rej, "psi_rejected": psi_rej, "sigma_b": sb, "sigma_a": sa, "factor": f,
+           "stats": stats}
+    if root:
+        out["Kr"], out["shift"] = Kr.T.copy(), shift
+    return out
+
+
+def enkf_noise_summary(table, stride, relaxation, D=None):
+    """The noise field's record from its [..., n_arow, 4 D + 1] table, over the slots any point analysed: ``rows`` [R],
+    ``noise_prior_mean``, ``noise_prior_std``, ``noise_post_mean``, ``noise_post_std`` [..., R, D], ``noise_rejected``
+    [..., R], ``noise_spread_ratio`` = the mean over nodes and rows of sigma_post / sigma_prior (nodes with sigma_prior
+    = 0 left out; NaN with no row), ``noise_relaxation``."""
+    t = np.asarray(table, dtype=np.float64)
+    D = (t.shape[-1] - 1) // 4 if D is None else int(D)
+    stats, rej = split_enkf_noise_table(t, D)
+    used = np.isfinite(rej).reshape(-1, t.shape[-2]).any(axis=0) if t.size else np.zeros(t.shape[-2], bool)
+    slots = np.flatnonzero(used)
+    sel = stats[..., slots, :, :]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = sel[..., 3, :] / sel[..., 1, :]
+    ok = np.isfinite(ratio) & (sel[..., 1, :] > 0)
+    return {"rows": slots.astype(np.int64) * int(stride), "noise_prior_mean": sel[..., 0, :],
+            "noise_prior_std": sel[..., 1, :], "noise_post_mean": sel[..., 2, :], "noise_post_std": sel[..., 3, :],
+            "noise_rejected": np.nan_to_num(rej[..., slots]).astype(np.int64),
+            "noise_spread_ratio": float(ratio[ok].mean()) if ok.any() else float("nan"),
+            "noise_relaxation": float(relaxation)}
 
 
 # ---- soil-moisture sensors in the EnKF (include/hydrocol.h hc_set_enkf_soil_moisture) ----------------------------------

@@ -66,6 +66,12 @@
  *   hc_set/get_enkf_method, hc_get_enkf_sqrt_gain/shift, hc_get_enkf_relaxation
  *                      <- (new) the EnKF's analysis scheme (perturbed observations or square root) and its relaxation to
  *                         prior spread
+ *   hc_set/get_enkf_noise_field, hc_get/set_enkf_noise_stats, hc_get_enkf_noise_gain, hc_get_enkf_noise_sqrt_gain/shift,
+ *   hc_get/set_enkf_noise_base
+ *                      <- (new) args_i["n_rnd"], one base vector of D standard normals per column
+ *                         (src/simulation.py:561,592; replaced for one row only on refresh rows, :599-601), is what
+ *                         vrettas_fung.py:154-190 turns into K_bkg: a member's conductivity field.  The EnKF's analysis
+ *                         updates it together with the member's psi (state augmentation)
  *   hc_set_enkf_window, hc_get/set_enkf_window_stats, hc_get/set_enkf_window_capture, hc_get_enkf_width,
  *   hc_get_enkf_window_width/y/eps/gain
  *                      <- (new) the well's record at rows inside the analysis window joins the analysis (asynchronous EnKF)
@@ -816,6 +822,48 @@ int hc_get_enkf_method(hc_handle *h, int32_t *method, double *relaxation);
 int hc_get_enkf_sqrt_gain(hc_handle *h, double *gain);
 int hc_get_enkf_sqrt_shift(hc_handle *h, double *shift);
 int hc_get_enkf_relaxation(hc_handle *h, double *sigma_b, double *sigma_a, double *factor);
+
+/* The noise field in the analysis (joint state-parameter estimation by state augmentation; Chen & Zhang 2006, Hendricks
+ * Franssen & Kinzelbach 2008).  A member's base noise vector z [D] -- args_i["n_rnd"] of src/simulation.py:561,592, which
+ * vrettas_fung.py:154,172,190 turns into K_bkg on every row but the refresh rows (src/simulation.py:599-601 replace it for
+ * that one row) -- is the member's conductivity field.  With on = 1 every analysis updates it with the member's psi, from
+ * the same observations, draws and m' x m' factor:
+ *     zbar_d, c_d,i = sum_k (z_dk - zbar_d)(Y_ki - Ybar_i)          (the tile rule of hc_set_enkf over (z, Y))
+ *     K^z_d = (rho_d o c_d / (N_p - 1)) S^-1                         (rho_d: node d at depth d dz, localisation_cm of
+ *                                                                     hc_set_enkf; S = rho o C_YY + R and its factor are
+ *                                                                     the state's to the bit)
+ *     z_dk <- z_dk + sum_i K^z_d,i delta_ki, i in order              (delta: the member's innovations of its psi update;
+ *                                                                     square root: the reduced gain, Ybar_i - Y_ki, and
+ *                                                                     the shift sum_i K^z_d,i (o_i - Ybar_i))
+ *   after the state's update (Y is still the forecast's).  A member whose psi analysis was rejected keeps its z to the
+ *   bit and is not counted here; a member whose updated z would hold a non-finite entry keeps its old z, is counted in
+ *   noise_rejected, and its psi update stands.  Then the anomalies of z are relaxed to prior spread with `relaxation` by
+ *   the rule of hc_set_enkf_method (its sigma_a = 0 rule included; the members of either kind above are left alone); parameters regain no spread from the dynamics, so
+ *   relaxation = 0 lets the field collapse over a long run.  All D entries are updated (a node that belongs to no layer
+ *   never reads its z); the refresh rows' vectors are one-row draws and are not estimated.  Nothing is drawn, no step
+ *   kernel is involved, and with on = 0 nothing is launched or allocated.
+ *   Table (hc_get/set_enkf_noise_stats), float64 [P][n_arow][4 D + 1], NaN until the row is analysed: per node the prior
+ *   mean and std of z_d, the mean and std after the relaxation ([4][D]), then noise_rejected.
+ *   Noise source: with host noise the vectors are the caller's (hc_set_noise_host) updated in place, and
+ *   hc_get_noise_base returns the analysed ones.  In a Philox run the step kernel keys its base vector by slot, so -- as
+ *   with the particle filter -- the handle fills base and refresh vectors from philox_normal itself and runs the
+ *   caller-noise path: hc_spinup and spin-up solves of hc_step_rows, and hc_set_noise_scale, are refused while it is on
+ *   (set it after the spin-up; the base vectors carry the x0.8 damping), and hc_get/set_enkf_noise_base read and write
+ *   the vectors [N][D] (a checkpoint; HC_ERR_ARG outside a Philox run with the field on).
+ * hc_set_enkf_noise_field: needs the EnKF on; HC_ERR_ARG for on outside {0, 1}, a relaxation outside [0, 1] or not finite,
+ *   or a sharded analysis (hc_set_enkf_shard refuses it in turn: the exchanged partials cover psi only).  Turned off by
+ *   whatever turns the EnKF off or re-creates it.  hc_get_enkf_noise_field: (0, 0) while it is off.
+ * Test hooks of the last analysis, [P][m'][D]: hc_get_enkf_noise_gain (K^z), hc_get_enkf_noise_sqrt_gain (the reduced
+ *   gain) and hc_get_enkf_noise_sqrt_shift [P][D], the latter two HC_ERR_ARG unless it was a square-root analysis. */
+int hc_set_enkf_noise_field(hc_handle *h, int32_t on, double relaxation);
+int hc_get_enkf_noise_field(hc_handle *h, int32_t *on, double *relaxation);
+int hc_get_enkf_noise_stats(hc_handle *h, double *table, int64_t n_entries);
+int hc_set_enkf_noise_stats(hc_handle *h, const double *table, int64_t n_entries);
+int hc_get_enkf_noise_gain(hc_handle *h, double *gain);
+int hc_get_enkf_noise_sqrt_gain(hc_handle *h, double *gain);
+int hc_get_enkf_noise_sqrt_shift(hc_handle *h, double *shift);
+int hc_get_enkf_noise_base(hc_handle *h, double *base, int64_t first_member, int64_t count);
+int hc_set_enkf_noise_base(hc_handle *h, const double *base);
 
 /* The well's record inside the window (asynchronous EnKF, Sakov, Evensen & Bertino 2010): at chosen rows before an
  * analysis row each member's y is recorded when the row is solved, and at the analysis those values join the batch as
