@@ -1,7 +1,9 @@
 """The ensemble Kalman filter on the GPU (include/hydrocol.h hc_set_enkf): y, eps, the gain and the analysis states against
 a float64 NumPy restatement from the forecast states; the neutral EnKF against a run without it; invariance under launch
-length, point order and the dealing of a sweep's points to handles; one member; the TWO-layout and split-column depths; a
-twin experiment against the open run and the particle filter; resume; the CLI's "Ensemble": {"EnKF": ...} block."""
+length, point order and the dealing of a sweep's points to handles; one member; the TWO-layout and split-column depths
+(D = 401, 581) for finiteness only -- the analysis is compared with NumPy at every slot count, D = 41 ... 640, in
+test_gpu_enkf_depths.py; a twin experiment against the open run and the particle filter; resume; the CLI's "Ensemble":
+{"EnKF": ...} block."""
 import copy
 import json
 
