@@ -136,6 +136,25 @@ struct Window : WindowBase {
     }
 };
 
+// What the EnKF keeps, per point, of a vector x [N][D] it analyses (the state psi, the members' noise vectors z), of the
+// last analysis (test hooks) and sized by the record's largest m', Wx: the raw sums of both prior passes over (x, Y),
+// s1 [P][D + m'] and s2 [P][s2_cols]; the gain [P][m'][D]; for the square-root scheme the reduced gain [P][m'][D] and
+// the mean's increment [P][D]; where the spread is wanted the sums of the squared anomalies before / after the update
+// and of the analysed columns, [P][D] each; where x is relaxed (sigma_b, sigma_a, f, the analysis's mean) [4][P][D]
+struct EnkfVec {
+    DevBuf<double> s1, s2, gain, rgain, dbar, sq_b, sq_a, mean_a, relax;
+    int ensure(int64_t P, int64_t D, int64_t Wx, int64_t s2_cols, bool root, bool spread, bool relaxed)
+    {
+        const size_t PD = (size_t)(P * D), PWD = (size_t)(P * Wx * D);
+        if (s1.ensure((size_t)(P * (D + Wx))) || s2.ensure((size_t)(P * s2_cols)) || gain.ensure(PWD) ||
+            (root && (rgain.ensure(PWD) || dbar.ensure(PD))) || (relaxed && relax.ensure(4 * PD)) ||
+            (spread && (sq_b.ensure(PD) || sq_a.ensure(PD) || mean_a.ensure(PD))))
+            return HC_ERR_DEVICE;
+        return HC_OK;
+    }
+    void release() { for (auto *b : {&s1, &s2, &gain, &rgain, &dbar, &sq_b, &sq_a, &mean_a, &relax}) b->release(); }
+};
+
 }  // namespace
 
 struct hc_handle {
@@ -284,25 +303,21 @@ struct hc_handle {
     std::vector<int64_t> fs_send_words, fs_recv_words;
     // ensemble Kalman filter (hc_set_enkf): diagnostics float64 [P][n_arow][8] keyed by (points, rows, stride); per
     // member the observations Y [N][m'] (the well's y first), the well's eps, the sensors' eps [N][n_s] and the
-    // posterior (y, theta..., rejected); per point the raw sums of both passes and the gain [P][m'][D] (the last
-    // analysis: test hooks); the tile partials
+    // posterior (y, theta..., rejected); what the analysis keeps of psi (EnkfVec, the spread only when psi is relaxed; the
+    // posterior's passes over Ypost reuse s1 and s2, so s2 holds the wider of the two); every pass's tile partials
     int enkf_stride = 0;         // 0: off
     double enkf_sigma = 0.0, enkf_loc = 0.0;
     uint64_t enkf_seed = 0;
     bool enkf_done = false;      // an analysis has run since the EnKF was set
     int enkf_width = 0;          // its m' (the rows of Y and the gain)
     AccTable<double> enkf{"entries"};
-    DevBuf<double> enkf_Y, enkf_eps, enkf_eps_s, enkf_Ypost, enkf_gain, enkf_s1, enkf_s2, enkf_part;
-    // the analysis scheme (hc_set_enkf_method): 0 = perturbed observations, 1 = square root (the reduced gain [P][m'][D]
-    // and the mean's increment [P][D] of the last analysis: test hooks); relaxation to prior spread alpha (> 0: the
-    // tile partials and sums of the squared psi anomalies before / after the update, the sums of the analysis columns,
-    // and (sigma_b, sigma_a, f, the analysis's mean) [4][P][D] of the last analysis: test hooks); what the last
-    // analysis ran with
-    int enkf_method = 0;
+    DevBuf<double> enkf_Y, enkf_eps, enkf_eps_s, enkf_Ypost, enkf_part, enkf_part_sq;
+    EnkfVec enkf_psi;
+    // the analysis scheme (hc_set_enkf_method): 0 = perturbed observations, 1 = square root; relaxation of psi to prior
+    // spread alpha; what the last analysis ran with
+    int enkf_method = 0, enkf_last_method = 0;
     double enkf_alpha = 0.0;
-    int enkf_last_method = 0;
     bool enkf_last_relaxed = false;
-    DevBuf<double> enkf_rgain, enkf_dbar, enkf_part_sq, enkf_sq_b, enkf_sq_a, enkf_mean_a, enkf_relax;
     // soil-moisture sensors in the EnKF analysis (hc_set_enkf_soil_moisture): the record
     SmRecord enkf_sm;
     // the well's record inside the window (hc_set_enkf_window): the window, of each member's y on the lagged rows; the
@@ -317,15 +332,14 @@ struct hc_handle {
     void *shard_ctx = nullptr;
     DevBuf<double> enkf_first;
     // the members' base noise vectors in the analysis (hc_set_enkf_noise_field): on / off and the relaxation of their
-    // anomalies; diagnostics float64 [P][n_arow][4 D + 1] keyed like the EnKF's; per point the raw sums of both prior
-    // passes over (z, Y), the gain [P][m'][D] (square root: the reduced gain and the mean's increment), the squared
-    // anomalies before / after, the sums of the analysed vectors, (sigma_b, sigma_a, f, mean) [4][P][D]; per member
-    // whether its updated vector was refused, and that flag's sum per point
+    // anomalies; diagnostics float64 [P][n_arow][4 D + 1] keyed like the EnKF's; what the analysis keeps of z (EnkfVec,
+    // always with the spread: the table reports it); per member whether its vector was refused, and the count per point
     bool enkf_nz = false, nz_done = false;   // on; an analysis has updated the vectors since it was set
     double enkf_nz_alpha = 0.0;
     bool noise_host() const { return (filt_stride > 0 || enkf_nz) && philox; }   // filt_host(), or the noise field's twin
     AccTable<double> enkf_nzt{"entries"};
-    DevBuf<double> nz_s1, nz_s2, nz_gain, nz_rgain, nz_dbar, nz_sq_b, nz_sq_a, nz_mean_a, nz_relax, nz_rej, nz_rejsum;
+    EnkfVec enkf_z;
+    DevBuf<double> nz_rej, nz_rejsum;
     int n_cu = 256;
     double jac_reject = NUM_JAC_DIFF_REJECT;
 };
@@ -3416,9 +3430,7 @@ void nz_off(hc_handle *h)
     h->enkf_nz = h->nz_done = false;
     h->enkf_nz_alpha = 0.0;
     h->enkf_nzt.release();
-    h->nz_s1.release(); h->nz_s2.release(); h->nz_gain.release(); h->nz_rgain.release(); h->nz_dbar.release();
-    h->nz_sq_b.release(); h->nz_sq_a.release(); h->nz_mean_a.release(); h->nz_relax.release(); h->nz_rej.release();
-    h->nz_rejsum.release();
+    h->enkf_z.release(); h->nz_rej.release(); h->nz_rejsum.release();
 }
 
 void enkf_off(hc_handle *h)
@@ -3429,14 +3441,12 @@ void enkf_off(hc_handle *h)
     h->enkf_done = false;
     h->enkf_width = 0;
     h->enkf.release();
-    h->enkf_Y.release(); h->enkf_eps.release(); h->enkf_Ypost.release(); h->enkf_gain.release();
-    h->enkf_s1.release(); h->enkf_s2.release(); h->enkf_part.release();
+    h->enkf_Y.release(); h->enkf_eps.release(); h->enkf_Ypost.release(); h->enkf_part.release();
+    h->enkf_part_sq.release(); h->enkf_psi.release();
     h->enkf_method = 0;
     h->enkf_alpha = 0.0;
     h->enkf_last_method = 0;
     h->enkf_last_relaxed = false;
-    h->enkf_rgain.release(); h->enkf_dbar.release(); h->enkf_part_sq.release(); h->enkf_sq_b.release();
-    h->enkf_sq_a.release(); h->enkf_mean_a.release(); h->enkf_relax.release();
     sm_off(h);
     win_off(h);
 }
@@ -4782,25 +4792,148 @@ int enkf_exchange(hc_handle *h, double *pass, int64_t n_words, int64_t first_wor
     return HC_OK;
 }
 
+// What the passes of one analysis share: the row, the shape, the tiles and where their partials go.  hc_set_enkf_shard:
+// the handle's members are tiles tile0 ... of a point with np members and n_tiles tiles, the partials the passes' global
+// layouts in the caller's buffer (part_sq_b behind the prior products it travels with).  Off: np = mpp, tile0 = 0.
+struct EnkfPass {
+    hc_handle *h;
+    const EnkfRow &s;
+    int64_t N, D, P, C, n_tiles, my_tiles, tile0, row;
+    long long ll_mpp, ll_tiles, ll_np, ll_tile0, n_arow, slot, draw_offset;
+    int W, V;
+    bool shard, root;
+    double dz, z_obs;
+    double *part, *part_sq_b, *part_sq;
+    dim3 tiles, members, cols_prior;   // a block per tile and point; 256 members a block; a thread per column of (x, Y)
+    unsigned blocks;                   // of the member kernels that walk x
+
+    // the tile partials of one pass (enkf_partial_kernel's arguments), at the handle's tile offset
+    hipError_t partials(bool square, const double *x, const double *Y, int width, const double *sums, int Dc, dim3 threads,
+                        double *out, double *out_sq) const
+    {
+        hipLaunchKernelGGL(square ? enkf_partial_kernel<true> : enkf_partial_kernel<false>, tiles, threads, 0, h->stream, x,
+                           Y, width, sums, ll_mpp, Dc, ll_tiles, out, out_sq, ll_np, ll_tile0);
+        return hipGetLastError();
+    }
+    // sums[p][c] of a pass of `cols` columns from its tile partials; sharded: the stream drained and the other handles'
+    // tiles gathered first (a copy: the partials are the ones one handle would have formed)
+    int reduce(double *pass, int64_t cols, double *sums) const
+    {
+        if (shard)
+            if (int rc = enkf_exchange(h, pass, n_tiles * cols, tile0 * cols, my_tiles * cols)) return rc;
+        hipLaunchKernelGGL(enkf_finish_kernel, dim3((unsigned)cols, (unsigned)P), dim3(ENKF_THREADS), 0, h->stream, pass,
+                           ll_tiles, (int)cols, sums);
+        HIP_TRY(hipGetLastError());
+        return HC_OK;
+    }
+    // v.mean_a, then v.sq_a: the sums of x's columns, then of their squared anomalies about that mean, both less each
+    // point's first member's column (its own in x, or the copy a sharded analysis's exchange brought)
+    int spread(const double *x, EnkfVec &v) const
+    {
+        for (int sq = 0; sq < 2; sq++) {
+            hipLaunchKernelGGL(enkf_spread_kernel, tiles, dim3((unsigned)((D + WAVE - 1) / WAVE * WAVE)), 0, h->stream, x,
+                               sq ? v.mean_a.p : nullptr, ll_mpp, (int)D, ll_tiles, part_sq, shard ? h->enkf_first.p : x,
+                               shard ? 0LL : ll_mpp * (long long)D, ll_np, ll_tile0);
+            HIP_TRY(hipGetLastError());
+            if (int rc = reduce(part_sq, D, sq ? v.sq_a.p : v.mean_a.p)) return rc;
+        }
+        return HC_OK;
+    }
+};
+
+// One vector's part of the analysis, in place on x [N][D]: the sums of (x, Y), then the products of their anomalies with
+// Y's (two passes over x); the gain; the update (one read + write of x; hc_set_enkf_method: the square-root scheme's
+// own, from the reduced gain and the mean's increment the gain kernel adds); with alpha > 0 the relaxation to prior
+// spread -- the analysis columns' sums, their squared anomalies (two more passes), the factors, the relaxed columns (one
+// read + write).  The caller chooses: `square`, whether the second prior pass takes the squared anomalies along (the
+// relaxation needs them; a table of the prior std does regardless); st, sst, wst, the EnKF's, the sensors' and the
+// window's table for the gain kernel's prior diagnostics (NULL: none); `refused`, per member whether the update or the
+// relaxation refused its vector (NULL: not kept; both read Ypost's rejected flag either way).  STATE (x is psi) chooses
+// the member kernels' instance, the draws -- made between the gain and the stochastic update of the state alone, any
+// other vector reuses them -- and whether the update writes y into Ypost: the state's does unless a relaxation follows
+// and writes it.  A sharded analysis exchanges before every reduction and, under relaxation, brings the point's first
+// member's column to every handle (enkf_first_member_kernel, one more exchange, enkf_first); the spread and the factors
+// then read that copy with stride 0 instead of x with stride mpp D.  The noise field's table and the posterior are
+// enkf_analyse's.  (The gain, the square-root update and the relaxation's factors take N_p = np; the latter two also
+// index the points by m / N_p: a sharded handle holds one point, m / np = 0.)
+template <bool STATE>
+int enkf_vector(const EnkfPass &g, double *x, EnkfVec &v, double alpha, bool square, double *st, double *sst, double *wst,
+                double *refused)
+{
+    hc_handle *h = g.h;
+    const EnkfRow &s = g.s;
+    const int64_t N = g.N, D = g.D, P = g.P, C = g.C;
+    const int W = g.W, V = g.V;
+    const bool relax = alpha > 0.0;
+    const int want_y = STATE && !relax ? 1 : 0;
+    int rc = HC_OK;
+    HIP_TRY(g.partials(false, x, h->enkf_Y.p, W, nullptr, (int)D, g.cols_prior, g.part, nullptr));
+    if ((rc = g.reduce(g.part, C, v.s1.p))) return rc;
+    HIP_TRY(g.partials(square, x, h->enkf_Y.p, W, v.s1.p, (int)D, g.cols_prior, g.part, square ? g.part_sq_b : nullptr));
+    if ((rc = g.reduce(g.part, C * W, v.s2.p))) return rc;
+    if (square && (rc = g.reduce(g.part_sq_b, D, v.sq_b.p))) return rc;
+    hipLaunchKernelGGL(enkf_gain_kernel, dim3((unsigned)P), dim3((unsigned)((D + WAVE - 1) / WAVE * WAVE)), 0, h->stream,
+                       v.s1.p, v.s2.p, g.ll_np, (int)D, s, h->enkf_sigma, h->enkf_loc, g.z_obs, g.dz, v.gain.p, st, sst,
+                       g.n_arow, g.slot, g.root ? v.rgain.p : nullptr, g.root ? v.dbar.p : nullptr, wst);
+    HIP_TRY(hipGetLastError());
+    if (g.root) {
+        hipLaunchKernelGGL(enkf_sqrt_update_kernel<STATE>, dim3(g.blocks), dim3(256), 0, h->stream, x, h->enkf_Y.p,
+                           v.rgain.p, v.dbar.p, v.s1.p, h->Pdev.p, (long long)N, g.ll_np, (int)D, g.dz, W, V, want_y,
+                           h->enkf_Ypost.p, refused);
+    } else {
+        if (STATE) {
+            hipLaunchKernelGGL(enkf_draw_kernel, g.members, dim3(256), 0, h->stream, (long long)N, g.ll_mpp,
+                               (unsigned long long)h->enkf_seed, P > 1 ? h->point_base.p : nullptr, g.draw_offset,
+                               (unsigned)g.row, s.n, h->enkf_eps.p, h->enkf_eps_s.p);
+            HIP_TRY(hipGetLastError());
+            if (s.m > s.ms) {
+                hipLaunchKernelGGL(enkf_window_draw_kernel, g.members, dim3(256), 0, h->stream, (long long)N, g.ll_mpp,
+                                   (unsigned long long)h->enkf_seed, P > 1 ? h->point_base.p : nullptr, g.draw_offset, s,
+                                   h->enkf_eps_w.p);
+                HIP_TRY(hipGetLastError());
+            }
+        }
+        hipLaunchKernelGGL(enkf_update_kernel<STATE>, dim3(g.blocks), dim3(256), 0, h->stream, x, h->enkf_Y.p, v.gain.p,
+                           h->Pdev.p, (long long)N, g.ll_mpp, (int)D, g.dz, g.z_obs, h->enkf_sigma, s, h->enkf_eps.p,
+                           h->enkf_eps_s.p, h->enkf_eps_w.p, want_y, h->enkf_Ypost.p, refused);
+    }
+    HIP_TRY(hipGetLastError());
+    if (!relax) return HC_OK;
+    if (g.shard) {
+        // the point's first member's analysis column, from the handle that holds it, to every handle
+        const bool mine = h->shard_first == 0;
+        if (mine) {
+            hipLaunchKernelGGL(enkf_first_member_kernel, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, h->stream, x,
+                               (int)D, h->shard_buf);
+            HIP_TRY(hipGetLastError());
+        }
+        if ((rc = enkf_exchange(h, h->shard_buf, D, 0, mine ? D : 0))) return rc;
+        HIP_TRY(hipMemcpyAsync(h->enkf_first.p, h->shard_buf, (size_t)D * 8, hipMemcpyDeviceToDevice, h->stream));
+    }
+    if ((rc = g.spread(x, v))) return rc;
+    hipLaunchKernelGGL(enkf_relax_factor_kernel, dim3((unsigned)((P * D + 255) / 256)), dim3(256), 0, h->stream, v.sq_b.p,
+                       v.sq_a.p, v.mean_a.p, g.shard ? h->enkf_first.p : x, v.gain.p, (long long)P, g.ll_np, (int)D, W, alpha,
+                       v.relax.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(enkf_relax_kernel<STATE>, dim3(g.blocks), dim3(256), 0, h->stream, x, v.relax.p + (size_t)(3 * P * D),
+                       v.relax.p + (size_t)(2 * P * D), h->Pdev.p, (long long)N, g.ll_mpp, (int)D, g.dz, V, h->enkf_Ypost.p,
+                       refused);
+    HIP_TRY(hipGetLastError());
+    return HC_OK;
+}
+
 // The EnKF's analysis at the launch's last row (its water-table indices are wtd_u16's last row), m' = 1 + s.m
-// observations per member, in place on psi: y and theta per member; per point the column and observation sums, then the
-// anomaly products (two passes over psi); the gain and the prior diagnostics; the update with eps and the posterior (y,
-// theta, rejected) per member (one read + write of psi); the posterior sums and diagnostics.  Scratch is sized by the
-// record's largest m', 1 + n_s.  hc_set_enkf_method: the square-root scheme swaps the draws and the update for its own
-// (the gain kernel adds the reduced gain and the mean's increment); a relaxation alpha > 0 takes the squared psi
-// anomalies along in the second prior pass, sums the analysis columns and their squared anomalies (two more passes over
-// psi), relaxes (one read + write, which also writes y: the update before it skips that) and only then forms the
-// posterior.  The partial and spread kernels take the point's size np and the handle's tile offset tile0: (mpp, 0)
-// unless hc_set_enkf_shard made the handle's members a part of the point's; then every partial pass writes the handle's
-// tiles into the pass's global layout in the caller's buffer and every reduction gathers the other handles' first (one
-// callback each; one more for the point's first member's column under relaxation), so the sums -- and everything after
-// them -- are those of the one handle that holds every member.
+// observations per member: y and theta per member; psi's part (enkf_vector: the prior diagnostics and the posterior y are
+// its); with hc_set_enkf_noise_field the base vectors z's part, from the same Y, factor, innovations and draws (Y is
+// still the forecast's; Ypost holds the rejected flags) with its own alpha, then the noise field's table; the posterior
+// theta, the sums over (y, theta, rejected) and diagnostics.  Scratch is sized by the record's largest m', Wx.  With
+// hc_set_enkf_shard every partial pass writes the handle's tiles into the pass's global layout in the caller's buffer
+// and every reduction gathers the other handles' first (one callback each), so the sums -- and everything after them
+// -- are those of the one handle that holds every member.
 int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
 {
     const int64_t N = h->n_members, D = h->p.dim_d, P = h->n_points, mpp = N / P;
     const int64_t row = c.row0 + c.rows - 1, slot = row / h->enkf_stride, n_arow = assim_rows(h);
-    // hc_set_enkf_shard: the handle's members are tiles tile0 ... of a point with np members and n_tiles tiles; every
-    // reduction gathers the other handles' partials first (reduce below).  Off: np = mpp, the handle's own tiles.
     const bool shard = h->shard_global > 0;
     const int64_t np = shard ? h->shard_global : mpp, tile0 = shard ? h->shard_first / ENKF_TILE : 0;
     const int64_t my_tiles = (mpp + ENKF_TILE - 1) / ENKF_TILE, n_tiles = (np + ENKF_TILE - 1) / ENKF_TILE;
@@ -4811,65 +4944,34 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
                     "after hc_set_enkf_shard: set the shard again)", (long long)h->shard_words,
                     (long long)shard_words_needed(h, np));
     const int64_t cols_x = std::max(Cx * Wx, (Wx + 1) * (Wx + 1));   // the widest pass: the prior products or the posterior's
+    const bool root = h->enkf_method == 1, relax = h->enkf_alpha > 0.0;
     if (h->enkf_Y.ensure((size_t)(N * Wx)) || h->enkf_eps.ensure((size_t)N) ||
         h->enkf_eps_s.ensure((size_t)(N * h->enkf_sm.n)) || h->enkf_eps_w.ensure((size_t)(N * h->enkf_win.n)) ||
-        h->enkf_Ypost.ensure((size_t)(N * (Wx + 1))) ||
-        h->enkf_gain.ensure((size_t)(P * Wx * D)) || h->enkf_s1.ensure((size_t)(P * Cx)) ||
-        h->enkf_s2.ensure((size_t)(P * cols_x)) || (!shard && h->enkf_part.ensure((size_t)(P * n_tiles * cols_x))))
-        return HC_ERR_DEVICE;
-    const bool root = h->enkf_method == 1, relax = h->enkf_alpha > 0.0;
-    if (root && (h->enkf_rgain.ensure((size_t)(P * Wx * D)) || h->enkf_dbar.ensure((size_t)(P * D)))) return HC_ERR_DEVICE;
-    if (relax && ((!shard && h->enkf_part_sq.ensure((size_t)(P * n_tiles * D))) || h->enkf_sq_b.ensure((size_t)(P * D)) ||
-                  (shard && h->enkf_first.ensure((size_t)D)) ||
-                  h->enkf_sq_a.ensure((size_t)(P * D)) || h->enkf_mean_a.ensure((size_t)(P * D)) ||
-                  h->enkf_relax.ensure((size_t)(4 * P * D))))
+        h->enkf_Ypost.ensure((size_t)(N * (Wx + 1))) || h->enkf_psi.ensure(P, D, Wx, cols_x, root, relax, relax) ||
+        (!shard && h->enkf_part.ensure((size_t)(P * n_tiles * cols_x))) ||
+        (relax && (shard ? h->enkf_first.ensure((size_t)D) : h->enkf_part_sq.ensure((size_t)(P * n_tiles * D)))))
         return HC_ERR_DEVICE;
     if (h->enkf_nz) {
         if (shard) return fail(HC_ERR_ARG, "the noise field with a sharded analysis: the exchanged partials cover psi only");
-        if (h->enkf_part_sq.ensure((size_t)(P * n_tiles * D)) || h->nz_s1.ensure((size_t)(P * Cx)) ||
-            h->nz_s2.ensure((size_t)(P * Cx * Wx)) || h->nz_gain.ensure((size_t)(P * Wx * D)) ||
-            h->nz_sq_b.ensure((size_t)(P * D)) || h->nz_sq_a.ensure((size_t)(P * D)) || h->nz_mean_a.ensure((size_t)(P * D)) ||
-            h->nz_rej.ensure((size_t)N) || h->nz_rejsum.ensure((size_t)P) ||
-            (root && (h->nz_rgain.ensure((size_t)(P * Wx * D)) || h->nz_dbar.ensure((size_t)(P * D)))) ||
-            (h->enkf_nz_alpha > 0.0 && h->nz_relax.ensure((size_t)(4 * P * D))))
+        if (h->enkf_part_sq.ensure((size_t)(P * n_tiles * D)) || h->nz_rej.ensure((size_t)N) || h->nz_rejsum.ensure((size_t)P) ||
+            h->enkf_z.ensure(P, D, Wx, Cx * Wx, root, true, h->enkf_nz_alpha > 0.0))
             return HC_ERR_DEVICE;
     }
     const unsigned short *w = h->wtd_u16.p + (size_t)(c.rows - 1) * N;
-    const double dz = h->p.dz, z_obs = (double)h->h_wtd_obs[(size_t)row] * dz;
+    const double dz = h->p.dz;
     const int special = (int)h->use_special();
-    const long long ll_mpp = (long long)mpp, ll_tiles = (long long)n_tiles, ll_np = (long long)np, ll_tile0 = (long long)tile0;
-    // the tile partials: the handle's own buffers, or the passes' global layouts in the caller's (the squared anomalies
-    // behind the prior products they travel with)
-    double *const part = shard ? h->shard_buf : h->enkf_part.p;
-    double *const part_sq_b = shard ? h->shard_buf + (size_t)(n_tiles * C * W) : h->enkf_part_sq.p;
-    double *const part_sq = shard ? h->shard_buf : h->enkf_part_sq.p;
-    const long long draw_offset = (long long)(shard ? h->shard_first : h->member_offset);
-    const dim3 tiles((unsigned)my_tiles, (unsigned)P);
-    // the tile partials of one pass (enkf_partial_kernel's arguments), at the handle's tile offset
-    auto partials = [&](bool square, const double *psi, const double *Y, int width, const double *sums, int Dc,
-                        dim3 threads, double *out, double *out_sq) {
-        if (square)
-            hipLaunchKernelGGL(enkf_partial_kernel<true>, tiles, threads, 0, h->stream, psi, Y, width, sums, ll_mpp, Dc,
-                               ll_tiles, out, out_sq, ll_np, ll_tile0);
-        else
-            hipLaunchKernelGGL(enkf_partial_kernel<false>, tiles, threads, 0, h->stream, psi, Y, width, sums, ll_mpp, Dc,
-                               ll_tiles, out, out_sq, ll_np, ll_tile0);
-        return hipGetLastError();
-    };
-    // sums[p][c] of a pass of `cols` columns from its tile partials; sharded: the stream drained and the other handles'
-    // tiles gathered first (a copy: the partials are the ones one handle would have formed)
-    auto reduce = [&](double *pass, int64_t cols, double *sums) -> int {
-        if (shard)
-            if (int rc = enkf_exchange(h, pass, n_tiles * cols, tile0 * cols, my_tiles * cols)) return rc;
-        hipLaunchKernelGGL(enkf_finish_kernel, dim3((unsigned)cols, (unsigned)P), dim3(ENKF_THREADS), 0, h->stream, pass,
-                           ll_tiles, (int)cols, sums);
-        HIP_TRY(hipGetLastError());
-        return HC_OK;
-    };
-    // (the kernels that take N_p alone -- the gain, the posterior -- get np; so do the square-root update and the
-    //  relaxation's factors, which also index the points by m / N_p: a sharded handle holds one point, m / np = 0)
+    const long long ll_mpp = (long long)mpp, ll_np = (long long)np;
+    const dim3 members((unsigned)((N + 255) / 256)), cols_post((unsigned)WAVE);
+    const EnkfPass g{h, s, N, D, P, C, n_tiles, my_tiles, tile0, row,
+                     ll_mpp, (long long)n_tiles, ll_np, (long long)tile0, (long long)n_arow, (long long)slot,
+                     (long long)(shard ? h->shard_first : h->member_offset),
+                     W, V, shard, root, dz, (double)h->h_wtd_obs[(size_t)row] * dz,
+                     shard ? h->shard_buf : h->enkf_part.p,
+                     shard ? h->shard_buf + (size_t)(n_tiles * C * W) : h->enkf_part_sq.p,
+                     shard ? h->shard_buf : h->enkf_part_sq.p,
+                     dim3((unsigned)my_tiles, (unsigned)P), members, dim3((unsigned)((C + WAVE - 1) / WAVE * WAVE)),
+                     (unsigned)std::min<int64_t>((N + 3) / 4, (int64_t)h->n_cu * 8)};
     int rc = HC_OK;
-    const dim3 members((unsigned)((N + 255) / 256));
     hipLaunchKernelGGL(enkf_obs_kernel, members, dim3(256), 0, h->stream, w, h->psi.p, h->Pdev.p, (long long)N, ll_mpp,
                        (int)D, dz, h->enkf_Y.p, W);
     HIP_TRY(hipGetLastError());
@@ -4883,129 +4985,20 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
                            h->enkf_Y.p, W);
         HIP_TRY(hipGetLastError());
     }
-    // prior: the sums of (psi, Y), then the products of their anomalies with Y's
-    const dim3 cols_prior((unsigned)((C + WAVE - 1) / WAVE * WAVE)), cols_post((unsigned)WAVE);
-    HIP_TRY(partials(false, h->psi.p, h->enkf_Y.p, W, nullptr, (int)D, cols_prior, part, nullptr));
-    if ((rc = reduce(part, C, h->enkf_s1.p))) return rc;
-    HIP_TRY(partials(relax, h->psi.p, h->enkf_Y.p, W, h->enkf_s1.p, (int)D, cols_prior, part, relax ? part_sq_b : nullptr));
-    if ((rc = reduce(part, C * W, h->enkf_s2.p))) return rc;
-    if (relax && (rc = reduce(part_sq_b, D, h->enkf_sq_b.p))) return rc;
     double *st = h->enkf.buf.p, *sst = h->enkf_sm.table.buf.p, *wst = h->enkf_win.table.buf.p;
-    hipLaunchKernelGGL(enkf_gain_kernel, dim3((unsigned)P), dim3((unsigned)((D + WAVE - 1) / WAVE * WAVE)), 0, h->stream,
-                       h->enkf_s1.p, h->enkf_s2.p, ll_np, (int)D, s, h->enkf_sigma, h->enkf_loc, z_obs, dz,
-                       h->enkf_gain.p, st, sst, (long long)n_arow, (long long)slot, root ? h->enkf_rgain.p : nullptr,
-                       root ? h->enkf_dbar.p : nullptr, wst);
-    HIP_TRY(hipGetLastError());
-    const unsigned blocks = (unsigned)std::min<int64_t>((N + 3) / 4, (int64_t)h->n_cu * 8);
-    if (root) {
-        hipLaunchKernelGGL(enkf_sqrt_update_kernel<true>, dim3(blocks), dim3(256), 0, h->stream, h->psi.p, h->enkf_Y.p,
-                           h->enkf_rgain.p, h->enkf_dbar.p, h->enkf_s1.p, h->Pdev.p, (long long)N, ll_np, (int)D, dz, W, V,
-                           relax ? 0 : 1, h->enkf_Ypost.p, nullptr);
-        HIP_TRY(hipGetLastError());
-    } else {
-        hipLaunchKernelGGL(enkf_draw_kernel, members, dim3(256), 0, h->stream, (long long)N, ll_mpp,
-                           (unsigned long long)h->enkf_seed, P > 1 ? h->point_base.p : nullptr,
-                           draw_offset, (unsigned)row, s.n, h->enkf_eps.p, h->enkf_eps_s.p);
-        HIP_TRY(hipGetLastError());
-        if (mw > 0) {
-            hipLaunchKernelGGL(enkf_window_draw_kernel, members, dim3(256), 0, h->stream, (long long)N, ll_mpp,
-                               (unsigned long long)h->enkf_seed, P > 1 ? h->point_base.p : nullptr,
-                               draw_offset, s, h->enkf_eps_w.p);
-            HIP_TRY(hipGetLastError());
-        }
-        hipLaunchKernelGGL(enkf_update_kernel<true>, dim3(blocks), dim3(256), 0, h->stream, h->psi.p, h->enkf_Y.p,
-                           h->enkf_gain.p, h->Pdev.p, (long long)N, ll_mpp, (int)D, dz, z_obs, h->enkf_sigma, s,
-                           h->enkf_eps.p, h->enkf_eps_s.p, h->enkf_eps_w.p, relax ? 0 : 1, h->enkf_Ypost.p, nullptr);
-        HIP_TRY(hipGetLastError());
-    }
-    if (relax) {
-        // the analysis columns' sums, then their squared anomalies; the factors; the relaxed columns and their y
-        const dim3 cols_psi((unsigned)((D + WAVE - 1) / WAVE * WAVE));
-        // (each point's first member's column: its own in psi, or the copy the exchange below brings)
-        auto spread = [&](const double *sums) {
-            hipLaunchKernelGGL(enkf_spread_kernel, tiles, cols_psi, 0, h->stream, h->psi.p, sums, ll_mpp, (int)D, ll_tiles,
-                               part_sq, shard ? h->enkf_first.p : h->psi.p, shard ? 0LL : ll_mpp * (long long)D, ll_np,
-                               ll_tile0);
-            return hipGetLastError();
-        };
-        if (shard) {
-            // the point's first member's analysis column, from the handle that holds it, to every handle
-            const bool mine = h->shard_first == 0;
-            if (mine) {
-                hipLaunchKernelGGL(enkf_first_member_kernel, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, h->stream,
-                                   h->psi.p, (int)D, h->shard_buf);
-                HIP_TRY(hipGetLastError());
-            }
-            if ((rc = enkf_exchange(h, h->shard_buf, D, 0, mine ? D : 0))) return rc;
-            HIP_TRY(hipMemcpyAsync(h->enkf_first.p, h->shard_buf, (size_t)D * 8, hipMemcpyDeviceToDevice, h->stream));
-        }
-        HIP_TRY(spread(nullptr));
-        if ((rc = reduce(part_sq, D, h->enkf_mean_a.p))) return rc;
-        HIP_TRY(spread(h->enkf_mean_a.p));
-        if ((rc = reduce(part_sq, D, h->enkf_sq_a.p))) return rc;
-        hipLaunchKernelGGL(enkf_relax_factor_kernel, dim3((unsigned)((P * D + 255) / 256)), dim3(256), 0, h->stream,
-                           h->enkf_sq_b.p, h->enkf_sq_a.p, h->enkf_mean_a.p, shard ? h->enkf_first.p : h->psi.p,
-                           h->enkf_gain.p, (long long)P, ll_np, (int)D, W, h->enkf_alpha, h->enkf_relax.p);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(enkf_relax_kernel<true>, dim3(blocks), dim3(256), 0, h->stream, h->psi.p,
-                           h->enkf_relax.p + (size_t)(3 * P * D), h->enkf_relax.p + (size_t)(2 * P * D), h->Pdev.p, (long long)N, ll_mpp, (int)D, dz, V,
-                           h->enkf_Ypost.p, nullptr);
-        HIP_TRY(hipGetLastError());
-    }
+    if ((rc = enkf_vector<true>(g, h->psi.p, h->enkf_psi, h->enkf_alpha, relax, st, sst, wst, nullptr))) return rc;
     if (h->enkf_nz) {
-        // the noise field (hc_set_enkf_noise_field): the base vectors z take the state's place in the same passes -- the
-        // sums of (z, Y) and their anomaly products (with the squared anomalies: the prior std), the gain from the same
-        // factor, the update with the same innovations (Y is still the forecast's; Ypost holds the refused flags), the
-        // relaxation with its own alpha, and the spread of what is left for the table
+        // the noise field, then for its table the spread of what the update and the relaxation, if any, left (never
+        // sharded: part_sq is the handle's own) and the refused vectors' count
         double *const z = h->base.p;
-        const dim3 cols_z((unsigned)((D + WAVE - 1) / WAVE * WAVE));
-        auto spread_z = [&](const double *sums) {
-            hipLaunchKernelGGL(enkf_spread_kernel, tiles, cols_z, 0, h->stream, z, sums, ll_mpp, (int)D, ll_tiles,
-                               h->enkf_part_sq.p, z, ll_mpp * (long long)D, ll_np, ll_tile0);
-            return hipGetLastError();
-        };
-        HIP_TRY(partials(false, z, h->enkf_Y.p, W, nullptr, (int)D, cols_prior, part, nullptr));
-        if ((rc = reduce(part, C, h->nz_s1.p))) return rc;
-        HIP_TRY(partials(true, z, h->enkf_Y.p, W, h->nz_s1.p, (int)D, cols_prior, part, h->enkf_part_sq.p));
-        if ((rc = reduce(part, C * W, h->nz_s2.p))) return rc;
-        if ((rc = reduce(h->enkf_part_sq.p, D, h->nz_sq_b.p))) return rc;
-        hipLaunchKernelGGL(enkf_gain_kernel, dim3((unsigned)P), dim3((unsigned)((D + WAVE - 1) / WAVE * WAVE)), 0, h->stream,
-                           h->nz_s1.p, h->nz_s2.p, ll_np, (int)D, s, h->enkf_sigma, h->enkf_loc, z_obs, dz, h->nz_gain.p,
-                           nullptr, nullptr, (long long)n_arow, (long long)slot, root ? h->nz_rgain.p : nullptr,
-                           root ? h->nz_dbar.p : nullptr, nullptr);
-        HIP_TRY(hipGetLastError());
-        if (root)
-            hipLaunchKernelGGL(enkf_sqrt_update_kernel<false>, dim3(blocks), dim3(256), 0, h->stream, z, h->enkf_Y.p,
-                               h->nz_rgain.p, h->nz_dbar.p, h->nz_s1.p, h->Pdev.p, (long long)N, ll_np, (int)D, dz, W, V, 0,
-                               h->enkf_Ypost.p, h->nz_rej.p);
-        else
-            hipLaunchKernelGGL(enkf_update_kernel<false>, dim3(blocks), dim3(256), 0, h->stream, z, h->enkf_Y.p,
-                               h->nz_gain.p, h->Pdev.p, (long long)N, ll_mpp, (int)D, dz, z_obs, h->enkf_sigma, s,
-                               h->enkf_eps.p, h->enkf_eps_s.p, h->enkf_eps_w.p, 0, h->enkf_Ypost.p, h->nz_rej.p);
-        HIP_TRY(hipGetLastError());
-        if (h->enkf_nz_alpha > 0.0) {
-            HIP_TRY(spread_z(nullptr));
-            if ((rc = reduce(h->enkf_part_sq.p, D, h->nz_mean_a.p))) return rc;
-            HIP_TRY(spread_z(h->nz_mean_a.p));
-            if ((rc = reduce(h->enkf_part_sq.p, D, h->nz_sq_a.p))) return rc;
-            hipLaunchKernelGGL(enkf_relax_factor_kernel, dim3((unsigned)((P * D + 255) / 256)), dim3(256), 0, h->stream,
-                               h->nz_sq_b.p, h->nz_sq_a.p, h->nz_mean_a.p, z, h->nz_gain.p, (long long)P, ll_np, (int)D, W,
-                               h->enkf_nz_alpha, h->nz_relax.p);
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(enkf_relax_kernel<false>, dim3(blocks), dim3(256), 0, h->stream, z,
-                               h->nz_relax.p + (size_t)(3 * P * D), h->nz_relax.p + (size_t)(2 * P * D), h->Pdev.p,
-                               (long long)N, ll_mpp, (int)D, dz, V, h->enkf_Ypost.p, h->nz_rej.p);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(spread_z(nullptr));
-        if ((rc = reduce(h->enkf_part_sq.p, D, h->nz_mean_a.p))) return rc;
-        HIP_TRY(spread_z(h->nz_mean_a.p));
-        if ((rc = reduce(h->enkf_part_sq.p, D, h->nz_sq_a.p))) return rc;
-        HIP_TRY(partials(false, nullptr, h->nz_rej.p, 1, nullptr, 0, cols_post, part, nullptr));
-        if ((rc = reduce(part, 1, h->nz_rejsum.p))) return rc;
-        hipLaunchKernelGGL(enkf_noise_diag_kernel, dim3((unsigned)((P * D + 255) / 256)), dim3(256), 0, h->stream,
-                           h->nz_s1.p, h->nz_sq_b.p, h->nz_mean_a.p, h->nz_sq_a.p, z, h->nz_rejsum.p, (long long)P, ll_np,
-                           (int)D, W, h->enkf_nzt.buf.p, (long long)n_arow, (long long)slot);
+        EnkfVec &v = h->enkf_z;
+        if ((rc = enkf_vector<false>(g, z, v, h->enkf_nz_alpha, true, nullptr, nullptr, nullptr, h->nz_rej.p))) return rc;
+        if ((rc = g.spread(z, v))) return rc;
+        HIP_TRY(g.partials(false, nullptr, h->nz_rej.p, 1, nullptr, 0, cols_post, g.part, nullptr));
+        if ((rc = g.reduce(g.part, 1, h->nz_rejsum.p))) return rc;
+        hipLaunchKernelGGL(enkf_noise_diag_kernel, dim3((unsigned)((P * D + 255) / 256)), dim3(256), 0, h->stream, v.s1.p,
+                           v.sq_b.p, v.mean_a.p, v.sq_a.p, z, h->nz_rejsum.p, (long long)P, ll_np, (int)D, W,
+                           h->enkf_nzt.buf.p, (long long)n_arow, (long long)slot);
         HIP_TRY(hipGetLastError());
         h->nz_done = true;
     }
@@ -5015,12 +5008,13 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
         HIP_TRY(hipGetLastError());
     }
     // posterior: the same two passes over (y, theta, rejected) alone
-    HIP_TRY(partials(false, nullptr, h->enkf_Ypost.p, V, nullptr, 0, cols_post, part, nullptr));
-    if ((rc = reduce(part, V, h->enkf_s1.p))) return rc;
-    HIP_TRY(partials(false, nullptr, h->enkf_Ypost.p, V, h->enkf_s1.p, 0, cols_post, part, nullptr));
-    if ((rc = reduce(part, V * V, h->enkf_s2.p))) return rc;
-    hipLaunchKernelGGL(enkf_post_kernel, dim3((unsigned)((P + 63) / 64)), dim3(64), 0, h->stream, h->enkf_s1.p,
-                       h->enkf_s2.p, (long long)P, ll_np, s, st, sst, (long long)n_arow, (long long)slot);
+    double *const s1 = h->enkf_psi.s1.p, *const s2 = h->enkf_psi.s2.p;
+    HIP_TRY(g.partials(false, nullptr, h->enkf_Ypost.p, V, nullptr, 0, cols_post, g.part, nullptr));
+    if ((rc = g.reduce(g.part, V, s1))) return rc;
+    HIP_TRY(g.partials(false, nullptr, h->enkf_Ypost.p, V, s1, 0, cols_post, g.part, nullptr));
+    if ((rc = g.reduce(g.part, V * V, s2))) return rc;
+    hipLaunchKernelGGL(enkf_post_kernel, dim3((unsigned)((P + 63) / 64)), dim3(64), 0, h->stream, s1, s2, (long long)P,
+                       ll_np, s, st, sst, (long long)n_arow, (long long)slot);
     HIP_TRY(hipGetLastError());
     h->enkf_done = true;
     h->enkf_width = W;
@@ -6188,11 +6182,23 @@ int hc_set_enkf_stats(hc_handle *h, const double *table, int64_t n_entries)
                       "hc_set_enkf_stats");
 }
 
+// What the last analysis was (test hooks): refuses in `who`'s name unless one has run since hc_set_enkf and, as asked,
+// the noise field took part in it, it was the square-root one, it relaxed psi
+static int enkf_last(const hc_handle *h, const char *who, bool noise = false, bool root = false, bool relaxed = false)
+{
+    const bool done = h->enkf_stride > 0 && h->enkf_done;
+    if (noise && !(done && h->enkf_nz && h->nz_done)) return fail(HC_ERR_ARG, "%s: no analysis since hc_set_enkf_noise_field", who);
+    if (root && !(done && h->enkf_last_method == 1)) return fail(HC_ERR_ARG, "%s: no square-root analysis since hc_set_enkf", who);
+    if (relaxed && !(done && h->enkf_last_relaxed)) return fail(HC_ERR_ARG, "%s: no relaxed analysis since hc_set_enkf", who);
+    if (!done) return fail(HC_ERR_ARG, "%s: no analysis since hc_set_enkf", who);
+    return HC_OK;
+}
+
 // the last analysis's buffers (test hooks): `rows` rows of `len` doubles, `pitch` apart on the device
 static int enkf_hook(hc_handle *h, const double *src, double *out, size_t rows, size_t len, size_t pitch, const char *who)
 {
     if (!h || !out) return fail(HC_ERR_ARG, "%s: bad argument", who);
-    if (h->enkf_stride <= 0 || !h->enkf_done) return fail(HC_ERR_ARG, "%s: no analysis since hc_set_enkf", who);
+    if (int rc = enkf_last(h, who)) return rc;
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (pitch == len) {
@@ -6209,7 +6215,7 @@ static int enkf_hook(hc_handle *h, const double *src, double *out, size_t rows, 
 int hc_get_enkf_gain(hc_handle *h, double *gain)
 {
     const size_t P = h ? (size_t)h->n_points : 0, D = h ? (size_t)h->p.dim_d : 0;
-    return enkf_hook(h, h ? h->enkf_gain.p : nullptr, gain, P, D, h ? h->enkf_width * D : 0, "hc_get_enkf_gain");
+    return enkf_hook(h, h ? h->enkf_psi.gain.p : nullptr, gain, P, D, h ? h->enkf_width * D : 0, "hc_get_enkf_gain");
 }
 
 int hc_get_enkf_y(hc_handle *h, double *y)
@@ -6303,7 +6309,7 @@ static int gain_hook(hc_handle *h, const double *dev, double *gain, size_t cols,
 int hc_get_enkf_sm_gain(hc_handle *h, double *gain)
 {
     if (int rc = sm_check(h, gain, "hc_get_enkf_sm_gain")) return rc;
-    return gain_hook(h, h->enkf_gain.p, gain, (size_t)h->enkf_sm.width, "hc_get_enkf_sm_gain");
+    return gain_hook(h, h->enkf_psi.gain.p, gain, (size_t)h->enkf_sm.width, "hc_get_enkf_sm_gain");
 }
 
 int hc_get_enkf_sm_eps(hc_handle *h, double *eps)
@@ -6388,8 +6394,7 @@ int hc_get_enkf_window_eps(hc_handle *h, double *eps)
 int hc_get_enkf_window_gain(hc_handle *h, double *gain)
 {
     if (!h || !gain) return fail(HC_ERR_ARG, "hc_get_enkf_window_gain: bad argument");
-    if (h->enkf_stride <= 0 || !h->enkf_done) return fail(HC_ERR_ARG, "hc_get_enkf_window_gain: no analysis since hc_set_enkf");
-    return gain_hook(h, h->enkf_gain.p, gain, (size_t)h->enkf_width, "hc_get_enkf_window_gain");
+    return gain_hook(h, h->enkf_psi.gain.p, gain, (size_t)h->enkf_width, "hc_get_enkf_window_gain");
 }
 
 int hc_get_enkf_shard_words(hc_handle *h, int64_t n_global, int64_t *n_words)
@@ -6476,29 +6481,32 @@ int hc_get_enkf_method(hc_handle *h, int32_t *method, double *relaxation)
 int hc_get_enkf_sqrt_gain(hc_handle *h, double *gain)
 {
     if (!h || !gain) return fail(HC_ERR_ARG, "hc_get_enkf_sqrt_gain: bad argument");
-    if (h->enkf_stride <= 0 || !h->enkf_done || h->enkf_last_method != 1)
-        return fail(HC_ERR_ARG, "hc_get_enkf_sqrt_gain: no square-root analysis since hc_set_enkf");
-    return gain_hook(h, h->enkf_rgain.p, gain, (size_t)h->enkf_width, "hc_get_enkf_sqrt_gain");
+    if (int rc = enkf_last(h, "hc_get_enkf_sqrt_gain", false, true)) return rc;
+    return gain_hook(h, h->enkf_psi.rgain.p, gain, (size_t)h->enkf_width, "hc_get_enkf_sqrt_gain");
+}
+
+// an array of the last analysis as on the device, psi's or (noise) z's: a gain [P][m'][D] or (shift) the shift [P][D]
+static int vec_hook(hc_handle *h, bool noise, DevBuf<double> EnkfVec::*src, double *out, bool root, bool shift, const char *who)
+{
+    if (!h || !out) return fail(HC_ERR_ARG, "%s: bad argument", who);
+    if (int rc = enkf_last(h, who, noise, root)) return rc;
+    const size_t n = (size_t)h->n_points * h->p.dim_d * (shift ? 1 : (size_t)h->enkf_width);
+    return enkf_hook(h, ((noise ? h->enkf_z : h->enkf_psi).*src).p, out, 1, n, n, who);
 }
 
 int hc_get_enkf_sqrt_shift(hc_handle *h, double *shift)
 {
-    if (!h || !shift) return fail(HC_ERR_ARG, "hc_get_enkf_sqrt_shift: bad argument");
-    if (h->enkf_stride <= 0 || !h->enkf_done || h->enkf_last_method != 1)
-        return fail(HC_ERR_ARG, "hc_get_enkf_sqrt_shift: no square-root analysis since hc_set_enkf");
-    const size_t n = (size_t)h->n_points * h->p.dim_d;
-    return enkf_hook(h, h->enkf_dbar.p, shift, 1, n, n, "hc_get_enkf_sqrt_shift");
+    return vec_hook(h, false, &EnkfVec::dbar, shift, true, true, "hc_get_enkf_sqrt_shift");
 }
 
 int hc_get_enkf_relaxation(hc_handle *h, double *sigma_b, double *sigma_a, double *factor)
 {
     if (!h || !sigma_b || !sigma_a || !factor) return fail(HC_ERR_ARG, "hc_get_enkf_relaxation: bad argument");
-    if (h->enkf_stride <= 0 || !h->enkf_done || !h->enkf_last_relaxed)
-        return fail(HC_ERR_ARG, "hc_get_enkf_relaxation: no relaxed analysis since hc_set_enkf");
+    if (int rc = enkf_last(h, "hc_get_enkf_relaxation", false, false, true)) return rc;
     const size_t n = (size_t)h->n_points * h->p.dim_d;
     double *out[3] = {sigma_b, sigma_a, factor};
     for (int k = 0; k < 3; k++)
-        if (int rc = enkf_hook(h, h->enkf_relax.p + k * n, out[k], 1, n, n, "hc_get_enkf_relaxation")) return rc;
+        if (int rc = enkf_hook(h, h->enkf_psi.relax.p + k * n, out[k], 1, n, n, "hc_get_enkf_relaxation")) return rc;
     return HC_OK;
 }
 
@@ -6565,30 +6573,20 @@ int hc_set_enkf_noise_stats(hc_handle *h, const double *table, int64_t n_entries
                       "hc_set_enkf_noise_stats");
 }
 
-// the last analysis's gain for the vectors, [P][m'][D] as on the device (and the square-root run's reduced gain; its
-// shift [P][D])
-static int nz_hook(hc_handle *h, const DevBuf<double> *src, double *out, bool root, bool shift, const char *who)
-{
-    if (!h || !out) return fail(HC_ERR_ARG, "%s: bad argument", who);
-    if (!h->enkf_nz || !h->nz_done || !h->enkf_done) return fail(HC_ERR_ARG, "%s: no analysis since hc_set_enkf_noise_field", who);
-    if (root && h->enkf_last_method != 1) return fail(HC_ERR_ARG, "%s: no square-root analysis since hc_set_enkf", who);
-    const size_t n = (size_t)h->n_points * h->p.dim_d * (shift ? 1 : (size_t)h->enkf_width);
-    return enkf_hook(h, src->p, out, 1, n, n, who);
-}
-
+// the last analysis's gain for the vectors as on the device, the square-root run's reduced gain and its shift
 int hc_get_enkf_noise_gain(hc_handle *h, double *gain)
 {
-    return nz_hook(h, h ? &h->nz_gain : nullptr, gain, false, false, "hc_get_enkf_noise_gain");
+    return vec_hook(h, true, &EnkfVec::gain, gain, false, false, "hc_get_enkf_noise_gain");
 }
 
 int hc_get_enkf_noise_sqrt_gain(hc_handle *h, double *gain)
 {
-    return nz_hook(h, h ? &h->nz_rgain : nullptr, gain, true, false, "hc_get_enkf_noise_sqrt_gain");
+    return vec_hook(h, true, &EnkfVec::rgain, gain, true, false, "hc_get_enkf_noise_sqrt_gain");
 }
 
 int hc_get_enkf_noise_sqrt_shift(hc_handle *h, double *shift)
 {
-    return nz_hook(h, h ? &h->nz_dbar : nullptr, shift, true, true, "hc_get_enkf_noise_sqrt_shift");
+    return vec_hook(h, true, &EnkfVec::dbar, shift, true, true, "hc_get_enkf_noise_sqrt_shift");
 }
 
 int hc_get_enkf_noise_base(hc_handle *h, double *base, int64_t first, int64_t count)
