@@ -155,6 +155,12 @@ EXPORTS = {
     "hc_get_filter_temper_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),
     "hc_set_filter_temper_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),
     "hc_get_filter_temper_trials": ([C.c_void_p, _lp], C.c_int),
+    "hc_set_filter_rejuvenation": ([C.c_void_p, C.c_double], C.c_int),
+    "hc_get_filter_rejuvenation": ([C.c_void_p, _dp, _dp], C.c_int),
+    "hc_get_filter_rejuvenation_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),
+    "hc_set_filter_rejuvenation_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),
+    "hc_get_filter_rejuvenation_moments": ([C.c_void_p, _dp], C.c_int),
+    "hc_filter_rejuvenation_normals": ([C.c_void_p, C.c_int64, C.c_int64, C.c_int64, _dp], C.c_int),
     "hc_set_enkf": ([C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_uint64], C.c_int),
     "hc_get_enkf_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),
     "hc_set_enkf_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),

@@ -102,6 +102,17 @@ unknown keys, only membership of the 12 is checked):
   happened.  With ``Soil_Moisture``, ``Sharded``, a sweep and either noise source.  Added to the file: ``filter_ess_floor``
   and, over the ``filter_rows`` ``[R]``, ``filter_beta``, ``filter_ess_tempered``, ``filter_ess_target`` (a sweep: a leading
   ``[P]`` axis), and the run ends with `` [Ensemble xN] filter tempering: K of R rows tempered, smallest beta = ...``.
+* ``"Filter": {..., "Rejuvenation": 0.95}``: rejuvenate the members' base noise vectors -- their conductivity fields, which
+  resampling only ever loses -- after every resampling that copied a member (Liu & West's kernel shrinkage with that
+  discount, 0.5 <= delta < 1; include/hydrocol.h hc_set_filter_rejuvenation): the vectors of a point are pulled towards
+  their mean by a = (3 delta - 1) / (2 delta) and given a Gaussian jitter of sqrt(1 - a^2) times their spread, so that mean
+  and variance per node stay what the resampling left and no two members share a field.  With ``Soil_Moisture``,
+  ``ESS_floor``, ``Window_Offsets``, period totals, a sweep and either noise source; not together with ``"Sharded": true``
+  on a single-point run (the gathered words are water-table indices).  With a single survivor there is no spread to restore:
+  give an ``ESS_floor`` as well.  Added to the file: ``filter_rejuvenation_discount``, ``filter_rejuvenation_shrinkage`` and,
+  over the ``filter_rows`` ``[R]``, ``filter_rejuvenated``, ``filter_rejuvenation_refused``, ``filter_noise_std_resampled``,
+  ``filter_noise_std_rejuvenated`` (a sweep: a leading ``[P]`` axis), and the run ends with `` [Ensemble xN] filter
+  rejuvenation: K of R rows, noise-field spread kept ... of resampled``.
 * ``"Filter": {..., "Window_Offsets": [12, 24, 36]}``: the well's record inside the window (include/hydrocol.h
   hc_set_filter_window), the counterpart of ``EnKF.Window_Offsets`` with its rules.  Each entry is a number of rows before
   the assimilation row; nothing is resampled in between, so every member's weight becomes the likelihood of all the
@@ -305,6 +316,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     periods = period_settings(ens)
     filt = filter_settings(ens, ranks.world)
     ess_floor = filter_ess_floor(ens)
+    rejuvenation = filter_rejuvenation(ens)
     enkf = enkf_settings(ens, ranks.world)
     sm = soil_moisture_settings(ens, ranks.world)
     fsm = soil_moisture_settings(ens, ranks.world, "Filter")
@@ -326,7 +338,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     if ens.get("Points"):
         return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels, filt,
                           enkf, record, scheme, window, frecord, theta, storage, periods, plan, ess_floor, fwindow,
-                          noise_alpha)
+                          noise_alpha, rejuvenation)
     sharded = enkf_sharded(ens)
     fsharded = filter_sharded(ens)
     if sharded:
@@ -348,7 +360,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
                              noise=str(ens.get("Noise", "philox")).lower(),
                              spinup=str(ens.get("Spinup", "shared")).lower(), profile_stride=stride,
                              wtd_hist_stride=dist_stride, theta_hist_bins=theta[0],
-                             **_filter_kwargs(filt, frecord, ess_floor, fwindow),
+                             **_filter_kwargs(filt, frecord, ess_floor, fwindow, rejuvenation),
                              **_enkf_kwargs(enkf, record, scheme, window, noise_alpha), **_storage_kwargs(storage),
                              **_period_kwargs(periods, plan), **shard_kw)
     label = f"Ensemble x{n_members}"
@@ -389,7 +401,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     # (placed by it alone; a sum over the ranks would count them world times)
     eids = [0] if ranks.rank == 0 else []
     ftables, filter_line = _reduce_filter(ranks, sim, eids, 1, forcing.dim_t, filt, label, keep_points=False,
-                                          ess_floor=ess_floor)
+                                          ess_floor=ess_floor, rejuvenation=rejuvenation)
     extra.update(ftables)
     fstables, fsm_line = _reduce_sm(ranks, sim, eids, 1, forcing.dim_t, filt[0], frecord, label, keep_points=False,
                                     owner="filter")
@@ -703,7 +715,7 @@ def _period_kwargs(periods, plan):
     return kw
 
 
-FILTER_KEYS = ("Stride", "Sigma_cm", "Seed", "Sharded", "Soil_Moisture", "ESS_floor", "Window_Offsets")
+FILTER_KEYS = ("Stride", "Sigma_cm", "Seed", "Sharded", "Soil_Moisture", "ESS_floor", "Window_Offsets", "Rejuvenation")
 
 
 def filter_settings(ens, n_gpus=1):
@@ -711,11 +723,13 @@ def filter_settings(ens, n_gpus=1):
     runs before any GPU call, and a bad value is a ValueError (message + exit status 1).  A single-point ensemble on more
     than one GPU is refused -- resampling would have to move states between ranks -- unless the block says
     ``"Sharded": true`` (:func:`filter_sharded`).  ``ESS_floor`` (:func:`filter_ess_floor`) is checked here too;
-    ``Window_Offsets`` by :func:`filter_window_settings`."""
+    ``Window_Offsets`` by :func:`filter_window_settings`; ``Rejuvenation`` (:func:`filter_rejuvenation`) here."""
     import math
     from numbers import Integral, Real
     if "ESS_floor" in ens:
         raise ValueError(" Ensemble: ESS_floor belongs inside the \"Filter\" block.")
+    if "Rejuvenation" in ens:
+        raise ValueError(" Ensemble: Rejuvenation belongs inside the \"Filter\" block.")
     if "Window_Offsets" in ens:
         raise ValueError(" Ensemble: Window_Offsets belongs inside the \"Filter\" or the \"EnKF\" block.")
     block = ens.get("Filter")
@@ -749,6 +763,17 @@ def filter_settings(ens, n_gpus=1):
             raise ValueError(f" Ensemble: Filter.ESS_floor = {floor!r} must be a finite number with 0 < ESS_floor < 1.")
         if not stride:
             raise ValueError(" Ensemble: Filter.ESS_floor needs an active filter (Filter.Stride > 0).")
+    if "Rejuvenation" in block:
+        delta = block["Rejuvenation"]
+        if isinstance(delta, bool) or not isinstance(delta, Real) or not math.isfinite(delta) or not 0.5 <= delta < 1:
+            raise ValueError(f" Ensemble: Filter.Rejuvenation = {delta!r} must be a finite number with "
+                             f"0.5 <= Rejuvenation < 1.")
+        if not stride:
+            raise ValueError(" Ensemble: Filter.Rejuvenation needs an active filter (Filter.Stride > 0).")
+        if sharded and not ens.get("Points"):
+            raise ValueError(" Ensemble: Filter.Rejuvenation is not available with \"Sharded\": true: the sharded filter "
+                             "gathers the members' water-table indices only, and the moments of the base noise vectors "
+                             "would need an exchange of their own.")
     if not stride:
         return 0, None, None
     if not ens.get("Points") and int(n_gpus) > 1 and not sharded:
@@ -766,6 +791,17 @@ def filter_ess_floor(ens):
     if not isinstance(block, dict) or "ESS_floor" not in block:
         return None
     return float(block["ESS_floor"])
+
+
+def filter_rejuvenation(ens):
+    """Ensemble.Filter.Rejuvenation -> Liu & West's discount delta (0.5 <= delta < 1) of the base noise vectors' move after
+    a resampling (include/hydrocol.h hc_set_filter_rejuvenation), or None when the key is not given.  Checked by
+    :func:`filter_settings`, which this runs first."""
+    filter_settings(ens)
+    block = ens.get("Filter")
+    if not isinstance(block, dict) or "Rejuvenation" not in block:
+        return None
+    return float(block["Rejuvenation"])
 
 
 def filter_window_settings(ens):
@@ -1226,7 +1262,7 @@ def _reduce_enkf(ranks, sim, ids, P, T, enkf, label, keep_points, z0_cm):
     return out, line
 
 
-def _filter_kwargs(filt, record=None, ess_floor=None, window=None):
+def _filter_kwargs(filt, record=None, ess_floor=None, window=None, rejuvenation=None):
     stride, sigma, seed = filt
     if not stride:
         return {}
@@ -1237,16 +1273,19 @@ def _filter_kwargs(filt, record=None, ess_floor=None, window=None):
         kw["filter_ess_floor"] = ess_floor
     if window:
         kw["filter_window_offsets"] = window
+    if rejuvenation is not None:
+        kw["filter_rejuvenation"] = rejuvenation
     return kw
 
 
-def _reduce_filter(ranks, sim, ids, P, T, filt, label, keep_points, ess_floor=None):
+def _reduce_filter(ranks, sim, ids, P, T, filt, label, keep_points, ess_floor=None, rejuvenation=None):
     """The filter's datasets from this rank's handle ``sim`` (None: no points), its points ``ids`` placed in the run's [P]
     table and summed over the ranks (float64 as int64 bits: ``multigpu.place_points``), and the closing line (rank 0).
-    ``ess_floor`` (Filter.ESS_floor): the tempering's table likewise, its datasets and a second closing line."""
+    ``ess_floor`` (Filter.ESS_floor): the tempering's table likewise, its datasets and a second closing line;
+    ``rejuvenation`` (Filter.Rejuvenation): the rejuvenation's, and a line of its own."""
     import numpy as np
     from .multigpu import place_points
-    from .stepper import filter_summary, stride_rows
+    from .stepper import filter_summary, rejuvenation_shrinkage, stride_rows
     stride, sigma, _ = filt
     if not stride:
         return {}, None
@@ -1258,7 +1297,13 @@ def _reduce_filter(ranks, sim, ids, P, T, filt, label, keep_points, ess_floor=No
         tlocal = sim.filter_temper_table().reshape(-1, n_arow, 4) if sim is not None else np.zeros((0, n_arow, 4))
         ttable = place_points(tlocal, ids, P, ranks)
         ttable = ttable if keep_points else ttable[0]
-    summary = filter_summary(table if keep_points else table[0], stride, sigma, temper_table=ttable)
+    rtable = None
+    if rejuvenation is not None:
+        rlocal = sim.filter_rejuvenation_table().reshape(-1, n_arow, 4) if sim is not None else np.zeros((0, n_arow, 4))
+        rtable = place_points(rlocal, ids, P, ranks)
+        rtable = rtable if keep_points else rtable[0]
+    summary = filter_summary(table if keep_points else table[0], stride, sigma, temper_table=ttable,
+                             rejuvenation_table=rtable)
     out = {"filter_rows": summary["rows"], "filter_count": summary["count"], "filter_ess": summary["ess"],
            "filter_loglik_rows": summary["loglik_rows"], "filter_survivors": summary["survivors"],
            "filter_loglik": np.asarray(summary["loglik"], dtype=np.float64),
@@ -1266,6 +1311,13 @@ def _reduce_filter(ranks, sim, ids, P, T, filt, label, keep_points, ess_floor=No
     if ess_floor is not None:
         out.update(filter_ess_floor=np.array(ess_floor, dtype=np.float64), filter_beta=summary["beta"],
                    filter_ess_tempered=summary["ess_tempered"], filter_ess_target=summary["ess_target"])
+    if rejuvenation is not None:
+        out.update(filter_rejuvenation_discount=np.array(rejuvenation, dtype=np.float64),
+                   filter_rejuvenation_shrinkage=np.array(rejuvenation_shrinkage(rejuvenation)[0], dtype=np.float64),
+                   filter_rejuvenated=summary["rejuvenated"].astype(np.int8),
+                   filter_rejuvenation_refused=summary["rejuvenation_refused"],
+                   filter_noise_std_resampled=summary["noise_std_resampled"],
+                   filter_noise_std_rejuvenated=summary["noise_std_rejuvenated"])
     n = int(summary["rows"].size)
     if ranks.rank != 0:
         return out, None
@@ -1281,6 +1333,15 @@ def _reduce_filter(ranks, sim, ids, P, T, filt, label, keep_points, ess_floor=No
         k = int((beta < 1.0).any(axis=0).sum())
         least = float(np.nanmin(beta)) if np.isfinite(beta).any() else float("nan")
         line += f"\n [{label}] filter tempering: {k} of {n} rows tempered, smallest beta = {least:.6g}"
+    if rejuvenation is not None:
+        # (a sweep: the rows on which any point was rejuvenated; the ratio's mean over every point and row that was)
+        moved = np.asarray(summary["rejuvenated"]).reshape(-1, n) > 0
+        before = np.asarray(summary["noise_std_resampled"], dtype=np.float64).reshape(-1, n)[moved]
+        after = np.asarray(summary["noise_std_rejuvenated"], dtype=np.float64).reshape(-1, n)[moved]
+        ok = before > 0
+        kept = float((after[ok] / before[ok]).mean()) if ok.any() else float("nan")
+        line += (f"\n [{label}] filter rejuvenation: {int(moved.any(axis=0).sum())} of {n} rows, noise-field spread kept "
+                 f"{kept:.4f} of resampled")
     return out, line
 
 
@@ -1512,7 +1573,8 @@ def _reduce_periods(ranks, sim, ids, P, cols, forcing, periods, plan, label, kee
 
 def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride=0, dist_levels=None,
                filt=(0, None, None), enkf=(0, None, None, None), record=None, scheme=None, window=None, frecord=None,
-               theta=(0, None), storage=None, periods=None, plan=None, ess_floor=None, fwindow=None, noise_alpha=None):
+               theta=(0, None), storage=None, periods=None, plan=None, ess_floor=None, fwindow=None, noise_alpha=None,
+               rejuvenation=None):
     """Parameter points x members: this rank's points in one handle (ensemble.SweepSimulation), the whole table assembled
     over the ranks (multigpu.assemble_points)."""
     import numpy as np
@@ -1539,7 +1601,7 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     if mine:
         sim = SweepSimulation(points, forcing, n_members, seed=int(ens.get("Seed", 0)), device=device, point_ids=mine,
                               profile_stride=stride, wtd_hist_stride=dist_stride, theta_hist_bins=theta[0],
-                              **_filter_kwargs(filt, frecord, ess_floor, fwindow),
+                              **_filter_kwargs(filt, frecord, ess_floor, fwindow, rejuvenation),
                               **_enkf_kwargs(enkf, record, scheme, window, noise_alpha),
                               **_storage_kwargs(storage), **_period_kwargs(periods, plan))
         _step_all(sim, rows, label, ranks)
@@ -1561,7 +1623,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     arrays.update(stor_tables)
     ptables, period_line = _reduce_periods(ranks, sim, mine, P, ref, forcing, periods, plan, label, keep_points=True)
     arrays.update(ptables)
-    ftables, filter_line = _reduce_filter(ranks, sim, mine, P, T, filt, label, keep_points=True, ess_floor=ess_floor)
+    ftables, filter_line = _reduce_filter(ranks, sim, mine, P, T, filt, label, keep_points=True, ess_floor=ess_floor,
+                                          rejuvenation=rejuvenation)
     arrays.update(ftables)
     fstables, fsm_line = _reduce_sm(ranks, sim, mine, P, T, filt[0], frecord, label, keep_points=True, owner="filter")
     arrays.update(fstables)

@@ -278,6 +278,13 @@ struct hc_handle {
     AccTable<double> ftemp{"entries"};
     DevBuf<long long> filt_trials, filt_tstate;
     DevBuf<unsigned long long> filt_tpart;
+    // rejuvenated base vectors (hc_set_filter_rejuvenation): the discount (0: off) and the shrinkage a, h; the table
+    // float64 [P][n_arow][4] keyed like the filter's; the spread passes' tile partials [P][tiles][D] and sums [2][P][D];
+    // the last row's moments [P][3][D] (test hook) and refused counts [P]
+    double rj_delta = 0.0, rj_a = 0.0, rj_h = 0.0;
+    AccTable<double> frej{"entries"};
+    DevBuf<double> rj_part, rj_sums, rj_mom;
+    DevBuf<unsigned long long> rj_refused;
     // the well's record inside the window (hc_set_filter_window): the window, of each member's water-table index on the
     // lagged rows; per member the largest of its indices on a windowed row (what counts it).  filt_ycols = the width
     // of Y on the last assimilation, m_s + m_w + 2 (0: it took the bin path)
@@ -2835,6 +2842,151 @@ __global__ __launch_bounds__(FILT_THREADS) void filter_temper_apply_kernel(
     }
 }
 
+// ---- rejuvenation of the members' base noise vectors (hc_set_filter_rejuvenation, include/hydrocol.h)
+// After a row's resampling, per point with 0 < survivors < N_p: the resampled vectors' mean and std per node by the
+// EnKF's spread passes (enkf_spread_kernel + enkf_finish_kernel), Liu & West's shrinkage towards the mean plus a Philox
+// jitter, then the spread passes again for the spread that is left.  Every decision is read on the device from the
+// survivors count filter_fill_kernel left; contraction is off.
+constexpr int REJUV_WIDTH = 4;                         // table entries per point and slot
+
+__device__ __forceinline__ bool rejuv_applies(const unsigned long long *surv, long long p, long long mpp)
+{
+    const unsigned long long s = surv[p];
+    return s > 0 && s < (unsigned long long)mpp;
+}
+
+// The two standard normals of the node pair q = d >> 1 under the filter's seed at counter (0x80000000 | q, row, gid_lo,
+// gid_hi), with philox_normal's Box-Muller step: the cosine for the even node, the sine for the odd one.  A noise
+// counter's first word is below 2^31 and the filter's and the EnKF's are >= 0xFFFFFFF0: the streams never meet.
+__device__ __forceinline__ void rejuv_normal_pair(unsigned long long seed, unsigned long long gid, unsigned row, uint32_t q,
+                                                  double &even, double &odd)
+{
+#pragma clang fp contract(off)
+    uint32_t r[4];
+    philox4x32_10(0x80000000u | q, row, (uint32_t)gid, (uint32_t)(gid >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    const uint64_t a = ((uint64_t)r[1] << 32) | r[0], b = ((uint64_t)r[3] << 32) | r[2];
+    const double u1 = ((double)(a >> 11) + 0.5) * (1.0 / 9007199254740992.0);
+    const double u2 = ((double)(b >> 11) + 0.5) * (1.0 / 9007199254740992.0);
+    const double rad = sqrt(-2.0 * log(u1));
+    double s, c;
+    sincospi(2.0 * u2, &s, &c);
+    even = rad * c;
+    odd = rad * s;
+}
+
+// the global member id of the handle's slot m: the id the EnKF's draws use
+__device__ __forceinline__ unsigned long long rejuv_gid(const long long *point_base, long long member_offset, long long m,
+                                                        long long mpp)
+{
+    return point_base ? (unsigned long long)(point_base[m / mpp] + m % mpp) : (unsigned long long)(member_offset + m);
+}
+
+// One wave per member, the column layout of enkf_relax_kernel (node c * WAVE + lane in slot c):
+// z'_d = mean_d + a (z_d - mean_d) + (h s_d) eps_d from mom = (mean, s) [P][3][D], stored only when every entry is
+// finite (enkf_keep_column's vote; else the member keeps its vector and is counted in refused[p]).  Lane l forms the
+// normals of the pairs c2 * WAVE + l -- one Philox block, one log and one sincospi for both nodes -- and a shuffle brings
+// node d's to the lane that holds it: nodes (2 c2 + j) WAVE + lane, j = 0, 1, are pair c2 WAVE + 32 j + lane / 2.
+__global__ __launch_bounds__(256) void filter_rejuvenate_kernel(double *base, const double *mom,
+                                                                const unsigned long long *surv, long long n_members,
+                                                                long long mpp, int D, double a, double hh,
+                                                                unsigned long long seed, const long long *point_base,
+                                                                long long member_offset, unsigned row,
+                                                                unsigned long long *refused)
+{
+#pragma clang fp contract(off)
+    static_assert(ENKF_SLOTS % 2 == 0, "the pairs of a wave cover two slots");
+    const int lane = threadIdx.x % WAVE;
+    const long long waves = (long long)gridDim.x * (blockDim.x / WAVE);
+    for (long long m = (long long)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE; m < n_members; m += waves) {
+        const long long p = m / mpp;
+        if (!rejuv_applies(surv, p, mpp)) continue;                   // (wave-uniform)
+        const unsigned long long gid = rejuv_gid(point_base, member_offset, m, mpp);
+        const double *mean = mom + (size_t)p * 3 * D, *sd = mean + D;
+        double *col = base + (size_t)m * D;
+        double z[ENKF_SLOTS], next[ENKF_SLOTS];
+#pragma unroll
+        for (int c2 = 0; c2 < ENKF_SLOTS / 2; c2++) {
+            const int q = c2 * WAVE + lane;
+            double even = 0.0, odd = 0.0;
+            if (2 * q < D) rejuv_normal_pair(seed, gid, row, (uint32_t)q, even, odd);
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+                const int c = 2 * c2 + j, d = c * WAVE + lane, src = (WAVE / 2) * j + lane / 2;
+                const double ve = __shfl(even, src), vo = __shfl(odd, src);
+                const double eps = lane & 1 ? vo : ve;
+                z[c] = 0.0;
+                next[c] = 0.0;
+                if (d < D) {
+                    const double mu = mean[d];
+                    z[c] = col[d];
+                    next[c] = (mu + a * (z[c] - mu)) + (hh * sd[d]) * eps;
+                }
+            }
+        }
+        const bool keep = enkf_keep_column(z, next, col, lane, D);
+        if (!keep && lane == 0) atomicAdd(refused + p, 1ull);
+    }
+}
+
+// The moments and the table's row from the sums of two spread passes over the base vectors (s1: of x - x_0; s2: of the
+// squared anomalies), one block per point, thread d = node d.  after = 0, the resampled vectors: mom[p][0] = mean_d =
+// x_0d + s1_d / N_p and mom[p][1] = s_d = sqrt(s2_d / (N_p - 1)) (N_p = 1: 0), entries 0 and 2 of the row, 1 and 3
+// created.  after = 1, the vectors the move left: mom[p][2] = s_d, entries 1 (the members refused) and 3.  Entries 2
+// and 3, sqrt(sum_d s_d^2 / D), are summed by thread 0, nodes ascending; NaN where the point was not rejuvenated.
+__global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void filter_rejuv_diag_kernel(
+    const double *base, const double *s1, const double *s2, const unsigned long long *surv, const unsigned long long *refused,
+    long long mpp, int D, int after, double *mom, double *table, long long n_arow, long long slot)
+{
+#pragma clang fp contract(off)
+    __shared__ double sq[HC_MAX_DEPTH_NODES];
+    const long long p = blockIdx.x;
+    const int d = threadIdx.x;
+    if (d < D) {
+        const size_t k = (size_t)p * D + d;
+        const double s = mpp > 1 ? sqrt(s2[k] / (double)(mpp - 1)) : 0.0;
+        double *mo = mom + (size_t)p * 3 * D;
+        if (!after) {
+            mo[d] = base[(size_t)(p * mpp) * D + d] + s1[k] / (double)mpp;
+            mo[D + d] = s;
+        } else {
+            mo[2 * D + d] = s;
+        }
+        sq[d] = s * s;
+    }
+    __syncthreads();
+    if (d != 0) return;
+    const bool applied = rejuv_applies(surv, p, mpp);
+    double sum = 0.0;
+    for (int i = 0; i < D; i++) sum += sq[i];
+    const double spread = applied ? sqrt(sum / (double)D) : __builtin_nan("");
+    double *st = table + ((size_t)p * n_arow + slot) * REJUV_WIDTH;
+    if (!after) {
+        st[0] = applied ? 1.0 : 0.0;
+        st[1] = 0.0;
+        st[2] = spread;
+        st[3] = __builtin_nan("");
+    } else {
+        st[1] = (double)refused[p];
+        st[3] = spread;
+    }
+}
+
+// the normals of slots first ... first + count - 1 at `row` as filter_rejuvenate_kernel forms them, out [count][D]; one
+// thread per slot and node pair (hc_filter_rejuvenation_normals)
+__global__ void filter_rejuv_normals_kernel(unsigned long long seed, const long long *point_base, long long member_offset,
+                                            long long mpp, unsigned row, long long first, long long count, int D, double *out)
+{
+    const int pairs = (D + 1) / 2;
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= count * pairs) return;
+    const long long j = k / pairs;
+    const int q = (int)(k % pairs);
+    double even, odd;
+    rejuv_normal_pair(seed, rejuv_gid(point_base, member_offset, first + j, mpp), row, (uint32_t)q, even, odd);
+    out[(size_t)j * D + 2 * q] = even;
+    if (2 * q + 1 < D) out[(size_t)j * D + 2 * q + 1] = odd;
+}
+
 __global__ void widen_u16(const unsigned short *in, int *out, size_t n)
 {
     size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -3353,6 +3505,21 @@ void temper_off(hc_handle *h)
     h->filt_trials.release(); h->filt_tstate.release(); h->filt_tpart.release();
 }
 
+// the table of the rejuvenation (hc_set_filter_rejuvenation): [P][n_arow][4] float64, created as NaN
+int ensure_frej(hc_handle *h)
+{
+    if (h->rj_delta <= 0.0) return fail(HC_ERR_ARG, "the base vectors are not rejuvenated (hc_set_filter_rejuvenation)");
+    if (int rc = ensure_filter(h)) return rc;
+    return ensure_da_table(h, h->frej, h->filt_stride, REJUV_WIDTH, 0);
+}
+
+void rejuv_off(hc_handle *h)
+{
+    h->rj_delta = h->rj_a = h->rj_h = 0.0;
+    h->frej.release();
+    h->rj_part.release(); h->rj_sums.release(); h->rj_mom.release(); h->rj_refused.release();
+}
+
 void fsm_off(hc_handle *h)
 {
     h->filt_sm.clear();
@@ -3368,6 +3535,7 @@ void filter_off(hc_handle *h)
     fsm_off(h);
     fwin_off(h);
     temper_off(h);
+    rejuv_off(h);
     h->filt_stride = 0;
     h->filt_done = false;
     h->filt.release();
@@ -4653,6 +4821,43 @@ int filter_temper(hc_handle *h, const unsigned short *w, int ms, int64_t mpp, in
     return HC_OK;
 }
 
+// The rejuvenation of a row's resampled base vectors x [N][D] (hc_set_filter_rejuvenation), in place: two spread passes
+// (the EnKF's kernels, unsharded: tile 0 first, each point's first member its own), the moments and the row's entries,
+// the move, two spread passes and the entries of what it left.  Everything is enqueued unconditionally -- no host
+// synchronisation; a point that is not rejuvenated leaves the move at once and its entries say so.
+int filter_rejuvenate(hc_handle *h, double *x, int64_t row, const long long *pbase, long long key)
+{
+    const int64_t N = h->n_members, D = h->p.dim_d, P = h->n_points, mpp = N / P;
+    const int64_t n_tiles = (mpp + ENKF_TILE - 1) / ENKF_TILE, slot = row / h->filt_stride, n_arow = assim_rows(h);
+    if (h->rj_part.ensure((size_t)(P * n_tiles * D)) || h->rj_sums.ensure((size_t)(2 * P * D)) ||
+        h->rj_mom.ensure((size_t)(3 * P * D)) || h->rj_refused.ensure((size_t)P))
+        return HC_ERR_DEVICE;
+    double *s1 = h->rj_sums.p, *s2 = s1 + (size_t)(P * D);
+    const dim3 tiles((unsigned)n_tiles, (unsigned)P), nodes((unsigned)((D + WAVE - 1) / WAVE * WAVE));
+    for (int after = 0; after < 2; after++) {
+        for (int sq = 0; sq < 2; sq++) {
+            hipLaunchKernelGGL(enkf_spread_kernel, tiles, nodes, 0, h->stream, x, sq ? s1 : nullptr, (long long)mpp, (int)D,
+                               (long long)n_tiles, h->rj_part.p, x, (long long)(mpp * D), (long long)mpp, 0LL);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(enkf_finish_kernel, dim3((unsigned)D, (unsigned)P), dim3(ENKF_THREADS), 0, h->stream,
+                               h->rj_part.p, (long long)n_tiles, (int)D, sq ? s2 : s1);
+            HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(filter_rejuv_diag_kernel, dim3((unsigned)P), nodes, 0, h->stream, x, s1, s2, h->filt_surv.p,
+                           h->rj_refused.p, (long long)mpp, (int)D, after, h->rj_mom.p, h->frej.buf.p, (long long)n_arow,
+                           (long long)slot);
+        HIP_TRY(hipGetLastError());
+        if (after) break;
+        HIP_TRY(hipMemsetAsync(h->rj_refused.p, 0, (size_t)P * 8, h->stream));
+        const unsigned blocks = (unsigned)std::min<size_t>(((size_t)N + 3) / 4, (size_t)h->n_cu * 64);
+        hipLaunchKernelGGL(filter_rejuvenate_kernel, dim3(blocks), dim3(256), 0, h->stream, x, h->rj_mom.p, h->filt_surv.p,
+                           (long long)N, (long long)mpp, (int)D, h->rj_a, h->rj_h, (unsigned long long)h->filt_seed, pbase, key,
+                           (unsigned)row, h->rj_refused.p);
+        HIP_TRY(hipGetLastError());
+    }
+    return HC_OK;
+}
+
 // The assimilation at the launch's last row (its water-table indices are wtd_u16's last row): weights, diagnostics and
 // draw per point, the member prefix scan, the slot fill, then psi and base gathered into the second buffers and swapped in.
 // hc_set_filter_shard: the handle's members are a part of a point of np members; the water-table indices of all of them
@@ -4764,6 +4969,8 @@ int assimilate(hc_handle *h, const Chunk &c)
     // the rest of this hc_step_rows call launches on the analysis (fill_args took the pointers before the swap)
     h->io_host.psi = h->psi.p;
     if (h->io_host.base_noise) h->io_host.base_noise = h->base.p;
+    if (h->rj_delta > 0.0)
+        if (int rc = filter_rejuvenate(h, h->base.p, row, pbase, key)) return rc;
     h->filt_done = true;
     return HC_OK;
 }
@@ -5083,6 +5290,7 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
     const bool da_on = filt_on || enkf_on;
     if (da_on && da.sm.n > 0 && (rc = da.ensure_sm(h))) return rc;
     if (filt_on && h->filt_floor > 0.0 && (rc = ensure_ftemp(h))) return rc;
+    if (filt_on && h->rj_delta > 0.0 && (rc = ensure_frej(h))) return rc;
     if (da_on && da.win.n > 0 && (rc = da.ensure_win(h))) return rc;
     int64_t fresh_consumed = 0;
     for (int64_t done = 0; done < a->n_rows;) {
@@ -5973,6 +6181,90 @@ int hc_get_filter_temper_trials(hc_handle *h, int64_t *trials)
                        "hc_get_filter_temper_trials");
 }
 
+int hc_set_filter_rejuvenation(hc_handle *h, double discount)
+{
+    if (!h) return fail(HC_ERR_ARG, "hc_set_filter_rejuvenation: bad argument");
+    if (discount != 0.0 && !(std::isfinite(discount) && discount >= 0.5 && discount < 1.0))
+        return fail(HC_ERR_ARG, "hc_set_filter_rejuvenation: discount = %g must be 0 (off) or finite with 0.5 <= discount < 1",
+                    discount);
+    if (discount != 0.0 && h->filt_stride <= 0)
+        return fail(HC_ERR_ARG, "hc_set_filter_rejuvenation: the particle filter is off (hc_set_filter comes first)");
+    if (discount != 0.0 && h->fs_n > 0)
+        return fail(HC_ERR_ARG, "hc_set_filter_rejuvenation: the filter is sharded (hc_set_filter_shard), and the sharded "
+                                "filter gathers water-table indices only: the moments of the base vectors would need an "
+                                "exchange of their own");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    rejuv_off(h);
+    if (discount == 0.0) return HC_OK;
+    // Liu & West's shrinkage, every operation rounded once
+    const double a = (3.0 * discount - 1.0) / (2.0 * discount);
+    h->rj_delta = discount;
+    h->rj_a = a;
+    h->rj_h = std::sqrt(1.0 - a * a);
+    const int rc = ensure_frej(h);
+    if (rc != HC_OK) rejuv_off(h);               // refused: off
+    return rc;
+}
+
+int hc_get_filter_rejuvenation(hc_handle *h, double *discount, double *shrinkage)
+{
+    if (!h || !discount || !shrinkage) return fail(HC_ERR_ARG, "hc_get_filter_rejuvenation: bad argument");
+    *discount = h->rj_delta;
+    *shrinkage = h->rj_delta > 0.0 ? h->rj_a : 0.0;
+    return HC_OK;
+}
+
+int hc_get_filter_rejuvenation_stats(hc_handle *h, double *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_get_filter_rejuvenation_stats: bad argument");
+    return table_copy(h, h->frej, ensure_frej, hipMemcpyDeviceToHost, table, n_entries, "hc_get_filter_rejuvenation_stats");
+}
+
+int hc_set_filter_rejuvenation_stats(hc_handle *h, const double *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_set_filter_rejuvenation_stats: bad argument");
+    return table_copy(h, h->frej, ensure_frej, hipMemcpyHostToDevice, const_cast<double *>(table), n_entries,
+                      "hc_set_filter_rejuvenation_stats");
+}
+
+int hc_get_filter_rejuvenation_moments(hc_handle *h, double *moments)
+{
+    if (!h || !moments) return fail(HC_ERR_ARG, "hc_get_filter_rejuvenation_moments: bad argument");
+    if (h->rj_delta <= 0.0)
+        return fail(HC_ERR_ARG, "hc_get_filter_rejuvenation_moments: the base vectors are not rejuvenated");
+    if (!h->rj_mom.p) return fail(HC_ERR_ARG, "hc_get_filter_rejuvenation_moments: no assimilation since the setting");
+    return filter_hook(h, h->rj_mom, moments, (size_t)h->n_points * 3 * h->p.dim_d, "hc_get_filter_rejuvenation_moments");
+}
+
+int hc_filter_rejuvenation_normals(hc_handle *h, int64_t row, int64_t first_member, int64_t count, double *out)
+{
+    if (!h || !out || row < 0 || row > (int64_t)UINT32_MAX || first_member < 0 || count < 0 ||
+        first_member + count > h->n_members)
+        return fail(HC_ERR_ARG, "hc_filter_rejuvenation_normals: bad argument");
+    if (h->filt_stride <= 0) return fail(HC_ERR_ARG, "hc_filter_rejuvenation_normals: the particle filter is off (hc_set_filter)");
+    // the points' keys: hc_set_filter uploaded them (fill_args), and new keys or a new member offset turn the filter off
+    if (h->n_points > 1 && !h->point_base.p)
+        return fail(HC_ERR_ARG, "hc_filter_rejuvenation_normals: the points' member bases are not in place (hc_set_filter)");
+    if (count == 0) return HC_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    const int D = h->p.dim_d;
+    const size_t n = (size_t)count * D;
+    DevBuf<double> eps;
+    if (eps.ensure(n)) return HC_ERR_DEVICE;
+    const long long work = (long long)count * ((D + 1) / 2);
+    hipLaunchKernelGGL(filter_rejuv_normals_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, h->stream,
+                       (unsigned long long)h->filt_seed, h->n_points > 1 ? h->point_base.p : nullptr,
+                       (long long)h->member_offset, (long long)(h->n_members / h->n_points), (unsigned)row,
+                       (long long)first_member, (long long)count, D, eps.p);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) e = hipMemcpy(out, eps.p, n * 8, hipMemcpyDeviceToHost);
+    eps.release();
+    if (e != hipSuccess) return fail(HC_ERR_DEVICE, "hc_filter_rejuvenation_normals: %s", hipGetErrorString(e));
+    return HC_OK;
+}
+
 int hc_get_filter_sm_width(hc_handle *h, int32_t *width)
 {
     if (!h || !width) return fail(HC_ERR_ARG, "hc_get_filter_sm_width: bad argument");
@@ -6113,6 +6405,10 @@ int hc_set_filter_shard(hc_handle *h, int32_t n_shards, const int64_t *bounds, i
     if (h->filt_win.n > 0)
         return fail(HC_ERR_ARG, "hc_set_filter_shard: window offsets are set (hc_set_filter_window), and the sharded filter "
                                 "gathers the water-table indices of the assimilation row only");
+    if (h->rj_delta > 0.0)
+        return fail(HC_ERR_ARG, "hc_set_filter_shard: the base vectors are rejuvenated (hc_set_filter_rejuvenation), and the "
+                                "sharded filter gathers water-table indices only: their moments would need an exchange of "
+                                "their own");
     if (h->per_n > 0)
         return fail(HC_ERR_ARG, "hc_set_filter_shard: period totals are set (hc_set_period_totals), and the routed columns do "
                                 "not carry the members' accumulators");

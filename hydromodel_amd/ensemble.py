@@ -12,7 +12,7 @@ from .digest import inverse_retention
 from .stepper import enkf_noise_summary, noise_field_settings
 from .stepper import (ENKF_METHODS, ENKF_WIDTH, SM_WIDTH, WINDOW_WIDTH, EnsembleStepper, enkf_sm_summary, enkf_summary,
                       enkf_window_settings, enkf_window_summary, filter_sm_summary, filter_summary,
-                      filter_window_settings, filter_window_summary,
+                      filter_window_settings, filter_window_summary, rejuvenation_discount,
                       flux_max_log2_of, layer_ranges, layer_storage_distribution, moments_to_mean_std, period_totals_distribution,
                       sensor_nodes, theta_distribution, wtd_distribution)
 
@@ -121,6 +121,13 @@ class _Run:
     filter_ess_floor: 0 < f < 1 holds the effective sample size of every resampling above f times the counted members by
     tempering the weights (include/hydrocol.h hc_set_filter_tempering); :meth:`filter_temper_table`, and
     :meth:`filter_summary` gains ``beta``, ``ess_tempered``, ``ess_target`` and ``tempered_rows``.
+    filter_rejuvenation: Liu & West's discount 0.5 <= delta < 1: after every resampling that copied a member the point's
+    base noise vectors -- the members' conductivity fields, which resampling otherwise only ever loses -- are pulled
+    towards their mean and jittered, so that mean and variance per node stay what the resampling left and no two members
+    share a field (include/hydrocol.h hc_set_filter_rejuvenation); :meth:`filter_rejuvenation_table`, and
+    :meth:`filter_summary` gains ``rejuvenated``, ``rejuvenation_refused``, ``noise_std_resampled``,
+    ``noise_std_rejuvenated`` and ``rejuvenated_rows``.  With a single survivor there is no spread to restore: give a
+    ``filter_ess_floor`` as well.
     filter_window_offsets: rows before each assimilation row (integers in [1, filter_stride), e.g. (12, 24, 36)) whose
     observation of the well joins the members' weights too: nothing is resampled in between, so a member's weight is the
     likelihood of everything its trajectory passed (include/hydrocol.h hc_set_filter_window);
@@ -149,7 +156,7 @@ class _Run:
                       enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None,
                       enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=(),
                       filter_soil_moisture=None, theta_hist_bins=0, storage_layers_cm=None, storage_bins=0,
-                      filter_ess_floor=0.0, filter_window_offsets=(), enkf_noise_field=None):
+                      filter_ess_floor=0.0, filter_window_offsets=(), enkf_noise_field=None, filter_rejuvenation=0.0):
         self.profile_stride = int(profile_stride)
         self.storage_layers_cm = None if storage_layers_cm is None or len(storage_layers_cm) == 0 else \
             np.asarray(storage_layers_cm, dtype=np.float64).reshape(-1, 2)
@@ -188,6 +195,11 @@ class _Run:
             if not self.filter_stride:
                 raise ValueError("filter_ess_floor needs the particle filter (filter_stride > 0)")
             self.stepper.set_filter_tempering(self.filter_ess_floor)
+        self.filter_rejuvenation = rejuvenation_discount(filter_rejuvenation)
+        if self.filter_rejuvenation:
+            if not self.filter_stride:
+                raise ValueError("filter_rejuvenation needs the particle filter (filter_stride > 0)")
+            self.stepper.set_filter_rejuvenation(self.filter_rejuvenation)
         self.filter_window_offsets = filter_window_settings(filter_window_offsets, self.filter_stride,
                                                             self.stepper.filter_sm_n)
         if self.filter_window_offsets:
@@ -344,17 +356,26 @@ class _Run:
         hc_set_filter_tempering); a sweep: [P][n_arow][4]."""
         return self.stepper.filter_temper_table().reshape(self._lead + (-1, 4))
 
-    def filter_summary(self, table=None, sm_table=None, temper_table=None, window_table=None):
+    def filter_rejuvenation_table(self):
+        """[n_arow][4] float64 (applied, members refused, the base vectors' spread before and after the move;
+        include/hydrocol.h hc_set_filter_rejuvenation); a sweep: [P][n_arow][4]."""
+        return self.stepper.filter_rejuvenation_table().reshape(self._lead + (-1, 4))
+
+    def filter_summary(self, table=None, sm_table=None, temper_table=None, window_table=None, rejuvenation_table=None):
         """The filter's record (stepper.filter_summary): ``rows``, ``count``, ``ess``, ``loglik_rows``, ``survivors`` over
         the assimilated rows and ``loglik``, the log marginal likelihood of the well record (log cm^-1 summed over the rows),
         with a leading [P] for a sweep; ``table``: e.g. the one assembled over ranks.  With a soil-moisture record the
         increments of the sensor rows are the joint ones, and the ``sm_*`` keys of :meth:`filter_sm_summary` come along.
         With ``filter_ess_floor`` the tempering's ``beta``, ``ess_tempered``, ``ess_target`` and ``tempered_rows`` too
-        (``temper_table``: as ``table``).  With a window the ``window_*`` keys of :meth:`filter_window_summary` too."""
+        (``temper_table``: as ``table``).  With a window the ``window_*`` keys of :meth:`filter_window_summary` too.  With
+        ``filter_rejuvenation`` the ``rejuvenated`` ... keys (``rejuvenation_table``: as ``table``)."""
         t = self.filter_table() if table is None else table
         if getattr(self, "filter_ess_floor", 0.0) and temper_table is None:      # (0.0: a run started without the setting)
             temper_table = self.filter_temper_table()
-        out = filter_summary(t, self.filter_stride, self.filter_sigma_cm, temper_table=temper_table)
+        if getattr(self, "filter_rejuvenation", 0.0) and rejuvenation_table is None:
+            rejuvenation_table = self.filter_rejuvenation_table()
+        out = filter_summary(t, self.filter_stride, self.filter_sigma_cm, temper_table=temper_table,
+                             rejuvenation_table=rejuvenation_table)
         if self.filter_soil_moisture is not None:
             out.update(("sm_" + k, v) for k, v in self.filter_sm_summary(sm_table).items())
         if getattr(self, "filter_window_offsets", ()):
@@ -454,9 +475,12 @@ class EnsembleSimulation(_Run):
                  enkf_window_offsets=(), enkf_shard=None, filter_shard=None, filter_soil_moisture=None,
                  theta_hist_bins=0, storage_layers_cm=None, storage_bins=0, period_ends=None, period_thresholds_cm=(),
                  period_bins=0, period_flux_max_cm=(16.0, 4.0), filter_ess_floor=0.0, filter_window_offsets=(),
-                 enkf_noise_field=None):
+                 enkf_noise_field=None, filter_rejuvenation=0.0):
         if enkf_shard is not None and noise_field_settings(enkf_noise_field, 0.0) is not None:
             raise ValueError("enkf_shard and enkf_noise_field exclude each other: the exchanged partials cover psi only")
+        if filter_shard is not None and rejuvenation_discount(filter_rejuvenation):
+            raise ValueError("filter_shard and filter_rejuvenation exclude each other: the sharded filter gathers "
+                             "water-table indices only, the moments of the base vectors would need an exchange of their own")
         if filter_shard is not None and filter_window_offsets is not None and len(filter_window_offsets):
             raise ValueError("filter_shard and filter_window_offsets exclude each other: the sharded filter gathers the "
                              "water-table indices of the assimilation row only")
@@ -475,7 +499,8 @@ class EnsembleSimulation(_Run):
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
                            enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins, storage_layers_cm,
-                           storage_bins, filter_ess_floor, filter_window_offsets, enkf_noise_field)
+                           storage_bins, filter_ess_floor, filter_window_offsets, enkf_noise_field,
+                           filter_rejuvenation=filter_rejuvenation)
         self._start_periods(period_ends, period_thresholds_cm, period_bins, period_flux_max_cm)
         self.enkf_shard = None
         if enkf_shard is not None:
@@ -620,7 +645,10 @@ class EnsembleSimulation(_Run):
             if self.filter_ess_floor:                     # (an untempered run keeps its key set)
                 arrays["filter_ess_floor"] = np.array(self.filter_ess_floor, dtype=np.float64)
                 arrays["filter_temper_table"] = self.stepper.filter_temper_table()
-            if self.filter_window_offsets:                # what was recorded for the coming assimilation travels along
+            if self.filter_rejuvenation:                  # (the moved vectors are filter_base; the draws are stateless)
+                arrays["filter_rejuvenation"] = np.array(self.filter_rejuvenation, dtype=np.float64)
+                arrays["filter_rejuvenation_table"] = self.stepper.filter_rejuvenation_table()
+            if self.filter_window_offsets:               # what was recorded for the coming assimilation travels along
                 b, rows = self.stepper.filter_window_capture()
                 arrays["filter_window_offsets"] = np.asarray(self.filter_window_offsets, dtype=np.int64)
                 arrays["filter_window_table"] = self.stepper.filter_window_table()
@@ -684,6 +712,9 @@ class EnsembleSimulation(_Run):
         tempered = bool(filt) and "filter_ess_floor" in data
         if tempered:
             fkw.update(filter_ess_floor=float(data["filter_ess_floor"]))
+        rejuvenated = bool(filt) and "filter_rejuvenation" in data
+        if rejuvenated:
+            fkw.update(filter_rejuvenation=float(data["filter_rejuvenation"]))
         periods = "period_ends" in data
         if periods:
             fkw.update(period_ends=np.asarray(data["period_ends"], dtype=np.int64).reshape(-1),
@@ -733,6 +764,8 @@ class EnsembleSimulation(_Run):
                 sim.stepper.set_filter_sm_table(np.asarray(data["filter_sm_table"], dtype=np.float64))
             if tempered:
                 sim.stepper.set_filter_temper_table(np.asarray(data["filter_temper_table"], dtype=np.float64))
+            if rejuvenated:
+                sim.stepper.set_filter_rejuvenation_table(np.asarray(data["filter_rejuvenation_table"], dtype=np.float64))
             if has_fwin:
                 sim.stepper.set_filter_window_table(np.asarray(data["filter_window_table"], dtype=np.float64))
                 sim.stepper.set_filter_window_capture(np.asarray(data["filter_window_index"], dtype=np.int32).reshape(-1, n),
@@ -863,7 +896,7 @@ class SweepSimulation(_Run):
                  enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=(),
                  filter_soil_moisture=None, theta_hist_bins=0, storage_layers_cm=None, storage_bins=0, period_ends=None,
                  period_thresholds_cm=(), period_bins=0, period_flux_max_cm=(16.0, 4.0), filter_ess_floor=0.0,
-                 filter_window_offsets=(), enkf_noise_field=None):
+                 filter_window_offsets=(), enkf_noise_field=None, filter_rejuvenation=0.0):
         self.points = list(cols_list)
         self.P, self.n = len(self.points), int(n_members)
         self._lead = (self.P,)
@@ -893,7 +926,8 @@ class SweepSimulation(_Run):
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
                            enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins, storage_layers_cm,
-                           storage_bins, filter_ess_floor, filter_window_offsets, enkf_noise_field)
+                           storage_bins, filter_ess_floor, filter_window_offsets, enkf_noise_field,
+                           filter_rejuvenation=filter_rejuvenation)
         self._start_periods(period_ends, period_thresholds_cm, period_bins, period_flux_max_cm)
         self.next_row, self.kernel_ms, self.launches = 1, 0.0, 0
 

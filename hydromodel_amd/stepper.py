@@ -83,6 +83,7 @@ class EnsembleStepper:
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = 0, 0.0, 0
         self.filter_sm_nodes = None
         self.filter_ess_floor = 0.0
+        self.filter_rejuvenation = 0.0
         self.filter_window_offsets = ()
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
         self.enkf_sm_nodes = None
@@ -588,6 +589,7 @@ class EnsembleStepper:
         self.filter_shard, self._filter_shard_keep = None, None                  # ... and the sharding with it
         self.filter_sm_nodes = None                                              # ... and the sensor record
         self.filter_ess_floor = 0.0                                              # ... and the tempering
+        self.filter_rejuvenation = 0.0                                           # ... and the rejuvenation
         self.filter_window_offsets = ()                                          # ... and the window
         L.check(self.lib.hc_set_filter(self.h, stride, sigma, int(seed) & 0xFFFFFFFFFFFFFFFF))
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = stride, sigma, int(seed)
@@ -597,6 +599,7 @@ class EnsembleStepper:
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = 0, 0.0, 0
         self.filter_sm_nodes = None
         self.filter_ess_floor = 0.0
+        self.filter_rejuvenation = 0.0
         self.filter_window_offsets = ()
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
         self.enkf_sm_nodes = None
@@ -677,6 +680,52 @@ class EnsembleStepper:
         unused rows k = -1 (test hook)."""
         out = np.zeros((self.P, TEMPER_TRIALS, TEMPER_WIDTH), dtype=np.int64)
         L.check(self.lib.hc_get_filter_temper_trials(self.h, L.lptr(out)))
+        return out
+
+    # -- rejuvenated base vectors (include/hydrocol.h hc_set_filter_rejuvenation) -----------------------------------------
+    def set_filter_rejuvenation(self, discount):
+        """After every resampling that copied a member (0 < survivors < N_p) pull the point's base noise vectors towards
+        their mean and jitter them (Liu & West's kernel shrinkage with ``discount`` delta, 0.5 <= delta < 1; 0 = off), so
+        that the per-node mean and variance stay what the resampling left and no two members share a field.  The filter
+        must be on and not sharded (:meth:`set_filter` first; it removes the setting again)."""
+        d = rejuvenation_discount(discount)
+        if d and self.filter_shard is not None:
+            raise ValueError("filter rejuvenation with a sharded filter: the gathered words are water-table indices, the "
+                             "moments of the base vectors would need an exchange of their own")
+        self.filter_rejuvenation = 0.0
+        L.check(self.lib.hc_set_filter_rejuvenation(self.h, d))
+        self.filter_rejuvenation = d
+
+    def filter_rejuvenation_shrinkage(self):
+        """(delta, a) as the library holds them; (0, 0) when off."""
+        d, a = np.zeros(1), np.zeros(1)
+        L.check(self.lib.hc_get_filter_rejuvenation(self.h, L.dptr(d), L.dptr(a)))
+        return float(d[0]), float(a[0])
+
+    def filter_rejuvenation_table(self):
+        """[P][n_arow][4] float64: applied, members refused, sqrt(mean_d s_d^2) of the resampled base vectors and of the
+        rejuvenated ones per assimilation slot (the last two NaN when not applied; all NaN where nothing was assimilated)."""
+        t = np.zeros((self.P, stride_rows(self.T, self.filter_stride), REJUV_WIDTH))
+        L.check(self.lib.hc_get_filter_rejuvenation_stats(self.h, L.dptr(t), t.size))
+        return t
+
+    def set_filter_rejuvenation_table(self, table):
+        t = L.as_f64(table).reshape(-1)
+        L.check(self.lib.hc_set_filter_rejuvenation_stats(self.h, L.dptr(t), t.size))
+
+    def filter_rejuvenation_moments(self):
+        """[P][3][D] float64 of the last assimilation: mean_d and s_d of the resampled base vectors, s_d of the vectors the
+        move left (test hook)."""
+        out = np.zeros((self.P, 3, self.D))
+        L.check(self.lib.hc_get_filter_rejuvenation_moments(self.h, L.dptr(out)))
+        return out
+
+    def filter_rejuvenation_normals(self, row, first=0, count=None):
+        """[count][D] float64: the jitter's standard normals of the handle's slots ``first`` ... at forcing row ``row``
+        (stateless test hook; the filter on)."""
+        count = self.N - int(first) if count is None else int(count)
+        out = np.zeros((count, self.D))
+        L.check(self.lib.hc_filter_rejuvenation_normals(self.h, int(row), int(first), count, L.dptr(out)))
         return out
 
     # -- soil-moisture sensors in the particle filter (include/hydrocol.h hc_set_filter_soil_moisture) -------------------
@@ -1995,12 +2044,84 @@ def filter_temper_of(l, counted, ess_floor, n_b=None):
     return k, trials, filter_temper_weights(l, counted, k)
 
 
-def filter_summary(table, stride, sigma_cm, temper_table=None):
+# ---- rejuvenated base vectors on the host (include/hydrocol.h hc_set_filter_rejuvenation) ------------------------------
+REJUV_WIDTH = 4
+
+
+def rejuvenation_discount(discount):
+    """Liu & West's discount as a float: 0 (off; None too) or finite with 0.5 <= delta < 1; anything else, a bool
+    included, is a ValueError."""
+    from numbers import Real
+    if discount is None:
+        return 0.0
+    if isinstance(discount, (bool, np.bool_)) or not isinstance(discount, (Real, np.floating, np.integer)):
+        raise ValueError(f"filter rejuvenation = {discount!r} must be a number: 0 (off) or 0.5 <= discount < 1")
+    d = float(discount)
+    if d != 0.0 and not (np.isfinite(d) and 0.5 <= d < 1.0):
+        raise ValueError(f"filter rejuvenation = {discount!r} must be 0 (off) or finite with 0.5 <= discount < 1")
+    return d
+
+
+def rejuvenation_shrinkage(discount):
+    """(a, h) = ((3 delta - 1) / (2 delta), sqrt(1 - a a)) in float64, every operation rounded once."""
+    d = np.float64(rejuvenation_discount(discount))
+    if d == 0.0:
+        raise ValueError("filter rejuvenation is off (discount 0): no shrinkage")
+    a = (np.float64(3.0) * d - np.float64(1.0)) / (np.float64(2.0) * d)
+    return float(a), float(np.sqrt(np.float64(1.0) - a * a))
+
+
+def filter_rejuvenation_of(z, eps, discount, survivors=None):
+    """The rejuvenation of ONE point's resampled base vectors ``z`` [N][D] restated in float64 NumPy (include/hydrocol.h
+    hc_set_filter_rejuvenation), with the standard normals ``eps`` [N][D].  ``survivors``: the resampling's count; None
+    counts the distinct rows of ``z``.  The point is rejuvenated iff 0 < survivors < N.
+
+    Moments as differences from the first member: mean_d = z_0d + S1_d / N, s_d = sqrt(S2_d / (N - 1)) (N = 1: 0); the
+    update z' = (mean + a (z - mean)) + (h s) eps; a member whose new vector has a non-finite entry keeps its vector and
+    is refused.  Returns ``z`` [N][D], ``applied``, ``refused`` [N] bool, ``mean``, ``s``, ``s_after`` [D] and ``row``
+    [4] = the table's entries (applied, members refused, sqrt(mean_d s_d^2) before and after; NaN when not applied)."""
+    z = np.asarray(z, dtype=np.float64)
+    eps = np.asarray(eps, dtype=np.float64)
+    N, D = z.shape
+    a, h = rejuvenation_shrinkage(discount)
+
+    def moments(x):
+        d0 = x - x[0][None, :]
+        s1 = d0.sum(axis=0)
+        mean = x[0] + s1 / N
+        if N == 1:
+            return mean, np.zeros(D)
+        an = d0 - (s1 / N)[None, :]
+        return mean, np.sqrt((an * an).sum(axis=0) / (N - 1))
+
+    with np.errstate(all="ignore"):
+        mean, s = moments(z)
+        if survivors is None:
+            survivors = np.unique(z, axis=0).shape[0]
+        applied = 0 < int(survivors) < N
+        refused = np.zeros(N, dtype=bool)
+        out = z.copy()
+        if applied:
+            cand = (mean[None, :] + a * (z - mean[None, :])) + (h * s)[None, :] * eps
+            refused = ~np.isfinite(cand).all(axis=1)
+            out = np.where(refused[:, None], z, cand)
+        s_after = moments(out)[1]
+        nan = float("nan")
+        row = np.array([1.0 if applied else 0.0, float(refused.sum()),
+                        np.sqrt((s * s).sum() / D) if applied else nan,
+                        np.sqrt((s_after * s_after).sum() / D) if applied else nan])
+    return {"z": out, "applied": applied, "refused": refused, "mean": mean, "s": s, "s_after": s_after, "row": row,
+            "a": a, "h": h}
+
+
+def filter_summary(table, stride, sigma_cm, temper_table=None, rejuvenation_table=None):
     """The filter's record from its [..., n_arow, 4] table: ``rows`` (forcing row of every assimilated slot), ``count``,
     ``ess``, ``loglik_rows`` (the increments), ``survivors`` [..., R] over the slots any point assimilated, and ``loglik``
     [...] = the sum of the increments in row order; ``stride``, ``sigma_cm``.  With the tempering's table
     (``temper_table`` [..., n_arow, 4]) also ``beta``, ``ess_tempered``, ``ess_target`` [..., R] and ``tempered_rows``
-    [...] = the rows resampled with beta < 1."""
+    [...] = the rows resampled with beta < 1.  With the rejuvenation's (``rejuvenation_table`` [..., n_arow, 4]) also
+    ``rejuvenated`` (0 / 1), ``rejuvenation_refused``, ``noise_std_resampled``, ``noise_std_rejuvenated`` [..., R] and
+    ``rejuvenated_rows`` [...] = the rows on which the base vectors were moved."""
     t = np.asarray(table, dtype=np.float64)
     used = (t[..., 0] > 0).reshape(-1, t.shape[-2]).any(axis=0)
     slots = np.flatnonzero(used)
@@ -2017,6 +2138,13 @@ def filter_summary(table, stride, sigma_cm, temper_table=None):
         tempered = (tt[..., 0] < 1.0).sum(axis=-1)
         out.update(beta=tt[..., 0], ess_tempered=tt[..., 1], ess_target=tt[..., 2],
                    tempered_rows=tempered if tempered.ndim else int(tempered))
+    if rejuvenation_table is not None:
+        rt = np.asarray(rejuvenation_table, dtype=np.float64)[..., slots, :]
+        moved = (rt[..., 0] > 0).sum(axis=-1)
+        out.update(rejuvenated=np.nan_to_num(rt[..., 0]).astype(np.int64),
+                   rejuvenation_refused=np.nan_to_num(rt[..., 1]).astype(np.int64),
+                   noise_std_resampled=rt[..., 2], noise_std_rejuvenated=rt[..., 3],
+                   rejuvenated_rows=moved if moved.ndim else int(moved))
     return out
 
 

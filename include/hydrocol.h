@@ -57,6 +57,8 @@
  *   hc_set_filter, hc_get/set_filter_stats, hc_get/set_filter_base, hc_get_filter_ancestors/weights/draw,
  *   hc_set_filter_soil_moisture, hc_get/set_filter_sm_stats, hc_get_filter_sm_width/member_weights/loglik/sm_theta
  *   hc_set_filter_tempering, hc_get/set_filter_temper_stats, hc_get_filter_temper_trials
+ *   hc_set/get_filter_rejuvenation, hc_get/set_filter_rejuvenation_stats, hc_get_filter_rejuvenation_moments,
+ *   hc_filter_rejuvenation_normals
  *                      <- (new) the ensemble conditioned on wtd_obs (src/simulation.py:582-612): a bootstrap particle filter,
  *                         and the log marginal likelihood of the well record per parameter point
  *   hc_set_enkf, hc_get/set_enkf_stats, hc_get_enkf_gain/y/eps
@@ -579,6 +581,50 @@ int hc_set_filter_tempering(hc_handle *h, double ess_floor);
 int hc_get_filter_temper_stats(hc_handle *h, double *table, int64_t n_entries);
 int hc_set_filter_temper_stats(hc_handle *h, const double *table, int64_t n_entries);
 int hc_get_filter_temper_trials(hc_handle *h, int64_t *trials);
+
+/* Rejuvenated base vectors: the kernel-shrinkage move of Liu & West (2001) on the members' base noise vectors.  A member's
+ * base vector is its static log-conductivity field (src/simulation.py:598-602 uses it on every row that is neither wet
+ * nor a multiple of 48), and resampling a static quantity only loses values: after a non-trivial resampling several slots
+ * of a point share one vector and nothing in the dynamics separates them again.  With a discount delta,
+ *   a = (3 delta - 1) / (2 delta),  h = sqrt(1 - a a)   (host, fp64, every operation rounded once),
+ * an assimilation row ends -- after the gather, the buffer swap, the period accumulators' gather and the sensors' posterior
+ * moments -- with, per parameter point p of N_p members:
+ *   Trigger: the point is rejuvenated iff 0 < survivors < N_p (entry 3 of the filter's table, read on the device: no host
+ *   synchronisation).  Systematic resampling is monotone, so survivors = N_p is the identity ancestry: flat weights and
+ *   the neutral filter leave every vector to the bit.
+ *   Moments of the resampled vectors x [N_p][D], node by node, by the EnKF's spread passes (differences from the point's
+ *   first member, tiles of 256 members in member order, the tile partials strided over 1024 threads and a fixed tree):
+ *   mean_d = x_0d + S1_d / N_p, S1_d = sum_k (x_kd - x_0d);  s_d = sqrt(S2_d / (N_p - 1)), S2_d = sum_k ((x_kd - x_0d) -
+ *   S1_d / N_p)^2  (N_p = 1: 0).
+ *   Update, no contraction:  z'_kd = (mean_d + a (z_kd - mean_d)) + (h s_d) eps_kd,  eps a standard normal of
+ *   Philox4x32-10 under the filter's seed at counter (0x80000000 | (d >> 1), row, gid_lo, gid_hi), gid the slot's global
+ *   member id (point base + j, or member offset + m: the id of the EnKF's draws), Box-Muller as the noise's normals: the
+ *   cosine for even d, the sine for odd d, both from one block.  A noise counter's first word is below 2^31, the filter's
+ *   draw and the EnKF's are >= 0xFFFFFFF0: the streams never meet, even under equal seeds.
+ *   Vote: the new vector is stored only if every entry is finite; otherwise the member keeps its vector and is counted.
+ *   psi and the refresh rows' one-row vectors are not touched.  The ensemble's mean and variance per node are, in
+ *   expectation, what the resampling left (a^2 + h^2 = 1), and no two members share a field.  With a single survivor
+ *   s_d = 0 and nothing can be restored: hold the ESS up as well (hc_set_filter_tempering).
+ *   The table, float64 [P][n_arow][4] per point and slot: applied (1 / 0); members refused; sqrt(sum_d s_d^2 / D) of the
+ *   resampled vectors; the same of the vectors the move left (two more spread passes).  The last two are summed by one
+ *   thread, nodes ascending, and NaN when not applied; slots without an assimilation hold NaN.
+ * hc_set_filter_rejuvenation: discount = 0 turns it off (the default: nothing is launched or allocated); otherwise finite
+ *   with 0.5 <= discount < 1 (HC_ERR_ARG else), the particle filter on (hc_set_filter first) and not sharded:
+ *   hc_set_filter_shard gathers water-table indices only, the moments would need an exchange of their own, and each of the
+ *   two refuses while the other is set.  Whatever turns the filter off removes it, hc_set_filter included.  Valid with a
+ *   soil-moisture record, tempering, a window, period totals, a sweep and either noise source.
+ * hc_get_filter_rejuvenation: discount and a (0, 0: off).
+ * hc_get/set_filter_rejuvenation_stats: the table (P n_arow 4 entries; checkpoints, the assembly of a sweep over ranks).
+ * Test hooks: hc_get_filter_rejuvenation_moments, the last assimilation's float64 [P][3][D] = mean_d, s_d of the resampled
+ *   vectors and s_d of the vectors the move left (computed whether or not the point was rejuvenated);
+ *   hc_filter_rejuvenation_normals, stateless: eps of the handle's slots first_member ... first_member + count - 1 at
+ *   forcing row `row`, out [count][D] (the filter on; the draws themselves are never stored). */
+int hc_set_filter_rejuvenation(hc_handle *h, double discount);
+int hc_get_filter_rejuvenation(hc_handle *h, double *discount, double *shrinkage);
+int hc_get_filter_rejuvenation_stats(hc_handle *h, double *table, int64_t n_entries);
+int hc_set_filter_rejuvenation_stats(hc_handle *h, const double *table, int64_t n_entries);
+int hc_get_filter_rejuvenation_moments(hc_handle *h, double *moments);
+int hc_filter_rejuvenation_normals(hc_handle *h, int64_t row, int64_t first_member, int64_t count, double *out);
 
 /* Soil-moisture sensors in the particle filter: a record of volumetric water content at up to 8 depth nodes joins the well
  * in the weights, which then belong to a member and not to a bin.  values [n_forcing_rows][n_sensors], NaN = no observation

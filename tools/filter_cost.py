@@ -3,7 +3,7 @@ assimilations every 48th row (one a day), one handle each, back to back on one G
 
     python tools/filter_cost.py [--members 262144] [--depth 300] [--days 30] [--warmup 1] [--strides 0,48]
                                 [--sigma 10] [--spread-cm 0] [--sensors 0,0] [--ess-floor 0,0.5] [--window 0,1]
-                                [--window-offsets 12,24,36] [--json out.json]
+                                [--window-offsets 12,24,36] [--rejuvenation 0.95] [--json out.json]
 
 Same set-up as tools/wtd_dist_cost.py and bench.py's timed region: synthetic 10-year forcing, Philox noise, the shared
 initial condition of the well's digest (tests/golden/g1_tables_<depth>.npz where it exists, else the hydrostatic profile),
@@ -21,7 +21,10 @@ of the tempered weights (hc_set_filter_tempering; 0 = off, the untempered path):
 timed assimilations, and -- when no run has stride 0 -- `kept` and `temper_ms_per_assimilation` are taken against the
 mean of the runs with floor 0.  --window lists, run by run, whether the well's record inside the window joins the weights
 (hc_set_filter_window with --window-offsets; 1 = on): `lagged_per_assimilation`, and -- when no run has stride 0 and no
-floor is set -- `kept` and `window_ms_per_assimilation` against the mean of the runs without a window.  Prints one JSON line.
+floor is set -- `kept` and `window_ms_per_assimilation` against the mean of the runs without a window.  --rejuvenation
+delta rejuvenates the base noise vectors of every filtered run (hc_set_filter_rejuvenation; 0 = off): `rejuvenated_rows`
+and `spread_kept` (the mean of the table's entry 3 over entry 2) over the timed assimilations; its cost is the
+`filter_ms_per_assimilation` of this command against the same command without the flag.  Prints one JSON line.
 """
 import argparse
 import json
@@ -36,7 +39,7 @@ sys.path.insert(0, str(REPO))
 
 
 def run(cols, forcing, psi0, members, stride, sigma, warmup_days, days, spread_cm=0.0, seed=2024, sensors=0,
-        sensor_sigma=0.05, ess_floor=0.0, window=()):
+        sensor_sigma=0.05, ess_floor=0.0, window=(), rejuvenation=0.0):
     from hydromodel_amd.stepper import EnsembleStepper, filter_summary
     st = EnsembleStepper(cols, forcing, members)
     try:
@@ -56,6 +59,8 @@ def run(cols, forcing, psi0, members, stride, sigma, warmup_days, days, spread_c
             st.set_filter_tempering(ess_floor)
         if stride and window:
             st.set_filter_window(window)
+        if stride and rejuvenation:
+            st.set_filter_rejuvenation(rejuvenation)
         row = 1
         if warmup_days:
             st.step_rows(row, 48 * warmup_days)
@@ -66,7 +71,7 @@ def run(cols, forcing, psi0, members, stride, sigma, warmup_days, days, spread_c
         st.lib.hc_synchronize(st.h)
         wall = time.perf_counter() - t0
         rec = {"stride": stride, "sensors": sensors if stride else 0, "ess_floor": ess_floor if stride else 0.0,
-               "window": list(window) if stride else [], "wall_s": wall, "step_kernel_ms": out["kernel_ms"], "launches": out["launches"],
+               "window": list(window) if stride else [], "rejuvenation": rejuvenation if stride else 0.0, "wall_s": wall, "step_kernel_ms": out["kernel_ms"], "launches": out["launches"],
                "other_ms": 1e3 * wall - out["kernel_ms"], "column_days_per_s": members * days / wall}
         if stride:
             s = filter_summary(st.filter_table()[0], stride, sigma)
@@ -82,6 +87,12 @@ def run(cols, forcing, psi0, members, stride, sigma, warmup_days, days, spread_c
             if window:
                 wt = st.filter_window_table()[0, s["rows"] // stride, :, 0][timed]
                 rec["lagged_per_assimilation"] = float((wt == 1.0).sum() / max(int(timed.sum()), 1))
+            if rejuvenation:
+                rt = st.filter_rejuvenation_table()[0, s["rows"] // stride][timed]
+                moved = rt[:, 0] == 1.0
+                rec["rejuvenated_rows"] = int(moved.sum())
+                rec["rejuvenation_refused"] = int(np.nansum(rt[:, 1]))
+                rec["spread_kept"] = float((rt[moved, 3] / rt[moved, 2]).mean()) if moved.any() else None
             if timed.any():
                 rec["longest_range"] = int(np.bincount(st.filter_ancestors(), minlength=members).max())   # the last one
         return rec
@@ -104,6 +115,7 @@ def main():
     ap.add_argument("--ess-floor", default="")
     ap.add_argument("--window", default="")
     ap.add_argument("--window-offsets", default="12,24,36")
+    ap.add_argument("--rejuvenation", type=float, default=0.0)
     ap.add_argument("--json", default="")
     args = ap.parse_args()
     from hydromodel_amd.digest import ColumnTables, ForcingDigest
@@ -128,7 +140,7 @@ def main():
     if len(windows) != len(strides):
         ap.error("--window lists one flag per entry of --strides")
     recs = [run(cols, forcing, psi0, args.members, s, args.sigma, args.warmup, args.days, args.spread_cm, sensors=n,
-                sensor_sigma=args.sensor_sigma, ess_floor=f, window=w)
+                sensor_sigma=args.sensor_sigma, ess_floor=f, window=w, rejuvenation=args.rejuvenation)
             for s, n, f, w in zip(strides, sensors, floors, windows)]
     base = [r for r in recs if r["stride"] == 0]
     if base:
