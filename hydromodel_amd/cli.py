@@ -190,7 +190,9 @@ unknown keys, only membership of the 12 is checked):
    instead of raising the reference's ``TypeError``.
 """
 import sys
+from dataclasses import dataclass
 from pathlib import Path
+from typing import Optional
 
 REQUIRED_KEYS = ("Trees", "Well_No", "Output_Name", "IC_Filename",
                  "Data_Filename", "Water_Content", "Environmental",
@@ -329,6 +331,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     record = soil_moisture_record_of(sm, cols, water_data)      # before any GPU call
     storage_ranges(storage, cols)                               # (its refusals too)
     frecord = soil_moisture_record_of(fsm, cols, water_data, "Filter")
+    assim = Assimilation(filt, frecord, ess_floor, fwindow, rejuvenation, enkf, record, scheme, window, noise_alpha)
     if cols.flags["PREDICT"] and not ens.get("repair_predict"):
         raise TypeError("'numpy.float64' object cannot be interpreted as an integer")     # richards_pde.py:327-330
     n_members = int(ens.get("Members", 4096))
@@ -336,9 +339,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     rows = min(days * 48, forcing.dim_t - 1)
     plan = period_plan(periods, cols, forcing, rows)            # before any GPU call, like the storage's ranges
     if ens.get("Points"):
-        return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels, filt,
-                          enkf, record, scheme, window, frecord, theta, storage, periods, plan, ess_floor, fwindow,
-                          noise_alpha, rejuvenation)
+        return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels, assim,
+                          theta, storage, periods, plan)
     sharded = enkf_sharded(ens)
     fsharded = filter_sharded(ens)
     if sharded:
@@ -359,10 +361,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     sim = EnsembleSimulation(cols, forcing, hi - lo, seed=int(ens.get("Seed", 0)), device=device, member_offset=lo,
                              noise=str(ens.get("Noise", "philox")).lower(),
                              spinup=str(ens.get("Spinup", "shared")).lower(), profile_stride=stride,
-                             wtd_hist_stride=dist_stride, theta_hist_bins=theta[0],
-                             **_filter_kwargs(filt, frecord, ess_floor, fwindow, rejuvenation),
-                             **_enkf_kwargs(enkf, record, scheme, window, noise_alpha), **_storage_kwargs(storage),
-                             **_period_kwargs(periods, plan), **shard_kw)
+                             wtd_hist_stride=dist_stride, theta_hist_bins=theta[0], **assim.kwargs(),
+                             **_storage_kwargs(storage), **_period_kwargs(periods, plan), **shard_kw)
     label = f"Ensemble x{n_members}"
     _step_all(sim, rows, label, ranks)
     # the run's one collective: int64 (count, sum idx, sum idx^2) per row, exact and order-independent
@@ -400,57 +400,102 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     # the filters' tables describe the one point: every rank of a sharded run holds the same ones, and rank 0's are taken
     # (placed by it alone; a sum over the ranks would count them world times)
     eids = [0] if ranks.rank == 0 else []
-    ftables, filter_line = _reduce_filter(ranks, sim, eids, 1, forcing.dim_t, filt, label, keep_points=False,
-                                          ess_floor=ess_floor, rejuvenation=rejuvenation)
-    extra.update(ftables)
-    fstables, fsm_line = _reduce_sm(ranks, sim, eids, 1, forcing.dim_t, filt[0], frecord, label, keep_points=False,
-                                    owner="filter")
-    extra.update(fstables)
-    fwtables, fwindow_line = _reduce_filter_window(ranks, sim, eids, 1, forcing.dim_t, filt, fwindow, label,
-                                                   keep_points=False, z0_cm=cols.z[0])
-    extra.update(fwtables)
+    atables, assim_lines = _reduce_assimilation(ranks, sim, eids, 1, forcing.dim_t, cols, assim, label, keep_points=False)
+    extra.update(atables)
     if fsharded is not None:
         extra["filter_sharded"] = np.array(1 if fsharded else 0, dtype=np.int8)
-    etables, enkf_line = _reduce_enkf(ranks, sim, eids, 1, forcing.dim_t, enkf, label, keep_points=False,
-                                         z0_cm=cols.z[0])
-    extra.update(etables)
-    extra.update(_enkf_method_arrays(enkf, scheme))
     if sharded is not None:
         extra["enkf_sharded"] = np.array(1 if sharded else 0, dtype=np.int8)
-    stables, sm_line = _reduce_sm(ranks, sim, eids, 1, forcing.dim_t, enkf[0], record, label, keep_points=False)
-    extra.update(stables)
-    wtables, window_line = _reduce_enkf_window(ranks, sim, eids, 1, forcing.dim_t, enkf, window, label, keep_points=False,
-                                               z0_cm=cols.z[0])
-    extra.update(wtables)
-    ntables, noise_line = _reduce_enkf_noise(ranks, sim, eids, 1, forcing.dim_t, cols.dim_d, enkf, noise_alpha, label,
-                                             keep_points=False)
-    extra.update(ntables)
     arrays = dict(moments=moments, wtd_mean_cm=mean_cm, wtd_std_cm=std_cm, rows=np.array(rows),
                   members=np.array(n_members), gpus=np.array(ranks.world), initial_cond=psi0, **extra)
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "ensemble water-table statistics", ranks)
-    if crps_line:
-        print(crps_line)
-    if filter_line:
-        print(filter_line)
-    if fsm_line:
-        print(fsm_line)
-    if fwindow_line:
-        print(fwindow_line)
-    if enkf_line:
-        print(enkf_line)
-    if sm_line:
-        print(sm_line)
-    if window_line:
-        print(window_line)
-    if noise_line:
-        print(noise_line)
-    if theta_line:
-        print(theta_line)
-    if storage_line:
-        print(storage_line)
-    if period_line:
-        print(period_line)
+    _print_lines(crps_line, *assim_lines, theta_line, storage_line, period_line)
     sim.close()
+
+
+def _print_lines(*lines):
+    """The run's closing lines, those that are there, in the order given."""
+    for line in lines:
+        if line:
+            print(line)
+
+
+@dataclass(frozen=True)
+class Assimilation:
+    """The assimilation settings of a run as the settings functions return them (``filter_settings``,
+    ``soil_moisture_record_of`` ... in the field order below; None / a zero stride: not given), from ``_run_ensemble`` to
+    the simulation's constructor and the reducers."""
+    filt: tuple = (0, None, None)
+    frecord: Optional[dict] = None
+    ess_floor: Optional[float] = None
+    fwindow: Optional[tuple] = None
+    rejuvenation: Optional[float] = None
+    enkf: tuple = (0, None, None, None)
+    record: Optional[dict] = None
+    scheme: Optional[tuple] = None
+    window: Optional[tuple] = None
+    noise_alpha: Optional[float] = None
+
+    def kwargs(self):
+        """The ``filter_*`` / ``enkf_*`` keywords of EnsembleSimulation / SweepSimulation: an owner that is off and an
+        option that was not given pass nothing."""
+        kw = {}
+        if self.filt[0]:
+            kw.update(filter_stride=self.filt[0], filter_sigma_cm=self.filt[1], filter_seed=self.filt[2])
+            given = dict(filter_soil_moisture=self.frecord, filter_ess_floor=self.ess_floor,
+                         filter_window_offsets=self.fwindow or None, filter_rejuvenation=self.rejuvenation)
+            kw.update((k, v) for k, v in given.items() if v is not None)
+        if self.enkf[0]:
+            kw.update(enkf_stride=self.enkf[0], enkf_sigma_cm=self.enkf[1], enkf_localisation_cm=self.enkf[2],
+                      enkf_seed=self.enkf[3])
+            given = dict(enkf_soil_moisture=self.record, enkf_window_offsets=self.window or None,
+                         enkf_noise_field=None if self.noise_alpha is None else {"relaxation": self.noise_alpha})
+            kw.update((k, v) for k, v in given.items() if v is not None)
+            if self.scheme is not None:
+                kw.update(enkf_method=self.scheme[0], enkf_relaxation=self.scheme[1])
+        return kw
+
+
+def _placed_table(ranks, sim, ids, P, T, D, stride, key, n=0):
+    """The assimilation table ``key`` (stepper.ASSIM_TABLES) of the run's ``P`` points: this rank's handle ``sim`` (None:
+    it holds no points) gives its points ``ids``, placed in the [P][n_arow] + trailing table and summed over the ranks
+    (float64 as int64 bits: ``multigpu.place_points``) -- one collective.  ``n``: the owner's sensors or offsets, for the
+    tables that have them."""
+    import numpy as np
+    from .multigpu import place_points
+    from .stepper import assim_table_shape, stride_rows
+    shape = (stride_rows(T, stride),) + assim_table_shape(key, D, n, n)
+    local = sim.assim_table(key).reshape((-1,) + shape) if sim is not None else np.zeros((0,) + shape)
+    return place_points(local, ids, P, ranks)
+
+
+def _reduce_assimilation(ranks, sim, ids, P, T, cols, a, label, keep_points):
+    """The datasets and the closing lines of the particle filter and the EnKF (``a``: the run's :class:`Assimilation`),
+    owner by owner: its own table placed once, the slots it assimilated taken from that, then its sensors', its
+    window's and the noise field's tables, one collective each.  Every rank takes the same path."""
+    import numpy as np
+    where = (ranks, sim, ids, P, T, cols.dim_d)
+    out, lines = {}, []
+    for owner, settings in (("filter", a.filt), ("enkf", a.enkf)):
+        stride = settings[0]
+        if not stride:
+            continue
+        table = _placed_table(*where, stride, owner)
+        slots = np.flatnonzero((table[..., 0] > 0).any(axis=0))         # the owner's filter_rows / enkf_rows
+        if owner == "filter":
+            parts = [_reduce_filter(*where, table, a, label, keep_points),
+                     _reduce_sm(*where, stride, a.frecord, slots, label, keep_points, owner),
+                     _reduce_window(*where, stride, a.fwindow, slots, label, keep_points, cols.z[0], owner)]
+        else:
+            parts = [_reduce_enkf(ranks, table, a.enkf, label, keep_points, cols.z[0]),
+                     (_enkf_method_arrays(a.enkf, a.scheme), None),
+                     _reduce_sm(*where, stride, a.record, slots, label, keep_points, owner),
+                     _reduce_window(*where, stride, a.window, slots, label, keep_points, cols.z[0], owner),
+                     _reduce_enkf_noise(*where, a.enkf, a.noise_alpha, label, keep_points)]
+        for datasets, line in parts:
+            out.update(datasets)
+            lines.append(line)
+    return out, lines
 
 
 DEFAULT_QUANTILES = (0.05, 0.25, 0.5, 0.75, 0.95)
@@ -818,34 +863,6 @@ def filter_window_settings(ens):
     return off
 
 
-def _reduce_filter_window(ranks, sim, ids, P, T, filt, window, label, keep_points, z0_cm):
-    """The window's datasets from this rank's handle over the filter's assimilated rows (its ``filter_rows``), the [P]
-    table placed and summed over the ranks like the filter's (float64 as int64 bits), and the closing line (rank 0)."""
-    import numpy as np
-    from .multigpu import place_points
-    from .stepper import WINDOW_WIDTH, stride_rows
-    stride = filt[0]
-    if not stride or not window:
-        return {}, None
-    n, n_arow = len(window), stride_rows(T, stride)
-    local = (sim.filter_window_table().reshape(-1, n_arow, n, WINDOW_WIDTH) if sim is not None
-             else np.zeros((0, n_arow, n, WINDOW_WIDTH)))
-    table = place_points(local, ids, P, ranks)
-    ftab = sim.filter_table().reshape(-1, n_arow, 4) if sim is not None else np.zeros((0, n_arow, 4))
-    used = place_points(ftab, ids, P, ranks)[..., 0] > 0
-    slots = np.flatnonzero(used.any(axis=0))               # the filter_rows of _reduce_filter
-    sel = table[:, slots] if keep_points else table[0, slots]
-    observed = sel[..., 0] == 1.0
-    out = {"filter_window_offsets": np.asarray(window, dtype=np.int64), "filter_window_observed": observed.astype(np.int8),
-           "filter_window_obs_cm": sel[..., 1] + float(z0_cm), "filter_window_prior_mean_cm": sel[..., 2] + float(z0_cm),
-           "filter_window_prior_std_cm": sel[..., 3]}
-    if ranks.rank != 0:
-        return out, None
-    first = table[0, slots, :, 0] == 1.0                   # the record is the same for every point
-    line = f" [{label}] filter window: {int(first.sum())} lagged observations over {int(first.any(axis=-1).sum())} rows"
-    return out, line
-
-
 def filter_sharded(ens):
     """Ensemble.Filter.Sharded -> True / False, or None when the key is not given (or the filter is off).  With true a
     single-point ensemble's members are dealt to the GPUs, every assimilation gathers their water-table indices and the
@@ -977,14 +994,11 @@ def _reduce_enkf_noise(ranks, sim, ids, P, T, D, enkf, noise_alpha, label, keep_
     """The noise field's datasets from this rank's handle over the EnKF's analysed rows (its ``enkf_rows``), the [P]
     table placed and summed over the ranks like the EnKF's (float64 as int64 bits), and the closing line (rank 0)."""
     import numpy as np
-    from .multigpu import place_points
-    from .stepper import enkf_noise_summary, stride_rows
+    from .stepper import enkf_noise_summary
     stride = enkf[0]
     if not stride or noise_alpha is None:
         return {}, None
-    n_arow, width = stride_rows(T, stride), 4 * D + 1
-    local = sim.enkf_noise_table().reshape(-1, n_arow, width) if sim is not None else np.zeros((0, n_arow, width))
-    table = place_points(local, ids, P, ranks)
+    table = _placed_table(ranks, sim, ids, P, T, D, stride, "enkf_noise")
     summary = enkf_noise_summary(table if keep_points else table[0], stride, noise_alpha, D)
     out = {"enkf_noise_field": np.array(1, dtype=np.int8), "enkf_noise_relaxation": np.array(noise_alpha, dtype=np.float64)}
     out.update(("enkf_" + k, summary[k]) for k in ("noise_prior_mean", "noise_prior_std", "noise_post_mean",
@@ -1028,49 +1042,28 @@ def _window_settings(ens, owner):
     return off or None
 
 
-def _reduce_enkf_window(ranks, sim, ids, P, T, enkf, window, label, keep_points, z0_cm):
-    """The window's datasets from this rank's handle over the EnKF's analysed rows (its ``enkf_rows``), the [P] table
-    placed and summed over the ranks like the EnKF's (float64 as int64 bits), and the closing line (rank 0)."""
+def _reduce_window(ranks, sim, ids, P, T, D, stride, window, slots, label, keep_points, z0_cm, owner):
+    """The window's datasets (``owner``: "enkf" or "filter", the prefix of the datasets and of the handle's table) from
+    this rank's handle over the owner's assimilated ``slots`` (its ``enkf_rows`` / ``filter_rows``), the [P] table placed
+    and summed over the ranks like the owner's, and the closing line (rank 0).  The EnKF's has the innovation too."""
     import numpy as np
-    from .multigpu import place_points
-    from .stepper import ENKF_WIDTH, WINDOW_WIDTH, stride_rows
-    stride = enkf[0]
     if not stride or not window:
         return {}, None
-    n, n_arow = len(window), stride_rows(T, stride)
-    local = (sim.enkf_window_table().reshape(-1, n_arow, n, WINDOW_WIDTH) if sim is not None
-             else np.zeros((0, n_arow, n, WINDOW_WIDTH)))
-    table = place_points(local, ids, P, ranks)
-    etab = sim.enkf_table().reshape(-1, n_arow, ENKF_WIDTH) if sim is not None else np.zeros((0, n_arow, ENKF_WIDTH))
-    used = place_points(etab, ids, P, ranks)[..., 0] > 0
-    slots = np.flatnonzero(used.any(axis=0))               # the enkf_rows of _reduce_enkf
+    table = _placed_table(ranks, sim, ids, P, T, D, stride, owner + "_window", len(window))
     sel = table[:, slots] if keep_points else table[0, slots]
     observed = sel[..., 0] == 1.0
-    out = {"enkf_window_offsets": np.asarray(window, dtype=np.int64), "enkf_window_observed": observed.astype(np.int8),
-           "enkf_window_obs_cm": sel[..., 1] + float(z0_cm), "enkf_window_prior_mean_cm": sel[..., 2] + float(z0_cm),
-           "enkf_window_prior_std_cm": sel[..., 3], "enkf_window_innovation_cm": sel[..., 1] - sel[..., 2]}
+    out = {f"{owner}_window_offsets": np.asarray(window, dtype=np.int64),
+           f"{owner}_window_observed": observed.astype(np.int8), f"{owner}_window_obs_cm": sel[..., 1] + float(z0_cm),
+           f"{owner}_window_prior_mean_cm": sel[..., 2] + float(z0_cm), f"{owner}_window_prior_std_cm": sel[..., 3]}
+    if owner == "enkf":
+        out["enkf_window_innovation_cm"] = sel[..., 1] - sel[..., 2]
     if ranks.rank != 0:
         return out, None
     first = table[0, slots, :, 0] == 1.0                   # the record is the same for every point
-    line = (f" [{label}] EnKF window: {int(first.sum())} lagged observations over {int(first.any(axis=-1).sum())} rows "
-            f"(offsets {list(window)})")
-    return out, line
-
-
-def _enkf_kwargs(enkf, record=None, scheme=None, window=None, noise_alpha=None):
-    stride, sigma, loc, seed = enkf
-    if not stride:
-        return {}
-    kw = dict(enkf_stride=stride, enkf_sigma_cm=sigma, enkf_localisation_cm=loc, enkf_seed=seed)
-    if record is not None:
-        kw["enkf_soil_moisture"] = record
-    if scheme is not None:
-        kw.update(enkf_method=scheme[0], enkf_relaxation=scheme[1])
-    if window:
-        kw["enkf_window_offsets"] = window
-    if noise_alpha is not None:
-        kw["enkf_noise_field"] = {"relaxation": noise_alpha}
-    return kw
+    line = f"{int(first.sum())} lagged observations over {int(first.any(axis=-1).sum())} rows"
+    if owner == "enkf":
+        return out, f" [{label}] EnKF window: {line} (offsets {list(window)})"
+    return out, f" [{label}] filter window: {line}"
 
 
 def _enkf_method_arrays(enkf, scheme):
@@ -1194,24 +1187,15 @@ def soil_moisture_record_of(sm, cols, water_data, owner="EnKF"):
 SM_DATASETS = ("observed", "obs", "prior_mean", "prior_std", "post_mean", "post_std")
 
 
-def _reduce_sm(ranks, sim, ids, P, T, stride, record, label, keep_points, owner="enkf"):
-    """The sensors' datasets (``owner``: "enkf" or "filter", the prefix of the datasets and of the handle's tables) from
-    this rank's handle over the owner's assimilated rows (its ``enkf_rows`` / ``filter_rows``), the [P] table placed and
-    summed over the ranks like the owner's (float64 as int64 bits), and the closing line (rank 0)."""
+def _reduce_sm(ranks, sim, ids, P, T, D, stride, record, slots, label, keep_points, owner="enkf"):
+    """The sensors' datasets (``owner``: "enkf" or "filter", the prefix of the datasets and of the handle's table) from
+    this rank's handle over the owner's assimilated ``slots`` (its ``enkf_rows`` / ``filter_rows``), the [P] table placed
+    and summed over the ranks like the owner's, and the closing line (rank 0)."""
     import numpy as np
-    from .multigpu import place_points
-    from .stepper import ENKF_WIDTH, SM_WIDTH, enkf_sm_summary, stride_rows
+    from .stepper import enkf_sm_summary
     if not stride or record is None:
         return {}, None
-    n = int(np.asarray(record["nodes"]).size)
-    n_arow = stride_rows(T, stride)
-    width = ENKF_WIDTH if owner == "enkf" else 4
-    local = (getattr(sim, owner + "_sm_table")().reshape(-1, n_arow, n, SM_WIDTH) if sim is not None
-             else np.zeros((0, n_arow, n, SM_WIDTH)))
-    table = place_points(local, ids, P, ranks)
-    etab = getattr(sim, owner + "_table")().reshape(-1, n_arow, width) if sim is not None else np.zeros((0, n_arow, width))
-    used = place_points(etab, ids, P, ranks)[..., 0] > 0
-    slots = np.flatnonzero(used.any(axis=0))               # the enkf_rows of _reduce_enkf, the filter_rows of _reduce_filter
+    table = _placed_table(ranks, sim, ids, P, T, D, stride, owner + "_sm", int(np.asarray(record["nodes"]).size))
     sel = table[:, slots] if keep_points else table[0, slots]
     out = {f"{owner}_sm_depths_cm": np.asarray(record["depths_cm"], dtype=np.float64),
            f"{owner}_sm_nodes": np.asarray(record["nodes"], dtype=np.int32),
@@ -1232,19 +1216,12 @@ def _reduce_sm(ranks, sim, ids, P, T, stride, record, label, keep_points, owner=
     return out, line
 
 
-def _reduce_enkf(ranks, sim, ids, P, T, enkf, label, keep_points, z0_cm):
-    """The EnKF's datasets from this rank's handle ``sim`` (None: no points), its points ``ids`` placed in the run's [P]
-    table and summed over the ranks (float64 as int64 bits: ``multigpu.place_points``), and the closing line (rank 0).
-    The means are given at the well's depths (``z0_cm`` = z[0] + the table's depths from the top node)."""
+def _reduce_enkf(ranks, table, enkf, label, keep_points, z0_cm):
+    """The EnKF's datasets from its placed [P] ``table`` (:func:`_placed_table`) and the closing line (rank 0).  The
+    means are given at the well's depths (``z0_cm`` = z[0] + the table's depths from the top node)."""
     import numpy as np
-    from .multigpu import place_points
-    from .stepper import ENKF_WIDTH, enkf_summary, stride_rows
+    from .stepper import enkf_summary
     stride, sigma, loc, _ = enkf
-    if not stride:
-        return {}, None
-    n_arow = stride_rows(T, stride)
-    local = sim.enkf_table().reshape(-1, n_arow, ENKF_WIDTH) if sim is not None else np.zeros((0, n_arow, ENKF_WIDTH))
-    table = place_points(local, ids, P, ranks)
     summary = enkf_summary(table if keep_points else table[0], stride, sigma, float(z0_cm))
     out = {f"enkf_{k}": summary[k] for k in ("rows", "count", "prior_mean_cm", "prior_std_cm", "innovation_cm",
                                              "post_mean_cm", "post_std_cm", "loglik_rows", "rejected")}
@@ -1262,45 +1239,19 @@ def _reduce_enkf(ranks, sim, ids, P, T, enkf, label, keep_points, z0_cm):
     return out, line
 
 
-def _filter_kwargs(filt, record=None, ess_floor=None, window=None, rejuvenation=None):
-    stride, sigma, seed = filt
-    if not stride:
-        return {}
-    kw = dict(filter_stride=stride, filter_sigma_cm=sigma, filter_seed=seed)
-    if record is not None:
-        kw["filter_soil_moisture"] = record
-    if ess_floor is not None:
-        kw["filter_ess_floor"] = ess_floor
-    if window:
-        kw["filter_window_offsets"] = window
-    if rejuvenation is not None:
-        kw["filter_rejuvenation"] = rejuvenation
-    return kw
-
-
-def _reduce_filter(ranks, sim, ids, P, T, filt, label, keep_points, ess_floor=None, rejuvenation=None):
-    """The filter's datasets from this rank's handle ``sim`` (None: no points), its points ``ids`` placed in the run's [P]
-    table and summed over the ranks (float64 as int64 bits: ``multigpu.place_points``), and the closing line (rank 0).
-    ``ess_floor`` (Filter.ESS_floor): the tempering's table likewise, its datasets and a second closing line;
-    ``rejuvenation`` (Filter.Rejuvenation): the rejuvenation's, and a line of its own."""
+def _reduce_filter(ranks, sim, ids, P, T, D, table, a, label, keep_points):
+    """The filter's datasets from its placed [P] ``table`` (:func:`_placed_table`) and the closing line (rank 0).
+    ``a.ess_floor`` (Filter.ESS_floor): the tempering's table placed likewise, its datasets and a second closing line;
+    ``a.rejuvenation`` (Filter.Rejuvenation): the rejuvenation's, and a line of its own."""
     import numpy as np
-    from .multigpu import place_points
-    from .stepper import filter_summary, rejuvenation_shrinkage, stride_rows
-    stride, sigma, _ = filt
-    if not stride:
-        return {}, None
-    n_arow = stride_rows(T, stride)
-    local = sim.filter_table().reshape(-1, n_arow, 4) if sim is not None else np.zeros((0, n_arow, 4))
-    table = place_points(local, ids, P, ranks)
-    ttable = None
+    from .stepper import filter_summary, rejuvenation_shrinkage
+    (stride, sigma, _), ess_floor, rejuvenation = a.filt, a.ess_floor, a.rejuvenation
+    ttable = rtable = None
     if ess_floor is not None:
-        tlocal = sim.filter_temper_table().reshape(-1, n_arow, 4) if sim is not None else np.zeros((0, n_arow, 4))
-        ttable = place_points(tlocal, ids, P, ranks)
+        ttable = _placed_table(ranks, sim, ids, P, T, D, stride, "filter_temper")
         ttable = ttable if keep_points else ttable[0]
-    rtable = None
     if rejuvenation is not None:
-        rlocal = sim.filter_rejuvenation_table().reshape(-1, n_arow, 4) if sim is not None else np.zeros((0, n_arow, 4))
-        rtable = place_points(rlocal, ids, P, ranks)
+        rtable = _placed_table(ranks, sim, ids, P, T, D, stride, "filter_rejuvenation")
         rtable = rtable if keep_points else rtable[0]
     summary = filter_summary(table if keep_points else table[0], stride, sigma, temper_table=ttable,
                              rejuvenation_table=rtable)
@@ -1572,9 +1523,7 @@ def _reduce_periods(ranks, sim, ids, P, cols, forcing, periods, plan, label, kee
 
 
 def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride=0, dist_levels=None,
-               filt=(0, None, None), enkf=(0, None, None, None), record=None, scheme=None, window=None, frecord=None,
-               theta=(0, None), storage=None, periods=None, plan=None, ess_floor=None, fwindow=None, noise_alpha=None,
-               rejuvenation=None):
+               assim=Assimilation(), theta=(0, None), storage=None, periods=None, plan=None):
     """Parameter points x members: this rank's points in one handle (ensemble.SweepSimulation), the whole table assembled
     over the ranks (multigpu.assemble_points)."""
     import numpy as np
@@ -1601,9 +1550,7 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     if mine:
         sim = SweepSimulation(points, forcing, n_members, seed=int(ens.get("Seed", 0)), device=device, point_ids=mine,
                               profile_stride=stride, wtd_hist_stride=dist_stride, theta_hist_bins=theta[0],
-                              **_filter_kwargs(filt, frecord, ess_floor, fwindow, rejuvenation),
-                              **_enkf_kwargs(enkf, record, scheme, window, noise_alpha),
-                              **_storage_kwargs(storage), **_period_kwargs(periods, plan))
+                              **assim.kwargs(), **_storage_kwargs(storage), **_period_kwargs(periods, plan))
         _step_all(sim, rows, label, ranks)
         table = sim.moments()
         for j, k in enumerate(mine):
@@ -1623,50 +1570,12 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     arrays.update(stor_tables)
     ptables, period_line = _reduce_periods(ranks, sim, mine, P, ref, forcing, periods, plan, label, keep_points=True)
     arrays.update(ptables)
-    ftables, filter_line = _reduce_filter(ranks, sim, mine, P, T, filt, label, keep_points=True, ess_floor=ess_floor,
-                                          rejuvenation=rejuvenation)
-    arrays.update(ftables)
-    fstables, fsm_line = _reduce_sm(ranks, sim, mine, P, T, filt[0], frecord, label, keep_points=True, owner="filter")
-    arrays.update(fstables)
-    fwtables, fwindow_line = _reduce_filter_window(ranks, sim, mine, P, T, filt, fwindow, label, keep_points=True,
-                                                   z0_cm=cols_all[0].z[0])
-    arrays.update(fwtables)
-    etables, enkf_line = _reduce_enkf(ranks, sim, mine, P, T, enkf, label, keep_points=True,
-                                         z0_cm=cols_all[0].z[0])
-    arrays.update(etables)
-    stables, sm_line = _reduce_sm(ranks, sim, mine, P, T, enkf[0], record, label, keep_points=True)
-    arrays.update(stables)
-    arrays.update(_enkf_method_arrays(enkf, scheme))
-    wtables, window_line = _reduce_enkf_window(ranks, sim, mine, P, T, enkf, window, label, keep_points=True,
-                                               z0_cm=cols_all[0].z[0])
-    arrays.update(wtables)
-    ntables, noise_line = _reduce_enkf_noise(ranks, sim, mine, P, T, ref.dim_d, enkf, noise_alpha, label, keep_points=True)
-    arrays.update(ntables)
+    atables, assim_lines = _reduce_assimilation(ranks, sim, mine, P, T, ref, assim, label, keep_points=True)
+    arrays.update(atables)
     if sim is not None:
         sim.close()
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "sweep's water-table statistics", ranks)
-    if crps_line:
-        print(crps_line)
-    if filter_line:
-        print(filter_line)
-    if fsm_line:
-        print(fsm_line)
-    if fwindow_line:
-        print(fwindow_line)
-    if enkf_line:
-        print(enkf_line)
-    if sm_line:
-        print(sm_line)
-    if window_line:
-        print(window_line)
-    if noise_line:
-        print(noise_line)
-    if theta_line:
-        print(theta_line)
-    if storage_line:
-        print(storage_line)
-    if period_line:
-        print(period_line)
+    _print_lines(crps_line, *assim_lines, theta_line, storage_line, period_line)
 
 
 def run_cli(argv=None):

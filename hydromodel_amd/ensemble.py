@@ -10,7 +10,7 @@ import numpy as np
 
 from .digest import inverse_retention
 from .stepper import enkf_noise_summary, noise_field_settings
-from .stepper import (ENKF_METHODS, ENKF_WIDTH, SM_WIDTH, WINDOW_WIDTH, EnsembleStepper, enkf_sm_summary, enkf_summary,
+from .stepper import (ASSIM_TABLES, ENKF_METHODS, EnsembleStepper, enkf_sm_summary, enkf_summary,
                       enkf_window_settings, enkf_window_summary, filter_sm_summary, filter_summary,
                       filter_window_settings, filter_window_summary, rejuvenation_discount,
                       flux_max_log2_of, layer_ranges, layer_storage_distribution, moments_to_mean_std, period_totals_distribution,
@@ -231,9 +231,24 @@ class _Run:
                 raise ValueError("enkf_noise_field needs the EnKF (enkf_stride > 0)")
             self.stepper.set_enkf_noise_field(True, self.enkf_noise_relaxation)
 
+    def assim_table(self, key):
+        """The handle's assimilation table ``key`` (stepper.ASSIM_TABLES): [n_arow] + its trailing shape, a sweep:
+        [P][n_arow] + ...  The named accessors below document each table."""
+        t = self.stepper.assim_table(key)
+        return t.reshape(self._lead + t.shape[1:])
+
+    def assim_tables_on(self):
+        """The keys of stepper.ASSIM_TABLES this run keeps, in the registry's order: what a checkpoint carries."""
+        on = {"filter": bool(self.filter_stride), "filter_sm": self.filter_soil_moisture is not None,
+              "filter_temper": bool(self.filter_ess_floor), "filter_rejuvenation": bool(self.filter_rejuvenation),
+              "filter_window": bool(self.filter_window_offsets), "enkf": bool(self.enkf_stride),
+              "enkf_sm": self.enkf_soil_moisture is not None, "enkf_window": bool(self.enkf_window_offsets),
+              "enkf_noise": self.enkf_noise_relaxation is not None}
+        return [key for key in ASSIM_TABLES if on[key]]
+
     def enkf_noise_table(self):
         """[n_arow][4 D + 1] float64 (include/hydrocol.h hc_set_enkf_noise_field); a sweep: [P][n_arow][4 D + 1]."""
-        return self.stepper.enkf_noise_table().reshape(self._lead + (-1, 4 * self.cols.dim_d + 1))
+        return self.assim_table("enkf_noise")
 
     def enkf_noise_summary(self, table=None):
         """stepper.enkf_noise_summary of the noise field's table (``table``: e.g. the one assembled over ranks)."""
@@ -349,17 +364,17 @@ class _Run:
 
     def filter_table(self):
         """[n_arow][4] float64 (count, ESS, log-likelihood increment, survivors per assimilation slot); a sweep: [P][n_arow][4]."""
-        return self.stepper.filter_table().reshape(self._lead + (-1, 4))
+        return self.assim_table("filter")
 
     def filter_temper_table(self):
         """[n_arow][4] float64 (beta, the ESS at beta, the target, the trials; include/hydrocol.h
         hc_set_filter_tempering); a sweep: [P][n_arow][4]."""
-        return self.stepper.filter_temper_table().reshape(self._lead + (-1, 4))
+        return self.assim_table("filter_temper")
 
     def filter_rejuvenation_table(self):
         """[n_arow][4] float64 (applied, members refused, the base vectors' spread before and after the move;
         include/hydrocol.h hc_set_filter_rejuvenation); a sweep: [P][n_arow][4]."""
-        return self.stepper.filter_rejuvenation_table().reshape(self._lead + (-1, 4))
+        return self.assim_table("filter_rejuvenation")
 
     def filter_summary(self, table=None, sm_table=None, temper_table=None, window_table=None, rejuvenation_table=None):
         """The filter's record (stepper.filter_summary): ``rows``, ``count``, ``ess``, ``loglik_rows``, ``survivors`` over
@@ -384,7 +399,7 @@ class _Run:
 
     def filter_window_table(self):
         """[n_arow][n][4] float64 (include/hydrocol.h hc_set_filter_window); a sweep: [P][n_arow][n][4]."""
-        return self.stepper.filter_window_table().reshape(self._lead + (-1, len(self.filter_window_offsets), WINDOW_WIDTH))
+        return self.assim_table("filter_window")
 
     def filter_window_summary(self, table=None):
         """stepper.filter_window_summary of the window's table (``table``: e.g. the one assembled over ranks): per
@@ -395,7 +410,7 @@ class _Run:
 
     def filter_sm_table(self):
         """[n_arow][n][6] float64 (include/hydrocol.h hc_set_filter_soil_moisture); a sweep: [P][n_arow][n][6]."""
-        return self.stepper.filter_sm_table().reshape(self._lead + (-1, self.stepper.filter_sm_n, SM_WIDTH))
+        return self.assim_table("filter_sm")
 
     def filter_sm_summary(self, table=None):
         """stepper.filter_sm_summary of the filter's sensor table (``table``: e.g. the one assembled over ranks)."""
@@ -404,7 +419,7 @@ class _Run:
 
     def enkf_table(self):
         """[n_arow][8] float64 (include/hydrocol.h hc_set_enkf; depths from the top node); a sweep: [P][n_arow][8]."""
-        return self.stepper.enkf_table().reshape(self._lead + (-1, ENKF_WIDTH))
+        return self.assim_table("enkf")
 
     def enkf_summary(self, table=None, sm_table=None, window_table=None, noise_table=None):
         """The EnKF's record (stepper.enkf_summary, means at the well's depths): ``rows``, ``count``, ``prior_mean_cm``,
@@ -425,7 +440,7 @@ class _Run:
 
     def enkf_window_table(self):
         """[n_arow][n][4] float64 (include/hydrocol.h hc_set_enkf_window); a sweep: [P][n_arow][n][4]."""
-        return self.stepper.enkf_window_table().reshape(self._lead + (-1, len(self.enkf_window_offsets), WINDOW_WIDTH))
+        return self.assim_table("enkf_window")
 
     def enkf_window_summary(self, table=None):
         """stepper.enkf_window_summary of the window's table (``table``: e.g. the one assembled over ranks): per
@@ -435,7 +450,7 @@ class _Run:
 
     def enkf_sm_table(self):
         """[n_arow][n][6] float64 (include/hydrocol.h hc_set_enkf_soil_moisture); a sweep: [P][n_arow][n][6]."""
-        return self.stepper.enkf_sm_table().reshape(self._lead + (-1, self.stepper.enkf_sm_n, SM_WIDTH))
+        return self.assim_table("enkf_sm")
 
     def enkf_sm_summary(self, table=None):
         """stepper.enkf_sm_summary of the sensor table (``table``: e.g. the one assembled over ranks): per sensor the
@@ -637,43 +652,34 @@ class EnsembleSimulation(_Run):
             arrays["filter_stride"] = np.array(self.filter_stride, dtype=np.int64)
             arrays["filter_sigma_cm"] = np.array(self.filter_sigma_cm, dtype=np.float64)
             arrays["filter_seed"] = np.array(self.filter_seed, dtype=np.uint64)
-            arrays["filter_table"] = self.stepper.filter_table()
             arrays["filter_base"] = self.stepper.filter_base()
             if self.filter_soil_moisture is not None:     # the record itself is supplied again at restore
                 arrays["filter_sm_nodes"] = np.asarray(self.filter_soil_moisture["nodes"], dtype=np.int32)
-                arrays["filter_sm_table"] = self.stepper.filter_sm_table()
             if self.filter_ess_floor:                     # (an untempered run keeps its key set)
                 arrays["filter_ess_floor"] = np.array(self.filter_ess_floor, dtype=np.float64)
-                arrays["filter_temper_table"] = self.stepper.filter_temper_table()
             if self.filter_rejuvenation:                  # (the moved vectors are filter_base; the draws are stateless)
                 arrays["filter_rejuvenation"] = np.array(self.filter_rejuvenation, dtype=np.float64)
-                arrays["filter_rejuvenation_table"] = self.stepper.filter_rejuvenation_table()
             if self.filter_window_offsets:               # what was recorded for the coming assimilation travels along
-                b, rows = self.stepper.filter_window_capture()
                 arrays["filter_window_offsets"] = np.asarray(self.filter_window_offsets, dtype=np.int64)
-                arrays["filter_window_table"] = self.stepper.filter_window_table()
-                arrays["filter_window_index"], arrays["filter_window_rows"] = b, rows
+                arrays["filter_window_index"], arrays["filter_window_rows"] = self.stepper.filter_window_capture()
         if self.enkf_stride:
             arrays["enkf_stride"] = np.array(self.enkf_stride, dtype=np.int64)
             arrays["enkf_sigma_cm"] = np.array(self.enkf_sigma_cm, dtype=np.float64)
             arrays["enkf_localisation_cm"] = np.array(self.enkf_localisation_cm, dtype=np.float64)
             arrays["enkf_seed"] = np.array(self.enkf_seed, dtype=np.uint64)
-            arrays["enkf_table"] = self.stepper.enkf_table()
             if (self.enkf_method, self.enkf_relaxation) != ("stochastic", 0.0):     # (a default run keeps its key set)
                 arrays["enkf_method"] = np.array(ENKF_METHODS.index(self.enkf_method), dtype=np.int64)
                 arrays["enkf_relaxation"] = np.array(self.enkf_relaxation, dtype=np.float64)
             if self.enkf_soil_moisture is not None:       # the record itself is supplied again at restore
                 arrays["enkf_sm_nodes"] = np.asarray(self.enkf_soil_moisture["nodes"], dtype=np.int32)
-                arrays["enkf_sm_table"] = self.stepper.enkf_sm_table()
             if self.enkf_window_offsets:                  # what was recorded for the coming analysis travels along
-                y, rows = self.stepper.enkf_window_capture()
                 arrays["enkf_window_offsets"] = np.asarray(self.enkf_window_offsets, dtype=np.int64)
-                arrays["enkf_window_table"] = self.stepper.enkf_window_table()
-                arrays["enkf_window_y"], arrays["enkf_window_rows"] = y, rows
+                arrays["enkf_window_y"], arrays["enkf_window_rows"] = self.stepper.enkf_window_capture()
             if self.enkf_noise_relaxation is not None:    # the analysed vectors carry the damping too (as a filtered run's)
                 arrays["enkf_noise_relaxation"] = np.array(self.enkf_noise_relaxation, dtype=np.float64)
-                arrays["enkf_noise_table"] = self.stepper.enkf_noise_table()
                 arrays["enkf_noise_base"] = self.stepper.enkf_noise_base()
+        for key in self.assim_tables_on():                # the filters' tables: one dataset each, <key>_table
+            arrays[key + "_table"] = self.stepper.assim_table(key)
         path = Path(path)
         if hdf5io.available() and path.suffix != ".npz":
             hdf5io.write(path, arrays)
@@ -709,11 +715,9 @@ class EnsembleSimulation(_Run):
         filt = int(data["filter_stride"]) if "filter_stride" in data else 0
         fkw = dict(filter_stride=filt, filter_sigma_cm=float(data["filter_sigma_cm"]),
                    filter_seed=int(data["filter_seed"])) if filt else {}
-        tempered = bool(filt) and "filter_ess_floor" in data
-        if tempered:
+        if filt and "filter_ess_floor" in data:
             fkw.update(filter_ess_floor=float(data["filter_ess_floor"]))
-        rejuvenated = bool(filt) and "filter_rejuvenation" in data
-        if rejuvenated:
+        if filt and "filter_rejuvenation" in data:
             fkw.update(filter_rejuvenation=float(data["filter_rejuvenation"]))
         periods = "period_ends" in data
         if periods:
@@ -732,7 +736,7 @@ class EnsembleSimulation(_Run):
         if has_nz:
             fkw.update(enkf_noise_field={"relaxation": float(data["enkf_noise_relaxation"])})
         def record(on, prefix, given):
-            """Whether the checkpoint holds the sensor table of ``prefix``'s record; the record given must match it."""
+            """The record given must match the one the checkpoint holds the sensor table of (``prefix``'s), if any."""
             has = bool(on) and prefix + "_sm_table" in data
             arg = prefix + "_soil_moisture"
             if has != (given is not None):
@@ -743,10 +747,9 @@ class EnsembleSimulation(_Run):
                 raise ValueError(f" EnsembleSimulation: {path} has sensors at other nodes than {arg}.")
             if has:
                 fkw[arg] = given
-            return has
 
-        has_sm = record(enkf, "enkf", enkf_soil_moisture)
-        has_fsm = record(filt, "filter", filter_soil_moisture)
+        record(enkf, "enkf", enkf_soil_moisture)
+        record(filt, "filter", filter_soil_moisture)
         has_fwin = bool(filt) and "filter_window_offsets" in data
         if has_fwin:
             fkw.update(filter_window_offsets=tuple(int(o) for o in np.asarray(data["filter_window_offsets"]).reshape(-1)))
@@ -757,30 +760,18 @@ class EnsembleSimulation(_Run):
                   psi0=np.asarray(data["initial_cond"], dtype=float).reshape(-1)[:D], flags=flags, profile_stride=stride,
                   wtd_hist_stride=hist_stride, theta_hist_bins=theta_bins, **(fkw_storage if storage else {}), **fkw)
         sim.stepper.set_state(psi if n > 1 else psi[0])
+        for key in sim.assim_tables_on():                 # the tables the constructor turned on, each from <key>_table
+            sim.stepper.set_assim_table(key, np.asarray(data[key + "_table"], dtype=np.float64))
         if filt:
-            sim.stepper.set_filter_table(np.asarray(data["filter_table"], dtype=np.float64))
             sim.stepper.set_filter_base(np.asarray(data["filter_base"], dtype=np.float64).reshape(n, D))
-            if has_fsm:
-                sim.stepper.set_filter_sm_table(np.asarray(data["filter_sm_table"], dtype=np.float64))
-            if tempered:
-                sim.stepper.set_filter_temper_table(np.asarray(data["filter_temper_table"], dtype=np.float64))
-            if rejuvenated:
-                sim.stepper.set_filter_rejuvenation_table(np.asarray(data["filter_rejuvenation_table"], dtype=np.float64))
             if has_fwin:
-                sim.stepper.set_filter_window_table(np.asarray(data["filter_window_table"], dtype=np.float64))
                 sim.stepper.set_filter_window_capture(np.asarray(data["filter_window_index"], dtype=np.int32).reshape(-1, n),
                                                       np.asarray(data["filter_window_rows"], dtype=np.int64))
         elif has_nz:
-            sim.stepper.set_enkf_noise_table(np.asarray(data["enkf_noise_table"], dtype=np.float64))
             sim.stepper.set_enkf_noise_base(np.asarray(data["enkf_noise_base"], dtype=np.float64).reshape(n, D))
         else:
             sim.stepper.set_noise_scale(np.asarray(data["noise_scale"], dtype=float).reshape(n))
-        if enkf:
-            sim.stepper.set_enkf_table(np.asarray(data["enkf_table"], dtype=np.float64))
-        if has_sm:
-            sim.stepper.set_enkf_sm_table(np.asarray(data["enkf_sm_table"], dtype=np.float64))
         if has_win:
-            sim.stepper.set_enkf_window_table(np.asarray(data["enkf_window_table"], dtype=np.float64))
             sim.stepper.set_enkf_window_capture(np.asarray(data["enkf_window_y"], dtype=np.float64).reshape(-1, n),
                                                 np.asarray(data["enkf_window_rows"], dtype=np.int64))
         sim.stepper.set_moments(np.asarray(data["moments"], dtype=np.int64))

@@ -609,16 +609,28 @@ class EnsembleStepper:
         self.enkf_noise_field, self.enkf_noise_relaxation = False, 0.0
         self.filter_shard, self._filter_shard_keep = None, None
 
+    # -- the assimilation tables: one path for the nine of them (ASSIM_TABLES below) -------------------------------------
+    def assim_table(self, key):
+        """[P][n_arow] + the key's trailing shape (:func:`assim_table_shape`) float64, n_arow the slots of the owner's
+        stride: ``hc_get_<key>_stats``.  The named accessors below document the columns."""
+        owner = ASSIM_TABLES[key][0]
+        trailing = assim_table_shape(key, self.D, getattr(self, owner + "_sm_n"), getattr(self, owner + "_window_n"))
+        t = np.zeros((self.P, stride_rows(self.T, getattr(self, owner + "_stride"))) + trailing)
+        L.check(getattr(self.lib, f"hc_get_{key}_stats")(self.h, L.dptr(t), t.size))
+        return t
+
+    def set_assim_table(self, key, table):
+        """``hc_set_<key>_stats``: the table :meth:`assim_table` gave, in any shape (a checkpoint's)."""
+        t = L.as_f64(table).reshape(-1)
+        L.check(getattr(self.lib, f"hc_set_{key}_stats")(self.h, L.dptr(t), t.size))
+
     def filter_table(self):
         """[P][n_arow][4] float64: count, ESS, log-likelihood increment, survivors per assimilation slot (slot j <-> row
         j stride; count 0 and NaN where nothing was assimilated)."""
-        t = np.zeros((self.P, stride_rows(self.T, self.filter_stride), 4))
-        L.check(self.lib.hc_get_filter_stats(self.h, L.dptr(t), t.size))
-        return t
+        return self.assim_table("filter")
 
     def set_filter_table(self, table):
-        t = L.as_f64(table).reshape(-1)
-        L.check(self.lib.hc_set_filter_stats(self.h, L.dptr(t), t.size))
+        self.set_assim_table("filter", table)
 
     def filter_base(self):
         """[N][D] base noise vectors of a filtered Philox run (what resampling carries from ancestor to slot)."""
@@ -667,13 +679,10 @@ class EnsembleStepper:
     def filter_temper_table(self):
         """[P][n_arow][4] float64: beta, the ESS at beta, the target T and the trials evaluated per assimilation slot (NaN
         where nothing was assimilated or no member was counted)."""
-        t = np.zeros((self.P, stride_rows(self.T, self.filter_stride), TEMPER_WIDTH))
-        L.check(self.lib.hc_get_filter_temper_stats(self.h, L.dptr(t), t.size))
-        return t
+        return self.assim_table("filter_temper")
 
     def set_filter_temper_table(self, table):
-        t = L.as_f64(table).reshape(-1)
-        L.check(self.lib.hc_set_filter_temper_stats(self.h, L.dptr(t), t.size))
+        self.set_assim_table("filter_temper", table)
 
     def filter_temper_trials(self):
         """[P][11][4] int64: {k, Q_k, S_k low word, S_k high word} of the last assimilation's trials in trial order,
@@ -705,13 +714,10 @@ class EnsembleStepper:
     def filter_rejuvenation_table(self):
         """[P][n_arow][4] float64: applied, members refused, sqrt(mean_d s_d^2) of the resampled base vectors and of the
         rejuvenated ones per assimilation slot (the last two NaN when not applied; all NaN where nothing was assimilated)."""
-        t = np.zeros((self.P, stride_rows(self.T, self.filter_stride), REJUV_WIDTH))
-        L.check(self.lib.hc_get_filter_rejuvenation_stats(self.h, L.dptr(t), t.size))
-        return t
+        return self.assim_table("filter_rejuvenation")
 
     def set_filter_rejuvenation_table(self, table):
-        t = L.as_f64(table).reshape(-1)
-        L.check(self.lib.hc_set_filter_rejuvenation_stats(self.h, L.dptr(t), t.size))
+        self.set_assim_table("filter_rejuvenation", table)
 
     def filter_rejuvenation_moments(self):
         """[P][3][D] float64 of the last assimilation: mean_d and s_d of the resampled base vectors, s_d of the vectors the
@@ -761,13 +767,10 @@ class EnsembleStepper:
         """[P][n_arow][n][6] float64 per assimilation slot and sensor: observed (0/1), observation, forecast mean and std
         of theta, posterior mean and std of theta over the resampled slots; NaN where the slot had no sensor value (and
         after observed = 0)."""
-        t = np.zeros((self.P, stride_rows(self.T, self.filter_stride), self.filter_sm_n, SM_WIDTH))
-        L.check(self.lib.hc_get_filter_sm_stats(self.h, L.dptr(t), t.size))
-        return t
+        return self.assim_table("filter_sm")
 
     def set_filter_sm_table(self, table):
-        t = L.as_f64(table).reshape(-1)
-        L.check(self.lib.hc_set_filter_sm_stats(self.h, L.dptr(t), t.size))
+        self.set_assim_table("filter_sm", table)
 
     def filter_sm_width(self):
         """m_s = the sensors present on the last assimilation (0: it took the bin path; test hook)."""
@@ -816,13 +819,10 @@ class EnsembleStepper:
         """[P][n_arow][n][4] float64 per assimilation slot and offset: observed (0/1), observation, forecast mean and std
         of the members' water-table depth on the lagged row (cm from the top node); NaN where the slot's assimilation had
         no lagged row (and after observed = 0)."""
-        t = np.zeros((self.P, stride_rows(self.T, self.filter_stride), self.filter_window_n, WINDOW_WIDTH))
-        L.check(self.lib.hc_get_filter_window_stats(self.h, L.dptr(t), t.size))
-        return t
+        return self.assim_table("filter_window")
 
     def set_filter_window_table(self, table):
-        t = L.as_f64(table).reshape(-1)
-        L.check(self.lib.hc_set_filter_window_stats(self.h, L.dptr(t), t.size))
+        self.set_assim_table("filter_window", table)
 
     def filter_window_capture(self):
         """(b [n][N] int32, rows [n] int64): the water-table indices the window holds for the coming assimilation (row
@@ -944,13 +944,10 @@ class EnsembleStepper:
         """[P][n_arow][8] float64 per analysis slot (slot j <-> row j stride): count, prior mean and std of y, innovation,
         log-likelihood increment, posterior mean and std of y, rejected members; count 0 and NaN where nothing was
         analysed.  Depths from the top node (z[i] - z[0])."""
-        t = np.zeros((self.P, stride_rows(self.T, self.enkf_stride), ENKF_WIDTH))
-        L.check(self.lib.hc_get_enkf_stats(self.h, L.dptr(t), t.size))
-        return t
+        return self.assim_table("enkf")
 
     def set_enkf_table(self, table):
-        t = L.as_f64(table).reshape(-1)
-        L.check(self.lib.hc_set_enkf_stats(self.h, L.dptr(t), t.size))
+        self.set_assim_table("enkf", table)
 
     def enkf_gain(self):
         """[P][D] the gain K_d of the last analysis (test hook)."""
@@ -1040,13 +1037,10 @@ class EnsembleStepper:
         """[P][n_arow][4 D + 1] float64 per analysis slot: the prior mean and std of every node's z, the mean and std
         after the relaxation, then the members whose updated vector was refused; NaN where nothing was analysed
         (:func:`split_enkf_noise_table`)."""
-        t = np.zeros((self.P, stride_rows(self.T, self.enkf_stride), 4 * self.D + 1))
-        L.check(self.lib.hc_get_enkf_noise_stats(self.h, L.dptr(t), t.size))
-        return t
+        return self.assim_table("enkf_noise")
 
     def set_enkf_noise_table(self, table):
-        t = L.as_f64(table).reshape(-1)
-        L.check(self.lib.hc_set_enkf_noise_stats(self.h, L.dptr(t), t.size))
+        self.set_assim_table("enkf_noise", table)
 
     def enkf_noise_gain(self):
         """[P][m'][D] the vectors' gain of the last analysis (test hook)."""
@@ -1103,13 +1097,10 @@ class EnsembleStepper:
     def enkf_sm_table(self):
         """[P][n_arow][n][6] float64 per analysis slot and sensor: observed (0/1), observation, prior mean and std of
         theta, posterior mean and std of theta; NaN where the slot took no joint analysis (and after observed = 0)."""
-        t = np.zeros((self.P, stride_rows(self.T, self.enkf_stride), self.enkf_sm_n, SM_WIDTH))
-        L.check(self.lib.hc_get_enkf_sm_stats(self.h, L.dptr(t), t.size))
-        return t
+        return self.assim_table("enkf_sm")
 
     def set_enkf_sm_table(self, table):
-        t = L.as_f64(table).reshape(-1)
-        L.check(self.lib.hc_set_enkf_sm_stats(self.h, L.dptr(t), t.size))
+        self.set_assim_table("enkf_sm", table)
 
     def enkf_sm_width(self):
         """m' = 1 + the sensors present on the last analysis (0: it had none; test hook)."""
@@ -1154,13 +1145,10 @@ class EnsembleStepper:
     def enkf_window_table(self):
         """[P][n_arow][n][4] float64 per analysis slot and offset: observed (0/1), observation, prior mean and std of the
         recorded y (cm from the top node); NaN where the slot's analysis had no lagged row (and after observed = 0)."""
-        t = np.zeros((self.P, stride_rows(self.T, self.enkf_stride), self.enkf_window_n, WINDOW_WIDTH))
-        L.check(self.lib.hc_get_enkf_window_stats(self.h, L.dptr(t), t.size))
-        return t
+        return self.assim_table("enkf_window")
 
     def set_enkf_window_table(self, table):
-        t = L.as_f64(table).reshape(-1)
-        L.check(self.lib.hc_set_enkf_window_stats(self.h, L.dptr(t), t.size))
+        self.set_assim_table("enkf_window", table)
 
     def enkf_window_capture(self):
         """(y [n][N], rows [n] int64): what the window holds for the coming analysis (row -1: nothing; checkpoints)."""
@@ -2150,6 +2138,7 @@ def filter_summary(table, stride, sigma_cm, temper_table=None, rejuvenation_tabl
 
 # ---- ensemble Kalman filter on the host (include/hydrocol.h hc_set_enkf) -----------------------------------------------
 ENKF_WIDTH = 8
+FILTER_WIDTH = 4                           # the particle filter's own table: count, ESS, log-likelihood increment, survivors
 ENKF_METHODS = ("stochastic", "sqrt")      # hc_set_enkf_method's 0 and 1
 
 
@@ -2436,6 +2425,31 @@ def filter_window_summary(table, stride, offsets, z0_cm=0.0):
     layout being the same -- ``prior_*`` the forecast ensemble's water-table depth on the lagged row, ``n_obs`` the lagged
     observations weighed, ``n_rows`` the assimilation rows that took any."""
     return enkf_window_summary(table, stride, offsets, z0_cm)
+
+
+# ---- the assimilation tables (include/hydrocol.h hc_get_<key>_stats / hc_set_<key>_stats) ------------------------------
+# key -> (owner, the trailing shape of one point's assimilation slot).  The key names the C entry points, the accessors
+# (<key>_table / set_<key>_table), the checkpoint's dataset (<key>_table) and the CLI's placed table; "sensors", "offsets"
+# and "4D+1" stand for the run's counts (:func:`assim_table_shape`).  A new table is one entry here, its two C entry
+# points in _lib.EXPORTS, and the named accessors that document its columns.
+ASSIM_TABLES = {
+    "filter": ("filter", (FILTER_WIDTH,)),
+    "filter_sm": ("filter", ("sensors", SM_WIDTH)),
+    "filter_temper": ("filter", (TEMPER_WIDTH,)),
+    "filter_rejuvenation": ("filter", (REJUV_WIDTH,)),
+    "filter_window": ("filter", ("offsets", WINDOW_WIDTH)),
+    "enkf": ("enkf", (ENKF_WIDTH,)),
+    "enkf_sm": ("enkf", ("sensors", SM_WIDTH)),
+    "enkf_window": ("enkf", ("offsets", WINDOW_WIDTH)),
+    "enkf_noise": ("enkf", ("4D+1",)),
+}
+
+
+def assim_table_shape(key, D, n_sensors=0, n_offsets=0):
+    """The trailing shape of the table ``key`` of ASSIM_TABLES -- what follows [P][n_arow] -- for ``D`` depth nodes and
+    the owner's ``n_sensors`` soil-moisture sensors and ``n_offsets`` window offsets.  Needs no handle."""
+    sizes = {"sensors": int(n_sensors), "offsets": int(n_offsets), "4D+1": 4 * int(D) + 1}
+    return tuple(sizes.get(n, n) for n in ASSIM_TABLES[key][1])
 
 
 def allreduce_handles(steppers):

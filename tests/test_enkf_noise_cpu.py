@@ -265,7 +265,8 @@ def test_hdf5_dataset_names_of_an_ensemble_and_a_sweep():
         def __init__(self, t):
             self.t = t
 
-        def enkf_noise_table(self):
+        def assim_table(self, key):
+            assert key == "enkf_noise"
             return self.t
 
     Dn, T = 6, 97                                        # 97 rows, stride 24: slots 0 ... 4
