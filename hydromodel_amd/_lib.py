@@ -69,6 +69,11 @@ EXPORTS = {
     "hc_get_noise_base": ([C.c_void_p, _dp, C.c_int64, C.c_int64], C.c_int),
     "hc_set_noise_philox": ([C.c_void_p, C.c_uint64, C.c_int64], C.c_int),
     "hc_philox_normals": ([C.c_void_p, C.c_int64, C.c_int64, _dp], C.c_int),
+    "hc_set_noise_correlation": ([C.c_void_p, _dp, _dp], C.c_int),
+    "hc_get_noise_correlation": ([C.c_void_p, _ip, _dp, _dp], C.c_int),
+    "hc_noise_field_normals": ([C.c_void_p, C.c_int64, C.c_int64, _dp], C.c_int),
+    "hc_get_noise_field_base": ([C.c_void_p, _dp, C.c_int64, C.c_int64], C.c_int),
+    "hc_set_noise_field_base": ([C.c_void_p, _dp], C.c_int),
     "hc_step_rows": ([C.c_void_p, C.POINTER(StepArgs)], C.c_int),
     "hc_spinup": ([C.c_void_p, C.POINTER(SpinupArgs)], C.c_int),
     "hc_synchronize": ([C.c_void_p], C.c_int),

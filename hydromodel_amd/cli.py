@@ -166,6 +166,13 @@ unknown keys, only membership of the 12 is checked):
   [0, 1] (default 0 = none), for either method: after each analysis every node's spread is (1 - alpha) sigma_a + alpha
   sigma_b, and the posterior datasets describe the relaxed ensemble.  Added to ``<Output_Name>_ensemble.h5`` when either
   is given: ``enkf_method`` (0 = stochastic, 1 = sqrt) and ``enkf_relaxation``.
+* ``"Ensemble": {..., "Noise_Correlation": {"Length_cm": 50.0, "Layers": true}}``: a vertical correlation length of the
+  conductivity noise fields (include/hydrocol.h hc_set_noise_correlation): every base and refresh vector of the Philox
+  source becomes an exponentially correlated field of unit variance, with ``Layers`` (default false) independent across
+  the layer interfaces inside the column; applied after the spin-up, before the filters.  Refused with ``"Noise":
+  "numpy"`` and with ``Filter.Rejuvenation``.  ``<Output_Name>_ensemble.h5`` gains ``noise_correlation_length_cm``,
+  ``noise_correlation_layers`` and ``noise_correlation_a`` (``[D]``; a sweep: ``[P][D]``), and the run ends with
+  `` [Ensemble xN] noise correlation: length ... cm, K breaks``.  Without the key every bit, file and line stays.
 * ``"EnKF": {..., "Noise_Field": true}`` or ``{"Noise_Field": {"Relaxation": 0.5}}``: every analysis also updates each
   member's base noise vector -- its conductivity field -- together with its state, from the same observations, draws and
   factor (include/hydrocol.h hc_set_enkf_noise_field).  The vectors' anomalies are relaxed to prior spread with the
@@ -257,6 +264,7 @@ def main(params_file=None, data_file=None, seed=None, device=0, gpus=None, _sett
             enkf_window_settings(params["Ensemble"])
             enkf_noise_settings(params["Ensemble"])
             filter_window_settings(params["Ensemble"])
+            noise_correlation_settings(params["Ensemble"])
         ranks = multigpu.Ranks(expect=n_gpus if (n_gpus > 1 or multigpu.in_rank()) else None)
         if ranks.world > 1:
             device = ranks.device_index()
@@ -326,6 +334,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     window = enkf_window_settings(ens)
     noise_alpha = enkf_noise_settings(ens)
     fwindow = filter_window_settings(ens)
+    corr = noise_correlation_settings(ens)
     cols = ColumnTables(params, load_site_well(params))
     forcing = ForcingDigest(params, water_data, cols)
     record = soil_moisture_record_of(sm, cols, water_data)      # before any GPU call
@@ -340,7 +349,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     plan = period_plan(periods, cols, forcing, rows)            # before any GPU call, like the storage's ranges
     if ens.get("Points"):
         return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels, assim,
-                          theta, storage, periods, plan)
+                          theta, storage, periods, plan, corr)
     sharded = enkf_sharded(ens)
     fsharded = filter_sharded(ens)
     if sharded:
@@ -362,7 +371,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
                              noise=str(ens.get("Noise", "philox")).lower(),
                              spinup=str(ens.get("Spinup", "shared")).lower(), profile_stride=stride,
                              wtd_hist_stride=dist_stride, theta_hist_bins=theta[0], **assim.kwargs(),
-                             **_storage_kwargs(storage), **_period_kwargs(periods, plan), **shard_kw)
+                             **_storage_kwargs(storage), **_period_kwargs(periods, plan), **shard_kw,
+                             **_noise_correlation_kwargs(corr))
     label = f"Ensemble x{n_members}"
     _step_all(sim, rows, label, ranks)
     # the run's one collective: int64 (count, sum idx, sum idx^2) per row, exact and order-independent
@@ -406,10 +416,12 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
         extra["filter_sharded"] = np.array(1 if fsharded else 0, dtype=np.int8)
     if sharded is not None:
         extra["enkf_sharded"] = np.array(1 if sharded else 0, dtype=np.int8)
+    ctables, corr_line = _noise_correlation_arrays(corr, [cols], label, keep_points=False)
+    extra.update(ctables)
     arrays = dict(moments=moments, wtd_mean_cm=mean_cm, wtd_std_cm=std_cm, rows=np.array(rows),
                   members=np.array(n_members), gpus=np.array(ranks.world), initial_cond=psi0, **extra)
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "ensemble water-table statistics", ranks)
-    _print_lines(crps_line, *assim_lines, theta_line, storage_line, period_line)
+    _print_lines(crps_line, *assim_lines, theta_line, storage_line, period_line, corr_line if ranks.rank == 0 else None)
     sim.close()
 
 
@@ -496,6 +508,62 @@ def _reduce_assimilation(ranks, sim, ids, P, T, cols, a, label, keep_points):
             out.update(datasets)
             lines.append(line)
     return out, lines
+
+
+NOISE_CORRELATION_KEYS = ("Length_cm", "Layers")
+
+
+def noise_correlation_settings(ens):
+    """Ensemble.Noise_Correlation -> {"length_cm": l, "layers": bool} (the ``noise_correlation=`` argument of
+    EnsembleSimulation / SweepSimulation), or None when the key is absent.  Pure: runs before any GPU call, and a bad value
+    is a ValueError (message + exit status 1).  Refused with ``"Noise": "numpy"`` (such a run shapes its own vectors) and with
+    ``Filter.Rejuvenation`` (its jitter is white per node and would erode the correlation)."""
+    import math
+    from numbers import Real
+    if "Noise_Correlation" not in ens:
+        return None
+    block = ens["Noise_Correlation"]
+    if not isinstance(block, dict):
+        raise ValueError(f" Ensemble: Noise_Correlation = {block!r} must be an object such as "
+                         f"{{\"Length_cm\": 50.0, \"Layers\": true}}.")
+    unknown = sorted(set(block) - set(NOISE_CORRELATION_KEYS))
+    if unknown:
+        raise ValueError(f" Ensemble: Noise_Correlation has unknown keys {unknown} (known: {list(NOISE_CORRELATION_KEYS)}).")
+    length = block.get("Length_cm")
+    if isinstance(length, bool) or not isinstance(length, Real) or not math.isfinite(length) or not length > 0:
+        raise ValueError(f" Ensemble: Noise_Correlation.Length_cm = {length!r} must be a finite number > 0 (cm).")
+    layers = block.get("Layers", False)
+    if not isinstance(layers, bool):
+        raise ValueError(f" Ensemble: Noise_Correlation.Layers = {layers!r} must be true or false.")
+    if str(ens.get("Noise", "philox")).lower() != "philox":
+        raise ValueError(f" Ensemble: Noise_Correlation with \"Noise\": {ens.get('Noise')!r}: the correlation shapes the Philox "
+                         f"source's vectors; a NumPy stream's caller shapes its own.")
+    filt = ens.get("Filter")
+    if isinstance(filt, dict) and "Rejuvenation" in filt:
+        raise ValueError(" Ensemble: Noise_Correlation and Filter.Rejuvenation exclude each other: the jitter is white per "
+                         "node and would erode the correlation by a share h^2 per move.")
+    return {"length_cm": float(length), "layers": layers}
+
+
+def _noise_correlation_kwargs(corr):
+    return {} if corr is None else {"noise_correlation": corr}
+
+
+def _noise_correlation_arrays(corr, cols_list, label, keep_points):
+    """The datasets and the closing line of a run with a noise correlation: the tables are the points' own (every rank
+    builds the same ones: no collective)."""
+    import numpy as np
+    from .stepper import noise_correlation_breaks, noise_correlation_tables
+    if corr is None:
+        return {}, None
+    a = np.stack([noise_correlation_tables(c.z, corr["length_cm"],
+                                           noise_correlation_breaks(c.layers, c.z) if corr["layers"] else ())[0]
+                  for c in cols_list])
+    out = {"noise_correlation_length_cm": np.array(corr["length_cm"], dtype=np.float64),
+           "noise_correlation_layers": np.array(1 if corr["layers"] else 0, dtype=np.int8),
+           "noise_correlation_a": a if keep_points else a[0]}
+    line = f" [{label}] noise correlation: length {corr['length_cm']:g} cm, {int((a[:, 1:] == 0.0).sum())} breaks"
+    return out, line
 
 
 DEFAULT_QUANTILES = (0.05, 0.25, 0.5, 0.75, 0.95)
@@ -1523,7 +1591,7 @@ def _reduce_periods(ranks, sim, ids, P, cols, forcing, periods, plan, label, kee
 
 
 def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride=0, dist_levels=None,
-               assim=Assimilation(), theta=(0, None), storage=None, periods=None, plan=None):
+               assim=Assimilation(), theta=(0, None), storage=None, periods=None, plan=None, corr=None):
     """Parameter points x members: this rank's points in one handle (ensemble.SweepSimulation), the whole table assembled
     over the ranks (multigpu.assemble_points)."""
     import numpy as np
@@ -1550,7 +1618,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     if mine:
         sim = SweepSimulation(points, forcing, n_members, seed=int(ens.get("Seed", 0)), device=device, point_ids=mine,
                               profile_stride=stride, wtd_hist_stride=dist_stride, theta_hist_bins=theta[0],
-                              **assim.kwargs(), **_storage_kwargs(storage), **_period_kwargs(periods, plan))
+                              **assim.kwargs(), **_storage_kwargs(storage), **_period_kwargs(periods, plan),
+                              **_noise_correlation_kwargs(corr))
         _step_all(sim, rows, label, ranks)
         table = sim.moments()
         for j, k in enumerate(mine):
@@ -1572,10 +1641,12 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     arrays.update(ptables)
     atables, assim_lines = _reduce_assimilation(ranks, sim, mine, P, T, ref, assim, label, keep_points=True)
     arrays.update(atables)
+    ctables, corr_line = _noise_correlation_arrays(corr, cols_all, label, keep_points=True)
+    arrays.update(ctables)
     if sim is not None:
         sim.close()
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "sweep's water-table statistics", ranks)
-    _print_lines(crps_line, *assim_lines, theta_line, storage_line, period_line)
+    _print_lines(crps_line, *assim_lines, theta_line, storage_line, period_line, corr_line if ranks.rank == 0 else None)
 
 
 def run_cli(argv=None):
@@ -1604,6 +1675,7 @@ def run_cli(argv=None):
                 enkf_window_settings(settings["Ensemble"])
                 enkf_noise_settings(settings["Ensemble"])
                 filter_window_settings(settings["Ensemble"])
+                noise_correlation_settings(settings["Ensemble"])
             except ValueError as bad:
                 print(bad)
                 sys.exit(1)

@@ -343,10 +343,17 @@ struct hc_handle {
     // always with the spread: the table reports it); per member whether its vector was refused, and the count per point
     bool enkf_nz = false, nz_done = false;   // on; an analysis has updated the vectors since it was set
     double enkf_nz_alpha = 0.0;
-    bool noise_host() const { return (filt_stride > 0 || enkf_nz) && philox; }   // filt_host(), or the noise field's twin
+    // filt_host(), the noise field's twin, or a correlated Philox source
+    bool noise_host() const { return (filt_stride > 0 || enkf_nz || ncorr) && philox; }
     AccTable<double> enkf_nzt{"entries"};
     EnkfVec enkf_z;
     DevBuf<double> nz_rej, nz_rejsum;
+    // vertical correlation of the Philox source's vectors (hc_set_noise_correlation): on / off, the recursion's
+    // coefficients a then b, [2][P][D], on the host and on the device
+    bool ncorr = false;
+    bool corr_host() const { return ncorr && philox && filt_stride <= 0 && !enkf_nz; }   // ... and nothing else owns base
+    std::vector<double> ncorr_ab;
+    DevBuf<double> ncorr_dev;
     int n_cu = 256;
     double jac_reject = NUM_JAC_DIFF_REJECT;
 };
@@ -1519,6 +1526,91 @@ __global__ void filter_philox_fill_kernel(double *out, long long n_vec, const lo
         const long long gid = point_base ? point_base[m / members_per_point] + m % members_per_point : member_offset + m;
         const double z = philox_normal(seed, (unsigned long long)gid, draw, (unsigned)i);
         out[e] = nscale ? z * nscale[m] : z;
+    }
+}
+
+// ---- correlated noise fields (hc_set_noise_correlation; include/hydrocol.h)
+// filter_philox_fill_kernel's job with a vertical correlation: the same vectors [n_vec][N][D] from the same streams, each
+// run through the point's recursion  z_i = xi_i where a_i == 0, else (a_i z_{i-1}) + (b_i xi_i)  down the column, in one
+// pass.  A work item is one vector's tile of NF_TILE members of one point (a tile never spans two points: a, b are the
+// point's), taken NF_CHUNK nodes at a time through LDS:
+//   all waves draw the chunk's normals, one Philox block per node pair as philox_normal pairs them (cosine to the even
+//   node, sine to the odd one: xi is philox_normal's to the bit), into tile[member][node];
+//   the first wave walks one member per lane down the chunk in node order, z_{i-1} carried in a register from chunk to
+//   chunk (lane stride NF_PITCH = 65 doubles: the 32 lanes of a ds_read_b64 group fall on 32 distinct bank pairs);
+//   all waves store the tile, one member's 64 contiguous doubles per wave instruction.
+// One block per work item (a grid-stride loop over the items cost 20 SGPRs and nine of them spilled).
+// The third barrier of a chunk keeps the next chunk's draws out of a tile that is still being stored.
+constexpr int NF_TILE = 64, NF_CHUNK = 64, NF_PITCH = NF_CHUNK + 1, NF_THREADS = 256;
+
+// philox_normal's two values of one counter block: nodes 2 k and 2 k + 1
+__device__ __forceinline__ void philox_normal_pair(uint64_t seed, uint64_t member, uint32_t draw, uint32_t k, double &even,
+                                                   double &odd)
+{
+    uint32_t r[4];
+    philox4x32_10(k, draw, (uint32_t)member, (uint32_t)(member >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    uint64_t a = ((uint64_t)r[1] << 32) | r[0], b = ((uint64_t)r[3] << 32) | r[2];
+    double u1 = ((double)(a >> 11) + 0.5) * (1.0 / 9007199254740992.0);
+    double u2 = ((double)(b >> 11) + 0.5) * (1.0 / 9007199254740992.0);
+    double rad = sqrt(-2.0 * log(u1));
+    double s, c;
+    sincospi(2.0 * u2, &s, &c);
+    even = rad * c;
+    odd = rad * s;
+}
+
+__global__ __launch_bounds__(NF_THREADS) void noise_field_fill_kernel(
+    double *out, long long n_vec, const long long *rows, const int *draw_idx, unsigned long long seed, long long member_offset,
+    const long long *point_base, long long members_per_point, long long n_members, int D, const double *nscale,
+    const double *a, const double *b)
+{
+#pragma clang fp contract(off)
+    __shared__ double tile[NF_TILE * NF_PITCH];
+    __shared__ double ab[2][NF_CHUNK];
+    const int t = threadIdx.x, lane = t % WAVE, wave = t / WAVE;
+    const long long n_points = n_members / members_per_point;
+    const long long tiles = (members_per_point + NF_TILE - 1) / NF_TILE, per_vec = n_points * tiles;
+    const long long w = blockIdx.x;             // (the host launches one block per work item)
+    if (w >= n_vec * per_vec) return;
+    const long long v = w / per_vec, point = (w % per_vec) / tiles, j0 = (w % tiles) * NF_TILE;
+    const int n_mem = (int)(members_per_point - j0 < NF_TILE ? members_per_point - j0 : NF_TILE);
+    const long long m0 = point * members_per_point + j0;                    // the tile's first slot
+    const unsigned long long gid0 = (unsigned long long)((point_base ? point_base[point] : member_offset) + j0);
+    const unsigned draw = rows ? (unsigned)draw_idx[rows[v]] : 0u;
+    const double *ap = a + (size_t)point * D, *bp = b + (size_t)point * D;
+    double *dst = out + ((size_t)v * n_members + m0) * D;
+    double zprev = 0.0;                                                     // (a_0 == 0: never read at node 0)
+    for (int c0 = 0; c0 < D; c0 += NF_CHUNK) {
+        const int len = D - c0 < NF_CHUNK ? D - c0 : NF_CHUNK;
+        if (wave == 1 && lane < len) ab[0][lane] = ap[c0 + lane];
+        if (wave == 2 && lane < len) ab[1][lane] = bp[c0 + lane];
+#pragma unroll 1
+        for (int q = t; q < NF_TILE * (NF_CHUNK / 2); q += NF_THREADS) {
+            const int ml = q / (NF_CHUNK / 2), j = 2 * (q % (NF_CHUNK / 2));
+            if (ml < n_mem && j < len) {
+                double even, odd;
+                philox_normal_pair(seed, gid0 + ml, draw, (unsigned)(c0 + j) >> 1, even, odd);
+                tile[ml * NF_PITCH + j] = even;
+                if (j + 1 < len) tile[ml * NF_PITCH + j + 1] = odd;
+            }
+        }
+        __syncthreads();
+        if (t < n_mem) {
+            double *row = tile + t * NF_PITCH;
+            for (int j = 0; j < len; j++) {
+                const double aj = ab[0][j], xi = row[j];
+                const double z = aj == 0.0 ? xi : (aj * zprev) + (ab[1][j] * xi);
+                row[j] = z;
+                zprev = z;
+            }
+        }
+        __syncthreads();
+        if (lane < len)
+            for (int ml = wave; ml < n_mem; ml += NF_THREADS / WAVE) {
+                const double z = tile[ml * NF_PITCH + lane];
+                dst[(size_t)ml * D + c0 + lane] = nscale ? z * nscale[m0 + ml] : z;
+            }
+        __syncthreads();
     }
 }
 
@@ -3619,11 +3711,44 @@ void enkf_off(hc_handle *h)
     win_off(h);
 }
 
-// what turns both filters off: new points, members or noise source (include/hydrocol.h hc_set_filter, hc_set_enkf)
+// the Philox source's vectors are white again (hc_set_noise_correlation)
+void noise_corr_off(hc_handle *h)
+{
+    h->ncorr = false;
+    h->ncorr_ab.clear();
+    h->ncorr_dev.release();
+}
+
+// A Philox run's caller-style vectors [n_vec][N][D] from the kernel's own normals: the base vectors times the members'
+// scales (rows == NULL, n_vec = 1) or the refresh rows rows[v]; correlated down the column when a correlation is set.
+int launch_noise_fill(hc_handle *h, double *out, int64_t n_vec, const long long *rows, const double *nscale)
+{
+    const long long N = h->n_members, mpp = N / h->n_points;
+    const int D = h->p.dim_d;
+    const long long *point_base = h->n_points > 1 ? h->point_base.p : nullptr;
+    if (h->ncorr) {
+        const size_t items = (size_t)n_vec * h->n_points * (size_t)((mpp + NF_TILE - 1) / NF_TILE);
+        if (items > (size_t)INT32_MAX)           // (one block per item; the 4 GiB a launch stages hold far fewer)
+            return fail(HC_ERR_ARG, "noise field: %zu tiles in one fill exceed 2^31 - 1", items);
+        hipLaunchKernelGGL(noise_field_fill_kernel, dim3((unsigned)items), dim3(NF_THREADS), 0, h->stream, out,
+                           (long long)n_vec, rows, h->draw_idx.p, (unsigned long long)h->seed, (long long)h->member_offset,
+                           point_base, mpp, N, D, nscale, h->ncorr_dev.p, h->ncorr_dev.p + (size_t)h->n_points * D);
+        return HC_OK;
+    }
+    const size_t cnt = (size_t)n_vec * N * D;
+    const unsigned blocks = (unsigned)std::min<size_t>((cnt + 255) / 256, (size_t)h->n_cu * 64);
+    hipLaunchKernelGGL(filter_philox_fill_kernel, dim3(blocks), dim3(256), 0, h->stream, out, (long long)n_vec, rows,
+                       h->draw_idx.p, (unsigned long long)h->seed, (long long)h->member_offset, point_base, mpp, N, D, nscale);
+    return HC_OK;
+}
+
+// what turns both filters and the noise correlation off: new points, members or noise source (include/hydrocol.h
+// hc_set_filter, hc_set_enkf, hc_set_noise_correlation)
 void assimilation_off(hc_handle *h)
 {
     filter_off(h);
     enkf_off(h);
+    noise_corr_off(h);
 }
 
 // The filter that is on (the particle filter and the EnKF exclude each other): its stride (0: neither), its record and
@@ -3973,7 +4098,7 @@ static int build_point(hc_handle *h, const hc_column_params *p, const double *no
     } else {
         h->special = h->special && special;
     }
-    if (h->filt_stride > 0 || h->enkf_stride > 0) {   // the points change: the filters are off
+    if (h->filt_stride > 0 || h->enkf_stride > 0 || h->ncorr) {   // the points change: the filters are off
         (void)hipStreamSynchronize(h->stream);
         assimilation_off(h);
     }
@@ -4209,6 +4334,126 @@ int hc_philox_normals(hc_handle *h, int64_t member, int64_t draw, double *out)
     return HC_OK;
 }
 
+// ---- correlated noise fields (include/hydrocol.h)
+int hc_set_noise_correlation(hc_handle *h, const double *a, const double *b)
+{
+    if (!h || (a && !b)) return fail(HC_ERR_ARG, "hc_set_noise_correlation: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    noise_corr_off(h);                            // (and off it stays when the tables are refused)
+    if (!a) return HC_OK;
+    if (!h->have_noise || !h->philox)
+        return fail(HC_ERR_ARG, "hc_set_noise_correlation: needs a Philox run (hc_set_noise_philox first); a host-noise "
+                                "caller shapes its own vectors");
+    if (h->filt_stride > 0 || h->enkf_nz)
+        return fail(HC_ERR_ARG, "hc_set_noise_correlation: the %s is on and its base vectors carry history: set the "
+                                "correlation first", h->filt_stride > 0 ? "particle filter" : "EnKF's noise field");
+    StepArgs A;
+    if (int rc = fill_args(h, A)) return rc;     // column, forcing, members and noise are in place; point keys uploaded
+    const int D = h->p.dim_d, NP = h->n_points;
+    const size_t n = (size_t)NP * D;
+    for (size_t k = 0; k < n; k++) {
+        const int p = (int)(k / D), i = (int)(k % D);
+        const double ai = a[k], bi = b[k];
+        if (!std::isfinite(ai) || !std::isfinite(bi))
+            return fail(HC_ERR_ARG, "hc_set_noise_correlation: point %d node %d: a = %g, b = %g not finite", p, i, ai, bi);
+        if (!(ai >= 0.0 && ai < 1.0) || !(bi > 0.0))
+            return fail(HC_ERR_ARG, "hc_set_noise_correlation: point %d node %d: a = %g outside [0, 1) or b = %g <= 0", p, i, ai, bi);
+        if (i == 0 && ai != 0.0)
+            return fail(HC_ERR_ARG, "hc_set_noise_correlation: point %d: a_0 = %g, the recursion starts at node 0 (a_0 = 0)", p, ai);
+        if (ai == 0.0 ? bi != 1.0 : std::fabs(ai * ai + bi * bi - 1.0) > 1e-12)
+            return fail(HC_ERR_ARG, "hc_set_noise_correlation: point %d node %d: a = %g, b = %g is no unit-variance step "
+                                    "(a^2 + b^2 = 1; b = 1 at a break)", p, i, ai, bi);
+    }
+    h->ncorr_ab.assign(a, a + n);
+    h->ncorr_ab.insert(h->ncorr_ab.end(), b, b + n);
+    int rc = h->ncorr_dev.ensure(2 * n);
+    if (rc == HC_OK) rc = h->base.ensure((size_t)h->n_members * D);
+    if (rc == HC_OK) {
+        // the base vectors: the correlated draw 0 times the scales as they stand (one rounding), from here on carried
+        // like the caller's -- damped in place -- and kept by a filter or a noise field set afterwards
+        h->ncorr = true;
+        hipError_t e = hipMemcpy(h->ncorr_dev.p, h->ncorr_ab.data(), 2 * n * 8, hipMemcpyHostToDevice);
+        if (e == hipSuccess && (rc = launch_noise_fill(h, h->base.p, 1, nullptr, h->nscale.p)) == HC_OK) e = hipGetLastError();
+        const hipError_t e2 = hipStreamSynchronize(h->stream);
+        if (rc == HC_OK && (e != hipSuccess || e2 != hipSuccess))
+            rc = fail(HC_ERR_DEVICE, "hc_set_noise_correlation: base vectors: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+    }
+    if (rc != HC_OK) noise_corr_off(h);          // refused: off
+    return rc;
+}
+
+int hc_get_noise_correlation(hc_handle *h, int32_t *on, double *a, double *b)
+{
+    if (!h || !on) return fail(HC_ERR_ARG, "hc_get_noise_correlation: bad argument");
+    *on = h->ncorr ? 1 : 0;
+    if (!h->ncorr) return HC_OK;
+    const size_t n = h->ncorr_ab.size() / 2;
+    if (a) std::copy(h->ncorr_ab.begin(), h->ncorr_ab.begin() + n, a);
+    if (b) std::copy(h->ncorr_ab.begin() + n, h->ncorr_ab.end(), b);
+    return HC_OK;
+}
+
+int hc_noise_field_normals(hc_handle *h, int64_t member, int64_t draw, double *out)
+{
+    if (!h || !out || member < 0 || draw < 0) return fail(HC_ERR_ARG, "hc_noise_field_normals: bad argument");
+    if (!h->ncorr) return hc_philox_normals(h, member, draw, out);
+    HIP_TRY(hipSetDevice(h->device));
+    // the point whose members' keys hold `member` (one point: its table serves every key)
+    const int D = h->p.dim_d, NP = h->n_points;
+    const long long mpp = h->n_members / NP;
+    int point = 0;
+    if (NP > 1) {
+        point = -1;
+        for (int k = 0; k < NP && point < 0; k++) {
+            const long long first = (int)h->base_host.size() == NP ? h->base_host[(size_t)k] : h->member_offset + k * mpp;
+            if (member >= first && member < first + mpp) point = k;
+        }
+        if (point < 0)
+            return fail(HC_ERR_ARG, "hc_noise_field_normals: member %lld is no key of this handle's points", (long long)member);
+    }
+    // the fill kernel itself on one member: rows = {0}, draw_idx = {draw}
+    const long long row0 = 0;
+    const int draw32 = (int)(unsigned)draw;
+    if (h->scratch_d.ensure((size_t)D + 2)) return HC_ERR_DEVICE;
+    long long *rows = reinterpret_cast<long long *>(h->scratch_d.p + D);
+    int *didx = reinterpret_cast<int *>(h->scratch_d.p + D + 1);
+    HIP_TRY(hipMemcpyAsync(rows, &row0, 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(didx, &draw32, 4, hipMemcpyHostToDevice, h->stream));
+    const double *ab = h->ncorr_dev.p;
+    hipLaunchKernelGGL(noise_field_fill_kernel, dim3(1), dim3(NF_THREADS), 0, h->stream, h->scratch_d.p, 1ll, rows, didx,
+                       (unsigned long long)h->seed, (long long)member, nullptr, 1ll, 1ll, D, nullptr,
+                       ab + (size_t)point * D, ab + ((size_t)NP + point) * D);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(out, h->scratch_d.p, (size_t)D * 8, hipMemcpyDeviceToHost));
+    return HC_OK;
+}
+
+int hc_get_noise_field_base(hc_handle *h, double *base, int64_t first, int64_t count)
+{
+    if (!h || !base || first < 0 || count < 0 || first + count > h->n_members || !(h->ncorr && h->philox))
+        return fail(HC_ERR_ARG, "hc_get_noise_field_base: bad argument (a Philox run with a noise correlation set)");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const int D = h->p.dim_d;
+    HIP_TRY(hipMemcpy(base, h->base.p + (size_t)first * D, (size_t)count * D * 8, hipMemcpyDeviceToHost));
+    return HC_OK;
+}
+
+int hc_set_noise_field_base(hc_handle *h, const double *base)
+{
+    if (!h || !base || !(h->ncorr && h->philox))
+        return fail(HC_ERR_ARG, "hc_set_noise_field_base: bad argument (a Philox run with a noise correlation set)");
+    const size_t n = (size_t)h->n_members * h->p.dim_d;
+    for (size_t i = 0; i < n; i++)
+        if (!std::isfinite(base[i])) return fail(HC_ERR_ARG, "hc_set_noise_field_base: entry %zu is not finite", i);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(h->base.p, base, n * 8, hipMemcpyHostToDevice));
+    return HC_OK;
+}
+
 // One simulated day per launch for very large ensembles; smaller ones get proportionally longer launches, so that a launch
 // holds ~1 M member-days of work (in-kernel noise; round 5: 64 k before) and the tail behind its slowest wavefront stays
 // small: 4 096 members x D = 200 over the year 308.5 k column-days/s at 16 days per launch, 319 k at 64, 324 k at 128, 327 k at
@@ -4416,8 +4661,9 @@ int window_slot(const hc_handle *h, int64_t row)
 }
 
 // The launch after `done` rows of the request.  With a filter on, a launch ends on the next assimilation row and, in a
-// Philox run with the particle filter, holds at most as many refresh rows as FILT_FRESH_BYTES admits; with either
-// filter's window on it ends on the next lagged row that takes part.
+// Philox run with the particle filter, holds at most as many refresh rows as FILT_FRESH_BYTES admits (so does any launch
+// of a Philox run that stages its vectors: the noise field's, a correlated source's); with either filter's window on it
+// ends on the next lagged row that takes part.
 Chunk plan_chunk(const hc_handle *h, const hc_step_args *a, int64_t done, bool prof_on)
 {
     const int64_t N = h->n_members, D = h->p.dim_d;
@@ -4444,15 +4690,15 @@ Chunk plan_chunk(const hc_handle *h, const hc_step_args *a, int64_t done, bool p
                     c.rows = r + 1;
                     break;
                 }
-        if (h->noise_host()) {
-            const int64_t cap = std::max<int64_t>(1, FILT_FRESH_BYTES / (N * D * 8));
-            int64_t n_fresh = 0;
-            for (int r = 0; r < c.rows; r++)
-                if (h->h_refresh[(size_t)(c.row0 + r)] && ++n_fresh > cap) {
-                    c.rows = r;
-                    break;
-                }
-        }
+    }
+    if (h->noise_host() && !a->spinup) {      // (with a correlation set also without a filter)
+        const int64_t cap = std::max<int64_t>(1, FILT_FRESH_BYTES / (N * D * 8));
+        int64_t n_fresh = 0;
+        for (int r = 0; r < c.rows; r++)
+            if (h->h_refresh[(size_t)(c.row0 + r)] && ++n_fresh > cap) {
+                c.rows = r;
+                break;
+            }
     }
     const int64_t diag_row = N * 2 * 8;
     if (h->per_n > 0 && !a->spinup) {
@@ -4495,11 +4741,7 @@ int stage_noise(hc_handle *h, const hc_step_args *a, const Chunk &c, int64_t con
         if (h->fresh.ensure(cnt) || h->filt_rows.ensure((size_t)n_fresh)) return HC_ERR_DEVICE;
         HIP_TRY(hipMemcpyAsync(h->filt_rows.p, h->filt_rows_host.data(), (size_t)n_fresh * 8, hipMemcpyHostToDevice,
                                h->stream));
-        const unsigned blocks = (unsigned)std::min<size_t>((cnt + 255) / 256, (size_t)h->n_cu * 64);
-        hipLaunchKernelGGL(filter_philox_fill_kernel, dim3(blocks), dim3(256), 0, h->stream, h->fresh.p, (long long)n_fresh,
-                           h->filt_rows.p, h->draw_idx.p, (unsigned long long)h->seed, (long long)h->member_offset,
-                           h->n_points > 1 ? h->point_base.p : nullptr, (long long)(N / h->n_points), (long long)N,
-                           (int)D, nullptr);
+        if (int rc = launch_noise_fill(h, h->fresh.p, n_fresh, h->filt_rows.p, nullptr)) return rc;
         HIP_TRY(hipGetLastError());
         return HC_OK;
     }
@@ -5280,6 +5522,8 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
     // the particle filter (hc_set_filter): spin-up solves are never filtered
     if (a->spinup && h->filt_host())
         return fail(HC_ERR_ARG, "spin-up solves with the particle filter on in a Philox run: set the filter after the spin-up");
+    if (a->spinup && h->corr_host())
+        return fail(HC_ERR_ARG, "spin-up solves with a noise correlation set: set the correlation after the spin-up");
     if (a->spinup && h->noise_host())
         return fail(HC_ERR_ARG, "spin-up solves with the EnKF's noise field on in a Philox run: set it after the spin-up");
     const bool filt_on = h->filt_stride > 0 && !a->spinup;
@@ -5337,6 +5581,8 @@ int hc_spinup(hc_handle *h, hc_spinup_args *a)
     if (a->max_iterations < 1 || a->max_iterations > 1000000) return fail(HC_ERR_ARG, "max_iterations out of range");
     if (h->filt_host())
         return fail(HC_ERR_ARG, "hc_spinup with the particle filter on in a Philox run: set the filter after the spin-up");
+    if (h->corr_host())
+        return fail(HC_ERR_ARG, "hc_spinup with a noise correlation set: set the correlation after the spin-up");
     if (h->noise_host())
         return fail(HC_ERR_ARG, "hc_spinup with the EnKF's noise field on in a Philox run: set it after the spin-up");
     HIP_TRY(hipSetDevice(h->device));
@@ -5898,17 +6144,13 @@ int hc_set_filter(hc_handle *h, int32_t stride, double sigma_cm, uint64_t seed)
     h->filt_sigma = sigma_cm;
     h->filt_seed = seed;
     int rc = ensure_filter(h);
-    if (rc == HC_OK && h->philox) {
+    if (rc == HC_OK && h->philox && !h->ncorr) {
         // the base vectors the kernel's Philox path would build, z * scale (one rounding), from here on carried like
-        // the caller's: damped in place, copied from the ancestor
+        // the caller's: damped in place, copied from the ancestor (a correlated source's are in place already)
         const size_t total = (size_t)h->n_members * h->p.dim_d;
         rc = h->base.ensure(total);
+        if (rc == HC_OK) rc = launch_noise_fill(h, h->base.p, 1, nullptr, h->nscale.p);
         if (rc == HC_OK) {
-            const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)h->n_cu * 64);
-            hipLaunchKernelGGL(filter_philox_fill_kernel, dim3(blocks), dim3(256), 0, h->stream, h->base.p, 1ll, nullptr,
-                               h->draw_idx.p, (unsigned long long)h->seed, (long long)h->member_offset,
-                               h->n_points > 1 ? h->point_base.p : nullptr, (long long)A.members_per_point,
-                               (long long)h->n_members, h->p.dim_d, h->nscale.p);
             const hipError_t e = hipGetLastError();
             const hipError_t e2 = hipStreamSynchronize(h->stream);
             if (e != hipSuccess || e2 != hipSuccess)
@@ -6828,16 +7070,12 @@ int hc_set_enkf_noise_field(hc_handle *h, int32_t on, double relaxation)
     h->enkf_nz = true;
     h->enkf_nz_alpha = relaxation;
     int rc = ensure_nz(h);
-    if (rc == HC_OK && h->philox && !was_on) {
+    if (rc == HC_OK && h->philox && !was_on && !h->ncorr) {
         // as hc_set_filter: the base vectors the kernel's Philox path would build, from here on carried like the caller's
         const size_t total = (size_t)h->n_members * h->p.dim_d;
         rc = h->base.ensure(total);
+        if (rc == HC_OK) rc = launch_noise_fill(h, h->base.p, 1, nullptr, h->nscale.p);
         if (rc == HC_OK) {
-            const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)h->n_cu * 64);
-            hipLaunchKernelGGL(filter_philox_fill_kernel, dim3(blocks), dim3(256), 0, h->stream, h->base.p, 1ll, nullptr,
-                               h->draw_idx.p, (unsigned long long)h->seed, (long long)h->member_offset,
-                               h->n_points > 1 ? h->point_base.p : nullptr, (long long)A.members_per_point,
-                               (long long)h->n_members, h->p.dim_d, h->nscale.p);
             const hipError_t e = hipGetLastError();
             const hipError_t e2 = hipStreamSynchronize(h->stream);
             if (e != hipSuccess || e2 != hipSuccess)
@@ -7002,6 +7240,10 @@ int hc_set_noise_scale(hc_handle *h, const double *scale, int64_t first, int64_t
     if (h->filt_host())
         return fail(HC_ERR_ARG, "hc_set_noise_scale: the particle filter is on and the base vectors carry the damping "
                                 "(set the scales before hc_set_filter, or the vectors with hc_set_filter_base)");
+    if (h->corr_host())
+        return fail(HC_ERR_ARG, "hc_set_noise_scale: a noise correlation is set and the base vectors carry the damping "
+                                "(set the scales, like the spin-up, before the correlation: set the correlation after the "
+                                "spin-up; or the vectors with hc_set_noise_field_base)");
     if (h->noise_host())
         return fail(HC_ERR_ARG, "hc_set_noise_scale: the EnKF's noise field is on and the base vectors carry the damping "
                                 "(set the scales before hc_set_enkf_noise_field, or the vectors with hc_set_enkf_noise_base)");
@@ -7018,7 +7260,7 @@ int hc_set_point_member_bases(hc_handle *h, const int64_t *base)
 {
     if (!h) return fail(HC_ERR_ARG, "NULL handle");
     if (!h->have_column) return fail(HC_ERR_ARG, "hc_set_column must come first");
-    if (h->filt_stride > 0 || h->enkf_stride > 0) {   // the points' stream keys change: the filters are off
+    if (h->filt_stride > 0 || h->enkf_stride > 0 || h->ncorr) {   // the points' stream keys change: the filters are off
         HIP_TRY(hipSetDevice(h->device));
         HIP_TRY(hipStreamSynchronize(h->stream));
         assimilation_off(h);

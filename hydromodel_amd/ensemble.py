@@ -10,6 +10,7 @@ import numpy as np
 
 from .digest import inverse_retention
 from .stepper import enkf_noise_summary, noise_field_settings
+from .stepper import noise_correlation_breaks, noise_correlation_settings, noise_correlation_tables
 from .stepper import (ASSIM_TABLES, ENKF_METHODS, EnsembleStepper, enkf_sm_summary, enkf_summary,
                       enkf_window_settings, enkf_window_summary, filter_sm_summary, filter_summary,
                       filter_window_settings, filter_window_summary, rejuvenation_discount,
@@ -148,6 +149,10 @@ class _Run:
     enkf_window_offsets: rows before each analysis row (integers in [1, enkf_stride), e.g. (12, 24, 36)) on which the
     well's record joins that analysis too -- the asynchronous EnKF (include/hydrocol.h hc_set_enkf_window);
     :meth:`enkf_window_table`, the ``window_*`` keys of :meth:`enkf_summary`.
+    noise_correlation: {"length_cm": l, "layers": bool} or None: the Philox source's base and refresh vectors become
+    exponentially correlated fields of unit variance down the column (include/hydrocol.h hc_set_noise_correlation),
+    with ``layers`` independent across the interfaces of ``cols.layers`` inside the column; applied after the spin-up
+    and before the filters, one table per point.  Not with noise="numpy" nor with filter_rejuvenation.
     ``_lead`` is the leading shape of the per-point tables: () for an ensemble, (P,) for a sweep."""
 
     _lead = ()
@@ -230,6 +235,41 @@ class _Run:
             if not self.enkf_stride:
                 raise ValueError("enkf_noise_field needs the EnKF (enkf_stride > 0)")
             self.stepper.set_enkf_noise_field(True, self.enkf_noise_relaxation)
+
+    @staticmethod
+    def _check_noise_correlation(who, noise_correlation, noise, filter_rejuvenation):
+        """(length_cm, layers) or None, before any handle is made."""
+        settings = noise_correlation_settings(noise_correlation)
+        if settings is not None and noise == "numpy":
+            raise ValueError(f" {who}: noise_correlation serves the Philox noise source; a noise='numpy' caller shapes "
+                             f"its own vectors (stepper.noise_correlate).")
+        if settings is not None and rejuvenation_discount(filter_rejuvenation):
+            raise ValueError(f" {who}: noise_correlation and filter_rejuvenation exclude each other: the jitter is white per "
+                             f"node and would erode the correlation by a share h^2 per move.")
+        return settings
+
+    def _start_noise_correlation(self, settings, points):
+        """Correlate the Philox vectors (include/hydrocol.h hc_set_noise_correlation): after the spin-up, before the filter,
+        the EnKF's noise field and the tables; one table per point from that point's layers."""
+        self.noise_correlation = None
+        self.noise_correlation_a = self.noise_correlation_b = None
+        self.noise_correlation_breaks_cm = ()
+        if settings is None:
+            return
+        length, layers = settings
+        breaks = [noise_correlation_breaks(c.layers, c.z) if layers else () for c in points]
+        ab = [noise_correlation_tables(c.z, length, br) for c, br in zip(points, breaks)]
+        a, b = np.stack([t[0] for t in ab]), np.stack([t[1] for t in ab])
+        self.stepper.set_noise_correlation(a, b)
+        self.noise_correlation = {"length_cm": length, "layers": layers}
+        self.noise_correlation_a = a.reshape(self._lead + a.shape[1:])          # [D]; a sweep: [P][D]
+        self.noise_correlation_b = b.reshape(self._lead + b.shape[1:])
+        self.noise_correlation_breaks_cm = tuple(breaks) if self._lead else breaks[0]
+
+    def noise_correlation_break_count(self):
+        """Breaks of the recursion below node 0, over all points."""
+        a = np.asarray(self.noise_correlation_a).reshape(-1, self.cols.dim_d)
+        return int((a[:, 1:] == 0.0).sum())
 
     def assim_table(self, key):
         """The handle's assimilation table ``key`` (stepper.ASSIM_TABLES): [n_arow] + its trailing shape, a sweep:
@@ -490,7 +530,8 @@ class EnsembleSimulation(_Run):
                  enkf_window_offsets=(), enkf_shard=None, filter_shard=None, filter_soil_moisture=None,
                  theta_hist_bins=0, storage_layers_cm=None, storage_bins=0, period_ends=None, period_thresholds_cm=(),
                  period_bins=0, period_flux_max_cm=(16.0, 4.0), filter_ess_floor=0.0, filter_window_offsets=(),
-                 enkf_noise_field=None, filter_rejuvenation=0.0):
+                 enkf_noise_field=None, filter_rejuvenation=0.0, noise_correlation=None):
+        corr = self._check_noise_correlation("EnsembleSimulation", noise_correlation, noise, filter_rejuvenation)
         if enkf_shard is not None and noise_field_settings(enkf_noise_field, 0.0) is not None:
             raise ValueError("enkf_shard and enkf_noise_field exclude each other: the exchanged partials cover psi only")
         if filter_shard is not None and rejuvenation_discount(filter_rejuvenation):
@@ -511,6 +552,7 @@ class EnsembleSimulation(_Run):
             from . import _lib
             _lib.load(with_torch=True)             # torch before the library: the shard's buffer is a torch tensor
         self._start(cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup)
+        self._start_noise_correlation(corr, [cols])
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
                            enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins, storage_layers_cm,
@@ -678,6 +720,14 @@ class EnsembleSimulation(_Run):
             if self.enkf_noise_relaxation is not None:    # the analysed vectors carry the damping too (as a filtered run's)
                 arrays["enkf_noise_relaxation"] = np.array(self.enkf_noise_relaxation, dtype=np.float64)
                 arrays["enkf_noise_base"] = self.stepper.enkf_noise_base()
+        if self.noise_correlation is not None:            # (a run without one keeps its key set)
+            arrays["noise_correlation_length_cm"] = np.array(self.noise_correlation["length_cm"], dtype=np.float64)
+            arrays["noise_correlation_layers"] = np.array(int(self.noise_correlation["layers"]), dtype=np.int64)
+            arrays["noise_correlation_a"] = np.asarray(self.noise_correlation_a, dtype=np.float64)
+            arrays["noise_correlation_b"] = np.asarray(self.noise_correlation_b, dtype=np.float64)
+            if not self.filter_stride and self.enkf_noise_relaxation is None:
+                # the base vectors carry the damping, as a filtered run's; those runs' own keys hold them already
+                arrays["noise_field_base"] = self.stepper.noise_field_base()
         for key in self.assim_tables_on():                # the filters' tables: one dataset each, <key>_table
             arrays[key + "_table"] = self.stepper.assim_table(key)
         path = Path(path)
@@ -756,9 +806,16 @@ class EnsembleSimulation(_Run):
         has_win = enkf and "enkf_window_offsets" in data
         if has_win:
             fkw.update(enkf_window_offsets=tuple(int(o) for o in np.asarray(data["enkf_window_offsets"]).reshape(-1)))
+        has_corr = "noise_correlation_length_cm" in data
+        if has_corr:
+            fkw.update(noise_correlation={"length_cm": float(data["noise_correlation_length_cm"]),
+                                          "layers": bool(int(data["noise_correlation_layers"]))})
         sim = cls(cols, forcing, n, seed=int(data["seed"]), device=device, member_offset=int(data["member_offset"]),
                   psi0=np.asarray(data["initial_cond"], dtype=float).reshape(-1)[:D], flags=flags, profile_stride=stride,
                   wtd_hist_stride=hist_stride, theta_hist_bins=theta_bins, **(fkw_storage if storage else {}), **fkw)
+        if has_corr and not (np.array_equal(np.asarray(data["noise_correlation_a"]).reshape(-1), sim.noise_correlation_a)
+                             and np.array_equal(np.asarray(data["noise_correlation_b"]).reshape(-1), sim.noise_correlation_b)):
+            raise ValueError(f" EnsembleSimulation: {path} holds the noise correlation's tables of another column.")
         sim.stepper.set_state(psi if n > 1 else psi[0])
         for key in sim.assim_tables_on():                 # the tables the constructor turned on, each from <key>_table
             sim.stepper.set_assim_table(key, np.asarray(data[key + "_table"], dtype=np.float64))
@@ -769,6 +826,8 @@ class EnsembleSimulation(_Run):
                                                       np.asarray(data["filter_window_rows"], dtype=np.int64))
         elif has_nz:
             sim.stepper.set_enkf_noise_base(np.asarray(data["enkf_noise_base"], dtype=np.float64).reshape(n, D))
+        elif has_corr:
+            sim.stepper.set_noise_field_base(np.asarray(data["noise_field_base"], dtype=np.float64).reshape(n, D))
         else:
             sim.stepper.set_noise_scale(np.asarray(data["noise_scale"], dtype=float).reshape(n))
         if has_win:
@@ -887,7 +946,8 @@ class SweepSimulation(_Run):
                  enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=(),
                  filter_soil_moisture=None, theta_hist_bins=0, storage_layers_cm=None, storage_bins=0, period_ends=None,
                  period_thresholds_cm=(), period_bins=0, period_flux_max_cm=(16.0, 4.0), filter_ess_floor=0.0,
-                 filter_window_offsets=(), enkf_noise_field=None, filter_rejuvenation=0.0):
+                 filter_window_offsets=(), enkf_noise_field=None, filter_rejuvenation=0.0, noise_correlation=None):
+        corr = self._check_noise_correlation("SweepSimulation", noise_correlation, "philox", filter_rejuvenation)
         self.points = list(cols_list)
         self.P, self.n = len(self.points), int(n_members)
         self._lead = (self.P,)
@@ -914,6 +974,7 @@ class SweepSimulation(_Run):
         self.stepper.set_noise_philox(self.seed, self.member_offset)
         if self.P > 1:
             self.stepper.set_point_member_bases(self.bases)
+        self._start_noise_correlation(corr, self.points)
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
                            enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins, storage_layers_cm,

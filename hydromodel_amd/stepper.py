@@ -90,6 +90,7 @@ class EnsembleStepper:
         self.enkf_method, self.enkf_relaxation = "stochastic", 0.0
         self.enkf_window_offsets = ()
         self.enkf_noise_field, self.enkf_noise_relaxation = False, 0.0
+        self.noise_corr = None
         self.philox = False
         self.device = int(device)
         self.enkf_shard, self._shard_keep, self._shard_error = None, None, None
@@ -150,6 +151,54 @@ class EnsembleStepper:
         out = np.empty(self.D)
         L.check(self.lib.hc_philox_normals(self.h, int(member), int(draw), L.dptr(out)))
         return out
+
+    # -- correlated noise fields (include/hydrocol.h hc_set_noise_correlation) ------------------------------------------
+    def set_noise_correlation(self, a, b=None):
+        """Correlate the Philox source's vectors down the column by the recursion of :func:`noise_correlate` with the
+        tables ``a``, ``b`` ([D] for every point, or [P][D]; :func:`noise_correlation_tables` builds them); ``None``
+        turns it off.  Needs a Philox run.  The handle then feeds the step kernel its own normals as caller noise: set
+        it after the spin-up and before a particle filter or the EnKF's noise field, and :meth:`set_noise_scale` is
+        refused while it is on."""
+        if a is None:
+            L.check(self.lib.hc_set_noise_correlation(self.h, None, None))
+            self.noise_corr = None
+            return
+        if b is None:
+            raise ValueError("the noise correlation needs both tables, a and b")
+        a, b = L.as_f64(a), L.as_f64(b)
+        if a.shape == (self.D,) and b.shape == (self.D,):
+            a, b = L.as_f64(np.tile(a, (self.P, 1))), L.as_f64(np.tile(b, (self.P, 1)))
+        if a.shape != (self.P, self.D) or b.shape != (self.P, self.D):
+            raise ValueError(f"the noise correlation's tables must be [{self.D}] or [{self.P}, {self.D}], got {a.shape} and {b.shape}")
+        self.noise_corr = None                   # (hc_set_noise_correlation leaves it off if it refuses)
+        L.check(self.lib.hc_set_noise_correlation(self.h, L.dptr(a), L.dptr(b)))
+        self.noise_corr = (a.copy(), b.copy())
+
+    def noise_correlation(self):
+        """``None`` while it is off, else the tables (a, b), each [P][D], as the library holds them."""
+        on = np.zeros(1, dtype=np.int32)
+        a, b = np.zeros((self.P, self.D)), np.zeros((self.P, self.D))
+        L.check(self.lib.hc_get_noise_correlation(self.h, L.iptr(on), L.dptr(a), L.dptr(b)))
+        return (a, b) if on[0] else None
+
+    def noise_field_normals(self, member, draw):
+        """[D] what the noise source now yields for (member, draw), unscaled (test hook): :meth:`philox_normals` run
+        through the correlation when one is set."""
+        out = np.empty(self.D)
+        L.check(self.lib.hc_noise_field_normals(self.h, int(member), int(draw), L.dptr(out)))
+        return out
+
+    def noise_field_base(self):
+        """[N][D] base noise vectors of a Philox run with a correlation set (a checkpoint's)."""
+        out = np.empty((self.N, self.D))
+        L.check(self.lib.hc_get_noise_field_base(self.h, L.dptr(out), 0, self.N))
+        return out
+
+    def set_noise_field_base(self, base):
+        base = L.as_f64(base)
+        if base.shape != (self.N, self.D):
+            raise ValueError(f"base noise must be [{self.N}, {self.D}]")
+        L.check(self.lib.hc_set_noise_field_base(self.h, L.dptr(base)))
 
     # -- stepping ------------------------------------------------------------------
     def n_refresh(self, row_begin, n_rows):
@@ -608,6 +657,7 @@ class EnsembleStepper:
         self.enkf_shard = None
         self.enkf_noise_field, self.enkf_noise_relaxation = False, 0.0
         self.filter_shard, self._filter_shard_keep = None, None
+        self.noise_corr = None                                                   # ... and the noise correlation
 
     # -- the assimilation tables: one path for the nine of them (ASSIM_TABLES below) -------------------------------------
     def assim_table(self, key):
@@ -2301,6 +2351,79 @@ def enkf_noise_summary(table, stride, relaxation, D=None):
             "noise_rejected": np.nan_to_num(rej[..., slots]).astype(np.int64),
             "noise_spread_ratio": float(ratio[ok].mean()) if ok.any() else float("nan"),
             "noise_relaxation": float(relaxation)}
+
+
+# ---- correlated noise fields (include/hydrocol.h hc_set_noise_correlation) ---------------------------------------------
+def noise_correlation_length(length_cm):
+    """The correlation length as a float; a ValueError unless it is a finite number > 0 (a bool is none)."""
+    if isinstance(length_cm, (bool, np.bool_)) or not isinstance(length_cm, (int, float, np.integer, np.floating)):
+        raise ValueError(f"noise correlation length_cm = {length_cm!r} must be a finite number > 0")
+    length = float(length_cm)
+    if not (np.isfinite(length) and length > 0.0):
+        raise ValueError(f"noise correlation length_cm = {length_cm!r} must be a finite number > 0")
+    return length
+
+
+def noise_correlation_tables(z, length_cm, breaks_cm=()):
+    """(a, b), each [D]: the recursion's coefficients for the exponential covariance exp(-|z_i - z_j| / length_cm) on
+    the grid ``z`` -- a_i = rho_i = exp(-(z_i - z_{i-1}) / length_cm), b_i = sqrt(1 - rho_i rho_i) -- with a_0 = 0 and a
+    break (a_i = 0, b_i = 1) at node i >= 1 wherever z[i-1] < L <= z[i] for an L of ``breaks_cm``: the first node at or
+    below the depth, the rule of :func:`sensor_nodes`.  A break outside (z[0], z[-1]] falls on no node."""
+    length = noise_correlation_length(length_cm)
+    z = np.asarray(z, dtype=np.float64).reshape(-1)
+    if z.size < 1 or not np.all(np.isfinite(z)) or np.any(np.diff(z) <= 0.0):
+        raise ValueError("noise correlation: z must be finite and strictly increasing")
+    a, b = np.zeros(z.size), np.ones(z.size)
+    rho = np.exp(-np.diff(z) / length)
+    a[1:], b[1:] = rho, np.sqrt(1.0 - rho * rho)
+    if np.any(a[1:] >= 1.0) or np.any(b[1:] <= 0.0):
+        raise ValueError(f"noise correlation length_cm = {length_cm!r} is too long for this grid: rho rounds to 1")
+    for lv in np.asarray(breaks_cm, dtype=np.float64).reshape(-1):
+        if not np.isfinite(lv):
+            raise ValueError(f"noise correlation break {float(lv)!r} cm is not finite")
+        i = np.flatnonzero((z[:-1] < lv) & (lv <= z[1:])) + 1
+        a[i], b[i] = 0.0, 1.0
+    return a, b
+
+
+def noise_correlate(xi, a, b):
+    """The field of the white vectors ``xi`` [..., D] under the tables ``a``, ``b`` [D] (or broadcastable to xi), the
+    library's recursion to the bit: z_0 = xi_0; z_i = xi_i where a_i == 0 (copied, not computed), else
+    (a_i z_{i-1}) + (b_i xi_i), sequentially along the last axis."""
+    xi = np.asarray(xi, dtype=np.float64)
+    a = np.broadcast_to(np.asarray(a, dtype=np.float64), xi.shape)
+    b = np.broadcast_to(np.asarray(b, dtype=np.float64), xi.shape)
+    z = xi.copy()
+    for i in range(1, xi.shape[-1]):
+        step = (a[..., i] * z[..., i - 1]) + (b[..., i] * xi[..., i])
+        z[..., i] = np.where(a[..., i] == 0.0, xi[..., i], step)
+    return z
+
+
+def noise_correlation_breaks(layers, z):
+    """The interfaces of ``cols.layers`` (soil, saprolite, weathered, fresh: cm) that lie inside the column ``z``: the
+    saprolite's and the weathered bedrock's tops, and the soil's if it is > 0."""
+    z = np.asarray(z, dtype=np.float64)
+    tops = [float(layers[0]), float(layers[1]), float(layers[2])]
+    return tuple(t for k, t in enumerate(tops) if (k > 0 or t > 0.0) and z[0] < t <= z[-1])
+
+
+def noise_correlation_settings(value):
+    """The ``noise_correlation=`` argument of EnsembleSimulation / SweepSimulation: ``None`` or
+    ``{"length_cm": l, "layers": bool}`` -> ``None`` or (length_cm, layers)."""
+    if value is None:
+        return None
+    if not isinstance(value, dict):
+        raise ValueError(f"noise_correlation must be a dict {{'length_cm': ..., 'layers': ...}} or None, got {value!r}")
+    unknown = sorted(set(value) - {"length_cm", "layers"})
+    if unknown:
+        raise ValueError(f"noise_correlation: unknown key(s) {unknown} (known: 'length_cm', 'layers')")
+    if "length_cm" not in value:
+        raise ValueError("noise_correlation needs 'length_cm'")
+    layers = value.get("layers", False)
+    if not isinstance(layers, (bool, np.bool_)):
+        raise ValueError(f"noise_correlation 'layers' = {layers!r} must be true or false")
+    return noise_correlation_length(value["length_cm"]), bool(layers)
 
 
 # ---- soil-moisture sensors in the EnKF (include/hydrocol.h hc_set_enkf_soil_moisture) ----------------------------------

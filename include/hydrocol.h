@@ -194,6 +194,47 @@ int hc_set_noise_philox(hc_handle *h, uint64_t seed, int64_t member_offset);
 /* What the Philox source yields for (member, draw): out[D] (test hook). */
 int hc_philox_normals(hc_handle *h, int64_t member, int64_t draw, double *out);
 
+/* Correlated noise fields: a vertical correlation of the Philox source's vectors.
+ * For a member and a draw, xi [D] is what hc_philox_normals returns.  Two coefficient vectors a [D] and b [D] per
+ * parameter point define the field z [D], in fp64 with contraction off (one product, one product, one sum):
+ *     z_0 = xi_0
+ *     z_i = xi_i                               where a_i == 0  (a break: the recursion restarts; a copy, no arithmetic)
+ *     z_i = (a_i * z_{i-1}) + (b_i * xi_i)     otherwise
+ * sequentially down the column, so the bits are defined by the tables alone (stepper.noise_correlate restates it in
+ * NumPy).  With a_i = rho = exp(-dz / l) and b_i = sqrt(1 - rho rho) this is the exact Cholesky factor of the exponential
+ * covariance exp(-|z_i - z_j| / l): every node's variance is 1, so sigma_noise and the noise coefficients keep their
+ * meaning; a break makes the two sides independent (a layer interface).
+ *   The base vector is z of draw 0 times the member's damping scale (one rounding, as the filter's fill), a refresh row's
+ *   vector is z of that row's draw index, spin-up vectors stay white.  The handle fills these vectors itself
+ *   (noise_field_fill_kernel: Philox, recursion and store in one pass) and runs the step kernel's caller-noise path, as
+ *   with the particle filter in a Philox run: the x0.8 damping mutates the base vector in place; the particle filter
+ *   copies it with psi; the EnKF's noise field analyses it like any other.  A launch stages at most 4 GiB of refresh
+ *   vectors.  Not modelled: correlation in time between a refresh vector and the base, a correlated rejuvenation jitter,
+ *   correlated spin-up vectors, other covariances, host-noise runs (such a caller shapes its own vectors).
+ * hc_set_noise_correlation: tables [n_points][D]; a == NULL turns it off (the in-kernel source again; the damping the
+ *   base vectors took meanwhile is not carried into the scales; under a filter or the noise field their base stays and
+ *   the refresh vectors are white again).  Needs a Philox run (hc_set_noise_philox first, and the
+ *   column, forcing, members and state in place).  HC_ERR_ARG for host noise, a non-finite entry, a_i outside [0, 1),
+ *   b_i <= 0, a_0 != 0, |a_i^2 + b_i^2 - 1| > 1e-12 where a_i != 0, b_i != 1 where a_i == 0, or the particle filter or the
+ *   EnKF's noise field already on (their base vectors carry history: set the correlation first); a refused call leaves
+ *   the correlation off.  On success base
+ *   [N][D] is allocated and filled with the correlated draw 0 times the current scales; hc_set_filter and
+ *   hc_set_enkf_noise_field called afterwards keep that base instead of refilling it.  While it is on, hc_spinup,
+ *   spin-up solves of hc_step_rows and hc_set_noise_scale are refused: set the correlation after the spin-up.  Turned off
+ *   by whatever resets the noise source: hc_set_noise_philox, hc_set_noise_host, hc_set_members, hc_set_column /
+ *   hc_add_point, hc_set_point_member_bases.  With nothing set, nothing is launched or allocated.
+ * hc_get_noise_correlation: on, and the tables when on (a, b may be NULL).
+ * hc_noise_field_normals: what the source now yields for (member, draw), unscaled (test hook; member is the stream's
+ *   key as in hc_philox_normals, and with several points the table is that of the point whose keys hold it).  With the
+ *   correlation off it is hc_philox_normals.
+ * hc_get/set_noise_field_base: the base vectors [N][D] (a checkpoint) while a correlation is on in a Philox run; with a
+ *   filter or the noise field on their own accessors read and write the same vectors. */
+int hc_set_noise_correlation(hc_handle *h, const double *a, const double *b);
+int hc_get_noise_correlation(hc_handle *h, int32_t *on, double *a, double *b);
+int hc_noise_field_normals(hc_handle *h, int64_t member, int64_t draw, double *out);
+int hc_get_noise_field_base(hc_handle *h, double *base, int64_t first_member, int64_t count);
+int hc_set_noise_field_base(hc_handle *h, const double *base);
+
 typedef struct {
     int64_t row_begin;      /* first row to solve (row i integrates t in [i-1, i]); >= 1      */
     int64_t n_rows;
