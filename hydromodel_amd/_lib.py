@@ -211,13 +211,17 @@ EXPORTS = {
                             C.c_int),
     "hc_get_filter_shard": ([C.c_void_p, _ip, _ip, _lp], C.c_int),
     "hc_rhs": ([C.c_void_p, C.c_int64, C.c_int32, _dp, _dp], C.c_int),
+    "hc_rhs_ex": ([C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _dp, _dp, _dp], C.c_int),
     "hc_model_nodes": ([C.c_void_p, _dp, _dp], C.c_int),
     "hc_plugin_eval": ([C.c_int, C.POINTER(ColumnParams), C.c_int64, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
                        C.c_int),
 }
 
+# hc_rhs_ex's `variant` (include/hydrocol.h: HC_RHS_HOOK, HC_RHS_AS_STEPPED, HC_RHS_HOOK_LAYOUT)
+RHS_VARIANTS = {"hook": 0, "step": 1, "hook_layout": 2}
+
 _lib = None
-_torch_first = False        # torch was in the process before the library: the two use ONE HIP runtime (torch's)
+_torch_first = False       # torch was in the process before the library: the two use ONE HIP runtime (torch's)
 
 
 def load(with_torch=False):

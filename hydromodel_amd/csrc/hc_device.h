@@ -1374,7 +1374,7 @@ __device__ __forceinline__ void rhs_eval(const ColumnDev &P, const RowDev &R, co
             aux[2 * (D - 1) + i] = fl[c];
         }
     }
-    if (aux && lane == 0) aux[3 * (D - 1)] = pL;
+    if (aux && lane == 0 && upper) aux[3 * (D - 1)] = pL;     // (a split column's lower half never holds pL)
 }
 
 }  // namespace hc

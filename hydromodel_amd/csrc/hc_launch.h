@@ -16,6 +16,7 @@ struct LaunchCfg {
     unsigned grid;       // workgroups
     bool special;        // every parameter point has the default exponents (n = 2, m = 1/2, lambda = 1, vrettas_fung)
     bool predict;        // repaired PREDICT lateral flow compiled in
+    bool as_stepped = false;   // RHS hook only: rhs_eval as the step kernel of this unit instantiates it (ONE_BALLOT = two_of(...))
 };
 
 inline size_t step_lds_bytes(int cpl, int wpb, int halves = 1, bool special = true)
@@ -35,28 +36,37 @@ inline size_t rhs_lds_bytes(int cpl, int wpb)
 // count AND one cell model (specialised / generic exponents), so that each can be compiled with its own scheduler settings
 template <int CPL, bool SPECIAL> hipError_t launch_step_part(const LaunchCfg &cfg, const StepArgs &A);
 template <int CPL, bool SPECIAL> hipError_t launch_rhs_part(const LaunchCfg &cfg, const StepArgs &A, long long row, double *dydt,
-                                                            double *aux);
+                                                            double *aux, double *diag);
+// ... the hook in the instantiation the unit's step kernel runs (cfg.as_stepped), where that is not the plain one: defined
+// by the unit's -DHC_INST_RHS_STEP translation unit, which exists for exactly the units with two_of(CPL, 1, SPECIAL)
+template <int CPL, bool SPECIAL> hipError_t launch_rhs_step_part(const LaunchCfg &cfg, const StepArgs &A, long long row, double *dydt,
+                                                                 double *aux, double *diag);
 template <int CPL> inline hipError_t launch_step_cpl(const LaunchCfg &cfg, const StepArgs &A)
 {
     return cfg.special ? launch_step_part<CPL, true>(cfg, A) : launch_step_part<CPL, false>(cfg, A);
 }
 template <int CPL> inline hipError_t launch_rhs_cpl(const LaunchCfg &cfg, const StepArgs &A, long long row, double *dydt,
-                                                    double *aux)
+                                                    double *aux, double *diag)
 {
-    return cfg.special ? launch_rhs_part<CPL, true>(cfg, A, row, dydt, aux) : launch_rhs_part<CPL, false>(cfg, A, row, dydt, aux);
+    return cfg.special ? launch_rhs_part<CPL, true>(cfg, A, row, dydt, aux, diag) : launch_rhs_part<CPL, false>(cfg, A, row, dydt, aux, diag);
 }
 // split column: two waves per member, PAIR_CPL nodes per lane each, D in (64 PAIR_CPL, 128 PAIR_CPL]  (hc_inst.hip with
 // -DHC_INST_PAIR)
 constexpr int PAIR_CPL = 5;
 hipError_t launch_step_pair(const LaunchCfg &cfg, const StepArgs &A);
-hipError_t launch_rhs_pair(const LaunchCfg &cfg, const StepArgs &A, long long row, double *dydt);   // test hook, no aux
+hipError_t launch_rhs_pair(const LaunchCfg &cfg, const StepArgs &A, long long row, double *dydt, double *aux, double *diag);   // test hook
+hipError_t launch_rhs_pair_step(const LaunchCfg &cfg, const StepArgs &A, long long row, double *dydt, double *aux, double *diag);   // (its HC_INST_RHS_STEP unit)
 #define HC_DECLARE_CPL(N)                                                                                        \
     template <> hipError_t launch_step_part<N, true>(const LaunchCfg &cfg, const StepArgs &A);                     \
     template <> hipError_t launch_step_part<N, false>(const LaunchCfg &cfg, const StepArgs &A);                    \
     template <> hipError_t launch_rhs_part<N, true>(const LaunchCfg &cfg, const StepArgs &A, long long row, double *dydt, \
-                                                    double *aux);                                                 \
+                                                    double *aux, double *diag);                                   \
     template <> hipError_t launch_rhs_part<N, false>(const LaunchCfg &cfg, const StepArgs &A, long long row, double *dydt, \
-                                                     double *aux);
+                                                     double *aux, double *diag);                                  \
+    template <> hipError_t launch_rhs_step_part<N, true>(const LaunchCfg &cfg, const StepArgs &A, long long row, double *dydt, \
+                                                         double *aux, double *diag);                              \
+    template <> hipError_t launch_rhs_step_part<N, false>(const LaunchCfg &cfg, const StepArgs &A, long long row, double *dydt, \
+                                                          double *aux, double *diag);
 HC_DECLARE_CPL(2) HC_DECLARE_CPL(3) HC_DECLARE_CPL(4) HC_DECLARE_CPL(5) HC_DECLARE_CPL(6)
 HC_DECLARE_CPL(7) HC_DECLARE_CPL(8) HC_DECLARE_CPL(9) HC_DECLARE_CPL(10)
 #undef HC_DECLARE_CPL

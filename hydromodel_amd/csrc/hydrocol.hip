@@ -3219,36 +3219,36 @@ hipError_t launch_step_cpl_any(int cpl, bool &known, const LaunchCfg &cfg, const
     known = false;
     return hipSuccess;
 }
-hipError_t launch_rhs_cpl_any(int cpl, bool &known, const LaunchCfg &cfg, const StepArgs &A, long long row, double *dydt, double *aux)
+hipError_t launch_rhs_cpl_any(int cpl, bool &known, const LaunchCfg &cfg, const StepArgs &A, long long row, double *dydt, double *aux, double *diag)
 {
     known = true;
     switch (cpl) {
 #if (HC_CPL_MASK >> 2) & 1
-        case 2: return launch_rhs_cpl<2>(cfg, A, row, dydt, aux);
+        case 2: return launch_rhs_cpl<2>(cfg, A, row, dydt, aux, diag);
 #endif
 #if (HC_CPL_MASK >> 3) & 1
-        case 3: return launch_rhs_cpl<3>(cfg, A, row, dydt, aux);
+        case 3: return launch_rhs_cpl<3>(cfg, A, row, dydt, aux, diag);
 #endif
 #if (HC_CPL_MASK >> 4) & 1
-        case 4: return launch_rhs_cpl<4>(cfg, A, row, dydt, aux);
+        case 4: return launch_rhs_cpl<4>(cfg, A, row, dydt, aux, diag);
 #endif
 #if (HC_CPL_MASK >> 5) & 1
-        case 5: return launch_rhs_cpl<5>(cfg, A, row, dydt, aux);
+        case 5: return launch_rhs_cpl<5>(cfg, A, row, dydt, aux, diag);
 #endif
 #if (HC_CPL_MASK >> 6) & 1
-        case 6: return launch_rhs_cpl<6>(cfg, A, row, dydt, aux);
+        case 6: return launch_rhs_cpl<6>(cfg, A, row, dydt, aux, diag);
 #endif
 #if (HC_CPL_MASK >> 7) & 1
-        case 7: return launch_rhs_cpl<7>(cfg, A, row, dydt, aux);
+        case 7: return launch_rhs_cpl<7>(cfg, A, row, dydt, aux, diag);
 #endif
 #if (HC_CPL_MASK >> 8) & 1
-        case 8: return launch_rhs_cpl<8>(cfg, A, row, dydt, aux);
+        case 8: return launch_rhs_cpl<8>(cfg, A, row, dydt, aux, diag);
 #endif
 #if (HC_CPL_MASK >> 9) & 1
-        case 9: return launch_rhs_cpl<9>(cfg, A, row, dydt, aux);
+        case 9: return launch_rhs_cpl<9>(cfg, A, row, dydt, aux, diag);
 #endif
 #if (HC_CPL_MASK >> 10) & 1
-        case 10: return launch_rhs_cpl<10>(cfg, A, row, dydt, aux);
+        case 10: return launch_rhs_cpl<10>(cfg, A, row, dydt, aux, diag);
 #endif
         default: break;
     }
@@ -3296,21 +3296,26 @@ int launch_step(hc_handle *h, const StepArgs &A)
     return HC_OK;
 }
 
-int launch_rhs(hc_handle *h, const StepArgs &A, long long row, double *dydt, double *aux)
+// variant (include/hydrocol.h, hc_rhs_ex): HC_RHS_HOOK keeps a split column's c | s | f view on the one-wave hook, as
+// hc_rhs always has; the other two follow the step kernel's routing, with the step kernel's rhs_eval (HC_RHS_AS_STEPPED)
+// or the plain one (HC_RHS_HOOK_LAYOUT)
+int launch_rhs(hc_handle *h, const StepArgs &A, long long row, int variant, double *dydt, double *aux, double *diag)
 {
     const int wpb = wpb_of(h->cpl, 1, h->use_special());
-    if (h->use_pair() && !aux) {          // the split-column code path (the c | s | f view stays with the one-wave hook)
+    if (h->use_pair() && (!aux || variant != HC_RHS_HOOK)) {          // the split-column code path
         StepArgs B = A;
         B.tab = h->tab_pair.p;
         B.gtab = h->gtab_pair.p;
         const int pairs = wpb_of(PAIR_CPL, 2) / 2;
-        const unsigned grid = (unsigned)((A.n_members + pairs - 1) / pairs);
-        HIP_TRY(launch_rhs_pair(launch_cfg(h, grid), B, row, dydt));
+        LaunchCfg cfg = launch_cfg(h, (unsigned)((A.n_members + pairs - 1) / pairs));
+        cfg.as_stepped = variant == HC_RHS_AS_STEPPED;
+        HIP_TRY(launch_rhs_pair(cfg, B, row, dydt, aux, diag));
         return HC_OK;
     }
-    const unsigned grid = (unsigned)((A.n_members + wpb - 1) / wpb);
+    LaunchCfg cfg = launch_cfg(h, (unsigned)((A.n_members + wpb - 1) / wpb));
+    cfg.as_stepped = variant == HC_RHS_AS_STEPPED;
     bool known = false;
-    const hipError_t err = launch_rhs_cpl_any(h->cpl, known, launch_cfg(h, grid), A, row, dydt, aux);
+    const hipError_t err = launch_rhs_cpl_any(h->cpl, known, cfg, A, row, dydt, aux, diag);
     if (!known) return unknown_depth(h);
     HIP_TRY(err);
     return HC_OK;
@@ -7313,7 +7318,14 @@ int hc_set_scipy_152(hc_handle *h, int32_t on)
 
 int hc_rhs(hc_handle *h, int64_t row, int32_t spinup, double *dydt, double *aux)
 {
+    return hc_rhs_ex(h, row, spinup, HC_RHS_HOOK, dydt, aux, nullptr);
+}
+
+int hc_rhs_ex(hc_handle *h, int64_t row, int32_t spinup, int32_t variant, double *dydt, double *aux, double *diag)
+{
     if (!h || !dydt) return fail(HC_ERR_ARG, "hc_rhs: NULL argument");
+    if (variant != HC_RHS_HOOK && variant != HC_RHS_AS_STEPPED && variant != HC_RHS_HOOK_LAYOUT)
+        return fail(HC_ERR_ARG, "hc_rhs_ex: variant %d (0 = hook, 1 = as stepped, 2 = hook on the step kernel's layout)", (int)variant);
     StepArgs A;
     int rc = fill_args(h, A);
     if (rc) return rc;
@@ -7322,18 +7334,21 @@ int hc_rhs(hc_handle *h, int64_t row, int32_t spinup, double *dydt, double *aux)
     HIP_TRY(hipSetDevice(h->device));
     const int D = h->p.dim_d;
     const size_t n = (size_t)h->n_members * D, na = (size_t)h->n_members * (3 * (D - 1) + 1);
-    if (h->scratch_d.ensure(n + (aux ? na : 0))) return HC_ERR_DEVICE;
+    const size_t nd = (size_t)h->n_members * 2;
+    if (h->scratch_d.ensure(n + na + nd)) return HC_ERR_DEVICE;
+    double *const aux_d = h->scratch_d.p + n, *const diag_d = aux_d + na;
     A.spinup = spinup;
     rc = push_io(h);
     if (rc) return rc;
 #ifdef HC_PROFILE
     if (const char *e = getenv("HYDROCOL_RHS_REPEAT")) A.n_rows = atoll(e);
 #endif
-    rc = launch_rhs(h, A, row, h->scratch_d.p, aux ? h->scratch_d.p + n : nullptr);
+    rc = launch_rhs(h, A, row, variant, h->scratch_d.p, aux ? aux_d : nullptr, diag ? diag_d : nullptr);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipMemcpy(dydt, h->scratch_d.p, n * 8, hipMemcpyDeviceToHost));
-    if (aux) HIP_TRY(hipMemcpy(aux, h->scratch_d.p + n, na * 8, hipMemcpyDeviceToHost));
+    if (aux) HIP_TRY(hipMemcpy(aux, aux_d, na * 8, hipMemcpyDeviceToHost));
+    if (diag) HIP_TRY(hipMemcpy(diag, diag_d, nd * 8, hipMemcpyDeviceToHost));
     return HC_OK;
 }
 

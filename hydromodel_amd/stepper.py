@@ -1297,14 +1297,26 @@ class EnsembleStepper:
         L.check(self.lib.hc_spinup(self.h, C.byref(a)))
         return iters, a.kernel_ms
 
-    def rhs(self, row, spinup=False, want_aux=False):
+    def rhs(self, row, spinup=False, want_aux=False, variant="hook", want_diag=False):
+        """dy/dt of every member's state on forcing row `row` (hc_rhs_ex).  `variant`: "hook" -- rhs_eval's plain
+        instantiation; "step" -- the instantiation and wave layout of this handle's step kernel; "hook_layout" -- the
+        plain instantiation on the step kernel's wave layout (include/hydrocol.h).  Returns dydt [N][D]; with `want_aux`
+        also {"c", "s", "f": [N][D-1], "pL": [N]}; with `want_diag` that dict also holds "diag": [N][2] = transpiration,
+        lateral flow of the evaluation."""
         out = np.empty((self.N, self.D))
         M = self.D - 1
         aux = np.empty((self.N, 3 * M + 1)) if want_aux else None
-        L.check(self.lib.hc_rhs(self.h, int(row), int(spinup), L.dptr(out), L.dptr(aux) if want_aux else None))
-        if not want_aux:
+        diag = np.empty((self.N, 2)) if want_diag else None
+        L.check(self.lib.hc_rhs_ex(self.h, int(row), int(spinup), L.RHS_VARIANTS[variant], L.dptr(out),
+                                   L.dptr(aux) if want_aux else None, L.dptr(diag) if want_diag else None))
+        if not (want_aux or want_diag):
             return out
-        return out, {"c": aux[:, :M], "s": aux[:, M:2 * M], "f": aux[:, 2 * M:3 * M], "pL": aux[:, 3 * M]}
+        extra = {}
+        if want_aux:
+            extra.update(c=aux[:, :M], s=aux[:, M:2 * M], f=aux[:, 2 * M:3 * M], pL=aux[:, 3 * M])
+        if want_diag:
+            extra["diag"] = diag
+        return out, extra
 
     def model_nodes(self):
         out = np.empty((4, self.N, self.D))

@@ -1110,9 +1110,26 @@ int hc_get_point_costs(hc_handle *h, uint64_t *cost);
 
 /* Test hooks -------------------------------------------------------------------------- */
 /* dydt for every member's current state on forcing row `row` (noise = base vectors).
- * aux (nullable): [n_members][3*(D-1)+1] = c | s | f at the midpoints, then pL.  Columns the split-column kernel serves
- * are evaluated on that path (two wavefronts per member) when aux is NULL, on the one-wave path when it is requested. */
+ * aux (nullable): [n_members][3*(D-1)+1] = c | s | f at the midpoints, then pL.
+ * diag (nullable): [n_members][2] = transpiration, lateral flow of this one evaluation -- the two integrals a stepped row
+ * reports for its last evaluation (hc_step_args.diag_out); asking for them changes no other output.
+ *
+ * The device function behind all of it, rhs_eval, exists in two instantiations.  The plain one (ONE_BALLOT = false) is what
+ * the step kernels of one wave per SIMD run: 2, 3, 8, 9, 10 cells per lane, generic exponents from 7 cells.  The step
+ * kernels of the two-waves-per-SIMD layout (two_of in csrc/hc_step.h: default exponents at 4 ... 7 cells per lane, generic
+ * exponents at 4 ... 6, the split column) run the other one (ONE_BALLOT = true): the same values by a shorter
+ * instruction sequence, every shortcut of which claims equal bits.  `variant` selects what is evaluated:
+ *   HC_RHS_HOOK         the plain instantiation.  A split column is evaluated by its two-wavefront kernel when aux is
+ *                       NULL and by the one-wave kernel of its depth when aux is requested.
+ *   HC_RHS_AS_STEPPED   what the handle's step kernel runs: its instantiation on its wave layout (a split column on two
+ *                       wavefronts, with or without aux).  Where two_of is false this is HC_RHS_HOOK's kernel.
+ *   HC_RHS_HOOK_LAYOUT  the plain instantiation on the step kernel's wave layout: HC_RHS_HOOK except that a split column
+ *                       stays on two wavefronts when aux is requested (the partner of HC_RHS_AS_STEPPED in a bit-for-bit
+ *                       comparison of aux there).
+ * hc_rhs(h, row, spinup, dydt, aux) is hc_rhs_ex(h, row, spinup, HC_RHS_HOOK, dydt, aux, NULL). */
+enum { HC_RHS_HOOK = 0, HC_RHS_AS_STEPPED = 1, HC_RHS_HOOK_LAYOUT = 2 };
 int hc_rhs(hc_handle *h, int64_t row, int32_t spinup, double *dydt, double *aux);
+int hc_rhs_ex(hc_handle *h, int64_t row, int32_t spinup, int32_t variant, double *dydt, double *aux, double *diag);
 /* plugin call on the nodes for every member's current state: out [4][n_members][D]
  * = theta, K, C, K_bkg; qinf [n_members] (nullable) */
 int hc_model_nodes(hc_handle *h, double *out, double *qinf);

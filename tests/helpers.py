@@ -31,6 +31,20 @@ def digest(well, model="vrettas_fung", n_years=1):
     return params, cols, forcing
 
 
+def forcing_with_row(forcing, row, precip, atm, daylight, wtd_obs, wet=None):
+    """A copy of the digest whose row `row` carries the given arguments (the golden states were evaluated with
+    explicit (hour, precip, atm, wtd) rather than a row of the synthetic forcing); never a refresh row.
+    `wet`: the row's wet-season flag (None: as the forcing has it)."""
+    import copy
+    f = copy.copy(forcing)
+    for name in ("precip", "atm", "daylight", "wtd_obs", "refresh", "wet_season"):
+        setattr(f, name, np.array(getattr(forcing, name)))
+    f.precip[row], f.atm[row], f.daylight[row], f.wtd_obs[row], f.refresh[row] = precip, atm, int(daylight), wtd_obs, 0
+    if wet is not None:
+        f.wet_season[row] = int(wet)
+    return f
+
+
 @lru_cache(maxsize=None)
 def points():
     """Non-default parameter points of tests/golden/points.json (fixtures g1p/g2p/g34p, synthetic well D=200)."""

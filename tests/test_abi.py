@@ -34,6 +34,19 @@ def test_every_declared_symbol_is_exported(lib):
         assert hasattr(lib, name), name
 
 
+def test_rhs_hook_variants(lib):
+    """hc_rhs_ex: the binding's variant names are the header's enumerators, and a NULL handle is an argument error before
+    anything touches a device (hc_rhs, the same call with variant 0 and no diagnostics, likewise)."""
+    from hydromodel_amd import _lib
+    text = (REPO / "include" / "hydrocol.h").read_text()
+    enum = dict(re.findall(r"(HC_RHS_[A-Z_]+) = (\d+)", text))
+    assert {k: int(v) for k, v in enum.items()} == {"HC_RHS_HOOK": 0, "HC_RHS_AS_STEPPED": 1, "HC_RHS_HOOK_LAYOUT": 2}
+    assert _lib.RHS_VARIANTS == {"hook": 0, "step": 1, "hook_layout": 2}
+    out = (C.c_double * 4)()
+    assert lib.hc_rhs_ex(None, 0, 0, 1, out, None, None) == lib.hc_rhs(None, 0, 0, out, None) != 0
+    assert b"NULL" in lib.hc_last_error()
+
+
 def test_struct_sizes():
     from hydromodel_amd import _lib
     assert C.sizeof(_lib.ColumnParams) == 8 * 4 + 15 * 8 + 2 * 4          # static_assert'ed on the C side

@@ -1,11 +1,9 @@
 """Round-3 GPU checks: every G4 state straight against the reference's solve, the whole year side by side (reference /
 oracle / GPU), BASELINE config 5 at its full size, bit-exact ensemble resume, the in-library RCCL all-reduce."""
-import copy
-
 import numpy as np
 import pytest
 
-from helpers import WELLS, digest, forcing_frame, golden
+from helpers import WELLS, digest, forcing_frame, forcing_with_row, golden
 
 pytestmark = pytest.mark.gpu
 
@@ -19,16 +17,6 @@ def gpu():
     ge.build()
     from hydromodel_amd import stepper
     return stepper
-
-
-def forcing_with_row(forcing, row, precip, atm, daylight, wtd_obs):
-    """A copy of the digest whose row `row` carries the given arguments (the golden states were evaluated with
-    explicit (hour, precip, atm, wtd) rather than a row of the synthetic forcing); never a refresh row."""
-    f = copy.copy(forcing)
-    for name in ("precip", "atm", "daylight", "wtd_obs", "refresh", "wet_season"):
-        setattr(f, name, np.array(getattr(forcing, name)))
-    f.precip[row], f.atm[row], f.daylight[row], f.wtd_obs[row], f.refresh[row] = precip, atm, int(daylight), wtd_obs, 0
-    return f
 
 
 @pytest.mark.parametrize("well", [1, 200, 300, 401, 581])
