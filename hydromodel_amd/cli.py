@@ -49,6 +49,21 @@ unknown keys, only membership of the 12 is checked):
   ``storage_hist_bins``, ``storage_hist_outside``, ``storage_quantile_levels`` and ``storage_quantile_cm``
   ``[T_out][Lv][L]`` (a sweep: a leading ``[P]`` axis on the per-row datasets), and the run ends with the line
   `` [Ensemble xN] storage: L layers on R rows``.
+* ``"Ensemble": {..., "Profiles": 48, "Covariance": {"Node_Stride": 4, "Sensor_Sigma": 0.02}}``: how the nodes of a
+  column and the water table move together, from exact integer second moments accumulated on the GPU on the profile rows
+  (include/hydrocol.h hc_set_theta_cov): theta_vol at every ``Node_Stride``-th node (default 1) quantised to 2^-20 and the
+  members' water-table index, their sums and sums of products over the members -- every other table is a marginal.  From
+  them the covariance of theta(z), its covariance and correlation with the water table and, with ``Sensor_Sigma``
+  (optional: a probe's error in m3/m3, > 0), the fraction of the water table's variance one probe at each node would
+  remove in a linear update, cov(theta_i, wtd)^2 / ((var theta_i + sigma^2) var wtd).  Needs ``"Profiles"`` >= 1; a
+  ``theta_cov`` dataset above 2 GiB is refused (take a larger node stride or a larger profile stride).  The table is summed
+  over the ranks like the profile statistics; with a filter or an EnKF it describes the forecast.  Added to
+  ``<Output_Name>_ensemble.h5``: ``theta_cov_node_stride``, ``theta_cov_nodes``, ``theta_cov_depth_cm`` ``[n]``,
+  ``theta_cov_rows``, ``theta_cov_count``, ``theta_cov_outside`` (members with a theta that was NaN or outside [0, 1]: none
+  in a sound run), ``theta_cov`` ``[T_out][n][n]``, ``wtd_theta_cov_cm`` ``[T_out][n]``, ``wtd_var_cm2`` ``[T_out]``,
+  ``theta_wtd_corr`` ``[T_out][n]`` and, with ``Sensor_Sigma``, ``theta_sensor_sigma`` and ``theta_sensor_gain``
+  ``[T_out][n]`` (a sweep: a leading ``[P]`` axis on the per-row datasets), and the run ends with the line
+  `` [Ensemble xN] covariance: n nodes on R rows``.
 * ``"Ensemble": {..., "Periods": {"Rows": 1440, "Shallower_than_cm": [100, 200], "Bins": 128, "Transpiration_max_cm": 16,
   "Lateral_flow_max_cm": 4, "Quantiles": [0.05, 0.5, 0.95]}}``: period totals per member, reduced on the GPU at the end of
   every period (include/hydrocol.h hc_set_period_totals): each member's transpiration and lateral flow summed over the
@@ -323,6 +338,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     dist_stride, dist_levels = distribution_settings(ens)
     theta = profile_distribution_settings(ens)
     storage = storage_settings(ens)
+    cov = covariance_settings(ens)
     periods = period_settings(ens)
     filt = filter_settings(ens, ranks.world)
     ess_floor = filter_ess_floor(ens)
@@ -339,6 +355,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     forcing = ForcingDigest(params, water_data, cols)
     record = soil_moisture_record_of(sm, cols, water_data)      # before any GPU call
     storage_ranges(storage, cols)                               # (its refusals too)
+    if cov is not None:
+        covariance_check(cov, cols.dim_d, forcing.dim_t, _profile_stride(ens), len(ens.get("Points") or [0]))
     frecord = soil_moisture_record_of(fsm, cols, water_data, "Filter")
     assim = Assimilation(filt, frecord, ess_floor, fwindow, rejuvenation, enkf, record, scheme, window, noise_alpha)
     if cols.flags["PREDICT"] and not ens.get("repair_predict"):
@@ -349,7 +367,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     plan = period_plan(periods, cols, forcing, rows)            # before any GPU call, like the storage's ranges
     if ens.get("Points"):
         return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels, assim,
-                          theta, storage, periods, plan, corr)
+                          theta, storage, periods, plan, corr, cov)
     sharded = enkf_sharded(ens)
     fsharded = filter_sharded(ens)
     if sharded:
@@ -371,8 +389,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
                              noise=str(ens.get("Noise", "philox")).lower(),
                              spinup=str(ens.get("Spinup", "shared")).lower(), profile_stride=stride,
                              wtd_hist_stride=dist_stride, theta_hist_bins=theta[0], **assim.kwargs(),
-                             **_storage_kwargs(storage), **_period_kwargs(periods, plan), **shard_kw,
-                             **_noise_correlation_kwargs(corr))
+                             **_storage_kwargs(storage), **_covariance_kwargs(cov), **_period_kwargs(periods, plan),
+                             **shard_kw, **_noise_correlation_kwargs(corr))
     label = f"Ensemble x{n_members}"
     _step_all(sim, rows, label, ranks)
     # the run's one collective: int64 (count, sum idx, sum idx^2) per row, exact and order-independent
@@ -405,6 +423,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     stor_tables, storage_line = _reduce_storage(ranks, sim, [0], 1, forcing.dim_t, cols, stride, storage, label,
                                                 keep_points=False)
     extra.update(stor_tables)
+    cov_tables, cov_line = _reduce_covariance(ranks, sim, [0], 1, forcing.dim_t, cols, stride, cov, label, keep_points=False)
+    extra.update(cov_tables)
     ptables, period_line = _reduce_periods(ranks, sim, [0], 1, cols, forcing, periods, plan, label, keep_points=False)
     extra.update(ptables)
     # the filters' tables describe the one point: every rank of a sharded run holds the same ones, and rank 0's are taken
@@ -421,7 +441,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     arrays = dict(moments=moments, wtd_mean_cm=mean_cm, wtd_std_cm=std_cm, rows=np.array(rows),
                   members=np.array(n_members), gpus=np.array(ranks.world), initial_cond=psi0, **extra)
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "ensemble water-table statistics", ranks)
-    _print_lines(crps_line, *assim_lines, theta_line, storage_line, period_line, corr_line if ranks.rank == 0 else None)
+    _print_lines(crps_line, *assim_lines, theta_line, storage_line, cov_line, period_line,
+                 corr_line if ranks.rank == 0 else None)
     sim.close()
 
 
@@ -712,6 +733,61 @@ def storage_ranges(storage, cols):
 
 def _storage_kwargs(storage):
     return {} if storage is None else dict(storage_layers_cm=storage[0], storage_bins=storage[1])
+
+
+COVARIANCE_KEYS = ("Node_Stride", "Sensor_Sigma")
+COVARIANCE_MAX_BYTES = 1 << 31
+
+
+def covariance_settings(ens):
+    """Ensemble.Covariance -> (node stride, sensor sigma or None); None when absent.  Pure: runs before any GPU call, and a
+    bad value is a ValueError (message + exit status 1).  The table lives on the profile rows, so the block needs
+    ``"Profiles"`` >= 1.  ``Node_Stride`` defaults to 1; ``Sensor_Sigma`` [m3/m3] is optional."""
+    import math
+    from numbers import Real
+    block = ens.get("Covariance")
+    if block is None:
+        return None
+    if not isinstance(block, dict):
+        raise ValueError(f" Ensemble: Covariance = {block!r} must be an object such as "
+                         f"{{\"Node_Stride\": 4, \"Sensor_Sigma\": 0.02}}.")
+    unknown = sorted(set(block) - set(COVARIANCE_KEYS))
+    if unknown:
+        raise ValueError(f" Ensemble: Covariance has unknown keys {unknown} (known: {list(COVARIANCE_KEYS)}).")
+    profiles = ens.get("Profiles", 0)
+    if (isinstance(profiles, bool) or not isinstance(profiles, Real) or not math.isfinite(profiles)
+            or profiles != int(profiles) or profiles < 1):
+        raise ValueError(f" Ensemble: Covariance needs the profile rows: Profiles = {profiles!r} must be a row stride >= 1.")
+    s = block.get("Node_Stride", 1)
+    if isinstance(s, bool) or not isinstance(s, Real) or not math.isfinite(s) or s != int(s) or s < 1:
+        raise ValueError(f" Ensemble: Covariance.Node_Stride = {s!r} must be a whole number of nodes >= 1.")
+    sigma = block.get("Sensor_Sigma")
+    if sigma is not None and (isinstance(sigma, bool) or not isinstance(sigma, Real) or not math.isfinite(sigma)
+                              or not sigma > 0):
+        raise ValueError(f" Ensemble: Covariance.Sensor_Sigma = {sigma!r} must be a number > 0 (m3/m3).")
+    return int(s), None if sigma is None else float(sigma)
+
+
+def covariance_check(cov, D, T, stride, P=1):
+    """The block's refusals that need the column and the record: a node stride beyond the column, a ``theta_cov`` dataset
+    above 2 GiB and a table beyond the library's HC_THETA_COV_MAX_WORDS, in the CLI's words.  Returns the selected nodes'
+    count n (None without a block)."""
+    from .stepper import THETA_COV_MAX_WORDS, stride_rows, theta_cov_shape
+    if cov is None:
+        return None
+    if cov[0] > D:
+        raise ValueError(f" Ensemble: Covariance.Node_Stride = {cov[0]} exceeds the column's {D} nodes.")
+    n, _, W = theta_cov_shape(D, cov[0])
+    t_out = stride_rows(T, stride)
+    size = int(P) * t_out * n * n * 8
+    if size > COVARIANCE_MAX_BYTES or int(P) * t_out * W > THETA_COV_MAX_WORDS:
+        raise ValueError(f" Ensemble: Covariance: theta_cov would hold {t_out} rows of {n} x {n} float64 "
+                         f"({size / 2 ** 30:.1f} GiB; at most 2 GiB): take a larger node stride or a larger profile stride.")
+    return n
+
+
+def _covariance_kwargs(cov):
+    return {} if cov is None else dict(theta_cov_stride=cov[0])
 
 
 PERIOD_KEYS = ("Rows", "Calendar", "Shallower_than_cm", "Bins", "Transpiration_max_cm", "Lateral_flow_max_cm", "Quantiles")
@@ -1531,6 +1607,45 @@ def _reduce_storage(ranks, sim, ids, P, T, cols, stride, storage, label, keep_po
     return out, line
 
 
+def _reduce_covariance(ranks, sim, ids, P, T, cols, stride, cov, label, keep_points):
+    """The theta covariance table (``cov``: node stride, sensor sigma) from this rank's handle ``sim`` (None: no points), its
+    points ``ids`` placed in the run's [P] table and summed over the ranks like the profile table -- the outside count with
+    it -- then the covariances, the correlations with the water table, the sensor gain and the closing line (rank 0)."""
+    import numpy as np
+    from .multigpu import place_points
+    from .stepper import stride_rows, theta_cov_finish, theta_cov_shape, theta_sensor_gain
+    if cov is None:
+        return {}, None
+    s, sigma = cov
+    n, _, W = theta_cov_shape(cols.dim_d, s)
+    local = (sim.stepper.theta_cov_table() if sim is not None else np.zeros((0, stride_rows(T, stride), W), dtype=np.int64))
+    table = place_points(local, ids, P, ranks)
+    outside = int(ranks.allreduce_sum(np.array([sim.stepper.theta_cov_outside() if sim is not None else 0],
+                                               dtype=np.int64))[0])
+    if ranks.rank != 0:
+        return {}, None
+    table = table if keep_points else table[0]
+    fin = theta_cov_finish(table, cols.dz, s, cols.dim_d)
+    nodes = np.arange(0, cols.dim_d, s, dtype=np.int64)
+    out = {"theta_cov_node_stride": np.array(s, dtype=np.int64), "theta_cov_nodes": nodes,
+           "theta_cov_depth_cm": np.asarray(cols.z, dtype=np.float64)[nodes],
+           "theta_cov_rows": np.arange(table.shape[-2], dtype=np.int64) * int(stride),
+           "theta_cov_count": np.asarray(fin["count"], dtype=np.int64),
+           "theta_cov_outside": np.array(outside, dtype=np.int64),
+           "theta_cov": np.asarray(fin["theta_cov"], dtype=np.float64),
+           "wtd_theta_cov_cm": np.asarray(fin["wtd_theta_cov_cm"], dtype=np.float64),
+           "wtd_var_cm2": np.asarray(fin["wtd_var_cm2"], dtype=np.float64),
+           "theta_wtd_corr": np.asarray(fin["theta_wtd_corr"], dtype=np.float64)}
+    if sigma is not None:
+        out["theta_sensor_sigma"] = np.array(sigma, dtype=np.float64)
+        out["theta_sensor_gain"] = np.asarray(theta_sensor_gain(fin, sigma), dtype=np.float64)
+    rows = int((np.asarray(fin["count"]).reshape(-1, table.shape[-2]) > 0).any(axis=0).sum())
+    line = f" [{label}] covariance: {n} nodes on {rows} rows"
+    if outside:
+        line += f" ({outside} members outside [0, 1])"
+    return out, line
+
+
 def _reduce_periods(ranks, sim, ids, P, cols, forcing, periods, plan, label, keep_points):
     """The period-totals tables (``periods``: the block's settings, ``plan``: end rows and threshold nodes) from this rank's
     handle ``sim`` (None: no points), its points ``ids`` placed in the run's [P] tables and summed over the ranks like the
@@ -1591,7 +1706,7 @@ def _reduce_periods(ranks, sim, ids, P, cols, forcing, periods, plan, label, kee
 
 
 def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride=0, dist_levels=None,
-               assim=Assimilation(), theta=(0, None), storage=None, periods=None, plan=None, corr=None):
+               assim=Assimilation(), theta=(0, None), storage=None, periods=None, plan=None, corr=None, cov=None):
     """Parameter points x members: this rank's points in one handle (ensemble.SweepSimulation), the whole table assembled
     over the ranks (multigpu.assemble_points)."""
     import numpy as np
@@ -1618,8 +1733,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     if mine:
         sim = SweepSimulation(points, forcing, n_members, seed=int(ens.get("Seed", 0)), device=device, point_ids=mine,
                               profile_stride=stride, wtd_hist_stride=dist_stride, theta_hist_bins=theta[0],
-                              **assim.kwargs(), **_storage_kwargs(storage), **_period_kwargs(periods, plan),
-                              **_noise_correlation_kwargs(corr))
+                              **assim.kwargs(), **_storage_kwargs(storage), **_covariance_kwargs(cov),
+                              **_period_kwargs(periods, plan), **_noise_correlation_kwargs(corr))
         _step_all(sim, rows, label, ranks)
         table = sim.moments()
         for j, k in enumerate(mine):
@@ -1637,6 +1752,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     arrays.update(ttables)
     stor_tables, storage_line = _reduce_storage(ranks, sim, mine, P, T, ref, stride, storage, label, keep_points=True)
     arrays.update(stor_tables)
+    cov_tables, cov_line = _reduce_covariance(ranks, sim, mine, P, T, ref, stride, cov, label, keep_points=True)
+    arrays.update(cov_tables)
     ptables, period_line = _reduce_periods(ranks, sim, mine, P, ref, forcing, periods, plan, label, keep_points=True)
     arrays.update(ptables)
     atables, assim_lines = _reduce_assimilation(ranks, sim, mine, P, T, ref, assim, label, keep_points=True)
@@ -1646,7 +1763,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     if sim is not None:
         sim.close()
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "sweep's water-table statistics", ranks)
-    _print_lines(crps_line, *assim_lines, theta_line, storage_line, period_line, corr_line if ranks.rank == 0 else None)
+    _print_lines(crps_line, *assim_lines, theta_line, storage_line, cov_line, period_line,
+                 corr_line if ranks.rank == 0 else None)
 
 
 def run_cli(argv=None):

@@ -236,6 +236,13 @@ struct hc_handle {
     int stor_range[HC_STORAGE_MAX_LAYERS][2] = {};
     AccTable<long long> stor{"words"};
     AccTable<int> shist{"entries"};
+    // ensemble covariance of theta(z) and the water table (hc_set_theta_cov): the node stride; the int64 table
+    // [P][n_prow][W] + the outside word, on the profile rows and keyed like the profile table; the members' quantised rows
+    // uint32 [P][chunk][E64], allocated by the first launch; HYDROCOL_COV_CHUNK_MEMBERS (0: from COV_Q_BYTES)
+    int cov_stride = 0;          // 0: off
+    AccTable<long long> cov{"words"};
+    DevBuf<unsigned> cov_q;
+    long long cov_chunk = 0;
     // period totals per member (hc_set_period_totals): the periods' inclusive end rows, the threshold nodes, the flux
     // histograms' bin count and range exponents; the members' int64 accumulators [K][N] keyed by (N, K) and their second
     // buffer for the particle filter's ancestry; the int64 table pmom [P][n_period][K][5], pcnt, ovf and, with bins, the
@@ -543,6 +550,172 @@ __global__ __launch_bounds__(PROF_TILE * PROF_WAVES) void theta_hist_kernel(
         if (c && node < D) atomicAdd(t + (size_t)node * B + k / PROF_TILE, (int)c);
     }
     if (threadIdx.x == 0 && outside_sum) atomicAdd(outside_word, (unsigned long long)outside_sum);
+}
+
+// ---- ensemble covariance of theta(z) and the water table (hc_set_theta_cov, include/hydrocol.h)
+constexpr int COV_TILE = 64;         // columns of a tile, and members of a chunk staged in LDS
+constexpr int COV_SLOTS = HC_MAX_DEPTH_NODES / COV_TILE + 1;     // 64-column slots of the widest row (E <= 641)
+constexpr int COV_THREADS = 256;
+
+// One profile row's members quantised: layer_storage_kernel's transposed shape.  Grid y = slices of members_per_block
+// members of the chunk [c0, c1) of one point's members, z = point; wave w of a block takes members m0 + w, m0 + w + 4,
+// ... and its lanes stride over the nodes, so every load is 64 contiguous doubles of one member's row.  psi is read on
+// all D nodes for the ballot that gives b (enkf_column_y's rule); theta -- which reads one node constant, the porosity,
+// kept in LDS as layer_storage_kernel keeps it -- is evaluated on the selected nodes only, lane l of slot c owning column
+// c 64 + l.  The wave votes on validity and writes the member's row of Q, uint32 [point][cap][E64]: the pads are zero and
+// a member that is not counted gets an all-zero row, so the product kernel needs no mask.  The wave keeps S1 of its
+// members in lane-owned registers; per block S1, count and outside meet in LDS and go to the table with integer atomics
+// (order-independent).
+__global__ __launch_bounds__(PROF_TILE * PROF_WAVES) void theta_cov_quantise_kernel(
+    const StepArgs A, const double *node_tabs, int special, const double *stage, const int *wtd_obs, long long row,
+    long long prow, long long n_prow, int snapshot, long long members_per_block, long long c0, long long c1, long long cap,
+    int s, int n, int E64, long long W, unsigned *Q, long long *cov, unsigned long long *outside_word)
+{
+#pragma clang fp contract(off)
+    if (!snapshot && wtd_obs[row] < 0) return;
+    const int D = A.D, E = n + 1;
+    const int lane = threadIdx.x % PROF_TILE, wave = threadIdx.x / PROF_TILE;
+    const long long point = blockIdx.z;
+    const long long m0 = c0 + (long long)blockIdx.y * members_per_block;
+    const long long m1 = m0 + members_per_block < c1 ? m0 + members_per_block : c1;
+    if (m0 >= m1) return;                    // (the whole block: nothing is shared yet)
+    extern __shared__ double cov_por[];      // [D]
+    __shared__ unsigned long long s1_sum[COV_SLOTS * COV_TILE];
+    __shared__ unsigned counted_sum, outside_sum;
+    const ColumnDev P = A.P[point];
+    for (int i = threadIdx.x; i < D; i += PROF_TILE * PROF_WAVES) cov_por[i] = node_tabs[(size_t)point * 3 * D + i];
+    for (int k = threadIdx.x; k < COV_SLOTS * COV_TILE; k += PROF_TILE * PROF_WAVES) s1_sum[k] = 0;
+    if (threadIdx.x == 0) counted_sum = 0, outside_sum = 0;
+    __syncthreads();
+
+    unsigned long long s1[COV_SLOTS] = {};   // lane l: the wave's sums of columns c 64 + l
+    unsigned counted = 0, outside = 0;
+    const double scale = ldexp(1.0, HC_THETA_COV_SCALE);
+    for (long long m = m0 + wave; m < m1; m += PROF_WAVES) {
+        const double *psi_m = stage + (size_t)(point * A.members_per_point + m) * D;
+        int deepest = -1;
+        for (int i0 = 0; i0 < D; i0 += PROF_TILE) {
+            const int i = i0 + lane;
+            const unsigned long long u = __ballot(i < D && !(psi_m[i] >= P.psi_sat));
+            if (u) deepest = i0 + 63 - __clzll((long long)u);
+        }
+        const int b = deepest < 0 ? 0 : (deepest + 1 < D - 1 ? deepest + 1 : D - 1);
+        unsigned q[COV_SLOTS];
+        bool bad = false;
+#pragma unroll
+        for (int c = 0; c < COV_SLOTS; c++) {
+            const int k = c * COV_TILE + lane;
+            q[c] = k == n ? (unsigned)b : 0u;
+            if (k < n) {
+                const int i = k * s;
+                double th, K, C, kb, pf;
+                if (special)
+                    model_cell<true>(P, psi_m[i], cov_por[i], 0.0, 0.0, 0.0, 0.0, 0.0, th, K, C, kb, pf);
+                else
+                    model_cell<false>(P, psi_m[i], cov_por[i], 0.0, 0.0, 0.0, 0.0, 0.0, th, K, C, kb, pf);
+                const bool ok = th >= 0.0 && th <= 1.0;          // (false for a NaN)
+                q[c] = ok ? (unsigned)rint(th * scale) : 0u;      // theta 2^20 is exact: the rounding is rint's alone
+                bad = bad || !ok;
+            }
+        }
+        const bool refused = __ballot(bad) != 0;
+        unsigned *qrow = Q + ((size_t)point * cap + (size_t)(m - c0)) * E64;
+#pragma unroll
+        for (int c = 0; c < COV_SLOTS; c++) {
+            const int k = c * COV_TILE + lane;
+            if (k < E64) {
+                const unsigned v = refused ? 0u : q[c];
+                qrow[k] = v;
+                s1[c] += v;
+            }
+        }
+        if (refused) outside++; else counted++;
+    }
+#pragma unroll
+    for (int c = 0; c < COV_SLOTS; c++)
+        if (s1[c]) atomicAdd(&s1_sum[c * COV_TILE + lane], s1[c]);
+    if (lane == 0) {
+        if (counted) atomicAdd(&counted_sum, counted);
+        if (outside) atomicAdd(&outside_sum, outside);
+    }
+    __syncthreads();
+    long long *t = cov + ((size_t)point * n_prow + prow) * W;
+    for (int k = threadIdx.x; k < E; k += PROF_TILE * PROF_WAVES) {
+        const unsigned long long v = s1_sum[k];
+        if (v) atomicAdd(reinterpret_cast<unsigned long long *>(t + 1 + k), v);
+    }
+    if (threadIdx.x == 0) {
+        if (counted_sum) atomicAdd(reinterpret_cast<unsigned long long *>(t), (unsigned long long)counted_sum);
+        if (outside_sum) atomicAdd(outside_word, (unsigned long long)outside_sum);
+    }
+}
+
+// S2 += Q^T Q of one chunk, in integers: grid x = pairs I <= J of 64-column tiles (row-major over the upper triangle), y =
+// slices of `slice` members of the chunk's `members`, z = point.  The block stages 64 members of both column tiles in LDS
+// as uint32 [member][64] -- 16 KiB each, one array on a diagonal pair -- and thread (ty, tx) of the 16 x 16 owns rows
+// 4 ty .. 4 ty + 3 and columns 4 tx .. 4 tx + 3 of the 64 x 64 output in sixteen 64-bit accumulators; a product is one
+// 32 x 32 -> 64-bit multiply-add.  A member's row of a tile is 256 bytes, the 64 banks of a 16-byte read once: the sixteen
+// tx of a read's lane group take its sixteen 16-byte slots (the lanes 16 apart that share one share its address), the ty
+// of a group are one address per sixteen lanes on distinct banks, so both reads are conflict-free or broadcast.  After its
+// slice the block adds the entries with a <= b < E to the table with 64-bit integer atomics, a diagonal pair its upper
+// triangle only; zeros (the pads, columns nobody moved) are skipped.  No floating point: no result depends on the slice
+// length or on any order.
+__global__ __launch_bounds__(COV_THREADS) void theta_cov_syrk_kernel(
+    const int *wtd_obs, long long row, long long prow, long long n_prow, int snapshot, long long members, long long cap,
+    long long slice, int E, int E64, long long W, const unsigned *Q, long long *cov)
+{
+    if (!snapshot && wtd_obs[row] < 0) return;
+    const int nt = E64 / COV_TILE;
+    int p = blockIdx.x, I = 0;
+    while (p >= nt - I) p -= nt - I, I++;
+    const int J = I + p;
+    const long long point = blockIdx.z;
+    const long long ms0 = (long long)blockIdx.y * slice;
+    const long long ms1 = ms0 + slice < members ? ms0 + slice : members;
+    if (ms0 >= ms1) return;                  // (the whole block: nothing is shared yet)
+    __shared__ __attribute__((aligned(16))) unsigned tile_a[COV_TILE][COV_TILE], tile_b[COV_TILE][COV_TILE];
+    const unsigned (*rhs)[COV_TILE] = I == J ? tile_a : tile_b;
+    const int tx = threadIdx.x % 16, ty = threadIdx.x / 16;
+    unsigned long long acc[4][4] = {};
+    const unsigned *Qp = Q + (size_t)point * cap * E64;
+    for (long long kc = ms0; kc < ms1; kc += COV_TILE) {
+#pragma unroll
+        for (int j = 0; j < COV_TILE * COV_TILE / 4 / COV_THREADS; j++) {
+            const int idx = threadIdx.x + COV_THREADS * j, mm = idx / 16, c4 = idx % 16;
+            const long long m = kc + mm;
+            uint4 a = make_uint4(0, 0, 0, 0), b = make_uint4(0, 0, 0, 0);
+            if (m < ms1) {
+                const unsigned *r = Qp + (size_t)m * E64;
+                a = *reinterpret_cast<const uint4 *>(r + COV_TILE * I + 4 * c4);
+                if (I != J) b = *reinterpret_cast<const uint4 *>(r + COV_TILE * J + 4 * c4);
+            }
+            *reinterpret_cast<uint4 *>(&tile_a[mm][4 * c4]) = a;
+            if (I != J) *reinterpret_cast<uint4 *>(&tile_b[mm][4 * c4]) = b;
+        }
+        __syncthreads();
+#pragma unroll 8
+        for (int k = 0; k < COV_TILE; k++) {
+            const uint4 a = *reinterpret_cast<const uint4 *>(&tile_a[k][4 * ty]);
+            const uint4 b = *reinterpret_cast<const uint4 *>(&rhs[k][4 * tx]);
+            const unsigned av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+            for (int r = 0; r < 4; r++)
+#pragma unroll
+                for (int c = 0; c < 4; c++) acc[r][c] += (unsigned long long)av[r] * bv[c];
+        }
+        __syncthreads();
+    }
+    long long *S2 = cov + ((size_t)point * n_prow + prow) * W + 1 + E;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const long long a = COV_TILE * I + 4 * ty + r;
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const long long b = COV_TILE * J + 4 * tx + c;
+            if (a <= b && b < E && acc[r][c])
+                atomicAdd(reinterpret_cast<unsigned long long *>(S2 + a * E - a * (a - 1) / 2 + (b - a)), acc[r][c]);
+        }
+    }
 }
 
 // ---- ensemble soil-water storage by depth layer (hc_set_layer_storage, include/hydrocol.h)
@@ -3391,6 +3564,41 @@ int ensure_thist(hc_handle *h)
     return h->thist.ensure(h->n_points, h->n_rows, h->p.dim_d, thist_bins_total(h) + 2);
 }
 
+// the theta covariance table (hc_set_theta_cov): int64 [P][n_prow][W] on the profile rows, then the outside word
+struct CovLayout {
+    int s = 0, n = 0, E = 0, E64 = 0;
+    int64_t W = 0, words = 0;
+};
+CovLayout cov_layout(const hc_handle *h)
+{
+    CovLayout C;
+    C.s = h->cov_stride;
+    C.n = (h->p.dim_d + C.s - 1) / C.s;
+    C.E = C.n + 1;
+    C.E64 = (C.E + COV_TILE - 1) / COV_TILE * COV_TILE;
+    C.W = 1 + C.E + (int64_t)C.E * (C.E + 1) / 2;
+    C.words = (int64_t)h->n_points * prof_layout(h).n_prow * C.W + 1;
+    return C;
+}
+int ensure_cov(hc_handle *h)
+{
+    if (h->cov_stride <= 0) return fail(HC_ERR_ARG, "the theta covariance is off (hc_set_theta_cov)");
+    if (h->prof_stride <= 0)
+        return fail(HC_ERR_ARG, "the theta covariance needs the profile statistics (hc_set_profile_stats)");
+    if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
+    if (h->cov_stride > h->p.dim_d)
+        return fail(HC_ERR_ARG, "theta covariance: node stride %d exceeds the column's %d nodes", h->cov_stride,
+                    (int)h->p.dim_d);
+    if (h->n_members / std::max(h->n_points, 1) > HC_THETA_COV_MAX_MEMBERS)
+        return fail(HC_ERR_ARG, "theta covariance: %lld members per point exceed HC_THETA_COV_MAX_MEMBERS (2^22: the sums "
+                    "of products stay within 2^62)", (long long)(h->n_members / std::max(h->n_points, 1)));
+    const CovLayout C = cov_layout(h);
+    if (C.words - 1 > HC_THETA_COV_MAX_WORDS)
+        return fail(HC_ERR_ARG, "theta covariance: %lld words exceed HC_THETA_COV_MAX_WORDS (take a larger node stride or a "
+                    "larger profile stride)", (long long)(C.words - 1));
+    return h->cov.ensure(h->n_points, h->n_rows, h->p.dim_d, C.words);
+}
+
 // the layer-storage tables (hc_set_layer_storage): int64 stor [P][n_prow][L][5], scnt [P][n_prow], ovf [1]; with bins the
 // int32 hist [P][n_prow][L][B] and the outside count (one uint64 in two entries, 8-byte aligned behind a multiple of 32)
 struct StorLayout {
@@ -3971,6 +4179,8 @@ int hc_create(int device_ordinal, hc_handle **out)
     if (const char *sv = getenv("HYDROCOL_SCIPY_152")) h->scipy_152 = atoi(sv) != 0;     // (the whole product at once: CLI, Simulation)
     if (const char *mi = getenv("HYDROCOL_DEBUG_MAX_ITER"))    // test hook: forces abandoned attempts
         if (atoi(mi) > 0) h->max_phase_iterations = atoi(mi);
+    if (const char *cc = getenv("HYDROCOL_COV_CHUNK_MEMBERS"))        // test hook: the theta covariance's members in chunks
+        if (atoi(cc) > 0) h->cov_chunk = atoi(cc);
     if (const char *gy = getenv("HYDROCOL_DEBUG_STORAGE_GRID_Y"))     // test hook: blocks of layer_storage_kernel take several slices
         if (atoi(gy) > 0) h->stor_grid_y = std::min(h->stor_grid_y, (long long)atoi(gy));
     const char *jr = getenv("HYDROCOL_DEBUG_JAC_REJECT");   // test hook: exercises num_jac's retry branch
@@ -3996,6 +4206,7 @@ int hc_destroy(hc_handle *h)
     h->point_base.release(); h->point_order.release(); h->point_cost.release();
     h->daylight.release(); h->refresh.release(); h->wtd_u16.release(); h->moments.release(); h->counters.release();
     h->prof.release(); h->hist.release(); h->thist.release(); h->stor.release(); h->shist.release();
+    h->cov.release(); h->cov_q.release();
     h->pacc.release(); h->pacc_alt.release(); h->pmom.release(); h->phist.release();
     assimilation_off(h);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -4510,6 +4721,45 @@ int launch_theta_hist(hc_handle *h, const StepArgs &A, const ProfLayout &L, cons
     return HC_OK;
 }
 
+// the theta covariance of the same row, from the same states.  The members' quantised rows Q [P][cap][E64] uint32 are
+// staged in at most COV_Q_BYTES (1 GiB: 262 144 members x E64 = 320 take 320 MiB), allocated by the first launch; a larger
+// ensemble runs in chunks of `cap` members a point (a multiple of 64 unless HYDROCOL_COV_CHUNK_MEMBERS says otherwise),
+// quantise then multiply, which changes no bit: every add is an integer's.  A quantise block takes 256 members (64 a wave:
+// E atomics a block); a product block a slice of 4096 (a 262 144-member point at E = 302: 15 tile pairs x 64 slices).
+constexpr int64_t COV_Q_BYTES = int64_t(1) << 30;
+constexpr long long COV_QUANT_MEMBERS_PER_BLOCK = 256, COV_SLICE_MEMBERS = 4096;
+int launch_theta_cov(hc_handle *h, const StepArgs &A, const ProfLayout &L, const double *stage, int64_t row, int snapshot)
+{
+    const CovLayout C = cov_layout(h);
+    const long long mpp = h->n_members / h->n_points;
+    long long cap = h->cov_chunk > 0
+        ? h->cov_chunk
+        : std::max<long long>(COV_TILE, COV_Q_BYTES / ((int64_t)h->n_points * C.E64 * 4) / COV_TILE * COV_TILE);
+    cap = std::min(cap, mpp);
+    if (h->cov_q.ensure((size_t)h->n_points * cap * C.E64)) return HC_ERR_DEVICE;
+    long long *t = h->cov.buf.p;
+    const int nt = C.E64 / COV_TILE;
+    const long long prow = row / h->prof_stride;
+    for (long long c0 = 0; c0 < mpp; c0 += cap) {
+        const long long len = std::min(cap, mpp - c0);
+        hipLaunchKernelGGL(theta_cov_quantise_kernel,
+                           dim3(1, (unsigned)((len + COV_QUANT_MEMBERS_PER_BLOCK - 1) / COV_QUANT_MEMBERS_PER_BLOCK),
+                                (unsigned)h->n_points),
+                           dim3(PROF_TILE * PROF_WAVES), (size_t)h->p.dim_d * sizeof(double), h->stream, A, h->node_tabs.p,
+                           (int)h->use_special(), stage, h->wtd_obs.p, (long long)row, prow, (long long)L.n_prow, snapshot,
+                           COV_QUANT_MEMBERS_PER_BLOCK, c0, c0 + len, cap, C.s, C.n, C.E64, (long long)C.W, h->cov_q.p, t,
+                           reinterpret_cast<unsigned long long *>(t + (h->cov.n - 1)));
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(theta_cov_syrk_kernel,
+                           dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)((len + COV_SLICE_MEMBERS - 1) / COV_SLICE_MEMBERS),
+                                (unsigned)h->n_points),
+                           dim3(COV_THREADS), 0, h->stream, h->wtd_obs.p, (long long)row, prow, (long long)L.n_prow, snapshot,
+                           len, cap, COV_SLICE_MEMBERS, C.E, C.E64, (long long)C.W, h->cov_q.p, t);
+        HIP_TRY(hipGetLastError());
+    }
+    return HC_OK;
+}
+
 // the layer storage of the same row, from the same states: a block per slice of STOR_MEMBERS_PER_BLOCK members (a wave
 // reads whole rows, so the slices are short: 32 members a wave make the block's set-up negligible and give a
 // 262 144-member point 2048 blocks); beyond stor_grid_y = 65 535 slices (8.4 M members a point) a block takes several, so
@@ -4815,6 +5065,8 @@ int accumulate(hc_handle *h, const StepArgs &A, const hc_step_args *a, const Chu
             if (int rc = launch_theta_hist(h, A, PL, stage, c.row0 + r, 0)) return rc;
         if (h->stor_layers > 0)
             if (int rc = launch_layer_storage(h, A, PL, stage, c.row0 + r, 0)) return rc;
+        if (h->cov_stride > 0)
+            if (int rc = launch_theta_cov(h, A, PL, stage, c.row0 + r, 0)) return rc;
     }
     long long *t = h->prof.buf.p;
     hipLaunchKernelGGL(flux_stats_kernel, dim3(c.rows, h->n_points), dim3(256), 0, h->stream, h->diag.p, h->wtd_u16.p,
@@ -5522,6 +5774,7 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
     if ((prof_on && (rc = ensure_prof(h))) || (hist_on && (rc = ensure_hist(h)))) return rc;
     if (prof_on && h->thist_bins > 0 && (rc = ensure_thist(h))) return rc;
     if (prof_on && h->stor_layers > 0 && (rc = ensure_stor(h))) return rc;
+    if (prof_on && h->cov_stride > 0 && (rc = ensure_cov(h))) return rc;
     const bool per_on = h->per_n > 0 && !a->spinup;       // period totals (hc_set_period_totals)
     if (per_on && (rc = ensure_period(h))) return rc;
     // the particle filter (hc_set_filter): spin-up solves are never filtered
@@ -5700,6 +5953,8 @@ int hc_set_profile_stats(hc_handle *h, int32_t stride)
     h->thist.release();
     h->stor_layers = h->stor_bins = 0;       // and so is the layer storage
     h->stor.release(), h->shist.release();
+    h->cov_stride = 0;           // ... and the theta covariance
+    h->cov.release(), h->cov_q.release();
     return stride == 0 ? HC_OK : ensure_prof(h);
 }
 
@@ -5726,11 +5981,15 @@ int hc_profile_snapshot(hc_handle *h, int64_t row)
         if (int rc2 = ensure_thist(h)) return rc2;
     if (h->stor_layers > 0)
         if (int rc2 = ensure_stor(h)) return rc2;
+    if (h->cov_stride > 0)
+        if (int rc2 = ensure_cov(h)) return rc2;
     if (int rc2 = launch_profile(h, A, prof_layout(h), h->psi.p, row, 1)) return rc2;
     if (h->thist_bins > 0)
         if (int rc2 = launch_theta_hist(h, A, prof_layout(h), h->psi.p, row, 1)) return rc2;
     if (h->stor_layers > 0)
         if (int rc2 = launch_layer_storage(h, A, prof_layout(h), h->psi.p, row, 1)) return rc2;
+    if (h->cov_stride > 0)
+        if (int rc2 = launch_theta_cov(h, A, prof_layout(h), h->psi.p, row, 1)) return rc2;
     HIP_TRY(hipStreamSynchronize(h->stream));
     return HC_OK;
 }
@@ -5950,6 +6209,75 @@ int hc_get_layer_storage_layout(hc_handle *h, int32_t *n_layers, int32_t *n_bins
     *n_layers = h->stor_layers, *n_bins = h->stor_bins;
     for (int l = 0; l < HC_STORAGE_MAX_LAYERS; l++)
         ranges[2 * l] = l < h->stor_layers ? h->stor_range[l][0] : 0, ranges[2 * l + 1] = l < h->stor_layers ? h->stor_range[l][1] : 0;
+    return HC_OK;
+}
+
+int hc_set_theta_cov(hc_handle *h, int32_t node_stride)
+{
+    if (!h) return fail(HC_ERR_ARG, "hc_set_theta_cov: bad argument");
+    if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->cov.release(), h->cov_q.release();    // re-created, zeroed, when on
+    h->cov_stride = 0;
+    if (node_stride == 0) return HC_OK;
+    if (node_stride < 1) return fail(HC_ERR_ARG, "hc_set_theta_cov: node stride %d (>= 1; 0 = off)", (int)node_stride);
+    h->cov_stride = node_stride;
+    const int rc = ensure_cov(h);            // (its refusals come before anything is allocated)
+    if (rc != HC_OK) h->cov_stride = 0, h->cov.release();        // refused: off
+    return rc;
+}
+
+int hc_get_theta_cov_layout(hc_handle *h, int32_t *node_stride, int32_t *n_nodes, int64_t *words_per_row)
+{
+    if (!h || !node_stride || !n_nodes || !words_per_row) return fail(HC_ERR_ARG, "hc_get_theta_cov_layout: bad argument");
+    *node_stride = *n_nodes = 0, *words_per_row = 0;
+    if (h->cov_stride <= 0) return HC_OK;
+    const CovLayout C = cov_layout(h);
+    *node_stride = C.s, *n_nodes = C.n, *words_per_row = C.W;
+    return HC_OK;
+}
+
+int hc_get_theta_cov_words(hc_handle *h, int64_t *n_words)
+{
+    if (!h || !n_words) return fail(HC_ERR_ARG, "hc_get_theta_cov_words: bad argument");
+    if (int rc = ensure_cov(h)) return rc;
+    *n_words = h->cov.n;
+    return HC_OK;
+}
+
+int hc_get_theta_cov(hc_handle *h, int64_t *table, int64_t n_words)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_get_theta_cov: bad argument");
+    return table_copy(h, h->cov, ensure_cov, hipMemcpyDeviceToHost, table, n_words, "hc_get_theta_cov");
+}
+
+int hc_set_theta_cov_tables(hc_handle *h, const int64_t *table, int64_t n_words)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_set_theta_cov_tables: bad argument");
+    return table_copy(h, h->cov, ensure_cov, hipMemcpyHostToDevice, const_cast<int64_t *>(table), n_words,
+                      "hc_set_theta_cov_tables");
+}
+
+int hc_export_theta_cov(hc_handle *h, void *device_dst, int64_t n_words)
+{
+    if (!h || !device_dst) return fail(HC_ERR_ARG, "hc_export_theta_cov: bad argument");
+    return table_copy(h, h->cov, ensure_cov, hipMemcpyDeviceToDevice, device_dst, n_words, "hc_export_theta_cov");
+}
+
+int hc_reset_theta_cov(hc_handle *h)
+{
+    if (!h) return fail(HC_ERR_ARG, "hc_reset_theta_cov: bad argument");
+    return table_reset(h, h->cov, ensure_cov);
+}
+
+int hc_get_theta_cov_outside(hc_handle *h, uint64_t *count)
+{
+    if (!h || !count) return fail(HC_ERR_ARG, "hc_get_theta_cov_outside: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = ensure_cov(h)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(count, h->cov.buf.p + (h->cov.n - 1), 8, hipMemcpyDeviceToHost));
     return HC_OK;
 }
 

@@ -10,6 +10,7 @@ import numpy as np
 
 from .digest import inverse_retention
 from .stepper import enkf_noise_summary, noise_field_settings
+from .stepper import theta_cov_finish, theta_sensor_gain
 from .stepper import noise_correlation_breaks, noise_correlation_settings, noise_correlation_tables
 from .stepper import (ASSIM_TABLES, ENKF_METHODS, EnsembleStepper, enkf_sm_summary, enkf_summary,
                       enkf_window_settings, enkf_window_summary, filter_sm_summary, filter_summary,
@@ -105,6 +106,9 @@ class _Run:
     storage_layers_cm (needs profile_stride): depth layers [(top, bottom), ...] in cm (stepper.layer_ranges) whose water
     storage dz sum theta is reduced per member on the device on the profile rows: :meth:`storage_stats` (mean and sigma in
     cm) and, with ``storage_bins`` (a power of two in 32 .. 1024), :meth:`storage_distribution` (quantile bands in cm).
+    theta_cov_stride > 0 (needs profile_stride): the exact second moments of theta_vol at the nodes 0, s, 2 s, ... and of
+    the water table on the profile rows (include/hydrocol.h hc_set_theta_cov): :meth:`theta_covariance` (covariance and
+    correlation of theta(z), cov(theta, wtd)) and, at stride 1, :meth:`layer_std_cm` (the sigma of any layer's storage).
     period_ends: the inclusive end rows of periods (stepper.period_ends) over which every member's transpiration and
     lateral flow are summed, its shallowest and deepest water table kept and the rows counted on which the water table
     stood at or above each of ``period_thresholds_cm`` (at most 4 depths, mapped to nodes like a sensor's), reduced over
@@ -161,8 +165,12 @@ class _Run:
                       enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None,
                       enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=(),
                       filter_soil_moisture=None, theta_hist_bins=0, storage_layers_cm=None, storage_bins=0,
-                      filter_ess_floor=0.0, filter_window_offsets=(), enkf_noise_field=None, filter_rejuvenation=0.0):
+                      filter_ess_floor=0.0, filter_window_offsets=(), enkf_noise_field=None, filter_rejuvenation=0.0,
+                      theta_cov_stride=0):
         self.profile_stride = int(profile_stride)
+        self.theta_cov_stride = int(theta_cov_stride or 0)
+        if self.theta_cov_stride and not self.profile_stride:
+            raise ValueError("theta_cov_stride needs the profile statistics (profile_stride > 0)")
         self.storage_layers_cm = None if storage_layers_cm is None or len(storage_layers_cm) == 0 else \
             np.asarray(storage_layers_cm, dtype=np.float64).reshape(-1, 2)
         self.storage_bins = int(storage_bins or 0) if self.storage_layers_cm is not None else 0
@@ -180,6 +188,8 @@ class _Run:
                 self.stepper.set_theta_hist(self.theta_hist_bins)
             if self.storage_ranges is not None:
                 self.stepper.set_layer_storage(self.storage_ranges, self.storage_bins)
+            if self.theta_cov_stride:
+                self.stepper.set_theta_cov(self.theta_cov_stride)
             self.stepper.profile_snapshot(0)       # psi[0], theta_vol[0]: the state before any solve
         self.wtd_hist_stride = int(wtd_hist_stride)
         if self.wtd_hist_stride:
@@ -326,6 +336,39 @@ class _Run:
         ``table``: e.g. the sum over ranks.  Other levels need no rerun."""
         t = self.theta_hist_table() if table is None else table
         return theta_distribution(t, levels, self.theta_hist_bins, self.profile_stride)
+
+    def theta_cov_table(self):
+        """[n_prow][W] int64: count, S1, S2 of the selected nodes and the water table on every profile row
+        (stepper.theta_cov_of); a sweep: [P][n_prow][W]."""
+        t = self.stepper.theta_cov_table()
+        return t.reshape(self._lead + t.shape[1:])
+
+    def theta_covariance(self, table=None, sensor_sigma=None):
+        """The ensemble's second-order structure per profile row (stepper.theta_cov_finish), with the leading shape of
+        the table: ``theta_cov`` [T_out][n][n], ``wtd_theta_cov_cm`` [T_out][n], ``wtd_var_cm2`` [T_out], ``theta_wtd_corr``
+        [T_out][n], ``theta_corr``, ``theta_mean``, ``wtd_mean_idx`` and ``count``, with ``rows``, ``node_stride``,
+        ``nodes`` and ``depth_cm`` [n]; with ``sensor_sigma`` [m3/m3] also ``theta_sensor_gain`` [T_out][n]
+        (stepper.theta_sensor_gain).  ``table``: e.g. the sum over ranks."""
+        t = self.theta_cov_table() if table is None else table
+        out = theta_cov_finish(t, self.cols.dz, self.theta_cov_stride, self.cols.dim_d)
+        nodes = np.arange(0, self.cols.dim_d, self.theta_cov_stride, dtype=np.int64)
+        out.update(rows=np.arange(np.asarray(t).shape[-2], dtype=np.int64) * self.profile_stride,
+                   node_stride=self.theta_cov_stride, nodes=nodes, depth_cm=np.asarray(self.cols.z, dtype=np.float64)[nodes])
+        if sensor_sigma is not None:
+            out["theta_sensor_gain"] = theta_sensor_gain(out, sensor_sigma)
+        return out
+
+    def layer_std_cm(self, layers_cm, table=None):
+        """The sigma [cm] of the water stored in each of the depth layers ``layers_cm`` = [(top, bottom), ...]
+        (stepper.layer_ranges) per profile row, dz sqrt(1' C 1) over the layer's nodes of the covariance table:
+        [T_out][L] (a sweep: [P][T_out][L]).  The layers are named after the run; needs a node stride of 1."""
+        if self.theta_cov_stride != 1:
+            raise ValueError("layer_std_cm needs the covariance of every node "
+                             f"(theta_cov_stride = 1, not {self.theta_cov_stride})")
+        C = self.theta_covariance(table)["theta_cov"]
+        out = [np.sqrt(np.maximum(C[..., i0:i1, i0:i1].sum(axis=(-2, -1)), 0.0))
+               for i0, i1 in layer_ranges(self.cols.z, layers_cm)]
+        return float(self.cols.dz) * np.stack(out, axis=-1)
 
     def _start_periods(self, period_ends, period_thresholds_cm, period_bins, period_flux_max_cm):
         self.period_ends = None if period_ends is None or len(period_ends) == 0 else \
@@ -510,9 +553,9 @@ class EnsembleSimulation(_Run):
     #1 base vector, then one vector per refresh row (simulation.py:426,561,601) -- and uploaded per launch.
     spinup="shared" (default): one spin-up (global member 0's first draw) broadcast to all members;
     spinup="member": every member spins up with its own first draw (`spinup_members_on_gpu`).
-    profile_stride, theta_hist_bins, storage_layers_cm / storage_bins, period_ends / period_thresholds_cm / period_bins /
-    period_flux_max_cm, wtd_hist_stride, filter_stride / filter_sigma_cm / filter_seed, enkf_stride / enkf_sigma_cm /
-    enkf_localisation_cm / enkf_seed: the optional tables, the particle filter and the EnKF (:class:`_Run`).
+    profile_stride, theta_hist_bins, storage_layers_cm / storage_bins, theta_cov_stride, period_ends /
+    period_thresholds_cm / period_bins / period_flux_max_cm, wtd_hist_stride, filter_stride / filter_sigma_cm /
+    filter_seed, enkf_stride / enkf_sigma_cm / enkf_localisation_cm / enkf_seed: the optional tables, the particle filter and the EnKF (:class:`_Run`).
     enkf_shard=(n_global, exchange): these members are [member_offset, member_offset + N) of an ensemble of ``n_global``
     whose other members run elsewhere, and the EnKF analyses the whole of it (include/hydrocol.h hc_set_enkf_shard;
     ``exchange``: e.g. a ``multigpu.ShardExchange``).  member_offset must be a multiple of 256, and so must N unless the
@@ -530,7 +573,8 @@ class EnsembleSimulation(_Run):
                  enkf_window_offsets=(), enkf_shard=None, filter_shard=None, filter_soil_moisture=None,
                  theta_hist_bins=0, storage_layers_cm=None, storage_bins=0, period_ends=None, period_thresholds_cm=(),
                  period_bins=0, period_flux_max_cm=(16.0, 4.0), filter_ess_floor=0.0, filter_window_offsets=(),
-                 enkf_noise_field=None, filter_rejuvenation=0.0, noise_correlation=None):
+                 enkf_noise_field=None, filter_rejuvenation=0.0, noise_correlation=None,
+                 theta_cov_stride=0):
         corr = self._check_noise_correlation("EnsembleSimulation", noise_correlation, noise, filter_rejuvenation)
         if enkf_shard is not None and noise_field_settings(enkf_noise_field, 0.0) is not None:
             raise ValueError("enkf_shard and enkf_noise_field exclude each other: the exchanged partials cover psi only")
@@ -557,7 +601,7 @@ class EnsembleSimulation(_Run):
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
                            enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins, storage_layers_cm,
                            storage_bins, filter_ess_floor, filter_window_offsets, enkf_noise_field,
-                           filter_rejuvenation=filter_rejuvenation)
+                           filter_rejuvenation=filter_rejuvenation, theta_cov_stride=theta_cov_stride)
         self._start_periods(period_ends, period_thresholds_cm, period_bins, period_flux_max_cm)
         self.enkf_shard = None
         if enkf_shard is not None:
@@ -675,6 +719,10 @@ class EnsembleSimulation(_Run):
             if self.storage_bins:
                 arrays["storage_hist"] = self.stepper.layer_storage_hist_table()
                 arrays["storage_hist_outside"] = np.array(self.stepper.layer_storage_outside(), dtype=np.uint64)
+        if self.theta_cov_stride:
+            arrays["theta_cov_stride"] = np.array(self.theta_cov_stride, dtype=np.int64)
+            arrays["theta_cov_table"] = self.stepper.theta_cov_table()
+            arrays["theta_cov_outside"] = np.array(self.stepper.theta_cov_outside(), dtype=np.uint64)
         if self.period_ends is not None:
             # the members' accumulators travel too: a restore in the middle of a period continues it
             arrays["period_ends"] = self.period_ends
@@ -758,6 +806,7 @@ class EnsembleSimulation(_Run):
         stride = int(data["profile_stride"]) if "profile_stride" in data else 0
         hist_stride = int(data["wtd_hist_stride"]) if "wtd_hist_stride" in data else 0
         theta_bins = int(data["theta_hist_bins"]) if "theta_hist_bins" in data else 0
+        cov_stride = int(data["theta_cov_stride"]) if "theta_cov_stride" in data else 0
         storage = "storage_layers_cm" in data
         if storage:
             fkw_storage = dict(storage_layers_cm=np.asarray(data["storage_layers_cm"], dtype=np.float64).reshape(-1, 2),
@@ -812,7 +861,8 @@ class EnsembleSimulation(_Run):
                                           "layers": bool(int(data["noise_correlation_layers"]))})
         sim = cls(cols, forcing, n, seed=int(data["seed"]), device=device, member_offset=int(data["member_offset"]),
                   psi0=np.asarray(data["initial_cond"], dtype=float).reshape(-1)[:D], flags=flags, profile_stride=stride,
-                  wtd_hist_stride=hist_stride, theta_hist_bins=theta_bins, **(fkw_storage if storage else {}), **fkw)
+                  wtd_hist_stride=hist_stride, theta_hist_bins=theta_bins, theta_cov_stride=cov_stride,
+                  **(fkw_storage if storage else {}), **fkw)
         if has_corr and not (np.array_equal(np.asarray(data["noise_correlation_a"]).reshape(-1), sim.noise_correlation_a)
                              and np.array_equal(np.asarray(data["noise_correlation_b"]).reshape(-1), sim.noise_correlation_b)):
             raise ValueError(f" EnsembleSimulation: {path} holds the noise correlation's tables of another column.")
@@ -842,6 +892,9 @@ class EnsembleSimulation(_Run):
             sim.stepper.set_layer_storage_table(np.asarray(data["storage_table"], dtype=np.int64))
             if sim.storage_bins:
                 sim.stepper.set_layer_storage_hist_table(np.asarray(data["storage_hist"]), int(data["storage_hist_outside"]))
+        if cov_stride:
+            sim.stepper.set_theta_cov_table(np.asarray(data["theta_cov_table"], dtype=np.int64),
+                                            int(data["theta_cov_outside"]))
         if periods:
             sim.stepper.set_period_totals_table(np.asarray(data["period_table"], dtype=np.int64))
             sim.stepper.set_period_totals_acc(np.asarray(data["period_acc"], dtype=np.int64))
@@ -946,7 +999,8 @@ class SweepSimulation(_Run):
                  enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=(),
                  filter_soil_moisture=None, theta_hist_bins=0, storage_layers_cm=None, storage_bins=0, period_ends=None,
                  period_thresholds_cm=(), period_bins=0, period_flux_max_cm=(16.0, 4.0), filter_ess_floor=0.0,
-                 filter_window_offsets=(), enkf_noise_field=None, filter_rejuvenation=0.0, noise_correlation=None):
+                 filter_window_offsets=(), enkf_noise_field=None, filter_rejuvenation=0.0, noise_correlation=None,
+                 theta_cov_stride=0):
         corr = self._check_noise_correlation("SweepSimulation", noise_correlation, "philox", filter_rejuvenation)
         self.points = list(cols_list)
         self.P, self.n = len(self.points), int(n_members)
@@ -979,7 +1033,7 @@ class SweepSimulation(_Run):
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
                            enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins, storage_layers_cm,
                            storage_bins, filter_ess_floor, filter_window_offsets, enkf_noise_field,
-                           filter_rejuvenation=filter_rejuvenation)
+                           filter_rejuvenation=filter_rejuvenation, theta_cov_stride=theta_cov_stride)
         self._start_periods(period_ends, period_thresholds_cm, period_bins, period_flux_max_cm)
         self.next_row, self.kernel_ms, self.launches = 1, 0.0, 0
 

@@ -78,6 +78,7 @@ class EnsembleStepper:
         self.wtd_hist_stride = 0
         self.theta_hist_bins = 0
         self.storage_ranges, self.storage_bins = np.zeros((0, 2), dtype=np.int32), 0
+        self.theta_cov_stride = 0
         self.period_ends, self.period_threshold_nodes = np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int32)
         self.period_bins, self.period_flux_max_log2 = 0, (0, 0)
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = 0, 0.0, 0
@@ -325,6 +326,7 @@ class EnsembleStepper:
         self.profile_stride = stride
         self.theta_hist_bins = 0          # keyed to the profile rows: the library turned it off
         self.storage_ranges, self.storage_bins = np.zeros((0, 2), dtype=np.int32), 0      # ... and the layer storage
+        self.theta_cov_stride = 0         # ... and the theta covariance
 
     def profile_snapshot(self, row=0):
         L.check(self.lib.hc_profile_snapshot(self.h, int(row)))
@@ -506,6 +508,58 @@ class EnsembleStepper:
         """Mean / sigma [cm] of ``layer_storage_table()`` (or of ``table``, e.g. summed over ranks): :func:`layer_storage_stats`."""
         t = self.layer_storage_table() if table is None else table
         return layer_storage_stats(t, self.P, self.T, len(self.storage_ranges), self.profile_stride)
+
+    # -- ensemble covariance of theta(z) and the water table (include/hydrocol.h hc_set_theta_cov) -------------------------
+    def set_theta_cov(self, node_stride):
+        """Accumulate the second moments of every member's theta_vol at the nodes 0, s, 2 s, ... and of its water-table
+        index on the profile rows, in exact integers (0 = off); needs :meth:`set_profile_stats`, and comes before
+        :meth:`profile_snapshot` for row 0 to be counted."""
+        s = int(node_stride)
+        if not -INT32_MAX <= s <= INT32_MAX:
+            raise ValueError("the node stride must be a node count")
+        self.theta_cov_stride = 0
+        L.check(self.lib.hc_set_theta_cov(self.h, s))
+        self.theta_cov_stride = s
+
+    def theta_cov_layout(self):
+        """(node stride, selected nodes n, words per row W) as the library holds them; zeros when off."""
+        s, n, w = C.c_int32(), C.c_int32(), C.c_int64()
+        L.check(self.lib.hc_get_theta_cov_layout(self.h, C.byref(s), C.byref(n), C.byref(w)))
+        return int(s.value), int(n.value), int(w.value)
+
+    def theta_cov_words(self):
+        n = C.c_int64()
+        L.check(self.lib.hc_get_theta_cov_words(self.h, C.byref(n)))
+        return int(n.value)
+
+    def _theta_cov_raw(self):
+        t = np.zeros(self.theta_cov_words(), dtype=np.int64)
+        L.check(self.lib.hc_get_theta_cov(self.h, L.lptr(t), t.size))
+        return t
+
+    def theta_cov_table(self):
+        """[P][n_prow][W] int64: count, S1 [E], S2 packed (:func:`theta_cov_of`) per point and profile row."""
+        return self._theta_cov_raw()[:-1].reshape(self.P, stride_rows(self.T, self.profile_stride), -1)
+
+    def set_theta_cov_table(self, table, outside=0):
+        """Install a table (a checkpoint's, a sum over handles) and the outside count that goes with it."""
+        if not 0 <= int(outside) < 1 << 63:
+            raise ValueError("the outside count must lie in [0, 2^63)")
+        t = np.concatenate([np.ascontiguousarray(table, dtype=np.int64).reshape(-1), np.array([int(outside)], dtype=np.int64)])
+        L.check(self.lib.hc_set_theta_cov_tables(self.h, L.lptr(t), t.size))
+
+    def export_theta_cov(self, device_ptr):
+        """Copy the table and its outside word device-to-device to ``device_ptr`` (``theta_cov_words()`` int64)."""
+        L.check(self.lib.hc_export_theta_cov(self.h, C.c_void_p(int(device_ptr)), self.theta_cov_words()))
+
+    def reset_theta_cov(self):
+        L.check(self.lib.hc_reset_theta_cov(self.h))
+
+    def theta_cov_outside(self):
+        """Members that were not counted (a selected theta NaN, below 0 or above 1) since the table was made."""
+        out = C.c_uint64()
+        L.check(self.lib.hc_get_theta_cov_outside(self.h, C.byref(out)))
+        return int(out.value)
 
     # -- period totals per member (include/hydrocol.h hc_set_period_totals) ---------------------------------------------
     def set_period_totals(self, ends, threshold_nodes=(), bins=0, flux_max_log2=(0, 0)):
@@ -1702,6 +1756,109 @@ def layer_storage_distribution(hist, ranges, dz, levels, stride=1):
     q = np.where(n[..., None, :] > 0, (np.minimum(idx, B - 1) + 0.5) / B * thick, np.nan)
     return {"rows": np.arange(hist.shape[-3], dtype=np.int64) * int(stride), "count": n, "quantiles_cm": q, "levels": lv,
             "thickness_cm": thick}
+
+
+# ---- covariance of theta(z) and the water table (include/hydrocol.h hc_set_theta_cov) ---------------------------------
+THETA_COV_SCALE = 20
+THETA_COV_MAX_MEMBERS = 1 << 22
+THETA_COV_MAX_WORDS = 1 << 30
+
+
+def theta_cov_shape(D, stride):
+    """(n, E, W) of a table at node stride ``stride`` on ``D`` nodes: n = ceil(D / stride) selected nodes, E = n + 1
+    columns (the last is the water table), W = 1 + E + E (E + 1) / 2 words a row."""
+    D, s = int(D), int(stride)
+    if not 1 <= s <= D:
+        raise ValueError(f"the node stride must lie in 1 .. {D}, got {s}")
+    n = (D + s - 1) // s
+    E = n + 1
+    return n, E, 1 + E + E * (E + 1) // 2
+
+
+def theta_cov_index(a, b, E):
+    """Offset of entry (a, b), a <= b < E, in the packed upper triangle: a E - a (a - 1) / 2 + (b - a)."""
+    return a * E - a * (a - 1) // 2 + (b - a)
+
+
+def theta_cov_of(theta, wtd_idx, stride):
+    """The device's table of one row restated in exact integers: ``theta`` [N][D], ``wtd_idx`` [N] -> (words [W] int64,
+    outside).  q_k = rint(theta_{k s} 2^20) for the selected nodes, q_n = the water-table index; a member with a selected
+    theta that is NaN, below 0 or above 1 adds nothing and is counted in ``outside``.  words = count, S1 [E], S2 packed by
+    rows (:func:`theta_cov_index`)."""
+    th = np.asarray(theta, dtype=np.float64)
+    th = th.reshape(-1, th.shape[-1])
+    n, E, W = theta_cov_shape(th.shape[1], stride)
+    sel = th[:, ::int(stride)]
+    with np.errstate(invalid="ignore"):
+        ok = np.all((sel >= 0.0) & (sel <= 1.0), axis=1)
+    q = np.empty((int(ok.sum()), E), dtype=np.int64)
+    q[:, :n] = np.rint(sel[ok] * float(1 << THETA_COV_SCALE)).astype(np.int64)
+    q[:, n] = np.asarray(wtd_idx, dtype=np.int64).reshape(-1)[ok]
+    if q.shape[0] > THETA_COV_MAX_MEMBERS:
+        raise ValueError(f"{q.shape[0]} members exceed 2^22: the sums of products would leave an int64")
+    words = np.zeros(W, dtype=np.int64)
+    words[0] = q.shape[0]
+    words[1:1 + E] = q.sum(axis=0)
+    S2 = q.T @ q                             # int64 matmul: exact, every sum is below 2^62
+    iu = np.triu_indices(E)
+    words[1 + E:] = S2[iu]                   # row-major upper triangle = the packed order
+    return words, int((~ok).sum())
+
+
+def theta_cov_finish(table, dz, stride, D):
+    """Population covariances from table rows ``table`` [..., W] (:func:`theta_cov_of`'s words): for a row of count c >= 1,
+    cov_ab = (c S2_ab - S1_a S1_b) / c^2 with the numerator formed in exact integers, scaled by 2^-20 per theta factor and
+    ``dz`` per water-table factor.  Returns ``count`` [...], ``theta_mean`` [..., n], ``wtd_mean_idx`` [...] (node units),
+    ``theta_cov`` [..., n, n] (symmetric), ``wtd_theta_cov_cm`` [..., n], ``wtd_var_cm2`` [...], ``theta_wtd_corr`` [..., n]
+    and ``theta_corr`` [..., n, n]; NaN where c = 0, correlations NaN where a variance is 0.
+
+    The numerator: with the integer r_a = S1_a mod c (0 <= r_a < c <= 2^22) and m_a = S1_a div c,
+    c S2_ab - S1_a S1_b = c (S2_ab - m_a S1_b - r_a m_b) - r_a r_b: the sum of squares about the integer mean.  It is
+    below 2^63 in magnitude (c^2 times a covariance of at most 2^40), so the wrap-around int64 products give it exactly."""
+    t = np.asarray(table, dtype=np.int64)
+    n, E, W = theta_cov_shape(D, stride)
+    if t.shape[-1] != W:
+        raise ValueError(f"theta covariance rows of {t.shape[-1]} words, the layout has {W}")
+    lead = t.shape[:-1]
+    t = t.reshape(-1, W)
+    c = t[:, 0]
+    S1 = t[:, 1:1 + E]
+    iu = np.triu_indices(E)
+    cs = np.maximum(c, 1)[:, None]
+    m, r = S1 // cs, S1 % cs
+    with np.errstate(over="ignore"):
+        z = t[:, 1 + E:] - m[:, iu[0]] * S1[:, iu[1]] - r[:, iu[0]] * m[:, iu[1]]      # (wraps cancel: |z| < 2^62 + 2^42)
+    lo = z & 0xFFFFFFFF
+    low = cs * lo - r[:, iu[0]] * r[:, iu[1]]                  # |low| < 2^54
+    hi = cs * (z >> 32) + (low >> 32)                         # |hi| < 2^53: exact as a double
+    num = hi.astype(np.float64) * 4294967296.0 + (low & 0xFFFFFFFF).astype(np.float64)     # two exact terms: one rounding
+    scale = np.full(E, 2.0 ** -THETA_COV_SCALE)
+    scale[n] = float(dz)
+    cf = c.astype(np.float64)[:, None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        packed = np.where(cf > 0, num / (cf * cf), np.nan) * (scale[iu[0]] * scale[iu[1]])
+        mean = np.where(cf > 0, S1 / cf, np.nan)
+    full = np.empty((t.shape[0], E, E))
+    full[:, iu[0], iu[1]] = packed
+    full[:, iu[1], iu[0]] = packed
+    var = np.einsum("rii->ri", full)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        vv = var[:, :, None] * var[:, None, :]                 # (the root of a square is exact: a diagonal of ones)
+        corr = np.where((var[:, :, None] > 0) & (var[:, None, :] > 0), full / np.sqrt(vv), np.nan)
+    out = {"count": c.copy(), "theta_mean": mean[:, :n] * 2.0 ** -THETA_COV_SCALE, "wtd_mean_idx": mean[:, n],
+           "theta_cov": full[:, :n, :n], "wtd_theta_cov_cm": full[:, :n, n], "wtd_var_cm2": full[:, n, n],
+           "theta_wtd_corr": corr[:, :n, n], "theta_corr": corr[:, :n, :n]}
+    return {k: v.reshape(lead + v.shape[1:]) for k, v in out.items()}
+
+
+def theta_sensor_gain(fin, sigma):
+    """cov(theta_i, wtd)^2 / ((var theta_i + sigma^2) var wtd) per row and selected node from :func:`theta_cov_finish`'s
+    arrays: the fraction of the water table's variance one probe of error ``sigma`` [m3/m3] at that node removes in a linear
+    update.  NaN where var wtd = 0."""
+    var_t = np.einsum("...ii->...i", fin["theta_cov"])
+    vw = fin["wtd_var_cm2"][..., None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(vw > 0, fin["wtd_theta_cov_cm"] ** 2 / ((var_t + float(sigma) ** 2) * vw), np.nan)
 
 
 # ---- period totals per member (include/hydrocol.h hc_set_period_totals) ------------------------------------------------

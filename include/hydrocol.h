@@ -48,6 +48,10 @@
  *   hc_get_layer_storage_outside, hc_get_layer_storage_overflow, hc_get_layer_storage_layout
  *                      <- (new) dz * sum of theta_vol (src/simulation.py:623) over a depth layer, per member: the water a
  *                         root zone or the whole column stores, as the ensemble's mean, sigma and histogram on the profile rows
+ *   hc_set_theta_cov, hc_get_theta_cov_layout, hc_get_theta_cov_words, hc_get_theta_cov, hc_set_theta_cov_tables,
+ *   hc_export_theta_cov, hc_reset_theta_cov, hc_get_theta_cov_outside
+ *                      <- (new) theta_vol (src/simulation.py:623) and wtd_est (:612) as the ensemble's second moments: the
+ *                         covariance of theta at the selected nodes and the water table on the profile rows
  *   hc_set_period_totals, hc_get_period_totals_words, hc_get_period_totals, hc_set_period_totals_tables,
  *   hc_export_period_totals, hc_get/set/export_period_totals_hist(_table), hc_get/set_period_totals_acc,
  *   hc_reset_period_totals, hc_get_period_totals_outside/overflow/layout
@@ -279,8 +283,9 @@ int hc_synchronize(hc_handle *h);
  * last of those happened: global member id << 24 | forcing row.
  * Test hooks read from the environment at hc_create: HYDROCOL_DEBUG_MAX_ITER (same as hc_set_iteration_budget),
  * HYDROCOL_DEBUG_JAC_REJECT (raises num_jac's retry threshold), HYDROCOL_ROWS_PER_LAUNCH, HYDROCOL_CHUNK_MEMBERS
- * (members per scheduling chunk when several parameter points share a launch), HYDROCOL_DEBUG_CUS (a persistent grid of
- * fewer workgroups than the device has compute units: measurements only). */
+ * (members per scheduling chunk when several parameter points share a launch), HYDROCOL_COV_CHUNK_MEMBERS (members per
+ * chunk of the theta covariance's staging, hc_set_theta_cov), HYDROCOL_DEBUG_CUS (a persistent grid of fewer workgroups
+ * than the device has compute units: measurements only). */
 int hc_get_counters(hc_handle *h, uint64_t *out4);
 /* Rows one kernel launch of hc_step_rows covers; hc_step_rows splits longer requests.  Default (and rows = 0): with the
  * in-kernel noise 48 = one simulated day for ensembles of >= 1 048 576 members, proportionally more for smaller ones
@@ -464,6 +469,48 @@ int hc_reset_layer_storage(hc_handle *h);
 int hc_get_layer_storage_outside(hc_handle *h, uint64_t *count);    /* 0 without a histogram */
 int hc_get_layer_storage_overflow(hc_handle *h, uint64_t *count);   /* the ovf slot */
 int hc_get_layer_storage_layout(hc_handle *h, int32_t *n_layers, int32_t *n_bins, int32_t *ranges);
+
+/* Ensemble covariance of theta(z) and the water table: the second moments of the members' theta_vol at the selected nodes
+ * and of their water-table index, on the profile rows (hc_set_profile_stats, which must be on), in exact integers.  Every
+ * other table is a marginal; this one says how the nodes of a column move together: the ensemble's vertical correlation,
+ * the spread of the storage of any layer chosen after the run, cov(theta_i, wtd) for placing a sensor.
+ *   nodes: with a node stride s >= 1 the selected nodes are i_k = k s, k = 0 .. n - 1, n = ceil(D / s); E = n + 1 columns,
+ *   column n is the water table.
+ *   rows: the profile rows, at the profile stride (slot j <-> row j stride, n_prow slots); row 0 is counted by
+ *   hc_profile_snapshot, the others by hc_step_rows from the states the profile statistics read.  Skipped rows (wtd_obs < 0)
+ *   count no members; spin-up solves accumulate nothing.
+ *   per member: q_k = rint(theta_{i_k} 2^20) for k < n, theta the cell model's theta_vol of the member's psi at the node
+ *   with no noise term (the value the profile statistics quantise and hc_model_nodes returns, bit for bit; theta 2^20 is
+ *   exact, so the rounding is rint's alone; 0 <= q_k <= 2^20).  q_n = b, the find_wtd index of the staged state over all D
+ *   nodes: one below the deepest node with !(psi >= psi_sat), clamped to D - 1, and 0 when there is none.
+ *   A member is counted iff every selected theta satisfies 0 <= theta <= 1 (false for a NaN); a member that is not counted
+ *   adds nothing to any word and one to `outside`.
+ *   table (int64): per point and profile row W = 1 + E + E (E + 1) / 2 words,
+ *     count            members counted
+ *     S1 [E]           sum q_a
+ *     S2 [E (E + 1) / 2]  sum q_a q_b for a <= b, packed by rows: entry (a, b) at a E - a (a - 1) / 2 + (b - a)
+ *   as [P][n_prow][W], then the one `outside` word: P n_prow W + 1 words.  A product is at most 2^40 (below 2^41); a point holds at most
+ *   2^22 members (HC_THETA_COV_MAX_MEMBERS), so S2 <= 2^62 fits an int64.  Integer adds only: the table is the same bits at
+ *   any launch length, member split, chunk length, point order and number of handles / ranks summed.
+ * hc_set_theta_cov: node_stride 0 = off (default); otherwise (re)creates the table zeroed.  HC_ERR_ARG (and off) when the
+ * profile statistics are off, for a stride below 1 or above D, for a point of more than HC_THETA_COV_MAX_MEMBERS members
+ * and for a table of more than HC_THETA_COV_MAX_WORDS words (take a larger node stride or a larger profile stride).
+ * hc_set_profile_stats turns it off.  Like the profile table it is re-created, zeroed, when the points, the forcing rows
+ * or the depth change.  get / set / export take the table's size in words (hc_get_theta_cov_words) and fail on any other.
+ * The members' quantised rows are staged in device memory allocated on first use, at most 1 GiB: a larger ensemble runs
+ * in chunks of members (test hook: HYDROCOL_COV_CHUNK_MEMBERS in the environment at hc_create forces the chunk length).
+ * The step kernels are the same with the table on or off, and with it off nothing is launched or allocated for it. */
+#define HC_THETA_COV_SCALE 20                       /* theta: 2^-20 steps */
+#define HC_THETA_COV_MAX_MEMBERS (1LL << 22)        /* per point: 2^22 products of at most 2^40 keep S2 <= 2^62 */
+#define HC_THETA_COV_MAX_WORDS (1LL << 30)          /* 8 GiB of int64 words */
+int hc_set_theta_cov(hc_handle *h, int32_t node_stride);
+int hc_get_theta_cov_layout(hc_handle *h, int32_t *node_stride, int32_t *n_nodes, int64_t *words_per_row);   /* 0, 0, 0: off */
+int hc_get_theta_cov_words(hc_handle *h, int64_t *n_words);
+int hc_get_theta_cov(hc_handle *h, int64_t *table, int64_t n_words);
+int hc_set_theta_cov_tables(hc_handle *h, const int64_t *table, int64_t n_words);   /* checkpoint / resume, rank sums */
+int hc_export_theta_cov(hc_handle *h, void *device_dst, int64_t n_words);           /* as hc_export_profile_stats */
+int hc_reset_theta_cov(hc_handle *h);
+int hc_get_theta_cov_outside(hc_handle *h, uint64_t *count);
 
 /* Period totals per member: what each member's transpiration and lateral flow sum to over a period of forcing rows (a
  * month, a season, a year), how shallow and how deep its water table got in the period and on how many rows it stood at or
