@@ -142,6 +142,21 @@ EXPORTS = {
     "hc_get_period_totals_outside": ([C.c_void_p, C.POINTER(C.c_uint64)], C.c_int),
     "hc_get_period_totals_overflow": ([C.c_void_p, C.POINTER(C.c_uint64)], C.c_int),
     "hc_get_period_totals_layout": ([C.c_void_p, _ip, _ip, _ip, _ip, _ip, _lp, C.c_int64], C.c_int),
+    "hc_set_root_uptake": ([C.c_void_p, C.c_int32, _ip, _ip, C.c_int32], C.c_int),
+    "hc_get_root_uptake_words": ([C.c_void_p, _lp], C.c_int),
+    "hc_get_root_uptake": ([C.c_void_p, _lp, C.c_int64], C.c_int),
+    "hc_set_root_uptake_tables": ([C.c_void_p, _lp, C.c_int64], C.c_int),
+    "hc_export_root_uptake": ([C.c_void_p, C.c_void_p, C.c_int64], C.c_int),
+    "hc_get_root_uptake_hist": ([C.c_void_p, _ip, C.c_int64], C.c_int),
+    "hc_set_root_uptake_hist_table": ([C.c_void_p, _ip, C.c_int64], C.c_int),
+    "hc_export_root_uptake_hist": ([C.c_void_p, C.c_void_p, C.c_int64], C.c_int),
+    "hc_get_root_uptake_acc": ([C.c_void_p, _lp, C.c_int64], C.c_int),
+    "hc_set_root_uptake_acc": ([C.c_void_p, _lp, C.c_int64], C.c_int),
+    "hc_reset_root_uptake": ([C.c_void_p], C.c_int),
+    "hc_get_root_uptake_outside": ([C.c_void_p, C.POINTER(C.c_uint64)], C.c_int),
+    "hc_get_root_uptake_overflow": ([C.c_void_p, C.POINTER(C.c_uint64)], C.c_int),
+    "hc_get_root_uptake_layout": ([C.c_void_p, _ip, _ip, _ip, _ip], C.c_int),
+    "hc_root_uptake_eval": ([C.c_void_p, C.c_int64, _dp, _dp], C.c_int),
     "hc_wtd_distribution": ([C.c_int, _ip, _ip, C.c_int64, C.c_int32, _dp, C.c_int32, C.c_double, _lp, _ip, _dp], C.c_int),
     "hc_set_filter": ([C.c_void_p, C.c_int32, C.c_double, C.c_uint64], C.c_int),
     "hc_get_filter_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),

@@ -86,6 +86,20 @@ unknown keys, only membership of the 12 is checked):
   ``period_quantile_levels`` and ``period_{transpiration,lateral_flow,wtd_shallowest,wtd_deepest}_quantile_cm``
   ``[n_period][Lv]`` (a sweep: a leading ``[P]`` axis on the per-period statistics), and the run ends with the line
   `` [Ensemble xN] periods: R periods, K quantities``.
+* ``"Periods": {..., "Uptake": {"Layers_cm": [[0, 100], [100, 300], [300, 1500]], "Bins": 128, "Quantiles": [0.05, 0.5,
+  0.95]}}``: root-water uptake by depth over the same periods (include/hydrocol.h hc_set_root_uptake): each member's uptake
+  of every solved daylight row, evaluated on the GPU from the row's end state, totalled over the period for the whole
+  column and for 1 to 8 depth layers (a midpoint belongs to a layer when top <= z + dz / 2 < bottom), reduced over the
+  members at the period's end, and the period's uptake at every midpoint.  ``Bins`` (optional) adds histograms of each
+  layer's share of a member's total and ``Quantiles`` (default 0.05, 0.5, 0.95; needs ``Bins``) their quantiles.  Refused
+  before any GPU call: a non-object, an unknown key, more than 8 layers, a layer that holds no root cell, ``Quantiles``
+  without ``Bins``, ``Simulation_Flags.ET`` off.  Added to the file: ``uptake_layers_cm``, ``uptake_cells``,
+  ``uptake_depth_cm`` ``[D-1]``, ``uptake_count``, ``uptake_total_{mean,std}_cm`` ``[n_period]``,
+  ``uptake_layer_{mean,std}_cm`` and ``uptake_share_of_mean`` ``[n_period][L]``, ``uptake_profile`` ``[n_period][D-1]``,
+  ``uptake_depth_quantile_cm`` ``[n_period][2]``, ``uptake_overflow`` and, with ``Bins``, ``uptake_share_hist``
+  ``[n_period][L][B]`` int32, ``uptake_hist_outside``, ``uptake_quantile_levels`` and ``uptake_share_quantile``
+  ``[n_period][Lv][L]`` (a sweep: a leading ``[P]`` axis), and the run ends with the line
+  `` [Ensemble xN] uptake: L layers over R periods, median depth ... cm``.
 * ``"Ensemble": {..., "Distribution": {"Stride": 48, "Quantiles": [0.05, 0.5, 0.95]}}``: the members' water-table index
   counted per row on the GPU -- every 48th forcing row (default 48; 0 = off) a histogram over the depth grid, summed over
   the ranks like the moments -- and from it the quantile depths (NumPy's ``method="inverted_cdf"``; default levels 0.05,
@@ -269,6 +283,7 @@ def main(params_file=None, data_file=None, seed=None, device=0, gpus=None, _sett
             profile_distribution_settings(params["Ensemble"])
             storage_settings(params["Ensemble"])
             period_settings(params["Ensemble"])
+            uptake_settings(params["Ensemble"])
         n_gpus = multigpu.requested_gpus(gpus, params)
         if params.get("Ensemble"):
             filter_settings(params["Ensemble"], n_gpus)     # so does a bad Filter block
@@ -365,9 +380,11 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     days = int(ens.get("Days", (forcing.dim_t - 1) // 48))
     rows = min(days * 48, forcing.dim_t - 1)
     plan = period_plan(periods, cols, forcing, rows)            # before any GPU call, like the storage's ranges
+    uptake = uptake_settings(ens)
     if ens.get("Points"):
         return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels, assim,
-                          theta, storage, periods, plan, corr, cov)
+                          theta, storage, periods, plan, corr, cov, uptake)
+    ucells = uptake_plan(uptake, [cols])                        # (so are the uptake's layers)
     sharded = enkf_sharded(ens)
     fsharded = filter_sharded(ens)
     if sharded:
@@ -390,7 +407,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
                              spinup=str(ens.get("Spinup", "shared")).lower(), profile_stride=stride,
                              wtd_hist_stride=dist_stride, theta_hist_bins=theta[0], **assim.kwargs(),
                              **_storage_kwargs(storage), **_covariance_kwargs(cov), **_period_kwargs(periods, plan),
-                             **shard_kw, **_noise_correlation_kwargs(corr))
+                             **_uptake_kwargs(uptake), **shard_kw, **_noise_correlation_kwargs(corr))
     label = f"Ensemble x{n_members}"
     _step_all(sim, rows, label, ranks)
     # the run's one collective: int64 (count, sum idx, sum idx^2) per row, exact and order-independent
@@ -427,6 +444,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     extra.update(cov_tables)
     ptables, period_line = _reduce_periods(ranks, sim, [0], 1, cols, forcing, periods, plan, label, keep_points=False)
     extra.update(ptables)
+    utables, uptake_line = _reduce_uptake(ranks, sim, [0], 1, cols, uptake, ucells, plan, label, keep_points=False)
+    extra.update(utables)
     # the filters' tables describe the one point: every rank of a sharded run holds the same ones, and rank 0's are taken
     # (placed by it alone; a sum over the ranks would count them world times)
     eids = [0] if ranks.rank == 0 else []
@@ -441,7 +460,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     arrays = dict(moments=moments, wtd_mean_cm=mean_cm, wtd_std_cm=std_cm, rows=np.array(rows),
                   members=np.array(n_members), gpus=np.array(ranks.world), initial_cond=psi0, **extra)
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "ensemble water-table statistics", ranks)
-    _print_lines(crps_line, *assim_lines, theta_line, storage_line, cov_line, period_line,
+    _print_lines(crps_line, *assim_lines, theta_line, storage_line, cov_line, period_line, uptake_line,
                  corr_line if ranks.rank == 0 else None)
     sim.close()
 
@@ -790,7 +809,81 @@ def _covariance_kwargs(cov):
     return {} if cov is None else dict(theta_cov_stride=cov[0])
 
 
-PERIOD_KEYS = ("Rows", "Calendar", "Shallower_than_cm", "Bins", "Transpiration_max_cm", "Lateral_flow_max_cm", "Quantiles")
+PERIOD_KEYS = ("Rows", "Calendar", "Shallower_than_cm", "Bins", "Transpiration_max_cm", "Lateral_flow_max_cm", "Quantiles",
+               "Uptake")
+UPTAKE_KEYS = ("Layers_cm", "Bins", "Quantiles")
+
+
+def uptake_settings(ens):
+    """Ensemble.Periods.Uptake -> {"layers_cm", "bins", "levels"}; None when absent.  Pure: runs before any GPU call, and
+    a bad value is a ValueError (message + exit status 1).  ``Layers_cm`` holds 1 to 8 [top, bottom] pairs in cm; ``Bins``
+    is optional (0: moments and the profile only) and ``Quantiles`` needs it.  (The enclosing block's own checks -- among
+    them the refusal of a sharded particle filter on a single-point run -- are period_settings'.)"""
+    import math
+    from numbers import Real
+    from .stepper import UPTAKE_MAX_LAYERS
+    periods = ens.get("Periods")
+    block = periods.get("Uptake") if isinstance(periods, dict) else None
+    if block is None:
+        return None
+    if not isinstance(block, dict):
+        raise ValueError(f" Ensemble: Periods.Uptake = {block!r} must be an object such as "
+                         f"{{\"Layers_cm\": [[0, 100], [100, 300], [300, 1500]], \"Bins\": 128}}.")
+    unknown = sorted(set(block) - set(UPTAKE_KEYS))
+    if unknown:
+        raise ValueError(f" Ensemble: Periods.Uptake has unknown keys {unknown} (known: {list(UPTAKE_KEYS)}).")
+    layers = block.get("Layers_cm")
+    if not isinstance(layers, (list, tuple)) or not 1 <= len(layers) <= UPTAKE_MAX_LAYERS:
+        raise ValueError(f" Ensemble: Periods.Uptake.Layers_cm = {layers!r} must be a list of 1 to {UPTAKE_MAX_LAYERS} "
+                         f"[top, bottom] pairs in cm.")
+    for lay in layers:
+        ok = isinstance(lay, (list, tuple)) and len(lay) == 2 and all(
+            not isinstance(v, bool) and isinstance(v, Real) and math.isfinite(v) for v in lay)
+        if not ok or not lay[0] < lay[1]:
+            raise ValueError(f" Ensemble: Periods.Uptake.Layers_cm: {lay!r} is not a [top, bottom] pair in cm with top < bottom.")
+    bins = block.get("Bins", 0)
+    if "Bins" in block and (isinstance(bins, bool) or not isinstance(bins, Real) or bins not in (32, 64, 128, 256, 512, 1024)):
+        raise ValueError(f" Ensemble: Periods.Uptake.Bins = {bins!r} must be a power of two in 32 .. 1024.")
+    if "Quantiles" in block and not bins:
+        raise ValueError(" Ensemble: Periods.Uptake.Quantiles needs Periods.Uptake.Bins (it belongs to the histograms).")
+    levels = None
+    if bins:
+        levels = block.get("Quantiles", [0.05, 0.5, 0.95])
+        if not isinstance(levels, (list, tuple)) or not levels or len(levels) > 16:
+            raise ValueError(f" Ensemble: Periods.Uptake.Quantiles = {levels!r} must be a list of 1 to 16 levels in [0, 1].")
+        for q in levels:
+            if isinstance(q, bool) or not isinstance(q, Real) or not math.isfinite(q) or not 0.0 <= q <= 1.0:
+                raise ValueError(f" Ensemble: Periods.Uptake.Quantiles: {q!r} is not a level in [0, 1].")
+        levels = tuple(float(q) for q in levels)
+    return {"layers_cm": tuple((float(a), float(b)) for a, b in layers), "bins": int(bins), "levels": levels}
+
+
+def uptake_plan(uptake, cols_list):
+    """The layers' midpoint-cell ranges on the column (stepper.layer_cells), with the refusals in the CLI's words: ET off
+    (there is no uptake), a layer that holds no midpoint, a layer that holds no root cell of some point.  None without a
+    block.  Before any GPU call."""
+    from .stepper import layer_cells
+    if uptake is None:
+        return None
+    cols = cols_list[0]
+    if not all(c.flags["ET"] for c in cols_list):
+        raise ValueError(" Ensemble: Periods.Uptake needs the evapo-transpiration (Simulation_Flags.ET is off: there is no "
+                         "root-water uptake to record).")
+    try:
+        cells = layer_cells(cols.z, uptake["layers_cm"])
+    except ValueError as bad:
+        raise ValueError(f" Ensemble: Periods.Uptake.Layers_cm: {bad}.") from None
+    for c in cols_list:
+        first = 0 if c.n_root_first else 1
+        for lay, (lo, hi) in zip(uptake["layers_cm"], cells):
+            if not (lo <= c.n_root_int and hi > first):
+                raise ValueError(f" Ensemble: Periods.Uptake.Layers_cm: layer {list(lay)!r} cm holds no root cell (the root "
+                                 f"zone ends at {float(c.z[c.n_root_int] + c.dz):g} cm).")
+    return cells
+
+
+def _uptake_kwargs(uptake):
+    return {} if uptake is None else dict(uptake_layers_cm=uptake["layers_cm"], uptake_bins=uptake["bins"])
 
 
 def period_settings(ens):
@@ -1705,8 +1798,65 @@ def _reduce_periods(ranks, sim, ids, P, cols, forcing, periods, plan, label, kee
     return out, line
 
 
+def _reduce_uptake(ranks, sim, ids, P, cols, uptake, cells, plan, label, keep_points):
+    """The root-uptake tables (``uptake``: the block's settings, ``cells``: the layers' cell ranges, ``plan``: the periods')
+    from this rank's handle ``sim`` (None: no points), its points ``ids`` placed in the run's [P] tables and summed over
+    the ranks like the period totals' -- the overflow and outside counts with them -- then the statistics, the profile,
+    the quantiles and the closing line (rank 0)."""
+    import numpy as np
+    from .multigpu import place_points
+    from .stepper import (root_uptake_distribution, root_uptake_profile, root_uptake_stats, root_uptake_table_layout,
+                          split_root_uptake_table)
+    if uptake is None:
+        return {}, None
+    ends = plan[0]
+    n_period, L, bins, D = len(ends), len(cells), uptake["bins"], cols.dim_d
+    local = (sim.uptake_table() if sim is not None else
+             np.zeros(root_uptake_table_layout(0, n_period, L, D)["words"][0], dtype=np.int64))
+    parts = split_root_uptake_table(local, len(ids), n_period, L, D)
+    table = ranks.allreduce_sum(np.concatenate([place_points(parts[k], ids, P).reshape(-1) for k in ("umom", "ucnt", "uprof")]
+                                               + [parts["ovf"]]))
+    if bins:
+        lh = sim.stepper.root_uptake_hist() if sim is not None else np.zeros((0, n_period, L, bins), dtype=np.int32)
+        hist = place_points(lh, ids, P, ranks)
+        outside = int(ranks.allreduce_sum(np.array([sim.stepper.root_uptake_outside() if sim is not None else 0],
+                                                   dtype=np.int64))[0])
+    if ranks.rank != 0:
+        return {}, None
+    stats = root_uptake_stats(table, P, ends, L, D)
+    prof = root_uptake_profile(table, P, ends, L, D, cols.z)
+    lead = (lambda v: v[None]) if keep_points and P == 1 else (lambda v: v)
+    out = {"uptake_layers_cm": np.asarray(uptake["layers_cm"], dtype=np.float64),
+           "uptake_cells": np.asarray(cells, dtype=np.int64),
+           "uptake_depth_cm": np.asarray(prof["depth_cm"], dtype=np.float64),
+           "uptake_count": np.asarray(lead(stats["count"]), dtype=np.int64),
+           "uptake_overflow": np.array(stats["overflow"], dtype=np.int64),
+           "uptake_profile": np.asarray(lead(prof["profile"]), dtype=np.float64),
+           "uptake_depth_quantile_cm": np.asarray(lead(prof["depth_quantile_cm"]), dtype=np.float64)}
+    for name in ("total_mean_cm", "total_std_cm", "layer_mean_cm", "layer_std_cm", "share_of_mean"):
+        out["uptake_" + name] = np.asarray(lead(stats[name]), dtype=np.float64)
+    if bins:
+        if not keep_points:
+            hist = hist[0]
+        dist = root_uptake_distribution(hist, uptake["levels"])
+        out.update({"uptake_share_hist": np.asarray(hist, dtype=np.int32),
+                    "uptake_hist_outside": np.array(outside, dtype=np.int64),
+                    "uptake_quantile_levels": np.asarray(dist["levels"], dtype=np.float64),
+                    "uptake_share_quantile": np.asarray(dist["share_quantile"], dtype=np.float64)})
+    n = int((np.asarray(stats["count"]).reshape(-1, n_period) > 0).any(axis=0).sum())
+    # the depth above which half of the run's uptake lies: the periods' (and points') limbs summed, then the quantile
+    whole = split_root_uptake_table(table, P, n_period, L, D)["uprof"].astype(object).sum(axis=(0, 1))
+    cum = np.cumsum(whole[:, 0] + whole[:, 1] * (1 << 20))
+    median = float(cols.z[int(np.argmax(2 * cum >= cum[-1]))] + cols.dz) if int(cum[-1]) > 0 else float("nan")
+    line = f" [{label}] uptake: {L} layers over {n} periods, median depth {median:g} cm"
+    if stats["overflow"]:
+        line += f" ({stats['overflow']} values clamped)"
+    return out, line
+
+
 def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride=0, dist_levels=None,
-               assim=Assimilation(), theta=(0, None), storage=None, periods=None, plan=None, corr=None, cov=None):
+               assim=Assimilation(), theta=(0, None), storage=None, periods=None, plan=None, corr=None, cov=None,
+               uptake=None):
     """Parameter points x members: this rank's points in one handle (ensemble.SweepSimulation), the whole table assembled
     over the ranks (multigpu.assemble_points)."""
     import numpy as np
@@ -1730,11 +1880,12 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     local, sim = {}, None
     stride = _profile_stride(ens)
     label = f"Sweep {P} points x{n_members}"
+    ucells = uptake_plan(uptake, cols_all)                      # before any GPU call
     if mine:
         sim = SweepSimulation(points, forcing, n_members, seed=int(ens.get("Seed", 0)), device=device, point_ids=mine,
                               profile_stride=stride, wtd_hist_stride=dist_stride, theta_hist_bins=theta[0],
                               **assim.kwargs(), **_storage_kwargs(storage), **_covariance_kwargs(cov),
-                              **_period_kwargs(periods, plan), **_noise_correlation_kwargs(corr))
+                              **_period_kwargs(periods, plan), **_uptake_kwargs(uptake), **_noise_correlation_kwargs(corr))
         _step_all(sim, rows, label, ranks)
         table = sim.moments()
         for j, k in enumerate(mine):
@@ -1756,6 +1907,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     arrays.update(cov_tables)
     ptables, period_line = _reduce_periods(ranks, sim, mine, P, ref, forcing, periods, plan, label, keep_points=True)
     arrays.update(ptables)
+    utables, uptake_line = _reduce_uptake(ranks, sim, mine, P, ref, uptake, ucells, plan, label, keep_points=True)
+    arrays.update(utables)
     atables, assim_lines = _reduce_assimilation(ranks, sim, mine, P, T, ref, assim, label, keep_points=True)
     arrays.update(atables)
     ctables, corr_line = _noise_correlation_arrays(corr, cols_all, label, keep_points=True)
@@ -1763,7 +1916,7 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     if sim is not None:
         sim.close()
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "sweep's water-table statistics", ranks)
-    _print_lines(crps_line, *assim_lines, theta_line, storage_line, cov_line, period_line,
+    _print_lines(crps_line, *assim_lines, theta_line, storage_line, cov_line, period_line, uptake_line,
                  corr_line if ranks.rank == 0 else None)
 
 

@@ -256,6 +256,23 @@ struct hc_handle {
     DevBuf<long long> pacc_alt;
     AccTable<long long> pmom{"words"};
     AccTable<int> phist{"entries"};
+    // root-water uptake by depth (hc_set_root_uptake), on the period totals' periods: the layers' midpoint-cell ranges and
+    // the share histograms' bin count; the points' midpoint tables as hc_set_column / hc_add_point received them plus
+    // 1 / (por - wlt), [P][5][D - 1], on the host and (uploaded by the first call that needs them) on the device; the
+    // members' int64 accumulators [L + 1][N] keyed by (N, L + 1) and their second buffer for the particle filter's
+    // ancestry; the int64 table umom [P][n_period][L + 1][5], ucnt, uprof [P][n_period][D - 1][2], ovf and, with bins, the
+    // int32 table [P][n_period][L][B] + the outside count, keyed like the profile table; the forcing's daylight on the host
+    int upt_layers = 0;          // 0: off
+    int upt_bins = 0;            // 0: no histogram
+    int upt_range[HC_UPTAKE_MAX_LAYERS][2] = {};
+    std::vector<double> mid_host;
+    DevBuf<double> mid_tabs;
+    bool mid_dirty = true;
+    AccTable<long long> uacc{"words"};
+    DevBuf<long long> uacc_alt;
+    AccTable<long long> upt{"words"};
+    AccTable<int> uhist{"entries"};
+    std::vector<unsigned char> h_daylight;
     // particle filter on the well's water table (hc_set_filter): diagnostics float64 [P][n_arow][4] keyed by
     // (points, rows, stride), the second state / base buffers of the gather, the last assimilation's q_b, {Q, r} and
     // ancestors (test hooks), and the host copy of wtd_obs that decides which rows are assimilated
@@ -844,6 +861,237 @@ __global__ __launch_bounds__(PROF_TILE * PROF_WAVES) void layer_storage_kernel(
     }
 }
 
+// ---- root-water uptake by depth (hc_set_root_uptake, include/hydrocol.h)
+// the layers of a handle as a kernel argument: midpoint-cell ranges [c0, c1); plane 0 of the totals is every cell
+struct UptLayers {
+    int n;
+    int c0[HC_UPTAKE_MAX_LAYERS], c1[HC_UPTAKE_MAX_LAYERS];
+};
+constexpr int UPT_TAB_POR = 0, UPT_TAB_FC = 1, UPT_TAB_WLT = 2, UPT_TAB_INVD1 = 3, UPT_TAB_ROOT = 4, UPT_NTAB = 5;
+
+// inclusive scan over the 64 lanes by doubling offsets: at offset o lane l >= o adds lane l - o's value of the step before
+__device__ __forceinline__ double upt_scan(double v, int lane)
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int o = 1; o < PROF_TILE; o <<= 1) {
+        const double w = __shfl_up(v, o, PROF_TILE);
+        v = lane >= o ? v + w : v;
+    }
+    return v;
+}
+// the 64 lanes' values by halving strides (layer_storage_kernel's order), lane 0's total handed to every lane
+__device__ __forceinline__ double upt_sum(double v)
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int s = PROF_TILE / 2; s > 0; s >>= 1) v += __shfl_down(v, s, PROF_TILE);
+    return __shfl(v, 0, PROF_TILE);
+}
+
+// One forcing row's uptake per member: layer_storage_kernel's shape.  Grid y = member slices of one point (block y takes
+// slices y, y + gridDim.y, ...), z = point; wave w of a block takes members m0 + w, m0 + w + 4, ... of a slice, and lane j
+// of it owns the midpoint cells i = 64 r + j of round r = 0, 1, ...: y_i = 0.5 (psi_i + psi_{i+1}) reads two runs of 64
+// contiguous doubles of the member's row.  The five midpoint tables of the point (porosity, field capacity, wilting
+// point, 1 / (por - wlt), root density: [5][cells] doubles, read with lane = consecutive double, one 256-byte bank row a
+// half-wave, no conflict) sit in LDS, and each wave has a row of `cells` doubles of its own there that holds theta, then
+// rho, then x of the member in turn: a lane reads back only what it wrote, so the row needs no barrier.  The cell model
+// runs on the cells 0 ... n_root_int alone (on every midpoint for the test hook, which also wants theta below the roots).
+// The order of every sum is fixed by n_root_int alone (include/hydrocol.h): lane partials over the rounds ascending, the 64
+// partials by halving strides; the cumulative theta by a doubling-offset scan per round plus the carry of the rounds
+// before, run twice (once for the total, once for the cells) instead of being stored.  Plain IEEE operations, no
+// contraction, no reciprocal shortcuts.  Lane l <= L then owns plane l of the member's totals: it quantises U_l and adds
+// it to the member's accumulator -- the member belongs to this wave alone, a plain read-modify-write.  The depth-resolved
+// q_i go as two 20-bit limbs into the block's LDS image uint64 [n_root_int + 1][2] with ds_add_u64 on the lane's own two
+// addresses (16 bytes a lane: a half-wave's 32 lanes cover two bank rows, two passes an instruction; the four waves meet
+// on a word only through the LDS atomic, and a zero adds nothing); after the barrier the nonzero words go to uprof with
+// int64 atomics.  Integer adds only beyond the member: the tables do not depend on any order.
+__global__ __launch_bounds__(PROF_TILE * PROF_WAVES) void root_uptake_kernel(
+    const StepArgs A, const double *mid_tabs, int special, const double *stage, const int *wtd_obs, const double *atm,
+    const unsigned char *daylight, long long row, long long period, long long n_period, long long members_per_block,
+    const UptLayers Ly, long long *uacc, long long *uprof, unsigned long long *ovf_word, double *theta_out, double *u_out)
+{
+#pragma clang fp contract(off)
+    const bool eval = theta_out != nullptr;
+    if (!eval && wtd_obs[row] < 0) return;
+    const int D = A.D, M = D - 1, L = Ly.n;
+    const int lane = threadIdx.x % PROF_TILE, wave = threadIdx.x / PROF_TILE;
+    const long long point = blockIdx.z;
+    const long long end = (point + 1) * A.members_per_point;
+    const long long slice0 = point * A.members_per_point + (long long)blockIdx.y * members_per_block;
+    const long long hop = (long long)gridDim.y * members_per_block;
+    if (slice0 >= end) return;               // (the whole block: nothing is shared yet)
+    const ColumnDev P = A.P[point];
+    const int n_int = P.n_root_int;
+    const int n_model = eval ? M : n_int + 1;                    // cells the cell model runs on
+    const int rounds = (n_model + PROF_TILE - 1) / PROF_TILE, cells = rounds * PROF_TILE;
+    const int n_img = 2 * (n_int + 1);
+    extern __shared__ double upt_lds[];      // tables [5][cells], the waves' rows [4][cells], the image uint64 [n_int + 1][2]
+    double *tab = upt_lds, *ws = upt_lds + (size_t)(UPT_NTAB + wave) * cells;
+    unsigned long long *img = reinterpret_cast<unsigned long long *>(upt_lds + (size_t)(UPT_NTAB + PROF_WAVES) * cells);
+    __shared__ unsigned ovf_sum;
+    for (int k = threadIdx.x; k < UPT_NTAB * cells; k += PROF_TILE * PROF_WAVES) {
+        const int t = k / cells, i = k % cells;
+        tab[k] = i < n_model ? mid_tabs[((size_t)point * UPT_NTAB + t) * M + i] : 0.0;
+    }
+    for (int k = threadIdx.x; k < n_img; k += PROF_TILE * PROF_WAVES) img[k] = 0;
+    if (threadIdx.x == 0) ovf_sum = 0;
+    __syncthreads();
+
+    const double *t_por = tab + UPT_TAB_POR * cells, *t_fc = tab + UPT_TAB_FC * cells, *t_wlt = tab + UPT_TAB_WLT * cells;
+    const double *t_invd1 = tab + UPT_TAB_INVD1 * cells, *t_root = tab + UPT_TAB_ROOT * cells;
+    const bool on = P.flag_et && (daylight[row] & 1);            // (the hook is a normal-mode call: never a spin-up solve)
+    const double atm_r = atm[row], dz = P.dz;
+    const double s_flux = ldexp(1.0, HC_PROF_SCALE_FLUX), s_prof = ldexp(1.0, HC_UPTAKE_SCALE_PROFILE);
+    const int r_int = (n_int + 1 + PROF_TILE - 1) / PROF_TILE;   // rounds that hold a root cell
+    unsigned ovf = 0;
+    for (long long m0 = slice0; m0 < end; m0 += hop) {
+        const long long m1 = m0 + members_per_block < end ? m0 + members_per_block : end;
+        for (long long m = m0 + wave; m < m1; m += PROF_WAVES) {
+            const double *psi_m = stage + (size_t)m * D;
+            // theta at the midpoints, and sum (theta - wlt) over the interior root cells 1 ... n_int
+            double s_w = 0.0, th0 = 0.0;
+            for (int r = 0; r < rounds; r++) {
+                const int i = r * PROF_TILE + lane;
+                double th = 0.0;
+                if (i < n_model) {
+                    const double y = 0.5 * (psi_m[i] + psi_m[i + 1]);
+                    double K, C, kb, pf;
+                    if (special)
+                        model_cell<true>(P, y, t_por[i], 0.0, 0.0, 0.0, 0.0, 0.0, th, K, C, kb, pf);
+                    else
+                        model_cell<false>(P, y, t_por[i], 0.0, 0.0, 0.0, 0.0, 0.0, th, K, C, kb, pf);
+                    if (eval) theta_out[(size_t)m * M + i] = th;
+                }
+                ws[i] = th;
+                s_w += (i >= 1 && i <= n_int) ? th - t_wlt[i] : 0.0;
+                if (r == 0) th0 = __shfl(th, 0, PROF_TILE);
+            }
+            // (a) the interior call: cells 1 ... n_int normalised together
+            double tr_pot = 0.0;             // 0: no uptake in the interior
+            if (on && n_int > 0) {
+                const double water_k = upt_sum(s_w) * dz;
+                double tot_x = 0.0;
+                if (water_k > 0.0) {
+                    double carry = 0.0;
+                    bool all_one = true;
+                    for (int r = 0; r < r_int; r++) {
+                        const int i = r * PROF_TILE + lane;
+                        const bool in = i >= 1 && i <= n_int;
+                        const double sc = upt_scan(in ? ws[i] : 0.0, lane);
+                        carry = carry + __shfl(sc, PROF_TILE - 1, PROF_TILE);
+                        all_one = all_one && (!in || ws[i] > t_fc[i]);
+                    }
+                    double total = carry * dz;
+                    total = total == 0.0 ? 1.0 : total;
+                    const double a2v = __all(all_one) ? 0.1 : 1.0;       // the "roots drowning" guard
+                    carry = 0.0;
+                    double s_r = 0.0;
+                    for (int r = 0; r < r_int; r++) {
+                        const int i = r * PROF_TILE + lane;
+                        const bool in = i >= 1 && i <= n_int;
+                        const double th = ws[i];
+                        const double sc = upt_scan(in ? th : 0.0, lane);
+                        const double local = (carry + sc) * dz;
+                        carry = carry + __shfl(sc, PROF_TILE - 1, PROF_TILE);
+                        const double a1 = fmax(th * t_invd1[i], local / total);
+                        const double rho = (in && th > t_fc[i]) ? fabs(a1 * a2v) : 0.0;
+                        ws[i] = rho;
+                        s_r += rho;
+                    }
+                    double tot = upt_sum(s_r) * dz;
+                    tot = tot == 0.0 ? 1.0 : tot;
+                    double s_x = 0.0;
+                    for (int r = 0; r < r_int; r++) {
+                        const int i = r * PROF_TILE + lane;
+                        const double x = (ws[i] / tot) * t_root[i];
+                        ws[i] = x;
+                        s_x += x;
+                    }
+                    tot_x = upt_sum(s_x) * dz;
+                    if (tot_x > 1.0) {
+                        s_x = 0.0;
+                        for (int r = 0; r < r_int; r++) {
+                            const int i = r * PROF_TILE + lane;
+                            const double x = ws[i] / tot_x;
+                            ws[i] = x;
+                            s_x += x;
+                        }
+                        tot_x = upt_sum(s_x) * dz;
+                    }
+                    if (tot_x > 0.0) tr_pot = fmin(atm_r, water_k) / tot_x;
+                }
+            }
+            const bool have = tr_pot != 0.0;     // (ws holds x only then; a zero rate gives zeros either way)
+            // (b) the first-midpoint call: cell 0 normalised on its own, by every lane alike
+            double u0 = 0.0;
+            if (on && P.n_root_first > 0) {
+                const double water_k = (th0 - t_wlt[0]) * dz;
+                if (water_k > 0.0) {
+                    const double local = th0 * dz;
+                    const double total = local == 0.0 ? 1.0 : local;
+                    const double a1 = fmax(th0 * t_invd1[0], local / total);
+                    double rho = th0 > t_fc[0] ? fabs(a1 * 0.1) : 0.0;   // one cell: above field capacity it is "all cells"
+                    double tot = rho * dz;
+                    tot = tot == 0.0 ? 1.0 : tot;
+                    double x0 = (rho / tot) * t_root[0];
+                    double tot_x = x0 * dz;
+                    if (tot_x > 1.0) {
+                        x0 = x0 / tot_x;
+                        tot_x = x0 * dz;
+                    }
+                    if (tot_x > 0.0) u0 = (fmin(atm_r, water_k) / tot_x) * x0;
+                }
+            }
+            // the member's u_i: the hook's output, or the layer totals and the depth-resolved limbs
+            double x[HC_UPTAKE_MAX_LAYERS + 1];
+#pragma unroll
+            for (int l = 0; l <= HC_UPTAKE_MAX_LAYERS; l++) x[l] = 0.0;
+            for (int r = 0; r < (eval ? rounds : r_int); r++) {
+                const int i = r * PROF_TILE + lane;
+                double u = (have && i >= 1 && i <= n_int) ? tr_pot * ws[i] : 0.0;
+                u = i == 0 ? u0 : u;
+                if (eval) {
+                    if (i < M) u_out[(size_t)m * M + i] = u;
+                    continue;
+                }
+                x[0] += u;
+#pragma unroll
+                for (int l = 0; l < HC_UPTAKE_MAX_LAYERS; l++)
+                    if (l < L) x[l + 1] += (i >= Ly.c0[l] && i < Ly.c1[l]) ? u : 0.0;
+                if (i <= n_int) {
+                    const long long q = prof_quantise(u, s_prof, ovf);
+                    if (q > 0) {
+                        atomicAdd(&img[2 * i], (unsigned long long)(q & ((1LL << 20) - 1)));
+                        atomicAdd(&img[2 * i + 1], (unsigned long long)(q >> 20));
+                    } else if (q < 0) {          // (u >= 0 by construction: a guard that keeps the limbs unsigned)
+                        ovf++;
+                    }
+                }
+            }
+            if (eval) continue;
+            double T = 0.0;
+#pragma unroll
+            for (int l = 0; l <= HC_UPTAKE_MAX_LAYERS; l++) {
+                if (l <= L) {                    // (wave-uniform)
+                    const double t = upt_sum(x[l]);
+                    T = lane == l ? t : T;
+                }
+            }
+            if (lane <= L) uacc[(size_t)lane * A.n_members + m] += prof_quantise(dz * T, s_flux, ovf);
+        }
+    }
+    if (eval) return;
+    if (ovf) atomicAdd(&ovf_sum, ovf);
+    __syncthreads();
+    long long *t = uprof + ((size_t)point * n_period + period) * M * 2;
+    for (int k = threadIdx.x; k < n_img; k += PROF_TILE * PROF_WAVES) {
+        const unsigned long long c = img[k];
+        if (c) atomicAdd(reinterpret_cast<unsigned long long *>(t + k), c);
+    }
+    if (threadIdx.x == 0 && ovf_sum) atomicAdd(ovf_word, (unsigned long long)ovf_sum);
+}
+
 // transpiration / lateral flow of every solved row of a launch, the member count and sum |obs - wtd| (abs_error in grid
 // steps): one block per (launch row, point) as moments_kernel, partial sums through cross-lane shuffles then LDS, one writer
 __global__ __launch_bounds__(256) void flux_stats_kernel(const double *diag, const unsigned short *wtd, const int *wtd_obs,
@@ -1130,6 +1378,123 @@ __global__ void period_gather_kernel(const long long *anc, const long long *acc,
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
         const long long m = (long long)(e % n_members), a = anc[m];
         acc_out[e] = acc[e - m + (a >= 0 && a < n_members ? a : m)];     // (every slot is filled: a guard)
+    }
+}
+
+// The end of period `period` for the uptake: period_reduce_kernel's shape, launched before it (the members it counts are
+// those period_reduce_kernel is about to count: wtd_shallowest != 65535 in the period accumulators `solved`).  A counted
+// member enters umom [P][n_period][L + 1][5] with v_k = A_k >> 12 (floor; 2^-20 cm; clamped to HC_PROF_Q_MAX and counted)
+// and, with B > 0, one entry per layer in bin min(B - 1, (v_l B) / v_0) of the block's LDS histogram uint32 [L][B] -- the
+// layer's share of the member's total by integer division; a member with v_0 <= 0 adds one to `outside` instead.  The
+// members of a point share a few bins a layer, so the lanes are grouped by bin first (period_bin_add).  Only nonzero
+// words and bins go to the tables, with integer atomics.  Every member's accumulators are reset to 0.
+__global__ __launch_bounds__(PERIOD_THREADS) void uptake_reduce_kernel(
+    long long *uacc, const long long *solved, long long n_members, long long members_per_point, long long members_per_block,
+    long long period, long long n_period, int L, int B, long long *umom, long long *ucnt, unsigned long long *ovf_word,
+    int *hist, unsigned long long *outside_word)
+{
+    constexpr int K1 = HC_UPTAKE_MAX_LAYERS + 1;
+    extern __shared__ unsigned uptake_bins[];        // [L][B]
+    __shared__ long long part[PERIOD_THREADS / WAVE][K1][HC_PROF_WORDS];
+    __shared__ long long cnt_part[PERIOD_THREADS / WAVE];
+    __shared__ unsigned ovf_sum, outside_sum;
+    const int n_bins = L * B;
+    for (int b = threadIdx.x; b < n_bins; b += PERIOD_THREADS) uptake_bins[b] = 0;
+    if (threadIdx.x == 0) ovf_sum = 0, outside_sum = 0;
+    __syncthreads();
+    const long long point = blockIdx.y;
+    const long long end = (point + 1) * members_per_point;
+    const long long m0 = point * members_per_point + (long long)blockIdx.x * members_per_block;
+    const long long m1 = m0 + members_per_block < end ? m0 + members_per_block : end;
+    const int lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
+    const long long qmax = HC_PROF_Q_MAX;
+    long long words[K1][HC_PROF_WORDS] = {};
+    long long counted = 0;
+    unsigned ovf = 0, outside = 0;
+    // wave-uniform trip count: every lane of a wave runs the ballots of every round
+    for (long long k0 = m0 + (threadIdx.x - lane); k0 < m1; k0 += PERIOD_THREADS) {
+        const long long m = k0 + lane;
+        const bool live = m < m1;
+        long long v[K1];
+#pragma unroll
+        for (int k = 0; k < K1; k++) v[k] = (live && k <= L) ? uacc[(size_t)k * n_members + m] : 0;
+        int bin[HC_UPTAKE_MAX_LAYERS];
+#pragma unroll
+        for (int l = 0; l < HC_UPTAKE_MAX_LAYERS; l++) bin[l] = -1;
+        if (live && solved[m] != PERIOD_WTD_NONE) {
+            counted++;
+#pragma unroll
+            for (int k = 0; k < K1; k++) {
+                if (k <= L) {
+                    v[k] >>= 12;                     // floor(A / 4096)
+                    if (v[k] > qmax) v[k] = qmax, ovf++;
+                    if (v[k] < -qmax) v[k] = -qmax, ovf++;
+                    prof_add(words[k], v[k]);
+                }
+            }
+            if (B > 0) {
+                if (v[0] > 0) {
+#pragma unroll
+                    for (int l = 0; l < HC_UPTAKE_MAX_LAYERS; l++) {
+                        if (l < L) {
+                            const long long s = v[l + 1] < 0 ? 0 : (v[l + 1] * B) / v[0];
+                            bin[l] = l * B + (int)(s < B - 1 ? s : B - 1);
+                        }
+                    }
+                } else {
+                    outside++;
+                }
+            }
+        }
+        if (live) {
+#pragma unroll
+            for (int k = 0; k < K1; k++)
+                if (k <= L) uacc[(size_t)k * n_members + m] = 0;
+        }
+        if (B > 0) {
+#pragma unroll
+            for (int l = 0; l < HC_UPTAKE_MAX_LAYERS; l++)
+                if (l < L) period_bin_add(uptake_bins, bin[l], lane);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < K1; k++) {
+        if (k <= L) {
+#pragma unroll
+            for (int w = 0; w < HC_PROF_WORDS; w++) {
+                long long s = words[k][w];
+                for (int o = WAVE / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
+                if (lane == 0) part[wave][k][w] = s;
+            }
+        }
+    }
+    for (int o = WAVE / 2; o > 0; o >>= 1) counted += __shfl_xor(counted, o);
+    if (lane == 0) cnt_part[wave] = counted;
+    if (ovf) atomicAdd(&ovf_sum, ovf);
+    if (outside) atomicAdd(&outside_sum, outside);
+    __syncthreads();
+    const size_t slot = (size_t)point * n_period + period;
+    if ((int)threadIdx.x < (L + 1) * HC_PROF_WORDS) {
+        const int k = threadIdx.x / HC_PROF_WORDS, w = threadIdx.x % HC_PROF_WORDS;
+        long long sum = 0;
+#pragma unroll
+        for (int u = 0; u < PERIOD_THREADS / WAVE; u++) sum += part[u][k][w];
+        if (sum) atomicAdd(reinterpret_cast<unsigned long long *>(umom + (slot * (L + 1) + k) * HC_PROF_WORDS + w), (unsigned long long)sum);
+    }
+    if (B > 0) {
+        int *t = hist + slot * n_bins;
+        for (int b = threadIdx.x; b < n_bins; b += PERIOD_THREADS) {
+            const unsigned c = uptake_bins[b];
+            if (c) atomicAdd(t + b, (int)c);
+        }
+    }
+    if (threadIdx.x == 0) {
+        long long n = 0;
+#pragma unroll
+        for (int u = 0; u < PERIOD_THREADS / WAVE; u++) n += cnt_part[u];
+        if (n) atomicAdd(reinterpret_cast<unsigned long long *>(ucnt + slot), (unsigned long long)n);
+        if (ovf_sum) atomicAdd(ovf_word, (unsigned long long)ovf_sum);
+        if (B > 0 && outside_sum) atomicAdd(outside_word, (unsigned long long)outside_sum);
     }
 }
 
@@ -3705,6 +4070,73 @@ int ensure_period_acc(hc_handle *h)
     return h->n_members > 0 ? HC_OK : fail(HC_ERR_ARG, "period totals: no members yet (hc_set_members / hc_set_state)");
 }
 
+// the root-uptake tables (hc_set_root_uptake): int64 umom [P][n_period][L + 1][5], ucnt [P][n_period], uprof
+// [P][n_period][D - 1][2], ovf [1]; with bins the int32 share histograms [P][n_period][L][B] and the outside count (one
+// uint64 in two entries, 8-byte aligned behind a multiple of 32)
+struct UptLayout {
+    int K = 0;
+    int64_t ucnt = 0, uprof = 0, ovf = 0, words = 0, bins = 0;
+};
+UptLayout uptake_layout(const hc_handle *h)
+{
+    UptLayout U;
+    const int64_t slots = (int64_t)h->n_points * h->per_n;
+    U.K = h->upt_layers + 1;
+    U.ucnt = slots * U.K * HC_PROF_WORDS;
+    U.uprof = U.ucnt + slots;
+    U.ovf = U.uprof + slots * (h->p.dim_d - 1) * 2;
+    U.words = U.ovf + 1;
+    U.bins = slots * h->upt_layers * h->upt_bins;
+    return U;
+}
+void uptake_off(hc_handle *h)
+{
+    h->upt_layers = h->upt_bins = 0;
+    h->uacc.release(), h->uacc_alt.release(), h->upt.release(), h->uhist.release(), h->mid_tabs.release();
+    h->mid_dirty = true;
+}
+int ensure_uptake(hc_handle *h)
+{
+    if (h->upt_layers <= 0) return fail(HC_ERR_ARG, "root uptake is off (hc_set_root_uptake)");
+    if (h->per_n <= 0) return fail(HC_ERR_ARG, "root uptake needs the period totals (hc_set_period_totals)");
+    if (int rc = ensure_period(h)) return rc;
+    const int M = h->p.dim_d - 1;
+    for (int l = 0; l < h->upt_layers; l++) {
+        const int c0 = h->upt_range[l][0], c1 = h->upt_range[l][1];
+        if (c0 < 0 || c0 >= c1 || c1 > M)
+            return fail(HC_ERR_ARG, "root uptake: layer %d is [%d, %d), not a range of midpoint cells 0 <= lo < hi <= %d", l, c0,
+                        c1, M);
+    }
+    const UptLayout U = uptake_layout(h);
+    if (U.bins > HC_WTD_HIST_MAX_ENTRIES)
+        return fail(HC_ERR_ARG, "root uptake: %lld histogram entries exceed HC_WTD_HIST_MAX_ENTRIES", (long long)U.bins);
+    if (int rc = h->upt.ensure(h->n_points, h->n_rows, h->p.dim_d, U.words)) return rc;
+    if (h->upt_bins > 0)
+        if (int rc = h->uhist.ensure(h->n_points, h->n_rows, h->p.dim_d, U.bins + 2)) return rc;
+    if (h->n_members > 0)
+        if (int rc = h->uacc.ensure(h->n_members, U.K, 0, h->n_members * U.K)) return rc;
+    return HC_OK;
+}
+int ensure_uptake_hist(hc_handle *h)
+{
+    if (int rc = ensure_uptake(h)) return rc;
+    return h->upt_bins > 0 ? HC_OK : fail(HC_ERR_ARG, "root uptake has no histogram (hc_set_root_uptake with bins = 0)");
+}
+int ensure_uptake_acc(hc_handle *h)
+{
+    if (int rc = ensure_uptake(h)) return rc;
+    return h->n_members > 0 ? HC_OK : fail(HC_ERR_ARG, "root uptake: no members yet (hc_set_members / hc_set_state)");
+}
+// the points' midpoint tables on the device, [P][5][D - 1]
+int ensure_mid_tabs(hc_handle *h)
+{
+    if (!h->mid_dirty && h->mid_tabs.p) return HC_OK;
+    if (h->mid_tabs.ensure(h->mid_host.size())) return HC_ERR_DEVICE;
+    HIP_TRY(hipMemcpy(h->mid_tabs.p, h->mid_host.data(), h->mid_host.size() * 8, hipMemcpyHostToDevice));
+    h->mid_dirty = false;
+    return HC_OK;
+}
+
 // An assimilation table keyed by (points, rows, stride): `per_row` entries per point and analysis row (every stride-th
 // row), created on a fresh key as NaN with each slot's count 0 (`width` entries a slot; 0: all NaN)
 int ensure_da_table(hc_handle *h, AccTable<double> &t, int64_t stride, int64_t per_row, int width)
@@ -4208,6 +4640,7 @@ int hc_destroy(hc_handle *h)
     h->prof.release(); h->hist.release(); h->thist.release(); h->stor.release(); h->shist.release();
     h->cov.release(); h->cov_q.release();
     h->pacc.release(); h->pacc_alt.release(); h->pmom.release(); h->phist.release();
+    uptake_off(h);
     assimilation_off(h);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -4318,6 +4751,20 @@ static int build_point(hc_handle *h, const hc_column_params *p, const double *no
         (void)hipStreamSynchronize(h->stream);
         assimilation_off(h);
     }
+    if (first) {                 // a new column: the root uptake (hc_set_root_uptake) is off
+        if (h->upt_layers > 0) (void)hipStreamSynchronize(h->stream);
+        uptake_off(h);
+        h->mid_host.clear();
+    }
+    // the midpoint tables the root uptake reads, as received, and 1 / (por - wlt) as the slot tables have it
+    // (UPT_TAB_*: porosity, field capacity, wilting point, the reciprocal, root density)
+    h->mid_host.insert(h->mid_host.end(), mid_tabs, mid_tabs + (size_t)3 * M);
+    for (int i = 0; i < M; i++) {
+        const double d1 = mid_tabs[i] - mid_tabs[2 * M + i];                   // tree_roots.py:235-238
+        h->mid_host.push_back(1.0 / (d1 == 0.0 ? 1.0 : d1));
+    }
+    h->mid_host.insert(h->mid_host.end(), mid_tabs + (size_t)3 * M, mid_tabs + (size_t)4 * M);
+    h->mid_dirty = true;
     h->P_host.push_back(P);
     h->tab_host.insert(h->tab_host.end(), tab.begin(), tab.end());
     h->node_host.insert(h->node_host.end(), node_tabs, node_tabs + (size_t)3 * D);
@@ -4413,6 +4860,7 @@ int hc_set_forcing(hc_handle *h, int64_t n_rows, const double *precip, const dou
     HIP_TRY(hipMemcpy(h->draw_idx.p, draw.data(), T * 4, hipMemcpyHostToDevice));
     h->h_refresh.assign(refresh, refresh + T);
     h->h_wtd_obs.assign(wtd_obs, wtd_obs + T);
+    h->h_daylight.assign(daylight, daylight + T);
     h->n_rows = n_rows;
     h->moments.invalidate();     // (re)allocated and zeroed by the next call that needs the moment tables
     h->have_forcing = true;
@@ -4434,6 +4882,7 @@ int hc_set_forcing_row(hc_handle *h, int64_t row, double precip, double atm, uin
     HIP_TRY(hipMemcpy(h->refresh.p + row, &zero, 1, hipMemcpyHostToDevice));
     h->h_refresh[(size_t)row] = 0;
     h->h_wtd_obs[(size_t)row] = wtd_obs;
+    h->h_daylight[(size_t)row] = daylight;
     return HC_OK;
 }
 
@@ -4444,6 +4893,7 @@ int hc_set_members(hc_handle *h, int64_t n_members)
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
     assimilation_off(h);
+    uptake_off(h);               // the root uptake's accumulators are the members': off
     const size_t n = (size_t)n_members * h->p.dim_d;
     if (h->psi.ensure(n) || h->nscale.ensure((size_t)n_members)) return HC_ERR_DEVICE;
     hipLaunchKernelGGL(fill_d, dim3((unsigned)((n_members + 255) / 256)), dim3(256), 0, h->stream, h->nscale.p, 1.0,
@@ -4797,11 +5247,80 @@ int64_t period_of(const hc_handle *h, int64_t row)
     return it == h->per_end.end() ? -1 : (int64_t)(it - h->per_end.begin());
 }
 
+// The root uptake (hc_set_root_uptake) of the launch's daylight rows from their staged end states, added to the members'
+// accumulators and to the period's depth profile: layer_storage_kernel's slices (a wave reads whole rows: 32 members a
+// wave, 2048 blocks for a 262 144-member point; grid y capped as there).  A night row has no uptake and launches
+// nothing; a skipped row returns at the kernel's first line.  theta_out / u_out: the test hook's launch on the current
+// states (stage = psi) of row `row0`, night rows included.
+constexpr long long UPT_MEMBERS_PER_BLOCK = 128;
+size_t uptake_lds_bytes(const hc_handle *h, bool eval)
+{
+    int n_int = 0;
+    for (const ColumnDev &P : h->P_host) n_int = std::max(n_int, P.n_root_int);
+    const int n_model = eval ? h->p.dim_d - 1 : n_int + 1;
+    const size_t cells = (size_t)((n_model + PROF_TILE - 1) / PROF_TILE) * PROF_TILE;
+    return ((UPT_NTAB + PROF_WAVES) * cells + 2 * (size_t)(n_int + 1)) * sizeof(double);
+}
+int launch_root_uptake(hc_handle *h, const StepArgs &A, const double *stage, int64_t row0, int rows, double *theta_out,
+                       double *u_out)
+{
+    const bool eval = theta_out != nullptr;
+    const int64_t N = h->n_members, D = h->p.dim_d;
+    const long long mpp = N / h->n_points;
+    const dim3 grid(1, (unsigned)std::min((mpp + UPT_MEMBERS_PER_BLOCK - 1) / UPT_MEMBERS_PER_BLOCK, h->stor_grid_y),
+                    (unsigned)h->n_points);
+    UptLayers Ly{};
+    Ly.n = eval ? 0 : h->upt_layers;
+    for (int l = 0; l < Ly.n; l++) Ly.c0[l] = h->upt_range[l][0], Ly.c1[l] = h->upt_range[l][1];
+    const size_t lds = uptake_lds_bytes(h, eval);
+    if (eval) {
+        hipLaunchKernelGGL(root_uptake_kernel, grid, dim3(PROF_TILE * PROF_WAVES), lds, h->stream, A, h->mid_tabs.p,
+                           (int)h->use_special(), stage, h->wtd_obs.p, h->atm.p, h->daylight.p, (long long)row0, 0LL, 1LL,
+                           UPT_MEMBERS_PER_BLOCK, Ly, nullptr, nullptr, nullptr, theta_out, u_out);
+        HIP_TRY(hipGetLastError());
+        return HC_OK;
+    }
+    const int64_t p = period_of(h, row0);
+    if (p < 0) return HC_OK;
+    const UptLayout U = uptake_layout(h);
+    long long *t = h->upt.buf.p;
+    const int n = (int)std::min<int64_t>(rows, h->per_end[(size_t)p] - row0 + 1);
+    for (int r = 0; r < n; r++) {
+        const int64_t row = row0 + r;
+        if (!(h->h_daylight[(size_t)row] & 1) || h->h_wtd_obs[(size_t)row] < 0) continue;
+        hipLaunchKernelGGL(root_uptake_kernel, grid, dim3(PROF_TILE * PROF_WAVES), lds, h->stream, A, h->mid_tabs.p,
+                           (int)h->use_special(), stage + (size_t)r * N * D, h->wtd_obs.p, h->atm.p, h->daylight.p,
+                           (long long)row, (long long)p, (long long)h->per_n, UPT_MEMBERS_PER_BLOCK, Ly, h->uacc.buf.p,
+                           t + U.uprof, reinterpret_cast<unsigned long long *>(t + U.ovf), nullptr, nullptr);
+        HIP_TRY(hipGetLastError());
+    }
+    return HC_OK;
+}
+
+// the end of period p for the uptake: before period_reduce_kernel, whose `wtd_shallowest` plane says who is counted
+constexpr long long PERIOD_MEMBERS_PER_BLOCK = 1024;
+int launch_uptake_reduce(hc_handle *h, int64_t p)
+{
+    const int64_t N = h->n_members;
+    const long long mpp = N / h->n_points;
+    const UptLayout U = uptake_layout(h);
+    const int B = h->upt_bins, L = h->upt_layers;
+    long long *t = h->upt.buf.p;
+    int *hist = B > 0 ? h->uhist.buf.p : nullptr;
+    const dim3 grid((unsigned)((mpp + PERIOD_MEMBERS_PER_BLOCK - 1) / PERIOD_MEMBERS_PER_BLOCK), (unsigned)h->n_points);
+    hipLaunchKernelGGL(uptake_reduce_kernel, grid, dim3(PERIOD_THREADS), (size_t)L * B * sizeof(unsigned), h->stream,
+                       h->uacc.buf.p, h->pacc.buf.p + 2 * N, (long long)N, mpp, PERIOD_MEMBERS_PER_BLOCK, (long long)p,
+                       (long long)h->per_n, L, B, t, t + U.ucnt, reinterpret_cast<unsigned long long *>(t + U.ovf), hist,
+                       reinterpret_cast<unsigned long long *>(B > 0 ? hist + U.bins : nullptr));
+    HIP_TRY(hipGetLastError());
+    return HC_OK;
+}
+
 // The launch's rows [row0, row0 + rows) added to the members' accumulators (plan_chunk ended the launch on the period's
 // end row at the latest, so they lie in one period) and, when the launch ends on the end row, the period reduced over
 // the members of each point: slices of PERIOD_MEMBERS_PER_BLOCK members (four a thread) give a 262 144-member point
-// 256 blocks, one a CU
-constexpr long long PERIOD_MEMBERS_PER_BLOCK = 1024;
+// 256 blocks, one a CU.  The root uptake (hc_set_root_uptake), whose rows the caller has added already, is reduced first:
+// it counts the members this reduction is about to count and reset.
 int launch_period(hc_handle *h, int64_t row0, int rows)
 {
     const int64_t p = period_of(h, row0);
@@ -4819,6 +5338,8 @@ int launch_period(hc_handle *h, int64_t row0, int rows)
                        (long long)row0, n, Th, h->pacc.buf.p, ovf);
     HIP_TRY(hipGetLastError());
     if (row0 + rows - 1 < end_row) return HC_OK;
+    if (h->upt_layers > 0)
+        if (int rc = launch_uptake_reduce(h, p)) return rc;
     const long long mpp = N / h->n_points;
     const int B = h->per_bins, D = (int)h->p.dim_d;
     int *hist = B > 0 ? h->phist.buf.p : nullptr;
@@ -4962,13 +5483,15 @@ Chunk plan_chunk(const hc_handle *h, const hc_step_args *a, int64_t done, bool p
             c.rows = (int)std::min<int64_t>(c.rows, h->per_end[(size_t)p] - c.row0 + 1);
         c.rows = (int)std::min<int64_t>(c.rows, std::max<int64_t>(1, PROF_DIAG_BYTES / diag_row));
     }
-    if (!prof_on) return c;
+    // the root uptake (hc_set_root_uptake) reads every row's end state: staged as for a short profile stride
+    const bool upt_on = h->upt_layers > 0 && !a->spinup;
+    if (!prof_on && !upt_on) return c;
     const int64_t s = h->prof_stride, row_bytes = N * D * 8;
     c.rows = (int)std::min<int64_t>(c.rows, std::max<int64_t>(1, PROF_DIAG_BYTES / diag_row));
     const int64_t cap_rows = std::max<int64_t>(1, (PROF_STAGE_BYTES - (int64_t)c.rows * diag_row) / row_bytes);
     if (a->psi_rows_out) {
         c.stage_all = true;       // every row is staged for the caller already
-    } else if (s >= cap_rows) {
+    } else if (!upt_on && s >= cap_rows) {
         const int64_t next = (c.row0 + s - 1) / s * s;
         c.rows = (int)std::min<int64_t>(c.rows, next - c.row0 + 1);
         c.end_on_profile = (c.row0 + c.rows - 1) % s == 0;
@@ -5051,6 +5574,10 @@ int accumulate(hc_handle *h, const StepArgs &A, const hc_step_args *a, const Chu
     }
     if (hist_on)
         if (int rc = launch_hist(h, c.row0, c.rows)) return rc;
+    if (h->upt_layers > 0 && !a->spinup) {
+        if (!c.stage_all) return fail(HC_ERR_DEVICE, "root uptake: the launch's rows are not staged (internal error)");
+        if (int rc = launch_root_uptake(h, A, h->psi_rows.p, c.row0, c.rows, nullptr, nullptr)) return rc;
+    }
     if (h->per_n > 0 && !a->spinup)
         if (int rc = launch_period(h, c.row0, c.rows)) return rc;
     if (!prof_on) return HC_OK;
@@ -5452,6 +5979,16 @@ int assimilate(hc_handle *h, const Chunk &c)
             HIP_TRY(hipGetLastError());
             std::swap(h->pacc.buf, h->pacc_alt);
         }
+        if (h->upt_layers > 0) {
+            // ... and so do their root-uptake accumulators (hc_set_root_uptake)
+            const int K = uptake_layout(h).K;
+            if (h->uacc_alt.ensure((size_t)(N * K))) return HC_ERR_DEVICE;
+            const unsigned ublocks = (unsigned)std::min<size_t>(((size_t)N * K + 255) / 256, (size_t)h->n_cu * 64);
+            hipLaunchKernelGGL(period_gather_kernel, dim3(ublocks), dim3(256), 0, h->stream, h->filt_anc.p, h->uacc.buf.p,
+                               h->uacc_alt.p, (long long)N, K);
+            HIP_TRY(hipGetLastError());
+            std::swap(h->uacc.buf, h->uacc_alt);
+        }
     }
     if (s.ms > 0) {
         // the sensors' posterior over the resampled slots, theta[anc[k]]: theta is a function of the copied column
@@ -5777,6 +6314,7 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
     if (prof_on && h->cov_stride > 0 && (rc = ensure_cov(h))) return rc;
     const bool per_on = h->per_n > 0 && !a->spinup;       // period totals (hc_set_period_totals)
     if (per_on && (rc = ensure_period(h))) return rc;
+    if (per_on && h->upt_layers > 0 && ((rc = ensure_uptake(h)) || (rc = ensure_mid_tabs(h)))) return rc;
     // the particle filter (hc_set_filter): spin-up solves are never filtered
     if (a->spinup && h->filt_host())
         return fail(HC_ERR_ARG, "spin-up solves with the particle filter on in a Philox run: set the filter after the spin-up");
@@ -6296,6 +6834,12 @@ int hc_set_period_totals(hc_handle *h, int32_t n_periods, const int64_t *end_row
     if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
+    // the root uptake (hc_set_root_uptake) lives on these periods: other ends turn it off, the same ends re-create its
+    // tables and accumulators, zeroed, with the period totals'
+    const bool same_ends = n_periods > 0 && (size_t)n_periods == h->per_end.size() &&
+                           std::equal(h->per_end.begin(), h->per_end.end(), end_rows);
+    const int keep_layers = same_ends ? h->upt_layers : 0, keep_bins = h->upt_bins;      // (the ranges stay where they are)
+    uptake_off(h);
     period_off(h);               // the tables and the accumulators are re-created when on
     if (n_periods == 0) return HC_OK;
     if (n_periods < 0 || n_periods > HC_PERIOD_MAX_PERIODS)
@@ -6323,6 +6867,10 @@ int hc_set_period_totals(hc_handle *h, int32_t n_periods, const int64_t *end_row
     h->per_n = n_periods, h->per_nthr = n_thresholds, h->per_bins = n_bins;
     const int rc = ensure_period(h);         // (its refusals come before anything is allocated)
     if (rc != HC_OK) period_off(h);          // refused: off
+    if (rc == HC_OK && keep_layers > 0) {
+        h->upt_layers = keep_layers, h->upt_bins = keep_bins;
+        if (ensure_uptake(h) != HC_OK) uptake_off(h);
+    }
     return rc;
 }
 
@@ -6425,6 +6973,148 @@ int hc_get_period_totals_layout(hc_handle *h, int32_t *n_periods, int32_t *n_thr
     for (int q = 0; q < 2; q++) flux_max_log2[q] = h->per_fexp[q];
     if (end_rows)
         for (int64_t p = 0; p < std::min<int64_t>(n_end_rows, h->per_n); p++) end_rows[p] = h->per_end[(size_t)p];
+    return HC_OK;
+}
+
+int hc_set_root_uptake(hc_handle *h, int32_t n_layers, const int32_t *cell_lo, const int32_t *cell_hi, int32_t n_bins)
+{
+    if (!h || (n_layers > 0 && (!cell_lo || !cell_hi))) return fail(HC_ERR_ARG, "hc_set_root_uptake: bad argument");
+    if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    uptake_off(h);               // the tables and the accumulators are re-created when on
+    if (n_layers == 0) return HC_OK;
+    if (h->per_n <= 0) return fail(HC_ERR_ARG, "hc_set_root_uptake: the period totals are off (hc_set_period_totals comes first)");
+    if (n_layers < 0 || n_layers > HC_UPTAKE_MAX_LAYERS)
+        return fail(HC_ERR_ARG, "hc_set_root_uptake: %d layers (1 to %d; 0 = off)", (int)n_layers, HC_UPTAKE_MAX_LAYERS);
+    if (n_bins != 0 && (n_bins < 32 || n_bins > 1024 || (n_bins & (n_bins - 1))))
+        return fail(HC_ERR_ARG, "hc_set_root_uptake: %d bins (a power of two in 32 .. 1024; 0 = no histogram)", (int)n_bins);
+    if (h->fs_n > 0)
+        return fail(HC_ERR_ARG, "hc_set_root_uptake: a sharded particle filter is set (hc_set_filter_shard), and the routed "
+                                "columns do not carry the members' accumulators");
+    for (int l = 0; l < n_layers; l++) h->upt_range[l][0] = cell_lo[l], h->upt_range[l][1] = cell_hi[l];
+    h->upt_layers = n_layers, h->upt_bins = n_bins;
+    const int rc = ensure_uptake(h);         // (its refusals come before anything is allocated)
+    if (rc != HC_OK) uptake_off(h);          // refused: off
+    return rc;
+}
+
+int hc_get_root_uptake_words(hc_handle *h, int64_t *n_words)
+{
+    if (!h || !n_words) return fail(HC_ERR_ARG, "hc_get_root_uptake_words: bad argument");
+    if (int rc = ensure_uptake(h)) return rc;
+    *n_words = h->upt.n;
+    return HC_OK;
+}
+
+int hc_get_root_uptake(hc_handle *h, int64_t *table, int64_t n_words)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_get_root_uptake: bad argument");
+    return table_copy(h, h->upt, ensure_uptake, hipMemcpyDeviceToHost, table, n_words, "hc_get_root_uptake");
+}
+
+int hc_set_root_uptake_tables(hc_handle *h, const int64_t *table, int64_t n_words)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_set_root_uptake_tables: bad argument");
+    return table_copy(h, h->upt, ensure_uptake, hipMemcpyHostToDevice, const_cast<int64_t *>(table), n_words,
+                      "hc_set_root_uptake_tables");
+}
+
+int hc_export_root_uptake(hc_handle *h, void *device_dst, int64_t n_words)
+{
+    if (!h || !device_dst) return fail(HC_ERR_ARG, "hc_export_root_uptake: bad argument");
+    return table_copy(h, h->upt, ensure_uptake, hipMemcpyDeviceToDevice, device_dst, n_words, "hc_export_root_uptake");
+}
+
+int hc_get_root_uptake_hist(hc_handle *h, int32_t *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_get_root_uptake_hist: bad argument");
+    return table_copy(h, h->uhist, ensure_uptake_hist, hipMemcpyDeviceToHost, table, n_entries, "hc_get_root_uptake_hist");
+}
+
+int hc_set_root_uptake_hist_table(hc_handle *h, const int32_t *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_set_root_uptake_hist_table: bad argument");
+    return table_copy(h, h->uhist, ensure_uptake_hist, hipMemcpyHostToDevice, const_cast<int32_t *>(table), n_entries,
+                      "hc_set_root_uptake_hist_table");
+}
+
+int hc_export_root_uptake_hist(hc_handle *h, void *device_dst, int64_t n_entries)
+{
+    if (!h || !device_dst) return fail(HC_ERR_ARG, "hc_export_root_uptake_hist: bad argument");
+    return table_copy(h, h->uhist, ensure_uptake_hist, hipMemcpyDeviceToDevice, device_dst, n_entries,
+                      "hc_export_root_uptake_hist");
+}
+
+int hc_get_root_uptake_acc(hc_handle *h, int64_t *acc, int64_t n_words)
+{
+    if (!h || !acc) return fail(HC_ERR_ARG, "hc_get_root_uptake_acc: bad argument");
+    return table_copy(h, h->uacc, ensure_uptake_acc, hipMemcpyDeviceToHost, acc, n_words, "hc_get_root_uptake_acc");
+}
+
+int hc_set_root_uptake_acc(hc_handle *h, const int64_t *acc, int64_t n_words)
+{
+    if (!h || !acc) return fail(HC_ERR_ARG, "hc_set_root_uptake_acc: bad argument");
+    return table_copy(h, h->uacc, ensure_uptake_acc, hipMemcpyHostToDevice, const_cast<int64_t *>(acc), n_words,
+                      "hc_set_root_uptake_acc");
+}
+
+int hc_reset_root_uptake(hc_handle *h)
+{
+    if (!h) return fail(HC_ERR_ARG, "hc_reset_root_uptake: bad argument");
+    h->uhist.invalidate(), h->uacc.invalidate();
+    return table_reset(h, h->upt, ensure_uptake);
+}
+
+int hc_get_root_uptake_outside(hc_handle *h, uint64_t *count)
+{
+    if (!h || !count) return fail(HC_ERR_ARG, "hc_get_root_uptake_outside: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = ensure_uptake(h)) return rc;
+    *count = 0;
+    if (h->upt_bins == 0) return HC_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(count, h->uhist.buf.p + (h->uhist.n - 2), 8, hipMemcpyDeviceToHost));
+    return HC_OK;
+}
+
+int hc_get_root_uptake_overflow(hc_handle *h, uint64_t *count)
+{
+    if (!h || !count) return fail(HC_ERR_ARG, "hc_get_root_uptake_overflow: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = ensure_uptake(h)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(count, h->upt.buf.p + uptake_layout(h).ovf, 8, hipMemcpyDeviceToHost));
+    return HC_OK;
+}
+
+int hc_get_root_uptake_layout(hc_handle *h, int32_t *n_layers, int32_t *n_bins, int32_t *cell_lo, int32_t *cell_hi)
+{
+    if (!h || !n_layers || !n_bins || !cell_lo || !cell_hi) return fail(HC_ERR_ARG, "hc_get_root_uptake_layout: bad argument");
+    *n_layers = h->upt_layers, *n_bins = h->upt_bins;
+    for (int l = 0; l < HC_UPTAKE_MAX_LAYERS; l++) {
+        cell_lo[l] = l < h->upt_layers ? h->upt_range[l][0] : 0;
+        cell_hi[l] = l < h->upt_layers ? h->upt_range[l][1] : 0;
+    }
+    return HC_OK;
+}
+
+int hc_root_uptake_eval(hc_handle *h, int64_t row, double *theta_mid, double *u)
+{
+    if (!h || !theta_mid || !u) return fail(HC_ERR_ARG, "hc_root_uptake_eval: bad argument");
+    StepArgs A;
+    int rc = fill_args(h, A);
+    if (rc) return rc;
+    if (row < 0 || row >= h->n_rows) return fail(HC_ERR_ARG, "hc_root_uptake_eval: row %lld outside [0, %lld)", (long long)row,
+                                                 (long long)h->n_rows);
+    HIP_TRY(hipSetDevice(h->device));
+    if ((rc = ensure_mid_tabs(h))) return rc;
+    const size_t n = (size_t)h->n_members * (h->p.dim_d - 1);
+    if (h->scratch_d.ensure(2 * n)) return HC_ERR_DEVICE;
+    if ((rc = launch_root_uptake(h, A, h->psi.p, row, 1, h->scratch_d.p, h->scratch_d.p + n))) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(theta_mid, h->scratch_d.p, n * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(u, h->scratch_d.p + n, n * 8, hipMemcpyDeviceToHost));
     return HC_OK;
 }
 
@@ -6986,6 +7676,9 @@ int hc_set_filter_shard(hc_handle *h, int32_t n_shards, const int64_t *bounds, i
                                 "their own");
     if (h->per_n > 0)
         return fail(HC_ERR_ARG, "hc_set_filter_shard: period totals are set (hc_set_period_totals), and the routed columns do "
+                                "not carry the members' accumulators");
+    if (h->upt_layers > 0)
+        return fail(HC_ERR_ARG, "hc_set_filter_shard: the root uptake is set (hc_set_root_uptake), and the routed columns do "
                                 "not carry the members' accumulators");
     if (!device_buf || !gather || !route) return fail(HC_ERR_ARG, "hc_set_filter_shard: NULL buffer or callback");
     const int64_t need = filter_shard_layout(np, h->n_members, n_shards, h->p.dim_d).words;

@@ -17,6 +17,7 @@ from .stepper import (ASSIM_TABLES, ENKF_METHODS, EnsembleStepper, enkf_sm_summa
                       filter_window_settings, filter_window_summary, rejuvenation_discount,
                       flux_max_log2_of, layer_ranges, layer_storage_distribution, moments_to_mean_std, period_totals_distribution,
                       sensor_nodes, theta_distribution, wtd_distribution)
+from .stepper import layer_cells, root_uptake_distribution, root_uptake_profile, root_uptake_stats
 
 
 def pressure_head(cols, theta):
@@ -412,6 +413,47 @@ class _Run:
         return period_totals_distribution(hf, hw, levels, self.stepper.period_flux_max_log2, float(self.cols.z[0]),
                                           self.cols.dz)
 
+    def _start_uptake(self, uptake_layers_cm, uptake_bins):
+        on = uptake_layers_cm is not None and len(uptake_layers_cm) > 0
+        if not on and uptake_bins:
+            raise ValueError("uptake_bins needs uptake_layers_cm")
+        if on and self.period_ends is None:
+            raise ValueError("uptake_layers_cm needs period_ends: the uptake is totalled over the periods")
+        self.uptake_layers_cm = np.asarray(uptake_layers_cm, dtype=np.float64).reshape(-1, 2) if on else None
+        self.uptake_bins = int(uptake_bins or 0) if on else 0
+        self.uptake_cells = layer_cells(self.cols.z, self.uptake_layers_cm) if on else None
+        if on:
+            self.stepper.set_root_uptake(self.uptake_cells, self.uptake_bins)
+
+    def uptake_table(self):
+        """The raw int64 table of the root uptake (stepper.root_uptake_table_layout)."""
+        return self.stepper.root_uptake_table()
+
+    def uptake_hist(self):
+        """[n_period][L][B] int32 share histograms; a sweep: a leading [P] axis."""
+        h = self.stepper.root_uptake_hist()
+        return h.reshape(self._lead + h.shape[1:])
+
+    def uptake_stats(self, table=None):
+        """Mean and sigma over the members of every period's root-water uptake [cm], in total and per layer of
+        ``uptake_layers_cm``, [n_period] and [n_period][L] (a sweep: a leading [P] axis), the layers' shares of the mean
+        total, count and end_rows (stepper.root_uptake_stats); ``table``: e.g. the sum over ranks."""
+        t = self.uptake_table() if table is None else table
+        out = root_uptake_stats(t, self.stepper.P, self.period_ends, len(self.uptake_cells), self.cols.dim_d)
+        out["layers_cm"], out["cells"] = self.uptake_layers_cm.copy(), self.uptake_cells.copy()
+        return out
+
+    def uptake_distribution(self, levels=(0.05, 0.5, 0.95), hist=None):
+        """Quantiles over the members of each layer's share of a member's period total (stepper.root_uptake_distribution);
+        ``hist``: e.g. the sum over ranks.  Needs ``uptake_bins``; other levels need no rerun."""
+        return root_uptake_distribution(self.uptake_hist() if hist is None else hist, levels)
+
+    def uptake_profile(self, table=None):
+        """Every period's uptake per cm of depth at the midpoints, the mean over the members, [n_period][D - 1], and the
+        depths above which 50 % and 90 % of it lie (stepper.root_uptake_profile); ``table``: e.g. the sum over ranks."""
+        t = self.uptake_table() if table is None else table
+        return root_uptake_profile(t, self.stepper.P, self.period_ends, len(self.uptake_cells), self.cols.dim_d, self.cols.z)
+
     def storage_table(self):
         """The raw int64 moments table of the layer storage (stepper.layer_storage_table_layout)."""
         return self.stepper.layer_storage_table()
@@ -574,7 +616,7 @@ class EnsembleSimulation(_Run):
                  theta_hist_bins=0, storage_layers_cm=None, storage_bins=0, period_ends=None, period_thresholds_cm=(),
                  period_bins=0, period_flux_max_cm=(16.0, 4.0), filter_ess_floor=0.0, filter_window_offsets=(),
                  enkf_noise_field=None, filter_rejuvenation=0.0, noise_correlation=None,
-                 theta_cov_stride=0):
+                 theta_cov_stride=0, uptake_layers_cm=None, uptake_bins=0):
         corr = self._check_noise_correlation("EnsembleSimulation", noise_correlation, noise, filter_rejuvenation)
         if enkf_shard is not None and noise_field_settings(enkf_noise_field, 0.0) is not None:
             raise ValueError("enkf_shard and enkf_noise_field exclude each other: the exchanged partials cover psi only")
@@ -603,6 +645,7 @@ class EnsembleSimulation(_Run):
                            storage_bins, filter_ess_floor, filter_window_offsets, enkf_noise_field,
                            filter_rejuvenation=filter_rejuvenation, theta_cov_stride=theta_cov_stride)
         self._start_periods(period_ends, period_thresholds_cm, period_bins, period_flux_max_cm)
+        self._start_uptake(uptake_layers_cm, uptake_bins)
         self.enkf_shard = None
         if enkf_shard is not None:
             if not self.enkf_stride:
@@ -734,6 +777,15 @@ class EnsembleSimulation(_Run):
                 arrays["period_flux_max_cm"] = np.asarray(self.period_flux_max_cm, dtype=np.float64)
                 arrays["period_hist"] = self.stepper.period_totals_hist_raw()[:-2]
                 arrays["period_hist_outside"] = np.array(self.stepper.period_totals_outside(), dtype=np.uint64)
+        if self.uptake_cells is not None:
+            # ... and so do the root uptake's
+            arrays["uptake_layers_cm"] = self.uptake_layers_cm
+            arrays["uptake_bins"] = np.array(self.uptake_bins, dtype=np.int64)
+            arrays["uptake_table"] = self.stepper.root_uptake_table()
+            arrays["uptake_acc"] = self.stepper.root_uptake_acc()
+            if self.uptake_bins:
+                arrays["uptake_hist"] = self.stepper.root_uptake_hist_raw()[:-2]
+                arrays["uptake_hist_outside"] = np.array(self.stepper.root_uptake_outside(), dtype=np.uint64)
         if self.wtd_hist_stride:
             arrays["wtd_hist_stride"] = np.array(self.wtd_hist_stride, dtype=np.int64)
             arrays["wtd_hist"] = self.stepper.wtd_hist_table()
@@ -825,6 +877,10 @@ class EnsembleSimulation(_Run):
                        period_bins=int(data["period_bins"]))
             if int(data["period_bins"]):
                 fkw.update(period_flux_max_cm=tuple(np.asarray(data["period_flux_max_cm"], dtype=np.float64).reshape(-1)))
+        uptake = "uptake_layers_cm" in data
+        if uptake:
+            fkw.update(uptake_layers_cm=np.asarray(data["uptake_layers_cm"], dtype=np.float64).reshape(-1, 2),
+                       uptake_bins=int(data["uptake_bins"]))
         enkf = int(data["enkf_stride"]) if "enkf_stride" in data else 0
         if enkf:
             fkw.update(enkf_stride=enkf, enkf_sigma_cm=float(data["enkf_sigma_cm"]),
@@ -901,6 +957,11 @@ class EnsembleSimulation(_Run):
             if sim.period_bins:
                 hf, hw = np.split(np.asarray(data["period_hist"]).reshape(-1), [len(sim.period_ends) * 2 * sim.period_bins])
                 sim.stepper.set_period_totals_hists(hf, hw, int(data["period_hist_outside"]))
+        if uptake:
+            sim.stepper.set_root_uptake_table(np.asarray(data["uptake_table"], dtype=np.int64))
+            sim.stepper.set_root_uptake_acc(np.asarray(data["uptake_acc"], dtype=np.int64))
+            if sim.uptake_bins:
+                sim.stepper.set_root_uptake_hist(np.asarray(data["uptake_hist"]), int(data["uptake_hist_outside"]))
         if hist_stride:
             sim.stepper.set_wtd_hist_table(np.asarray(data["wtd_hist"]))
         sim.next_row = int(data["next_row"])
@@ -1000,7 +1061,7 @@ class SweepSimulation(_Run):
                  filter_soil_moisture=None, theta_hist_bins=0, storage_layers_cm=None, storage_bins=0, period_ends=None,
                  period_thresholds_cm=(), period_bins=0, period_flux_max_cm=(16.0, 4.0), filter_ess_floor=0.0,
                  filter_window_offsets=(), enkf_noise_field=None, filter_rejuvenation=0.0, noise_correlation=None,
-                 theta_cov_stride=0):
+                 theta_cov_stride=0, uptake_layers_cm=None, uptake_bins=0):
         corr = self._check_noise_correlation("SweepSimulation", noise_correlation, "philox", filter_rejuvenation)
         self.points = list(cols_list)
         self.P, self.n = len(self.points), int(n_members)
@@ -1035,6 +1096,7 @@ class SweepSimulation(_Run):
                            storage_bins, filter_ess_floor, filter_window_offsets, enkf_noise_field,
                            filter_rejuvenation=filter_rejuvenation, theta_cov_stride=theta_cov_stride)
         self._start_periods(period_ends, period_thresholds_cm, period_bins, period_flux_max_cm)
+        self._start_uptake(uptake_layers_cm, uptake_bins)
         self.next_row, self.kernel_ms, self.launches = 1, 0.0, 0
 
     def _spinup(self, flags):

@@ -81,6 +81,7 @@ class EnsembleStepper:
         self.theta_cov_stride = 0
         self.period_ends, self.period_threshold_nodes = np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int32)
         self.period_bins, self.period_flux_max_log2 = 0, (0, 0)
+        self.uptake_cells, self.uptake_bins = np.zeros((0, 2), dtype=np.int32), 0
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = 0, 0.0, 0
         self.filter_sm_nodes = None
         self.filter_ess_floor = 0.0
@@ -579,7 +580,10 @@ class EnsembleStepper:
         t32, f32 = np.ascontiguousarray(t, dtype=np.int32), np.ascontiguousarray(f, dtype=np.int32)
         self.period_ends, self.period_threshold_nodes = np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int32)
         self.period_bins, self.period_flux_max_log2 = 0, (0, 0)
-        L.check(self.lib.hc_set_period_totals(self.h, e.size, L.lptr(e), t32.size, L.iptr(t32), int(bins), L.iptr(f32)))
+        try:
+            L.check(self.lib.hc_set_period_totals(self.h, e.size, L.lptr(e), t32.size, L.iptr(t32), int(bins), L.iptr(f32)))
+        finally:
+            self._sync_root_uptake()     # other ends turn the root uptake off
         if e.size:
             self.period_ends, self.period_threshold_nodes = e, t32
             self.period_bins, self.period_flux_max_log2 = int(bins), ((int(f[0]), int(f[1])) if bins else (0, 0))
@@ -674,6 +678,116 @@ class EnsembleStepper:
         t = self.period_totals_table() if table is None else table
         return period_totals_stats(t, self.P, self.period_ends, len(self.period_threshold_nodes), float(self.cols.z[0]),
                                    float(self.params.dz), self.forcing.wtd_obs)
+
+    # -- root-water uptake by depth (include/hydrocol.h hc_set_root_uptake) ---------------------------------------------
+    def set_root_uptake(self, cells, bins=0):
+        """Accumulate per member, over the periods of :meth:`set_period_totals` (which comes first), the root-water
+        uptake of every solved daylight row in total and in the layers ``cells`` = [(lo, hi), ...] (ranges of midpoint
+        cells, see :func:`layer_cells`; at most 8), and per period the uptake at every midpoint; reduce the totals over
+        the members of each point at every end row: exact moments and, with ``bins`` (a power of two in 32 .. 1024),
+        histograms of each layer's share of a member's total.  No layers = off."""
+        r = np.asarray(cells, dtype=np.int64).reshape(-1, 2)
+        if r.size and np.abs(r).max() > INT32_MAX:
+            raise ValueError("uptake layers are ranges of midpoint cells")
+        lo, hi = (np.ascontiguousarray(r[:, k], dtype=np.int32) for k in (0, 1))
+        self.uptake_cells, self.uptake_bins = np.zeros((0, 2), dtype=np.int32), 0
+        L.check(self.lib.hc_set_root_uptake(self.h, r.shape[0], L.iptr(lo), L.iptr(hi), int(bins)))
+        if r.shape[0]:
+            self.uptake_cells, self.uptake_bins = r.astype(np.int32), int(bins)
+
+    def root_uptake_layout(self):
+        """(cells [L][2], bins) as the library holds them."""
+        n, b = C.c_int32(), C.c_int32()
+        lo, hi = np.zeros(UPTAKE_MAX_LAYERS, dtype=np.int32), np.zeros(UPTAKE_MAX_LAYERS, dtype=np.int32)
+        L.check(self.lib.hc_get_root_uptake_layout(self.h, C.byref(n), C.byref(b), L.iptr(lo), L.iptr(hi)))
+        return np.stack([lo[:n.value], hi[:n.value]], axis=1), int(b.value)
+
+    def _sync_root_uptake(self):
+        self.uptake_cells, self.uptake_bins = self.root_uptake_layout()
+
+    def root_uptake_words(self):
+        n = C.c_int64()
+        L.check(self.lib.hc_get_root_uptake_words(self.h, C.byref(n)))
+        return int(n.value)
+
+    def root_uptake_table(self):
+        """The raw int64 table (layout: :func:`root_uptake_table_layout`)."""
+        t = np.zeros(self.root_uptake_words(), dtype=np.int64)
+        L.check(self.lib.hc_get_root_uptake(self.h, L.lptr(t), t.size))
+        return t
+
+    def set_root_uptake_table(self, table):
+        t = np.ascontiguousarray(table, dtype=np.int64).reshape(-1)
+        L.check(self.lib.hc_set_root_uptake_tables(self.h, L.lptr(t), t.size))
+
+    def export_root_uptake(self, device_ptr):
+        """Copy the table device-to-device to ``device_ptr`` (``root_uptake_words()`` int64 on this device)."""
+        L.check(self.lib.hc_export_root_uptake(self.h, C.c_void_p(int(device_ptr)), self.root_uptake_words()))
+
+    def root_uptake_hist_entries(self):
+        return self.P * len(self.period_ends) * len(self.uptake_cells) * self.uptake_bins + 2
+
+    def root_uptake_hist_raw(self):
+        """The raw int32 share histograms with the outside count in their two last entries."""
+        t = np.zeros(self.root_uptake_hist_entries(), dtype=np.int32)
+        L.check(self.lib.hc_get_root_uptake_hist(self.h, L.iptr(t), t.size))
+        return t
+
+    def root_uptake_hist(self):
+        """[P][n_period][L][B] int32: members of each point per bin of the layer's share of their total."""
+        return self.root_uptake_hist_raw()[:-2].reshape(self.P, len(self.period_ends), len(self.uptake_cells), self.uptake_bins)
+
+    def set_root_uptake_hist(self, hist, outside=0):
+        h = np.ascontiguousarray(hist, dtype=np.int32).reshape(-1)
+        tail = np.array([int(outside) & 0xFFFFFFFF, int(outside) >> 32], dtype=np.uint32).view(np.int32)
+        t = np.ascontiguousarray(np.concatenate([h, tail]))
+        L.check(self.lib.hc_set_root_uptake_hist_table(self.h, L.iptr(t), t.size))
+
+    def export_root_uptake_hist(self, device_ptr):
+        L.check(self.lib.hc_export_root_uptake_hist(self.h, C.c_void_p(int(device_ptr)), self.root_uptake_hist_entries()))
+
+    def root_uptake_acc(self):
+        """The members' accumulators [L + 1][N] int64 as they stand (the running period's; 0 after an end row)."""
+        a = np.zeros((len(self.uptake_cells) + 1, self.N), dtype=np.int64)
+        L.check(self.lib.hc_get_root_uptake_acc(self.h, L.lptr(a), a.size))
+        return a
+
+    def set_root_uptake_acc(self, acc):
+        a = np.ascontiguousarray(acc, dtype=np.int64)
+        L.check(self.lib.hc_set_root_uptake_acc(self.h, L.lptr(a), a.size))
+
+    def reset_root_uptake(self):
+        L.check(self.lib.hc_reset_root_uptake(self.h))
+
+    def root_uptake_outside(self):
+        """Members with a zero period total, which no share histogram holds (0 without bins)."""
+        out = C.c_uint64()
+        L.check(self.lib.hc_get_root_uptake_outside(self.h, C.byref(out)))
+        return int(out.value)
+
+    def root_uptake_overflow(self):
+        out = C.c_uint64()
+        L.check(self.lib.hc_get_root_uptake_overflow(self.h, C.byref(out)))
+        return int(out.value)
+
+    def root_uptake_eval(self, row):
+        """(theta_mid, u), [N][D - 1] each: theta at the midpoints of the members' current states and the uptake the RHS
+        applies there on forcing row ``row``, from the device code the tables are built with (test hook)."""
+        th, u = np.zeros((self.N, self.D - 1)), np.zeros((self.N, self.D - 1))
+        L.check(self.lib.hc_root_uptake_eval(self.h, int(row), L.dptr(th), L.dptr(u)))
+        return th, u
+
+    def root_uptake_tables(self, point=0):
+        """The five midpoint tables [5][D - 1] of a point as the device holds them (:func:`root_uptake_mid_tables`)."""
+        return root_uptake_mid_tables(self.points[point])
+
+    def root_uptake_stats(self, table=None):
+        """The science arrays of ``root_uptake_table()`` (or of ``table``, e.g. summed over ranks):
+        :func:`root_uptake_stats`; with ``root_uptake_profile``'s arrays."""
+        t = self.root_uptake_table() if table is None else table
+        out = root_uptake_stats(t, self.P, self.period_ends, len(self.uptake_cells), self.D)
+        out.update(root_uptake_profile(t, self.P, self.period_ends, len(self.uptake_cells), self.D, self.cols.z))
+        return out
 
     # -- particle filter on the well's water table (include/hydrocol.h hc_set_filter) ----------------------------------
     def set_filter(self, stride, sigma_cm=None, seed=0):
@@ -2093,6 +2207,318 @@ def period_totals_distribution(hist_flux, hist_wtd, levels, flux_max_log2, z0, d
         out[name + "_quantile_cm"] = np.where(n[..., q, None] > 0, float(z0) + float(dz) * idx[..., q, :], np.nan)
     out["count"] = n[..., 0]
     return out
+
+
+# ---- root-water uptake by depth (include/hydrocol.h hc_set_root_uptake) -------------------------------------------------
+UPTAKE_MAX_LAYERS = 8
+UPTAKE_SCALE_PROFILE = 44                # u_i enters the depth profile as rint(u 2^44), in two 20-bit limbs
+UPTAKE_LIMB = 20
+
+
+def layer_cells(z, layers_cm):
+    """Midpoint-cell ranges [L][2] = (lo, hi) of the depth layers ``layers_cm`` = [(top, bottom), ...] in cm on the node
+    grid ``z`` (ascending, evenly spaced): layer l holds the midpoints i with top <= z_i + dz / 2 < bottom.  ValueError for
+    more than 8 layers, for top >= bottom and for a layer that holds no midpoint."""
+    z = np.asarray(z, dtype=np.float64).reshape(-1)
+    if z.size < 2:
+        raise ValueError("the node grid has at least two nodes")
+    zm = z[:-1] + 0.5 * (z[1] - z[0])
+    layers = [tuple(float(v) for v in np.asarray(lay, dtype=np.float64).reshape(-1)) for lay in layers_cm]
+    if not 1 <= len(layers) <= UPTAKE_MAX_LAYERS:
+        raise ValueError(f"1 to {UPTAKE_MAX_LAYERS} uptake layers, got {len(layers)}")
+    out = []
+    for lay in layers:
+        if len(lay) != 2 or not all(np.isfinite(lay)) or lay[0] >= lay[1]:
+            raise ValueError(f"an uptake layer is (top, bottom) in cm with top < bottom, got {lay!r}")
+        lo, hi = int(np.searchsorted(zm, lay[0], side="left")), int(np.searchsorted(zm, lay[1], side="left"))
+        if lo >= hi:
+            raise ValueError(f"uptake layer {lay!r} cm holds no midpoint of the column [{float(zm[0])!r}, {float(zm[-1])!r}] cm")
+        out.append((lo, hi))
+    return np.array(out, dtype=np.int32)
+
+
+def _check_cells(cells, M):
+    r = np.asarray(cells, dtype=np.int64).reshape(-1, 2)
+    if not 1 <= r.shape[0] <= UPTAKE_MAX_LAYERS or np.any(r[:, 0] < 0) or np.any(r[:, 0] >= r[:, 1]) or np.any(r[:, 1] > M):
+        raise ValueError(f"1 to {UPTAKE_MAX_LAYERS} cell ranges [lo, hi) with 0 <= lo < hi <= {M}, got {r.tolist()}")
+    return r
+
+
+def root_uptake_mid_tables(cols):
+    """[5][D - 1]: midpoint porosity, field capacity, wilting point, 1 / (por - wlt) (a zero denominator counts as 1) and
+    root density of a ``digest.ColumnTables``, as the device holds them."""
+    por, fc, wlt, root = (np.asarray(v, dtype=np.float64) for v in (cols.por_mid, cols.fc_mid, cols.wlt_mid, cols.root_mid))
+    d1 = por - wlt
+    return np.stack([por, fc, wlt, 1.0 / np.where(d1 == 0.0, 1.0, d1), root])
+
+
+def _uptake_sum(v):
+    """S of include/hydrocol.h over [N][64 R]: lane partials by ascending round from 0.0, then halving strides."""
+    p = np.zeros((v.shape[0], 64))
+    for r in range(v.shape[1] // 64):
+        p = p + v[:, 64 * r:64 * (r + 1)]
+    s = 32
+    while s:
+        p[:, :s] = p[:, :s] + p[:, s:2 * s]
+        s //= 2
+    return p[:, 0]
+
+
+def _uptake_scan(v):
+    """C of include/hydrocol.h over [N][64 R]: (c [N][64 R], the carry after the last round)."""
+    c, carry = np.zeros_like(v), np.zeros(v.shape[0])
+    for r in range(v.shape[1] // 64):
+        t = v[:, 64 * r:64 * (r + 1)].copy()
+        o = 1
+        while o < 64:
+            nxt = t.copy()
+            nxt[:, o:] = t[:, o:] + t[:, :-o]
+            t = nxt
+            o *= 2
+        c[:, 64 * r:64 * (r + 1)] = carry[:, None] + t
+        carry = carry + t[:, 63]
+    return c, carry
+
+
+def _uptake_pad(a, C):
+    a = np.asarray(a, dtype=np.float64)
+    out = np.zeros(a.shape[:-1] + (C,))
+    n = min(C, a.shape[-1])
+    out[..., :n] = a[..., :n]
+    return out
+
+
+def root_uptake_of(theta_mid, tables, atm, daylight, n_root_first, n_root_int, dz, flag_et=True):
+    """The device's u restated in NumPy, in its order (include/hydrocol.h hc_set_root_uptake): ``theta_mid`` [N][D - 1] (or
+    [D - 1]) at the midpoints, ``tables`` [5][D - 1] (:func:`root_uptake_mid_tables`), the row's ``atm`` and ``daylight``.
+    Returns u [N][D - 1] >= 0, the uptake the RHS applies (its sink is -u): cells 1 .. n_root_int normalised together, cell 0
+    on its own when ``n_root_first``; zeros at night or with ET off.  Equal to the device's bits from the same theta."""
+    th = np.asarray(theta_mid, dtype=np.float64)
+    th = th.reshape(-1, th.shape[-1])
+    N, M = th.shape
+    tabs = np.asarray(tables, dtype=np.float64).reshape(5, M)
+    n, dz, atm = int(n_root_int), np.float64(dz), np.float64(atm)
+    u = np.zeros((N, M))
+    if not (int(daylight) & 1) or not flag_et:
+        return u
+    with np.errstate(all="ignore"):
+        if n > 0:
+            C = (n + 1 + 63) // 64 * 64
+            t = _uptake_pad(th, C)
+            por, fc, wlt, invd1, root = _uptake_pad(tabs, C)
+            i = np.arange(C)
+            inn = (i >= 1) & (i <= n)
+            water_k = _uptake_sum(np.where(inn, t - wlt, 0.0)) * dz
+            c, carry = _uptake_scan(np.where(inn, t, 0.0))
+            total = carry * dz
+            total = np.where(total == 0.0, 1.0, total)
+            g = np.where(np.all(~inn | (t > fc), axis=1), 0.1, 1.0)
+            a1 = np.maximum(t * invd1, (c * dz) / total[:, None])
+            rho = np.where(inn & (t > fc), np.abs(a1 * g[:, None]), 0.0)
+            tot = _uptake_sum(rho) * dz
+            tot = np.where(tot == 0.0, 1.0, tot)
+            x = (rho / tot[:, None]) * root
+            tot_x = _uptake_sum(x) * dz
+            big = tot_x > 1.0
+            xb = x / np.where(big, tot_x, 1.0)[:, None]
+            x = np.where(big[:, None], xb, x)
+            tot_x = np.where(big, _uptake_sum(xb) * dz, tot_x)
+            ok = (water_k > 0.0) & (tot_x > 0.0)
+            tr = np.where(ok, np.minimum(atm, water_k) / np.where(ok, tot_x, 1.0), 0.0)
+            ui = np.where((ok & (tr != 0.0))[:, None] & inn, tr[:, None] * x, 0.0)
+            u[:, :min(C, M)] = ui[:, :min(C, M)]
+        if int(n_root_first) > 0:
+            por, fc, wlt, invd1, root = tabs[:, 0]
+            t0 = th[:, 0]
+            water_k = (t0 - wlt) * dz
+            local = t0 * dz
+            total = np.where(local == 0.0, 1.0, local)
+            a1 = np.maximum(t0 * invd1, local / total)
+            rho = np.where(t0 > fc, np.abs(a1 * 0.1), 0.0)
+            tot = rho * dz
+            tot = np.where(tot == 0.0, 1.0, tot)
+            x0 = (rho / tot) * root
+            tot_x = x0 * dz
+            big = tot_x > 1.0
+            x0 = np.where(big, x0 / np.where(big, tot_x, 1.0), x0)
+            tot_x = np.where(big, x0 * dz, tot_x)
+            ok = (water_k > 0.0) & (tot_x > 0.0)
+            u[:, 0] = np.where(ok, (np.minimum(atm, water_k) / np.where(ok, tot_x, 1.0)) * x0, 0.0)
+    return u
+
+
+def root_uptake_layer_totals(u, cells, n_root_int, dz):
+    """U [N][L + 1] in cm per row from u [N][D - 1]: plane 0 every cell, plane l the cells [lo_l, hi_l), each dz times the
+    sum over the cells 0 .. n_root_int in the device's order (lane partials by ascending round, halving strides)."""
+    u = np.asarray(u, dtype=np.float64)
+    u = u.reshape(-1, u.shape[-1])
+    r = _check_cells(cells, u.shape[1])
+    C = (int(n_root_int) + 1 + 63) // 64 * 64
+    i = np.arange(C)
+    v = np.where(i <= int(n_root_int), _uptake_pad(u, C), 0.0)
+    planes = [_uptake_sum(v)] + [_uptake_sum(np.where((i >= lo) & (i < hi), v, 0.0)) for lo, hi in r]
+    return np.float64(dz) * np.stack(planes, axis=1)
+
+
+def root_uptake_table_layout(P, n_period, L, D):
+    """{part: (offset, shape)} of the int64 table: umom [P][n_period][L + 1][5], ucnt [P][n_period], uprof
+    [P][n_period][D - 1][2], ovf [1]."""
+    out, off = {}, 0
+    for name, shape in (("umom", (P, n_period, L + 1, PROF_WORDS)), ("ucnt", (P, n_period)),
+                        ("uprof", (P, n_period, D - 1, 2)), ("ovf", (1,))):
+        out[name] = (off, shape)
+        off += int(np.prod(shape))
+    out["words"] = (off, ())
+    return out
+
+
+def split_root_uptake_table(table, P, n_period, L, D):
+    """Views of the parts of a flat table (see :func:`root_uptake_table_layout`)."""
+    t = np.asarray(table, dtype=np.int64).reshape(-1)
+    lay = root_uptake_table_layout(P, n_period, L, D)
+    if t.size != lay["words"][0]:
+        raise ValueError(f"root-uptake table of {t.size} words, the layout has {lay['words'][0]}")
+    return {k: t[o:o + int(np.prod(sh))].reshape(sh) for k, (o, sh) in lay.items() if k != "words"}
+
+
+def root_uptake_tables_of(u_rows, wtd_obs, ends, cells, n_root_int, dz, bins=0, ancestors=None, row_begin=1, acc=None,
+                          solved=False, daylight=None):
+    """The device's root-uptake tables of one point restated in NumPy integers.  ``u_rows`` [R][N][D - 1] is the uptake at
+    the end states of forcing rows row_begin ... row_begin + R - 1 (:func:`root_uptake_of`; zeros on a night row),
+    ``wtd_obs`` [T] the forcing's (a skipped row adds nothing), ``daylight`` [T] if given drops the night rows as the
+    device does.  ``ancestors`` {row: anc [N]}: the particle filter's resampling after that row.  ``acc`` [L + 1][N] and
+    ``solved``: the accumulators to start from and whether the running period has had a solved row (default: reset).
+    Returns ``acc`` as they stand after the last row, ``solved``, ``acc_at_end`` [n_period][L + 1][N], ``table`` (flat
+    int64: umom [1][n_period][L + 1][5], ucnt, uprof, ovf), ``hist`` [n_period][L][bins] int32 (None without bins),
+    ``outside`` and ``overflow``.  The device's tables, bit for bit."""
+    u_rows = np.asarray(u_rows, dtype=np.float64)
+    R, N, M = u_rows.shape
+    e = _check_period_ends(ends)
+    r = _check_cells(cells, M)
+    bins, n = int(bins), int(n_root_int)
+    if bins and bins not in STORAGE_BINS:
+        raise ValueError("share histograms have a power of two in 32 .. 1024 bins")
+    L_, n_period = r.shape[0], e.size
+    acc = np.zeros((L_ + 1, N), dtype=np.int64) if acc is None else np.array(acc, dtype=np.int64).reshape(L_ + 1, N)
+    acc_at_end = np.zeros((n_period, L_ + 1, N), dtype=np.int64)
+    umom = np.zeros((1, n_period, L_ + 1, PROF_WORDS), dtype=np.int64)
+    ucnt = np.zeros((1, n_period), dtype=np.int64)
+    uprof = np.zeros((1, n_period, M, 2), dtype=np.int64)
+    hist = np.zeros((n_period, L_, bins), dtype=np.int64) if bins else None
+    ovf = outside = 0
+    solved = bool(solved)
+    for k in range(R):
+        row = int(row_begin) + k
+        p = int(np.searchsorted(e, row, side="left"))
+        if p >= n_period:
+            break
+        if wtd_obs[row] >= 0:
+            solved = True
+            if daylight is None or (int(daylight[row]) & 1):
+                q, bad = profile_quantise(root_uptake_layer_totals(u_rows[k], r, n, dz), PROF_SCALE_FLUX)
+                acc += q.T
+                qi, bad_i = profile_quantise(u_rows[k][:, :n + 1], UPTAKE_SCALE_PROFILE)
+                neg = qi < 0
+                ovf += bad + bad_i + int(neg.sum())
+                qi = np.where(neg, 0, qi)
+                uprof[0, p, :n + 1, 0] += (qi & ((1 << UPTAKE_LIMB) - 1)).sum(axis=0)
+                uprof[0, p, :n + 1, 1] += (qi >> UPTAKE_LIMB).sum(axis=0)
+        if row == e[p]:
+            acc_at_end[p] = acc
+            if solved:
+                v = acc >> PERIOD_FLUX_SHIFT                      # floor(A / 4096): an arithmetic shift
+                ovf += int((np.abs(v) > PROF_Q_MAX).sum())
+                v = np.clip(v, -PROF_Q_MAX, PROF_Q_MAX)
+                umom[0, p] = profile_words_of(v).astype(object).sum(axis=1).astype(np.int64)
+                ucnt[0, p] = N
+                if bins:
+                    has = v[0] > 0
+                    outside += int((~has).sum())
+                    for l in range(L_):
+                        share = np.minimum(bins - 1, (np.maximum(v[l + 1][has], 0) * bins) // v[0][has])
+                        np.add.at(hist[p, l], share, 1)
+            acc = np.zeros_like(acc)
+            solved = False
+        if ancestors is not None and row in ancestors:
+            acc = acc[:, np.asarray(ancestors[row], dtype=np.int64)]
+    table = np.concatenate([umom.reshape(-1), ucnt.reshape(-1), uprof.reshape(-1), np.array([ovf], dtype=np.int64)])
+    return {"acc": acc, "solved": solved, "acc_at_end": acc_at_end, "table": table, "overflow": ovf, "outside": outside,
+            "hist": hist.astype(np.int32) if bins else None}
+
+
+def root_uptake_stats(table, P, ends, L, D):
+    """The science arrays of a root-uptake table, formed as :func:`limbs_to_mean_std` forms them (exact integers, rounded
+    once): ``total_mean_cm`` / ``total_std_cm`` [P][n_period] (the members' uptake over the period, every cell),
+    ``layer_mean_cm`` / ``layer_std_cm`` [P][n_period][L], ``share_of_mean`` [P][n_period][L] (layer mean over total mean;
+    NaN where the total is 0), ``count`` [P][n_period]; ``end_rows`` and ``overflow``.  NaN where nobody was counted.  The
+    leading [P] axis is dropped for a single point."""
+    e = _check_period_ends(ends)
+    parts = split_root_uptake_table(table, P, e.size, int(L), int(D))
+    cnt, w = parts["ucnt"], parts["umom"]
+    mean, std = limbs_to_mean_std(cnt[..., None], w, PERIOD_SCALE_TOTAL)
+    out = {"total_mean_cm": mean[..., 0], "total_std_cm": std[..., 0], "layer_mean_cm": mean[..., 1:],
+           "layer_std_cm": std[..., 1:], "count": cnt.copy()}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["share_of_mean"] = np.where(mean[..., :1] > 0, mean[..., 1:] / mean[..., :1], np.nan)
+    if P == 1:
+        out = {k: v[0] for k, v in out.items()}
+    out["end_rows"] = e.copy()
+    out["overflow"] = int(parts["ovf"][0])
+    return out
+
+
+def root_uptake_profile(table, P, ends, L, D, z, fractions=(0.5, 0.9)):
+    """The depth profile of a root-uptake table: ``profile`` [P][n_period][D - 1], the period's uptake per cm of depth as
+    the mean over the members counted (the two limbs recombined with Python integers, divided once; NaN where nobody was
+    counted), ``depth_cm`` [D - 1] the midpoints, and ``depth_quantile_cm`` [P][n_period][len(fractions)]: the depth of
+    the bottom of the first cell at which the cumulative profile reaches that fraction of the period's uptake (NaN when
+    there was none).  The leading [P] axis is dropped for a single point."""
+    e = _check_period_ends(ends)
+    parts = split_root_uptake_table(table, P, e.size, int(L), int(D))
+    z = np.asarray(z, dtype=np.float64).reshape(-1)
+    dz = z[1] - z[0]
+    lim = parts["uprof"].astype(object)
+    s = lim[..., 0] + lim[..., 1] * (1 << UPTAKE_LIMB)                        # [P][n_period][M] exact
+    cnt = parts["ucnt"]
+    no = np.where(cnt > 0, cnt, 1).astype(object)[..., None]
+    prof = np.asarray(s / no, dtype=np.float64) * 2.0 ** -UPTAKE_SCALE_PROFILE
+    prof = np.where(cnt[..., None] > 0, prof, np.nan)
+    cum = np.cumsum(s, axis=-1)                                              # Python integers: exact
+    tot = cum[..., -1]
+    fr = np.asarray(fractions, dtype=np.float64).reshape(-1)
+    dq = np.full(cnt.shape + (fr.size,), np.nan)
+    for idx in np.ndindex(*cnt.shape):
+        if int(tot[idx]) > 0:
+            c = np.asarray(cum[idx] / int(tot[idx]), dtype=np.float64)
+            for j, f in enumerate(fr):
+                dq[idx + (j,)] = z[int(np.argmax(c >= f))] + dz
+    out = {"profile": prof, "depth_quantile_cm": dq}
+    if P == 1:
+        out = {k: v[0] for k, v in out.items()}
+    out["depth_cm"] = z[:-1] + 0.5 * dz
+    return out
+
+
+def root_uptake_distribution(hist, levels):
+    """Quantiles of each layer's share of a member's period total from the histograms ``hist`` [..., n_period, L, B], in
+    NumPy integers: level p is the first bin b whose cumulative count reaches k = max(1, ceil(n p)) in fp64 -- the rank of
+    :func:`theta_distribution`, numpy.quantile(..., method="inverted_cdf") on the bin index -- reported as the bin centre
+    (b + 0.5) / B.  ``share_quantile`` [..., n_period, Lv, L] (NaN where nobody was binned), ``count`` [..., n_period]
+    and ``levels``."""
+    h = np.asarray(hist)
+    if h.ndim < 3:
+        raise ValueError(f"share histograms must be [..., n_period, L, B], got {h.shape}")
+    B = h.shape[-1]
+    if B not in STORAGE_BINS:
+        raise ValueError(f"share histograms have a power of two in 32 .. 1024 bins, not {B}")
+    if h.size and h.min() < 0:
+        raise ValueError("histogram counts must be >= 0")
+    lv = np.asarray(levels, dtype=np.float64).reshape(-1)
+    if lv.size > WTD_MAX_LEVELS or not np.all((lv >= 0.0) & (lv <= 1.0)):
+        raise ValueError(f"at most {WTD_MAX_LEVELS} quantile levels, each in [0, 1]: got {lv.tolist()}")
+    idx, n = _rank_bins(h, lv)                                            # [..., n_period, L, Lv]
+    q = np.where(n[..., None] > 0, (idx + 0.5) / B, np.nan)
+    return {"levels": lv, "share_quantile": np.swapaxes(q, -1, -2), "count": n[..., 0]}
 
 
 # ---- particle filter on the host (include/hydrocol.h hc_set_filter) ----------------------------------------------------

@@ -579,6 +579,83 @@ int hc_get_period_totals_overflow(hc_handle *h, uint64_t *count);   /* the ovf s
 int hc_get_period_totals_layout(hc_handle *h, int32_t *n_periods, int32_t *n_thresholds, int32_t *n_bins,
                                 int32_t *threshold_nodes, int32_t *flux_max_log2, int64_t *end_rows, int64_t n_end_rows);
 
+/* Root-water uptake by depth: from which layer the trees take their water in each period of hc_set_period_totals, per
+ * member first (the rate is zero at night: a sampled row says nothing), then as exact integer moments, share histograms
+ * and a depth profile over the members.  The sink depends on theta at the midpoints, the root and porosity tables and the
+ * row's atm / daylight alone, so it is evaluated after the fact from the end state of every solved daylight row: a
+ * launch stages its rows' end states (as a short profile stride does, within the same ~4 GiB) and a kernel behind it reads
+ * them.  The step kernels are the same with the feature on or off.
+ *   quantity, for a member's psi [D] after the solve of forcing row r (normal mode, flag_et on, daylight), M = D - 1:
+ *     y_i = 0.5 (psi_i + psi_{i+1}), theta_i = the cell model's theta at y_i with the midpoint porosity (no noise term),
+ *     u_i >= 0 the uptake the reference's RHS applies at that state (its sink is -u_i): cells 1 .. n_root_int from the
+ *     interior call, normalised together; cell 0 from the first-midpoint call, normalised on its own, when n_root_first
+ *     = 1; zero elsewhere, on a night row, with flag_et off.  With R = cells 1 .. n = n_root_int, in fp64 without
+ *     contraction, every division a division:
+ *       water_k = dz S(theta_i - wlt_i); water_k <= 0: all zero.  Otherwise
+ *       c_i = C(theta)_i, total = dz C(theta)_n' (0 -> 1), a1_i = max(theta_i invd1_i, (dz c_i) / total),
+ *       a2_i = theta_i > fc_i; g = 0.1 when a2_i holds on all of R, else 1; rho_i = a2_i ? |a1_i g| : 0,
+ *       tot = dz S(rho) (0 -> 1), x_i = (rho_i / tot) root_i, tot_x = dz S(x);
+ *       tot_x > 1: x_i = x_i / tot_x, tot_x = dz S(x);  tot_x > 0: u_i = (min(atm, water_k) / tot_x) x_i, else zero.
+ *     The first-midpoint call is the same with R = {0} (one cell: no sums, c_0 = theta_0, g = 0.1).
+ *     invd1 = 1 / (por - wlt) (0 -> 1) is formed once on the host.
+ *   order of the sums (fixed by n_root_int alone; cell i sits in round i / 64 at lane i % 64, cells outside R add 0.0):
+ *     S(v): lane j's partial p_j = the values of its cells by ascending round, from 0.0; then for s = 32, 16 .. 1:
+ *       p_j += p_{j+s} (j < s); S = p_0.
+ *     C(v): per round the inclusive scan over the lanes by doubling offsets -- for o = 1, 2 .. 32: t_j += t_{j-o}
+ *       (j >= o), all lanes at once -- and c_i = carry + t_j, where carry = the sum, by ascending round from 0.0, of the
+ *       earlier rounds' t_63.  C(v)_n' = the carry after the last round that holds a cell of R.
+ *   layers: L <= HC_UPTAKE_MAX_LAYERS ranges [lo_l, hi_l) of midpoint cells, 0 <= lo < hi <= M; they may overlap or lie
+ *     below the roots.  U_0 = dz S'(u over every cell), U_l = dz S'(u over the layer's cells), S' = S over the cells
+ *     0 .. n_root_int (cell 0 included).
+ *   accumulators (int64 [L + 1][N], member m of plane l at l N + m): the sum over the period's solved daylight rows of
+ *     q = rint(U_l 2^HC_PROF_SCALE_FLUX), |q| <= HC_PROF_Q_MAX (a clamped or NaN value adds one to ovf).
+ *   depth profile: q_i = rint(u_i 2^HC_UPTAKE_SCALE_PROFILE) of every member and solved daylight row of period p, clamped
+ *     to HC_PROF_Q_MAX (counted in ovf; so is a negative q_i, which adds nothing), added as two 20-bit limbs
+ *     q_i & (2^20 - 1) and q_i >> 20 to uprof [P][n_period][M][2]: 2^22 members x 2^20 rows x 2^20 stays below 2^62.
+ *   At the end of a period, before the period totals' own reduction and from the members it counts (those with a solved
+ *   row in the period), per point, v_l = A_l >> 12 = floor(A_l / 4096) (units of 2^-20 cm, clamped to |v| <=
+ *   HC_PROF_Q_MAX and counted in ovf):
+ *   tables (int64), in this order:
+ *     umom  [P][n_period][L + 1][5]  word 0 the sum of v_l, words 1..4 the 20-bit limbs of the sum of v_l^2
+ *     ucnt  [P][n_period]            the members counted
+ *     uprof [P][n_period][M][2]
+ *     ovf   [1]
+ *     P n_period (5 (L + 1) + 1 + 2 M) + 1 words.
+ *   histogram (int32; n_bins = 0: none): [P][n_period][L][B], B a power of two in 32 .. 1024: a counted member adds one
+ *     per layer to bin min(B - 1, (v_l B) / v_0) -- the layer's share of its total, by integer division -- and a member
+ *     with v_0 <= 0 adds one to `outside` instead, one uint64 in two more entries (low word first): P n_period L B + 2.
+ *   After the reduction the accumulators are reset to 0.  On an assimilation row the reduction runs before the resampling
+ *   or the analysis; the particle filter's resampling copies an ancestor's accumulators with its state, EnKF members
+ *   persist.  Integer adds only beyond the member: the tables are the same bits at any launch length, member split, point
+ *   order and number of handles summed.
+ * hc_set_root_uptake: n_layers 0 = off (default); otherwise (re)creates the tables zeroed and the accumulators reset.
+ * HC_ERR_ARG (and off) while the period totals are off, for more than HC_UPTAKE_MAX_LAYERS layers, an empty or
+ * out-of-column range, any other bin count, and while a sharded particle filter is set (hc_set_filter_shard, which in
+ * turn refuses while this is set).  hc_set_period_totals with other end rows, hc_set_members and hc_set_column turn it
+ * off; hc_set_period_totals with the same end rows re-creates it zeroed.  get / set / export take the size in words
+ * (hc_get_root_uptake_words; (L + 1) N for the accumulators) or entries and fail on any other; the histogram calls fail
+ * when there is none.  hc_get_root_uptake_layout fills cell_lo / cell_hi ([HC_UPTAKE_MAX_LAYERS]).  With the feature off
+ * nothing is launched, staged or allocated for it and no launch is cut.
+ * hc_root_uptake_eval (test hook): theta_mid and u, [N][M] each, of the members' CURRENT states on forcing row `row`
+ * (its atm and daylight; a night row gives u = 0), computed by the same device code; needs no hc_set_root_uptake. */
+#define HC_UPTAKE_MAX_LAYERS 8
+#define HC_UPTAKE_SCALE_PROFILE 44    /* u [1 / row]: 2^-44 steps, u < 2^-4 */
+int hc_set_root_uptake(hc_handle *h, int32_t n_layers, const int32_t *cell_lo, const int32_t *cell_hi, int32_t n_bins);
+int hc_get_root_uptake_words(hc_handle *h, int64_t *n_words);
+int hc_get_root_uptake(hc_handle *h, int64_t *table, int64_t n_words);
+int hc_set_root_uptake_tables(hc_handle *h, const int64_t *table, int64_t n_words);    /* checkpoint / resume, rank sums */
+int hc_export_root_uptake(hc_handle *h, void *device_dst, int64_t n_words);            /* as hc_export_profile_stats */
+int hc_get_root_uptake_hist(hc_handle *h, int32_t *table, int64_t n_entries);
+int hc_set_root_uptake_hist_table(hc_handle *h, const int32_t *table, int64_t n_entries);
+int hc_export_root_uptake_hist(hc_handle *h, void *device_dst, int64_t n_entries);
+int hc_get_root_uptake_acc(hc_handle *h, int64_t *acc, int64_t n_words);               /* [L + 1][N], for checkpoints */
+int hc_set_root_uptake_acc(hc_handle *h, const int64_t *acc, int64_t n_words);
+int hc_reset_root_uptake(hc_handle *h);
+int hc_get_root_uptake_outside(hc_handle *h, uint64_t *count);     /* 0 without a histogram */
+int hc_get_root_uptake_overflow(hc_handle *h, uint64_t *count);    /* the ovf slot */
+int hc_get_root_uptake_layout(hc_handle *h, int32_t *n_layers, int32_t *n_bins, int32_t *cell_lo, int32_t *cell_hi);
+int hc_root_uptake_eval(hc_handle *h, int64_t row, double *theta_mid, double *u);
+
 /* Particle filter on the well's water table (bootstrap filter, systematic resampling in exact integers).
  *   Assimilation rows: r >= 1, r % stride == 0 and wtd_obs[r] >= 0 (wtd_obs as it stands when hc_step_rows reaches the row:
  *   hc_set_forcing_row before the row's step sets or removes its observation).  Slot j <-> row j stride,
