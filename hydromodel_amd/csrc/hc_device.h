@@ -22,18 +22,39 @@ constexpr int WAVE = 64;
 // T_RDELTA (round 5): the refined reciprocal of delta = por - theta_res, the divisor of the effective saturation -- a constant
 // of the cell that every evaluation otherwise recomputes (v_rcp_f64 + two Newton steps: 5 of the ~94 VALU instructions of a
 // cell, one of them a quarter-rate one).  Filled on the DEVICE (fill_rdelta in hydrocol.hip: the same instruction sequence,
-// the same bits), never by the host.  It is the LAST table: the kernels that do not read it stage the first NTAB - 1 only.
+// the same bits), never by the host.  It and T_KSAT are the LAST tables: a kernel stages the ones before the first it does not read.
 // Read where it pays (rdelta_table below): up to 5 cells per lane on one wave per member, +2.1 ... 2.5 % at D = 300 and +1.5 % at
 // 241; at 6 cells per lane the LDS it takes from the factorisation costs more than it saves (-5 %), the split column is as
 // short of LDS.  -DHC_RDELTA_TABLE=0: nobody reads it (A/B builds).
 #ifndef HC_RDELTA_TABLE
 #define HC_RDELTA_TABLE 1
 #endif
-enum { T_POR = 0, T_FC, T_WLT, T_ROOT, T_LOGM, T_INVM2, T_NOISEC, T_VALID, T_INVD1, T_RDELTA, NTAB };
+// T_KSAT (round 6): K of the cell when it is saturated -- exp_mid(log m), or sat_soil in a cell of no layer -- which depends on
+// neither psi nor the noise.  Filled on the device like T_RDELTA (fill_ksat in hc_inst.hip: the cell model's own statements on a
+// saturated cell, compiled with the step kernel's flags, so the bits the full evaluation returns there).  Read by the packed cell
+// model of the 5-cells-per-lane default-exponent kernel (HC_MODEL_PACK, rhs_eval) and staged by that kernel alone; the LAST table.
+#ifndef HC_MODEL_PACK
+#define HC_MODEL_PACK 1
+#endif
+// A/B builds of the packed cell model (LAB_NOTES.md "The packed cell model"; the defaults are what measured best):
+// HC_PACK_BATCH = 1: its two cells as two batches of one instead of one batch of two (-3.8 %); HC_PACK_NOISE_ATTEMPT = 0: the
+// noise packed at every evaluation instead of once per attempt by the caller, who hands it over in Comm<1>::rnd_pk -- two
+// more registers live across the attempt, six swaps fewer per evaluation (-2.1 %).
+#ifndef HC_PACK_BATCH
+#define HC_PACK_BATCH 2
+#endif
+#ifndef HC_PACK_NOISE_ATTEMPT
+#define HC_PACK_NOISE_ATTEMPT 1
+#endif
+enum { T_POR = 0, T_FC, T_WLT, T_ROOT, T_LOGM, T_INVM2, T_NOISEC, T_VALID, T_INVD1, T_RDELTA, T_KSAT, NTAB };
 // `slots` = table row stride = 64 x cells per lane x waves per member
 // (the generic-exponent cell model, twice the working set, LOSES 12 % with the table at 5 cells per lane: default exponents only)
 __host__ __device__ constexpr bool rdelta_table(int slots, bool special = true) { return HC_RDELTA_TABLE && special && slots <= 64 * 5; }
-__host__ __device__ constexpr int ntab_lds(int slots, bool special = true) { return rdelta_table(slots, special) ? (int)NTAB : (int)NTAB - 1; }
+__host__ __device__ constexpr bool ksat_table(int slots, bool special = true) { return HC_MODEL_PACK && rdelta_table(slots, special) && slots == 64 * 5; }
+__host__ __device__ constexpr int ntab_lds(int slots, bool special = true)
+{
+    return ksat_table(slots, special) ? (int)NTAB : rdelta_table(slots, special) ? (int)NTAB - 1 : (int)NTAB - 2;
+}
 // round 5: masks as factors in the ET sums, the lateral-flow total only when it is asked for (+0.5 ... 2.3 %, same bits).  In
 // the two-waves-per-SIMD kernels only (compiled with -ffp-contract=on: source-determined bits); the one-wave kernels are
 // compiled with hipcc's default contraction, where ANY change of the code's shape may move a fusion decision and with it
@@ -61,7 +82,8 @@ struct ColumnDev {
     // repaired PREDICT mode (richards_pde.py:312-351; an extension, the reference raises TypeError at :327-330):
     // low_lim = dim_d - (sat_cells - 1) of the interior call (k = D - 2 cells) as an int, 0 when not positive;
     // predict_first = 1 when the single-cell first-midpoint call has low_lim >= 1 (sat_cells <= 1)
-    int flag_predict, predict_low, predict_first, pad_;   // read only by the kernels built with PREDICT = true
+    int flag_predict, predict_low, predict_first;   // read only by the kernels built with PREDICT = true
+    int flag_pack;      // the packed cell model may be taken (rhs_eval; HYDROCOL_MODEL_PACK=0 clears it)
 };
 
 struct RowDev {
@@ -110,6 +132,45 @@ __device__ __forceinline__ double dpp_z(double v)
     lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROWMASK, 0xf, true);
     hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROWMASK, 0xf, true);
     return __hiloint2double(hi, lo);
+}
+
+// gfx950 row swaps of a double (a row = 16 lanes): v_permlane16_swap exchanges the ODD rows of `a` with the EVEN rows of `b`
+// (a.row1 <-> b.row0, a.row3 <-> b.row2), v_permlane32_swap rows 2, 3 of `a` with rows 0, 1 of `b`.  One VALU instruction
+// per 32-bit half, no LDS.
+#if defined(__gfx950__)
+__device__ __forceinline__ void swap16_d(double &a, double &b)
+{
+    const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
+    const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
+    a = __hiloint2double((int)hi[0], (int)lo[0]);
+    b = __hiloint2double((int)hi[1], (int)lo[1]);
+}
+__device__ __forceinline__ void swap32_d(double &a, double &b)
+{
+    const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
+    const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
+    a = __hiloint2double((int)hi[0], (int)lo[0]);
+    b = __hiloint2double((int)hi[1], (int)lo[1]);
+}
+#else    // (the host pass and other targets only parse this)
+__device__ __forceinline__ void swap16_d(double &, double &) {}
+__device__ __forceinline__ void swap32_d(double &, double &) {}
+#endif
+// Row 0 of four per-lane values side by side: row r of the result holds row 0 of x_r.  The other three registers of the
+// exchange come out as  b = [x0.r1, x1.r1, x0.r3, x1.r3],  c = [x0.r2, x1.r2, x2.r2, x3.r2],  d = [x2.r1, x3.r1, x2.r3, x3.r3];
+// unpack_row0 is the inverse: given the packed row 0 and b, c, d it returns x0 .. x3 whole.
+__device__ __forceinline__ double pack_row0(double x0, double x1, double x2, double x3)
+{
+    swap16_d(x0, x1);
+    swap16_d(x2, x3);
+    swap32_d(x0, x2);
+    return x0;
+}
+__device__ __forceinline__ void unpack_row0(double &x0, double &x1, double &x2, double &x3)   // in: packed, b, c, d
+{
+    swap32_d(x0, x2);
+    swap16_d(x0, x1);
+    swap16_d(x2, x3);
 }
 
 // wave-wide sum, result uniform (no LDS traffic: 6 DPP steps + readlane)
@@ -334,6 +395,10 @@ template <>
 struct Comm<1> {
     static constexpr int H = 1;
     int half;                  // always 0
+#if HC_PACK_NOISE_ATTEMPT
+    double rnd_pk;             // rhs_eval's packed noise (pack_row0 of rnd[0..3]), formed once per attempt by the caller; set and
+                               // read by the kernels with the packed cell model only
+#endif
     static constexpr bool dead = false;
     __device__ __forceinline__ double sum(double v) const { return wave_sum(v); }
     __device__ __forceinline__ void sum2(double &a, double &b) const { wave_sum2(a, b); }
@@ -597,12 +662,15 @@ __device__ __forceinline__ void model_cell(const ColumnDev &P, double psi, doubl
 template <int N, int SLOTS, bool DIET = false>
 __device__ __forceinline__ void model_cells_special(const ColumnDev &P, const double *tab, int slot0,
                                                     const double *psi, const double *rnd, double *theta, double *K,
-                                                    double *C, double *kbo, double *pfac)
+                                                    double *C, double *kbo, double *pfac, const int *at = nullptr)
 {
-    // tab + slot0 addresses cell 0 of the batch; cell c is WAVE slots further.  Each table is read where it
+    // tab + slot0 addresses cell 0 of the batch; cell c is WAVE slots further -- or, with `at`, cell c sits at slot at[c]
+    // (the packed batch of rhs_eval).  Each table is read where it
     // is first needed, not at the top: four more live vectors would push caller state out of the VGPR file.
+    int so[N];
+    HC_V(so[c] = at ? at[c] : slot0 + c * WAVE)
     double por[N], invm2[N], logm[N], noisec[N];
-    HC_V(por[c] = tab[T_POR * SLOTS + slot0 + c * WAVE])
+    HC_V(por[c] = tab[T_POR * SLOTS + so[c]])
     double delta[N], ap[N], a[N], b[N], d[N], e[N], g[N], h[N], s[N], Lt[N], f[N], z[N], w[N], t1[N], t2[N], dk[N];
     bool sat[N], lo[N];
     int ex[N];
@@ -620,10 +688,10 @@ __device__ __forceinline__ void model_cells_special(const ColumnDev &P, const do
     HC_V(a[c] = fma(delta[c], pfac[c], P.theta_res))
     HC_V(theta[c] = sat[c] ? por[c] : a[c])
     // s = (theta - theta_res) / delta   (the next table read is issued here, a division ahead of its use)
-    HC_V(invm2[c] = tab[T_INVM2 * SLOTS + slot0 + c * WAVE])
+    HC_V(invm2[c] = tab[T_INVM2 * SLOTS + so[c]])
     HC_V(a[c] = theta[c] - P.theta_res)
     if constexpr (rdelta_table(SLOTS)) {
-        HC_V(b[c] = tab[T_RDELTA * SLOTS + slot0 + c * WAVE])
+        HC_V(b[c] = tab[T_RDELTA * SLOTS + so[c]])
     } else {
         HC_V(b[c] = __builtin_amdgcn_rcp(delta[c]))
         HC_V(d[c] = fma(-delta[c], b[c], 1.0))
@@ -676,8 +744,8 @@ __device__ __forceinline__ void model_cells_special(const ColumnDev &P, const do
     HC_V(b[c] = (h[c] - b[c]) - f[c])
     HC_V(Lt[c] = dk[c] * 6.93147180369123816490e-01 - b[c])
     // sig = sqrt_pos(Lt)
-    HC_V(logm[c] = tab[T_LOGM * SLOTS + slot0 + c * WAVE])
-    HC_V(noisec[c] = tab[T_NOISEC * SLOTS + slot0 + c * WAVE])
+    HC_V(logm[c] = tab[T_LOGM * SLOTS + so[c]])
+    HC_V(noisec[c] = tab[T_NOISEC * SLOTS + so[c]])
     HC_V(a[c] = __builtin_amdgcn_rsq(Lt[c]))
     HC_V(g[c] = Lt[c] * a[c])
     HC_V(h[c] = 0.5 * a[c])
@@ -957,7 +1025,7 @@ __device__ __forceinline__ int deepest_true(const bool (&pred)[CPL])
 #endif
 #endif
 // Sub-regions (ids 32..63: entries counted, cycles stay with the enclosing region): 33-37 change_D at order 1-5, 41-45
-// accept_update, 49-53 predictor, 56 ET interior call, 57 its water_k > 0 block, 58 the tot_x > 1 renormalisation,
+// accept_update, 49-53 predictor, 54 the packed cell model (its share of region 24's entries), 56 ET interior call, 57 its water_k > 0 block, 58 the tot_x > 1 renormalisation,
 // 59 ET first-midpoint call, 60 lateral-flow sink, 61 hydraulic lift, 62 FD-Jacobian step sizes, 63 group scatter
 
 // ---------------------------------------------------------------- RHS of the method of lines
@@ -995,6 +1063,7 @@ __device__ __forceinline__ void rhs_eval(const ColumnDev &P, const RowDev &R, co
     constexpr int H = CommT::H;
     constexpr bool DIET = ONE_BALLOT && HC_RHS_DIET;           // (ONE_BALLOT = "a two-waves-per-SIMD kernel": see HC_RHS_DIET)
     constexpr bool MDIET = ONE_BALLOT && HC_MODEL_DIET;
+    constexpr bool PACK = ONE_BALLOT && SPECIAL && CPL == 5 && H == 1 && HC_MODEL_PACK;
     constexpr int SLOTS = WAVE * CPL * H;                      // table row stride
     const int hb = H == 2 ? comm.half * (WAVE * CPL) : 0;      // index of this wave's first node
     const bool last_half = H == 1 || comm.half == H - 1;
@@ -1034,7 +1103,61 @@ __device__ __forceinline__ void rhs_eval(const ColumnDev &P, const RowDev &R, co
             }
         }
         HC_RSTAMP(24);
-        if (SPECIAL) {
+        // The packed cell model (round 6; the two-waves-per-SIMD kernel of 5 cells per lane, default exponents).  With the water
+        // table above node 80 every unsaturated cell sits in lanes 0..15, and a saturated cell's outputs are table constants
+        // (theta = por, C = epsilon, K = T_KSAT).  So: row 0 (16 lanes) of slots 0..3 side by side in ONE register by row swaps,
+        // slot 4 as it is (its row 0 is the fifth cell of those lanes, lane 63 holds the top-node cell), the model on these TWO
+        // cells instead of five, and the results swapped back against the constants of rows 1..3 -- read from the tables at
+        // the permuted slots pack_row0 documents, so that the inverse exchange returns slots 0..3 whole, without a select.
+        // One wave-uniform branch per evaluation; the same statements per cell, so the same bits.
+        bool full = true;
+        if constexpr (PACK) {
+            bool un = false;
+#pragma unroll
+            for (int c = 0; c < CPL - 1; c++) un = int(un) | int(!(ym[c] >= P.psi_sat));
+            un = int(un) | (int(!(ym[CPL - 1] >= P.psi_sat)) & int(lane != WAVE - 1));     // (not the top-node cell)
+            const unsigned long long um = __ballot(un);
+            if (P.flag_pack && !(um & ~0xFFFFull)) {
+                HC_RSUB(54);
+                full = false;
+                const int r = lane >> 4, i = lane & 15, ro = 16 * (r | 1) + i;
+                const int at[2] = {r * WAVE + i, (CPL - 1) * WAVE + lane};
+                const int sb = (r & 1) * WAVE + ro, sc = r * WAVE + 32 + i, sd = (2 + (r & 1)) * WAVE + ro;
+                const double pp[2] = {pack_row0(ym[0], ym[1], ym[2], ym[3]), ym[CPL - 1]};
+#if HC_PACK_NOISE_ATTEMPT
+                const double pr[2] = {comm.rnd_pk, rnd[CPL - 1]};
+#else
+                const double pr[2] = {pack_row0(rnd[0], rnd[1], rnd[2], rnd[3]), rnd[CPL - 1]};
+#endif
+                double pth[2], pK[2], pC[2], pkb[2], ppf[2];
+                th[1] = tab[T_POR * SLOTS + sb];
+                th[2] = tab[T_POR * SLOTS + sc];
+                th[3] = tab[T_POR * SLOTS + sd];
+                Kc[1] = tab[T_KSAT * SLOTS + sb];
+                Kc[2] = tab[T_KSAT * SLOTS + sc];
+                Kc[3] = tab[T_KSAT * SLOTS + sd];
+                if constexpr (HC_PACK_BATCH == 2) {
+                    model_cells_special<2, SLOTS, MDIET>(P, tab, 0, pp, pr, pth, pK, pC, pkb, ppf, at);
+                } else {
+                    model_cells_special<1, SLOTS, MDIET>(P, tab, 0, pp, pr, pth, pK, pC, pkb, ppf, at);
+                    model_cells_special<1, SLOTS, MDIET>(P, tab, 0, pp + 1, pr + 1, pth + 1, pK + 1, pC + 1, pkb + 1, ppf + 1, at + 1);
+                }
+                th[0] = pth[0];
+                Kc[0] = pK[0];
+                Cc[0] = pC[0];
+                Cc[1] = Cc[2] = Cc[3] = P.epsilon;
+                unpack_row0(th[0], th[1], th[2], th[3]);
+                unpack_row0(Kc[0], Kc[1], Kc[2], Kc[3]);
+                unpack_row0(Cc[0], Cc[1], Cc[2], Cc[3]);
+                th[CPL - 1] = pth[1];
+                Kc[CPL - 1] = pK[1];
+                Cc[CPL - 1] = pC[1];
+                kbv[CPL - 1] = pkb[1];      // (read at the top-node cell only)
+                pfv[CPL - 1] = ppf[1];
+            }
+        }
+        if (!full) {
+        } else if (SPECIAL) {
             // batches of HC_MODEL_BATCH cells: enough independent chains to hide the fp64 latency, few
             // enough to keep the working set in VGPRs
             constexpr int B = HC_MODEL_BATCH < CPL ? HC_MODEL_BATCH : CPL;

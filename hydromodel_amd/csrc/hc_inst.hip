@@ -224,6 +224,9 @@ __global__ __launch_bounds__(WPB *WAVE, 1) void rhs_kernel(const StepArgs A, lon
         idx = (i < D - 1) ? idx : 0;
         rnd[c] = tab[T_NOISEC * SLOTS + c * WAVE + lane] * nz[(idx % CPL) * WAVE + idx / CPL];
     }
+#if HC_PACK_NOISE_ATTEMPT
+    if constexpr (CPL == 5 && SPECIAL && STEP) comm.rnd_pk = pack_row0(rnd[0], rnd[1], rnd[2], rnd[3]);     // (as the step kernel's attempt does)
+#endif
 #ifdef HC_PROFILE
     // diagnostic build: repeat the evaluation (loop-carried through y) to time the RHS alone
     for (long long rep = 1; rep < A.n_rows; rep++) {
@@ -303,6 +306,28 @@ hipError_t launch_rhs_step_part<HC_INST_CPL, HC_INST_SPECIAL != 0>(const LaunchC
     constexpr bool S = HC_INST_SPECIAL != 0;
     return rhs_step<HC_INST_CPL, S, two_of(HC_INST_CPL, 1, S)>(cfg, A, row, dydt, aux, diag);
 }
+#if HC_INST_CPL == 5 && HC_INST_SPECIAL != 0
+static_assert(KSAT_CPL == HC_INST_CPL, "T_KSAT is filled by the unit whose step kernel reads it");
+// T_KSAT of every point: K of each cell at psi = psi_sat without noise, by the cell model as the step kernel of this unit
+// compiles it (this unit has the step kernel's flags: the same statements, the same contraction, the same bits)
+__global__ void fill_ksat_kernel(double *tab, const ColumnDev *Pp)
+{
+    constexpr int SLOTS = WAVE * KSAT_CPL;
+    double *t = tab + (size_t)blockIdx.x * NTAB * SLOTS;
+    const ColumnDev P = Pp[blockIdx.x];
+    for (int k = threadIdx.x; k < SLOTS; k += blockDim.x) {
+        const double psi[1] = {P.psi_sat}, rnd[1] = {0.0};
+        double th[1], K[1], C[1], kb[1], pf[1];
+        model_cells_special<1, SLOTS, two_of(KSAT_CPL, 1, true) && HC_MODEL_DIET>(P, t, k, psi, rnd, th, K, C, kb, pf);
+        t[(size_t)T_KSAT * SLOTS + k] = K[0];
+    }
+}
+hipError_t launch_fill_ksat(hipStream_t stream, double *tab, const ColumnDev *P, int n_points)
+{
+    hipLaunchKernelGGL(fill_ksat_kernel, dim3((unsigned)n_points), dim3(64), 0, stream, tab, P);
+    return hipGetLastError();
+}
+#endif
 #else
 template <>
 hipError_t launch_step_part<HC_INST_CPL, HC_INST_SPECIAL != 0>(const LaunchCfg &cfg, const StepArgs &A)

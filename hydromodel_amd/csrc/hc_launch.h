@@ -50,6 +50,10 @@ template <int CPL> inline hipError_t launch_rhs_cpl(const LaunchCfg &cfg, const 
 {
     return cfg.special ? launch_rhs_part<CPL, true>(cfg, A, row, dydt, aux, diag) : launch_rhs_part<CPL, false>(cfg, A, row, dydt, aux, diag);
 }
+// T_KSAT of tab[n_points][NTAB][64 KSAT_CPL] (hc_device.h): defined next to the RHS hook of the one unit that reads it, the
+// -DHC_INST_RHS_STEP unit of 5 cells per lane and default exponents, because the table must hold that unit's arithmetic
+constexpr int KSAT_CPL = 5;
+hipError_t launch_fill_ksat(hipStream_t stream, double *tab, const ColumnDev *P, int n_points);
 // split column: two waves per member, PAIR_CPL nodes per lane each, D in (64 PAIR_CPL, 128 PAIR_CPL]  (hc_inst.hip with
 // -DHC_INST_PAIR)
 constexpr int PAIR_CPL = 5;

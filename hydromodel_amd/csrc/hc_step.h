@@ -1396,6 +1396,10 @@ __global__ __launch_bounds__(WPB * WAVE, WPB / 4) void step_kernel(const StepArg
                     }
                     rnd[c] = tabw[T_NOISEC * TSLOTS + c * WAVE + lane] * z;
                 }
+#if HC_PACK_NOISE_ATTEMPT
+                // (the packed cell model's noise, rhs_eval: once per attempt, not at each of its ~19 evaluations)
+                if constexpr (HALVES == 1 && CPL == 5 && SPECIAL && TWO) comm.rnd_pk = pack_row0(rnd[0], rnd[1], rnd[2], rnd[3]);
+#endif
                 // ================= one BDF integration over [t0, tf] =================
                 double ycur[CPL], f[CPL], yp[CPL], psiv[CPL], scl[CPL] /* 1/scale */, dd[CPL];
                 double jl[CPL], jd[CPL], ju[CPL], hj[CPL];

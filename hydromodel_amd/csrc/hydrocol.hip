@@ -187,7 +187,10 @@ struct hc_handle {
     // (round 5: the split column runs on the TWO layout, four pairs per CU -- 125 k column-days/s at D = 513 ... 640 against
     //  96 k of the one-wave kernel of 9 cells per lane at D = 541 -- so it is the default from 513 nodes on)
     bool use_pair() const { return pair_ok && !no_split && (force_split || cpl >= 9); }
-    int chunk_members = 0;       // HYDROCOL_CHUNK_MEMBERS (0: derived from the member count)
+    // HYDROCOL_MODEL_PACK=0: the 5-cells-per-lane step kernel never takes its packed cell model (ColumnDev::flag_pack; A/B,
+    // cross-checks: the same binary, the same bits)
+    bool model_pack = true;
+    int chunk_members = 0;      // HYDROCOL_CHUNK_MEMBERS (0: derived from the member count)
     DevBuf<double> tab, node_tabs, precip, atm, psi, base, nscale, fresh, psi_rows, scratch_d, diag;
     DevBuf<double> wave_spill;   // per-wave vectors of deep columns that do not fit in LDS (hc_step.h WaveVecs)
     DevBuf<int> spin_iters;
@@ -4470,6 +4473,10 @@ int fill_args(hc_handle *h, StepArgs &A)
             hipLaunchKernelGGL(fill_rdelta, dim3((unsigned)NP), dim3(256), 0, h->stream, h->tab.p, h->Pdev.p, S1);
             if (h->pair_ok)
                 hipLaunchKernelGGL(fill_rdelta, dim3((unsigned)NP), dim3(256), 0, h->stream, h->tab_pair.p, h->Pdev.p, 2 * WAVE * PAIR_CPL);
+#if (HC_CPL_MASK >> 5) & 1
+            if (h->cpl == KSAT_CPL)      // ... and so is a saturated cell's K (T_KSAT; it reads T_RDELTA)
+                HIP_TRY(launch_fill_ksat(h->stream, h->tab.p, h->Pdev.p, NP));
+#endif
             HIP_TRY(hipStreamSynchronize(h->stream));
         }
         h->points_dirty = false;
@@ -4608,6 +4615,7 @@ int hc_create(int device_ordinal, hc_handle **out)
         h->no_split = atoi(sc) == 0;
         h->force_split = atoi(sc) == 1;
     }
+    if (const char *mp = getenv("HYDROCOL_MODEL_PACK")) h->model_pack = atoi(mp) != 0;
     if (const char *sv = getenv("HYDROCOL_SCIPY_152")) h->scipy_152 = atoi(sv) != 0;     // (the whole product at once: CLI, Simulation)
     if (const char *mi = getenv("HYDROCOL_DEBUG_MAX_ITER"))    // test hook: forces abandoned attempts
         if (atoi(mi) > 0) h->max_phase_iterations = atoi(mi);
@@ -4683,6 +4691,7 @@ static int build_point(hc_handle *h, const hc_column_params *p, const double *no
     P.flag_predict = p->flag_predict ? 1 : 0;
     P.predict_low = std::min(D - 2, std::max(0, (D - 2) - (p->sat_cells - 1)));
     P.predict_first = (1 - (p->sat_cells - 1)) >= 1 ? 1 : 0;
+    P.flag_pack = h->model_pack ? 1 : 0;
 
     const int M = D - 1;
     // Slot tables for `halves` waves per member with `cpl` nodes per lane: node / midpoint i sits with wide lane

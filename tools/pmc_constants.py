@@ -17,6 +17,13 @@ keeps the step-kernel rows as profiles/<tag>_pmc_<key>_<pass>.csv, and writes th
 
 keyed by the kernel hash in <dir>/library_hash.txt (hc_version() of the library the passes ran on).  Also writes
 profiles/<tag>_pmc_calib.txt: every calibration kernel's counters against its known bytes.
+
+    python tools/pmc_constants.py <dir> --tag r06 --only 300/special
+
+takes fresh passes for the named kernels only: the calibration and every other kernel's record are kept from the committed
+profiles/pmc_constants.json under the new hash.  That is right only when the other kernels' instruction streams are what
+they were when their passes ran -- compare the disassembly of both builds first and keep the comparison with the
+profiles (profiles/r06_isa_vs_parent.txt is the one of round 6).
 """
 import argparse
 import csv
@@ -95,12 +102,23 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("dir")
     ap.add_argument("--tag", default="r05")
+    ap.add_argument("--only", action="append", default=[], metavar="KEY",
+                    help="fresh passes for this kernel only (repeatable); calibration and the other records are kept")
     a = ap.parse_args()
     prof = os.path.join(R, "profiles")
     khash = open(os.path.join(a.dir, "library_hash.txt")).read().split()[-1]
-    cal = calibration(a.dir, prof, a.tag)
-    table = {"kernel_hash": khash, "calibration": cal, "kernels": {}}
+    if a.only:
+        if not set(a.only) <= set(KEYS):
+            raise SystemExit(f"--only: unknown kernel key among {a.only}; known: {sorted(KEYS)}")
+        table = json.load(open(os.path.join(prof, "pmc_constants.json")))
+        table["kernel_hash"] = khash
+        cal = table["calibration"]
+    else:
+        cal = calibration(a.dir, prof, a.tag)
+        table = {"kernel_hash": khash, "calibration": cal, "kernels": {}}
     for key, members in KEYS.items():
+        if a.only and key not in a.only:
+            continue
         tagk = key.replace("/", "_")
         vals, sources = {}, []
         for what in ("fetch", "write", "f64", "tcc"):

@@ -62,10 +62,12 @@ rhs = sum(prof[k] for k in (16, 24, 25, 26, 27, 28, 29))
 SUBS = {33: "change_D order 1", 34: "change_D order 2", 35: "change_D order 3", 36: "change_D order 4", 37: "change_D order 5",
         41: "accept order 1", 42: "accept order 2", 43: "accept order 3", 44: "accept order 4", 45: "accept order 5",
         49: "predict order 1", 50: "predict order 2", 51: "predict order 3", 52: "predict order 4", 53: "predict order 5",
-        56: "ET interior call", 57: "ET water_k > 0", 58: "ET renormalise", 59: "ET first midpoint", 60: "LF sink",
+        54: "packed cell model", 56: "ET interior call", 57: "ET water_k > 0", 58: "ET renormalise", 59: "ET first midpoint", 60: "LF sink",
         61: "hydraulic lift", 62: "num_jac step sizes", 63: "num_jac group scatter"}
 print("sub-region entries per column-step: " + ", ".join(f"{SUBS.get(32 + k, 32 + k)} {v / steps:.2f}" for k, v in enumerate(sub) if v))
 print(f"RHS evaluations: {cnt[16] / steps:.2f} per column-step, {rhs / max(cnt[16], 1):.0f} cycles each, {100.0 * rhs / tot:.1f} % of the cycles")
+if sub[54 - 32]:      # the 5-cells-per-lane default-exponent kernel: evaluations whose cell model ran packed (hc_device.h HC_MODEL_PACK)
+    print(f"packed cell model: {sub[54 - 32] / steps:.2f} of {cnt[24] / steps:.2f} evaluations per column-step ({100.0 * sub[54 - 32] / max(cnt[24], 1):.1f} %)")
 if "--json" in sys.argv:
     path = sys.argv[sys.argv.index("--json") + 1]
     json.dump({"source": f"{os.path.basename(so)}, {N} members x D={DEPTH}, rows {row0}..{row0 + 47} (tools/prof_phases.py)",

@@ -10,6 +10,7 @@ E = dict(att=1.00, jac=1.00, grp=5.00, lu=3.73, nwt=12.22, stp=6.11, rise=0.18, 
 def layout(cpl, halves=1):
     slots = 64 * cpl
     ntab = NTAB + (1 if slots * halves <= 320 else 0)        # + the reciprocal table where the cell model reads it (hc_device.h rdelta_table)
+    ntab += 1 if slots * halves == 320 else 0                # + K of the saturated cell for the packed cell model (ksat_table)
     tables = (ntab * slots * 8 + 4 * slots) * halves
     boxes = 4 * BOX if halves == 2 else 0
     per_wave = (LDS_BYTES - tables - boxes) // 8 - SCRATCH
