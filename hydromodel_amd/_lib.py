@@ -179,6 +179,16 @@ EXPORTS = {
     "hc_get_filter_window_capture": ([C.c_void_p, _ip, _lp], C.c_int),
     "hc_set_filter_window_capture": ([C.c_void_p, _ip, _lp], C.c_int),
     "hc_get_filter_window_width": ([C.c_void_p, _ip, _ip], C.c_int),
+    "hc_set_filter_smoother": ([C.c_void_p, C.c_int32, C.c_int32], C.c_int),
+    "hc_get_filter_smoother_layout": ([C.c_void_p, _ip, _ip, _lp], C.c_int),
+    "hc_get_filter_smoother_hist": ([C.c_void_p, _ip, C.c_int64], C.c_int),
+    "hc_set_filter_smoother_hist_table": ([C.c_void_p, _ip, C.c_int64], C.c_int),
+    "hc_get_filter_smoother_paths": ([C.c_void_p, _lp, C.c_int64], C.c_int),
+    "hc_set_filter_smoother_paths": ([C.c_void_p, _lp, C.c_int64], C.c_int),
+    "hc_get_filter_smoother_ring": ([C.c_void_p, _ip, _lp, _lp, _lp], C.c_int),
+    "hc_set_filter_smoother_ring": ([C.c_void_p, _ip, _lp, _lp, C.c_int64], C.c_int),
+    "hc_filter_smoother_flush": ([C.c_void_p], C.c_int),
+    "hc_reset_filter_smoother": ([C.c_void_p], C.c_int),
     "hc_set_filter_tempering": ([C.c_void_p, C.c_double], C.c_int),
     "hc_get_filter_temper_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),
     "hc_set_filter_temper_stats": ([C.c_void_p, _dp, C.c_int64], C.c_int),

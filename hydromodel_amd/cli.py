@@ -151,6 +151,19 @@ unknown keys, only membership of the 12 is checked):
   ``filter_rows`` ``[R]``, ``filter_window_observed``, ``filter_window_obs_cm``, ``filter_window_prior_mean_cm``,
   ``filter_window_prior_std_cm`` ``[R][n]`` (NaN where the offset's row took no part; a sweep: a leading ``[P]`` axis), and
   the run ends with `` [Ensemble xN] filter window: K lagged observations over R rows``.
+* ``"Filter": {..., "Smoother": {"Stride": 48, "Lag_rows": 480, "Quantiles": [0.05, 0.5, 0.95]}}``: the fixed-lag smoother
+  of the water table by ancestry (include/hydrocol.h hc_set_filter_smoother): every slot carries the water-table indices of
+  the member it descends from on every ``Stride``-th row, and a row is counted ``Lag_rows`` later (a multiple of ``Stride``,
+  at most 64 of them; 0: the analysis) -- its distribution given the well's record up to then.  This is the one table that
+  describes the posterior: every other one describes the forecast.  The rows the run's end leaves pending are counted with
+  the lag they reached (``smooth_lag_rows``).  Far enough back every slot descends from one member: ``smooth_unique_paths``
+  counts the distinct paths behind each row, and when it falls towards 1 give an ``ESS_floor`` or a shorter lag.  Refused:
+  a block that is no object, unknown keys, bools, a ``Lag_rows`` that is no multiple of ``Stride`` or more than 64 of them,
+  more than 16 levels, a filter whose ``Stride`` is 0, and ``"Sharded": true`` on a single-point run.  Added to the file,
+  over the emitted rows ``smooth_rows`` ``[R]``: ``smooth_count``, ``smooth_lag_rows``, ``smooth_unique_paths``,
+  ``smooth_crps_cm`` ``[R]``, ``smooth_hist`` ``[R][D]``, ``smooth_quantile_cm`` ``[R][L]``, ``smooth_quantile_levels``,
+  ``smooth_crps_mean_cm``, ``smooth_stride`` and ``smooth_lag`` (a sweep: a leading ``[P]`` axis), and the run ends with
+  `` [Ensemble xN] smoother: CRPS = ... cm at lag L rows over R rows, fewest paths K``.
 * ``"Filter": {..., "Soil_Moisture": {"Filename": "sm.csv", "Depths_cm": [30, 60, 120], "Sigma": 0.02}}``: a soil-moisture
   record joins the well in the filter's weights (include/hydrocol.h hc_set_filter_soil_moisture): on a row with sensor
   values every member is weighted by the joint Gaussian likelihood of the well and of theta at the sensors' nodes, so the
@@ -294,6 +307,7 @@ def main(params_file=None, data_file=None, seed=None, device=0, gpus=None, _sett
             enkf_window_settings(params["Ensemble"])
             enkf_noise_settings(params["Ensemble"])
             filter_window_settings(params["Ensemble"])
+            filter_smoother_settings(params["Ensemble"])
             noise_correlation_settings(params["Ensemble"])
         ranks = multigpu.Ranks(expect=n_gpus if (n_gpus > 1 or multigpu.in_rank()) else None)
         if ranks.world > 1:
@@ -365,6 +379,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     window = enkf_window_settings(ens)
     noise_alpha = enkf_noise_settings(ens)
     fwindow = filter_window_settings(ens)
+    smoother = filter_smoother_settings(ens)
     corr = noise_correlation_settings(ens)
     cols = ColumnTables(params, load_site_well(params))
     forcing = ForcingDigest(params, water_data, cols)
@@ -373,7 +388,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     if cov is not None:
         covariance_check(cov, cols.dim_d, forcing.dim_t, _profile_stride(ens), len(ens.get("Points") or [0]))
     frecord = soil_moisture_record_of(fsm, cols, water_data, "Filter")
-    assim = Assimilation(filt, frecord, ess_floor, fwindow, rejuvenation, enkf, record, scheme, window, noise_alpha)
+    assim = Assimilation(filt, frecord, ess_floor, fwindow, rejuvenation, enkf, record, scheme, window, noise_alpha,
+                         smoother=smoother)
     if cols.flags["PREDICT"] and not ens.get("repair_predict"):
         raise TypeError("'numpy.float64' object cannot be interpreted as an integer")     # richards_pde.py:327-330
     n_members = int(ens.get("Members", 4096))
@@ -451,6 +467,9 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     eids = [0] if ranks.rank == 0 else []
     atables, assim_lines = _reduce_assimilation(ranks, sim, eids, 1, forcing.dim_t, cols, assim, label, keep_points=False)
     extra.update(atables)
+    stables, smooth_line = _reduce_smoother(ranks, sim, eids, 1, forcing.dim_t, cols, forcing, assim.smoother, device, label,
+                                            keep_points=False)
+    extra.update(stables)
     if fsharded is not None:
         extra["filter_sharded"] = np.array(1 if fsharded else 0, dtype=np.int8)
     if sharded is not None:
@@ -460,7 +479,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     arrays = dict(moments=moments, wtd_mean_cm=mean_cm, wtd_std_cm=std_cm, rows=np.array(rows),
                   members=np.array(n_members), gpus=np.array(ranks.world), initial_cond=psi0, **extra)
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "ensemble water-table statistics", ranks)
-    _print_lines(crps_line, *assim_lines, theta_line, storage_line, cov_line, period_line, uptake_line,
+    _print_lines(crps_line, *assim_lines, smooth_line, theta_line, storage_line, cov_line, period_line, uptake_line,
                  corr_line if ranks.rank == 0 else None)
     sim.close()
 
@@ -487,6 +506,7 @@ class Assimilation:
     scheme: Optional[tuple] = None
     window: Optional[tuple] = None
     noise_alpha: Optional[float] = None
+    smoother: Optional[tuple] = None
 
     def kwargs(self):
         """The ``filter_*`` / ``enkf_*`` keywords of EnsembleSimulation / SweepSimulation: an owner that is off and an
@@ -497,6 +517,8 @@ class Assimilation:
             given = dict(filter_soil_moisture=self.frecord, filter_ess_floor=self.ess_floor,
                          filter_window_offsets=self.fwindow or None, filter_rejuvenation=self.rejuvenation)
             kw.update((k, v) for k, v in given.items() if v is not None)
+            if self.smoother is not None:
+                kw.update(filter_smoother={"stride": self.smoother[0], "lag_rows": self.smoother[0] * self.smoother[1]})
         if self.enkf[0]:
             kw.update(enkf_stride=self.enkf[0], enkf_sigma_cm=self.enkf[1], enkf_localisation_cm=self.enkf[2],
                       enkf_seed=self.enkf[3])
@@ -997,7 +1019,8 @@ def _period_kwargs(periods, plan):
     return kw
 
 
-FILTER_KEYS = ("Stride", "Sigma_cm", "Seed", "Sharded", "Soil_Moisture", "ESS_floor", "Window_Offsets", "Rejuvenation")
+FILTER_KEYS = ("Stride", "Sigma_cm", "Seed", "Sharded", "Soil_Moisture", "ESS_floor", "Window_Offsets", "Rejuvenation",
+               "Smoother")
 
 
 def filter_settings(ens, n_gpus=1):
@@ -1098,6 +1121,98 @@ def filter_window_settings(ens):
         raise ValueError(" Ensemble: Filter.Window_Offsets is not available with \"Sharded\": true: the sharded filter "
                          "gathers the members' water-table indices of the assimilation row only.")
     return off
+
+
+SMOOTHER_KEYS = ("Stride", "Lag_rows", "Quantiles")
+
+
+def filter_smoother_settings(ens):
+    """Ensemble.Filter.Smoother -> (stride, K = Lag_rows / Stride, quantile levels), or None when the block is absent (the
+    run, its file and its lines are then those of a Filter block without it).  Pure, like :func:`filter_settings`, which
+    this runs first: a bad value is a ValueError (message + exit status 1).  ``Stride`` (default 48) is the row stride of
+    the record rows, ``Lag_rows`` (default 0: the analysis) a multiple of it with at most 64 strides, ``Quantiles`` at most
+    16 levels in [0, 1] (default 0.05, 0.5, 0.95).  Needs an active filter; refused together with ``"Sharded": true`` on a
+    single-point run."""
+    import math
+    from numbers import Real
+    from .stepper import SMOOTHER_MAX_LAG, WTD_MAX_LEVELS
+    if "Smoother" in ens:
+        raise ValueError(" Ensemble: Smoother belongs inside the \"Filter\" block.")
+    filt_stride = filter_settings(ens)[0]
+    block = ens.get("Filter")
+    if not isinstance(block, dict) or "Smoother" not in block:
+        return None
+    sm = block["Smoother"]
+    if not isinstance(sm, dict):
+        raise ValueError(f" Ensemble: Filter.Smoother = {sm!r} must be an object such as "
+                         f"{{\"Stride\": 48, \"Lag_rows\": 480}}.")
+    unknown = sorted(set(sm) - set(SMOOTHER_KEYS))
+    if unknown:
+        raise ValueError(f" Ensemble: Filter.Smoother has unknown keys {unknown} (known: {list(SMOOTHER_KEYS)}).")
+    stride, lag_rows = sm.get("Stride", 48), sm.get("Lag_rows", 0)
+    if (isinstance(stride, bool) or not isinstance(stride, Real) or not math.isfinite(stride) or stride != int(stride)
+            or stride < 1 or stride > (1 << 31) - 1):
+        raise ValueError(f" Ensemble: Filter.Smoother.Stride = {stride!r} must be a row stride >= 1.")
+    if (isinstance(lag_rows, bool) or not isinstance(lag_rows, Real) or not math.isfinite(lag_rows)
+            or lag_rows != int(lag_rows) or lag_rows < 0):
+        raise ValueError(f" Ensemble: Filter.Smoother.Lag_rows = {lag_rows!r} must be a number of rows >= 0.")
+    stride, lag_rows = int(stride), int(lag_rows)
+    if lag_rows % stride:
+        raise ValueError(f" Ensemble: Filter.Smoother.Lag_rows = {lag_rows} must be a multiple of its Stride = {stride}.")
+    if lag_rows // stride > SMOOTHER_MAX_LAG:
+        raise ValueError(f" Ensemble: Filter.Smoother.Lag_rows = {lag_rows} is {lag_rows // stride} strides of {stride} "
+                         f"rows, at most {SMOOTHER_MAX_LAG}.")
+    levels = sm.get("Quantiles", [0.05, 0.5, 0.95])
+    if (not isinstance(levels, (list, tuple)) or len(levels) > WTD_MAX_LEVELS
+            or any(isinstance(v, bool) or not isinstance(v, Real) or not math.isfinite(v) or not 0.0 <= v <= 1.0
+                   for v in levels)):
+        raise ValueError(f" Ensemble: Filter.Smoother.Quantiles = {levels!r} must be a list of at most {WTD_MAX_LEVELS} "
+                         f"levels in [0, 1].")
+    if not filt_stride:
+        raise ValueError(" Ensemble: Filter.Smoother needs an active filter (Filter.Stride > 0).")
+    if not ens.get("Points") and block.get("Sharded", False):
+        raise ValueError(" Ensemble: Filter.Smoother is not available with \"Sharded\": true: the columns the ranks "
+                         "exchange do not carry the smoother's ring.")
+    return stride, lag_rows // stride, tuple(float(v) for v in levels)
+
+
+def _reduce_smoother(ranks, sim, ids, P, T, ref, forcing, smoother, device, label, keep_points):
+    """The smoother's datasets and closing line (``smoother``: :func:`filter_smoother_settings`; None: nothing): each
+    rank flushes its handle ``sim`` (None: it holds no points), its points' tables are placed at ``ids`` of the run's
+    ``P`` and summed over the ranks -- two collectives every rank joins -- and rank 0 forms the summary."""
+    import numpy as np
+    from .multigpu import place_points
+    from .stepper import filter_smoother_summary, stride_rows
+    if smoother is None:
+        return {}, None
+    stride, lag, levels = smoother
+    n_srow, D = stride_rows(T, stride), ref.dim_d
+    if sim is not None:
+        sim.stepper.filter_smoother_flush()
+        lhist, lpaths = sim.stepper.filter_smoother_hist(), sim.stepper.filter_smoother_paths()
+    else:
+        lhist, lpaths = np.zeros((0, n_srow, D), dtype=np.int32), np.zeros((0, n_srow, 2), dtype=np.int64)
+    hist, paths = place_points(lhist, ids, P, ranks), place_points(lpaths, ids, P, ranks)
+    if ranks.rank != 0:
+        return {}, None
+    if not keep_points:
+        hist, paths = hist[0], paths[0]
+    summ = filter_smoother_summary(hist, paths, forcing.wtd_obs, levels, ref.dz, ref.z, stride, device)
+    emitted = np.flatnonzero((np.asarray(summ["lag_rows"]) >= 0).reshape(-1, n_srow).any(axis=0))
+    out = {"smooth_rows": summ["rows"][emitted], "smooth_count": summ["count"][..., emitted],
+           "smooth_hist": np.asarray(hist, dtype=np.int32)[..., emitted, :],
+           "smooth_lag_rows": summ["lag_rows"][..., emitted], "smooth_unique_paths": summ["unique_paths"][..., emitted],
+           "smooth_quantile_levels": np.asarray(summ["levels"], dtype=np.float64),
+           "smooth_quantile_cm": summ["quantile_cm"][..., emitted, :], "smooth_crps_cm": summ["crps_cm"][..., emitted],
+           "smooth_stride": np.array(stride, dtype=np.int64), "smooth_lag": np.array(lag, dtype=np.int64)}
+    # the mean over the rows that counted members, per point (as wtd_crps_mean_cm)
+    out["smooth_crps_mean_cm"] = np.asarray(summ["crps_mean_cm"], dtype=np.float64)
+    solved = np.asarray(out["smooth_count"]) > 0
+    n = int(solved.reshape(-1, emitted.size).any(axis=0).sum())
+    mean = float(np.asarray(out["smooth_crps_cm"])[solved].mean()) if solved.any() else float("nan")
+    fewest = int(np.asarray(out["smooth_unique_paths"])[solved].min()) if solved.any() else 0
+    line = (f" [{label}] smoother: CRPS = {mean:.3f} cm at lag {lag * stride} rows over {n} rows, fewest paths {fewest}")
+    return out, line
 
 
 def filter_sharded(ens):
@@ -1911,12 +2026,15 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     arrays.update(utables)
     atables, assim_lines = _reduce_assimilation(ranks, sim, mine, P, T, ref, assim, label, keep_points=True)
     arrays.update(atables)
+    stables, smooth_line = _reduce_smoother(ranks, sim, mine, P, T, ref, forcing, assim.smoother, device, label,
+                                            keep_points=True)
+    arrays.update(stables)
     ctables, corr_line = _noise_correlation_arrays(corr, cols_all, label, keep_points=True)
     arrays.update(ctables)
     if sim is not None:
         sim.close()
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "sweep's water-table statistics", ranks)
-    _print_lines(crps_line, *assim_lines, theta_line, storage_line, cov_line, period_line, uptake_line,
+    _print_lines(crps_line, *assim_lines, smooth_line, theta_line, storage_line, cov_line, period_line, uptake_line,
                  corr_line if ranks.rank == 0 else None)
 
 
@@ -1946,6 +2064,7 @@ def run_cli(argv=None):
                 enkf_window_settings(settings["Ensemble"])
                 enkf_noise_settings(settings["Ensemble"])
                 filter_window_settings(settings["Ensemble"])
+                filter_smoother_settings(settings["Ensemble"])
                 noise_correlation_settings(settings["Ensemble"])
             except ValueError as bad:
                 print(bad)

@@ -335,6 +335,18 @@ struct hc_handle {
     DevBuf<unsigned short> fs_w;
     std::vector<long long> fs_counts;
     std::vector<int64_t> fs_send_words, fs_recv_words;
+    // fixed-lag smoother of the water table by ancestry (hc_set_filter_smoother): the stride (0: off) and the lag K in
+    // record rows; the ring of K + 1 planes -- the members' water-table indices uint16 [K + 1][N], the index within its
+    // point of the member each slot descends from uint32 [K + 1][N], their second buffers for the ancestry, and on the
+    // host the forcing row each plane holds (-1: none); the last row stepped (what a flush conditions on; -1: none);
+    // the tables shist int32 [P][n_srow][D] and spaths int64 [P][n_srow][2], keyed by (points, rows, depth)
+    int smo_stride = 0, smo_lag = 0;
+    DevBuf<unsigned short> smo_w, smo_w_alt;
+    DevBuf<unsigned> smo_id, smo_id_alt;
+    std::vector<int64_t> smo_row;
+    int64_t smo_last = -1;
+    AccTable<int> smo_hist{"entries"};
+    AccTable<long long> smo_paths{"entries"};
     // ensemble Kalman filter (hc_set_enkf): diagnostics float64 [P][n_arow][8] keyed by (points, rows, stride); per
     // member the observations Y [N][m'] (the well's y first), the well's eps, the sensors' eps [N][n_s] and the
     // posterior (y, theta..., rejected); what the analysis keeps of psi (EnkfVec, the spread only when psi is relaxed; the
@@ -3161,6 +3173,95 @@ __global__ void window_capture_kernel(const unsigned short *w, long long n_membe
     if (k < n_members) out[k] = (int)w[k];
 }
 
+// ---- fixed-lag smoother of the water table by ancestry (hc_set_filter_smoother, include/hydrocol.h): integers only
+constexpr int SMO_PLANES = HC_SMOOTHER_MAX_LAG + 1;
+// the ring's planes a gather moves: those that hold a row
+struct SmootherPlanes {
+    int n;
+    unsigned char plane[SMO_PLANES];
+};
+
+// a record row into its plane: every member's water-table index of that row and, as the path's id, the member's index
+// within its point
+__global__ void smoother_store_kernel(const unsigned short *w, long long n_members, long long members_per_point,
+                                      unsigned short *ring_w, unsigned *ring_id)
+{
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n_members) {
+        ring_w[k] = w[k];
+        ring_id[k] = (unsigned)(k % members_per_point);
+    }
+}
+
+// the particle filter's ancestry applied to the ring, next to period_gather_kernel: slot m takes its ancestor's values of
+// every live plane (into the second buffers; the host swaps them in).  One thread per slot reads anc[m] once; each plane
+// is read through it -- the ancestry of systematic resampling is non-decreasing within a point, so a wave's loads fall
+// into a few lines -- and written coalesced.
+__global__ __launch_bounds__(256) void smoother_gather_kernel(const long long *anc, long long n_members,
+                                                              const SmootherPlanes L, const unsigned short *w,
+                                                              const unsigned *id, unsigned short *w_out, unsigned *id_out)
+{
+    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n_members) return;
+    const long long a = anc[m];
+    const size_t src = (size_t)(a >= 0 && a < n_members ? a : m);     // (every slot is filled: a guard)
+    for (int j = 0; j < L.n; j++) {
+        const size_t at = (size_t)L.plane[j] * (size_t)n_members;
+        w_out[at + (size_t)m] = w[at + src];
+        id_out[at + (size_t)m] = id[at + src];
+    }
+}
+
+// One plane into record slot `slot` of the tables: grid x = member slice, y = point.  The bins are counted as
+// wtd_hist_kernel counts them (LDS, the wave's lanes grouped by bin with ballots first, int32 atomics of nonzero bins
+// only; an index >= D goes to no bin).  The distinct paths: a store writes the identity and every ancestry is
+// non-decreasing within a point, so the ids of a point's slots are non-decreasing and their distinct values number the
+// slots that open a run -- the point's first slot and every slot whose id differs from its left neighbour's.  The left
+// neighbour of a slice's first slot is read from the plane like any other (it lies in the same point); the point's first
+// slot has none, and nothing at or past the slice's end is read.  One uint64 atomic per wave adds the count to
+// spaths[point][slot][0]; the conditioning row goes to [1].
+__global__ __launch_bounds__(HIST_THREADS) void smoother_emit_kernel(const unsigned short *w, const unsigned *id,
+                                                                     long long members_per_point,
+                                                                     long long members_per_block, long long n_srow,
+                                                                     long long slot, long long cond_row, int D, int *shist,
+                                                                     long long *spaths)
+{
+    __shared__ unsigned bins[HC_MAX_DEPTH_NODES];
+    for (int b = threadIdx.x; b < D; b += HIST_THREADS) bins[b] = 0;
+    __syncthreads();
+    const long long point = blockIdx.y;
+    const long long start = point * members_per_point, end = start + members_per_point;
+    const long long m0 = start + (long long)blockIdx.x * members_per_block;
+    const long long m1 = m0 + members_per_block < end ? m0 + members_per_block : end;
+    const int lane = threadIdx.x % WAVE;
+    unsigned long long heads = 0;
+    // wave-uniform trip count: every lane of a wave runs the ballots of every round
+    for (long long k0 = m0 + (threadIdx.x - lane); k0 < m1; k0 += HIST_THREADS) {
+        const long long k = k0 + lane;
+        const bool in = k < m1;
+        const int b = in ? (int)w[k] : -1;
+        const bool head = in && (k == start || id[k] != id[k - 1]);
+        heads += (unsigned long long)__popcll(__ballot(head));
+        unsigned long long pending = __ballot(b >= 0 && b < D);
+        while (pending) {
+            const int leader = __ffsll((long long)pending) - 1;
+            const int v = __builtin_amdgcn_readlane(b, leader);
+            const unsigned long long same = __ballot(b == v) & pending;
+            if (lane == leader) atomicAdd(&bins[v], (unsigned)__popcll(same));
+            pending &= ~same;
+        }
+    }
+    __syncthreads();
+    int *t = shist + ((size_t)point * n_srow + (size_t)slot) * D;
+    for (int b = threadIdx.x; b < D; b += HIST_THREADS) {
+        const unsigned c = bins[b];
+        if (c) atomicAdd(t + b, (int)c);
+    }
+    long long *p = spaths + ((size_t)point * n_srow + (size_t)slot) * 2;
+    if (lane == 0 && heads) atomicAdd(reinterpret_cast<unsigned long long *>(p), heads);
+    if (blockIdx.x == 0 && threadIdx.x == 0) p[1] = cond_row;
+}
+
 // ---- tempered weights (hc_set_filter_tempering, include/hydrocol.h)
 // After the weight kernels, per point: the largest k of a bisection over beta_k = k / 1024 for which the weights
 // q = floor(2^31 exp(beta_k (l - s))) keep Q^2 >= T sum q^2.  Q, sum q^2 and the comparison are exact integers, so k
@@ -4268,10 +4369,55 @@ void fsm_off(hc_handle *h)
     h->filt_ipart.release();
 }
 
+// the smoother's tables (hc_set_filter_smoother): shist [P][n_srow][D] int32 zeroed and spaths [P][n_srow][2] int64 as
+// (0, -1), and the ring's buffers; on a fresh key (the points, the forcing rows or the depth changed) the ring is emptied
+int64_t smoother_rows(const hc_handle *h) { return (h->n_rows - 1) / h->smo_stride + 1; }
+int64_t smoother_entries(const hc_handle *h) { return (int64_t)h->n_points * smoother_rows(h) * h->p.dim_d; }
+int smoother_paths_init(hc_handle *h)
+{
+    std::vector<long long> init((size_t)h->smo_paths.n);
+    for (size_t k = 0; k < init.size(); k++) init[k] = k % 2 ? -1 : 0;
+    HIP_TRY(hipMemcpy(h->smo_paths.buf.p, init.data(), init.size() * 8, hipMemcpyHostToDevice));
+    return HC_OK;
+}
+int ensure_smoother(hc_handle *h)
+{
+    if (h->smo_stride <= 0) return fail(HC_ERR_ARG, "the filter's smoother is off (hc_set_filter_smoother)");
+    if (int rc = ensure_filter(h)) return rc;
+    if (smoother_entries(h) > HC_WTD_HIST_MAX_ENTRIES)
+        return fail(HC_ERR_ARG, "the filter's smoother: %lld entries exceed HC_WTD_HIST_MAX_ENTRIES (take a longer stride)",
+                    (long long)smoother_entries(h));
+    const AccTable<int> &t = h->smo_hist;
+    const bool fresh = !(t.key[0] == h->n_points && t.key[1] == h->n_rows && t.key[2] == h->p.dim_d);
+    if (int rc = h->smo_hist.ensure(h->n_points, h->n_rows, h->p.dim_d, smoother_entries(h))) return rc;
+    if (int rc = h->smo_paths.ensure(h->n_points, h->n_rows, h->p.dim_d, (int64_t)h->n_points * smoother_rows(h) * 2))
+        return rc;
+    const size_t ring = (size_t)(h->smo_lag + 1) * (size_t)h->n_members;
+    if (h->smo_w.ensure(ring) || h->smo_w_alt.ensure(ring) || h->smo_id.ensure(ring) || h->smo_id_alt.ensure(ring))
+        return HC_ERR_DEVICE;
+    if (fresh) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        if (int rc = smoother_paths_init(h)) return rc;
+        h->smo_row.assign((size_t)(h->smo_lag + 1), (int64_t)-1);
+        h->smo_last = -1;
+    }
+    return HC_OK;
+}
+
+void smoother_off(hc_handle *h)
+{
+    h->smo_stride = h->smo_lag = 0;
+    h->smo_last = -1;
+    h->smo_row.clear();
+    h->smo_hist.release(); h->smo_paths.release();
+    h->smo_w.release(); h->smo_w_alt.release(); h->smo_id.release(); h->smo_id_alt.release();
+}
+
 // what turns the filter off: new points, members or noise source (include/hydrocol.h hc_set_filter)
 void filter_off(hc_handle *h)
 {
     filter_shard_off(h);
+    smoother_off(h);
     fsm_off(h);
     fwin_off(h);
     temper_off(h);
@@ -6020,6 +6166,69 @@ int assimilate(hc_handle *h, const Chunk &c)
     return HC_OK;
 }
 
+// The smoother (hc_set_filter_smoother): the plane of record slot j into the tables, conditioned on row `cond_row`; the
+// plane is then empty
+int smoother_emit(hc_handle *h, int64_t j, int64_t cond_row)
+{
+    const int64_t N = h->n_members, plane = j % (h->smo_lag + 1);
+    const long long mpp = N / h->n_points;
+    const long long mpb = std::max(HIST_MEMBERS_PER_BLOCK, (mpp + 65535) / 65536);
+    const long long slices = (mpp + mpb - 1) / mpb;
+    hipLaunchKernelGGL(smoother_emit_kernel, dim3((unsigned)slices, (unsigned)h->n_points), dim3(HIST_THREADS), 0, h->stream,
+                       h->smo_w.p + (size_t)plane * N, h->smo_id.p + (size_t)plane * N, mpp, mpb,
+                       (long long)smoother_rows(h), (long long)j, (long long)cond_row, (int)h->p.dim_d, h->smo_hist.buf.p,
+                       h->smo_paths.buf.p);
+    HIP_TRY(hipGetLastError());
+    h->smo_row[(size_t)plane] = -1;
+    return HC_OK;
+}
+
+// ... every live plane of both rings through the ancestor table of the row just resampled, out of place, swapped in
+int smoother_gather(hc_handle *h)
+{
+    SmootherPlanes L{};
+    for (size_t k = 0; k < h->smo_row.size(); k++)
+        if (h->smo_row[k] >= 0) L.plane[L.n++] = (unsigned char)k;
+    if (L.n == 0) return HC_OK;
+    const int64_t N = h->n_members;
+    hipLaunchKernelGGL(smoother_gather_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, h->filt_anc.p,
+                       (long long)N, L, h->smo_w.p, h->smo_id.p, h->smo_w_alt.p, h->smo_id_alt.p);
+    HIP_TRY(hipGetLastError());
+    std::swap(h->smo_w, h->smo_w_alt);
+    std::swap(h->smo_id, h->smo_id_alt);
+    return HC_OK;
+}
+
+// ... after a launch and its assimilation, if any (`resampled`): the launch's record rows in ascending order, each
+// stored from the launch's water-table indices (an unobserved one empties its plane instead), the last one gathered if
+// the filter resampled on it, then the plane K record rows back emitted; an assimilation row that is no record row
+// gathers only
+int smoother_launch(hc_handle *h, const Chunk &c, bool resampled)
+{
+    const int64_t N = h->n_members, s = h->smo_stride, K = h->smo_lag;
+    const int64_t last = c.row0 + c.rows - 1;
+    for (int64_t r = std::max<int64_t>(s, (c.row0 + s - 1) / s * s); r <= last; r += s) {
+        const int64_t j = r / s, plane = j % (K + 1);
+        if (h->h_wtd_obs[(size_t)r] >= 0) {
+            hipLaunchKernelGGL(smoother_store_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream,
+                               h->wtd_u16.p + (size_t)(r - c.row0) * N, (long long)N, (long long)(N / h->n_points),
+                               h->smo_w.p + (size_t)plane * N, h->smo_id.p + (size_t)plane * N);
+            HIP_TRY(hipGetLastError());
+            h->smo_row[(size_t)plane] = r;
+        } else {
+            h->smo_row[(size_t)plane] = -1;
+        }
+        if (r == last && resampled)
+            if (int rc = smoother_gather(h)) return rc;
+        if (j - K >= 1 && h->smo_row[(size_t)((j - K) % (K + 1))] >= 0)
+            if (int rc = smoother_emit(h, j - K, r)) return rc;
+    }
+    if (resampled && last % s != 0)
+        if (int rc = smoother_gather(h)) return rc;
+    h->smo_last = last;
+    return HC_OK;
+}
+
 // The lagged row the launch ended on: every member's y into the window's buffer, by the analysis's own kernel
 int enkf_capture(hc_handle *h, const Chunk &c, int slot)
 {
@@ -6341,6 +6550,8 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
     if (filt_on && h->filt_floor > 0.0 && (rc = ensure_ftemp(h))) return rc;
     if (filt_on && h->rj_delta > 0.0 && (rc = ensure_frej(h))) return rc;
     if (da_on && da.win.n > 0 && (rc = da.ensure_win(h))) return rc;
+    const bool smo_on = filt_on && h->smo_stride > 0;        // the smoother (hc_set_filter_smoother)
+    if (smo_on && (rc = ensure_smoother(h))) return rc;
     int64_t fresh_consumed = 0;
     for (int64_t done = 0; done < a->n_rows;) {
         const Chunk c = plan_chunk(h, a, done, prof_on);
@@ -6351,6 +6562,7 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
         if ((rc = copy_outputs(h, a, c, done))) return rc;
         const int64_t last = c.row0 + c.rows - 1;
         if (filt_on && is_assimilation_row(h, last) && (rc = assimilate(h, c))) return rc;
+        if (smo_on && (rc = smoother_launch(h, c, is_assimilation_row(h, last)))) return rc;
         if (enkf_on && is_assimilation_row(h, last) &&
             (rc = enkf_analyse(h, c, assim_row(h, h->enkf_sm, h->enkf_win, h->enkf_sigma, last))))
             return rc;
@@ -7624,6 +7836,154 @@ int hc_get_filter_window_width(hc_handle *h, int32_t *width, int32_t *slots)
     return window_width(h->filt_win, h->filt_stride > 0 && h->filt_done, width, slots);
 }
 
+int hc_set_filter_smoother(hc_handle *h, int32_t stride, int32_t lag)
+{
+    if (!h) return fail(HC_ERR_ARG, "hc_set_filter_smoother: bad argument");
+    if (stride < 0) return fail(HC_ERR_ARG, "hc_set_filter_smoother: stride = %d must be >= 0", (int)stride);
+    if (stride > 0 && (lag < 0 || lag > HC_SMOOTHER_MAX_LAG))
+        return fail(HC_ERR_ARG, "hc_set_filter_smoother: lag = %d outside [0, %d] record rows", (int)lag, HC_SMOOTHER_MAX_LAG);
+    if (stride > 0 && h->enkf_stride > 0)
+        return fail(HC_ERR_ARG, "hc_set_filter_smoother: the EnKF is on (the smoother follows the particle filter's ancestry)");
+    if (stride > 0 && h->filt_stride <= 0)
+        return fail(HC_ERR_ARG, "hc_set_filter_smoother: the particle filter is off (hc_set_filter comes first)");
+    if (stride > 0 && h->fs_n > 0)
+        return fail(HC_ERR_ARG, "hc_set_filter_smoother: the filter is sharded (hc_set_filter_shard), and the routed columns "
+                                "do not carry the smoother's ring");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    smoother_off(h);
+    if (stride == 0) return HC_OK;
+    h->smo_stride = stride;
+    h->smo_lag = lag;
+    const int rc = ensure_smoother(h);
+    if (rc != HC_OK) smoother_off(h);            // refused: off
+    return rc;
+}
+
+int hc_get_filter_smoother_layout(hc_handle *h, int32_t *stride, int32_t *lag, int64_t *n_srow)
+{
+    if (!h || !stride || !lag || !n_srow) return fail(HC_ERR_ARG, "hc_get_filter_smoother_layout: bad argument");
+    *stride = h->smo_stride;
+    *lag = h->smo_lag;
+    *n_srow = h->smo_stride > 0 && h->have_forcing ? smoother_rows(h) : 0;
+    return HC_OK;
+}
+
+int hc_get_filter_smoother_hist(hc_handle *h, int32_t *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_get_filter_smoother_hist: bad argument");
+    return table_copy(h, h->smo_hist, ensure_smoother, hipMemcpyDeviceToHost, table, n_entries, "hc_get_filter_smoother_hist");
+}
+
+int hc_set_filter_smoother_hist_table(hc_handle *h, const int32_t *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_set_filter_smoother_hist_table: bad argument");
+    return table_copy(h, h->smo_hist, ensure_smoother, hipMemcpyHostToDevice, const_cast<int32_t *>(table), n_entries,
+                      "hc_set_filter_smoother_hist_table");
+}
+
+int hc_get_filter_smoother_paths(hc_handle *h, int64_t *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_get_filter_smoother_paths: bad argument");
+    return table_copy(h, h->smo_paths, ensure_smoother, hipMemcpyDeviceToHost, table, n_entries,
+                      "hc_get_filter_smoother_paths");
+}
+
+int hc_set_filter_smoother_paths(hc_handle *h, const int64_t *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_set_filter_smoother_paths: bad argument");
+    return table_copy(h, h->smo_paths, ensure_smoother, hipMemcpyHostToDevice, const_cast<int64_t *>(table), n_entries,
+                      "hc_set_filter_smoother_paths");
+}
+
+int hc_get_filter_smoother_ring(hc_handle *h, int32_t *w, int64_t *id, int64_t *rows, int64_t *last_row)
+{
+    if (!h || !w || !id || !rows || !last_row) return fail(HC_ERR_ARG, "hc_get_filter_smoother_ring: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = ensure_smoother(h)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const size_t N = (size_t)h->n_members;
+    std::vector<unsigned short> hw(N);
+    std::vector<unsigned> hid(N);
+    for (int k = 0; k <= h->smo_lag; k++) {
+        rows[k] = h->smo_row[(size_t)k];
+        if (rows[k] >= 0) {
+            HIP_TRY(hipMemcpy(hw.data(), h->smo_w.p + (size_t)k * N, N * sizeof(unsigned short), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(hid.data(), h->smo_id.p + (size_t)k * N, N * sizeof(unsigned), hipMemcpyDeviceToHost));
+            for (size_t m = 0; m < N; m++) w[(size_t)k * N + m] = (int32_t)hw[m], id[(size_t)k * N + m] = (int64_t)hid[m];
+        } else {
+            std::fill_n(w + (size_t)k * N, N, (int32_t)0);
+            std::fill_n(id + (size_t)k * N, N, (int64_t)0);
+        }
+    }
+    *last_row = h->smo_last;
+    return HC_OK;
+}
+
+int hc_set_filter_smoother_ring(hc_handle *h, const int32_t *w, const int64_t *id, const int64_t *rows, int64_t last_row)
+{
+    if (!h || !w || !id || !rows) return fail(HC_ERR_ARG, "hc_set_filter_smoother_ring: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = ensure_smoother(h)) return rc;
+    const size_t N = (size_t)h->n_members, K1 = (size_t)h->smo_lag + 1;
+    const int64_t mpp = h->n_members / h->n_points, s = h->smo_stride;
+    if (last_row < -1 || last_row >= h->n_rows)
+        return fail(HC_ERR_ARG, "hc_set_filter_smoother_ring: last row %lld outside [-1, %lld)", (long long)last_row,
+                    (long long)h->n_rows);
+    for (size_t k = 0; k < K1; k++) {
+        if (rows[k] == -1) continue;
+        if (rows[k] < 1 || rows[k] >= h->n_rows || rows[k] % s != 0 || (size_t)(rows[k] / s) % K1 != k)
+            return fail(HC_ERR_ARG, "hc_set_filter_smoother_ring: row %lld is not a record row of plane %zu",
+                        (long long)rows[k], k);
+        for (size_t m = 0; m < N; m++) {
+            if (w[k * N + m] < 0 || w[k * N + m] > 65535)
+                return fail(HC_ERR_ARG, "hc_set_filter_smoother_ring: index %d (plane %zu, member %zu) outside [0, 65535]",
+                            (int)w[k * N + m], k, m);
+            if (id[k * N + m] < 0 || id[k * N + m] >= mpp)
+                return fail(HC_ERR_ARG, "hc_set_filter_smoother_ring: id %lld (plane %zu, member %zu) outside [0, %lld)",
+                            (long long)id[k * N + m], k, m, (long long)mpp);
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    std::vector<unsigned short> hw(K1 * N);
+    std::vector<unsigned> hid(K1 * N);
+    for (size_t e = 0; e < K1 * N; e++) {
+        const bool live = rows[e / N] >= 0;
+        hw[e] = live ? (unsigned short)w[e] : 0;
+        hid[e] = live ? (unsigned)id[e] : 0;
+    }
+    HIP_TRY(hipMemcpy(h->smo_w.p, hw.data(), hw.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->smo_id.p, hid.data(), hid.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+    h->smo_row.assign(rows, rows + K1);
+    h->smo_last = last_row;
+    return HC_OK;
+}
+
+int hc_filter_smoother_flush(hc_handle *h)
+{
+    if (!h) return fail(HC_ERR_ARG, "hc_filter_smoother_flush: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = ensure_smoother(h)) return rc;
+    std::vector<int64_t> pending;
+    for (const int64_t r : h->smo_row)
+        if (r >= 0) pending.push_back(r);
+    std::sort(pending.begin(), pending.end());
+    for (const int64_t r : pending)
+        if (int rc = smoother_emit(h, r / h->smo_stride, std::max(h->smo_last, r))) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return HC_OK;
+}
+
+int hc_reset_filter_smoother(hc_handle *h)
+{
+    if (!h) return fail(HC_ERR_ARG, "hc_reset_filter_smoother: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->smo_hist.invalidate();
+    h->smo_paths.invalidate();
+    return ensure_smoother(h);
+}
+
 }  // extern "C"
 namespace {
 // the argument checks the two shard entry points share; n_global through *np
@@ -7683,6 +8043,9 @@ int hc_set_filter_shard(hc_handle *h, int32_t n_shards, const int64_t *bounds, i
         return fail(HC_ERR_ARG, "hc_set_filter_shard: the base vectors are rejuvenated (hc_set_filter_rejuvenation), and the "
                                 "sharded filter gathers water-table indices only: their moments would need an exchange of "
                                 "their own");
+    if (h->smo_stride > 0)
+        return fail(HC_ERR_ARG, "hc_set_filter_shard: the smoother is set (hc_set_filter_smoother), and the routed columns do "
+                                "not carry its ring");
     if (h->per_n > 0)
         return fail(HC_ERR_ARG, "hc_set_filter_shard: period totals are set (hc_set_period_totals), and the routed columns do "
                                 "not carry the members' accumulators");

@@ -14,7 +14,8 @@ from .stepper import theta_cov_finish, theta_sensor_gain
 from .stepper import noise_correlation_breaks, noise_correlation_settings, noise_correlation_tables
 from .stepper import (ASSIM_TABLES, ENKF_METHODS, EnsembleStepper, enkf_sm_summary, enkf_summary,
                       enkf_window_settings, enkf_window_summary, filter_sm_summary, filter_summary,
-                      filter_window_settings, filter_window_summary, rejuvenation_discount,
+                      filter_smoother_config, filter_smoother_summary, filter_window_settings, filter_window_summary,
+                      rejuvenation_discount,
                       flux_max_log2_of, layer_ranges, layer_storage_distribution, moments_to_mean_std, period_totals_distribution,
                       sensor_nodes, theta_distribution, wtd_distribution)
 from .stepper import layer_cells, root_uptake_distribution, root_uptake_profile, root_uptake_stats
@@ -151,6 +152,10 @@ class _Run:
     conductivity fields -- with the same observations, draws and factor (include/hydrocol.h hc_set_enkf_noise_field),
     relaxed to prior spread with ``a`` (default: enkf_relaxation); the ``noise_*`` keys of :meth:`enkf_summary`.
     Parameters regain no spread from the dynamics: without a relaxation a long run collapses the field.
+    filter_smoother: ``{"stride": s, "lag_rows": L}`` (L a multiple of s, L / s <= 64): the fixed-lag smoother of the water
+    table by ancestry -- every slot carries its ancestors' water-table indices of each s-th row through the resamplings, and
+    the row is counted L rows later: its distribution given the well's record up to then, the one table that describes the
+    posterior (include/hydrocol.h hc_set_filter_smoother); :meth:`filter_smoothed`.  Not with filter_shard.
     enkf_window_offsets: rows before each analysis row (integers in [1, enkf_stride), e.g. (12, 24, 36)) on which the
     well's record joins that analysis too -- the asynchronous EnKF (include/hydrocol.h hc_set_enkf_window);
     :meth:`enkf_window_table`, the ``window_*`` keys of :meth:`enkf_summary`.
@@ -167,7 +172,7 @@ class _Run:
                       enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=(),
                       filter_soil_moisture=None, theta_hist_bins=0, storage_layers_cm=None, storage_bins=0,
                       filter_ess_floor=0.0, filter_window_offsets=(), enkf_noise_field=None, filter_rejuvenation=0.0,
-                      theta_cov_stride=0):
+                      theta_cov_stride=0, filter_smoother=None):
         self.profile_stride = int(profile_stride)
         self.theta_cov_stride = int(theta_cov_stride or 0)
         if self.theta_cov_stride and not self.profile_stride:
@@ -220,6 +225,12 @@ class _Run:
                                                             self.stepper.filter_sm_n)
         if self.filter_window_offsets:
             self.stepper.set_filter_window(self.filter_window_offsets)
+        # the fixed-lag smoother (after everything else of the filter's): (stride, lag in record rows) or None
+        self.filter_smoother = filter_smoother_config(filter_smoother)
+        if self.filter_smoother is not None:
+            if not self.filter_stride:
+                raise ValueError("filter_smoother needs the particle filter (filter_stride > 0)")
+            self.stepper.set_filter_smoother(*self.filter_smoother)
         self.enkf_stride = int(enkf_stride or 0)
         self.enkf_sigma_cm = float(enkf_sigma_cm) if self.enkf_stride else None
         self.enkf_localisation_cm = float(enkf_localisation_cm or 0.0) if self.enkf_stride else None
@@ -522,6 +533,25 @@ class _Run:
             out.update(("window_" + k, v) for k, v in self.filter_window_summary(window_table).items())
         return out
 
+    def filter_smoothed(self, levels=(0.05, 0.5, 0.95), hist=None, paths=None):
+        """The smoothed water-table distributions (include/hydrocol.h hc_set_filter_smoother): flushes the ring -- every
+        pending row is emitted with the lag it reached -- and returns stepper.filter_smoother_summary of the tables
+        (``hist`` / ``paths``: e.g. those assembled over ranks, after each rank's own flush): ``rows``, ``count``,
+        ``hist``, ``quantile_cm``, ``crps_cm`` against the well, ``crps_mean_cm``, ``lag_rows`` (the lag each row really
+        got) and ``unique_paths`` (towards 1 the histogram is one trajectory: hold the ESS up with filter_ess_floor, or
+        take a shorter lag); a sweep: a leading [P].  This is the one table that describes the posterior."""
+        if getattr(self, "filter_smoother", None) is None:
+            raise ValueError(f" {self.__class__.__name__}: no smoother (filter_smoother).")
+        self.stepper.filter_smoother_flush()
+        h = self.stepper.filter_smoother_hist() if hist is None else np.asarray(hist)
+        p = self.stepper.filter_smoother_paths() if paths is None else np.asarray(paths)
+        if hist is None:
+            h = h.reshape(self._lead + h.shape[1:])
+        if paths is None:
+            p = p.reshape(self._lead + p.shape[1:])
+        return filter_smoother_summary(h, p, self.forcing.wtd_obs, levels, self.cols.dz, self.cols.z,
+                                       self.filter_smoother[0], device=self.stepper.device)
+
     def filter_window_table(self):
         """[n_arow][n][4] float64 (include/hydrocol.h hc_set_filter_window); a sweep: [P][n_arow][n][4]."""
         return self.assim_table("filter_window")
@@ -616,7 +646,7 @@ class EnsembleSimulation(_Run):
                  theta_hist_bins=0, storage_layers_cm=None, storage_bins=0, period_ends=None, period_thresholds_cm=(),
                  period_bins=0, period_flux_max_cm=(16.0, 4.0), filter_ess_floor=0.0, filter_window_offsets=(),
                  enkf_noise_field=None, filter_rejuvenation=0.0, noise_correlation=None,
-                 theta_cov_stride=0, uptake_layers_cm=None, uptake_bins=0):
+                 theta_cov_stride=0, uptake_layers_cm=None, uptake_bins=0, filter_smoother=None):
         corr = self._check_noise_correlation("EnsembleSimulation", noise_correlation, noise, filter_rejuvenation)
         if enkf_shard is not None and noise_field_settings(enkf_noise_field, 0.0) is not None:
             raise ValueError("enkf_shard and enkf_noise_field exclude each other: the exchanged partials cover psi only")
@@ -629,6 +659,9 @@ class EnsembleSimulation(_Run):
         if filter_shard is not None and period_ends is not None and len(period_ends):
             raise ValueError("period_ends and filter_shard exclude each other: the sharded filter routes the members' "
                              "columns, which do not carry the period accumulators")
+        if filter_shard is not None and filter_smoother_config(filter_smoother) is not None:
+            raise ValueError("filter_shard and filter_smoother exclude each other: the routed columns do not carry the "
+                             "smoother's ring")
         if filter_shard is not None and not int(filter_stride or 0):
             raise ValueError("filter_shard needs the particle filter (filter_stride > 0)")
         if filter_shard is not None and filter_soil_moisture is not None:
@@ -643,7 +676,8 @@ class EnsembleSimulation(_Run):
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
                            enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins, storage_layers_cm,
                            storage_bins, filter_ess_floor, filter_window_offsets, enkf_noise_field,
-                           filter_rejuvenation=filter_rejuvenation, theta_cov_stride=theta_cov_stride)
+                           filter_rejuvenation=filter_rejuvenation, theta_cov_stride=theta_cov_stride,
+                           filter_smoother=filter_smoother)
         self._start_periods(period_ends, period_thresholds_cm, period_bins, period_flux_max_cm)
         self._start_uptake(uptake_layers_cm, uptake_bins)
         self.enkf_shard = None
@@ -804,6 +838,13 @@ class EnsembleSimulation(_Run):
             if self.filter_window_offsets:               # what was recorded for the coming assimilation travels along
                 arrays["filter_window_offsets"] = np.asarray(self.filter_window_offsets, dtype=np.int64)
                 arrays["filter_window_index"], arrays["filter_window_rows"] = self.stepper.filter_window_capture()
+            if self.filter_smoother is not None:         # (a run without one keeps its key set) the tables and the ring
+                arrays["filter_smoother"] = np.asarray(self.filter_smoother, dtype=np.int64)
+                arrays["filter_smoother_hist"] = self.stepper.filter_smoother_hist()
+                arrays["filter_smoother_paths"] = self.stepper.filter_smoother_paths()
+                w, ids, rows, last = self.stepper.filter_smoother_ring()
+                arrays["filter_smoother_ring_w"], arrays["filter_smoother_ring_id"] = w, ids
+                arrays["filter_smoother_ring_rows"] = np.append(rows, last)       # ... and the last row stepped
         if self.enkf_stride:
             arrays["enkf_stride"] = np.array(self.enkf_stride, dtype=np.int64)
             arrays["enkf_sigma_cm"] = np.array(self.enkf_sigma_cm, dtype=np.float64)
@@ -908,6 +949,10 @@ class EnsembleSimulation(_Run):
         has_fwin = bool(filt) and "filter_window_offsets" in data
         if has_fwin:
             fkw.update(filter_window_offsets=tuple(int(o) for o in np.asarray(data["filter_window_offsets"]).reshape(-1)))
+        has_smo = bool(filt) and "filter_smoother" in data
+        if has_smo:
+            stride_k = [int(v) for v in np.asarray(data["filter_smoother"]).reshape(-1)]
+            fkw.update(filter_smoother={"stride": stride_k[0], "lag_rows": stride_k[0] * stride_k[1]})
         has_win = enkf and "enkf_window_offsets" in data
         if has_win:
             fkw.update(enkf_window_offsets=tuple(int(o) for o in np.asarray(data["enkf_window_offsets"]).reshape(-1)))
@@ -930,6 +975,13 @@ class EnsembleSimulation(_Run):
             if has_fwin:
                 sim.stepper.set_filter_window_capture(np.asarray(data["filter_window_index"], dtype=np.int32).reshape(-1, n),
                                                       np.asarray(data["filter_window_rows"], dtype=np.int64))
+            if has_smo:
+                sim.stepper.set_filter_smoother_hist(np.asarray(data["filter_smoother_hist"]))
+                sim.stepper.set_filter_smoother_paths(np.asarray(data["filter_smoother_paths"], dtype=np.int64))
+                rows = np.asarray(data["filter_smoother_ring_rows"], dtype=np.int64).reshape(-1)
+                sim.stepper.set_filter_smoother_ring(np.asarray(data["filter_smoother_ring_w"], dtype=np.int32).reshape(-1, n),
+                                                     np.asarray(data["filter_smoother_ring_id"], dtype=np.int64).reshape(-1, n),
+                                                     rows[:-1], int(rows[-1]))
         elif has_nz:
             sim.stepper.set_enkf_noise_base(np.asarray(data["enkf_noise_base"], dtype=np.float64).reshape(n, D))
         elif has_corr:
@@ -1061,7 +1113,7 @@ class SweepSimulation(_Run):
                  filter_soil_moisture=None, theta_hist_bins=0, storage_layers_cm=None, storage_bins=0, period_ends=None,
                  period_thresholds_cm=(), period_bins=0, period_flux_max_cm=(16.0, 4.0), filter_ess_floor=0.0,
                  filter_window_offsets=(), enkf_noise_field=None, filter_rejuvenation=0.0, noise_correlation=None,
-                 theta_cov_stride=0, uptake_layers_cm=None, uptake_bins=0):
+                 theta_cov_stride=0, uptake_layers_cm=None, uptake_bins=0, filter_smoother=None):
         corr = self._check_noise_correlation("SweepSimulation", noise_correlation, "philox", filter_rejuvenation)
         self.points = list(cols_list)
         self.P, self.n = len(self.points), int(n_members)
@@ -1094,7 +1146,8 @@ class SweepSimulation(_Run):
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
                            enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins, storage_layers_cm,
                            storage_bins, filter_ess_floor, filter_window_offsets, enkf_noise_field,
-                           filter_rejuvenation=filter_rejuvenation, theta_cov_stride=theta_cov_stride)
+                           filter_rejuvenation=filter_rejuvenation, theta_cov_stride=theta_cov_stride,
+                           filter_smoother=filter_smoother)
         self._start_periods(period_ends, period_thresholds_cm, period_bins, period_flux_max_cm)
         self._start_uptake(uptake_layers_cm, uptake_bins)
         self.next_row, self.kernel_ms, self.launches = 1, 0.0, 0

@@ -87,6 +87,7 @@ class EnsembleStepper:
         self.filter_ess_floor = 0.0
         self.filter_rejuvenation = 0.0
         self.filter_window_offsets = ()
+        self.filter_smoother = (0, 0)
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
         self.enkf_sm_nodes = None
         self.enkf_method, self.enkf_relaxation = "stochastic", 0.0
@@ -808,6 +809,7 @@ class EnsembleStepper:
         self.filter_ess_floor = 0.0                                              # ... and the tempering
         self.filter_rejuvenation = 0.0                                           # ... and the rejuvenation
         self.filter_window_offsets = ()                                          # ... and the window
+        self.filter_smoother = (0, 0)                                            # ... and the smoother
         L.check(self.lib.hc_set_filter(self.h, stride, sigma, int(seed) & 0xFFFFFFFFFFFFFFFF))
         self.filter_stride, self.filter_sigma_cm, self.filter_seed = stride, sigma, int(seed)
 
@@ -818,6 +820,7 @@ class EnsembleStepper:
         self.filter_ess_floor = 0.0
         self.filter_rejuvenation = 0.0
         self.filter_window_offsets = ()
+        self.filter_smoother = (0, 0)
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = 0, 0.0, 0.0, 0
         self.enkf_sm_nodes = None
         self.enkf_method, self.enkf_relaxation = "stochastic", 0.0
@@ -1063,6 +1066,76 @@ class EnsembleStepper:
         w, slots = np.zeros(1, dtype=np.int32), np.zeros(SM_MAX_SENSORS, dtype=np.int32)
         L.check(self.lib.hc_get_filter_window_width(self.h, L.iptr(w), L.iptr(slots)))
         return slots[:int(w[0])].copy()
+
+    # -- fixed-lag smoother of the water table by ancestry (include/hydrocol.h hc_set_filter_smoother) -------------------
+    def set_filter_smoother(self, stride, lag=0):
+        """Carry every slot's water-table index of each ``stride``-th forcing row (the record rows) through the filter's
+        resamplings and count it ``lag`` record rows later (0 <= lag <= 64): the distribution of that row given the
+        observations up to the later one -- the one table that describes the posterior.  ``stride`` 0 turns it off.  The
+        filter must be on (:meth:`set_filter` first; it removes the smoother again) and not sharded."""
+        stride, lag = filter_smoother_settings(stride, lag)
+        self.filter_smoother = (0, 0)
+        L.check(self.lib.hc_set_filter_smoother(self.h, stride, lag))
+        self.filter_smoother = (stride, lag)
+
+    def filter_smoother_layout(self):
+        """(stride, lag, n_srow) as the library holds them; zeros: off."""
+        s, k, n = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.int64)
+        L.check(self.lib.hc_get_filter_smoother_layout(self.h, L.iptr(s), L.iptr(k), L.lptr(n)))
+        return int(s[0]), int(k[0]), int(n[0])
+
+    def _smoother_rows(self):
+        """n_srow (off: 1, and the library refuses the call)"""
+        return stride_rows(self.T, self.filter_smoother[0]) if self.filter_smoother[0] else 1
+
+    def filter_smoother_hist(self):
+        """[P][n_srow][D] int32: the smoothed histograms (slot j <-> forcing row j stride; empty until emitted)."""
+        t = np.zeros((self.P, self._smoother_rows(), self.D), dtype=np.int32)
+        L.check(self.lib.hc_get_filter_smoother_hist(self.h, L.iptr(t), t.size))
+        return t
+
+    def set_filter_smoother_hist(self, table):
+        t = np.asarray(table)
+        if t.size and (t.min() < 0 or t.max() > INT32_MAX):
+            raise ValueError("histogram counts must lie in [0, 2^31 - 1]")
+        t = np.ascontiguousarray(t, dtype=np.int32).reshape(-1)
+        L.check(self.lib.hc_set_filter_smoother_hist_table(self.h, L.iptr(t), t.size))
+
+    def filter_smoother_paths(self):
+        """[P][n_srow][2] int64: (distinct paths behind the slot's histogram, the row it is conditioned on); (0, -1) until
+        emitted."""
+        t = np.zeros((self.P, self._smoother_rows(), 2), dtype=np.int64)
+        L.check(self.lib.hc_get_filter_smoother_paths(self.h, L.lptr(t), t.size))
+        return t
+
+    def set_filter_smoother_paths(self, table):
+        t = np.ascontiguousarray(table, dtype=np.int64).reshape(-1)
+        L.check(self.lib.hc_set_filter_smoother_paths(self.h, L.lptr(t), t.size))
+
+    def filter_smoother_ring(self):
+        """(w [K + 1][N] int32, id [K + 1][N] int64, rows [K + 1] int64, last row stepped): what the ring holds for the
+        coming emissions (row -1: nothing, the plane reads 0; checkpoints)."""
+        K1 = self.filter_smoother[1] + 1
+        w, ids = np.zeros((K1, self.N), dtype=np.int32), np.zeros((K1, self.N), dtype=np.int64)
+        rows, last = np.zeros(K1, dtype=np.int64), np.zeros(1, dtype=np.int64)
+        L.check(self.lib.hc_get_filter_smoother_ring(self.h, L.iptr(w), L.lptr(ids), L.lptr(rows), L.lptr(last)))
+        return w, ids, rows, int(last[0])
+
+    def set_filter_smoother_ring(self, w, ids, rows, last_row=-1):
+        K1 = self.filter_smoother[1] + 1
+        w = np.ascontiguousarray(w, dtype=np.int32)
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        if w.shape != (K1, self.N) or ids.shape != (K1, self.N) or rows.size != K1:
+            raise ValueError(f"the smoother's ring must be [{K1}, {self.N}] twice with as many rows")
+        L.check(self.lib.hc_set_filter_smoother_ring(self.h, L.iptr(w), L.lptr(ids), L.lptr(rows), int(last_row)))
+
+    def filter_smoother_flush(self):
+        """Emit every pending plane, conditioned on the last row stepped (the end of a run)."""
+        L.check(self.lib.hc_filter_smoother_flush(self.h))
+
+    def reset_filter_smoother(self):
+        L.check(self.lib.hc_reset_filter_smoother(self.h))
 
     # -- one point's members on several handles, particle filter (include/hydrocol.h hc_set_filter_shard) ----------------
     def filter_shard_words(self, bounds, index):
@@ -3143,6 +3216,118 @@ def filter_window_summary(table, stride, offsets, z0_cm=0.0):
     layout being the same -- ``prior_*`` the forecast ensemble's water-table depth on the lagged row, ``n_obs`` the lagged
     observations weighed, ``n_rows`` the assimilation rows that took any."""
     return enkf_window_summary(table, stride, offsets, z0_cm)
+
+
+# ---- fixed-lag smoother of the water table by ancestry (include/hydrocol.h hc_set_filter_smoother) ---------------------
+SMOOTHER_MAX_LAG = 64
+
+
+def filter_smoother_settings(stride, lag=0):
+    """(stride, lag) of :meth:`EnsembleStepper.set_filter_smoother`, checked: integers, stride >= 0, lag in [0, 64]
+    record rows."""
+    for name, v in (("stride", stride), ("lag", lag)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"the smoother's {name} must be an integer, got {v!r}")
+    stride, lag = int(stride), int(lag)
+    if stride < 0:
+        raise ValueError(f"the smoother's stride must be >= 0, got {stride}")
+    if stride and not 0 <= lag <= SMOOTHER_MAX_LAG:
+        raise ValueError(f"the smoother's lag must lie in [0, {SMOOTHER_MAX_LAG}] record rows, got {lag}")
+    return stride, (lag if stride else 0)
+
+
+def filter_smoother_config(cfg, who="filter_smoother"):
+    """``{"stride": s, "lag_rows": L}`` -> (s, K = L / s), checked (L a multiple of s, K <= 64); None or stride 0: None."""
+    if cfg is None:
+        return None
+    if not isinstance(cfg, dict) or set(cfg) - {"stride", "lag_rows"} or "stride" not in cfg:
+        raise ValueError(f"{who} must be {{'stride': s, 'lag_rows': L}}, got {cfg!r}")
+    stride, lag_rows = cfg["stride"], cfg.get("lag_rows", 0)
+    for name, v in (("stride", stride), ("lag_rows", lag_rows)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError(f"{who}: {name} must be an integer >= 0, got {v!r}")
+    stride, lag_rows = int(stride), int(lag_rows)
+    if stride == 0:
+        return None
+    if lag_rows % stride:
+        raise ValueError(f"{who}: lag_rows = {lag_rows} is not a multiple of the stride {stride}")
+    return filter_smoother_settings(stride, lag_rows // stride)
+
+
+def filter_smoother_of(w_rows, ancestors_by_row, stride, lag, members_per_point, D, wtd_obs, last_row):
+    """The smoother's tables restated in NumPy: store, gather, emit and flush of include/hydrocol.h
+    hc_set_filter_smoother, one row at a time (a launch ends on every assimilation row, so that is what the library's
+    order amounts to).  ``w_rows[r]`` [N] are the members' water-table indices of forcing row r (what ``want_wtd``
+    returns; read on record rows only), ``ancestors_by_row`` maps each row the filter resampled on to its ancestor table
+    [N], ``wtd_obs`` [T] is the forcing's, rows 1 ... ``last_row`` have been stepped.  The distinct paths are counted
+    with ``np.unique``, not by the neighbour rule the kernel relies on.  Returns ``hist`` [P][n_srow][D] int32 and
+    ``paths`` [P][n_srow][2] int64 before the flush, ``hist_flushed`` and ``paths_flushed`` after it, and the ring before
+    it: ``ring_w`` [K + 1][N] int32, ``ring_id`` [K + 1][N] int64, ``ring_rows`` [K + 1] (an empty plane reads 0)."""
+    s, K, Np, D = int(stride), int(lag), int(members_per_point), int(D)
+    obs = np.asarray(wtd_obs).reshape(-1)
+    T, last_row = obs.size, int(last_row)
+    N = int(np.asarray(w_rows[s]).size)                   # (the first record row)
+    P, n_srow = N // Np, (T - 1) // s + 1
+    hist = np.zeros((P, n_srow, D), dtype=np.int32)
+    paths = np.zeros((P, n_srow, 2), dtype=np.int64)
+    paths[..., 1] = -1
+    ring_w, ring_id = np.zeros((K + 1, N), dtype=np.int32), np.zeros((K + 1, N), dtype=np.int64)
+    ring_rows = np.full(K + 1, -1, dtype=np.int64)
+
+    def gather(anc):
+        anc = np.asarray(anc, dtype=np.int64)
+        for k in np.flatnonzero(ring_rows >= 0):
+            ring_w[k], ring_id[k] = ring_w[k][anc], ring_id[k][anc]
+
+    def emit(j, cond, hist, paths, rows):
+        k = j % (K + 1)
+        for p in range(P):
+            w, ids = ring_w[k, p * Np:(p + 1) * Np], ring_id[k, p * Np:(p + 1) * Np]
+            hist[p, j] += np.bincount(w[w < D], minlength=D).astype(np.int32)
+            paths[p, j] = (np.unique(ids).size, cond)
+        rows[k] = -1
+
+    for r in range(1, last_row + 1):
+        anc = ancestors_by_row.get(r)
+        if r % s:
+            if anc is not None:
+                gather(anc)
+            continue
+        j = r // s
+        k = j % (K + 1)
+        if obs[r] >= 0:
+            ring_w[k] = np.asarray(w_rows[r], dtype=np.int32)
+            ring_id[k] = np.arange(N, dtype=np.int64) % Np
+            ring_rows[k] = r
+        else:
+            ring_rows[k] = -1
+        if anc is not None:
+            gather(anc)
+        if j - K >= 1 and ring_rows[(j - K) % (K + 1)] >= 0:
+            emit(j - K, r, hist, paths, ring_rows)
+    live = (ring_rows >= 0)[:, None]
+    out = {"hist": hist.copy(), "paths": paths.copy(), "ring_w": np.where(live, ring_w, 0),
+           "ring_id": np.where(live, ring_id, 0), "ring_rows": ring_rows.copy()}
+    pending = ring_rows.copy()
+    for r in np.sort(pending[pending >= 0]):
+        emit(int(r) // s, max(last_row, int(r)), hist, paths, pending)
+    out["hist_flushed"], out["paths_flushed"] = hist, paths
+    return out
+
+
+def filter_smoother_summary(hist, paths, obs_idx, levels, dz, z, stride, device=0):
+    """The smoothed distributions from the tables ``hist`` [..., n_srow, D] and ``paths`` [..., n_srow, 2]
+    (:func:`wtd_distribution` on the histograms): its keys -- ``rows``, ``count``, ``quantile_idx``, ``quantile_cm``,
+    ``crps_cm``, ``crps_mean_cm``, ``levels`` -- and ``hist``, ``lag_rows`` [..., n_srow] (the conditioning row minus the
+    row: the lag the slot really got, -1 where nothing was emitted) and ``unique_paths`` [..., n_srow] (the distinct
+    paths behind the histogram: towards 1 it is one trajectory, not a distribution)."""
+    hist, paths = np.asarray(hist), np.asarray(paths)
+    out = wtd_distribution(hist, obs_idx, levels, dz, z, device=device, stride=stride)
+    emitted = paths[..., 1] >= 0
+    out["hist"] = hist
+    out["lag_rows"] = np.where(emitted, paths[..., 1] - out["rows"], -1).astype(np.int64)
+    out["unique_paths"] = np.where(emitted, paths[..., 0], 0).astype(np.int64)
+    return out
 
 
 # ---- the assimilation tables (include/hydrocol.h hc_get_<key>_stats / hc_set_<key>_stats) ------------------------------

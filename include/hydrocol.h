@@ -65,6 +65,10 @@
  *   hc_filter_rejuvenation_normals
  *                      <- (new) the ensemble conditioned on wtd_obs (src/simulation.py:582-612): a bootstrap particle filter,
  *                         and the log marginal likelihood of the well record per parameter point
+ *   hc_set_filter_smoother, hc_get_filter_smoother_layout, hc_get_filter_smoother_hist, hc_set_filter_smoother_hist_table,
+ *   hc_get/set_filter_smoother_paths, hc_get/set_filter_smoother_ring, hc_filter_smoother_flush, hc_reset_filter_smoother
+ *                      <- (new) wtd_est (src/simulation.py:612) of earlier rows given the later record: the filter's
+ *                         genealogy as a fixed-lag smoother, the one table that describes the posterior
  *   hc_set_enkf, hc_get/set_enkf_stats, hc_get_enkf_gain/y/eps
  *                      <- (new) the same conditioning by a stochastic ensemble Kalman filter on a continuous water table
  *   hc_set_enkf_soil_moisture, hc_get/set_enkf_sm_stats, hc_get_enkf_sm_width/y/gain/eps
@@ -893,6 +897,64 @@ int hc_set_filter_window_stats(hc_handle *h, const double *table, int64_t n_entr
 int hc_get_filter_window_capture(hc_handle *h, int32_t *b, int64_t *rows);
 int hc_set_filter_window_capture(hc_handle *h, const int32_t *b, const int64_t *rows);
 int hc_get_filter_window_width(hc_handle *h, int32_t *width, int32_t *slots);
+
+/* Fixed-lag smoother of the water table by ancestry (Kitagawa 1996): the filter's own genealogy.  Every slot carries the
+ * water-table indices of the member it descends from on the last K + 1 record rows; after a resampling the slots' values
+ * for a record row K record rows back are a sample of p(water table there | the observations up to the present row).
+ * This is the one table that describes the posterior: every other table of an assimilated run describes the forecast.
+ * No state is stored, no row is solved twice, nothing is assumed Gaussian, the step kernels are not involved; the
+ * quantity carried is the integer index wtd_out returns, so the tables are exact integers with the same bits at any
+ * launch length, point order or dealing of a sweep's points to handles or ranks.
+ *   Record rows: r >= 1 with r % stride == 0; n_srow = (n_forcing_rows - 1) / stride + 1, slot j <-> row j stride, slot 0
+ *   stays empty.  lag = K record rows, 0 <= K <= HC_SMOOTHER_MAX_LAG.  The stride is independent of the filter's.
+ *   The ring, per handle, K + 1 planes: ring_w uint16 [K + 1][N] (water-table indices), ring_id uint32 [K + 1][N] (the
+ *   member's index within its point when the plane was recorded) and ring_row int64 [K + 1] (the forcing row a plane
+ *   holds; -1: none).
+ *   After each launch of hc_step_rows (launches end on assimilation rows and nothing is resampled inside one, so this is
+ *   the same as processing the rows one by one), after every forecast table has accumulated and after the launch's
+ *   assimilation, over the launch's record rows R in ascending order, j = R / stride:
+ *     1. store: plane j mod (K + 1) takes b_m(R), the index wtd_out returns, and id = m - p N_p; its row becomes R.  If
+ *        wtd_obs[R] < 0 the row is skipped: the plane's row becomes -1 instead.
+ *     2. gather, if R is the launch's last row and the filter resampled on it: every plane with row >= 0, of both rings,
+ *        goes through the row's ancestor table (slot m takes the values of anc[m]).  An assimilation row that is not a
+ *        record row runs this step alone.
+ *     3. emit plane (j - K) mod (K + 1), if j - K >= 1 and its row >= 0: shist[p][j - K][b] += the members of p whose
+ *        plane value is b (a value >= D goes to no bin); spaths[p][j - K] = (distinct ids among the point's slots, R);
+ *        then the plane's row becomes -1.
+ *   K = 0 gives the analysis distribution of the row itself; K > 0 the distribution of row R - K stride conditioned on
+ *   the observations up to R.  With flat weights the table equals hc_set_wtd_hist's on those rows and every path count
+ *   is N_p.
+ *   Path degeneracy: far enough back every slot descends from one member.  spaths reports it, as the number of distinct
+ *   paths behind a row's histogram; towards 1 the histogram is one trajectory, not a distribution (take a shorter lag, or
+ *   hold the ESS up with hc_set_filter_tempering).
+ *   Tables: shist int32 [P][n_srow][D], at most HC_WTD_HIST_MAX_ENTRIES entries; spaths int64 [P][n_srow][2], (0, -1)
+ *   until emitted.  Both are re-created and the ring emptied when the points, the forcing row count or the depth change.
+ * hc_set_filter_smoother: stride 0 turns it off: nothing is then launched or allocated, and every bit is that of
+ *   hc_set_filter alone.  Needs the particle filter on (hc_set_filter first); HC_ERR_ARG for a lag outside
+ *   [0, HC_SMOOTHER_MAX_LAG], stride < 0, a table above the cap, while the EnKF is on and while hc_set_filter_shard is
+ *   set -- which is refused in turn while the smoother is set: the exchanged columns do not carry the ring.  Whatever
+ *   turns the filter off removes the smoother (hc_set_filter included).
+ * hc_get_filter_smoother_layout: stride, lag, n_srow (zeros: off).
+ * hc_get_filter_smoother_hist / hc_set_filter_smoother_hist_table, hc_get/set_filter_smoother_paths: the tables (P n_srow D
+ *   and P n_srow 2 entries; checkpoints, the assembly of a sweep over ranks).
+ * hc_get/set_filter_smoother_ring: w int32 [K + 1][N], id int64 [K + 1][N], rows [K + 1] and the last row stepped (what a
+ *   flush conditions on; -1: none): what a checkpoint between a store and its emission must carry.  A plane without a row
+ *   reads 0.  Indices lie in [0, 65535], ids in [0, N_p), a row is -1 or the record row of its plane (HC_ERR_ARG else).
+ * hc_filter_smoother_flush: emits every pending plane, in ascending row order, each with the conditioning row it reached
+ *   -- the last row stepped -- and empties it, so that further stepping counts nothing twice: spaths[..][1] - row is the
+ *   lag a slot really got.
+ * hc_reset_filter_smoother: the tables as created, the ring empty. */
+#define HC_SMOOTHER_MAX_LAG 64
+int hc_set_filter_smoother(hc_handle *h, int32_t stride, int32_t lag);
+int hc_get_filter_smoother_layout(hc_handle *h, int32_t *stride, int32_t *lag, int64_t *n_srow);
+int hc_get_filter_smoother_hist(hc_handle *h, int32_t *table, int64_t n_entries);
+int hc_set_filter_smoother_hist_table(hc_handle *h, const int32_t *table, int64_t n_entries);
+int hc_get_filter_smoother_paths(hc_handle *h, int64_t *table, int64_t n_entries);
+int hc_set_filter_smoother_paths(hc_handle *h, const int64_t *table, int64_t n_entries);
+int hc_get_filter_smoother_ring(hc_handle *h, int32_t *w, int64_t *id, int64_t *rows, int64_t *last_row);
+int hc_set_filter_smoother_ring(hc_handle *h, const int32_t *w, const int64_t *id, const int64_t *rows, int64_t last_row);
+int hc_filter_smoother_flush(hc_handle *h);
+int hc_reset_filter_smoother(hc_handle *h);
 
 /* Ensemble Kalman filter on the well's water table (stochastic EnKF: perturbed observations, Evensen 1994 / Burgers et al.
  * 1998).  It moves every member's psi by the sample covariance between psi and the observed quantity; noise is untouched.
