@@ -447,21 +447,9 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
         else:
             extra["initial_cond_members"] = np.array([lo, hi])
     # the optional tables are integer sums like the moments: one more exact all-reduce each
-    tables, crps_line = _reduce_optional(ranks, sim, [0], [cols], forcing, stride, dist_stride, dist_levels, device,
-                                         label, keep_points=False)
+    tables, lines = _reduce_diagnostics(ranks, sim, [0], [cols], forcing, stride, (dist_stride, dist_levels), theta, storage,
+                                        cov, periods, plan, uptake, ucells, device, label, keep_points=False)
     extra.update(tables)
-    ttables, theta_line = _reduce_theta(ranks, sim, [0], 1, forcing.dim_t, cols.dim_d, stride, theta, label,
-                                        keep_points=False)
-    extra.update(ttables)
-    stor_tables, storage_line = _reduce_storage(ranks, sim, [0], 1, forcing.dim_t, cols, stride, storage, label,
-                                                keep_points=False)
-    extra.update(stor_tables)
-    cov_tables, cov_line = _reduce_covariance(ranks, sim, [0], 1, forcing.dim_t, cols, stride, cov, label, keep_points=False)
-    extra.update(cov_tables)
-    ptables, period_line = _reduce_periods(ranks, sim, [0], 1, cols, forcing, periods, plan, label, keep_points=False)
-    extra.update(ptables)
-    utables, uptake_line = _reduce_uptake(ranks, sim, [0], 1, cols, uptake, ucells, plan, label, keep_points=False)
-    extra.update(utables)
     # the filters' tables describe the one point: every rank of a sharded run holds the same ones, and rank 0's are taken
     # (placed by it alone; a sum over the ranks would count them world times)
     eids = [0] if ranks.rank == 0 else []
@@ -479,8 +467,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     arrays = dict(moments=moments, wtd_mean_cm=mean_cm, wtd_std_cm=std_cm, rows=np.array(rows),
                   members=np.array(n_members), gpus=np.array(ranks.world), initial_cond=psi0, **extra)
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "ensemble water-table statistics", ranks)
-    _print_lines(crps_line, *assim_lines, smooth_line, theta_line, storage_line, cov_line, period_line, uptake_line,
-                 corr_line if ranks.rank == 0 else None)
+    _print_lines(lines.pop("crps"), *assim_lines, smooth_line, *lines.values(), corr_line if ranks.rank == 0 else None)
     sim.close()
 
 
@@ -541,6 +528,23 @@ def _placed_table(ranks, sim, ids, P, T, D, stride, key, n=0):
     shape = (stride_rows(T, stride),) + assim_table_shape(key, D, n, n)
     local = sim.assim_table(key).reshape((-1,) + shape) if sim is not None else np.zeros((0,) + shape)
     return place_points(local, ids, P, ranks)
+
+
+def _placed_diag(ranks, sim, ids, P, key, counts):
+    """The parts of the diagnostic table ``key`` (stepper.DIAG_TABLES) of the run's ``P`` points: this rank's handle ``sim``
+    (None: it holds no points, and gives the layout at P = 0 of ``counts``, stepper.diag_counts) gives its points ``ids``;
+    the [P]-leading parts are placed at them, the global words (overflow, outside count) go as they are, and the whole
+    is summed over the ranks as int64 -- one collective, an int32 histogram's outside count with it."""
+    import numpy as np
+    from .multigpu import place_points
+    from .stepper import DIAG_TABLES, diag_layout, diag_placed, join_diag, split_diag
+    if sim is not None:
+        parts = sim.stepper.diag_parts(key)
+    else:
+        none = dict(counts, P=0)
+        parts = split_diag(key, np.zeros(diag_layout(key, none)["words"][0], dtype=DIAG_TABLES[key].dtype), none)
+    parts.update((name, place_points(parts[name], ids, P)) for name in diag_placed(key))
+    return split_diag(key, ranks.allreduce_sum(join_diag(key, parts, wide=True)), dict(counts, P=P), wide=True)
 
 
 def _reduce_assimilation(ranks, sim, ids, P, T, cols, a, label, keep_points):
@@ -1707,26 +1711,19 @@ def _reduce_optional(ranks, sim, ids, cols_all, forcing, stride, dist_stride, di
     datasets (a sweep, ``keep_points``: with the leading [P] axis, at P = 1 too) and the closing CRPS line (rank 0, and
     only with histograms; None otherwise)."""
     import numpy as np
-    from .multigpu import place_points
-    from .stepper import (join_profile_table, profile_layout, profile_tables_to_stats, split_profile_table,
-                          wtd_distribution, wtd_hist_slots)
+    from .stepper import diag_counts, join_diag, profile_tables_to_stats, wtd_distribution
     P, T, D, ref = len(cols_all), forcing.dim_t, cols_all[0].dim_d, cols_all[0]
+    counts = diag_counts(P, T, D, profile_stride=stride, wtd_hist_stride=dist_stride)
     out, crps_line = {}, None
     if stride:
-        # the [P]-leading parts are placed at the points, the global overflow word is summed as it is
-        local = sim.profile_table() if sim is not None else np.zeros(profile_layout(0, T, D, stride)["words"][0], dtype=np.int64)
-        parts = split_profile_table(local, len(ids), T, D, stride)
-        table = ranks.allreduce_sum(join_profile_table({k: v if k == "ovf" else place_points(v, ids, P)
-                                                        for k, v in parts.items()}))
+        table = join_diag("profile", _placed_diag(ranks, sim, ids, P, "profile", counts))
         stats = profile_tables_to_stats(table, P, T, D, stride, np.stack([c.por_node for c in cols_all]), ref.dz)
         if keep_points and P == 1:
             stats = {k: (v[None] if isinstance(v, np.ndarray) and k != "rows" else v) for k, v in stats.items()}
         out.update(_profile_datasets(stats))
     if dist_stride:
         # int32 counts, summed as int64 like the moments; rank 0 forms the summary
-        local = (sim.stepper.wtd_hist_table() if sim is not None else
-                 np.zeros((0, wtd_hist_slots(T, dist_stride), D), dtype=np.int32))
-        hist = place_points(local, ids, P, ranks)
+        hist = _placed_diag(ranks, sim, ids, P, "wtd_hist", counts)["hist"]
         hist = hist if keep_points else hist[0]
         if ranks.rank == 0:
             dist = wtd_distribution(hist, forcing.wtd_obs, dist_levels, ref.dz, ref.z, device, dist_stride)
@@ -1740,17 +1737,12 @@ def _reduce_theta(ranks, sim, ids, P, T, D, stride, theta, label, keep_points):
     ``ids`` placed in the run's [P] table and summed over the ranks like the water-table histograms -- int32 counts as
     int64, the outside count with them -- then the quantile bands and the closing line (rank 0)."""
     import numpy as np
-    from .multigpu import place_points
-    from .stepper import stride_rows, theta_distribution
+    from .stepper import diag_counts, theta_distribution
     bins, levels = theta
     if not bins:
         return {}, None
-    local = (sim.stepper.theta_hist_table() if sim is not None else
-             np.zeros((0, stride_rows(T, stride), D, bins), dtype=np.int32))
-    hist = place_points(local, ids, P, ranks)
-    outside = int(ranks.allreduce_sum(np.array([sim.stepper.theta_hist_outside() if sim is not None else 0],
-                                               dtype=np.int64))[0])
-    hist = hist if keep_points else hist[0]
+    parts = _placed_diag(ranks, sim, ids, P, "theta_hist", diag_counts(P, T, D, profile_stride=stride, theta_bins=bins))
+    hist, outside = parts["hist"] if keep_points else parts["hist"][0], parts["outside"]
     if ranks.rank != 0:
         return {}, None
     dist = theta_distribution(hist, levels, bins, stride)
@@ -1772,25 +1764,17 @@ def _reduce_storage(ranks, sim, ids, P, T, cols, stride, storage, label, keep_po
     histograms -- the overflow and outside counts with them -- then mean, sigma, the quantile bands and the closing line
     (rank 0)."""
     import numpy as np
-    from .multigpu import place_points
-    from .stepper import (layer_storage_distribution, layer_storage_stats, layer_storage_table_layout,
-                          split_layer_storage_table, stride_rows)
+    from .stepper import diag_counts, join_diag, layer_storage_distribution, layer_storage_stats
     if storage is None:
         return {}, None
     layers, bins, levels = storage
     ranges = storage_ranges(storage, cols)
     L = len(ranges)
-    local = (sim.storage_table() if sim is not None else
-             np.zeros(layer_storage_table_layout(0, T, L, stride)["words"][0], dtype=np.int64))
-    parts = split_layer_storage_table(local, len(ids), T, L, stride)
-    table = ranks.allreduce_sum(np.concatenate([place_points(parts["stor"], ids, P).reshape(-1),
-                                                place_points(parts["scnt"], ids, P).reshape(-1), parts["ovf"]]))
+    counts = diag_counts(P, T, cols.dim_d, profile_stride=stride, storage_layers=L, storage_bins=bins)
+    table = join_diag("storage", _placed_diag(ranks, sim, ids, P, "storage", counts))
     if bins:
-        lhist = (sim.stepper.layer_storage_hist_table() if sim is not None else
-                 np.zeros((0, stride_rows(T, stride), L, bins), dtype=np.int32))
-        hist = place_points(lhist, ids, P, ranks)
-        outside = int(ranks.allreduce_sum(np.array([sim.stepper.layer_storage_outside() if sim is not None else 0],
-                                                   dtype=np.int64))[0])
+        parts = _placed_diag(ranks, sim, ids, P, "storage_hist", counts)
+        hist, outside = parts["hist"], parts["outside"]
     if ranks.rank != 0:
         return {}, None
     stats = layer_storage_stats(table, P, T, L, stride)
@@ -1820,16 +1804,13 @@ def _reduce_covariance(ranks, sim, ids, P, T, cols, stride, cov, label, keep_poi
     points ``ids`` placed in the run's [P] table and summed over the ranks like the profile table -- the outside count with
     it -- then the covariances, the correlations with the water table, the sensor gain and the closing line (rank 0)."""
     import numpy as np
-    from .multigpu import place_points
-    from .stepper import stride_rows, theta_cov_finish, theta_cov_shape, theta_sensor_gain
+    from .stepper import diag_counts, theta_cov_finish, theta_cov_shape, theta_sensor_gain
     if cov is None:
         return {}, None
     s, sigma = cov
-    n, _, W = theta_cov_shape(cols.dim_d, s)
-    local = (sim.stepper.theta_cov_table() if sim is not None else np.zeros((0, stride_rows(T, stride), W), dtype=np.int64))
-    table = place_points(local, ids, P, ranks)
-    outside = int(ranks.allreduce_sum(np.array([sim.stepper.theta_cov_outside() if sim is not None else 0],
-                                               dtype=np.int64))[0])
+    n = theta_cov_shape(cols.dim_d, s)[0]
+    parts = _placed_diag(ranks, sim, ids, P, "theta_cov", diag_counts(P, T, cols.dim_d, profile_stride=stride, cov_stride=s))
+    table, outside = parts["cov"], parts["outside"]
     if ranks.rank != 0:
         return {}, None
     table = table if keep_points else table[0]
@@ -1860,24 +1841,16 @@ def _reduce_periods(ranks, sim, ids, P, cols, forcing, periods, plan, label, kee
     storage tables -- the overflow and outside counts with them -- then the statistics, the quantiles and the closing line
     (rank 0)."""
     import numpy as np
-    from .multigpu import place_points
-    from .stepper import (flux_max_log2_of, period_totals_distribution, period_totals_stats, period_totals_table_layout,
-                          split_period_totals_table)
+    from .stepper import diag_counts, flux_max_log2_of, join_diag, period_totals_distribution, period_totals_stats
     if periods is None:
         return {}, None
     ends, nodes = plan
-    n_period, K, bins, D = len(ends), 4 + len(nodes), periods["bins"], cols.dim_d
-    local = (sim.period_table() if sim is not None else
-             np.zeros(period_totals_table_layout(0, n_period, K)["words"][0], dtype=np.int64))
-    parts = split_period_totals_table(local, len(ids), n_period, K)
-    table = ranks.allreduce_sum(np.concatenate([place_points(parts["pmom"], ids, P).reshape(-1),
-                                                place_points(parts["pcnt"], ids, P).reshape(-1), parts["ovf"]]))
+    n_period, K, bins = len(ends), 4 + len(nodes), periods["bins"]
+    counts = diag_counts(P, D=cols.dim_d, periods=n_period, thresholds=len(nodes), period_bins=bins)
+    table = join_diag("period", _placed_diag(ranks, sim, ids, P, "period", counts))
     if bins:
-        lf, lw = (sim.stepper.period_totals_hists() if sim is not None else
-                  (np.zeros((0, n_period, 2, bins), dtype=np.int32), np.zeros((0, n_period, 2, D), dtype=np.int32)))
-        hist_flux, hist_wtd = place_points(lf, ids, P, ranks), place_points(lw, ids, P, ranks)
-        outside = int(ranks.allreduce_sum(np.array([sim.stepper.period_totals_outside() if sim is not None else 0],
-                                                   dtype=np.int64))[0])
+        parts = _placed_diag(ranks, sim, ids, P, "period_hist", counts)
+        hist_flux, hist_wtd, outside = parts["flux"], parts["wtd"], parts["outside"]
     if ranks.rank != 0:
         return {}, None
     stats = period_totals_stats(table, P, ends, len(nodes), float(cols.z[0]), cols.dz, forcing.wtd_obs)
@@ -1919,23 +1892,17 @@ def _reduce_uptake(ranks, sim, ids, P, cols, uptake, cells, plan, label, keep_po
     the ranks like the period totals' -- the overflow and outside counts with them -- then the statistics, the profile,
     the quantiles and the closing line (rank 0)."""
     import numpy as np
-    from .multigpu import place_points
-    from .stepper import (root_uptake_distribution, root_uptake_profile, root_uptake_stats, root_uptake_table_layout,
-                          split_root_uptake_table)
+    from .stepper import diag_counts, join_diag, root_uptake_distribution, root_uptake_profile, root_uptake_stats
     if uptake is None:
         return {}, None
     ends = plan[0]
     n_period, L, bins, D = len(ends), len(cells), uptake["bins"], cols.dim_d
-    local = (sim.uptake_table() if sim is not None else
-             np.zeros(root_uptake_table_layout(0, n_period, L, D)["words"][0], dtype=np.int64))
-    parts = split_root_uptake_table(local, len(ids), n_period, L, D)
-    table = ranks.allreduce_sum(np.concatenate([place_points(parts[k], ids, P).reshape(-1) for k in ("umom", "ucnt", "uprof")]
-                                               + [parts["ovf"]]))
+    counts = diag_counts(P, D=D, periods=n_period, uptake_layers=L, uptake_bins=bins)
+    whole = _placed_diag(ranks, sim, ids, P, "uptake", counts)
+    table = join_diag("uptake", whole)
     if bins:
-        lh = sim.stepper.root_uptake_hist() if sim is not None else np.zeros((0, n_period, L, bins), dtype=np.int32)
-        hist = place_points(lh, ids, P, ranks)
-        outside = int(ranks.allreduce_sum(np.array([sim.stepper.root_uptake_outside() if sim is not None else 0],
-                                                   dtype=np.int64))[0])
+        parts = _placed_diag(ranks, sim, ids, P, "uptake_hist", counts)
+        hist, outside = parts["hist"], parts["outside"]
     if ranks.rank != 0:
         return {}, None
     stats = root_uptake_stats(table, P, ends, L, D)
@@ -1960,13 +1927,34 @@ def _reduce_uptake(ranks, sim, ids, P, cols, uptake, cells, plan, label, keep_po
                     "uptake_share_quantile": np.asarray(dist["share_quantile"], dtype=np.float64)})
     n = int((np.asarray(stats["count"]).reshape(-1, n_period) > 0).any(axis=0).sum())
     # the depth above which half of the run's uptake lies: the periods' (and points') limbs summed, then the quantile
-    whole = split_root_uptake_table(table, P, n_period, L, D)["uprof"].astype(object).sum(axis=(0, 1))
-    cum = np.cumsum(whole[:, 0] + whole[:, 1] * (1 << 20))
+    limbs = whole["uprof"].astype(object).sum(axis=(0, 1))
+    cum = np.cumsum(limbs[:, 0] + limbs[:, 1] * (1 << 20))
     median = float(cols.z[int(np.argmax(2 * cum >= cum[-1]))] + cols.dz) if int(cum[-1]) > 0 else float("nan")
     line = f" [{label}] uptake: {L} layers over {n} periods, median depth {median:g} cm"
     if stats["overflow"]:
         line += f" ({stats['overflow']} values clamped)"
     return out, line
+
+
+def _reduce_diagnostics(ranks, sim, ids, cols_all, forcing, stride, dist, theta, storage, cov, periods, plan, uptake, ucells,
+                        device, label, keep_points):
+    """Every diagnostic block of the run, reduced over the ranks in the one order both an ensemble and a sweep write their
+    datasets in (a later block's dataset replaces an earlier one of the same name).  Returns the datasets and
+    {block: closing line or None}, ``crps`` first, the others in the order their lines are printed."""
+    P, T, ref = len(cols_all), forcing.dim_t, cols_all[0]
+    reducers = (
+        ("crps", lambda: _reduce_optional(ranks, sim, ids, cols_all, forcing, stride, dist[0], dist[1], device, label,
+                                          keep_points)),
+        ("theta", lambda: _reduce_theta(ranks, sim, ids, P, T, ref.dim_d, stride, theta, label, keep_points)),
+        ("storage", lambda: _reduce_storage(ranks, sim, ids, P, T, ref, stride, storage, label, keep_points)),
+        ("covariance", lambda: _reduce_covariance(ranks, sim, ids, P, T, ref, stride, cov, label, keep_points)),
+        ("periods", lambda: _reduce_periods(ranks, sim, ids, P, ref, forcing, periods, plan, label, keep_points)),
+        ("uptake", lambda: _reduce_uptake(ranks, sim, ids, P, ref, uptake, ucells, plan, label, keep_points)))
+    out, lines = {}, {}
+    for block, reduce in reducers:
+        tables, lines[block] = reduce()
+        out.update(tables)
+    return out, lines
 
 
 def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride=0, dist_levels=None,
@@ -2011,19 +1999,9 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     arrays = dict(moments=moments, wtd_mean_cm=mean_cm, wtd_std_cm=std_cm, rows=np.array(rows),
                   members=np.array(n_members), points=np.array(P), gpus=np.array(ranks.world), initial_cond=psi0,
                   spinup_iterations=spin)
-    tables, crps_line = _reduce_optional(ranks, sim, mine, cols_all, forcing, stride, dist_stride, dist_levels, device,
-                                         label, keep_points=True)
+    tables, lines = _reduce_diagnostics(ranks, sim, mine, cols_all, forcing, stride, (dist_stride, dist_levels), theta, storage,
+                                        cov, periods, plan, uptake, ucells, device, label, keep_points=True)
     arrays.update(tables)
-    ttables, theta_line = _reduce_theta(ranks, sim, mine, P, T, ref.dim_d, stride, theta, label, keep_points=True)
-    arrays.update(ttables)
-    stor_tables, storage_line = _reduce_storage(ranks, sim, mine, P, T, ref, stride, storage, label, keep_points=True)
-    arrays.update(stor_tables)
-    cov_tables, cov_line = _reduce_covariance(ranks, sim, mine, P, T, ref, stride, cov, label, keep_points=True)
-    arrays.update(cov_tables)
-    ptables, period_line = _reduce_periods(ranks, sim, mine, P, ref, forcing, periods, plan, label, keep_points=True)
-    arrays.update(ptables)
-    utables, uptake_line = _reduce_uptake(ranks, sim, mine, P, ref, uptake, ucells, plan, label, keep_points=True)
-    arrays.update(utables)
     atables, assim_lines = _reduce_assimilation(ranks, sim, mine, P, T, ref, assim, label, keep_points=True)
     arrays.update(atables)
     stables, smooth_line = _reduce_smoother(ranks, sim, mine, P, T, ref, forcing, assim.smoother, device, label,
@@ -2034,8 +2012,7 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     if sim is not None:
         sim.close()
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "sweep's water-table statistics", ranks)
-    _print_lines(crps_line, *assim_lines, smooth_line, theta_line, storage_line, cov_line, period_line, uptake_line,
-                 corr_line if ranks.rank == 0 else None)
+    _print_lines(lines.pop("crps"), *assim_lines, smooth_line, *lines.values(), corr_line if ranks.rank == 0 else None)
 
 
 def run_cli(argv=None):

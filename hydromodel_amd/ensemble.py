@@ -12,6 +12,7 @@ from .digest import inverse_retention
 from .stepper import enkf_noise_summary, noise_field_settings
 from .stepper import theta_cov_finish, theta_sensor_gain
 from .stepper import noise_correlation_breaks, noise_correlation_settings, noise_correlation_tables
+from .stepper import DIAG_TABLES, diag_checkpoint, diag_from_checkpoint
 from .stepper import (ASSIM_TABLES, ENKF_METHODS, EnsembleStepper, enkf_sm_summary, enkf_summary,
                       enkf_window_settings, enkf_window_summary, filter_sm_summary, filter_summary,
                       filter_smoother_config, filter_smoother_summary, filter_window_settings, filter_window_summary,
@@ -307,6 +308,16 @@ class _Run:
               "enkf_sm": self.enkf_soil_moisture is not None, "enkf_window": bool(self.enkf_window_offsets),
               "enkf_noise": self.enkf_noise_relaxation is not None}
         return [key for key in ASSIM_TABLES if on[key]]
+
+    def diag_tables_on(self):
+        """The keys of stepper.DIAG_TABLES this run keeps, in the registry's order: what a checkpoint carries and installs."""
+        periods, uptake = self.period_ends is not None, self.uptake_cells is not None
+        on = {"profile": bool(self.profile_stride), "theta_hist": bool(self.theta_hist_bins),
+              "storage": self.storage_ranges is not None, "storage_hist": bool(self.storage_bins),
+              "theta_cov": bool(self.theta_cov_stride), "period": periods, "period_acc": periods,
+              "period_hist": bool(self.period_bins), "uptake": uptake, "uptake_acc": uptake,
+              "uptake_hist": bool(self.uptake_bins), "wtd_hist": bool(self.wtd_hist_stride)}
+        return [key for key in DIAG_TABLES if on[key]]
 
     def enkf_noise_table(self):
         """[n_arow][4 D + 1] float64 (include/hydrocol.h hc_set_enkf_noise_field); a sweep: [P][n_arow][4 D + 1]."""
@@ -782,47 +793,25 @@ class EnsembleSimulation(_Run):
                       seed=np.array(self.seed, dtype=np.uint64), member_offset=np.array(self.member_offset, dtype=np.int64),
                       n_members=np.array(self.n_members, dtype=np.int64), dim_d=np.array(self.cols.dim_d, dtype=np.int64),
                       dim_t=np.array(self.forcing.dim_t, dtype=np.int64), initial_cond=np.asarray(self.psi0, dtype=float))
-        if self.profile_stride:
-            arrays["profile_stride"] = np.array(self.profile_stride, dtype=np.int64)
-            arrays["profile_table"] = self.stepper.profile_table()
-        if self.theta_hist_bins:
-            arrays["theta_hist_bins"] = np.array(self.theta_hist_bins, dtype=np.int64)
-            arrays["theta_hist"] = self.stepper.theta_hist_table()
-            arrays["theta_hist_outside"] = np.array(self.stepper.theta_hist_outside(), dtype=np.uint64)
+        # the diagnostics' settings, from which restore builds the run; their tables follow below, from the registry
+        for k in ("profile_stride", "theta_hist_bins", "theta_cov_stride", "wtd_hist_stride"):
+            if getattr(self, k):
+                arrays[k] = np.array(getattr(self, k), dtype=np.int64)
         if self.storage_ranges is not None:
             arrays["storage_layers_cm"] = self.storage_layers_cm
             arrays["storage_bins"] = np.array(self.storage_bins, dtype=np.int64)
-            arrays["storage_table"] = self.stepper.layer_storage_table()
-            if self.storage_bins:
-                arrays["storage_hist"] = self.stepper.layer_storage_hist_table()
-                arrays["storage_hist_outside"] = np.array(self.stepper.layer_storage_outside(), dtype=np.uint64)
-        if self.theta_cov_stride:
-            arrays["theta_cov_stride"] = np.array(self.theta_cov_stride, dtype=np.int64)
-            arrays["theta_cov_table"] = self.stepper.theta_cov_table()
-            arrays["theta_cov_outside"] = np.array(self.stepper.theta_cov_outside(), dtype=np.uint64)
         if self.period_ends is not None:
-            # the members' accumulators travel too: a restore in the middle of a period continues it
             arrays["period_ends"] = self.period_ends
             arrays["period_thresholds_cm"] = self.period_thresholds_cm
             arrays["period_bins"] = np.array(self.period_bins, dtype=np.int64)
-            arrays["period_table"] = self.stepper.period_totals_table()
-            arrays["period_acc"] = self.stepper.period_totals_acc()
             if self.period_bins:
                 arrays["period_flux_max_cm"] = np.asarray(self.period_flux_max_cm, dtype=np.float64)
-                arrays["period_hist"] = self.stepper.period_totals_hist_raw()[:-2]
-                arrays["period_hist_outside"] = np.array(self.stepper.period_totals_outside(), dtype=np.uint64)
         if self.uptake_cells is not None:
-            # ... and so do the root uptake's
             arrays["uptake_layers_cm"] = self.uptake_layers_cm
             arrays["uptake_bins"] = np.array(self.uptake_bins, dtype=np.int64)
-            arrays["uptake_table"] = self.stepper.root_uptake_table()
-            arrays["uptake_acc"] = self.stepper.root_uptake_acc()
-            if self.uptake_bins:
-                arrays["uptake_hist"] = self.stepper.root_uptake_hist_raw()[:-2]
-                arrays["uptake_hist_outside"] = np.array(self.stepper.root_uptake_outside(), dtype=np.uint64)
-        if self.wtd_hist_stride:
-            arrays["wtd_hist_stride"] = np.array(self.wtd_hist_stride, dtype=np.int64)
-            arrays["wtd_hist"] = self.stepper.wtd_hist_table()
+        # (the members' accumulators of the periods and the uptake are among them: a restore inside a period continues it)
+        for key in self.diag_tables_on():
+            arrays.update(diag_checkpoint(key, self.stepper.diag_raw(key), self.stepper.diag_counts()))
         if self.filter_stride:
             # the base vectors carry the damping and the ancestry of a filtered run (noise_scale no longer follows it)
             arrays["filter_stride"] = np.array(self.filter_stride, dtype=np.int64)
@@ -896,30 +885,25 @@ class EnsembleSimulation(_Run):
             raise ValueError(f" EnsembleSimulation: checkpoint of a [{D}]-node column over {T} rows does not fit "
                              f"this run ([{cols.dim_d}], {forcing.dim_t}).")
         psi = np.asarray(data["psi"], dtype=float).reshape(n, D)
-        stride = int(data["profile_stride"]) if "profile_stride" in data else 0
-        hist_stride = int(data["wtd_hist_stride"]) if "wtd_hist_stride" in data else 0
-        theta_bins = int(data["theta_hist_bins"]) if "theta_hist_bins" in data else 0
-        cov_stride = int(data["theta_cov_stride"]) if "theta_cov_stride" in data else 0
-        storage = "storage_layers_cm" in data
-        if storage:
-            fkw_storage = dict(storage_layers_cm=np.asarray(data["storage_layers_cm"], dtype=np.float64).reshape(-1, 2),
-                               storage_bins=int(data["storage_bins"]))
+        # the settings the constructor takes; which tables it then keeps says which are installed (diag_tables_on)
+        fkw = {k: int(data[k]) for k in ("profile_stride", "wtd_hist_stride", "theta_hist_bins", "theta_cov_stride") if k in data}
+        if "storage_layers_cm" in data:
+            fkw.update(storage_layers_cm=np.asarray(data["storage_layers_cm"], dtype=np.float64).reshape(-1, 2),
+                       storage_bins=int(data["storage_bins"]))
         filt = int(data["filter_stride"]) if "filter_stride" in data else 0
-        fkw = dict(filter_stride=filt, filter_sigma_cm=float(data["filter_sigma_cm"]),
-                   filter_seed=int(data["filter_seed"])) if filt else {}
+        if filt:
+            fkw.update(filter_stride=filt, filter_sigma_cm=float(data["filter_sigma_cm"]), filter_seed=int(data["filter_seed"]))
         if filt and "filter_ess_floor" in data:
             fkw.update(filter_ess_floor=float(data["filter_ess_floor"]))
         if filt and "filter_rejuvenation" in data:
             fkw.update(filter_rejuvenation=float(data["filter_rejuvenation"]))
-        periods = "period_ends" in data
-        if periods:
+        if "period_ends" in data:
             fkw.update(period_ends=np.asarray(data["period_ends"], dtype=np.int64).reshape(-1),
                        period_thresholds_cm=np.asarray(data["period_thresholds_cm"], dtype=np.float64).reshape(-1),
                        period_bins=int(data["period_bins"]))
             if int(data["period_bins"]):
                 fkw.update(period_flux_max_cm=tuple(np.asarray(data["period_flux_max_cm"], dtype=np.float64).reshape(-1)))
-        uptake = "uptake_layers_cm" in data
-        if uptake:
+        if "uptake_layers_cm" in data:
             fkw.update(uptake_layers_cm=np.asarray(data["uptake_layers_cm"], dtype=np.float64).reshape(-1, 2),
                        uptake_bins=int(data["uptake_bins"]))
         enkf = int(data["enkf_stride"]) if "enkf_stride" in data else 0
@@ -961,9 +945,7 @@ class EnsembleSimulation(_Run):
             fkw.update(noise_correlation={"length_cm": float(data["noise_correlation_length_cm"]),
                                           "layers": bool(int(data["noise_correlation_layers"]))})
         sim = cls(cols, forcing, n, seed=int(data["seed"]), device=device, member_offset=int(data["member_offset"]),
-                  psi0=np.asarray(data["initial_cond"], dtype=float).reshape(-1)[:D], flags=flags, profile_stride=stride,
-                  wtd_hist_stride=hist_stride, theta_hist_bins=theta_bins, theta_cov_stride=cov_stride,
-                  **(fkw_storage if storage else {}), **fkw)
+                  psi0=np.asarray(data["initial_cond"], dtype=float).reshape(-1)[:D], flags=flags, **fkw)
         if has_corr and not (np.array_equal(np.asarray(data["noise_correlation_a"]).reshape(-1), sim.noise_correlation_a)
                              and np.array_equal(np.asarray(data["noise_correlation_b"]).reshape(-1), sim.noise_correlation_b)):
             raise ValueError(f" EnsembleSimulation: {path} holds the noise correlation's tables of another column.")
@@ -992,30 +974,8 @@ class EnsembleSimulation(_Run):
             sim.stepper.set_enkf_window_capture(np.asarray(data["enkf_window_y"], dtype=np.float64).reshape(-1, n),
                                                 np.asarray(data["enkf_window_rows"], dtype=np.int64))
         sim.stepper.set_moments(np.asarray(data["moments"], dtype=np.int64))
-        if stride:
-            sim.stepper.set_profile_table(np.asarray(data["profile_table"], dtype=np.int64))
-        if theta_bins:
-            sim.stepper.set_theta_hist_table(np.asarray(data["theta_hist"]), int(data["theta_hist_outside"]))
-        if storage:
-            sim.stepper.set_layer_storage_table(np.asarray(data["storage_table"], dtype=np.int64))
-            if sim.storage_bins:
-                sim.stepper.set_layer_storage_hist_table(np.asarray(data["storage_hist"]), int(data["storage_hist_outside"]))
-        if cov_stride:
-            sim.stepper.set_theta_cov_table(np.asarray(data["theta_cov_table"], dtype=np.int64),
-                                            int(data["theta_cov_outside"]))
-        if periods:
-            sim.stepper.set_period_totals_table(np.asarray(data["period_table"], dtype=np.int64))
-            sim.stepper.set_period_totals_acc(np.asarray(data["period_acc"], dtype=np.int64))
-            if sim.period_bins:
-                hf, hw = np.split(np.asarray(data["period_hist"]).reshape(-1), [len(sim.period_ends) * 2 * sim.period_bins])
-                sim.stepper.set_period_totals_hists(hf, hw, int(data["period_hist_outside"]))
-        if uptake:
-            sim.stepper.set_root_uptake_table(np.asarray(data["uptake_table"], dtype=np.int64))
-            sim.stepper.set_root_uptake_acc(np.asarray(data["uptake_acc"], dtype=np.int64))
-            if sim.uptake_bins:
-                sim.stepper.set_root_uptake_hist(np.asarray(data["uptake_hist"]), int(data["uptake_hist_outside"]))
-        if hist_stride:
-            sim.stepper.set_wtd_hist_table(np.asarray(data["wtd_hist"]))
+        for key in sim.diag_tables_on():                  # the diagnostics the constructor turned on, in the registry's order
+            sim.stepper.set_diag_raw(key, diag_from_checkpoint(key, data))
         sim.next_row = int(data["next_row"])
         return sim
 

@@ -4,6 +4,7 @@ Mirrors what ``Simulation.run`` does per row (``/root/reference/code/src/simulat
 for N ensemble members at once; see include/hydrocol.h for the entry points.
 """
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 
@@ -317,6 +318,63 @@ class EnsembleStepper:
     def reset_moments(self):
         L.check(self.lib.hc_reset_moments(self.h))
 
+    # -- the diagnostic tables (DIAG_TABLES below): one path for every accumulated table of the handle ---------------
+    def diag_counts(self):
+        """The counts the handle's diagnostic tables are shaped by (:func:`diag_counts`), from its settings."""
+        return diag_counts(self.P, self.T, self.D, self.N, self.profile_stride, self.wtd_hist_stride, self.theta_hist_bins,
+                           len(self.storage_ranges), self.storage_bins, self.theta_cov_stride, len(self.period_ends),
+                           len(self.period_threshold_nodes), self.period_bins, len(self.uptake_cells), self.uptake_bins)
+
+    def diag_words(self, key):
+        """Elements of the raw table ``key`` of DIAG_TABLES, trailing words included: the library's count where it has
+        an entry point for it, else the layout's."""
+        name = f"hc_get_{DIAG_TABLES[key].stem}_words"
+        if name not in L.EXPORTS:
+            return diag_layout(key, self.diag_counts())["words"][0]
+        n = C.c_int64()
+        L.check(getattr(self.lib, name)(self.h, C.byref(n)))
+        return int(n.value)
+
+    def diag_raw(self, key):
+        """The raw device table ``key`` as the library hands it out: flat, the entry's element type, its trailing words
+        (overflow, outside count) included."""
+        e = DIAG_TABLES[key]
+        t = np.zeros(self.diag_words(key), dtype=e.dtype)
+        L.check(getattr(self.lib, "hc_get_" + e.stem)(self.h, _diag_ptr(t), t.size))
+        return t
+
+    def set_diag_raw(self, key, raw):
+        """Install a raw table (a checkpoint's, a sum over handles): flattened, made contiguous and checked here for every
+        entry -- int32 counts in [0, 2^31 - 1], the outside count in its carrier's range; the library checks the size."""
+        t = pack_diag(key, *unpack_diag(key, raw))
+        L.check(getattr(self.lib, DIAG_TABLES[key].set)(self.h, _diag_ptr(t), t.size))
+
+    def diag_parts(self, key):
+        """{part: shaped array} of the table ``key`` (:func:`split_diag`), with ``outside`` as an integer where the entry
+        carries an outside count; the overflow word of an int64 table is its part ``ovf`` [1]."""
+        return split_diag(key, self.diag_raw(key), self.diag_counts())
+
+    def set_diag_parts(self, key, parts):
+        """Install the table from its parts (:func:`join_diag`; ``outside`` defaults to 0), checked as :meth:`set_diag_raw`."""
+        self.set_diag_raw(key, join_diag(key, parts))
+
+    def export_diag(self, key, device_ptr):
+        """Copy the raw table device-to-device to ``device_ptr`` (``diag_words(key)`` elements on this handle's device)."""
+        name = "hc_export_" + DIAG_TABLES[key].stem
+        if name not in L.EXPORTS:
+            raise ValueError(f"the table {key!r} has no device-to-device export")
+        L.check(getattr(self.lib, name)(self.h, C.c_void_p(int(device_ptr)), self.diag_words(key)))
+
+    def reset_diag(self, key):
+        """Zero the table ``key`` -- and, where its family has one reset for all its tables, the others with it."""
+        L.check(getattr(self.lib, DIAG_TABLES[key].reset)(self.h))
+
+    def _diag_counter(self, name):
+        """A trailing count read on its own (``hc_get_*_outside`` / ``hc_get_*_overflow``)."""
+        out = C.c_uint64()
+        L.check(getattr(self.lib, name)(self.h, C.byref(out)))
+        return int(out.value)
+
     # -- ensemble profile statistics (include/hydrocol.h hc_set_profile_stats) ---------------------------------------
     def set_profile_stats(self, stride):
         """Accumulate psi / theta of every ``stride``-th forcing row and the fluxes of every solved row (0 = off).  Row 0 is
@@ -334,31 +392,17 @@ class EnsembleStepper:
         L.check(self.lib.hc_profile_snapshot(self.h, int(row)))
 
     def profile_words(self):
-        n = C.c_int64()
-        L.check(self.lib.hc_get_profile_stats_words(self.h, C.byref(n)))
-        return int(n.value)
+        return self.diag_words("profile")
 
     def profile_table(self):
         """The raw int64 table (layout: :func:`profile_layout`)."""
-        t = np.zeros(self.profile_words(), dtype=np.int64)
-        L.check(self.lib.hc_get_profile_stats(self.h, L.lptr(t), t.size))
-        return t
+        return self.diag_raw("profile")
 
     def set_profile_table(self, table):
-        t = np.ascontiguousarray(table, dtype=np.int64).reshape(-1)
-        L.check(self.lib.hc_set_profile_stats_tables(self.h, L.lptr(t), t.size))
-
-    def export_profile_stats(self, device_ptr):
-        """Copy the table device-to-device to ``device_ptr`` (``profile_words()`` int64 on this handle's device)."""
-        L.check(self.lib.hc_export_profile_stats(self.h, C.c_void_p(int(device_ptr)), self.profile_words()))
-
-    def reset_profile_stats(self):
-        L.check(self.lib.hc_reset_profile_stats(self.h))
+        self.set_diag_raw("profile", table)
 
     def profile_overflow(self):
-        out = C.c_uint64()
-        L.check(self.lib.hc_get_profile_overflow(self.h, C.byref(out)))
-        return int(out.value)
+        return self._diag_counter("hc_get_profile_overflow")
 
     def profile_stats(self, table=None):
         """Mean / sigma arrays of ``profile_table()`` (or of ``table``, e.g. summed over ranks): :func:`profile_tables_to_stats`."""
@@ -378,19 +422,10 @@ class EnsembleStepper:
 
     def wtd_hist_table(self):
         """[P][n_hrow][D] int32 (slot j <-> forcing row j stride: :func:`wtd_hist_rows`)."""
-        t = np.zeros((self.P, wtd_hist_slots(self.T, self.wtd_hist_stride), self.D), dtype=np.int32)
-        L.check(self.lib.hc_get_wtd_hist(self.h, L.iptr(t), t.size))
-        return t
+        return self.diag_parts("wtd_hist")["hist"]
 
     def set_wtd_hist_table(self, table):
-        t = np.asarray(table)
-        if t.size and (t.min() < 0 or t.max() > INT32_MAX):
-            raise ValueError("histogram counts must lie in [0, 2^31 - 1]")
-        t = np.ascontiguousarray(t, dtype=np.int32).reshape(-1)
-        L.check(self.lib.hc_set_wtd_hist_table(self.h, L.iptr(t), t.size))
-
-    def reset_wtd_hist(self):
-        L.check(self.lib.hc_reset_wtd_hist(self.h))
+        self.set_diag_parts("wtd_hist", {"hist": table})
 
     # -- ensemble soil-moisture histograms (include/hydrocol.h hc_set_theta_hist) ---------------------------------------
     def set_theta_hist(self, bins):
@@ -402,34 +437,20 @@ class EnsembleStepper:
         L.check(self.lib.hc_set_theta_hist(self.h, bins))
         self.theta_hist_bins = bins
 
-    def _theta_hist_raw(self):
-        t = np.zeros(self.P * stride_rows(self.T, self.profile_stride) * self.D * self.theta_hist_bins + 2, dtype=np.int32)
-        L.check(self.lib.hc_get_theta_hist(self.h, L.iptr(t), t.size))
-        return t
-
     def theta_hist_table(self):
         """[P][n_prow][D][B] int32: members of each point per bin of theta, node and profile row (:func:`theta_hist_of`)."""
-        return self._theta_hist_raw()[:-2].reshape(self.P, -1, self.D, self.theta_hist_bins)
+        return self.diag_parts("theta_hist")["hist"]
 
     def set_theta_hist_table(self, table, outside=0):
         """Install a table (a checkpoint's, a sum over handles) and the outside count that goes with it."""
-        t = np.asarray(table)
-        if t.size and (t.min() < 0 or t.max() > INT32_MAX):
-            raise ValueError("histogram counts must lie in [0, 2^31 - 1]")
-        if not 0 <= int(outside) < 1 << 64:
-            raise ValueError("the outside count must lie in [0, 2^64)")
-        tail = np.array([int(outside)], dtype=np.uint64).view(np.int32)
-        t = np.concatenate([np.ascontiguousarray(t, dtype=np.int32).reshape(-1), tail])
-        L.check(self.lib.hc_set_theta_hist_table(self.h, L.iptr(t), t.size))
+        self.set_diag_parts("theta_hist", {"hist": table, "outside": outside})
 
     def reset_theta_hist(self):
-        L.check(self.lib.hc_reset_theta_hist(self.h))
+        self.reset_diag("theta_hist")
 
     def theta_hist_outside(self):
         """Members' values that fell in no bin (theta NaN, below 0 or above 1) since the table was made."""
-        out = C.c_uint64()
-        L.check(self.lib.hc_get_theta_hist_outside(self.h, C.byref(out)))
-        return int(out.value)
+        return self._diag_counter("hc_get_theta_hist_outside")
 
     # -- ensemble soil-water storage by depth layer (include/hydrocol.h hc_set_layer_storage) ---------------------------
     def set_layer_storage(self, ranges, bins=0):
@@ -453,58 +474,32 @@ class EnsembleStepper:
         return r[:n.value].copy(), int(b.value)
 
     def layer_storage_words(self):
-        n = C.c_int64()
-        L.check(self.lib.hc_get_layer_storage_words(self.h, C.byref(n)))
-        return int(n.value)
+        return self.diag_words("storage")
 
     def layer_storage_table(self):
         """The raw int64 moments table (layout: :func:`layer_storage_table_layout`)."""
-        t = np.zeros(self.layer_storage_words(), dtype=np.int64)
-        L.check(self.lib.hc_get_layer_storage(self.h, L.lptr(t), t.size))
-        return t
+        return self.diag_raw("storage")
 
     def set_layer_storage_table(self, table):
-        t = np.ascontiguousarray(table, dtype=np.int64).reshape(-1)
-        L.check(self.lib.hc_set_layer_storage_tables(self.h, L.lptr(t), t.size))
-
-    def export_layer_storage(self, device_ptr):
-        """Copy the moments table device-to-device to ``device_ptr`` (``layer_storage_words()`` int64 on this device)."""
-        L.check(self.lib.hc_export_layer_storage(self.h, C.c_void_p(int(device_ptr)), self.layer_storage_words()))
-
-    def _layer_storage_hist_raw(self):
-        n = self.P * stride_rows(self.T, self.profile_stride) * len(self.storage_ranges) * self.storage_bins
-        t = np.zeros(n + 2, dtype=np.int32)
-        L.check(self.lib.hc_get_layer_storage_hist(self.h, L.iptr(t), t.size))
-        return t
+        self.set_diag_raw("storage", table)
 
     def layer_storage_hist_table(self):
         """[P][n_prow][L][B] int32: members of each point per bin of the layer's mean theta and profile row."""
-        return self._layer_storage_hist_raw()[:-2].reshape(self.P, -1, len(self.storage_ranges), self.storage_bins)
+        return self.diag_parts("storage_hist")["hist"]
 
     def set_layer_storage_hist_table(self, table, outside=0):
         """Install a histogram table (a checkpoint's, a sum over handles) and the outside count that goes with it."""
-        t = np.asarray(table)
-        if t.size and (t.min() < 0 or t.max() > INT32_MAX):
-            raise ValueError("histogram counts must lie in [0, 2^31 - 1]")
-        if not 0 <= int(outside) < 1 << 64:
-            raise ValueError("the outside count must lie in [0, 2^64)")
-        tail = np.array([int(outside)], dtype=np.uint64).view(np.int32)
-        t = np.concatenate([np.ascontiguousarray(t, dtype=np.int32).reshape(-1), tail])
-        L.check(self.lib.hc_set_layer_storage_hist_table(self.h, L.iptr(t), t.size))
+        self.set_diag_parts("storage_hist", {"hist": table, "outside": outside})
 
     def reset_layer_storage(self):
-        L.check(self.lib.hc_reset_layer_storage(self.h))
+        self.reset_diag("storage")
 
     def layer_storage_outside(self):
         """Members' layer means that fell in no bin (NaN, below 0 or above 1) since the tables were made."""
-        out = C.c_uint64()
-        L.check(self.lib.hc_get_layer_storage_outside(self.h, C.byref(out)))
-        return int(out.value)
+        return self._diag_counter("hc_get_layer_storage_outside")
 
     def layer_storage_overflow(self):
-        out = C.c_uint64()
-        L.check(self.lib.hc_get_layer_storage_overflow(self.h, C.byref(out)))
-        return int(out.value)
+        return self._diag_counter("hc_get_layer_storage_overflow")
 
     def layer_storage_stats(self, table=None):
         """Mean / sigma [cm] of ``layer_storage_table()`` (or of ``table``, e.g. summed over ranks): :func:`layer_storage_stats`."""
@@ -530,38 +525,22 @@ class EnsembleStepper:
         return int(s.value), int(n.value), int(w.value)
 
     def theta_cov_words(self):
-        n = C.c_int64()
-        L.check(self.lib.hc_get_theta_cov_words(self.h, C.byref(n)))
-        return int(n.value)
-
-    def _theta_cov_raw(self):
-        t = np.zeros(self.theta_cov_words(), dtype=np.int64)
-        L.check(self.lib.hc_get_theta_cov(self.h, L.lptr(t), t.size))
-        return t
+        return self.diag_words("theta_cov")
 
     def theta_cov_table(self):
         """[P][n_prow][W] int64: count, S1 [E], S2 packed (:func:`theta_cov_of`) per point and profile row."""
-        return self._theta_cov_raw()[:-1].reshape(self.P, stride_rows(self.T, self.profile_stride), -1)
+        return self.diag_parts("theta_cov")["cov"]
 
     def set_theta_cov_table(self, table, outside=0):
         """Install a table (a checkpoint's, a sum over handles) and the outside count that goes with it."""
-        if not 0 <= int(outside) < 1 << 63:
-            raise ValueError("the outside count must lie in [0, 2^63)")
-        t = np.concatenate([np.ascontiguousarray(table, dtype=np.int64).reshape(-1), np.array([int(outside)], dtype=np.int64)])
-        L.check(self.lib.hc_set_theta_cov_tables(self.h, L.lptr(t), t.size))
-
-    def export_theta_cov(self, device_ptr):
-        """Copy the table and its outside word device-to-device to ``device_ptr`` (``theta_cov_words()`` int64)."""
-        L.check(self.lib.hc_export_theta_cov(self.h, C.c_void_p(int(device_ptr)), self.theta_cov_words()))
+        self.set_diag_parts("theta_cov", {"cov": table, "outside": outside})
 
     def reset_theta_cov(self):
-        L.check(self.lib.hc_reset_theta_cov(self.h))
+        self.reset_diag("theta_cov")
 
     def theta_cov_outside(self):
         """Members that were not counted (a selected theta NaN, below 0 or above 1) since the table was made."""
-        out = C.c_uint64()
-        L.check(self.lib.hc_get_theta_cov_outside(self.h, C.byref(out)))
-        return int(out.value)
+        return self._diag_counter("hc_get_theta_cov_outside")
 
     # -- period totals per member (include/hydrocol.h hc_set_period_totals) ---------------------------------------------
     def set_period_totals(self, ends, threshold_nodes=(), bins=0, flux_max_log2=(0, 0)):
@@ -604,74 +583,44 @@ class EnsembleStepper:
         return 4 + len(self.period_threshold_nodes)
 
     def period_totals_words(self):
-        n = C.c_int64()
-        L.check(self.lib.hc_get_period_totals_words(self.h, C.byref(n)))
-        return int(n.value)
+        return self.diag_words("period")
 
     def period_totals_table(self):
         """The raw int64 moments table (layout: :func:`period_totals_table_layout`)."""
-        t = np.zeros(self.period_totals_words(), dtype=np.int64)
-        L.check(self.lib.hc_get_period_totals(self.h, L.lptr(t), t.size))
-        return t
+        return self.diag_raw("period")
 
     def set_period_totals_table(self, table):
-        t = np.ascontiguousarray(table, dtype=np.int64).reshape(-1)
-        L.check(self.lib.hc_set_period_totals_tables(self.h, L.lptr(t), t.size))
-
-    def export_period_totals(self, device_ptr):
-        """Copy the moments table device-to-device to ``device_ptr`` (``period_totals_words()`` int64 on this device)."""
-        L.check(self.lib.hc_export_period_totals(self.h, C.c_void_p(int(device_ptr)), self.period_totals_words()))
-
-    def period_totals_hist_entries(self):
-        return self.P * len(self.period_ends) * 2 * (self.period_bins + self.D) + 2
+        self.set_diag_raw("period", table)
 
     def period_totals_hist_raw(self):
         """The raw int32 histogram table: phist_flux, phist_wtd, then the outside count in two entries."""
-        t = np.zeros(self.period_totals_hist_entries(), dtype=np.int32)
-        L.check(self.lib.hc_get_period_totals_hist(self.h, L.iptr(t), t.size))
-        return t
+        return self.diag_raw("period_hist")
 
     def period_totals_hists(self):
         """(phist_flux [P][n_period][2][B], phist_wtd [P][n_period][2][D]) int32: members of each point per bin."""
-        return split_period_hist(self.period_totals_hist_raw()[:-2], self.P, len(self.period_ends), self.period_bins, self.D)
+        parts = self.diag_parts("period_hist")
+        return parts["flux"], parts["wtd"]
 
     def set_period_totals_hists(self, hist_flux, hist_wtd, outside=0):
         """Install both histograms (a checkpoint's, a sum over handles) and the outside count that goes with them."""
-        t = np.concatenate([np.asarray(hist_flux).reshape(-1), np.asarray(hist_wtd).reshape(-1)])
-        if t.size and (t.min() < 0 or t.max() > INT32_MAX):
-            raise ValueError("histogram counts must lie in [0, 2^31 - 1]")
-        if not 0 <= int(outside) < 1 << 64:
-            raise ValueError("the outside count must lie in [0, 2^64)")
-        tail = np.array([int(outside)], dtype=np.uint64).view(np.int32)
-        t = np.concatenate([np.ascontiguousarray(t, dtype=np.int32), tail])
-        L.check(self.lib.hc_set_period_totals_hist_table(self.h, L.iptr(t), t.size))
-
-    def export_period_totals_hist(self, device_ptr):
-        L.check(self.lib.hc_export_period_totals_hist(self.h, C.c_void_p(int(device_ptr)), self.period_totals_hist_entries()))
+        self.set_diag_parts("period_hist", {"flux": hist_flux, "wtd": hist_wtd, "outside": outside})
 
     def period_totals_acc(self):
         """The members' accumulators [K][N] int64 as they stand (the running period's; reset values after an end row)."""
-        a = np.zeros((self.period_k, self.N), dtype=np.int64)
-        L.check(self.lib.hc_get_period_totals_acc(self.h, L.lptr(a), a.size))
-        return a
+        return self.diag_parts("period_acc")["acc"]
 
     def set_period_totals_acc(self, acc):
-        a = np.ascontiguousarray(acc, dtype=np.int64).reshape(-1)
-        L.check(self.lib.hc_set_period_totals_acc(self.h, L.lptr(a), a.size))
+        self.set_diag_parts("period_acc", {"acc": acc})
 
     def reset_period_totals(self):
-        L.check(self.lib.hc_reset_period_totals(self.h))
+        self.reset_diag("period")
 
     def period_totals_outside(self):
         """Members' values that fell in no bin of their histogram since the tables were made."""
-        out = C.c_uint64()
-        L.check(self.lib.hc_get_period_totals_outside(self.h, C.byref(out)))
-        return int(out.value)
+        return self._diag_counter("hc_get_period_totals_outside")
 
     def period_totals_overflow(self):
-        out = C.c_uint64()
-        L.check(self.lib.hc_get_period_totals_overflow(self.h, C.byref(out)))
-        return int(out.value)
+        return self._diag_counter("hc_get_period_totals_overflow")
 
     def period_totals_stats(self, table=None):
         """The science arrays of ``period_totals_table()`` (or of ``table``, e.g. summed over ranks):
@@ -707,69 +656,43 @@ class EnsembleStepper:
         self.uptake_cells, self.uptake_bins = self.root_uptake_layout()
 
     def root_uptake_words(self):
-        n = C.c_int64()
-        L.check(self.lib.hc_get_root_uptake_words(self.h, C.byref(n)))
-        return int(n.value)
+        return self.diag_words("uptake")
 
     def root_uptake_table(self):
         """The raw int64 table (layout: :func:`root_uptake_table_layout`)."""
-        t = np.zeros(self.root_uptake_words(), dtype=np.int64)
-        L.check(self.lib.hc_get_root_uptake(self.h, L.lptr(t), t.size))
-        return t
+        return self.diag_raw("uptake")
 
     def set_root_uptake_table(self, table):
-        t = np.ascontiguousarray(table, dtype=np.int64).reshape(-1)
-        L.check(self.lib.hc_set_root_uptake_tables(self.h, L.lptr(t), t.size))
-
-    def export_root_uptake(self, device_ptr):
-        """Copy the table device-to-device to ``device_ptr`` (``root_uptake_words()`` int64 on this device)."""
-        L.check(self.lib.hc_export_root_uptake(self.h, C.c_void_p(int(device_ptr)), self.root_uptake_words()))
-
-    def root_uptake_hist_entries(self):
-        return self.P * len(self.period_ends) * len(self.uptake_cells) * self.uptake_bins + 2
+        self.set_diag_raw("uptake", table)
 
     def root_uptake_hist_raw(self):
         """The raw int32 share histograms with the outside count in their two last entries."""
-        t = np.zeros(self.root_uptake_hist_entries(), dtype=np.int32)
-        L.check(self.lib.hc_get_root_uptake_hist(self.h, L.iptr(t), t.size))
-        return t
+        return self.diag_raw("uptake_hist")
 
     def root_uptake_hist(self):
         """[P][n_period][L][B] int32: members of each point per bin of the layer's share of their total."""
-        return self.root_uptake_hist_raw()[:-2].reshape(self.P, len(self.period_ends), len(self.uptake_cells), self.uptake_bins)
+        return self.diag_parts("uptake_hist")["hist"]
 
     def set_root_uptake_hist(self, hist, outside=0):
-        h = np.ascontiguousarray(hist, dtype=np.int32).reshape(-1)
-        tail = np.array([int(outside) & 0xFFFFFFFF, int(outside) >> 32], dtype=np.uint32).view(np.int32)
-        t = np.ascontiguousarray(np.concatenate([h, tail]))
-        L.check(self.lib.hc_set_root_uptake_hist_table(self.h, L.iptr(t), t.size))
-
-    def export_root_uptake_hist(self, device_ptr):
-        L.check(self.lib.hc_export_root_uptake_hist(self.h, C.c_void_p(int(device_ptr)), self.root_uptake_hist_entries()))
+        """Install the share histograms (a checkpoint's, a sum over handles) and the outside count that goes with them."""
+        self.set_diag_parts("uptake_hist", {"hist": hist, "outside": outside})
 
     def root_uptake_acc(self):
         """The members' accumulators [L + 1][N] int64 as they stand (the running period's; 0 after an end row)."""
-        a = np.zeros((len(self.uptake_cells) + 1, self.N), dtype=np.int64)
-        L.check(self.lib.hc_get_root_uptake_acc(self.h, L.lptr(a), a.size))
-        return a
+        return self.diag_parts("uptake_acc")["acc"]
 
     def set_root_uptake_acc(self, acc):
-        a = np.ascontiguousarray(acc, dtype=np.int64)
-        L.check(self.lib.hc_set_root_uptake_acc(self.h, L.lptr(a), a.size))
+        self.set_diag_parts("uptake_acc", {"acc": acc})
 
     def reset_root_uptake(self):
-        L.check(self.lib.hc_reset_root_uptake(self.h))
+        self.reset_diag("uptake")
 
     def root_uptake_outside(self):
         """Members with a zero period total, which no share histogram holds (0 without bins)."""
-        out = C.c_uint64()
-        L.check(self.lib.hc_get_root_uptake_outside(self.h, C.byref(out)))
-        return int(out.value)
+        return self._diag_counter("hc_get_root_uptake_outside")
 
     def root_uptake_overflow(self):
-        out = C.c_uint64()
-        L.check(self.lib.hc_get_root_uptake_overflow(self.h, C.byref(out)))
-        return int(out.value)
+        return self._diag_counter("hc_get_root_uptake_overflow")
 
     def root_uptake_eval(self, row):
         """(theta_mid, u), [N][D - 1] each: theta at the midpoints of the members' current states and the uptake the RHS
@@ -1591,30 +1514,17 @@ def stride_rows(T, stride):
 def profile_layout(P, T, D, stride):
     """{part: (offset, shape)} of the int64 table: prof [P][T_out][D][2][5] (psi_press, theta_vol), pcnt [P][T_out],
     flux [P][T][2][5] (transpiration, lateral_flow), fcnt [P][T], aerr [P][T], ovf [1]; T_out = stride_rows(T, stride)."""
-    n_prow = stride_rows(T, stride)
-    shapes = [("prof", (P, n_prow, D, 2, PROF_WORDS)), ("pcnt", (P, n_prow)), ("flux", (P, T, 2, PROF_WORDS)),
-              ("fcnt", (P, T)), ("aerr", (P, T)), ("ovf", (1,))]
-    out, off = {}, 0
-    for name, shape in shapes:
-        out[name] = (off, shape)
-        off += int(np.prod(shape))
-    out["words"] = (off, ())
-    return out
+    return diag_layout("profile", diag_counts(P, T, D, profile_stride=stride))
 
 
 def split_profile_table(table, P, T, D, stride):
     """Views of the parts of a flat table (see :func:`profile_layout`)."""
-    t = np.asarray(table, dtype=np.int64).reshape(-1)
-    lay = profile_layout(P, T, D, stride)
-    if t.size != lay["words"][0]:
-        raise ValueError(f"profile table of {t.size} words, the layout has {lay['words'][0]}")
-    return {k: t[o:o + int(np.prod(sh))].reshape(sh) for k, (o, sh) in lay.items() if k != "words"}
+    return split_diag("profile", table, diag_counts(P, T, D, profile_stride=stride))
 
 
 def join_profile_table(parts):
     """The flat table of ``split_profile_table`` parts (same order)."""
-    return np.concatenate([np.asarray(parts[k], dtype=np.int64).reshape(-1)
-                           for k in ("prof", "pcnt", "flux", "fcnt", "aerr", "ovf")])
+    return join_diag("profile", parts)
 
 
 def profile_quantise(x, scale_bits):
@@ -1859,22 +1769,12 @@ def layer_storage_hist_of(u, bins):
 
 def layer_storage_table_layout(P, T, L, stride):
     """{part: (offset, shape)} of the int64 table: stor [P][T_out][L][5], scnt [P][T_out], ovf [1]."""
-    n_prow = stride_rows(T, stride)
-    out, off = {}, 0
-    for name, shape in (("stor", (P, n_prow, L, PROF_WORDS)), ("scnt", (P, n_prow)), ("ovf", (1,))):
-        out[name] = (off, shape)
-        off += int(np.prod(shape))
-    out["words"] = (off, ())
-    return out
+    return diag_layout("storage", diag_counts(P, T, profile_stride=stride, storage_layers=L))
 
 
 def split_layer_storage_table(table, P, T, L, stride):
     """Views of the parts of a flat moments table (see :func:`layer_storage_table_layout`)."""
-    t = np.asarray(table, dtype=np.int64).reshape(-1)
-    lay = layer_storage_table_layout(P, T, L, stride)
-    if t.size != lay["words"][0]:
-        raise ValueError(f"layer-storage table of {t.size} words, the layout has {lay['words'][0]}")
-    return {k: t[o:o + int(np.prod(sh))].reshape(sh) for k, (o, sh) in lay.items() if k != "words"}
+    return split_diag("storage", table, diag_counts(P, T, profile_stride=stride, storage_layers=L))
 
 
 def layer_storage_tables_of(theta_rows, ranges, dz, bins=0, counted=None):
@@ -2112,30 +2012,18 @@ def period_solved_rows(wtd_obs, ends):
 
 def period_totals_table_layout(P, n_period, K):
     """{part: (offset, shape)} of the int64 table: pmom [P][n_period][K][5], pcnt [P][n_period], ovf [1]."""
-    out, off = {}, 0
-    for name, shape in (("pmom", (P, n_period, K, PROF_WORDS)), ("pcnt", (P, n_period)), ("ovf", (1,))):
-        out[name] = (off, shape)
-        off += int(np.prod(shape))
-    out["words"] = (off, ())
-    return out
+    return diag_layout("period", diag_counts(P, periods=n_period, thresholds=K - 4))
 
 
 def split_period_totals_table(table, P, n_period, K):
     """Views of the parts of a flat moments table (see :func:`period_totals_table_layout`)."""
-    t = np.asarray(table, dtype=np.int64).reshape(-1)
-    lay = period_totals_table_layout(P, n_period, K)
-    if t.size != lay["words"][0]:
-        raise ValueError(f"period-totals table of {t.size} words, the layout has {lay['words'][0]}")
-    return {k: t[o:o + int(np.prod(sh))].reshape(sh) for k, (o, sh) in lay.items() if k != "words"}
+    return split_diag("period", table, diag_counts(P, periods=n_period, thresholds=K - 4))
 
 
 def split_period_hist(entries, P, n_period, B, D):
     """(phist_flux [P][n_period][2][B], phist_wtd [P][n_period][2][D]) of the histogram table without its two last entries."""
-    t = np.asarray(entries).reshape(-1)
-    nf = P * n_period * 2 * B
-    if t.size != nf + P * n_period * 2 * D:
-        raise ValueError(f"period histograms of {t.size} entries, the layout has {nf + P * n_period * 2 * D}")
-    return t[:nf].reshape(P, n_period, 2, B), t[nf:].reshape(P, n_period, 2, D)
+    parts = _diag_views("period_hist", entries, diag_counts(P, D=D, periods=n_period, period_bins=B))
+    return parts["flux"], parts["wtd"]
 
 
 def period_totals_of(diag_rows, wtd_rows, wtd_obs, ends, threshold_nodes=(), bins=0, flux_max_log2=(0, 0), ancestors=None,
@@ -2436,22 +2324,12 @@ def root_uptake_layer_totals(u, cells, n_root_int, dz):
 def root_uptake_table_layout(P, n_period, L, D):
     """{part: (offset, shape)} of the int64 table: umom [P][n_period][L + 1][5], ucnt [P][n_period], uprof
     [P][n_period][D - 1][2], ovf [1]."""
-    out, off = {}, 0
-    for name, shape in (("umom", (P, n_period, L + 1, PROF_WORDS)), ("ucnt", (P, n_period)),
-                        ("uprof", (P, n_period, D - 1, 2)), ("ovf", (1,))):
-        out[name] = (off, shape)
-        off += int(np.prod(shape))
-    out["words"] = (off, ())
-    return out
+    return diag_layout("uptake", diag_counts(P, D=D, periods=n_period, uptake_layers=L))
 
 
 def split_root_uptake_table(table, P, n_period, L, D):
     """Views of the parts of a flat table (see :func:`root_uptake_table_layout`)."""
-    t = np.asarray(table, dtype=np.int64).reshape(-1)
-    lay = root_uptake_table_layout(P, n_period, L, D)
-    if t.size != lay["words"][0]:
-        raise ValueError(f"root-uptake table of {t.size} words, the layout has {lay['words'][0]}")
-    return {k: t[o:o + int(np.prod(sh))].reshape(sh) for k, (o, sh) in lay.items() if k != "words"}
+    return split_diag("uptake", table, diag_counts(P, D=D, periods=n_period, uptake_layers=L))
 
 
 def root_uptake_tables_of(u_rows, wtd_obs, ends, cells, n_root_int, dz, bins=0, ancestors=None, row_begin=1, acc=None,
@@ -3353,6 +3231,166 @@ def assim_table_shape(key, D, n_sensors=0, n_offsets=0):
     the owner's ``n_sensors`` soil-moisture sensors and ``n_offsets`` window offsets.  Needs no handle."""
     sizes = {"sensors": int(n_sensors), "offsets": int(n_offsets), "4D+1": 4 * int(D) + 1}
     return tuple(sizes.get(n, n) for n in ASSIM_TABLES[key][1])
+
+
+# ---- the diagnostic tables (include/hydrocol.h: the accumulated integer tables of the handle) ---------------------------
+# key -> one raw device table, in the order a checkpoint installs them:
+#   stem     names hc_get_<stem> and, where _lib.EXPORTS has them, hc_get_<stem>_words and hc_export_<stem>
+#   set      the setter (the suffixes differ: _tables, _table, none); reset: the family's reset, which zeroes all its tables
+#   dtype    the element type of the raw table
+#   parts    (name, shape) in table order, the shapes in the run's counts (:func:`diag_counts`).  The parts that lead with
+#            "P" belong to the points: a sum over ranks places them at the points (:func:`diag_placed`).  The others are
+#            global words (ovf [1]: values clamped) and are summed as they are -- or, the members' accumulators, per
+#            member and not summed at all.
+#   outside  how the count of values that fell in no bin follows the parts: None, "int64" (one word) or "uint64" (in the
+#            last two int32 entries)
+#   stored   the checkpoint's (dataset, dataset of the outside count or None, shaped): the parts flat in table order, or
+#            the one part shaped, both without the outside count
+# A new table is one entry here, its C entry points in _lib.EXPORTS, its counts in diag_counts, and the named accessors
+# that document its columns; EnsembleStepper.diag_*, the checkpoint (_Run.diag_tables_on) and the CLI's placed table follow.
+_T = namedtuple("DiagTable", "stem set reset dtype parts outside stored")
+_PR, _PER = ("P", "prows"), ("P", "periods")
+DIAG_TABLES = {
+    "profile": _T("profile_stats", "hc_set_profile_stats_tables", "hc_reset_profile_stats", np.int64,
+                  (("prof", _PR + ("D", 2, PROF_WORDS)), ("pcnt", _PR), ("flux", ("P", "T", 2, PROF_WORDS)),
+                   ("fcnt", ("P", "T")), ("aerr", ("P", "T")), ("ovf", (1,))), None, ("profile_table", None, False)),
+    "theta_hist": _T("theta_hist", "hc_set_theta_hist_table", "hc_reset_theta_hist", np.int32,
+                     (("hist", _PR + ("D", "theta_bins")),), "uint64", ("theta_hist", "theta_hist_outside", True)),
+    "storage": _T("layer_storage", "hc_set_layer_storage_tables", "hc_reset_layer_storage", np.int64,
+                  (("stor", _PR + ("storage_layers", PROF_WORDS)), ("scnt", _PR), ("ovf", (1,))), None,
+                  ("storage_table", None, False)),
+    "storage_hist": _T("layer_storage_hist", "hc_set_layer_storage_hist_table", "hc_reset_layer_storage", np.int32,
+                       (("hist", _PR + ("storage_layers", "storage_bins")),), "uint64",
+                       ("storage_hist", "storage_hist_outside", True)),
+    "theta_cov": _T("theta_cov", "hc_set_theta_cov_tables", "hc_reset_theta_cov", np.int64,
+                    (("cov", _PR + ("cov_words",)),), "int64", ("theta_cov_table", "theta_cov_outside", True)),
+    "period": _T("period_totals", "hc_set_period_totals_tables", "hc_reset_period_totals", np.int64,
+                 (("pmom", _PER + ("K", PROF_WORDS)), ("pcnt", _PER), ("ovf", (1,))), None, ("period_table", None, False)),
+    "period_acc": _T("period_totals_acc", "hc_set_period_totals_acc", "hc_reset_period_totals", np.int64,
+                     (("acc", ("K", "N")),), None, ("period_acc", None, True)),
+    "period_hist": _T("period_totals_hist", "hc_set_period_totals_hist_table", "hc_reset_period_totals", np.int32,
+                      (("flux", _PER + (2, "period_bins")), ("wtd", _PER + (2, "D"))), "uint64",
+                      ("period_hist", "period_hist_outside", False)),
+    "uptake": _T("root_uptake", "hc_set_root_uptake_tables", "hc_reset_root_uptake", np.int64,
+                 (("umom", _PER + ("uptake_layers+1", PROF_WORDS)), ("ucnt", _PER), ("uprof", _PER + ("D-1", 2)),
+                  ("ovf", (1,))), None, ("uptake_table", None, False)),
+    "uptake_acc": _T("root_uptake_acc", "hc_set_root_uptake_acc", "hc_reset_root_uptake", np.int64,
+                     (("acc", ("uptake_layers+1", "N")),), None, ("uptake_acc", None, True)),
+    "uptake_hist": _T("root_uptake_hist", "hc_set_root_uptake_hist_table", "hc_reset_root_uptake", np.int32,
+                      (("hist", _PER + ("uptake_layers", "uptake_bins")),), "uint64",
+                      ("uptake_hist", "uptake_hist_outside", False)),
+    "wtd_hist": _T("wtd_hist", "hc_set_wtd_hist_table", "hc_reset_wtd_hist", np.int32,
+                   (("hist", ("P", "hslots", "D")),), None, ("wtd_hist", None, True)),
+}
+
+
+def diag_counts(P, T=1, D=1, N=0, profile_stride=0, wtd_hist_stride=0, theta_bins=0, storage_layers=0, storage_bins=0,
+                cov_stride=0, periods=0, thresholds=0, period_bins=0, uptake_layers=0, uptake_bins=0):
+    """The counts the shapes of DIAG_TABLES are written in, from a run's settings (a rank without points: ``P`` = 0).
+    Needs no handle; a family that is off has no rows."""
+    T, D = int(T), int(D)
+    return {"P": int(P), "T": T, "D": D, "D-1": D - 1, "N": int(N),
+            "prows": stride_rows(T, profile_stride) if profile_stride else 0,
+            "hslots": wtd_hist_slots(T, wtd_hist_stride) if wtd_hist_stride else 0,
+            "theta_bins": int(theta_bins), "storage_layers": int(storage_layers), "storage_bins": int(storage_bins),
+            "cov_words": theta_cov_shape(D, cov_stride)[2] if cov_stride else 0,
+            "periods": int(periods), "K": 4 + int(thresholds), "period_bins": int(period_bins),
+            "uptake_layers": int(uptake_layers), "uptake_layers+1": int(uptake_layers) + 1, "uptake_bins": int(uptake_bins)}
+
+
+def diag_placed(key):
+    """The names of the table's parts that lead with [P]: what a sum over ranks places at the points."""
+    return tuple(name for name, shape in DIAG_TABLES[key].parts if shape[0] == "P")
+
+
+def diag_layout(key, counts, wide=False):
+    """{part: (offset, shape)} of the raw table ``key`` at ``counts`` (:func:`diag_counts`), and ``words``: its elements
+    with the entries the outside count takes.  ``wide``: the table as it is summed over ranks -- every element int64,
+    the outside count in one word whatever its carrier.  The one place the tables' offsets come from."""
+    e = DIAG_TABLES[key]
+    out, off = {}, 0
+    for name, shape in e.parts:
+        shape = tuple(counts[n] if isinstance(n, str) else n for n in shape)
+        out[name] = (off, shape)
+        off += int(np.prod(shape))
+    out["words"] = (off + (0 if e.outside is None else 1 if wide or e.outside == "int64" else 2), ())
+    return out
+
+
+def pack_diag(key, body, outside=0, wide=False):
+    """The flat raw table of its parts' elements ``body`` and its outside count, of the entry's element type (``wide``:
+    as :func:`diag_layout`).  Every table that is installed passes here: int32 counts outside [0, 2^31 - 1] and an
+    outside count outside its carrier's range are refused."""
+    e = DIAG_TABLES[key]
+    body = np.asarray(body).reshape(-1)
+    dtype = np.int64 if wide else e.dtype
+    if dtype == np.int32 and body.size and (body.min() < 0 or body.max() > INT32_MAX):
+        raise ValueError("histogram counts must lie in [0, 2^31 - 1]")
+    if e.outside is None:
+        return np.ascontiguousarray(body, dtype=dtype)
+    bits = 63 if e.outside == "int64" else 64
+    if not 0 <= int(outside) < 1 << bits:
+        raise ValueError(f"the outside count must lie in [0, 2^{bits})")
+    tail = np.array([int(outside)], dtype=np.uint64).view(np.int32)         # (the low half first, as the device holds it)
+    return np.concatenate([np.ascontiguousarray(body, dtype=dtype), tail.view(dtype)])
+
+
+def unpack_diag(key, raw, wide=False):
+    """(the parts' elements, the outside count or None) of a flat raw table: the inverse of :func:`pack_diag`."""
+    e = DIAG_TABLES[key]
+    t = np.asarray(raw).reshape(-1)
+    if e.outside is None:
+        return t, None
+    n = 1 if wide or e.dtype == np.int64 else 2
+    tail = np.ascontiguousarray(t[t.size - n:], dtype=np.int64 if n == 1 else np.int32)
+    return t[:t.size - n], int(tail.view(np.uint64)[0])
+
+
+def _diag_views(key, body, counts):
+    """{part: shaped view} of the parts' elements ``body`` (a table without its outside count)."""
+    lay = diag_layout(key, counts, wide=True)
+    t, n = np.asarray(body).reshape(-1), lay.pop("words")[0] - (DIAG_TABLES[key].outside is not None)
+    if t.size != n:
+        what = "words" if DIAG_TABLES[key].dtype == np.int64 else "entries"
+        raise ValueError(f"{key} table of {t.size} {what}, the layout has {n}")
+    return {k: t[o:o + int(np.prod(sh))].reshape(sh) for k, (o, sh) in lay.items()}
+
+
+def split_diag(key, raw, counts, wide=False):
+    """{part: shaped view} of the raw table ``key`` (the overflow word of an int64 table is its part ``ovf`` [1]), with
+    ``outside`` as an integer where the entry carries one; ``wide`` as :func:`diag_layout`."""
+    body, outside = unpack_diag(key, np.asarray(raw, dtype=np.int64 if wide else DIAG_TABLES[key].dtype), wide)
+    out = _diag_views(key, body, counts)
+    if outside is not None:
+        out["outside"] = outside
+    return out
+
+
+def join_diag(key, parts, wide=False):
+    """The flat raw table of :func:`split_diag`'s parts (``outside`` defaults to 0): its inverse."""
+    body = np.concatenate([np.asarray(parts[name]).reshape(-1) for name, _ in DIAG_TABLES[key].parts])
+    return pack_diag(key, body, parts.get("outside", 0), wide)
+
+
+def diag_checkpoint(key, raw, counts):
+    """{dataset: array} a checkpoint holds of the raw table ``key`` (the entry's ``stored``)."""
+    e = DIAG_TABLES[key]
+    name, outside_name, shaped = e.stored
+    body, outside = unpack_diag(key, raw)
+    out = {name: body.reshape(diag_layout(key, counts)[e.parts[0][0]][1]) if shaped else body}
+    if outside_name is not None:
+        out[outside_name] = np.array(outside, dtype=np.uint64)
+    return out
+
+
+def diag_from_checkpoint(key, data):
+    """The raw table ``key`` of a checkpoint's datasets ``data``: the inverse of :func:`diag_checkpoint`."""
+    name, outside_name, _ = DIAG_TABLES[key].stored
+    return pack_diag(key, data[name], 0 if outside_name is None else int(data[outside_name]))
+
+
+def _diag_ptr(t):
+    return L.lptr(t) if t.dtype == np.int64 else L.iptr(t)
 
 
 def allreduce_handles(steppers):
