@@ -71,9 +71,20 @@ __host__ __device__ constexpr int ntab_lds(int slots, bool special = true)
 // the compiler spills and reloads with two v_readlane per use), T_INVD1 = 1/(por - wlt) (a zero denominator counts as 1)
 // per-slot integer tables, [NGTAB][64*CPL]
 enum { G_SELF = 0, G_PREV, G_NEXT, NGTAB };
+// Round 7 (hc_step.h, JAC3): the 5-cells-per-lane default-exponent kernel holds a second group-id table behind the first one's four
+// rows, the three groups i % 3 in the same [NGTAB][slots] layout -- computed by the kernel, in the 1 280 B of LDS its layout left over.
+#ifndef HC_JAC_LOCAL3
+#define HC_JAC_LOCAL3 1
+#endif
+__host__ __device__ constexpr bool jac3_table(int slots, bool special = true) { return HC_JAC_LOCAL3 && special && slots == 64 * 5; }
+// bytes per slot of the group-id tables (the fourth row of the first: the multi-point mode's chunk bookkeeping)
+__host__ __device__ constexpr int gtab_rows(int slots, bool special = true) { return 4 + (jac3_table(slots, special) ? (int)NGTAB : 0); }
 
 struct ColumnDev {
-    int D, model, flag_et, flag_lf, flag_hlift, n_root_first, n_root_int, n_groups;
+    // flag_jac3: an FD Jacobian of a row with a local RHS may run on three column groups (hc_step.h JAC3; HYDROCOL_JAC_LOCAL3=0
+    // clears it).  It sits where the struct carried a copy of n_groups no kernel read (StepArgs::n_groups is the one they
+    // use): the struct keeps its size, and with it every other kernel its instruction stream.
+    int D, model, flag_et, flag_lf, flag_hlift, n_root_first, n_root_int, flag_jac3;
     double theta_res, alpha, n, m, psi_sat, epsilon, lambda, sigma, sat_soil, dz, inv_dz;
     double ipsi50, lai, surface_evap, interception, evap_delta_min;
     double mn_alpha;    // (m*n)*alpha

@@ -143,7 +143,7 @@ constexpr int LDS_BYTES = 160 * 1024;
 __host__ __device__ constexpr int lds_wave_bytes(int cpl, int halves = 1, bool special = true)
 {
     const int slots = 64 * cpl;
-    const int tables = (ntab_lds(slots * halves, special) * slots * 8 + 4 * slots) * halves;
+    const int tables = (ntab_lds(slots * halves, special) * slots * 8 + gtab_rows(slots * halves, special) * slots) * halves;
     const int wpb = wpb_of(cpl, halves, special);
     const int boxes = halves == 2 ? (wpb / 2) * (int)sizeof(PairBox) : 0;
     return (LDS_BYTES - tables - boxes) / wpb - WAVE_SCRATCH * 8;
@@ -180,7 +180,7 @@ __host__ __device__ constexpr int lds_extra(int cpl, int halves = 1, bool specia
     //  is an AGPR move, cheaper than the LDS round trip)
     if (halves != 1 || wpb_of(cpl, halves, special) != 8) return 0;
     const int slots = 64 * cpl;
-    const int tables = ntab_lds(slots, special) * slots * 8 + 4 * slots;
+    const int tables = ntab_lds(slots, special) * slots * 8 + gtab_rows(slots, special) * slots;
     const int n = ((LDS_BYTES - tables) / wpb_of(cpl, halves, special) - WAVE_SCRATCH * 8) / (slots * 8);
     return n >= NVEC + 4 ? 4 : 0;
 }
@@ -878,7 +878,7 @@ __global__ __launch_bounds__(WPB * WAVE, WPB / 4) void step_kernel(const StepArg
     double *tab = lds;
     constexpr int NTAB_L = ntab_lds(TSLOTS, SPECIAL);         // tables this kernel stages (the last one, T_RDELTA, only where it is read)
     signed char *gtab = reinterpret_cast<signed char *>(tab + NTAB_L * TSLOTS);     // group ids < 16: a byte each
-    double *wave_base = reinterpret_cast<double *>(gtab + 4 * TSLOTS);
+    double *wave_base = reinterpret_cast<double *>(gtab + gtab_rows(TSLOTS, SPECIAL) * TSLOTS);
     constexpr int NVEC_K = lds_vectors(CPL, HALVES, SPECIAL);
     constexpr int NEXTRA = lds_extra(CPL, HALVES, SPECIAL);
     constexpr bool J_LDS = NEXTRA == 4;
@@ -947,6 +947,14 @@ __global__ __launch_bounds__(WPB * WAVE, WPB / 4) void step_kernel(const StepArg
     if (!multi)
         for (int k = threadIdx.x; k < NTAB_L * TSLOTS; k += WPB * WAVE) tab[k] = A.tab[k];
     for (int k = threadIdx.x; k < NGTAB * TSLOTS; k += WPB * WAVE) gtab[k] = (signed char)A.gtab[k];
+    if constexpr (jac3_table(TSLOTS, SPECIAL)) {
+        // the three groups i % 3 in the first table's layout (JAC3 below): node i sits in slot (i % CPL) * 64 + i / CPL; nodes
+        // without a column and padding slots hold -1, as the host's table has them
+        for (int k = threadIdx.x; k < NGTAB * TSLOTS; k += WPB * WAVE) {
+            const int slot = k % TSLOTS, i = (slot % WAVE) * CPL + slot / WAVE, j = i + (k / TSLOTS == G_PREV ? -1 : k / TSLOTS == G_NEXT ? 1 : 0);
+            gtab[4 * TSLOTS + k] = (signed char)((i < A.D && j >= 0 && j < A.D) ? j % 3 : -1);
+        }
+    }
     if (threadIdx.x == 0) {
         chunk_state[0] = 0;
         chunk_state[1] = 0;
@@ -1260,10 +1268,25 @@ __global__ __launch_bounds__(WPB * WAVE, WPB / 4) void step_kernel(const StepArg
             gn_keep[c] = gtabw[G_NEXT * TSLOTS + c * WAVE + lane];
         }
     }
+    // Round 7, three FD-Jacobian groups on rows whose RHS is local (the 5-cells-per-lane default-exponent kernel at two
+    // waves per SIMD only).  The host's five groups are scipy's group_columns in a random visiting order; a tridiagonal
+    // pattern needs three.  Where f_i depends on y[i-1], y[i], y[i+1] alone -- no ET normalisation (night, spin-up, ET
+    // off), no surface evaporation beyond row 0's own cell -- and no perturbation moves the water-table search of the
+    // lateral flow, f_i(y + h e_G) at the rows next to a perturbed column is the same for every valid grouping G, bit
+    // for bit, so the groups i % 3 give the Jacobian the five give.  PH_JAC decides per Jacobian (`jac3`, wave-uniform);
+    // the ids are then read from the second table (hc_device.h jac3_table): the same loads at another base, no branch.
+    // (The ids by index arithmetic under a wave-uniform branch, no table: bit-equal, and 0.8 % SLOWER than the parent --
+    // 26 more VGPR spills; LAB_NOTES.md §40.)  -DHC_JAC_LOCAL3=0 compiles the path out, HYDROCOL_JAC_LOCAL3=0 clears
+    // ColumnDev::flag_jac3 in the same binary.
+    constexpr bool JAC3 = jac3_table(TSLOTS, SPECIAL) && TWO && HALVES == 1 && CPL == 5;
+    static_assert(!JAC3 || DEEP, "the three-group ids are read from LDS at each Jacobian phase");
 #define HC_GROUPS()                                                                          \
     int gs[CPL], gp[CPL], gn[CPL];                                                           \
+    HC_GROUPS_FILL()
+#define HC_GROUPS_FILL()                                                                     \
     {                                                                                        \
         auto gq = (const __attribute__((address_space(3))) signed char *)gtabw;              \
+        if constexpr (JAC3) gq += jac3 ? 4 * TSLOTS : 0;                                     \
         if (DEEP) asm volatile("" : "+v"(gq));                                               \
         _Pragma("unroll") for (int c = 0; c < CPL; c++) {                                    \
             gs[c] = DEEP ? (int)gq[G_SELF * TSLOTS + c * WAVE + lane] : gs_keep[c];          \
@@ -1409,6 +1432,7 @@ __global__ __launch_bounds__(WPB * WAVE, WPB / 4) void step_kernel(const StepArg
                 int order = 1, n_equal = 0, have_lu = 0, current_jac = 0, newton_k = 0, n_iter = 0;
                 int g = 0, jac_init = 1, nfev = 0, njev = 0, nlu = 0, nsteps = 0, ok = 0;
                 int redo_mask = 0, jac_stage = 0;
+                int jac3 = 0;       // (JAC3) this Jacobian runs on the three groups i % 3: set by PH_JAC, read until C_JAC_FIN
 #pragma unroll
                 for (int c = 0; c < CPL; c++) {
                     // sol.y[:, -1] before any accepted step is y0 itself
@@ -1700,6 +1724,7 @@ __global__ __launch_bounds__(WPB * WAVE, WPB / 4) void step_kernel(const StepArg
                         if (g < 0) {
                             HC_SUB(62);
                             // common.num_jac: step h per column from factor, f sign and |y|
+                            double hfar[CPL], fb0 = 0.0;       // (JAC3 only)
 #pragma unroll
                             for (int c = 0; c < CPL; c++) {
                                 const int slot = c * WAVE + lane;
@@ -1714,6 +1739,41 @@ __global__ __launch_bounds__(WPB * WAVE, WPB / 4) void step_kernel(const StepArg
                                 W.template st<V_FAC>(slot, fac);
                                 hj[c] = vnode[c] ? h : 1.0;
                                 if constexpr (TWO_J) W.template stJ<V_HJ>(slot, hj[c]);
+                                // the farthest this column is moved: the retry pass's step, 10 x the factor just stored
+                                if constexpr (JAC3) hfar[c] = vnode[c] ? fabs((yp[c] + (10.0 * fac) * ysc) - yp[c]) : 0.0;
+                                if constexpr (JAC3) fb0 = c == 0 ? fb : fb0;
+                            }
+                            if constexpr (JAC3) {
+                                // Three groups for this Jacobian?  (a) the row's RHS is local; (b) no midpoint of the
+                                // water-table search, 1 .. D - 2, leaves the base state's side of psi_sat when either
+                                // neighbour moves by its farthest step, either way -- the midpoints formed as rhs_eval
+                                // forms them, no tolerance; a smaller step of the same column lies between (the rounded
+                                // sums are monotone); (c) base f of row 0 is a non-zero number, so that an all-zero column's
+                                // scale is positive whichever evaluation lends it row 0 (col_stats); (d) the run-time switch.
+                                const ColumnDev Pj = load_const(A.P + point);
+                                jac3 = 0;
+                                if (Pj.flag_jac3 && A.n_groups > 3 && !(Pj.flag_et && !R.spinup && R.daylight)) {
+                                    const double y_nf = shfl_down1(yp[0], lane, 0.0), hfar_nf = shfl_down1(hfar[0], lane, 0.0);
+                                    bool moved = false;
+#pragma unroll
+                                    for (int c = 0; c < CPL; c++) {
+                                        const int i = lane * CPL + c;
+                                        const double yn = c + 1 < CPL ? yp[c + 1 < CPL ? c + 1 : c] : y_nf;
+                                        const double fn = c + 1 < CPL ? hfar[c + 1 < CPL ? c + 1 : c] : hfar_nf;
+                                        const bool sat = 0.5 * (yp[c] + yn) >= Pj.psi_sat;
+                                        const bool s0 = 0.5 * ((yp[c] + hfar[c]) + yn) >= Pj.psi_sat;
+                                        const bool s1 = 0.5 * ((yp[c] - hfar[c]) + yn) >= Pj.psi_sat;
+                                        const bool s2 = 0.5 * (yp[c] + (yn + fn)) >= Pj.psi_sat;
+                                        const bool s3 = 0.5 * (yp[c] + (yn - fn)) >= Pj.psi_sat;
+                                        const int diff = int(s0 != sat) | int(s1 != sat) | int(s2 != sat) | int(s3 != sat);
+                                        moved = int(moved) | (diff & int(i >= 1) & int(i <= D - 2));
+                                    }
+                                    const double fb_row0 = comm.first_row(fb0);
+                                    jac3 = !__any(moved) && fabs(fb_row0) > 0.0;
+                                }
+                                // the budget counts phase-loop trips: the saved ones count as taken
+                                if (jac3) guard += A.n_groups - 3;
+                                HC_GROUPS_FILL();
                             }
                             g = 0;
                         } else {
@@ -1751,7 +1811,7 @@ __global__ __launch_bounds__(WPB * WAVE, WPB / 4) void step_kernel(const StepArg
                         }
                         if constexpr (!TWO_J) { HC_J_STORE(); }
                         HC_SUB_END();
-                        if (g < A.n_groups) {
+                        if (g < ((JAC3 && jac3) ? 3 : A.n_groups)) {
 #pragma unroll
                             for (int c = 0; c < CPL; c++) ycur[c] = yp[c] + ((gs[c] == g) ? hj[c] : 0.0);
                         } else {
@@ -1837,9 +1897,22 @@ __global__ __launch_bounds__(WPB * WAVE, WPB / 4) void step_kernel(const StepArg
                             // rare: some column moved f by less than EPS^0.875 of its size -> retry those columns
                             // with a 10x step, group by group (num_jac's diff_too_small branch); nothing committed yet
                             redo_mask = 0;
-                            for (int q = 0; q < A.n_groups; q++)
+                            for (int q = 0; q < ((JAC3 && jac3) ? 3 : A.n_groups); q++)
                                 if (__any((my_groups >> q) & 1)) redo_mask |= 1 << q;
                             redo_mask = comm.or_bits(uniform_i(redo_mask));
+                            if constexpr (JAC3) {
+                                if (jac3) {
+                                    // the retry pass takes one trip per group with a small column: the budget counts the
+                                    // trips the host's groups would have taken
+                                    int their_groups = 0, their_mask = 0;
+#pragma unroll
+                                    for (int c = 0; c < CPL; c++)
+                                        their_groups |= ((small_bits >> c) & 1) ? (1 << (gtabw[G_SELF * TSLOTS + c * WAVE + lane] & 15)) : 0;
+                                    for (int q = 0; q < A.n_groups; q++)
+                                        if (__any((their_groups >> q) & 1)) their_mask |= 1 << q;
+                                    guard += __popc(their_mask) - __popc(redo_mask);
+                                }
+                            }
                             flags_lds[lane] = small_bits;
                             __builtin_amdgcn_wave_barrier();
                             if (lane == 0 && comm.half == 0) atomicAdd(&load_const(A.io).counters[0], 1ull);

@@ -190,6 +190,9 @@ struct hc_handle {
     // HYDROCOL_MODEL_PACK=0: the 5-cells-per-lane step kernel never takes its packed cell model (ColumnDev::flag_pack; A/B,
     // cross-checks: the same binary, the same bits)
     bool model_pack = true;
+    // HYDROCOL_JAC_LOCAL3=0: the same kernel always evaluates the host's column groups for its FD Jacobian, never the three
+    // groups i % 3 on rows with a local RHS (ColumnDev::flag_jac3; A/B, cross-checks: the same binary, the same bits)
+    bool jac_local3 = true;
     int chunk_members = 0;      // HYDROCOL_CHUNK_MEMBERS (0: derived from the member count)
     DevBuf<double> tab, node_tabs, precip, atm, psi, base, nscale, fresh, psi_rows, scratch_d, diag;
     DevBuf<double> wave_spill;   // per-wave vectors of deep columns that do not fit in LDS (hc_step.h WaveVecs)
@@ -4657,7 +4660,7 @@ int fill_args(hc_handle *h, StepArgs &A)
     A.gtab = h->gtab.p;
     A.n_members = h->n_members;
     A.D = h->P.D;
-    A.n_groups = h->P.n_groups;
+    A.n_groups = h->p.n_groups;
     A.host_noise = h->philox && !h->noise_host() ? 0 : 1;   // a filtered Philox run hands its normals over as caller noise
     A.psi_sat = h->P.psi_sat;
     A.jac_reject = h->jac_reject;
@@ -4762,6 +4765,7 @@ int hc_create(int device_ordinal, hc_handle **out)
         h->force_split = atoi(sc) == 1;
     }
     if (const char *mp = getenv("HYDROCOL_MODEL_PACK")) h->model_pack = atoi(mp) != 0;
+    if (const char *j3 = getenv("HYDROCOL_JAC_LOCAL3")) h->jac_local3 = atoi(j3) != 0;
     if (const char *sv = getenv("HYDROCOL_SCIPY_152")) h->scipy_152 = atoi(sv) != 0;     // (the whole product at once: CLI, Simulation)
     if (const char *mi = getenv("HYDROCOL_DEBUG_MAX_ITER"))    // test hook: forces abandoned attempts
         if (atoi(mi) > 0) h->max_phase_iterations = atoi(mi);
@@ -4824,7 +4828,7 @@ static int build_point(hc_handle *h, const hc_column_params *p, const double *no
             return fail(HC_ERR_ARG, "cell %d: porosity %g is not above theta_res = %g", i, mid_tabs[i], p->theta_res);
     ColumnDev P{};
     P.D = D; P.model = p->model; P.flag_et = p->flag_et; P.flag_lf = p->flag_lf; P.flag_hlift = p->flag_hlift;
-    P.n_root_first = p->n_root_first; P.n_root_int = p->n_root_int; P.n_groups = p->n_groups;
+    P.n_root_first = p->n_root_first; P.n_root_int = p->n_root_int;
     P.theta_res = p->theta_res; P.alpha = p->alpha; P.n = p->n; P.m = p->m; P.psi_sat = p->psi_sat;
     P.epsilon = p->epsilon; P.lambda = p->lambda_exp; P.sigma = p->sigma_noise; P.sat_soil = p->sat_soil;
     P.dz = p->dz; P.inv_dz = 1.0 / p->dz; P.ipsi50 = p->ipsi50; P.lai = p->lai; P.surface_evap = p->surface_evap;
@@ -4838,6 +4842,7 @@ static int build_point(hc_handle *h, const hc_column_params *p, const double *no
     P.predict_low = std::min(D - 2, std::max(0, (D - 2) - (p->sat_cells - 1)));
     P.predict_first = (1 - (p->sat_cells - 1)) >= 1 ? 1 : 0;
     P.flag_pack = h->model_pack ? 1 : 0;
+    P.flag_jac3 = h->jac_local3 ? 1 : 0;
 
     const int M = D - 1;
     // Slot tables for `halves` waves per member with `cpl` nodes per lane: node / midpoint i sits with wide lane
