@@ -74,6 +74,14 @@ EXPORTS = {
     "hc_noise_field_normals": ([C.c_void_p, C.c_int64, C.c_int64, _dp], C.c_int),
     "hc_get_noise_field_base": ([C.c_void_p, _dp, C.c_int64, C.c_int64], C.c_int),
     "hc_set_noise_field_base": ([C.c_void_p, _dp], C.c_int),
+    "hc_set_forcing_perturbation": ([C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint64], C.c_int),
+    "hc_clear_forcing_perturbation": ([C.c_void_p], C.c_int),
+    "hc_set_forcing_member_offset": ([C.c_void_p, C.c_int64], C.c_int),
+    "hc_get_forcing_perturbation": ([C.c_void_p, _ip, _dp, _dp, _dp, _dp, C.POINTER(C.c_uint64)], C.c_int),
+    "hc_get_forcing_state": ([C.c_void_p, _dp, C.POINTER(C.c_int64)], C.c_int),
+    "hc_set_forcing_state": ([C.c_void_p, _dp, C.c_int64], C.c_int),
+    "hc_forcing_normals": ([C.c_void_p, C.c_int64, C.c_int64, C.c_int64, _dp], C.c_int),
+    "hc_forcing_factors": ([C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _dp], C.c_int),
     "hc_step_rows": ([C.c_void_p, C.POINTER(StepArgs)], C.c_int),
     "hc_spinup": ([C.c_void_p, C.POINTER(SpinupArgs)], C.c_int),
     "hc_synchronize": ([C.c_void_p], C.c_int),

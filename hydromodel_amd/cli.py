@@ -215,6 +215,20 @@ unknown keys, only membership of the 12 is checked):
   "numpy"`` and with ``Filter.Rejuvenation``.  ``<Output_Name>_ensemble.h5`` gains ``noise_correlation_length_cm``,
   ``noise_correlation_layers`` and ``noise_correlation_a`` (``[D]``; a sweep: ``[P][D]``), and the run ends with
   `` [Ensemble xN] noise correlation: length ... cm, K breaks``.  Without the key every bit, file and line stays.
+* ``"Ensemble": {..., "Forcing_Perturbation": {"Precipitation_Sigma": 0.3, "Demand_Sigma": 0.1, "Correlation_Days": 3,
+  "Seed": s}}``: input uncertainty (include/hydrocol.h hc_set_forcing_perturbation).  Every member integrates with the
+  record's rainfall and atmospheric demand times a log-normal factor of mean one of its own, constant over a day (48
+  rows) and an AR(1) from day to day with e-folding time ``Correlation_Days``; the refresh rule, surface evaporation,
+  daylight, the well's record and the spin-up stay the record's.  At least one sigma is required, each a finite number in
+  [0, 1]; ``Correlation_Days`` in [0, 365], default 0 (white in time); ``Seed`` defaults to the ensemble's.  Applied after
+  the spin-up, before the filters; the particle filter moves a member's factor state with it, the EnKF leaves it alone.
+  Works with either noise source, both filters, every table, a sweep, a sharded EnKF and ``--gpus N`` (members are keyed
+  by their global id).  Refused: a non-object, an unknown key, a bool or non-finite number, a value outside its range, and
+  ``"Filter": {"Sharded": true}`` on a single-point run (the exchanged columns do not carry the factor state).
+  ``<Output_Name>_ensemble.h5`` gains ``forcing_precipitation_sigma``, ``forcing_demand_sigma``,
+  ``forcing_correlation_days``, ``forcing_phi`` and ``forcing_seed``, and the run ends with `` [Ensemble xN] forcing
+  perturbation: precipitation sigma ..., demand sigma ..., correlation ... days``.  Without the key every bit, file and
+  line stays.
 * ``"EnKF": {..., "Noise_Field": true}`` or ``{"Noise_Field": {"Relaxation": 0.5}}``: every analysis also updates each
   member's base noise vector -- its conductivity field -- together with its state, from the same observations, draws and
   factor (include/hydrocol.h hc_set_enkf_noise_field).  The vectors' anomalies are relaxed to prior spread with the
@@ -309,6 +323,7 @@ def main(params_file=None, data_file=None, seed=None, device=0, gpus=None, _sett
             filter_window_settings(params["Ensemble"])
             filter_smoother_settings(params["Ensemble"])
             noise_correlation_settings(params["Ensemble"])
+            forcing_perturbation_settings(params["Ensemble"])
         ranks = multigpu.Ranks(expect=n_gpus if (n_gpus > 1 or multigpu.in_rank()) else None)
         if ranks.world > 1:
             device = ranks.device_index()
@@ -381,6 +396,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     fwindow = filter_window_settings(ens)
     smoother = filter_smoother_settings(ens)
     corr = noise_correlation_settings(ens)
+    pert = forcing_perturbation_settings(ens)
     cols = ColumnTables(params, load_site_well(params))
     forcing = ForcingDigest(params, water_data, cols)
     record = soil_moisture_record_of(sm, cols, water_data)      # before any GPU call
@@ -399,7 +415,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     uptake = uptake_settings(ens)
     if ens.get("Points"):
         return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels, assim,
-                          theta, storage, periods, plan, corr, cov, uptake)
+                          theta, storage, periods, plan, corr, cov, uptake, pert)
     ucells = uptake_plan(uptake, [cols])                        # (so are the uptake's layers)
     sharded = enkf_sharded(ens)
     fsharded = filter_sharded(ens)
@@ -423,7 +439,8 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
                              spinup=str(ens.get("Spinup", "shared")).lower(), profile_stride=stride,
                              wtd_hist_stride=dist_stride, theta_hist_bins=theta[0], **assim.kwargs(),
                              **_storage_kwargs(storage), **_covariance_kwargs(cov), **_period_kwargs(periods, plan),
-                             **_uptake_kwargs(uptake), **shard_kw, **_noise_correlation_kwargs(corr))
+                             **_uptake_kwargs(uptake), **shard_kw, **_noise_correlation_kwargs(corr),
+                             **_forcing_perturbation_kwargs(pert))
     label = f"Ensemble x{n_members}"
     _step_all(sim, rows, label, ranks)
     # the run's one collective: int64 (count, sum idx, sum idx^2) per row, exact and order-independent
@@ -464,10 +481,13 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
         extra["enkf_sharded"] = np.array(1 if sharded else 0, dtype=np.int8)
     ctables, corr_line = _noise_correlation_arrays(corr, [cols], label, keep_points=False)
     extra.update(ctables)
+    ptables, pert_line = _forcing_perturbation_arrays(pert, label)
+    extra.update(ptables)
     arrays = dict(moments=moments, wtd_mean_cm=mean_cm, wtd_std_cm=std_cm, rows=np.array(rows),
                   members=np.array(n_members), gpus=np.array(ranks.world), initial_cond=psi0, **extra)
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "ensemble water-table statistics", ranks)
-    _print_lines(lines.pop("crps"), *assim_lines, smooth_line, *lines.values(), corr_line if ranks.rank == 0 else None)
+    _print_lines(lines.pop("crps"), *assim_lines, smooth_line, *lines.values(), corr_line if ranks.rank == 0 else None,
+                 pert_line if ranks.rank == 0 else None)
     sim.close()
 
 
@@ -629,6 +649,68 @@ def _noise_correlation_arrays(corr, cols_list, label, keep_points):
            "noise_correlation_layers": np.array(1 if corr["layers"] else 0, dtype=np.int8),
            "noise_correlation_a": a if keep_points else a[0]}
     line = f" [{label}] noise correlation: length {corr['length_cm']:g} cm, {int((a[:, 1:] == 0.0).sum())} breaks"
+    return out, line
+
+
+FORCING_PERTURBATION_KEYS = ("Precipitation_Sigma", "Demand_Sigma", "Correlation_Days", "Seed")
+
+
+def forcing_perturbation_settings(ens):
+    """Ensemble.Forcing_Perturbation -> {"precipitation_sigma", "demand_sigma", "correlation_days", "seed"} (the
+    ``forcing_perturbation=`` argument of EnsembleSimulation / SweepSimulation, the seed filled in), or None when the key is
+    absent.  Pure: runs before any GPU call, and a bad value is a ValueError (message + exit status 1)."""
+    import math
+    from numbers import Integral, Real
+    if "Forcing_Perturbation" not in ens:
+        return None
+    block = ens["Forcing_Perturbation"]
+    if not isinstance(block, dict):
+        raise ValueError(f" Ensemble: Forcing_Perturbation = {block!r} must be an object such as "
+                         f"{{\"Precipitation_Sigma\": 0.3, \"Demand_Sigma\": 0.1, \"Correlation_Days\": 3}}.")
+    unknown = sorted(set(block) - set(FORCING_PERTURBATION_KEYS))
+    if unknown:
+        raise ValueError(f" Ensemble: Forcing_Perturbation has unknown keys {unknown} (known: "
+                         f"{list(FORCING_PERTURBATION_KEYS)}).")
+    if "Precipitation_Sigma" not in block and "Demand_Sigma" not in block:
+        raise ValueError(" Ensemble: Forcing_Perturbation needs Precipitation_Sigma or Demand_Sigma.")
+
+    def number(key, lo, hi):
+        v = block.get(key, 0.0)
+        if isinstance(v, bool) or not isinstance(v, Real) or not math.isfinite(v) or not lo <= v <= hi:
+            raise ValueError(f" Ensemble: Forcing_Perturbation.{key} = {v!r} must be a finite number in [{lo:g}, {hi:g}].")
+        return float(v)
+
+    out = {"precipitation_sigma": number("Precipitation_Sigma", 0.0, 1.0), "demand_sigma": number("Demand_Sigma", 0.0, 1.0),
+           "correlation_days": number("Correlation_Days", 0.0, 365.0)}
+    seed = block.get("Seed", ens.get("Seed", 0))
+    if isinstance(seed, bool) or not isinstance(seed, Integral) or seed < 0:
+        raise ValueError(f" Ensemble: Forcing_Perturbation.Seed = {seed!r} must be an integer >= 0.")
+    out["seed"] = int(seed)
+    filt = ens.get("Filter")
+    if isinstance(filt, dict) and filt.get("Sharded") and filt.get("Stride") and not ens.get("Points"):
+        raise ValueError(" Ensemble: Forcing_Perturbation with \"Filter\": {\"Sharded\": true}: the columns the ranks exchange "
+                         "do not carry the members' forcing state; run the filter unsharded.")
+    return out
+
+
+def _forcing_perturbation_kwargs(pert):
+    return {} if pert is None else {"forcing_perturbation": pert}
+
+
+def _forcing_perturbation_arrays(pert, label):
+    """The datasets and the closing line of a run with perturbed forcing (every rank holds the same settings: no
+    collective)."""
+    import numpy as np
+    from .stepper import forcing_coefficients
+    if pert is None:
+        return {}, None
+    out = {"forcing_precipitation_sigma": np.array(pert["precipitation_sigma"], dtype=np.float64),
+           "forcing_demand_sigma": np.array(pert["demand_sigma"], dtype=np.float64),
+           "forcing_correlation_days": np.array(pert["correlation_days"], dtype=np.float64),
+           "forcing_phi": np.array(forcing_coefficients(pert["correlation_days"])[0], dtype=np.float64),
+           "forcing_seed": np.array(pert["seed"], dtype=np.uint64)}
+    line = (f" [{label}] forcing perturbation: precipitation sigma {pert['precipitation_sigma']:g}, demand sigma "
+            f"{pert['demand_sigma']:g}, correlation {pert['correlation_days']:g} days")
     return out, line
 
 
@@ -1959,7 +2041,7 @@ def _reduce_diagnostics(ranks, sim, ids, cols_all, forcing, stride, dist, theta,
 
 def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride=0, dist_levels=None,
                assim=Assimilation(), theta=(0, None), storage=None, periods=None, plan=None, corr=None, cov=None,
-               uptake=None):
+               uptake=None, pert=None):
     """Parameter points x members: this rank's points in one handle (ensemble.SweepSimulation), the whole table assembled
     over the ranks (multigpu.assemble_points)."""
     import numpy as np
@@ -1988,7 +2070,8 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
         sim = SweepSimulation(points, forcing, n_members, seed=int(ens.get("Seed", 0)), device=device, point_ids=mine,
                               profile_stride=stride, wtd_hist_stride=dist_stride, theta_hist_bins=theta[0],
                               **assim.kwargs(), **_storage_kwargs(storage), **_covariance_kwargs(cov),
-                              **_period_kwargs(periods, plan), **_uptake_kwargs(uptake), **_noise_correlation_kwargs(corr))
+                              **_period_kwargs(periods, plan), **_uptake_kwargs(uptake), **_noise_correlation_kwargs(corr),
+                              **_forcing_perturbation_kwargs(pert))
         _step_all(sim, rows, label, ranks)
         table = sim.moments()
         for j, k in enumerate(mine):
@@ -2009,10 +2092,13 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     arrays.update(stables)
     ctables, corr_line = _noise_correlation_arrays(corr, cols_all, label, keep_points=True)
     arrays.update(ctables)
+    ptables, pert_line = _forcing_perturbation_arrays(pert, label)
+    arrays.update(ptables)
     if sim is not None:
         sim.close()
     _save(output_name.strip().replace(" ", "_") + "_ensemble", arrays, "sweep's water-table statistics", ranks)
-    _print_lines(lines.pop("crps"), *assim_lines, smooth_line, *lines.values(), corr_line if ranks.rank == 0 else None)
+    _print_lines(lines.pop("crps"), *assim_lines, smooth_line, *lines.values(), corr_line if ranks.rank == 0 else None,
+                 pert_line if ranks.rank == 0 else None)
 
 
 def run_cli(argv=None):
@@ -2043,6 +2129,7 @@ def run_cli(argv=None):
                 filter_window_settings(settings["Ensemble"])
                 filter_smoother_settings(settings["Ensemble"])
                 noise_correlation_settings(settings["Ensemble"])
+                forcing_perturbation_settings(settings["Ensemble"])
             except ValueError as bad:
                 print(bad)
                 sys.exit(1)

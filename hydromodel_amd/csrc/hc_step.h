@@ -416,6 +416,25 @@ struct IoArgs {
     unsigned long long *point_cost;  // [n_points] RHS evaluations spent on each point's members by this launch
     double *trace;            // diagnostic builds: [1 + 6 * HC_TRACE_N] phase trace of member 0, or null
 };
+// ... and what follows it in device memory: the perturbed forcing (hc_set_forcing_perturbation, include/hydrocol.h), read
+// by the PREDICT builds only and through a load of its own (StepArgs::io points at an IoArgsExt).  Every other load takes
+// IoArgs, the struct as it was, under the name it had: a copy of another SIZE moved the register allocation of the
+// one-wave kernels of 9 and 10 cells per lane, whichever fields were read, and the same struct under another NAME swapped
+// registers in fourteen monitoring-mode kernels -- they keep the instruction stream they had (profiles/r08_isa_vs_parent.txt).
+struct IoArgsExt : IoArgs {
+    const double *fmul;       // [n_days][2][N] the members' factors of the days this launch touches, or null (off)
+    long long fmul_day0;      // the day (row / FORCING_DAY_ROWS) of fmul's first plane
+};
+
+constexpr int FORCING_DAY_ROWS = 48;     // the model's daily clock (simulation.py:599 refreshes the noise at i % 48 == 0)
+
+// A member's forcing value: the record's times the member's factor of the day, ONE IEEE product (never fused into what
+// the RHS does with it: a member must equal a run on its own scaled record, bit for bit)
+__device__ __forceinline__ double forcing_product(double x, double f)
+{
+#pragma clang fp contract(off)
+    return x * f;
+}
 
 constexpr unsigned PHILOX_DRAW_SPINUP = 0xFFFFFFFFu;
 constexpr int HC_TRACE_N = 20000;
@@ -1316,6 +1335,16 @@ __global__ __launch_bounds__(WPB * WAVE, WPB / 4) void step_kernel(const StepArg
             row = A.spinup ? io.row_begin : io.row_begin + r;
             R.precip = io.precip[row];
             R.atm = io.atm[row];
+            if constexpr (PREDICT) {
+                // perturbed forcing: the member's two factors of the row's day, wave-uniform (refresh, surface_evap,
+                // daylight / wet, wtd_obs and spin-up solves stay with the record)
+                const IoArgsExt iof = load_const(static_cast<const IoArgsExt *>(A.io));
+                if (!A.spinup && iof.fmul) {
+                    const double *fm = iof.fmul + (size_t)(row / FORCING_DAY_ROWS - iof.fmul_day0) * 2 * A.n_members + member;
+                    R.precip = forcing_product(R.precip, fm[0]);
+                    R.atm = forcing_product(R.atm, fm[A.n_members]);
+                }
+            }
             const int day_bits = io.daylight[row];   // bit 0: daylight, bit 1: wet season (PREDICT mode)
             R.daylight = day_bits & 1;
             R.wet = (day_bits >> 1) & 1;

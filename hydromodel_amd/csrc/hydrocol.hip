@@ -207,7 +207,7 @@ struct hc_handle {
     AccTable<long long> moments{"words"};     // [P][3][T], keyed by the point count, reset by hc_set_forcing
     DevBuf<unsigned long long> counters;
     DevBuf<ColumnDev> Pdev;
-    DevBuf<IoArgs> iodev;
+    DevBuf<IoArgsExt> iodev;
     // several parameter points: Philox key of each point's first member, walk order of the chunk ticket, per-point cost
     DevBuf<long long> point_base;
     DevBuf<int> point_order;
@@ -216,7 +216,7 @@ struct hc_handle {
     std::vector<int> order_host;
     bool fixed_order = false;                    // HYDROCOL_POINT_ORDER=fixed: keep the walk in point order (A/B timing)
     std::vector<unsigned long long> cost_total;  // RHS evaluations per point since the points were installed
-    IoArgs io_host{};
+    IoArgsExt io_host{};
     std::vector<unsigned char> h_refresh;
     int64_t n_rows = 0, n_members = 0;
     bool philox = false;
@@ -396,6 +396,15 @@ struct hc_handle {
     bool corr_host() const { return ncorr && philox && filt_stride <= 0 && !enkf_nz; }   // ... and nothing else owns base
     std::vector<double> ncorr_ab;
     DevBuf<double> ncorr_dev;
+    // perturbed forcing (hc_set_forcing_perturbation): on / off and the parameters; the carried state g [2][N], its second
+    // buffer for the particle filter's ancestry and the day it stands at (-1: none yet); the factors of one launch's days
+    bool fp_on = false;
+    double fp_sigma[2] = {}, fp_phi = 0.0, fp_c = 1.0;
+    uint64_t fp_seed = 0;
+    int64_t fp_day = -1;
+    int64_t fp_day_next = -1;    // the day fp_g_alt stands at: a fill is pending until its step launch is issued
+    int64_t fp_offset = -1;      // hc_set_forcing_member_offset (-1: the noise source's)
+    DevBuf<double> fp_g, fp_g_alt, fp_fmul;
     int n_cu = 256;
     double jac_reject = NUM_JAC_DIFF_REJECT;
 };
@@ -2216,7 +2225,8 @@ struct EnkfRow {
 
 // One standard normal of Philox4x32-10 under the EnKF seed at counter (word0, row, gid_lo, gid_hi), with the Box-Muller
 // step of philox_normal (its cosine branch): the well's eps_k at word0 = 0xFFFFFFFE, sensor i's at 0xFFFFFFF0 + i.  A noise
-// counter's first word is a depth index / 2 and the particle filter's draw has 0xFFFFFFFF: they never meet.
+// counter's first word is a depth index / 2 and the particle filter's draw has 0xFFFFFFFF: they never meet.  (The
+// perturbed forcing's two streams have 0xFFFFFFE0 and 0xFFFFFFE1: HC_FORCING_WORD_PRECIP / _DEMAND.)
 __device__ __forceinline__ double enkf_normal_at(uint32_t word0, unsigned long long seed, unsigned long long gid,
                                                  unsigned row)
 {
@@ -3594,7 +3604,8 @@ __device__ __forceinline__ bool rejuv_applies(const unsigned long long *surv, lo
 
 // The two standard normals of the node pair q = d >> 1 under the filter's seed at counter (0x80000000 | q, row, gid_lo,
 // gid_hi), with philox_normal's Box-Muller step: the cosine for the even node, the sine for the odd one.  A noise
-// counter's first word is below 2^31 and the filter's and the EnKF's are >= 0xFFFFFFF0: the streams never meet.
+// counter's first word is below 2^31, the perturbed forcing's are 0xFFFFFFE0 and 0xFFFFFFE1 and the filter's and the
+// EnKF's are >= 0xFFFFFFF0: the streams never meet.
 __device__ __forceinline__ void rejuv_normal_pair(unsigned long long seed, unsigned long long gid, unsigned row, uint32_t q,
                                                   double &even, double &odd)
 {
@@ -3616,6 +3627,62 @@ __device__ __forceinline__ unsigned long long rejuv_gid(const long long *point_b
                                                         long long mpp)
 {
     return point_base ? (unsigned long long)(point_base[m / mpp] + m % mpp) : (unsigned long long)(member_offset + m);
+}
+
+// ---- perturbed forcing (hc_set_forcing_perturbation, include/hydrocol.h)
+static_assert(FORCING_DAY_ROWS == HC_FORCING_DAY_ROWS, "one daily clock");
+struct ForcingPert {
+    double sigma[2], half[2];      // sigma_s and h_s = sigma_s^2 / 2
+    double phi, c;
+    unsigned long long seed;
+};
+
+// xi_{gid, day, s}: enkf_normal_at's block and Box-Muller step under the feature's seed at the stream's first word
+__device__ __forceinline__ double forcing_normal(const ForcingPert &F, int s, unsigned long long gid, long long day)
+{
+    return enkf_normal_at(s ? HC_FORCING_WORD_DEMAND : HC_FORCING_WORD_PRECIP, F.seed, gid, (unsigned)day);
+}
+
+// Thread e = s * count + j: stream s of slot first + j.  It starts from the carried g (standing at day g_day >= 0) or,
+// with none (g == NULL or g_day < 0), from g_0 = xi_0; walks the days up to day1 by the recursion; stores the factor of
+// every day >= day0 into fmul [day1 - day0 + 1][2][count] (consecutive threads, consecutive addresses) and, where g_out
+// is given, g of day1 into it: the host's second buffer, which replaces the carried one once the step launch is issued.
+// The host guarantees g_day <= day0 <= day1.
+__global__ __launch_bounds__(256) void forcing_factor_fill_kernel(const double *g, double *g_out, long long g_day,
+                                                                  long long g_stride, double *fmul,
+                                                                  long long first, long long count, long long day0,
+                                                                  long long day1, long long mpp, const long long *point_base,
+                                                                  long long member_offset, const ForcingPert F)
+{
+#pragma clang fp contract(off)
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= 2 * count) return;
+    const int s = (int)(e / count);
+    const long long j = e % count, m = first + j;
+    const unsigned long long gid = rejuv_gid(point_base, member_offset, m, mpp);
+    const bool carried = g != nullptr && g_day >= 0;
+    long long d = carried ? g_day : 0;
+    double gv = carried ? g[(size_t)s * g_stride + m] : forcing_normal(F, s, gid, 0);
+    for (;;) {
+        if (d >= day0) {
+            const double sg = F.sigma[s] * gv;
+            fmul[(size_t)((d - day0) * 2 + s) * count + j] = F.sigma[s] == 0.0 ? 1.0 : exp(sg - F.half[s]);
+        }
+        if (d >= day1) break;
+        d++;
+        const double keep = F.phi * gv, fresh = F.c * forcing_normal(F, s, gid, d);
+        gv = keep + fresh;
+    }
+    if (g_out) g_out[(size_t)s * g_stride + m] = gv;
+}
+
+// the raw normals of one stream key: out[n_days][2] (hc_forcing_normals)
+__global__ void forcing_normals_kernel(double *out, unsigned long long gid, long long first_day, long long n_days,
+                                       const ForcingPert F)
+{
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= 2 * n_days) return;
+    out[e] = forcing_normal(F, (int)(e % 2), gid, first_day + e / 2);
 }
 
 // One wave per member, the column layout of enkf_relax_kernel (node c * WAVE + lane in slot c):
@@ -3907,11 +3974,13 @@ int unknown_depth(hc_handle *h)
                 h->p.dim_d, h->cpl, HC_MAX_DEPTH_NODES, HC_CPL_MASK);
 }
 
-LaunchCfg launch_cfg(hc_handle *h, unsigned grid)
+LaunchCfg launch_cfg(hc_handle *h, unsigned grid, bool step = false)
 {
     // PREDICT is per point in the tables but one kernel serves the launch: any predictive point selects the build
-    // with the branch compiled in; a monitoring-mode point inside such a launch keeps its own semantics (flag_predict)
-    bool predict = false;
+    // with the branch compiled in; a monitoring-mode point inside such a launch keeps its own semantics (flag_predict).
+    // Those builds also carry the perturbed forcing's two products, so a step launch with the feature on takes them
+    // (the RHS hooks stay with the record and with the build they had).
+    bool predict = step && h->fp_on;
     for (const ColumnDev &P : h->P_host) predict = predict || P.flag_predict;
     return LaunchCfg{h->stream, grid, h->use_special(), predict};
 }
@@ -3928,14 +3997,14 @@ int launch_step(hc_handle *h, const StepArgs &A)
         StepArgs B = A;
         B.tab = h->tab_pair.p;
         B.gtab = h->gtab_pair.p;
-        HIP_TRY(launch_step_pair(launch_cfg(h, grid), B));
+        HIP_TRY(launch_step_pair(launch_cfg(h, grid, true), B));
         return HC_OK;
     }
     // persistent grid: LDS admits one workgroup per CU; fewer workgroups when there are fewer members
     const long long want = (A.n_members + wpb - 1) / wpb;
     const unsigned grid = (unsigned)std::min<long long>(want, (long long)h->n_cu);
     bool known = false;
-    const hipError_t err = launch_step_cpl_any(h->cpl, known, launch_cfg(h, grid), A);
+    const hipError_t err = launch_step_cpl_any(h->cpl, known, launch_cfg(h, grid, true), A);
     if (!known) return unknown_depth(h);
     HIP_TRY(err);
     return HC_OK;
@@ -4541,6 +4610,64 @@ int launch_noise_fill(hc_handle *h, double *out, int64_t n_vec, const long long 
 
 // what turns both filters and the noise correlation off: new points, members or noise source (include/hydrocol.h
 // hc_set_filter, hc_set_enkf, hc_set_noise_correlation)
+void forcing_pert_off(hc_handle *h)
+{
+    h->fp_on = false;
+    h->fp_day = h->fp_day_next = h->fp_offset = -1;
+    h->fp_g.release(), h->fp_g_alt.release(), h->fp_fmul.release();
+}
+
+// the global id of the handle's first member: the one given, else the Philox source's, else (host noise) 0
+long long forcing_member_offset(const hc_handle *h)
+{
+    return h->fp_offset >= 0 ? h->fp_offset : (h->philox ? h->member_offset : 0);
+}
+
+ForcingPert forcing_pert_of(const hc_handle *h)
+{
+    ForcingPert F;
+    for (int s = 0; s < 2; s++) {
+        F.sigma[s] = h->fp_sigma[s];
+        F.half[s] = h->fp_sigma[s] * h->fp_sigma[s] / 2.0;
+    }
+    F.phi = h->fp_phi;
+    F.c = h->fp_c;
+    F.seed = h->fp_seed;
+    return F;
+}
+
+// The factors of the days rows [row0, row0 + rows) touch -> fp_fmul [n_days][2][N], the state advanced to the last of them
+// in the second buffer (forcing_fill_commit takes it over once the step launch is issued: a launch that fails leaves the
+// state where it stood); IoArgs told where they are.  (fill_args has uploaded the points' keys.)
+int launch_forcing_fill(hc_handle *h, int64_t row0, int64_t rows)
+{
+    const long long N = h->n_members, day0 = row0 / HC_FORCING_DAY_ROWS, day1 = (row0 + rows - 1) / HC_FORCING_DAY_ROWS;
+    if (h->fp_day > day0)
+        return fail(HC_ERR_ARG, "perturbed forcing: row %lld lies in day %lld, behind day %lld the members' state stands at "
+                                "(hc_set_forcing_state or hc_set_forcing_perturbation rewinds it)", (long long)row0, day0,
+                    (long long)h->fp_day);
+    if (day1 > (long long)UINT32_MAX) return fail(HC_ERR_ARG, "perturbed forcing: day %lld exceeds 2^32 - 1", day1);
+    if (h->fp_g.ensure((size_t)(2 * N)) || h->fp_g_alt.ensure((size_t)(2 * N)) ||
+        h->fp_fmul.ensure((size_t)((day1 - day0 + 1) * 2 * N)))
+        return HC_ERR_DEVICE;
+    hipLaunchKernelGGL(forcing_factor_fill_kernel, dim3((unsigned)((2 * N + 255) / 256)), dim3(256), 0, h->stream, h->fp_g.p,
+                       h->fp_g_alt.p, (long long)h->fp_day, N, h->fp_fmul.p, 0LL, N, day0, day1, N / h->n_points,
+                       h->n_points > 1 ? h->point_base.p : nullptr, forcing_member_offset(h), forcing_pert_of(h));
+    HIP_TRY(hipGetLastError());
+    h->fp_day_next = day1;
+    h->io_host.fmul = h->fp_fmul.p;
+    h->io_host.fmul_day0 = day0;
+    return HC_OK;
+}
+
+void forcing_fill_commit(hc_handle *h)
+{
+    if (h->fp_day_next < 0) return;
+    std::swap(h->fp_g, h->fp_g_alt);
+    h->fp_day = h->fp_day_next;
+    h->fp_day_next = -1;
+}
+
 void assimilation_off(hc_handle *h)
 {
     filter_off(h);
@@ -4591,7 +4718,7 @@ int table_reset(hc_handle *h, AccTable<T> &t, int (*ensure)(hc_handle *))
 
 int push_io(hc_handle *h)
 {
-    HIP_TRY(hipMemcpyAsync(h->iodev.p, &h->io_host, sizeof(IoArgs), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->iodev.p, &h->io_host, sizeof(IoArgsExt), hipMemcpyHostToDevice, h->stream));
     return HC_OK;
 }
 
@@ -4602,7 +4729,7 @@ int fill_args(hc_handle *h, StepArgs &A)
     if (h->n_members <= 0 || !h->psi.p) return fail(HC_ERR_ARG, "hc_set_members / hc_set_state has not been called");
     if (!h->have_noise) return fail(HC_ERR_ARG, "no noise source: call hc_set_noise_host or hc_set_noise_philox");
     memset(&A, 0, sizeof(A));
-    IoArgs &io = h->io_host;
+    IoArgsExt &io = h->io_host;
     memset(&io, 0, sizeof(io));
     const int NP = h->n_points;
     if (h->n_members % NP != 0)
@@ -4800,6 +4927,7 @@ int hc_destroy(hc_handle *h)
     h->pacc.release(); h->pacc_alt.release(); h->pmom.release(); h->phist.release();
     uptake_off(h);
     assimilation_off(h);
+    forcing_pert_off(h);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -4911,6 +5039,10 @@ static int build_point(hc_handle *h, const hc_column_params *p, const double *no
         (void)hipStreamSynchronize(h->stream);
         assimilation_off(h);
     }
+    if (h->fp_on) {              // ... and so is the perturbed forcing (its state is the members' of the old points)
+        (void)hipStreamSynchronize(h->stream);
+        forcing_pert_off(h);
+    }
     if (first) {                 // a new column: the root uptake (hc_set_root_uptake) is off
         if (h->upt_layers > 0) (void)hipStreamSynchronize(h->stream);
         uptake_off(h);
@@ -4996,6 +5128,10 @@ int hc_set_forcing(hc_handle *h, int64_t n_rows, const double *precip, const dou
     if (!h || n_rows < 1 || !precip || !atm || !daylight || !wtd_obs || !refresh)
         return fail(HC_ERR_ARG, "hc_set_forcing: bad argument");
     HIP_TRY(hipSetDevice(h->device));
+    if (h->fp_on) {              // another record: the perturbed forcing is off
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        forcing_pert_off(h);
+    }
     const size_t T = (size_t)n_rows;
     // A skipped row (wtd_obs < 0) consumes no noise draw: the reference `continue`s before drawing
     // (simulation.py:582-588 come before :599-602), so its refresh flag is dropped here for everybody downstream.
@@ -5053,6 +5189,7 @@ int hc_set_members(hc_handle *h, int64_t n_members)
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
     assimilation_off(h);
+    forcing_pert_off(h);         // the perturbed forcing's state is the members': off
     uptake_off(h);               // the root uptake's accumulators are the members': off
     const size_t n = (size_t)n_members * h->p.dim_d;
     if (h->psi.ensure(n) || h->nscale.ensure((size_t)n_members)) return HC_ERR_DEVICE;
@@ -5710,6 +5847,10 @@ int launch_chunk(hc_handle *h, StepArgs &A, const hc_step_args *a, const Chunk &
     h->io_host.stats = a->stats_out ? h->stats.p : nullptr;
     h->io_host.psi_rows = (a->psi_rows_out || c.stage_all) ? h->psi_rows.p : nullptr;
     h->io_host.diag = (a->diag_out || diag_on) ? h->diag.p : nullptr;
+    h->io_host.fmul = nullptr;
+    h->fp_day_next = -1;
+    if (h->fp_on && !a->spinup)
+        if (int rc = launch_forcing_fill(h, c.row0, c.rows)) return rc;
     if (int rc = push_io(h)) return rc;
     if (h->n_points > 1) {
         HIP_TRY(hipMemcpyAsync(h->point_order.p, h->order_host.data(), (size_t)h->n_points * 4, hipMemcpyHostToDevice,
@@ -5718,6 +5859,7 @@ int launch_chunk(hc_handle *h, StepArgs &A, const hc_step_args *a, const Chunk &
     }
     HIP_TRY(hipEventRecord(h->ev0, h->stream));
     if (int rc = launch_step(h, A)) return rc;
+    forcing_fill_commit(h);      // the step launch is issued: the perturbed forcing's state stands at its last day
     HIP_TRY(hipEventRecord(h->ev1, h->stream));
     return HC_OK;
 }
@@ -6148,6 +6290,17 @@ int assimilate(hc_handle *h, const Chunk &c)
                                h->uacc_alt.p, (long long)N, K);
             HIP_TRY(hipGetLastError());
             std::swap(h->uacc.buf, h->uacc_alt);
+        }
+        if (h->fp_on && h->fp_day >= 0) {
+            // ... and so does the perturbed forcing's g, a latent state of the member's trajectory: its two planes as
+            // 8-byte words
+            if (h->fp_g_alt.ensure((size_t)(2 * N))) return HC_ERR_DEVICE;
+            const unsigned gblocks = (unsigned)std::min<size_t>(((size_t)N * 2 + 255) / 256, (size_t)h->n_cu * 64);
+            hipLaunchKernelGGL(period_gather_kernel, dim3(gblocks), dim3(256), 0, h->stream, h->filt_anc.p,
+                               reinterpret_cast<const long long *>(h->fp_g.p), reinterpret_cast<long long *>(h->fp_g_alt.p),
+                               (long long)N, 2);
+            HIP_TRY(hipGetLastError());
+            std::swap(h->fp_g, h->fp_g_alt);
         }
     }
     if (s.ms > 0) {
@@ -8057,6 +8210,9 @@ int hc_set_filter_shard(hc_handle *h, int32_t n_shards, const int64_t *bounds, i
     if (h->upt_layers > 0)
         return fail(HC_ERR_ARG, "hc_set_filter_shard: the root uptake is set (hc_set_root_uptake), and the routed columns do "
                                 "not carry the members' accumulators");
+    if (h->fp_on)
+        return fail(HC_ERR_ARG, "hc_set_filter_shard: the forcing is perturbed (hc_set_forcing_perturbation), and the routed "
+                                "columns do not carry the members' forcing state");
     if (!device_buf || !gather || !route) return fail(HC_ERR_ARG, "hc_set_filter_shard: NULL buffer or callback");
     const int64_t need = filter_shard_layout(np, h->n_members, n_shards, h->p.dim_d).words;
     if (n_words < need)
@@ -8668,12 +8824,166 @@ int hc_set_point_member_bases(hc_handle *h, const int64_t *base)
         HIP_TRY(hipStreamSynchronize(h->stream));
         assimilation_off(h);
     }
+    if (h->fp_on) {              // ... and so is the perturbed forcing, keyed by them
+        HIP_TRY(hipSetDevice(h->device));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        forcing_pert_off(h);
+    }
     h->base_host.clear();
     if (base) {
         for (int k = 0; k < h->n_points; k++)
             if (base[k] < 0) return fail(HC_ERR_ARG, "member base of point %d is negative", k);
         h->base_host.assign(base, base + h->n_points);
     }
+    return HC_OK;
+}
+
+// ---- perturbed forcing (include/hydrocol.h)
+int hc_set_forcing_perturbation(hc_handle *h, double sigma_precip, double sigma_demand, double phi, double c, uint64_t seed)
+{
+    if (!h) return fail(HC_ERR_ARG, "NULL handle");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    forcing_pert_off(h);                          // (and off it stays when the parameters are refused)
+    if (!h->have_column || !h->have_forcing || h->n_members <= 0 || !h->psi.p)
+        return fail(HC_ERR_ARG, "hc_set_forcing_perturbation: hc_set_column, hc_set_forcing, hc_set_members and hc_set_state "
+                                "must come first");
+    if (!std::isfinite(sigma_precip) || !std::isfinite(sigma_demand) || !std::isfinite(phi) || !std::isfinite(c))
+        return fail(HC_ERR_ARG, "hc_set_forcing_perturbation: sigma = %g, %g, phi = %g, c = %g not finite", sigma_precip,
+                    sigma_demand, phi, c);
+    if (!(sigma_precip >= 0.0 && sigma_precip <= 1.0) || !(sigma_demand >= 0.0 && sigma_demand <= 1.0))
+        return fail(HC_ERR_ARG, "hc_set_forcing_perturbation: sigma = %g, %g outside [0, 1]", sigma_precip, sigma_demand);
+    if (!(phi >= 0.0 && phi < 1.0) || !(c > 0.0))
+        return fail(HC_ERR_ARG, "hc_set_forcing_perturbation: phi = %g outside [0, 1) or c = %g <= 0", phi, c);
+    if (std::fabs(phi * phi + c * c - 1.0) > 1e-12)
+        return fail(HC_ERR_ARG, "hc_set_forcing_perturbation: phi = %g, c = %g is no unit-variance step (phi^2 + c^2 = 1)", phi, c);
+    if (h->fs_n > 0)
+        return fail(HC_ERR_ARG, "hc_set_forcing_perturbation: the particle filter is sharded (hc_set_filter_shard), and the "
+                                "routed columns do not carry the members' forcing state");
+    if (h->n_members % h->n_points != 0)
+        return fail(HC_ERR_ARG, "%lld members do not divide into %d parameter points", (long long)h->n_members, h->n_points);
+    h->fp_sigma[0] = sigma_precip;
+    h->fp_sigma[1] = sigma_demand;
+    h->fp_phi = phi;
+    h->fp_c = c;
+    h->fp_seed = seed;
+    h->fp_on = true;
+    return HC_OK;
+}
+
+int hc_set_forcing_member_offset(hc_handle *h, int64_t member_offset)
+{
+    if (!h || member_offset < 0) return fail(HC_ERR_ARG, "hc_set_forcing_member_offset: bad argument");
+    if (!h->fp_on)
+        return fail(HC_ERR_ARG, "hc_set_forcing_member_offset: the forcing is not perturbed (hc_set_forcing_perturbation)");
+    if (h->n_points > 1)
+        return fail(HC_ERR_ARG, "hc_set_forcing_member_offset: %d parameter points: their members' ids are those of "
+                                "hc_set_point_member_bases", h->n_points);
+    if (h->fp_day >= 0)
+        return fail(HC_ERR_ARG, "hc_set_forcing_member_offset: rows have been stepped (the state stands at day %lld): set the "
+                                "offset first", (long long)h->fp_day);
+    h->fp_offset = member_offset;
+    return HC_OK;
+}
+
+int hc_clear_forcing_perturbation(hc_handle *h)
+{
+    if (!h) return fail(HC_ERR_ARG, "NULL handle");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    forcing_pert_off(h);
+    return HC_OK;
+}
+
+int hc_get_forcing_perturbation(hc_handle *h, int32_t *on, double *sigma_precip, double *sigma_demand, double *phi, double *c,
+                                uint64_t *seed)
+{
+    if (!h || !on) return fail(HC_ERR_ARG, "hc_get_forcing_perturbation: bad argument");
+    *on = h->fp_on ? 1 : 0;
+    if (!h->fp_on) return HC_OK;
+    if (sigma_precip) *sigma_precip = h->fp_sigma[0];
+    if (sigma_demand) *sigma_demand = h->fp_sigma[1];
+    if (phi) *phi = h->fp_phi;
+    if (c) *c = h->fp_c;
+    if (seed) *seed = h->fp_seed;
+    return HC_OK;
+}
+
+int hc_get_forcing_state(hc_handle *h, double *g, int64_t *day)
+{
+    if (!h || !g || !day) return fail(HC_ERR_ARG, "hc_get_forcing_state: bad argument");
+    if (!h->fp_on) return fail(HC_ERR_ARG, "hc_get_forcing_state: the forcing is not perturbed (hc_set_forcing_perturbation)");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    *day = h->fp_day;
+    const size_t n = (size_t)(2 * h->n_members);
+    if (h->fp_day < 0) std::fill(g, g + n, 0.0);
+    else HIP_TRY(hipMemcpy(g, h->fp_g.p, n * 8, hipMemcpyDeviceToHost));
+    return HC_OK;
+}
+
+int hc_set_forcing_state(hc_handle *h, const double *g, int64_t day)
+{
+    if (!h || !g || day < -1 || day > (int64_t)UINT32_MAX) return fail(HC_ERR_ARG, "hc_set_forcing_state: bad argument");
+    if (!h->fp_on) return fail(HC_ERR_ARG, "hc_set_forcing_state: the forcing is not perturbed (hc_set_forcing_perturbation)");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const size_t n = (size_t)(2 * h->n_members);
+    if (day >= 0) {
+        for (size_t i = 0; i < n; i++)
+            if (!std::isfinite(g[i])) return fail(HC_ERR_ARG, "hc_set_forcing_state: entry %zu is not finite", i);
+        if (h->fp_g.ensure(n)) return HC_ERR_DEVICE;
+        HIP_TRY(hipMemcpy(h->fp_g.p, g, n * 8, hipMemcpyHostToDevice));
+    }
+    h->fp_day = day;
+    return HC_OK;
+}
+
+int hc_forcing_normals(hc_handle *h, int64_t member, int64_t first_day, int64_t n_days, double *out)
+{
+    if (!h || !out || member < 0 || first_day < 0 || n_days < 1 || first_day + n_days - 1 > (int64_t)UINT32_MAX)
+        return fail(HC_ERR_ARG, "hc_forcing_normals: bad argument");
+    if (!h->fp_on) return fail(HC_ERR_ARG, "hc_forcing_normals: the forcing is not perturbed (hc_set_forcing_perturbation)");
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t n = (size_t)(2 * n_days);
+    if (h->scratch_d.ensure(n)) return HC_ERR_DEVICE;
+    hipLaunchKernelGGL(forcing_normals_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->scratch_d.p,
+                       (unsigned long long)member, (long long)first_day, (long long)n_days, forcing_pert_of(h));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(out, h->scratch_d.p, n * 8, hipMemcpyDeviceToHost));
+    return HC_OK;
+}
+
+int hc_forcing_factors(hc_handle *h, int64_t first_member, int64_t count, int64_t first_day, int64_t n_days, double *out)
+{
+    if (!h || !out || first_member < 0 || count < 1 || first_day < 0 || n_days < 1 ||
+        first_day + n_days - 1 > (int64_t)UINT32_MAX)
+        return fail(HC_ERR_ARG, "hc_forcing_factors: bad argument");
+    if (!h->fp_on) return fail(HC_ERR_ARG, "hc_forcing_factors: the forcing is not perturbed (hc_set_forcing_perturbation)");
+    if (first_member + count > h->n_members) return fail(HC_ERR_ARG, "hc_forcing_factors: bad member range");
+    HIP_TRY(hipSetDevice(h->device));
+    const int NP = h->n_points;
+    const long long mpp = h->n_members / NP;
+    if (NP > 1) {                                 // the points' keys as fill_args uploads them
+        if (h->point_base.ensure((size_t)NP)) return HC_ERR_DEVICE;
+        std::vector<long long> base(h->base_host);
+        if ((int)base.size() != NP) {
+            base.resize((size_t)NP);
+            for (int k = 0; k < NP; k++) base[(size_t)k] = h->member_offset + (long long)k * mpp;
+        }
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY(hipMemcpy(h->point_base.p, base.data(), (size_t)NP * 8, hipMemcpyHostToDevice));
+    }
+    const size_t n = (size_t)(n_days * 2 * count);
+    if (h->scratch_d.ensure(n)) return HC_ERR_DEVICE;
+    hipLaunchKernelGGL(forcing_factor_fill_kernel, dim3((unsigned)((2 * count + 255) / 256)), dim3(256), 0, h->stream,
+                       (const double *)nullptr, (double *)nullptr, -1LL, 0LL, h->scratch_d.p, (long long)first_member,
+                       (long long)count, (long long)first_day, (long long)(first_day + n_days - 1), mpp,
+                       NP > 1 ? h->point_base.p : nullptr, forcing_member_offset(h), forcing_pert_of(h));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(out, h->scratch_d.p, n * 8, hipMemcpyDeviceToHost));
     return HC_OK;
 }
 

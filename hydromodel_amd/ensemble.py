@@ -11,6 +11,7 @@ import numpy as np
 from .digest import inverse_retention
 from .stepper import enkf_noise_summary, noise_field_settings
 from .stepper import theta_cov_finish, theta_sensor_gain
+from .stepper import forcing_coefficients, forcing_perturbation_settings
 from .stepper import noise_correlation_breaks, noise_correlation_settings, noise_correlation_tables
 from .stepper import DIAG_TABLES, diag_checkpoint, diag_from_checkpoint
 from .stepper import (ASSIM_TABLES, ENKF_METHODS, EnsembleStepper, enkf_sm_summary, enkf_summary,
@@ -160,6 +161,11 @@ class _Run:
     enkf_window_offsets: rows before each analysis row (integers in [1, enkf_stride), e.g. (12, 24, 36)) on which the
     well's record joins that analysis too -- the asynchronous EnKF (include/hydrocol.h hc_set_enkf_window);
     :meth:`enkf_window_table`, the ``window_*`` keys of :meth:`enkf_summary`.
+    forcing_perturbation: {"precipitation_sigma": .., "demand_sigma": .., "correlation_days": .., "seed": ..} or None: every
+    member sees the record's rainfall and atmospheric demand times a log-normal factor of mean one of its own, constant
+    over a day and an AR(1) from day to day (include/hydrocol.h hc_set_forcing_perturbation); at least one sigma, in
+    [0, 1]; correlation_days in [0, 365], default 0; seed default: the ensemble's.  Set after the spin-up, before the
+    filters; the particle filter moves the members' state with them; ``dump`` / ``restore`` carry it.
     noise_correlation: {"length_cm": l, "layers": bool} or None: the Philox source's base and refresh vectors become
     exponentially correlated fields of unit variance down the column (include/hydrocol.h hc_set_noise_correlation),
     with ``layers`` independent across the interfaces of ``cols.layers`` inside the column; applied after the spin-up
@@ -288,6 +294,46 @@ class _Run:
         self.noise_correlation_a = a.reshape(self._lead + a.shape[1:])          # [D]; a sweep: [P][D]
         self.noise_correlation_b = b.reshape(self._lead + b.shape[1:])
         self.noise_correlation_breaks_cm = tuple(breaks) if self._lead else breaks[0]
+
+    def _start_forcing_perturbation(self, settings):
+        """Perturb the members' rainfall and demand (include/hydrocol.h hc_set_forcing_perturbation): after the spin-up,
+        before the filters.  ``settings``: what :func:`stepper.forcing_perturbation_settings` returned."""
+        self.forcing_perturbation = None
+        if settings is None:
+            return
+        seed = self.seed if settings["seed"] is None else settings["seed"]
+        phi, c = forcing_coefficients(settings["correlation_days"])
+        # a shard of a host-noise ensemble has no stream key of its own: the feature is told the first member's id
+        offset = self.member_offset if getattr(self, "noise", "philox") == "numpy" else None
+        self.stepper.set_forcing_perturbation(settings["precipitation_sigma"], settings["demand_sigma"], seed=seed, phi=phi, c=c,
+                                              member_offset=offset)
+        self.forcing_perturbation = dict(settings, seed=int(seed), phi=phi)
+
+    def _dump_forcing_perturbation(self, arrays):
+        """... its parameters and the members' state into a checkpoint's arrays (a run without it keeps its key set)"""
+        if self.forcing_perturbation is None:
+            return
+        fp = self.forcing_perturbation
+        arrays["forcing_precipitation_sigma"] = np.array(fp["precipitation_sigma"], dtype=np.float64)
+        arrays["forcing_demand_sigma"] = np.array(fp["demand_sigma"], dtype=np.float64)
+        arrays["forcing_correlation_days"] = np.array(fp["correlation_days"], dtype=np.float64)
+        arrays["forcing_seed"] = np.array(fp["seed"], dtype=np.uint64)
+        g, day = self.stepper.forcing_state()
+        arrays["forcing_state"], arrays["forcing_state_day"] = g, np.array(day, dtype=np.int64)
+
+    @staticmethod
+    def _restored_forcing_perturbation(data):
+        """... and the constructor's argument back out of them (None: the checkpoint has none)"""
+        if "forcing_precipitation_sigma" not in data:
+            return None
+        return {"precipitation_sigma": float(data["forcing_precipitation_sigma"]),
+                "demand_sigma": float(data["forcing_demand_sigma"]),
+                "correlation_days": float(data["forcing_correlation_days"]), "seed": int(data["forcing_seed"])}
+
+    def _restore_forcing_state(self, data):
+        if self.forcing_perturbation is not None:
+            g = np.asarray(data["forcing_state"], dtype=np.float64).reshape(2, -1)
+            self.stepper.set_forcing_state(g, int(np.asarray(data["forcing_state_day"]).reshape(-1)[0]))
 
     def noise_correlation_break_count(self):
         """Breaks of the recursion below node 0, over all points."""
@@ -657,8 +703,13 @@ class EnsembleSimulation(_Run):
                  theta_hist_bins=0, storage_layers_cm=None, storage_bins=0, period_ends=None, period_thresholds_cm=(),
                  period_bins=0, period_flux_max_cm=(16.0, 4.0), filter_ess_floor=0.0, filter_window_offsets=(),
                  enkf_noise_field=None, filter_rejuvenation=0.0, noise_correlation=None,
-                 theta_cov_stride=0, uptake_layers_cm=None, uptake_bins=0, filter_smoother=None):
+                 theta_cov_stride=0, uptake_layers_cm=None, uptake_bins=0, filter_smoother=None,
+                 forcing_perturbation=None):
         corr = self._check_noise_correlation("EnsembleSimulation", noise_correlation, noise, filter_rejuvenation)
+        pert = forcing_perturbation_settings(forcing_perturbation)
+        if filter_shard is not None and pert is not None:
+            raise ValueError("filter_shard and forcing_perturbation exclude each other: the routed columns do not carry the "
+                             "members' forcing state")
         if enkf_shard is not None and noise_field_settings(enkf_noise_field, 0.0) is not None:
             raise ValueError("enkf_shard and enkf_noise_field exclude each other: the exchanged partials cover psi only")
         if filter_shard is not None and rejuvenation_discount(filter_rejuvenation):
@@ -683,6 +734,7 @@ class EnsembleSimulation(_Run):
             _lib.load(with_torch=True)             # torch before the library: the shard's buffer is a torch tensor
         self._start(cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup)
         self._start_noise_correlation(corr, [cols])
+        self._start_forcing_perturbation(pert)
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
                            enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins, storage_layers_cm,
@@ -858,6 +910,7 @@ class EnsembleSimulation(_Run):
             if not self.filter_stride and self.enkf_noise_relaxation is None:
                 # the base vectors carry the damping, as a filtered run's; those runs' own keys hold them already
                 arrays["noise_field_base"] = self.stepper.noise_field_base()
+        self._dump_forcing_perturbation(arrays)
         for key in self.assim_tables_on():                # the filters' tables: one dataset each, <key>_table
             arrays[key + "_table"] = self.stepper.assim_table(key)
         path = Path(path)
@@ -944,8 +997,12 @@ class EnsembleSimulation(_Run):
         if has_corr:
             fkw.update(noise_correlation={"length_cm": float(data["noise_correlation_length_cm"]),
                                           "layers": bool(int(data["noise_correlation_layers"]))})
+        pert = cls._restored_forcing_perturbation(data)
+        if pert is not None:
+            fkw.update(forcing_perturbation=pert)
         sim = cls(cols, forcing, n, seed=int(data["seed"]), device=device, member_offset=int(data["member_offset"]),
                   psi0=np.asarray(data["initial_cond"], dtype=float).reshape(-1)[:D], flags=flags, **fkw)
+        sim._restore_forcing_state(data)
         if has_corr and not (np.array_equal(np.asarray(data["noise_correlation_a"]).reshape(-1), sim.noise_correlation_a)
                              and np.array_equal(np.asarray(data["noise_correlation_b"]).reshape(-1), sim.noise_correlation_b)):
             raise ValueError(f" EnsembleSimulation: {path} holds the noise correlation's tables of another column.")
@@ -1073,8 +1130,10 @@ class SweepSimulation(_Run):
                  filter_soil_moisture=None, theta_hist_bins=0, storage_layers_cm=None, storage_bins=0, period_ends=None,
                  period_thresholds_cm=(), period_bins=0, period_flux_max_cm=(16.0, 4.0), filter_ess_floor=0.0,
                  filter_window_offsets=(), enkf_noise_field=None, filter_rejuvenation=0.0, noise_correlation=None,
-                 theta_cov_stride=0, uptake_layers_cm=None, uptake_bins=0, filter_smoother=None):
+                 theta_cov_stride=0, uptake_layers_cm=None, uptake_bins=0, filter_smoother=None,
+                 forcing_perturbation=None):
         corr = self._check_noise_correlation("SweepSimulation", noise_correlation, "philox", filter_rejuvenation)
+        pert = forcing_perturbation_settings(forcing_perturbation)
         self.points = list(cols_list)
         self.P, self.n = len(self.points), int(n_members)
         self._lead = (self.P,)
@@ -1102,6 +1161,7 @@ class SweepSimulation(_Run):
         if self.P > 1:
             self.stepper.set_point_member_bases(self.bases)
         self._start_noise_correlation(corr, self.points)
+        self._start_forcing_perturbation(pert)
         self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
                            enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
                            enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins, storage_layers_cm,

@@ -204,6 +204,65 @@ class EnsembleStepper:
             raise ValueError(f"base noise must be [{self.N}, {self.D}]")
         L.check(self.lib.hc_set_noise_field_base(self.h, L.dptr(base)))
 
+    # -- perturbed forcing (include/hydrocol.h hc_set_forcing_perturbation) --------------------------------------------
+    def set_forcing_perturbation(self, precipitation_sigma=0.0, demand_sigma=0.0, correlation_days=0.0, seed=0, phi=None,
+                                 c=None, member_offset=None):
+        """Give every member its own log-normal factor of mean one on the rainfall and on the atmospheric demand, per
+        day (row // 48), an AR(1) in time with e-folding time ``correlation_days`` (or explicit ``phi``, ``c``); the
+        recursion is :func:`forcing_recursion_of`.  Both sigmas 0 keeps every factor at exactly 1.0 on the wider build.
+        ``None`` as the first argument turns it off.  Set it after the spin-up and before a filter.  The members are
+        keyed by the global ids of their noise streams; ``member_offset`` gives the first member's id where there is no
+        such stream (a shard of a host-noise ensemble: otherwise its ids start at 0)."""
+        if precipitation_sigma is None:
+            L.check(self.lib.hc_clear_forcing_perturbation(self.h))
+            return
+        if phi is None:
+            phi, c = forcing_coefficients(correlation_days)
+        L.check(self.lib.hc_set_forcing_perturbation(self.h, float(precipitation_sigma), float(demand_sigma), float(phi),
+                                                     float(c), int(seed)))
+        if member_offset is not None:
+            L.check(self.lib.hc_set_forcing_member_offset(self.h, int(member_offset)))
+
+    def forcing_perturbation(self):
+        """``None`` while it is off, else ``{"precipitation_sigma", "demand_sigma", "phi", "c", "seed"}`` as the library
+        holds them."""
+        on = np.zeros(1, dtype=np.int32)
+        v = np.zeros(4)
+        seed = C.c_uint64(0)
+        L.check(self.lib.hc_get_forcing_perturbation(self.h, L.iptr(on), L.dptr(v[0:]), L.dptr(v[1:]), L.dptr(v[2:]),
+                                                     L.dptr(v[3:]), C.byref(seed)))
+        if not on[0]:
+            return None
+        return {"precipitation_sigma": float(v[0]), "demand_sigma": float(v[1]), "phi": float(v[2]), "c": float(v[3]),
+                "seed": int(seed.value)}
+
+    def forcing_state(self):
+        """(g [2][N], day): the members' AR(1) state of the two streams and the day it stands at (-1: no row stepped
+        yet); a checkpoint's."""
+        g = np.empty((2, self.N))
+        day = C.c_int64(0)
+        L.check(self.lib.hc_get_forcing_state(self.h, L.dptr(g), C.byref(day)))
+        return g, int(day.value)
+
+    def set_forcing_state(self, g, day):
+        g = L.as_f64(g)
+        if g.shape != (2, self.N):
+            raise ValueError(f"the forcing state must be [2, {self.N}]")
+        L.check(self.lib.hc_set_forcing_state(self.h, L.dptr(g), int(day)))
+
+    def forcing_normals(self, member, first_day, n_days):
+        """[n_days][2] the raw normals xi of the stream key ``member`` (a global id) for the two streams (test hook)."""
+        out = np.empty((int(n_days), 2))
+        L.check(self.lib.hc_forcing_normals(self.h, int(member), int(first_day), int(n_days), L.dptr(out)))
+        return out
+
+    def forcing_factors(self, first_member, count, first_day, n_days):
+        """[n_days][2][count] the factors of the handle's slots first_member ... by the stateless recursion from day 0, on
+        the device code that fills them for the step kernel (valid for slots no resampling has touched)."""
+        out = np.empty((int(n_days), 2, int(count)))
+        L.check(self.lib.hc_forcing_factors(self.h, int(first_member), int(count), int(first_day), int(n_days), L.dptr(out)))
+        return out
+
     # -- stepping ------------------------------------------------------------------
     def n_refresh(self, row_begin, n_rows):
         """Noise vectors rows [row_begin, row_begin + n_rows) consume: refresh rows that are actually solved (a row
@@ -2944,6 +3003,85 @@ def noise_correlate(xi, a, b):
         step = (a[..., i] * z[..., i - 1]) + (b[..., i] * xi[..., i])
         z[..., i] = np.where(a[..., i] == 0.0, xi[..., i], step)
     return z
+
+
+# ---- perturbed forcing (include/hydrocol.h hc_set_forcing_perturbation) --------------------------------------------------
+FORCING_DAY_ROWS = 48
+
+
+def forcing_day_of_row(row):
+    """The day of forcing row ``row``: row // 48, the model's daily clock."""
+    return np.asarray(row) // FORCING_DAY_ROWS
+
+
+def forcing_coefficients(correlation_days):
+    """(phi, c) of the AR(1) with e-folding time ``correlation_days``: phi = exp(-1 / tau), c = sqrt(1 - phi phi);
+    tau = 0 gives (0, 1), white in time."""
+    if isinstance(correlation_days, (bool, np.bool_)) or not isinstance(correlation_days, (int, float, np.integer, np.floating)):
+        raise ValueError(f"forcing perturbation: correlation_days = {correlation_days!r} must be a finite number >= 0")
+    tau = float(correlation_days)
+    if not (np.isfinite(tau) and tau >= 0.0):
+        raise ValueError(f"forcing perturbation: correlation_days = {correlation_days!r} must be a finite number >= 0")
+    if tau == 0.0:
+        return 0.0, 1.0
+    phi = float(np.exp(-1.0 / tau))
+    c = float(np.sqrt(1.0 - phi * phi))
+    if not (phi < 1.0 and c > 0.0):
+        raise ValueError(f"forcing perturbation: correlation_days = {correlation_days!r} is too long: phi rounds to 1")
+    return phi, c
+
+
+def forcing_recursion_of(xi, phi, c):
+    """g of the normals ``xi`` [n_days, ...] (days along the FIRST axis), the library's recursion to the bit:
+    g_0 = xi_0, g_k = (phi g_{k-1}) + (c xi_k)."""
+    xi = np.asarray(xi, dtype=np.float64)
+    phi, c = np.float64(phi), np.float64(c)
+    g = xi.copy()
+    for k in range(1, xi.shape[0]):
+        g[k] = (phi * g[k - 1]) + (c * xi[k])
+    return g
+
+
+def forcing_factors_of(g, sigma):
+    """exp((sigma g) - sigma^2 / 2) as NumPy evaluates it, exactly 1.0 where sigma == 0 (the library's rule; its exp may
+    differ from NumPy's in the last bits)."""
+    g = np.asarray(g, dtype=np.float64)
+    sigma = np.float64(sigma)
+    if sigma == 0.0:
+        return np.ones_like(g)
+    return np.exp((sigma * g) - (sigma * sigma / 2.0))
+
+
+def forcing_perturbation_settings(value):
+    """The ``forcing_perturbation=`` argument of EnsembleSimulation / SweepSimulation: ``None`` or
+    ``{"precipitation_sigma": .., "demand_sigma": .., "correlation_days": .., "seed": ..}`` -> ``None`` or the dict
+    with every key present (seed ``None``: the ensemble's)."""
+    if value is None:
+        return None
+    if not isinstance(value, dict):
+        raise ValueError(f"forcing_perturbation = {value!r} must be a dict")
+    known = {"precipitation_sigma", "demand_sigma", "correlation_days", "seed"}
+    if set(value) - known:
+        raise ValueError(f"forcing_perturbation: unknown key(s) {sorted(set(value) - known)}; known: {sorted(known)}")
+    if "precipitation_sigma" not in value and "demand_sigma" not in value:
+        raise ValueError("forcing_perturbation needs precipitation_sigma or demand_sigma")
+    out = {}
+    for key in ("precipitation_sigma", "demand_sigma"):
+        v = value.get(key, 0.0)
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(float(v)) or not 0.0 <= float(v) <= 1.0:
+            raise ValueError(f"forcing_perturbation: {key} = {v!r} must be a finite number in [0, 1]")
+        out[key] = float(v)
+    tau = value.get("correlation_days", 0.0)
+    forcing_coefficients(tau)
+    if float(tau) > 365.0:
+        raise ValueError(f"forcing_perturbation: correlation_days = {tau!r} must lie in [0, 365]")
+    out["correlation_days"] = float(tau)
+    seed = value.get("seed")
+    if seed is not None and (isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or seed < 0):
+        raise ValueError(f"forcing_perturbation: seed = {seed!r} must be an integer >= 0")
+    out["seed"] = None if seed is None else int(seed)
+    return out
 
 
 def noise_correlation_breaks(layers, z):

@@ -243,6 +243,64 @@ int hc_noise_field_normals(hc_handle *h, int64_t member, int64_t draw, double *o
 int hc_get_noise_field_base(hc_handle *h, double *base, int64_t first_member, int64_t count);
 int hc_set_noise_field_base(hc_handle *h, const double *base);
 
+/* Perturbed forcing: a multiplicative log-normal error per member on the two forcing streams, s = 0 precipitation and
+ * s = 1 atmospheric demand, with memory in time.
+ *   The day of forcing row i is k = i / 48 (integer division: the model's own daily clock, the one the noise refresh
+ *   runs on).  xi_{m,k,s} is the standard normal of ONE Philox4x32-10 block keyed by `seed` at the counter
+ *   (word_s, k, gid_lo, gid_hi), word_0 = HC_FORCING_WORD_PRECIP, word_1 = HC_FORCING_WORD_DEMAND, taken from the cosine
+ *   branch of the Box-Muller step as the EnKF's draws are.  (First counter words in use: the noise streams depth / 2
+ *   < 2^31, the rejuvenation jitter 0x80000000 | depth / 2, the EnKF 0xFFFFFFF0 + i and 0xFFFFFFFE, the particle filter
+ *   0xFFFFFFFF: the streams never meet.)  gid is the member's global id, the one its noise stream is keyed by:
+ *   member_offset + m, or with several points point_base[k] + j.  A host-noise run has no such stream: its ids are
+ *   0 + m unless hc_set_forcing_member_offset gives the first member's id (the shards of one host-noise ensemble).
+ *   In fp64 with contraction off, one product, one product, one sum, in this order:
+ *       g_{m,0,s} = xi_{m,0,s}
+ *       g_{m,k,s} = (phi * g_{m,k-1,s}) + (c * xi_{m,k,s})          an AR(1) of unit variance
+ *       f_{m,k,s} = exp((sigma_s * g_{m,k,s}) - h_s)                 a log-normal of mean one; exactly 1.0 where sigma_s == 0
+ *   with phi = exp(-1 / tau) and c = sqrt(1 - phi phi) formed by the caller (tau = 0: phi = 0, c = 1, g = xi) and
+ *   h_s = sigma_s sigma_s / 2 formed on the host (stepper.forcing_recursion_of restates g in NumPy, bit for bit given xi).
+ *   On a solved row i of member m that is no spin-up solve the step kernel integrates with precip_i * f_{m,k,0} and
+ *   atm_i * f_{m,k,1}, one IEEE product each, and nothing else changes: the refresh rule (precip > 0.5) and the draw
+ *   indices, surface_evap, daylight / wet, wtd_obs, spin-up solves, hc_rhs, hc_rhs_ex and the Python RHS stay with the
+ *   record.  A member is therefore, bit for bit, a run on its own scaled record with the ensemble's refresh flags.
+ *   Before each launch the handle fills the factors of the days the launch touches (forcing_factor_fill_kernel: Philox,
+ *   recursion, exp and a coalesced store in one pass) and advances the carried state g [2][N] and the day it stands at
+ *   (into a second buffer that replaces the first once the step launch is issued: a launch that fails before that leaves
+ *   the state where it stood, and the same rows can be stepped again);
+ *   a launch that starts inside that day reuses its g, so nothing depends on where launch boundaries fall.  Rows must
+ *   not go back behind the day the state stands at (HC_ERR_ARG; hc_set_forcing_state or a new
+ *   hc_set_forcing_perturbation rewinds).  After a particle filter's resampling g travels with the member (a latent state
+ *   of its trajectory; the refresh draws stay with the slot); the EnKF leaves g alone.  While it is on, the step kernel
+ *   is the build that carries the predictive lateral-flow branch (a monitoring-mode point keeps its semantics through
+ *   flag_predict, as in a mixed sweep); with nothing set nothing is launched or allocated and the build is the one it was.
+ *   Not modelled: g in the EnKF analysis, a per-member refresh rule, additive or gamma errors, correlation between the
+ *   two streams, the sharded particle filter (refused).
+ * hc_set_forcing_perturbation: needs the column, forcing, members and state in place.  HC_ERR_ARG for a non-finite value,
+ *   sigma outside [0, 1], phi outside [0, 1), c <= 0, |phi^2 + c^2 - 1| > 1e-12, or a sharded particle filter.  Both sigma = 0
+ *   is allowed: the factors are 1.0 and the wider build runs.  The state starts empty (day -1).  Turned off by
+ *   hc_set_forcing, hc_set_members, hc_set_column / hc_add_point, hc_set_point_member_bases and hc_clear_forcing_perturbation.
+ * hc_set_forcing_member_offset: the global id of the handle's first member for this feature alone, in place of the noise
+ *   source's (no other stream reads it).  Needs the feature on, one parameter point, and no row stepped yet (HC_ERR_ARG);
+ *   a new hc_set_forcing_perturbation forgets it.
+ * hc_get_forcing_perturbation: on, and the parameters when on (each pointer may be NULL).
+ * hc_get/set_forcing_state: g [2][N] and the day it stands at (-1: no row stepped yet, g is not read): a checkpoint.
+ * hc_forcing_normals: the raw xi of the stream key `member` (a global id), out[n_days][2] (test hook).
+ * hc_forcing_factors: f of the handle's slots first_member ... + count over the days first_day ... + n_days by the
+ *   stateless recursion from day 0 on the same device code, out[n_days][2][count]; what the step kernel applies to slots
+ *   no resampling has touched. */
+#define HC_FORCING_WORD_PRECIP 0xFFFFFFE0u
+#define HC_FORCING_WORD_DEMAND 0xFFFFFFE1u
+#define HC_FORCING_DAY_ROWS 48
+int hc_set_forcing_perturbation(hc_handle *h, double sigma_precip, double sigma_demand, double phi, double c, uint64_t seed);
+int hc_clear_forcing_perturbation(hc_handle *h);
+int hc_set_forcing_member_offset(hc_handle *h, int64_t member_offset);
+int hc_get_forcing_perturbation(hc_handle *h, int32_t *on, double *sigma_precip, double *sigma_demand, double *phi, double *c,
+                                uint64_t *seed);
+int hc_get_forcing_state(hc_handle *h, double *g, int64_t *day);
+int hc_set_forcing_state(hc_handle *h, const double *g, int64_t day);
+int hc_forcing_normals(hc_handle *h, int64_t member, int64_t first_day, int64_t n_days, double *out);
+int hc_forcing_factors(hc_handle *h, int64_t first_member, int64_t count, int64_t first_day, int64_t n_days, double *out);
+
 typedef struct {
     int64_t row_begin;      /* first row to solve (row i integrates t in [i-1, i]); >= 1      */
     int64_t n_rows;

@@ -24,6 +24,12 @@ takes fresh passes for the named kernels only: the calibration and every other k
 profiles/pmc_constants.json under the new hash.  That is right only when the other kernels' instruction streams are what
 they were when their passes ran -- compare the disassembly of both builds first and keep the comparison with the
 profiles (profiles/r06_isa_vs_parent.txt is the one of round 6).
+
+    python tools/pmc_constants.py --restamp
+
+takes no passes at all: every record is kept under the hash of the device code this tree builds
+(__graft_entry__.kernel_hash()).  That is right only when tools/isa_vs_parent.py shows all five kernels' instruction
+streams to be the parent's (profiles/r08_isa_vs_parent.txt: a change compiled into the PREDICT builds only).
 """
 import argparse
 import csv
@@ -100,12 +106,26 @@ def calibration(d, prof, tag):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("dir")
+    ap.add_argument("dir", nargs="?")
+    ap.add_argument("--restamp", action="store_true",
+                    help="keep every record, under the kernel hash of this tree (the five kernels' code is the parent's)")
     ap.add_argument("--tag", default="r05")
     ap.add_argument("--only", action="append", default=[], metavar="KEY",
                     help="fresh passes for this kernel only (repeatable); calibration and the other records are kept")
     a = ap.parse_args()
     prof = os.path.join(R, "profiles")
+    if a.restamp:
+        import sys
+        sys.path.insert(0, R)
+        import __graft_entry__ as entry
+        path = os.path.join(prof, "pmc_constants.json")
+        table = json.load(open(path))
+        was, table["kernel_hash"] = table["kernel_hash"], entry.kernel_hash()
+        json.dump(table, open(path, "w"), indent=1, sort_keys=True)
+        print(f"kernel hash {was} -> {table['kernel_hash']}, {len(table['kernels'])} kernel records kept")
+        return
+    if not a.dir:
+        ap.error("the directory of the counter passes is required (or --restamp)")
     khash = open(os.path.join(a.dir, "library_hash.txt")).read().split()[-1]
     if a.only:
         if not set(a.only) <= set(KEYS):
