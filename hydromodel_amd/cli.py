@@ -253,7 +253,7 @@ unknown keys, only membership of the 12 is checked):
    instead of raising the reference's ``TypeError``.
 """
 import sys
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from pathlib import Path
 from typing import Optional
 
@@ -413,10 +413,11 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     rows = min(days * 48, forcing.dim_t - 1)
     plan = period_plan(periods, cols, forcing, rows)            # before any GPU call, like the storage's ranges
     uptake = uptake_settings(ens)
+    run = RunSettings(dist=(dist_stride, dist_levels), theta=theta, storage=storage, cov=cov, periods=periods, plan=plan,
+                      uptake=uptake, corr=corr, pert=pert, assim=assim)
     if ens.get("Points"):
-        return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride, dist_levels, assim,
-                          theta, storage, periods, plan, corr, cov, uptake, pert)
-    ucells = uptake_plan(uptake, [cols])                        # (so are the uptake's layers)
+        return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, run)
+    run = replace(run, ucells=uptake_plan(uptake, [cols]))      # (so are the uptake's layers)
     sharded = enkf_sharded(ens)
     fsharded = filter_sharded(ens)
     if sharded:
@@ -433,14 +434,10 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
         shard_kw = {}
     if hi <= lo:
         raise ValueError(f" Ensemble: {n_members} members do not shard over {ranks.world} GPUs (a rank would be empty).")
-    stride = _profile_stride(ens)
+    run = replace(run, stride=_profile_stride(ens))
     sim = EnsembleSimulation(cols, forcing, hi - lo, seed=int(ens.get("Seed", 0)), device=device, member_offset=lo,
                              noise=str(ens.get("Noise", "philox")).lower(),
-                             spinup=str(ens.get("Spinup", "shared")).lower(), profile_stride=stride,
-                             wtd_hist_stride=dist_stride, theta_hist_bins=theta[0], **assim.kwargs(),
-                             **_storage_kwargs(storage), **_covariance_kwargs(cov), **_period_kwargs(periods, plan),
-                             **_uptake_kwargs(uptake), **shard_kw, **_noise_correlation_kwargs(corr),
-                             **_forcing_perturbation_kwargs(pert))
+                             spinup=str(ens.get("Spinup", "shared")).lower(), **run.kwargs(), **shard_kw)
     label = f"Ensemble x{n_members}"
     _step_all(sim, rows, label, ranks)
     # the run's one collective: int64 (count, sum idx, sum idx^2) per row, exact and order-independent
@@ -464,15 +461,14 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
         else:
             extra["initial_cond_members"] = np.array([lo, hi])
     # the optional tables are integer sums like the moments: one more exact all-reduce each
-    tables, lines = _reduce_diagnostics(ranks, sim, [0], [cols], forcing, stride, (dist_stride, dist_levels), theta, storage,
-                                        cov, periods, plan, uptake, ucells, device, label, keep_points=False)
+    tables, lines = _reduce_diagnostics(ranks, sim, [0], [cols], forcing, run, device, label, keep_points=False)
     extra.update(tables)
     # the filters' tables describe the one point: every rank of a sharded run holds the same ones, and rank 0's are taken
     # (placed by it alone; a sum over the ranks would count them world times)
     eids = [0] if ranks.rank == 0 else []
     atables, assim_lines = _reduce_assimilation(ranks, sim, eids, 1, forcing.dim_t, cols, assim, label, keep_points=False)
     extra.update(atables)
-    stables, smooth_line = _reduce_smoother(ranks, sim, eids, 1, forcing.dim_t, cols, forcing, assim.smoother, device, label,
+    stables, smooth_line = _reduce_smoother(ranks, sim, eids, 1, forcing.dim_t, cols, forcing, assim, device, label,
                                             keep_points=False)
     extra.update(stables)
     if fsharded is not None:
@@ -534,6 +530,42 @@ class Assimilation:
             kw.update((k, v) for k, v in given.items() if v is not None)
             if self.scheme is not None:
                 kw.update(enkf_method=self.scheme[0], enkf_relaxation=self.scheme[1])
+        return kw
+
+
+@dataclass(frozen=True)
+class RunSettings:
+    """Everything ``Ensemble`` asks of a run, as the ``*_settings`` functions returned it (None / a zero stride: not
+    given) and with the plans made from it before any GPU call: built once by ``_run_ensemble`` and handed as one value
+    to the simulation's constructor (:meth:`kwargs`), the sweep and the reducers."""
+    stride: int = 0                         # the profile statistics' (_profile_stride), read where the run is built
+    dist: tuple = (0, None)                 # distribution_settings: (stride, levels)
+    theta: tuple = (0, None)                # profile_distribution_settings: (bins, levels)
+    storage: Optional[tuple] = None
+    cov: Optional[tuple] = None
+    periods: Optional[dict] = None
+    plan: Optional[tuple] = None            # period_plan
+    uptake: Optional[dict] = None
+    ucells: Optional[object] = None         # uptake_plan, of the run's points
+    corr: Optional[dict] = None
+    pert: Optional[dict] = None
+    assim: Assimilation = Assimilation()
+
+    def kwargs(self):
+        """The keywords of EnsembleSimulation / SweepSimulation: what was not given passes nothing."""
+        kw = dict(profile_stride=self.stride, wtd_hist_stride=self.dist[0], theta_hist_bins=self.theta[0], **self.assim.kwargs())
+        given = dict(noise_correlation=self.corr, forcing_perturbation=self.pert,
+                     theta_cov_stride=None if self.cov is None else self.cov[0])
+        kw.update((k, v) for k, v in given.items() if v is not None)
+        if self.storage is not None:
+            kw.update(storage_layers_cm=self.storage[0], storage_bins=self.storage[1])
+        if self.periods is not None:
+            kw.update(period_ends=self.plan[0], period_thresholds_cm=self.periods["thresholds_cm"],
+                      period_bins=self.periods["bins"])
+            if self.periods["bins"]:
+                kw.update(period_flux_max_cm=self.periods["flux_max_cm"])
+        if self.uptake is not None:
+            kw.update(uptake_layers_cm=self.uptake["layers_cm"], uptake_bins=self.uptake["bins"])
         return kw
 
 
@@ -631,10 +663,6 @@ def noise_correlation_settings(ens):
     return {"length_cm": float(length), "layers": layers}
 
 
-def _noise_correlation_kwargs(corr):
-    return {} if corr is None else {"noise_correlation": corr}
-
-
 def _noise_correlation_arrays(corr, cols_list, label, keep_points):
     """The datasets and the closing line of a run with a noise correlation: the tables are the points' own (every rank
     builds the same ones: no collective)."""
@@ -691,10 +719,6 @@ def forcing_perturbation_settings(ens):
         raise ValueError(" Ensemble: Forcing_Perturbation with \"Filter\": {\"Sharded\": true}: the columns the ranks exchange "
                          "do not carry the members' forcing state; run the filter unsharded.")
     return out
-
-
-def _forcing_perturbation_kwargs(pert):
-    return {} if pert is None else {"forcing_perturbation": pert}
 
 
 def _forcing_perturbation_arrays(pert, label):
@@ -858,10 +882,6 @@ def storage_ranges(storage, cols):
     return ranges
 
 
-def _storage_kwargs(storage):
-    return {} if storage is None else dict(storage_layers_cm=storage[0], storage_bins=storage[1])
-
-
 COVARIANCE_KEYS = ("Node_Stride", "Sensor_Sigma")
 COVARIANCE_MAX_BYTES = 1 << 31
 
@@ -911,10 +931,6 @@ def covariance_check(cov, D, T, stride, P=1):
         raise ValueError(f" Ensemble: Covariance: theta_cov would hold {t_out} rows of {n} x {n} float64 "
                          f"({size / 2 ** 30:.1f} GiB; at most 2 GiB): take a larger node stride or a larger profile stride.")
     return n
-
-
-def _covariance_kwargs(cov):
-    return {} if cov is None else dict(theta_cov_stride=cov[0])
 
 
 PERIOD_KEYS = ("Rows", "Calendar", "Shallower_than_cm", "Bins", "Transpiration_max_cm", "Lateral_flow_max_cm", "Quantiles",
@@ -988,10 +1004,6 @@ def uptake_plan(uptake, cols_list):
                 raise ValueError(f" Ensemble: Periods.Uptake.Layers_cm: layer {list(lay)!r} cm holds no root cell (the root "
                                  f"zone ends at {float(c.z[c.n_root_int] + c.dz):g} cm).")
     return cells
-
-
-def _uptake_kwargs(uptake):
-    return {} if uptake is None else dict(uptake_layers_cm=uptake["layers_cm"], uptake_bins=uptake["bins"])
 
 
 def period_settings(ens):
@@ -1094,15 +1106,6 @@ def period_plan(periods, cols, forcing, run_rows):
     if longest > PERIOD_MAX_ROWS:
         raise ValueError(f" Ensemble: Periods: a period of {longest} rows; at most {PERIOD_MAX_ROWS} are supported.")
     return ends, nodes
-
-
-def _period_kwargs(periods, plan):
-    if periods is None:
-        return {}
-    kw = dict(period_ends=plan[0], period_thresholds_cm=periods["thresholds_cm"], period_bins=periods["bins"])
-    if periods["bins"]:
-        kw["period_flux_max_cm"] = periods["flux_max_cm"]
-    return kw
 
 
 FILTER_KEYS = ("Stride", "Sigma_cm", "Seed", "Sharded", "Soil_Moisture", "ESS_floor", "Window_Offsets", "Rejuvenation",
@@ -1262,16 +1265,16 @@ def filter_smoother_settings(ens):
     return stride, lag_rows // stride, tuple(float(v) for v in levels)
 
 
-def _reduce_smoother(ranks, sim, ids, P, T, ref, forcing, smoother, device, label, keep_points):
-    """The smoother's datasets and closing line (``smoother``: :func:`filter_smoother_settings`; None: nothing): each
+def _reduce_smoother(ranks, sim, ids, P, T, ref, forcing, a, device, label, keep_points):
+    """The smoother's datasets and closing line (``a``: the run's :class:`Assimilation`; no smoother: nothing): each
     rank flushes its handle ``sim`` (None: it holds no points), its points' tables are placed at ``ids`` of the run's
     ``P`` and summed over the ranks -- two collectives every rank joins -- and rank 0 forms the summary."""
     import numpy as np
     from .multigpu import place_points
     from .stepper import filter_smoother_summary, stride_rows
-    if smoother is None:
+    if a.smoother is None:
         return {}, None
-    stride, lag, levels = smoother
+    stride, lag, levels = a.smoother
     n_srow, D = stride_rows(T, stride), ref.dim_d
     if sim is not None:
         sim.stepper.filter_smoother_flush()
@@ -2018,20 +2021,19 @@ def _reduce_uptake(ranks, sim, ids, P, cols, uptake, cells, plan, label, keep_po
     return out, line
 
 
-def _reduce_diagnostics(ranks, sim, ids, cols_all, forcing, stride, dist, theta, storage, cov, periods, plan, uptake, ucells,
-                        device, label, keep_points):
-    """Every diagnostic block of the run, reduced over the ranks in the one order both an ensemble and a sweep write their
-    datasets in (a later block's dataset replaces an earlier one of the same name).  Returns the datasets and
-    {block: closing line or None}, ``crps`` first, the others in the order their lines are printed."""
-    P, T, ref = len(cols_all), forcing.dim_t, cols_all[0]
+def _reduce_diagnostics(ranks, sim, ids, cols_all, forcing, run, device, label, keep_points):
+    """Every diagnostic block of the run (``run``: its :class:`RunSettings`), reduced over the ranks in the one order both
+    an ensemble and a sweep write their datasets in (a later block's dataset replaces an earlier one of the same name).
+    Returns the datasets and {block: closing line or None}, ``crps`` first, the others in the order their lines are printed."""
+    P, T, ref, stride = len(cols_all), forcing.dim_t, cols_all[0], run.stride
     reducers = (
-        ("crps", lambda: _reduce_optional(ranks, sim, ids, cols_all, forcing, stride, dist[0], dist[1], device, label,
+        ("crps", lambda: _reduce_optional(ranks, sim, ids, cols_all, forcing, stride, run.dist[0], run.dist[1], device, label,
                                           keep_points)),
-        ("theta", lambda: _reduce_theta(ranks, sim, ids, P, T, ref.dim_d, stride, theta, label, keep_points)),
-        ("storage", lambda: _reduce_storage(ranks, sim, ids, P, T, ref, stride, storage, label, keep_points)),
-        ("covariance", lambda: _reduce_covariance(ranks, sim, ids, P, T, ref, stride, cov, label, keep_points)),
-        ("periods", lambda: _reduce_periods(ranks, sim, ids, P, ref, forcing, periods, plan, label, keep_points)),
-        ("uptake", lambda: _reduce_uptake(ranks, sim, ids, P, ref, uptake, ucells, plan, label, keep_points)))
+        ("theta", lambda: _reduce_theta(ranks, sim, ids, P, T, ref.dim_d, stride, run.theta, label, keep_points)),
+        ("storage", lambda: _reduce_storage(ranks, sim, ids, P, T, ref, stride, run.storage, label, keep_points)),
+        ("covariance", lambda: _reduce_covariance(ranks, sim, ids, P, T, ref, stride, run.cov, label, keep_points)),
+        ("periods", lambda: _reduce_periods(ranks, sim, ids, P, ref, forcing, run.periods, run.plan, label, keep_points)),
+        ("uptake", lambda: _reduce_uptake(ranks, sim, ids, P, ref, run.uptake, run.ucells, run.plan, label, keep_points)))
     out, lines = {}, {}
     for block, reduce in reducers:
         tables, lines[block] = reduce()
@@ -2039,11 +2041,9 @@ def _reduce_diagnostics(ranks, sim, ids, cols_all, forcing, stride, dist, theta,
     return out, lines
 
 
-def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, dist_stride=0, dist_levels=None,
-               assim=Assimilation(), theta=(0, None), storage=None, periods=None, plan=None, corr=None, cov=None,
-               uptake=None, pert=None):
-    """Parameter points x members: this rank's points in one handle (ensemble.SweepSimulation), the whole table assembled
-    over the ranks (multigpu.assemble_points)."""
+def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, run=RunSettings()):
+    """Parameter points x members (``run``: the :class:`RunSettings`): this rank's points in one handle
+    (ensemble.SweepSimulation), the whole table assembled over the ranks (multigpu.assemble_points)."""
     import numpy as np
     from . import multigpu
     from .digest import ColumnTables, load_site_well
@@ -2063,15 +2063,11 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     cols_all = [ColumnTables(m, well) for m in merged]
     points, ref, T = [cols_all[k] for k in mine], cols_all[0], forcing.dim_t
     local, sim = {}, None
-    stride = _profile_stride(ens)
     label = f"Sweep {P} points x{n_members}"
-    ucells = uptake_plan(uptake, cols_all)                      # before any GPU call
+    run = replace(run, stride=_profile_stride(ens), ucells=uptake_plan(run.uptake, cols_all))       # before any GPU call
     if mine:
         sim = SweepSimulation(points, forcing, n_members, seed=int(ens.get("Seed", 0)), device=device, point_ids=mine,
-                              profile_stride=stride, wtd_hist_stride=dist_stride, theta_hist_bins=theta[0],
-                              **assim.kwargs(), **_storage_kwargs(storage), **_covariance_kwargs(cov),
-                              **_period_kwargs(periods, plan), **_uptake_kwargs(uptake), **_noise_correlation_kwargs(corr),
-                              **_forcing_perturbation_kwargs(pert))
+                              **run.kwargs())
         _step_all(sim, rows, label, ranks)
         table = sim.moments()
         for j, k in enumerate(mine):
@@ -2082,17 +2078,15 @@ def _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks
     arrays = dict(moments=moments, wtd_mean_cm=mean_cm, wtd_std_cm=std_cm, rows=np.array(rows),
                   members=np.array(n_members), points=np.array(P), gpus=np.array(ranks.world), initial_cond=psi0,
                   spinup_iterations=spin)
-    tables, lines = _reduce_diagnostics(ranks, sim, mine, cols_all, forcing, stride, (dist_stride, dist_levels), theta, storage,
-                                        cov, periods, plan, uptake, ucells, device, label, keep_points=True)
+    tables, lines = _reduce_diagnostics(ranks, sim, mine, cols_all, forcing, run, device, label, keep_points=True)
     arrays.update(tables)
-    atables, assim_lines = _reduce_assimilation(ranks, sim, mine, P, T, ref, assim, label, keep_points=True)
+    atables, assim_lines = _reduce_assimilation(ranks, sim, mine, P, T, ref, run.assim, label, keep_points=True)
     arrays.update(atables)
-    stables, smooth_line = _reduce_smoother(ranks, sim, mine, P, T, ref, forcing, assim.smoother, device, label,
-                                            keep_points=True)
+    stables, smooth_line = _reduce_smoother(ranks, sim, mine, P, T, ref, forcing, run.assim, device, label, keep_points=True)
     arrays.update(stables)
-    ctables, corr_line = _noise_correlation_arrays(corr, cols_all, label, keep_points=True)
+    ctables, corr_line = _noise_correlation_arrays(run.corr, cols_all, label, keep_points=True)
     arrays.update(ctables)
-    ptables, pert_line = _forcing_perturbation_arrays(pert, label)
+    ptables, pert_line = _forcing_perturbation_arrays(run.pert, label)
     arrays.update(ptables)
     if sim is not None:
         sim.close()

@@ -8,19 +8,14 @@ all-reduce of the per-row water-table moments (see :func:`allreduce_moments`).
 """
 import numpy as np
 
+from . import settings
 from .digest import inverse_retention
-from .stepper import enkf_noise_summary, noise_field_settings
-from .stepper import theta_cov_finish, theta_sensor_gain
-from .stepper import forcing_coefficients, forcing_perturbation_settings
-from .stepper import noise_correlation_breaks, noise_correlation_settings, noise_correlation_tables
 from .stepper import DIAG_TABLES, diag_checkpoint, diag_from_checkpoint
-from .stepper import (ASSIM_TABLES, ENKF_METHODS, EnsembleStepper, enkf_sm_summary, enkf_summary,
-                      enkf_window_settings, enkf_window_summary, filter_sm_summary, filter_summary,
-                      filter_smoother_config, filter_smoother_summary, filter_window_settings, filter_window_summary,
-                      rejuvenation_discount,
-                      flux_max_log2_of, layer_ranges, layer_storage_distribution, moments_to_mean_std, period_totals_distribution,
-                      sensor_nodes, theta_distribution, wtd_distribution)
-from .stepper import layer_cells, root_uptake_distribution, root_uptake_profile, root_uptake_stats
+from .stepper import (ASSIM_TABLES, EnsembleStepper, enkf_noise_summary, enkf_sm_summary, enkf_summary, enkf_window_summary,
+                      filter_sm_summary, filter_smoother_summary, filter_summary, filter_window_summary, layer_ranges,
+                      layer_storage_distribution, moments_to_mean_std, period_totals_distribution, root_uptake_distribution,
+                      root_uptake_profile, root_uptake_stats, theta_cov_finish, theta_distribution, theta_sensor_gain,
+                      wtd_distribution)
 
 
 def pressure_head(cols, theta):
@@ -174,167 +169,6 @@ class _Run:
 
     _lead = ()
 
-    def _start_tables(self, profile_stride, wtd_hist_stride, filter_stride=0, filter_sigma_cm=None, filter_seed=None,
-                      enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None,
-                      enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=(),
-                      filter_soil_moisture=None, theta_hist_bins=0, storage_layers_cm=None, storage_bins=0,
-                      filter_ess_floor=0.0, filter_window_offsets=(), enkf_noise_field=None, filter_rejuvenation=0.0,
-                      theta_cov_stride=0, filter_smoother=None):
-        self.profile_stride = int(profile_stride)
-        self.theta_cov_stride = int(theta_cov_stride or 0)
-        if self.theta_cov_stride and not self.profile_stride:
-            raise ValueError("theta_cov_stride needs the profile statistics (profile_stride > 0)")
-        self.storage_layers_cm = None if storage_layers_cm is None or len(storage_layers_cm) == 0 else \
-            np.asarray(storage_layers_cm, dtype=np.float64).reshape(-1, 2)
-        self.storage_bins = int(storage_bins or 0) if self.storage_layers_cm is not None else 0
-        if storage_bins and self.storage_layers_cm is None:
-            raise ValueError("storage_bins needs storage_layers_cm")
-        if self.storage_layers_cm is not None and not self.profile_stride:
-            raise ValueError("storage_layers_cm needs the profile statistics (profile_stride > 0)")
-        self.storage_ranges = None if self.storage_layers_cm is None else layer_ranges(self.cols.z, self.storage_layers_cm)
-        self.theta_hist_bins = int(theta_hist_bins or 0)
-        if self.theta_hist_bins and not self.profile_stride:
-            raise ValueError("theta_hist_bins needs the profile statistics (profile_stride > 0)")
-        if self.profile_stride:
-            self.stepper.set_profile_stats(self.profile_stride)
-            if self.theta_hist_bins:
-                self.stepper.set_theta_hist(self.theta_hist_bins)
-            if self.storage_ranges is not None:
-                self.stepper.set_layer_storage(self.storage_ranges, self.storage_bins)
-            if self.theta_cov_stride:
-                self.stepper.set_theta_cov(self.theta_cov_stride)
-            self.stepper.profile_snapshot(0)       # psi[0], theta_vol[0]: the state before any solve
-        self.wtd_hist_stride = int(wtd_hist_stride)
-        if self.wtd_hist_stride:
-            self.stepper.set_wtd_hist(self.wtd_hist_stride)
-        self.filter_stride = int(filter_stride or 0)
-        self.filter_sigma_cm = float(filter_sigma_cm) if self.filter_stride else None
-        self.filter_seed = (self.seed if filter_seed is None else int(filter_seed)) if self.filter_stride else None
-        if self.filter_stride:
-            self.stepper.set_filter(self.filter_stride, self.filter_sigma_cm, self.filter_seed)
-        self.filter_soil_moisture = filter_soil_moisture
-        if filter_soil_moisture is not None:
-            if not self.filter_stride:
-                raise ValueError("filter_soil_moisture needs the particle filter (filter_stride > 0)")
-            sm = filter_soil_moisture
-            self.stepper.set_filter_soil_moisture(sm["nodes"], sm["values"], sm["sigma"])
-        self.filter_ess_floor = float(filter_ess_floor or 0.0)
-        if self.filter_ess_floor:
-            if not self.filter_stride:
-                raise ValueError("filter_ess_floor needs the particle filter (filter_stride > 0)")
-            self.stepper.set_filter_tempering(self.filter_ess_floor)
-        self.filter_rejuvenation = rejuvenation_discount(filter_rejuvenation)
-        if self.filter_rejuvenation:
-            if not self.filter_stride:
-                raise ValueError("filter_rejuvenation needs the particle filter (filter_stride > 0)")
-            self.stepper.set_filter_rejuvenation(self.filter_rejuvenation)
-        self.filter_window_offsets = filter_window_settings(filter_window_offsets, self.filter_stride,
-                                                            self.stepper.filter_sm_n)
-        if self.filter_window_offsets:
-            self.stepper.set_filter_window(self.filter_window_offsets)
-        # the fixed-lag smoother (after everything else of the filter's): (stride, lag in record rows) or None
-        self.filter_smoother = filter_smoother_config(filter_smoother)
-        if self.filter_smoother is not None:
-            if not self.filter_stride:
-                raise ValueError("filter_smoother needs the particle filter (filter_stride > 0)")
-            self.stepper.set_filter_smoother(*self.filter_smoother)
-        self.enkf_stride = int(enkf_stride or 0)
-        self.enkf_sigma_cm = float(enkf_sigma_cm) if self.enkf_stride else None
-        self.enkf_localisation_cm = float(enkf_localisation_cm or 0.0) if self.enkf_stride else None
-        self.enkf_seed = (self.seed if enkf_seed is None else int(enkf_seed)) if self.enkf_stride else None
-        if self.enkf_stride:
-            self.stepper.set_enkf(self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed)
-        self.enkf_soil_moisture = enkf_soil_moisture if self.enkf_stride else None
-        if enkf_soil_moisture is not None and not self.enkf_stride:
-            raise ValueError("enkf_soil_moisture needs the EnKF (enkf_stride > 0)")
-        if self.enkf_soil_moisture is not None:
-            sm = self.enkf_soil_moisture
-            self.stepper.set_enkf_soil_moisture(sm["nodes"], sm["values"], sm["sigma"])
-        self.enkf_method, self.enkf_relaxation = str(enkf_method), float(enkf_relaxation)
-        if (self.enkf_method, self.enkf_relaxation) != ("stochastic", 0.0):
-            if not self.enkf_stride:
-                raise ValueError("enkf_method / enkf_relaxation need the EnKF (enkf_stride > 0)")
-            self.stepper.set_enkf_method(self.enkf_method, self.enkf_relaxation)
-        self.enkf_window_offsets = enkf_window_settings(enkf_window_offsets, self.enkf_stride, self.stepper.enkf_sm_n)
-        if self.enkf_window_offsets:
-            self.stepper.set_enkf_window(self.enkf_window_offsets)
-        # the noise field (after any spin-up: a Philox run then takes the caller-noise path); None: off
-        self.enkf_noise_relaxation = noise_field_settings(enkf_noise_field, self.enkf_relaxation)
-        if self.enkf_noise_relaxation is not None:
-            if not self.enkf_stride:
-                raise ValueError("enkf_noise_field needs the EnKF (enkf_stride > 0)")
-            self.stepper.set_enkf_noise_field(True, self.enkf_noise_relaxation)
-
-    @staticmethod
-    def _check_noise_correlation(who, noise_correlation, noise, filter_rejuvenation):
-        """(length_cm, layers) or None, before any handle is made."""
-        settings = noise_correlation_settings(noise_correlation)
-        if settings is not None and noise == "numpy":
-            raise ValueError(f" {who}: noise_correlation serves the Philox noise source; a noise='numpy' caller shapes "
-                             f"its own vectors (stepper.noise_correlate).")
-        if settings is not None and rejuvenation_discount(filter_rejuvenation):
-            raise ValueError(f" {who}: noise_correlation and filter_rejuvenation exclude each other: the jitter is white per "
-                             f"node and would erode the correlation by a share h^2 per move.")
-        return settings
-
-    def _start_noise_correlation(self, settings, points):
-        """Correlate the Philox vectors (include/hydrocol.h hc_set_noise_correlation): after the spin-up, before the filter,
-        the EnKF's noise field and the tables; one table per point from that point's layers."""
-        self.noise_correlation = None
-        self.noise_correlation_a = self.noise_correlation_b = None
-        self.noise_correlation_breaks_cm = ()
-        if settings is None:
-            return
-        length, layers = settings
-        breaks = [noise_correlation_breaks(c.layers, c.z) if layers else () for c in points]
-        ab = [noise_correlation_tables(c.z, length, br) for c, br in zip(points, breaks)]
-        a, b = np.stack([t[0] for t in ab]), np.stack([t[1] for t in ab])
-        self.stepper.set_noise_correlation(a, b)
-        self.noise_correlation = {"length_cm": length, "layers": layers}
-        self.noise_correlation_a = a.reshape(self._lead + a.shape[1:])          # [D]; a sweep: [P][D]
-        self.noise_correlation_b = b.reshape(self._lead + b.shape[1:])
-        self.noise_correlation_breaks_cm = tuple(breaks) if self._lead else breaks[0]
-
-    def _start_forcing_perturbation(self, settings):
-        """Perturb the members' rainfall and demand (include/hydrocol.h hc_set_forcing_perturbation): after the spin-up,
-        before the filters.  ``settings``: what :func:`stepper.forcing_perturbation_settings` returned."""
-        self.forcing_perturbation = None
-        if settings is None:
-            return
-        seed = self.seed if settings["seed"] is None else settings["seed"]
-        phi, c = forcing_coefficients(settings["correlation_days"])
-        # a shard of a host-noise ensemble has no stream key of its own: the feature is told the first member's id
-        offset = self.member_offset if getattr(self, "noise", "philox") == "numpy" else None
-        self.stepper.set_forcing_perturbation(settings["precipitation_sigma"], settings["demand_sigma"], seed=seed, phi=phi, c=c,
-                                              member_offset=offset)
-        self.forcing_perturbation = dict(settings, seed=int(seed), phi=phi)
-
-    def _dump_forcing_perturbation(self, arrays):
-        """... its parameters and the members' state into a checkpoint's arrays (a run without it keeps its key set)"""
-        if self.forcing_perturbation is None:
-            return
-        fp = self.forcing_perturbation
-        arrays["forcing_precipitation_sigma"] = np.array(fp["precipitation_sigma"], dtype=np.float64)
-        arrays["forcing_demand_sigma"] = np.array(fp["demand_sigma"], dtype=np.float64)
-        arrays["forcing_correlation_days"] = np.array(fp["correlation_days"], dtype=np.float64)
-        arrays["forcing_seed"] = np.array(fp["seed"], dtype=np.uint64)
-        g, day = self.stepper.forcing_state()
-        arrays["forcing_state"], arrays["forcing_state_day"] = g, np.array(day, dtype=np.int64)
-
-    @staticmethod
-    def _restored_forcing_perturbation(data):
-        """... and the constructor's argument back out of them (None: the checkpoint has none)"""
-        if "forcing_precipitation_sigma" not in data:
-            return None
-        return {"precipitation_sigma": float(data["forcing_precipitation_sigma"]),
-                "demand_sigma": float(data["forcing_demand_sigma"]),
-                "correlation_days": float(data["forcing_correlation_days"]), "seed": int(data["forcing_seed"])}
-
-    def _restore_forcing_state(self, data):
-        if self.forcing_perturbation is not None:
-            g = np.asarray(data["forcing_state"], dtype=np.float64).reshape(2, -1)
-            self.stepper.set_forcing_state(g, int(np.asarray(data["forcing_state_day"]).reshape(-1)[0]))
-
     def noise_correlation_break_count(self):
         """Breaks of the recursion below node 0, over all points."""
         a = np.asarray(self.noise_correlation_a).reshape(-1, self.cols.dim_d)
@@ -348,22 +182,12 @@ class _Run:
 
     def assim_tables_on(self):
         """The keys of stepper.ASSIM_TABLES this run keeps, in the registry's order: what a checkpoint carries."""
-        on = {"filter": bool(self.filter_stride), "filter_sm": self.filter_soil_moisture is not None,
-              "filter_temper": bool(self.filter_ess_floor), "filter_rejuvenation": bool(self.filter_rejuvenation),
-              "filter_window": bool(self.filter_window_offsets), "enkf": bool(self.enkf_stride),
-              "enkf_sm": self.enkf_soil_moisture is not None, "enkf_window": bool(self.enkf_window_offsets),
-              "enkf_noise": self.enkf_noise_relaxation is not None}
-        return [key for key in ASSIM_TABLES if on[key]]
+        return settings.tables_on(ASSIM_TABLES, self.on)
 
     def diag_tables_on(self):
         """The keys of stepper.DIAG_TABLES this run keeps, in the registry's order: what a checkpoint carries and installs."""
-        periods, uptake = self.period_ends is not None, self.uptake_cells is not None
-        on = {"profile": bool(self.profile_stride), "theta_hist": bool(self.theta_hist_bins),
-              "storage": self.storage_ranges is not None, "storage_hist": bool(self.storage_bins),
-              "theta_cov": bool(self.theta_cov_stride), "period": periods, "period_acc": periods,
-              "period_hist": bool(self.period_bins), "uptake": uptake, "uptake_acc": uptake,
-              "uptake_hist": bool(self.uptake_bins), "wtd_hist": bool(self.wtd_hist_stride)}
-        return [key for key in DIAG_TABLES if on[key]]
+        return settings.tables_on(DIAG_TABLES, self.on)
+
 
     def enkf_noise_table(self):
         """[n_arow][4 D + 1] float64 (include/hydrocol.h hc_set_enkf_noise_field); a sweep: [P][n_arow][4 D + 1]."""
@@ -439,22 +263,6 @@ class _Run:
                for i0, i1 in layer_ranges(self.cols.z, layers_cm)]
         return float(self.cols.dz) * np.stack(out, axis=-1)
 
-    def _start_periods(self, period_ends, period_thresholds_cm, period_bins, period_flux_max_cm):
-        self.period_ends = None if period_ends is None or len(period_ends) == 0 else \
-            np.asarray(period_ends, dtype=np.int64).reshape(-1)
-        on = self.period_ends is not None
-        if not on and (len(period_thresholds_cm or ()) or period_bins):
-            raise ValueError("period_thresholds_cm / period_bins need period_ends")
-        self.period_thresholds_cm = np.asarray(period_thresholds_cm if on and period_thresholds_cm is not None else [],
-                                               dtype=np.float64).reshape(-1)
-        self.period_bins = int(period_bins or 0) if on else 0
-        self.period_flux_max_cm = tuple(float(v) for v in period_flux_max_cm) if self.period_bins else None
-        if self.period_bins and len(self.period_flux_max_cm) != 2:
-            raise ValueError("period_flux_max_cm is (transpiration, lateral flow)")
-        self.period_threshold_nodes = sensor_nodes(self.cols.z, self.period_thresholds_cm) if on else None
-        if on:
-            fexp = [flux_max_log2_of(v) for v in self.period_flux_max_cm] if self.period_bins else (0, 0)
-            self.stepper.set_period_totals(self.period_ends, self.period_threshold_nodes, self.period_bins, fexp)
 
     def period_table(self):
         """The raw int64 moments table of the period totals (stepper.period_totals_table_layout)."""
@@ -481,17 +289,6 @@ class _Run:
         return period_totals_distribution(hf, hw, levels, self.stepper.period_flux_max_log2, float(self.cols.z[0]),
                                           self.cols.dz)
 
-    def _start_uptake(self, uptake_layers_cm, uptake_bins):
-        on = uptake_layers_cm is not None and len(uptake_layers_cm) > 0
-        if not on and uptake_bins:
-            raise ValueError("uptake_bins needs uptake_layers_cm")
-        if on and self.period_ends is None:
-            raise ValueError("uptake_layers_cm needs period_ends: the uptake is totalled over the periods")
-        self.uptake_layers_cm = np.asarray(uptake_layers_cm, dtype=np.float64).reshape(-1, 2) if on else None
-        self.uptake_bins = int(uptake_bins or 0) if on else 0
-        self.uptake_cells = layer_cells(self.cols.z, self.uptake_layers_cm) if on else None
-        if on:
-            self.stepper.set_root_uptake(self.uptake_cells, self.uptake_bins)
 
     def uptake_table(self):
         """The raw int64 table of the root uptake (stepper.root_uptake_table_layout)."""
@@ -696,65 +493,17 @@ class EnsembleSimulation(_Run):
     """
 
     def __init__(self, cols, forcing, n_members, seed=0, device=0, member_offset=0, psi0=None, flags=None,
-                 noise="philox", spinup="shared", profile_stride=0, wtd_hist_stride=0, filter_stride=0,
-                 filter_sigma_cm=None, filter_seed=None, enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0,
-                 enkf_seed=None, enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0,
-                 enkf_window_offsets=(), enkf_shard=None, filter_shard=None, filter_soil_moisture=None,
-                 theta_hist_bins=0, storage_layers_cm=None, storage_bins=0, period_ends=None, period_thresholds_cm=(),
-                 period_bins=0, period_flux_max_cm=(16.0, 4.0), filter_ess_floor=0.0, filter_window_offsets=(),
-                 enkf_noise_field=None, filter_rejuvenation=0.0, noise_correlation=None,
-                 theta_cov_stride=0, uptake_layers_cm=None, uptake_bins=0, filter_smoother=None,
-                 forcing_perturbation=None):
-        corr = self._check_noise_correlation("EnsembleSimulation", noise_correlation, noise, filter_rejuvenation)
-        pert = forcing_perturbation_settings(forcing_perturbation)
-        if filter_shard is not None and pert is not None:
-            raise ValueError("filter_shard and forcing_perturbation exclude each other: the routed columns do not carry the "
-                             "members' forcing state")
-        if enkf_shard is not None and noise_field_settings(enkf_noise_field, 0.0) is not None:
-            raise ValueError("enkf_shard and enkf_noise_field exclude each other: the exchanged partials cover psi only")
-        if filter_shard is not None and rejuvenation_discount(filter_rejuvenation):
-            raise ValueError("filter_shard and filter_rejuvenation exclude each other: the sharded filter gathers "
-                             "water-table indices only, the moments of the base vectors would need an exchange of their own")
-        if filter_shard is not None and filter_window_offsets is not None and len(filter_window_offsets):
-            raise ValueError("filter_shard and filter_window_offsets exclude each other: the sharded filter gathers the "
-                             "water-table indices of the assimilation row only")
-        if filter_shard is not None and period_ends is not None and len(period_ends):
-            raise ValueError("period_ends and filter_shard exclude each other: the sharded filter routes the members' "
-                             "columns, which do not carry the period accumulators")
-        if filter_shard is not None and filter_smoother_config(filter_smoother) is not None:
-            raise ValueError("filter_shard and filter_smoother exclude each other: the routed columns do not carry the "
-                             "smoother's ring")
-        if filter_shard is not None and not int(filter_stride or 0):
-            raise ValueError("filter_shard needs the particle filter (filter_stride > 0)")
-        if filter_shard is not None and filter_soil_moisture is not None:
-            raise ValueError("filter_shard and filter_soil_moisture exclude each other: the sharded filter gathers "
-                             "water-table indices only")
+                 noise="philox", spinup="shared", enkf_shard=None, filter_shard=None, **options):
+        """``options``: the run's options (settings.OPTIONS; :class:`_Run` describes them), normalised and cross-checked
+        before any handle exists."""
+        s = settings.normalise("EnsembleSimulation", options, [cols], seed, noise=noise, member_offset=member_offset,
+                               enkf_shard=enkf_shard, filter_shard=filter_shard)
         if enkf_shard is not None or filter_shard is not None:
             from . import _lib
             _lib.load(with_torch=True)             # torch before the library: the shard's buffer is a torch tensor
         self._start(cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup)
-        self._start_noise_correlation(corr, [cols])
-        self._start_forcing_perturbation(pert)
-        self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
-                           enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
-                           enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins, storage_layers_cm,
-                           storage_bins, filter_ess_floor, filter_window_offsets, enkf_noise_field,
-                           filter_rejuvenation=filter_rejuvenation, theta_cov_stride=theta_cov_stride,
-                           filter_smoother=filter_smoother)
-        self._start_periods(period_ends, period_thresholds_cm, period_bins, period_flux_max_cm)
-        self._start_uptake(uptake_layers_cm, uptake_bins)
-        self.enkf_shard = None
-        if enkf_shard is not None:
-            if not self.enkf_stride:
-                raise ValueError("enkf_shard needs the EnKF (enkf_stride > 0)")
-            n_global, exchange = enkf_shard
-            self.stepper.set_enkf_shard(n_global, self.member_offset, exchange)      # (after the sensors and the window)
-            self.enkf_shard = (int(n_global), self.member_offset)
-        self.filter_shard = None
-        if filter_shard is not None:
-            bounds, index, exchange = filter_shard
-            self.stepper.set_filter_shard(bounds, index, exchange)
-            self.filter_shard = self.stepper.filter_shard
+        settings.start(self, s)
+
 
     def _start(self, cols, forcing, n_members, seed, device, member_offset, psi0, flags, noise, spinup):
         if noise not in ("philox", "numpy") or spinup not in ("shared", "member"):
@@ -834,7 +583,8 @@ class EnsembleSimulation(_Run):
     def dump(self, path):
         """Everything a stopped Philox ensemble is defined by, in the results container (HDF5 through libhdf5, ``.npz``
         where no libhdf5 loads): member states, per-member damping of the base noise vector, the moment table, the
-        next forcing row and the stream keys.  ``restore`` continues bit for bit."""
+        next forcing row and the stream keys, then what every option that is on adds (settings.SETTING_DATASETS, RUN_STATE
+        and MEMBER_STATE, the tables of the two registries).  ``restore`` continues bit for bit."""
         if self.noise != "philox":
             raise ValueError(" EnsembleSimulation: dump/restore serves the Philox noise source "
                              "(a NumPy stream's position is not part of the stepper).")
@@ -845,72 +595,11 @@ class EnsembleSimulation(_Run):
                       seed=np.array(self.seed, dtype=np.uint64), member_offset=np.array(self.member_offset, dtype=np.int64),
                       n_members=np.array(self.n_members, dtype=np.int64), dim_d=np.array(self.cols.dim_d, dtype=np.int64),
                       dim_t=np.array(self.forcing.dim_t, dtype=np.int64), initial_cond=np.asarray(self.psi0, dtype=float))
-        # the diagnostics' settings, from which restore builds the run; their tables follow below, from the registry
-        for k in ("profile_stride", "theta_hist_bins", "theta_cov_stride", "wtd_hist_stride"):
-            if getattr(self, k):
-                arrays[k] = np.array(getattr(self, k), dtype=np.int64)
-        if self.storage_ranges is not None:
-            arrays["storage_layers_cm"] = self.storage_layers_cm
-            arrays["storage_bins"] = np.array(self.storage_bins, dtype=np.int64)
-        if self.period_ends is not None:
-            arrays["period_ends"] = self.period_ends
-            arrays["period_thresholds_cm"] = self.period_thresholds_cm
-            arrays["period_bins"] = np.array(self.period_bins, dtype=np.int64)
-            if self.period_bins:
-                arrays["period_flux_max_cm"] = np.asarray(self.period_flux_max_cm, dtype=np.float64)
-        if self.uptake_cells is not None:
-            arrays["uptake_layers_cm"] = self.uptake_layers_cm
-            arrays["uptake_bins"] = np.array(self.uptake_bins, dtype=np.int64)
+        # the options' settings, from which restore builds the run, and their live state; the tables follow, from the registries
+        arrays.update(settings.checkpoint_datasets(self, self.stepper))
         # (the members' accumulators of the periods and the uptake are among them: a restore inside a period continues it)
         for key in self.diag_tables_on():
             arrays.update(diag_checkpoint(key, self.stepper.diag_raw(key), self.stepper.diag_counts()))
-        if self.filter_stride:
-            # the base vectors carry the damping and the ancestry of a filtered run (noise_scale no longer follows it)
-            arrays["filter_stride"] = np.array(self.filter_stride, dtype=np.int64)
-            arrays["filter_sigma_cm"] = np.array(self.filter_sigma_cm, dtype=np.float64)
-            arrays["filter_seed"] = np.array(self.filter_seed, dtype=np.uint64)
-            arrays["filter_base"] = self.stepper.filter_base()
-            if self.filter_soil_moisture is not None:     # the record itself is supplied again at restore
-                arrays["filter_sm_nodes"] = np.asarray(self.filter_soil_moisture["nodes"], dtype=np.int32)
-            if self.filter_ess_floor:                     # (an untempered run keeps its key set)
-                arrays["filter_ess_floor"] = np.array(self.filter_ess_floor, dtype=np.float64)
-            if self.filter_rejuvenation:                  # (the moved vectors are filter_base; the draws are stateless)
-                arrays["filter_rejuvenation"] = np.array(self.filter_rejuvenation, dtype=np.float64)
-            if self.filter_window_offsets:               # what was recorded for the coming assimilation travels along
-                arrays["filter_window_offsets"] = np.asarray(self.filter_window_offsets, dtype=np.int64)
-                arrays["filter_window_index"], arrays["filter_window_rows"] = self.stepper.filter_window_capture()
-            if self.filter_smoother is not None:         # (a run without one keeps its key set) the tables and the ring
-                arrays["filter_smoother"] = np.asarray(self.filter_smoother, dtype=np.int64)
-                arrays["filter_smoother_hist"] = self.stepper.filter_smoother_hist()
-                arrays["filter_smoother_paths"] = self.stepper.filter_smoother_paths()
-                w, ids, rows, last = self.stepper.filter_smoother_ring()
-                arrays["filter_smoother_ring_w"], arrays["filter_smoother_ring_id"] = w, ids
-                arrays["filter_smoother_ring_rows"] = np.append(rows, last)       # ... and the last row stepped
-        if self.enkf_stride:
-            arrays["enkf_stride"] = np.array(self.enkf_stride, dtype=np.int64)
-            arrays["enkf_sigma_cm"] = np.array(self.enkf_sigma_cm, dtype=np.float64)
-            arrays["enkf_localisation_cm"] = np.array(self.enkf_localisation_cm, dtype=np.float64)
-            arrays["enkf_seed"] = np.array(self.enkf_seed, dtype=np.uint64)
-            if (self.enkf_method, self.enkf_relaxation) != ("stochastic", 0.0):     # (a default run keeps its key set)
-                arrays["enkf_method"] = np.array(ENKF_METHODS.index(self.enkf_method), dtype=np.int64)
-                arrays["enkf_relaxation"] = np.array(self.enkf_relaxation, dtype=np.float64)
-            if self.enkf_soil_moisture is not None:       # the record itself is supplied again at restore
-                arrays["enkf_sm_nodes"] = np.asarray(self.enkf_soil_moisture["nodes"], dtype=np.int32)
-            if self.enkf_window_offsets:                  # what was recorded for the coming analysis travels along
-                arrays["enkf_window_offsets"] = np.asarray(self.enkf_window_offsets, dtype=np.int64)
-                arrays["enkf_window_y"], arrays["enkf_window_rows"] = self.stepper.enkf_window_capture()
-            if self.enkf_noise_relaxation is not None:    # the analysed vectors carry the damping too (as a filtered run's)
-                arrays["enkf_noise_relaxation"] = np.array(self.enkf_noise_relaxation, dtype=np.float64)
-                arrays["enkf_noise_base"] = self.stepper.enkf_noise_base()
-        if self.noise_correlation is not None:            # (a run without one keeps its key set)
-            arrays["noise_correlation_length_cm"] = np.array(self.noise_correlation["length_cm"], dtype=np.float64)
-            arrays["noise_correlation_layers"] = np.array(int(self.noise_correlation["layers"]), dtype=np.int64)
-            arrays["noise_correlation_a"] = np.asarray(self.noise_correlation_a, dtype=np.float64)
-            arrays["noise_correlation_b"] = np.asarray(self.noise_correlation_b, dtype=np.float64)
-            if not self.filter_stride and self.enkf_noise_relaxation is None:
-                # the base vectors carry the damping, as a filtered run's; those runs' own keys hold them already
-                arrays["noise_field_base"] = self.stepper.noise_field_base()
-        self._dump_forcing_perturbation(arrays)
         for key in self.assim_tables_on():                # the filters' tables: one dataset each, <key>_table
             arrays[key + "_table"] = self.stepper.assim_table(key)
         path = Path(path)
@@ -938,98 +627,16 @@ class EnsembleSimulation(_Run):
             raise ValueError(f" EnsembleSimulation: checkpoint of a [{D}]-node column over {T} rows does not fit "
                              f"this run ([{cols.dim_d}], {forcing.dim_t}).")
         psi = np.asarray(data["psi"], dtype=float).reshape(n, D)
-        # the settings the constructor takes; which tables it then keeps says which are installed (diag_tables_on)
-        fkw = {k: int(data[k]) for k in ("profile_stride", "wtd_hist_stride", "theta_hist_bins", "theta_cov_stride") if k in data}
-        if "storage_layers_cm" in data:
-            fkw.update(storage_layers_cm=np.asarray(data["storage_layers_cm"], dtype=np.float64).reshape(-1, 2),
-                       storage_bins=int(data["storage_bins"]))
-        filt = int(data["filter_stride"]) if "filter_stride" in data else 0
-        if filt:
-            fkw.update(filter_stride=filt, filter_sigma_cm=float(data["filter_sigma_cm"]), filter_seed=int(data["filter_seed"]))
-        if filt and "filter_ess_floor" in data:
-            fkw.update(filter_ess_floor=float(data["filter_ess_floor"]))
-        if filt and "filter_rejuvenation" in data:
-            fkw.update(filter_rejuvenation=float(data["filter_rejuvenation"]))
-        if "period_ends" in data:
-            fkw.update(period_ends=np.asarray(data["period_ends"], dtype=np.int64).reshape(-1),
-                       period_thresholds_cm=np.asarray(data["period_thresholds_cm"], dtype=np.float64).reshape(-1),
-                       period_bins=int(data["period_bins"]))
-            if int(data["period_bins"]):
-                fkw.update(period_flux_max_cm=tuple(np.asarray(data["period_flux_max_cm"], dtype=np.float64).reshape(-1)))
-        if "uptake_layers_cm" in data:
-            fkw.update(uptake_layers_cm=np.asarray(data["uptake_layers_cm"], dtype=np.float64).reshape(-1, 2),
-                       uptake_bins=int(data["uptake_bins"]))
-        enkf = int(data["enkf_stride"]) if "enkf_stride" in data else 0
-        if enkf:
-            fkw.update(enkf_stride=enkf, enkf_sigma_cm=float(data["enkf_sigma_cm"]),
-                       enkf_localisation_cm=float(data["enkf_localisation_cm"]), enkf_seed=int(data["enkf_seed"]))
-        if enkf and "enkf_method" in data:
-            fkw.update(enkf_method=ENKF_METHODS[int(data["enkf_method"])], enkf_relaxation=float(data["enkf_relaxation"]))
-        has_nz = bool(enkf) and "enkf_noise_relaxation" in data
-        if has_nz:
-            fkw.update(enkf_noise_field={"relaxation": float(data["enkf_noise_relaxation"])})
-        def record(on, prefix, given):
-            """The record given must match the one the checkpoint holds the sensor table of (``prefix``'s), if any."""
-            has = bool(on) and prefix + "_sm_table" in data
-            arg = prefix + "_soil_moisture"
-            if has != (given is not None):
-                raise ValueError(f" EnsembleSimulation: {path} was written {'with' if has else 'without'} a soil-moisture "
-                                 f"record: pass {'the same record' if has else 'none'} as {arg}.")
-            if has and not np.array_equal(np.asarray(data[prefix + "_sm_nodes"]).reshape(-1),
-                                          np.asarray(given["nodes"]).reshape(-1)):
-                raise ValueError(f" EnsembleSimulation: {path} has sensors at other nodes than {arg}.")
-            if has:
-                fkw[arg] = given
-
-        record(enkf, "enkf", enkf_soil_moisture)
-        record(filt, "filter", filter_soil_moisture)
-        has_fwin = bool(filt) and "filter_window_offsets" in data
-        if has_fwin:
-            fkw.update(filter_window_offsets=tuple(int(o) for o in np.asarray(data["filter_window_offsets"]).reshape(-1)))
-        has_smo = bool(filt) and "filter_smoother" in data
-        if has_smo:
-            stride_k = [int(v) for v in np.asarray(data["filter_smoother"]).reshape(-1)]
-            fkw.update(filter_smoother={"stride": stride_k[0], "lag_rows": stride_k[0] * stride_k[1]})
-        has_win = enkf and "enkf_window_offsets" in data
-        if has_win:
-            fkw.update(enkf_window_offsets=tuple(int(o) for o in np.asarray(data["enkf_window_offsets"]).reshape(-1)))
-        has_corr = "noise_correlation_length_cm" in data
-        if has_corr:
-            fkw.update(noise_correlation={"length_cm": float(data["noise_correlation_length_cm"]),
-                                          "layers": bool(int(data["noise_correlation_layers"]))})
-        pert = cls._restored_forcing_perturbation(data)
-        if pert is not None:
-            fkw.update(forcing_perturbation=pert)
+        # the settings the constructor takes; which options it then has on says what is installed
+        options = settings.checkpoint_keywords(data, path, enkf_soil_moisture=enkf_soil_moisture,
+                                               filter_soil_moisture=filter_soil_moisture)
         sim = cls(cols, forcing, n, seed=int(data["seed"]), device=device, member_offset=int(data["member_offset"]),
-                  psi0=np.asarray(data["initial_cond"], dtype=float).reshape(-1)[:D], flags=flags, **fkw)
-        sim._restore_forcing_state(data)
-        if has_corr and not (np.array_equal(np.asarray(data["noise_correlation_a"]).reshape(-1), sim.noise_correlation_a)
-                             and np.array_equal(np.asarray(data["noise_correlation_b"]).reshape(-1), sim.noise_correlation_b)):
-            raise ValueError(f" EnsembleSimulation: {path} holds the noise correlation's tables of another column.")
+                  psi0=np.asarray(data["initial_cond"], dtype=float).reshape(-1)[:D], flags=flags, **options)
+        settings.install_state(settings.RUN_STATE, sim, data, path)
         sim.stepper.set_state(psi if n > 1 else psi[0])
         for key in sim.assim_tables_on():                 # the tables the constructor turned on, each from <key>_table
             sim.stepper.set_assim_table(key, np.asarray(data[key + "_table"], dtype=np.float64))
-        if filt:
-            sim.stepper.set_filter_base(np.asarray(data["filter_base"], dtype=np.float64).reshape(n, D))
-            if has_fwin:
-                sim.stepper.set_filter_window_capture(np.asarray(data["filter_window_index"], dtype=np.int32).reshape(-1, n),
-                                                      np.asarray(data["filter_window_rows"], dtype=np.int64))
-            if has_smo:
-                sim.stepper.set_filter_smoother_hist(np.asarray(data["filter_smoother_hist"]))
-                sim.stepper.set_filter_smoother_paths(np.asarray(data["filter_smoother_paths"], dtype=np.int64))
-                rows = np.asarray(data["filter_smoother_ring_rows"], dtype=np.int64).reshape(-1)
-                sim.stepper.set_filter_smoother_ring(np.asarray(data["filter_smoother_ring_w"], dtype=np.int32).reshape(-1, n),
-                                                     np.asarray(data["filter_smoother_ring_id"], dtype=np.int64).reshape(-1, n),
-                                                     rows[:-1], int(rows[-1]))
-        elif has_nz:
-            sim.stepper.set_enkf_noise_base(np.asarray(data["enkf_noise_base"], dtype=np.float64).reshape(n, D))
-        elif has_corr:
-            sim.stepper.set_noise_field_base(np.asarray(data["noise_field_base"], dtype=np.float64).reshape(n, D))
-        else:
-            sim.stepper.set_noise_scale(np.asarray(data["noise_scale"], dtype=float).reshape(n))
-        if has_win:
-            sim.stepper.set_enkf_window_capture(np.asarray(data["enkf_window_y"], dtype=np.float64).reshape(-1, n),
-                                                np.asarray(data["enkf_window_rows"], dtype=np.int64))
+        settings.install_state(settings.MEMBER_STATE, sim, data, path)
         sim.stepper.set_moments(np.asarray(data["moments"], dtype=np.int64))
         for key in sim.diag_tables_on():                  # the diagnostics the constructor turned on, in the registry's order
             sim.stepper.set_diag_raw(key, diag_from_checkpoint(key, data))
@@ -1124,19 +731,13 @@ class SweepSimulation(_Run):
     result is broadcast to the point's members."""
 
     def __init__(self, cols_list, forcing, n_members, seed=0, device=0, first_point=0, flags=None, psi0=None,
-                 point_ids=None, profile_stride=0, wtd_hist_stride=0, filter_stride=0, filter_sigma_cm=None,
-                 filter_seed=None, enkf_stride=0, enkf_sigma_cm=None, enkf_localisation_cm=0.0, enkf_seed=None,
-                 enkf_soil_moisture=None, enkf_method="stochastic", enkf_relaxation=0.0, enkf_window_offsets=(),
-                 filter_soil_moisture=None, theta_hist_bins=0, storage_layers_cm=None, storage_bins=0, period_ends=None,
-                 period_thresholds_cm=(), period_bins=0, period_flux_max_cm=(16.0, 4.0), filter_ess_floor=0.0,
-                 filter_window_offsets=(), enkf_noise_field=None, filter_rejuvenation=0.0, noise_correlation=None,
-                 theta_cov_stride=0, uptake_layers_cm=None, uptake_bins=0, filter_smoother=None,
-                 forcing_perturbation=None):
-        corr = self._check_noise_correlation("SweepSimulation", noise_correlation, "philox", filter_rejuvenation)
-        pert = forcing_perturbation_settings(forcing_perturbation)
+                 point_ids=None, **options):
+        """``options``: the run's options (settings.OPTIONS; :class:`_Run` describes them), normalised and cross-checked
+        before any handle exists."""
         self.points = list(cols_list)
         self.P, self.n = len(self.points), int(n_members)
         self._lead = (self.P,)
+        s = settings.normalise("SweepSimulation", options, self.points, seed, lead=self._lead)
         self.forcing, self.seed, self.device = forcing, int(seed), device
         # global index of each of this handle's points in the whole sweep: consecutive from `first_point`, or any
         # list (`point_ids`) when points are dealt to ranks round-robin so that every rank gets the same mix of costs
@@ -1160,16 +761,7 @@ class SweepSimulation(_Run):
         self.stepper.set_noise_philox(self.seed, self.member_offset)
         if self.P > 1:
             self.stepper.set_point_member_bases(self.bases)
-        self._start_noise_correlation(corr, self.points)
-        self._start_forcing_perturbation(pert)
-        self._start_tables(profile_stride, wtd_hist_stride, filter_stride, filter_sigma_cm, filter_seed, enkf_stride,
-                           enkf_sigma_cm, enkf_localisation_cm, enkf_seed, enkf_soil_moisture, enkf_method,
-                           enkf_relaxation, enkf_window_offsets, filter_soil_moisture, theta_hist_bins, storage_layers_cm,
-                           storage_bins, filter_ess_floor, filter_window_offsets, enkf_noise_field,
-                           filter_rejuvenation=filter_rejuvenation, theta_cov_stride=theta_cov_stride,
-                           filter_smoother=filter_smoother)
-        self._start_periods(period_ends, period_thresholds_cm, period_bins, period_flux_max_cm)
-        self._start_uptake(uptake_layers_cm, uptake_bins)
+        settings.start(self, s)
         self.next_row, self.kernel_ms, self.launches = 1, 0.0, 0
 
     def _spinup(self, flags):

@@ -318,16 +318,20 @@ def test_the_checkpoint_holds_the_datasets_it_held():
 
 
 def test_a_run_keeps_the_tables_its_settings_turn_on_in_the_registrys_order():
+    from helpers import digest
+    from hydromodel_amd import settings
+    _, cols, _ = digest(1)
     run = object.__new__(_Run)
-    run.profile_stride = run.theta_hist_bins = run.storage_bins = run.theta_cov_stride = run.wtd_hist_stride = 0
-    run.period_bins = run.uptake_bins = 0
-    run.storage_ranges = run.period_ends = run.uptake_cells = None
-    assert run.diag_tables_on() == []
-    run.profile_stride, run.storage_ranges, run.period_ends, run.wtd_hist_stride = 12, np.zeros((2, 2)), np.array([48]), 12
-    assert run.diag_tables_on() == ["profile", "storage", "period", "period_acc", "wtd_hist"]
-    run.theta_hist_bins = run.storage_bins = run.period_bins = run.uptake_bins = 32
-    run.theta_cov_stride, run.uptake_cells = 4, np.zeros((2, 2))
-    assert run.diag_tables_on() == list(KEYS)
+
+    def tables_on(**options):                             # (the one source: what the constructor normalises its keywords to)
+        run.on = settings.normalise("EnsembleSimulation", options, [cols], 0).on
+        return run.diag_tables_on()
+
+    assert tables_on() == []
+    some = dict(profile_stride=12, storage_layers_cm=[(0.0, 100.0), (100.0, 300.0)], period_ends=[48], wtd_hist_stride=12)
+    assert tables_on(**some) == ["profile", "storage", "period", "period_acc", "wtd_hist"]
+    assert tables_on(theta_hist_bins=32, storage_bins=32, period_bins=32, uptake_bins=32, theta_cov_stride=4,
+                     uptake_layers_cm=[(0.0, 100.0), (100.0, 300.0)], **some) == list(KEYS)
 
 
 # ---- 5. the CLI's placed table -------------------------------------------------------------------------------------------

@@ -181,24 +181,23 @@ class _FakeStepper:
 
 
 def test_dump_layout_and_the_way_back():
-    from hydromodel_amd.ensemble import EnsembleSimulation
-    sim = EnsembleSimulation.__new__(EnsembleSimulation)
+    from hydromodel_amd import settings
+    plain = settings.normalise("EnsembleSimulation", {}, [None], 0)
+    assert plain.forcing_perturbation is None and settings.checkpoint_datasets(plain) == {}      # without it: no key
+    assert settings.checkpoint_keywords({}, "ck.h5") == {}
+    given = {"precipitation_sigma": 0.3, "demand_sigma": 0.1, "correlation_days": 3.0, "seed": 11}
+    sim = settings.normalise("EnsembleSimulation", {"forcing_perturbation": given}, [None], 0)
     sim.stepper = _FakeStepper()
-    sim.forcing_perturbation = None
-    arrays = {}
-    sim._dump_forcing_perturbation(arrays)
-    assert arrays == {} and EnsembleSimulation._restored_forcing_perturbation(arrays) is None     # without it: no key
-    sim.forcing_perturbation = {"precipitation_sigma": 0.3, "demand_sigma": 0.1, "correlation_days": 3.0, "seed": 11,
-                                "phi": 0.7}
-    sim._dump_forcing_perturbation(arrays)
+    (_, write, install), = [f for f in settings.RUN_STATE if f[0] == "forcing_perturbation"]
+    arrays = dict(settings.checkpoint_datasets(sim), **write(sim, sim.stepper))
     assert sorted(arrays) == ["forcing_correlation_days", "forcing_demand_sigma", "forcing_precipitation_sigma",
                               "forcing_seed", "forcing_state", "forcing_state_day"]
     assert arrays["forcing_state"].shape == (2, 3) and arrays["forcing_state"].dtype == np.float64
     assert arrays["forcing_state_day"].dtype == np.int64 and int(arrays["forcing_state_day"]) == 4
     assert arrays["forcing_seed"].dtype == np.uint64
-    back = EnsembleSimulation._restored_forcing_perturbation(arrays)
-    assert back == {"precipitation_sigma": 0.3, "demand_sigma": 0.1, "correlation_days": 3.0, "seed": 11}
-    sim._restore_forcing_state({k: np.asarray(v).reshape(-1) for k, v in arrays.items()})       # (a flat container)
+    back = settings.checkpoint_keywords(arrays, "ck.h5")
+    assert back == {"forcing_perturbation": given}
+    install(sim, {k: np.asarray(v).reshape(-1) for k, v in arrays.items()}, "ck.h5")            # (a flat container)
     assert _same(sim.stepper.got[0], np.arange(6, dtype=np.float64).reshape(2, 3)) and sim.stepper.got[1] == 4
 
 

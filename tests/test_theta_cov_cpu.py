@@ -188,11 +188,11 @@ def test_layer_std_matches_the_direct_sigma_of_the_layers_storage():
 
 # ---- the CLI's block -----------------------------------------------------------------------------------------------------
 def test_the_cli_key_parses():
-    from hydromodel_amd.cli import _covariance_kwargs, covariance_check, covariance_settings
-    assert covariance_settings({"Members": 8}) is None and _covariance_kwargs(None) == {}
+    from hydromodel_amd.cli import RunSettings, covariance_check, covariance_settings
+    assert covariance_settings({"Members": 8}) is None and "theta_cov_stride" not in RunSettings(cov=None).kwargs()
     assert covariance_settings({"Profiles": 48, "Covariance": {"Node_Stride": 4, "Sensor_Sigma": 0.02}}) == (4, 0.02)
     assert covariance_settings({"Profiles": 1, "Covariance": {}}) == (1, None)
-    assert _covariance_kwargs((4, 0.02)) == {"theta_cov_stride": 4}
+    assert RunSettings(cov=(4, 0.02)).kwargs()["theta_cov_stride"] == 4
     assert covariance_check((4, 0.02), 200, 17521, 48) == 50 and covariance_check(None, 200, 17521, 48) is None
     assert covariance_check((200, None), 200, 17521, 1) == 1
 
