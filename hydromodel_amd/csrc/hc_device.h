@@ -67,6 +67,17 @@ __host__ __device__ constexpr int ntab_lds(int slots, bool special = true)
 #ifndef HC_RHS_DIET
 #define HC_RHS_DIET 1
 #endif
+// Round 9: independent work of the RHS side by side instead of one after another (rhs_eval's ILP: the kernel of 5 cells per lane
+// with default exponents, its PREDICT twin and its step RHS hook only).  A bit mask of the parts, each measured on its own
+// (LAB_NOTES.md §43); no statement's arithmetic changes, only the order of independent instructions, so the same bits.
+//   1: the five divisions of the assembly of dy/dt statement by statement across the cells (the cell model's HC_V style)
+//   4: the table reads of the first-midpoint ET call ahead of the interior call, which reads the same four slots
+//   8: the fifteen table reads of the ET interior call's water_k > 0 block back to back in front of one wait
+//   (2, the ET interior call's wave reductions with their two chains pinned step by step, was measured and is not kept: §43)
+// -DHC_RHS_ILP=0: the code before round 9.
+#ifndef HC_RHS_ILP
+#define HC_RHS_ILP 13
+#endif
 // T_VALID = 1.0 in the slots of the D-1 midpoints, 0.0 beyond (a lane mask as data: a mask proper is an SGPR pair
 // the compiler spills and reloads with two v_readlane per use), T_INVD1 = 1/(por - wlt) (a zero denominator counts as 1)
 // per-slot integer tables, [NGTAB][64*CPL]
@@ -1075,6 +1086,7 @@ __device__ __forceinline__ void rhs_eval(const ColumnDev &P, const RowDev &R, co
     constexpr bool DIET = ONE_BALLOT && HC_RHS_DIET;           // (ONE_BALLOT = "a two-waves-per-SIMD kernel": see HC_RHS_DIET)
     constexpr bool MDIET = ONE_BALLOT && HC_MODEL_DIET;
     constexpr bool PACK = ONE_BALLOT && SPECIAL && CPL == 5 && H == 1 && HC_MODEL_PACK;
+    constexpr int ILP = (ONE_BALLOT && SPECIAL && CPL == 5 && H == 1) ? (HC_RHS_ILP) : 0;      // (round 9: see HC_RHS_ILP)
     constexpr int SLOTS = WAVE * CPL * H;                      // table row stride
     const int hb = H == 2 ? comm.half * (WAVE * CPL) : 0;      // index of this wave's first node
     const bool last_half = H == 1 || comm.half == H - 1;
@@ -1223,6 +1235,17 @@ __device__ __forceinline__ void rhs_eval(const ColumnDev &P, const RowDev &R, co
     // ---- evapo-transpiration (daylight only), richards_pde.py:258-302 + tree_roots.py:213-291
     HC_RSTAMP(26);
     if (P.flag_et && normal_mode && R.daylight && (H == 1 || comm.half == 0)) {   // the root zone lies in the upper half
+        // Round 9 (HC_RHS_ILP bit 4): the four table reads of the first-midpoint call (b) are issued here, ahead of the interior
+        // call (a).  They are slot 0's, (a)'s own reads at c = 0: one LDS read serves both calls, and (b), which sits behind (a)'s
+        // reductions and wave-uniform branches, no longer begins with an LDS wait of its own.
+        constexpr bool FM_EARLY = (ILP & 4) != 0;
+        double fm_wlt = 0.0, fm_fc = 0.0, fm_invd1 = 0.0, fm_root = 0.0;
+        if constexpr (FM_EARLY) {
+            fm_wlt = tab[T_WLT * SLOTS + lane];
+            fm_fc = tab[T_FC * SLOTS + lane];
+            fm_invd1 = tab[T_INVD1 * SLOTS + lane];
+            fm_root = tab[T_ROOT * SLOTS + lane];
+        }
         // (a) interior call: midpoints 1..n_root_int, normalised together.
         // alpha_02 (tree_roots.py:245-265) is exactly 1 where theta > field capacity and 0 elsewhere:
         // inside (wlt, fc] the reference's (theta - fc)/(fc - wlt) is <= 0 and gets clipped to 0.
@@ -1273,6 +1296,15 @@ __device__ __forceinline__ void rhs_eval(const ColumnDev &P, const RowDev &R, co
             double tot_x = 0.0;
             if (water_k > 0.0) {
                 HC_RSUB(57);
+                if constexpr ((ILP & 8) != 0) {
+                    // Round 9 (HC_RHS_ILP bit 8): the fifteen table values this block reads, all asked for here.  The compiler sinks
+                    // their reads into this block (they are dead when water_k <= 0) and then issues them one or two at a time,
+                    // each followed by its own wait for the LDS; one statement that needs them all puts the reads back to back
+                    // in front of a single wait.
+                    asm("" : "+v"(t_fc[0]), "+v"(t_fc[1]), "+v"(t_fc[2]), "+v"(t_fc[3]), "+v"(t_fc[4]), "+v"(t_invd1[0]), "+v"(t_invd1[1]),
+                        "+v"(t_invd1[2]), "+v"(t_invd1[3]), "+v"(t_invd1[4]), "+v"(t_root[0]), "+v"(t_root[1]), "+v"(t_root[2]),
+                        "+v"(t_root[3]), "+v"(t_root[4]));
+                }
                 double total = tot_theta * P.dz;
                 total = total == 0.0 ? 1.0 : total;
                 const double inv_total = fast_rcp(total);
@@ -1335,16 +1367,16 @@ __device__ __forceinline__ void rhs_eval(const ColumnDev &P, const RowDev &R, co
         if (P.n_root_first > 0) {
             HC_RSUB(59);
             // evaluated by every lane on its own slot-0 cell (no divergent branch); only lane 0's result is kept
-            const double t0 = th[0], w0 = tab[T_WLT * SLOTS + lane], f0 = tab[T_FC * SLOTS + lane];
+            const double t0 = th[0], w0 = FM_EARLY ? fm_wlt : tab[T_WLT * SLOTS + lane], f0 = FM_EARLY ? fm_fc : tab[T_FC * SLOTS + lane];
             const double water_k = fmax((t0 - w0) * P.dz, 0.0);
             const double local = t0 * P.dz;
             const double ratio = local == 0.0 ? 0.0 : 1.0;              // local / (local or 1): exactly 0 or 1
-            const double a1 = fmax(t0 * tab[T_INVD1 * SLOTS + lane], ratio);
+            const double a1 = fmax(t0 * (FM_EARLY ? fm_invd1 : tab[T_INVD1 * SLOTS + lane]), ratio);
             // single cell: the all-ones guard always applies, alpha_02 * 0.1 (tree_roots.py:270-272)
             const double rho = (water_k > 0.0 && t0 > f0) ? fabs(a1 * 0.1) : 0.0;
             double tot = rho * P.dz;
             tot = tot == 0.0 ? 1.0 : tot;
-            double x0 = fast_div(rho, tot) * tab[T_ROOT * SLOTS + lane];
+            double x0 = fast_div(rho, tot) * (FM_EARLY ? fm_root : tab[T_ROOT * SLOTS + lane]);
             double tot_x = x0 * P.dz;
             const bool big = tot_x > 1.0;
             const double x0n = fast_div(x0, big ? tot_x : 1.0);
@@ -1492,20 +1524,55 @@ __device__ __forceinline__ void rhs_eval(const ColumnDev &P, const RowDev &R, co
     const double cP0 = shfl_up1(Cc[CPL - 1], lane, upper ? 0.0 : edge_C);
     const double sP0 = shfl_up1(sk[CPL - 1], lane, upper ? 0.0 : edge_s);
     const double fP0 = shfl_up1(fl[CPL - 1], lane, upper ? -pL : edge_f);
+    if constexpr ((ILP & 1) != 0) {
+        // Round 9: fast_div's eight operations statement by statement across the cells -- the five reciprocals back to back, every
+        // refinement line five independent FMAs: one chain nine deep and five wide where the loop below compiles to five chains
+        // in sequence.  Per cell the operations and operands of fast_div(num, den); the rest as below.
+        double den[CPL], num[CPL], r[CPL], e[CPL], q[CPL];
 #pragma unroll
-    for (int c = 0; c < CPL; c++) {
-        const int i = hb + lane * CPL + c;
-        const double cP = c == 0 ? cP0 : Cc[c > 0 ? c - 1 : 0];
-        const double sP = c == 0 ? sP0 : sk[c > 0 ? c - 1 : 0];
-        const double fP = c == 0 ? fP0 : fl[c > 0 ? c - 1 : 0];
-        double den = half * Cc[c] + half * cP;
-        const double num = (fl[c] - fP) + (half * sk[c] + half * sP);
-        den = den == 0.0 ? 1.0 : den;
-        f[c] = fast_div(num, den);
-        if (aux && i < D - 1) {
-            aux[i] = Cc[c];
-            aux[(D - 1) + i] = sk[c];
-            aux[2 * (D - 1) + i] = fl[c];
+        for (int c = 0; c < CPL; c++) {
+            const double cP = c == 0 ? cP0 : Cc[c > 0 ? c - 1 : 0];
+            const double sP = c == 0 ? sP0 : sk[c > 0 ? c - 1 : 0];
+            const double fP = c == 0 ? fP0 : fl[c > 0 ? c - 1 : 0];
+            den[c] = half * Cc[c] + half * cP;
+            num[c] = (fl[c] - fP) + (half * sk[c] + half * sP);
+            den[c] = den[c] == 0.0 ? 1.0 : den[c];
+        }
+#define HC_DIVV(a, expr) _Pragma("unroll") for (int c = 0; c < CPL; c++) a[c] = (expr);
+        HC_DIVV(r, __builtin_amdgcn_rcp(den[c]))
+        HC_DIVV(e, fma(-den[c], r[c], 1.0))
+        HC_DIVV(r, fma(e[c], r[c], r[c]))
+        HC_DIVV(e, fma(-den[c], r[c], 1.0))
+        HC_DIVV(r, fma(e[c], r[c], r[c]))
+        HC_DIVV(q, num[c] * r[c])
+        HC_DIVV(e, fma(-den[c], q[c], num[c]))
+        HC_DIVV(f, fma(e[c], r[c], q[c]))
+#undef HC_DIVV
+#pragma unroll
+        for (int c = 0; c < CPL; c++) {
+            const int i = hb + lane * CPL + c;
+            if (aux && i < D - 1) {
+                aux[i] = Cc[c];
+                aux[(D - 1) + i] = sk[c];
+                aux[2 * (D - 1) + i] = fl[c];
+            }
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < CPL; c++) {
+            const int i = hb + lane * CPL + c;
+            const double cP = c == 0 ? cP0 : Cc[c > 0 ? c - 1 : 0];
+            const double sP = c == 0 ? sP0 : sk[c > 0 ? c - 1 : 0];
+            const double fP = c == 0 ? fP0 : fl[c > 0 ? c - 1 : 0];
+            double den = half * Cc[c] + half * cP;
+            const double num = (fl[c] - fP) + (half * sk[c] + half * sP);
+            den = den == 0.0 ? 1.0 : den;
+            f[c] = fast_div(num, den);
+            if (aux && i < D - 1) {
+                aux[i] = Cc[c];
+                aux[(D - 1) + i] = sk[c];
+                aux[2 * (D - 1) + i] = fl[c];
+            }
         }
     }
     if (aux && lane == 0 && upper) aux[3 * (D - 1)] = pL;     // (a split column's lower half never holds pL)
