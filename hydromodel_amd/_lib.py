@@ -232,6 +232,13 @@ EXPORTS = {
     "hc_get_enkf_noise_gain": ([C.c_void_p, _dp], C.c_int),
     "hc_get_enkf_noise_sqrt_gain": ([C.c_void_p, _dp], C.c_int),
     "hc_get_enkf_noise_sqrt_shift": ([C.c_void_p, _dp], C.c_int),
+    "hc_set_enkf_forcing": ([C.c_void_p, C.c_int32, C.c_double], C.c_int),
+    "hc_get_enkf_forcing": ([C.c_void_p, C.POINTER(C.c_int32), _dp], C.c_int),
+    "hc_get_enkf_g_table": ([C.c_void_p, _dp, C.c_int64], C.c_int),
+    "hc_set_enkf_g_table": ([C.c_void_p, _dp, C.c_int64], C.c_int),
+    "hc_get_enkf_g_gain": ([C.c_void_p, _dp], C.c_int),
+    "hc_get_enkf_g_sqrt_gain": ([C.c_void_p, _dp], C.c_int),
+    "hc_get_enkf_g_sqrt_shift": ([C.c_void_p, _dp], C.c_int),
     "hc_get_enkf_noise_base": ([C.c_void_p, _dp, C.c_int64, C.c_int64], C.c_int),
     "hc_set_enkf_noise_base": ([C.c_void_p, _dp], C.c_int),
     "hc_set_enkf_window": ([C.c_void_p, C.c_int32, _ip], C.c_int),

@@ -221,7 +221,8 @@ unknown keys, only membership of the 12 is checked):
   rows) and an AR(1) from day to day with e-folding time ``Correlation_Days``; the refresh rule, surface evaporation,
   daylight, the well's record and the spin-up stay the record's.  At least one sigma is required, each a finite number in
   [0, 1]; ``Correlation_Days`` in [0, 365], default 0 (white in time); ``Seed`` defaults to the ensemble's.  Applied after
-  the spin-up, before the filters; the particle filter moves a member's factor state with it, the EnKF leaves it alone.
+  the spin-up, before the filters; the particle filter moves a member's factor state with it, the EnKF leaves it alone
+  unless the block says ``"EnKF": true`` (below).
   Works with either noise source, both filters, every table, a sweep, a sharded EnKF and ``--gpus N`` (members are keyed
   by their global id).  Refused: a non-object, an unknown key, a bool or non-finite number, a value outside its range, and
   ``"Filter": {"Sharded": true}`` on a single-point run (the exchanged columns do not carry the factor state).
@@ -229,6 +230,19 @@ unknown keys, only membership of the 12 is checked):
   ``forcing_correlation_days``, ``forcing_phi`` and ``forcing_seed``, and the run ends with `` [Ensemble xN] forcing
   perturbation: precipitation sigma ..., demand sigma ..., correlation ... days``.  Without the key every bit, file and
   line stays.
+* ``"Forcing_Perturbation": {..., "EnKF": true}`` or ``{"EnKF": {"Relaxation": 0.2}}``: joint state and forcing-error
+  estimation (include/hydrocol.h hc_set_enkf_forcing).  Every EnKF analysis also updates each member's factor state g of
+  the day the row lies in, from the same observations, draws and factor, with no taper on its covariance with the
+  observations; the rest of that day, and through the AR(1) every later day, then run with the corrected factors.  The
+  anomalies are relaxed to prior spread with the given ``Relaxation`` (``true``: the EnKF block's); g regains spread from
+  its own recursion, so 0 is a sound choice.  Refused before any GPU call: a value that is neither a bool nor an object,
+  an unknown inner key, a relaxation that is a bool or outside [0, 1], no ``EnKF`` block with ``Stride`` > 0 (a ``Filter``
+  block instead included), and ``"EnKF": {"Sharded": true}`` on a single-point run (the exchanged partials cover psi
+  only).  A sweep works on any number of GPUs.  Without the key, or with ``false``, nothing changes.  Added to
+  ``<Output_Name>_ensemble.h5``: ``enkf_forcing`` (1), ``enkf_forcing_relaxation`` and, over the ``enkf_rows`` ``[R]``,
+  ``enkf_forcing_prior_mean``, ``enkf_forcing_prior_std``, ``enkf_forcing_post_mean``, ``enkf_forcing_post_std``
+  ``[R][2]`` (precipitation, demand) and ``enkf_forcing_rejected`` ``[R]`` (a sweep: a leading ``[P]`` axis), and the run
+  ends with `` [Ensemble xN] EnKF forcing: posterior spread ... / ... of prior (precipitation / demand) over R rows``.
 * ``"EnKF": {..., "Noise_Field": true}`` or ``{"Noise_Field": {"Relaxation": 0.5}}``: every analysis also updates each
   member's base noise vector -- its conductivity field -- together with its state, from the same observations, draws and
   factor (include/hydrocol.h hc_set_enkf_noise_field).  The vectors' anomalies are relaxed to prior spread with the
@@ -405,7 +419,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
         covariance_check(cov, cols.dim_d, forcing.dim_t, _profile_stride(ens), len(ens.get("Points") or [0]))
     frecord = soil_moisture_record_of(fsm, cols, water_data, "Filter")
     assim = Assimilation(filt, frecord, ess_floor, fwindow, rejuvenation, enkf, record, scheme, window, noise_alpha,
-                         smoother=smoother)
+                         smoother=smoother, forcing_alpha=None if pert is None else pert.get("enkf_relaxation"))
     if cols.flags["PREDICT"] and not ens.get("repair_predict"):
         raise TypeError("'numpy.float64' object cannot be interpreted as an integer")     # richards_pde.py:327-330
     n_members = int(ens.get("Members", 4096))
@@ -510,6 +524,7 @@ class Assimilation:
     window: Optional[tuple] = None
     noise_alpha: Optional[float] = None
     smoother: Optional[tuple] = None
+    forcing_alpha: Optional[float] = None   # Forcing_Perturbation.EnKF (it reaches the constructor inside RunSettings.pert)
 
     def kwargs(self):
         """The ``filter_*`` / ``enkf_*`` keywords of EnsembleSimulation / SweepSimulation: an owner that is off and an
@@ -621,7 +636,8 @@ def _reduce_assimilation(ranks, sim, ids, P, T, cols, a, label, keep_points):
                      (_enkf_method_arrays(a.enkf, a.scheme), None),
                      _reduce_sm(*where, stride, a.record, slots, label, keep_points, owner),
                      _reduce_window(*where, stride, a.window, slots, label, keep_points, cols.z[0], owner),
-                     _reduce_enkf_noise(*where, a.enkf, a.noise_alpha, label, keep_points)]
+                     _reduce_enkf_noise(*where, a.enkf, a.noise_alpha, label, keep_points),
+                     _reduce_enkf_forcing(ranks, sim, ids, P, T, a.enkf, a.forcing_alpha, label, keep_points)]
         for datasets, line in parts:
             out.update(datasets)
             lines.append(line)
@@ -680,7 +696,7 @@ def _noise_correlation_arrays(corr, cols_list, label, keep_points):
     return out, line
 
 
-FORCING_PERTURBATION_KEYS = ("Precipitation_Sigma", "Demand_Sigma", "Correlation_Days", "Seed")
+FORCING_PERTURBATION_KEYS = ("Precipitation_Sigma", "Demand_Sigma", "Correlation_Days", "Seed", "EnKF")
 
 
 def forcing_perturbation_settings(ens):
@@ -718,7 +734,67 @@ def forcing_perturbation_settings(ens):
     if isinstance(filt, dict) and filt.get("Sharded") and filt.get("Stride") and not ens.get("Points"):
         raise ValueError(" Ensemble: Forcing_Perturbation with \"Filter\": {\"Sharded\": true}: the columns the ranks exchange "
                          "do not carry the members' forcing state; run the filter unsharded.")
+    alpha = _forcing_enkf_settings(ens, block)
+    if alpha is not None:
+        out["enkf_relaxation"] = alpha
     return out
+
+
+def _forcing_enkf_settings(ens, block):
+    """Forcing_Perturbation.EnKF -> the relaxation of the forcing state's anomalies in the EnKF's analysis, or None when
+    the key is absent or false (the run, its file and its lines are then those of a block without it).  ``true``: the EnKF
+    block's ``Relaxation`` (0 without one); ``{"Relaxation": a}``: a.  A ValueError for a value of another type, an unknown
+    inner key, a relaxation that is a bool or outside [0, 1], no active EnKF block, and a sharded single-point run."""
+    from numbers import Real
+    from .stepper import forcing_enkf_settings
+    if "EnKF" not in block:
+        return None
+    value = block["EnKF"]
+    if not isinstance(value, (bool, dict)):
+        raise ValueError(f" Ensemble: Forcing_Perturbation.EnKF = {value!r} must be true, false or {{\"Relaxation\": a}}.")
+    enkf = ens.get("EnKF")
+    inherited = enkf.get("Relaxation", 0.0) if isinstance(enkf, dict) else 0.0
+    inherited = float(inherited) if isinstance(inherited, Real) and not isinstance(inherited, bool) else 0.0
+    try:
+        alpha = forcing_enkf_settings(value, inherited if 0.0 <= inherited <= 1.0 else 0.0)
+    except ValueError as bad:
+        raise ValueError(f" Ensemble: {str(bad)[0].upper()}{str(bad)[1:]}.") from None
+    if alpha is None:
+        return None
+    if ens.get("Filter") is not None and not isinstance(enkf, dict):
+        raise ValueError(" Ensemble: Forcing_Perturbation.EnKF with a \"Filter\" block: the particle filter carries the "
+                         "members' forcing state already; the key serves the \"EnKF\" block.")
+    stride = enkf.get("Stride", 48) if isinstance(enkf, dict) else 0
+    if not isinstance(enkf, dict) or (isinstance(stride, Real) and not isinstance(stride, bool) and stride == 0):
+        raise ValueError(" Ensemble: Forcing_Perturbation.EnKF needs an active \"EnKF\" block (EnKF.Stride > 0).")
+    if enkf.get("Sharded") is True and not ens.get("Points"):
+        raise ValueError(" Ensemble: Forcing_Perturbation.EnKF with \"EnKF\": {\"Sharded\": true}: the partials the ranks "
+                         "exchange cover psi only, not the forcing state.")
+    return alpha
+
+
+def _reduce_enkf_forcing(ranks, sim, ids, P, T, enkf, forcing_alpha, label, keep_points):
+    """The forcing analysis's datasets over the EnKF's analysed rows, the [P][n_arow][9] table placed at this rank's points
+    and summed over the ranks like the EnKF's (float64 as int64 bits, one collective), and the closing line (rank 0)."""
+    import numpy as np
+    from .multigpu import place_points
+    from .stepper import ENKF_FORCING_WIDTH, enkf_forcing_summary, stride_rows
+    stride = enkf[0]
+    if not stride or forcing_alpha is None:
+        return {}, None
+    shape = (stride_rows(T, stride), ENKF_FORCING_WIDTH)
+    local = sim.stepper.enkf_forcing_table().reshape((-1,) + shape) if sim is not None else np.zeros((0,) + shape)
+    table = place_points(local[:len(ids)], ids, P, ranks)
+    summary = enkf_forcing_summary(table if keep_points else table[0], stride, forcing_alpha)
+    out = {"enkf_forcing": np.array(1, dtype=np.int8), "enkf_forcing_relaxation": np.array(forcing_alpha, dtype=np.float64)}
+    out.update(("enkf_" + k, summary[k]) for k in ("forcing_prior_mean", "forcing_prior_std", "forcing_post_mean",
+                                                    "forcing_post_std", "forcing_rejected"))
+    if ranks.rank != 0:
+        return out, None
+    ratio = summary["forcing_spread_ratio"]
+    line = (f" [{label}] EnKF forcing: posterior spread {ratio[0]:.4f} / {ratio[1]:.4f} of prior (precipitation / demand) "
+            f"over {int(summary['rows'].size)} rows")
+    return out, line
 
 
 def _forcing_perturbation_arrays(pert, label):

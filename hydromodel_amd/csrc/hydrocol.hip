@@ -405,6 +405,14 @@ struct hc_handle {
     int64_t fp_day_next = -1;    // the day fp_g_alt stands at: a fill is pending until its step launch is issued
     int64_t fp_offset = -1;      // hc_set_forcing_member_offset (-1: the noise source's)
     DevBuf<double> fp_g, fp_g_alt, fp_fmul;
+    // the members' forcing state in the EnKF analysis (hc_set_enkf_forcing): on / off and the relaxation of its anomalies;
+    // diagnostics float64 [P][n_arow][9] keyed like the EnKF's; g as the member-major columns x [N][2] the analysis
+    // works on; what it keeps of x (EnkfVec with D = 2, always with the spread); the refused members and their count
+    bool enkf_fg = false, fg_done = false;   // on; an analysis has updated g since it was set
+    double enkf_fg_alpha = 0.0;
+    AccTable<double> enkf_fgt{"entries"};
+    EnkfVec enkf_gv;
+    DevBuf<double> fg_x, fg_rej, fg_rejsum;
     int n_cu = 256;
     double jac_reject = NUM_JAC_DIFF_REJECT;
 };
@@ -2200,6 +2208,7 @@ constexpr int ENKF_TILE = 256;                         // members per partial of
 constexpr int ENKF_THREADS = 1024;                     // the sums of the tile partials
 constexpr int ENKF_SLOTS = HC_MAX_DEPTH_NODES / WAVE;  // depth nodes per lane of the update (one wave per member)
 constexpr int ENKF_WIDTH = 8;                          // diagnostics per point and slot
+constexpr int ENKF_FORCING_WIDTH = 9;                  // forcing-state diagnostics per point and slot (hc_set_enkf_forcing)
 constexpr int ENKF_SENSORS = 8;                        // sensors in a record
 constexpr int ENKF_OBS = ENKF_SENSORS + 1;             // observations per member: the well, then the sensors present
 constexpr int ENKF_SENSOR_WIDTH = 6;                   // sensor diagnostics per point, slot and sensor
@@ -2414,13 +2423,14 @@ __device__ bool enkf_cholesky(const double *A, int n, double *L)
 // reduced gain Kr_d = (rho_d o c_d) L^-T (L + R^1/2)^-1 into rgain[p][i][d]: the forward substitution once more, then a
 // backward substitution with the lower-triangular L + R^1/2 (the same LDS working set).
 // stats == NULL (the noise field's gain, hc_set_enkf_noise_field: s1 and s2 are the sums over (z, Y), whose Y block is
-// the state's to the bit, and so is the factor): no table is written.
+// the state's to the bit, and so is the factor): no table is written.  taper_x = 0 (the forcing state's gain,
+// hc_set_enkf_forcing: its D = 2 rows have no depth): rho_d = 1, while S keeps its taper.
 __global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void enkf_gain_kernel(const double *s1, const double *s2, long long mpp,
                                                                        int D, const EnkfRow s, double sigma, double loc,
                                                                        double z_obs, double dz, double *gain,
                                                                        double *stats, double *sm_stats, long long n_arow,
                                                                        long long slot, double *rgain, double *dbar,
-                                                                       double *win_stats)
+                                                                       double *win_stats, int taper_x)
 {
 #pragma clang fp contract(off)
     // the working sets live in LDS (dynamically indexed: in registers they would go to scratch)
@@ -2508,7 +2518,7 @@ __global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void enkf_gain_kernel(const dou
     }
     double *u = U[d];
     for (int i = 0; i < W; i++) {
-        const double rho = loc > 0.0 ? gaspari_cohn(fabs((double)d * dz - zeta[i]) / loc) : 1.0;
+        const double rho = loc > 0.0 && taper_x ? gaspari_cohn(fabs((double)d * dz - zeta[i]) / loc) : 1.0;
         double v = rho * (mpp > 1 ? S2[(size_t)d * W + i] / n1 : 0.0);
         for (int k = 0; k < i; k++) v -= Ls[i * ENKF_OBS + k] * u[k];
         u[i] = v / Ls[i * ENKF_OBS + i];
@@ -2524,7 +2534,7 @@ __global__ __launch_bounds__(HC_MAX_DEPTH_NODES) void enkf_gain_kernel(const dou
     for (int i = 0; i < W; i++) inc += u[i] * dl[i];
     dbar[(size_t)p * D + d] = inc;
     for (int i = 0; i < W; i++) {
-        const double rho = loc > 0.0 ? gaspari_cohn(fabs((double)d * dz - zeta[i]) / loc) : 1.0;
+        const double rho = loc > 0.0 && taper_x ? gaspari_cohn(fabs((double)d * dz - zeta[i]) / loc) : 1.0;
         double v = rho * (mpp > 1 ? S2[(size_t)d * W + i] / n1 : 0.0);
         for (int k = 0; k < i; k++) v -= Ls[i * ENKF_OBS + k] * u[k];
         u[i] = v / Ls[i * ENKF_OBS + i];
@@ -2866,6 +2876,49 @@ __global__ void enkf_noise_diag_kernel(const double *s1, const double *sq_b, con
     t[2 * D + d] = base[(size_t)(p * mpp) * D + d] + sums[k] / (double)mpp;
     t[3 * D + d] = mpp > 1 ? sqrt(sq_a[k] / n1) : 0.0;
     if (d == 0) t[4 * (size_t)D] = rejsum[p];
+}
+
+// ---- the members' forcing state in the analysis (hc_set_enkf_forcing): g [2][N] is stream-major, the analysis's kernels
+// walk member-major columns, so g goes through x [N][2] and back (one thread per member; a copy keeps every bit)
+__global__ void enkf_forcing_gather_kernel(const double *g, long long n_members, double *x)
+{
+    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n_members) return;
+    x[2 * (size_t)m] = g[m];
+    x[2 * (size_t)m + 1] = g[(size_t)n_members + m];
+}
+
+// ... and back, the streams that are analysed alone (active_s = sigma_s > 0): the other keeps every bit of its g
+__global__ void enkf_forcing_scatter_kernel(const double *x, long long n_members, int active0, int active1, double *g)
+{
+    const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n_members) return;
+    if (active0) g[m] = x[2 * (size_t)m];
+    if (active1) g[(size_t)n_members + m] = x[2 * (size_t)m + 1];
+}
+
+// The forcing state's diagnostics, one thread per point and stream, into table[p][slot][9]: columns 4 s + (prior mean,
+// prior std, posterior mean, posterior std) as enkf_noise_diag_kernel forms them from the prior sums (s1 [P][2 + m'],
+// sq_b) and the spread passes after the relaxation (x of the point's first member + sums / N_p; sq_a); a stream that is
+// not analysed reports its prior twice; stream 0's thread adds the point's refused count in column 8.
+__global__ void enkf_forcing_diag_kernel(const double *s1, const double *sq_b, const double *sums, const double *sq_a,
+                                         const double *x, const double *rejsum, long long n_points, long long mpp, int W,
+                                         int active0, int active1, double *table, long long n_arow, long long slot)
+{
+#pragma clang fp contract(off)
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_points * 2) return;
+    const long long p = k / 2;
+    const int s = (int)(k % 2);
+    const double n1 = (double)(mpp - 1);
+    double *t = table + ((size_t)p * n_arow + slot) * ENKF_FORCING_WIDTH;
+    const double mean_b = s1[(size_t)p * (2 + W) + s] / (double)mpp, std_b = mpp > 1 ? sqrt(sq_b[k] / n1) : 0.0;
+    const bool active = s ? active1 != 0 : active0 != 0;
+    t[4 * s] = mean_b;
+    t[4 * s + 1] = std_b;
+    t[4 * s + 2] = active ? x[(size_t)(p * mpp) * 2 + s] + sums[k] / (double)mpp : mean_b;
+    t[4 * s + 3] = active ? (mpp > 1 ? sqrt(sq_a[k] / n1) : 0.0) : std_b;
+    if (s == 0) t[8] = rejsum[p];
 }
 
 // One thread per point: the posterior diagnostics from the raw sums of Ypost (s1 [P][W + 1], s2 [P][W + 1][W + 1]): the
@@ -4518,6 +4571,14 @@ int ensure_nz(hc_handle *h)
     return ensure_da_table(h, h->enkf_nzt, h->enkf_stride, 4 * (int64_t)h->p.dim_d + 1, 0);
 }
 
+// the forcing state's diagnostics (hc_set_enkf_forcing): [P][n_arow][9] float64, created as NaN
+int ensure_fg(hc_handle *h)
+{
+    if (!h->enkf_fg) return fail(HC_ERR_ARG, "the forcing analysis is off (hc_set_enkf_forcing)");
+    if (int rc = ensure_enkf(h)) return rc;
+    return ensure_da_table(h, h->enkf_fgt, h->enkf_stride, ENKF_FORCING_WIDTH, 0);
+}
+
 int ensure_sm(hc_handle *h) { return ensure_record(h, h->enkf_sm, ensure_enkf, h->enkf_stride, "hc_set_enkf_soil_moisture"); }
 int ensure_win(hc_handle *h) { return ensure_window(h, h->enkf_win, ensure_enkf, h->enkf_stride, "hc_set_enkf_window"); }
 
@@ -4559,10 +4620,19 @@ void nz_off(hc_handle *h)
     h->enkf_z.release(); h->nz_rej.release(); h->nz_rejsum.release();
 }
 
+void fg_off(hc_handle *h)
+{
+    h->enkf_fg = h->fg_done = false;
+    h->enkf_fg_alpha = 0.0;
+    h->enkf_fgt.release();
+    h->enkf_gv.release(); h->fg_x.release(); h->fg_rej.release(); h->fg_rejsum.release();
+}
+
 void enkf_off(hc_handle *h)
 {
     shard_off(h);
     nz_off(h);
+    fg_off(h);
     h->enkf_stride = 0;
     h->enkf_done = false;
     h->enkf_width = 0;
@@ -4612,6 +4682,7 @@ int launch_noise_fill(hc_handle *h, double *out, int64_t n_vec, const long long 
 // hc_set_filter, hc_set_enkf, hc_set_noise_correlation)
 void forcing_pert_off(hc_handle *h)
 {
+    fg_off(h);                   // (the state the EnKF would analyse goes with it)
     h->fp_on = false;
     h->fp_day = h->fp_day_next = h->fp_offset = -1;
     h->fp_g.release(), h->fp_g_alt.release(), h->fp_fmul.release();
@@ -6425,6 +6496,7 @@ struct EnkfPass {
     double *part, *part_sq_b, *part_sq;
     dim3 tiles, members, cols_prior;   // a block per tile and point; 256 members a block; a thread per column of (x, Y)
     unsigned blocks;                   // of the member kernels that walk x
+    bool taper_x = true;               // the gain tapers C_xY (off: a vector without depth, hc_set_enkf_forcing)
 
     // the tile partials of one pass (enkf_partial_kernel's arguments), at the handle's tile offset
     hipError_t partials(bool square, const double *x, const double *Y, int width, const double *sums, int Dc, dim3 threads,
@@ -6493,7 +6565,7 @@ int enkf_vector(const EnkfPass &g, double *x, EnkfVec &v, double alpha, bool squ
     if (square && (rc = g.reduce(g.part_sq_b, D, v.sq_b.p))) return rc;
     hipLaunchKernelGGL(enkf_gain_kernel, dim3((unsigned)P), dim3((unsigned)((D + WAVE - 1) / WAVE * WAVE)), 0, h->stream,
                        v.s1.p, v.s2.p, g.ll_np, (int)D, s, h->enkf_sigma, h->enkf_loc, g.z_obs, g.dz, v.gain.p, st, sst,
-                       g.n_arow, g.slot, g.root ? v.rgain.p : nullptr, g.root ? v.dbar.p : nullptr, wst);
+                       g.n_arow, g.slot, g.root ? v.rgain.p : nullptr, g.root ? v.dbar.p : nullptr, wst, g.taper_x ? 1 : 0);
     HIP_TRY(hipGetLastError());
     if (g.root) {
         hipLaunchKernelGGL(enkf_sqrt_update_kernel<STATE>, dim3(g.blocks), dim3(256), 0, h->stream, x, h->enkf_Y.p,
@@ -6576,6 +6648,13 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
             h->enkf_z.ensure(P, D, Wx, Cx * Wx, root, true, h->enkf_nz_alpha > 0.0))
             return HC_ERR_DEVICE;
     }
+    if (h->enkf_fg) {
+        if (shard) return fail(HC_ERR_ARG, "the forcing analysis with a sharded analysis: the exchanged partials cover psi only");
+        if (h->enkf_part_sq.ensure((size_t)(P * n_tiles * D)) || h->fg_x.ensure((size_t)(2 * N)) ||
+            h->fg_rej.ensure((size_t)N) || h->fg_rejsum.ensure((size_t)P) ||
+            h->enkf_gv.ensure(P, 2, Wx, (2 + Wx) * Wx, root, true, h->enkf_fg_alpha > 0.0))
+            return HC_ERR_DEVICE;
+    }
     const unsigned short *w = h->wtd_u16.p + (size_t)(c.rows - 1) * N;
     const double dz = h->p.dz;
     const int special = (int)h->use_special();
@@ -6620,6 +6699,36 @@ int enkf_analyse(hc_handle *h, const Chunk &c, const EnkfRow &s)
                            h->enkf_nzt.buf.p, (long long)n_arow, (long long)slot);
         HIP_TRY(hipGetLastError());
         h->nz_done = true;
+    }
+    if (h->enkf_fg) {
+        // the members' forcing state g of the row's day, as the columns x [N][2] of a pass with D = 2 and no taper on C_gY;
+        // then, as for the noise field, the spread of what was left and the refused count for the table; the analysed
+        // streams go back into the carried buffer, which the next launch starts from
+        if (!h->fp_on || h->fp_day != row / HC_FORCING_DAY_ROWS || !h->fp_g.p)
+            return fail(HC_ERR_ARG, "the forcing analysis of row %lld: the members' forcing state stands at day %lld",
+                        (long long)row, (long long)h->fp_day);
+        EnkfPass gf = g;
+        gf.D = 2;
+        gf.C = 2 + W;
+        gf.cols_prior = dim3((unsigned)((gf.C + WAVE - 1) / WAVE * WAVE));
+        gf.taper_x = false;
+        EnkfVec &v = h->enkf_gv;
+        double *const x = h->fg_x.p;
+        const int act0 = h->fp_sigma[0] > 0.0 ? 1 : 0, act1 = h->fp_sigma[1] > 0.0 ? 1 : 0;
+        hipLaunchKernelGGL(enkf_forcing_gather_kernel, members, dim3(256), 0, h->stream, h->fp_g.p, (long long)N, x);
+        HIP_TRY(hipGetLastError());
+        if ((rc = enkf_vector<false>(gf, x, v, h->enkf_fg_alpha, true, nullptr, nullptr, nullptr, h->fg_rej.p))) return rc;
+        if ((rc = gf.spread(x, v))) return rc;
+        HIP_TRY(gf.partials(false, nullptr, h->fg_rej.p, 1, nullptr, 0, cols_post, gf.part, nullptr));
+        if ((rc = gf.reduce(gf.part, 1, h->fg_rejsum.p))) return rc;
+        hipLaunchKernelGGL(enkf_forcing_diag_kernel, dim3((unsigned)((2 * P + 63) / 64)), dim3(64), 0, h->stream, v.s1.p,
+                           v.sq_b.p, v.mean_a.p, v.sq_a.p, x, h->fg_rejsum.p, (long long)P, ll_np, W, act0, act1,
+                           h->enkf_fgt.buf.p, (long long)n_arow, (long long)slot);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(enkf_forcing_scatter_kernel, members, dim3(256), 0, h->stream, x, (long long)N, act0, act1,
+                           h->fp_g.p);
+        HIP_TRY(hipGetLastError());
+        h->fg_done = true;
     }
     if (s.ms > 0) {
         hipLaunchKernelGGL(enkf_theta_kernel, members, dim3(256), 0, h->stream, h->psi.p, h->Pdev.p, h->node_tabs.p, special,
@@ -6702,6 +6811,7 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
     const bool enkf_on = h->enkf_stride > 0 && !a->spinup;   // (the EnKF: spin-up solves are never analysed either)
     if ((filt_on && (rc = ensure_filter(h))) || (enkf_on && (rc = ensure_enkf(h)))) return rc;
     if (enkf_on && h->enkf_nz && (rc = ensure_nz(h))) return rc;
+    if (enkf_on && h->enkf_fg && (rc = ensure_fg(h))) return rc;
     const Assim da = assim(h);                               // whichever is on: its record's and its window's tables
     const bool da_on = filt_on || enkf_on;
     if (da_on && da.sm.n > 0 && (rc = da.ensure_sm(h))) return rc;
@@ -8514,6 +8624,9 @@ int hc_set_enkf_shard(hc_handle *h, int64_t n_global, int64_t first_global, void
     if (h->enkf_nz)
         return fail(HC_ERR_ARG, "hc_set_enkf_shard: the noise field is on (hc_set_enkf_noise_field), and the exchanged "
                                 "partials cover psi only");
+    if (h->enkf_fg)
+        return fail(HC_ERR_ARG, "hc_set_enkf_shard: the forcing analysis is on (hc_set_enkf_forcing), and the exchanged "
+                                "partials cover psi only");
     if (h->n_points > 1)
         return fail(HC_ERR_ARG, "hc_set_enkf_shard: the handle holds %d points (a shard is a part of one point's members)",
                     h->n_points);
@@ -8680,6 +8793,78 @@ int hc_get_enkf_noise_sqrt_gain(hc_handle *h, double *gain)
 int hc_get_enkf_noise_sqrt_shift(hc_handle *h, double *shift)
 {
     return vec_hook(h, true, &EnkfVec::dbar, shift, true, true, "hc_get_enkf_noise_sqrt_shift");
+}
+
+// ---- the members' forcing state in the analysis (include/hydrocol.h)
+int hc_set_enkf_forcing(hc_handle *h, int32_t on, double relaxation)
+{
+    if (!h || (on != 0 && on != 1)) return fail(HC_ERR_ARG, "hc_set_enkf_forcing: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (!on) {
+        fg_off(h);
+        return HC_OK;
+    }
+    if (h->enkf_stride <= 0) return fail(HC_ERR_ARG, "hc_set_enkf_forcing: the EnKF is off (hc_set_enkf comes first)");
+    if (!h->fp_on)
+        return fail(HC_ERR_ARG, "hc_set_enkf_forcing: the forcing is not perturbed (hc_set_forcing_perturbation comes first)");
+    if (h->shard_global > 0)
+        return fail(HC_ERR_ARG, "hc_set_enkf_forcing: the analysis is sharded (hc_set_enkf_shard), and the exchanged "
+                                "partials cover psi only");
+    if (!(std::isfinite(relaxation) && relaxation >= 0.0 && relaxation <= 1.0))
+        return fail(HC_ERR_ARG, "hc_set_enkf_forcing: relaxation = %g must be finite and in [0, 1]", relaxation);
+    h->enkf_fg = true;
+    h->enkf_fg_alpha = relaxation;
+    const int rc = ensure_fg(h);
+    if (rc != HC_OK) fg_off(h);                  // refused: off
+    return rc;
+}
+
+int hc_get_enkf_forcing(hc_handle *h, int32_t *on, double *relaxation)
+{
+    if (!h || !on || !relaxation) return fail(HC_ERR_ARG, "hc_get_enkf_forcing: bad argument");
+    *on = h->enkf_fg ? 1 : 0;
+    *relaxation = h->enkf_fg ? h->enkf_fg_alpha : 0.0;
+    return HC_OK;
+}
+
+int hc_get_enkf_g_table(hc_handle *h, double *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_get_enkf_g_table: bad argument");
+    return table_copy(h, h->enkf_fgt, ensure_fg, hipMemcpyDeviceToHost, table, n_entries, "hc_get_enkf_g_table");
+}
+
+int hc_set_enkf_g_table(hc_handle *h, const double *table, int64_t n_entries)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_set_enkf_g_table: bad argument");
+    return table_copy(h, h->enkf_fgt, ensure_fg, hipMemcpyHostToDevice, const_cast<double *>(table), n_entries,
+                      "hc_set_enkf_g_table");
+}
+
+// the last analysis's gain for g as on the device [P][m'][2], the square-root run's reduced gain and its shift [P][2]
+static int forcing_hook(hc_handle *h, DevBuf<double> EnkfVec::*src, double *out, bool root, bool shift, const char *who)
+{
+    if (!h || !out) return fail(HC_ERR_ARG, "%s: bad argument", who);
+    if (!(h->enkf_stride > 0 && h->enkf_done && h->enkf_fg && h->fg_done))
+        return fail(HC_ERR_ARG, "%s: no analysis since hc_set_enkf_forcing", who);
+    if (int rc = enkf_last(h, who, false, root)) return rc;
+    const size_t n = (size_t)h->n_points * 2 * (shift ? 1 : (size_t)h->enkf_width);
+    return enkf_hook(h, (h->enkf_gv.*src).p, out, 1, n, n, who);
+}
+
+int hc_get_enkf_g_gain(hc_handle *h, double *gain)
+{
+    return forcing_hook(h, &EnkfVec::gain, gain, false, false, "hc_get_enkf_g_gain");
+}
+
+int hc_get_enkf_g_sqrt_gain(hc_handle *h, double *gain)
+{
+    return forcing_hook(h, &EnkfVec::rgain, gain, true, false, "hc_get_enkf_g_sqrt_gain");
+}
+
+int hc_get_enkf_g_sqrt_shift(hc_handle *h, double *shift)
+{
+    return forcing_hook(h, &EnkfVec::dbar, shift, true, true, "hc_get_enkf_g_sqrt_shift");
 }
 
 int hc_get_enkf_noise_base(hc_handle *h, double *base, int64_t first, int64_t count)

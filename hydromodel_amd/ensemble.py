@@ -11,8 +11,8 @@ import numpy as np
 from . import settings
 from .digest import inverse_retention
 from .stepper import DIAG_TABLES, diag_checkpoint, diag_from_checkpoint
-from .stepper import (ASSIM_TABLES, EnsembleStepper, enkf_noise_summary, enkf_sm_summary, enkf_summary, enkf_window_summary,
-                      filter_sm_summary, filter_smoother_summary, filter_summary, filter_window_summary, layer_ranges,
+from .stepper import (ASSIM_TABLES, EnsembleStepper, enkf_forcing_summary, enkf_noise_summary, enkf_sm_summary, enkf_summary,
+                      enkf_window_summary, filter_sm_summary, filter_smoother_summary, filter_summary, filter_window_summary, layer_ranges,
                       layer_storage_distribution, moments_to_mean_std, period_totals_distribution, root_uptake_distribution,
                       root_uptake_profile, root_uptake_stats, theta_cov_finish, theta_distribution, theta_sensor_gain,
                       wtd_distribution)
@@ -160,7 +160,11 @@ class _Run:
     member sees the record's rainfall and atmospheric demand times a log-normal factor of mean one of its own, constant
     over a day and an AR(1) from day to day (include/hydrocol.h hc_set_forcing_perturbation); at least one sigma, in
     [0, 1]; correlation_days in [0, 365], default 0; seed default: the ensemble's.  Set after the spin-up, before the
-    filters; the particle filter moves the members' state with them; ``dump`` / ``restore`` carry it.
+    filters; the particle filter moves the members' state with them; ``dump`` / ``restore`` carry it.  With the further
+    key ``"enkf_relaxation": a`` (a in [0, 1]; absent or None: off) every EnKF analysis also updates the members' forcing
+    state from the same observations, draws and factor (include/hydrocol.h hc_set_enkf_forcing), relaxed to prior spread
+    with ``a``; it needs enkf_stride > 0 and no enkf_shard; :meth:`enkf_forcing_table`, the ``forcing_*`` keys of
+    :meth:`enkf_summary`.
     noise_correlation: {"length_cm": l, "layers": bool} or None: the Philox source's base and refresh vectors become
     exponentially correlated fields of unit variance down the column (include/hydrocol.h hc_set_noise_correlation),
     with ``layers`` independent across the interfaces of ``cols.layers`` inside the column; applied after the spin-up
@@ -430,7 +434,17 @@ class _Run:
         """[n_arow][8] float64 (include/hydrocol.h hc_set_enkf; depths from the top node); a sweep: [P][n_arow][8]."""
         return self.assim_table("enkf")
 
-    def enkf_summary(self, table=None, sm_table=None, window_table=None, noise_table=None):
+    def enkf_forcing_table(self):
+        """[n_arow][9] float64 (include/hydrocol.h hc_set_enkf_forcing); a sweep: [P][n_arow][9]."""
+        t = self.stepper.enkf_forcing_table()
+        return t.reshape(self._lead + t.shape[1:])
+
+    def enkf_forcing_summary(self, table=None):
+        """stepper.enkf_forcing_summary of the forcing analysis's table (``table``: e.g. the one assembled over ranks)."""
+        t = self.enkf_forcing_table() if table is None else table
+        return enkf_forcing_summary(t, self.enkf_stride, self.forcing_perturbation["enkf_relaxation"])
+
+    def enkf_summary(self, table=None, sm_table=None, window_table=None, noise_table=None, forcing_table=None):
         """The EnKF's record (stepper.enkf_summary, means at the well's depths): ``rows``, ``count``, ``prior_mean_cm``,
         ``prior_std_cm``, ``innovation_cm``, ``loglik_rows``, ``post_mean_cm``, ``post_std_cm``, ``rejected`` over the
         analysed rows and ``loglik``, the log marginal likelihood of the well record (log cm^-1), with a leading [P] for a
@@ -445,6 +459,8 @@ class _Run:
             out.update(("window_" + k, v) for k, v in self.enkf_window_summary(window_table).items())
         if self.enkf_noise_relaxation is not None:      # the noise_* keys (include/hydrocol.h hc_set_enkf_noise_field)
             out.update((k, v) for k, v in self.enkf_noise_summary(noise_table).items() if k.startswith("noise_"))
+        if self.on["forcing_enkf"]:                     # the forcing_* keys (include/hydrocol.h hc_set_enkf_forcing)
+            out.update((k, v) for k, v in self.enkf_forcing_summary(forcing_table).items() if k.startswith("forcing_"))
         return out
 
     def enkf_window_table(self):

@@ -82,6 +82,13 @@ def normalise(who, options, points, seed, lead=(), noise="philox", member_offset
     cols, s = points[0], SimpleNamespace()
     corr = noise_correlation_settings(o.noise_correlation)
     pert = forcing_perturbation_settings(o.forcing_perturbation)
+    # the forcing state in the EnKF's analysis is a key of the perturbation's value: its two refusals are raised here, where
+    # the value is read
+    forcing_enkf = pert is not None and "enkf_relaxation" in pert
+    if forcing_enkf and not int(o.enkf_stride or 0):
+        raise ValueError("forcing_perturbation.enkf_relaxation needs the EnKF (enkf_stride > 0)")
+    if forcing_enkf and enkf_shard is not None:
+        raise ValueError("enkf_shard and the forcing analysis exclude each other: the exchanged partials cover psi only")
     s.profile_stride, s.wtd_hist_stride = int(o.profile_stride), int(o.wtd_hist_stride)
     s.theta_cov_stride, s.theta_hist_bins = int(o.theta_cov_stride or 0), int(o.theta_hist_bins or 0)
     s.storage_layers_cm = np.asarray(o.storage_layers_cm, dtype=np.float64).reshape(-1, 2) if _some(o.storage_layers_cm) else None
@@ -117,8 +124,8 @@ def normalise(who, options, points, seed, lead=(), noise="philox", member_offset
               period_thresholds_cm=_some(o.period_thresholds_cm), enkf_method=s.enkf_method != "stochastic",
               enkf_relaxation=s.enkf_relaxation != 0.0, enkf_scheme=(s.enkf_method, s.enkf_relaxation) != ("stochastic", 0.0),
               enkf_noise_field=s.enkf_noise_relaxation is not None, noise_correlation=corr is not None,
-              forcing_perturbation=pert is not None, noise_numpy=noise == "numpy", enkf_shard=enkf_shard is not None,
-              filter_shard=filter_shard is not None, always=True)
+              forcing_perturbation=pert is not None, forcing_enkf=forcing_enkf, noise_numpy=noise == "numpy",
+              enkf_shard=enkf_shard is not None, filter_shard=filter_shard is not None, always=True)
     for option, relation, other, message in REFUSALS:
         if on[option] and on[other] == (relation == "excludes"):
             raise ValueError(message.format(who=who))
@@ -180,6 +187,7 @@ START = (
     ("enkf_window_offsets", lambda st, s: st.set_enkf_window(s.enkf_window_offsets)),
     # (after any spin-up: a Philox run then takes the caller-noise path)
     ("enkf_noise_field", lambda st, s: st.set_enkf_noise_field(True, s.enkf_noise_relaxation)),
+    ("forcing_enkf", lambda st, s: st.set_enkf_forcing(True, s.forcing_perturbation["enkf_relaxation"])),
     ("period_ends", lambda st, s: st.set_period_totals(s.period_ends, s.period_threshold_nodes, s.period_bins,
                                                        s._period_flux_log2)),
     ("uptake_layers_cm", lambda st, s: st.set_root_uptake(s.uptake_cells, s.uptake_bins)),
@@ -289,6 +297,7 @@ SETTING_DATASETS = (
     ("forcing_perturbation", "forcing_demand_sigma", _F64, "forcing_perturbation.demand_sigma"),
     ("forcing_perturbation", "forcing_correlation_days", _F64, "forcing_perturbation.correlation_days"),
     ("forcing_perturbation", "forcing_seed", _U64, "forcing_perturbation.seed"),
+    ("forcing_enkf", "forcing_enkf_relaxation", _F64, "forcing_perturbation.enkf_relaxation"),
 )
 
 
@@ -346,6 +355,14 @@ def _set_forcing_state(sim, data, path):
     sim.stepper.set_forcing_state(_array(np.float64, 2, -1)(data["forcing_state"]), day)
 
 
+def _forcing_enkf_table(s, st):
+    return {"enkf_forcing_table": st.enkf_forcing_table()}
+
+
+def _set_forcing_enkf_table(sim, data, path):
+    sim.stepper.set_enkf_forcing_table(np.asarray(data["enkf_forcing_table"], dtype=np.float64))
+
+
 def _check_correlation(sim, data, path):
     if not (np.array_equal(np.asarray(data["noise_correlation_a"]).reshape(-1), sim.noise_correlation_a)
             and np.array_equal(np.asarray(data["noise_correlation_b"]).reshape(-1), sim.noise_correlation_b)):
@@ -390,6 +407,7 @@ def _set_smoother(sim, data, path):
 # before the members' state and the filters' tables, the members' after them
 RUN_STATE = (
     ("forcing_perturbation", _forcing_state, _set_forcing_state),
+    ("forcing_enkf", _forcing_enkf_table, _set_forcing_enkf_table),      # (no entry of the stepper's registry: its own row)
     ("noise_correlation", None, _check_correlation),
 )
 MEMBER_STATE = (

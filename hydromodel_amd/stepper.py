@@ -94,6 +94,7 @@ class EnsembleStepper:
         self.enkf_method, self.enkf_relaxation = "stochastic", 0.0
         self.enkf_window_offsets = ()
         self.enkf_noise_field, self.enkf_noise_relaxation = False, 0.0
+        self.enkf_forcing, self.enkf_forcing_relaxation = False, 0.0
         self.noise_corr = None
         self.philox = False
         self.device = int(device)
@@ -213,6 +214,7 @@ class EnsembleStepper:
         ``None`` as the first argument turns it off.  Set it after the spin-up and before a filter.  The members are
         keyed by the global ids of their noise streams; ``member_offset`` gives the first member's id where there is no
         such stream (a shard of a host-noise ensemble: otherwise its ids start at 0)."""
+        self.enkf_forcing, self.enkf_forcing_relaxation = False, 0.0     # (the library turns the EnKF's part off with it)
         if precipitation_sigma is None:
             L.check(self.lib.hc_clear_forcing_perturbation(self.h))
             return
@@ -258,7 +260,8 @@ class EnsembleStepper:
 
     def forcing_factors(self, first_member, count, first_day, n_days):
         """[n_days][2][count] the factors of the handle's slots first_member ... by the stateless recursion from day 0, on
-        the device code that fills them for the step kernel (valid for slots no resampling has touched)."""
+        the device code that fills them for the step kernel (valid for slots that neither a resampling nor an analysis
+        of :meth:`set_enkf_forcing` has touched)."""
         out = np.empty((int(n_days), 2, int(count)))
         L.check(self.lib.hc_forcing_factors(self.h, int(first_member), int(count), int(first_day), int(n_days), L.dptr(out)))
         return out
@@ -809,6 +812,7 @@ class EnsembleStepper:
         self.enkf_window_offsets = ()
         self.enkf_shard = None
         self.enkf_noise_field, self.enkf_noise_relaxation = False, 0.0
+        self.enkf_forcing, self.enkf_forcing_relaxation = False, 0.0
         self.filter_shard, self._filter_shard_keep = None, None
         self.noise_corr = None                                                   # ... and the noise correlation
 
@@ -1210,6 +1214,7 @@ class EnsembleStepper:
         self.enkf_window_offsets = ()                         # ... and turns the window off
         self.enkf_shard = None                                # ... and the sharding
         self.enkf_noise_field, self.enkf_noise_relaxation = False, 0.0   # ... and the noise field
+        self.enkf_forcing, self.enkf_forcing_relaxation = False, 0.0     # ... and the forcing state's analysis
         L.check(self.lib.hc_set_enkf(self.h, stride, sigma, loc, int(seed) & 0xFFFFFFFFFFFFFFFF))
         self.enkf_stride, self.enkf_sigma_cm, self.enkf_localisation_cm, self.enkf_seed = stride, sigma, loc, int(seed)
 
@@ -1348,6 +1353,58 @@ class EnsembleStepper:
         if base.shape != (self.N, self.D):
             raise ValueError(f"base must be [{self.N}][{self.D}], got {base.shape}")
         L.check(self.lib.hc_set_enkf_noise_base(self.h, L.dptr(base)))
+
+    # -- the members' forcing state in the EnKF analysis (include/hydrocol.h hc_set_enkf_forcing) ------------------------
+    def set_enkf_forcing(self, on=True, relaxation=0.0):
+        """Update every member's forcing state g -- the AR(1) behind its rainfall and demand factors
+        (:meth:`set_forcing_perturbation`) -- together with its psi on every analysis row, from the same observations,
+        draws and factor, without a taper on C_gY; ``relaxation``: the RTPS factor of g's anomalies in [0, 1] (g regains
+        spread from its recursion, so 0 is a sound default).  The EnKF and the perturbation must be on, the analysis not
+        sharded.  The analysed g is what the rest of the day and, through the recursion, every later day run with."""
+        on = bool(on)
+        alpha = forcing_enkf_relaxation(relaxation) if on else 0.0
+        if on and not self.enkf_stride:
+            raise ValueError("the forcing analysis needs the EnKF on (set_enkf first)")
+        if on and self.enkf_shard is not None:
+            raise ValueError("the forcing analysis with a sharded analysis: the exchanged partials cover psi only")
+        L.check(self.lib.hc_set_enkf_forcing(self.h, int(on), alpha))
+        self.enkf_forcing, self.enkf_forcing_relaxation = on, alpha
+
+    def get_enkf_forcing(self):
+        """(on, relaxation) as the library holds them."""
+        m, a = np.zeros(1, dtype=np.int32), np.zeros(1)
+        L.check(self.lib.hc_get_enkf_forcing(self.h, L.iptr(m), L.dptr(a)))
+        return bool(m[0]), float(a[0])
+
+    def enkf_forcing_table(self):
+        """[P][n_arow][9] float64 per analysis slot: for stream s (0 precipitation, 1 demand) columns 4 s + (prior mean,
+        prior std, mean and std after the relaxation) of g, then the members whose updated g was refused; NaN where
+        nothing was analysed (:func:`split_enkf_forcing_table`)."""
+        t = np.zeros((self.P, stride_rows(self.T, self.enkf_stride), ENKF_FORCING_WIDTH))
+        L.check(self.lib.hc_get_enkf_g_table(self.h, L.dptr(t), t.size))
+        return t
+
+    def set_enkf_forcing_table(self, table):
+        t = L.as_f64(table).reshape(-1)
+        L.check(self.lib.hc_set_enkf_g_table(self.h, L.dptr(t), t.size))
+
+    def enkf_forcing_gain(self):
+        """[P][m'][2] the gain K^g of the last analysis (test hook)."""
+        out = np.zeros((self.P, self.enkf_width(), 2))
+        L.check(self.lib.hc_get_enkf_g_gain(self.h, L.dptr(out)))
+        return out
+
+    def enkf_forcing_sqrt_gain(self):
+        """[P][m'][2] g's reduced gain of the last analysis, a square-root one (test hook)."""
+        out = np.zeros((self.P, self.enkf_width(), 2))
+        L.check(self.lib.hc_get_enkf_g_sqrt_gain(self.h, L.dptr(out)))
+        return out
+
+    def enkf_forcing_sqrt_shift(self):
+        """[P][2] the shift of g's mean in the last analysis, a square-root one (test hook)."""
+        out = np.zeros((self.P, 2))
+        L.check(self.lib.hc_get_enkf_g_sqrt_shift(self.h, L.dptr(out)))
+        return out
 
     # -- soil-moisture sensors in the EnKF analysis (include/hydrocol.h hc_set_enkf_soil_moisture) ----------------------
     def set_enkf_soil_moisture(self, nodes, values=None, sigma=None):
@@ -2858,9 +2915,10 @@ def split_enkf_noise_table(table, D):
     return t[..., :4 * D].reshape(t.shape[:-1] + (4, D)), t[..., 4 * D]
 
 
-def _enkf_gains_of(x, Y, obs, sigma, zeta, dz, loc, want_sqrt):
+def _enkf_gains_of(x, Y, obs, sigma, zeta, dz, loc, want_sqrt, taper_x=True):
     """One point: K [D][m'] = (rho o C_xY)(rho o C_YY + R)^-1 of the columns x [N][D] against Y [N][m'], and for the
-    square-root scheme the reduced gain and the mean's shift."""
+    square-root scheme the reduced gain and the mean's shift.  ``taper_x`` False: rho on C_xY is all ones (columns
+    without a depth, :func:`enkf_forcing_analysis_of`); S keeps its taper."""
     N, D = x.shape
     W = Y.shape[1]
     yb = Y.mean(axis=0)
@@ -2872,7 +2930,7 @@ def _enkf_gains_of(x, Y, obs, sigma, zeta, dz, loc, want_sqrt):
     depth = np.arange(D) * float(dz)
     if loc > 0:
         rho_yy = gaspari_cohn(np.abs(zt[:, None] - zt[None, :]) / loc)
-        rho_xy = gaspari_cohn(np.abs(depth[:, None] - zt[None, :]) / loc)
+        rho_xy = gaspari_cohn(np.abs(depth[:, None] - zt[None, :]) / loc) if taper_x else np.ones((D, W))
     else:
         rho_yy, rho_xy = np.ones((W, W)), np.ones((D, W))
     R = np.asarray(sigma, dtype=np.float64) ** 2
@@ -3055,12 +3113,14 @@ def forcing_factors_of(g, sigma):
 def forcing_perturbation_settings(value):
     """The ``forcing_perturbation=`` argument of EnsembleSimulation / SweepSimulation: ``None`` or
     ``{"precipitation_sigma": .., "demand_sigma": .., "correlation_days": .., "seed": ..}`` -> ``None`` or the dict
-    with every key present (seed ``None``: the ensemble's)."""
+    with every key present (seed ``None``: the ensemble's).  ``"enkf_relaxation": a`` has the EnKF analyse the members'
+    forcing state with relaxation ``a`` (:meth:`EnsembleStepper.set_enkf_forcing`); the key comes back only when it is
+    given and not ``None``."""
     if value is None:
         return None
     if not isinstance(value, dict):
         raise ValueError(f"forcing_perturbation = {value!r} must be a dict")
-    known = {"precipitation_sigma", "demand_sigma", "correlation_days", "seed"}
+    known = {"precipitation_sigma", "demand_sigma", "correlation_days", "seed", "enkf_relaxation"}
     if set(value) - known:
         raise ValueError(f"forcing_perturbation: unknown key(s) {sorted(set(value) - known)}; known: {sorted(known)}")
     if "precipitation_sigma" not in value and "demand_sigma" not in value:
@@ -3081,7 +3141,124 @@ def forcing_perturbation_settings(value):
     if seed is not None and (isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or seed < 0):
         raise ValueError(f"forcing_perturbation: seed = {seed!r} must be an integer >= 0")
     out["seed"] = None if seed is None else int(seed)
+    if value.get("enkf_relaxation") is not None:
+        out["enkf_relaxation"] = forcing_enkf_relaxation(value["enkf_relaxation"])
     return out
+
+
+# ---- the members' forcing state in the EnKF (include/hydrocol.h hc_set_enkf_forcing) --------------------------------------
+ENKF_FORCING_WIDTH = 9
+FORCING_STREAMS = ("precipitation", "demand")
+
+
+def forcing_enkf_relaxation(value):
+    """The relaxation of the forcing state's anomalies: a finite number in [0, 1], not a bool."""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise ValueError(f"the forcing analysis's relaxation = {value!r} must be a number in [0, 1]")
+    a = float(value)
+    if not (np.isfinite(a) and 0.0 <= a <= 1.0):
+        raise ValueError(f"the forcing analysis's relaxation = {value!r} must be a finite number in [0, 1]")
+    return a
+
+
+def forcing_enkf_settings(value, block_relaxation=0.0):
+    """The ``EnKF`` key of a ``Forcing_Perturbation`` block: None or False -> None (off); True -> the EnKF block's
+    relaxation; {"Relaxation": a} -> a.  Anything else is a ValueError."""
+    if value is None or value is False:
+        return None
+    if value is True:
+        return forcing_enkf_relaxation(block_relaxation)
+    if isinstance(value, dict) and set(value) - {"Relaxation"}:
+        raise ValueError(f"Forcing_Perturbation.EnKF has unknown keys {sorted(set(value) - {'Relaxation'}, key=str)} "
+                         f"(known: ['Relaxation'])")
+    if isinstance(value, dict) and value:
+        return forcing_enkf_relaxation(value["Relaxation"])
+    raise ValueError(f"Forcing_Perturbation.EnKF = {value!r} must be true, false or {{\"Relaxation\": a}}")
+
+
+def split_enkf_forcing_table(table):
+    """[..., n_arow, 9] -> (stats [..., n_arow, 4, 2]: prior mean, prior std, posterior mean, posterior std of the two
+    streams' g; rejected [..., n_arow])."""
+    t = np.asarray(table, dtype=np.float64)
+    return np.swapaxes(t[..., :8].reshape(t.shape[:-1] + (2, 4)), -1, -2), t[..., 8]
+
+
+def enkf_forcing_analysis_of(psi_f, g_f, Y, obs, sigma, eps=None, active=(True, True), zeta=(), dz=1.0, localisation_cm=0.0,
+                             method="stochastic", relaxation=0.0):
+    """The forcing state's analysis for ONE point in float64 NumPy (include/hydrocol.h hc_set_enkf_forcing): from the
+    forecast states ``psi_f`` [N][D], forcing states ``g_f`` [N][2] (precipitation, demand), observations of the members
+    ``Y`` [N][m'] (the well's y first), the observed values ``obs`` and their errors ``sigma`` [m'], and for the stochastic
+    scheme the draws ``eps`` [N][m']; ``zeta`` [m' - 1]: the taper centres of the columns beyond the well's (they shape S
+    alone: C_gY is not tapered); ``active`` [2]: whether the stream is analysed (sigma_s > 0).
+
+    K^g = C_gY (rho o C_YY + R)^-1; g + (obs + sigma eps - Y) K^g^T, or with "sqrt" g + shift + (Ybar - Y) Kr^T.  A member
+    whose psi analysis has a non-finite entry keeps its g; one whose updated (g_0, g_1) has a non-finite entry keeps its
+    old g and is ``rejected``.  Then the anomalies are relaxed by the noise field's rules
+    (:func:`enkf_noise_analysis_of`).  A stream that is not active goes through the same arithmetic and is then put
+    back: its g keeps every bit and its posterior statistics repeat the prior's.
+
+    Returns ``K`` [m'][2] (and ``Kr``, ``shift`` with "sqrt"), ``g`` [N][2], ``rejected`` and ``psi_rejected`` [N] bool,
+    ``sigma_b``, ``sigma_a``, ``factor`` [2], and ``stats`` [4][2]: prior mean and std, posterior (relaxed) mean and
+    std."""
+    if method not in ENKF_METHODS:
+        raise ValueError(f"EnKF method = {method!r} must be one of {list(ENKF_METHODS)}")
+    psi_f, g_f, Y = (np.asarray(a, dtype=np.float64) for a in (psi_f, g_f, Y))
+    obs, sigma = np.asarray(obs, dtype=np.float64).reshape(-1), np.asarray(sigma, dtype=np.float64).reshape(-1)
+    alpha = forcing_enkf_relaxation(relaxation)
+    act = np.asarray(active, dtype=bool).reshape(2)
+    N = g_f.shape[0]
+    if g_f.shape != (N, 2):
+        raise ValueError(f"g_f must be [N][2], got {g_f.shape}")
+    root = method == "sqrt"
+    with np.errstate(all="ignore"):
+        def increments(x, taper_x):
+            K, Kr, shift, yb = _enkf_gains_of(x, Y, obs, sigma, zeta, dz, float(localisation_cm), root, taper_x)
+            if root:
+                return K, Kr, shift, shift[None, :] + (yb[None, :] - Y) @ Kr.T
+            return K, None, None, ((obs[None, :] + sigma[None, :] * np.asarray(eps, dtype=np.float64)) - Y) @ K.T
+        psi_rej = ~np.isfinite(psi_f + increments(psi_f, True)[3]).all(axis=1)
+        K, Kr, shift, inc = increments(g_f, False)
+        cand = g_f + inc
+        rej = ~np.isfinite(cand).all(axis=1) & ~psi_rej
+        g = np.where((rej | psi_rej)[:, None], g_f, cand)
+        std = (lambda a: a.std(axis=0, ddof=1)) if N > 1 else (lambda a: np.zeros(2))
+        sb, sa = std(g_f), std(g)
+        f = np.ones(2)
+        if alpha > 0.0:
+            good = (sa > 0) & np.isfinite(sa) & np.isfinite(K[0, 0])
+            f = np.where(good, 1.0 + alpha * (sb - sa) / np.where(good, sa, 1.0), 1.0)
+            mean = g.mean(axis=0)
+            relaxed = np.where(f[None, :] == 1.0, g, mean[None, :] + f[None, :] * (g - mean[None, :]))
+            keep = np.isfinite(relaxed).all(axis=1) & ~psi_rej & ~rej
+            g = np.where(keep[:, None], relaxed, g)
+        g = np.where(act[None, :], g, g_f)
+        stats = np.stack([g_f.mean(axis=0), sb, g.mean(axis=0), std(g)])
+        stats[2:] = np.where(act[None, :], stats[2:], stats[:2])
+    out = {"K": K.T.copy(), "g": g, "rejected": rej, "psi_rejected": psi_rej, "sigma_b": sb, "sigma_a": sa, "factor": f,
+           "stats": stats}
+    if root:
+        out["Kr"], out["shift"] = Kr.T.copy(), shift
+    return out
+
+
+def enkf_forcing_summary(table, stride, relaxation):
+    """The forcing analysis's record from its [..., n_arow, 9] table, over the slots any point analysed: ``rows`` [R],
+    ``forcing_prior_mean``, ``forcing_prior_std``, ``forcing_post_mean``, ``forcing_post_std`` [..., R, 2] (precipitation,
+    demand), ``forcing_rejected`` [..., R], ``forcing_spread_ratio`` [2] = per stream the mean over rows (and points) of
+    sigma_post / sigma_prior (entries with sigma_prior = 0 left out; NaN with none), ``forcing_relaxation``."""
+    t = np.asarray(table, dtype=np.float64)
+    stats, rej = split_enkf_forcing_table(t)
+    used = np.isfinite(rej).reshape(-1, t.shape[-2]).any(axis=0) if t.size else np.zeros(t.shape[-2], bool)
+    slots = np.flatnonzero(used)
+    sel = stats[..., slots, :, :]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = sel[..., 3, :] / sel[..., 1, :]
+    ok = np.isfinite(ratio) & (sel[..., 1, :] > 0)
+    spread = np.array([float(ratio[..., s][ok[..., s]].mean()) if ok[..., s].any() else float("nan") for s in range(2)])
+    return {"rows": slots.astype(np.int64) * int(stride), "forcing_prior_mean": sel[..., 0, :],
+            "forcing_prior_std": sel[..., 1, :], "forcing_post_mean": sel[..., 2, :], "forcing_post_std": sel[..., 3, :],
+            "forcing_rejected": np.nan_to_num(rej[..., slots]).astype(np.int64), "forcing_spread_ratio": spread,
+            "forcing_relaxation": float(relaxation)}
 
 
 def noise_correlation_breaks(layers, z):

@@ -82,6 +82,9 @@
  *                         (src/simulation.py:561,592; replaced for one row only on refresh rows, :599-601), is what
  *                         vrettas_fung.py:154-190 turns into K_bkg: a member's conductivity field.  The EnKF's analysis
  *                         updates it together with the member's psi (state augmentation)
+ *   hc_set/get_enkf_forcing, hc_get/set_enkf_g_table, hc_get_enkf_g_gain, hc_get_enkf_g_sqrt_gain/shift
+ *                      <- (new) the members' forcing-error state g (hc_set_forcing_perturbation) in the EnKF's analysis:
+ *                         joint state and forcing-error estimation by state augmentation
  *   hc_set_enkf_window, hc_get/set_enkf_window_stats, hc_get/set_enkf_window_capture, hc_get_enkf_width,
  *   hc_get_enkf_window_width/y/eps/gain
  *                      <- (new) the well's record at rows inside the analysis window joins the analysis (asynchronous EnKF)
@@ -270,11 +273,13 @@ int hc_set_noise_field_base(hc_handle *h, const double *base);
  *   a launch that starts inside that day reuses its g, so nothing depends on where launch boundaries fall.  Rows must
  *   not go back behind the day the state stands at (HC_ERR_ARG; hc_set_forcing_state or a new
  *   hc_set_forcing_perturbation rewinds).  After a particle filter's resampling g travels with the member (a latent state
- *   of its trajectory; the refresh draws stay with the slot); the EnKF leaves g alone.  While it is on, the step kernel
+ *   of its trajectory; the refresh draws stay with the slot); the EnKF leaves g alone unless hc_set_enkf_forcing has it
+ *   analysed with the member's state (below: the analysed g is what the rest of the day and, through the recursion, every
+ *   later day integrate with).  While it is on, the step kernel
  *   is the build that carries the predictive lateral-flow branch (a monitoring-mode point keeps its semantics through
  *   flag_predict, as in a mixed sweep); with nothing set nothing is launched or allocated and the build is the one it was.
- *   Not modelled: g in the EnKF analysis, a per-member refresh rule, additive or gamma errors, correlation between the
- *   two streams, the sharded particle filter (refused).
+ *   Not modelled: g in a sharded EnKF analysis (refused) or in a smoother, a per-member refresh rule, additive or gamma
+ *   errors, correlation between the two streams, the sharded particle filter (refused).
  * hc_set_forcing_perturbation: needs the column, forcing, members and state in place.  HC_ERR_ARG for a non-finite value,
  *   sigma outside [0, 1], phi outside [0, 1), c <= 0, |phi^2 + c^2 - 1| > 1e-12, or a sharded particle filter.  Both sigma = 0
  *   is allowed: the factors are 1.0 and the wider build runs.  The state starts empty (day -1).  Turned off by
@@ -287,7 +292,7 @@ int hc_set_noise_field_base(hc_handle *h, const double *base);
  * hc_forcing_normals: the raw xi of the stream key `member` (a global id), out[n_days][2] (test hook).
  * hc_forcing_factors: f of the handle's slots first_member ... + count over the days first_day ... + n_days by the
  *   stateless recursion from day 0 on the same device code, out[n_days][2][count]; what the step kernel applies to slots
- *   no resampling has touched. */
+ *   that neither a resampling nor an analysis (hc_set_enkf_forcing) has touched. */
 #define HC_FORCING_WORD_PRECIP 0xFFFFFFE0u
 #define HC_FORCING_WORD_DEMAND 0xFFFFFFE1u
 #define HC_FORCING_DAY_ROWS 48
@@ -1195,6 +1200,44 @@ int hc_get_enkf_noise_sqrt_gain(hc_handle *h, double *gain);
 int hc_get_enkf_noise_sqrt_shift(hc_handle *h, double *shift);
 int hc_get_enkf_noise_base(hc_handle *h, double *base, int64_t first_member, int64_t count);
 int hc_set_enkf_noise_base(hc_handle *h, const double *base);
+
+/* The members' forcing state in the analysis (joint state and forcing-error estimation by state augmentation).  With
+ * hc_set_forcing_perturbation every member carries g_{m,s} (s = 0 precipitation, 1 demand), an AR(1) over days whose
+ * log-normal scales its record.  With on = 1 every analysis row r updates g of the day k = r / 48 the row lies in, after
+ * psi (and after the noise field's vectors), from the same forecast Y [N][m'], observation errors, draws and factor:
+ *     gbar_s, c_s,i = sum_k (g_ks - gbar_s)(Y_ki - Ybar_i)           (the tile rule of hc_set_enkf over (g, Y))
+ *     K^g_s = (c_s / (N_p - 1)) S^-1                                  (NO taper on C_gY: g has no depth; S = rho o C_YY + R
+ *                                                                      and its factor are the state's to the bit)
+ *     g_ks <- g_ks + sum_i K^g_s,i delta_ki, i in order               (delta: the member's innovations of its psi update;
+ *                                                                      square root: the reduced gain, Ybar_i - Y_ki, and
+ *                                                                      the shift sum_i K^g_s,i (o_i - Ybar_i))
+ *   A member whose psi analysis was rejected keeps its g to the bit; a member whose updated (g_0, g_1) would hold a
+ *   non-finite entry keeps its old g and is counted as refused.  A stream with sigma_s = 0 is not written: its g keeps
+ *   every bit (its factor is 1.0 regardless) and its table columns repeat the prior.  Then the anomalies are relaxed to
+ *   prior spread with `relaxation`, by the noise field's rules.  Unlike the noise field g regains spread from its own
+ *   recursion, so relaxation = 0 is a sound choice.  The analysed g is written into the carried state: the next launch
+ *   starts inside day k from it, and g_{k+1} = (phi g_k) + (c xi_{k+1}) carries the update to every later day.  With a
+ *   stride that is a multiple of 48 the analysis row is the first row of its day, so the covariance of g_k with y comes
+ *   through phi from the day before (phi = 0: from that one row alone).  The work is done by the analysis's own kernels on
+ *   the member-major copy x [N][2] of g (a pass with D = 2): sums over tiles of 256 members reduced in the fixed order, so
+ *   the analysed g has the same bits at any launch length and point order.  No step kernel is involved; with on = 0
+ *   nothing is launched or allocated.
+ *   Table (hc_get/set_enkf_g_table), float64 [P][n_arow][9], NaN until the row is analysed: per stream s columns
+ *   4 s + (prior mean, prior std, mean and std after the relaxation), then in column 8 the refused members.
+ * hc_set_enkf_forcing: needs hc_set_enkf and hc_set_forcing_perturbation first; HC_ERR_ARG for on outside {0, 1}, a
+ *   relaxation outside [0, 1] or not finite, the EnKF off, the perturbation off, or a sharded analysis (hc_set_enkf_shard
+ *   refuses it in turn: the exchanged partials cover psi only).  Turned off by whatever turns the EnKF or the perturbation
+ *   off or sets either again.  hc_get_enkf_forcing: (0, 0) while it is off.
+ * Test hooks of the last analysis: hc_get_enkf_g_gain (K^g [P][m'][2]), hc_get_enkf_g_sqrt_gain (the reduced
+ *   gain, [P][m'][2]) and hc_get_enkf_g_sqrt_shift [P][2], the latter two HC_ERR_ARG unless it was a square-root
+ *   analysis, all three unless an analysis has run since hc_set_enkf_forcing.  g itself: hc_get_forcing_state. */
+int hc_set_enkf_forcing(hc_handle *h, int32_t on, double relaxation);
+int hc_get_enkf_forcing(hc_handle *h, int32_t *on, double *relaxation);
+int hc_get_enkf_g_table(hc_handle *h, double *table, int64_t n_entries);
+int hc_set_enkf_g_table(hc_handle *h, const double *table, int64_t n_entries);
+int hc_get_enkf_g_gain(hc_handle *h, double *gain);
+int hc_get_enkf_g_sqrt_gain(hc_handle *h, double *gain);
+int hc_get_enkf_g_sqrt_shift(hc_handle *h, double *shift);
 
 /* The well's record inside the window (asynchronous EnKF, Sakov, Evensen & Bertino 2010): at chosen rows before an
  * analysis row each member's y is recorded when the row is solved, and at the analysis those values join the batch as
