@@ -74,9 +74,16 @@ __host__ __device__ constexpr int ntab_lds(int slots, bool special = true)
 //   4: the table reads of the first-midpoint ET call ahead of the interior call, which reads the same four slots
 //   8: the fifteen table reads of the ET interior call's water_k > 0 block back to back in front of one wait
 //   (2, the ET interior call's wave reductions with their two chains pinned step by step, was measured and is not kept: §43)
-// -DHC_RHS_ILP=0: the code before round 9.
+// Round 10 (LAB_NOTES.md §45): reads issued early and waited for late.  An empty asm that needs the values puts the reads together
+// but also the wait in front of itself; __builtin_amdgcn_sched_barrier(0) behind the reads only keeps the scheduler from
+// moving them back down, and the waits stay at the first uses.
+//  32: the packed cell model's ten table values and the six constants of the saturated rows ahead of the model
+//  64: the assembly's five table values ahead of the top boundary
+//  (16, the column parameters in one scalar-memory round trip; 128, the lateral-flow search ahead of ET; the asm-pinned forms
+//   of 32 and 64: measured, not kept -- §45)
+// -DHC_RHS_ILP=13: the code of round 9.  -DHC_RHS_ILP=0: the code before round 9.
 #ifndef HC_RHS_ILP
-#define HC_RHS_ILP 13
+#define HC_RHS_ILP 109
 #endif
 // T_VALID = 1.0 in the slots of the D-1 midpoints, 0.0 beyond (a lane mask as data: a mask proper is an SGPR pair
 // the compiler spills and reloads with two v_readlane per use), T_INVD1 = 1/(por - wlt) (a zero denominator counts as 1)
@@ -681,18 +688,24 @@ __device__ __forceinline__ void model_cell(const ColumnDev &P, double psi, doubl
 #endif
 #define HC_V(...)                         \
     _Pragma("unroll") for (int c = 0; c < N; c++) { __VA_ARGS__; }
-template <int N, int SLOTS, bool DIET = false>
+// The table values of one cell of the model, for a caller that reads them itself (PRE below)
+struct ModelTabs {
+    double por, invm2, rdelta, logm, noisec;
+};
+template <int N, int SLOTS, bool DIET = false, bool PRE = false>
 __device__ __forceinline__ void model_cells_special(const ColumnDev &P, const double *tab, int slot0,
                                                     const double *psi, const double *rnd, double *theta, double *K,
-                                                    double *C, double *kbo, double *pfac, const int *at = nullptr)
+                                                    double *C, double *kbo, double *pfac, const int *at = nullptr,
+                                                    const ModelTabs *pre = nullptr)
 {
     // tab + slot0 addresses cell 0 of the batch; cell c is WAVE slots further -- or, with `at`, cell c sits at slot at[c]
     // (the packed batch of rhs_eval).  Each table is read where it
     // is first needed, not at the top: four more live vectors would push caller state out of the VGPR file.
+    // PRE (round 10, HC_RHS_ILP bit 32; the packed batch only): the caller has read the five values of cell c into pre[c].
     int so[N];
     HC_V(so[c] = at ? at[c] : slot0 + c * WAVE)
     double por[N], invm2[N], logm[N], noisec[N];
-    HC_V(por[c] = tab[T_POR * SLOTS + so[c]])
+    HC_V(por[c] = PRE ? pre[c].por : tab[T_POR * SLOTS + so[c]])
     double delta[N], ap[N], a[N], b[N], d[N], e[N], g[N], h[N], s[N], Lt[N], f[N], z[N], w[N], t1[N], t2[N], dk[N];
     bool sat[N], lo[N];
     int ex[N];
@@ -710,10 +723,10 @@ __device__ __forceinline__ void model_cells_special(const ColumnDev &P, const do
     HC_V(a[c] = fma(delta[c], pfac[c], P.theta_res))
     HC_V(theta[c] = sat[c] ? por[c] : a[c])
     // s = (theta - theta_res) / delta   (the next table read is issued here, a division ahead of its use)
-    HC_V(invm2[c] = tab[T_INVM2 * SLOTS + so[c]])
+    HC_V(invm2[c] = PRE ? pre[c].invm2 : tab[T_INVM2 * SLOTS + so[c]])
     HC_V(a[c] = theta[c] - P.theta_res)
     if constexpr (rdelta_table(SLOTS)) {
-        HC_V(b[c] = tab[T_RDELTA * SLOTS + so[c]])
+        HC_V(b[c] = PRE ? pre[c].rdelta : tab[T_RDELTA * SLOTS + so[c]])
     } else {
         HC_V(b[c] = __builtin_amdgcn_rcp(delta[c]))
         HC_V(d[c] = fma(-delta[c], b[c], 1.0))
@@ -766,8 +779,8 @@ __device__ __forceinline__ void model_cells_special(const ColumnDev &P, const do
     HC_V(b[c] = (h[c] - b[c]) - f[c])
     HC_V(Lt[c] = dk[c] * 6.93147180369123816490e-01 - b[c])
     // sig = sqrt_pos(Lt)
-    HC_V(logm[c] = tab[T_LOGM * SLOTS + so[c]])
-    HC_V(noisec[c] = tab[T_NOISEC * SLOTS + so[c]])
+    HC_V(logm[c] = PRE ? pre[c].logm : tab[T_LOGM * SLOTS + so[c]])
+    HC_V(noisec[c] = PRE ? pre[c].noisec : tab[T_NOISEC * SLOTS + so[c]])
     HC_V(a[c] = __builtin_amdgcn_rsq(Lt[c]))
     HC_V(g[c] = Lt[c] * a[c])
     HC_V(h[c] = 0.5 * a[c])
@@ -1159,7 +1172,25 @@ __device__ __forceinline__ void rhs_eval(const ColumnDev &P, const RowDev &R, co
                 Kc[1] = tab[T_KSAT * SLOTS + sb];
                 Kc[2] = tab[T_KSAT * SLOTS + sc];
                 Kc[3] = tab[T_KSAT * SLOTS + sd];
-                if constexpr (HC_PACK_BATCH == 2) {
+                if constexpr ((ILP & 32) != 0 && HC_PACK_BATCH == 2) {
+                    // Round 10 (HC_RHS_ILP bit 32): the model reads its tables in three groups, each waited for at its first use,
+                    // and the compiler sinks the six constants above behind the model, where unpack_row0 then waits for them
+                    // one by one.  All sixteen values asked for here, in front of a scheduling barrier that keeps the reads from
+                    // being moved back down: nine ds_read back to back, and the waits fall on the first uses inside the model.
+                    // (Pinned by an empty asm instead, as part 8 is, the wave waits for all sixteen before the model begins:
+                    // measured, no gain.)
+                    ModelTabs mt[2];
+#pragma unroll
+                    for (int c = 0; c < 2; c++) {
+                        mt[c].por = tab[T_POR * SLOTS + at[c]];
+                        mt[c].invm2 = tab[T_INVM2 * SLOTS + at[c]];
+                        mt[c].rdelta = tab[T_RDELTA * SLOTS + at[c]];
+                        mt[c].logm = tab[T_LOGM * SLOTS + at[c]];
+                        mt[c].noisec = tab[T_NOISEC * SLOTS + at[c]];
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    model_cells_special<2, SLOTS, MDIET, true>(P, tab, 0, pp, pr, pth, pK, pC, pkb, ppf, at, mt);
+                } else if constexpr (HC_PACK_BATCH == 2) {
                     model_cells_special<2, SLOTS, MDIET>(P, tab, 0, pp, pr, pth, pK, pC, pkb, ppf, at);
                 } else {
                     model_cells_special<1, SLOTS, MDIET>(P, tab, 0, pp, pr, pth, pK, pC, pkb, ppf, at);
@@ -1495,6 +1526,15 @@ __device__ __forceinline__ void rhs_eval(const ColumnDev &P, const RowDev &R, co
     }
     // ---- top boundary, richards_pde.py:414-476 (computed in lane 63's spare slot)
     HC_RSTAMP(28);
+    // Round 10 (HC_RHS_ILP bit 64): the assembly's five table values asked for here, at the head of the block the top boundary
+    // and the assembly share, and kept there by a scheduling barrier: the boundary's two dozen instructions run while the
+    // LDS answers, and the waits fall on the first uses.  (Left alone, the scheduler puts the reads behind the boundary.)
+    double as_valid[CPL];
+    if constexpr ((ILP & 64) != 0) {
+#pragma unroll
+        for (int c = 0; c < CPL; c++) as_valid[c] = tab[T_VALID * SLOTS + c * WAVE + lane];
+        __builtin_amdgcn_sched_barrier(0);
+    }
     double pL;
     if constexpr (H == 2) {
         pL = pL_pair;                                           // (only the upper half uses it)
@@ -1516,7 +1556,7 @@ __device__ __forceinline__ void rhs_eval(const ColumnDev &P, const RowDev &R, co
     HC_RSTAMP(29);
 #pragma unroll
     for (int c = 0; c < CPL; c++) {
-        const double valid = tab[T_VALID * SLOTS + c * WAVE + lane];    // 1.0 / 0.0; the cell values are finite
+        const double valid = (ILP & 64) != 0 ? as_valid[c] : tab[T_VALID * SLOTS + c * WAVE + lane];    // 1.0 / 0.0; the cell values are finite
         Cc[c] *= valid;
         fl[c] *= valid;
     }
