@@ -128,6 +128,16 @@ EXPORTS = {
     "hc_get_layer_storage_outside": ([C.c_void_p, C.POINTER(C.c_uint64)], C.c_int),
     "hc_get_layer_storage_overflow": ([C.c_void_p, C.POINTER(C.c_uint64)], C.c_int),
     "hc_get_layer_storage_layout": ([C.c_void_p, _ip, _ip, _ip], C.c_int),
+    "hc_set_conductivity_stats": ([C.c_void_p, C.c_int32, _ip], C.c_int),
+    "hc_clear_conductivity_stats": ([C.c_void_p], C.c_int),
+    "hc_get_conductivity_stats_words": ([C.c_void_p, _lp], C.c_int),
+    "hc_get_conductivity_stats": ([C.c_void_p, _lp, C.c_int64], C.c_int),
+    "hc_set_conductivity_stats_tables": ([C.c_void_p, _lp, C.c_int64], C.c_int),
+    "hc_export_conductivity_stats": ([C.c_void_p, C.c_void_p, C.c_int64], C.c_int),
+    "hc_reset_conductivity_stats": ([C.c_void_p], C.c_int),
+    "hc_get_conductivity_stats_layout": ([C.c_void_p, _ip, _ip, _ip], C.c_int),
+    "hc_get_conductivity_stats_overflow": ([C.c_void_p, C.POINTER(C.c_uint64)], C.c_int),
+    "hc_conductivity_eval": ([C.c_void_p, C.c_int64, _dp], C.c_int),
     "hc_set_theta_cov": ([C.c_void_p, C.c_int32], C.c_int),
     "hc_get_theta_cov_layout": ([C.c_void_p, _ip, _ip, _lp], C.c_int),
     "hc_get_theta_cov_words": ([C.c_void_p, _lp], C.c_int),

@@ -49,6 +49,22 @@ unknown keys, only membership of the 12 is checked):
   ``storage_hist_bins``, ``storage_hist_outside``, ``storage_quantile_levels`` and ``storage_quantile_cm``
   ``[T_out][Lv][L]`` (a sweep: a leading ``[P]`` axis on the per-row datasets), and the run ends with the line
   `` [Ensemble xN] storage: L layers on R rows``.
+* ``"Ensemble": {..., "Profiles": 48, "Conductivity": true}`` or ``"Conductivity": {"Layers_cm": [[0, 100], [100, 300]]}``:
+  the two conductivities the reference reports per saved row (``K_hrc``, ``K_bkg``, simulation.py:661-665), over the
+  members, reduced on the GPU on the profile rows (include/hydrocol.h hc_set_conductivity_stats).  Every member's K at
+  every node is the cell model's with the noise vector its row was solved with; the statistics are taken on ln K -- K is
+  log-normal by construction and spans decades down an unsaturated column -- from exact integer sums: mean and sigma of
+  ln K and the geometric mean K = exp(mean), in cm per row.  A K that is not finite and > 0 (K_hrc is exactly 0 where theta
+  sits at theta_res) is left out, which the per-node counts show.  ``Layers_cm`` (optional; at most 8 layers, which may
+  overlap; each must hold a node and less than 4096 cm) adds each layer's effective vertical conductivity
+  K_eff = n / sum 1 / K_hrc, reduced per member before the members are.  Needs ``"Profiles"`` >= 1; ``false`` is the same as
+  no key.  While it is on a launch ends on every profile row; the members' states do not depend on it.  The table is
+  summed over the ranks like the profile statistics; with a filter or an EnKF it describes the forecast.  Added to
+  ``<Output_Name>_ensemble.h5``: ``conductivity_rows``, ``conductivity_count`` ``[T_out][D][2]``, ``lnK_hrc_mean``,
+  ``lnK_hrc_std``, ``K_hrc_geomean``, ``lnK_bkg_mean``, ``lnK_bkg_std``, ``K_bkg_geomean`` ``[T_out][D]``,
+  ``conductivity_overflow`` and, with layers, ``K_eff_layers_cm``, ``K_eff_nodes`` ``[L][2]``, ``K_eff_count``,
+  ``lnK_eff_mean``, ``lnK_eff_std``, ``K_eff_geomean`` ``[T_out][L]`` (a sweep: a leading ``[P]`` axis on the per-row
+  datasets), and the run ends with the line `` [Ensemble xN] conductivity: D nodes and L layers on R rows``.
 * ``"Ensemble": {..., "Profiles": 48, "Covariance": {"Node_Stride": 4, "Sensor_Sigma": 0.02}}``: how the nodes of a
   column and the water table move together, from exact integer second moments accumulated on the GPU on the profile rows
   (include/hydrocol.h hc_set_theta_cov): theta_vol at every ``Node_Stride``-th node (default 1) quantised to 2^-20 and the
@@ -323,6 +339,7 @@ def main(params_file=None, data_file=None, seed=None, device=0, gpus=None, _sett
             distribution_settings(params["Ensemble"])      # a bad Distribution block fails before any GPU is touched
             profile_distribution_settings(params["Ensemble"])
             storage_settings(params["Ensemble"])
+            conductivity_settings(params["Ensemble"])
             period_settings(params["Ensemble"])
             uptake_settings(params["Ensemble"])
         n_gpus = multigpu.requested_gpus(gpus, params)
@@ -396,6 +413,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     dist_stride, dist_levels = distribution_settings(ens)
     theta = profile_distribution_settings(ens)
     storage = storage_settings(ens)
+    cond = conductivity_settings(ens)
     cov = covariance_settings(ens)
     periods = period_settings(ens)
     filt = filter_settings(ens, ranks.world)
@@ -415,6 +433,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     forcing = ForcingDigest(params, water_data, cols)
     record = soil_moisture_record_of(sm, cols, water_data)      # before any GPU call
     storage_ranges(storage, cols)                               # (its refusals too)
+    conductivity_layer_ranges(cond, cols)                       # (and the conductivity layers')
     if cov is not None:
         covariance_check(cov, cols.dim_d, forcing.dim_t, _profile_stride(ens), len(ens.get("Points") or [0]))
     frecord = soil_moisture_record_of(fsm, cols, water_data, "Filter")
@@ -428,7 +447,7 @@ def _run_ensemble(params, water_data, output_name, ens, device, ranks):
     plan = period_plan(periods, cols, forcing, rows)            # before any GPU call, like the storage's ranges
     uptake = uptake_settings(ens)
     run = RunSettings(dist=(dist_stride, dist_levels), theta=theta, storage=storage, cov=cov, periods=periods, plan=plan,
-                      uptake=uptake, corr=corr, pert=pert, assim=assim)
+                      conductivity=cond, uptake=uptake, corr=corr, pert=pert, assim=assim)
     if ens.get("Points"):
         return _run_sweep(params, forcing, output_name, ens, n_members, rows, device, ranks, run)
     run = replace(run, ucells=uptake_plan(uptake, [cols]))      # (so are the uptake's layers)
@@ -558,6 +577,7 @@ class RunSettings:
     theta: tuple = (0, None)                # profile_distribution_settings: (bins, levels)
     storage: Optional[tuple] = None
     cov: Optional[tuple] = None
+    conductivity: Optional[tuple] = None    # conductivity_settings: the layers (none: ())
     periods: Optional[dict] = None
     plan: Optional[tuple] = None            # period_plan
     uptake: Optional[dict] = None
@@ -574,6 +594,8 @@ class RunSettings:
         kw.update((k, v) for k, v in given.items() if v is not None)
         if self.storage is not None:
             kw.update(storage_layers_cm=self.storage[0], storage_bins=self.storage[1])
+        if self.conductivity is not None:
+            kw.update(conductivity={"layers_cm": list(self.conductivity) or None})
         if self.periods is not None:
             kw.update(period_ends=self.plan[0], period_thresholds_cm=self.periods["thresholds_cm"],
                       period_bins=self.periods["bins"])
@@ -604,12 +626,12 @@ def _placed_diag(ranks, sim, ids, P, key, counts):
     is summed over the ranks as int64 -- one collective, an int32 histogram's outside count with it."""
     import numpy as np
     from .multigpu import place_points
-    from .stepper import DIAG_TABLES, diag_layout, diag_placed, join_diag, split_diag
+    from .stepper import diag_entry, diag_layout, diag_placed, join_diag, split_diag
     if sim is not None:
         parts = sim.stepper.diag_parts(key)
     else:
         none = dict(counts, P=0)
-        parts = split_diag(key, np.zeros(diag_layout(key, none)["words"][0], dtype=DIAG_TABLES[key].dtype), none)
+        parts = split_diag(key, np.zeros(diag_layout(key, none)["words"][0], dtype=diag_entry(key).dtype), none)
     parts.update((name, place_points(parts[name], ids, P)) for name in diag_placed(key))
     return split_diag(key, ranks.allreduce_sum(join_diag(key, parts, wide=True)), dict(counts, P=P), wide=True)
 
@@ -956,6 +978,55 @@ def storage_ranges(storage, cols):
             raise ValueError(f" Ensemble: Storage.Layers_cm: {list(lay)!r} holds {(int(i1) - int(i0)) * float(cols.dz):g} cm "
                              f"of column; a layer must stay below {STORAGE_MAX_CM:g} cm.")
     return ranges
+
+
+CONDUCTIVITY_KEYS = ("Layers_cm",)
+
+
+def conductivity_settings(ens):
+    """Ensemble.Conductivity -> the layers ((top, bottom), ...) in cm, () for none; None when absent or ``false``.  Pure:
+    runs before any GPU call, and a bad value is a ValueError (message + exit status 1).  The table lives on the profile
+    rows, so the key needs ``"Profiles"`` >= 1."""
+    import math
+    from numbers import Real
+    block = ens.get("Conductivity")
+    if block is None or block is False:
+        return None
+    if block is not True and not isinstance(block, dict):
+        raise ValueError(f" Ensemble: Conductivity = {block!r} must be true or an object such as "
+                         f"{{\"Layers_cm\": [[0, 100], [100, 300]]}}.")
+    block = {} if block is True else block
+    unknown = sorted(set(block) - set(CONDUCTIVITY_KEYS))
+    if unknown:
+        raise ValueError(f" Ensemble: Conductivity has unknown keys {unknown} (known: {list(CONDUCTIVITY_KEYS)}).")
+    profiles = ens.get("Profiles", 0)
+    if (isinstance(profiles, bool) or not isinstance(profiles, Real) or not math.isfinite(profiles)
+            or profiles != int(profiles) or profiles < 1):
+        raise ValueError(f" Ensemble: Conductivity needs the profile rows: Profiles = {profiles!r} must be a row stride >= 1.")
+    if "Layers_cm" not in block:
+        return ()
+    layers = block["Layers_cm"]
+    if not isinstance(layers, (list, tuple)) or not 1 <= len(layers) <= 8:
+        raise ValueError(f" Ensemble: Conductivity.Layers_cm = {layers!r} must be a list of 1 to 8 [top, bottom] pairs in cm.")
+    for lay in layers:
+        if (not isinstance(lay, (list, tuple)) or len(lay) != 2
+                or any(isinstance(v, bool) or not isinstance(v, Real) or not math.isfinite(v) for v in lay)):
+            raise ValueError(f" Ensemble: Conductivity.Layers_cm: {lay!r} is not a [top, bottom] pair of numbers in cm.")
+        if not lay[0] < lay[1]:
+            raise ValueError(f" Ensemble: Conductivity.Layers_cm: {lay!r} must have top < bottom.")
+    return tuple((float(a), float(b)) for a, b in layers)
+
+
+def conductivity_layer_ranges(cond, cols):
+    """The node ranges of the key's layers on the column's grid (stepper.conductivity_ranges), with its refusals in the
+    CLI's words: a layer that holds no node, or one of 4096 cm or more.  None without the key."""
+    from .stepper import conductivity_ranges
+    if cond is None:
+        return None
+    try:
+        return conductivity_ranges(cols.z, cols.dz, cond)
+    except ValueError as bad:
+        raise ValueError(f" Ensemble: Conductivity.Layers_cm: {bad}.") from None
 
 
 COVARIANCE_KEYS = ("Node_Stride", "Sensor_Sigma")
@@ -1960,6 +2031,38 @@ def _reduce_storage(ranks, sim, ids, P, T, cols, stride, storage, label, keep_po
     return out, line
 
 
+def _reduce_conductivity(ranks, sim, ids, P, T, cols, stride, cond, label, keep_points):
+    """The conductivity table (``cond``: the layers) from this rank's handle ``sim`` (None: no points), its points ``ids``
+    placed in the run's [P] table and summed over the ranks like the profile table -- the overflow count with it -- then
+    mean and sigma of ln K, the geometric means and the closing line (rank 0)."""
+    import numpy as np
+    from .stepper import conductivity_stats, diag_counts, join_diag
+    if cond is None:
+        return {}, None
+    ranges = conductivity_layer_ranges(cond, cols)
+    L, D = len(ranges), cols.dim_d
+    counts = diag_counts(P, T, D, profile_stride=stride, conductivity_layers=L)
+    table = join_diag("conductivity", _placed_diag(ranks, sim, ids, P, "conductivity", counts))
+    if ranks.rank != 0:
+        return {}, None
+    stats = conductivity_stats(table, P, T, D, L, stride)
+    lead = (lambda v: v[None]) if keep_points and P == 1 else (lambda v: v)
+    out = {"conductivity_rows": np.asarray(stats["rows"], dtype=np.int64),
+           "conductivity_count": np.asarray(lead(stats["count"]), dtype=np.int64),
+           "conductivity_overflow": np.array(stats["overflow"], dtype=np.int64)}
+    names = ["lnK_hrc_mean", "lnK_hrc_std", "K_hrc_geomean", "lnK_bkg_mean", "lnK_bkg_std", "K_bkg_geomean"]
+    if L:
+        out.update(K_eff_layers_cm=np.asarray(cond, dtype=np.float64), K_eff_nodes=np.asarray(ranges, dtype=np.int64),
+                   K_eff_count=np.asarray(lead(stats["K_eff_count"]), dtype=np.int64))
+        names += ["lnK_eff_mean", "lnK_eff_std", "K_eff_geomean"]
+    out.update((name, np.asarray(lead(stats[name]), dtype=np.float64)) for name in names)
+    n = int((np.asarray(stats["count"]).reshape(-1, stats["rows"].size, D * 2) > 0).any(axis=(0, 2)).sum())
+    line = f" [{label}] conductivity: {D} nodes and {L} layers on {n} rows"
+    if stats["overflow"]:
+        line += f" ({stats['overflow']} values clamped)"
+    return out, line
+
+
 def _reduce_covariance(ranks, sim, ids, P, T, cols, stride, cov, label, keep_points):
     """The theta covariance table (``cov``: node stride, sensor sigma) from this rank's handle ``sim`` (None: no points), its
     points ``ids`` placed in the run's [P] table and summed over the ranks like the profile table -- the outside count with
@@ -2108,6 +2211,8 @@ def _reduce_diagnostics(ranks, sim, ids, cols_all, forcing, run, device, label, 
         ("theta", lambda: _reduce_theta(ranks, sim, ids, P, T, ref.dim_d, stride, run.theta, label, keep_points)),
         ("storage", lambda: _reduce_storage(ranks, sim, ids, P, T, ref, stride, run.storage, label, keep_points)),
         ("covariance", lambda: _reduce_covariance(ranks, sim, ids, P, T, ref, stride, run.cov, label, keep_points)),
+        ("conductivity", lambda: _reduce_conductivity(ranks, sim, ids, P, T, ref, stride, run.conductivity, label,
+                                                      keep_points)),
         ("periods", lambda: _reduce_periods(ranks, sim, ids, P, ref, forcing, run.periods, run.plan, label, keep_points)),
         ("uptake", lambda: _reduce_uptake(ranks, sim, ids, P, ref, run.uptake, run.ucells, run.plan, label, keep_points)))
     out, lines = {}, {}

@@ -242,6 +242,15 @@ struct hc_handle {
     int stor_range[HC_STORAGE_MAX_LAYERS][2] = {};
     AccTable<long long> stor{"words"};
     AccTable<int> shist{"entries"};
+    // ensemble conductivity profiles (hc_set_conductivity_stats): on / off, the layers of K_eff (0: none) and their node
+    // ranges; the int64 table kmom [P][n_prow][D][2][5], kcnt [P][n_prow][D][2], kmom_layer [P][n_prow][L][5], kcnt_layer
+    // [P][n_prow][L], ovf, on the profile rows and keyed like the profile table; the vector of h->fresh the last launch
+    // staged last (-1: none), which is its last row's own when that row refreshed
+    bool cond_on = false;
+    int cond_layers = 0;
+    int cond_range[HC_STORAGE_MAX_LAYERS][2] = {};
+    AccTable<long long> cond{"words"};
+    int64_t cond_fresh_last = -1;
     // ensemble covariance of theta(z) and the water table (hc_set_theta_cov): the node stride; the int64 table
     // [P][n_prow][W] + the outside word, on the profile rows and keyed like the profile table; the members' quantised rows
     // uint32 [P][chunk][E64], allocated by the first launch; HYDROCOL_COV_CHUNK_MEMBERS (0: from COV_Q_BYTES)
@@ -894,6 +903,218 @@ __global__ __launch_bounds__(PROF_TILE * PROF_WAVES) void layer_storage_kernel(
         if (ovf_sum) atomicAdd(ovf_word, (unsigned long long)ovf_sum);
         if (B > 0 && outside_sum) atomicAdd(outside_word, (unsigned long long)outside_sum);
     }
+}
+
+// ---- ensemble conductivity profiles (hc_set_conductivity_stats, include/hydrocol.h)
+// Where a profile row's noise vector comes from (the rule of include/hydrocol.h), as a kernel argument.  mode: 0 = the
+// members' base vectors in memory, 1 = the row's own vectors in memory (`vec` [N][D] in both), 2 = the Philox base (draw 0
+// times the member's scale, one product), 3 = the Philox draw of a refresh row.  A refresh row's vector (modes 1, 3) is
+// then multiplied by 0.8 once per failed attempt of the row, stats [N][6] being the row's (NULL: no failed attempt).
+struct CondNoise {
+    int mode;
+    const double *vec, *nscale;
+    const int *stats;
+    unsigned long long seed;
+    long long member_offset;
+    const long long *point_base;     // NULL with one point
+    const int *draw_idx;             // the forcing's draw indices, read at `row` (mode 3)
+    long long row;
+};
+__device__ __forceinline__ double cond_noise(const CondNoise &Z, long long m, long long point, long long members_per_point,
+                                             int i, int D)
+{
+#pragma clang fp contract(off)
+    double z;
+    if (Z.mode <= 1) {
+        z = Z.vec[(size_t)m * D + i];
+    } else {
+        const long long gid = Z.point_base ? Z.point_base[point] + (m - point * members_per_point) : Z.member_offset + m;
+        const unsigned draw = Z.mode == 3 ? (unsigned)Z.draw_idx[Z.row] : 0u;
+        z = philox_normal(Z.seed, (unsigned long long)gid, draw, (unsigned)i);
+        if (Z.mode == 2) z = z * Z.nscale[m];
+    }
+    if ((Z.mode & 1) && Z.stats) {
+        const int failed = Z.stats[(size_t)m * 6 + 5] >> 8;
+        for (int k = 0; k < failed; k++) z = z * 0.8;
+    }
+    return z;
+}
+// K_hrc and K_bkg of one node as model_nodes_kernel computes them: the same call on the same values
+__device__ __forceinline__ void cond_cell(const ColumnDev &P, int special, double psi, double por, double rdelta, double logm,
+                                          double invm2, double noisec, double z, double &K, double &kb)
+{
+    double th, C, pf;
+    if (special)
+        model_cell<true>(P, psi, por, rdelta, logm, invm2, noisec, noisec * z, th, K, C, kb, pf);
+    else
+        model_cell<false>(P, psi, por, rdelta, logm, invm2, noisec, noisec * z, th, K, C, kb, pf);
+}
+__device__ __forceinline__ bool cond_counted(double K) { return K > 0.0 && K < INFINITY; }      // (false for a NaN)
+
+// ln K_hrc and ln K_bkg of one profile row: profile_kernel's shape (grid x = 64-node tiles, y = member slices of one
+// point, z = point; lane = node, wave w reads members w, w + 4, ... of its slice, every psi, base or fresh load 64
+// contiguous doubles of one member's row).  A K that is not finite and > 0 adds to no sum: each (node, quantity) keeps its
+// own count of the members added.  The four waves' integer partials meet in LDS; wave 0 adds them to the table with int64
+// atomics (order-independent).  A skipped row (wtd_obs < 0) counts nobody unless the row is a snapshot.  `eval` (the test
+// hook): [4][N][D] = K_hrc, K_bkg, ln K_hrc, ln K_bkg of every member instead, and no table.
+__global__ __launch_bounds__(PROF_TILE * PROF_WAVES) void conductivity_kernel(
+    const StepArgs A, const double *node_tabs, int special, const double *stage, const int *wtd_obs, long long row,
+    long long prow, long long n_prow, int snapshot, long long members_per_block, const CondNoise Z, long long *kmom,
+    long long *kcnt, unsigned long long *ovf_word, double *eval)
+{
+    if (!eval && !snapshot && wtd_obs[row] < 0) return;
+    const int D = A.D;
+    const int lane = threadIdx.x % PROF_TILE, wave = threadIdx.x / PROF_TILE;
+    const int i = blockIdx.x * PROF_TILE + lane;
+    const long long point = blockIdx.z;
+    const long long end = (point + 1) * A.members_per_point;
+    const long long m0 = point * A.members_per_point + (long long)blockIdx.y * members_per_block;
+    const long long m1 = m0 + members_per_block < end ? m0 + members_per_block : end;
+    long long acc[2][HC_PROF_WORDS] = {};
+    long long cnt[2] = {};
+    unsigned ovf = 0;
+    if (i < D) {
+        const ColumnDev P = A.P[point];
+        const double *nt = node_tabs + (size_t)point * 3 * D;
+        const double por = nt[i], meank = nt[D + i], noisec = nt[2 * D + i];
+        const double mk = meank == 0.0 ? 1.0e-7 : meank;
+        const double rdelta = 1.0 / (por - P.theta_res), logm = log(mk), invm2 = 1.0 / (mk * mk);
+        const double s_lnk = ldexp(1.0, HC_PROF_SCALE_LNK);
+        const size_t total = (size_t)A.n_members * D;
+        for (long long m = m0 + wave; m < m1; m += PROF_WAVES) {
+            const double psi = stage[(size_t)m * D + i];
+            const double z = cond_noise(Z, m, point, A.members_per_point, i, D);
+            double K[2];
+            cond_cell(P, special, psi, por, rdelta, logm, invm2, noisec, z, K[0], K[1]);
+#pragma unroll
+            for (int q = 0; q < 2; q++) {
+                const double lnk = log(K[q]);
+                if (eval) {
+                    eval[q * total + (size_t)m * D + i] = K[q];
+                    eval[(2 + q) * total + (size_t)m * D + i] = lnk;
+                } else if (cond_counted(K[q])) {
+                    prof_add(acc[q], prof_quantise(lnk, s_lnk, ovf));
+                    cnt[q]++;
+                }
+            }
+        }
+    }
+    if (eval) return;                        // (the whole grid: nothing is shared)
+    constexpr int W = 2 * HC_PROF_WORDS + 2;
+    __shared__ long long part[PROF_WAVES][W][PROF_TILE];
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+#pragma unroll
+        for (int k = 0; k < HC_PROF_WORDS; k++) part[wave][q * HC_PROF_WORDS + k][lane] = acc[q][k];
+        part[wave][2 * HC_PROF_WORDS + q][lane] = cnt[q];
+    }
+    __syncthreads();
+    if (wave == 0 && i < D) {
+        const size_t node = ((size_t)point * n_prow + prow) * D + i;
+#pragma unroll
+        for (int w = 0; w < W; w++) {
+            long long sum = 0;
+#pragma unroll
+            for (int v = 0; v < PROF_WAVES; v++) sum += part[v][w][lane];
+            long long *t = w < 2 * HC_PROF_WORDS ? kmom + node * 2 * HC_PROF_WORDS + w : kcnt + node * 2 + (w - 2 * HC_PROF_WORDS);
+            if (sum) atomicAdd(reinterpret_cast<unsigned long long *>(t), (unsigned long long)sum);
+        }
+    }
+    if (ovf) atomicAdd(ovf_word, (unsigned long long)ovf);
+}
+
+// The effective vertical conductivity of one profile row per member and layer, K_eff = n / sum_i 1 / K_hrc,i (the harmonic
+// mean over the layer's n nodes): layer_storage_kernel's shape (grid y = member slices of one point, block y takes slices
+// y, y + gridDim.y, ...; a wave owns a member and its lanes stride over the nodes) and its summation order -- lane j adds
+// 1 / K_i, i mod 64 == j ascending, a node outside the layer adds 0.0, then the halving tree; nothing contracted.  The
+// reduction over depth comes before the one over members: the nodes of one member covary.  Lane l then owns layer l and adds
+// q = rint(ln K_eff 2^30) to the wave's five words; a member whose K_eff is not finite and > 0 (one node with K_hrc = 0
+// is enough) is left out of that layer, which the layer's count shows.  Integer atomics only.
+__global__ __launch_bounds__(PROF_TILE * PROF_WAVES) void conductivity_layer_kernel(
+    const StepArgs A, const double *node_tabs, int special, const double *stage, const int *wtd_obs, long long row,
+    long long prow, long long n_prow, int snapshot, long long members_per_block, const StorLayers Ly, const CondNoise Z,
+    long long *kmom_layer, long long *kcnt_layer, unsigned long long *ovf_word)
+{
+#pragma clang fp contract(off)
+    if (!snapshot && wtd_obs[row] < 0) return;
+    const int D = A.D, L = Ly.n;
+    const int lane = threadIdx.x % PROF_TILE, wave = threadIdx.x / PROF_TILE;
+    const long long point = blockIdx.z;
+    const long long end = (point + 1) * A.members_per_point;
+    const long long slice0 = point * A.members_per_point + (long long)blockIdx.y * members_per_block;
+    const long long hop = (long long)gridDim.y * members_per_block;      // to the block's next slice
+    if (slice0 >= end) return;               // (the whole block: nothing is shared yet)
+    extern __shared__ double cond_lds[];     // the point's node tables [3][D]
+    __shared__ long long part[PROF_WAVES][HC_STORAGE_MAX_LAYERS][HC_PROF_WORDS + 1];
+    __shared__ unsigned ovf_sum;
+    const ColumnDev P = A.P[point];
+    for (int k = threadIdx.x; k < 3 * D; k += PROF_TILE * PROF_WAVES) cond_lds[k] = node_tabs[(size_t)point * 3 * D + k];
+    if (threadIdx.x == 0) ovf_sum = 0;
+    __syncthreads();
+
+    long long words[HC_PROF_WORDS] = {}, counted = 0;    // lane l < L: the wave's sums of layer l
+    unsigned ovf = 0;
+    double own_n = 1.0;                      // nodes of the lane's own layer
+#pragma unroll
+    for (int l = 0; l < HC_STORAGE_MAX_LAYERS; l++) own_n = (lane == l && l < L) ? (double)(Ly.i1[l] - Ly.i0[l]) : own_n;
+    const double s_lnk = ldexp(1.0, HC_PROF_SCALE_LNK);
+    const int first = Ly.lo / PROF_TILE * PROF_TILE + lane;      // lane j takes nodes i mod 64 == j
+    for (long long m0 = slice0; m0 < end; m0 += hop) {
+        const long long m1 = m0 + members_per_block < end ? m0 + members_per_block : end;
+        for (long long m = m0 + wave; m < m1; m += PROF_WAVES) {
+            const double *psi_m = stage + (size_t)m * D;
+            double x[HC_STORAGE_MAX_LAYERS];
+#pragma unroll
+            for (int l = 0; l < HC_STORAGE_MAX_LAYERS; l++) x[l] = 0.0;
+            for (int i = first; i < Ly.hi; i += PROF_TILE) {
+                if (i < Ly.lo) continue;
+                const double por = cond_lds[i], meank = cond_lds[D + i], noisec = cond_lds[2 * D + i];
+                const double mk = meank == 0.0 ? 1.0e-7 : meank;
+                const double z = cond_noise(Z, m, point, A.members_per_point, i, D);
+                double K, kb;
+                cond_cell(P, special, psi_m[i], por, 1.0 / (por - P.theta_res), log(mk), 1.0 / (mk * mk), noisec, z, K, kb);
+                const double r = 1.0 / K;
+#pragma unroll
+                for (int l = 0; l < HC_STORAGE_MAX_LAYERS; l++)
+                    if (l < L) x[l] += (i >= Ly.i0[l] && i < Ly.i1[l]) ? r : 0.0;
+            }
+            double T = 0.0;
+#pragma unroll
+            for (int l = 0; l < HC_STORAGE_MAX_LAYERS; l++) {
+                if (l < L) {                     // (wave-uniform)
+                    double v = x[l];
+#pragma unroll
+                    for (int s = PROF_TILE / 2; s > 0; s >>= 1) v += __shfl_down(v, s, PROF_TILE);
+                    const double t = __shfl(v, 0, PROF_TILE);
+                    T = lane == l ? t : T;
+                }
+            }
+            if (lane < L) {
+                const double keff = own_n / T;
+                if (cond_counted(keff)) {
+                    prof_add(words, prof_quantise(log(keff), s_lnk, ovf));
+                    counted++;
+                }
+            }
+        }
+    }
+    if (lane < L) {
+#pragma unroll
+        for (int k = 0; k < HC_PROF_WORDS; k++) part[wave][lane][k] = words[k];
+        part[wave][lane][HC_PROF_WORDS] = counted;
+        if (ovf) atomicAdd(&ovf_sum, ovf);
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < L * (HC_PROF_WORDS + 1)) {
+        const int l = threadIdx.x / (HC_PROF_WORDS + 1), k = threadIdx.x % (HC_PROF_WORDS + 1);
+        long long sum = 0;
+#pragma unroll
+        for (int v = 0; v < PROF_WAVES; v++) sum += part[v][l][k];
+        const size_t slot = ((size_t)point * n_prow + prow) * L + l;
+        long long *t = k < HC_PROF_WORDS ? kmom_layer + slot * HC_PROF_WORDS + k : kcnt_layer + slot;
+        if (sum) atomicAdd(reinterpret_cast<unsigned long long *>(t), (unsigned long long)sum);
+    }
+    if (threadIdx.x == 0 && ovf_sum) atomicAdd(ovf_word, (unsigned long long)ovf_sum);
 }
 
 // ---- root-water uptake by depth (hc_set_root_uptake, include/hydrocol.h)
@@ -4237,6 +4458,46 @@ int ensure_stor_hist(hc_handle *h)
     return h->stor_bins > 0 ? HC_OK : fail(HC_ERR_ARG, "layer storage has no histogram (hc_set_layer_storage with n_bins = 0)");
 }
 
+// the conductivity table (hc_set_conductivity_stats): int64 kmom [P][n_prow][D][2][5], kcnt [P][n_prow][D][2], kmom_layer
+// [P][n_prow][L][5], kcnt_layer [P][n_prow][L], ovf [1]
+struct CondLayout {
+    int64_t kcnt = 0, kmom_layer = 0, kcnt_layer = 0, ovf = 0, words = 0;
+};
+CondLayout cond_layout(const hc_handle *h)
+{
+    CondLayout C;
+    const int64_t slots = (int64_t)h->n_points * prof_layout(h).n_prow, D = h->p.dim_d, L = h->cond_layers;
+    C.kcnt = slots * D * 2 * HC_PROF_WORDS;
+    C.kmom_layer = C.kcnt + slots * D * 2;
+    C.kcnt_layer = C.kmom_layer + slots * L * HC_PROF_WORDS;
+    C.ovf = C.kcnt_layer + slots * L;
+    C.words = C.ovf + 1;
+    return C;
+}
+void cond_off(hc_handle *h)
+{
+    h->cond_on = false;
+    h->cond_layers = 0;
+    h->cond.release();
+}
+int ensure_cond(hc_handle *h)
+{
+    if (!h->cond_on) return fail(HC_ERR_ARG, "the conductivity statistics are off (hc_set_conductivity_stats)");
+    if (h->prof_stride <= 0)
+        return fail(HC_ERR_ARG, "the conductivity statistics need the profile statistics (hc_set_profile_stats)");
+    if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
+    for (int l = 0; l < h->cond_layers; l++) {
+        const int i0 = h->cond_range[l][0], i1 = h->cond_range[l][1];
+        if (i0 < 0 || i0 >= i1 || i1 > h->p.dim_d)
+            return fail(HC_ERR_ARG, "conductivity statistics: layer %d is [%d, %d), not a range of nodes 0 <= i0 < i1 <= %d", l,
+                        i0, i1, (int)h->p.dim_d);
+        if ((double)(i1 - i0) * h->p.dz >= HC_STORAGE_MAX_CM)
+            return fail(HC_ERR_ARG, "conductivity statistics: layer %d is %g cm thick (less than %g cm, the layer storage's rule)",
+                        l, (double)(i1 - i0) * h->p.dz, HC_STORAGE_MAX_CM);
+    }
+    return h->cond.ensure(h->n_points, h->n_rows, h->p.dim_d, cond_layout(h).words);
+}
+
 // the period-totals tables (hc_set_period_totals): int64 pmom [P][n_period][K][5], pcnt [P][n_period], ovf [1]; with bins
 // the int32 phist_flux [P][n_period][2][B], phist_wtd [P][n_period][2][D] and the outside count (one uint64 in two
 // entries, 8-byte aligned behind an even count)
@@ -4995,6 +5256,7 @@ int hc_destroy(hc_handle *h)
     h->daylight.release(); h->refresh.release(); h->wtd_u16.release(); h->moments.release(); h->counters.release();
     h->prof.release(); h->hist.release(); h->thist.release(); h->stor.release(); h->shist.release();
     h->cov.release(); h->cov_q.release();
+    h->cond.release();
     h->pacc.release(); h->pacc_alt.release(); h->pmom.release(); h->phist.release();
     uptake_off(h);
     assimilation_off(h);
@@ -5608,6 +5870,61 @@ int launch_layer_storage(hc_handle *h, const StepArgs &A, const ProfLayout &L, c
     return HC_OK;
 }
 
+// The conductivities of the same row, from the same states and the row's noise vector as its solve left it
+// (include/hydrocol.h): a non-refresh row -- a snapshot, row 0 -- reads the members' base, a refresh row its own vector
+// damped once per failed attempt (`stats`: the row's [N][6] of the launch, NULL: none failed).  Vectors in memory when the
+// step kernel reads them there (caller noise, or a Philox run whose handle fills it), else Philox as the step kernel keys
+// it.  `eval` (hc_conductivity_eval): the members' values [4][N][D] instead of the table.
+int launch_conductivity(hc_handle *h, const StepArgs &A, const ProfLayout &L, const double *stage, int64_t row, int snapshot,
+                        const int *stats, double *eval)
+{
+    const int64_t N = h->n_members, D = h->p.dim_d;
+    const long long mpp = N / h->n_points;
+    const bool refresh = !snapshot && row > 0 && h->h_refresh[(size_t)row];
+    CondNoise Z{};
+    Z.stats = refresh ? stats : nullptr;
+    if (A.host_noise) {
+        Z.mode = refresh ? 1 : 0;
+        if (refresh && h->cond_fresh_last < 0)
+            return fail(HC_ERR_ARG, "conductivity statistics: row %lld refreshes the noise and no launch has staged its vector",
+                        (long long)row);
+        Z.vec = refresh ? h->fresh.p + (size_t)h->cond_fresh_last * N * D : h->base.p;
+    } else {
+        Z.mode = refresh ? 3 : 2;
+        Z.nscale = h->nscale.p;
+        Z.seed = h->seed;
+        Z.member_offset = h->member_offset;
+        Z.point_base = h->n_points > 1 ? h->point_base.p : nullptr;
+        Z.draw_idx = h->draw_idx.p;
+        Z.row = row;
+    }
+    const CondLayout C = eval ? CondLayout{} : cond_layout(h);     // (the hook touches no table: the row needs no slot)
+    long long *t = eval ? nullptr : h->cond.buf.p;
+    const long long prow = eval ? 0 : row / h->prof_stride;
+    const dim3 grid((unsigned)((D + PROF_TILE - 1) / PROF_TILE),
+                    (unsigned)((mpp + PROF_MEMBERS_PER_BLOCK - 1) / PROF_MEMBERS_PER_BLOCK), (unsigned)h->n_points);
+    hipLaunchKernelGGL(conductivity_kernel, grid, dim3(PROF_TILE * PROF_WAVES), 0, h->stream, A, h->node_tabs.p,
+                       (int)h->use_special(), stage, h->wtd_obs.p, (long long)row, prow, (long long)L.n_prow, snapshot,
+                       PROF_MEMBERS_PER_BLOCK, Z, t, eval ? nullptr : t + C.kcnt,
+                       reinterpret_cast<unsigned long long *>(eval ? nullptr : t + C.ovf), eval);
+    HIP_TRY(hipGetLastError());
+    if (eval || h->cond_layers <= 0) return HC_OK;
+    StorLayers Ly{};
+    Ly.n = h->cond_layers, Ly.lo = (int)D, Ly.hi = 0;
+    for (int l = 0; l < Ly.n; l++) {
+        Ly.i0[l] = h->cond_range[l][0], Ly.i1[l] = h->cond_range[l][1];
+        Ly.lo = std::min(Ly.lo, Ly.i0[l]), Ly.hi = std::max(Ly.hi, Ly.i1[l]);
+    }
+    const dim3 lgrid(1, (unsigned)std::min((mpp + STOR_MEMBERS_PER_BLOCK - 1) / STOR_MEMBERS_PER_BLOCK, h->stor_grid_y),
+                     (unsigned)h->n_points);
+    hipLaunchKernelGGL(conductivity_layer_kernel, lgrid, dim3(PROF_TILE * PROF_WAVES), (size_t)3 * D * sizeof(double),
+                       h->stream, A, h->node_tabs.p, (int)h->use_special(), stage, h->wtd_obs.p, (long long)row, prow,
+                       (long long)L.n_prow, snapshot, STOR_MEMBERS_PER_BLOCK, Ly, Z, t + C.kmom_layer, t + C.kcnt_layer,
+                       reinterpret_cast<unsigned long long *>(t + C.ovf));
+    HIP_TRY(hipGetLastError());
+    return HC_OK;
+}
+
 // the period (index into per_end) that forcing row `row` belongs to, -1: after the last end
 int64_t period_of(const hc_handle *h, int64_t row)
 {
@@ -5867,6 +6184,9 @@ Chunk plan_chunk(const hc_handle *h, const hc_step_args *a, int64_t done, bool p
         c.rows = (int)std::min<int64_t>(c.rows, cap_rows);
         c.stage_all = true;
     }
+    // the conductivity statistics (hc_set_conductivity_stats) read the base vectors and scales as the profile row left
+    // them: the launch ends on it, staged or not
+    if (prof_on && h->cond_on) c.rows = (int)std::min<int64_t>(c.rows, (c.row0 + s - 1) / s * s - c.row0 + 1);
     return c;
 }
 
@@ -5900,13 +6220,14 @@ int stage_noise(hc_handle *h, const hc_step_args *a, const Chunk &c, int64_t con
 }
 
 // the launch's staging buffers and IoArgs, the points' walk order, and the step kernel between the two timing events
-// (diag_on: the profile statistics or the period totals read the launch's diag)
-int launch_chunk(hc_handle *h, StepArgs &A, const hc_step_args *a, const Chunk &c, bool diag_on)
+// (diag_on: the profile statistics or the period totals read the launch's diag; stats_on: the conductivity statistics read
+// the failed attempts of its last row)
+int launch_chunk(hc_handle *h, StepArgs &A, const hc_step_args *a, const Chunk &c, bool diag_on, bool stats_on)
 {
     const int64_t N = h->n_members, D = h->p.dim_d;
     const size_t rows = (size_t)c.rows;
     if (h->wtd_u16.ensure(rows * N)) return HC_ERR_DEVICE;
-    if (a->stats_out && h->stats.ensure(rows * N * 6)) return HC_ERR_DEVICE;
+    if ((a->stats_out || stats_on) && h->stats.ensure(rows * N * 6)) return HC_ERR_DEVICE;
     if (a->psi_rows_out && h->psi_rows.ensure(rows * N * D)) return HC_ERR_DEVICE;
     if ((a->diag_out || diag_on) && h->diag.ensure(rows * N * 2)) return HC_ERR_DEVICE;
     if (c.stage_all && h->psi_rows.ensure(rows * N * D)) return HC_ERR_DEVICE;
@@ -5915,7 +6236,7 @@ int launch_chunk(hc_handle *h, StepArgs &A, const hc_step_args *a, const Chunk &
     A.n_rows = c.rows;
     A.spinup = a->spinup;
     h->io_host.wtd_u16 = h->wtd_u16.p;
-    h->io_host.stats = a->stats_out ? h->stats.p : nullptr;
+    h->io_host.stats = (a->stats_out || stats_on) ? h->stats.p : nullptr;
     h->io_host.psi_rows = (a->psi_rows_out || c.stage_all) ? h->psi_rows.p : nullptr;
     h->io_host.diag = (a->diag_out || diag_on) ? h->diag.p : nullptr;
     h->io_host.fmul = nullptr;
@@ -5967,6 +6288,11 @@ int accumulate(hc_handle *h, const StepArgs &A, const hc_step_args *a, const Chu
             if (int rc = launch_layer_storage(h, A, PL, stage, c.row0 + r, 0)) return rc;
         if (h->cov_stride > 0)
             if (int rc = launch_theta_cov(h, A, PL, stage, c.row0 + r, 0)) return rc;
+        if (h->cond_on) {
+            if (r != c.rows - 1) return fail(HC_ERR_DEVICE, "profile row %lld does not end its launch (internal error)",
+                                             (long long)(c.row0 + r));
+            if (int rc = launch_conductivity(h, A, PL, stage, c.row0 + r, 0, h->stats.p + (size_t)r * N * 6, nullptr)) return rc;
+        }
     }
     long long *t = h->prof.buf.p;
     hipLaunchKernelGGL(flux_stats_kernel, dim3(c.rows, h->n_points), dim3(256), 0, h->stream, h->diag.p, h->wtd_u16.p,
@@ -6797,6 +7123,8 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
     if (prof_on && h->thist_bins > 0 && (rc = ensure_thist(h))) return rc;
     if (prof_on && h->stor_layers > 0 && (rc = ensure_stor(h))) return rc;
     if (prof_on && h->cov_stride > 0 && (rc = ensure_cov(h))) return rc;
+    const bool cond_on = prof_on && h->cond_on;           // conductivity statistics (hc_set_conductivity_stats)
+    if (cond_on && (rc = ensure_cond(h))) return rc;
     const bool per_on = h->per_n > 0 && !a->spinup;       // period totals (hc_set_period_totals)
     if (per_on && (rc = ensure_period(h))) return rc;
     if (per_on && h->upt_layers > 0 && ((rc = ensure_uptake(h)) || (rc = ensure_mid_tabs(h)))) return rc;
@@ -6825,7 +7153,8 @@ int hc_step_rows(hc_handle *h, hc_step_args *a)
         const Chunk c = plan_chunk(h, a, done, prof_on);
         int n_fresh = 0;
         if ((rc = stage_noise(h, a, c, fresh_consumed, n_fresh))) return rc;
-        if ((rc = launch_chunk(h, A, a, c, prof_on || per_on))) return rc;
+        h->cond_fresh_last = n_fresh - 1;
+        if ((rc = launch_chunk(h, A, a, c, prof_on || per_on, cond_on))) return rc;
         if ((rc = accumulate(h, A, a, c, prof_on, hist_on))) return rc;
         if ((rc = copy_outputs(h, a, c, done))) return rc;
         const int64_t last = c.row0 + c.rows - 1;
@@ -6982,6 +7311,7 @@ int hc_set_profile_stats(hc_handle *h, int32_t stride)
     h->stor.release(), h->shist.release();
     h->cov_stride = 0;           // ... and the theta covariance
     h->cov.release(), h->cov_q.release();
+    cond_off(h);                 // ... and the conductivity statistics
     return stride == 0 ? HC_OK : ensure_prof(h);
 }
 
@@ -7010,6 +7340,8 @@ int hc_profile_snapshot(hc_handle *h, int64_t row)
         if (int rc2 = ensure_stor(h)) return rc2;
     if (h->cov_stride > 0)
         if (int rc2 = ensure_cov(h)) return rc2;
+    if (h->cond_on)
+        if (int rc2 = ensure_cond(h)) return rc2;
     if (int rc2 = launch_profile(h, A, prof_layout(h), h->psi.p, row, 1)) return rc2;
     if (h->thist_bins > 0)
         if (int rc2 = launch_theta_hist(h, A, prof_layout(h), h->psi.p, row, 1)) return rc2;
@@ -7017,6 +7349,8 @@ int hc_profile_snapshot(hc_handle *h, int64_t row)
         if (int rc2 = launch_layer_storage(h, A, prof_layout(h), h->psi.p, row, 1)) return rc2;
     if (h->cov_stride > 0)
         if (int rc2 = launch_theta_cov(h, A, prof_layout(h), h->psi.p, row, 1)) return rc2;
+    if (h->cond_on)
+        if (int rc2 = launch_conductivity(h, A, prof_layout(h), h->psi.p, row, 1, nullptr, nullptr)) return rc2;
     HIP_TRY(hipStreamSynchronize(h->stream));
     return HC_OK;
 }
@@ -7236,6 +7570,94 @@ int hc_get_layer_storage_layout(hc_handle *h, int32_t *n_layers, int32_t *n_bins
     *n_layers = h->stor_layers, *n_bins = h->stor_bins;
     for (int l = 0; l < HC_STORAGE_MAX_LAYERS; l++)
         ranges[2 * l] = l < h->stor_layers ? h->stor_range[l][0] : 0, ranges[2 * l + 1] = l < h->stor_layers ? h->stor_range[l][1] : 0;
+    return HC_OK;
+}
+
+int hc_set_conductivity_stats(hc_handle *h, int32_t n_layers, const int32_t *ranges)
+{
+    if (!h || (n_layers > 0 && !ranges)) return fail(HC_ERR_ARG, "hc_set_conductivity_stats: bad argument");
+    if (!h->have_forcing || !h->have_column) return fail(HC_ERR_ARG, "hc_set_column and hc_set_forcing must come first");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    cond_off(h);                 // re-created, zeroed, when on
+    if (n_layers < 0) return HC_OK;
+    if (n_layers > HC_STORAGE_MAX_LAYERS)
+        return fail(HC_ERR_ARG, "hc_set_conductivity_stats: %d layers (0 to %d; -1 = off)", (int)n_layers, HC_STORAGE_MAX_LAYERS);
+    for (int l = 0; l < n_layers; l++) h->cond_range[l][0] = ranges[2 * l], h->cond_range[l][1] = ranges[2 * l + 1];
+    h->cond_on = true, h->cond_layers = n_layers;
+    const int rc = ensure_cond(h);           // (its refusals come before anything is allocated)
+    if (rc != HC_OK) cond_off(h);            // refused: off
+    return rc;
+}
+
+int hc_clear_conductivity_stats(hc_handle *h) { return hc_set_conductivity_stats(h, -1, nullptr); }
+
+int hc_get_conductivity_stats_words(hc_handle *h, int64_t *n_words)
+{
+    if (!h || !n_words) return fail(HC_ERR_ARG, "hc_get_conductivity_stats_words: bad argument");
+    if (int rc = ensure_cond(h)) return rc;
+    *n_words = h->cond.n;
+    return HC_OK;
+}
+
+int hc_get_conductivity_stats(hc_handle *h, int64_t *table, int64_t n_words)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_get_conductivity_stats: bad argument");
+    return table_copy(h, h->cond, ensure_cond, hipMemcpyDeviceToHost, table, n_words, "hc_get_conductivity_stats");
+}
+
+int hc_set_conductivity_stats_tables(hc_handle *h, const int64_t *table, int64_t n_words)
+{
+    if (!h || !table) return fail(HC_ERR_ARG, "hc_set_conductivity_stats_tables: bad argument");
+    return table_copy(h, h->cond, ensure_cond, hipMemcpyHostToDevice, const_cast<int64_t *>(table), n_words,
+                      "hc_set_conductivity_stats_tables");
+}
+
+int hc_export_conductivity_stats(hc_handle *h, void *device_dst, int64_t n_words)
+{
+    if (!h || !device_dst) return fail(HC_ERR_ARG, "hc_export_conductivity_stats: bad argument");
+    return table_copy(h, h->cond, ensure_cond, hipMemcpyDeviceToDevice, device_dst, n_words, "hc_export_conductivity_stats");
+}
+
+int hc_reset_conductivity_stats(hc_handle *h)
+{
+    if (!h) return fail(HC_ERR_ARG, "hc_reset_conductivity_stats: bad argument");
+    return table_reset(h, h->cond, ensure_cond);
+}
+
+int hc_get_conductivity_stats_layout(hc_handle *h, int32_t *on, int32_t *n_layers, int32_t *ranges)
+{
+    if (!h || !on || !n_layers || !ranges) return fail(HC_ERR_ARG, "hc_get_conductivity_stats_layout: bad argument");
+    *on = h->cond_on ? 1 : 0, *n_layers = h->cond_layers;
+    for (int l = 0; l < HC_STORAGE_MAX_LAYERS; l++)
+        ranges[2 * l] = l < h->cond_layers ? h->cond_range[l][0] : 0, ranges[2 * l + 1] = l < h->cond_layers ? h->cond_range[l][1] : 0;
+    return HC_OK;
+}
+
+int hc_get_conductivity_stats_overflow(hc_handle *h, uint64_t *count)
+{
+    if (!h || !count) return fail(HC_ERR_ARG, "hc_get_conductivity_stats_overflow: bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = ensure_cond(h)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(count, h->cond.buf.p + cond_layout(h).ovf, 8, hipMemcpyDeviceToHost));
+    return HC_OK;
+}
+
+int hc_conductivity_eval(hc_handle *h, int64_t row, double *out)
+{
+    if (!h || !out) return fail(HC_ERR_ARG, "hc_conductivity_eval: bad argument");
+    StepArgs A;
+    int rc = fill_args(h, A);
+    if (rc) return rc;
+    if (row < 0 || row >= h->n_rows) return fail(HC_ERR_ARG, "hc_conductivity_eval: row %lld outside [0, %lld)", (long long)row,
+                                                 (long long)h->n_rows);
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t n = (size_t)h->n_members * h->p.dim_d;
+    if (h->scratch_d.ensure(4 * n)) return HC_ERR_DEVICE;
+    if ((rc = launch_conductivity(h, A, ProfLayout{}, h->psi.p, row, 0, nullptr, h->scratch_d.p))) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipMemcpy(out, h->scratch_d.p, 4 * n * 8, hipMemcpyDeviceToHost));
     return HC_OK;
 }
 

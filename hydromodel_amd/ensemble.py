@@ -10,7 +10,7 @@ import numpy as np
 
 from . import settings
 from .digest import inverse_retention
-from .stepper import DIAG_TABLES, diag_checkpoint, diag_from_checkpoint
+from .stepper import DIAG_TABLES, MORE_DIAG_TABLES, diag_checkpoint, diag_from_checkpoint
 from .stepper import (ASSIM_TABLES, EnsembleStepper, enkf_forcing_summary, enkf_noise_summary, enkf_sm_summary, enkf_summary,
                       enkf_window_summary, filter_sm_summary, filter_smoother_summary, filter_summary, filter_window_summary, layer_ranges,
                       layer_storage_distribution, moments_to_mean_std, period_totals_distribution, root_uptake_distribution,
@@ -108,6 +108,11 @@ class _Run:
     theta_cov_stride > 0 (needs profile_stride): the exact second moments of theta_vol at the nodes 0, s, 2 s, ... and of
     the water table on the profile rows (include/hydrocol.h hc_set_theta_cov): :meth:`theta_covariance` (covariance and
     correlation of theta(z), cov(theta, wtd)) and, at stride 1, :meth:`layer_std_cm` (the sigma of any layer's storage).
+    conductivity (needs profile_stride): ``True`` or ``{"layers_cm": [(top, bottom), ...]}``: ln K_hrc and ln K_bkg of every
+    member at every node of the profile rows, evaluated with the noise vector the row was solved with, and ln of the
+    layers' effective vertical conductivity n / sum 1 / K_hrc (at most 8 layers, stepper.layer_ranges), as exact integer
+    moments (include/hydrocol.h hc_set_conductivity_stats): :meth:`conductivity_stats` (mean and sigma of ln K, geometric
+    mean K in cm per row).  While it is on, a launch ends on every profile row; the members' states do not depend on it.
     period_ends: the inclusive end rows of periods (stepper.period_ends) over which every member's transpiration and
     lateral flow are summed, its shallowest and deepest water table kept and the rows counted on which the water table
     stood at or above each of ``period_thresholds_cm`` (at most 4 depths, mapped to nodes like a sensor's), reduced over
@@ -190,7 +195,7 @@ class _Run:
 
     def diag_tables_on(self):
         """The keys of stepper.DIAG_TABLES this run keeps, in the registry's order: what a checkpoint carries and installs."""
-        return settings.tables_on(DIAG_TABLES, self.on)
+        return settings.tables_on({**DIAG_TABLES, **MORE_DIAG_TABLES}, self.on)
 
 
     def enkf_noise_table(self):
@@ -332,6 +337,19 @@ class _Run:
         count (stepper.layer_storage_stats); ``table``: e.g. the sum over ranks."""
         out = self.stepper.layer_storage_stats(table)
         out["layers_cm"], out["nodes"] = self.storage_layers_cm.copy(), self.storage_ranges.copy()
+        return out
+
+    def conductivity_table(self):
+        """The raw int64 table of the conductivity statistics (stepper.conductivity_table_layout)."""
+        return self.stepper.conductivity_table()
+
+    def conductivity_stats(self, table=None):
+        """Mean and sigma of ln K_hrc and ln K_bkg and the geometric-mean K per profile row and node, [T_out][D] (a sweep:
+        [P][T_out][D]), with the members added per node and quantity and, with layers, the same of the layers' effective
+        conductivity [T_out][L] (stepper.conductivity_stats); ``table``: e.g. the sum over ranks."""
+        out = self.stepper.conductivity_stats(table)
+        if self.conductivity_ranges is not None and len(self.conductivity_ranges):
+            out["layers_cm"], out["nodes"] = np.asarray(self.conductivity["layers_cm"]).copy(), self.conductivity_ranges.copy()
         return out
 
     def storage_hist_table(self):
@@ -510,7 +528,7 @@ class EnsembleSimulation(_Run):
 
     def __init__(self, cols, forcing, n_members, seed=0, device=0, member_offset=0, psi0=None, flags=None,
                  noise="philox", spinup="shared", enkf_shard=None, filter_shard=None, **options):
-        """``options``: the run's options (settings.OPTIONS; :class:`_Run` describes them), normalised and cross-checked
+        """``options``: the run's options (settings.OPTIONS and MORE_OPTIONS; :class:`_Run` describes them), normalised and cross-checked
         before any handle exists."""
         s = settings.normalise("EnsembleSimulation", options, [cols], seed, noise=noise, member_offset=member_offset,
                                enkf_shard=enkf_shard, filter_shard=filter_shard)
@@ -748,7 +766,7 @@ class SweepSimulation(_Run):
 
     def __init__(self, cols_list, forcing, n_members, seed=0, device=0, first_point=0, flags=None, psi0=None,
                  point_ids=None, **options):
-        """``options``: the run's options (settings.OPTIONS; :class:`_Run` describes them), normalised and cross-checked
+        """``options``: the run's options (settings.OPTIONS and MORE_OPTIONS; :class:`_Run` describes them), normalised and cross-checked
         before any handle exists."""
         self.points = list(cols_list)
         self.P, self.n = len(self.points), int(n_members)

@@ -1,4 +1,4 @@
-"""The options of a run, each defined once: keyword and default (:data:`OPTIONS`), the normalised values and every refusal
+"""The options of a run, each defined once: keyword and default (:data:`OPTIONS`, :data:`MORE_OPTIONS`), the normalised values and every refusal
 before a handle exists (:func:`normalise`, :data:`REFUSALS`), the ordered walk that starts the handle (:data:`START`), which
 tables are on (:data:`TABLE_OPTION`) and the two halves of the checkpoint (:data:`SETTING_DATASETS`, :data:`RUN_STATE`,
 :data:`MEMBER_STATE`).  A new run option is one entry in each of these, plus its ``hc_set_*`` accessor on the stepper.
@@ -7,7 +7,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from .stepper import (ENKF_METHODS, enkf_window_settings,
+from .stepper import (ENKF_METHODS, conductivity_ranges, conductivity_settings, enkf_window_settings,
                       filter_smoother_config, filter_window_settings, flux_max_log2_of, forcing_coefficients,
                       forcing_perturbation_settings, layer_cells, layer_ranges, noise_correlation_breaks,
                       noise_correlation_settings, noise_correlation_tables, noise_field_settings, rejuvenation_discount,
@@ -21,6 +21,8 @@ OPTIONS = dict(
     storage_bins=0, period_ends=None, period_thresholds_cm=(), period_bins=0, period_flux_max_cm=(16.0, 4.0),
     filter_ess_floor=0.0, filter_window_offsets=(), enkf_noise_field=None, filter_rejuvenation=0.0, noise_correlation=None,
     theta_cov_stride=0, uptake_layers_cm=None, uptake_bins=0, filter_smoother=None, forcing_perturbation=None)
+# ... and the options that joined after those: taken by both constructors in the same way, through their ``**options``
+MORE_OPTIONS = dict(conductivity=None)
 
 
 # ---- 2. the refusals: (option, "needs" or "excludes", the other option, message); ``{who}`` is the class ------------------
@@ -76,9 +78,9 @@ def normalise(who, options, points, seed, lead=(), noise="philox", member_offset
     point); ``seed``: the run's, the default of the features' own; ``lead``: the leading shape of per-point tables.
     Returns the namespace; ``on`` in it says for every option whether the run has it."""
     for key in options:
-        if key not in OPTIONS:
+        if key not in OPTIONS and key not in MORE_OPTIONS:
             raise TypeError(f"{who}.__init__() got an unexpected keyword argument '{key}'")
-    o = SimpleNamespace(**dict(OPTIONS, **options))
+    o = SimpleNamespace(**{**OPTIONS, **MORE_OPTIONS, **options})
     cols, s = points[0], SimpleNamespace()
     corr = noise_correlation_settings(o.noise_correlation)
     pert = forcing_perturbation_settings(o.forcing_perturbation)
@@ -93,6 +95,10 @@ def normalise(who, options, points, seed, lead=(), noise="philox", member_offset
     s.theta_cov_stride, s.theta_hist_bins = int(o.theta_cov_stride or 0), int(o.theta_hist_bins or 0)
     s.storage_layers_cm = np.asarray(o.storage_layers_cm, dtype=np.float64).reshape(-1, 2) if _some(o.storage_layers_cm) else None
     s.storage_bins = int(o.storage_bins or 0) if s.storage_layers_cm is not None else 0
+    # the conductivity statistics' value is validated where it is read, and its one refusal is raised with it
+    s.conductivity = conductivity_settings(o.conductivity)              # None: off; {"layers_cm": [L][2] or None}
+    if s.conductivity is not None and not s.profile_stride:
+        raise ValueError(f"conductivity needs {_OWNER['profile_stride']}")
     s.filter_stride = int(o.filter_stride or 0)
     s.filter_sigma_cm = float(o.filter_sigma_cm) if s.filter_stride else None
     s.filter_seed = (int(seed) if o.filter_seed is None else int(o.filter_seed)) if s.filter_stride else None
@@ -133,6 +139,7 @@ def normalise(who, options, points, seed, lead=(), noise="philox", member_offset
         raise ValueError("period_flux_max_cm is (transpiration, lateral flow)")
     # what needs the columns
     s.storage_ranges = layer_ranges(cols.z, s.storage_layers_cm) if on["storage_layers_cm"] else None
+    s.conductivity_ranges = conductivity_ranges(cols.z, cols.dz, s.conductivity["layers_cm"]) if on["conductivity"] else None
     s.period_threshold_nodes = sensor_nodes(cols.z, s.period_thresholds_cm) if periods else None
     s._period_flux_log2 = [flux_max_log2_of(v) for v in s.period_flux_max_cm] if s.period_bins else (0, 0)
     s.uptake_cells = layer_cells(cols.z, s.uptake_layers_cm) if on["uptake_layers_cm"] else None
@@ -173,6 +180,7 @@ START = (
     ("theta_hist_bins", lambda st, s: st.set_theta_hist(s.theta_hist_bins)),
     ("storage_layers_cm", lambda st, s: st.set_layer_storage(s.storage_ranges, s.storage_bins)),
     ("theta_cov_stride", lambda st, s: st.set_theta_cov(s.theta_cov_stride)),
+    ("conductivity", lambda st, s: st.set_conductivity_stats(s.conductivity_ranges)),
     ("profile_stride", lambda st, s: st.profile_snapshot(0)),             # psi[0], theta_vol[0]: the state before any solve
     ("wtd_hist_stride", lambda st, s: st.set_wtd_hist(s.wtd_hist_stride)),
     ("filter_stride", lambda st, s: st.set_filter(s.filter_stride, s.filter_sigma_cm, s.filter_seed)),
@@ -213,7 +221,8 @@ TABLE_OPTION = {"filter": "filter_stride", "filter_sm": "filter_soil_moisture", 
                 "filter_rejuvenation": "filter_rejuvenation", "filter_window": "filter_window_offsets", "enkf": "enkf_stride",
                 "enkf_sm": "enkf_soil_moisture", "enkf_window": "enkf_window_offsets", "enkf_noise": "enkf_noise_field",
                 "profile": "profile_stride", "theta_hist": "theta_hist_bins", "storage": "storage_layers_cm",
-                "storage_hist": "storage_bins", "theta_cov": "theta_cov_stride", "period": "period_ends",
+                "storage_hist": "storage_bins", "theta_cov": "theta_cov_stride", "conductivity": "conductivity",
+                "period": "period_ends",
                 "period_acc": "period_ends", "period_hist": "period_bins", "uptake": "uptake_layers_cm",
                 "uptake_acc": "uptake_layers_cm", "uptake_hist": "uptake_bins", "wtd_hist": "wtd_hist_stride"}
 
@@ -249,6 +258,7 @@ def _tuple(cast, dtype):
 _I64, _U64, _F64 = (((lambda v, d=d: np.array(v, dtype=d)), cast)
                     for d, cast in ((np.int64, int), (np.uint64, int), (np.float64, float)))
 _PAIRS, _ROWS, _DEPTHS = (np.asarray, _array(np.float64, -1, 2)), (np.asarray, _array(np.int64)), (np.asarray, _array(np.float64))
+_LAYERS = (lambda v: np.zeros((0, 2)) if v is None else np.asarray(v, dtype=np.float64)), _array(np.float64, -1, 2)   # (none: [0][2])
 _OFFSETS, _FLUX_MAX = _tuple(int, np.int64), _tuple(np.float64, np.float64)
 _NODES, _TABLE = (_array(np.int32), None), (lambda a: np.asarray(a, dtype=np.float64), None)
 _METHOD = (lambda m: np.array(ENKF_METHODS.index(m), dtype=np.int64)), (lambda a: ENKF_METHODS[int(a)])
@@ -266,6 +276,7 @@ SETTING_DATASETS = (
     ("wtd_hist_stride", "wtd_hist_stride", _I64),
     ("storage_layers_cm", "storage_layers_cm", _PAIRS),
     ("storage_layers_cm", "storage_bins", _I64),
+    ("conductivity", "conductivity_layers_cm", _LAYERS, "conductivity.layers_cm"),
     ("period_ends", "period_ends", _ROWS),
     ("period_ends", "period_thresholds_cm", _DEPTHS),
     ("period_ends", "period_bins", _I64),

@@ -43,6 +43,8 @@ class EnsembleStepper:
     forcing): with P points the N members are point-major, point k owns members [k N/P, (k+1) N/P), and one launch
     advances all of them; ``moments()`` then returns [P][3][T]."""
 
+    conductivity, conductivity_ranges = False, np.zeros((0, 2), dtype=np.int32)      # (off until set_conductivity_stats)
+
     def __init__(self, cols, forcing, n_members, device=0, flags=None, profile_stride=0):
         self.lib = L.load()
         points = list(cols) if isinstance(cols, (list, tuple)) else [cols]
@@ -80,6 +82,7 @@ class EnsembleStepper:
         self.theta_hist_bins = 0
         self.storage_ranges, self.storage_bins = np.zeros((0, 2), dtype=np.int32), 0
         self.theta_cov_stride = 0
+        self.conductivity, self.conductivity_ranges = False, np.zeros((0, 2), dtype=np.int32)
         self.period_ends, self.period_threshold_nodes = np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int32)
         self.period_bins, self.period_flux_max_log2 = 0, (0, 0)
         self.uptake_cells, self.uptake_bins = np.zeros((0, 2), dtype=np.int32), 0
@@ -385,12 +388,13 @@ class EnsembleStepper:
         """The counts the handle's diagnostic tables are shaped by (:func:`diag_counts`), from its settings."""
         return diag_counts(self.P, self.T, self.D, self.N, self.profile_stride, self.wtd_hist_stride, self.theta_hist_bins,
                            len(self.storage_ranges), self.storage_bins, self.theta_cov_stride, len(self.period_ends),
-                           len(self.period_threshold_nodes), self.period_bins, len(self.uptake_cells), self.uptake_bins)
+                           len(self.period_threshold_nodes), self.period_bins, len(self.uptake_cells), self.uptake_bins,
+                           len(self.conductivity_ranges))
 
     def diag_words(self, key):
         """Elements of the raw table ``key`` of DIAG_TABLES, trailing words included: the library's count where it has
         an entry point for it, else the layout's."""
-        name = f"hc_get_{DIAG_TABLES[key].stem}_words"
+        name = f"hc_get_{diag_entry(key).stem}_words"
         if name not in L.EXPORTS:
             return diag_layout(key, self.diag_counts())["words"][0]
         n = C.c_int64()
@@ -400,7 +404,7 @@ class EnsembleStepper:
     def diag_raw(self, key):
         """The raw device table ``key`` as the library hands it out: flat, the entry's element type, its trailing words
         (overflow, outside count) included."""
-        e = DIAG_TABLES[key]
+        e = diag_entry(key)
         t = np.zeros(self.diag_words(key), dtype=e.dtype)
         L.check(getattr(self.lib, "hc_get_" + e.stem)(self.h, _diag_ptr(t), t.size))
         return t
@@ -409,7 +413,7 @@ class EnsembleStepper:
         """Install a raw table (a checkpoint's, a sum over handles): flattened, made contiguous and checked here for every
         entry -- int32 counts in [0, 2^31 - 1], the outside count in its carrier's range; the library checks the size."""
         t = pack_diag(key, *unpack_diag(key, raw))
-        L.check(getattr(self.lib, DIAG_TABLES[key].set)(self.h, _diag_ptr(t), t.size))
+        L.check(getattr(self.lib, diag_entry(key).set)(self.h, _diag_ptr(t), t.size))
 
     def diag_parts(self, key):
         """{part: shaped array} of the table ``key`` (:func:`split_diag`), with ``outside`` as an integer where the entry
@@ -422,14 +426,14 @@ class EnsembleStepper:
 
     def export_diag(self, key, device_ptr):
         """Copy the raw table device-to-device to ``device_ptr`` (``diag_words(key)`` elements on this handle's device)."""
-        name = "hc_export_" + DIAG_TABLES[key].stem
+        name = "hc_export_" + diag_entry(key).stem
         if name not in L.EXPORTS:
             raise ValueError(f"the table {key!r} has no device-to-device export")
         L.check(getattr(self.lib, name)(self.h, C.c_void_p(int(device_ptr)), self.diag_words(key)))
 
     def reset_diag(self, key):
         """Zero the table ``key`` -- and, where its family has one reset for all its tables, the others with it."""
-        L.check(getattr(self.lib, DIAG_TABLES[key].reset)(self.h))
+        L.check(getattr(self.lib, diag_entry(key).reset)(self.h))
 
     def _diag_counter(self, name):
         """A trailing count read on its own (``hc_get_*_outside`` / ``hc_get_*_overflow``)."""
@@ -449,6 +453,7 @@ class EnsembleStepper:
         self.theta_hist_bins = 0          # keyed to the profile rows: the library turned it off
         self.storage_ranges, self.storage_bins = np.zeros((0, 2), dtype=np.int32), 0      # ... and the layer storage
         self.theta_cov_stride = 0         # ... and the theta covariance
+        self.conductivity, self.conductivity_ranges = False, np.zeros((0, 2), dtype=np.int32)     # ... and the conductivities
 
     def profile_snapshot(self, row=0):
         L.check(self.lib.hc_profile_snapshot(self.h, int(row)))
@@ -567,6 +572,57 @@ class EnsembleStepper:
         """Mean / sigma [cm] of ``layer_storage_table()`` (or of ``table``, e.g. summed over ranks): :func:`layer_storage_stats`."""
         t = self.layer_storage_table() if table is None else table
         return layer_storage_stats(t, self.P, self.T, len(self.storage_ranges), self.profile_stride)
+
+    # -- ensemble conductivity profiles (include/hydrocol.h hc_set_conductivity_stats) ----------------------------------------
+    def set_conductivity_stats(self, ranges=(), on=True):
+        """Accumulate ln K_hrc and ln K_bkg of every member at every node of the profile rows -- with the noise vector each
+        row was solved with -- and, with node ranges ``ranges`` [L][2] = (i0, i1) (see :func:`layer_ranges`), ln of the
+        layers' effective vertical conductivity: exact integer moments.  ``on=False`` = off.  Needs
+        :meth:`set_profile_stats`, and comes before :meth:`profile_snapshot` for row 0 to be counted.  While it is on, a
+        launch ends on every profile row."""
+        r = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(-1, 2))
+        if r.size and (r.min() < -INT32_MAX or r.max() > INT32_MAX):
+            raise ValueError("layer ranges must be node indices")
+        r32 = np.ascontiguousarray(r, dtype=np.int32)
+        self.conductivity, self.conductivity_ranges = False, np.zeros((0, 2), dtype=np.int32)
+        if not on:
+            L.check(self.lib.hc_clear_conductivity_stats(self.h))
+            return
+        L.check(self.lib.hc_set_conductivity_stats(self.h, r32.shape[0], L.iptr(r32)))
+        self.conductivity, self.conductivity_ranges = True, r32
+
+    def conductivity_layout(self):
+        """(on, ranges [L][2]) as the library holds them."""
+        on, n = C.c_int32(), C.c_int32()
+        r = np.zeros((STORAGE_MAX_LAYERS, 2), dtype=np.int32)
+        L.check(self.lib.hc_get_conductivity_stats_layout(self.h, C.byref(on), C.byref(n), L.iptr(r)))
+        return bool(on.value), r[:n.value].copy()
+
+    def conductivity_table(self):
+        """The raw int64 table (layout: :func:`conductivity_table_layout`)."""
+        return self.diag_raw("conductivity")
+
+    def set_conductivity_table(self, table):
+        self.set_diag_raw("conductivity", table)
+
+    def reset_conductivity_stats(self):
+        self.reset_diag("conductivity")
+
+    def conductivity_overflow(self):
+        return self._diag_counter("hc_get_conductivity_stats_overflow")
+
+    def conductivity_stats(self, table=None):
+        """Mean / sigma of ln K and the geometric-mean K of ``conductivity_table()`` (or of ``table``, e.g. summed over
+        ranks): :func:`conductivity_stats`."""
+        t = self.conductivity_table() if table is None else table
+        return conductivity_stats(t, self.P, self.T, self.D, len(self.conductivity_ranges), self.profile_stride)
+
+    def conductivity_eval(self, row):
+        """[4][N][D] = K_hrc, K_bkg, ln K_hrc, ln K_bkg of the members' current states with the noise vector of forcing row
+        ``row`` and no failed attempt (``hc_conductivity_eval``: the table's own device code)."""
+        out = np.zeros((4, self.N, self.D))
+        L.check(self.lib.hc_conductivity_eval(self.h, int(row), L.dptr(out)))
+        return out
 
     # -- ensemble covariance of theta(z) and the water table (include/hydrocol.h hc_set_theta_cov) -------------------------
     def set_theta_cov(self, node_stride):
@@ -1929,6 +1985,157 @@ def layer_storage_stats(table, P, T, L, stride):
     if P == 1:
         out = {k: v[0] for k, v in out.items()}
     out["rows"] = np.arange(parts["scnt"].shape[1], dtype=np.int64) * int(stride)
+    out["overflow"] = int(parts["ovf"][0])
+    return out
+
+
+# ---- conductivity profiles (include/hydrocol.h hc_set_conductivity_stats) ------------------------------------------------
+PROF_SCALE_LNK = 30
+
+
+def conductivity_settings(value):
+    """The run option ``conductivity`` normalised: None / False -> None (off); True -> {"layers_cm": None} (the node
+    statistics alone); {"layers_cm": [(top, bottom), ...]} -> the same with the layers as float64 [L][2].  TypeError for any
+    other value, ValueError for an unknown key or layers that are not 1 to 8 (top, bottom) pairs with top < bottom."""
+    if value is None or value is False:
+        return None
+    if value is True:
+        return {"layers_cm": None}
+    if not isinstance(value, dict):
+        raise TypeError(f"conductivity is None, True or {{'layers_cm': [(top, bottom), ...]}}, got {value!r}")
+    unknown = sorted(set(value) - {"layers_cm"})
+    if unknown:
+        raise ValueError(f"conductivity has unknown keys {unknown} (known: ['layers_cm'])")
+    layers = value.get("layers_cm")
+    if layers is None or np.size(layers) == 0:
+        return {"layers_cm": None}
+    layers = np.asarray(layers, dtype=np.float64)
+    if layers.ndim != 2 or layers.shape[1] != 2 or not 1 <= layers.shape[0] <= STORAGE_MAX_LAYERS:
+        raise ValueError(f"conductivity.layers_cm holds 1 to {STORAGE_MAX_LAYERS} (top, bottom) pairs in cm, got {value['layers_cm']!r}")
+    if not np.all(np.isfinite(layers)) or np.any(layers[:, 0] >= layers[:, 1]):
+        raise ValueError(f"a conductivity layer is (top, bottom) in cm with top < bottom, got {layers.tolist()!r}")
+    return {"layers_cm": layers}
+
+
+def conductivity_ranges(z, dz, layers_cm):
+    """Node ranges [L][2] of the conductivity layers on the grid ``z`` (:func:`layer_ranges`; no layers: [0][2]), with the
+    layer storage's refusals: a layer that holds no node, and one of 4096 cm or more."""
+    if layers_cm is None or np.size(layers_cm) == 0:
+        return np.zeros((0, 2), dtype=np.int32)
+    ranges = layer_ranges(z, layers_cm)
+    for lay, (i0, i1) in zip(np.asarray(layers_cm, dtype=np.float64).reshape(-1, 2), ranges):
+        if (int(i1) - int(i0)) * float(dz) >= STORAGE_MAX_CM:
+            raise ValueError(f"conductivity layer {lay.tolist()!r} holds {(int(i1) - int(i0)) * float(dz):g} cm of column; "
+                             f"a layer must stay below {STORAGE_MAX_CM:g} cm")
+    return ranges
+
+
+def conductivity_noise_of(base, fresh, refresh, failed, scale=None):
+    """The noise vector the conductivity statistics use on each row of a batch: the vector the row's solve left behind
+    (include/hydrocol.h).  One member: ``refresh`` / ``failed`` [n] are the rows' refresh flag and count of failed
+    attempts, ``fresh`` [n_refresh][D] the vectors of the batch's refresh rows.  Returns [n][D].
+
+    Vectors in memory (``scale`` None): ``base`` [D] is the base vector when the batch starts; a row that does not
+    refresh damps it in place, x0.8 per failed attempt, for itself and every later row, and a refresh row damps its own
+    copy only -- :func:`hydromodel_amd.simulation.rows_noise`.  In-kernel Philox (``scale``: the member's scale when the
+    batch starts): ``base`` is the draw-0 normals xi; a row that does not refresh multiplies the SCALE by 0.8 per failed
+    attempt and its vector is xi * scale, one product, as the step kernel rebuilds it; a refresh row as above."""
+    from .simulation import rows_noise
+    base = np.array(base, dtype=np.float64).reshape(-1)
+    refresh, failed = np.asarray(refresh, dtype=bool).reshape(-1), np.asarray(failed, dtype=np.int64).reshape(-1)
+    fresh = np.asarray(fresh, dtype=np.float64).reshape(-1, base.size)
+    if scale is None:
+        return rows_noise(base, fresh, refresh, failed)
+    out, s, k = np.empty((refresh.size, base.size)), np.float64(scale), 0
+    for i, (is_fresh, n_fail) in enumerate(zip(refresh, failed)):
+        if is_fresh:
+            out[i] = rows_noise(base, fresh[k:k + 1], [True], [n_fail])[0]
+            k += 1
+        else:
+            for _ in range(int(n_fail)):
+                s = s * 0.8
+            out[i] = base * s
+    return out
+
+
+def conductivity_layer_of(k_hrc, ranges):
+    """The device's per-member reduction restated: ``k_hrc`` [N][D] -> K_eff [N][L] = n / sum 1 / K_hrc,i over the layer's n
+    nodes, the sum in :func:`layer_storage_of`'s order on 1 / K.  Equal to the device's bits."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        R, _ = layer_storage_of(1.0 / np.asarray(k_hrc, dtype=np.float64), ranges, 1.0)
+        n = np.diff(_check_ranges(ranges, np.shape(k_hrc)[-1]), axis=1).reshape(-1).astype(np.float64)
+        return n / R
+
+
+def conductivity_table_layout(P, T, D, L, stride):
+    """{part: (offset, shape)} of the int64 table: kmom [P][T_out][D][2][5] (K_hrc, K_bkg), kcnt [P][T_out][D][2],
+    kmom_layer [P][T_out][L][5], kcnt_layer [P][T_out][L], ovf [1]."""
+    return diag_layout("conductivity", diag_counts(P, T, D, profile_stride=stride, conductivity_layers=L))
+
+
+def split_conductivity_table(table, P, T, D, L, stride):
+    """Views of the parts of a flat table (see :func:`conductivity_table_layout`)."""
+    return split_diag("conductivity", table, diag_counts(P, T, D, profile_stride=stride, conductivity_layers=L))
+
+
+def _lnk_words(lnk):
+    """(words [..., 5] summed over axis 0, members added [...], values clamped) of ln K [N][...]: a value that is not
+    finite adds nothing."""
+    lnk = np.asarray(lnk, dtype=np.float64)
+    ok = np.isfinite(lnk)
+    q, bad = profile_quantise(np.where(ok, lnk, 0.0), PROF_SCALE_LNK)
+    words = np.where(ok[..., None], profile_words_of(q), 0)
+    return words.astype(object).sum(axis=0).astype(np.int64), ok.sum(axis=0).astype(np.int64), bad
+
+
+def conductivity_tables_of(lnk_rows, ranges=(), counted=None, k_rows=None):
+    """The table of one point from the members' ln K on every profile row, ``lnk_rows`` [R][2][N][D] (ln K_hrc, ln K_bkg;
+    ``counted`` [R] bool: rows that count their members, default all), with the layers ``ranges`` from ``k_rows`` [R][N][D]
+    = K_hrc (default: exp of its ln): the flat int64 table (kmom [1][R][D][2][5], kcnt, kmom_layer, kcnt_layer, ovf).  A
+    value that is not finite (K = 0, NaN, infinite) is left out and, through the count, visible; one beyond 2^10 is clamped
+    and counted in ovf.  The device's table, bit for bit."""
+    lnk = np.asarray(lnk_rows, dtype=np.float64)
+    R, _, N, D = lnk.shape
+    r = _check_ranges(ranges, D) if np.size(ranges) else np.zeros((0, 2), dtype=np.int64)
+    counted = np.ones(R, dtype=bool) if counted is None else np.asarray(counted, dtype=bool)
+    kmom, kcnt = np.zeros((1, R, D, 2, PROF_WORDS), dtype=np.int64), np.zeros((1, R, D, 2), dtype=np.int64)
+    lmom, lcnt, ovf = np.zeros((1, R, len(r), PROF_WORDS), dtype=np.int64), np.zeros((1, R, len(r)), dtype=np.int64), 0
+    for j in range(R):
+        if not counted[j]:
+            continue
+        for q in range(2):
+            kmom[0, j, :, q], kcnt[0, j, :, q], bad = _lnk_words(lnk[j, q])
+            ovf += bad
+        if len(r):
+            with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+                keff = conductivity_layer_of(np.exp(lnk[j, 0]) if k_rows is None else np.asarray(k_rows)[j], r)
+                ln = np.log(np.where((keff > 0.0) & (keff < np.inf), keff, np.nan))
+            lmom[0, j], lcnt[0, j], bad = _lnk_words(ln)
+            ovf += bad
+    return np.concatenate([kmom.reshape(-1), kcnt.reshape(-1), lmom.reshape(-1), lcnt.reshape(-1),
+                           np.array([ovf], dtype=np.int64)])
+
+
+def conductivity_stats(table, P, T, D, L, stride):
+    """Mean and population sigma of ln K from a table, as :func:`profile_tables_to_stats` forms them (exact integers,
+    rounded once), and the geometric mean K = exp(mean): ``lnK_{hrc,bkg}_{mean,std}``, ``K_{hrc,bkg}_geomean`` [P][T_out][D]
+    (NaN where no member was added), ``count`` [P][T_out][D][2]; with layers ``lnK_eff_{mean,std}``, ``K_eff_geomean``
+    and ``K_eff_count`` [P][T_out][L]; ``rows`` [T_out] and ``overflow``.  The leading [P] axis is dropped for a single
+    point."""
+    parts = split_conductivity_table(table, P, T, D, L, stride)
+    out = {}
+    moments = [(name, parts["kcnt"][..., q], parts["kmom"][..., q, :]) for q, name in enumerate(("hrc", "bkg"))]
+    moments += [("eff", parts["kcnt_layer"], parts["kmom_layer"])] if L else []
+    for name, count, words in moments:
+        mean, std = limbs_to_mean_std(count, words, PROF_SCALE_LNK)
+        with np.errstate(over="ignore"):                     # (a clamped ln K of 2^10: the geometric mean is inf)
+            out[f"lnK_{name}_mean"], out[f"lnK_{name}_std"], out[f"K_{name}_geomean"] = mean, std, np.exp(mean)
+    out["count"] = parts["kcnt"].copy()
+    if L:
+        out["K_eff_count"] = parts["kcnt_layer"].copy()
+    if P == 1:
+        out = {k: v[0] for k, v in out.items()}
+    out["rows"] = np.arange(parts["kcnt"].shape[1], dtype=np.int64) * int(stride)
     out["overflow"] = int(parts["ovf"][0])
     return out
 
@@ -3597,10 +3804,30 @@ DIAG_TABLES = {
     "wtd_hist": _T("wtd_hist", "hc_set_wtd_hist_table", "hc_reset_wtd_hist", np.int32,
                    (("hist", ("P", "hslots", "D")),), None, ("wtd_hist", None, True)),
 }
+# ... and the tables that joined the registry after those twelve: the same record, found by the same functions
+# (:func:`diag_entry`), carried by the same path.  They stand apart because "every entry of DIAG_TABLES on at once" is the
+# configuration the registry's fixtures and recorded call sequences were written for.
+MORE_DIAG_TABLES = {
+    "conductivity": _T("conductivity_stats", "hc_set_conductivity_stats_tables", "hc_reset_conductivity_stats", np.int64,
+                       (("kmom", _PR + ("D", 2, PROF_WORDS)), ("kcnt", _PR + ("D", 2)),
+                        ("kmom_layer", _PR + ("conductivity_layers", PROF_WORDS)),
+                        ("kcnt_layer", _PR + ("conductivity_layers",)), ("ovf", (1,))), None,
+                       ("conductivity_table", None, False)),
+}
+
+
+def diag_entry(key):
+    """The record of the diagnostic table ``key``, of DIAG_TABLES or MORE_DIAG_TABLES (KeyError: no such table)."""
+    return DIAG_TABLES[key] if key in DIAG_TABLES else MORE_DIAG_TABLES[key]
+
+
+def diag_keys():
+    """Every diagnostic table's key, in the order a checkpoint installs them."""
+    return tuple(DIAG_TABLES) + tuple(MORE_DIAG_TABLES)
 
 
 def diag_counts(P, T=1, D=1, N=0, profile_stride=0, wtd_hist_stride=0, theta_bins=0, storage_layers=0, storage_bins=0,
-                cov_stride=0, periods=0, thresholds=0, period_bins=0, uptake_layers=0, uptake_bins=0):
+                cov_stride=0, periods=0, thresholds=0, period_bins=0, uptake_layers=0, uptake_bins=0, conductivity_layers=0):
     """The counts the shapes of DIAG_TABLES are written in, from a run's settings (a rank without points: ``P`` = 0).
     Needs no handle; a family that is off has no rows."""
     T, D = int(T), int(D)
@@ -3610,22 +3837,26 @@ def diag_counts(P, T=1, D=1, N=0, profile_stride=0, wtd_hist_stride=0, theta_bin
             "theta_bins": int(theta_bins), "storage_layers": int(storage_layers), "storage_bins": int(storage_bins),
             "cov_words": theta_cov_shape(D, cov_stride)[2] if cov_stride else 0,
             "periods": int(periods), "K": 4 + int(thresholds), "period_bins": int(period_bins),
-            "uptake_layers": int(uptake_layers), "uptake_layers+1": int(uptake_layers) + 1, "uptake_bins": int(uptake_bins)}
+            "uptake_layers": int(uptake_layers), "uptake_layers+1": int(uptake_layers) + 1, "uptake_bins": int(uptake_bins),
+            **({"conductivity_layers": int(conductivity_layers)} if conductivity_layers else {})}
+
+
+_COUNTS_ABSENT = {"conductivity_layers": 0}       # the counts :func:`diag_counts` leaves out when their option is off
 
 
 def diag_placed(key):
     """The names of the table's parts that lead with [P]: what a sum over ranks places at the points."""
-    return tuple(name for name, shape in DIAG_TABLES[key].parts if shape[0] == "P")
+    return tuple(name for name, shape in diag_entry(key).parts if shape[0] == "P")
 
 
 def diag_layout(key, counts, wide=False):
     """{part: (offset, shape)} of the raw table ``key`` at ``counts`` (:func:`diag_counts`), and ``words``: its elements
     with the entries the outside count takes.  ``wide``: the table as it is summed over ranks -- every element int64,
     the outside count in one word whatever its carrier.  The one place the tables' offsets come from."""
-    e = DIAG_TABLES[key]
+    e = diag_entry(key)
     out, off = {}, 0
     for name, shape in e.parts:
-        shape = tuple(counts[n] if isinstance(n, str) else n for n in shape)
+        shape = tuple((counts[n] if n in counts else _COUNTS_ABSENT[n]) if isinstance(n, str) else n for n in shape)
         out[name] = (off, shape)
         off += int(np.prod(shape))
     out["words"] = (off + (0 if e.outside is None else 1 if wide or e.outside == "int64" else 2), ())
@@ -3636,7 +3867,7 @@ def pack_diag(key, body, outside=0, wide=False):
     """The flat raw table of its parts' elements ``body`` and its outside count, of the entry's element type (``wide``:
     as :func:`diag_layout`).  Every table that is installed passes here: int32 counts outside [0, 2^31 - 1] and an
     outside count outside its carrier's range are refused."""
-    e = DIAG_TABLES[key]
+    e = diag_entry(key)
     body = np.asarray(body).reshape(-1)
     dtype = np.int64 if wide else e.dtype
     if dtype == np.int32 and body.size and (body.min() < 0 or body.max() > INT32_MAX):
@@ -3652,7 +3883,7 @@ def pack_diag(key, body, outside=0, wide=False):
 
 def unpack_diag(key, raw, wide=False):
     """(the parts' elements, the outside count or None) of a flat raw table: the inverse of :func:`pack_diag`."""
-    e = DIAG_TABLES[key]
+    e = diag_entry(key)
     t = np.asarray(raw).reshape(-1)
     if e.outside is None:
         return t, None
@@ -3664,9 +3895,9 @@ def unpack_diag(key, raw, wide=False):
 def _diag_views(key, body, counts):
     """{part: shaped view} of the parts' elements ``body`` (a table without its outside count)."""
     lay = diag_layout(key, counts, wide=True)
-    t, n = np.asarray(body).reshape(-1), lay.pop("words")[0] - (DIAG_TABLES[key].outside is not None)
+    t, n = np.asarray(body).reshape(-1), lay.pop("words")[0] - (diag_entry(key).outside is not None)
     if t.size != n:
-        what = "words" if DIAG_TABLES[key].dtype == np.int64 else "entries"
+        what = "words" if diag_entry(key).dtype == np.int64 else "entries"
         raise ValueError(f"{key} table of {t.size} {what}, the layout has {n}")
     return {k: t[o:o + int(np.prod(sh))].reshape(sh) for k, (o, sh) in lay.items()}
 
@@ -3674,7 +3905,7 @@ def _diag_views(key, body, counts):
 def split_diag(key, raw, counts, wide=False):
     """{part: shaped view} of the raw table ``key`` (the overflow word of an int64 table is its part ``ovf`` [1]), with
     ``outside`` as an integer where the entry carries one; ``wide`` as :func:`diag_layout`."""
-    body, outside = unpack_diag(key, np.asarray(raw, dtype=np.int64 if wide else DIAG_TABLES[key].dtype), wide)
+    body, outside = unpack_diag(key, np.asarray(raw, dtype=np.int64 if wide else diag_entry(key).dtype), wide)
     out = _diag_views(key, body, counts)
     if outside is not None:
         out["outside"] = outside
@@ -3683,13 +3914,13 @@ def split_diag(key, raw, counts, wide=False):
 
 def join_diag(key, parts, wide=False):
     """The flat raw table of :func:`split_diag`'s parts (``outside`` defaults to 0): its inverse."""
-    body = np.concatenate([np.asarray(parts[name]).reshape(-1) for name, _ in DIAG_TABLES[key].parts])
+    body = np.concatenate([np.asarray(parts[name]).reshape(-1) for name, _ in diag_entry(key).parts])
     return pack_diag(key, body, parts.get("outside", 0), wide)
 
 
 def diag_checkpoint(key, raw, counts):
     """{dataset: array} a checkpoint holds of the raw table ``key`` (the entry's ``stored``)."""
-    e = DIAG_TABLES[key]
+    e = diag_entry(key)
     name, outside_name, shaped = e.stored
     body, outside = unpack_diag(key, raw)
     out = {name: body.reshape(diag_layout(key, counts)[e.parts[0][0]][1]) if shaped else body}
@@ -3700,7 +3931,7 @@ def diag_checkpoint(key, raw, counts):
 
 def diag_from_checkpoint(key, data):
     """The raw table ``key`` of a checkpoint's datasets ``data``: the inverse of :func:`diag_checkpoint`."""
-    name, outside_name, _ = DIAG_TABLES[key].stored
+    name, outside_name, _ = diag_entry(key).stored
     return pack_diag(key, data[name], 0 if outside_name is None else int(data[outside_name]))
 
 

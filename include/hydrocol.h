@@ -537,6 +537,66 @@ int hc_get_layer_storage_outside(hc_handle *h, uint64_t *count);    /* 0 without
 int hc_get_layer_storage_overflow(hc_handle *h, uint64_t *count);   /* the ovf slot */
 int hc_get_layer_storage_layout(hc_handle *h, int32_t *n_layers, int32_t *n_bins, int32_t *ranges);
 
+/* Ensemble conductivity profiles: the mean and spread over the members of ln K_hrc and ln K_bkg at every node, and of the
+ * effective vertical conductivity of depth layers, on the profile rows (hc_set_profile_stats, which must be on), as exact
+ * integer moments.  K is the one quantity the model's noise enters, log-normal by construction and many decades wide down
+ * an unsaturated column: the statistics are taken on ln K (exp of the mean is the geometric mean).
+ *   rows: the profile rows, at the profile stride (slot j <-> row j stride, n_prow slots); row 0 is counted by
+ *   hc_profile_snapshot, the others by hc_step_rows from the states the profile statistics read, before the row's
+ *   assimilation (the forecast, as every table).  Skipped rows (wtd_obs < 0) count no members; spin-up solves accumulate nothing.
+ *   noise: nu, the row's noise vector as its solve left it --
+ *     a row that does not refresh the noise (and row 0): the member's base vector as it stands after the row, every
+ *       earlier x0.8 in it;
+ *     a refresh row: the row's own vector (draw index draw_idx[row], or the caller's / staged fresh vector), multiplied by
+ *       0.8 once per failed attempt of that row, successive IEEE products.
+ *     Vectors in memory (hc_set_noise_host; a Philox run whose handle fills caller noise: particle filter, the EnKF's
+ *     noise field, a noise correlation): base_noise after the launch, or the launch's last staged fresh vector.  In-kernel
+ *     Philox: philox_normal(seed, gid, 0, i) * nscale[m], one product, for the base; philox_normal(seed, gid,
+ *     draw_idx[row], i) for a refresh row; gid as the step kernel keys it (member_offset + m, or the point's base + j).
+ *     So that the base and the scale are the row's own, a launch ends on every profile row while the table is on, staged
+ *     rows included, and the launch stages the per-row stats (the failed attempts of its last row).  No state depends on
+ *     where a launch ends; the step kernels are the same.
+ *   per member m and node i: (K_hrc, K_bkg) = the cell model at (psi_{m,i}, rnd = nu_i), the values hc_model_nodes returns
+ *   on the same inputs, bit for bit; q = rint(log(K) * 2^HC_PROF_SCALE_LNK), |q| <= HC_PROF_Q_MAX (|ln K| < 2^10 covers
+ *   every finite positive double).  A K that is not finite or not > 0 (K_hrc is exactly 0 where theta is clamped to
+ *   theta_res) adds to no sum: every (node, quantity) has its own count.
+ *   per member and layer l (node range [i0, i1), n = i1 - i0; at most HC_STORAGE_MAX_LAYERS, which may overlap):
+ *   K_eff = (double)n / R, R = sum_{i0 <= i < i1} 1 / K_hrc,i -- the harmonic mean, which governs flow across layers --
+ *   in the layer storage's order: x_j, j = 0..63, starts at 0.0 and adds 1 / K_hrc,i of the layer's nodes with i mod 64 == j
+ *   in ascending i; then x_j += x_{j+32} (j < 32), ..., x_0 += x_1; R = x_0.  fp64, nothing contracted.  q =
+ *   rint(log(K_eff) * 2^HC_PROF_SCALE_LNK); a member whose K_eff is not finite and > 0 is left out of that layer.  The sum
+ *   over depth comes before the one over members: the nodes of one member covary.
+ *   table (int64), in this order:
+ *     kmom       [P][n_prow][D][2][5]  0 = K_hrc, 1 = K_bkg: word 0 sum q, words 1..4 the 20-bit limbs of sum q^2
+ *     kcnt       [P][n_prow][D][2]     members added
+ *     kmom_layer [P][n_prow][L][5]     ln K_eff, as kmom
+ *     kcnt_layer [P][n_prow][L]        members added
+ *     ovf        [1]                   values clamped by the quantisation
+ *     P n_prow (12 D + 6 L) + 1 words.  Integer adds only across members: the same bits at any launch length, member split,
+ *     point order and number of handles / ranks summed.
+ * hc_set_conductivity_stats: n_layers -1 = off (default; hc_clear_conductivity_stats does the same), 0 = the node
+ * statistics alone, otherwise with `ranges` [L][2] = (i0, i1); (re)creates the table zeroed.  HC_ERR_ARG (and off) when the
+ * profile statistics are off, for more than HC_STORAGE_MAX_LAYERS layers, an empty or out-of-column range or a layer of
+ * HC_STORAGE_MAX_CM or more.  hc_set_profile_stats turns it off.  Like the profile table it is re-created, zeroed, when the
+ * points, the forcing rows or the depth change.  get / set / export take the table's size in words
+ * (hc_get_conductivity_stats_words) and fail on any other.  hc_get_conductivity_stats_layout returns on / off, L and the
+ * ranges ([HC_STORAGE_MAX_LAYERS][2], the first L filled).  With the table off nothing is launched or staged for it and no
+ * launch is cut.
+ * hc_conductivity_eval (test hook): out [4][N][D] = K_hrc, K_bkg, ln K_hrc, ln K_bkg of the members' current states with
+ * the noise of forcing row `row` by the rule above and no failed attempt, from the same device code.  A refresh row of
+ * vectors in memory reads the vector the last launch staged last. */
+#define HC_PROF_SCALE_LNK 30        /* ln K: 2^-30 steps, |ln K| < 2^10                                             */
+int hc_set_conductivity_stats(hc_handle *h, int32_t n_layers, const int32_t *ranges);
+int hc_clear_conductivity_stats(hc_handle *h);
+int hc_get_conductivity_stats_words(hc_handle *h, int64_t *n_words);
+int hc_get_conductivity_stats(hc_handle *h, int64_t *table, int64_t n_words);
+int hc_set_conductivity_stats_tables(hc_handle *h, const int64_t *table, int64_t n_words);   /* checkpoint / resume, rank sums */
+int hc_export_conductivity_stats(hc_handle *h, void *device_dst, int64_t n_words);           /* as hc_export_profile_stats */
+int hc_reset_conductivity_stats(hc_handle *h);
+int hc_get_conductivity_stats_layout(hc_handle *h, int32_t *on, int32_t *n_layers, int32_t *ranges);
+int hc_get_conductivity_stats_overflow(hc_handle *h, uint64_t *count);   /* the ovf slot */
+int hc_conductivity_eval(hc_handle *h, int64_t row, double *out);
+
 /* Ensemble covariance of theta(z) and the water table: the second moments of the members' theta_vol at the selected nodes
  * and of their water-table index, on the profile rows (hc_set_profile_stats, which must be on), in exact integers.  Every
  * other table is a marginal; this one says how the nodes of a column move together: the ensemble's vertical correlation,
